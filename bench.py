@@ -44,6 +44,8 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 F_IN, F_HID = 32, 64
+DUMP_MAX_ROWS = 1 << 19      # --dump-outputs: 10 float64 + 3 float32 fields = 92 B a row, 48 MiB at most
+DUMP_SEED = 0xA1A2D0           # --dump-outputs: the hash that picks the sample
 
 
 def parse():
@@ -80,7 +82,13 @@ def parse():
                                                                    "GPU's power management has left its idle state when the clock starts (0 = none)")
     ap.add_argument("--profile-mode", action="store_true", help="only warm-up + the timed steps (no diagnostic passes, no CPU baseline): "
                                                                   "the run rocprofv3 wraps, so its per-kernel averages are those of the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the edge rows the last timed window produced (what sg_window_read hands a caller) as "
+                         "DIR/<field>.npy, one file per sg_edge_out field, ordered by (from_ref, to_ref); float64, the fp32 fields float32; "
+                         f"above {DUMP_MAX_ROWS} rows a fixed seeded sample of that many edges.  One GPU, one window in flight")
     a = ap.parse_args()
+    if a.dump_outputs and (a.gpus > 1 or a.windows > 1):
+        ap.error("--dump-outputs reads the last timed window back with sg_window_read: --gpus 1 and --windows 1 only")
     if a.config == 0:
         a.config = 3 if a.gpus == 1 else 4
     dflt = {2: (200, 20), 3: (30, 5), 4: (30, 5), 5: (10, 2)}[a.config]
@@ -237,6 +245,37 @@ def measured_copy_gbs(torch):
     return 2.0 * n * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9
 
 
+def dump_outputs(path, rows, obips):
+    """--dump-outputs: the rows of one window as DIR/<field>.npy, ordered by (from_ref, to_ref) so that two builds compare row for
+    row whatever order they emit.  A window of more than DUMP_MAX_ROWS edges is sampled by a seeded hash of (from_ref, to_ref): the
+    same edges are picked whenever they are there.  edges_in_window.npy holds the full row count; outbound_ips.npy, the table that
+    resolves OBIP refs, only when the window has raw outbound destinations (an HTTP-only replay has none: no empty file is written).
+    Returns what was written."""
+    os.makedirs(path, exist_ok=True)
+    key = (rows["from_ref"].astype(np.uint64) << np.uint64(32)) | rows["to_ref"].astype(np.uint64)
+    n_all = len(rows)
+    if n_all > DUMP_MAX_ROWS:
+        with np.errstate(over="ignore"):                     # murmur3 fmix64 (a bijection: one row per edge, so no ties)
+            h = key ^ np.uint64(DUMP_SEED)
+            h = (h ^ (h >> np.uint64(33))) * np.uint64(0xFF51AFD7ED558CCD)
+            h = (h ^ (h >> np.uint64(33))) * np.uint64(0xC4CEB9FE1A85EC53)
+            h ^= h >> np.uint64(33)
+        pick = np.argpartition(h, DUMP_MAX_ROWS - 1)[:DUMP_MAX_ROWS]
+        rows, key = rows[pick], key[pick]
+    rows = rows[np.argsort(key, kind="stable")]
+    files = {}
+    for name in rows.dtype.names:
+        col = rows[name]
+        files[name] = col.astype(np.float32 if col.dtype.kind == "f" else np.float64)    # (the u64 sums of a window stay far below 2^53)
+    if len(obips):
+        files["outbound_ips"] = np.asarray(obips).astype(np.float64)
+    files["edges_in_window"] = np.array([n_all], dtype=np.float64)
+    for name, arr in files.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr)
+    return {"dir": path, "rows": int(len(rows)), "edges_in_window": n_all, "sampled": n_all > DUMP_MAX_ROWS,
+            "bytes": int(sum(arr.nbytes for arr in files.values())), "files": sorted(f"{k}.npy" for k in files)}
+
+
 def algorithmic_bytes(Ev, E, N, L):
     """compulsory traffic per window and kernel group."""
     b = {"K1a": 32.0 * Ev, "K1b": 32.0 * E, "K2": 16.0 * E + 4.0 * (N + 1), "K3-in": 32.0 * E, "K3-feat": 4.0 * F_IN * N,
@@ -287,6 +326,8 @@ def main():
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(a)                                        # `python bench.py --gpus N`: one rank per GPU under torch.distributed.run
     force_sharded = os.environ.get("SG_FORCE_SHARDED") == "1"      # exercise the multi-GPU code path at world = 1
+    if a.dump_outputs and (world > 1 or force_sharded):
+        sys.exit("bench.py: --dump-outputs reads the last timed window back from the unsharded engine: not with the sharded path")
     # the contract is ONE line on stdout: libraries that print there (RCCL writes its version banner to stdout when the
     # first communicator is created) are sent to stderr for the duration of the run
     sys.stdout.flush()
@@ -517,6 +558,8 @@ def bench_single(a, device):
         k1b_s = k1b_s.reshape(nwin_s, per_w).sum(axis=1)
         k1b = (float(k1b_s.mean()), nwin_s)
     st_timed = g.stats()
+    # --dump-outputs: the rows of the last timed window, read back before anything below ingests again (they stay in place until then)
+    dumped = dump_outputs(a.dump_outputs, g.window_read(), g.outbound_ips()) if a.dump_outputs else None
     # SURVEY 8(d) run protocol (median + min): a separate untimed pass — the event pair around every window costs a few microseconds, so it
     # stays out of the region `value` is taken from — of at least 100 windows (or the driver's --steps if that is more), one record each
     # from in front of the window's pass A to behind its score kernel
@@ -653,6 +696,8 @@ def bench_single(a, device):
                          "windows_read": {"warm": int(st.windows_warm), "cold": int(st.windows_cold)}},
         "value_basis": "mean over the timed steps (wall clock around K back-to-back windows, one window in flight); per_step holds median / min of single windows",
     }
+    if dumped:
+        res["dump_outputs"] = dumped
     # diagnostic (never `value`): the same steps with several windows in flight inside one engine — the
     # latency-bound close of window w overlaps the ingest of window w+1; no timing events in this pass
     # (the diagnostic passes below must never cost the line above: an exception in one of them is reported in its object)

@@ -1,5 +1,5 @@
-"""Regenerates tests/golden/*.json from the reference checkout (run in the build container only;
-/root/reference does not exist on the GPU box, the committed JSON files travel instead).
+"""Regenerates tests/golden/*.json from a checkout of the reference repository (the tests read only the committed
+JSON files; none of them needs the reference).  usage: make_fixtures.py REFERENCE_CHECKOUT
 
   pg_kat.json   the Parse / Bind payloads and expected strings of aggregator/pg_test.go
                 (TestPostgresParseWithKnownStmt :10-92, TestPostgresParseWithUnknownStmt :94-119).
@@ -9,12 +9,16 @@
                 testconfig/config1.json) restated as one tiny trace with the outputs the reference's
                 code produces for it, derived by hand from aggregator/data.go:508-531, 827-870,
                 1208-1249, 1740-1767 and datastore/backend.go:824-839.
+  datastore_iface.json  the methods of the reference's datastore.DataStore interface
+                (datastore/datastore.go:3-20) as name -> [parameter types, result]: what the Go
+                decorator must implement (tests/test_go_surface.py).
 """
 import json
 import os
 import re
+import sys
 
-REF = "/root/reference"
+REF = ""
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -76,7 +80,22 @@ def main():
     }
     json.dump(sim, open(os.path.join(HERE, "sim_kat.json"), "w"), indent=1)
     print("wrote pg_kat.json, sim_kat.json")
+    datastore_fixture()
     hpack_fixture()
+
+
+def datastore_fixture():
+    """datastore_iface.json: the DataStore interface's method set, parsed from the Go source (comments dropped)."""
+    src = open(os.path.join(REF, "datastore/datastore.go"), encoding="utf-8").read()
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+    body = re.search(r"type\s+DataStore\s+interface\s*\{(.*?)\n\}", src, flags=re.S).group(1)
+    methods = {}
+    for m in re.finditer(r"^\s*(\w+)\(([^)]*)\)\s*(\w+)\s*$", body, flags=re.M):
+        methods[m.group(1)] = [[p.split()[-1] for p in m.group(2).split(",") if p.strip()], m.group(3)]
+    assert len(methods) == 11, sorted(methods)
+    json.dump({"source": "datastore/datastore.go:3-20 @ 2024_10_08", "methods": methods},
+              open(os.path.join(HERE, "datastore_iface.json"), "w"), indent=1)
+    print("wrote datastore_iface.json")
 
 
 def hpack_fixture(independent_copy: str = ""):
@@ -100,4 +119,7 @@ def hpack_fixture(independent_copy: str = ""):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        sys.exit("usage: make_fixtures.py REFERENCE_CHECKOUT")
+    REF = sys.argv[1]
     main()

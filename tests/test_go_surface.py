@@ -2,12 +2,14 @@
 textually: every C.sg_* function, C.SG_* constant and every field of sg_config / sg_stats / sg_event / sg_edge_out it touches
 must exist in include/servicegraph.h, with the argument count the header declares; and on the other side it must implement the
 eleven methods of the reference's datastore.DataStore (datastore/datastore.go:3-20) with the reference's signatures."""
+import json
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GO = os.path.join(ROOT, "go", "servicegraph", "graphds.go")
 HDR = os.path.join(ROOT, "include", "servicegraph.h")
+IFACE = os.path.join(ROOT, "tests", "golden", "datastore_iface.json")
 
 # datastore/datastore.go:3-20, method name -> (parameter types, result)
 DATASTORE = {
@@ -133,12 +135,6 @@ def test_go_decorator_implements_the_reference_datastore_interface():
     for name, (params, res) in DATASTORE.items():
         assert name in have, f"GraphDS lacks {name} (datastore/datastore.go:3-20)"
         assert have[name] == (params, res), f"{name}: {have[name]} != {(params, res)}"
-    # where the reference is at hand (this container, not the GPU box), the table above is checked against its source
-    ref = "/root/reference/datastore/datastore.go"
-    if os.path.exists(ref):
-        src = _strip_go(open(ref).read())
-        body = re.search(r"type\s+DataStore\s+interface\s*\{(.*?)\n\}", src, flags=re.S).group(1)
-        found = {}
-        for m in re.finditer(r"^\s*(\w+)\(([^)]*)\)\s*(\w+)\s*$", body, flags=re.M):
-            found[m.group(1)] = ([p.split()[-1] for p in m.group(2).split(",") if p.strip()], m.group(3))
-        assert found == DATASTORE
+    # the table above against the interface as the reference's source declares it (tests/golden/make_fixtures.py)
+    found = {k: (v[0], v[1]) for k, v in json.load(open(IFACE))["methods"].items()}
+    assert found == DATASTORE
