@@ -22,29 +22,21 @@
 #include <dlfcn.h>
 
 #include "join_host.hpp"
+#include "sg_plan.hpp"
 #include "sg_kernels.h"
 #include "shard_seq.hpp"
 
 namespace {
 
-constexpr int kStageSlots = 32;                      // staging ring slots at most (sg_engine::n_stage of them are allocated)
+using sgplan::kStageSlots;
+using sgplan::kLdsBytes;
 constexpr int kUpdSlots = 4;             // pinned ring for join-table word updates
 constexpr u32 kUpdCap = 1u << 15;         // (word offset, value) pairs per slot = sgjoin::Table::max_dirty
-constexpr size_t kLdsBytes = 160 * 1024;  // per workgroup on gfx950
 
 struct TimingRec { hipEvent_t a, b; int kernel; };
 
-u32 next_pow2(u64 v) { u64 p = 1; while (p < v) p <<= 1; return (u32)p; }
-
-// Tuning knobs (SG_NP, SG_HT, SG_K1A, SG_ABLATE, ...: tools/k1_sweep.py, the A/B tests of alternative kernel paths) are read from the
-// environment by the DEVELOPMENT build only (-DSG_DEV_KNOBS -> lib/libservicegraph_dev.so); the shipped library reads none.
-inline const char* sg_knob(const char* name) {
-#ifdef SG_DEV_KNOBS
-    return std::getenv(name);
-#else
-    (void)name; return nullptr;
-#endif
-}
+using sgplan::next_pow2;
+using sgplan::grid_for;
 
 }  // namespace
 
@@ -54,11 +46,13 @@ struct sg_engine {
     std::string err;
     hipStream_t stream = nullptr;
     Dev d{};
+    // every sizing decision (sg_plan.hpp): made at create from the config and the development build's overrides; pass A's
+    // geometry follows the join tables (sync_tables)
+    sgplan::Overrides ov;
+    sgplan::Plan plan;
+    sgplan::PassA pa;
     std::vector<void*> allocs;
-    // SG_ARENA=1: everything below 32 MiB is carved out of 256 MiB chunks instead of one hipMalloc per array (a test of whether the
-    // small arrays' page-table entries cost the window close — a chain of small latency-bound kernels — anything: measured on one box,
-    // 507.7 / 508.3 us per C3 window with the chunks, 505.1 / 504.8 without; off).
-    char* arena_base = nullptr; size_t arena_left = 0; bool arena_on = false;
+    char* arena_base = nullptr; size_t arena_left = 0;         // SG_ARENA (Plan::arena_on): the chunk small arrays are carved from
 
     // join tables: the two reference maps + the word image the kernels read (join_host.hpp).  Mutations are logged as
     // changed words and shipped to the device copy in stream order (k_join_apply); a whole-image upload only when
@@ -74,13 +68,11 @@ struct sg_engine {
     std::vector<hipStream_t> k1_streams;             // streams with K1 launches since the last table modification
     hipStream_t tab_stream = nullptr;
     u32 n_known = 0;
-    // pass-A launch geometry, follows the table state
-    bool l2_in_lds = false, l2_u16 = false, k1a_team = false; u32 k1a_ct = 2048, k1a_nsub = 2, k1a_teams = 2, k1a_nt = 1024;
     // staging ring for sg_ingest()
     sg_event* h_stage[kStageSlots] = {}; sg_event* d_stage[kStageSlots] = {}; hipEvent_t stage_ev[kStageSlots] = {};
-    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr; int n_copy = 1, copy_rr = 0; hipEvent_t copied_ev[kStageSlots] = {};   // H2D copies run on their own stream: batch i + 1 is copied while K1a folds batch i
+    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr; int copy_rr = 0; hipEvent_t copied_ev[kStageSlots] = {};   // H2D copies run on their own stream: batch i + 1 is copied while K1a folds batch i
     std::vector<std::pair<const char*, size_t>> registered;          // caller memory page-locked by sg_host_register
-    int stage_next = 0, n_stage = 16;
+    int stage_next = 0;
     sg_edge_out* h_rows = nullptr; sg_edge_out* h_rows_old = nullptr; size_t h_rows_cap = 0;              // page-locked destination of sg_flush_window_view (grown on demand)
     bool stage_busy[kStageSlots] = {};                                   // a feeder thread is copying into the slot (outside the lock)
     int pending_copies = 0; std::condition_variable cv;                 // window closes wait for the copies that began before them
@@ -93,19 +85,12 @@ struct sg_engine {
     u64 first_kernel = 0, first_user = 0;
     float* d_W = nullptr; bool have_w = false;
     u32 n_labels_decl = 0;
-    u32 ecap = 0, obcap = 0, ob_list_cap = 0;
     u32* d_ob_list = nullptr; u32* d_ob_n = nullptr;
 
     sg_stats st{};
     u64 h_ctr[C_COUNT] = {};
     std::vector<u32> last_obips;
     bool closed = false;       // window_close has run; rows readable after score
-    bool use_mfma = true;
-    int k1_grid = 0;
-    size_t k1a_lds = 0, k1b_lds = 0, k3in_lds = 0;
-    u32 k3_ranges = 1, k3_slices = 8;
-    u32 k1b_threads = 512, k1b_u = 4, k1b_cus = 256;
-    bool k1b_pack = false;                    // narrow pass B: count + duration sum of a record in one 64-bit LDS add (sn x nwg < 2^16)
     // warm windows (sg_device.h): the host only decides whether a window TRIES the warm path; whether it may is decided on the device
     bool warm_on = true;                      // sg_set_warm
     u32 cold_streak = 0;                      // consecutive windows whose warm attempt met an unknown key (C_COLD = 2), by the device's note
@@ -153,7 +138,7 @@ int dev_alloc(sg_engine* e, T** p, size_t n, int fill = 0) {
     void* q = nullptr;
     size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
     constexpr size_t kArenaMax = (size_t)32 << 20, kArenaChunk = (size_t)256 << 20, kArenaAlign = 4096;
-    if (e->arena_on && bytes < kArenaMax) {
+    if (e->plan.arena_on && bytes < kArenaMax) {
         const size_t need = (bytes + kArenaAlign - 1) & ~(kArenaAlign - 1);
         if (need > e->arena_left) {                                  // (what is left of the previous chunk stays unused)
             void* c = nullptr;
@@ -189,78 +174,14 @@ struct Timed {
 // ---- join tables on the device: the host mirror's changes since the last launch, in stream order ------------------
 // (processPod / processSvc analogue: aggregator/persist.go:55-71, 114-130 — one map write there, a few words here)
 
-// pass-A geometry that follows the table state: does level 2 fit LDS beside the edge cache (and, narrow path, the tile)?
-// Returns false when no legal geometry exists (the caller fails the call with a message instead of launching a kernel that
-// asks for more than a CU's LDS).
-bool k1a_geometry(sg_engine* e) {
-    const Dev& d = e->d;
-    const size_t l1b = (size_t)e->jt.l1_entries * 8, l2b = (size_t)e->jt.blocks_bytes();
-    const size_t stage_max = (size_t)K1A_NJ * K1A_THREADS * 16;    // what the prologue can stage: six 16-byte words per lane
-    e->l2_in_lds = false;
-    if (d.narrow) {
-        // cache | 6 counters per partition | statistics | tile | join tables.  Level 2 is staged as u16 entries
-        // (half the bytes) when every node id fits 14 bits.
-        e->l2_u16 = e->cfg.max_known_nodes <= 16384 && !sg_knob("SG_L2_U32");
-        const size_t l2lds = e->l2_u16 ? l2b / 2 : l2b;
-        if (const char* v = sg_knob("SG_NSUB")) { const int x = std::atoi(v); if (x == 1 || x == 2) e->k1a_nsub = (u32)x; }
-        // round 4: two teams per workgroup (k1a_team_partition) when their two tiles and counter sets fit beside a cache of 256 slots or
-        // more; SG_K1A=tile keeps the one-team kernel (k1a_tile_partition), SG_K1A=team takes the two-team kernel whenever it fits at all
-        const char* kv = sg_knob("SG_K1A");
-        const bool want_tile = kv && !std::strcmp(kv, "tile"), force_team = kv && !std::strcmp(kv, "team");
-        const size_t fixed_tile = (size_t)d.np * 24 + 64 + (size_t)K1T_TS(e->k1a_nsub) * 8 + l1b;
-        // the two-team kernel is instantiated for 256 / 512 / 1024 partitions, 1024 threads (two teams of eight waves, one group of four events
-        // per thread and tile: round 6; round 4 ran two groups at 768 threads) and a join blob its prologue can stage; everything else keeps
-        // the one-team kernel
-        const int teams = 2, nt = 1024;
-        const size_t lds_cap = kLdsBytes;
-        // (what the team kernel's prologue can stage: six 16-byte words per lane of its threads.  Level 1 always goes through it, level 2
-        // only when it is staged — an engine whose level 2 stays in global memory needs room for level 1 alone)
-        const size_t stage_team = (size_t)K1A_NJ * nt * 16;
-        // (endpoint spaces beyond 15 bits — a shard of BASELINE config 5: 18 — leave no room for the partition number in a parked record: the
-        // kernel's 16-lanes-per-run copy-out takes over, the workgroup has the 1024 threads it is written for since round 6)
-        const bool team_ok = (d.np == 256 || d.np == 512 || d.np == 1024) && (size_t)d.np * d.nwg * d.punits * 8 < ((size_t)1 << 31) && l1b <= stage_team;
-        e->k1a_teams = (u32)teams; e->k1a_nt = (u32)nt;
-        const size_t fixed_team = K1M_LDS_FIXED(d.np, teams, nt) + l1b;
-        auto pick = [&](size_t fixed, u32 ct_min, size_t stage_cap, u32& ct, bool& in_lds) {
-            ct = 0; in_lds = false;
-            // (the cache flattens the hottest keys; beyond 1024 slots it costs more aggregates than it saves records)
-            for (u32 c : {1024u, 512u, 256u, 128u}) if (c >= ct_min && (size_t)c * 40 + fixed + l2lds <= lds_cap && l1b + l2b <= stage_cap) { in_lds = true; ct = c; break; }
-            if (!ct) for (u32 c : {1024u, 512u, 256u, 128u, 64u}) if (c >= ct_min && (size_t)c * 40 + fixed <= lds_cap) { ct = c; break; }
-        };
-        u32 ct = 0; bool in_lds = false;
-        e->k1a_team = false;
-        if (!want_tile && team_ok) { pick(fixed_team, force_team ? 64u : 256u, stage_team, ct, in_lds); e->k1a_team = ct != 0; }
-        if (!ct) pick(fixed_tile, 64u, stage_max, ct, in_lds);
-        const size_t fixed = e->k1a_team ? fixed_team : fixed_tile;
-        e->l2_in_lds = in_lds;
-        if (sg_knob("SG_L2_GLOBAL")) e->l2_in_lds = false;
-        if (const char* v = sg_knob("SG_CT")) { const u32 x = (u32)std::strtoul(v, nullptr, 0); if (x >= 64 && x <= 2048 && (x & (x - 1)) == 0 && (size_t)x * 40 + fixed + (e->l2_in_lds ? l2lds : 0) <= lds_cap) ct = x; }
-        if (!ct || l1b > stage_max) return false;
-        e->k1a_ct = ct;
-        e->k1a_lds = (size_t)ct * 40 + fixed + (e->l2_in_lds ? l2lds : 0);
-        return true;
-    }
-    const size_t fixed = (size_t)d.np * 4 + 64 + l1b;
-    const size_t slot = d.hist ? 72 : 40;                    // cache slot: key + 4 accumulators (+ 16 x u16 bins)
-    u32 ct = 0;
-    for (u32 c : {2048u, 1024u, 512u}) if ((size_t)c * slot + fixed + l2b <= kLdsBytes && l1b + l2b <= stage_max) { e->l2_in_lds = true; ct = c; break; }
-    // level 2 stays in global memory: the largest cache that fits beside the counters and level 1
-    if (!ct) for (u32 c : {2048u, 1024u, 512u, 256u, 128u, 64u}) if ((size_t)c * slot + fixed <= kLdsBytes) { ct = c; break; }
-    if (const char* v = sg_knob("SG_CT")) { const u32 x = (u32)std::strtoul(v, nullptr, 0); if (x >= 64 && x <= 2048 && (x & (x - 1)) == 0 && (size_t)x * slot + fixed + (e->l2_in_lds ? l2b : 0) <= kLdsBytes) ct = x; }
-    if (sg_knob("SG_L2_GLOBAL")) e->l2_in_lds = false;
-    if (!ct || l1b > stage_max) return false;
-    e->k1a_ct = ct;
-    e->k1a_lds = (size_t)ct * slot + fixed + (e->l2_in_lds ? l2b : 0);
-    return true;
-}
 // the sizes a K1 launch needs from the table state (pointers are fixed at create)
 void join_view(const sg_engine* e, Dev& d) {
     d.jl1mask = e->jt.l1_entries - 1;
     d.jl2_words = e->jt.use_blocks ? e->jt.blocks_used * 256u : 0u;
     d.ck_n = e->jt.ck_n;
-    d.jstage_bytes = (u32)((size_t)e->jt.l1_entries * 8 + (e->l2_in_lds ? e->jt.blocks_bytes() : 0));
-    d.jl2_in_lds = e->l2_in_lds ? 1u : 0u;
-    d.k1a_ct = e->k1a_ct;
+    d.jstage_bytes = (u32)((size_t)e->jt.l1_entries * 8 + (e->pa.l2_in_lds ? e->jt.blocks_bytes() : 0));
+    d.jl2_in_lds = e->pa.l2_in_lds ? 1u : 0u;
+    d.k1a_ct = e->pa.k1a_ct;
 }
 
 int sync_tables(sg_engine* e, hipStream_t s) {
@@ -295,7 +216,7 @@ int sync_tables(sg_engine* e, hipStream_t s) {
     }
     HIP_TRY(e, hipEventRecord(e->tab_ev, s));
     e->tab_seq++; e->tab_stream = s;
-    if (e->d.variant == 0 && !k1a_geometry(e)) { e->err = "K1 pass A: the join tables' level 1 and the piece counters do not fit a CU's LDS (fewer partitions / IP blocks needed)"; return SG_ENOSPC; }
+    if (e->d.variant == 0 && !sgplan::plan_pass_a(e->plan, e->jt.l1_entries, e->jt.blocks_bytes(), e->ov, &e->pa)) { e->err = "K1 pass A: the join tables' level 1 and the piece counters do not fit a CU's LDS (fewer partitions / IP blocks needed)"; return SG_ENOSPC; }
     return SG_OK;
 }
 // K1 on stream s reads the tables: after the last modification if that ran on another stream
@@ -329,7 +250,7 @@ int launch_k1(sg_engine* e, const sg_event* d_ev, size_t n, hipStream_t s) {
         return SG_OK;
     }
     const size_t kMaxTeam = (size_t)1 << 25;                             // k1a_team_partition addresses a launch's events with byte offsets below 2 GiB
-    if (e->d.variant == 0 && e->d.narrow && e->k1a_team && n > kMaxTeam) {
+    if (e->d.variant == 0 && e->d.narrow && e->pa.k1a_team && n > kMaxTeam) {
         for (size_t o = 0; o < n; o += kMaxTeam) { const int rc = launch_k1(e, d_ev + o, std::min(kMaxTeam, n - o), s); if (rc) return rc; }
         return SG_OK;
     }
@@ -347,36 +268,36 @@ int launch_k1(sg_engine* e, const sg_event* d_ev, size_t n, hipStream_t s) {
         hipEvent_t ta = tk ? get_event(e) : nullptr, tb = tk ? get_event(e) : nullptr;
         da.batch_state = e->window_events_in == 0 ? 1u : 0u;     // first batch of this window?
         const bool sh = e->d.world > 1;
-#define K1A_GO(L2, SH, HI) hipExtLaunchKernelGGL((k1a_partition<L2, SH, HI>), dim3(e->d.nwg), dim3(K1A_THREADS), (uint32_t)e->k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n)
+#define K1A_GO(L2, SH, HI) hipExtLaunchKernelGGL((k1a_partition<L2, SH, HI>), dim3(e->d.nwg), dim3(K1A_THREADS), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n)
 #define K1A_GO2(L2, SH) do { if (e->d.hist) K1A_GO(L2, SH, true); else K1A_GO(L2, SH, false); } while (0)
-#define K1T_GO(L2, SH, NS) hipExtLaunchKernelGGL((k1a_tile_partition<L2, SH, NS>), dim3(e->d.nwg), dim3(K1T_THREADS), (uint32_t)e->k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n)
-#define K1T_GO2(L2, SH) do { if (e->k1a_nsub == 2) K1T_GO(L2, SH, 2); else K1T_GO(L2, SH, 1); } while (0)
-#define K1M_GO(L2, SH) do { if (e->d.np == 256) hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 8>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); \
-                            else if (e->d.np == 512) hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 9>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); \
-                            else hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 10>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); } while (0)
+#define K1T_GO(L2, SH, NS) hipExtLaunchKernelGGL((k1a_tile_partition<L2, SH, NS>), dim3(e->d.nwg), dim3(K1T_THREADS), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n)
+#define K1T_GO2(L2, SH) do { if (e->pa.k1a_nsub == 2) K1T_GO(L2, SH, 2); else K1T_GO(L2, SH, 1); } while (0)
+#define K1M_GO(L2, SH) do { if (e->d.np == 256) hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 8>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); \
+                            else if (e->d.np == 512) hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 9>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); \
+                            else hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 10>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); } while (0)
         da.k1a_rot = e->d.k1a_rot;
         rot0 = e->d.k1a_rot; tb0 = e->d.k1a_ticket_base;           // (restored below when the launch is refused: the device counter only moves if the kernel runs)
-        if (e->d.narrow && !e->k1a_team) {                           // the next launch's first chunk goes to the workgroup behind this launch's last one
+        if (e->d.narrow && !e->pa.k1a_team) {                           // the next launch's first chunk goes to the workgroup behind this launch's last one
             const u64 per = (n + e->d.nwg - 1) / e->d.nwg, chunk = per >= 4096 ? 4096 : (per + 1023) / 1024 * 1024;
             e->d.k1a_rot = (u32)((e->d.k1a_rot + (n + chunk - 1) / chunk) % e->d.nwg);
         }
-        if (e->d.narrow && e->k1a_team) {
-            e->d.k1a_rot = (u32)((e->d.k1a_rot + k1m_tiles(n, e->d.nwg, e->k1a_teams, e->k1a_nt)) % ((u64)e->k1a_teams * e->d.nwg));
+        if (e->d.narrow && e->pa.k1a_team) {
+            e->d.k1a_rot = (u32)((e->d.k1a_rot + k1m_tiles(n, e->d.nwg, e->pa.k1a_teams, e->pa.k1a_nt)) % ((u64)e->pa.k1a_teams * e->d.nwg));
             da.k1a_ticket_base = e->d.k1a_ticket_base;
             {   // what this launch draws from the slot's ticket counter: one per tile beyond every team's first, one failing draw per active team
-                const unsigned long long nt_ = k1m_tiles(n, e->d.nwg, e->k1a_teams, e->k1a_nt), units_ = (unsigned long long)e->k1a_teams * e->d.nwg;
+                const unsigned long long nt_ = k1m_tiles(n, e->d.nwg, e->pa.k1a_teams, e->pa.k1a_nt), units_ = (unsigned long long)e->pa.k1a_teams * e->d.nwg;
                 if (!(e->d.ablate & 0x4u)) e->d.k1a_ticket_base += (u32)((nt_ > units_ ? nt_ - units_ : 0) + std::min(units_, nt_));
             }
-            if (e->l2_in_lds && e->l2_u16) { if (sh) K1M_GO(2, true); else K1M_GO(2, false); }
-            else if (e->l2_in_lds) { if (sh) K1M_GO(1, true); else K1M_GO(1, false); }
+            if (e->pa.l2_in_lds && e->pa.l2_u16) { if (sh) K1M_GO(2, true); else K1M_GO(2, false); }
+            else if (e->pa.l2_in_lds) { if (sh) K1M_GO(1, true); else K1M_GO(1, false); }
             else { if (sh) K1M_GO(0, true); else K1M_GO(0, false); }
         }
         else if (e->d.narrow) {
-            if (e->l2_in_lds && e->l2_u16) { if (sh) K1T_GO2(2, true); else K1T_GO2(2, false); }
-            else if (e->l2_in_lds) { if (sh) K1T_GO2(1, true); else K1T_GO2(1, false); }
+            if (e->pa.l2_in_lds && e->pa.l2_u16) { if (sh) K1T_GO2(2, true); else K1T_GO2(2, false); }
+            else if (e->pa.l2_in_lds) { if (sh) K1T_GO2(1, true); else K1T_GO2(1, false); }
             else { if (sh) K1T_GO2(0, true); else K1T_GO2(0, false); }
         }
-        else if (e->l2_in_lds) { if (sh) K1A_GO2(true, true); else K1A_GO2(true, false); }
+        else if (e->pa.l2_in_lds) { if (sh) K1A_GO2(true, true); else K1A_GO2(true, false); }
         else { if (sh) K1A_GO2(false, true); else K1A_GO2(false, false); }
 #undef K1M_GO
 #undef K1T_GO2
@@ -387,7 +308,7 @@ int launch_k1(sg_engine* e, const sg_event* d_ev, size_t n, hipStream_t s) {
     } else {
         Timed t(e, s, 1);
         u64 want = (n + 255) / 256;
-        int grid = (int)std::min<u64>(want, (u64)e->k1_grid);
+        int grid = (int)std::min<u64>(want, (u64)e->plan.k1_grid);
         hipLaunchKernelGGL(k1_resolve_aggregate, dim3(grid), dim3(256), 0, s, da, d_ev, (u64)n);
     }
     {
@@ -426,15 +347,9 @@ size_t layer_offset(u32 l) {
     return n;
 }
 
-int grid_for(u64 items, int per_block, int cap = 2048) {
-    u64 g = (items + per_block - 1) / per_block;
-    return (int)std::max<u64>(1, std::min<u64>(g, (u64)cap));
-}
-
 // the halo request lists and the active node lists of a sharded window: many workgroups, one launch (SG_K6_ONE_WG=1: the round-3 builder)
 void launch_halo_lists(sg_engine* e, hipStream_t s, u32* req, u32 capp) {
-    static const bool one_wg = sg_knob("SG_K6_ONE_WG") != nullptr;
-    if (one_wg) {
+    if (e->plan.k6_one_wg) {
         if (e->d.ncap <= K6_FLAGS_LDS) hipLaunchKernelGGL(k6_halo_build_padded<true>, dim3(1), dim3(1024), 0, s, e->d, req, capp);
         else hipLaunchKernelGGL(k6_halo_build_padded<false>, dim3(1), dim3(1024), 0, s, e->d, req, capp);
         return;
@@ -478,23 +393,23 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
     const u32 wt = warm_try ? 1u : 0u;
     {
         Timed tp(e, s, 2);
-        if (ob_mode == 1) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, e->d_ob_list, (const u32*)e->d_ob_n, e->ob_list_cap, 1u, (const u32*)nullptr, 0u, 0u, wt);
-        else if (ob_mode == 0) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, const_cast<u32*>(d_union), d_union_n, e->ob_list_cap, 0u, (const u32*)nullptr, 0u, 0u, wt);
-        else hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, e->d_ob_list, (const u32*)e->d_ob_n, e->ob_list_cap, 2u, d_union, stride, gworld, wt);
+        if (ob_mode == 1) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, e->d_ob_list, (const u32*)e->d_ob_n, e->plan.ob_list_cap, 1u, (const u32*)nullptr, 0u, 0u, wt);
+        else if (ob_mode == 0) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, const_cast<u32*>(d_union), d_union_n, e->plan.ob_list_cap, 0u, (const u32*)nullptr, 0u, 0u, wt);
+        else hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, e->d_ob_list, (const u32*)e->d_ob_n, e->plan.ob_list_cap, 2u, d_union, stride, gworld, wt);
     }
     if (d.variant == 0) {                                    // group 7 = K1 pass B (k1b_merge), kernel-exact timing as for pass A
         const bool tk = ((e->timing >> 7) & 1u) && e->closes % e->timing_stride == 0;
         hipEvent_t ta = tk ? get_event(e) : nullptr, tb = tk ? get_event(e) : nullptr;
         Dev db = d; db.batch_state = e->window_events_in == 0 ? 2u : 0u;          // a window without any batch: nothing to merge
         db.kept_compact = d.warm;                                                 // (a warm engine's pass B builds / feeds the kept state: compact node ids, sg_kernels.h sg_kept_compact)
-        const bool share = d.npb > e->k1b_cus && 2 * e->k1b_lds <= kLdsBytes;   // several partitions per CU and room for two tables: the SGPR-capped build lets two workgroups share a CU
+        const bool share = d.npb > e->plan.cus && 2 * e->plan.k1b_lds <= kLdsBytes;   // several partitions per CU and room for two tables: the SGPR-capped build lets two workgroups share a CU
         // warm engines: the warm attempt (WM 1: seeded tables, accumulators straight to their kept positions; returns at once when
         // kc_prepare has already called the window cold), then the cold merge (WM 2: returns at once on a warm window).  Both are records
         // of group 7: a window's pass B is the SUM of its group-7 records.
-#define K1B8W_GOP(U_, SPT_, P_, WM_) do { if (share) hipExtLaunchKernelGGL((k1b_stream_merge<U_, SPT_, P_, WM_>), dim3(d.npb), dim3(e->k1b_threads), (uint32_t)e->k1b_lds, s, ta, tb, 0u, db); \
-                                     else hipExtLaunchKernelGGL((k1b_stream_merge_wide<U_, SPT_, P_, WM_>), dim3(d.npb), dim3(e->k1b_threads), (uint32_t)e->k1b_lds, s, ta, tb, 0u, db); } while (0)
-#define K1B8W_GO(SPT_, WM_) do { if (e->k1b_pack) K1B8W_GOP(K1B_WARM_U, SPT_, true, WM_); else K1B8W_GOP(K1B_WARM_U, SPT_, false, WM_); } while (0)
-#define K1B8W_GO2(WM_) do { const u32 spt = d.k1b_ht / e->k1b_threads; if (spt >= 4) K1B8W_GO(4, WM_); else if (spt == 2) K1B8W_GO(2, WM_); else K1B8W_GO(1, WM_); } while (0)
+#define K1B8W_GOP(U_, SPT_, P_, WM_) do { if (share) hipExtLaunchKernelGGL((k1b_stream_merge<U_, SPT_, P_, WM_>), dim3(d.npb), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); \
+                                     else hipExtLaunchKernelGGL((k1b_stream_merge_wide<U_, SPT_, P_, WM_>), dim3(d.npb), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); } while (0)
+#define K1B8W_GO(SPT_, WM_) do { if (e->plan.k1b_pack) K1B8W_GOP(K1B_WARM_U, SPT_, true, WM_); else K1B8W_GOP(K1B_WARM_U, SPT_, false, WM_); } while (0)
+#define K1B8W_GO2(WM_) do { const u32 spt = d.k1b_ht / e->plan.k1b_threads; if (spt >= 4) K1B8W_GO(4, WM_); else if (spt == 2) K1B8W_GO(2, WM_); else K1B8W_GO(1, WM_); } while (0)
         if (d.warm) {
             if (warm_try) {
                 K1B8W_GO2(1);
@@ -502,14 +417,14 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
             }
             K1B8W_GO2(2);
         } else {
-#define K1B_GO(U_, H_) do { if (share) hipExtLaunchKernelGGL((k1b_merge<U_, H_>), dim3(d.np), dim3(e->k1b_threads), (uint32_t)e->k1b_lds, s, ta, tb, 0u, db); \
-                            else hipExtLaunchKernelGGL((k1b_merge_wide<U_, H_>), dim3(d.np), dim3(e->k1b_threads), (uint32_t)e->k1b_lds, s, ta, tb, 0u, db); } while (0)
-#define K1B8_GOP(U_, SPT_, P_) do { if (share) hipExtLaunchKernelGGL((k1b_stream_merge<U_, SPT_, P_>), dim3(d.npb), dim3(e->k1b_threads), (uint32_t)e->k1b_lds, s, ta, tb, 0u, db); \
-                               else hipExtLaunchKernelGGL((k1b_stream_merge_wide<U_, SPT_, P_>), dim3(d.npb), dim3(e->k1b_threads), (uint32_t)e->k1b_lds, s, ta, tb, 0u, db); } while (0)
-#define K1B8_GO(U_, SPT_) do { if (e->k1b_pack) K1B8_GOP(U_, SPT_, true); else K1B8_GOP(U_, SPT_, false); } while (0)
-#define K1B8_GO2(U_) do { const u32 spt = d.k1b_ht / e->k1b_threads; if (spt >= 4) K1B8_GO(U_, 4); else if (spt == 2) K1B8_GO(U_, 2); else K1B8_GO(U_, 1); } while (0)
-        if (d.narrow) { if (e->k1b_u == 8) K1B8_GO2(8); else K1B8_GO2(4); }
-        else if (d.hist) K1B_GO(4, true); else if (e->k1b_u == 8) K1B_GO(8, false); else K1B_GO(4, false);
+#define K1B_GO(U_, H_) do { if (share) hipExtLaunchKernelGGL((k1b_merge<U_, H_>), dim3(d.np), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); \
+                            else hipExtLaunchKernelGGL((k1b_merge_wide<U_, H_>), dim3(d.np), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); } while (0)
+#define K1B8_GOP(U_, SPT_, P_) do { if (share) hipExtLaunchKernelGGL((k1b_stream_merge<U_, SPT_, P_>), dim3(d.npb), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); \
+                               else hipExtLaunchKernelGGL((k1b_stream_merge_wide<U_, SPT_, P_>), dim3(d.npb), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); } while (0)
+#define K1B8_GO(U_, SPT_) do { if (e->plan.k1b_pack) K1B8_GOP(U_, SPT_, true); else K1B8_GOP(U_, SPT_, false); } while (0)
+#define K1B8_GO2(U_) do { const u32 spt = d.k1b_ht / e->plan.k1b_threads; if (spt >= 4) K1B8_GO(U_, 4); else if (spt == 2) K1B8_GO(U_, 2); else K1B8_GO(U_, 1); } while (0)
+        if (d.narrow) { if (e->plan.k1b_u == 8) K1B8_GO2(8); else K1B8_GO2(4); }
+        else if (d.hist) K1B_GO(4, true); else if (e->plan.k1b_u == 8) K1B_GO(8, false); else K1B_GO(4, false);
         }
 #undef K1B8_GO2
 #undef K1B8_GO
@@ -533,7 +448,7 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
             dk.st_sum = e->scr_sum[e->cur]; dk.st_max = e->scr_max[e->cur]; dk.row_mu = e->scr_mu[e->cur]; dk.row_sd = e->scr_mu[e->cur] + d.ncap + 1;
         }
         if (d.variant == 1) {
-            const u32 ntiles = e->ecap / K2_TILE;
+            const u32 ntiles = e->plan.ecap / K2_TILE;
             hipLaunchKernelGGL(k2_edge_count, dim3(ntiles), dim3(256), 0, s, d);
             hipLaunchKernelGGL(k2_scan_tiles, dim3(1), dim3(1024), 0, s, d, ntiles);
             hipLaunchKernelGGL(k2_edge_compact, dim3(ntiles), dim3(256), 0, s, d);
@@ -554,16 +469,15 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
     {
         Timed t3(e, s, 8);                                   // group 8 = in-statistics (group 3 = node + edge features)
         const u32 fin = d.warm ? (u32)std::min<u64>(64, ((u64)d.ncap + 255) / 256) : 1u;   // finishing workgroups: the block-sorted rows (1), every row of a warm window
-        const bool no_fuse = sg_knob("SG_K3_NO_FUSE") != nullptr;      // (development build: the two-launch form beside the fused one on one box)
-        if (fuse_in && !no_fuse) {
+        if (fuse_in && e->plan.k3_fuse_allowed) {
             // the one-call pipelines (nothing reads the in-statistics between the close and the features): the features sum the partials, the
             // finishing work rides at the end of k3_in_part's launch — fifteen launches per window instead of sixteen
             const u32 finp = d.warm ? (fin + 3) / 4 : 1u;        // (1024-thread workgroups there)
-            hipLaunchKernelGGL(k3_in_part, dim3(e->k3_ranges * e->k3_slices + finp), dim3(1024), e->k3in_lds, s, d, e->k3_slices, finp);
-            e->in_fused_slices = e->k3_slices;
+            hipLaunchKernelGGL(k3_in_part, dim3(e->plan.k3_ranges * e->plan.k3_slices + finp), dim3(1024), e->plan.k3in_lds, s, d, e->plan.k3_slices, finp);
+            e->in_fused_slices = e->plan.k3_slices;
         } else {
-            hipLaunchKernelGGL(k3_in_part, dim3(e->k3_ranges * e->k3_slices), dim3(1024), e->k3in_lds, s, d, e->k3_slices, 0u);
-            hipLaunchKernelGGL(k3_in_reduce, dim3(grid_for((u64)d.ncap * 6, 256, 1024) + fin), dim3(256), 0, s, d, e->k3_slices, fin);
+            hipLaunchKernelGGL(k3_in_part, dim3(e->plan.k3_ranges * e->plan.k3_slices), dim3(1024), e->plan.k3in_lds, s, d, e->plan.k3_slices, 0u);
+            hipLaunchKernelGGL(k3_in_reduce, dim3(grid_for((u64)d.ncap * 6, 256, 1024) + fin), dim3(256), 0, s, d, e->plan.k3_slices, fin);
             e->in_fused_slices = 0;
         }
     }
@@ -593,19 +507,16 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
     const int grid = grid_for(d.ncap, 16);
     const bool pj = fuse_proj && l + 1 == e->cfg.layers && d.world == 1;
     Timed t(e, s, 4);
-    // two launches per layer: the gather-mean at high occupancy (8 rows per workgroup), then the dense tiles
-    // (small graphs keep the fused kernel: at C2 the second launch costs more than the gather gains — 16.6 vs 20.9 us)
-    bool split = e->cfg.max_edges > (1u << 17);              // (C2's 66 k-edge engine stays fused; a 160 k-edge shard of C4 — with its hub rows — splits)
-    if (const char* v = sg_knob("SG_K4_FUSED")) split = std::atoi(v) == 0;
+    const bool split = e->plan.k4_split;                    // two launches per layer: the gather-mean, then the dense tiles (sg_plan.hpp)
 #define K4_LAUNCH(FI, MF, PJ, HIN, HOUT) do { if (split) { \
             hipLaunchKernelGGL((k4_gather<FI>), dim3(grid_for(d.ncap, K4G_ROWS, 4096 * 8 / K4G_ROWS)), dim3(K4G_ROWS * 64), 0, s, d, HIN); \
             hipLaunchKernelGGL((k4_sage_layer<FI, MF, PJ, (PJ ? 512 : 256), true>), dim3(grid), dim3(PJ ? 512 : 256), 0, s, d, HIN, HOUT, Wl, Wh); \
         } else hipLaunchKernelGGL((k4_sage_layer<FI, MF, PJ, (FI == 32 ? 1024 : 512), false>), dim3(grid), dim3(FI == 32 ? 1024 : 512), 0, s, d, HIN, HOUT, Wl, Wh); } while (0)
     if (l == 0) {
-        if (e->use_mfma) { if (pj) K4_LAUNCH(32, true, true, d.x0, d.h[1]); else K4_LAUNCH(32, true, false, d.x0, d.h[1]); }
+        if (e->plan.use_mfma) { if (pj) K4_LAUNCH(32, true, true, d.x0, d.h[1]); else K4_LAUNCH(32, true, false, d.x0, d.h[1]); }
         else { if (pj) K4_LAUNCH(32, false, true, d.x0, d.h[1]); else K4_LAUNCH(32, false, false, d.x0, d.h[1]); }
     } else {
-        if (e->use_mfma) { if (pj) K4_LAUNCH(64, true, true, d.h[l], d.h[l + 1]); else K4_LAUNCH(64, true, false, d.h[l], d.h[l + 1]); }
+        if (e->plan.use_mfma) { if (pj) K4_LAUNCH(64, true, true, d.h[l], d.h[l + 1]); else K4_LAUNCH(64, true, false, d.h[l], d.h[l + 1]); }
         else { if (pj) K4_LAUNCH(64, false, true, d.h[l], d.h[l + 1]); else K4_LAUNCH(64, false, false, d.h[l], d.h[l + 1]); }
     }
 #undef K4_LAUNCH
@@ -621,15 +532,11 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     const float* Wh = e->d_W + layer_offset(e->cfg.layers);
     Timed t(e, s, 5);
     if (!(proj_done && d.world == 1)) {
-        if (e->use_mfma) hipLaunchKernelGGL((k5_node_proj<true>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
+        if (e->plan.use_mfma) hipLaunchKernelGGL((k5_node_proj<true>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
         else hipLaunchKernelGGL((k5_node_proj<false>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
     }
     const bool fr = fuse_reset && d.variant == 0;
-    // ONE round of workgroups: the kernel runs 3 waves per SIMD (144 registers, amdgpu_waves_per_eu(3)) = 3 workgroups of 256 threads per CU at a
-    // time, and its waves stride over the edges — 2 048 workgroups were 2.67 rounds, the last one two-thirds empty.  Same box, C3, two
-    // repetitions: K5 61.1 us at 2 048, 61.7 at 1 024, 58.9 at 1 536, 57.8-57.9 at 768 (profiles/r06_grids_ab_c3.txt)
-    int g5 = grid_for(e->cfg.max_edges, 32, 3 * (int)e->k1b_cus);
-    if (const char* v = sg_knob("SG_K5_GRID")) { const int x = std::atoi(v); if (x >= 1 && x <= 65535) g5 = std::min(grid_for(e->cfg.max_edges, 32, 65535), x); }
+    const int g5 = (int)e->plan.k5_grid;                    // one round of workgroups (sg_plan.hpp)
     if (fr) hipLaunchKernelGGL(k5_edge_score<true>, dim3(g5), dim3(256), 0, s, d, Wh);
     else hipLaunchKernelGGL(k5_edge_score<false>, dim3(g5), dim3(256), 0, s, d, Wh);
     if (did_reset) *did_reset = fr;
@@ -638,7 +545,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
 }
 
 int do_reset(sg_engine* e, hipStream_t s) {
-    hipLaunchKernelGGL(k_reset_window, dim3(grid_for(std::max<u64>((u64)e->d.ncap * SG_NODE_STAT_SUM_WORDS, e->obcap), 256, 512)), dim3(256), 0, s, e->d);
+    hipLaunchKernelGGL(k_reset_window, dim3(grid_for(std::max<u64>((u64)e->d.ncap * SG_NODE_STAT_SUM_WORDS, e->plan.obcap), 256, 512)), dim3(256), 0, s, e->d);
     HIP_TRY(e, hipGetLastError());
     e->closed = false;
     e->window_events_in = 0;            // (an open window that is reset is discarded: the next batch is a first batch again)
@@ -715,6 +622,16 @@ int do_read(sg_engine* e, sg_edge_out* out, size_t cap, size_t* n, const sg_edge
     return SG_OK;
 }
 
+// the largest dynamic LDS a launch of these kernels may ask for (a process-wide attribute of each kernel)
+template <class... K>
+hipError_t lds_limit(size_t bytes, K... kernels) {
+    for (const void* f : {reinterpret_cast<const void*>(kernels)...}) {
+        const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (r != hipSuccess) return r;
+    }
+    return hipSuccess;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -728,19 +645,12 @@ uint32_t sg_hash32(uint32_t x) { return sg_fmix32(x); }
 
 const char* sg_last_error(sg_handle h) { return h ? h->err.c_str() : "null handle"; }
 
-int sg_create(const sg_config* cfg, sg_handle* out) {
-    if (!cfg || !out) return SG_EINVAL;
+int sg_create(const sg_config* cfg_in, sg_handle* out) {
+    if (!cfg_in || !out) return SG_EINVAL;
     *out = nullptr;
-    // ABI 3: the caller states how much of sg_config it knows about; the rest is zero
-    constexpr uint32_t kCfgMin = 88;                                 // sizeof(sg_config) when struct_size was introduced
-    if (cfg->struct_size < kCfgMin || cfg->struct_size > 4096) return SG_EINVAL;
-    sg_config full; std::memset(&full, 0, sizeof full);
-    std::memcpy(&full, cfg, std::min<size_t>(cfg->struct_size, sizeof full));
-    full.struct_size = (uint32_t)sizeof full;
-    cfg = &full;
-    if (cfg->abi_version != SG_ABI_VERSION || cfg->layers < 1 || cfg->layers > SG_MAX_LAYERS || cfg->max_edges == 0 ||
-        cfg->max_known_nodes == 0 || cfg->world == 0 || cfg->rank >= cfg->world || cfg->max_known_nodes > 0x3FFFFFFFu)
-        return SG_EINVAL;
+    sg_config c;
+    if (const int rc = sgplan::check_config(*cfg_in, &c)) return rc;
+    const sg_config* cfg = &c;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SG_ENODEV;
     hipDeviceProp_t prop;
@@ -748,125 +658,26 @@ int sg_create(const sg_config* cfg, sg_handle* out) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SG_ENODEV;   // MI355X only: the kernels are gfx950 code objects
     sg_engine* e = new sg_engine();
     e->cfg = *cfg;
-    if (const char* v = sg_knob("SG_ARENA")) e->arena_on = std::atoi(v) != 0;
-    if (e->cfg.max_batch == 0) e->cfg.max_batch = 1u << 20;
-    if (e->cfg.max_ips == 0) e->cfg.max_ips = e->cfg.max_known_nodes;
     auto fail = [&](int rc) { std::fprintf(stderr, "sg_create: %s\n", e->err.c_str()); sg_destroy(e); return rc; };
 #define CR(call) do { int _rc = (call); if (_rc) return fail(_rc); } while (0)
 #define CH(call) do { hipError_t _r = (call); if (_r != hipSuccess) { e->err = std::string(#call) + ": " + hipGetErrorString(_r); return fail(_r == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV); } } while (0)
+#ifdef SG_DEV_KNOBS
+    e->ov = sgplan::from_env();
+#endif
+    sgplan::DeviceFacts facts;
+    facts.cus = prop.multiProcessorCount; facts.lds_bytes = kLdsBytes;
+    CR(sgplan::make_plan(*cfg, facts, e->ov, &e->plan, &e->err));
+    const sgplan::Plan& P = e->plan;
     CH(hipSetDevice(cfg->device));
     CH(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     CH(hipEventCreateWithFlags(&e->tab_ev, hipEventDisableTiming));
-    e->k1_grid = std::min<int>(SG_MAX_K1_WGS, prop.multiProcessorCount * 8);
-    e->k1b_cus = (u32)std::max(1, prop.multiProcessorCount);
-    const char* env = sg_knob("SG_DENSE_VALU");
-    e->use_mfma = !(env && env[0] == '1');
 
     Dev& d = e->d;
+    sgplan::plan_to_dev(P, *cfg, d);
     const u64 ME = cfg->max_edges;
-    e->ecap = next_pow2(std::max<u64>(2 * ME, K2_TILE));
-    e->obcap = next_pow2(std::max<u64>(2 * (u64)cfg->max_outbound_ips, 64));
-    e->ob_list_cap = next_pow2(std::max<u64>((u64)cfg->max_outbound_ips * std::max<u32>(cfg->world, 1), 64));
-    d.max_known = cfg->max_known_nodes; d.max_labels = cfg->max_labels; d.max_obip = std::max<u32>(cfg->max_outbound_ips, 1);
-    d.rank = cfg->rank; d.world = cfg->world; d.max_edges = ME; d.layers = cfg->layers;
-    d.ncap = cfg->max_known_nodes + cfg->max_labels + d.max_obip;
-    d.emask = e->ecap - 1; d.obmask = e->obcap - 1;
-
-    // K1 variant: 0 = partitioned LDS aggregation (fast; bounded edges per partition), 1 = global table + atomics
-    if (e->cfg.max_window_events == 0) e->cfg.max_window_events = e->cfg.max_batch;
-    d.variant = cfg->k1_variant == 1 ? 1u : 0u;
-    d.hist = (cfg->flags & SG_CFG_EDGE_HISTOGRAM) ? 1u : 0u;
-    d.agg_slots = d.hist ? 5u : 3u;
-    {
-        // Narrow-record K1 (default): an endpoint is a compact index below 2^nb — KNOWN ids, then LABEL ids, then slots of the
-        // outbound-IP table — and the mixed pair's top bits are the partition (sg_hash.h sg_kmix); it needs the in-partition
-        // remainder of the key to fit 31 bits.  k1_variant 2 (or SG_K1_LEGACY) keeps the 16-byte-record kernels, which also
-        // carry the per-edge histogram.
-        const u64 cn = (u64)cfg->max_known_nodes + cfg->max_labels + e->obcap;
-        u32 nb = 12; while ((1ull << nb) < cn && nb < 31) nb++;
-        bool narrow = d.variant == 0 && !d.hist && cfg->k1_variant != 2 && !sg_knob("SG_K1_LEGACY") && nb <= 24;
-        // k1_variant 0 (auto) picks by the WINDOW, not only by what fits: the 8-byte path pays from a few million events or a quarter
-        // of a million edges per window up; below that (BASELINE config 2: 1 M events, 54 k edges) a window is a dozen launches of
-        // 5-30 us and the 16-byte kernels' shorter prologue and simpler pass B win — same box, C2: 130 us per window against 147-155
-        // (three rounds of tuning for config 3 had been paid for at config 2).  3 asks for the 8-byte path by name.
-        const bool small_window = ME < (1ull << 18) && e->cfg.max_window_events <= (2ull << 20);
-        if (cfg->k1_variant == 0 && small_window && !sg_knob("SG_K1_NARROW")) narrow = false;
-        u64 np = 0;
-        if (narrow) {
-            // partitions: ~2700 distinct edges each at the configured capacity at most (pass B's LDS table: 4096 slots of 36
-            // bytes, 3072 may fill), at least 256.  Fewer partitions = longer runs per tile in pass A.
-            np = next_pow2(std::max<u64>((ME + 2699) / 2700, 256));
-            u32 pbt = 0; while ((1ull << pbt) < np) pbt++;
-            if (np > 2048 || 2 * nb - pbt > 31) narrow = false;          // (one wave scans the run lengths: beyond this the 16-byte kernels / variant 1)
-        }
-        d.k1b_split = 1;
-        if (narrow) {
-            // pass B: a partition that may hold more than ~1150 edges is merged by TWO workgroups (sub-tables of 2048 slots, two
-            // workgroups per CU) rather than by one with a 4096-slot table that owns the CU alone
-            if (ME / np > 1150) { d.k1b_split = 2; d.k1b_ht = 2048; }
-            else d.k1b_ht = ME / np > 550 ? 2048 : 1024;
-            // (sizing the partitions by the window's RECORDS as well — 512 x 2 workgroups for a shard of C4, 10 M events over 126 k
-            // edges — was measured and bought nothing: 79 vs 73 us)
-            if (const char* v = sg_knob("SG_SPLIT")) { const int x = std::atoi(v); if (x == 1 || x == 2) { d.k1b_split = (u32)x; d.k1b_ht = ME / (np * x) > 1150 ? 4096 : (ME / (np * x) > 550 ? 2048 : 1024); } }
-        } else {
-            // 16-byte records: at most ~1250 distinct edges per partition (pass B's LDS table: 2048 slots, 1536 may fill; 1024 slots
-            // for small graphs), at least one per CU.  C3 with 1024 partitions 181 us, 2048: 198 us, 4096: 292 us.
-            np = next_pow2(std::max<u64>((ME + 1249) / 1250, 256));
-            if (np > 4096) np = 4096;
-            if (cfg->k1_variant != 1 && ME > (u64)4096 * 1400) d.variant = 1;   // beyond the partitioned path's range
-            d.k1b_ht = ME / np > 600 ? 2048 : 1024;
-            if (d.hist && d.k1b_ht == 2048) { d.k1b_ht = 1024; np = std::min<u64>(4096, np * 2); }   // 16 x u32 bins per slot: 104 bytes, half the slots, twice the partitions
-        }
-        d.np = (u32)np; d.nwg = 256;
-        // tuning overrides (tools/k1_sweep.py); anything that is not a legal geometry is ignored
-        if (const char* v = sg_knob("SG_NP")) { const u64 x = std::strtoull(v, nullptr, 0); if (x >= 64 && x <= (narrow ? 2048u : 4096u) && (x & (x - 1)) == 0) d.np = (u32)x; }
-        if (const char* v = sg_knob("SG_HT")) { const u64 x = std::strtoull(v, nullptr, 0); if (x >= 256 && x <= (narrow ? 4096u : 2048u) && (x & (x - 1)) == 0) d.k1b_ht = (u32)x; }
-        if (const char* v = sg_knob("SG_NWG")) { const u64 x = std::strtoull(v, nullptr, 0); if (x >= 1 && x <= (u64)SG_MAX_K1_WGS) d.nwg = (u32)x; }
-        d.pb = 0; while ((1u << d.pb) < d.np) d.pb++;
-        if (narrow && 2 * nb - d.pb > 31) { d.np = (u32)np; d.pb = 0; while ((1u << d.pb) < d.np) d.pb++; }   // an SG_NP override that would not leave 31 remainder bits
-        d.narrow = (narrow && d.variant == 0) ? 1u : 0u;
-        if (!d.narrow) d.k1b_split = 1;
-        // warm windows: the 8-byte-record path without the per-edge histogram (whose bins would have to follow the kept order too);
-        // SG_CFG_NO_WARM / SG_WARM=0 keep every window on the full rebuild.  (k1b_u = 8, the one-table-per-CU build, has no warm instantiation.)
-        // By default only where it pays: on a graph below a quarter of a million edges the rebuild's four kernels cost about what the
-        // compaction plus their four empty launches do (C2, same box: 147 us per window without, 155 with).  SG_CFG_WARM asks for it anyway.
-        d.warm = (d.narrow && !d.hist && !(cfg->flags & SG_CFG_NO_WARM) && ((cfg->flags & SG_CFG_WARM) || ME >= (1ull << 18))) ? 1u : 0u;
-        if (const char* v = sg_knob("SG_WARM")) { d.warm = (std::atoi(v) != 0 && d.narrow && !d.hist) ? 1u : 0u; }
-        d.npb = d.np * d.k1b_split;
-        d.nb = nb; d.rb = 2 * nb - d.pb;
-        d.pcap = d.narrow ? d.k1b_ht * 13 / 16 : d.k1b_ht * 3 / 4;       // (u32 keys probe cheaply: the narrow tables may fill to 0.81)
-        const double m = (double)e->cfg.max_window_events / ((double)d.np * d.nwg);
-        d.sa = std::min<u32>(24, std::max<u32>(8, (2 * 2048 / d.np + 6 + 1) & ~1u));   // aggregates per piece: cache slots / partitions, with head room
-        if (d.narrow) {
-            // a hot key the cache missed lands in ONE piece: twice the mean + 8 sigma + 24 records, then the overflow list
-            d.sn = ((u32)(2.0 * m + 8.0 * std::sqrt(m + 1.0) + 24.0) + 1u) & ~1u;
-            d.sn = std::min<u32>(d.sn, (1u << 20) - 16);
-            d.sw = std::min<u32>(64, std::max<u32>(8, d.sn / 8));
-            d.punits = (d.sn + 2 * d.sw + 5 * d.sa + 15) / 16 * 16;     // a piece = whole 128-byte lines; the slack goes to the narrow region
-            d.sn = d.punits - 2 * d.sw - 5 * d.sa;
-            d.ss = 0; d.pslots = 0;
-        } else {
-            d.ss = (u32)(2.0 * m + 8.0 * std::sqrt(m + 1.0) + 24.0);          // a hot key the cache missed lands in ONE piece: head room, then the overflow list
-            d.ss = (d.ss + d.agg_slots * d.sa + 7) / 8 * 8 - d.agg_slots * d.sa;   // a piece = whole 128-byte lines
-            d.ss = std::min<u32>(d.ss, (1u << 20) - 8);
-            d.pslots = d.ss + d.agg_slots * d.sa;
-        }
-        d.ovf_cap = 1u << 16;
-        e->k1b_threads = 1024u;                                          // measured: 1024 threads beat 2 x 512 (C3 135 vs 153 us, C2 15.5 vs 22.9 us)
-        // narrow pass B: 8 x 16 bytes per lane in flight where a CU holds one table anyway; two workgroups per CU need <= 64 VGPRs
-        if (d.narrow) e->k1b_u = ((size_t)d.k1b_ht * 36 + 8) * 2 > kLdsBytes && m > 24.0 ? 8 : 4;
-        if (const char* v = sg_knob("SG_K1B_U")) { if (std::atoi(v) == 8) e->k1b_u = 8; if (std::atoi(v) == 4) e->k1b_u = 4; }
-        if (e->k1b_u == 8) d.warm = 0;
-        // the packed add of pass B is exact while a workgroup merges fewer than 2^16 narrow records: a partition's pieces hold sn each
-        e->k1b_pack = d.narrow && (u64)d.sn * d.nwg < 65536ull;
-        if (const char* v = sg_knob("SG_K1B_PACK")) { if (std::atoi(v) == 0) e->k1b_pack = false; }
-        if (const char* v = sg_knob("SG_K1B_THREADS")) { const u64 x = std::strtoull(v, nullptr, 0); if ((x == 256 && !d.narrow) || x == 512 || x == 1024) e->k1b_threads = (u32)x; }
-        if (d.narrow && d.k1b_ht / e->k1b_threads > 4) e->k1b_threads = 1024u;    // (the compaction takes at most four table slots per thread)
-    }
     // join tables: word image (join_host.hpp) on the host, one device copy, a pinned ring for word updates
     {
-        const u32 max_blocks = d.variant == 0 ? (u32)std::min<u64>(1024, std::max<u64>(64, (u64)e->cfg.max_ips / 32)) : 2u;
-        const sgjoin::Layout L = sgjoin::Table::make_layout(e->cfg.max_ips, cfg->max_known_nodes, max_blocks);
+        const sgjoin::Layout L = sgjoin::Table::make_layout(cfg->max_ips, cfg->max_known_nodes, P.max_blocks);
         e->jt_mirror.assign(L.words, 0);
         e->jt.init(L, e->jt_mirror.data(), d.variant == 0);
         e->jt.max_dirty = kUpdCap;
@@ -886,85 +697,40 @@ int sg_create(const sg_config* cfg, sg_handle* out) {
         d.kind = reinterpret_cast<const uint8_t*>(e->d_blob + L.off_kind);
     }
     if (d.variant == 0) {
-        if (!k1a_geometry(e)) { e->err = "K1 pass A: piece counters and join level 1 do not fit a CU's LDS"; return fail(SG_ENOSPC); }
-        // (narrow: accumulators, keys, two counters, then the warm path's touch bits and new-key bits — one each per slot — and three words)
-        e->k1b_lds = d.narrow ? ((size_t)d.k1b_ht * 36 + 8 + (size_t)d.k1b_ht / 4 + 12 + 15) / 16 * 16 : (size_t)d.k1b_ht * (8 + 32 + (d.hist ? 4 * SG_HIST_BINS : 0));
-        for (const void* f : {reinterpret_cast<const void*>(k1a_partition<true, true, false>), reinterpret_cast<const void*>(k1a_partition<true, false, false>),
-                              reinterpret_cast<const void*>(k1a_partition<false, true, false>), reinterpret_cast<const void*>(k1a_partition<false, false, false>),
-                              reinterpret_cast<const void*>(k1a_partition<true, true, true>), reinterpret_cast<const void*>(k1a_partition<true, false, true>),
-                              reinterpret_cast<const void*>(k1a_partition<false, true, true>), reinterpret_cast<const void*>(k1a_partition<false, false, true>),
-                              reinterpret_cast<const void*>(k1a_tile_partition<2, true, 2>), reinterpret_cast<const void*>(k1a_tile_partition<2, false, 2>),
-                              reinterpret_cast<const void*>(k1a_tile_partition<1, true, 2>), reinterpret_cast<const void*>(k1a_tile_partition<1, false, 2>),
-                              reinterpret_cast<const void*>(k1a_tile_partition<0, true, 2>), reinterpret_cast<const void*>(k1a_tile_partition<0, false, 2>),
-                              reinterpret_cast<const void*>(k1a_tile_partition<2, true, 1>), reinterpret_cast<const void*>(k1a_tile_partition<2, false, 1>),
-                              reinterpret_cast<const void*>(k1a_tile_partition<1, true, 1>), reinterpret_cast<const void*>(k1a_tile_partition<1, false, 1>),
-                              reinterpret_cast<const void*>(k1a_tile_partition<0, true, 1>), reinterpret_cast<const void*>(k1a_tile_partition<0, false, 1>),
-                              reinterpret_cast<const void*>(k1a_team_partition<2, true, 2, 1024, 8>), reinterpret_cast<const void*>(k1a_team_partition<2, false, 2, 1024, 8>),
-                              reinterpret_cast<const void*>(k1a_team_partition<2, true, 2, 1024, 9>), reinterpret_cast<const void*>(k1a_team_partition<2, false, 2, 1024, 9>),
-                              reinterpret_cast<const void*>(k1a_team_partition<2, true, 2, 1024, 10>), reinterpret_cast<const void*>(k1a_team_partition<2, false, 2, 1024, 10>),
-                              reinterpret_cast<const void*>(k1a_team_partition<1, true, 2, 1024, 8>), reinterpret_cast<const void*>(k1a_team_partition<1, false, 2, 1024, 8>),
-                              reinterpret_cast<const void*>(k1a_team_partition<1, true, 2, 1024, 9>), reinterpret_cast<const void*>(k1a_team_partition<1, false, 2, 1024, 9>),
-                              reinterpret_cast<const void*>(k1a_team_partition<1, true, 2, 1024, 10>), reinterpret_cast<const void*>(k1a_team_partition<1, false, 2, 1024, 10>),
-                              reinterpret_cast<const void*>(k1a_team_partition<0, true, 2, 1024, 8>), reinterpret_cast<const void*>(k1a_team_partition<0, false, 2, 1024, 8>),
-                              reinterpret_cast<const void*>(k1a_team_partition<0, true, 2, 1024, 9>), reinterpret_cast<const void*>(k1a_team_partition<0, false, 2, 1024, 9>),
-                              reinterpret_cast<const void*>(k1a_team_partition<0, true, 2, 1024, 10>), reinterpret_cast<const void*>(k1a_team_partition<0, false, 2, 1024, 10>)})
-            CH(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        for (const void* f : {reinterpret_cast<const void*>(k1b_merge<4, false>), reinterpret_cast<const void*>(k1b_merge<8, false>), reinterpret_cast<const void*>(k1b_merge<4, true>),
-                              reinterpret_cast<const void*>(k1b_merge_wide<4, false>), reinterpret_cast<const void*>(k1b_merge_wide<8, false>), reinterpret_cast<const void*>(k1b_merge_wide<4, true>),
-                              reinterpret_cast<const void*>(k1b_stream_merge<4, 1, false>), reinterpret_cast<const void*>(k1b_stream_merge<4, 2, false>), reinterpret_cast<const void*>(k1b_stream_merge<4, 4, false>),
-                              reinterpret_cast<const void*>(k1b_stream_merge<8, 1, false>), reinterpret_cast<const void*>(k1b_stream_merge<8, 2, false>), reinterpret_cast<const void*>(k1b_stream_merge<8, 4, false>),
-                              reinterpret_cast<const void*>(k1b_stream_merge_wide<4, 1, false>), reinterpret_cast<const void*>(k1b_stream_merge_wide<4, 2, false>), reinterpret_cast<const void*>(k1b_stream_merge_wide<4, 4, false>),
-                              reinterpret_cast<const void*>(k1b_stream_merge_wide<8, 1, false>), reinterpret_cast<const void*>(k1b_stream_merge_wide<8, 2, false>), reinterpret_cast<const void*>(k1b_stream_merge_wide<8, 4, false>),
-                              reinterpret_cast<const void*>(k1b_stream_merge<4, 1, true>), reinterpret_cast<const void*>(k1b_stream_merge<4, 2, true>), reinterpret_cast<const void*>(k1b_stream_merge<4, 4, true>),
-                              reinterpret_cast<const void*>(k1b_stream_merge<8, 1, true>), reinterpret_cast<const void*>(k1b_stream_merge<8, 2, true>), reinterpret_cast<const void*>(k1b_stream_merge<8, 4, true>),
-                              reinterpret_cast<const void*>(k1b_stream_merge_wide<4, 1, true>), reinterpret_cast<const void*>(k1b_stream_merge_wide<4, 2, true>), reinterpret_cast<const void*>(k1b_stream_merge_wide<4, 4, true>),
-                              reinterpret_cast<const void*>(k1b_stream_merge_wide<8, 1, true>), reinterpret_cast<const void*>(k1b_stream_merge_wide<8, 2, true>), reinterpret_cast<const void*>(k1b_stream_merge_wide<8, 4, true>)})
-            CH(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->k1b_lds));
-        for (const void* f : {reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 1, false, 1>), reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 2, false, 1>), reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 4, false, 1>),
-                              reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 1, true, 1>), reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 2, true, 1>), reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 4, true, 1>),
-                              reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 1, false, 1>), reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 2, false, 1>), reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 4, false, 1>),
-                              reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 1, true, 1>), reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 2, true, 1>), reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 4, true, 1>),
-                              reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 1, false, 2>), reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 2, false, 2>), reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 4, false, 2>),
-                              reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 1, true, 2>), reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 2, true, 2>), reinterpret_cast<const void*>(k1b_stream_merge<K1B_WARM_U, 4, true, 2>),
-                              reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 1, false, 2>), reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 2, false, 2>), reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 4, false, 2>),
-                              reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 1, true, 2>), reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 2, true, 2>), reinterpret_cast<const void*>(k1b_stream_merge_wide<K1B_WARM_U, 4, true, 2>)})
-            CH(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->k1b_lds));
-        CH(hipFuncSetAttribute(reinterpret_cast<const void*>(kw_compact), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)KW_ROWS * 5 * sizeof(u64))));
-        e->ecap = K2_TILE;                                              // the global edge table is not used
+        if (!sgplan::plan_pass_a(P, e->jt.l1_entries, e->jt.blocks_bytes(), e->ov, &e->pa)) { e->err = "K1 pass A: piece counters and join level 1 do not fit a CU's LDS"; return fail(SG_ENOSPC); }
+        CH(lds_limit(kLdsBytes, k1a_partition<true, true, false>, k1a_partition<true, false, false>, k1a_partition<false, true, false>, k1a_partition<false, false, false>,
+                     k1a_partition<true, true, true>, k1a_partition<true, false, true>, k1a_partition<false, true, true>, k1a_partition<false, false, true>,
+                     k1a_tile_partition<2, true, 2>, k1a_tile_partition<2, false, 2>, k1a_tile_partition<1, true, 2>, k1a_tile_partition<1, false, 2>,
+                     k1a_tile_partition<0, true, 2>, k1a_tile_partition<0, false, 2>, k1a_tile_partition<2, true, 1>, k1a_tile_partition<2, false, 1>,
+                     k1a_tile_partition<1, true, 1>, k1a_tile_partition<1, false, 1>, k1a_tile_partition<0, true, 1>, k1a_tile_partition<0, false, 1>,
+                     k1a_team_partition<2, true, 2, 1024, 8>, k1a_team_partition<2, false, 2, 1024, 8>, k1a_team_partition<2, true, 2, 1024, 9>,
+                     k1a_team_partition<2, false, 2, 1024, 9>, k1a_team_partition<2, true, 2, 1024, 10>, k1a_team_partition<2, false, 2, 1024, 10>,
+                     k1a_team_partition<1, true, 2, 1024, 8>, k1a_team_partition<1, false, 2, 1024, 8>, k1a_team_partition<1, true, 2, 1024, 9>,
+                     k1a_team_partition<1, false, 2, 1024, 9>, k1a_team_partition<1, true, 2, 1024, 10>, k1a_team_partition<1, false, 2, 1024, 10>,
+                     k1a_team_partition<0, true, 2, 1024, 8>, k1a_team_partition<0, false, 2, 1024, 8>, k1a_team_partition<0, true, 2, 1024, 9>,
+                     k1a_team_partition<0, false, 2, 1024, 9>, k1a_team_partition<0, true, 2, 1024, 10>, k1a_team_partition<0, false, 2, 1024, 10>));
+        CH(lds_limit(P.k1b_lds, k1b_merge<4, false>, k1b_merge<8, false>, k1b_merge<4, true>, k1b_merge_wide<4, false>, k1b_merge_wide<8, false>, k1b_merge_wide<4, true>,
+                     k1b_stream_merge<4, 1, false>, k1b_stream_merge<4, 2, false>, k1b_stream_merge<4, 4, false>,
+                     k1b_stream_merge<8, 1, false>, k1b_stream_merge<8, 2, false>, k1b_stream_merge<8, 4, false>,
+                     k1b_stream_merge_wide<4, 1, false>, k1b_stream_merge_wide<4, 2, false>, k1b_stream_merge_wide<4, 4, false>,
+                     k1b_stream_merge_wide<8, 1, false>, k1b_stream_merge_wide<8, 2, false>, k1b_stream_merge_wide<8, 4, false>,
+                     k1b_stream_merge<4, 1, true>, k1b_stream_merge<4, 2, true>, k1b_stream_merge<4, 4, true>,
+                     k1b_stream_merge<8, 1, true>, k1b_stream_merge<8, 2, true>, k1b_stream_merge<8, 4, true>,
+                     k1b_stream_merge_wide<4, 1, true>, k1b_stream_merge_wide<4, 2, true>, k1b_stream_merge_wide<4, 4, true>,
+                     k1b_stream_merge_wide<8, 1, true>, k1b_stream_merge_wide<8, 2, true>, k1b_stream_merge_wide<8, 4, true>));
+        CH(lds_limit(P.k1b_lds, k1b_stream_merge<K1B_WARM_U, 1, false, 1>, k1b_stream_merge<K1B_WARM_U, 2, false, 1>, k1b_stream_merge<K1B_WARM_U, 4, false, 1>,
+                     k1b_stream_merge<K1B_WARM_U, 1, true, 1>, k1b_stream_merge<K1B_WARM_U, 2, true, 1>, k1b_stream_merge<K1B_WARM_U, 4, true, 1>,
+                     k1b_stream_merge_wide<K1B_WARM_U, 1, false, 1>, k1b_stream_merge_wide<K1B_WARM_U, 2, false, 1>, k1b_stream_merge_wide<K1B_WARM_U, 4, false, 1>,
+                     k1b_stream_merge_wide<K1B_WARM_U, 1, true, 1>, k1b_stream_merge_wide<K1B_WARM_U, 2, true, 1>, k1b_stream_merge_wide<K1B_WARM_U, 4, true, 1>,
+                     k1b_stream_merge<K1B_WARM_U, 1, false, 2>, k1b_stream_merge<K1B_WARM_U, 2, false, 2>, k1b_stream_merge<K1B_WARM_U, 4, false, 2>,
+                     k1b_stream_merge<K1B_WARM_U, 1, true, 2>, k1b_stream_merge<K1B_WARM_U, 2, true, 2>, k1b_stream_merge<K1B_WARM_U, 4, true, 2>,
+                     k1b_stream_merge_wide<K1B_WARM_U, 1, false, 2>, k1b_stream_merge_wide<K1B_WARM_U, 2, false, 2>, k1b_stream_merge_wide<K1B_WARM_U, 4, false, 2>,
+                     k1b_stream_merge_wide<K1B_WARM_U, 1, true, 2>, k1b_stream_merge_wide<K1B_WARM_U, 2, true, 2>, k1b_stream_merge_wide<K1B_WARM_U, 4, true, 2>));
+        CH(lds_limit((size_t)KW_ROWS * 5 * sizeof(u64), kw_compact));
     }
-    d.emask = e->ecap - 1;
-    d.alive_cap = cfg->max_alive ? cfg->max_alive : 65536u;
-    e->k3_ranges = (d.ncap + K3_IN_NR - 1) / K3_IN_NR;
-    // slices of the in-statistics' scan: 8 192 edges each at least; at most 48 where ranges x 48 workgroups (one per CU: 144 KiB of LDS) are ONE
-    // round of the chip — since the node features sum the partials themselves (k3_in_reduce is gone from the one-call pipelines) the shorter scan
-    // wins: same box, C3, K3-in + K3-feat 53.5-54.4 us at 32 slices, 49.6-49.8 at 48, 53.4 at 51 (profiles/r06_k3slices_ab_c3.txt) — else 32 (a
-    // config-5 shard's 49 ranges: more slices only add partials to write and read)
-    e->k3_slices = (u32)std::min<u64>((u64)e->k3_ranges * K3_IN_SMAX <= e->k1b_cus ? K3_IN_SMAX : 32, std::max<u64>(8, ME / 8192));
-    if (const char* v = sg_knob("SG_K3_SLICES")) { const u64 x = std::strtoull(v, nullptr, 0); if (x >= 1 && x <= 256) e->k3_slices = (u32)x; }
-    e->k3in_lds = (size_t)K3_IN_NR * 48;
-    {   // the row sort's two LDS arrays: large enough for a bitmap of the node capacity when that fits (a config-5 shard: 150 k nodes = 4.7 k words)
-        const u64 bw = ((u64)d.ncap + 31) / 32;
-        d.k2_sortw = bw <= K2_SORT_LDS ? K2_SORT_LDS : (u32)std::min<u64>(K2_SORT_LDS_MAX, (bw + 255) / 256 * 256);
-        CH(hipFuncSetAttribute(reinterpret_cast<const void*>(k2_rowsort_gather), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * (size_t)d.k2_sortw * sizeof(u32))));
-    }
-    {   // row degrees / in-row ranks by LDS histograms instead of one returning device atomic per edge (k2_deg_hist): when a u32 counter
-        // per node fits one workgroup's LDS.  G workgroups of npb / G consecutive output partitions each (G a power of two, 16 .. K2_DH_GMAX).
-        d.dh_g = d.dh_ppw = d.dh_ns = 0;
-        u32 g = std::min<u32>(K2_DH_GMAX, d.variant == 0 ? d.npb : 0u);            // (k2_rowptr: a multiple of 16)
-        // small graphs keep the degree atomics: their cost grows with the edges (1 M: 23 us of pass B), the histogram launch and the wider
-        // row scan cost 6-7 us whatever the size — C2 (66 k-edge capacity), same box: window 128.5 / 130.2 us with it, 124.4 / 125.3 without
-        if (ME < (1ull << 19)) g = 0;
-        // an engine that keeps warm-window state rebuilds rarely, and every launch of the rebuild chain is ~4.5 us of an EMPTY launch on a
-        // warm window: there the degree atomics (23-30 us more on a cold window at C3, no launch) are the better trade
-        if (d.warm) g = 0;
-        if (const char* v = sg_knob("SG_DH_G")) { const u64 x = std::strtoull(v, nullptr, 0); g = (x >= 16 && x <= K2_DH_GMAX && (x & (x - 1)) == 0 && d.variant == 0 && x <= d.npb) ? (u32)x : 0u; }
-        if (g >= 16 && (g & (g - 1)) == 0 && d.npb % g == 0 && ((size_t)d.ncap + 1) * sizeof(u32) <= 128u * 1024u && (u64)d.npb * d.pcap < (1ull << 32)) {
-            d.dh_g = g; d.dh_ppw = d.npb / g; d.dh_ns = (d.ncap + 1 + 63u) & ~63u;
-            CH(hipFuncSetAttribute(reinterpret_cast<const void*>(k2_deg_hist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)d.ncap + 1) * sizeof(u32))));
-        }
-    }
-    CH(hipFuncSetAttribute(reinterpret_cast<const void*>(k3_in_part), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->k3in_lds));
-    { const char* ab = sg_knob("SG_ABLATE"); d.ablate = ab ? (u32)std::strtoul(ab, nullptr, 0) : 0u; }
+    CH(lds_limit(2 * (size_t)d.k2_sortw * sizeof(u32), k2_rowsort_gather));
+    if (d.dh_g) CH(lds_limit(((size_t)d.ncap + 1) * sizeof(u32), k2_deg_hist));
+    CH(lds_limit(P.k3in_lds, k3_in_part));
     CR(dev_alloc(e, &d.dbg, (size_t)4 * 4096 * 8));
     CR(dev_alloc(e, &d.clk, (size_t)4));
     // everything a window owns; allocated once per slot
@@ -974,7 +740,7 @@ int sg_create(const sg_config* cfg, sg_handle* out) {
         if (w.variant == 0) {
             eslots = std::max<size_t>(ME, (size_t)w.npb * w.pcap);
             if (w.narrow) { LR(dev_alloc(e, &w.slab8, (size_t)w.np * w.nwg * w.punits)); LR(dev_alloc(e, &w.hdr8, (size_t)w.np * w.nwg));
-                            if (!sg_knob("SG_K1B_NO_ORDER")) { LR(dev_alloc(e, &w.k1b_cnt, w.np)); LR(dev_alloc(e, &w.k1b_order, w.np)); } }   // (pass B's largest-first order: sg_k2.h kc_prepare)
+                            if (P.k1b_order) { LR(dev_alloc(e, &w.k1b_cnt, w.np)); LR(dev_alloc(e, &w.k1b_order, w.np)); } }   // (pass B's largest-first order: sg_k2.h kc_prepare)
             else { LR(dev_alloc(e, &w.slab_s, (size_t)w.np * w.nwg * w.pslots)); LR(dev_alloc(e, &w.hdr, (size_t)w.np * w.nwg)); }
             LR(dev_alloc(e, &w.ovf, (size_t)w.ovf_cap * 9));
             LR(dev_alloc(e, &w.ovf_p, (size_t)w.ovf_cap));
@@ -1005,36 +771,35 @@ int sg_create(const sg_config* cfg, sg_handle* out) {
                 e->h_note.push_back(hn); e->note_seen.push_back(0);
             }
         }
-        const size_t KE = w.warm ? std::max<size_t>(ME, (size_t)w.npb * w.pcap) : ME;   // arrays the rebuild indexes by KEPT position on a warm engine
-        LR(dev_alloc(e, &w.ekeys, e->ecap, 0xFF));
-        LR(dev_alloc(e, &w.eacc, (size_t)e->ecap * 4));
+        const size_t KE = P.kept_edges;                               // arrays the rebuild indexes by KEPT position on a warm engine
+        LR(dev_alloc(e, &w.ekeys, P.ecap, 0xFF));
+        LR(dev_alloc(e, &w.eacc, (size_t)P.ecap * 4));
         if (w.variant == 1) w.acc_src = w.eacc;
-        LR(dev_alloc(e, &w.obkeys, e->obcap));
+        LR(dev_alloc(e, &w.obkeys, P.obcap));
         LR(dev_alloc(e, &w.wgstat, (size_t)SG_MAX_K1_WGS * WS_WORDS));
         LR(dev_alloc(e, &w.ctr, C_COUNT));
         LR(dev_alloc(e, &w.ob_sorted, w.max_obip));
-        LR(dev_alloc(e, &ob_list, e->ob_list_cap));
+        LR(dev_alloc(e, &ob_list, P.ob_list_cap));
         LR(dev_alloc(e, &ob_n, 4));
-        LR(dev_alloc(e, &w.tile_cnt, e->ecap / K2_TILE));
-        LR(dev_alloc(e, &w.tile_off, e->ecap / K2_TILE));
+        LR(dev_alloc(e, &w.tile_cnt, P.ecap / K2_TILE));
+        LR(dev_alloc(e, &w.tile_off, P.ecap / K2_TILE));
         LR(dev_alloc(e, &w.e_slot, ME)); LR(dev_alloc(e, &w.e_from, eslots)); LR(dev_alloc(e, &w.e_to, eslots));
         LR(dev_alloc(e, &w.longrows, (size_t)w.ncap + 1));
         LR(dev_alloc(e, &w.deg, ((size_t)w.ncap + 1) * SG_DEG_REP * SG_DEG_STRIDE)); LR(dev_alloc(e, &w.rp_tot, ((size_t)w.ncap + K2_RP_ROWS_DH) / K2_RP_ROWS_DH + 1)); LR(dev_alloc(e, &w.k6_tot, (((size_t)w.ncap + 1023) / 1024 + 1) * 16)); LR(dev_alloc(e, &w.k1a_ticket, 4)); LR(dev_alloc(e, &w.lb_ticket, 4)); w.k1a_ticket_base = 0; w.k1a_rot = 0; LR(dev_alloc(e, &w.rowptr, (size_t)w.ncap + 1)); LR(dev_alloc(e, &w.cursor, (size_t)w.ncap + 1));
         LR(dev_alloc(e, &w.col, ME)); LR(dev_alloc(e, &w.cs, KE)); LR(dev_alloc(e, &w.csr_from, ME));
         LR(dev_alloc(e, &w.sort_k, 2 * KE)); LR(dev_alloc(e, &w.sort_v, 2 * KE));
         LR(dev_alloc(e, &w.acc_csr, ME * 4));
-        if (w.hist) { LR(dev_alloc(e, &w.hist_src, (w.variant == 0 ? (size_t)w.npb * w.pcap : (size_t)e->ecap) * SG_HIST_BINS)); LR(dev_alloc(e, &w.hist_csr, ME * SG_HIST_BINS)); }
+        if (w.hist) { LR(dev_alloc(e, &w.hist_src, (w.variant == 0 ? (size_t)w.npb * w.pcap : (size_t)P.ecap) * SG_HIST_BINS)); LR(dev_alloc(e, &w.hist_csr, ME * SG_HIST_BINS)); }
         LR(dev_alloc(e, &w.st_sum, (size_t)w.ncap * SG_NODE_STAT_SUM_WORDS)); LR(dev_alloc(e, &w.st_max, (size_t)w.ncap * SG_NODE_STAT_MAX_WORDS));
         LR(dev_alloc(e, &w.x0, (size_t)w.ncap * SG_F_IN));
         for (u32 l = 1; l <= cfg->layers; l++) LR(dev_alloc(e, &w.h[l], (size_t)w.ncap * SG_F_HID));
         LR(dev_alloc(e, &w.P, (size_t)w.ncap * SG_F_HID)); LR(dev_alloc(e, &w.Q, (size_t)w.ncap * SG_F_HID));
         LR(dev_alloc(e, &w.nmean, (size_t)w.ncap * SG_F_HID));
-        w.hub_cap = (u32)std::min<u64>(KE / 256 + 16, 1u << 24);         // blocks of the rows longer than one block: at most E / 512 + one per such row
         LR(dev_alloc(e, &w.hub_items, w.hub_cap)); LR(dev_alloc(e, &w.hub_base, (size_t)w.ncap + 1)); LR(dev_alloc(e, &w.hub_part, (size_t)w.hub_cap * SG_F_HID));
         LR(dev_alloc(e, &w.efeat, ME * SG_F_EDGE)); LR(dev_alloc(e, &w.latz, ME)); LR(dev_alloc(e, &w.errr, ME));
         LR(dev_alloc(e, &w.row_mu, (size_t)w.ncap + 1)); LR(dev_alloc(e, &w.row_sd, (size_t)w.ncap + 1));
         LR(dev_alloc(e, &w.rows, ME));
-        LR(dev_alloc(e, &w.in_part, (size_t)e->k3_ranges * e->k3_slices * K3_IN_NR * 6));
+        LR(dev_alloc(e, &w.in_part, (size_t)P.k3_ranges * P.k3_slices * K3_IN_NR * 6));
         LR(dev_alloc(e, &w.alive_keys, w.alive_cap)); LR(dev_alloc(e, &w.alive_csr, KE));
         LR(dev_alloc(e, &w.act_l, (size_t)w.ncap + 1)); LR(dev_alloc(e, &w.act_p, (size_t)w.ncap + 1));
         // arm the per-workgroup statistic slots (tmin = ~0)
@@ -1056,11 +821,9 @@ int sg_create(const sg_config* cfg, sg_handle* out) {
         d.l1p_tab = tab;
     }
     CH(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking)); CH(hipStreamCreateWithFlags(&e->copy_stream2, hipStreamNonBlocking));
-    if (const char* v = sg_knob("SG_COPY_STREAMS")) e->n_copy = std::atoi(v) == 2 ? 2 : 1;
     CH(hipStreamCreateWithFlags(&e->rd_stream, hipStreamNonBlocking)); CH(hipEventCreateWithFlags(&e->score_ev, hipEventDisableTiming));
     CH(hipHostMalloc((void**)&e->h_ctr_pin, sizeof(e->h_ctr)));
-    if (const char* v = sg_knob("SG_STAGE_SLOTS")) e->n_stage = std::min(kStageSlots, std::max(2, std::atoi(v)));
-    for (int i = 0; i < e->n_stage; i++) {
+    for (int i = 0; i < P.n_stage; i++) {
         CH(hipEventCreateWithFlags(&e->copied_ev[i], hipEventDisableTiming));
         CH(hipHostMalloc((void**)&e->h_stage[i], (size_t)e->cfg.max_batch * sizeof(sg_event)));
         CR(dev_alloc(e, &e->d_stage[i], e->cfg.max_batch));
@@ -1069,7 +832,7 @@ int sg_create(const sg_config* cfg, sg_handle* out) {
     CH(hipStreamSynchronize(e->stream));
     // further windows in flight: same tables and weights, own window buffers and stream
     {
-        const u32 nw = std::min<u32>(std::max<u32>(cfg->windows_in_flight, 1), 8);
+        const u32 nw = P.n_slots;
         e->slots.resize(nw); e->plain_slot.assign(nw, 0);
         e->slots[0] = sg_engine::WinSlot{e->d, e->stream, e->d_ob_list, e->d_ob_n, false, 0};
         for (u32 k = 1; k < nw; k++) {
@@ -1116,12 +879,12 @@ int sg_destroy(sg_handle e) {
 int sg_geometry_get(sg_handle e, sg_geometry* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const Dev& d = e->d;
-    out->k1_variant = d.variant; out->k1_narrow = d.narrow; out->partitions = d.np; out->table_slots = d.k1b_ht; out->pass_b_split = d.k1b_split;
-    out->pass_a_workgroups = d.nwg; out->cache_slots = e->k1a_ct; out->join_l2_in_lds = e->l2_in_lds ? (e->d.narrow && e->l2_u16 ? 2u : 1u) : 0u;
-    out->tile_records = d.narrow ? (e->k1a_team ? 4u * e->k1a_nt / e->k1a_teams : K1T_TS(e->k1a_nsub)) : 0u; out->pass_a_teams = d.narrow && e->k1a_team ? e->k1a_teams : 0u; out->endpoint_bits = d.narrow ? d.nb : 0u;
-    out->piece_bytes = d.variant != 0 ? 0u : (d.narrow ? d.punits * 8u : d.pslots * 16u);
-    out->warm_windows = d.warm;
+    const sgplan::Plan& p = e->plan; const sgplan::PassA& a = e->pa;
+    out->k1_variant = p.variant; out->k1_narrow = p.narrow; out->partitions = p.np; out->table_slots = p.k1b_ht; out->pass_b_split = p.k1b_split;
+    out->pass_a_workgroups = p.nwg; out->cache_slots = a.k1a_ct; out->join_l2_in_lds = a.l2_in_lds ? (p.narrow && a.l2_u16 ? 2u : 1u) : 0u;
+    out->tile_records = p.narrow ? (a.k1a_team ? 4u * a.k1a_nt / a.k1a_teams : K1T_TS(a.k1a_nsub)) : 0u; out->pass_a_teams = p.narrow && a.k1a_team ? a.k1a_teams : 0u; out->endpoint_bits = p.narrow ? p.nb : 0u;
+    out->piece_bytes = p.variant != 0 ? 0u : (p.narrow ? p.punits * 8u : p.pslots * 16u);
+    out->warm_windows = p.warm;
     return SG_OK;
 }
 
@@ -1175,14 +938,14 @@ int sg_load_weights(sg_handle e, const float* w, size_t n) {
 namespace {
 // a free staging slot (neither being filled by another feeder nor still in flight), or -1: the ring is full
 int stage_take(sg_engine* e) {
-    for (int k = 0; k < e->n_stage; k++) {
-        const int c = (e->stage_next + k) % e->n_stage;
-        if (!e->stage_busy[c] && hipEventQuery(e->stage_ev[c]) != hipErrorNotReady) { e->stage_busy[c] = true; e->stage_next = (c + 1) % e->n_stage; e->pending_copies++; return c; }
+    for (int k = 0; k < e->plan.n_stage; k++) {
+        const int c = (e->stage_next + k) % e->plan.n_stage;
+        if (!e->stage_busy[c] && hipEventQuery(e->stage_ev[c]) != hipErrorNotReady) { e->stage_busy[c] = true; e->stage_next = (c + 1) % e->plan.n_stage; e->pending_copies++; return c; }
     }
     return -1;
 }
 // the copy stream a batch's host -> device copy goes on (engine lock held; two streams alternate when the engine has two)
-hipStream_t stage_stream(sg_engine* e) { return (e->n_copy == 2 && (e->copy_rr++ & 1)) ? e->copy_stream2 : e->copy_stream; }
+hipStream_t stage_stream(sg_engine* e) { return (e->plan.n_copy == 2 && (e->copy_rr++ & 1)) ? e->copy_stream2 : e->copy_stream; }
 // behind a slot's copy (already enqueued on `cs`, or refused): K1 pass A on the window's stream, the slot handed back (engine lock held)
 int stage_finish(sg_engine* e, int slot, size_t n, hipStream_t cs, bool copy_ok) {
     int rc = SG_OK;
@@ -1345,7 +1108,7 @@ int sg_window_close_gathered(sg_handle e, const uint32_t* d_gathered, uint32_t s
     if (!e || !d_gathered || stride < 2 || world == 0 || world > 8) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
     e->cv.wait(g, [&] { return e->pending_copies == 0; });
-    if ((u64)(stride - 1) * world > e->ob_list_cap) { e->err = "gathered outbound-ip lists exceed the engine's list capacity"; return SG_ENOSPC; }
+    if ((u64)(stride - 1) * world > e->plan.ob_list_cap) { e->err = "gathered outbound-ip lists exceed the engine's list capacity"; return SG_ENOSPC; }
     return do_close(e, pick(e, stream), d_gathered, nullptr, 2u, stride, world);
 }
 
@@ -1664,7 +1427,7 @@ int sg_window_run_sharded(sg_handle e, sg_comm* c, void* stream) {
         sg_engine::Xchg& x = e->xc;
         x.ob_stride = e->d.max_obip + 1;
         x.capp = std::max<u32>(1, std::min<u32>(e->d.ncap, 2 * ((e->d.ncap + W - 1) / W) + 1024));   // rows one shard may ask ONE owner for: twice an owner's mean share
-        if ((u64)(x.ob_stride - 1) * W > e->ob_list_cap) { e->err = "gathered outbound-ip lists exceed the engine's list capacity"; return SG_ENOSPC; }
+        if ((u64)(x.ob_stride - 1) * W > e->plan.ob_list_cap) { e->err = "gathered outbound-ip lists exceed the engine's list capacity"; return SG_ENOSPC; }
         int rc;
         if ((rc = dev_alloc(e, &x.ob_local, x.ob_stride)) || (rc = dev_alloc(e, &x.ob_all, (size_t)W * x.ob_stride)) ||
             (rc = dev_alloc(e, &x.req, (size_t)W * (x.capp + 1))) || (rc = dev_alloc(e, &x.serve, (size_t)W * (x.capp + 1))) ||

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/servicegraph.h"
+#include "sg_sizes.h"
 
 typedef unsigned long long u64;
 typedef uint32_t u32;
@@ -75,7 +76,6 @@ enum {
 // per-workgroup statistics slots written by K1 (one 64-byte line per workgroup: no cross-WG
 // contention), reduced at window close.
 enum { WS_TMIN = 0, WS_TMAX, WS_MAXLABEL, WS_DROPPED_SRC, WS_DROPPED_CAP, WS_MISROUTED, WS_ACCEPTED, WS_PAD, WS_WORDS };
-#define SG_MAX_K1_WGS 2048
 
 // node statistics words (SUM block), see include/servicegraph.h SG_NODE_STAT_SUM_WORDS
 enum { ST_OUT_DEG = 0, ST_IN_DEG, ST_OUT_CNT, ST_IN_CNT, ST_OUT_ERR, ST_IN_ERR, ST_OUT_SUM, ST_IN_SUM, ST_OUT_SSQ, ST_IN_SSQ, ST_OUT_ALIVE, ST_IN_ALIVE };

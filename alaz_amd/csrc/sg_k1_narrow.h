@@ -16,12 +16,9 @@
 // and leave as 40-byte aggregates.  Integer adds / max only: bit-exact whatever the order.
 #pragma once
 
-#define K1T_THREADS 1024
 #ifndef K1B_WARM_U
 #define K1B_WARM_U 2            // pass B of an engine that keeps state: 16-byte loads per lane in the rolling buffer (two workgroups per CU: 64 registers)
 #endif
-#define K1T_CHUNK   4096u         // events per chunk at most: four per thread
-#define K1T_TS(NSUB) (K1T_CHUNK * (NSUB))   // records per tile: NSUB chunks (1 or 2)
 #define K1T_NONE    0xFFFFFFFFu
 #define K1T_RANK_SHIFT 12         // stash word: partition (<= 12 bits) | rank in the partition's run << 12
 

@@ -26,8 +26,6 @@
 
 #define K1M_OOB     0x80000000u   // buffer offset of a lane without work (out of range of every buffer the kernel addresses)
 #define K1M_RARE    0xFFFFFFFEu   // parked-record tag: a rare event, joined by the general path at the end of its tile
-// LDS besides the cache and the join tables: piece counters + per team 4 counter arrays, statistics + barrier words, tile(s) of 4 records per thread (+ trash words)
-#define K1M_LDS_FIXED(np, teams, nt) ((size_t)(np) * 4 * (2 + 4 * (teams)) + 128 + ((size_t)(nt) * 4 + 4) * 8)
 
 // tiles of a launch of n events (the kernel's own arithmetic, for the host's ticket accounting)
 static inline unsigned long long k1m_tiles(unsigned long long n, unsigned nwg, unsigned teams, unsigned nt) {

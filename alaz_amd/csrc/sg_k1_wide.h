@@ -11,9 +11,7 @@
 // the position inside it is an LDS counter.
 // Pass B (k1b_merge, at window close): one workgroup per partition merges its pieces in an LDS table and writes each
 // distinct edge once with plain stores.
-#define K1A_THREADS 1024
 #define K1A_G       4         // events per thread per step
-#define K1A_NJ      6         // 16-byte join-blob words a thread stages into LDS (6 * 1024 * 16 B = 96 KiB at most)
 
 // Issue a global load NOW and leave it in flight; a later s_waitcnt (inline asm that names the
 // destination registers as in/out operands) is the matching wait.  Written as inline asm because the

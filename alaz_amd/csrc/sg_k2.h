@@ -173,7 +173,6 @@ __global__ __launch_bounds__(1024) void k2_ob_collect(Dev d, u32* list, u32 list
 }
 
 // ---- variant 1 only: compaction of the global edge table in ascending slot order -------------------
-#define K2_TILE 2048   // table slots per workgroup (256 threads x 8)
 
 __global__ __launch_bounds__(256) void k2_edge_count(Dev d) {
     const u32 tile = blockIdx.x;
@@ -245,7 +244,6 @@ __global__ __launch_bounds__(256) void k2_edge_compact(Dev d) {
 // round trip for a 1024-thread workgroup: taken one partition at a time the kernel would be dh_ppw dependent round trips).
 #define K2_DH_THREADS 1024
 #define K2_DH_FLIGHT 16
-#define K2_DH_GMAX 128           // k2_rowptr keeps a row's column of counts in registers: GMAX / 8 per lane
 #define SG_WARM_WINDOW(d) ((d).warm && !(d).ctr[C_COLD])             /* (uniform) this window is closed on the warm path: the rebuild kernels return at once */
 // The rebuild chain (k2_rowptr .. k2_rowsort_gather) on an engine that keeps state runs in one of three ways, decided on the device:
 //   0  a full rebuild (cold window) on the Dev the host set up — its CSR pointers are the KEPT arrays (buffer 0);
@@ -611,8 +609,6 @@ __device__ __forceinline__ void edge_features(const Dev& d, u32 pos) {
     d.latz[pos] = lat_z; d.errr[pos] = err_ratio;
 }
 
-#define K2_SORT_LDS 4096         // words of each of the row sort's two LDS arrays — at least: the host sizes them (Dev::k2_sortw) so that a node bitmap fits, up to K2_SORT_LDS_MAX
-#define K2_SORT_LDS_MAX 16384
 #define K2_LONG_WGS 1024
 #define K2_WAVE_ROW 512          // rows of up to this many edges are sorted by ONE wave (bitmap rank in a wave-private slice of the LDS arrays)
 #define K2_WAVE_BW  1024         // ... when the node bitmap fits this many words (N <= 32768)

@@ -58,7 +58,6 @@ __device__ __forceinline__ void kw_capture(const Dev& d, u64* scratch_sum, u64* 
 #define KW_NW (KW_THREADS / 64)
 #define KW_Q 4
 #define KW_CH (KW_THREADS * KW_Q)
-#define KW_ROWS 512                                                  // rows per chunk with LDS accumulators (5 x u64 each: 20 KiB)
 #define KW_RESIDENT (3 * SG_LB_RESIDENT)                             // working chunks that are certainly resident together (<= 80 VGPRs, 21 KiB of LDS)
 
 // kw_compact on a DELTA window (round 6): the warm pass B met keys the kept set lacks and emitted them as new edges; the rebuild chain has

@@ -1,0 +1,371 @@
+// sg_plan.hpp — the engine's launch plan: every sizing decision sg_create and the launches take, computed from the config,
+// two facts of the device and the development build's overrides.
+//
+// One place for the rules that each round retunes (which K1 path a window takes, partitions and pass-B table slots, the pass-A
+// cache and its teams, warm-window state, the close's slices / splits / grids), each with the measured reason it has.
+// No HIP in this file: tests/micro/plan_test.cpp drives it on the CPU and tests/test_plan.py compares its plans with the
+// ones the engine made before it existed (tests/golden/plans.json).
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <optional>
+#include <string>
+
+#include "../../include/servicegraph.h"
+#include "sg_sizes.h"
+
+namespace sgplan {
+
+typedef uint32_t u32;
+typedef uint64_t u64;
+
+constexpr size_t kLdsBytes = 160 * 1024;  // per workgroup on gfx950
+constexpr int kStageSlots = 32;           // staging ring slots at most (Plan::n_stage of them are allocated)
+
+inline u32 next_pow2(u64 v) { u64 p = 1; while (p < v) p <<= 1; return (u32)p; }
+inline int grid_for(u64 items, int per_block, int cap = 2048) {
+    u64 g = (items + per_block - 1) / per_block;
+    return (int)std::max<u64>(1, std::min<u64>(g, (u64)cap));
+}
+
+struct DeviceFacts {
+    int cus = 256;                        // compute units
+    size_t lds_bytes = kLdsBytes;         // LDS per workgroup
+};
+
+// Tuning knobs (tools/k1_sweep.py, the A/B tests of alternative kernel paths): read from the environment by the DEVELOPMENT build
+// only (-DSG_DEV_KNOBS -> lib/libservicegraph_dev.so); the shipped library plans with Overrides{}.  An override that is not a legal
+// value is ignored by the rule it overrides.
+struct Overrides {
+    typedef std::optional<std::string> Knob;
+    Knob ablate, np, ht, ct, nwg, nsub, split, warm, k1a, k1_narrow, k1_legacy, k1b_u, k1b_threads, k1b_pack, k1b_no_order,
+         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena;
+};
+struct KnobName { const char* name; Overrides::Knob Overrides::*field; };
+// the one list of knob names (alaz_amd/engine.py DEV_KNOBS is checked against it)
+constexpr KnobName kKnobs[] = {
+    {"SG_ABLATE", &Overrides::ablate}, {"SG_NP", &Overrides::np}, {"SG_HT", &Overrides::ht}, {"SG_CT", &Overrides::ct},
+    {"SG_NWG", &Overrides::nwg}, {"SG_NSUB", &Overrides::nsub}, {"SG_SPLIT", &Overrides::split}, {"SG_WARM", &Overrides::warm},
+    {"SG_K1A", &Overrides::k1a}, {"SG_K1_NARROW", &Overrides::k1_narrow}, {"SG_K1_LEGACY", &Overrides::k1_legacy},
+    {"SG_K1B_U", &Overrides::k1b_u}, {"SG_K1B_THREADS", &Overrides::k1b_threads}, {"SG_K1B_PACK", &Overrides::k1b_pack},
+    {"SG_K1B_NO_ORDER", &Overrides::k1b_no_order}, {"SG_L2_GLOBAL", &Overrides::l2_global}, {"SG_L2_U32", &Overrides::l2_u32},
+    {"SG_DH_G", &Overrides::dh_g}, {"SG_K3_SLICES", &Overrides::k3_slices}, {"SG_K3_NO_FUSE", &Overrides::k3_no_fuse},
+    {"SG_K4_FUSED", &Overrides::k4_fused}, {"SG_K5_GRID", &Overrides::k5_grid}, {"SG_K6_ONE_WG", &Overrides::k6_one_wg},
+    {"SG_DENSE_VALU", &Overrides::dense_valu}, {"SG_COPY_STREAMS", &Overrides::copy_streams}, {"SG_STAGE_SLOTS", &Overrides::stage_slots},
+    {"SG_ARENA", &Overrides::arena},
+};
+#ifdef SG_DEV_KNOBS
+inline Overrides from_env() {
+    Overrides o;
+    for (const KnobName& k : kKnobs) if (const char* v = std::getenv(k.name)) o.*k.field = std::string(v);
+    return o;
+}
+#endif
+inline int ival(const Overrides::Knob& k) { return std::atoi(k->c_str()); }
+inline u64 uval(const Overrides::Knob& k) { return std::strtoull(k->c_str(), nullptr, 0); }
+
+struct Plan {
+    // K1 (Dev fields of the same names)
+    u32 variant = 0, narrow = 0, hist = 0, agg_slots = 3, nb = 0, np = 0, pb = 0, nwg = 256, k1b_split = 1, k1b_ht = 0, npb = 0, rb = 0,
+        pcap = 0, sa = 0, sn = 0, sw = 0, punits = 0, ss = 0, pslots = 0, ovf_cap = 0, warm = 0;
+    u32 k1b_threads = 1024, k1b_u = 4;
+    bool k1b_pack = false;                    // narrow pass B: count + duration sum of a record in one 64-bit LDS add (sn x nwg < 2^16)
+    bool k1b_order = false;                   // narrow pass B takes its partitions largest first (sg_k2.h kc_prepare)
+    size_t k1b_lds = 0;                       // pass B's dynamic LDS (variant 0)
+    // table sizes
+    u32 ecap = 0, obcap = 0, ob_list_cap = 0, ncap = 0, max_obip = 1, alive_cap = 0, hub_cap = 0, max_blocks = 0;
+    u64 kept_edges = 0;                       // arrays the rebuild indexes by KEPT position on a warm engine: max(max_edges, npb x pcap), else max_edges
+    u32 max_known = 0;
+    // the close
+    u32 k3_ranges = 1, k3_slices = 8;
+    size_t k3in_lds = 0;
+    u32 k2_sortw = 0, dh_g = 0, dh_ppw = 0, dh_ns = 0;
+    bool k4_split = false;                    // K4 in two launches per layer (gather, then the dense tiles)
+    u32 k5_grid = 0;
+    bool k3_fuse_allowed = true;              // the one-call pipelines may fold k3_in_reduce into k3_in_part's launch
+    bool k6_one_wg = false;                   // the round-3 single-workgroup halo-list builder
+    bool use_mfma = true;
+    // host resources
+    u32 cus = 1;                              // compute units (pass B's "one round" arithmetic)
+    int k1_grid = 0, n_copy = 1, n_stage = 16;
+    bool arena_on = false;
+    u32 n_slots = 1;                          // window slots in flight
+    u32 ablate = 0;
+};
+
+// pass A's geometry: follows the join tables' state (the engine re-plans it whenever they change)
+struct PassA {
+    bool l2_u16 = false, k1a_team = false, l2_in_lds = false;
+    u32 k1a_nsub = 2, k1a_teams = 2, k1a_nt = 1024, k1a_ct = 2048;
+    size_t k1a_lds = 0;
+};
+
+// struct_size / ABI / range checks and the config's defaults (0 = max_batch / max_known_nodes / max_batch)
+inline int check_config(const sg_config& in, sg_config* out) {
+    // ABI 3: the caller states how much of sg_config it knows about; the rest is zero
+    constexpr uint32_t kCfgMin = 88;                                 // sizeof(sg_config) when struct_size was introduced
+    if (in.struct_size < kCfgMin || in.struct_size > 4096) return SG_EINVAL;
+    sg_config c; std::memset(&c, 0, sizeof c);
+    std::memcpy(&c, &in, std::min<size_t>(in.struct_size, sizeof c));
+    c.struct_size = (uint32_t)sizeof c;
+    if (c.abi_version != SG_ABI_VERSION || c.layers < 1 || c.layers > SG_MAX_LAYERS || c.max_edges == 0 ||
+        c.max_known_nodes == 0 || c.world == 0 || c.rank >= c.world || c.max_known_nodes > 0x3FFFFFFFu)
+        return SG_EINVAL;
+    if (c.max_batch == 0) c.max_batch = 1u << 20;
+    if (c.max_ips == 0) c.max_ips = c.max_known_nodes;
+    if (c.max_window_events == 0) c.max_window_events = c.max_batch;
+    *out = c;
+    return SG_OK;
+}
+
+// cfg: as check_config left it
+inline int make_plan(const sg_config& cfg, const DeviceFacts& dev, const Overrides& ov, Plan* out, std::string* why) {
+    sg_config chk;
+    if (check_config(cfg, &chk) != SG_OK) { if (why) *why = "invalid config"; return SG_EINVAL; }
+    Plan p;
+    const size_t lds = dev.lds_bytes;
+    // SG_ARENA=1: everything below 32 MiB is carved out of 256 MiB chunks instead of one hipMalloc per array (a test of whether the
+    // small arrays' page-table entries cost the window close — a chain of small latency-bound kernels — anything: measured on one box,
+    // 507.7 / 508.3 us per C3 window with the chunks, 505.1 / 504.8 without; off).
+    if (ov.arena) p.arena_on = ival(ov.arena) != 0;
+    p.k1_grid = std::min<int>(SG_MAX_K1_WGS, dev.cus * 8);
+    p.cus = (u32)std::max(1, dev.cus);
+    p.use_mfma = !(ov.dense_valu && (*ov.dense_valu)[0] == '1');
+    p.max_known = cfg.max_known_nodes;
+
+    const u64 ME = cfg.max_edges;
+    p.ecap = next_pow2(std::max<u64>(2 * ME, K2_TILE));
+    p.obcap = next_pow2(std::max<u64>(2 * (u64)cfg.max_outbound_ips, 64));
+    p.ob_list_cap = next_pow2(std::max<u64>((u64)cfg.max_outbound_ips * std::max<u32>(cfg.world, 1), 64));
+    p.max_obip = std::max<u32>(cfg.max_outbound_ips, 1);
+    p.ncap = cfg.max_known_nodes + cfg.max_labels + p.max_obip;
+
+    // K1 variant: 0 = partitioned LDS aggregation (fast; bounded edges per partition), 1 = global table + atomics
+    p.variant = cfg.k1_variant == 1 ? 1u : 0u;
+    p.hist = (cfg.flags & SG_CFG_EDGE_HISTOGRAM) ? 1u : 0u;
+    p.agg_slots = p.hist ? 5u : 3u;
+    // Narrow-record K1 (default): an endpoint is a compact index below 2^nb — KNOWN ids, then LABEL ids, then slots of the
+    // outbound-IP table — and the mixed pair's top bits are the partition (sg_hash.h sg_kmix); it needs the in-partition
+    // remainder of the key to fit 31 bits.  k1_variant 2 (or SG_K1_LEGACY) keeps the 16-byte-record kernels, which also
+    // carry the per-edge histogram.
+    const u64 cn = (u64)cfg.max_known_nodes + cfg.max_labels + p.obcap;
+    u32 nb = 12; while ((1ull << nb) < cn && nb < 31) nb++;
+    bool narrow = p.variant == 0 && !p.hist && cfg.k1_variant != 2 && !ov.k1_legacy && nb <= 24;
+    // k1_variant 0 (auto) picks by the WINDOW, not only by what fits: the 8-byte path pays from a few million events or a quarter
+    // of a million edges per window up; below that (BASELINE config 2: 1 M events, 54 k edges) a window is a dozen launches of
+    // 5-30 us and the 16-byte kernels' shorter prologue and simpler pass B win — same box, C2: 130 us per window against 147-155
+    // (three rounds of tuning for config 3 had been paid for at config 2).  3 asks for the 8-byte path by name.
+    const bool small_window = ME < (1ull << 18) && cfg.max_window_events <= (2ull << 20);
+    if (cfg.k1_variant == 0 && small_window && !ov.k1_narrow) narrow = false;
+    u64 np = 0;
+    if (narrow) {
+        // partitions: ~2700 distinct edges each at the configured capacity at most (pass B's LDS table: 4096 slots of 36
+        // bytes, 3072 may fill), at least 256.  Fewer partitions = longer runs per tile in pass A.
+        np = next_pow2(std::max<u64>((ME + 2699) / 2700, 256));
+        u32 pbt = 0; while ((1ull << pbt) < np) pbt++;
+        if (np > 2048 || 2 * nb - pbt > 31) narrow = false;          // (one wave scans the run lengths: beyond this the 16-byte kernels / variant 1)
+    }
+    p.k1b_split = 1;
+    if (narrow) {
+        // pass B: a partition that may hold more than ~1150 edges is merged by TWO workgroups (sub-tables of 2048 slots, two
+        // workgroups per CU) rather than by one with a 4096-slot table that owns the CU alone
+        if (ME / np > 1150) { p.k1b_split = 2; p.k1b_ht = 2048; }
+        else p.k1b_ht = ME / np > 550 ? 2048 : 1024;
+        // (sizing the partitions by the window's RECORDS as well — 512 x 2 workgroups for a shard of C4, 10 M events over 126 k
+        // edges — was measured and bought nothing: 79 vs 73 us)
+        if (ov.split) { const int x = ival(ov.split); if (x == 1 || x == 2) { p.k1b_split = (u32)x; p.k1b_ht = ME / (np * x) > 1150 ? 4096 : (ME / (np * x) > 550 ? 2048 : 1024); } }
+    } else {
+        // 16-byte records: at most ~1250 distinct edges per partition (pass B's LDS table: 2048 slots, 1536 may fill; 1024 slots
+        // for small graphs), at least one per CU.  C3 with 1024 partitions 181 us, 2048: 198 us, 4096: 292 us.
+        np = next_pow2(std::max<u64>((ME + 1249) / 1250, 256));
+        if (np > 4096) np = 4096;
+        if (cfg.k1_variant != 1 && ME > (u64)4096 * 1400) p.variant = 1;   // beyond the partitioned path's range
+        p.k1b_ht = ME / np > 600 ? 2048 : 1024;
+        if (p.hist && p.k1b_ht == 2048) { p.k1b_ht = 1024; np = std::min<u64>(4096, np * 2); }   // 16 x u32 bins per slot: 104 bytes, half the slots, twice the partitions
+    }
+    p.np = (u32)np; p.nwg = 256;
+    // tuning overrides (tools/k1_sweep.py); anything that is not a legal geometry is ignored
+    if (ov.np) { const u64 x = uval(ov.np); if (x >= 64 && x <= (narrow ? 2048u : 4096u) && (x & (x - 1)) == 0) p.np = (u32)x; }
+    if (ov.ht) { const u64 x = uval(ov.ht); if (x >= 256 && x <= (narrow ? 4096u : 2048u) && (x & (x - 1)) == 0) p.k1b_ht = (u32)x; }
+    if (ov.nwg) { const u64 x = uval(ov.nwg); if (x >= 1 && x <= (u64)SG_MAX_K1_WGS) p.nwg = (u32)x; }
+    p.pb = 0; while ((1u << p.pb) < p.np) p.pb++;
+    if (narrow && 2 * nb - p.pb > 31) { p.np = (u32)np; p.pb = 0; while ((1u << p.pb) < p.np) p.pb++; }   // an SG_NP override that would not leave 31 remainder bits
+    p.narrow = (narrow && p.variant == 0) ? 1u : 0u;
+    if (!p.narrow) p.k1b_split = 1;
+    // warm windows: the 8-byte-record path without the per-edge histogram (whose bins would have to follow the kept order too);
+    // SG_CFG_NO_WARM / SG_WARM=0 keep every window on the full rebuild.  (k1b_u = 8, the one-table-per-CU build, has no warm instantiation.)
+    // By default only where it pays: on a graph below a quarter of a million edges the rebuild's four kernels cost about what the
+    // compaction plus their four empty launches do (C2, same box: 147 us per window without, 155 with).  SG_CFG_WARM asks for it anyway.
+    p.warm = (p.narrow && !p.hist && !(cfg.flags & SG_CFG_NO_WARM) && ((cfg.flags & SG_CFG_WARM) || ME >= (1ull << 18))) ? 1u : 0u;
+    if (ov.warm) p.warm = (ival(ov.warm) != 0 && p.narrow && !p.hist) ? 1u : 0u;
+    p.npb = p.np * p.k1b_split;
+    p.nb = nb; p.rb = 2 * nb - p.pb;
+    p.pcap = p.narrow ? p.k1b_ht * 13 / 16 : p.k1b_ht * 3 / 4;       // (u32 keys probe cheaply: the narrow tables may fill to 0.81)
+    const double m = (double)cfg.max_window_events / ((double)p.np * p.nwg);
+    p.sa = std::min<u32>(24, std::max<u32>(8, (2 * 2048 / p.np + 6 + 1) & ~1u));   // aggregates per piece: cache slots / partitions, with head room
+    if (p.narrow) {
+        // a hot key the cache missed lands in ONE piece: twice the mean + 8 sigma + 24 records, then the overflow list
+        p.sn = ((u32)(2.0 * m + 8.0 * std::sqrt(m + 1.0) + 24.0) + 1u) & ~1u;
+        p.sn = std::min<u32>(p.sn, (1u << 20) - 16);
+        p.sw = std::min<u32>(64, std::max<u32>(8, p.sn / 8));
+        p.punits = (p.sn + 2 * p.sw + 5 * p.sa + 15) / 16 * 16;     // a piece = whole 128-byte lines; the slack goes to the narrow region
+        p.sn = p.punits - 2 * p.sw - 5 * p.sa;
+        p.ss = 0; p.pslots = 0;
+    } else {
+        p.ss = (u32)(2.0 * m + 8.0 * std::sqrt(m + 1.0) + 24.0);          // a hot key the cache missed lands in ONE piece: head room, then the overflow list
+        p.ss = (p.ss + p.agg_slots * p.sa + 7) / 8 * 8 - p.agg_slots * p.sa;   // a piece = whole 128-byte lines
+        p.ss = std::min<u32>(p.ss, (1u << 20) - 8);
+        p.pslots = p.ss + p.agg_slots * p.sa;
+    }
+    p.ovf_cap = 1u << 16;
+    p.k1b_threads = 1024u;                                          // measured: 1024 threads beat 2 x 512 (C3 135 vs 153 us, C2 15.5 vs 22.9 us)
+    // pass B's LDS table (narrow: accumulators, keys, two counters, then the warm path's touch bits and new-key bits — one each per slot
+    // — and three words; 16-byte records: key, accumulators and the histogram's bins per slot)
+    if (p.variant == 0)
+        p.k1b_lds = p.narrow ? ((size_t)p.k1b_ht * 36 + 8 + (size_t)p.k1b_ht / 4 + 12 + 15) / 16 * 16 : (size_t)p.k1b_ht * (8 + 32 + (p.hist ? 4 * SG_HIST_BINS : 0));
+    // narrow pass B: 8 x 16 bytes per lane in flight where a CU holds one table anyway; two workgroups per CU need <= 64 VGPRs
+    if (p.narrow) p.k1b_u = 2 * p.k1b_lds > lds && m > 24.0 ? 8 : 4;
+    if (ov.k1b_u) { if (ival(ov.k1b_u) == 8) p.k1b_u = 8; if (ival(ov.k1b_u) == 4) p.k1b_u = 4; }
+    if (p.k1b_u == 8) p.warm = 0;
+    // the packed add of pass B is exact while a workgroup merges fewer than 2^16 narrow records: a partition's pieces hold sn each
+    p.k1b_pack = p.narrow && (u64)p.sn * p.nwg < 65536ull;
+    if (ov.k1b_pack) { if (ival(ov.k1b_pack) == 0) p.k1b_pack = false; }
+    if (ov.k1b_threads) { const u64 x = uval(ov.k1b_threads); if ((x == 256 && !p.narrow) || x == 512 || x == 1024) p.k1b_threads = (u32)x; }
+    if (p.narrow && p.k1b_ht / p.k1b_threads > 4) p.k1b_threads = 1024u;    // (the compaction takes at most four table slots per thread)
+    p.k1b_order = p.narrow && !ov.k1b_no_order;
+    // join tables: IP blocks of the two-level table (variant 1 probes the cuckoo table only)
+    p.max_blocks = p.variant == 0 ? (u32)std::min<u64>(1024, std::max<u64>(64, (u64)cfg.max_ips / 32)) : 2u;
+    if (p.variant == 0) p.ecap = K2_TILE;                            // the global edge table is not used
+    p.alive_cap = cfg.max_alive ? cfg.max_alive : 65536u;
+    p.kept_edges = p.warm ? std::max<u64>(ME, (u64)p.npb * p.pcap) : ME;
+    p.hub_cap = (u32)std::min<u64>(p.kept_edges / 256 + 16, 1u << 24);   // blocks of the rows longer than one block: at most E / 512 + one per such row
+
+    p.k3_ranges = (p.ncap + K3_IN_NR - 1) / K3_IN_NR;
+    // slices of the in-statistics' scan: 8 192 edges each at least; at most 48 where ranges x 48 workgroups (one per CU: 144 KiB of LDS) are ONE
+    // round of the chip — since the node features sum the partials themselves (k3_in_reduce is gone from the one-call pipelines) the shorter scan
+    // wins: same box, C3, K3-in + K3-feat 53.5-54.4 us at 32 slices, 49.6-49.8 at 48, 53.4 at 51 (profiles/r06_k3slices_ab_c3.txt) — else 32 (a
+    // config-5 shard's 49 ranges: more slices only add partials to write and read)
+    p.k3_slices = (u32)std::min<u64>((u64)p.k3_ranges * K3_IN_SMAX <= p.cus ? K3_IN_SMAX : 32, std::max<u64>(8, ME / 8192));
+    if (ov.k3_slices) { const u64 x = uval(ov.k3_slices); if (x >= 1 && x <= 256) p.k3_slices = (u32)x; }
+    p.k3in_lds = (size_t)K3_IN_NR * 48;
+    {   // the row sort's two LDS arrays: large enough for a bitmap of the node capacity when that fits (a config-5 shard: 150 k nodes = 4.7 k words)
+        const u64 bw = ((u64)p.ncap + 31) / 32;
+        p.k2_sortw = bw <= K2_SORT_LDS ? K2_SORT_LDS : (u32)std::min<u64>(K2_SORT_LDS_MAX, (bw + 255) / 256 * 256);
+    }
+    {   // row degrees / in-row ranks by LDS histograms instead of one returning device atomic per edge (k2_deg_hist): when a u32 counter
+        // per node fits one workgroup's LDS.  G workgroups of npb / G consecutive output partitions each (G a power of two, 16 .. K2_DH_GMAX).
+        u32 g = std::min<u32>(K2_DH_GMAX, p.variant == 0 ? p.npb : 0u);            // (k2_rowptr: a multiple of 16)
+        // small graphs keep the degree atomics: their cost grows with the edges (1 M: 23 us of pass B), the histogram launch and the wider
+        // row scan cost 6-7 us whatever the size — C2 (66 k-edge capacity), same box: window 128.5 / 130.2 us with it, 124.4 / 125.3 without
+        if (ME < (1ull << 19)) g = 0;
+        // an engine that keeps warm-window state rebuilds rarely, and every launch of the rebuild chain is ~4.5 us of an EMPTY launch on a
+        // warm window: there the degree atomics (23-30 us more on a cold window at C3, no launch) are the better trade.  (SG_DH_G cannot
+        // switch the histogram on for such an engine: its delta windows rank the new edges with the degree replicas.)
+        if (p.warm) g = 0;
+        else if (ov.dh_g) { const u64 x = uval(ov.dh_g); g = (x >= 16 && x <= K2_DH_GMAX && (x & (x - 1)) == 0 && p.variant == 0 && x <= p.npb) ? (u32)x : 0u; }
+        if (g >= 16 && (g & (g - 1)) == 0 && p.npb % g == 0 && ((size_t)p.ncap + 1) * sizeof(u32) <= 128u * 1024u && (u64)p.npb * p.pcap < (1ull << 32)) {
+            p.dh_g = g; p.dh_ppw = p.npb / g; p.dh_ns = (p.ncap + 1 + 63u) & ~63u;
+        }
+    }
+    p.ablate = ov.ablate ? (u32)std::strtoul(ov.ablate->c_str(), nullptr, 0) : 0u;
+    // K4: two launches per layer — the gather-mean at high occupancy (8 rows per workgroup), then the dense tiles.  Small graphs keep
+    // the fused kernel: at C2 the second launch costs more than the gather gains — 16.6 vs 20.9 us.  (C2's 66 k-edge engine stays fused;
+    // a 160 k-edge shard of C4 — with its hub rows — splits.)
+    p.k4_split = cfg.max_edges > (1u << 17);
+    if (ov.k4_fused) p.k4_split = ival(ov.k4_fused) == 0;
+    // K5: ONE round of workgroups: the kernel runs 3 waves per SIMD (144 registers, amdgpu_waves_per_eu(3)) = 3 workgroups of 256 threads per CU at a
+    // time, and its waves stride over the edges — 2 048 workgroups were 2.67 rounds, the last one two-thirds empty.  Same box, C3, two
+    // repetitions: K5 61.1 us at 2 048, 61.7 at 1 024, 58.9 at 1 536, 57.8-57.9 at 768 (profiles/r06_grids_ab_c3.txt)
+    p.k5_grid = (u32)grid_for(cfg.max_edges, 32, 3 * (int)p.cus);
+    if (ov.k5_grid) { const int x = ival(ov.k5_grid); if (x >= 1 && x <= 65535) p.k5_grid = (u32)std::min(grid_for(cfg.max_edges, 32, 65535), x); }
+    p.k3_fuse_allowed = !ov.k3_no_fuse;                              // (development build: the two-launch form beside the fused one on one box)
+    p.k6_one_wg = (bool)ov.k6_one_wg;
+    if (ov.copy_streams) p.n_copy = ival(ov.copy_streams) == 2 ? 2 : 1;
+    if (ov.stage_slots) p.n_stage = std::min(kStageSlots, std::max(2, ival(ov.stage_slots)));
+    p.n_slots = std::min<u32>(std::max<u32>(cfg.windows_in_flight, 1), 8);
+    *out = p;
+    return SG_OK;
+}
+
+// Pass A's geometry for join tables of l1_entries level-1 entries and l2_bytes of level-2 blocks: does level 2 fit LDS beside the
+// edge cache (and, narrow path, the tile)?  Returns false when no legal geometry exists (the engine fails the call with a message
+// instead of launching a kernel that asks for more than a CU's LDS).
+inline bool plan_pass_a(const Plan& p, uint32_t l1_entries, size_t l2_bytes, const Overrides& ov, PassA* out) {
+    PassA a;
+    const size_t lds_cap = kLdsBytes;
+    const size_t l1b = (size_t)l1_entries * 8, l2b = l2_bytes;
+    const size_t stage_max = (size_t)K1A_NJ * K1A_THREADS * 16;    // what the prologue can stage: six 16-byte words per lane
+    if (p.narrow) {
+        // cache | 6 counters per partition | statistics | tile | join tables.  Level 2 is staged as u16 entries
+        // (half the bytes) when every node id fits 14 bits.
+        a.l2_u16 = p.max_known <= 16384 && !ov.l2_u32;
+        const size_t l2lds = a.l2_u16 ? l2b / 2 : l2b;
+        if (ov.nsub) { const int x = ival(ov.nsub); if (x == 1 || x == 2) a.k1a_nsub = (u32)x; }
+        // round 4: two teams per workgroup (k1a_team_partition) when their two tiles and counter sets fit beside a cache of 256 slots or
+        // more; SG_K1A=tile keeps the one-team kernel (k1a_tile_partition), SG_K1A=team takes the two-team kernel whenever it fits at all
+        const bool want_tile = ov.k1a && *ov.k1a == "tile", force_team = ov.k1a && *ov.k1a == "team";
+        const size_t fixed_tile = (size_t)p.np * 24 + 64 + (size_t)K1T_TS(a.k1a_nsub) * 8 + l1b;
+        // the two-team kernel is instantiated for 256 / 512 / 1024 partitions, 1024 threads (two teams of eight waves, one group of four events
+        // per thread and tile: round 6; round 4 ran two groups at 768 threads) and a join blob its prologue can stage; everything else keeps
+        // the one-team kernel
+        const int teams = 2, nt = 1024;
+        // (what the team kernel's prologue can stage: six 16-byte words per lane of its threads.  Level 1 always goes through it, level 2
+        // only when it is staged — an engine whose level 2 stays in global memory needs room for level 1 alone)
+        const size_t stage_team = (size_t)K1A_NJ * nt * 16;
+        // (endpoint spaces beyond 15 bits — a shard of BASELINE config 5: 18 — leave no room for the partition number in a parked record: the
+        // kernel's 16-lanes-per-run copy-out takes over, the workgroup has the 1024 threads it is written for since round 6)
+        const bool team_ok = (p.np == 256 || p.np == 512 || p.np == 1024) && (size_t)p.np * p.nwg * p.punits * 8 < ((size_t)1 << 31) && l1b <= stage_team;
+        a.k1a_teams = (u32)teams; a.k1a_nt = (u32)nt;
+        const size_t fixed_team = K1M_LDS_FIXED(p.np, teams, nt) + l1b;
+        auto pick = [&](size_t fixed, u32 ct_min, size_t stage_cap, u32& ct, bool& in_lds) {
+            ct = 0; in_lds = false;
+            // (the cache flattens the hottest keys; beyond 1024 slots it costs more aggregates than it saves records)
+            for (u32 c : {1024u, 512u, 256u, 128u}) if (c >= ct_min && (size_t)c * 40 + fixed + l2lds <= lds_cap && l1b + l2b <= stage_cap) { in_lds = true; ct = c; break; }
+            if (!ct) for (u32 c : {1024u, 512u, 256u, 128u, 64u}) if (c >= ct_min && (size_t)c * 40 + fixed <= lds_cap) { ct = c; break; }
+        };
+        u32 ct = 0; bool in_lds = false;
+        if (!want_tile && team_ok) { pick(fixed_team, force_team ? 64u : 256u, stage_team, ct, in_lds); a.k1a_team = ct != 0; }
+        if (!ct) pick(fixed_tile, 64u, stage_max, ct, in_lds);
+        const size_t fixed = a.k1a_team ? fixed_team : fixed_tile;
+        a.l2_in_lds = in_lds;
+        if (ov.l2_global) a.l2_in_lds = false;
+        if (ov.ct) { const u32 x = (u32)std::strtoul(ov.ct->c_str(), nullptr, 0); if (x >= 64 && x <= 2048 && (x & (x - 1)) == 0 && (size_t)x * 40 + fixed + (a.l2_in_lds ? l2lds : 0) <= lds_cap) ct = x; }
+        if (!ct || l1b > stage_max) return false;
+        a.k1a_ct = ct;
+        a.k1a_lds = (size_t)ct * 40 + fixed + (a.l2_in_lds ? l2lds : 0);
+        *out = a;
+        return true;
+    }
+    const size_t fixed = (size_t)p.np * 4 + 64 + l1b;
+    const size_t slot = p.hist ? 72 : 40;                    // cache slot: key + 4 accumulators (+ 16 x u16 bins)
+    u32 ct = 0;
+    for (u32 c : {2048u, 1024u, 512u}) if ((size_t)c * slot + fixed + l2b <= lds_cap && l1b + l2b <= stage_max) { a.l2_in_lds = true; ct = c; break; }
+    // level 2 stays in global memory: the largest cache that fits beside the counters and level 1
+    if (!ct) for (u32 c : {2048u, 1024u, 512u, 256u, 128u, 64u}) if ((size_t)c * slot + fixed <= lds_cap) { ct = c; break; }
+    if (ov.ct) { const u32 x = (u32)std::strtoul(ov.ct->c_str(), nullptr, 0); if (x >= 64 && x <= 2048 && (x & (x - 1)) == 0 && (size_t)x * slot + fixed + (a.l2_in_lds ? l2b : 0) <= lds_cap) ct = x; }
+    if (ov.l2_global) a.l2_in_lds = false;
+    if (!ct || l1b > stage_max) return false;
+    a.k1a_ct = ct;
+    a.k1a_lds = (size_t)ct * slot + fixed + (a.l2_in_lds ? l2b : 0);
+    *out = a;
+    return true;
+}
+
+// the plan's share of the kernels' argument (Dev, sg_device.h; a template so that the CPU test can fill a struct of the same names)
+template <class D>
+void plan_to_dev(const Plan& p, const sg_config& cfg, D& d) {
+    d.max_known = cfg.max_known_nodes; d.max_labels = cfg.max_labels; d.max_obip = p.max_obip;
+    d.rank = cfg.rank; d.world = cfg.world; d.max_edges = cfg.max_edges; d.layers = cfg.layers;
+    d.ncap = p.ncap; d.emask = p.ecap - 1; d.obmask = p.obcap - 1;
+    d.variant = p.variant; d.narrow = p.narrow; d.hist = p.hist; d.agg_slots = p.agg_slots;
+    d.nb = p.nb; d.np = p.np; d.pb = p.pb; d.rb = p.rb; d.nwg = p.nwg; d.k1b_split = p.k1b_split; d.npb = p.npb; d.k1b_ht = p.k1b_ht;
+    d.pcap = p.pcap; d.sa = p.sa; d.sn = p.sn; d.sw = p.sw; d.punits = p.punits; d.ss = p.ss; d.pslots = p.pslots; d.ovf_cap = p.ovf_cap;
+    d.warm = p.warm; d.alive_cap = p.alive_cap; d.hub_cap = p.hub_cap;
+    d.k2_sortw = p.k2_sortw; d.dh_g = p.dh_g; d.dh_ppw = p.dh_ppw; d.dh_ns = p.dh_ns;
+    d.ablate = p.ablate;
+}
+
+}  // namespace sgplan

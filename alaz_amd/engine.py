@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SG_LIB_PATH") or os.path.join(_HERE, "lib", "libservi
 # the development build (-DSG_DEV_KNOBS, alaz_amd/build.py): the only one that reads SG_* tuning knobs from the environment and has the
 # SG_ABLATE bits / phase stamps compiled in.  ServiceGraph(dev_knobs=True) — tools/, the A/B tests of alternative kernel paths — loads it.
 LIB_DEV_PATH = os.path.join(_HERE, "lib", "libservicegraph_dev.so")
-#: the knobs the development build reads (servicegraph.hip sg_knob); ServiceGraph(dev_knobs=None) picks that build when one of them is set
+#: the knobs the development build reads (csrc/sg_plan.hpp kKnobs); ServiceGraph(dev_knobs=None) picks that build when one of them is set
 DEV_KNOBS = ("SG_ABLATE", "SG_NP", "SG_HT", "SG_CT", "SG_NWG", "SG_NSUB", "SG_SPLIT", "SG_WARM", "SG_K1A", "SG_K1_NARROW", "SG_K1_LEGACY", "SG_K1B_U",
              "SG_K1B_THREADS", "SG_K1B_PACK", "SG_K1B_NO_ORDER", "SG_L2_GLOBAL", "SG_L2_U32", "SG_DH_G", "SG_K3_SLICES", "SG_K3_NO_FUSE", "SG_K4_FUSED", "SG_K5_GRID", "SG_K6_ONE_WG", "SG_DENSE_VALU",
              "SG_COPY_STREAMS", "SG_STAGE_SLOTS", "SG_ARENA")
@@ -102,6 +102,9 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         if _lib_dev is not None:
             return _lib_dev
         path = os.environ.get("SG_LIB_DEV", LIB_DEV_PATH)   # (another development build: A/B runs of two kernel forms on one box)
+        if path == LIB_DEV_PATH:                             # the tree's own development build: rebuilt when older than its sources
+            from . import build
+            build.build_engine(dev=True)
     else:
         if _lib is not None:
             return _lib
