@@ -16,6 +16,7 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     SG_SYM(upsert_service, "sg_upsert_service"); SG_SYM(delete_service, "sg_delete_service"); SG_SYM(set_label_count, "sg_set_label_count");
     SG_SYM(ingest, "sg_ingest"); SG_SYM(flush_window, "sg_flush_window"); SG_SYM(window_outbound_ips, "sg_window_outbound_ips");
     o->flush_window_view = reinterpret_cast<decltype(o->flush_window_view)>(dlsym(dl, "sg_flush_window_view"));   // optional
+    o->flush_window_top = reinterpret_cast<decltype(o->flush_window_top)>(dlsym(dl, "sg_flush_window_top"));      // optional
     SG_SYM(last_error, "sg_last_error");
 #undef SG_SYM
     return true;
@@ -220,6 +221,13 @@ int GraphDS::IngestWire(const uint8_t* recs, size_t n, const uint32_t* kafka_msg
     return rc;
 }
 
+int GraphDS::SetSelection(uint32_t k, float min_score) {
+    if (k > SG_SELECT_MAX_K || !api_.flush_window_top) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(flush_mu_);
+    select_ = true; sel_k_ = k; sel_min_ = min_score;
+    return SG_OK;
+}
+
 long GraphDS::FlushWindow(int64_t window_end_ms) {
     std::lock_guard<std::mutex> fg(flush_mu_);
     std::vector<sg_edge_out> own;                  // only without sg_flush_window_view: a pageable copy of up to max_edges rows
@@ -235,8 +243,15 @@ long GraphDS::FlushWindow(int64_t window_end_ms) {
     { std::lock_guard<std::mutex> g(id_mu_); retire_now.swap(retired_); }     // ids whose last IP went away before this window closed
     api_.set_label_count(h_, (uint32_t)labels.size());
     int rc;
-    if (api_.flush_window_view) rc = api_.flush_window_view(h_, (uint64_t)window_end_ms, &rows, &n);     // rows stay valid: flush_mu_ is held
-    else { own.resize(max_edges_); rc = api_.flush_window(h_, (uint64_t)window_end_ms, own.data(), own.size(), &n); rows = own.data(); n = std::min(n, own.size()); }
+    size_t n_conv = 0;                             // rows handed to the sink: all of them, or the selected ones
+    if (select_) {                                 // only the selected rows leave the device
+        own.resize(sel_k_ ? std::min<size_t>(sel_k_, max_edges_) : max_edges_);
+        size_t n_sel = 0;
+        rc = api_.flush_window_top(h_, (uint64_t)window_end_ms, sel_k_, sel_min_, own.data(), nullptr, own.size(), &n_sel, &n);
+        rows = own.data(); n_conv = std::min(n_sel, own.size());
+    }
+    else if (api_.flush_window_view) { rc = api_.flush_window_view(h_, (uint64_t)window_end_ms, &rows, &n); n_conv = n; }     // rows stay valid: flush_mu_ is held
+    else { own.resize(max_edges_); rc = api_.flush_window(h_, (uint64_t)window_end_ms, own.data(), own.size(), &n); rows = own.data(); n = std::min(n, own.size()); n_conv = n; }
     if (rc != SG_OK) return rc;
     // the label table again, AFTER the window has closed: a feeder may have interned a label and pushed its event into this
     // window between the first snapshot and the close (labels are append-only, so the later snapshot is a superset)
@@ -247,7 +262,7 @@ long GraphDS::FlushWindow(int64_t window_end_ms) {
         obips.resize(no);
         if (no) api_.window_outbound_ips(h_, obips.data(), no, &no);
     }
-    std::vector<EdgeRow> out(n);
+    std::vector<EdgeRow> out(n_conv);
     auto name = [&](uint32_t ref, std::string* type, std::string* uid) {
         const uint32_t t = SG_REF_TYPE(ref), v = SG_REF_VALUE(ref);
         if (t == SG_REF_KNOWN && v < uid_of_.size()) { *type = kind_of_[v] == SG_NODE_SERVICE ? "service" : "pod"; *uid = uid_of_[v]; }
@@ -257,7 +272,7 @@ long GraphDS::FlushWindow(int64_t window_end_ms) {
     };
     {
         std::lock_guard<std::mutex> g(id_mu_);       // uid_of_ / kind_of_ are appended to by PersistPod / PersistService
-        for (size_t i = 0; i < n; i++) {
+        for (size_t i = 0; i < n_conv; i++) {
             const sg_edge_out& r = rows[i]; EdgeRow& o = out[i];
             name(r.from_ref, &o.FromType, &o.FromUID); name(r.to_ref, &o.ToType, &o.ToUID);
             o.Count = r.count; o.ErrCount = r.err_count; o.SumNs = r.sum_ns; o.MaxNs = r.max_ns; o.SumSqUs = r.sumsq_us;

@@ -41,6 +41,7 @@ struct SgApi {
     int (*flush_window)(sg_handle, uint64_t, sg_edge_out*, size_t, size_t*) = nullptr;
     int (*flush_window_view)(sg_handle, uint64_t, const sg_edge_out**, size_t*) = nullptr;   // optional (absent in a recording stand-in): rows stay in the engine's pinned buffer
     int (*window_outbound_ips)(sg_handle, uint32_t*, size_t, size_t*) = nullptr;
+    int (*flush_window_top)(sg_handle, uint64_t, uint32_t, float, sg_edge_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;   // optional: SetSelection needs it
     const char* (*last_error)(sg_handle) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
@@ -102,6 +103,11 @@ public:
 
     // close the window: pending batches -> engine, K2..K5, rows -> sink.  Returns the number of edges or < 0.
     long FlushWindow(int64_t window_end_ms);
+    // From the next FlushWindow on, only the window's selected rows go to the sink, in selection order (sg_flush_window_top: k = 0
+    // every row scoring >= min_score in canonical order, else the k highest-scoring of them); FlushWindow still returns the
+    // window's edge count.  SG_EINVAL for k > SG_SELECT_MAX_K or an engine without sg_flush_window_top.  ClearSelection: all rows.
+    int SetSelection(uint32_t k, float min_score);
+    void ClearSelection() { std::lock_guard<std::mutex> g(flush_mu_); select_ = false; }
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }
@@ -137,7 +143,8 @@ private:
     std::mutex pk_mu_;                                 // packer_ (labels, prepared statements, HPACK state), dto_labels_
     L7Packer packer_;
     std::unordered_map<std::string, uint32_t> dto_labels_;   // labels seen through the PersistRequest tap share the packer's id space
-    std::mutex flush_mu_;                              // one FlushWindow at a time
+    std::mutex flush_mu_;                              // one FlushWindow at a time; the selection below
+    bool select_ = false; uint32_t sel_k_ = 0; float sel_min_ = 0;
     std::atomic<uint64_t> offered_{0}, batches_dropped_{0}, engine_errors_{0};
 };
 

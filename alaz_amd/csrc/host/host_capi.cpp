@@ -25,6 +25,7 @@ struct MockEngine {
     std::vector<sg_event> events;
     std::vector<std::array<uint32_t, 3>> table_ops;   // {op: 1 upsert_pod 2 delete_pod 3 upsert_svc 4 delete_svc, ip, id}
     uint32_t label_count = 0; uint32_t flushes = 0; uint32_t max_known = 0x3FFFFFFFu;
+    uint32_t top_flushes = 0, top_k = 0; float top_min = 0;             // flush_window_top: calls, the last k and min_score
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
 };
 #define M_LOCK(h) std::lock_guard<std::mutex> _g(reinterpret_cast<MockEngine*>(h)->mu)
@@ -37,6 +38,12 @@ int m_delete_svc(sg_handle h, uint32_t ip) { M_LOCK(h); reinterpret_cast<MockEng
 int m_labels(sg_handle h, uint32_t n) { M_LOCK(h); reinterpret_cast<MockEngine*>(h)->label_count = n; return SG_OK; }
 int m_ingest(sg_handle h, const sg_event* ev, size_t n) { M_LOCK(h); auto* m = reinterpret_cast<MockEngine*>(h); m->events.insert(m->events.end(), ev, ev + n); return SG_OK; }
 int m_flush(sg_handle h, uint64_t, sg_edge_out*, size_t, size_t* n) { M_LOCK(h); reinterpret_cast<MockEngine*>(h)->flushes++; if (n) *n = 0; return SG_OK; }
+int m_flush_top(sg_handle h, uint64_t, uint32_t k, float min_score, sg_edge_out*, uint32_t*, size_t, size_t* n_sel, size_t* n) {
+    M_LOCK(h); auto* m = reinterpret_cast<MockEngine*>(h); m->top_flushes++; m->top_k = k; m->top_min = min_score;
+    if (n_sel) *n_sel = 0;
+    if (n) *n = 0;
+    return SG_OK;
+}
 int m_obips(sg_handle, uint32_t*, size_t, size_t* n) { if (n) *n = 0; return SG_OK; }
 const char* m_err(sg_handle) { return ""; }
 
@@ -119,7 +126,7 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->mock = true;
         c->api.create = m_create; c->api.destroy = m_destroy; c->api.upsert_pod = m_upsert_pod; c->api.delete_pod = m_delete_pod;
         c->api.upsert_service = m_upsert_svc; c->api.delete_service = m_delete_svc; c->api.set_label_count = m_labels; c->api.ingest = m_ingest;
-        c->api.flush_window = m_flush; c->api.window_outbound_ips = m_obips; c->api.last_error = m_err;
+        c->api.flush_window = m_flush; c->api.window_outbound_ips = m_obips; c->api.last_error = m_err; c->api.flush_window_top = m_flush_top;
     }
     if (c->api.create(cfg, &c->h) != SG_OK) return nullptr;        // no usable GPU => no GraphDS: there is no CPU fallback
     c->ds = std::make_unique<GraphDS>(&c->inner, c->api, c->h, &c->sink, cfg ? (size_t)cfg->max_edges : 1024, batch ? batch : 4096,
@@ -369,6 +376,9 @@ size_t sgh_graphds_sweep(void* g, int64_t now_ms, int send_alive) { auto* c = st
 
 size_t sgh_graphds_labels(void* g, char* buf, size_t cap) { return join_labels(static_cast<HostCtx*>(g)->ds->Labels(), buf, cap); }
 uint64_t sgh_graphds_dropped_parse(void* g) { return static_cast<HostCtx*>(g)->ds->Packer().DroppedParse(); }
+int sgh_graphds_set_selection(void* g, uint32_t k, float min_score) { return static_cast<HostCtx*>(g)->ds->SetSelection(k, min_score); }
+void sgh_graphds_clear_selection(void* g) { static_cast<HostCtx*>(g)->ds->ClearSelection(); }
+size_t sgh_graphds_sink_rows(void* g) { return static_cast<HostCtx*>(g)->sink.rows.size(); }   // rows the last sgh_graphds_flush handed to the sink
 void* sgh_graphds_engine(void* g) { return static_cast<HostCtx*>(g)->h; }
 // {events offered, batches dropped, engine errors, live node ids, requests / kafka events / alive connections / pods / services that reached the inner store}
 void sgh_graphds_counters(void* g, uint64_t out[9]) {
@@ -389,6 +399,13 @@ size_t sgh_mock_table_ops(void* g, uint32_t* out3, size_t cap) {
     const size_t k = std::min(cap, m->table_ops.size());
     for (size_t i = 0; i < k; i++) { out3[3 * i] = m->table_ops[i][0]; out3[3 * i + 1] = m->table_ops[i][1]; out3[3 * i + 2] = m->table_ops[i][2]; }
     return m->table_ops.size();
+}
+// the stand-in's flush counts {flush_window calls, flush_window_top calls, last k} and the last min_score
+void sgh_mock_flushes(void* g, uint32_t out[3], float* min_score) {
+    auto* c = static_cast<HostCtx*>(g); out[0] = out[1] = out[2] = 0; if (min_score) *min_score = 0;
+    if (!c->mock) return;
+    auto* m = reinterpret_cast<MockEngine*>(c->h); std::lock_guard<std::mutex> l(m->mu);
+    out[0] = m->flushes; out[1] = m->top_flushes; out[2] = m->top_k; if (min_score) *min_score = m->top_min;
 }
 uint32_t sgh_mock_label_count(void* g) { auto* c = static_cast<HostCtx*>(g); return c->mock ? reinterpret_cast<MockEngine*>(c->h)->label_count : 0; }
 

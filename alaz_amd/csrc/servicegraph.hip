@@ -24,6 +24,7 @@
 #include "join_host.hpp"
 #include "sg_plan.hpp"
 #include "sg_kernels.h"
+#include "sg_sel.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -120,6 +121,11 @@ struct sg_engine {
     std::vector<hipEvent_t> ev_pool;
     // sg_window_run_sharded: exchange buffers of the sharded window (allocated at the first call; world = cfg.world)
     struct Xchg { u32* ob_local = nullptr; u32* ob_all = nullptr; u32* req = nullptr; u32* serve = nullptr; float* rows_out = nullptr; float* rows_in = nullptr; u32 capp = 0, ob_stride = 0; } xc;
+    // K7, the selection (sg_sel.h): scratch allocated at the first selection (sg_plan.hpp plan_select), the host flushes' device
+    // staging grown on demand.  Selections on different streams share the scratch: each one waits for the previous one (ev).
+    struct Sel { sgplan::SelPlan plan; u32* keys = nullptr; u32* hist = nullptr; u32* blk = nullptr; u32* state = nullptr; u64* pairs = nullptr; u64* n = nullptr;
+                 sg_edge_out* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; u64* h_n = nullptr; hipEvent_t ev = nullptr; bool pending = false; } sel;
+    u64* last_ctr = nullptr; hipStream_t last_stream = nullptr;   // counters and stream of the window last_rows belongs to (sg_window_select)
 };
 
 namespace {
@@ -632,6 +638,61 @@ hipError_t lds_limit(size_t bytes, K... kernels) {
     return hipSuccess;
 }
 
+// ---- K7, the selection (engine lock held) ---------------------------------------------------------------------------------------
+// the scratch at the first selection; the device staging of the host flushes holds at least stage_rows rows
+int sel_reserve(sg_engine* e, u64 stage_rows) {
+    sg_engine::Sel& s = e->sel;
+    if (!s.keys) {
+        s.plan = sgplan::plan_select(e->cfg.max_edges, true);
+        const sgplan::SelPlan& p = s.plan;
+        char* b = nullptr;
+        HIP_TRY(e, hipMalloc((void**)&b, p.scratch_bytes));
+        e->allocs.push_back(b);
+        s.pairs = (u64*)b; b += p.pair_bytes;                                 // (the u64 arrays first: every offset stays 8-aligned)
+        s.n = (u64*)b; s.state = (u32*)(b + 8); b += p.state_bytes;
+        s.blk = (u32*)b; b += p.blk_bytes;
+        s.hist = (u32*)b; b += p.hist_bytes;
+        s.keys = (u32*)b;
+        HIP_TRY(e, hipHostMalloc((void**)&s.h_n, sizeof(u64)));
+        HIP_TRY(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+        HIP_TRY(e, lds_limit(sgplan::select_sort_lds(SG_SELECT_MAX_K), k7_sort));
+    }
+    if (stage_rows > s.stage_cap) {                                          // (no selection is in flight: every host flush synchronises)
+        if (s.stage) { hipFree(s.stage); hipFree(s.stage_idx); s.stage = nullptr; s.stage_idx = nullptr; s.stage_cap = 0; }
+        HIP_TRY(e, hipMalloc((void**)&s.stage, stage_rows * sizeof(sg_edge_out)));
+        HIP_TRY(e, hipMalloc((void**)&s.stage_idx, stage_rows * sizeof(u32)));
+        s.stage_cap = stage_rows;
+    }
+    return SG_OK;
+}
+
+// enqueue the selection on stream st: a.rows / a.ctr / a.n_host / a.out / a.out_idx / a.cap / a.n_out set by the caller
+int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_score) {
+    sg_engine::Sel& s = e->sel;
+    const u32 wgs = s.plan.wgs;
+    a.max_edges = e->cfg.max_edges; a.k = k; a.min_score = min_score;
+    a.keys = s.keys; a.hist = s.hist; a.blk = s.blk; a.state = s.state; a.pairs = s.pairs;
+    if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
+    hipLaunchKernelGGL(k7_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a);
+    if (k) {
+        for (u32 r = 0; r < 4; r++) {
+            if (r) hipLaunchKernelGGL(k7_hist, dim3(wgs), dim3(K7_THREADS), 0, st, a, r);
+            hipLaunchKernelGGL(k7_pick, dim3(1), dim3(K7_PICK_THREADS), 0, st, a, r, wgs);
+        }
+    }
+    hipLaunchKernelGGL(k7_count, dim3(wgs), dim3(K7_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k7_scan, dim3(1), dim3(K7_PICK_THREADS), 0, st, a, wgs);
+    hipLaunchKernelGGL(k7_scatter, dim3(wgs), dim3(K7_THREADS), 0, st, a);
+    if (k) {
+        const u32 n = sgplan::next_pow2(std::max<u64>(1, std::min<u64>(k, e->cfg.max_edges)));
+        hipLaunchKernelGGL(k7_sort, dim3(1), dim3(K7_PICK_THREADS), (size_t)n * 8, st, a, n);
+    }
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(s.ev, st));
+    s.pending = true;
+    return SG_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -868,6 +929,10 @@ int sg_destroy(sg_handle e) {
     if (e->h_ctr_pin) hipHostFree(e->h_ctr_pin);
     if (e->h_rows) hipHostFree(e->h_rows);
     if (e->h_rows_old) hipHostFree(e->h_rows_old);
+    if (e->sel.stage) hipFree(e->sel.stage);
+    if (e->sel.stage_idx) hipFree(e->sel.stage_idx);
+    if (e->sel.h_n) hipHostFree(e->sel.h_n);
+    if (e->sel.ev) hipEventDestroy(e->sel.ev);
     for (auto& r : e->trecs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto v : e->ev_pool) hipEventDestroy(v);
     if (e->tab_ev) hipEventDestroy(e->tab_ev);
@@ -1195,7 +1260,9 @@ int sg_window_reset(sg_handle e, void* stream) {
 //                 of copy per C3 window: every feeder thread stood still for a quarter of the window period.)
 // sg_flush_window / sg_flush_window_view = begin + end, for callers with one thread.
 namespace {
-int flush_begin_locked(sg_engine* e, std::unique_lock<std::mutex>& g) {
+// rows_to_host = false (sg_flush_window_top): where the reset is its own launch, the counters and outbound IPs are read here but
+// the rows stay on the device for the selection (the reset and the next window's K1 do not write them; only the next close does)
+int flush_begin_locked(sg_engine* e, std::unique_lock<std::mutex>& g, bool rows_to_host = true) {
     // One boundary at a time: `closing` is also the "a begin is in progress" flag — the wait for the staging copies below releases the
     // engine lock, and a second flusher that got in there used to pass the flush_open test too, close the NEXT window and rewrite the
     // rows / counters the first one's unlocked fetch was reading.  It waits here instead and then sees flush_open.
@@ -1219,7 +1286,7 @@ int flush_begin_locked(sg_engine* e, std::unique_lock<std::mutex>& g) {
         e->flush_async = true;
     } else {                                                             // (variant 1: the reset is its own launch and must follow the read)
         size_t n = 0; const sg_edge_out* v = nullptr;
-        if ((rc = do_read(e, nullptr, 0, &n, &v))) return rc;
+        if ((rc = do_read(e, nullptr, 0, &n, rows_to_host ? &v : nullptr))) return rc;
         if ((rc = do_reset(e, s))) return rc;
         e->flush_async = false;
     }
@@ -1265,6 +1332,57 @@ int flush_end_unlocked(sg_engine* e, std::unique_lock<std::mutex>& g, sg_edge_ou
     if (view) *view = e->h_rows;
     return SG_OK;
 }
+// flush_end_unlocked with the selection: it runs on the read stream behind the window's score kernel (or, where begin already read the
+// counters under the lock, behind its device sync), and only the selected rows, their indices and one count cross PCIe
+int flush_end_top_unlocked(sg_engine* e, std::unique_lock<std::mutex>& g, u32 k, float min_score, sg_edge_out* out, u32* row_index,
+                           size_t cap, size_t* n_selected, size_t* n_edges) {
+    e->cv.wait(g, [&] { return !e->fetching; });
+    if (!e->flush_open) { e->err = "sg_flush_end_top without sg_flush_begin"; return SG_ESTATE; }
+    const u64 ME = e->cfg.max_edges;
+    const u64 stage = std::min<u64>(cap, k ? std::min<u64>(k, ME) : ME);   // rows the selection writes at most
+    { const int rc = sel_reserve(e, std::max<u64>(stage, 1)); if (rc) return rc; }
+    const sg_edge_out* d_rows = e->fl_rows; const u32* d_ob = e->fl_ob;
+    const bool async = e->flush_async;
+    size_t E = async ? 0 : (size_t)e->h_ctr[C_N_EDGES];                   // (not async: begin has read the counters and the outbound IPs)
+    e->fetching = true;                                                  // claimed: the fetch below runs without the engine lock
+    g.unlock();
+    int rc = SG_OK; std::string err;
+    std::vector<u32> obips;
+    u64 m = 0;
+    do {
+        size_t nob = 0;
+        if (async) {
+            if (hipEventSynchronize(e->score_ev) != hipSuccess) { err = "hipEventSynchronize (window pipeline)"; rc = SG_ENODEV; break; }
+            E = (size_t)e->h_ctr_pin[C_N_EDGES];
+            nob = (size_t)e->h_ctr_pin[C_N_OBIP];
+        }
+        SelArgs a{};
+        a.rows = d_rows; a.ctr = nullptr; a.n_host = E;
+        a.out = e->sel.stage; a.out_idx = e->sel.stage_idx; a.cap = stage; a.n_out = e->sel.n;
+        g.lock(); rc = launch_select(e, e->rd_stream, a, k, min_score); g.unlock();
+        if (rc) break;
+        if (hipMemcpyAsync(e->sel.h_n, e->sel.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream) != hipSuccess) { err = "hipMemcpyAsync (selected count)"; rc = SG_ENODEV; break; }
+        obips.resize(nob);
+        if (nob && hipMemcpyAsync(obips.data(), d_ob, nob * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream) != hipSuccess) { err = "hipMemcpyAsync (outbound ips)"; rc = SG_ENODEV; break; }
+        if (hipStreamSynchronize(e->rd_stream) != hipSuccess) { err = "hipStreamSynchronize (read stream)"; rc = SG_ENODEV; break; }
+        m = *e->sel.h_n;
+        const size_t take = (size_t)std::min<u64>(m, stage);
+        if (out && take && hipMemcpyAsync(out, e->sel.stage, take * sizeof(sg_edge_out), hipMemcpyDeviceToHost, e->rd_stream) != hipSuccess) { err = "hipMemcpyAsync (rows)"; rc = SG_ENODEV; break; }
+        if (row_index && take && hipMemcpyAsync(row_index, e->sel.stage_idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream) != hipSuccess) { err = "hipMemcpyAsync (row indices)"; rc = SG_ENODEV; break; }
+        if (hipStreamSynchronize(e->rd_stream) != hipSuccess) { err = "hipStreamSynchronize (read stream)"; rc = SG_ENODEV; break; }
+    } while (0);
+    g.lock();
+    e->fetching = false; e->flush_open = false; e->cv.notify_all();
+    if (rc) { if (!err.empty()) e->err = err; return rc; }
+    if (async) {
+        std::memcpy(e->h_ctr, e->h_ctr_pin, sizeof(e->h_ctr));
+        e->last_obips.swap(obips);
+        account_window(e);
+    }
+    if (n_selected) *n_selected = (size_t)m;
+    if (n_edges) *n_edges = E;
+    return SG_OK;
+}
 }  // namespace
 
 int sg_flush_begin(sg_handle e, uint64_t window_end_ms) {
@@ -1298,6 +1416,32 @@ int sg_flush_window_view(sg_handle e, uint64_t window_end_ms, const sg_edge_out*
     e->cv.wait(g, [&] { return !e->closing && !e->flush_open; });
     if (const int rc = flush_begin_locked(e, g)) return rc;
     return flush_end_unlocked(e, g, nullptr, 0, n, rows);
+}
+int sg_flush_end_top(sg_handle e, uint32_t k, float min_score, sg_edge_out* out, uint32_t* row_index, size_t cap, size_t* n_selected, size_t* n_edges) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    return flush_end_top_unlocked(e, g, k, min_score, out, row_index, cap, n_selected, n_edges);
+}
+int sg_flush_window_top(sg_handle e, uint64_t window_end_ms, uint32_t k, float min_score, sg_edge_out* out, uint32_t* row_index, size_t cap,
+                        size_t* n_selected, size_t* n_edges) {
+    (void)window_end_ms;
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    e->cv.wait(g, [&] { return !e->closing && !e->flush_open; });
+    if (const int rc = flush_begin_locked(e, g, false)) return rc;
+    return flush_end_top_unlocked(e, g, k, min_score, out, row_index, cap, n_selected, n_edges);
+}
+// the rows sg_window_rows_buffer names, selected on the device into caller memory; E from that window's counters on the device
+int sg_window_select(sg_handle e, uint32_t k, float min_score, sg_edge_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n, void* stream) {
+    if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = sel_reserve(e, 0)) return rc;
+    SelArgs a{};
+    a.rows = e->last_rows ? e->last_rows : e->d.rows;
+    a.ctr = e->last_rows ? e->last_ctr : e->d.ctr;
+    a.out = d_out; a.out_idx = d_index; a.cap = cap; a.n_out = reinterpret_cast<u64*>(d_n);
+    hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
+    return launch_select(e, s, a, k, min_score);
 }
 
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.
@@ -1449,7 +1593,7 @@ int sg_window_run_sharded(sg_handle e, sg_comm* c, void* stream) {
     const int rc = sg_run_sharded_window(&st, &sc);
     if (rc) { if (e->err.empty()) e->err = "sg_window_run_sharded: a stage or a collective failed"; return rc; }
     window_timed_end(e, s);
-    e->last_rows = e->d.rows;
+    e->last_rows = e->d.rows; e->last_ctr = e->d.ctr; e->last_stream = s;
     return SG_OK;
 }
 
@@ -1475,7 +1619,7 @@ int sg_window_run(sg_handle e, void* stream) {
     if ((rc = do_score(e, s, true, true, &did))) return rc;
     if (did) e->closed = false; else if ((rc = do_reset(e, s))) return rc;
     window_timed_end(e, s);
-    e->last_rows = e->d.rows;
+    e->last_rows = e->d.rows; e->last_ctr = e->d.ctr; e->last_stream = s;
     rotate_window(e);                                    // the next sg_ingest* goes to the next slot (if any)
     return SG_OK;
 }

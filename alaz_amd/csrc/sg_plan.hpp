@@ -354,6 +354,36 @@ inline bool plan_pass_a(const Plan& p, uint32_t l1_entries, size_t l2_bytes, con
     return true;
 }
 
+// K7, the selection (sg_sel.h): its scratch and grids.  Allocated at an engine's first selection: an engine that never selects
+// asks for nothing (used = false).  Rows are split into `wgs` contiguous spans of at least 2048 (eight rows per lane of a 256-thread
+// workgroup, two such workgroups per CU at 1 M edges); k7_scan scans one count per thread of one 1024-thread workgroup.
+constexpr u32 kSelThreads = 256, kSelMaxWgs = 1024, kSelRowsPerWg = 2048, kSelStateWords = 8;
+struct SelPlan {
+    u32 wgs = 0;                  // workgroups of k7_keys / k7_hist / k7_count / k7_scatter
+    u64 key_bytes = 0;            // one u32 key per row: max_edges
+    u64 hist_bytes = 0;           // [wgs][256] u32
+    u64 blk_bytes = 0;            // [wgs][4] u32
+    u64 pair_bytes = 0;           // [SG_SELECT_MAX_K] u64 (top-k)
+    u64 state_bytes = 0;          // k7 state words + the selected count (u64)
+    u64 scratch_bytes = 0;        // all of the above: what sg_window_select needs
+    u64 stage_rows = 0;           // device staging of the host flushes' rows: threshold mode may select every row
+};
+inline SelPlan plan_select(u64 max_edges, bool used) {
+    SelPlan s;
+    if (!used) return s;
+    s.wgs = (u32)std::max<u64>(1, std::min<u64>(kSelMaxWgs, (max_edges + kSelRowsPerWg - 1) / kSelRowsPerWg));
+    s.key_bytes = max_edges * 4;
+    s.hist_bytes = (u64)s.wgs * 256 * 4;
+    s.blk_bytes = (u64)s.wgs * 4 * 4;
+    s.pair_bytes = (u64)SG_SELECT_MAX_K * 8;
+    s.state_bytes = kSelStateWords * 4 + 8;
+    s.scratch_bytes = s.key_bytes + s.hist_bytes + s.blk_bytes + s.pair_bytes + s.state_bytes;
+    s.stage_rows = max_edges;
+    return s;
+}
+// k7_sort's LDS: the selected (key, index) pairs padded to a power of two, 8 bytes each
+inline size_t select_sort_lds(u32 k) { return (size_t)next_pow2(std::max<u32>(k, 1)) * 8; }
+
 // the plan's share of the kernels' argument (Dev, sg_device.h; a template so that the CPU test can fill a struct of the same names)
 template <class D>
 void plan_to_dev(const Plan& p, const sg_config& cfg, D& d) {

@@ -25,6 +25,7 @@ DEV_KNOBS = ("SG_ABLATE", "SG_NP", "SG_HT", "SG_CT", "SG_NWG", "SG_NSUB", "SG_SP
              "SG_COPY_STREAMS", "SG_STAGE_SLOTS", "SG_ARENA")
 
 SG_OK, SG_EINVAL, SG_ENOMEM, SG_ENODEV, SG_ENOSPC, SG_EAGAIN, SG_ESTATE = 0, -22, -12, -19, -28, -11, -71
+SELECT_MAX_K = 16384      # SG_SELECT_MAX_K: the largest k of a top-k selection
 F_IN, F_HID, F_EDGE = 32, 64, 8
 STAT_SUM_WORDS, STAT_MAX_WORDS = 12, 2
 REF_KNOWN, REF_LABEL, REF_OBIP = 0, 1, 2
@@ -41,6 +42,7 @@ EXPORTS = [
     "sg_halo_pack_padded", "sg_halo_unpack_padded", "sg_window_outbound_ips", "sg_stats_get",
     "sg_timing_enable", "sg_timing_reset", "sg_timing_get", "sg_timing_samples", "sg_timing_stride", "sg_latency_probe", "sg_set_warm", "sg_debug_stamps", "sg_route", "sg_window_hist", "sg_geometry_get",
     "sg_clock_probe", "sg_comm_probe", "sg_window_halo_counts", "sg_comm_unique_id", "sg_comm_create", "sg_comm_destroy", "sg_window_run_sharded", "sg_host_register", "sg_host_unregister", "sg_ingest_pinned", "sg_ingest_bulk",
+    "sg_flush_window_top", "sg_flush_end_top", "sg_window_select",
 ]
 
 
@@ -167,6 +169,9 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_comm_destroy": (C.c_int, [P]), "sg_window_run_sharded": (C.c_int, [H, P, P]),
         "sg_host_register": (C.c_int, [H, P, sz]), "sg_host_unregister": (C.c_int, [H, P]), "sg_ingest_pinned": (C.c_int, [H, P, sz]),
         "sg_ingest_bulk": (C.c_int, [H, P, sz, C.c_int, C.POINTER(u64)]),
+        "sg_flush_window_top": (C.c_int, [H, u64, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "sg_flush_end_top": (C.c_int, [H, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "sg_window_select": (C.c_int, [H, u32, C.c_float, P, P, sz, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -338,6 +343,30 @@ class ServiceGraph:
         out = np.zeros(cap, dtype=EDGE_OUT_DTYPE); n = C.c_size_t(0)
         self._ck(self._l.sg_flush_end(self._h, out.ctypes.data, cap, C.byref(n)))
         return out[: min(n.value, cap)]
+
+    # ---- selection (K7): only the selected rows leave the device ----
+    def _top(self, call, k: int, cap: Optional[int]):
+        cap = (k if k else self.max_edges) if cap is None else cap
+        out = np.zeros(cap, dtype=EDGE_OUT_DTYPE); idx = np.zeros(cap, dtype=np.uint32)
+        ns, ne = C.c_size_t(0), C.c_size_t(0)
+        self._ck(call(out.ctypes.data, idx.ctypes.data, cap, C.byref(ns), C.byref(ne)))
+        m = min(ns.value, cap)
+        return out[:m], idx[:m], ne.value
+
+    def flush_window_top(self, k: int, min_score: float = float("-inf"), window_end_ms: int = 0, cap: Optional[int] = None):
+        """Close the window and return (rows, row_index, n_edges) of its selection (sg_flush_window_top): k = 0 every row with
+        score >= min_score in canonical order, else the k highest-scoring such rows, descending, ties by row position.  cap
+        defaults to k (k > 0) or max_edges; rows beyond it are counted, not returned."""
+        return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_window_top(self._h, window_end_ms, k, min_score, o, i, c, ns, ne), k, cap)
+
+    def flush_end_top(self, k: int, min_score: float = float("-inf"), cap: Optional[int] = None):
+        """flush_window_top for the window flush_begin closed (sg_flush_end_top)."""
+        return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_end_top(self._h, k, min_score, o, i, c, ns, ne), k, cap)
+
+    def window_select(self, k: int, min_score: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
+        """Select from the rows of the window window_run closed last into device memory (sg_window_select): d_out [cap] rows,
+        d_index [cap] u32 (0 = none), d_n one u64 = rows selected; enqueued on `stream` (0 = that window's stream)."""
+        self._ck(self._l.sg_window_select(self._h, k, min_score, d_out or None, d_index or None, cap, d_n, stream or None))
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

@@ -92,6 +92,8 @@ def load() -> C.CDLL:
             "sgh_crc32": (u32, [C.c_int, C.c_char_p, sz]), "sgh_xxh32": (u32, [C.c_char_p, sz, u32]),
             "sgh_graphds_create2": (P, [C.c_char_p, P, sz, C.c_int]), "sgh_graphds_counters": (None, [P, P]),
             "sgh_mock_events": (sz, [P, P, sz]), "sgh_mock_table_ops": (sz, [P, P, sz]), "sgh_mock_label_count": (u32, [P]),
+            "sgh_graphds_set_selection": (C.c_int, [P, u32, C.c_float]), "sgh_graphds_clear_selection": (None, [P]), "sgh_graphds_sink_rows": (sz, [P]),
+            "sgh_mock_flushes": (None, [P, P, C.POINTER(C.c_float)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -378,6 +380,32 @@ class GraphDS:
             d[(r.from_type.decode(), r.from_uid.decode(), r.to_type.decode(), r.to_uid.decode())] = (
                 r.count, r.err_count, r.sum_ns, r.max_ns, r.sumsq_us, r.score, r.lat_z, r.err_ratio, r.alive, r.p50_us, r.p99_us)
         return d
+
+    def FlushWindowRows(self, window_end_ms: int = 0):
+        """FlushWindow as (n_edges, [(from_type, from_uid, to_type, to_uid, count, err_count, sum_ns, max_ns, sumsq_us, score, lat_z,
+        err_ratio, alive, p50_us, p99_us), ...]) in the order the sink received the rows."""
+        out = (EdgeRowC * self.max_edges)()
+        n = self._l.sgh_graphds_flush(self._g, window_end_ms, out, self.max_edges)
+        if n < 0:
+            raise RuntimeError(f"FlushWindow rc={n}")
+        rows = []
+        for i in range(min(self._l.sgh_graphds_sink_rows(self._g), self.max_edges)):
+            r = out[i]
+            rows.append((r.from_type.decode(), r.from_uid.decode(), r.to_type.decode(), r.to_uid.decode(), r.count, r.err_count, r.sum_ns,
+                         r.max_ns, r.sumsq_us, r.score, r.lat_z, r.err_ratio, r.alive, r.p50_us, r.p99_us))
+        return n, rows
+
+    def set_selection(self, k: int, min_score: float = float("-inf")) -> int:
+        """GraphDS::SetSelection: from the next FlushWindow on only the selected rows reach the sink (rc, SG_EINVAL for k > 16384)."""
+        return self._l.sgh_graphds_set_selection(self._g, k, min_score)
+
+    def clear_selection(self): self._l.sgh_graphds_clear_selection(self._g)
+
+    def mock_flushes(self) -> dict:
+        """the stand-in engine's flush calls: plain ones, flush_window_top ones, and the last k / min_score it received"""
+        a = (C.c_uint32 * 3)(); f = C.c_float(0)
+        self._l.sgh_mock_flushes(self._g, a, C.byref(f))
+        return {"flush_window": a[0], "flush_window_top": a[1], "k": a[2], "min_score": f.value}
 
     # ---- f-2: TCP connect events -> socket lines -> alive connections ----
     def tcp_wire(self, recs: bytes) -> int:

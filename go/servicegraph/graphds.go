@@ -101,6 +101,11 @@ type GraphDS struct {
 	next    atomic.Uint32
 	flushMu sync.Mutex
 
+	maxEdges int     // sg_config.max_edges
+	selOn    bool    // SetSelection (under flushMu): FlushWindow returns the selected rows only
+	selK     uint32
+	selMin   float32
+
 	EngineErrors   atomic.Uint64 // SG_ENOSPC and friends from the engine (the inner store still got the call)
 	BatchesDropped atomic.Uint64 // SG_EAGAIN: staging ring full, batch dropped and counted by the engine
 	// Filter, when set, is asked before an event of the early tap (IngestL7) is packed: the aggregator's own
@@ -146,7 +151,7 @@ func New(inner datastore.DataStore, c Config) (*GraphDS, error) {
 		cfg.flags |= C.SG_CFG_EDGE_HISTOGRAM
 	}
 	g := &GraphDS{inner: inner, divert: c.Divert, ids: map[string]uint32{}, podIP: map[uint32]uint32{}, svcIP: map[uint32]uint32{},
-		labels: map[string]uint32{}, maxKnown: c.MaxKnownNodes}
+		labels: map[string]uint32{}, maxKnown: c.MaxKnownNodes, maxEdges: int(c.MaxEdges)}
 	if rc := C.sg_create(&cfg, &g.h); rc != 0 {
 		return nil, fmt.Errorf("servicegraph: sg_create = %d (no usable gfx950 device, or bad config)", int(rc))
 	}
@@ -552,6 +557,25 @@ func (g *GraphDS) IngestHttp2(d *l7_req.L7Event, req *datastore.Request, authori
 
 // FlushWindow closes the window: K1 pass B .. K5 on the GPU, rows left in the engine's page-locked host buffer
 // (sg_flush_begin + sg_flush_end_view: valid until the next flush, so they are converted before this returns).
+// SetSelection: from the next FlushWindow on, only the window's selected rows are returned, in selection order — k = 0 every row
+// scoring >= minScore in canonical order, 1 <= k <= SG_SELECT_MAX_K the k highest-scoring of them, descending (sg_flush_window_top).
+// Only those rows cross PCIe.  ClearSelection returns to every row.
+func (g *GraphDS) SetSelection(k uint32, minScore float32) error {
+	if k > C.SG_SELECT_MAX_K {
+		return fmt.Errorf("servicegraph: selection k = %d beyond SG_SELECT_MAX_K", k)
+	}
+	g.flushMu.Lock()
+	g.selOn, g.selK, g.selMin = true, k, minScore
+	g.flushMu.Unlock()
+	return nil
+}
+
+func (g *GraphDS) ClearSelection() {
+	g.flushMu.Lock()
+	g.selOn = false
+	g.flushMu.Unlock()
+}
+
 func (g *GraphDS) FlushWindow(windowEndMs int64) ([]EdgeRow, error) {
 	g.flushMu.Lock()
 	defer g.flushMu.Unlock()
@@ -575,11 +599,27 @@ func (g *GraphDS) FlushWindow(windowEndMs int64) ([]EdgeRow, error) {
 	// (add -> flushShard) go on while the rows come back — they belong to the next window.
 	var rows *C.sg_edge_out
 	var n C.size_t
-	if rc := C.sg_flush_begin(g.h, C.uint64_t(windowEndMs)); rc != 0 {
-		return nil, fmt.Errorf("servicegraph: sg_flush_begin = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
-	}
-	if rc := C.sg_flush_end_view(g.h, &rows, &n); rc != 0 {
-		return nil, fmt.Errorf("servicegraph: sg_flush_end_view = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	if g.selOn { // the selection: only the selected rows leave the device, copied into memory of this call
+		capRows := int(g.selK)
+		if capRows == 0 || capRows > g.maxEdges {
+			capRows = g.maxEdges
+		}
+		buf := make([]C.sg_edge_out, capRows+1)
+		var nsel C.size_t
+		if rc := C.sg_flush_window_top(g.h, C.uint64_t(windowEndMs), C.uint32_t(g.selK), C.float(g.selMin), &buf[0], nil, C.size_t(capRows), &nsel, &n); rc != 0 {
+			return nil, fmt.Errorf("servicegraph: sg_flush_window_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		rows, n = &buf[0], nsel
+		if int(n) > capRows {
+			n = C.size_t(capRows)
+		}
+	} else {
+		if rc := C.sg_flush_begin(g.h, C.uint64_t(windowEndMs)); rc != 0 {
+			return nil, fmt.Errorf("servicegraph: sg_flush_begin = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		if rc := C.sg_flush_end_view(g.h, &rows, &n); rc != 0 {
+			return nil, fmt.Errorf("servicegraph: sg_flush_end_view = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
 	}
 	var nob C.size_t
 	C.sg_window_outbound_ips(g.h, nil, 0, &nob)

@@ -293,6 +293,27 @@ int sg_flush_window(sg_handle h, uint64_t window_end_ms, sg_edge_out* out, size_
  * (a Go shim building its payload, GraphDS::FlushWindow): a pageable 64 MB destination costs more than the transfer. */
 int sg_flush_window_view(sg_handle h, uint64_t window_end_ms, const sg_edge_out** rows, size_t* n);
 
+/* ---- selection (K7): only the window's most anomalous rows leave the device ---------------------------------------------- *
+ * Candidates are the rows with score >= min_score (a plain float comparison: a NaN score is never one; -INFINITY admits every
+ * other row).  k == 0: every candidate, in canonical order.  1 <= k <= SG_SELECT_MAX_K: the min(k, candidates) highest-scoring
+ * candidates, descending by score, equal scores (-0.0 == +0.0) by ascending canonical position.  k > SG_SELECT_MAX_K: SG_EINVAL
+ * before anything is enqueued or any window is closed.  Each row is byte-identical to the one sg_flush_window returns at that
+ * position; row_index[j] (may be NULL) = that position.  *n_selected = rows selected (may exceed cap; then only cap rows and
+ * indices were written), *n_edges = edges of the window.  The engine's state afterwards — sg_stats, sg_window_outbound_ips,
+ * sg_window_hist, the kept warm state — is exactly what a plain flush of the window leaves.                                      */
+#define SG_SELECT_MAX_K 16384u
+int sg_flush_window_top(sg_handle h, uint64_t window_end_ms, uint32_t k, float min_score,
+                        sg_edge_out* out, uint32_t* row_index, size_t cap, size_t* n_selected, size_t* n_edges);
+/* sg_flush_end with the selection: ends the window sg_flush_begin closed.                                                    */
+int sg_flush_end_top(sg_handle h, uint32_t k, float min_score,
+                     sg_edge_out* out, uint32_t* row_index, size_t cap, size_t* n_selected, size_t* n_edges);
+/* Device-resident form for sg_window_run drivers: selects from the rows sg_window_rows_buffer names (the window sg_window_run
+ * closed last, whichever slot it ran on) into caller-owned device memory — d_out [cap] rows, d_index [cap] u32 (may be NULL),
+ * *d_n (u64) = rows selected — enqueued on `stream` (NULL = the stream that window ran on), no host sync.  Enqueue it behind that
+ * window's sg_window_run and before the slot's next ingest.                                                                   */
+int sg_window_select(sg_handle h, uint32_t k, float min_score, sg_edge_out* d_out, uint32_t* d_index,
+                     size_t cap, uint64_t* d_n, void* stream);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
