@@ -25,6 +25,7 @@
 #include "sg_plan.hpp"
 #include "sg_kernels.h"
 #include "sg_sel.h"
+#include "sg_trend.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -126,6 +127,11 @@ struct sg_engine {
     struct Sel { sgplan::SelPlan plan; u32* keys = nullptr; u32* hist = nullptr; u32* blk = nullptr; u32* state = nullptr; u64* pairs = nullptr; u64* n = nullptr;
                  sg_edge_out* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; u64* h_n = nullptr; hipEvent_t ev = nullptr; bool pending = false; } sel;
     u64* last_ctr = nullptr; hipStream_t last_stream = nullptr;   // counters and stream of the window last_rows belongs to (sg_window_select)
+    // K8, the per-edge baselines (sg_trend.h): allocated at sg_set_trend (sg_plan.hpp plan_trend), one allocation.  The baseline is
+    // engine-wide: every update waits for the previous one (ev), whichever slot's stream it runs on.  w = trend windows enqueued.
+    struct Trend { bool on = false; sg_trend_params p{}; sgplan::TrendPlan plan; char* mem = nullptr; TrendSoA buf[2] = {}; u64* ctl = nullptr; u32* blk = nullptr;
+                   K8Thread* th = nullptr; std::vector<sg_edge_trend*> rows; u32 w = 0; hipEvent_t ev = nullptr; bool pending = false; int run_slot = -1;
+                   sg_edge_trend* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; } trend;
 };
 
 namespace {
@@ -530,23 +536,60 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
     return SG_OK;
 }
 
+// ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
+// enqueue window w's update on stream s behind the previous update (any stream); the window's trend rows go to the slot's buffer
+int launch_trend(sg_engine* e, hipStream_t s) {
+    sg_engine::Trend& t = e->trend;
+    const sg_trend_params& p = t.p;
+    TrendArgs a{};
+    a.rows = e->d.rows; a.ctr = e->d.ctr; a.ob_sorted = e->d.ob_sorted; a.max_obip = e->d.max_obip;
+    a.max_edges = e->cfg.max_edges; a.cap = t.plan.entries;
+    a.buf[0] = t.buf[0]; a.buf[1] = t.buf[1];
+    a.out = t.rows[e->cur]; a.th = t.th; a.blk = t.blk; a.ctl = t.ctl;
+    a.w = t.w + 1; a.warmup = p.warmup; a.ttl = p.ttl;
+    a.alpha = std::ldexp(1.0, -(int)p.shift); a.lat_floor = (double)p.lat_floor_ns; a.err_floor = (double)p.err_floor;
+    if (t.pending) HIP_TRY(e, hipStreamWaitEvent(s, t.ev, 0));
+    hipLaunchKernelGGL(k8_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs);
+    hipLaunchKernelGGL(k8_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(t.ev, s));
+    t.pending = true;
+    t.w++;
+    return SG_OK;
+}
+void free_trend(sg_engine* e) {
+    sg_engine::Trend& t = e->trend;
+    if (t.mem || t.stage) hipDeviceSynchronize();
+    if (t.mem) hipFree(t.mem);
+    if (t.stage) hipFree(t.stage);
+    if (t.stage_idx) hipFree(t.stage_idx);
+    if (t.ev) hipEventDestroy(t.ev);
+    t = sg_engine::Trend{};
+}
+
 // proj_done: the last SAGE layer already wrote P and Q.  fuse_reset: fold the window reset into the
 // score kernel (unsharded variant-0 pipelines; saves a launch) — returns true through *did_reset.
 int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool* did_reset) {
     const Dev& d = e->d;
     if (!e->have_w) { e->err = "sg_load_weights not called"; return SG_ESTATE; }
     const float* Wh = e->d_W + layer_offset(e->cfg.layers);
-    Timed t(e, s, 5);
-    if (!(proj_done && d.world == 1)) {
-        if (e->plan.use_mfma) hipLaunchKernelGGL((k5_node_proj<true>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
-        else hipLaunchKernelGGL((k5_node_proj<false>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
-    }
     const bool fr = fuse_reset && d.variant == 0;
-    const int g5 = (int)e->plan.k5_grid;                    // one round of workgroups (sg_plan.hpp)
-    if (fr) hipLaunchKernelGGL(k5_edge_score<true>, dim3(g5), dim3(256), 0, s, d, Wh);
-    else hipLaunchKernelGGL(k5_edge_score<false>, dim3(g5), dim3(256), 0, s, d, Wh);
+    {
+        Timed t(e, s, 5);
+        if (!(proj_done && d.world == 1)) {
+            if (e->plan.use_mfma) hipLaunchKernelGGL((k5_node_proj<true>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
+            else hipLaunchKernelGGL((k5_node_proj<false>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
+        }
+        const int g5 = (int)e->plan.k5_grid;                // one round of workgroups (sg_plan.hpp)
+        if (fr) hipLaunchKernelGGL(k5_edge_score<true>, dim3(g5), dim3(256), 0, s, d, Wh);
+        else hipLaunchKernelGGL(k5_edge_score<false>, dim3(g5), dim3(256), 0, s, d, Wh);
+    }
     if (did_reset) *did_reset = fr;
     HIP_TRY(e, hipGetLastError());
+    // K8 right behind K5: every pipeline scores here.  The rows, the counters and the outbound-IP list survive K5's fused reset and
+    // the separate one (sg_k5.h, sg_k3.h k_reset_window), and the next window's K1 queues behind K8 on this stream.
+    if (e->trend.on) return launch_trend(e, s);
     return SG_OK;
 }
 
@@ -933,6 +976,7 @@ int sg_destroy(sg_handle e) {
     if (e->sel.stage_idx) hipFree(e->sel.stage_idx);
     if (e->sel.h_n) hipHostFree(e->sel.h_n);
     if (e->sel.ev) hipEventDestroy(e->sel.ev);
+    free_trend(e);
     for (auto& r : e->trecs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto v : e->ev_pool) hipEventDestroy(v);
     if (e->tab_ev) hipEventDestroy(e->tab_ev);
@@ -1444,6 +1488,117 @@ int sg_window_select(sg_handle e, uint32_t k, float min_score, sg_edge_out* d_ou
     return launch_select(e, s, a, k, min_score);
 }
 
+// ---- K8, the per-edge baselines ------------------------------------------------------------------------------------------------
+int sg_set_trend(sg_handle e, const sg_trend_params* p) {
+    if (!e) return SG_EINVAL;
+    sg_trend_params r{};
+    if (p && sgplan::check_trend(*p, e->cfg.max_edges, &r)) { e->err = "sg_set_trend: bad parameters"; return SG_EINVAL; }
+    std::unique_lock<std::mutex> g(e->mu);
+    if (e->closing || e->flush_open) { e->err = "sg_set_trend while a flush is open"; return SG_ESTATE; }
+    free_trend(e);
+    if (!p) return SG_OK;
+    sg_engine::Trend& t = e->trend;
+    t.p = r;
+    t.plan = sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r);
+    const sgplan::TrendPlan& P = t.plan;
+    HIP_TRY(e, hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+    {
+        const hipError_t rc = hipMalloc((void**)&t.mem, P.total_bytes);
+        if (rc != hipSuccess) { free_trend(e); e->err = std::string("sg_set_trend: hipMalloc: ") + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
+    }
+    HIP_TRY(e, hipMemset(t.mem, 0, P.total_bytes));                  // an empty baseline (B = 0 for both parities), zero statistics and rows
+    const u64 C = P.entries;
+    char* b = t.mem;
+    for (int k = 0; k < 2; k++) {                                     // (the u64 / fp64 arrays first: every offset stays 8-aligned)
+        TrendSoA& x = t.buf[k];
+        char* q = b;
+        x.from_key = (u64*)q; q += C * 8; x.to_key = (u64*)q; q += C * 8;
+        x.lat_mean = (double*)q; q += C * 8; x.lat_dev = (double*)q; q += C * 8; x.err_mean = (double*)q; q += C * 8; x.err_dev = (double*)q; q += C * 8;
+        x.n = (u32*)q; q += C * 4; x.last = (u32*)q;
+        b += P.soa_bytes;
+    }
+    t.ctl = (u64*)b; b += P.ctl_bytes;
+    t.blk = (u32*)b; b += P.blk_bytes;
+    t.th = (K8Thread*)b; b += P.thread_bytes;
+    for (size_t k = 0; k < e->slots.size(); k++) { t.rows.push_back((sg_edge_trend*)b); b += P.rows_bytes; }
+    t.on = true;
+    return SG_OK;
+}
+int sg_window_trend(sg_handle e, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::Trend& t = e->trend;
+    if (!t.on) { e->err = "sg_window_trend: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    const size_t E = (size_t)e->h_ctr[C_N_EDGES];                      // of the last read window
+    const sg_edge_trend* src = t.rows[e->cur];
+    if (!row_index) {
+        if (n) *n = E;
+        const size_t take = std::min(E, cap);
+        if (out && take) { if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev)); HIP_TRY(e, hipMemcpy(out, src, take * sizeof(sg_edge_trend), hipMemcpyDeviceToHost)); }
+        return SG_OK;
+    }
+    for (size_t k = 0; k < n_index; k++) if (row_index[k] >= E) { e->err = "sg_window_trend: a row index beyond the window's edges"; return SG_EINVAL; }
+    if (n) *n = n_index;
+    const size_t take = std::min(n_index, cap);
+    if (!out || !take) return SG_OK;
+    if (take > t.stage_cap) {
+        if (t.stage) { hipFree(t.stage); hipFree(t.stage_idx); t.stage = nullptr; t.stage_idx = nullptr; t.stage_cap = 0; }
+        const size_t want = std::max<size_t>(take, 1024);
+        HIP_TRY(e, hipMalloc((void**)&t.stage, want * sizeof(sg_edge_trend)));
+        HIP_TRY(e, hipMalloc((void**)&t.stage_idx, want * sizeof(u32)));
+        t.stage_cap = want;
+    }
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    HIP_TRY(e, hipMemcpyAsync(t.stage_idx, row_index, take * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
+    hipLaunchKernelGGL(k8_gather, dim3((unsigned)((take + 255) / 256)), dim3(256), 0, e->rd_stream, (const sg_edge_trend*)src, (const u32*)t.stage_idx, (u64)take, t.stage);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(out, t.stage, take * sizeof(sg_edge_trend), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    return SG_OK;
+}
+int sg_window_trend_buffer(sg_handle e, void** d_trend) {
+    if (!e || !d_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Trend& t = e->trend;
+    if (!t.on) { e->err = "sg_window_trend_buffer: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    *d_trend = t.rows[t.run_slot >= 0 ? t.run_slot : e->cur];
+    return SG_OK;
+}
+int sg_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Trend& t = e->trend;
+    if (!t.on) { e->err = "sg_trend_entries: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    u64 ctl[K8C_WORDS];
+    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+    const u32 par = t.w & 1u;                                          // (w = 0: parity 0, B = 0)
+    const size_t B = (size_t)ctl[K8C_B0 + par];
+    if (n) *n = B;
+    const size_t take = std::min(B, cap);
+    if (!out || !take) return SG_OK;
+    const TrendSoA& x = t.buf[par];
+    std::vector<u64> fk(take), tk(take); std::vector<double> lm(take), ld(take), em(take), ed(take); std::vector<u32> cn(take), ls(take);
+    HIP_TRY(e, hipMemcpy(fk.data(), x.from_key, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(tk.data(), x.to_key, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(lm.data(), x.lat_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ld.data(), x.lat_dev, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(em.data(), x.err_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ed.data(), x.err_dev, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(cn.data(), x.n, take * 4, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ls.data(), x.last, take * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < take; i++) out[i] = sg_trend_entry{fk[i], tk[i], lm[i], ld[i], em[i], ed[i], cn[i], ls[i]};
+    return SG_OK;
+}
+int sg_trend_stats_get(sg_handle e, sg_trend_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Trend& t = e->trend;
+    if (!t.on) { e->err = "sg_trend_stats_get: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    u64 ctl[K8C_WORDS];
+    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+    out->windows = ctl[K8C_WINDOWS]; out->entries = ctl[K8C_B0 + (t.w & 1u)];
+    out->inserted = ctl[K8C_INSERTED]; out->expired = ctl[K8C_EXPIRED]; out->dropped = ctl[K8C_DROPPED];
+    return SG_OK;
+}
+
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.
 // ---- the sharded window in ONE call (judge item r2-2): local stages + RCCL collectives, all enqueued on one stream ----------
 // RCCL is reached through dlopen (the copy already in the process, e.g. torch's, else /opt/rocm/lib/librccl.so): the engine
@@ -1594,6 +1749,7 @@ int sg_window_run_sharded(sg_handle e, sg_comm* c, void* stream) {
     if (rc) { if (e->err.empty()) e->err = "sg_window_run_sharded: a stage or a collective failed"; return rc; }
     window_timed_end(e, s);
     e->last_rows = e->d.rows; e->last_ctr = e->d.ctr; e->last_stream = s;
+    e->trend.run_slot = e->cur;
     return SG_OK;
 }
 
@@ -1620,6 +1776,7 @@ int sg_window_run(sg_handle e, void* stream) {
     if (did) e->closed = false; else if ((rc = do_reset(e, s))) return rc;
     window_timed_end(e, s);
     e->last_rows = e->d.rows; e->last_ctr = e->d.ctr; e->last_stream = s;
+    e->trend.run_slot = e->cur;
     rotate_window(e);                                    // the next sg_ingest* goes to the next slot (if any)
     return SG_OK;
 }

@@ -384,6 +384,51 @@ inline SelPlan plan_select(u64 max_edges, bool used) {
 // k7_sort's LDS: the selected (key, index) pairs padded to a power of two, 8 bytes each
 inline size_t select_sort_lds(u32 k) { return (size_t)next_pow2(std::max<u32>(k, 1)) * 8; }
 
+// K8, the per-edge baselines (sg_trend.h): the parameters with their defaults filled in, and the device memory sg_set_trend
+// allocates — never sg_create: an engine without the trend asks for nothing.  The merge of B <= max_entries old entries with
+// E <= max_edges rows is split into one span per thread of `wgs` 256-thread workgroups, about eight merged elements per thread
+// (at most 1024 workgroups: k8_scan scans one count per thread of one 1024-thread workgroup; beyond that the spans grow).
+constexpr u32 kTrendThreads = 256, kTrendMaxWgs = 1024, kTrendPerThread = 8, kTrendCtlWords = 8;
+constexpr u64 kTrendMaxEntries = 1ull << 31;              // the per-window counts are u32
+constexpr u64 kTrendAlign = 256;
+// SG_OK and *out = p with every 0 replaced by its default, or SG_EINVAL
+inline int check_trend(const sg_trend_params& p, u64 max_edges, sg_trend_params* out) {
+    if (p.struct_size != sizeof(sg_trend_params) || p.reserved != 0 || p.shift > 10 || p.max_entries > kTrendMaxEntries) return SG_EINVAL;
+    sg_trend_params r = p;
+    if (!r.shift) r.shift = 4;
+    if (!r.warmup) r.warmup = 4;
+    if (!r.ttl) r.ttl = 64;
+    if (!r.max_entries) r.max_entries = std::min<u64>(kTrendMaxEntries, 2 * std::max<u64>(max_edges, 1));
+    if (!r.lat_floor_ns) r.lat_floor_ns = 1000;
+    if (!r.err_floor) r.err_floor = 10486;
+    *out = r;
+    return SG_OK;
+}
+struct TrendPlan {
+    u64 entries = 0;              // max_entries
+    u32 wgs = 0;                  // workgroups of k8_count / k8_write
+    u64 soa_bytes = 0;            // one baseline buffer: 56 bytes per entry (from_key, to_key, four fp64, n, last)
+    u64 ctl_bytes = 0;            // the control block: B per parity, room, statistics
+    u64 blk_bytes = 0;            // [wgs][4] u32
+    u64 thread_bytes = 0;         // [wgs * 256] per-thread split + counts (16 bytes)
+    u64 rows_bytes = 0;           // one window slot's trend rows: [max_edges] sg_edge_trend
+    u64 total_bytes = 0;          // two baseline buffers, the scratch and every slot's rows, each 256-byte aligned
+};
+inline u64 trend_align(u64 b) { return (b + kTrendAlign - 1) / kTrendAlign * kTrendAlign; }
+inline TrendPlan plan_trend(u64 max_edges, u32 slots, const sg_trend_params& p) {
+    TrendPlan t;
+    t.entries = p.max_entries;
+    const u64 T = p.max_entries + max_edges, per_wg = (u64)kTrendThreads * kTrendPerThread;
+    t.wgs = (u32)std::max<u64>(1, std::min<u64>(kTrendMaxWgs, (T + per_wg - 1) / per_wg));
+    t.soa_bytes = trend_align(p.max_entries * (2 * 8 + 4 * 8 + 2 * 4));
+    t.ctl_bytes = trend_align(kTrendCtlWords * 8);
+    t.blk_bytes = trend_align((u64)t.wgs * 4 * 4);
+    t.thread_bytes = trend_align((u64)t.wgs * kTrendThreads * 16);
+    t.rows_bytes = trend_align(std::max<u64>(max_edges, 1) * sizeof(sg_edge_trend));
+    t.total_bytes = 2 * t.soa_bytes + t.ctl_bytes + t.blk_bytes + t.thread_bytes + (u64)std::max<u32>(slots, 1) * t.rows_bytes;
+    return t;
+}
+
 // the plan's share of the kernels' argument (Dev, sg_device.h; a template so that the CPU test can fill a struct of the same names)
 template <class D>
 void plan_to_dev(const Plan& p, const sg_config& cfg, D& d) {

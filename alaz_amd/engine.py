@@ -43,7 +43,15 @@ EXPORTS = [
     "sg_timing_enable", "sg_timing_reset", "sg_timing_get", "sg_timing_samples", "sg_timing_stride", "sg_latency_probe", "sg_set_warm", "sg_debug_stamps", "sg_route", "sg_window_hist", "sg_geometry_get",
     "sg_clock_probe", "sg_comm_probe", "sg_window_halo_counts", "sg_comm_unique_id", "sg_comm_create", "sg_comm_destroy", "sg_window_run_sharded", "sg_host_register", "sg_host_unregister", "sg_ingest_pinned", "sg_ingest_bulk",
     "sg_flush_window_top", "sg_flush_end_top", "sg_window_select",
+    "sg_set_trend", "sg_window_trend", "sg_window_trend_buffer", "sg_trend_entries", "sg_trend_stats_get",
 ]
+
+#: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
+TREND_DTYPE = np.dtype([("lat_dev", "<f4"), ("err_dev", "<f4"), ("base_mean_us", "<f4"), ("windows_seen", "<u4")])
+TREND_ENTRY_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
+                              ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4")])
+#: sg_trend_params defaults (a 0 in the struct means the same)
+TREND_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, lat_floor_ns=1000, err_floor=10486)
 
 
 class SgConfig(C.Structure):
@@ -83,6 +91,15 @@ class SgStats(C.Structure):
                 ("join_word_updates", C.c_uint64), ("join_full_uploads", C.c_uint64), ("ingest_waits", C.c_uint64),
                 ("windows_warm", C.c_uint64), ("windows_cold", C.c_uint64),
                 ("windows_delta", C.c_uint64), ("windows_plain", C.c_uint64), ("last_window_new_edges", C.c_uint64)]
+
+
+class SgTrendParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("shift", C.c_uint32), ("warmup", C.c_uint32), ("ttl", C.c_uint32),
+                ("max_entries", C.c_uint64), ("lat_floor_ns", C.c_uint64), ("err_floor", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SgTrendStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("windows", "entries", "inserted", "expired", "dropped")]
 
 
 class ServiceGraphError(RuntimeError):
@@ -172,6 +189,9 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_flush_window_top": (C.c_int, [H, u64, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
         "sg_flush_end_top": (C.c_int, [H, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
         "sg_window_select": (C.c_int, [H, u32, C.c_float, P, P, sz, P, P]),
+        "sg_set_trend": (C.c_int, [H, P]), "sg_window_trend": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
+        "sg_window_trend_buffer": (C.c_int, [H, C.POINTER(C.c_void_p)]), "sg_trend_entries": (C.c_int, [H, P, sz, C.POINTER(sz)]),
+        "sg_trend_stats_get": (C.c_int, [H, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -367,6 +387,59 @@ class ServiceGraph:
         """Select from the rows of the window window_run closed last into device memory (sg_window_select): d_out [cap] rows,
         d_index [cap] u32 (0 = none), d_n one u64 = rows selected; enqueued on `stream` (0 = that window's stream)."""
         self._ck(self._l.sg_window_select(self._h, k, min_score, d_out or None, d_index or None, cap, d_n, stream or None))
+
+    # ---- per-edge baselines (K8): each edge against its own past ----
+    def set_trend(self, params: Optional[dict] = (), **kw):
+        """Switch the per-edge baseline on (sg_set_trend; shift, warmup, ttl, max_entries, lat_floor_ns, err_floor as keywords or a
+        dict — see TREND_DEFAULTS; set_trend() = every default; (re)enabling starts an empty baseline) or off: set_trend(None)."""
+        if params is None:
+            if kw:
+                raise TypeError("set_trend(None) switches the trend off and takes no parameters")
+            self._ck(self._l.sg_set_trend(self._h, None))
+            return
+        v = dict(TREND_DEFAULTS)
+        v.update(params or {}); v.update(kw)
+        unknown = set(v) - set(TREND_DEFAULTS) - {"struct_size", "reserved"}
+        if unknown:
+            raise TypeError(f"unknown trend parameters: {sorted(unknown)}")
+        p = SgTrendParams(v.get("struct_size", C.sizeof(SgTrendParams)), v["shift"], v["warmup"], v["ttl"], v["max_entries"],
+                          v["lat_floor_ns"], v["err_floor"], v.get("reserved", 0))
+        self._ck(self._l.sg_set_trend(self._h, C.byref(p)))
+
+    def window_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """TREND_DTYPE rows of the last read window (sg_window_trend): every row, or the rows at `index` (only those cross PCIe)."""
+        n = C.c_size_t(0)
+        if index is None:
+            self._ck(self._l.sg_window_trend(self._h, None, 0, None, 0, C.byref(n)))
+            out = np.zeros(n.value, dtype=TREND_DTYPE)
+            if n.value:
+                self._ck(self._l.sg_window_trend(self._h, None, 0, out.ctypes.data, n.value, C.byref(n)))
+            return out
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        out = np.zeros(len(idx), dtype=TREND_DTYPE)
+        if len(idx):
+            self._ck(self._l.sg_window_trend(self._h, idx.ctypes.data, len(idx), out.ctypes.data, len(idx), C.byref(n)))
+        return out
+
+    def trend_buffer(self) -> int:
+        """device pointer of the sg_edge_trend rows of the window window_run closed last (sg_window_trend_buffer)"""
+        p = C.c_void_p()
+        self._ck(self._l.sg_window_trend_buffer(self._h, C.byref(p)))
+        return p.value
+
+    def trend_entries(self) -> np.ndarray:
+        """the baseline in key order, TREND_ENTRY_DTYPE (sg_trend_entries)"""
+        n = C.c_size_t(0)
+        self._ck(self._l.sg_trend_entries(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=TREND_ENTRY_DTYPE)
+        if n.value:
+            self._ck(self._l.sg_trend_entries(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def trend_stats(self) -> SgTrendStats:
+        s = SgTrendStats()
+        self._ck(self._l.sg_trend_stats_get(self._h, C.byref(s)))
+        return s
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

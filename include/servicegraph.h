@@ -314,6 +314,52 @@ int sg_flush_end_top(sg_handle h, uint32_t k, float min_score,
 int sg_window_select(sg_handle h, uint32_t k, float min_score, sg_edge_out* d_out, uint32_t* d_index,
                      size_t cap, uint64_t* d_n, void* stream);
 
+/* ---- per-edge baselines (K8): each edge against its own past, kept on the device across windows --------------------------- *
+ * Opt-in (sg_set_trend); an engine without it computes and allocates nothing for it, and its rows are the same either way.
+ * Edge key: from_key, to_key = type << 32 | v with type = SG_REF_TYPE(ref), v = SG_REF_VALUE(ref) for KNOWN / LABEL refs and the
+ * IPv4 address (the window's outbound-IP list at SG_REF_VALUE(ref)) for OBIP refs.  The canonical row order is strictly
+ * ascending in (from_key, to_key), and the baseline is kept sorted by it: each window is a merge of two sorted lists.
+ * Sample of a row with count > 0 (rows with count == 0 — alive-only edges — neither create nor refresh an entry), exact in fp64:
+ *   x_lat = min(sum_ns / count, 2^52), x_err = (err_count << 20) / count   (u64 integer divisions; err in units of 2^-20)
+ * Entry update in trend window w (w counts the windows closed while the trend is on, from 1; alpha = 2^-shift): a new entry gets
+ * mean = x, dev = 0, n = 1, last = w; an existing one d = x - mean, mean += d * alpha, dev += (|d| - dev) * alpha, n = min(n + 1,
+ * 2^32 - 1), last = w (latency and error alike).  Every product is exact: the state equals a float64 reference bit for bit.  An
+ * entry NOT updated in window w with w - last >= ttl is removed.  Capacity: the kept old entries never exceed max_entries; new
+ * ones go in in key order while there is room, the rest are dropped and counted.
+ * Per row, from the entry as it was BEFORE the window's update: windows_seen = its n (0: never seen, expired or dropped — with
+ * count > 0 a new dependency); lat_dev = (float)((x_lat - lat_mean) / max(lat_dev, lat_floor_ns)), 0 when count == 0 or
+ * windows_seen < warmup; err_dev likewise with err_floor; base_mean_us = (float)(lat_mean / 1000), 0 without an entry.          */
+typedef struct sg_trend_params {
+    uint32_t struct_size;       /* sizeof(sg_trend_params)                                                                  */
+    uint32_t shift;             /* alpha = 2^-shift, 1..10 (0 = 4)                                                           */
+    uint32_t warmup;            /* windows an entry must have seen before its rows report deviations (0 = 4)                 */
+    uint32_t ttl;               /* windows an entry survives without a sample (0 = 64)                                       */
+    uint64_t max_entries;       /* baseline capacity, at most 2^31 (0 = 2 x max_edges)                                       */
+    uint64_t lat_floor_ns;      /* latency deviation floor (0 = 1000)                                                        */
+    uint32_t err_floor;         /* error deviation floor in units of 2^-20 (0 = 10486, 1 %)                                  */
+    uint32_t reserved;          /* 0                                                                                         */
+} sg_trend_params;
+typedef struct sg_edge_trend { float lat_dev, err_dev, base_mean_us; uint32_t windows_seen; } sg_edge_trend;
+typedef struct sg_trend_entry { uint64_t from_key, to_key; double lat_mean, lat_dev, err_mean, err_dev; uint32_t n, last; } sg_trend_entry;
+typedef struct sg_trend_stats {
+    uint64_t windows;           /* windows the baseline was updated by since it was (re)enabled                              */
+    uint64_t entries;           /* entries now                                                                               */
+    uint64_t inserted, expired, dropped;   /* totals since it was (re)enabled                                                */
+} sg_trend_stats;
+/* NULL = off (frees the baseline); params = on, and (re)enabling starts an empty baseline.  Buffers are allocated here, not at
+ * create.  SG_ESTATE while a flush is open, SG_EINVAL on bad params.  Trend calls on an engine without the trend: SG_ESTATE. */
+int sg_set_trend(sg_handle h, const sg_trend_params* p);
+/* The trend rows of the last READ window (the rows sg_flush_window* / sg_window_read returned; all zero for a window closed before
+ * the trend was enabled).  row_index NULL: every row, *n = edges; else out[k] = the trend of row row_index[k] (each < edges, else
+ * SG_EINVAL), *n = n_index — only those n_index entries cross PCIe.  min(*n, cap) entries are written.                         */
+int sg_window_trend(sg_handle h, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n);
+/* Device sg_edge_trend[E] of the window sg_window_run / sg_window_run_sharded closed last (valid until its slot is reused; read it
+ * on that window's stream).                                                                                                   */
+int sg_window_trend_buffer(sg_handle h, void** d_trend);
+/* The baseline in key order: min(*n, cap) entries, *n = entries (waits for the updates enqueued so far).                        */
+int sg_trend_entries(sg_handle h, sg_trend_entry* out, size_t cap, size_t* n);
+int sg_trend_stats_get(sg_handle h, sg_trend_stats* out);   /* (waits for the updates enqueued so far) */
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
