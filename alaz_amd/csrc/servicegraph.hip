@@ -132,6 +132,12 @@ struct sg_engine {
     struct Trend { bool on = false; sg_trend_params p{}; sgplan::TrendPlan plan; char* mem = nullptr; TrendSoA buf[2] = {}; u64* ctl = nullptr; u32* blk = nullptr;
                    K8Thread* th = nullptr; std::vector<sg_edge_trend*> rows; u32 w = 0; hipEvent_t ev = nullptr; bool pending = false; int run_slot = -1;
                    sg_edge_trend* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; } trend;
+    // K9, the node rollup (sg_nodes.h): allocated at sg_set_nodes (sg_plan.hpp plan_nodes), one allocation.  The tables are scratch
+    // shared by the window slots: every rollup waits for the previous one (ev), whichever slot's stream it runs on.  Per slot: the
+    // node rows and count, and whether the window in the slot was rolled up (valid).
+    struct Nodes { bool on = false; sgplan::NodesPlan plan; char* mem = nullptr; u32* dst = nullptr; K9Side* tout = nullptr; K9Side* tin = nullptr;
+                   K9Side* part = nullptr; u32* blk = nullptr; std::vector<sg_node_out*> rows; std::vector<u64*> count; std::vector<char> valid;
+                   hipEvent_t ev = nullptr; bool pending = false; int run_slot = -1; } nodes;
 };
 
 namespace {
@@ -558,6 +564,39 @@ int launch_trend(sg_engine* e, hipStream_t s) {
     t.w++;
     return SG_OK;
 }
+// ---- K9, the node rollup (engine lock held) ---------------------------------------------------------------------------------
+static_assert(sgplan::kNodesThreads == K9_THREADS && sgplan::kNodesChunk == K9_CHUNK && sgplan::kNodesRangeNodes == K9_IN_NR &&
+              sgplan::kNodesMaxWgs == K9_MAX_WGS && sgplan::kNodesMaxWgs <= K9_SCAN_THREADS && sgplan::kNodesSideBytes == sizeof(K9Side),
+              "plan_nodes sizes the launches of sg_nodes.h");
+// enqueue the rollup of the window in slot cur on stream s, behind the previous rollup (any stream)
+int launch_nodes(sg_engine* e, hipStream_t s) {
+    sg_engine::Nodes& n = e->nodes;
+    const sgplan::NodesPlan& P = n.plan;
+    NodesArgs a{};
+    a.rows = e->d.rows; a.ctr = e->d.ctr; a.max_edges = e->cfg.max_edges;
+    a.mk = e->d.max_known; a.ml = e->d.max_labels; a.mob = e->d.max_obip; a.ncap = P.ncap;
+    a.slices = P.slices; a.node_per = P.node_per;
+    a.dst = n.dst; a.tout = n.tout; a.tin = n.tin; a.part = n.part; a.blk = n.blk;
+    a.out = n.rows[e->cur]; a.count = n.count[e->cur];
+    if (n.pending) HIP_TRY(e, hipStreamWaitEvent(s, n.ev, 0));
+    hipLaunchKernelGGL(k9_out, dim3(P.out_wgs), dim3(K9_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k9_in_part, dim3(P.ranges * P.slices), dim3(K9_IN_THREADS), (size_t)P.lds_bytes, s, a);
+    hipLaunchKernelGGL(k9_count, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a, P.node_wgs);
+    hipLaunchKernelGGL(k9_write, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(n.ev, s));
+    n.pending = true;
+    n.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_nodes(sg_engine* e) {
+    sg_engine::Nodes& n = e->nodes;
+    if (n.mem) { hipDeviceSynchronize(); hipFree(n.mem); }
+    if (n.ev) hipEventDestroy(n.ev);
+    n = sg_engine::Nodes{};
+}
+
 void free_trend(sg_engine* e) {
     sg_engine::Trend& t = e->trend;
     if (t.mem || t.stage) hipDeviceSynchronize();
@@ -589,7 +628,9 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     HIP_TRY(e, hipGetLastError());
     // K8 right behind K5: every pipeline scores here.  The rows, the counters and the outbound-IP list survive K5's fused reset and
     // the separate one (sg_k5.h, sg_k3.h k_reset_window), and the next window's K1 queues behind K8 on this stream.
-    if (e->trend.on) return launch_trend(e, s);
+    if (e->trend.on) { const int rc = launch_trend(e, s); if (rc) return rc; }
+    // K9 behind them: it reads the rows and the window counters only
+    if (e->nodes.on) return launch_nodes(e, s);
     return SG_OK;
 }
 
@@ -977,6 +1018,7 @@ int sg_destroy(sg_handle e) {
     if (e->sel.h_n) hipHostFree(e->sel.h_n);
     if (e->sel.ev) hipEventDestroy(e->sel.ev);
     free_trend(e);
+    free_nodes(e);
     for (auto& r : e->trecs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto v : e->ev_pool) hipEventDestroy(v);
     if (e->tab_ev) hipEventDestroy(e->tab_ev);
@@ -1599,6 +1641,62 @@ int sg_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     return SG_OK;
 }
 
+// ---- K9, the node rollup ----------------------------------------------------------------------------------------------------
+int sg_set_nodes(sg_handle e, int on) {
+    if (!e || (on != 0 && on != 1)) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (e->cfg.world > 1) { e->err = "sg_set_nodes: the node rollup of a sharded engine is not supported"; return SG_EINVAL; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_nodes while a flush is open"; return SG_ESTATE; }
+    if (!on) { free_nodes(e); return SG_OK; }
+    sg_engine::Nodes& n = e->nodes;
+    if (n.on) return SG_OK;
+    const u32 slots = (u32)std::max<size_t>(e->slots.size(), 1);
+    n.plan = sgplan::plan_nodes(e->cfg.max_edges, e->d.ncap, slots);
+    const sgplan::NodesPlan& P = n.plan;
+    HIP_TRY(e, lds_limit(P.lds_bytes, k9_in_part));
+    HIP_TRY(e, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
+    {
+        const hipError_t rc = hipMalloc((void**)&n.mem, P.total_bytes);
+        if (rc != hipSuccess) { free_nodes(e); e->err = std::string("sg_set_nodes: hipMalloc: ") + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
+    }
+    HIP_TRY(e, hipMemset(n.mem, 0, P.total_bytes));                   // the out table starts at zero (k9_write keeps it so)
+    char* b = n.mem;                                                  // (the 64-byte tables first: every offset stays 256-aligned anyway)
+    n.tout = (K9Side*)b; b += P.table_bytes;
+    n.tin = (K9Side*)b; b += P.table_bytes;
+    n.part = (K9Side*)b; b += P.part_bytes;
+    n.dst = (u32*)b; b += P.dst_bytes;
+    n.blk = (u32*)b; b += P.blk_bytes;
+    for (u32 k = 0; k < slots; k++) { n.rows.push_back((sg_node_out*)b); b += P.rows_bytes; n.count.push_back((u64*)b); b += P.count_bytes; }
+    n.valid.assign(slots, 0);
+    n.on = true;
+    return SG_OK;
+}
+int sg_window_nodes(sg_handle e, sg_node_out* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Nodes& x = e->nodes;
+    if (!x.on) { e->err = "sg_window_nodes: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_window_nodes while a flush is open"; return SG_ESTATE; }
+    if (!x.valid[e->cur]) { e->err = "sg_window_nodes: the last read window was closed while the node rollup was off"; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, x.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    if (n) *n = (size_t)cnt;
+    const size_t take = std::min((size_t)cnt, cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, x.rows[e->cur], take * sizeof(sg_node_out), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+int sg_window_nodes_buffer(sg_handle e, void** d_nodes, void** d_count) {
+    if (!e || !d_nodes || !d_count) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Nodes& x = e->nodes;
+    if (!x.on) { e->err = "sg_window_nodes_buffer: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
+    const int slot = x.run_slot >= 0 ? x.run_slot : e->cur;
+    if (!x.valid[slot]) { e->err = "sg_window_nodes_buffer: the window was closed while the node rollup was off"; return SG_ESTATE; }
+    *d_nodes = x.rows[slot]; *d_count = x.count[slot];
+    return SG_OK;
+}
+
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.
 // ---- the sharded window in ONE call (judge item r2-2): local stages + RCCL collectives, all enqueued on one stream ----------
 // RCCL is reached through dlopen (the copy already in the process, e.g. torch's, else /opt/rocm/lib/librccl.so): the engine
@@ -1750,6 +1848,7 @@ int sg_window_run_sharded(sg_handle e, sg_comm* c, void* stream) {
     window_timed_end(e, s);
     e->last_rows = e->d.rows; e->last_ctr = e->d.ctr; e->last_stream = s;
     e->trend.run_slot = e->cur;
+    e->nodes.run_slot = e->cur;
     return SG_OK;
 }
 
@@ -1777,6 +1876,7 @@ int sg_window_run(sg_handle e, void* stream) {
     window_timed_end(e, s);
     e->last_rows = e->d.rows; e->last_ctr = e->d.ctr; e->last_stream = s;
     e->trend.run_slot = e->cur;
+    e->nodes.run_slot = e->cur;
     rotate_window(e);                                    // the next sg_ingest* goes to the next slot (if any)
     return SG_OK;
 }

@@ -298,3 +298,4 @@ __global__ __launch_bounds__(256) void k1_resolve_aggregate(Dev d, const sg_even
 #include "sg_k4.h"          // K4: gather-mean + dense (MFMA)
 #include "sg_k5.h"          // K5: projections + edge score
 #include "sg_k6.h"          // K6: halo lists, pack / unpack
+#include "sg_nodes.h"       // K9: the node rollup (opt-in, behind K5)

@@ -429,6 +429,49 @@ inline TrendPlan plan_trend(u64 max_edges, u32 slots, const sg_trend_params& p) 
     return t;
 }
 
+// K9, the node rollup (sg_nodes.h): the device memory sg_set_nodes allocates — never sg_create.  Nodes are keyed by an id below
+// ncap = max_known + max_labels + max_obip.  k9_out takes chunks of 2048 rows (256 threads x 8); k9_in_part a grid of node ranges
+// of 2048 (128 KiB of LDS each) x row slices — about 32 K rows per slice, at most 16 slices, as k3_in_part; k9_count / k9_write
+// one 256-thread workgroup per block of node_per nodes, at most 1024 blocks (k9_scan scans one count per thread).
+constexpr u32 kNodesThreads = 256, kNodesChunk = 2048, kNodesRangeNodes = 2048, kNodesMaxSlices = 16, kNodesSliceRows = 32768,
+              kNodesMaxWgs = 1024;
+constexpr u64 kNodesSideBytes = 64;       // one side of a node: a table entry, an LDS entry, a partial
+struct NodesPlan {
+    u32 ncap = 0;
+    u32 out_wgs = 0;              // workgroups of k9_out: chunks of max_edges
+    u32 ranges = 0, slices = 0;   // k9_in_part's grid = ranges x slices
+    u32 node_wgs = 0, node_per = 0;   // k9_count / k9_write: workgroups, nodes per workgroup (a multiple of 256)
+    u64 dst_bytes = 0;            // [max_edges] u32 destination node per row
+    u64 table_bytes = 0;          // one side's table: [ncap] x 64 bytes (out and in: two of them)
+    u64 part_bytes = 0;           // [ranges][slices][2048] x 64 bytes
+    u64 blk_bytes = 0;            // [2][1024] u32
+    u64 rows_bytes = 0;           // one window slot's node rows: [ncap] sg_node_out
+    u64 count_bytes = 0;          // one window slot's node count (u64)
+    u64 lds_bytes = 0;            // k9_in_part's dynamic LDS
+    u64 total_bytes = 0;          // the scratch and every slot's rows and count, each 256-byte aligned
+};
+inline NodesPlan plan_nodes(u64 max_edges, u32 ncap, u32 slots) {
+    NodesPlan n;
+    const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(ncap, 1);
+    n.ncap = ncap;
+    n.out_wgs = (u32)((ME + kNodesChunk - 1) / kNodesChunk);
+    n.ranges = (u32)((NC + kNodesRangeNodes - 1) / kNodesRangeNodes);
+    n.slices = (u32)std::max<u64>(1, std::min<u64>(kNodesMaxSlices, (ME + kNodesSliceRows - 1) / kNodesSliceRows));
+    n.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kNodesMaxWgs, (NC + kNodesThreads - 1) / kNodesThreads));
+    const u64 per = (NC + n.node_wgs - 1) / n.node_wgs;
+    n.node_per = (u32)((per + kNodesThreads - 1) / kNodesThreads * kNodesThreads);
+    n.node_wgs = (u32)((NC + n.node_per - 1) / n.node_per);           // (the rounding can leave the last blocks without nodes)
+    n.dst_bytes = trend_align(ME * 4);
+    n.table_bytes = trend_align(NC * kNodesSideBytes);
+    n.part_bytes = trend_align((u64)n.ranges * n.slices * kNodesRangeNodes * kNodesSideBytes);
+    n.blk_bytes = trend_align(2ull * kNodesMaxWgs * 4);
+    n.rows_bytes = trend_align(NC * sizeof(sg_node_out));
+    n.count_bytes = trend_align(8);
+    n.lds_bytes = (u64)kNodesRangeNodes * kNodesSideBytes;
+    n.total_bytes = n.dst_bytes + 2 * n.table_bytes + n.part_bytes + n.blk_bytes + (u64)std::max<u32>(slots, 1) * (n.rows_bytes + n.count_bytes);
+    return n;
+}
+
 // the plan's share of the kernels' argument (Dev, sg_device.h; a template so that the CPU test can fill a struct of the same names)
 template <class D>
 void plan_to_dev(const Plan& p, const sg_config& cfg, D& d) {

@@ -44,12 +44,17 @@ EXPORTS = [
     "sg_clock_probe", "sg_comm_probe", "sg_window_halo_counts", "sg_comm_unique_id", "sg_comm_create", "sg_comm_destroy", "sg_window_run_sharded", "sg_host_register", "sg_host_unregister", "sg_ingest_pinned", "sg_ingest_bulk",
     "sg_flush_window_top", "sg_flush_end_top", "sg_window_select",
     "sg_set_trend", "sg_window_trend", "sg_window_trend_buffer", "sg_trend_entries", "sg_trend_stats_get",
+    "sg_set_nodes", "sg_window_nodes", "sg_window_nodes_buffer",
 ]
 
 #: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
 TREND_DTYPE = np.dtype([("lat_dev", "<f4"), ("err_dev", "<f4"), ("base_mean_us", "<f4"), ("windows_seen", "<u4")])
 TREND_ENTRY_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
                               ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4")])
+#: sg_node_out (136 bytes) of include/servicegraph.h: one node of a window's rollup (K9)
+NODE_DTYPE = np.dtype([(f"{side}_{f}", "<u8") for f in ("count", "err", "sum_ns", "sumsq_us", "max_ns", "score_q32") for side in ("out", "in")]
+                      + [(f, "<u4") for f in ("ref", "out_edges", "in_edges", "out_alive", "in_alive", "out_worst_row", "in_worst_row")]
+                      + [(f, "<f4") for f in ("out_score_max", "in_score_max", "score")])
 #: sg_trend_params defaults (a 0 in the struct means the same)
 TREND_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, lat_floor_ns=1000, err_floor=10486)
 
@@ -192,6 +197,8 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_set_trend": (C.c_int, [H, P]), "sg_window_trend": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
         "sg_window_trend_buffer": (C.c_int, [H, C.POINTER(C.c_void_p)]), "sg_trend_entries": (C.c_int, [H, P, sz, C.POINTER(sz)]),
         "sg_trend_stats_get": (C.c_int, [H, P]),
+        "sg_set_nodes": (C.c_int, [H, C.c_int]), "sg_window_nodes": (C.c_int, [H, P, sz, C.POINTER(sz)]),
+        "sg_window_nodes_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -440,6 +447,27 @@ class ServiceGraph:
         s = SgTrendStats()
         self._ck(self._l.sg_trend_stats_get(self._h, C.byref(s)))
         return s
+
+    # ---- node rollup (K9): each window's rows reduced per node on the device ----
+    def set_nodes(self, on: bool = True):
+        """Switch the per-window node rollup on (sg_set_nodes: allocates its buffers) or off (frees them)."""
+        self._ck(self._l.sg_set_nodes(self._h, 1 if on else 0))
+
+    def window_nodes(self) -> np.ndarray:
+        """NODE_DTYPE rows of the last read window (sg_window_nodes), ascending by (ref type, ref value)"""
+        n = C.c_size_t(0)
+        self._ck(self._l.sg_window_nodes(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=NODE_DTYPE)
+        if n.value:
+            self._ck(self._l.sg_window_nodes(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def nodes_buffer(self) -> Tuple[int, int]:
+        """(device pointer of the sg_node_out rows, device pointer of their u64 count) of the window window_run closed last
+        (sg_window_nodes_buffer)"""
+        p, c = C.c_void_p(), C.c_void_p()
+        self._ck(self._l.sg_window_nodes_buffer(self._h, C.byref(p), C.byref(c)))
+        return p.value, c.value
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

@@ -360,6 +360,39 @@ int sg_window_trend_buffer(sg_handle h, void** d_trend);
 int sg_trend_entries(sg_handle h, sg_trend_entry* out, size_t cap, size_t* n);
 int sg_trend_stats_get(sg_handle h, sg_trend_stats* out);   /* (waits for the updates enqueued so far) */
 
+/* ---- node rollup (K9): each window's scored edges reduced per node, on the device ------------------------------------------ *
+ * Opt-in (sg_set_nodes); an engine without it computes and allocates nothing for it, and its rows are the same either way.
+ * Over the window's rows r_0 .. r_{E-1} in canonical order, the node set is every from_ref and to_ref of some row.  Node rows come
+ * out ascending by (SG_REF_TYPE(ref), SG_REF_VALUE(ref)): KNOWN by id, then LABEL, then OBIP by index into the window's
+ * outbound-IP list.  For node x the out_* fields reduce over the rows with from_ref == x, the in_* fields over the rows with
+ * to_ref == x; a row with from_ref == to_ref counts on both sides.
+ *   *_edges        rows                                 *_count, *_err     sum of count, err_count
+ *   *_sum_ns, *_sumsq_us   wrapping u64 sums            *_max_ns           max of max_ns (0 without rows)
+ *   *_alive        sum of alive                         *_score_q32        wrapping u64 sum of (uint64_t)((double)score * 2^32)
+ *                                                                          (a score that is not > 0 adds 0): exact, order-free
+ *   *_score_max    the largest score (0 without rows)   *_worst_row        the smallest row index among the side's rows whose
+ *                                                                          score equals *_score_max (0xFFFFFFFF without rows)
+ *   score          max(out_score_max, in_score_max)
+ * Scores are compared by value with +0.0 above -0.0 (the window's scores are sigmoids in [0, 1]).  Every field is an integer sum, an
+ * integer max or a max of floats: the result has one correct value, and each field merges across shards by sum or max.  The row
+ * indices are the positions of sg_flush_window*, sg_flush_window_top's row_index and sg_window_trend's row_index.            */
+typedef struct sg_node_out {
+    uint64_t out_count, in_count, out_err, in_err, out_sum_ns, in_sum_ns, out_sumsq_us, in_sumsq_us, out_max_ns, in_max_ns,
+             out_score_q32, in_score_q32;
+    uint32_t ref, out_edges, in_edges, out_alive, in_alive, out_worst_row, in_worst_row;
+    float    out_score_max, in_score_max, score;
+} sg_node_out;                  /* 136 bytes, no padding */
+/* on = 1: allocate the per-slot node buffers (a no-op when on); on = 0: free them.  SG_ESTATE while a flush is open, SG_EINVAL on
+ * an engine with world > 1.  Node calls on an engine without the rollup: SG_ESTATE.                                            */
+int sg_set_nodes(sg_handle h, int on);
+/* The node rows of the last READ window (the window whose rows sg_flush_window* / sg_window_read returned): *n = nodes, min(*n, cap)
+ * rows are written (a window without rows: *n = 0).  SG_ESTATE for a window closed while the rollup was off, and while a flush is
+ * open (its window is being rolled up into the same buffer).                                                                  */
+int sg_window_nodes(sg_handle h, sg_node_out* out, size_t cap, size_t* n);
+/* Device sg_node_out[] and its count (one uint64_t) of the window sg_window_run closed last (valid until its slot is reused; read
+ * them on that window's stream).                                                                                              */
+int sg_window_nodes_buffer(sg_handle h, void** d_nodes, void** d_count);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
