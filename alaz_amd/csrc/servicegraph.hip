@@ -132,6 +132,10 @@ struct sg_engine {
     struct Trend { bool on = false; sg_trend_params p{}; sgplan::TrendPlan plan; char* mem = nullptr; TrendSoA buf[2] = {}; u64* ctl = nullptr; u32* blk = nullptr;
                    K8Thread* th = nullptr; std::vector<sg_edge_trend*> rows; u32 w = 0; hipEvent_t ev = nullptr; bool pending = false; int run_slot = -1;
                    sg_edge_trend* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; } trend;
+    // K8's vanished list: allocated at sg_set_vanished (sg_plan.hpp plan_vanished), one allocation, freed by any sg_set_trend.  The
+    // counts are scratch shared like the baseline; per slot: the list, its count, and whether the window in the slot made one (valid).
+    struct Vanished { bool on = false; sg_vanished_params p{}; sgplan::VanishedPlan plan; char* mem = nullptr; u32* th = nullptr; u32* blk = nullptr;
+                      std::vector<sg_edge_vanished*> rows; std::vector<u64*> count; std::vector<char> valid; } vanished;
     // K9, the node rollup (sg_nodes.h): allocated at sg_set_nodes (sg_plan.hpp plan_nodes), one allocation.  The tables are scratch
     // shared by the window slots: every rollup waits for the previous one (ev), whichever slot's stream it runs on.  Per slot: the
     // node rows and count, and whether the window in the slot was rolled up (valid).
@@ -543,6 +547,8 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
 }
 
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
+static_assert(sizeof(sg_edge_vanished) == 64 && sgplan::kTrendThreads == K8_THREADS && sgplan::kTrendMaxWgs <= K8_SCAN_THREADS,
+              "plan_trend / plan_vanished size the launches of sg_trend.h");
 // enqueue window w's update on stream s behind the previous update (any stream); the window's trend rows go to the slot's buffer
 int launch_trend(sg_engine* e, hipStream_t s) {
     sg_engine::Trend& t = e->trend;
@@ -555,9 +561,20 @@ int launch_trend(sg_engine* e, hipStream_t s) {
     a.w = t.w + 1; a.warmup = p.warmup; a.ttl = p.ttl;
     a.alpha = std::ldexp(1.0, -(int)p.shift); a.lat_floor = (double)p.lat_floor_ns; a.err_floor = (double)p.err_floor;
     if (t.pending) HIP_TRY(e, hipStreamWaitEvent(s, t.ev, 0));
-    hipLaunchKernelGGL(k8_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-    hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs);
-    hipLaunchKernelGGL(k8_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+    sg_engine::Vanished& v = e->vanished;
+    if (v.on) {                                                       // the same three launches with the vanished count
+        VanArgs va{};
+        va.out = v.rows[e->cur]; va.count = v.count[e->cur]; va.th = v.th; va.blk = v.blk;
+        va.max_rows = v.plan.rows; va.silent = v.p.silent_windows; va.min_seen = v.p.min_seen;
+        hipLaunchKernelGGL(k8_count_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
+        hipLaunchKernelGGL(k8_scan_v, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs, va);
+        hipLaunchKernelGGL(k8_write_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
+        v.valid[e->cur] = 1;
+    } else {
+        hipLaunchKernelGGL(k8_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+        hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs);
+        hipLaunchKernelGGL(k8_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+    }
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipEventRecord(t.ev, s));
     t.pending = true;
@@ -597,7 +614,14 @@ void free_nodes(sg_engine* e) {
     n = sg_engine::Nodes{};
 }
 
+void free_vanished(sg_engine* e) {
+    sg_engine::Vanished& v = e->vanished;
+    if (v.mem) { hipDeviceSynchronize(); hipFree(v.mem); }
+    v = sg_engine::Vanished{};
+}
+
 void free_trend(sg_engine* e) {
+    free_vanished(e);
     sg_engine::Trend& t = e->trend;
     if (t.mem || t.stage) hipDeviceSynchronize();
     if (t.mem) hipFree(t.mem);
@@ -750,14 +774,16 @@ int sel_reserve(sg_engine* e, u64 stage_rows) {
     return SG_OK;
 }
 
-// enqueue the selection on stream st: a.rows / a.ctr / a.n_host / a.out / a.out_idx / a.cap / a.n_out set by the caller
-int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_score) {
+// enqueue the selection on stream st: a.rows / a.ctr / a.n_host / a.out / a.out_idx / a.cap / a.n_out set by the caller; by != SG_SEL_SCORE
+// keys the window's trend rows tr
+int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_score, u32 by = SG_SEL_SCORE, const sg_edge_trend* tr = nullptr) {
     sg_engine::Sel& s = e->sel;
     const u32 wgs = s.plan.wgs;
     a.max_edges = e->cfg.max_edges; a.k = k; a.min_score = min_score;
     a.keys = s.keys; a.hist = s.hist; a.blk = s.blk; a.state = s.state; a.pairs = s.pairs;
     if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
-    hipLaunchKernelGGL(k7_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a);
+    if (by == SG_SEL_SCORE) hipLaunchKernelGGL(k7_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(k7_keys_by, dim3(wgs), dim3(K7_THREADS), 0, st, a, tr, by);
     if (k) {
         for (u32 r = 0; r < 4; r++) {
             if (r) hipLaunchKernelGGL(k7_hist, dim3(wgs), dim3(K7_THREADS), 0, st, a, r);
@@ -1421,13 +1447,15 @@ int flush_end_unlocked(sg_engine* e, std::unique_lock<std::mutex>& g, sg_edge_ou
 // flush_end_unlocked with the selection: it runs on the read stream behind the window's score kernel (or, where begin already read the
 // counters under the lock, behind its device sync), and only the selected rows, their indices and one count cross PCIe
 int flush_end_top_unlocked(sg_engine* e, std::unique_lock<std::mutex>& g, u32 k, float min_score, sg_edge_out* out, u32* row_index,
-                           size_t cap, size_t* n_selected, size_t* n_edges) {
+                           size_t cap, size_t* n_selected, size_t* n_edges, u32 by = SG_SEL_SCORE) {
     e->cv.wait(g, [&] { return !e->fetching; });
     if (!e->flush_open) { e->err = "sg_flush_end_top without sg_flush_begin"; return SG_ESTATE; }
     const u64 ME = e->cfg.max_edges;
     const u64 stage = std::min<u64>(cap, k ? std::min<u64>(k, ME) : ME);   // rows the selection writes at most
     { const int rc = sel_reserve(e, std::max<u64>(stage, 1)); if (rc) return rc; }
     const sg_edge_out* d_rows = e->fl_rows; const u32* d_ob = e->fl_ob;
+    // the window's trend rows: written by the K8 launches do_score enqueued behind K5, before score_ev (and before begin's device sync)
+    const sg_edge_trend* d_tr = by != SG_SEL_SCORE ? e->trend.rows[e->cur] : nullptr;
     const bool async = e->flush_async;
     size_t E = async ? 0 : (size_t)e->h_ctr[C_N_EDGES];                   // (not async: begin has read the counters and the outbound IPs)
     e->fetching = true;                                                  // claimed: the fetch below runs without the engine lock
@@ -1445,7 +1473,7 @@ int flush_end_top_unlocked(sg_engine* e, std::unique_lock<std::mutex>& g, u32 k,
         SelArgs a{};
         a.rows = d_rows; a.ctr = nullptr; a.n_host = E;
         a.out = e->sel.stage; a.out_idx = e->sel.stage_idx; a.cap = stage; a.n_out = e->sel.n;
-        g.lock(); rc = launch_select(e, e->rd_stream, a, k, min_score); g.unlock();
+        g.lock(); rc = launch_select(e, e->rd_stream, a, k, min_score, by, d_tr); g.unlock();
         if (rc) break;
         if (hipMemcpyAsync(e->sel.h_n, e->sel.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream) != hipSuccess) { err = "hipMemcpyAsync (selected count)"; rc = SG_ENODEV; break; }
         obips.resize(nob);
@@ -1528,6 +1556,48 @@ int sg_window_select(sg_handle e, uint32_t k, float min_score, sg_edge_out* d_ou
     a.out = d_out; a.out_idx = d_index; a.cap = cap; a.n_out = reinterpret_cast<u64*>(d_n);
     hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
     return launch_select(e, s, a, k, min_score);
+}
+
+// ---- K7 by a trend key ------------------------------------------------------------------------------------------------------
+namespace {
+// by > 3: SG_EINVAL; a trend key without the trend: SG_ESTATE (engine lock held; before anything is closed or enqueued)
+int check_by(sg_engine* e, u32 by) {
+    if (by > SG_SEL_NEW) { e->err = "selection: unknown key (by > SG_SEL_NEW)"; return SG_EINVAL; }
+    if (by != SG_SEL_SCORE && !e->trend.on) { e->err = "selection by a trend key: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    return SG_OK;
+}
+}  // namespace
+int sg_flush_end_top_by(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_edge_out* out, uint32_t* row_index, size_t cap,
+                        size_t* n_selected, size_t* n_edges) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (const int rc = check_by(e, by)) return rc;
+    return flush_end_top_unlocked(e, g, k, min_value, out, row_index, cap, n_selected, n_edges, by);
+}
+int sg_flush_window_top_by(sg_handle e, uint64_t window_end_ms, uint32_t by, uint32_t k, float min_value, sg_edge_out* out,
+                           uint32_t* row_index, size_t cap, size_t* n_selected, size_t* n_edges) {
+    (void)window_end_ms;
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (const int rc = check_by(e, by)) return rc;
+    e->cv.wait(g, [&] { return !e->closing && !e->flush_open; });
+    if (const int rc = flush_begin_locked(e, g, false)) return rc;
+    return flush_end_top_unlocked(e, g, k, min_value, out, row_index, cap, n_selected, n_edges, by);
+}
+// sg_window_select by a trend key: the trend rows of the slot sg_window_run closed last (the slot of sg_window_rows_buffer's rows)
+int sg_window_select_by(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_edge_out* d_out, uint32_t* d_index, size_t cap,
+                        uint64_t* d_n, void* stream) {
+    if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = check_by(e, by)) return rc;
+    if (const int rc = sel_reserve(e, 0)) return rc;
+    SelArgs a{};
+    a.rows = e->last_rows ? e->last_rows : e->d.rows;
+    a.ctr = e->last_rows ? e->last_ctr : e->d.ctr;
+    a.out = d_out; a.out_idx = d_index; a.cap = cap; a.n_out = reinterpret_cast<u64*>(d_n);
+    const sg_edge_trend* tr = by != SG_SEL_SCORE ? e->trend.rows[e->trend.run_slot >= 0 ? e->trend.run_slot : e->cur] : nullptr;
+    hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
+    return launch_select(e, s, a, k, min_value, by, tr);
 }
 
 // ---- K8, the per-edge baselines ------------------------------------------------------------------------------------------------
@@ -1638,6 +1708,60 @@ int sg_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
     out->windows = ctl[K8C_WINDOWS]; out->entries = ctl[K8C_B0 + (t.w & 1u)];
     out->inserted = ctl[K8C_INSERTED]; out->expired = ctl[K8C_EXPIRED]; out->dropped = ctl[K8C_DROPPED];
+    return SG_OK;
+}
+
+// ---- K8's vanished list ---------------------------------------------------------------------------------------------------
+int sg_set_vanished(sg_handle e, const sg_vanished_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->trend.on) { e->err = "sg_set_vanished: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_vanished while a flush is open"; return SG_ESTATE; }
+    sg_vanished_params r{};
+    if (p && sgplan::check_vanished(*p, e->trend.p, &r)) { e->err = "sg_set_vanished: bad parameters"; return SG_EINVAL; }
+    free_vanished(e);
+    if (!p) return SG_OK;
+    sg_engine::Vanished& v = e->vanished;
+    const u32 slots = (u32)std::max<size_t>(e->slots.size(), 1);
+    v.p = r;
+    v.plan = sgplan::plan_vanished(e->trend.plan, slots, r);
+    const sgplan::VanishedPlan& P = v.plan;
+    {
+        const hipError_t rc = hipMalloc((void**)&v.mem, P.total_bytes);
+        if (rc != hipSuccess) { free_vanished(e); e->err = std::string("sg_set_vanished: hipMalloc: ") + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
+    }
+    HIP_TRY(e, hipMemset(v.mem, 0, P.total_bytes));
+    char* b = v.mem;
+    v.th = (u32*)b; b += P.thread_bytes;
+    v.blk = (u32*)b; b += P.blk_bytes;
+    for (u32 k = 0; k < slots; k++) { v.rows.push_back((sg_edge_vanished*)b); b += P.list_bytes; v.count.push_back((u64*)b); b += P.count_bytes; }
+    v.valid.assign(slots, 0);
+    v.on = true;
+    return SG_OK;
+}
+int sg_window_vanished(sg_handle e, sg_edge_vanished* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Vanished& v = e->vanished;
+    if (!v.on) { e->err = "sg_window_vanished: the vanished list is off (sg_set_vanished)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_window_vanished while a flush is open"; return SG_ESTATE; }
+    if (!v.valid[e->cur]) { e->err = "sg_window_vanished: the last read window was closed while the vanished list was off"; return SG_ESTATE; }
+    if (e->trend.pending) HIP_TRY(e, hipEventSynchronize(e->trend.ev));
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, v.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    if (n) *n = (size_t)cnt;
+    const size_t take = (size_t)std::min<u64>(std::min<u64>(cnt, v.plan.rows), cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, v.rows[e->cur], take * sizeof(sg_edge_vanished), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+int sg_window_vanished_buffer(sg_handle e, void** d_rows, void** d_count) {
+    if (!e || !d_rows || !d_count) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Vanished& v = e->vanished;
+    if (!v.on) { e->err = "sg_window_vanished_buffer: the vanished list is off (sg_set_vanished)"; return SG_ESTATE; }
+    const int slot = e->trend.run_slot >= 0 ? e->trend.run_slot : e->cur;
+    if (!v.valid[slot]) { e->err = "sg_window_vanished_buffer: the window was closed while the vanished list was off"; return SG_ESTATE; }
+    *d_rows = v.rows[slot]; *d_count = v.count[slot];
     return SG_OK;
 }
 

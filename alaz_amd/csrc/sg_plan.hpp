@@ -429,6 +429,39 @@ inline TrendPlan plan_trend(u64 max_edges, u32 slots, const sg_trend_params& p) 
     return t;
 }
 
+// K8's vanished list (sg_set_vanished): the parameters with their defaults filled in against the trend's resolved parameters, and
+// the device memory sg_set_vanished allocates — never sg_create or sg_set_trend.  The per-thread and per-workgroup counts are
+// scratch of k8_count_v / k8_scan_v / k8_write_v (the trend's grid); each window slot keeps its list and its count.
+constexpr u32 kVanishedDefaultRows = 65536;
+inline int check_vanished(const sg_vanished_params& p, const sg_trend_params& trend, sg_vanished_params* out) {
+    if (p.struct_size != sizeof(sg_vanished_params)) return SG_EINVAL;
+    sg_vanished_params r = p;
+    if (!r.silent_windows) r.silent_windows = 1;
+    if (!r.min_seen) r.min_seen = trend.warmup;
+    if (!r.max_rows) r.max_rows = (u32)std::min<u64>(kVanishedDefaultRows, trend.max_entries);
+    if (r.silent_windows >= trend.ttl || r.max_rows > trend.max_entries) return SG_EINVAL;
+    *out = r;
+    return SG_OK;
+}
+struct VanishedPlan {
+    u64 rows = 0;                 // max_rows
+    u64 thread_bytes = 0;         // [wgs * 256] u32 per-thread counts
+    u64 blk_bytes = 0;            // [wgs] u32 per-workgroup counts
+    u64 list_bytes = 0;           // one window slot's list: [max_rows] sg_edge_vanished
+    u64 count_bytes = 0;          // one window slot's count (u64)
+    u64 total_bytes = 0;          // the scratch and every slot's list and count, each 256-byte aligned
+};
+inline VanishedPlan plan_vanished(const TrendPlan& t, u32 slots, const sg_vanished_params& p) {
+    VanishedPlan v;
+    v.rows = p.max_rows;
+    v.thread_bytes = trend_align((u64)t.wgs * kTrendThreads * 4);
+    v.blk_bytes = trend_align((u64)t.wgs * 4);
+    v.list_bytes = trend_align(std::max<u64>(p.max_rows, 1) * sizeof(sg_edge_vanished));
+    v.count_bytes = trend_align(8);
+    v.total_bytes = v.thread_bytes + v.blk_bytes + (u64)std::max<u32>(slots, 1) * (v.list_bytes + v.count_bytes);
+    return v;
+}
+
 // K9, the node rollup (sg_nodes.h): the device memory sg_set_nodes allocates — never sg_create.  Nodes are keyed by an id below
 // ncap = max_known + max_labels + max_obip.  k9_out takes chunks of 2048 rows (256 threads x 8); k9_in_part a grid of node ranges
 // of 2048 (128 KiB of LDS each) x row slices — about 32 K rows per slice, at most 16 slices, as k3_in_part; k9_count / k9_write

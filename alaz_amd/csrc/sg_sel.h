@@ -5,6 +5,7 @@
 // workgroups run in (per-workgroup LDS histograms and counts, reduced by one workgroup; no global atomics).
 //
 //   k7_keys     key of every row (0 = not a candidate) + per-workgroup histogram of the key's top byte
+//   k7_keys_by  the same from the window's trend rows (sg_edge_trend: lat_dev / err_dev, or windows_seen == 0 with count > 0)
 //   k7_pick     (1 workgroup) round r of the MSD radix select: which byte of the k-th largest key, how many above it
 //   k7_hist     per-workgroup histogram of byte r among the keys that share the bytes picked so far (rounds 1..3)
 //   k7_count    per workgroup: keys above the threshold key T, keys equal to T
@@ -85,6 +86,32 @@ __global__ __launch_bounds__(K7_THREADS) void k7_keys(SelArgs a) {
     }
     for (; i < hi; i += K7_THREADS) {
         const u32 key = k7_key(sc[i * 16], a.min_score);
+        a.keys[i] = key;
+        if (key && a.k) atomicAdd(&h[key >> 24], 1u);
+    }
+    __syncthreads();
+    a.hist[(size_t)blockIdx.x * 256 + t] = h[t];
+}
+
+// k7_keys with the key of a trend value (SG_SEL_LAT_DEV: byte 0 of a 16-byte sg_edge_trend, SG_SEL_ERR_DEV: byte 4) or, for
+// SG_SEL_NEW, one key for every new dependency (windows_seen == 0 and count > 0): ties by row position give the first k of them
+__global__ __launch_bounds__(K7_THREADS) void k7_keys_by(SelArgs a, const sg_edge_trend* tr, u32 by) {
+    __shared__ u32 h[256];
+    const u32 t = threadIdx.x;
+    h[t] = 0;
+    if (blockIdx.x == 0 && t == 0) {
+        a.state[K7S_PREFIX] = 0; a.state[K7S_REM] = a.k; a.state[K7S_DONE] = a.k == 0 ? 1u : 0u; a.state[K7S_SEL] = 0;
+    }
+    __syncthreads();
+    const u64 E = k7_rows(a);
+    u64 lo, hi; k7_span(E, lo, hi);
+    const u32* tw = reinterpret_cast<const u32*>(tr);                      // 4 words per trend row
+    const u32* cw = reinterpret_cast<const u32*>(a.rows) + 8;               // count: byte 32 of a 64-byte row
+    const u32 off = by == SG_SEL_ERR_DEV ? 1u : 0u;
+    for (u64 i = lo + t; i < hi; i += K7_THREADS) {
+        u32 key;
+        if (by == SG_SEL_NEW) key = tw[i * 4 + 3] == 0u && cw[i * 16] > 0u ? 0x80000000u : 0u;
+        else key = k7_key(__uint_as_float(tw[i * 4 + off]), a.min_score);
         a.keys[i] = key;
         if (key && a.k) atomicAdd(&h[key >> 24], 1u);
     }

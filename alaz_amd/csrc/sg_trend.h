@@ -14,6 +14,11 @@
 // looks at the row behind it (the next row of the walk).  Each element decides alone, so a matched pair that straddles two spans
 // needs nothing special.  Nothing depends on workgroup order and there are no global atomics: every count is reduced in order.
 // The device control block keeps B per parity: window w reads buffer / B of parity (w - 1) & 1 and writes those of parity w & 1.
+//
+// Vanished dependencies (sg_set_vanished) ride on the same walk: k8_count_v / k8_scan_v / k8_write_v are the three kernels with one
+// more count.  An old entry the walk passes that is not refreshed, has seen min_seen windows and went without a sample for exactly
+// silent windows is counted per thread and per workgroup, scanned, and written at its key-order position; the row behind it (the
+// next row of the walk) is the window's alive-only row with its key, if there is one.  With the list off the plain kernels run.
 #pragma once
 
 #define K8_THREADS 256            // k8_count / k8_write
@@ -46,6 +51,16 @@ struct TrendArgs {
     u64* ctl;                     // [K8C_WORDS]
     u32 w, warmup, ttl, pad;
     double alpha, lat_floor, err_floor;
+};
+
+// the vanished list of one window (sg_set_vanished): per slot the list and its count, the per-thread / per-workgroup counts scratch
+struct VanArgs {
+    sg_edge_vanished* out;        // [max_rows] the window slot's list
+    u64* count;                   // the slot's count: every vanished entry of the window
+    u32* th;                      // [wgs * K8_THREADS] per-thread counts (k8_count_v)
+    u32* blk;                     // [wgs] per-workgroup counts -> vanished before (k8_scan_v)
+    u64 max_rows;
+    u32 silent, min_seen;
 };
 
 struct K8Key { u64 f, t; };
@@ -99,9 +114,10 @@ __device__ __forceinline__ double k8_x_lat(const K8Row& r) {
 __device__ __forceinline__ double k8_x_err(const K8Row& r) { return (double)(((u64)r.err << 20) / r.count); }
 
 // The walk of one thread's span, shared by both passes.  WRITE = false: trend rows + counts; true: the merged entries.
-template <bool WRITE>
-__device__ __forceinline__ void k8_walk(const TrendArgs& a, const K8Geom& g, u64 i, u64 j, u64 n, u32& kept, u32& fresh, u32& expired,
-                                        u64 kb, u64 nb, u64 room) {
+// VAN: also count (and with WRITE write) the vanished entries: van counts them, vb = the position of this thread's first one.
+template <bool WRITE, bool VAN>
+__device__ __forceinline__ void k8_walk_t(const TrendArgs& a, const K8Geom& g, u64 i, u64 j, u64 n, u32& kept, u32& fresh, u32& expired,
+                                        u64 kb, u64 nb, u64 room, const VanArgs& v, u32& van, u64 vb) {
 #pragma clang fp contract(off)
     const TrendSoA& A = *g.old;
     K8Key ak{}, pk{};                                   // the old entry at i, the one in front of it (i - 1)
@@ -114,6 +130,21 @@ __device__ __forceinline__ void k8_walk(const TrendArgs& a, const K8Geom& g, u64
             const bool upd = j < g.E && r.count > 0 && k8_eq(ak, r.k);
             const u32 last = A.last[i];
             const bool keep = upd || a.w - last < a.ttl;
+            if (VAN && !upd && a.w - last == v.silent && A.n[i] >= v.min_seen) {   // (silent < ttl: kept, unchanged)
+                if (WRITE) {
+                    const u64 p = vb + van;
+                    if (p < v.max_rows) {
+                        sg_edge_vanished x;
+                        x.from_key = ak.f; x.to_key = ak.t;
+                        x.lat_mean = A.lat_mean[i]; x.lat_dev = A.lat_dev[i]; x.err_mean = A.err_mean[i]; x.err_dev = A.err_dev[i];
+                        x.n = A.n[i]; x.last = last;
+                        x.row = j < g.E && k8_eq(ak, r.k) ? (u32)j : 0xFFFFFFFFu;    // the row behind it: alive-only (upd is false)
+                        x.reserved = 0;
+                        v.out[p] = x;
+                    }
+                }
+                van++;
+            }
             if (keep) {
                 if (WRITE) {
                     const u64 p = kb + (nb < room ? nb : room);
@@ -175,6 +206,14 @@ __device__ __forceinline__ void k8_walk(const TrendArgs& a, const K8Geom& g, u64
     }
 }
 
+// the plain walk (k8_count / k8_write)
+template <bool WRITE>
+__device__ __forceinline__ void k8_walk(const TrendArgs& a, const K8Geom& g, u64 i, u64 j, u64 n, u32& kept, u32& fresh, u32& expired,
+                                        u64 kb, u64 nb, u64 room) {
+    u32 van = 0;
+    k8_walk_t<WRITE, false>(a, g, i, j, n, kept, fresh, expired, kb, nb, room, VanArgs{}, van, 0);
+}
+
 __global__ __launch_bounds__(K8_THREADS) void k8_count(TrendArgs a) {
     __shared__ u32 ws[3][K8_THREADS / 64];
     const u32 t = threadIdx.x;
@@ -201,6 +240,35 @@ __global__ __launch_bounds__(K8_THREADS) void k8_count(TrendArgs a) {
     }
 }
 
+// k8_count with the vanished entries counted per thread and per workgroup
+__global__ __launch_bounds__(K8_THREADS) void k8_count_v(TrendArgs a, VanArgs v) {
+    __shared__ u32 ws[4][K8_THREADS / 64];
+    const u32 t = threadIdx.x;
+    const K8Geom g = k8_geom(a);
+    const u64 T = g.B + g.E;
+    u64 d0, d1; k8_span(T, d0, d1);
+    // merge path: how many old entries are among the first d0 merged elements (old first on equal keys)
+    u64 lo = d0 > g.E ? d0 - g.E : 0, hi = d0 < g.B ? d0 : g.B;
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (k8_le(k8_entry_key(*g.old, mid), k8_row(a, d0 - 1 - mid, g.nob).k)) lo = mid + 1; else hi = mid;
+    }
+    u32 kept = 0, fresh = 0, expired = 0, van = 0;
+    k8_walk_t<false, true>(a, g, lo, d0 - lo, d1 - d0, kept, fresh, expired, 0, 0, 0, v, van, 0);
+    K8Thread& me = a.th[(size_t)blockIdx.x * K8_THREADS + t];
+    me.i = lo; me.kept = kept; me.fresh = fresh;
+    v.th[(size_t)blockIdx.x * K8_THREADS + t] = van;
+    kept = wave_sum_u32(kept); fresh = wave_sum_u32(fresh); expired = wave_sum_u32(expired); van = wave_sum_u32(van);
+    if ((t & 63) == 0) { ws[0][t >> 6] = kept; ws[1][t >> 6] = fresh; ws[2][t >> 6] = expired; ws[3][t >> 6] = van; }
+    __syncthreads();
+    if (t == 0) {
+        u32 k = 0, f = 0, x = 0, y = 0;
+        for (int w = 0; w < K8_THREADS / 64; w++) { k += ws[0][w]; f += ws[1][w]; x += ws[2][w]; y += ws[3][w]; }
+        a.blk[(size_t)blockIdx.x * 4] = k; a.blk[(size_t)blockIdx.x * 4 + 1] = f; a.blk[(size_t)blockIdx.x * 4 + 2] = x;
+        v.blk[blockIdx.x] = y;
+    }
+}
+
 // one workgroup: exclusive scans of the per-workgroup counts, the capacity cut (the kept old entries never exceed max_entries: the
 // first max_entries - kept new ones in key order go in), the new B and the running statistics
 __global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan(TrendArgs a, u32 nwg) {
@@ -212,6 +280,35 @@ __global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan(TrendArgs a, u32 nwg)
     const u32 fb = block_excl_scan<K8_SCAN_THREADS>(f, wsum, &ftot);
     block_excl_scan<K8_SCAN_THREADS>(x, wsum, &xtot);
     if (t < nwg) { a.blk[(size_t)t * 4 + 2] = kb; a.blk[(size_t)t * 4 + 3] = fb; }
+    if (t == 0) {
+        const u64 room = a.cap > ktot ? a.cap - ktot : 0ull;
+        const u64 ins = ftot < room ? ftot : room;
+        a.ctl[K8C_ROOM] = room;
+        a.ctl[K8C_B0 + (a.w & 1u)] = ktot + ins;
+        a.ctl[K8C_WINDOWS] += 1;
+        a.ctl[K8C_INSERTED] += ins;
+        a.ctl[K8C_EXPIRED] += xtot;
+        a.ctl[K8C_DROPPED] += ftot - ins;
+    }
+}
+
+// k8_scan with the vanished counts scanned too: their per-workgroup base and the window's count
+__global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan_v(TrendArgs a, u32 nwg, VanArgs v) {
+    __shared__ u32 wsum[K8_SCAN_THREADS / 64 + 1];
+    const u32 t = threadIdx.x;
+    const u32 k = t < nwg ? a.blk[(size_t)t * 4] : 0u, f = t < nwg ? a.blk[(size_t)t * 4 + 1] : 0u, x = t < nwg ? a.blk[(size_t)t * 4 + 2] : 0u;
+    u32 ktot, ftot, xtot;
+    const u32 kb = block_excl_scan<K8_SCAN_THREADS>(k, wsum, &ktot);
+    const u32 fb = block_excl_scan<K8_SCAN_THREADS>(f, wsum, &ftot);
+    block_excl_scan<K8_SCAN_THREADS>(x, wsum, &xtot);
+    if (t < nwg) { a.blk[(size_t)t * 4 + 2] = kb; a.blk[(size_t)t * 4 + 3] = fb; }
+    {
+        u32 vtot;
+        const u32 y = t < nwg ? v.blk[t] : 0u;
+        const u32 yb = block_excl_scan<K8_SCAN_THREADS>(y, wsum, &vtot);
+        if (t < nwg) v.blk[t] = yb;
+        if (t == 0) *v.count = vtot;
+    }
     if (t == 0) {
         const u64 room = a.cap > ktot ? a.cap - ktot : 0ull;
         const u64 ins = ftot < room ? ftot : room;
@@ -237,6 +334,23 @@ __global__ __launch_bounds__(K8_THREADS) void k8_write(TrendArgs a) {
     const u64 kb = (u64)a.blk[(size_t)blockIdx.x * 4 + 2] + kx, nb = (u64)a.blk[(size_t)blockIdx.x * 4 + 3] + fx;
     u32 kept = 0, fresh = 0, expired = 0;
     k8_walk<true>(a, g, me.i, d0 - me.i, d1 - d0, kept, fresh, expired, kb, nb, a.ctl[K8C_ROOM]);
+}
+
+// k8_write with each vanished entry written at its key-order position
+__global__ __launch_bounds__(K8_THREADS) void k8_write_v(TrendArgs a, VanArgs v) {
+    __shared__ u32 wsum[K8_THREADS / 64 + 1];
+    const u32 t = threadIdx.x;
+    const K8Geom g = k8_geom(a);
+    const u64 T = g.B + g.E;
+    u64 d0, d1; k8_span(T, d0, d1);
+    const K8Thread me = a.th[(size_t)blockIdx.x * K8_THREADS + t];
+    u32 tot;
+    const u32 kx = block_excl_scan<K8_THREADS>(me.kept, wsum, &tot);
+    const u32 fx = block_excl_scan<K8_THREADS>(me.fresh, wsum, &tot);
+    const u64 kb = (u64)a.blk[(size_t)blockIdx.x * 4 + 2] + kx, nb = (u64)a.blk[(size_t)blockIdx.x * 4 + 3] + fx;
+    const u64 vb = (u64)v.blk[blockIdx.x] + block_excl_scan<K8_THREADS>(v.th[(size_t)blockIdx.x * K8_THREADS + t], wsum, &tot);
+    u32 kept = 0, fresh = 0, expired = 0, van = 0;
+    k8_walk_t<true, true>(a, g, me.i, d0 - me.i, d1 - d0, kept, fresh, expired, kb, nb, a.ctl[K8C_ROOM], v, van, vb);
 }
 
 // sg_window_trend with an index: the asked-for rows gathered on the device, so that only they cross PCIe

@@ -45,6 +45,8 @@ EXPORTS = [
     "sg_flush_window_top", "sg_flush_end_top", "sg_window_select",
     "sg_set_trend", "sg_window_trend", "sg_window_trend_buffer", "sg_trend_entries", "sg_trend_stats_get",
     "sg_set_nodes", "sg_window_nodes", "sg_window_nodes_buffer",
+    "sg_set_vanished", "sg_window_vanished", "sg_window_vanished_buffer",
+    "sg_flush_window_top_by", "sg_flush_end_top_by", "sg_window_select_by",
 ]
 
 #: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
@@ -55,6 +57,14 @@ TREND_ENTRY_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean
 NODE_DTYPE = np.dtype([(f"{side}_{f}", "<u8") for f in ("count", "err", "sum_ns", "sumsq_us", "max_ns", "score_q32") for side in ("out", "in")]
                       + [(f, "<u4") for f in ("ref", "out_edges", "in_edges", "out_alive", "in_alive", "out_worst_row", "in_worst_row")]
                       + [(f, "<f4") for f in ("out_score_max", "in_score_max", "score")])
+#: sg_edge_vanished (64 bytes) of include/servicegraph.h: one baseline entry that went silent (K8's vanished list)
+VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
+                           ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4"), ("row", "<u4"), ("reserved", "<u4")])
+#: sg_vanished_params defaults (a 0 in the struct means the same: silent_windows 1, min_seen = the trend's warmup, max_rows =
+#: min(65536, max_entries))
+VANISHED_DEFAULTS = dict(silent_windows=0, min_seen=0, max_rows=0)
+#: SG_SEL_*: the key of a selection
+SEL_BY = dict(score=0, lat_dev=1, err_dev=2, new=3)
 #: sg_trend_params defaults (a 0 in the struct means the same)
 TREND_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, lat_floor_ns=1000, err_floor=10486)
 
@@ -101,6 +111,10 @@ class SgStats(C.Structure):
 class SgTrendParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("shift", C.c_uint32), ("warmup", C.c_uint32), ("ttl", C.c_uint32),
                 ("max_entries", C.c_uint64), ("lat_floor_ns", C.c_uint64), ("err_floor", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SgVanishedParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("silent_windows", C.c_uint32), ("min_seen", C.c_uint32), ("max_rows", C.c_uint32)]
 
 
 class SgTrendStats(C.Structure):
@@ -199,6 +213,11 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_trend_stats_get": (C.c_int, [H, P]),
         "sg_set_nodes": (C.c_int, [H, C.c_int]), "sg_window_nodes": (C.c_int, [H, P, sz, C.POINTER(sz)]),
         "sg_window_nodes_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+        "sg_set_vanished": (C.c_int, [H, P]), "sg_window_vanished": (C.c_int, [H, P, sz, C.POINTER(sz)]),
+        "sg_window_vanished_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+        "sg_flush_window_top_by": (C.c_int, [H, u64, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "sg_flush_end_top_by": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "sg_window_select_by": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -380,20 +399,39 @@ class ServiceGraph:
         m = min(ns.value, cap)
         return out[:m], idx[:m], ne.value
 
-    def flush_window_top(self, k: int, min_score: float = float("-inf"), window_end_ms: int = 0, cap: Optional[int] = None):
+    @staticmethod
+    def _by(by) -> int:
+        if by not in SEL_BY:
+            raise ValueError(f"by must be one of {sorted(SEL_BY)}, not {by!r}")
+        return SEL_BY[by]
+
+    def flush_window_top(self, k: int, min_score: float = float("-inf"), window_end_ms: int = 0, cap: Optional[int] = None,
+                         by: str = "score"):
         """Close the window and return (rows, row_index, n_edges) of its selection (sg_flush_window_top): k = 0 every row with
         score >= min_score in canonical order, else the k highest-scoring such rows, descending, ties by row position.  cap
-        defaults to k (k > 0) or max_edges; rows beyond it are counted, not returned."""
+        defaults to k (k > 0) or max_edges; rows beyond it are counted, not returned.  by = "lat_dev" / "err_dev" / "new" selects
+        by the row's trend instead of its score (sg_flush_window_top_by; min_score is then the threshold on that value)."""
+        b = self._by(by)
+        if b:
+            return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_window_top_by(self._h, window_end_ms, b, k, min_score, o, i, c, ns, ne), k, cap)
         return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_window_top(self._h, window_end_ms, k, min_score, o, i, c, ns, ne), k, cap)
 
-    def flush_end_top(self, k: int, min_score: float = float("-inf"), cap: Optional[int] = None):
-        """flush_window_top for the window flush_begin closed (sg_flush_end_top)."""
+    def flush_end_top(self, k: int, min_score: float = float("-inf"), cap: Optional[int] = None, by: str = "score"):
+        """flush_window_top for the window flush_begin closed (sg_flush_end_top / sg_flush_end_top_by)."""
+        b = self._by(by)
+        if b:
+            return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_end_top_by(self._h, b, k, min_score, o, i, c, ns, ne), k, cap)
         return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_end_top(self._h, k, min_score, o, i, c, ns, ne), k, cap)
 
-    def window_select(self, k: int, min_score: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
+    def window_select(self, k: int, min_score: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0, by: str = "score"):
         """Select from the rows of the window window_run closed last into device memory (sg_window_select): d_out [cap] rows,
-        d_index [cap] u32 (0 = none), d_n one u64 = rows selected; enqueued on `stream` (0 = that window's stream)."""
-        self._ck(self._l.sg_window_select(self._h, k, min_score, d_out or None, d_index or None, cap, d_n, stream or None))
+        d_index [cap] u32 (0 = none), d_n one u64 = rows selected; enqueued on `stream` (0 = that window's stream).  by as in
+        flush_window_top (sg_window_select_by: that window's trend rows)."""
+        b = self._by(by)
+        if b:
+            self._ck(self._l.sg_window_select_by(self._h, b, k, min_score, d_out or None, d_index or None, cap, d_n, stream or None))
+        else:
+            self._ck(self._l.sg_window_select(self._h, k, min_score, d_out or None, d_index or None, cap, d_n, stream or None))
 
     # ---- per-edge baselines (K8): each edge against its own past ----
     def set_trend(self, params: Optional[dict] = (), **kw):
@@ -412,6 +450,7 @@ class ServiceGraph:
         p = SgTrendParams(v.get("struct_size", C.sizeof(SgTrendParams)), v["shift"], v["warmup"], v["ttl"], v["max_entries"],
                           v["lat_floor_ns"], v["err_floor"], v.get("reserved", 0))
         self._ck(self._l.sg_set_trend(self._h, C.byref(p)))
+        self._trend_entries = v["max_entries"] or min(1 << 31, 2 * max(self.max_edges, 1))   # the baseline's capacity
 
     def window_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
         """TREND_DTYPE rows of the last read window (sg_window_trend): every row, or the rows at `index` (only those cross PCIe)."""
@@ -447,6 +486,41 @@ class ServiceGraph:
         s = SgTrendStats()
         self._ck(self._l.sg_trend_stats_get(self._h, C.byref(s)))
         return s
+
+    def set_vanished(self, params: Optional[dict] = (), **kw):
+        """Switch K8's vanished list on (sg_set_vanished; silent_windows, min_seen, max_rows as keywords or a dict — see
+        VANISHED_DEFAULTS; needs the trend on) or off: set_vanished(None).  Any set_trend call switches it off."""
+        if params is None:
+            if kw:
+                raise TypeError("set_vanished(None) switches the list off and takes no parameters")
+            self._ck(self._l.sg_set_vanished(self._h, None))
+            return
+        v = dict(VANISHED_DEFAULTS)
+        v.update(params or {}); v.update(kw)
+        unknown = set(v) - set(VANISHED_DEFAULTS) - {"struct_size"}
+        if unknown:
+            raise TypeError(f"unknown vanished parameters: {sorted(unknown)}")
+        p = SgVanishedParams(v.get("struct_size", C.sizeof(SgVanishedParams)), v["silent_windows"], v["min_seen"], v["max_rows"])
+        self._ck(self._l.sg_set_vanished(self._h, C.byref(p)))
+        self._van_rows = v["max_rows"] or min(65536, self._trend_entries)   # (the rows a window's list holds at most)
+
+    def window_vanished(self, with_count: bool = False):
+        """VANISHED_DTYPE list of the last read window (sg_window_vanished), ascending by edge key; with_count: (list, count of
+        every vanished entry of the window, which may exceed max_rows)."""
+        n = C.c_size_t(0)
+        self._ck(self._l.sg_window_vanished(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=VANISHED_DTYPE)
+        if n.value:
+            self._ck(self._l.sg_window_vanished(self._h, out.ctypes.data, n.value, C.byref(n)))
+        rows = out[: min(n.value, self._van_rows)]
+        return (rows, n.value) if with_count else rows
+
+    def vanished_buffer(self) -> Tuple[int, int]:
+        """(device pointer of the sg_edge_vanished list, device pointer of its u64 count) of the window window_run closed last
+        (sg_window_vanished_buffer)"""
+        p, c = C.c_void_p(), C.c_void_p()
+        self._ck(self._l.sg_window_vanished_buffer(self._h, C.byref(p), C.byref(c)))
+        return p.value, c.value
 
     # ---- node rollup (K9): each window's rows reduced per node on the device ----
     def set_nodes(self, on: bool = True):

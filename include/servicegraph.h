@@ -360,6 +360,59 @@ int sg_window_trend_buffer(sg_handle h, void** d_trend);
 int sg_trend_entries(sg_handle h, sg_trend_entry* out, size_t cap, size_t* n);
 int sg_trend_stats_get(sg_handle h, sg_trend_stats* out);   /* (waits for the updates enqueued so far) */
 
+/* Vanished dependencies: the baseline entries that stopped getting samples.  Opt-in (sg_set_vanished, on an engine with the trend);
+ * the trend's rows and entries are the same either way.  In trend window w an OLD entry (one that was in the baseline before the
+ * window) is vanished when all of these hold:
+ *   - no row of the window with its key and count > 0 refreshes it;
+ *   - its n >= min_seen;
+ *   - w - last == silent_windows.
+ * So an entry is reported once per silence, in the silent_windows-th window without a sample, and again if it comes back and goes
+ * silent again.  New entries the capacity cut dropped were never old entries: they are never reported.  silent_windows < ttl, so a
+ * reported entry has not expired: its fields are the entry as it stands after the window (unchanged by it).  row = the position of
+ * the window's alive-only row (count == 0) with the entry's key, 0xFFFFFFFF when the window has no row with it.
+ * The list of a window is in ascending key order (the merge order); *n counts every vanished entry of the window, and the first
+ * min(*n, max_rows, cap) in key order are written.                                                                             */
+typedef struct sg_vanished_params {
+    uint32_t struct_size;       /* sizeof(sg_vanished_params)                                                                 */
+    uint32_t silent_windows;    /* 1 .. ttl - 1 (0 = 1)                                                                       */
+    uint32_t min_seen;          /* windows an entry must have seen (0 = the trend's warmup)                                   */
+    uint32_t max_rows;          /* rows kept per window, 1 .. max_entries (0 = min(65536, max_entries))                       */
+} sg_vanished_params;
+typedef struct sg_edge_vanished {
+    uint64_t from_key, to_key;                      /* K8's edge key                                                         */
+    double   lat_mean, lat_dev, err_mean, err_dev;  /* the entry as it stands after the window                                */
+    uint32_t n, last;                               /* windows seen; trend window of its last sample                          */
+    uint32_t row;                                   /* this window's alive-only row with the key, else 0xFFFFFFFF              */
+    uint32_t reserved;                              /* 0                                                                      */
+} sg_edge_vanished;             /* 64 bytes, no padding */
+/* NULL = off (frees the lists); params = on: the per-slot lists are allocated here, never at create.  SG_ESTATE when the trend is
+ * off or a flush is open, SG_EINVAL on bad params.  Any sg_set_trend call switches the vanished list off and frees it.           */
+int sg_set_vanished(sg_handle h, const sg_vanished_params* p);
+/* The vanished list of the last READ window (as sg_window_nodes).  SG_ESTATE for a window closed while the list was off, and while
+ * a flush is open.                                                                                                              */
+int sg_window_vanished(sg_handle h, sg_edge_vanished* out, size_t cap, size_t* n);
+/* Device sg_edge_vanished[max_rows] and its count (one uint64_t) of the window sg_window_run / sg_window_run_sharded closed last
+ * (valid until its slot is reused; read them on that window's stream).                                                         */
+int sg_window_vanished_buffer(sg_handle h, void** d_rows, void** d_count);
+
+/* Selection (K7) by a trend key: the K7 semantics with the score replaced by the chosen value of the row's sg_edge_trend — a plain
+ * float comparison value >= min_value (NaN never), k = 0 every candidate in canonical order, 1 <= k <= SG_SELECT_MAX_K the highest
+ * values descending, ties (-0.0 == +0.0) by row position.  SG_SEL_NEW: the candidates are the rows with windows_seen == 0 and
+ * count > 0, all with the same key (min_value ignored): k > 0 gives the first k new edges in canonical order.  Rows are byte-identical
+ * to the plain flush's; row_index can be passed straight to sg_window_trend.  by > 3: SG_EINVAL; a trend key on an engine without the
+ * trend: SG_ESTATE — both before any window is closed.  by = SG_SEL_SCORE is the plain selection (same bytes).                   */
+#define SG_SEL_SCORE   0u   /* = sg_flush_window_top and friends                                                              */
+#define SG_SEL_LAT_DEV 1u   /* sg_edge_trend.lat_dev of the row                                                               */
+#define SG_SEL_ERR_DEV 2u   /* sg_edge_trend.err_dev of the row                                                               */
+#define SG_SEL_NEW     3u   /* rows with windows_seen == 0 and count > 0; min_value ignored                                   */
+int sg_flush_window_top_by(sg_handle h, uint64_t window_end_ms, uint32_t by, uint32_t k, float min_value,
+                           sg_edge_out* out, uint32_t* row_index, size_t cap, size_t* n_selected, size_t* n_edges);
+int sg_flush_end_top_by(sg_handle h, uint32_t by, uint32_t k, float min_value,
+                        sg_edge_out* out, uint32_t* row_index, size_t cap, size_t* n_selected, size_t* n_edges);
+/* sg_window_select by a trend key: the trend rows of the window sg_window_rows_buffer names.                                    */
+int sg_window_select_by(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_edge_out* d_out, uint32_t* d_index,
+                        size_t cap, uint64_t* d_n, void* stream);
+
 /* ---- node rollup (K9): each window's scored edges reduced per node, on the device ------------------------------------------ *
  * Opt-in (sg_set_nodes); an engine without it computes and allocates nothing for it, and its rows are the same either way.
  * Over the window's rows r_0 .. r_{E-1} in canonical order, the node set is every from_ref and to_ref of some row.  Node rows come

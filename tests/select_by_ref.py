@@ -1,0 +1,17 @@
+"""numpy reference of the selection by a trend key (sg_flush_window_top_by, include/servicegraph.h): the positions K7 selects when
+the key is a row's sg_edge_trend value instead of its score."""
+import numpy as np
+
+
+def ref_select_by(rows, trend, by, k, min_value):
+    """positions selected from `rows` (canonical order) with `trend` = the window's TREND_DTYPE rows"""
+    if by == "new":
+        ci = np.flatnonzero((trend["windows_seen"] == 0) & (rows["count"] > 0))
+        return ci[: k if k else len(ci)].astype(np.uint32)         # one key for all: canonical order
+    v = trend[by]
+    with np.errstate(invalid="ignore"):
+        ci = np.flatnonzero(v >= np.float32(min_value))
+    if k == 0:
+        return ci.astype(np.uint32)
+    cs = v[ci].astype(np.float64) + 0.0                               # -0.0 == +0.0
+    return ci[np.lexsort((ci, -cs))][:k].astype(np.uint32)
