@@ -86,6 +86,8 @@ struct sg_engine {
 
     u64 first_kernel = 0, first_user = 0;
     float* d_W = nullptr; bool have_w = false;
+    // per stream that has run K4 / K5: an event behind its last such launch (sg_load_weights waits for them before it overwrites d_W)
+    std::vector<std::pair<hipStream_t, hipEvent_t>> w_readers;
     u32 n_labels_decl = 0;
     u32* d_ob_list = nullptr; u32* d_ob_n = nullptr;
 
@@ -520,6 +522,21 @@ int do_features(sg_engine* e, hipStream_t s) {
     return SG_OK;
 }
 
+// K4 and K5 read d_W on whatever stream the close runs on (the engine's, a window slot's, a caller's): record an event behind them
+// there, one per stream.  Entries whose work has finished are dropped before a new stream is added, so the list stays short.
+int note_w_read(sg_engine* e, hipStream_t s) {
+    for (auto& r : e->w_readers) if (r.first == s) { HIP_TRY(e, hipEventRecord(r.second, s)); return SG_OK; }
+    for (size_t i = 0; i < e->w_readers.size();) {
+        if (hipEventQuery(e->w_readers[i].second) == hipSuccess) { hipEventDestroy(e->w_readers[i].second); e->w_readers[i] = e->w_readers.back(); e->w_readers.pop_back(); }
+        else i++;
+    }
+    hipEvent_t v = nullptr;
+    HIP_TRY(e, hipEventCreateWithFlags(&v, hipEventDisableTiming));
+    e->w_readers.emplace_back(s, v);
+    HIP_TRY(e, hipEventRecord(v, s));
+    return SG_OK;
+}
+
 // fuse_proj: the last layer also writes the score head's P and Q (unsharded pipelines only)
 int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
     const Dev& d = e->d;
@@ -543,7 +560,7 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
     }
 #undef K4_LAUNCH
     HIP_TRY(e, hipGetLastError());
-    return SG_OK;
+    return fuse_proj ? SG_OK : note_w_read(e, s);           // (the one-call pipelines score on the same stream next: K5's event covers K4)
 }
 
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
@@ -650,6 +667,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     }
     if (did_reset) *did_reset = fr;
     HIP_TRY(e, hipGetLastError());
+    if (const int rc = note_w_read(e, s)) return rc;
     // K8 right behind K5: every pipeline scores here.  The rows, the counters and the outbound-IP list survive K5's fused reset and
     // the separate one (sg_k5.h, sg_k3.h k_reset_window), and the next window's K1 queues behind K8 on this stream.
     if (e->trend.on) { const int rc = launch_trend(e, s); if (rc) return rc; }
@@ -1036,6 +1054,7 @@ int sg_destroy(sg_handle e) {
     if (e->copy_stream2) hipStreamDestroy(e->copy_stream2);
     if (e->rd_stream) hipStreamDestroy(e->rd_stream);
     if (e->score_ev) hipEventDestroy(e->score_ev);
+    for (auto& r : e->w_readers) hipEventDestroy(r.second);
     if (e->h_ctr_pin) hipHostFree(e->h_ctr_pin);
     if (e->h_rows) hipHostFree(e->h_rows);
     if (e->h_rows_old) hipHostFree(e->h_rows_old);
@@ -1107,6 +1126,11 @@ int sg_load_weights(sg_handle e, const float* w, size_t n) {
     if (!e || !w) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (n != weights_count(e->cfg.layers)) { e->err = "weight count mismatch"; return SG_EINVAL; }
+    // every close already enqueued finishes with the blob it began with: wait for the K4 / K5 launches that read d_W (the copy below
+    // runs on the null stream, which does not order itself behind the engine's non-blocking streams), then overwrite it
+    for (auto& r : e->w_readers) HIP_TRY(e, hipEventSynchronize(r.second));
+    for (auto& r : e->w_readers) hipEventDestroy(r.second);
+    e->w_readers.clear();
     HIP_TRY(e, hipMemcpy(e->d_W, w, n * sizeof(float), hipMemcpyHostToDevice));
     e->have_w = true;
     return SG_OK;

@@ -255,7 +255,11 @@ int sg_set_clock(sg_handle h, uint64_t first_kernel_ns, uint64_t first_user_ns);
  * LABEL id range of the next closed window.                                                    */
 int sg_set_label_count(sg_handle h, uint32_t n_labels);
 
-/* fp32 weight blob, layout documented in DESIGN.md §"weights"; copied.                         */
+/* fp32 weight blob, layout documented in DESIGN.md §"weights"; copied.  A close is scored with
+ * the blob that was loaded when the close began: a call made while closes are still queued on
+ * the device (sg_flush_begin before sg_flush_end, sg_window_run with windows in flight, the
+ * staged sg_window_* calls) first waits for their layer and score kernels, then replaces the
+ * blob.  Closes begun after it returns use the new blob.                                      */
 int sg_load_weights(sg_handle h, const float* w, size_t n);
 
 /* ---- ingest: replaces processL7 .. setFromToV2 .. PersistRequest for the edge fields ------ *
