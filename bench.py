@@ -13,7 +13,9 @@ the window reset.  Workloads (BASELINE.json configs, alaz_amd/replay.py):
                       (the same 10M-event replay routed over the N GPUs), the weak figure (10M events per GPU and window) in `weak`.
 
 Steps cycle through a ring of distinct batches larger than the 256 MiB Infinity Cache, so every step streams its events
-from HBM.  One JSON line on stdout (rank 0):
+from HBM.  One JSON line on stdout (rank 0).  A plain one-GPU run sets up, settles, warms up, times the steps, writes
+--dump-outputs if asked and prints the headline fields (metric, value, unit, higher_is_better, dtype, ms_per_step, the
+workload); everything below beside `value` is measured only with --full, which runs every leg the line has:
 
   value        events/s of the timed device-resident steps (never includes PCIe; `end_to_end` does)
   roofline     the dominant kernel K1 (pass A k1a_team_partition + pass B k1b_stream_merge): algorithmic bytes 32*Ev + 32*E per window
@@ -48,23 +50,27 @@ DUMP_MAX_ROWS = 1 << 19      # --dump-outputs: 10 float64 + 3 float32 fields = 9
 DUMP_SEED = 0xA1A2D0           # --dump-outputs: the hash that picks the sample
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="timed windows (0 = per config: C2 200, C3/C4 30, C5 10)")
     ap.add_argument("--warmup", type=int, default=-1, help="untimed windows (-1 = per config: C2 20, C3/C4 5, C5 2)")
     ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 4, 5], help="0 = 3 for one GPU, 4 (C3's graph sharded) for several")
     ap.add_argument("--batches", type=int, default=0, help="distinct event batches in the HBM ring (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
-    ap.add_argument("--no-churn", action="store_true", help="skip the churn leg (windows that bring 0.1 % / 1 % / 4 % new edges)")
-    ap.add_argument("--stream", action="store_true", help="config 5 only: add the streaming run (tools/c5_stream.py: raw 1096-byte records at the "
+    ap.add_argument("--full", action="store_true", help="one GPU: also measure everything beside the headline figure — "
+                                                       "CPU baseline, per-step distribution, K1 roofline, per-kernel groups, cold path, churn, "
+                                                       "several windows in flight, end-to-end from host memory, box probes (the --no-* options "
+                                                       "below leave single legs out).  Without it a run does only what `value` needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the end-to-end pass")
+    ap.add_argument("--no-churn", action="store_true", help="--full: skip the churn leg (windows that bring 0.1 %% / 1 %% / 4 %% new edges)")
+    ap.add_argument("--stream", action="store_true", help="--full, config 5 only: add the streaming run (tools/c5_stream.py: raw 1096-byte records at the "
                                                          "nominal 5 M events/s through the C++ host side, a window per second, ten windows)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="seconds per CPU-baseline variant")
-    ap.add_argument("--feeders", type=int, default=8, help="host threads calling sg_ingest in the end-to-end pass")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="--full: seconds per CPU-baseline variant")
+    ap.add_argument("--feeders", type=int, default=8, help="--full: host threads calling sg_ingest in the end-to-end pass")
     ap.add_argument("--windows", type=int, default=1, help="window slots in flight for the timed region (sg_config.windows_in_flight); "
                                                             "1 keeps the per-kernel timings uncontended")
-    ap.add_argument("--overlap-windows", type=int, default=4, help="extra diagnostic pass with this many windows in flight (0 = skip)")
+    ap.add_argument("--overlap-windows", type=int, default=4, help="--full: extra diagnostic pass with this many windows in flight (0 = skip)")
     ap.add_argument("--graph", choices=["fixed", "scaled"], default="fixed",
                     help="N > 1: 'fixed' shards the configuration's own graph over the N GPUs (what BASELINE's multi-GPU configurations "
                          "do with theirs); 'scaled' also grows the graph N-fold")
@@ -86,9 +92,11 @@ def parse():
                     help="after the timed steps, write the edge rows the last timed window produced (what sg_window_read hands a caller) as "
                          "DIR/<field>.npy, one file per sg_edge_out field, ordered by (from_ref, to_ref); float64, the fp32 fields float32; "
                          f"above {DUMP_MAX_ROWS} rows a fixed seeded sample of that many edges.  One GPU, one window in flight")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.dump_outputs and (a.gpus > 1 or a.windows > 1):
         ap.error("--dump-outputs reads the last timed window back with sg_window_read: --gpus 1 and --windows 1 only")
+    if a.stream and not a.full:
+        ap.error("--stream is one of the --full legs: add --full")
     if a.config == 0:
         a.config = 3 if a.gpus == 1 else 4
     dflt = {2: (200, 20), 3: (30, 5), 4: (30, 5), 5: (10, 2)}[a.config]
@@ -362,6 +370,24 @@ def main():
         dist.destroy_process_group()
 
 
+def headline(a, cfgno, c, topo, Ev, L, nb, geo, dt):
+    """The fields every one-GPU line has (all that a plain run prints): the figure of the timed steps and the workload it was taken on."""
+    variant = ("global-table K1 (variant 1)" if geo["k1_variant"] == 1 else
+               f"partitioned K1 (variant 0, {'8' if geo['k1_narrow'] else '16'}-byte records, {geo['partitions']} partitions)")
+    return {
+        "metric": "L7 edge-events/s ingested->scored service-map", "value": Ev * a.steps / dt, "unit": "events/s",
+        "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+        # (one GPU: the job of the N > 1 default — BASELINE config 4 = this replay routed over N ranks, total work fixed — at N = 1)
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": {"workload": (f"ONE SHARD OF {a.shard_of} of " if a.shard_of > 1 else "") + f"C{cfgno} device-resident replay: {c['pods']} pods / {topo.n_svcs} services / {len(topo.edge_src)} edges, "
+                               f"{Ev} {'mixed HTTP/Kafka/Postgres' if cfgno == 5 else 'HTTP'} l7 events per window already in HBM, {L}-layer SAGE + MLP score, "
+                               f"{variant}; {nb}-batch HBM ring (value excludes PCIe: see end_to_end with --full)",
+                   "events_per_window": Ev, "layers": L, "windows_in_flight": a.windows, "shard_of": a.shard_of,
+                   "parallelism": "1 GPU" if a.shard_of == 1 else f"1 GPU standing in for one rank of {a.shard_of} (no exchanges: K1 and the local window close of the shard's shape)"},
+        "value_basis": "mean over the timed steps (wall clock around K back-to-back windows, one window in flight)",
+    }
+
+
 def geo_warm(g) -> bool:
     """does this engine carry the edge set from window to window (sg_geometry.warm_windows)"""
     try:
@@ -507,7 +533,7 @@ def bench_single(a, device):
         if cpath:
             np.save(cpath, ev_all)
     cpu = None
-    if not a.no_cpu_baseline and not a.profile_mode:                 # before the GPU runtime exists in this process (fork)
+    if a.full and not a.no_cpu_baseline and not a.profile_mode:      # before the GPU runtime exists in this process (fork)
         cpu = cpu_baseline(topo, ev_all[:Ev], labels, L, a.cpu_seconds)
 
     import torch
@@ -522,8 +548,9 @@ def bench_single(a, device):
         g.ingest_device(dev[i % nb].data_ptr(), Ev, s)
         g.window_run(s)
 
-    # Settle: the CPU-baseline leg leaves the GPU idle for tens of seconds and the timed region is only a few milliseconds long —
-    # whatever DPM state the chip is in would be what gets timed.  Untimed real windows until the clock is up.
+    # Settle: the setup (and with --full the CPU-baseline leg) leaves the GPU idle for seconds and the timed region is only a few
+    # milliseconds long — whatever DPM state the chip is in would be what gets timed.  Untimed real windows until
+    # the clock is up.
     settle_windows = 0
     if a.settle_ms > 0 and not a.profile_mode:
         ts = time.perf_counter()
@@ -537,7 +564,7 @@ def bench_single(a, device):
     clk_before = g.clock_probe(200)                          # (all-CU spin now, pass A of the settle + warm-up windows)
     # dispatch stamps of the K1 launches (pass A + pass B) on their stream, on every third window of the timed steps: the stamps cost a few
     # microseconds per launch (three stamped launches a window moved the timed mean 17 us above the unstamped median), the averages below
-    # are still over launches of the timed region
+    # are still over launches of the timed region.  A plain run takes them too and reads none: the timed steps are the same either way
     stride = 3 if a.steps >= 9 else 1
     g.timing_reset(); g.timing_stride(stride); g.timing_enable((1 << 1) | (1 << 7))
     torch.cuda.synchronize()
@@ -547,6 +574,15 @@ def bench_single(a, device):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     g.timing_enable(0); g.timing_stride(1)
+    if not a.full and not a.profile_mode:
+        # a plain run: the headline line, the last timed window's rows if asked, nothing else
+        dumped = dump_outputs(a.dump_outputs, g.window_read(), g.outbound_ips()) if a.dump_outputs else None
+        geo = g.geometry()
+        g.close()
+        res = headline(a, cfgno, c, topo, Ev, L, nb, geo, dt)
+        if dumped:
+            res["dump_outputs"] = dumped
+        return res
     clk_after = g.clock_probe(200)                           # (spin right after the timed steps, pass A of exactly the timed steps)
     k1a, k1b = g.timing(1), g.timing(7)
     k1a_s, k1b_s = g.timing_samples(1), g.timing_samples(7)  # every launch of the timed steps, by the dispatch's own stamps
@@ -654,19 +690,9 @@ def bench_single(a, device):
                for k in ("K1a", "K1b", "K2", "K3-in", "K3-feat", "K4", "K5") if k in kern_us]
     b_total = sum(alg.values())
     ms_step = dt / a.steps * 1e3
-    variant = ("global-table K1 (variant 1)" if geo["k1_variant"] == 1 else
-               f"partitioned K1 (variant 0, {'8' if geo['k1_narrow'] else '16'}-byte records, {geo['partitions']} partitions)")
-    res = {
-        "metric": "L7 edge-events/s ingested->scored service-map", "value": Ev * a.steps / dt, "unit": "events/s",
-        "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_step,
-        # (one GPU: the job of the N > 1 default — BASELINE config 4 = this replay routed over N ranks, total work fixed — at N = 1)
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-        "config": {"workload": (f"ONE SHARD OF {a.shard_of} of " if a.shard_of > 1 else "") + f"C{cfgno} device-resident replay: {c['pods']} pods / {topo.n_svcs} services / {len(topo.edge_src)} edges, "
-                               f"{Ev} {'mixed HTTP/Kafka/Postgres' if cfgno == 5 else 'HTTP'} l7 events per window already in HBM, {L}-layer SAGE + MLP score, "
-                               f"{variant}; {nb}-batch HBM ring (value excludes PCIe: see end_to_end)",
-                   "events_per_window": Ev, "edges_per_window": E, "nodes": N, "layers": L,
-                   "events_dropped_cap": int(st.events_dropped_cap), "windows_in_flight": a.windows, "shard_of": a.shard_of,
-                   "parallelism": "1 GPU" if a.shard_of == 1 else f"1 GPU standing in for one rank of {a.shard_of} (no exchanges: K1 and the local window close of the shard's shape)"},
+    res = headline(a, cfgno, c, topo, Ev, L, nb, geo, dt)
+    res["config"].update({"edges_per_window": E, "nodes": N, "events_dropped_cap": int(st.events_dropped_cap)})
+    res.update({
         "roofline": {"bound": "hbm", "kernel": "K1 resolve_aggregate = " + " + ".join(kn), "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "traffic_calibrated": traffic_cal,   # the same counters divided by their reading for known byte counts in K1's access patterns (profiles/*_pmc_calibration.json)
@@ -694,8 +720,8 @@ def bench_single(a, device):
                          # windows that meet NEW edges (0.1 % / 1 % / 4 % of the graph per window, spread over all rows): merged in, not rebuilt
                          "churn": churn,
                          "windows_read": {"warm": int(st.windows_warm), "cold": int(st.windows_cold)}},
-        "value_basis": "mean over the timed steps (wall clock around K back-to-back windows, one window in flight); per_step holds median / min of single windows",
-    }
+    })
+    res["value_basis"] = res.pop("value_basis") + "; per_step holds median / min of single windows"
     if dumped:
         res["dump_outputs"] = dumped
     # diagnostic (never `value`): the same steps with several windows in flight inside one engine — the

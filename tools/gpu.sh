@@ -5,7 +5,7 @@
 #   smoke                    __graft_entry__.smoke()
 #   sweep:CONFIG:VAR;VAR     tools/k1_sweep.py CONFIG with the ';'-separated environment variants (e.g. sweep:3:SG_NP=1024,SG_HT=2048;SG_K1_LEGACY=1)
 #   stamps:CONFIG[:ENV]      phase stamps of the K1 kernels (tools/stamps.py)
-#   bench:TAG[:ARGS]         bench.py ARGS -> gpurun_out/TAG_bench.json
+#   bench:TAG[:ARGS]         bench.py --full ARGS (the line with every leg) -> TAG_bench.json in the output folder
 #   prof:TAG:CONFIG          rocprofv3 --kernel-trace --stats of bench.py --profile-mode -> TAG_kernel_stats_cCONFIG.txt
 #   pmc:TAG:CONFIG           FETCH_SIZE / WRITE_SIZE (separate passes) of the K1 kernels -> TAG_pmc_k1_cCONFIG.json, TAG_pmc_summary_cCONFIG.txt
 #   mfma:TAG:CONFIG          SQ_VALU_MFMA_BUSY_CYCLES / SQ_BUSY_CYCLES pass -> TAG_mfma_cCONFIG.txt
@@ -32,7 +32,7 @@ for step in "$@"; do
     smoke) timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 3 ;;
     sweep) IFS=';' read -ra V <<< "$a2"; timeout 900 python tools/k1_sweep.py "$a1" "${V[@]}" 2>&1 | grep -v amdgpu.ids | tee -a "$O/sweep_c$a1.log" ;;
     stamps) env $a2 timeout 300 python tools/stamps.py "$a1" 2>&1 | grep -v amdgpu.ids | tee "$O/stamps_c$a1.log" ;;
-    bench) timeout 900 python bench.py $a2 > "$O/${a1}_bench.json" 2> "$O/${a1}_bench.err"; echo "bench rc=$?"; tail -n 1 "$O/${a1}_bench.json" | cut -c1-1500 ;;
+    bench) timeout 900 python bench.py --full $a2 > "$O/${a1}_bench.json" 2> "$O/${a1}_bench.err"; echo "bench rc=$?"; tail -n 1 "$O/${a1}_bench.json" | cut -c1-1500 ;;
     prof)
       ( cd /tmp && rm -rf "$O/prof_$a1" && timeout 600 rocprofv3 --kernel-trace --stats -d "$O/prof_$a1" -o kt -- python "$R/bench.py" --config "$a2" --profile-mode > "$O/rocprof_${a1}_c$a2.log" 2>&1
         python "$R/tools/rocpd_stats.py" "$O/prof_$a1/kt_results.db" "$O/${a1}_kernel_stats_c$a2.txt" | head -n 24; rm -rf "$O/prof_$a1" ) ;;
