@@ -26,6 +26,7 @@
 #include "sg_kernels.h"
 #include "sg_sel.h"
 #include "sg_trend.h"
+#include "sg_node_trend.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -144,6 +145,16 @@ struct sg_engine {
     struct Nodes { bool on = false; sgplan::NodesPlan plan; char* mem = nullptr; u32* dst = nullptr; K9Side* tout = nullptr; K9Side* tin = nullptr;
                    K9Side* part = nullptr; u32* blk = nullptr; std::vector<sg_node_out*> rows; std::vector<u64*> count; std::vector<char> valid;
                    hipEvent_t ev = nullptr; bool pending = false; int run_slot = -1; } nodes;
+    // K10, the per-node baselines (sg_node_trend.h): allocated at sg_set_node_trend (sg_plan.hpp plan_node_trend), one allocation,
+    // freed with the rollup.  Chained like K8 (ev); per slot: the node trend rows and whether the window in the slot made them.
+    struct NodeTrend { bool on = false; sg_trend_params p{}; sgplan::NodeTrendPlan plan; char* mem = nullptr; TrendSoA buf[2] = {}; u64* ctl = nullptr;
+                       u32* blk = nullptr; K8Thread* th = nullptr; std::vector<sg_node_trend*> rows; std::vector<char> valid; u32 w = 0;
+                       hipEvent_t ev = nullptr; bool pending = false; sg_node_trend* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; } ntrend;
+    // node selection (K7 over node rows): scratch of plan_select(ncap) allocated at the first one, with the counter block k10_keys
+    // fills, an index array and the host form's row staging (ncap each).  Node selections wait for each other (ev).
+    struct NSel { sgplan::SelPlan plan; u32* keys = nullptr; u32* hist = nullptr; u32* blk = nullptr; u32* state = nullptr; u64* pairs = nullptr;
+                  u64* n = nullptr; u64* ctr = nullptr; u32* idx = nullptr; sg_node_out* stage = nullptr; u64* h_n = nullptr; char* mem = nullptr;
+                  hipEvent_t ev = nullptr; bool pending = false; } nsel;
 };
 
 namespace {
@@ -624,7 +635,44 @@ int launch_nodes(sg_engine* e, hipStream_t s) {
     n.valid[e->cur] = 1;
     return SG_OK;
 }
+// ---- K10, the per-node baselines (engine lock held) ------------------------------------------------------------------------------
+static_assert(sizeof(sg_node_trend) == 32 && sizeof(K10Sample) == 40, "sg_node_trend layout");
+// enqueue the node baseline's update by the window in slot cur on stream s (behind its rollup, on the same stream), behind the
+// previous update (any stream); the window's node trend rows go to the slot's buffer
+int launch_node_trend(sg_engine* e, hipStream_t s) {
+    sg_engine::NodeTrend& t = e->ntrend;
+    const sg_trend_params& p = t.p;
+    NodeTrendArgs a{};
+    a.t.ctr = e->d.ctr; a.t.ob_sorted = e->d.ob_sorted; a.t.max_obip = e->d.max_obip;
+    a.t.cap = t.plan.entries;
+    a.t.buf[0] = t.buf[0]; a.t.buf[1] = t.buf[1];
+    a.t.th = t.th; a.t.blk = t.blk; a.t.ctl = t.ctl;
+    a.t.w = t.w + 1; a.t.warmup = p.warmup; a.t.ttl = p.ttl;
+    a.t.alpha = std::ldexp(1.0, -(int)p.shift); a.t.lat_floor = (double)p.lat_floor_ns; a.t.err_floor = (double)p.err_floor;
+    a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur]; a.ncap = e->nodes.plan.ncap; a.out = t.rows[e->cur];
+    if (t.pending) HIP_TRY(e, hipStreamWaitEvent(s, t.ev, 0));
+    hipLaunchKernelGGL(k10_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs);
+    hipLaunchKernelGGL(k10_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(t.ev, s));
+    t.pending = true;
+    t.valid[e->cur] = 1;
+    t.w++;
+    return SG_OK;
+}
+void free_node_trend(sg_engine* e) {
+    sg_engine::NodeTrend& t = e->ntrend;
+    if (t.mem || t.stage) hipDeviceSynchronize();
+    if (t.mem) hipFree(t.mem);
+    if (t.stage) hipFree(t.stage);
+    if (t.stage_idx) hipFree(t.stage_idx);
+    if (t.ev) hipEventDestroy(t.ev);
+    t = sg_engine::NodeTrend{};
+}
+
 void free_nodes(sg_engine* e) {
+    free_node_trend(e);
     sg_engine::Nodes& n = e->nodes;
     if (n.mem) { hipDeviceSynchronize(); hipFree(n.mem); }
     if (n.ev) hipEventDestroy(n.ev);
@@ -671,8 +719,11 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     // K8 right behind K5: every pipeline scores here.  The rows, the counters and the outbound-IP list survive K5's fused reset and
     // the separate one (sg_k5.h, sg_k3.h k_reset_window), and the next window's K1 queues behind K8 on this stream.
     if (e->trend.on) { const int rc = launch_trend(e, s); if (rc) return rc; }
-    // K9 behind them: it reads the rows and the window counters only
-    if (e->nodes.on) return launch_nodes(e, s);
+    // K9 behind them: it reads the rows and the window counters only; K10 behind K9: the node rows, their count, the outbound IPs
+    if (e->nodes.on) {
+        if (const int rc = launch_nodes(e, s)) return rc;
+        if (e->ntrend.on) return launch_node_trend(e, s);
+    }
     return SG_OK;
 }
 
@@ -792,16 +843,8 @@ int sel_reserve(sg_engine* e, u64 stage_rows) {
     return SG_OK;
 }
 
-// enqueue the selection on stream st: a.rows / a.ctr / a.n_host / a.out / a.out_idx / a.cap / a.n_out set by the caller; by != SG_SEL_SCORE
-// keys the window's trend rows tr
-int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_score, u32 by = SG_SEL_SCORE, const sg_edge_trend* tr = nullptr) {
-    sg_engine::Sel& s = e->sel;
-    const u32 wgs = s.plan.wgs;
-    a.max_edges = e->cfg.max_edges; a.k = k; a.min_score = min_score;
-    a.keys = s.keys; a.hist = s.hist; a.blk = s.blk; a.state = s.state; a.pairs = s.pairs;
-    if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
-    if (by == SG_SEL_SCORE) hipLaunchKernelGGL(k7_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(k7_keys_by, dim3(wgs), dim3(K7_THREADS), 0, st, a, tr, by);
+// K7's passes after the key pass (row-agnostic): the radix pick, the counts, the scans, the compaction, the top-k sort
+void enqueue_k7_select(hipStream_t st, const SelArgs& a, u32 k, u32 wgs, u64 max_rows) {
     if (k) {
         for (u32 r = 0; r < 4; r++) {
             if (r) hipLaunchKernelGGL(k7_hist, dim3(wgs), dim3(K7_THREADS), 0, st, a, r);
@@ -812,15 +855,83 @@ int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_scor
     hipLaunchKernelGGL(k7_scan, dim3(1), dim3(K7_PICK_THREADS), 0, st, a, wgs);
     hipLaunchKernelGGL(k7_scatter, dim3(wgs), dim3(K7_THREADS), 0, st, a);
     if (k) {
-        const u32 n = sgplan::next_pow2(std::max<u64>(1, std::min<u64>(k, e->cfg.max_edges)));
+        const u32 n = sgplan::next_pow2(std::max<u64>(1, std::min<u64>(k, max_rows)));
         hipLaunchKernelGGL(k7_sort, dim3(1), dim3(K7_PICK_THREADS), (size_t)n * 8, st, a, n);
     }
+}
+
+// enqueue the selection on stream st: a.rows / a.ctr / a.n_host / a.out / a.out_idx / a.cap / a.n_out set by the caller; by != SG_SEL_SCORE
+// keys the window's trend rows tr
+int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_score, u32 by = SG_SEL_SCORE, const sg_edge_trend* tr = nullptr) {
+    sg_engine::Sel& s = e->sel;
+    const u32 wgs = s.plan.wgs;
+    a.max_edges = e->cfg.max_edges; a.k = k; a.min_score = min_score;
+    a.keys = s.keys; a.hist = s.hist; a.blk = s.blk; a.state = s.state; a.pairs = s.pairs;
+    if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
+    if (by == SG_SEL_SCORE) hipLaunchKernelGGL(k7_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(k7_keys_by, dim3(wgs), dim3(K7_THREADS), 0, st, a, tr, by);
+    enqueue_k7_select(st, a, k, wgs, e->cfg.max_edges);
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipEventRecord(s.ev, st));
     s.pending = true;
     return SG_OK;
 }
 
+// ---- node selection (engine lock held) ------------------------------------------------------------------------------------------
+// the scratch at the first node selection (plan_select over the node capacity, the counter block, indices and staging)
+int nsel_reserve(sg_engine* e) {
+    sg_engine::NSel& s = e->nsel;
+    if (s.keys) return SG_OK;
+    const u64 NC = std::max<u32>(e->d.ncap, 1);
+    s.plan = sgplan::plan_select(NC, true);
+    const sgplan::SelPlan& p = s.plan;
+    const u64 ctr_bytes = sgplan::trend_align(sizeof(e->h_ctr)), idx_bytes = sgplan::trend_align(NC * 4);
+    const u64 stage_bytes = sgplan::trend_align(NC * sizeof(sg_node_out));
+    const u64 total = sgplan::trend_align(p.scratch_bytes) + ctr_bytes + idx_bytes + stage_bytes;
+    HIP_TRY(e, hipMalloc((void**)&s.mem, total));
+    HIP_TRY(e, hipMemset(s.mem, 0, total));
+    char* b = s.mem;
+    s.stage = (sg_node_out*)b; b += stage_bytes;                              // (256-aligned pieces first, then plan_select's layout)
+    s.ctr = (u64*)b; b += ctr_bytes;
+    s.idx = (u32*)b; b += idx_bytes;
+    s.pairs = (u64*)b; b += p.pair_bytes;
+    s.n = (u64*)b; s.state = (u32*)(b + 8); b += p.state_bytes;
+    s.blk = (u32*)b; b += p.blk_bytes;
+    s.hist = (u32*)b; b += p.hist_bytes;
+    s.keys = (u32*)b;
+    HIP_TRY(e, hipHostMalloc((void**)&s.h_n, sizeof(u64)));
+    HIP_TRY(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    HIP_TRY(e, lds_limit(sgplan::select_sort_lds(SG_SELECT_MAX_K), k7_sort));
+    return SG_OK;
+}
+// enqueue a selection over the node rows of slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
+// be NULL), the count to d_n; behind that window's rollup and node trend (events) and the previous node selection
+int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
+                       u64 cap, u64* d_n) {
+    sg_engine::NSel& s = e->nsel;
+    const u32 wgs = s.plan.wgs;
+    const u64 NC = std::max<u32>(e->d.ncap, 1);
+    SelArgs a{};
+    a.rows = nullptr; a.ctr = s.ctr; a.max_edges = NC; a.k = k; a.min_score = min_value;
+    a.keys = s.keys; a.hist = s.hist; a.blk = s.blk; a.state = s.state; a.pairs = s.pairs;
+    a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, NC); a.n_out = d_n;
+    if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
+    if (e->nodes.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->nodes.ev, 0));
+    if (by != SG_NSEL_SCORE && e->ntrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->ntrend.ev, 0));
+    const sg_node_out* nodes = e->nodes.rows[slot];
+    const sg_node_trend* tr = by != SG_NSEL_SCORE ? e->ntrend.rows[slot] : nullptr;
+    hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, nodes, (const u64*)e->nodes.count[slot], tr, by, s.ctr);
+    enqueue_k7_select(st, a, k, wgs, NC);
+    if (d_out) {
+        const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, NC) : NC);
+        hipLaunchKernelGGL(k10_gather_rows, dim3((unsigned)std::max<u64>(1, std::min<u64>((m + 255) / 256, 1024))), dim3(256), 0, st,
+                           nodes, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
+    }
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(s.ev, st));
+    s.pending = true;
+    return SG_OK;
+}
 }  // namespace
 
 // ================================================================================================
@@ -1064,6 +1175,9 @@ int sg_destroy(sg_handle e) {
     if (e->sel.ev) hipEventDestroy(e->sel.ev);
     free_trend(e);
     free_nodes(e);
+    if (e->nsel.mem) hipFree(e->nsel.mem);
+    if (e->nsel.h_n) hipHostFree(e->nsel.h_n);
+    if (e->nsel.ev) hipEventDestroy(e->nsel.ev);
     for (auto& r : e->trecs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto v : e->ev_pool) hipEventDestroy(v);
     if (e->tab_ev) hipEventDestroy(e->tab_ev);
@@ -1843,6 +1957,174 @@ int sg_window_nodes_buffer(sg_handle e, void** d_nodes, void** d_count) {
     if (!x.valid[slot]) { e->err = "sg_window_nodes_buffer: the window was closed while the node rollup was off"; return SG_ESTATE; }
     *d_nodes = x.rows[slot]; *d_count = x.count[slot];
     return SG_OK;
+}
+
+// ---- K10, the per-node baselines ---------------------------------------------------------------------------------------------
+int sg_set_node_trend(sg_handle e, const sg_trend_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->nodes.on) { e->err = "sg_set_node_trend: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_node_trend while a flush is open"; return SG_ESTATE; }
+    sg_trend_params r{};
+    if (p && sgplan::check_node_trend(*p, e->nodes.plan.ncap, &r)) { e->err = "sg_set_node_trend: bad parameters"; return SG_EINVAL; }
+    free_node_trend(e);
+    if (!p) return SG_OK;
+    sg_engine::NodeTrend& t = e->ntrend;
+    const u32 slots = (u32)std::max<size_t>(e->slots.size(), 1);
+    t.p = r;
+    t.plan = sgplan::plan_node_trend(e->nodes.plan.ncap, slots, r);
+    const sgplan::NodeTrendPlan& P = t.plan;
+    HIP_TRY(e, hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+    {
+        const hipError_t rc = hipMalloc((void**)&t.mem, P.total_bytes);
+        if (rc != hipSuccess) { free_node_trend(e); e->err = std::string("sg_set_node_trend: hipMalloc: ") + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
+    }
+    HIP_TRY(e, hipMemset(t.mem, 0, P.total_bytes));                  // an empty baseline (B = 0 for both parities), zero statistics and rows
+    const u64 C = P.entries;
+    char* b = t.mem;
+    for (int k = 0; k < 2; k++) {                                     // (K8's SoA layout)
+        TrendSoA& x = t.buf[k];
+        char* q = b;
+        x.from_key = (u64*)q; q += C * 8; x.to_key = (u64*)q; q += C * 8;
+        x.lat_mean = (double*)q; q += C * 8; x.lat_dev = (double*)q; q += C * 8; x.err_mean = (double*)q; q += C * 8; x.err_dev = (double*)q; q += C * 8;
+        x.n = (u32*)q; q += C * 4; x.last = (u32*)q;
+        b += P.soa_bytes;
+    }
+    t.ctl = (u64*)b; b += P.ctl_bytes;
+    t.blk = (u32*)b; b += P.blk_bytes;
+    t.th = (K8Thread*)b; b += P.thread_bytes;
+    for (u32 k = 0; k < slots; k++) { t.rows.push_back((sg_node_trend*)b); b += P.rows_bytes; }
+    t.valid.assign(slots, 0);
+    t.on = true;
+    return SG_OK;
+}
+int sg_window_node_trend(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::NodeTrend& t = e->ntrend;
+    if (!t.on) { e->err = "sg_window_node_trend: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_window_node_trend while a flush is open"; return SG_ESTATE; }
+    if (!t.valid[e->cur]) { e->err = "sg_window_node_trend: the last read window was closed while the node trend was off"; return SG_ESTATE; }
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const size_t N = (size_t)cnt;
+    const sg_node_trend* src = t.rows[e->cur];
+    if (!node_index) {
+        if (n) *n = N;
+        const size_t take = std::min(N, cap);
+        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(sg_node_trend), hipMemcpyDeviceToHost));
+        return SG_OK;
+    }
+    for (size_t k = 0; k < n_index; k++) if (node_index[k] >= N) { e->err = "sg_window_node_trend: a node index beyond the window's nodes"; return SG_EINVAL; }
+    if (n) *n = n_index;
+    const size_t take = std::min(n_index, cap);
+    if (!out || !take) return SG_OK;
+    if (take > t.stage_cap) {
+        if (t.stage) { hipFree(t.stage); hipFree(t.stage_idx); t.stage = nullptr; t.stage_idx = nullptr; t.stage_cap = 0; }
+        const size_t want = std::max<size_t>(take, 1024);
+        HIP_TRY(e, hipMalloc((void**)&t.stage, want * sizeof(sg_node_trend)));
+        HIP_TRY(e, hipMalloc((void**)&t.stage_idx, want * sizeof(u32)));
+        t.stage_cap = want;
+    }
+    HIP_TRY(e, hipMemcpyAsync(t.stage_idx, node_index, take * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
+    hipLaunchKernelGGL(k10_gather, dim3((unsigned)((take + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)t.stage_idx, (u64)take, t.stage);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(out, t.stage, take * sizeof(sg_node_trend), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    return SG_OK;
+}
+int sg_window_node_trend_buffer(sg_handle e, void** d_trend) {
+    if (!e || !d_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::NodeTrend& t = e->ntrend;
+    if (!t.on) { e->err = "sg_window_node_trend_buffer: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
+    const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
+    if (!t.valid[slot]) { e->err = "sg_window_node_trend_buffer: the window was closed while the node trend was off"; return SG_ESTATE; }
+    *d_trend = t.rows[slot];
+    return SG_OK;
+}
+int sg_node_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::NodeTrend& t = e->ntrend;
+    if (!t.on) { e->err = "sg_node_trend_entries: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    u64 ctl[K8C_WORDS];
+    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+    const u32 par = t.w & 1u;                                          // (w = 0: parity 0, B = 0)
+    const size_t B = (size_t)ctl[K8C_B0 + par];
+    if (n) *n = B;
+    const size_t take = std::min(B, cap);
+    if (!out || !take) return SG_OK;
+    const TrendSoA& x = t.buf[par];
+    std::vector<u64> fk(take), tk(take); std::vector<double> lm(take), ld(take), em(take), ed(take); std::vector<u32> cn(take), ls(take);
+    HIP_TRY(e, hipMemcpy(fk.data(), x.from_key, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(tk.data(), x.to_key, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(lm.data(), x.lat_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ld.data(), x.lat_dev, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(em.data(), x.err_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ed.data(), x.err_dev, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(cn.data(), x.n, take * 4, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ls.data(), x.last, take * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < take; i++) out[i] = sg_trend_entry{fk[i], tk[i], lm[i], ld[i], em[i], ed[i], cn[i], ls[i]};
+    return SG_OK;
+}
+int sg_node_trend_stats_get(sg_handle e, sg_trend_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::NodeTrend& t = e->ntrend;
+    if (!t.on) { e->err = "sg_node_trend_stats_get: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    u64 ctl[K8C_WORDS];
+    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+    out->windows = ctl[K8C_WINDOWS]; out->entries = ctl[K8C_B0 + (t.w & 1u)];
+    out->inserted = ctl[K8C_INSERTED]; out->expired = ctl[K8C_EXPIRED]; out->dropped = ctl[K8C_DROPPED];
+    return SG_OK;
+}
+
+// ---- node selection ---------------------------------------------------------------------------------------------------------
+namespace {
+// by > 5: SG_EINVAL; the rollup off, or a trend key with the node trend off: SG_ESTATE; then the window in `slot` must have them
+int check_nsel(sg_engine* e, u32 by, int slot) {
+    if (by > SG_NSEL_NEW) { e->err = "node selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
+    if (!e->nodes.on) { e->err = "node selection: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
+    if (by != SG_NSEL_SCORE && !e->ntrend.on) { e->err = "node selection by a trend key: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
+    if (!e->nodes.valid[slot]) { e->err = "node selection: the window was closed while the node rollup was off"; return SG_ESTATE; }
+    if (by != SG_NSEL_SCORE && !e->ntrend.valid[slot]) { e->err = "node selection: the window was closed while the node trend was off"; return SG_ESTATE; }
+    return SG_OK;
+}
+}  // namespace
+int sg_window_nodes_top(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
+                        size_t* n_selected, size_t* n_nodes) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (by > SG_NSEL_NEW) { e->err = "node selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
+    if (e->closing || e->flush_open) { e->err = "sg_window_nodes_top while a flush is open"; return SG_ESTATE; }
+    if (const int rc = check_nsel(e, by, e->cur)) return rc;
+    if (const int rc = nsel_reserve(e)) return rc;
+    sg_engine::NSel& s = e->nsel;
+    const u64 NC = std::max<u32>(e->d.ncap, 1);
+    const u64 stage = std::min<u64>(cap, NC);
+    if (const int rc = launch_node_select(e, e->rd_stream, e->cur, by, k, min_value, out ? s.stage : nullptr, nullptr, stage, s.n)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipMemcpyAsync(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    const u64 m = *s.h_n;
+    const size_t take = (size_t)std::min<u64>(m, stage);
+    if (out && take) HIP_TRY(e, hipMemcpyAsync(out, s.stage, take * sizeof(sg_node_out), hipMemcpyDeviceToHost, e->rd_stream));
+    if (node_index && take) HIP_TRY(e, hipMemcpyAsync(node_index, s.idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    if (n_selected) *n_selected = (size_t)m;
+    if (n_nodes) *n_nodes = (size_t)cnt;
+    return SG_OK;
+}
+int sg_window_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out, uint32_t* d_index, size_t cap,
+                           uint64_t* d_n, void* stream) {
+    if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
+    if (const int rc = check_nsel(e, by, slot)) return rc;
+    if (const int rc = nsel_reserve(e)) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
+    return launch_node_select(e, s, slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.

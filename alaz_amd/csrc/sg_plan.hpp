@@ -505,6 +505,40 @@ inline NodesPlan plan_nodes(u64 max_edges, u32 ncap, u32 slots) {
     return n;
 }
 
+// K10, the per-node baselines (sg_node_trend.h): K8's parameters and memory over the node rows — sg_set_node_trend allocates it,
+// never sg_create or sg_set_nodes.  A window has at most 2 x ncap samples (two sides per node row); max_entries defaults to
+// 4 x ncap (two sides, and OBIP nodes change from window to window).  The grid is K8's rule over B + 2 x ncap merged elements.
+// Node selection reuses K7's plan over ncap rows (plan_select(ncap)) and its own index / row staging of ncap each.
+inline int check_node_trend(const sg_trend_params& p, u32 ncap, sg_trend_params* out) {
+    if (p.struct_size != sizeof(sg_trend_params)) return SG_EINVAL;
+    sg_trend_params q = p;
+    if (!q.max_entries) q.max_entries = std::min<u64>(kTrendMaxEntries, 4 * std::max<u64>(ncap, 1));
+    return check_trend(q, 0, out);
+}
+struct NodeTrendPlan {
+    u64 entries = 0;              // max_entries
+    u32 wgs = 0;                  // workgroups of k10_count / k10_write (and k8_scan's count of them)
+    u64 soa_bytes = 0;            // one baseline buffer: 56 bytes per entry (K8's SoA)
+    u64 ctl_bytes = 0;            // the control block (K8's words)
+    u64 blk_bytes = 0;            // [wgs][4] u32
+    u64 thread_bytes = 0;         // [wgs * 256] per-thread split + counts (16 bytes)
+    u64 rows_bytes = 0;           // one window slot's node trend rows: [ncap] sg_node_trend
+    u64 total_bytes = 0;          // two baseline buffers, the scratch and every slot's rows, each 256-byte aligned
+};
+inline NodeTrendPlan plan_node_trend(u32 ncap, u32 slots, const sg_trend_params& p) {
+    NodeTrendPlan t;
+    t.entries = p.max_entries;
+    const u64 T = p.max_entries + 2 * (u64)ncap, per_wg = (u64)kTrendThreads * kTrendPerThread;
+    t.wgs = (u32)std::max<u64>(1, std::min<u64>(kTrendMaxWgs, (T + per_wg - 1) / per_wg));
+    t.soa_bytes = trend_align(p.max_entries * (2 * 8 + 4 * 8 + 2 * 4));
+    t.ctl_bytes = trend_align(kTrendCtlWords * 8);
+    t.blk_bytes = trend_align((u64)t.wgs * 4 * 4);
+    t.thread_bytes = trend_align((u64)t.wgs * kTrendThreads * 16);
+    t.rows_bytes = trend_align(std::max<u64>(ncap, 1) * sizeof(sg_node_trend));
+    t.total_bytes = 2 * t.soa_bytes + t.ctl_bytes + t.blk_bytes + t.thread_bytes + (u64)std::max<u32>(slots, 1) * t.rows_bytes;
+    return t;
+}
+
 // the plan's share of the kernels' argument (Dev, sg_device.h; a template so that the CPU test can fill a struct of the same names)
 template <class D>
 void plan_to_dev(const Plan& p, const sg_config& cfg, D& d) {

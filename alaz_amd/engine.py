@@ -47,6 +47,8 @@ EXPORTS = [
     "sg_set_nodes", "sg_window_nodes", "sg_window_nodes_buffer",
     "sg_set_vanished", "sg_window_vanished", "sg_window_vanished_buffer",
     "sg_flush_window_top_by", "sg_flush_end_top_by", "sg_window_select_by",
+    "sg_set_node_trend", "sg_window_node_trend", "sg_window_node_trend_buffer", "sg_node_trend_entries", "sg_node_trend_stats_get",
+    "sg_window_nodes_top", "sg_window_nodes_select",
 ]
 
 #: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
@@ -57,6 +59,9 @@ TREND_ENTRY_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean
 NODE_DTYPE = np.dtype([(f"{side}_{f}", "<u8") for f in ("count", "err", "sum_ns", "sumsq_us", "max_ns", "score_q32") for side in ("out", "in")]
                       + [(f, "<u4") for f in ("ref", "out_edges", "in_edges", "out_alive", "in_alive", "out_worst_row", "in_worst_row")]
                       + [(f, "<f4") for f in ("out_score_max", "in_score_max", "score")])
+#: sg_node_trend (32 bytes) of include/servicegraph.h: one node row's two sides against the node baseline (K10)
+NODE_TREND_DTYPE = np.dtype([(f, "<f4") for f in ("in_lat_dev", "in_err_dev", "out_lat_dev", "out_err_dev", "in_base_mean_us", "out_base_mean_us")]
+                            + [("in_seen", "<u4"), ("out_seen", "<u4")])
 #: sg_edge_vanished (64 bytes) of include/servicegraph.h: one baseline entry that went silent (K8's vanished list)
 VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
                            ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4"), ("row", "<u4"), ("reserved", "<u4")])
@@ -65,6 +70,8 @@ VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", 
 VANISHED_DEFAULTS = dict(silent_windows=0, min_seen=0, max_rows=0)
 #: SG_SEL_*: the key of a selection
 SEL_BY = dict(score=0, lat_dev=1, err_dev=2, new=3)
+#: SG_NSEL_*: the key of a node selection
+NSEL_BY = dict(score=0, in_lat_dev=1, in_err_dev=2, out_lat_dev=3, out_err_dev=4, new=5)
 #: sg_trend_params defaults (a 0 in the struct means the same)
 TREND_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, lat_floor_ns=1000, err_floor=10486)
 
@@ -218,6 +225,11 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_flush_window_top_by": (C.c_int, [H, u64, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
         "sg_flush_end_top_by": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
         "sg_window_select_by": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, P, P]),
+        "sg_set_node_trend": (C.c_int, [H, P]), "sg_window_node_trend": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
+        "sg_window_node_trend_buffer": (C.c_int, [H, C.POINTER(C.c_void_p)]), "sg_node_trend_entries": (C.c_int, [H, P, sz, C.POINTER(sz)]),
+        "sg_node_trend_stats_get": (C.c_int, [H, P]),
+        "sg_window_nodes_top": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "sg_window_nodes_select": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -542,6 +554,92 @@ class ServiceGraph:
         p, c = C.c_void_p(), C.c_void_p()
         self._ck(self._l.sg_window_nodes_buffer(self._h, C.byref(p), C.byref(c)))
         return p.value, c.value
+
+    # ---- node baselines (K10) and node selection: each service against its own past ----
+    def set_node_trend(self, params: Optional[dict] = (), **kw):
+        """Switch the per-node baseline on (sg_set_node_trend; the parameters of set_trend, max_entries 0 = 4 x the node capacity;
+        needs the node rollup on; (re)enabling starts an empty baseline) or off: set_node_trend(None)."""
+        if params is None:
+            if kw:
+                raise TypeError("set_node_trend(None) switches the node trend off and takes no parameters")
+            self._ck(self._l.sg_set_node_trend(self._h, None))
+            return
+        v = dict(TREND_DEFAULTS)
+        v.update(params or {}); v.update(kw)
+        unknown = set(v) - set(TREND_DEFAULTS) - {"struct_size", "reserved"}
+        if unknown:
+            raise TypeError(f"unknown node trend parameters: {sorted(unknown)}")
+        p = SgTrendParams(v.get("struct_size", C.sizeof(SgTrendParams)), v["shift"], v["warmup"], v["ttl"], v["max_entries"],
+                          v["lat_floor_ns"], v["err_floor"], v.get("reserved", 0))
+        self._ck(self._l.sg_set_node_trend(self._h, C.byref(p)))
+
+    def window_node_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """NODE_TREND_DTYPE rows of the last read window (sg_window_node_trend), row k for node row k of window_nodes(); or the rows
+        of the nodes at `index` (window_nodes_top's indices; only those cross PCIe)."""
+        n = C.c_size_t(0)
+        if index is None:
+            self._ck(self._l.sg_window_node_trend(self._h, None, 0, None, 0, C.byref(n)))
+            out = np.zeros(n.value, dtype=NODE_TREND_DTYPE)
+            if n.value:
+                self._ck(self._l.sg_window_node_trend(self._h, None, 0, out.ctypes.data, n.value, C.byref(n)))
+            return out
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        out = np.zeros(len(idx), dtype=NODE_TREND_DTYPE)
+        if len(idx):
+            self._ck(self._l.sg_window_node_trend(self._h, idx.ctypes.data, len(idx), out.ctypes.data, len(idx), C.byref(n)))
+        return out
+
+    def node_trend_buffer(self) -> int:
+        """device pointer of the sg_node_trend rows of the window window_run closed last (sg_window_node_trend_buffer)"""
+        p = C.c_void_p()
+        self._ck(self._l.sg_window_node_trend_buffer(self._h, C.byref(p)))
+        return p.value
+
+    def node_trend_entries(self) -> np.ndarray:
+        """the node baseline in key order, TREND_ENTRY_DTYPE with to_key = side (0 in, 1 out) (sg_node_trend_entries)"""
+        n = C.c_size_t(0)
+        self._ck(self._l.sg_node_trend_entries(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=TREND_ENTRY_DTYPE)
+        if n.value:
+            self._ck(self._l.sg_node_trend_entries(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def node_trend_stats(self) -> SgTrendStats:
+        s = SgTrendStats()
+        self._ck(self._l.sg_node_trend_stats_get(self._h, C.byref(s)))
+        return s
+
+    @staticmethod
+    def _nby(by) -> int:
+        if by not in NSEL_BY:
+            raise ValueError(f"by must be one of {sorted(NSEL_BY)}, not {by!r}")
+        return NSEL_BY[by]
+
+    def window_nodes_top(self, k: int, min_value: float = float("-inf"), by: str = "score", cap: Optional[int] = None):
+        """(node rows, node indices, n_nodes) of a selection over the last read window's node rows (sg_window_nodes_top): k = 0
+        every node with value >= min_value in node order, else the k highest such, descending, ties by node position.  by: a key
+        of NSEL_BY.  cap defaults to k (k > 0) or the window's node count; nodes beyond it are counted, not returned."""
+        b = self._nby(by)
+        if cap is None:
+            if k:
+                cap = k
+            else:
+                n = C.c_size_t(0)
+                self._ck(self._l.sg_window_nodes(self._h, None, 0, C.byref(n)))
+                cap = n.value
+        out = np.zeros(cap, dtype=NODE_DTYPE); idx = np.zeros(cap, dtype=np.uint32)
+        ns, nn = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._l.sg_window_nodes_top(self._h, b, k, min_value, out.ctypes.data, idx.ctypes.data, cap, C.byref(ns), C.byref(nn)))
+        m = min(ns.value, cap)
+        return out[:m], idx[:m], nn.value
+
+    def window_nodes_select(self, k: int, min_value: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0,
+                            by: str = "score"):
+        """Select from the node rows of the window window_run closed last into device memory (sg_window_nodes_select): d_out
+        [cap] node rows (0 = none), d_index [cap] u32 (0 = none), d_n one u64 = nodes selected; enqueued on `stream` (0 = that
+        window's stream)."""
+        self._ck(self._l.sg_window_nodes_select(self._h, self._nby(by), k, min_value, d_out or None, d_index or None, cap, d_n,
+                                                stream or None))
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

@@ -450,6 +450,63 @@ int sg_window_nodes(sg_handle h, sg_node_out* out, size_t cap, size_t* n);
  * them on that window's stream).                                                                                              */
 int sg_window_nodes_buffer(sg_handle h, void** d_nodes, void** d_count);
 
+/* ---- node baselines (K10) and node selection: each service against its own past, on the device ----------------------------- *
+ * Opt-in (sg_set_node_trend, on an engine with the node rollup); without it nothing is computed or allocated, and the edge rows,
+ * node rows, edge trend and vanished lists are the same either way.  K8's baseline kept per node side instead of per edge:
+ * node key nk = type << 32 | x with K8's rule for one ref (x = SG_REF_VALUE(ref), the IPv4 address for OBIP refs); each node has
+ * two entries, (from_key, to_key) = (nk, 0) "in" (the requests it received: in_count, in_err, in_sum_ns) and (nk, 1) "out" (the
+ * requests it sent: out_*).  Node rows are ascending by ref and the outbound-IP list is ascending, so a window's samples are
+ * strictly ascending in (nk, side) and an OBIP node keeps its baseline when its index in the list changes.
+ * Sample of a side with count c > 0 (u64), sum s (the node row's wrapping u64 *_sum_ns) and errors e, exact in fp64:
+ *   x_lat = min(floor(s / c), 2^52), x_err = floor(e * 2^20 / c)   (exact: the product does not overflow)
+ * A side with c == 0 neither creates nor refreshes an entry.  The entry update, expiry and capacity cut are K8's word for word,
+ * with sg_trend_params (max_entries 0 = min(2^31, 4 x the engine's node capacity)) and a trend-window counter of its own.
+ * Row k of a window's sg_node_trend belongs to node row k of sg_window_nodes; each side is K8's row rule from that side's entry as
+ * it stood BEFORE the window's update: *_seen = its n; *_lat_dev / *_err_dev are 0 when the side's count is 0 or *_seen < warmup;
+ * *_base_mean_us = (float)(lat_mean / 1000), 0 without an entry.  Every close path updates it (one call, begin + end,
+ * sg_window_run); with several windows in flight the updates run in window order.                                            */
+typedef struct sg_node_trend {
+    float    in_lat_dev, in_err_dev, out_lat_dev, out_err_dev;
+    float    in_base_mean_us, out_base_mean_us;
+    uint32_t in_seen, out_seen;
+} sg_node_trend;                /* 32 bytes, no padding */
+/* NULL = off (frees the baseline); params = on, and (re)enabling starts an empty baseline.  Memory is allocated here, never at
+ * create.  SG_ESTATE when the node rollup is off or a flush is open, SG_EINVAL on bad params.  sg_set_nodes(h, 0) switches it
+ * off too; sg_set_trend does not touch it, nor it the edge trend.  Node trend calls on an engine without it: SG_ESTATE.        */
+int sg_set_node_trend(sg_handle h, const sg_trend_params* p);
+/* The node trend rows of the last READ window (as sg_window_nodes).  node_index NULL: every node row, *n = nodes; else out[k] =
+ * the row of node node_index[k] (each < nodes, else SG_EINVAL), *n = n_index.  min(*n, cap) rows are written.  SG_ESTATE for a
+ * window closed while the node trend was off, and while a flush is open.                                                     */
+int sg_window_node_trend(sg_handle h, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n);
+/* Device sg_node_trend[] of the window sg_window_run closed last (its count is sg_window_nodes_buffer's; valid until the slot is
+ * reused; read it on that window's stream).                                                                                  */
+int sg_window_node_trend_buffer(sg_handle h, void** d_trend);
+/* The node baseline in key order (to_key = side): min(*n, cap) entries, *n = entries (waits for the updates enqueued so far).    */
+int sg_node_trend_entries(sg_handle h, sg_trend_entry* out, size_t cap, size_t* n);
+int sg_node_trend_stats_get(sg_handle h, sg_trend_stats* out);   /* (waits for the updates enqueued so far) */
+
+/* Node selection (K7 over node rows): the K7 semantics with "row" read as "node row" and the key chosen by `by` — a plain float
+ * comparison value >= min_value (NaN never), k = 0 every candidate in node order, 1 <= k <= SG_SELECT_MAX_K the highest values
+ * descending, ties (-0.0 == +0.0) by node position.  SG_NSEL_NEW: the nodes with in_seen == 0, out_seen == 0 and a request on
+ * either side, all with one key (min_value ignored): k > 0 gives the first k in node order.  Rows are byte-identical to
+ * sg_window_nodes's; node_index[j] (may be NULL) = that position, to pass straight to sg_window_node_trend.  by > 5 or
+ * k > SG_SELECT_MAX_K: SG_EINVAL; the node rollup off, or a trend key with the node trend off: SG_ESTATE.                    */
+#define SG_NSEL_SCORE       0u  /* sg_node_out.score (needs only the rollup) */
+#define SG_NSEL_IN_LAT_DEV  1u
+#define SG_NSEL_IN_ERR_DEV  2u
+#define SG_NSEL_OUT_LAT_DEV 3u
+#define SG_NSEL_OUT_ERR_DEV 4u
+#define SG_NSEL_NEW         5u  /* in_seen == 0 && out_seen == 0 && in_count + out_count > 0; min_value ignored */
+/* Over the node rows of the last READ window, on the engine's read stream; returns when done.  *n_selected = nodes selected (may
+ * exceed cap; then only cap rows and indices were written), *n_nodes = nodes of the window.  SG_ESTATE also for a window closed
+ * while the rollup (or, for a trend key, the node trend) was off, and while a flush is open.                                  */
+int sg_window_nodes_top(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out,
+                        uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
+/* Device-resident form over the window sg_window_run closed last: d_out [cap] node rows (may be NULL), d_index [cap] u32 (may be
+ * NULL), *d_n (u64) = nodes selected, enqueued on `stream` (NULL = the stream that window ran on), no host sync.                */
+int sg_window_nodes_select(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out,
+                           uint32_t* d_index, size_t cap, uint64_t* d_n, void* stream);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.

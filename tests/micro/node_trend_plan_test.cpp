@@ -1,0 +1,37 @@
+// CPU driver of the per-node baselines' plan in alaz_amd/csrc/sg_plan.hpp (tests/test_node_trend_host.py).  stdin: one
+// "ncap slots struct_size shift warmup ttl max_entries lat_floor_ns err_floor reserved" per line; stdout: one JSON object per line —
+// check_node_trend's verdict, the parameters it resolved and plan_node_trend of them.
+#include <cstdio>
+#include <iostream>
+#include <sstream>
+#include <string>
+
+#include "../../alaz_amd/csrc/sg_plan.hpp"
+
+using namespace sgplan;
+
+int main() {
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        if (line.empty()) continue;
+        std::istringstream in(line);
+        unsigned long long nc, slots, ss, shift, warmup, ttl, maxe, lf, ef, res;
+        in >> nc >> slots >> ss >> shift >> warmup >> ttl >> maxe >> lf >> ef >> res;
+        sg_trend_params p{(uint32_t)ss, (uint32_t)shift, (uint32_t)warmup, (uint32_t)ttl, maxe, lf, (uint32_t)ef, (uint32_t)res};
+        sg_trend_params r{};
+        const int rc = check_node_trend(p, (u32)nc, &r);
+        std::printf("{\"ncap\": %llu, \"slots\": %llu, \"rc\": %d, \"node_trend_size\": %zu", nc, slots, rc, sizeof(sg_node_trend));
+        if (rc == SG_OK) {
+            const NodeTrendPlan t = plan_node_trend((u32)nc, (u32)slots, r);
+            std::printf(", \"shift\": %u, \"warmup\": %u, \"ttl\": %u, \"max_entries\": %llu, \"lat_floor_ns\": %llu, \"err_floor\": %u, "
+                        "\"entries\": %llu, \"wgs\": %u, \"soa_bytes\": %llu, \"ctl_bytes\": %llu, \"blk_bytes\": %llu, \"thread_bytes\": %llu, "
+                        "\"rows_bytes\": %llu, \"total_bytes\": %llu, \"threads\": %u, \"max_wgs\": %u, \"per_thread\": %u",
+                        r.shift, r.warmup, r.ttl, (unsigned long long)r.max_entries, (unsigned long long)r.lat_floor_ns, r.err_floor,
+                        (unsigned long long)t.entries, t.wgs, (unsigned long long)t.soa_bytes, (unsigned long long)t.ctl_bytes,
+                        (unsigned long long)t.blk_bytes, (unsigned long long)t.thread_bytes, (unsigned long long)t.rows_bytes,
+                        (unsigned long long)t.total_bytes, kTrendThreads, kTrendMaxWgs, kTrendPerThread);
+        }
+        std::printf("}\n");
+    }
+    return 0;
+}
