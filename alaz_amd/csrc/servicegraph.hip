@@ -125,16 +125,23 @@ struct sg_engine {
     std::vector<hipEvent_t> ev_pool;
     // sg_window_run_sharded: exchange buffers of the sharded window (allocated at the first call; world = cfg.world)
     struct Xchg { u32* ob_local = nullptr; u32* ob_all = nullptr; u32* req = nullptr; u32* serve = nullptr; float* rows_out = nullptr; float* rows_in = nullptr; u32 capp = 0, ob_stride = 0; } xc;
-    // K7, the selection (sg_sel.h): scratch allocated at the first selection (sg_plan.hpp plan_select), the host flushes' device
-    // staging grown on demand.  Selections on different streams share the scratch: each one waits for the previous one (ev).
-    struct Sel { sgplan::SelPlan plan; u32* keys = nullptr; u32* hist = nullptr; u32* blk = nullptr; u32* state = nullptr; u64* pairs = nullptr; u64* n = nullptr;
-                 sg_edge_out* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; u64* h_n = nullptr; hipEvent_t ev = nullptr; bool pending = false; } sel;
+    // K7's scratch in plan_select's layout (sg_sel.h; carved by sel_init), the host count and the event: selections that share it
+    // wait for each other (ev).
+    struct SelScratch { sgplan::SelPlan plan; u32* keys = nullptr; u32* hist = nullptr; u32* blk = nullptr; u32* state = nullptr; u64* pairs = nullptr;
+                        u64* n = nullptr; u64* h_n = nullptr; hipEvent_t ev = nullptr; bool pending = false; };
+    // K7, the selection: scratch allocated at the first selection (sg_plan.hpp plan_select), the host flushes' device staging grown
+    // on demand.  Selections on different streams share the scratch.
+    struct Sel : SelScratch { sg_edge_out* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; } sel;
     u64* last_ctr = nullptr; hipStream_t last_stream = nullptr;   // counters and stream of the window last_rows belongs to (sg_window_select)
-    // K8, the per-edge baselines (sg_trend.h): allocated at sg_set_trend (sg_plan.hpp plan_trend), one allocation.  The baseline is
+    // A baseline (sg_trend.h), K8's per-edge one (trend, Row = sg_edge_trend) or K10's per-node one (ntrend, sg_node_trend):
+    // allocated at sg_set_trend / sg_set_node_trend (sg_plan.hpp plan_trend / plan_node_trend), one allocation.  The baseline is
     // engine-wide: every update waits for the previous one (ev), whichever slot's stream it runs on.  w = trend windows enqueued.
-    struct Trend { bool on = false; sg_trend_params p{}; sgplan::TrendPlan plan; char* mem = nullptr; TrendSoA buf[2] = {}; u64* ctl = nullptr; u32* blk = nullptr;
-                   K8Thread* th = nullptr; std::vector<sg_edge_trend*> rows; u32 w = 0; hipEvent_t ev = nullptr; bool pending = false; int run_slot = -1;
-                   sg_edge_trend* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; } trend;
+    // Per slot: the trend rows; K10's also whether the window in the slot made them (valid).  run_slot is K8's (K10 uses the rollup's).
+    template <class Row>
+    struct Baseline { bool on = false; sg_trend_params p{}; sgplan::TrendPlan plan; char* mem = nullptr; TrendSoA buf[2] = {}; u64* ctl = nullptr;
+                      u32* blk = nullptr; K8Thread* th = nullptr; std::vector<Row*> rows; std::vector<char> valid; u32 w = 0; hipEvent_t ev = nullptr;
+                      bool pending = false; int run_slot = -1; Row* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; };
+    Baseline<sg_edge_trend> trend;
     // K8's vanished list: allocated at sg_set_vanished (sg_plan.hpp plan_vanished), one allocation, freed by any sg_set_trend.  The
     // counts are scratch shared like the baseline; per slot: the list, its count, and whether the window in the slot made one (valid).
     struct Vanished { bool on = false; sg_vanished_params p{}; sgplan::VanishedPlan plan; char* mem = nullptr; u32* th = nullptr; u32* blk = nullptr;
@@ -145,16 +152,11 @@ struct sg_engine {
     struct Nodes { bool on = false; sgplan::NodesPlan plan; char* mem = nullptr; u32* dst = nullptr; K9Side* tout = nullptr; K9Side* tin = nullptr;
                    K9Side* part = nullptr; u32* blk = nullptr; std::vector<sg_node_out*> rows; std::vector<u64*> count; std::vector<char> valid;
                    hipEvent_t ev = nullptr; bool pending = false; int run_slot = -1; } nodes;
-    // K10, the per-node baselines (sg_node_trend.h): allocated at sg_set_node_trend (sg_plan.hpp plan_node_trend), one allocation,
-    // freed with the rollup.  Chained like K8 (ev); per slot: the node trend rows and whether the window in the slot made them.
-    struct NodeTrend { bool on = false; sg_trend_params p{}; sgplan::NodeTrendPlan plan; char* mem = nullptr; TrendSoA buf[2] = {}; u64* ctl = nullptr;
-                       u32* blk = nullptr; K8Thread* th = nullptr; std::vector<sg_node_trend*> rows; std::vector<char> valid; u32 w = 0;
-                       hipEvent_t ev = nullptr; bool pending = false; sg_node_trend* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; } ntrend;
+    // K10, the per-node baselines (sg_node_trend.h): a Baseline, freed with the rollup
+    Baseline<sg_node_trend> ntrend;
     // node selection (K7 over node rows): scratch of plan_select(ncap) allocated at the first one, with the counter block k10_keys
-    // fills, an index array and the host form's row staging (ncap each).  Node selections wait for each other (ev).
-    struct NSel { sgplan::SelPlan plan; u32* keys = nullptr; u32* hist = nullptr; u32* blk = nullptr; u32* state = nullptr; u64* pairs = nullptr;
-                  u64* n = nullptr; u64* ctr = nullptr; u32* idx = nullptr; sg_node_out* stage = nullptr; u64* h_n = nullptr; char* mem = nullptr;
-                  hipEvent_t ev = nullptr; bool pending = false; } nsel;
+    // fills, an index array and the host form's row staging (ncap each), in a block of its own (mem).
+    struct NSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; sg_node_out* stage = nullptr; char* mem = nullptr; } nsel;
 };
 
 namespace {
@@ -577,37 +579,51 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
 static_assert(sizeof(sg_edge_vanished) == 64 && sgplan::kTrendThreads == K8_THREADS && sgplan::kTrendMaxWgs <= K8_SCAN_THREADS,
               "plan_trend / plan_vanished size the launches of sg_trend.h");
-// enqueue window w's update on stream s behind the previous update (any stream); the window's trend rows go to the slot's buffer
-int launch_trend(sg_engine* e, hipStream_t s) {
-    sg_engine::Trend& t = e->trend;
+// TrendArgs' baseline part of window w + 1's update of t: the window's outbound-IP list, the buffers and scratch, the parameters
+template <class Row>
+TrendArgs baseline_args(const sg_engine* e, const sg_engine::Baseline<Row>& t) {
     const sg_trend_params& p = t.p;
     TrendArgs a{};
-    a.rows = e->d.rows; a.ctr = e->d.ctr; a.ob_sorted = e->d.ob_sorted; a.max_obip = e->d.max_obip;
-    a.max_edges = e->cfg.max_edges; a.cap = t.plan.entries;
+    a.ctr = e->d.ctr; a.ob_sorted = e->d.ob_sorted; a.max_obip = e->d.max_obip;
+    a.cap = t.plan.entries;
     a.buf[0] = t.buf[0]; a.buf[1] = t.buf[1];
-    a.out = t.rows[e->cur]; a.th = t.th; a.blk = t.blk; a.ctl = t.ctl;
+    a.th = t.th; a.blk = t.blk; a.ctl = t.ctl;
     a.w = t.w + 1; a.warmup = p.warmup; a.ttl = p.ttl;
     a.alpha = std::ldexp(1.0, -(int)p.shift); a.lat_floor = (double)p.lat_floor_ns; a.err_floor = (double)p.err_floor;
+    return a;
+}
+// enqueue an update of t on stream s (the launches: launch()) behind the previous update (any stream)
+template <class Row, class F>
+int enqueue_baseline(sg_engine* e, sg_engine::Baseline<Row>& t, hipStream_t s, F launch) {
     if (t.pending) HIP_TRY(e, hipStreamWaitEvent(s, t.ev, 0));
-    sg_engine::Vanished& v = e->vanished;
-    if (v.on) {                                                       // the same three launches with the vanished count
-        VanArgs va{};
-        va.out = v.rows[e->cur]; va.count = v.count[e->cur]; va.th = v.th; va.blk = v.blk;
-        va.max_rows = v.plan.rows; va.silent = v.p.silent_windows; va.min_seen = v.p.min_seen;
-        hipLaunchKernelGGL(k8_count_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
-        hipLaunchKernelGGL(k8_scan_v, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs, va);
-        hipLaunchKernelGGL(k8_write_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
-        v.valid[e->cur] = 1;
-    } else {
-        hipLaunchKernelGGL(k8_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-        hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs);
-        hipLaunchKernelGGL(k8_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-    }
+    launch();
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipEventRecord(t.ev, s));
     t.pending = true;
     t.w++;
     return SG_OK;
+}
+// enqueue window w's update on stream s; the window's trend rows go to the slot's buffer
+int launch_trend(sg_engine* e, hipStream_t s) {
+    sg_engine::Baseline<sg_edge_trend>& t = e->trend;
+    TrendArgs a = baseline_args(e, t);
+    a.rows = e->d.rows; a.max_edges = e->cfg.max_edges; a.out = t.rows[e->cur];
+    sg_engine::Vanished& v = e->vanished;
+    return enqueue_baseline(e, t, s, [&] {
+        if (v.on) {                                                   // the same three launches with the vanished count
+            VanArgs va{};
+            va.out = v.rows[e->cur]; va.count = v.count[e->cur]; va.th = v.th; va.blk = v.blk;
+            va.max_rows = v.plan.rows; va.silent = v.p.silent_windows; va.min_seen = v.p.min_seen;
+            hipLaunchKernelGGL(k8_count_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
+            hipLaunchKernelGGL(k8_scan_v, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs, va);
+            hipLaunchKernelGGL(k8_write_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
+            v.valid[e->cur] = 1;
+        } else {
+            hipLaunchKernelGGL(k8_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs);
+            hipLaunchKernelGGL(k8_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+        }
+    });
 }
 // ---- K9, the node rollup (engine lock held) ---------------------------------------------------------------------------------
 static_assert(sgplan::kNodesThreads == K9_THREADS && sgplan::kNodesChunk == K9_CHUNK && sgplan::kNodesRangeNodes == K9_IN_NR &&
@@ -637,42 +653,33 @@ int launch_nodes(sg_engine* e, hipStream_t s) {
 }
 // ---- K10, the per-node baselines (engine lock held) ------------------------------------------------------------------------------
 static_assert(sizeof(sg_node_trend) == 32 && sizeof(K10Sample) == 40, "sg_node_trend layout");
-// enqueue the node baseline's update by the window in slot cur on stream s (behind its rollup, on the same stream), behind the
-// previous update (any stream); the window's node trend rows go to the slot's buffer
+// enqueue the node baseline's update by the window in slot cur on stream s (behind its rollup, on the same stream); the window's
+// node trend rows go to the slot's buffer
 int launch_node_trend(sg_engine* e, hipStream_t s) {
-    sg_engine::NodeTrend& t = e->ntrend;
-    const sg_trend_params& p = t.p;
+    sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
     NodeTrendArgs a{};
-    a.t.ctr = e->d.ctr; a.t.ob_sorted = e->d.ob_sorted; a.t.max_obip = e->d.max_obip;
-    a.t.cap = t.plan.entries;
-    a.t.buf[0] = t.buf[0]; a.t.buf[1] = t.buf[1];
-    a.t.th = t.th; a.t.blk = t.blk; a.t.ctl = t.ctl;
-    a.t.w = t.w + 1; a.t.warmup = p.warmup; a.t.ttl = p.ttl;
-    a.t.alpha = std::ldexp(1.0, -(int)p.shift); a.t.lat_floor = (double)p.lat_floor_ns; a.t.err_floor = (double)p.err_floor;
+    a.t = baseline_args(e, t);
     a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur]; a.ncap = e->nodes.plan.ncap; a.out = t.rows[e->cur];
-    if (t.pending) HIP_TRY(e, hipStreamWaitEvent(s, t.ev, 0));
-    hipLaunchKernelGGL(k10_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-    hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs);
-    hipLaunchKernelGGL(k10_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(t.ev, s));
-    t.pending = true;
+    if (const int rc = enqueue_baseline(e, t, s, [&] {
+            hipLaunchKernelGGL(k10_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs);
+            hipLaunchKernelGGL(k10_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+        })) return rc;
     t.valid[e->cur] = 1;
-    t.w++;
     return SG_OK;
 }
-void free_node_trend(sg_engine* e) {
-    sg_engine::NodeTrend& t = e->ntrend;
+template <class Row>
+void free_baseline(sg_engine::Baseline<Row>& t) {
     if (t.mem || t.stage) hipDeviceSynchronize();
     if (t.mem) hipFree(t.mem);
     if (t.stage) hipFree(t.stage);
     if (t.stage_idx) hipFree(t.stage_idx);
     if (t.ev) hipEventDestroy(t.ev);
-    t = sg_engine::NodeTrend{};
+    t = sg_engine::Baseline<Row>{};
 }
 
 void free_nodes(sg_engine* e) {
-    free_node_trend(e);
+    free_baseline(e->ntrend);
     sg_engine::Nodes& n = e->nodes;
     if (n.mem) { hipDeviceSynchronize(); hipFree(n.mem); }
     if (n.ev) hipEventDestroy(n.ev);
@@ -687,13 +694,7 @@ void free_vanished(sg_engine* e) {
 
 void free_trend(sg_engine* e) {
     free_vanished(e);
-    sg_engine::Trend& t = e->trend;
-    if (t.mem || t.stage) hipDeviceSynchronize();
-    if (t.mem) hipFree(t.mem);
-    if (t.stage) hipFree(t.stage);
-    if (t.stage_idx) hipFree(t.stage_idx);
-    if (t.ev) hipEventDestroy(t.ev);
-    t = sg_engine::Trend{};
+    free_baseline(e->trend);
 }
 
 // proj_done: the last SAGE layer already wrote P and Q.  fuse_reset: fold the window reset into the
@@ -816,6 +817,22 @@ hipError_t lds_limit(size_t bytes, K... kernels) {
 }
 
 // ---- K7, the selection (engine lock held) ---------------------------------------------------------------------------------------
+// the scratch of s.plan carved from b (plan_select's layout), the host count, the event and k7_sort's LDS limit
+int sel_init(sg_engine* e, sg_engine::SelScratch& s, char* b) {
+    const sgplan::SelPlan& p = s.plan;
+    s.pairs = (u64*)b; b += p.pair_bytes;                                     // (the u64 arrays first: every offset stays 8-aligned)
+    s.n = (u64*)b; s.state = (u32*)(b + 8); b += p.state_bytes;
+    s.blk = (u32*)b; b += p.blk_bytes;
+    s.hist = (u32*)b; b += p.hist_bytes;
+    s.keys = (u32*)b;
+    HIP_TRY(e, hipHostMalloc((void**)&s.h_n, sizeof(u64)));
+    HIP_TRY(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    HIP_TRY(e, lds_limit(sgplan::select_sort_lds(SG_SELECT_MAX_K), k7_sort));
+    return SG_OK;
+}
+// SelArgs' scratch: s's
+void sel_scratch_args(SelArgs& a, const sg_engine::SelScratch& s) { a.keys = s.keys; a.hist = s.hist; a.blk = s.blk; a.state = s.state; a.pairs = s.pairs; }
+
 // the scratch at the first selection; the device staging of the host flushes holds at least stage_rows rows
 int sel_reserve(sg_engine* e, u64 stage_rows) {
     sg_engine::Sel& s = e->sel;
@@ -825,14 +842,7 @@ int sel_reserve(sg_engine* e, u64 stage_rows) {
         char* b = nullptr;
         HIP_TRY(e, hipMalloc((void**)&b, p.scratch_bytes));
         e->allocs.push_back(b);
-        s.pairs = (u64*)b; b += p.pair_bytes;                                 // (the u64 arrays first: every offset stays 8-aligned)
-        s.n = (u64*)b; s.state = (u32*)(b + 8); b += p.state_bytes;
-        s.blk = (u32*)b; b += p.blk_bytes;
-        s.hist = (u32*)b; b += p.hist_bytes;
-        s.keys = (u32*)b;
-        HIP_TRY(e, hipHostMalloc((void**)&s.h_n, sizeof(u64)));
-        HIP_TRY(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-        HIP_TRY(e, lds_limit(sgplan::select_sort_lds(SG_SELECT_MAX_K), k7_sort));
+        if (const int rc = sel_init(e, s, b)) return rc;
     }
     if (stage_rows > s.stage_cap) {                                          // (no selection is in flight: every host flush synchronises)
         if (s.stage) { hipFree(s.stage); hipFree(s.stage_idx); s.stage = nullptr; s.stage_idx = nullptr; s.stage_cap = 0; }
@@ -866,7 +876,7 @@ int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_scor
     sg_engine::Sel& s = e->sel;
     const u32 wgs = s.plan.wgs;
     a.max_edges = e->cfg.max_edges; a.k = k; a.min_score = min_score;
-    a.keys = s.keys; a.hist = s.hist; a.blk = s.blk; a.state = s.state; a.pairs = s.pairs;
+    sel_scratch_args(a, s);
     if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
     if (by == SG_SEL_SCORE) hipLaunchKernelGGL(k7_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a);
     else hipLaunchKernelGGL(k7_keys_by, dim3(wgs), dim3(K7_THREADS), 0, st, a, tr, by);
@@ -894,15 +904,7 @@ int nsel_reserve(sg_engine* e) {
     s.stage = (sg_node_out*)b; b += stage_bytes;                              // (256-aligned pieces first, then plan_select's layout)
     s.ctr = (u64*)b; b += ctr_bytes;
     s.idx = (u32*)b; b += idx_bytes;
-    s.pairs = (u64*)b; b += p.pair_bytes;
-    s.n = (u64*)b; s.state = (u32*)(b + 8); b += p.state_bytes;
-    s.blk = (u32*)b; b += p.blk_bytes;
-    s.hist = (u32*)b; b += p.hist_bytes;
-    s.keys = (u32*)b;
-    HIP_TRY(e, hipHostMalloc((void**)&s.h_n, sizeof(u64)));
-    HIP_TRY(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    HIP_TRY(e, lds_limit(sgplan::select_sort_lds(SG_SELECT_MAX_K), k7_sort));
-    return SG_OK;
+    return sel_init(e, s, b);
 }
 // enqueue a selection over the node rows of slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
 // be NULL), the count to d_n; behind that window's rollup and node trend (events) and the previous node selection
@@ -913,7 +915,7 @@ int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, fl
     const u64 NC = std::max<u32>(e->d.ncap, 1);
     SelArgs a{};
     a.rows = nullptr; a.ctr = s.ctr; a.max_edges = NC; a.k = k; a.min_score = min_value;
-    a.keys = s.keys; a.hist = s.hist; a.blk = s.blk; a.state = s.state; a.pairs = s.pairs;
+    sel_scratch_args(a, s);
     a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, NC); a.n_out = d_n;
     if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
     if (e->nodes.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->nodes.ev, 0));
@@ -930,6 +932,102 @@ int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, fl
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipEventRecord(s.ev, st));
     s.pending = true;
+    return SG_OK;
+}
+
+// ---- the baselines' and the per-window buffers' shared host code (engine lock held) -----------------------------------------
+// one block of `bytes` for sg_set_*, zeroed; on a failing hipMalloc release() runs and e->err names `call`
+template <class F>
+int alloc_block(sg_engine* e, char** mem, u64 bytes, const char* call, F release) {
+    const hipError_t rc = hipMalloc((void**)mem, bytes);
+    if (rc != hipSuccess) { release(); e->err = std::string(call) + ": hipMalloc: " + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
+    HIP_TRY(e, hipMemset(*mem, 0, bytes));
+    return SG_OK;
+}
+// switch baseline t on (t freed): parameters r, plan P, one block carved into the two SoA buffers, the control block, the scratch
+// and every slot's trend rows — an empty baseline (B = 0 for both parities), zero statistics and rows
+template <class Row, class F>
+int baseline_on(sg_engine* e, sg_engine::Baseline<Row>& t, const sg_trend_params& r, const sgplan::TrendPlan& P, const char* call, F release) {
+    t.p = r;
+    t.plan = P;
+    HIP_TRY(e, hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &t.mem, P.total_bytes, call, release)) return rc;
+    const u64 C = P.entries;
+    char* b = t.mem;
+    for (int k = 0; k < 2; k++) {                                     // (the u64 / fp64 arrays first: every offset stays 8-aligned)
+        TrendSoA& x = t.buf[k];
+        char* q = b;
+        x.from_key = (u64*)q; q += C * 8; x.to_key = (u64*)q; q += C * 8;
+        x.lat_mean = (double*)q; q += C * 8; x.lat_dev = (double*)q; q += C * 8; x.err_mean = (double*)q; q += C * 8; x.err_dev = (double*)q; q += C * 8;
+        x.n = (u32*)q; q += C * 4; x.last = (u32*)q;
+        b += P.soa_bytes;
+    }
+    t.ctl = (u64*)b; b += P.ctl_bytes;
+    t.blk = (u32*)b; b += P.blk_bytes;
+    t.th = (K8Thread*)b; b += P.thread_bytes;
+    for (size_t k = 0; k < e->slots.size(); k++) { t.rows.push_back((Row*)b); b += P.rows_bytes; }
+    t.on = true;
+    return SG_OK;
+}
+// the trend rows of the last read window (slot cur), N of them: every row, or those at idx (an index >= N: SG_EINVAL, `beyond`),
+// gathered on the device so that only they cross PCIe
+template <class Row>
+int baseline_rows(sg_engine* e, sg_engine::Baseline<Row>& t, size_t N, const u32* idx, size_t n_index, Row* out, size_t cap, size_t* n,
+                  void (*gather)(const Row*, const u32*, u64, Row*), const char* beyond) {
+    const Row* src = t.rows[e->cur];
+    if (!idx) {
+        if (n) *n = N;
+        const size_t take = std::min(N, cap);
+        if (out && take) { if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev)); HIP_TRY(e, hipMemcpy(out, src, take * sizeof(Row), hipMemcpyDeviceToHost)); }
+        return SG_OK;
+    }
+    for (size_t k = 0; k < n_index; k++) if (idx[k] >= N) { e->err = beyond; return SG_EINVAL; }
+    if (n) *n = n_index;
+    const size_t take = std::min(n_index, cap);
+    if (!out || !take) return SG_OK;
+    if (take > t.stage_cap) {
+        if (t.stage) { hipFree(t.stage); hipFree(t.stage_idx); t.stage = nullptr; t.stage_idx = nullptr; t.stage_cap = 0; }
+        const size_t want = std::max<size_t>(take, 1024);
+        HIP_TRY(e, hipMalloc((void**)&t.stage, want * sizeof(Row)));
+        HIP_TRY(e, hipMalloc((void**)&t.stage_idx, want * sizeof(u32)));
+        t.stage_cap = want;
+    }
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    HIP_TRY(e, hipMemcpyAsync(t.stage_idx, idx, take * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
+    hipLaunchKernelGGL(gather, dim3((unsigned)((take + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)t.stage_idx, (u64)take, t.stage);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(out, t.stage, take * sizeof(Row), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    return SG_OK;
+}
+// the baseline in key order (sg_trend_entries, sg_node_trend_entries)
+template <class Row>
+int baseline_entries(sg_engine* e, const sg_engine::Baseline<Row>& t, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    u64 ctl[K8C_WORDS];
+    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+    const u32 par = t.w & 1u;                                          // (w = 0: parity 0, B = 0)
+    const size_t B = (size_t)ctl[K8C_B0 + par];
+    if (n) *n = B;
+    const size_t take = std::min(B, cap);
+    if (!out || !take) return SG_OK;
+    const TrendSoA& x = t.buf[par];
+    std::vector<u64> fk(take), tk(take); std::vector<double> lm(take), ld(take), em(take), ed(take); std::vector<u32> cn(take), ls(take);
+    HIP_TRY(e, hipMemcpy(fk.data(), x.from_key, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(tk.data(), x.to_key, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(lm.data(), x.lat_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ld.data(), x.lat_dev, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(em.data(), x.err_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ed.data(), x.err_dev, take * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(cn.data(), x.n, take * 4, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ls.data(), x.last, take * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < take; i++) out[i] = sg_trend_entry{fk[i], tk[i], lm[i], ld[i], em[i], ed[i], cn[i], ls[i]};
+    return SG_OK;
+}
+// the baseline's running statistics (sg_trend_stats_get, sg_node_trend_stats_get)
+template <class Row>
+int baseline_stats(sg_engine* e, const sg_engine::Baseline<Row>& t, sg_trend_stats* out) {
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    u64 ctl[K8C_WORDS];
+    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+    out->windows = ctl[K8C_WINDOWS]; out->entries = ctl[K8C_B0 + (t.w & 1u)];
+    out->inserted = ctl[K8C_INSERTED]; out->expired = ctl[K8C_EXPIRED]; out->dropped = ctl[K8C_DROPPED];
     return SG_OK;
 }
 }  // namespace
@@ -1747,69 +1845,19 @@ int sg_set_trend(sg_handle e, const sg_trend_params* p) {
     if (e->closing || e->flush_open) { e->err = "sg_set_trend while a flush is open"; return SG_ESTATE; }
     free_trend(e);
     if (!p) return SG_OK;
-    sg_engine::Trend& t = e->trend;
-    t.p = r;
-    t.plan = sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r);
-    const sgplan::TrendPlan& P = t.plan;
-    HIP_TRY(e, hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
-    {
-        const hipError_t rc = hipMalloc((void**)&t.mem, P.total_bytes);
-        if (rc != hipSuccess) { free_trend(e); e->err = std::string("sg_set_trend: hipMalloc: ") + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
-    }
-    HIP_TRY(e, hipMemset(t.mem, 0, P.total_bytes));                  // an empty baseline (B = 0 for both parities), zero statistics and rows
-    const u64 C = P.entries;
-    char* b = t.mem;
-    for (int k = 0; k < 2; k++) {                                     // (the u64 / fp64 arrays first: every offset stays 8-aligned)
-        TrendSoA& x = t.buf[k];
-        char* q = b;
-        x.from_key = (u64*)q; q += C * 8; x.to_key = (u64*)q; q += C * 8;
-        x.lat_mean = (double*)q; q += C * 8; x.lat_dev = (double*)q; q += C * 8; x.err_mean = (double*)q; q += C * 8; x.err_dev = (double*)q; q += C * 8;
-        x.n = (u32*)q; q += C * 4; x.last = (u32*)q;
-        b += P.soa_bytes;
-    }
-    t.ctl = (u64*)b; b += P.ctl_bytes;
-    t.blk = (u32*)b; b += P.blk_bytes;
-    t.th = (K8Thread*)b; b += P.thread_bytes;
-    for (size_t k = 0; k < e->slots.size(); k++) { t.rows.push_back((sg_edge_trend*)b); b += P.rows_bytes; }
-    t.on = true;
-    return SG_OK;
+    return baseline_on(e, e->trend, r, sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r), "sg_set_trend", [e] { free_trend(e); });
 }
 int sg_window_trend(sg_handle e, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::Trend& t = e->trend;
-    if (!t.on) { e->err = "sg_window_trend: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    if (!e->trend.on) { e->err = "sg_window_trend: the trend is off (sg_set_trend)"; return SG_ESTATE; }
     const size_t E = (size_t)e->h_ctr[C_N_EDGES];                      // of the last read window
-    const sg_edge_trend* src = t.rows[e->cur];
-    if (!row_index) {
-        if (n) *n = E;
-        const size_t take = std::min(E, cap);
-        if (out && take) { if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev)); HIP_TRY(e, hipMemcpy(out, src, take * sizeof(sg_edge_trend), hipMemcpyDeviceToHost)); }
-        return SG_OK;
-    }
-    for (size_t k = 0; k < n_index; k++) if (row_index[k] >= E) { e->err = "sg_window_trend: a row index beyond the window's edges"; return SG_EINVAL; }
-    if (n) *n = n_index;
-    const size_t take = std::min(n_index, cap);
-    if (!out || !take) return SG_OK;
-    if (take > t.stage_cap) {
-        if (t.stage) { hipFree(t.stage); hipFree(t.stage_idx); t.stage = nullptr; t.stage_idx = nullptr; t.stage_cap = 0; }
-        const size_t want = std::max<size_t>(take, 1024);
-        HIP_TRY(e, hipMalloc((void**)&t.stage, want * sizeof(sg_edge_trend)));
-        HIP_TRY(e, hipMalloc((void**)&t.stage_idx, want * sizeof(u32)));
-        t.stage_cap = want;
-    }
-    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
-    HIP_TRY(e, hipMemcpyAsync(t.stage_idx, row_index, take * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
-    hipLaunchKernelGGL(k8_gather, dim3((unsigned)((take + 255) / 256)), dim3(256), 0, e->rd_stream, (const sg_edge_trend*)src, (const u32*)t.stage_idx, (u64)take, t.stage);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipMemcpyAsync(out, t.stage, take * sizeof(sg_edge_trend), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    return SG_OK;
+    return baseline_rows(e, e->trend, E, row_index, n_index, out, cap, n, k8_gather, "sg_window_trend: a row index beyond the window's edges");
 }
 int sg_window_trend_buffer(sg_handle e, void** d_trend) {
     if (!e || !d_trend) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Trend& t = e->trend;
+    const sg_engine::Baseline<sg_edge_trend>& t = e->trend;
     if (!t.on) { e->err = "sg_window_trend_buffer: the trend is off (sg_set_trend)"; return SG_ESTATE; }
     *d_trend = t.rows[t.run_slot >= 0 ? t.run_slot : e->cur];
     return SG_OK;
@@ -1817,36 +1865,14 @@ int sg_window_trend_buffer(sg_handle e, void** d_trend) {
 int sg_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Trend& t = e->trend;
-    if (!t.on) { e->err = "sg_trend_entries: the trend is off (sg_set_trend)"; return SG_ESTATE; }
-    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
-    u64 ctl[K8C_WORDS];
-    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-    const u32 par = t.w & 1u;                                          // (w = 0: parity 0, B = 0)
-    const size_t B = (size_t)ctl[K8C_B0 + par];
-    if (n) *n = B;
-    const size_t take = std::min(B, cap);
-    if (!out || !take) return SG_OK;
-    const TrendSoA& x = t.buf[par];
-    std::vector<u64> fk(take), tk(take); std::vector<double> lm(take), ld(take), em(take), ed(take); std::vector<u32> cn(take), ls(take);
-    HIP_TRY(e, hipMemcpy(fk.data(), x.from_key, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(tk.data(), x.to_key, take * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(lm.data(), x.lat_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ld.data(), x.lat_dev, take * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(em.data(), x.err_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ed.data(), x.err_dev, take * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(cn.data(), x.n, take * 4, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ls.data(), x.last, take * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < take; i++) out[i] = sg_trend_entry{fk[i], tk[i], lm[i], ld[i], em[i], ed[i], cn[i], ls[i]};
-    return SG_OK;
+    if (!e->trend.on) { e->err = "sg_trend_entries: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    return baseline_entries(e, e->trend, out, cap, n);
 }
 int sg_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Trend& t = e->trend;
-    if (!t.on) { e->err = "sg_trend_stats_get: the trend is off (sg_set_trend)"; return SG_ESTATE; }
-    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
-    u64 ctl[K8C_WORDS];
-    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-    out->windows = ctl[K8C_WINDOWS]; out->entries = ctl[K8C_B0 + (t.w & 1u)];
-    out->inserted = ctl[K8C_INSERTED]; out->expired = ctl[K8C_EXPIRED]; out->dropped = ctl[K8C_DROPPED];
-    return SG_OK;
+    if (!e->trend.on) { e->err = "sg_trend_stats_get: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    return baseline_stats(e, e->trend, out);
 }
 
 // ---- K8's vanished list ---------------------------------------------------------------------------------------------------
@@ -1864,11 +1890,7 @@ int sg_set_vanished(sg_handle e, const sg_vanished_params* p) {
     v.p = r;
     v.plan = sgplan::plan_vanished(e->trend.plan, slots, r);
     const sgplan::VanishedPlan& P = v.plan;
-    {
-        const hipError_t rc = hipMalloc((void**)&v.mem, P.total_bytes);
-        if (rc != hipSuccess) { free_vanished(e); e->err = std::string("sg_set_vanished: hipMalloc: ") + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
-    }
-    HIP_TRY(e, hipMemset(v.mem, 0, P.total_bytes));
+    if (const int rc = alloc_block(e, &v.mem, P.total_bytes, "sg_set_vanished", [e] { free_vanished(e); })) return rc;
     char* b = v.mem;
     v.th = (u32*)b; b += P.thread_bytes;
     v.blk = (u32*)b; b += P.blk_bytes;
@@ -1917,11 +1939,7 @@ int sg_set_nodes(sg_handle e, int on) {
     const sgplan::NodesPlan& P = n.plan;
     HIP_TRY(e, lds_limit(P.lds_bytes, k9_in_part));
     HIP_TRY(e, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
-    {
-        const hipError_t rc = hipMalloc((void**)&n.mem, P.total_bytes);
-        if (rc != hipSuccess) { free_nodes(e); e->err = std::string("sg_set_nodes: hipMalloc: ") + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
-    }
-    HIP_TRY(e, hipMemset(n.mem, 0, P.total_bytes));                   // the out table starts at zero (k9_write keeps it so)
+    if (const int rc = alloc_block(e, &n.mem, P.total_bytes, "sg_set_nodes", [e] { free_nodes(e); })) return rc;   // (zeroed: the out table starts at zero, k9_write keeps it so)
     char* b = n.mem;                                                  // (the 64-byte tables first: every offset stays 256-aligned anyway)
     n.tout = (K9Side*)b; b += P.table_bytes;
     n.tin = (K9Side*)b; b += P.table_bytes;
@@ -1967,77 +1985,30 @@ int sg_set_node_trend(sg_handle e, const sg_trend_params* p) {
     if (e->closing || e->flush_open) { e->err = "sg_set_node_trend while a flush is open"; return SG_ESTATE; }
     sg_trend_params r{};
     if (p && sgplan::check_node_trend(*p, e->nodes.plan.ncap, &r)) { e->err = "sg_set_node_trend: bad parameters"; return SG_EINVAL; }
-    free_node_trend(e);
+    sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
+    free_baseline(t);
     if (!p) return SG_OK;
-    sg_engine::NodeTrend& t = e->ntrend;
-    const u32 slots = (u32)std::max<size_t>(e->slots.size(), 1);
-    t.p = r;
-    t.plan = sgplan::plan_node_trend(e->nodes.plan.ncap, slots, r);
-    const sgplan::NodeTrendPlan& P = t.plan;
-    HIP_TRY(e, hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
-    {
-        const hipError_t rc = hipMalloc((void**)&t.mem, P.total_bytes);
-        if (rc != hipSuccess) { free_node_trend(e); e->err = std::string("sg_set_node_trend: hipMalloc: ") + hipGetErrorString(rc); return rc == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV; }
-    }
-    HIP_TRY(e, hipMemset(t.mem, 0, P.total_bytes));                  // an empty baseline (B = 0 for both parities), zero statistics and rows
-    const u64 C = P.entries;
-    char* b = t.mem;
-    for (int k = 0; k < 2; k++) {                                     // (K8's SoA layout)
-        TrendSoA& x = t.buf[k];
-        char* q = b;
-        x.from_key = (u64*)q; q += C * 8; x.to_key = (u64*)q; q += C * 8;
-        x.lat_mean = (double*)q; q += C * 8; x.lat_dev = (double*)q; q += C * 8; x.err_mean = (double*)q; q += C * 8; x.err_dev = (double*)q; q += C * 8;
-        x.n = (u32*)q; q += C * 4; x.last = (u32*)q;
-        b += P.soa_bytes;
-    }
-    t.ctl = (u64*)b; b += P.ctl_bytes;
-    t.blk = (u32*)b; b += P.blk_bytes;
-    t.th = (K8Thread*)b; b += P.thread_bytes;
-    for (u32 k = 0; k < slots; k++) { t.rows.push_back((sg_node_trend*)b); b += P.rows_bytes; }
+    const u32 slots = (u32)e->slots.size();
+    if (const int rc = baseline_on(e, t, r, sgplan::plan_node_trend(e->nodes.plan.ncap, slots, r), "sg_set_node_trend", [&t] { free_baseline(t); })) return rc;
     t.valid.assign(slots, 0);
-    t.on = true;
     return SG_OK;
 }
 int sg_window_node_trend(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::NodeTrend& t = e->ntrend;
+    sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
     if (!t.on) { e->err = "sg_window_node_trend: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
     if (e->closing || e->flush_open) { e->err = "sg_window_node_trend while a flush is open"; return SG_ESTATE; }
     if (!t.valid[e->cur]) { e->err = "sg_window_node_trend: the last read window was closed while the node trend was off"; return SG_ESTATE; }
     if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
     u64 cnt = 0;
     HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    const size_t N = (size_t)cnt;
-    const sg_node_trend* src = t.rows[e->cur];
-    if (!node_index) {
-        if (n) *n = N;
-        const size_t take = std::min(N, cap);
-        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(sg_node_trend), hipMemcpyDeviceToHost));
-        return SG_OK;
-    }
-    for (size_t k = 0; k < n_index; k++) if (node_index[k] >= N) { e->err = "sg_window_node_trend: a node index beyond the window's nodes"; return SG_EINVAL; }
-    if (n) *n = n_index;
-    const size_t take = std::min(n_index, cap);
-    if (!out || !take) return SG_OK;
-    if (take > t.stage_cap) {
-        if (t.stage) { hipFree(t.stage); hipFree(t.stage_idx); t.stage = nullptr; t.stage_idx = nullptr; t.stage_cap = 0; }
-        const size_t want = std::max<size_t>(take, 1024);
-        HIP_TRY(e, hipMalloc((void**)&t.stage, want * sizeof(sg_node_trend)));
-        HIP_TRY(e, hipMalloc((void**)&t.stage_idx, want * sizeof(u32)));
-        t.stage_cap = want;
-    }
-    HIP_TRY(e, hipMemcpyAsync(t.stage_idx, node_index, take * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
-    hipLaunchKernelGGL(k10_gather, dim3((unsigned)((take + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)t.stage_idx, (u64)take, t.stage);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipMemcpyAsync(out, t.stage, take * sizeof(sg_node_trend), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    return SG_OK;
+    return baseline_rows(e, t, (size_t)cnt, node_index, n_index, out, cap, n, k10_gather, "sg_window_node_trend: a node index beyond the window's nodes");
 }
 int sg_window_node_trend_buffer(sg_handle e, void** d_trend) {
     if (!e || !d_trend) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::NodeTrend& t = e->ntrend;
+    const sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
     if (!t.on) { e->err = "sg_window_node_trend_buffer: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
     const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
     if (!t.valid[slot]) { e->err = "sg_window_node_trend_buffer: the window was closed while the node trend was off"; return SG_ESTATE; }
@@ -2047,36 +2018,14 @@ int sg_window_node_trend_buffer(sg_handle e, void** d_trend) {
 int sg_node_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::NodeTrend& t = e->ntrend;
-    if (!t.on) { e->err = "sg_node_trend_entries: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
-    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
-    u64 ctl[K8C_WORDS];
-    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-    const u32 par = t.w & 1u;                                          // (w = 0: parity 0, B = 0)
-    const size_t B = (size_t)ctl[K8C_B0 + par];
-    if (n) *n = B;
-    const size_t take = std::min(B, cap);
-    if (!out || !take) return SG_OK;
-    const TrendSoA& x = t.buf[par];
-    std::vector<u64> fk(take), tk(take); std::vector<double> lm(take), ld(take), em(take), ed(take); std::vector<u32> cn(take), ls(take);
-    HIP_TRY(e, hipMemcpy(fk.data(), x.from_key, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(tk.data(), x.to_key, take * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(lm.data(), x.lat_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ld.data(), x.lat_dev, take * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(em.data(), x.err_mean, take * 8, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ed.data(), x.err_dev, take * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(cn.data(), x.n, take * 4, hipMemcpyDeviceToHost)); HIP_TRY(e, hipMemcpy(ls.data(), x.last, take * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < take; i++) out[i] = sg_trend_entry{fk[i], tk[i], lm[i], ld[i], em[i], ed[i], cn[i], ls[i]};
-    return SG_OK;
+    if (!e->ntrend.on) { e->err = "sg_node_trend_entries: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
+    return baseline_entries(e, e->ntrend, out, cap, n);
 }
 int sg_node_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::NodeTrend& t = e->ntrend;
-    if (!t.on) { e->err = "sg_node_trend_stats_get: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
-    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
-    u64 ctl[K8C_WORDS];
-    HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-    out->windows = ctl[K8C_WINDOWS]; out->entries = ctl[K8C_B0 + (t.w & 1u)];
-    out->inserted = ctl[K8C_INSERTED]; out->expired = ctl[K8C_EXPIRED]; out->dropped = ctl[K8C_DROPPED];
-    return SG_OK;
+    if (!e->ntrend.on) { e->err = "sg_node_trend_stats_get: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
+    return baseline_stats(e, e->ntrend, out);
 }
 
 // ---- node selection ---------------------------------------------------------------------------------------------------------

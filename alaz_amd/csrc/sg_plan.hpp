@@ -406,27 +406,32 @@ inline int check_trend(const sg_trend_params& p, u64 max_edges, sg_trend_params*
 }
 struct TrendPlan {
     u64 entries = 0;              // max_entries
-    u32 wgs = 0;                  // workgroups of k8_count / k8_write
+    u32 wgs = 0;                  // workgroups of the count and write passes (k8_count / k8_write, k10_count / k10_write)
     u64 soa_bytes = 0;            // one baseline buffer: 56 bytes per entry (from_key, to_key, four fp64, n, last)
     u64 ctl_bytes = 0;            // the control block: B per parity, room, statistics
     u64 blk_bytes = 0;            // [wgs][4] u32
     u64 thread_bytes = 0;         // [wgs * 256] per-thread split + counts (16 bytes)
-    u64 rows_bytes = 0;           // one window slot's trend rows: [max_edges] sg_edge_trend
+    u64 rows_bytes = 0;           // one window slot's trend rows
     u64 total_bytes = 0;          // two baseline buffers, the scratch and every slot's rows, each 256-byte aligned
 };
 inline u64 trend_align(u64 b) { return (b + kTrendAlign - 1) / kTrendAlign * kTrendAlign; }
-inline TrendPlan plan_trend(u64 max_edges, u32 slots, const sg_trend_params& p) {
+// a baseline of max_entries entries merged with at most `samples` samples a window, `row_bytes` of trend rows per window slot
+inline TrendPlan plan_baseline(const sg_trend_params& p, u64 samples, u64 row_bytes, u32 slots) {
     TrendPlan t;
     t.entries = p.max_entries;
-    const u64 T = p.max_entries + max_edges, per_wg = (u64)kTrendThreads * kTrendPerThread;
+    const u64 T = p.max_entries + samples, per_wg = (u64)kTrendThreads * kTrendPerThread;
     t.wgs = (u32)std::max<u64>(1, std::min<u64>(kTrendMaxWgs, (T + per_wg - 1) / per_wg));
     t.soa_bytes = trend_align(p.max_entries * (2 * 8 + 4 * 8 + 2 * 4));
     t.ctl_bytes = trend_align(kTrendCtlWords * 8);
     t.blk_bytes = trend_align((u64)t.wgs * 4 * 4);
     t.thread_bytes = trend_align((u64)t.wgs * kTrendThreads * 16);
-    t.rows_bytes = trend_align(std::max<u64>(max_edges, 1) * sizeof(sg_edge_trend));
+    t.rows_bytes = trend_align(row_bytes);
     t.total_bytes = 2 * t.soa_bytes + t.ctl_bytes + t.blk_bytes + t.thread_bytes + (u64)std::max<u32>(slots, 1) * t.rows_bytes;
     return t;
+}
+// K8: the window's edge rows, [max_edges] sg_edge_trend per slot
+inline TrendPlan plan_trend(u64 max_edges, u32 slots, const sg_trend_params& p) {
+    return plan_baseline(p, max_edges, std::max<u64>(max_edges, 1) * sizeof(sg_edge_trend), slots);
 }
 
 // K8's vanished list (sg_set_vanished): the parameters with their defaults filled in against the trend's resolved parameters, and
@@ -515,28 +520,11 @@ inline int check_node_trend(const sg_trend_params& p, u32 ncap, sg_trend_params*
     if (!q.max_entries) q.max_entries = std::min<u64>(kTrendMaxEntries, 4 * std::max<u64>(ncap, 1));
     return check_trend(q, 0, out);
 }
-struct NodeTrendPlan {
-    u64 entries = 0;              // max_entries
-    u32 wgs = 0;                  // workgroups of k10_count / k10_write (and k8_scan's count of them)
-    u64 soa_bytes = 0;            // one baseline buffer: 56 bytes per entry (K8's SoA)
-    u64 ctl_bytes = 0;            // the control block (K8's words)
-    u64 blk_bytes = 0;            // [wgs][4] u32
-    u64 thread_bytes = 0;         // [wgs * 256] per-thread split + counts (16 bytes)
-    u64 rows_bytes = 0;           // one window slot's node trend rows: [ncap] sg_node_trend
-    u64 total_bytes = 0;          // two baseline buffers, the scratch and every slot's rows, each 256-byte aligned
-};
-inline NodeTrendPlan plan_node_trend(u32 ncap, u32 slots, const sg_trend_params& p) {
-    NodeTrendPlan t;
-    t.entries = p.max_entries;
-    const u64 T = p.max_entries + 2 * (u64)ncap, per_wg = (u64)kTrendThreads * kTrendPerThread;
-    t.wgs = (u32)std::max<u64>(1, std::min<u64>(kTrendMaxWgs, (T + per_wg - 1) / per_wg));
-    t.soa_bytes = trend_align(p.max_entries * (2 * 8 + 4 * 8 + 2 * 4));
-    t.ctl_bytes = trend_align(kTrendCtlWords * 8);
-    t.blk_bytes = trend_align((u64)t.wgs * 4 * 4);
-    t.thread_bytes = trend_align((u64)t.wgs * kTrendThreads * 16);
-    t.rows_bytes = trend_align(std::max<u64>(ncap, 1) * sizeof(sg_node_trend));
-    t.total_bytes = 2 * t.soa_bytes + t.ctl_bytes + t.blk_bytes + t.thread_bytes + (u64)std::max<u32>(slots, 1) * t.rows_bytes;
-    return t;
+// K10: two samples per node row, [ncap] sg_node_trend per slot.  The node plan is K8's type; NodeTrendPlan names it for the CPU
+// driver tests/micro/node_trend_plan_test.cpp.
+using NodeTrendPlan = TrendPlan;
+inline TrendPlan plan_node_trend(u32 ncap, u32 slots, const sg_trend_params& p) {
+    return plan_baseline(p, 2 * (u64)ncap, std::max<u64>(ncap, 1) * sizeof(sg_node_trend), slots);
 }
 
 // the plan's share of the kernels' argument (Dev, sg_device.h; a template so that the CPU test can fill a struct of the same names)

@@ -15,10 +15,14 @@
 // needs nothing special.  Nothing depends on workgroup order and there are no global atomics: every count is reduced in order.
 // The device control block keeps B per parity: window w reads buffer / B of parity (w - 1) & 1 and writes those of parity w & 1.
 //
-// Vanished dependencies (sg_set_vanished) ride on the same walk: k8_count_v / k8_scan_v / k8_write_v are the three kernels with one
-// more count.  An old entry the walk passes that is not refreshed, has seen min_seen windows and went without a sample for exactly
-// silent windows is counted per thread and per workgroup, scanned, and written at its key-order position; the row behind it (the
-// next row of the walk) is the window's alive-only row with its key, if there is one.  With the list off the plain kernels run.
+// The split, the walk, the scan and the write pass are one template body each (k8_count_t, k8_walk_t, k8_scan_t, k8_write_t),
+// generic over a sample source: K8Edges here (the window's rows), K10Nodes in sg_node_trend.h (two samples per node row).  The
+// count, scan and write kernels of K8 and K10 are one-line wrappers of them.
+//
+// Vanished dependencies (sg_set_vanished) ride on the same walk: k8_count_v / k8_scan_v / k8_write_v are the three bodies with VAN
+// set, one more count.  An old entry the walk passes that is not refreshed, has seen min_seen windows and went without a sample for
+// exactly silent windows is counted per thread and per workgroup, scanned, and written at its key-order position; the row behind it
+// (the next row of the walk) is the window's alive-only row with its key, if there is one.  With the list off the plain kernels run.
 #pragma once
 
 #define K8_THREADS 256            // k8_count / k8_write
@@ -84,13 +88,38 @@ __device__ __forceinline__ K8Row k8_row(const TrendArgs& a, u64 j, u32 nob) {
 }
 __device__ __forceinline__ K8Key k8_entry_key(const TrendSoA& b, u64 i) { K8Key k; k.f = b.from_key[i]; k.t = b.to_key[i]; return k; }
 
+// the per-window samples: exact integers in fp64
+__device__ __forceinline__ double k8_x_lat(const K8Row& r) {
+    u64 m = r.sum / r.count;
+    if (m > (1ull << 52)) m = 1ull << 52;
+    return (double)m;
+}
+__device__ __forceinline__ double k8_x_err(const K8Row& r) { return (double)(((u64)r.err << 20) / r.count); }
+
+// K8's sample source: the window's edge rows, E = ctr[C_N_EDGES] clamped to max_edges, one sg_edge_trend per row.  A source (K10's
+// nodes are the other: sg_node_trend.h) names its kernel argument (Args; the passes take its TrendArgs part beside it) and its
+// sample type, says how many samples the window has (count: given the window's edge counter, which k8_geom loads together with the
+// outbound-IP counter next to it), reads sample j, finds x_lat / x_err of it and stores its trend output.
+struct K8Edges {
+    typedef TrendArgs Args;
+    typedef K8Row Sample;
+    static __device__ __forceinline__ u64 count(const TrendArgs& a, u64 edges) { return edges < a.max_edges ? edges : a.max_edges; }
+    static __device__ __forceinline__ K8Row sample(const TrendArgs& a, u64 j, u32 nob) { return k8_row(a, j, nob); }
+    static __device__ __forceinline__ double x_lat(const K8Row& r) { return k8_x_lat(r); }
+    static __device__ __forceinline__ double x_err(const K8Row& r) { return k8_x_err(r); }
+    static __device__ __forceinline__ void put(const TrendArgs& a, u64 j, float ld, float ed, float base, u32 seen) {
+        sg_edge_trend t; t.lat_dev = ld; t.err_dev = ed; t.base_mean_us = base; t.windows_seen = seen;
+        a.out[j] = t;
+    }
+};
+
 struct K8Geom { u64 B, E; u32 nob; const TrendSoA* old; TrendSoA* nw; u32 par; };
-__device__ __forceinline__ K8Geom k8_geom(const TrendArgs& a) {
+template <class S>
+__device__ __forceinline__ K8Geom k8_geom(const TrendArgs& a, const typename S::Args& sa) {
     K8Geom g;
     g.par = a.w & 1u;
     g.B = a.ctl[K8C_B0 + (g.par ^ 1u)];
-    const u64 E = a.ctr[C_N_EDGES];
-    g.E = E < a.max_edges ? E : a.max_edges;
+    g.E = S::count(sa, a.ctr[C_N_EDGES]);
     const u64 nob = a.ctr[C_N_OBIP];
     g.nob = (u32)(nob < a.max_obip ? nob : a.max_obip);
     g.old = &a.buf[g.par ^ 1u]; g.nw = const_cast<TrendSoA*>(&a.buf[g.par]);
@@ -105,26 +134,19 @@ __device__ __forceinline__ void k8_span(u64 T, u64& d0, u64& d1) {
     if (d1 > T) d1 = T;
 }
 
-// the per-window samples: exact integers in fp64
-__device__ __forceinline__ double k8_x_lat(const K8Row& r) {
-    u64 m = r.sum / r.count;
-    if (m > (1ull << 52)) m = 1ull << 52;
-    return (double)m;
-}
-__device__ __forceinline__ double k8_x_err(const K8Row& r) { return (double)(((u64)r.err << 20) / r.count); }
-
-// The walk of one thread's span, shared by both passes.  WRITE = false: trend rows + counts; true: the merged entries.
-// VAN: also count (and with WRITE write) the vanished entries: van counts them, vb = the position of this thread's first one.
-template <bool WRITE, bool VAN>
-__device__ __forceinline__ void k8_walk_t(const TrendArgs& a, const K8Geom& g, u64 i, u64 j, u64 n, u32& kept, u32& fresh, u32& expired,
-                                        u64 kb, u64 nb, u64 room, const VanArgs& v, u32& van, u64 vb) {
+// The walk of one thread's span over source S's samples, shared by both passes.  WRITE = false: trend rows + counts; true: the
+// merged entries.  VAN (edges only): also count (and with WRITE write) the vanished entries: van counts them, vb = the position of
+// this thread's first one.
+template <class S, bool WRITE, bool VAN>
+__device__ __forceinline__ void k8_walk_t(const TrendArgs& a, const typename S::Args& sa, const K8Geom& g, u64 i, u64 j, u64 n, u32& kept,
+                                          u32& fresh, u32& expired, u64 kb, u64 nb, u64 room, const VanArgs& v, u32& van, u64 vb) {
 #pragma clang fp contract(off)
     const TrendSoA& A = *g.old;
     K8Key ak{}, pk{};                                   // the old entry at i, the one in front of it (i - 1)
-    K8Row r{};
+    typename S::Sample r{};
     if (i < g.B) ak = k8_entry_key(A, i);
     if (i > 0) pk = k8_entry_key(A, i - 1);
-    if (j < g.E) r = k8_row(a, j, g.nob);
+    if (j < g.E) r = S::sample(sa, j, g.nob);
     for (u64 s = 0; s < n; s++) {
         if (i < g.B && (j >= g.E || k8_le(ak, r.k))) {  // an old entry
             const bool upd = j < g.E && r.count > 0 && k8_eq(ak, r.k);
@@ -153,7 +175,7 @@ __device__ __forceinline__ void k8_walk_t(const TrendArgs& a, const K8Geom& g, u
                         double lm = A.lat_mean[i], ld = A.lat_dev[i], em = A.err_mean[i], ed = A.err_dev[i];
                         u32 cnt = A.n[i], ls = last;
                         if (upd) {
-                            const double xl = k8_x_lat(r), xe = k8_x_err(r);
+                            const double xl = S::x_lat(r), xe = S::x_err(r);
                             const double dl = xl - lm, de = xe - em;
                             lm = lm + dl * a.alpha; ld = ld + (fabs(dl) - ld) * a.alpha;
                             em = em + de * a.alpha; ed = ed + (fabs(de) - ed) * a.alpha;
@@ -170,23 +192,23 @@ __device__ __forceinline__ void k8_walk_t(const TrendArgs& a, const K8Geom& g, u
             }
             pk = ak; i++;
             if (i < g.B) ak = k8_entry_key(A, i);
-        } else {                                        // a row
+        } else {                                        // a sample
             const bool match = i > 0 && k8_eq(pk, r.k);
             if (!WRITE) {
-                sg_edge_trend t; t.lat_dev = 0.f; t.err_dev = 0.f; t.base_mean_us = 0.f; t.windows_seen = 0u;
+                float ld = 0.f, ed = 0.f, base = 0.f;
+                u32 seen = 0;
                 if (match) {
                     const u64 q = i - 1;
-                    const u32 seen = A.n[q];
+                    seen = A.n[q];
                     const double lm = A.lat_mean[q];
-                    t.windows_seen = seen;
-                    t.base_mean_us = (float)(lm / 1000.0);
+                    base = (float)(lm / 1000.0);
                     if (r.count > 0 && seen >= a.warmup) {
-                        const double ld = A.lat_dev[q], em = A.err_mean[q], ed = A.err_dev[q];
-                        t.lat_dev = (float)((k8_x_lat(r) - lm) / (ld > a.lat_floor ? ld : a.lat_floor));
-                        t.err_dev = (float)((k8_x_err(r) - em) / (ed > a.err_floor ? ed : a.err_floor));
+                        const double dd = A.lat_dev[q], em = A.err_mean[q], de = A.err_dev[q];
+                        ld = (float)((S::x_lat(r) - lm) / (dd > a.lat_floor ? dd : a.lat_floor));
+                        ed = (float)((S::x_err(r) - em) / (de > a.err_floor ? de : a.err_floor));
                     }
                 }
-                a.out[j] = t;
+                S::put(sa, j, ld, ed, base, seen);
             }
             if (!match && r.count > 0) {
                 if (WRITE && nb < room) {
@@ -194,84 +216,60 @@ __device__ __forceinline__ void k8_walk_t(const TrendArgs& a, const K8Geom& g, u
                     if (p < a.cap) {
                         TrendSoA& o = *g.nw;
                         o.from_key[p] = r.k.f; o.to_key[p] = r.k.t;
-                        o.lat_mean[p] = k8_x_lat(r); o.lat_dev[p] = 0.0; o.err_mean[p] = k8_x_err(r); o.err_dev[p] = 0.0;
+                        o.lat_mean[p] = S::x_lat(r); o.lat_dev[p] = 0.0; o.err_mean[p] = S::x_err(r); o.err_dev[p] = 0.0;
                         o.n[p] = 1u; o.last[p] = a.w;
                     }
                 }
                 nb++; fresh++;
             }
             j++;
-            if (j < g.E) r = k8_row(a, j, g.nob);
+            if (j < g.E) r = S::sample(sa, j, g.nob);
         }
     }
 }
 
-// the plain walk (k8_count / k8_write)
-template <bool WRITE>
-__device__ __forceinline__ void k8_walk(const TrendArgs& a, const K8Geom& g, u64 i, u64 j, u64 n, u32& kept, u32& fresh, u32& expired,
-                                        u64 kb, u64 nb, u64 room) {
-    u32 van = 0;
-    k8_walk_t<WRITE, false>(a, g, i, j, n, kept, fresh, expired, kb, nb, room, VanArgs{}, van, 0);
-}
-
-__global__ __launch_bounds__(K8_THREADS) void k8_count(TrendArgs a) {
-    __shared__ u32 ws[3][K8_THREADS / 64];
+// the count pass (k8_count, k8_count_v, k10_count): the merge-path split, the walk, the per-thread and per-workgroup counts
+template <class S, bool VAN>
+__device__ __forceinline__ void k8_count_t(const TrendArgs& a, const typename S::Args& sa, const VanArgs& v) {
+    __shared__ u32 ws[VAN ? 4 : 3][K8_THREADS / 64];
     const u32 t = threadIdx.x;
-    const K8Geom g = k8_geom(a);
+    const K8Geom g = k8_geom<S>(a, sa);
     const u64 T = g.B + g.E;
     u64 d0, d1; k8_span(T, d0, d1);
     // merge path: how many old entries are among the first d0 merged elements (old first on equal keys)
     u64 lo = d0 > g.E ? d0 - g.E : 0, hi = d0 < g.B ? d0 : g.B;
     while (lo < hi) {
         const u64 mid = (lo + hi) >> 1;
-        if (k8_le(k8_entry_key(*g.old, mid), k8_row(a, d0 - 1 - mid, g.nob).k)) lo = mid + 1; else hi = mid;
-    }
-    u32 kept = 0, fresh = 0, expired = 0;
-    k8_walk<false>(a, g, lo, d0 - lo, d1 - d0, kept, fresh, expired, 0, 0, 0);
-    K8Thread& me = a.th[(size_t)blockIdx.x * K8_THREADS + t];
-    me.i = lo; me.kept = kept; me.fresh = fresh;
-    kept = wave_sum_u32(kept); fresh = wave_sum_u32(fresh); expired = wave_sum_u32(expired);
-    if ((t & 63) == 0) { ws[0][t >> 6] = kept; ws[1][t >> 6] = fresh; ws[2][t >> 6] = expired; }
-    __syncthreads();
-    if (t == 0) {
-        u32 k = 0, f = 0, x = 0;
-        for (int w = 0; w < K8_THREADS / 64; w++) { k += ws[0][w]; f += ws[1][w]; x += ws[2][w]; }
-        a.blk[(size_t)blockIdx.x * 4] = k; a.blk[(size_t)blockIdx.x * 4 + 1] = f; a.blk[(size_t)blockIdx.x * 4 + 2] = x;
-    }
-}
-
-// k8_count with the vanished entries counted per thread and per workgroup
-__global__ __launch_bounds__(K8_THREADS) void k8_count_v(TrendArgs a, VanArgs v) {
-    __shared__ u32 ws[4][K8_THREADS / 64];
-    const u32 t = threadIdx.x;
-    const K8Geom g = k8_geom(a);
-    const u64 T = g.B + g.E;
-    u64 d0, d1; k8_span(T, d0, d1);
-    // merge path: how many old entries are among the first d0 merged elements (old first on equal keys)
-    u64 lo = d0 > g.E ? d0 - g.E : 0, hi = d0 < g.B ? d0 : g.B;
-    while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if (k8_le(k8_entry_key(*g.old, mid), k8_row(a, d0 - 1 - mid, g.nob).k)) lo = mid + 1; else hi = mid;
+        if (k8_le(k8_entry_key(*g.old, mid), S::sample(sa, d0 - 1 - mid, g.nob).k)) lo = mid + 1; else hi = mid;
     }
     u32 kept = 0, fresh = 0, expired = 0, van = 0;
-    k8_walk_t<false, true>(a, g, lo, d0 - lo, d1 - d0, kept, fresh, expired, 0, 0, 0, v, van, 0);
+    k8_walk_t<S, false, VAN>(a, sa, g, lo, d0 - lo, d1 - d0, kept, fresh, expired, 0, 0, 0, v, van, 0);
     K8Thread& me = a.th[(size_t)blockIdx.x * K8_THREADS + t];
     me.i = lo; me.kept = kept; me.fresh = fresh;
-    v.th[(size_t)blockIdx.x * K8_THREADS + t] = van;
-    kept = wave_sum_u32(kept); fresh = wave_sum_u32(fresh); expired = wave_sum_u32(expired); van = wave_sum_u32(van);
-    if ((t & 63) == 0) { ws[0][t >> 6] = kept; ws[1][t >> 6] = fresh; ws[2][t >> 6] = expired; ws[3][t >> 6] = van; }
+    if constexpr (VAN) v.th[(size_t)blockIdx.x * K8_THREADS + t] = van;
+    kept = wave_sum_u32(kept); fresh = wave_sum_u32(fresh); expired = wave_sum_u32(expired);
+    if constexpr (VAN) van = wave_sum_u32(van);
+    if ((t & 63) == 0) {
+        ws[0][t >> 6] = kept; ws[1][t >> 6] = fresh; ws[2][t >> 6] = expired;
+        if constexpr (VAN) ws[3][t >> 6] = van;
+    }
     __syncthreads();
     if (t == 0) {
         u32 k = 0, f = 0, x = 0, y = 0;
-        for (int w = 0; w < K8_THREADS / 64; w++) { k += ws[0][w]; f += ws[1][w]; x += ws[2][w]; y += ws[3][w]; }
+        for (int w = 0; w < K8_THREADS / 64; w++) {
+            k += ws[0][w]; f += ws[1][w]; x += ws[2][w];
+            if constexpr (VAN) y += ws[3][w];
+        }
         a.blk[(size_t)blockIdx.x * 4] = k; a.blk[(size_t)blockIdx.x * 4 + 1] = f; a.blk[(size_t)blockIdx.x * 4 + 2] = x;
-        v.blk[blockIdx.x] = y;
+        if constexpr (VAN) v.blk[blockIdx.x] = y;
     }
 }
 
-// one workgroup: exclusive scans of the per-workgroup counts, the capacity cut (the kept old entries never exceed max_entries: the
-// first max_entries - kept new ones in key order go in), the new B and the running statistics
-__global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan(TrendArgs a, u32 nwg) {
+// the scan (k8_scan, k8_scan_v; one workgroup): exclusive scans of the per-workgroup counts, the capacity cut (the kept old entries
+// never exceed max_entries: the first max_entries - kept new ones in key order go in), the new B and the running statistics; VAN:
+// the vanished counts scanned too, their per-workgroup base and the window's count
+template <bool VAN>
+__device__ __forceinline__ void k8_scan_t(const TrendArgs& a, u32 nwg, const VanArgs& v) {
     __shared__ u32 wsum[K8_SCAN_THREADS / 64 + 1];
     const u32 t = threadIdx.x;
     const u32 k = t < nwg ? a.blk[(size_t)t * 4] : 0u, f = t < nwg ? a.blk[(size_t)t * 4 + 1] : 0u, x = t < nwg ? a.blk[(size_t)t * 4 + 2] : 0u;
@@ -280,29 +278,7 @@ __global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan(TrendArgs a, u32 nwg)
     const u32 fb = block_excl_scan<K8_SCAN_THREADS>(f, wsum, &ftot);
     block_excl_scan<K8_SCAN_THREADS>(x, wsum, &xtot);
     if (t < nwg) { a.blk[(size_t)t * 4 + 2] = kb; a.blk[(size_t)t * 4 + 3] = fb; }
-    if (t == 0) {
-        const u64 room = a.cap > ktot ? a.cap - ktot : 0ull;
-        const u64 ins = ftot < room ? ftot : room;
-        a.ctl[K8C_ROOM] = room;
-        a.ctl[K8C_B0 + (a.w & 1u)] = ktot + ins;
-        a.ctl[K8C_WINDOWS] += 1;
-        a.ctl[K8C_INSERTED] += ins;
-        a.ctl[K8C_EXPIRED] += xtot;
-        a.ctl[K8C_DROPPED] += ftot - ins;
-    }
-}
-
-// k8_scan with the vanished counts scanned too: their per-workgroup base and the window's count
-__global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan_v(TrendArgs a, u32 nwg, VanArgs v) {
-    __shared__ u32 wsum[K8_SCAN_THREADS / 64 + 1];
-    const u32 t = threadIdx.x;
-    const u32 k = t < nwg ? a.blk[(size_t)t * 4] : 0u, f = t < nwg ? a.blk[(size_t)t * 4 + 1] : 0u, x = t < nwg ? a.blk[(size_t)t * 4 + 2] : 0u;
-    u32 ktot, ftot, xtot;
-    const u32 kb = block_excl_scan<K8_SCAN_THREADS>(k, wsum, &ktot);
-    const u32 fb = block_excl_scan<K8_SCAN_THREADS>(f, wsum, &ftot);
-    block_excl_scan<K8_SCAN_THREADS>(x, wsum, &xtot);
-    if (t < nwg) { a.blk[(size_t)t * 4 + 2] = kb; a.blk[(size_t)t * 4 + 3] = fb; }
-    {
+    if constexpr (VAN) {
         u32 vtot;
         const u32 y = t < nwg ? v.blk[t] : 0u;
         const u32 yb = block_excl_scan<K8_SCAN_THREADS>(y, wsum, &vtot);
@@ -321,10 +297,13 @@ __global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan_v(TrendArgs a, u32 nw
     }
 }
 
-__global__ __launch_bounds__(K8_THREADS) void k8_write(TrendArgs a) {
+// the write pass (k8_write, k8_write_v, k10_write): the walk again from the count pass's split, at the scanned positions; VAN: each
+// vanished entry written at its key-order position
+template <class S, bool VAN>
+__device__ __forceinline__ void k8_write_t(const TrendArgs& a, const typename S::Args& sa, const VanArgs& v) {
     __shared__ u32 wsum[K8_THREADS / 64 + 1];
     const u32 t = threadIdx.x;
-    const K8Geom g = k8_geom(a);
+    const K8Geom g = k8_geom<S>(a, sa);
     const u64 T = g.B + g.E;
     u64 d0, d1; k8_span(T, d0, d1);
     const K8Thread me = a.th[(size_t)blockIdx.x * K8_THREADS + t];
@@ -332,26 +311,18 @@ __global__ __launch_bounds__(K8_THREADS) void k8_write(TrendArgs a) {
     const u32 kx = block_excl_scan<K8_THREADS>(me.kept, wsum, &tot);
     const u32 fx = block_excl_scan<K8_THREADS>(me.fresh, wsum, &tot);
     const u64 kb = (u64)a.blk[(size_t)blockIdx.x * 4 + 2] + kx, nb = (u64)a.blk[(size_t)blockIdx.x * 4 + 3] + fx;
-    u32 kept = 0, fresh = 0, expired = 0;
-    k8_walk<true>(a, g, me.i, d0 - me.i, d1 - d0, kept, fresh, expired, kb, nb, a.ctl[K8C_ROOM]);
+    u64 vb = 0;
+    if constexpr (VAN) vb = (u64)v.blk[blockIdx.x] + block_excl_scan<K8_THREADS>(v.th[(size_t)blockIdx.x * K8_THREADS + t], wsum, &tot);
+    u32 kept = 0, fresh = 0, expired = 0, van = 0;
+    k8_walk_t<S, true, VAN>(a, sa, g, me.i, d0 - me.i, d1 - d0, kept, fresh, expired, kb, nb, a.ctl[K8C_ROOM], v, van, vb);
 }
 
-// k8_write with each vanished entry written at its key-order position
-__global__ __launch_bounds__(K8_THREADS) void k8_write_v(TrendArgs a, VanArgs v) {
-    __shared__ u32 wsum[K8_THREADS / 64 + 1];
-    const u32 t = threadIdx.x;
-    const K8Geom g = k8_geom(a);
-    const u64 T = g.B + g.E;
-    u64 d0, d1; k8_span(T, d0, d1);
-    const K8Thread me = a.th[(size_t)blockIdx.x * K8_THREADS + t];
-    u32 tot;
-    const u32 kx = block_excl_scan<K8_THREADS>(me.kept, wsum, &tot);
-    const u32 fx = block_excl_scan<K8_THREADS>(me.fresh, wsum, &tot);
-    const u64 kb = (u64)a.blk[(size_t)blockIdx.x * 4 + 2] + kx, nb = (u64)a.blk[(size_t)blockIdx.x * 4 + 3] + fx;
-    const u64 vb = (u64)v.blk[blockIdx.x] + block_excl_scan<K8_THREADS>(v.th[(size_t)blockIdx.x * K8_THREADS + t], wsum, &tot);
-    u32 kept = 0, fresh = 0, expired = 0, van = 0;
-    k8_walk_t<true, true>(a, g, me.i, d0 - me.i, d1 - d0, kept, fresh, expired, kb, nb, a.ctl[K8C_ROOM], v, van, vb);
-}
+__global__ __launch_bounds__(K8_THREADS) void k8_count(TrendArgs a) { k8_count_t<K8Edges, false>(a, a, VanArgs{}); }
+__global__ __launch_bounds__(K8_THREADS) void k8_count_v(TrendArgs a, VanArgs v) { k8_count_t<K8Edges, true>(a, a, v); }
+__global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan(TrendArgs a, u32 nwg) { k8_scan_t<false>(a, nwg, VanArgs{}); }
+__global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan_v(TrendArgs a, u32 nwg, VanArgs v) { k8_scan_t<true>(a, nwg, v); }
+__global__ __launch_bounds__(K8_THREADS) void k8_write(TrendArgs a) { k8_write_t<K8Edges, false>(a, a, VanArgs{}); }
+__global__ __launch_bounds__(K8_THREADS) void k8_write_v(TrendArgs a, VanArgs v) { k8_write_t<K8Edges, true>(a, a, v); }
 
 // sg_window_trend with an index: the asked-for rows gathered on the device, so that only they cross PCIe
 __global__ __launch_bounds__(256) void k8_gather(const sg_edge_trend* src, const u32* idx, u64 n, sg_edge_trend* dst) {

@@ -449,34 +449,44 @@ class ServiceGraph:
     def set_trend(self, params: Optional[dict] = (), **kw):
         """Switch the per-edge baseline on (sg_set_trend; shift, warmup, ttl, max_entries, lat_floor_ns, err_floor as keywords or a
         dict — see TREND_DEFAULTS; set_trend() = every default; (re)enabling starts an empty baseline) or off: set_trend(None)."""
+        v = self._set_baseline(self._l.sg_set_trend, params, kw, "set_trend(None) switches the trend off", "trend")
+        if v is not None:
+            self._trend_entries = v["max_entries"] or min(1 << 31, 2 * max(self.max_edges, 1))   # the baseline's capacity
+
+    def _set_baseline(self, call, params, kw, off_text: str, what: str):
+        """set_trend / set_node_trend: call(h, NULL) for params None, else call(h, sg_trend_params) and the parameters"""
         if params is None:
             if kw:
-                raise TypeError("set_trend(None) switches the trend off and takes no parameters")
-            self._ck(self._l.sg_set_trend(self._h, None))
-            return
+                raise TypeError(f"{off_text} and takes no parameters")
+            self._ck(call(self._h, None))
+            return None
         v = dict(TREND_DEFAULTS)
         v.update(params or {}); v.update(kw)
         unknown = set(v) - set(TREND_DEFAULTS) - {"struct_size", "reserved"}
         if unknown:
-            raise TypeError(f"unknown trend parameters: {sorted(unknown)}")
+            raise TypeError(f"unknown {what} parameters: {sorted(unknown)}")
         p = SgTrendParams(v.get("struct_size", C.sizeof(SgTrendParams)), v["shift"], v["warmup"], v["ttl"], v["max_entries"],
                           v["lat_floor_ns"], v["err_floor"], v.get("reserved", 0))
-        self._ck(self._l.sg_set_trend(self._h, C.byref(p)))
-        self._trend_entries = v["max_entries"] or min(1 << 31, 2 * max(self.max_edges, 1))   # the baseline's capacity
+        self._ck(call(self._h, C.byref(p)))
+        return v
 
     def window_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
         """TREND_DTYPE rows of the last read window (sg_window_trend): every row, or the rows at `index` (only those cross PCIe)."""
+        return self._window_rows(self._l.sg_window_trend, TREND_DTYPE, index)
+
+    def _window_rows(self, call, dtype, index):
+        """window_trend / window_node_trend: every row of the last read window (two calls: the count, the rows), or those at index"""
         n = C.c_size_t(0)
         if index is None:
-            self._ck(self._l.sg_window_trend(self._h, None, 0, None, 0, C.byref(n)))
-            out = np.zeros(n.value, dtype=TREND_DTYPE)
+            self._ck(call(self._h, None, 0, None, 0, C.byref(n)))
+            out = np.zeros(n.value, dtype=dtype)
             if n.value:
-                self._ck(self._l.sg_window_trend(self._h, None, 0, out.ctypes.data, n.value, C.byref(n)))
+                self._ck(call(self._h, None, 0, out.ctypes.data, n.value, C.byref(n)))
             return out
         idx = np.ascontiguousarray(index, dtype=np.uint32)
-        out = np.zeros(len(idx), dtype=TREND_DTYPE)
+        out = np.zeros(len(idx), dtype=dtype)
         if len(idx):
-            self._ck(self._l.sg_window_trend(self._h, idx.ctypes.data, len(idx), out.ctypes.data, len(idx), C.byref(n)))
+            self._ck(call(self._h, idx.ctypes.data, len(idx), out.ctypes.data, len(idx), C.byref(n)))
         return out
 
     def trend_buffer(self) -> int:
@@ -487,16 +497,23 @@ class ServiceGraph:
 
     def trend_entries(self) -> np.ndarray:
         """the baseline in key order, TREND_ENTRY_DTYPE (sg_trend_entries)"""
+        return self._entries(self._l.sg_trend_entries)
+
+    def _entries(self, call) -> np.ndarray:
+        """trend_entries / node_trend_entries: the count, then the entries"""
         n = C.c_size_t(0)
-        self._ck(self._l.sg_trend_entries(self._h, None, 0, C.byref(n)))
+        self._ck(call(self._h, None, 0, C.byref(n)))
         out = np.zeros(n.value, dtype=TREND_ENTRY_DTYPE)
         if n.value:
-            self._ck(self._l.sg_trend_entries(self._h, out.ctypes.data, n.value, C.byref(n)))
+            self._ck(call(self._h, out.ctypes.data, n.value, C.byref(n)))
         return out[: n.value]
 
     def trend_stats(self) -> SgTrendStats:
+        return self._stats(self._l.sg_trend_stats_get)
+
+    def _stats(self, call) -> SgTrendStats:
         s = SgTrendStats()
-        self._ck(self._l.sg_trend_stats_get(self._h, C.byref(s)))
+        self._ck(call(self._h, C.byref(s)))
         return s
 
     def set_vanished(self, params: Optional[dict] = (), **kw):
@@ -559,35 +576,12 @@ class ServiceGraph:
     def set_node_trend(self, params: Optional[dict] = (), **kw):
         """Switch the per-node baseline on (sg_set_node_trend; the parameters of set_trend, max_entries 0 = 4 x the node capacity;
         needs the node rollup on; (re)enabling starts an empty baseline) or off: set_node_trend(None)."""
-        if params is None:
-            if kw:
-                raise TypeError("set_node_trend(None) switches the node trend off and takes no parameters")
-            self._ck(self._l.sg_set_node_trend(self._h, None))
-            return
-        v = dict(TREND_DEFAULTS)
-        v.update(params or {}); v.update(kw)
-        unknown = set(v) - set(TREND_DEFAULTS) - {"struct_size", "reserved"}
-        if unknown:
-            raise TypeError(f"unknown node trend parameters: {sorted(unknown)}")
-        p = SgTrendParams(v.get("struct_size", C.sizeof(SgTrendParams)), v["shift"], v["warmup"], v["ttl"], v["max_entries"],
-                          v["lat_floor_ns"], v["err_floor"], v.get("reserved", 0))
-        self._ck(self._l.sg_set_node_trend(self._h, C.byref(p)))
+        self._set_baseline(self._l.sg_set_node_trend, params, kw, "set_node_trend(None) switches the node trend off", "node trend")
 
     def window_node_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
         """NODE_TREND_DTYPE rows of the last read window (sg_window_node_trend), row k for node row k of window_nodes(); or the rows
         of the nodes at `index` (window_nodes_top's indices; only those cross PCIe)."""
-        n = C.c_size_t(0)
-        if index is None:
-            self._ck(self._l.sg_window_node_trend(self._h, None, 0, None, 0, C.byref(n)))
-            out = np.zeros(n.value, dtype=NODE_TREND_DTYPE)
-            if n.value:
-                self._ck(self._l.sg_window_node_trend(self._h, None, 0, out.ctypes.data, n.value, C.byref(n)))
-            return out
-        idx = np.ascontiguousarray(index, dtype=np.uint32)
-        out = np.zeros(len(idx), dtype=NODE_TREND_DTYPE)
-        if len(idx):
-            self._ck(self._l.sg_window_node_trend(self._h, idx.ctypes.data, len(idx), out.ctypes.data, len(idx), C.byref(n)))
-        return out
+        return self._window_rows(self._l.sg_window_node_trend, NODE_TREND_DTYPE, index)
 
     def node_trend_buffer(self) -> int:
         """device pointer of the sg_node_trend rows of the window window_run closed last (sg_window_node_trend_buffer)"""
@@ -597,17 +591,10 @@ class ServiceGraph:
 
     def node_trend_entries(self) -> np.ndarray:
         """the node baseline in key order, TREND_ENTRY_DTYPE with to_key = side (0 in, 1 out) (sg_node_trend_entries)"""
-        n = C.c_size_t(0)
-        self._ck(self._l.sg_node_trend_entries(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=TREND_ENTRY_DTYPE)
-        if n.value:
-            self._ck(self._l.sg_node_trend_entries(self._h, out.ctypes.data, n.value, C.byref(n)))
-        return out[: n.value]
+        return self._entries(self._l.sg_node_trend_entries)
 
     def node_trend_stats(self) -> SgTrendStats:
-        s = SgTrendStats()
-        self._ck(self._l.sg_node_trend_stats_get(self._h, C.byref(s)))
-        return s
+        return self._stats(self._l.sg_node_trend_stats_get)
 
     @staticmethod
     def _nby(by) -> int:
