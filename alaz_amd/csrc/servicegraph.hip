@@ -41,6 +41,15 @@ struct TimingRec { hipEvent_t a, b; int kernel; };
 using sgplan::next_pow2;
 using sgplan::grid_for;
 
+// the kernel families that come in several instantiations (the kernel tables below), by signature
+typedef void (*K1aFn)(Dev, const sg_event*, u64);
+typedef void (*K1bFn)(Dev);
+typedef void (*K2RowptrFn)(Dev, u32);
+typedef void (*K4GatherFn)(Dev, const float*);
+typedef void (*K4LayerFn)(Dev, const float*, float*, const float*, const float*);
+typedef void (*K5ProjFn)(Dev, const float*, const float*);
+typedef void (*K5ScoreFn)(Dev, const float*);
+
 }  // namespace
 
 struct sg_engine {
@@ -54,6 +63,12 @@ struct sg_engine {
     sgplan::Overrides ov;
     sgplan::Plan plan;
     sgplan::PassA pa;
+    // the kernel instantiations the plan chose (sg_plan.hpp choose_kernels) and their pointers out of the kernel tables below: resolved at
+    // create, pass A's again whenever it is re-planned.  k1b is the cold (or, on a warm engine, the plain) pass B, k1b_try / k1b_cold a
+    // warm engine's two; K4's layer by [layer > 0][projection].
+    sgplan::Kernels kn;
+    struct Fns { K1aFn k1a = nullptr; K1bFn k1b = nullptr, k1b_try = nullptr, k1b_cold = nullptr; K2RowptrFn k2_rowptr = nullptr;
+                 K4LayerFn k4_layer[2][2] = {}; K5ProjFn k5_proj = nullptr; } fn;
     std::vector<void*> allocs;
     char* arena_base = nullptr; size_t arena_left = 0;         // SG_ARENA (Plan::arena_on): the chunk small arrays are carved from
 
@@ -208,6 +223,81 @@ struct Timed {
     ~Timed() { if (on) { hipEventRecord(r.b, s); e->trecs.push_back(r); } }
 };
 
+// ---- kernel tables ------------------------------------------------------------------------------------------------------------------
+// One table per kernel family that comes in several instantiations: the family's keys (sg_plan.hpp, one per instantiation the library
+// holds) expanded into kernel pointers, so that every instantiation is named once, here.  kernel_of finds the plan's choice in it,
+// lds_limit_all walks it.  Both run at create (pass A's lookup again when the join tables re-plan it), never on the window path.
+static_assert(sgplan::kK1bWarmU == K1B_WARM_U, "sg_plan.hpp's copy of pass B's warm U");
+constexpr int k4_threads(int fi, bool proj, bool split) { return split ? (proj ? 512 : 256) : (fi == 32 ? 1024 : 512); }
+template <class FnT, const auto& Keys> struct Family { typedef FnT Fn; static constexpr auto& keys = Keys; };
+struct K1aWide : Family<K1aFn, sgplan::kK1aWideKeys> { template <size_t I> static Fn at() { constexpr auto k = keys[I]; return k1a_partition<(bool)k[0], (bool)k[1], (bool)k[2]>; } };
+struct K1aTile : Family<K1aFn, sgplan::kK1aTileKeys> { template <size_t I> static Fn at() { constexpr auto k = keys[I]; return k1a_tile_partition<k[0], (bool)k[1], k[2]>; } };
+struct K1aTeam : Family<K1aFn, sgplan::kK1aTeamKeys> { template <size_t I> static Fn at() { constexpr auto k = keys[I]; return k1a_team_partition<k[0], (bool)k[1], 2, 1024, k[2]>; } };
+struct K1bMerge : Family<K1bFn, sgplan::kK1bMergeKeys> { template <size_t I> static Fn at() {
+    constexpr auto k = keys[I]; if constexpr (k[2]) return k1b_merge<k[0], (bool)k[1]>; else return k1b_merge_wide<k[0], (bool)k[1]>; } };
+struct K1bStream : Family<K1bFn, sgplan::kK1bStreamKeys> { template <size_t I> static Fn at() {
+    constexpr auto k = keys[I]; if constexpr (k[4]) return k1b_stream_merge<k[0], k[1], (bool)k[2], k[3]>; else return k1b_stream_merge_wide<k[0], k[1], (bool)k[2], k[3]>; } };
+struct K4Layer : Family<K4LayerFn, sgplan::kK4LayerKeys> { template <size_t I> static Fn at() {
+    constexpr auto k = keys[I]; return k4_sage_layer<k[0], (bool)k[1], (bool)k[2], k4_threads(k[0], k[2], k[3]), (bool)k[3]>; } };
+// (the pairs need no keys: indexed by the one boolean or the layer's input width)
+constexpr K2RowptrFn kK2Rowptr[2] = {k2_rowptr<K2_RP_ROWS, false>, k2_rowptr<K2_RP_ROWS_DH, true>};    // [over the degree histograms]
+constexpr K4GatherFn kK4Gather[2] = {k4_gather<32>, k4_gather<64>};                                    // [layer > 0]
+constexpr K5ProjFn kK5Proj[2] = {k5_node_proj<false>, k5_node_proj<true>};                             // [MFMA]
+constexpr K5ScoreFn kK5Score[2] = {k5_edge_score<false>, k5_edge_score<true>};                         // [fused reset]
+template <class F, size_t... I>
+const std::array<typename F::Fn, sizeof...(I)>& kernel_table(std::index_sequence<I...>) {
+    static const std::array<typename F::Fn, sizeof...(I)> t{{F::template at<I>()...}};
+    return t;
+}
+template <class F> const auto& kernel_table() { return kernel_table<F>(std::make_index_sequence<F::keys.size()>{}); }
+// the family's kernel for these template arguments; when the library holds none, nullptr and ok = false
+template <class F, class... A>
+typename F::Fn kernel_of(bool& ok, A... args) {
+    const int i = sgplan::find_key(F::keys, sgplan::Key<sizeof...(A)>{{(int)args...}});
+    if (i < 0) ok = false;
+    return i < 0 ? nullptr : kernel_table<F>()[i];
+}
+// the largest dynamic LDS a launch of these kernels may ask for (a process-wide attribute of each kernel)
+template <class... K>
+hipError_t lds_limit(size_t bytes, K... kernels) {
+    for (const void* f : {reinterpret_cast<const void*>(kernels)...}) {
+        const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (r != hipSuccess) return r;
+    }
+    return hipSuccess;
+}
+template <class F>
+hipError_t lds_limit_all(size_t bytes) { hipError_t r = hipSuccess; for (const auto f : kernel_table<F>()) if (r == hipSuccess) r = lds_limit(bytes, f); return r; }
+
+// Pass A's geometry and kernel for the join tables as they are now (sg_create, sync_tables).  When the tables leave no legal geometry,
+// or the library no kernel for it, the engine keeps what it had and the call fails with a message.
+int plan_pass_a(sg_engine* e) {
+    sgplan::PassA pa = e->pa;
+    if (!sgplan::plan_pass_a(e->plan, e->jt.l1_entries, e->jt.blocks_bytes(), e->ov, &pa)) { e->err = "K1 pass A: the join tables' level 1 and the piece counters do not fit a CU's LDS (fewer partitions / IP blocks needed)"; return SG_ENOSPC; }
+    const sgplan::PassAKernel k = sgplan::choose_pass_a(e->plan, pa, e->cfg);
+    bool ok = true;
+    const K1aFn f = k.family == sgplan::K1A_TEAM ? kernel_of<K1aTeam>(ok, k.l2, k.sharded, k.pb)
+                  : k.family == sgplan::K1A_TILE ? kernel_of<K1aTile>(ok, k.l2, k.sharded, k.nsub) : kernel_of<K1aWide>(ok, k.l2, k.sharded, k.hist);
+    if (!ok) { e->err = "K1 pass A: the library holds no kernel for family " + std::to_string(k.family) + ", level 2 mode " + std::to_string(k.l2); return SG_ENODEV; }
+    e->pa = pa; e->kn.k1a = k; e->fn.k1a = f;
+    return SG_OK;
+}
+// every other family's choice (e->kn) to kernel pointers: once, at create
+int resolve_kernels(sg_engine* e) {
+    const sgplan::Kernels& k = e->kn;
+    sg_engine::Fns& f = e->fn;
+    bool ok = true;
+    if (k.k1b_family == sgplan::K1B_STREAM) {
+        f.k1b = kernel_of<K1bStream>(ok, k.k1b_u, k.k1b_spt, k.k1b_pack, 0, k.k1b_share);
+        if (k.k1b_warm) f.k1b_try = kernel_of<K1bStream>(ok, sgplan::kK1bWarmU, k.k1b_spt, k.k1b_pack, 1, k.k1b_share);
+        if (k.k1b_warm) f.k1b_cold = kernel_of<K1bStream>(ok, sgplan::kK1bWarmU, k.k1b_spt, k.k1b_pack, 2, k.k1b_share);
+    } else if (k.k1b_family == sgplan::K1B_MERGE) f.k1b = kernel_of<K1bMerge>(ok, k.k1b_u, k.k1b_hist, k.k1b_share);
+    f.k2_rowptr = kK2Rowptr[k.k2_dh]; f.k5_proj = kK5Proj[k.k5_mfma];
+    for (int w = 0; w < 2; w++) for (int pj = 0; pj < 2; pj++) f.k4_layer[w][pj] = kernel_of<K4Layer>(ok, w ? 64 : 32, k.k4_mfma, pj, k.k4_split);
+    if (!ok) { e->err = "the library holds no kernel for one of the plan's choices (sg_plan.hpp choose_kernels)"; return SG_ENODEV; }
+    return SG_OK;
+}
+
 // ---- join tables on the device: the host mirror's changes since the last launch, in stream order ------------------
 // (processPod / processSvc analogue: aggregator/persist.go:55-71, 114-130 — one map write there, a few words here)
 
@@ -253,8 +343,7 @@ int sync_tables(sg_engine* e, hipStream_t s) {
     }
     HIP_TRY(e, hipEventRecord(e->tab_ev, s));
     e->tab_seq++; e->tab_stream = s;
-    if (e->d.variant == 0 && !sgplan::plan_pass_a(e->plan, e->jt.l1_entries, e->jt.blocks_bytes(), e->ov, &e->pa)) { e->err = "K1 pass A: the join tables' level 1 and the piece counters do not fit a CU's LDS (fewer partitions / IP blocks needed)"; return SG_ENOSPC; }
-    return SG_OK;
+    return e->d.variant == 0 ? plan_pass_a(e) : SG_OK;
 }
 // K1 on stream s reads the tables: after the last modification if that ran on another stream
 int order_after_tables(sg_engine* e, hipStream_t s) {
@@ -304,14 +393,6 @@ int launch_k1(sg_engine* e, const sg_event* d_ev, size_t n, hipStream_t s) {
         const bool tk = ((e->timing >> 1) & 1u) && e->closes % e->timing_stride == 0;   // (the window this batch belongs to is the closes-th)
         hipEvent_t ta = tk ? get_event(e) : nullptr, tb = tk ? get_event(e) : nullptr;
         da.batch_state = e->window_events_in == 0 ? 1u : 0u;     // first batch of this window?
-        const bool sh = e->d.world > 1;
-#define K1A_GO(L2, SH, HI) hipExtLaunchKernelGGL((k1a_partition<L2, SH, HI>), dim3(e->d.nwg), dim3(K1A_THREADS), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n)
-#define K1A_GO2(L2, SH) do { if (e->d.hist) K1A_GO(L2, SH, true); else K1A_GO(L2, SH, false); } while (0)
-#define K1T_GO(L2, SH, NS) hipExtLaunchKernelGGL((k1a_tile_partition<L2, SH, NS>), dim3(e->d.nwg), dim3(K1T_THREADS), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n)
-#define K1T_GO2(L2, SH) do { if (e->pa.k1a_nsub == 2) K1T_GO(L2, SH, 2); else K1T_GO(L2, SH, 1); } while (0)
-#define K1M_GO(L2, SH) do { if (e->d.np == 256) hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 8>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); \
-                            else if (e->d.np == 512) hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 9>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); \
-                            else hipExtLaunchKernelGGL((k1a_team_partition<L2, SH, 2, 1024, 10>), dim3(e->d.nwg), dim3(1024), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n); } while (0)
         da.k1a_rot = e->d.k1a_rot;
         rot0 = e->d.k1a_rot; tb0 = e->d.k1a_ticket_base;           // (restored below when the launch is refused: the device counter only moves if the kernel runs)
         if (e->d.narrow && !e->pa.k1a_team) {                           // the next launch's first chunk goes to the workgroup behind this launch's last one
@@ -325,22 +406,9 @@ int launch_k1(sg_engine* e, const sg_event* d_ev, size_t n, hipStream_t s) {
                 const unsigned long long nt_ = k1m_tiles(n, e->d.nwg, e->pa.k1a_teams, e->pa.k1a_nt), units_ = (unsigned long long)e->pa.k1a_teams * e->d.nwg;
                 if (!(e->d.ablate & 0x4u)) e->d.k1a_ticket_base += (u32)((nt_ > units_ ? nt_ - units_ : 0) + std::min(units_, nt_));
             }
-            if (e->pa.l2_in_lds && e->pa.l2_u16) { if (sh) K1M_GO(2, true); else K1M_GO(2, false); }
-            else if (e->pa.l2_in_lds) { if (sh) K1M_GO(1, true); else K1M_GO(1, false); }
-            else { if (sh) K1M_GO(0, true); else K1M_GO(0, false); }
         }
-        else if (e->d.narrow) {
-            if (e->pa.l2_in_lds && e->pa.l2_u16) { if (sh) K1T_GO2(2, true); else K1T_GO2(2, false); }
-            else if (e->pa.l2_in_lds) { if (sh) K1T_GO2(1, true); else K1T_GO2(1, false); }
-            else { if (sh) K1T_GO2(0, true); else K1T_GO2(0, false); }
-        }
-        else if (e->pa.l2_in_lds) { if (sh) K1A_GO2(true, true); else K1A_GO2(true, false); }
-        else { if (sh) K1A_GO2(false, true); else K1A_GO2(false, false); }
-#undef K1M_GO
-#undef K1T_GO2
-#undef K1T_GO
-#undef K1A_GO2
-#undef K1A_GO
+        const u32 threads = !e->d.narrow ? K1A_THREADS : e->pa.k1a_team ? 1024 : K1T_THREADS;
+        hipExtLaunchKernelGGL(e->fn.k1a, dim3(e->d.nwg), dim3(threads), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n);
         if (tk) { TimingRec r; r.a = ta; r.b = tb; r.kernel = 1; e->trecs.push_back(r); }
     } else {
         Timed t(e, s, 1);
@@ -439,37 +507,15 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
         hipEvent_t ta = tk ? get_event(e) : nullptr, tb = tk ? get_event(e) : nullptr;
         Dev db = d; db.batch_state = e->window_events_in == 0 ? 2u : 0u;          // a window without any batch: nothing to merge
         db.kept_compact = d.warm;                                                 // (a warm engine's pass B builds / feeds the kept state: compact node ids, sg_kernels.h sg_kept_compact)
-        const bool share = d.npb > e->plan.cus && 2 * e->plan.k1b_lds <= kLdsBytes;   // several partitions per CU and room for two tables: the SGPR-capped build lets two workgroups share a CU
         // warm engines: the warm attempt (WM 1: seeded tables, accumulators straight to their kept positions; returns at once when
         // kc_prepare has already called the window cold), then the cold merge (WM 2: returns at once on a warm window).  Both are records
-        // of group 7: a window's pass B is the SUM of its group-7 records.
-#define K1B8W_GOP(U_, SPT_, P_, WM_) do { if (share) hipExtLaunchKernelGGL((k1b_stream_merge<U_, SPT_, P_, WM_>), dim3(d.npb), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); \
-                                     else hipExtLaunchKernelGGL((k1b_stream_merge_wide<U_, SPT_, P_, WM_>), dim3(d.npb), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); } while (0)
-#define K1B8W_GO(SPT_, WM_) do { if (e->plan.k1b_pack) K1B8W_GOP(K1B_WARM_U, SPT_, true, WM_); else K1B8W_GOP(K1B_WARM_U, SPT_, false, WM_); } while (0)
-#define K1B8W_GO2(WM_) do { const u32 spt = d.k1b_ht / e->plan.k1b_threads; if (spt >= 4) K1B8W_GO(4, WM_); else if (spt == 2) K1B8W_GO(2, WM_); else K1B8W_GO(1, WM_); } while (0)
-        if (d.warm) {
-            if (warm_try) {
-                K1B8W_GO2(1);
-                if (tk) { TimingRec r; r.a = ta; r.b = tb; r.kernel = 7; e->trecs.push_back(r); ta = get_event(e); tb = get_event(e); }
-            }
-            K1B8W_GO2(2);
-        } else {
-#define K1B_GO(U_, H_) do { if (share) hipExtLaunchKernelGGL((k1b_merge<U_, H_>), dim3(d.np), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); \
-                            else hipExtLaunchKernelGGL((k1b_merge_wide<U_, H_>), dim3(d.np), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); } while (0)
-#define K1B8_GOP(U_, SPT_, P_) do { if (share) hipExtLaunchKernelGGL((k1b_stream_merge<U_, SPT_, P_>), dim3(d.npb), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); \
-                               else hipExtLaunchKernelGGL((k1b_stream_merge_wide<U_, SPT_, P_>), dim3(d.npb), dim3(e->plan.k1b_threads), (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db); } while (0)
-#define K1B8_GO(U_, SPT_) do { if (e->plan.k1b_pack) K1B8_GOP(U_, SPT_, true); else K1B8_GOP(U_, SPT_, false); } while (0)
-#define K1B8_GO2(U_) do { const u32 spt = d.k1b_ht / e->plan.k1b_threads; if (spt >= 4) K1B8_GO(U_, 4); else if (spt == 2) K1B8_GO(U_, 2); else K1B8_GO(U_, 1); } while (0)
-        if (d.narrow) { if (e->plan.k1b_u == 8) K1B8_GO2(8); else K1B8_GO2(4); }
-        else if (d.hist) K1B_GO(4, true); else if (e->plan.k1b_u == 8) K1B_GO(8, false); else K1B_GO(4, false);
+        // of group 7: a window's pass B is the SUM of its group-7 records.  (A window such an engine closes the plain way takes k1b.)
+        const dim3 grid(d.narrow ? d.npb : d.np), block(e->plan.k1b_threads);
+        if (d.warm && warm_try) {
+            hipExtLaunchKernelGGL(e->fn.k1b_try, grid, block, (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db);
+            if (tk) { TimingRec r; r.a = ta; r.b = tb; r.kernel = 7; e->trecs.push_back(r); ta = get_event(e); tb = get_event(e); }
         }
-#undef K1B8_GO2
-#undef K1B8_GO
-#undef K1B8_GOP
-#undef K1B_GO
-#undef K1B8W_GO2
-#undef K1B8W_GO
-#undef K1B8W_GOP
+        hipExtLaunchKernelGGL(d.warm ? e->fn.k1b_cold : e->fn.k1b, grid, block, (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db);
         if (tk) { TimingRec r; r.a = ta; r.b = tb; r.kernel = 7; e->trecs.push_back(r); }
     }
     {
@@ -491,8 +537,8 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
             hipLaunchKernelGGL(k2_edge_compact, dim3(ntiles), dim3(256), 0, s, d);
         }
         if (d.dh_g) hipLaunchKernelGGL(k2_deg_hist, dim3(d.dh_g), dim3(K2_DH_THREADS), ((size_t)d.ncap + 1) * sizeof(u32), s, dk);
-        if (d.dh_g) hipLaunchKernelGGL((k2_rowptr<K2_RP_ROWS_DH, true>), dim3(((size_t)d.ncap + K2_RP_ROWS_DH) / K2_RP_ROWS_DH), dim3(1024), 0, s, dk, ++e->rp_epoch);
-        else hipLaunchKernelGGL((k2_rowptr<K2_RP_ROWS, false>), dim3(((size_t)d.ncap + K2_RP_ROWS) / K2_RP_ROWS), dim3(1024), 0, s, dk, ++e->rp_epoch);
+        const size_t rpr = d.dh_g ? K2_RP_ROWS_DH : K2_RP_ROWS;
+        hipLaunchKernelGGL(e->fn.k2_rowptr, dim3(((size_t)d.ncap + rpr) / rpr), dim3(1024), 0, s, dk, ++e->rp_epoch);
         if (d.variant == 1) hipLaunchKernelGGL(k2_scatter_table, dim3(grid_for(e->cfg.max_edges, 256)), dim3(256), 0, s, d);
         else hipLaunchKernelGGL(k2_scatter_parts, dim3(d.npb), dim3(256), 0, s, dk);
         hipLaunchKernelGGL(k2_rowsort_gather, dim3(std::max(2, std::min(4096, 2 * K2_LONG_WGS + grid_for(d.ncap, 8)))), dim3(256), 2 * (size_t)d.k2_sortw * sizeof(u32), s, dk);
@@ -560,18 +606,10 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
     const bool pj = fuse_proj && l + 1 == e->cfg.layers && d.world == 1;
     Timed t(e, s, 4);
     const bool split = e->plan.k4_split;                    // two launches per layer: the gather-mean, then the dense tiles (sg_plan.hpp)
-#define K4_LAUNCH(FI, MF, PJ, HIN, HOUT) do { if (split) { \
-            hipLaunchKernelGGL((k4_gather<FI>), dim3(grid_for(d.ncap, K4G_ROWS, 4096 * 8 / K4G_ROWS)), dim3(K4G_ROWS * 64), 0, s, d, HIN); \
-            hipLaunchKernelGGL((k4_sage_layer<FI, MF, PJ, (PJ ? 512 : 256), true>), dim3(grid), dim3(PJ ? 512 : 256), 0, s, d, HIN, HOUT, Wl, Wh); \
-        } else hipLaunchKernelGGL((k4_sage_layer<FI, MF, PJ, (FI == 32 ? 1024 : 512), false>), dim3(grid), dim3(FI == 32 ? 1024 : 512), 0, s, d, HIN, HOUT, Wl, Wh); } while (0)
-    if (l == 0) {
-        if (e->plan.use_mfma) { if (pj) K4_LAUNCH(32, true, true, d.x0, d.h[1]); else K4_LAUNCH(32, true, false, d.x0, d.h[1]); }
-        else { if (pj) K4_LAUNCH(32, false, true, d.x0, d.h[1]); else K4_LAUNCH(32, false, false, d.x0, d.h[1]); }
-    } else {
-        if (e->plan.use_mfma) { if (pj) K4_LAUNCH(64, true, true, d.h[l], d.h[l + 1]); else K4_LAUNCH(64, true, false, d.h[l], d.h[l + 1]); }
-        else { if (pj) K4_LAUNCH(64, false, true, d.h[l], d.h[l + 1]); else K4_LAUNCH(64, false, false, d.h[l], d.h[l + 1]); }
-    }
-#undef K4_LAUNCH
+    const int wide = l != 0;                                // layer 0 reads the 32 input features, the others 64 hidden ones
+    const float* hin = wide ? d.h[l] : d.x0;
+    if (split) hipLaunchKernelGGL(kK4Gather[wide], dim3(grid_for(d.ncap, K4G_ROWS, 4096 * 8 / K4G_ROWS)), dim3(K4G_ROWS * 64), 0, s, d, hin);
+    hipLaunchKernelGGL(e->fn.k4_layer[wide][pj], dim3(grid), dim3(k4_threads(wide ? 64 : 32, pj, split)), 0, s, d, hin, d.h[l + 1], Wl, Wh);
     HIP_TRY(e, hipGetLastError());
     return fuse_proj ? SG_OK : note_w_read(e, s);           // (the one-call pipelines score on the same stream next: K5's event covers K4)
 }
@@ -706,13 +744,8 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     const bool fr = fuse_reset && d.variant == 0;
     {
         Timed t(e, s, 5);
-        if (!(proj_done && d.world == 1)) {
-            if (e->plan.use_mfma) hipLaunchKernelGGL((k5_node_proj<true>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
-            else hipLaunchKernelGGL((k5_node_proj<false>), dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
-        }
-        const int g5 = (int)e->plan.k5_grid;                // one round of workgroups (sg_plan.hpp)
-        if (fr) hipLaunchKernelGGL(k5_edge_score<true>, dim3(g5), dim3(256), 0, s, d, Wh);
-        else hipLaunchKernelGGL(k5_edge_score<false>, dim3(g5), dim3(256), 0, s, d, Wh);
+        if (!(proj_done && d.world == 1)) hipLaunchKernelGGL(e->fn.k5_proj, dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
+        hipLaunchKernelGGL(kK5Score[fr], dim3((int)e->plan.k5_grid), dim3(256), 0, s, d, Wh);   // one round of workgroups (sg_plan.hpp)
     }
     if (did_reset) *did_reset = fr;
     HIP_TRY(e, hipGetLastError());
@@ -804,16 +837,6 @@ int do_read(sg_engine* e, sg_edge_out* out, size_t cap, size_t* n, const sg_edge
     if (nob) HIP_TRY(e, hipMemcpy(e->last_obips.data(), e->d.ob_sorted, nob * sizeof(u32), hipMemcpyDeviceToHost));
     account_window(e);
     return SG_OK;
-}
-
-// the largest dynamic LDS a launch of these kernels may ask for (a process-wide attribute of each kernel)
-template <class... K>
-hipError_t lds_limit(size_t bytes, K... kernels) {
-    for (const void* f : {reinterpret_cast<const void*>(kernels)...}) {
-        const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (r != hipSuccess) return r;
-    }
-    return hipSuccess;
 }
 
 // ---- K7, the selection (engine lock held) ---------------------------------------------------------------------------------------
@@ -1095,37 +1118,13 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
         d.kind = reinterpret_cast<const uint8_t*>(e->d_blob + L.off_kind);
     }
     if (d.variant == 0) {
-        if (!sgplan::plan_pass_a(P, e->jt.l1_entries, e->jt.blocks_bytes(), e->ov, &e->pa)) { e->err = "K1 pass A: piece counters and join level 1 do not fit a CU's LDS"; return fail(SG_ENOSPC); }
-        CH(lds_limit(kLdsBytes, k1a_partition<true, true, false>, k1a_partition<true, false, false>, k1a_partition<false, true, false>, k1a_partition<false, false, false>,
-                     k1a_partition<true, true, true>, k1a_partition<true, false, true>, k1a_partition<false, true, true>, k1a_partition<false, false, true>,
-                     k1a_tile_partition<2, true, 2>, k1a_tile_partition<2, false, 2>, k1a_tile_partition<1, true, 2>, k1a_tile_partition<1, false, 2>,
-                     k1a_tile_partition<0, true, 2>, k1a_tile_partition<0, false, 2>, k1a_tile_partition<2, true, 1>, k1a_tile_partition<2, false, 1>,
-                     k1a_tile_partition<1, true, 1>, k1a_tile_partition<1, false, 1>, k1a_tile_partition<0, true, 1>, k1a_tile_partition<0, false, 1>,
-                     k1a_team_partition<2, true, 2, 1024, 8>, k1a_team_partition<2, false, 2, 1024, 8>, k1a_team_partition<2, true, 2, 1024, 9>,
-                     k1a_team_partition<2, false, 2, 1024, 9>, k1a_team_partition<2, true, 2, 1024, 10>, k1a_team_partition<2, false, 2, 1024, 10>,
-                     k1a_team_partition<1, true, 2, 1024, 8>, k1a_team_partition<1, false, 2, 1024, 8>, k1a_team_partition<1, true, 2, 1024, 9>,
-                     k1a_team_partition<1, false, 2, 1024, 9>, k1a_team_partition<1, true, 2, 1024, 10>, k1a_team_partition<1, false, 2, 1024, 10>,
-                     k1a_team_partition<0, true, 2, 1024, 8>, k1a_team_partition<0, false, 2, 1024, 8>, k1a_team_partition<0, true, 2, 1024, 9>,
-                     k1a_team_partition<0, false, 2, 1024, 9>, k1a_team_partition<0, true, 2, 1024, 10>, k1a_team_partition<0, false, 2, 1024, 10>));
-        CH(lds_limit(P.k1b_lds, k1b_merge<4, false>, k1b_merge<8, false>, k1b_merge<4, true>, k1b_merge_wide<4, false>, k1b_merge_wide<8, false>, k1b_merge_wide<4, true>,
-                     k1b_stream_merge<4, 1, false>, k1b_stream_merge<4, 2, false>, k1b_stream_merge<4, 4, false>,
-                     k1b_stream_merge<8, 1, false>, k1b_stream_merge<8, 2, false>, k1b_stream_merge<8, 4, false>,
-                     k1b_stream_merge_wide<4, 1, false>, k1b_stream_merge_wide<4, 2, false>, k1b_stream_merge_wide<4, 4, false>,
-                     k1b_stream_merge_wide<8, 1, false>, k1b_stream_merge_wide<8, 2, false>, k1b_stream_merge_wide<8, 4, false>,
-                     k1b_stream_merge<4, 1, true>, k1b_stream_merge<4, 2, true>, k1b_stream_merge<4, 4, true>,
-                     k1b_stream_merge<8, 1, true>, k1b_stream_merge<8, 2, true>, k1b_stream_merge<8, 4, true>,
-                     k1b_stream_merge_wide<4, 1, true>, k1b_stream_merge_wide<4, 2, true>, k1b_stream_merge_wide<4, 4, true>,
-                     k1b_stream_merge_wide<8, 1, true>, k1b_stream_merge_wide<8, 2, true>, k1b_stream_merge_wide<8, 4, true>));
-        CH(lds_limit(P.k1b_lds, k1b_stream_merge<K1B_WARM_U, 1, false, 1>, k1b_stream_merge<K1B_WARM_U, 2, false, 1>, k1b_stream_merge<K1B_WARM_U, 4, false, 1>,
-                     k1b_stream_merge<K1B_WARM_U, 1, true, 1>, k1b_stream_merge<K1B_WARM_U, 2, true, 1>, k1b_stream_merge<K1B_WARM_U, 4, true, 1>,
-                     k1b_stream_merge_wide<K1B_WARM_U, 1, false, 1>, k1b_stream_merge_wide<K1B_WARM_U, 2, false, 1>, k1b_stream_merge_wide<K1B_WARM_U, 4, false, 1>,
-                     k1b_stream_merge_wide<K1B_WARM_U, 1, true, 1>, k1b_stream_merge_wide<K1B_WARM_U, 2, true, 1>, k1b_stream_merge_wide<K1B_WARM_U, 4, true, 1>,
-                     k1b_stream_merge<K1B_WARM_U, 1, false, 2>, k1b_stream_merge<K1B_WARM_U, 2, false, 2>, k1b_stream_merge<K1B_WARM_U, 4, false, 2>,
-                     k1b_stream_merge<K1B_WARM_U, 1, true, 2>, k1b_stream_merge<K1B_WARM_U, 2, true, 2>, k1b_stream_merge<K1B_WARM_U, 4, true, 2>,
-                     k1b_stream_merge_wide<K1B_WARM_U, 1, false, 2>, k1b_stream_merge_wide<K1B_WARM_U, 2, false, 2>, k1b_stream_merge_wide<K1B_WARM_U, 4, false, 2>,
-                     k1b_stream_merge_wide<K1B_WARM_U, 1, true, 2>, k1b_stream_merge_wide<K1B_WARM_U, 2, true, 2>, k1b_stream_merge_wide<K1B_WARM_U, 4, true, 2>));
+        CR(plan_pass_a(e));
+        CH(lds_limit_all<K1aWide>(kLdsBytes)); CH(lds_limit_all<K1aTile>(kLdsBytes)); CH(lds_limit_all<K1aTeam>(kLdsBytes));
+        CH(lds_limit_all<K1bMerge>(P.k1b_lds)); CH(lds_limit_all<K1bStream>(P.k1b_lds));
         CH(lds_limit((size_t)KW_ROWS * 5 * sizeof(u64), kw_compact));
     }
+    e->kn = sgplan::choose_kernels(P, e->pa, *cfg);
+    CR(resolve_kernels(e));
     CH(lds_limit(2 * (size_t)d.k2_sortw * sizeof(u32), k2_rowsort_gather));
     if (d.dh_g) CH(lds_limit(((size_t)d.ncap + 1) * sizeof(u32), k2_deg_hist));
     CH(lds_limit(P.k3in_lds, k3_in_part));

@@ -3,10 +3,13 @@
 //
 // One place for the rules that each round retunes (which K1 path a window takes, partitions and pass-B table slots, the pass-A
 // cache and its teams, warm-window state, the close's slices / splits / grids), each with the measured reason it has.
+// It also chooses the kernel instantiation of every launch site that has several (Kernels) and lists the instantiations the
+// library holds (k*Keys), which servicegraph.hip expands into its kernel tables.
 // No HIP in this file: tests/micro/plan_test.cpp drives it on the CPU and tests/test_plan.py compares its plans with the
 // ones the engine made before it existed (tests/golden/plans.json).
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -353,6 +356,82 @@ inline bool plan_pass_a(const Plan& p, uint32_t l1_entries, size_t l2_bytes, con
     *out = a;
     return true;
 }
+
+// ---- which kernel instantiation each launch site runs -------------------------------------------------------------------------
+// The template arguments of the kernel families that come in several instantiations, chosen from the plan: servicegraph.hip
+// resolves them to kernel pointers through one table per family (at create, and pass A's again whenever it is re-planned), and
+// tests/test_plan.py checks the choice on the CPU.  A field the chosen family does not take is 0.
+enum K1aFamily { K1A_GLOBAL = 0, K1A_WIDE = 1, K1A_TILE = 2, K1A_TEAM = 3 };   // k1_resolve_aggregate, k1a_partition, k1a_tile_partition, k1a_team_partition
+enum K1bFamily { K1B_NONE = 0, K1B_MERGE = 1, K1B_STREAM = 2 };                // (variant 1 has no pass B), k1b_merge, k1b_stream_merge
+constexpr int kK1bWarmU = 2;                  // K1B_WARM_U (sg_k1_narrow.h): pass B's U on an engine that keeps warm state
+struct PassAKernel {
+    int family = K1A_GLOBAL;
+    int l2 = 0;                               // level 2 of the join tables: 0 = global memory, 1 = LDS, 2 = LDS as u16 entries (tile, team)
+    bool sharded = false, hist = false;       // (hist: k1a_partition only)
+    int nsub = 0, pb = 0;                     // tile: sub-tiles (1, 2); team: log2 of the partitions (8, 9, 10)
+};
+struct Kernels {
+    PassAKernel k1a;
+    // pass B.  share: the SGPR-capped build (two workgroups share a CU) rather than its _wide twin.  warm: the engine launches the
+    // warm attempt and the cold merge (WM 1 and 2, U = kK1bWarmU); a window it closes the plain way takes the WM 0 form with k1b_u.
+    int k1b_family = K1B_NONE, k1b_u = 0, k1b_spt = 0;
+    bool k1b_pack = false, k1b_hist = false, k1b_share = false, k1b_warm = false;
+    bool k2_dh = false;                       // k2_rowptr over the degree histograms
+    bool k4_split = false, k4_mfma = true;    // k4_sage_layer (input width, projection and threads follow the layer at launch)
+    bool k5_mfma = true;                      // k5_node_proj (k5_edge_score's fused reset is the caller's argument)
+};
+inline PassAKernel choose_pass_a(const Plan& p, const PassA& a, const sg_config& cfg) {
+    PassAKernel k;
+    if (p.variant != 0) return k;
+    k.sharded = cfg.world > 1;
+    if (!p.narrow) { k.family = K1A_WIDE; k.l2 = a.l2_in_lds ? 1 : 0; k.hist = p.hist != 0; return k; }
+    k.l2 = a.l2_in_lds ? (a.l2_u16 ? 2 : 1) : 0;
+    if (a.k1a_team) { k.family = K1A_TEAM; k.pb = p.np == 256 ? 8 : p.np == 512 ? 9 : 10; }
+    else { k.family = K1A_TILE; k.nsub = a.k1a_nsub == 2 ? 2 : 1; }
+    return k;
+}
+inline Kernels choose_kernels(const Plan& p, const PassA& a, const sg_config& cfg) {
+    Kernels k;
+    k.k1a = choose_pass_a(p, a, cfg);
+    if (p.variant == 0) {
+        // several partitions per CU and room for two tables: the SGPR-capped build lets two workgroups share a CU
+        k.k1b_share = p.npb > p.cus && 2 * p.k1b_lds <= kLdsBytes;
+        const u32 spt = p.k1b_ht / p.k1b_threads;                      // table slots per thread of the compaction
+        k.k1b_u = p.k1b_u == 8 ? 8 : 4;
+        if (p.warm || p.narrow) { k.k1b_family = K1B_STREAM; k.k1b_spt = spt >= 4 ? 4 : spt == 2 ? 2 : 1; k.k1b_pack = p.k1b_pack; k.k1b_warm = p.warm != 0; }
+        else { k.k1b_family = K1B_MERGE; k.k1b_hist = p.hist != 0; if (k.k1b_hist) k.k1b_u = 4; }
+    }
+    k.k2_dh = p.dh_g != 0;
+    k.k4_split = p.k4_split; k.k4_mfma = p.use_mfma; k.k5_mfma = p.use_mfma;
+    return k;
+}
+
+// The instantiations the library holds, per family: one key per kernel, its template arguments in the kernel's own order (pass B's
+// last element: share).  servicegraph.hip expands these into its kernel tables; plan_test --domains prints them.
+template <size_t N> using Key = std::array<int, N>;
+template <size_t... L>
+constexpr std::array<Key<sizeof...(L)>, (L * ...)> product(const int (&... v)[L]) {      // every combination of one value per list
+    std::array<Key<sizeof...(L)>, (L * ...)> out{};
+    for (size_t i = 0; i < out.size(); i++) { size_t r = i, k = 0; ((out[i][k++] = v[r % L], r /= L), ...); }
+    return out;
+}
+template <size_t N, size_t A, size_t B>
+constexpr std::array<Key<N>, A + B> concat(const std::array<Key<N>, A>& a, const std::array<Key<N>, B>& b) {
+    std::array<Key<N>, A + B> out{};
+    for (size_t i = 0; i < A; i++) out[i] = a[i];
+    for (size_t i = 0; i < B; i++) out[A + i] = b[i];
+    return out;
+}
+template <size_t N, size_t M>
+int find_key(const std::array<Key<N>, M>& dom, const Key<N>& k) { for (size_t i = 0; i < M; i++) if (dom[i] == k) return (int)i; return -1; }
+
+inline constexpr auto kK1aWideKeys = product({0, 1}, {0, 1}, {0, 1});                    // k1a_partition<l2, sharded, hist>
+inline constexpr auto kK1aTileKeys = product({0, 1, 2}, {0, 1}, {1, 2});                 // k1a_tile_partition<l2, sharded, nsub>
+inline constexpr auto kK1aTeamKeys = product({0, 1, 2}, {0, 1}, {8, 9, 10});             // k1a_team_partition<l2, sharded, 2, 1024, pb>
+inline constexpr auto kK1bMergeKeys = concat(product({4, 8}, {0}, {0, 1}), product({4}, {1}, {0, 1}));   // k1b_merge[_wide]<u, hist>, share
+inline constexpr auto kK1bStreamKeys = concat(product({4, 8}, {1, 2, 4}, {0, 1}, {0}, {0, 1}),           // k1b_stream_merge[_wide]<u, spt, pack, wm>, share
+                                              product({kK1bWarmU}, {1, 2, 4}, {0, 1}, {1, 2}, {0, 1}));
+inline constexpr auto kK4LayerKeys = product({32, 64}, {0, 1}, {0, 1}, {0, 1});          // k4_sage_layer<fi, mfma, proj, threads, split>
 
 // K7, the selection (sg_sel.h): its scratch and grids.  Allocated at an engine's first selection: an engine that never selects
 // asks for nothing (used = false).  Rows are split into `wgs` contiguous spans of at least 2048 (eight rows per lane of a 256-thread

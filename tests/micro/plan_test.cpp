@@ -1,7 +1,9 @@
 // CPU driver of alaz_amd/csrc/sg_plan.hpp (tests/test_plan.py).  stdin: one case per line,
 //   name key=value ...   config fields (sg_config names), SG_* overrides, l1= / l2= join-table sizes for a second pass-A plan.
 // stdout: one JSON object per case — the plan, the Dev fields the engine fills from it at create, pass A for the join tables as
-// sg_create builds them and, given l1 / l2, pass A for those sizes.  --knobs: the knob names, one per line.
+// sg_create builds them and, given l1 / l2, pass A for those sizes; "kernels" (and "kernels_after") is the kernel instantiation each
+// launch site takes under that plan.  --knobs: the knob names, one per line.  --domains: the instantiations the library holds, per
+// kernel family, as lists of template arguments (one JSON object).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,8 +38,33 @@ static std::string pass_a_json(u32 l1, size_t l2, const PassA& a) {
     return j.str();
 }
 
+static std::string kernels_json(const Kernels& k) {
+    Json j;
+    j.kv("k1a_family", k.k1a.family); j.kv("k1a_l2", k.k1a.l2); j.kv("k1a_sharded", k.k1a.sharded); j.kv("k1a_hist", k.k1a.hist);
+    j.kv("k1a_nsub", k.k1a.nsub); j.kv("k1a_pb", k.k1a.pb);
+    j.kv("k1b_family", k.k1b_family); j.kv("k1b_u", k.k1b_u); j.kv("k1b_spt", k.k1b_spt); j.kv("k1b_pack", k.k1b_pack); j.kv("k1b_hist", k.k1b_hist);
+    j.kv("k1b_share", k.k1b_share); j.kv("k1b_warm", k.k1b_warm);
+    j.kv("k2_dh", k.k2_dh); j.kv("k4_split", k.k4_split); j.kv("k4_mfma", k.k4_mfma); j.kv("k5_mfma", k.k5_mfma);
+    return j.str();
+}
+
+template <size_t N, size_t M>
+static std::string keys_json(const char* name, const std::array<Key<N>, M>& keys) {
+    std::ostringstream o;
+    o << '"' << name << "\": [";
+    for (size_t i = 0; i < M; i++) { o << (i ? ", [" : "["); for (size_t k = 0; k < N; k++) o << (k ? ", " : "") << keys[i][k]; o << "]"; }
+    o << "]";
+    return o.str();
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && !std::strcmp(argv[1], "--knobs")) { for (const KnobName& k : kKnobs) std::printf("%s\n", k.name); return 0; }
+    if (argc > 1 && !std::strcmp(argv[1], "--domains")) {
+        std::cout << "{" << keys_json("k1a_wide", kK1aWideKeys) << ", " << keys_json("k1a_tile", kK1aTileKeys) << ", " << keys_json("k1a_team", kK1aTeamKeys)
+                  << ", " << keys_json("k1b_merge", kK1bMergeKeys) << ", " << keys_json("k1b_stream", kK1bStreamKeys) << ", " << keys_json("k4_layer", kK4LayerKeys)
+                  << ", \"k1b_warm_u\": " << kK1bWarmU << "}" << std::endl;
+        return 0;
+    }
     DeviceFacts dev;
     std::string line;
     while (std::getline(std::cin, line)) {
@@ -96,10 +123,14 @@ int main(int argc, char** argv) {
 #undef P
 #undef D
             o << ", \"cus\": " << p.cus << ", \"plan\": " << j.str() << ", \"pass_a\": " << pass_a_json(jt.l1_entries, jt.blocks_bytes(), pa);
+            Kernels kn = choose_kernels(p, pa, cfg);
+            o << ", \"kernels\": " << kernels_json(kn);
             if (after) {
                 PassA pb = pa;                                      // (the engine keeps its geometry when the tables leave no legal one)
                 const bool ok = p.variant != 0 || plan_pass_a(p, (u32)l1, (size_t)l2, ov, &pb);
                 o << ", \"upsert_rc\": " << (ok ? SG_OK : SG_ENOSPC) << ", \"pass_a_after\": " << pass_a_json((u32)l1, (size_t)l2, pb);
+                kn.k1a = choose_pass_a(p, pb, cfg);                // (the rest of the choice is made once, at create)
+                o << ", \"kernels_after\": " << kernels_json(kn);
             }
         }
         o << "}";

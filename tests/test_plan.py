@@ -68,3 +68,99 @@ def test_knob_list_is_the_engines(plan_exe):
     from alaz_amd import engine
     out = subprocess.run([plan_exe, "--knobs"], capture_output=True, text=True, timeout=60, check=True)
     assert tuple(out.stdout.split()) == engine.DEV_KNOBS
+
+
+K1A_GLOBAL, K1A_WIDE, K1A_TILE, K1A_TEAM = range(4)
+K1B_NONE, K1B_MERGE, K1B_STREAM = range(3)
+LDS_BYTES = 160 * 1024
+
+
+def ladder_choice(plan, pa, world, cus):
+    """The kernel instantiation each launch site took before the choice was a plan field: the launch ladders of servicegraph.hip at
+    commit 69acf5a, restated over the plan and pass-A fields the driver prints.  A field the chosen kernel does not take is 0.
+
+    - pass A, launch_k1, lines 307-338: `sh` = world > 1; narrow and k1a_team: K1M_GO (312-314: np 256 -> 8, 512 -> 9, anything else
+      -> 10) under the level-2 chain of 328-330 (l2_in_lds and l2_u16 -> 2, l2_in_lds -> 1, else 0); narrow: K1T_GO2 (311: nsub == 2 -> 2,
+      else 1) under the same chain, 333-335; else K1A_GO2 (309: hist) with l2_in_lds as a boolean, 337-338; variant 1 launches
+      k1_resolve_aggregate, 349.
+    - pass B, do_close, lines 442-464: `share` (442); warm engines take K1B8W_GO2 with K1B_WARM_U for the attempt and the cold merge
+      (450-455) and, on a window closed the plain way (425), the cold arm; K1B8_GO2 / K1B8W_GO2 fold the slots per thread (449, 462:
+      >= 4 -> 4, == 2 -> 2, else 1); 463: narrow, k1b_u == 8 -> 8 else 4; 464: hist -> <4, true>, k1b_u == 8 -> <8, false>, else <4, false>.
+    - k2_rowptr, lines 494-495: dh_g.  K4, do_layer, lines 562-572: split, use_mfma.  K5, do_score, lines 710-711: use_mfma."""
+    k = dict(k1a_family=K1A_GLOBAL, k1a_l2=0, k1a_sharded=0, k1a_hist=0, k1a_nsub=0, k1a_pb=0,
+             k1b_family=K1B_NONE, k1b_u=0, k1b_spt=0, k1b_pack=0, k1b_hist=0, k1b_share=0, k1b_warm=0,
+             k2_dh=int(plan["dh_g"] != 0), k4_split=plan["k4_split"], k4_mfma=plan["use_mfma"], k5_mfma=plan["use_mfma"])
+    if plan["variant"] != 0:
+        return k
+    k["k1a_sharded"] = int(world > 1)
+    l2m = 2 if pa["l2_in_lds"] and pa["l2_u16"] else 1 if pa["l2_in_lds"] else 0
+    if plan["narrow"] and pa["k1a_team"]:
+        k.update(k1a_family=K1A_TEAM, k1a_l2=l2m, k1a_pb={256: 8, 512: 9}.get(plan["np"], 10))
+    elif plan["narrow"]:
+        k.update(k1a_family=K1A_TILE, k1a_l2=l2m, k1a_nsub=2 if pa["k1a_nsub"] == 2 else 1)
+    else:
+        k.update(k1a_family=K1A_WIDE, k1a_l2=int(bool(pa["l2_in_lds"])), k1a_hist=plan["hist"])
+    k["k1b_share"] = int(plan["npb"] > cus and 2 * plan["k1b_lds"] <= LDS_BYTES)
+    spt = plan["k1b_ht"] // plan["k1b_threads"]
+    spt = 4 if spt >= 4 else 2 if spt == 2 else 1
+    u = 8 if plan["k1b_u"] == 8 else 4
+    if plan["warm"] or plan["narrow"]:
+        k.update(k1b_family=K1B_STREAM, k1b_u=u, k1b_spt=spt, k1b_pack=plan["k1b_pack"], k1b_warm=plan["warm"])
+    elif plan["hist"]:
+        k.update(k1b_family=K1B_MERGE, k1b_u=4, k1b_hist=1)
+    else:
+        k.update(k1b_family=K1B_MERGE, k1b_u=u)
+    return k
+
+
+def choice_keys(k, warm_u):
+    """(family of the library, template arguments) of every kernel an engine with this choice may launch"""
+    keys = []
+    if k["k1a_family"] == K1A_WIDE:
+        keys.append(("k1a_wide", [k["k1a_l2"], k["k1a_sharded"], k["k1a_hist"]]))
+    if k["k1a_family"] == K1A_TILE:
+        keys.append(("k1a_tile", [k["k1a_l2"], k["k1a_sharded"], k["k1a_nsub"]]))
+    if k["k1a_family"] == K1A_TEAM:
+        keys.append(("k1a_team", [k["k1a_l2"], k["k1a_sharded"], k["k1a_pb"]]))
+    if k["k1b_family"] == K1B_MERGE:
+        keys.append(("k1b_merge", [k["k1b_u"], k["k1b_hist"], k["k1b_share"]]))
+    if k["k1b_family"] == K1B_STREAM:
+        keys.append(("k1b_stream", [k["k1b_u"], k["k1b_spt"], k["k1b_pack"], 0, k["k1b_share"]]))
+        if k["k1b_warm"]:
+            keys += [("k1b_stream", [warm_u, k["k1b_spt"], k["k1b_pack"], wm, k["k1b_share"]]) for wm in (1, 2)]
+    keys += [("k4_layer", [fi, k["k4_mfma"], pj, k["k4_split"]]) for fi in (32, 64) for pj in (0, 1)]
+    return keys
+
+
+def test_kernel_choice_is_the_launch_ladders(plan_exe):
+    """every case of plans.json (bench shapes, knob cases, the pass-A states after upserts): the planner's kernel choice against
+    ladder_choice, and every kernel it may launch inside the instantiations the library enumerates"""
+    cases = json.load(open(GOLDEN))["cases"]
+    got = run_plans(plan_exe, [planner_input(c) for c in cases])
+    out = subprocess.run([plan_exe, "--domains"], capture_output=True, text=True, timeout=60, check=True)
+    domains = json.loads(out.stdout)
+    warm_u = domains.pop("k1b_warm_u")
+    # the instantiation counts of the library: k1b_merge and k1b_stream_merge each with a _wide twin
+    assert {f: len(v) for f, v in domains.items()} == dict(k1a_wide=8, k1a_tile=12, k1a_team=18, k1b_merge=2 * 3, k1b_stream=2 * 24,
+                                                           k4_layer=16)
+    assert all(len(set(map(tuple, v))) == len(v) for v in domains.values())
+    checked, families, after = 0, set(), 0
+    for c in cases:
+        have = got[c["name"]]
+        if have["rc"] != 0:
+            assert "kernels" not in have
+            continue
+        world = int(dict(t.split("=") for t in c["input"].split()).get("world", 1))
+        for part, pa in (("kernels", "pass_a"), ("kernels_after", "pass_a_after")):
+            if pa not in have:
+                continue
+            want = ladder_choice(have["plan"], have[pa], world, have["cus"])
+            assert have[part] == want, (c["name"], part, {f: (want[f], have[part][f]) for f in want if want[f] != have[part].get(f)})
+            for fam, key in choice_keys(have[part], warm_u):
+                assert key in domains[fam], (c["name"], part, fam, key)
+            checked += 1
+            after += part == "kernels_after"
+            families.add((have[part]["k1a_family"], have[part]["k1b_family"]))
+    assert checked >= 127 + 11 and after >= 11
+    # the recorded cases reach every pass-A and pass-B family
+    assert families >= {(K1A_GLOBAL, K1B_NONE), (K1A_WIDE, K1B_MERGE), (K1A_TILE, K1B_STREAM), (K1A_TEAM, K1B_STREAM)}
