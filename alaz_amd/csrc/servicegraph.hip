@@ -27,6 +27,7 @@
 #include "sg_sel.h"
 #include "sg_trend.h"
 #include "sg_node_trend.h"
+#include "sg_rank.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -172,6 +173,13 @@ struct sg_engine {
     // node selection (K7 over node rows): scratch of plan_select(ncap) allocated at the first one, with the counter block k10_keys
     // fills, an index array and the host form's row staging (ncap each), in a block of its own (mem).
     struct NSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; sg_node_out* stage = nullptr; char* mem = nullptr; } nsel;
+    // K11, the culprit ranking (sg_rank.h): allocated at sg_set_rank (sg_plan.hpp plan_rank), one allocation, freed with the rollup.
+    // The per-row and per-node-key arrays and the partials are scratch shared by the window slots: every ranking waits for the
+    // previous one (ev), whichever slot's stream it runs on.  Per slot: the rank rows, and whether the window in the slot was ranked.
+    struct Rank { bool on = false; sg_rank_params p{}; sgplan::RankPlan plan; char* mem = nullptr; u32* src = nullptr; u32* dst = nullptr; u32* w = nullptr;
+                  u64* W = nullptr; u64* R = nullptr; u64* base = nullptr; u64* t = nullptr; u64* part = nullptr; u64* seed_sum = nullptr;
+                  sg_node_rank* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_node_rank*> rows; std::vector<char> valid;
+                  hipEvent_t ev = nullptr; bool pending = false; } rank;
 };
 
 namespace {
@@ -716,7 +724,46 @@ void free_baseline(sg_engine::Baseline<Row>& t) {
     t = sg_engine::Baseline<Row>{};
 }
 
+// ---- K11, the culprit ranking (engine lock held) ---------------------------------------------------------------------------------
+static_assert(sgplan::kRankThreads == K11_THREADS && sgplan::kRankRangeNodes == K11_NR && sgplan::kRankMaxWgs == K11_MAX_WGS &&
+              sgplan::kRankRangeNodes * 8 <= sgplan::kLdsBytes, "plan_rank sizes the launches of sg_rank.h");
+// enqueue the ranking of the window in slot cur on stream s (behind its rollup, on the same stream) and behind the previous
+// ranking (any stream): 2 * iters + 3 plain launches, the rank rows go to the slot's buffer
+int launch_rank(sg_engine* e, hipStream_t s) {
+    sg_engine::Rank& r = e->rank;
+    const sgplan::RankPlan& P = r.plan;
+    RankArgs a{};
+    a.nd.rows = e->d.rows; a.nd.ctr = e->d.ctr; a.nd.max_edges = e->cfg.max_edges;
+    a.nd.mk = e->d.max_known; a.nd.ml = e->d.max_labels; a.nd.mob = e->d.max_obip; a.nd.ncap = P.ncap;
+    a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur];
+    a.slices = P.slices; a.prep_wgs = P.prep_wgs; a.damping = r.p.damping_q8; a.seed = r.p.seed; a.seed_min = r.p.seed_min_score;
+    a.src = r.src; a.dst = r.dst; a.w = r.w; a.W = r.W; a.R = r.R; a.base = r.base; a.t = r.t; a.part = r.part; a.seed_sum = r.seed_sum;
+    a.out = r.rows[e->cur];
+    if (r.pending) HIP_TRY(e, hipStreamWaitEvent(s, r.ev, 0));
+    const dim3 eg(P.ranges * P.slices), et(K11_EDGE_THREADS), ng(P.node_wgs), nt(K11_THREADS);
+    hipLaunchKernelGGL(k11_prep, dim3(P.prep_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k11_edge<true>, eg, et, (size_t)P.lds_bytes, s, a);
+    hipLaunchKernelGGL((k11_node<true, false>), ng, nt, 0, s, a);
+    for (u32 i = 1; i <= r.p.iters; i++) {
+        hipLaunchKernelGGL(k11_edge<false>, eg, et, (size_t)P.lds_bytes, s, a);
+        if (i < r.p.iters) hipLaunchKernelGGL((k11_node<false, false>), ng, nt, 0, s, a);
+        else hipLaunchKernelGGL((k11_node<false, true>), ng, nt, 0, s, a);
+    }
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(r.ev, s));
+    r.pending = true;
+    r.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_rank(sg_engine* e) {
+    sg_engine::Rank& r = e->rank;
+    if (r.mem) { hipDeviceSynchronize(); hipFree(r.mem); }
+    if (r.ev) hipEventDestroy(r.ev);
+    r = sg_engine::Rank{};
+}
+
 void free_nodes(sg_engine* e) {
+    free_rank(e);
     free_baseline(e->ntrend);
     sg_engine::Nodes& n = e->nodes;
     if (n.mem) { hipDeviceSynchronize(); hipFree(n.mem); }
@@ -756,7 +803,8 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     // K9 behind them: it reads the rows and the window counters only; K10 behind K9: the node rows, their count, the outbound IPs
     if (e->nodes.on) {
         if (const int rc = launch_nodes(e, s)) return rc;
-        if (e->ntrend.on) return launch_node_trend(e, s);
+        if (e->ntrend.on) { if (const int rc = launch_node_trend(e, s)) return rc; }
+        if (e->rank.on) return launch_rank(e, s);                    // K11 behind K9: the rows, the counters, the node rows and their count
     }
     return SG_OK;
 }
@@ -930,9 +978,11 @@ int nsel_reserve(sg_engine* e) {
     return sel_init(e, s, b);
 }
 // enqueue a selection over the node rows of slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
-// be NULL), the count to d_n; behind that window's rollup and node trend (events) and the previous node selection
-int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
-                       u64 cap, u64* d_n) {
+// be NULL), the count to d_n; behind that window's rollup (event) and the previous node selection.  keys(a, wgs) launches the key
+// pass (k10_keys, k11_keys) and waits for what it reads; after(a, grid) launches what else gathers by the selected indices.
+template <class Keys, class After>
+int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
+                       u64 cap, u64* d_n, Keys keys, After after) {
     sg_engine::NSel& s = e->nsel;
     const u32 wgs = s.plan.wgs;
     const u64 NC = std::max<u32>(e->d.ncap, 1);
@@ -942,19 +992,62 @@ int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, fl
     a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, NC); a.n_out = d_n;
     if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
     if (e->nodes.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->nodes.ev, 0));
-    if (by != SG_NSEL_SCORE && e->ntrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->ntrend.ev, 0));
     const sg_node_out* nodes = e->nodes.rows[slot];
-    const sg_node_trend* tr = by != SG_NSEL_SCORE ? e->ntrend.rows[slot] : nullptr;
-    hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, nodes, (const u64*)e->nodes.count[slot], tr, by, s.ctr);
+    if (const int rc = keys(a, wgs)) return rc;
     enqueue_k7_select(st, a, k, wgs, NC);
-    if (d_out) {
-        const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, NC) : NC);
-        hipLaunchKernelGGL(k10_gather_rows, dim3((unsigned)std::max<u64>(1, std::min<u64>((m + 255) / 256, 1024))), dim3(256), 0, st,
-                           nodes, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
-    }
+    const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, NC) : NC);
+    const dim3 grid((unsigned)std::max<u64>(1, std::min<u64>((m + 255) / 256, 1024)));
+    if (d_out) hipLaunchKernelGGL(k10_gather_rows, grid, dim3(256), 0, st, nodes, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
+    after(a, grid);
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipEventRecord(s.ev, st));
     s.pending = true;
+    return SG_OK;
+}
+// by a key of SG_NSEL_*: k10_keys over the node rows and, for a trend key, the window's node trend rows (behind its update)
+int launch_node_select_by(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
+                          u64 cap, u64* d_n) {
+    return launch_node_select(e, st, slot, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+        if (by != SG_NSEL_SCORE && e->ntrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->ntrend.ev, 0));
+        const sg_node_trend* tr = by != SG_NSEL_SCORE ? e->ntrend.rows[slot] : nullptr;
+        hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, (const sg_node_out*)e->nodes.rows[slot], (const u64*)e->nodes.count[slot], tr, by, e->nsel.ctr);
+        return (int)SG_OK;
+    }, [](const SelArgs&, dim3) {});
+}
+// by the culprit rank: k11_keys over the window's rank rows (behind its ranking); d_rank (may be NULL) gets the selected rank rows
+int launch_rank_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_share, sg_node_out* d_out, sg_node_rank* d_rank, u32* d_index,
+                       u64 cap, u64* d_n) {
+    const sg_node_rank* rk = e->rank.rows[slot];
+    return launch_node_select(e, st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+        if (e->rank.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->rank.ev, 0));
+        hipLaunchKernelGGL(k11_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, rk, (const u64*)e->nodes.count[slot], e->nsel.ctr);
+        return (int)SG_OK;
+    }, [&](const SelArgs& a, dim3 grid) {
+        if (d_rank) hipLaunchKernelGGL(k11_gather_sel, grid, dim3(256), 0, st, rk, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_rank);
+    });
+}
+// the host form of a node selection over the last read window (sg_window_nodes_top, sg_window_rank_top): launch(out_stage,
+// rank_stage, cap, d_n) enqueues it on the read stream; the selected rows, rank rows and indices come back, then the counts
+template <class L>
+int node_top_host(sg_engine* e, L launch, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap, size_t* n_selected,
+                  size_t* n_nodes) {
+    if (const int rc = nsel_reserve(e)) return rc;
+    sg_engine::NSel& s = e->nsel;
+    const u64 NC = std::max<u32>(e->d.ncap, 1);
+    const u64 stage = std::min<u64>(cap, NC);
+    if (const int rc = launch(out ? s.stage : nullptr, rank_out ? e->rank.stage : nullptr, stage, s.n)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipMemcpyAsync(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    const u64 m = *s.h_n;
+    const size_t take = (size_t)std::min<u64>(m, stage);
+    if (out && take) HIP_TRY(e, hipMemcpyAsync(out, s.stage, take * sizeof(sg_node_out), hipMemcpyDeviceToHost, e->rd_stream));
+    if (rank_out && take) HIP_TRY(e, hipMemcpyAsync(rank_out, e->rank.stage, take * sizeof(sg_node_rank), hipMemcpyDeviceToHost, e->rd_stream));
+    if (node_index && take) HIP_TRY(e, hipMemcpyAsync(node_index, s.idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    if (n_selected) *n_selected = (size_t)m;
+    if (n_nodes) *n_nodes = (size_t)cnt;
     return SG_OK;
 }
 
@@ -2046,23 +2139,9 @@ int sg_window_nodes_top(sg_handle e, uint32_t by, uint32_t k, float min_value, s
     if (by > SG_NSEL_NEW) { e->err = "node selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
     if (e->closing || e->flush_open) { e->err = "sg_window_nodes_top while a flush is open"; return SG_ESTATE; }
     if (const int rc = check_nsel(e, by, e->cur)) return rc;
-    if (const int rc = nsel_reserve(e)) return rc;
-    sg_engine::NSel& s = e->nsel;
-    const u64 NC = std::max<u32>(e->d.ncap, 1);
-    const u64 stage = std::min<u64>(cap, NC);
-    if (const int rc = launch_node_select(e, e->rd_stream, e->cur, by, k, min_value, out ? s.stage : nullptr, nullptr, stage, s.n)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipMemcpyAsync(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    const u64 m = *s.h_n;
-    const size_t take = (size_t)std::min<u64>(m, stage);
-    if (out && take) HIP_TRY(e, hipMemcpyAsync(out, s.stage, take * sizeof(sg_node_out), hipMemcpyDeviceToHost, e->rd_stream));
-    if (node_index && take) HIP_TRY(e, hipMemcpyAsync(node_index, s.idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    if (n_selected) *n_selected = (size_t)m;
-    if (n_nodes) *n_nodes = (size_t)cnt;
-    return SG_OK;
+    return node_top_host(e, [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
+        return launch_node_select_by(e, e->rd_stream, e->cur, by, k, min_value, d_out, nullptr, stage, d_n);
+    }, out, nullptr, node_index, cap, n_selected, n_nodes);
 }
 int sg_window_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out, uint32_t* d_index, size_t cap,
                            uint64_t* d_n, void* stream) {
@@ -2072,7 +2151,107 @@ int sg_window_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min_value
     if (const int rc = check_nsel(e, by, slot)) return rc;
     if (const int rc = nsel_reserve(e)) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
-    return launch_node_select(e, s, slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return launch_node_select_by(e, s, slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
+}
+
+// ---- K11, the culprit ranking ---------------------------------------------------------------------------------------------------
+int sg_set_rank(sg_handle e, const sg_rank_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->nodes.on) { e->err = "sg_set_rank: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_rank while a flush is open"; return SG_ESTATE; }
+    sg_rank_params q{};
+    if (p && sgplan::check_rank(*p, &q)) { e->err = "sg_set_rank: bad parameters"; return SG_EINVAL; }
+    free_rank(e);
+    if (!p) return SG_OK;
+    sg_engine::Rank& r = e->rank;
+    const u32 slots = (u32)std::max<size_t>(e->slots.size(), 1);
+    r.p = q;
+    r.plan = sgplan::plan_rank(e->cfg.max_edges, e->nodes.plan.ncap, slots);
+    const sgplan::RankPlan& P = r.plan;
+    HIP_TRY(e, lds_limit(P.lds_bytes, k11_edge<true>, k11_edge<false>));
+    HIP_TRY(e, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &r.mem, P.total_bytes, "sg_set_rank", [e] { free_rank(e); })) return rc;
+    char* b = r.mem;                                                  // (every piece is 256-aligned)
+    r.W = (u64*)b; b += P.node_bytes; r.R = (u64*)b; b += P.node_bytes; r.base = (u64*)b; b += P.node_bytes; r.t = (u64*)b; b += P.node_bytes;
+    r.part = (u64*)b; b += P.part_bytes;
+    r.seed_sum = (u64*)b; b += P.seed_bytes;
+    r.src = (u32*)b; b += P.row_bytes; r.dst = (u32*)b; b += P.row_bytes; r.w = (u32*)b; b += P.row_bytes;
+    r.stage = (sg_node_rank*)b; b += P.stage_bytes;
+    r.stage_idx = (u32*)b; b += P.stage_idx_bytes;
+    for (u32 k = 0; k < slots; k++) { r.rows.push_back((sg_node_rank*)b); b += P.rows_bytes; }
+    r.valid.assign(slots, 0);
+    r.on = true;
+    return SG_OK;
+}
+int sg_window_rank(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_rank* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::Rank& r = e->rank;
+    if (!r.on) { e->err = "sg_window_rank: the ranking is off (sg_set_rank)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_window_rank while a flush is open"; return SG_ESTATE; }
+    if (!r.valid[e->cur]) { e->err = "sg_window_rank: the last read window was closed while the ranking was off"; return SG_ESTATE; }
+    if (r.pending) HIP_TRY(e, hipEventSynchronize(r.ev));
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const size_t N = (size_t)cnt;
+    const sg_node_rank* src = r.rows[e->cur];
+    if (!node_index) {
+        if (n) *n = N;
+        const size_t take = std::min(N, cap);
+        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(sg_node_rank), hipMemcpyDeviceToHost));
+        return SG_OK;
+    }
+    for (size_t k = 0; k < n_index; k++) if (node_index[k] >= N) { e->err = "sg_window_rank: a node index beyond the window's nodes"; return SG_EINVAL; }
+    if (n) *n = n_index;
+    const size_t take = std::min(n_index, cap), chunk = std::max<size_t>(r.plan.ncap, 1);
+    if (!out) return SG_OK;
+    for (size_t o = 0; o < take; o += chunk) {                        // (the staging holds ncap rows: a longer index goes in pieces)
+        const size_t m = std::min(chunk, take - o);
+        HIP_TRY(e, hipMemcpyAsync(r.stage_idx, node_index + o, m * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
+        hipLaunchKernelGGL(k11_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)r.stage_idx, (u64)m, r.stage);
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipMemcpyAsync(out + o, r.stage, m * sizeof(sg_node_rank), hipMemcpyDeviceToHost, e->rd_stream));
+        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    }
+    return SG_OK;
+}
+int sg_window_rank_buffer(sg_handle e, void** d_rank) {
+    if (!e || !d_rank) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Rank& r = e->rank;
+    if (!r.on) { e->err = "sg_window_rank_buffer: the ranking is off (sg_set_rank)"; return SG_ESTATE; }
+    const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
+    if (!r.valid[slot]) { e->err = "sg_window_rank_buffer: the window was closed while the ranking was off"; return SG_ESTATE; }
+    *d_rank = r.rows[slot];
+    return SG_OK;
+}
+namespace {
+int check_rsel(sg_engine* e, int slot) {
+    if (!e->nodes.on) { e->err = "rank selection: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
+    if (!e->rank.on) { e->err = "rank selection: the ranking is off (sg_set_rank)"; return SG_ESTATE; }
+    if (!e->nodes.valid[slot] || !e->rank.valid[slot]) { e->err = "rank selection: the window was closed while the ranking was off"; return SG_ESTATE; }
+    return SG_OK;
+}
+}  // namespace
+int sg_window_rank_top(sg_handle e, uint32_t k, float min_share, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap,
+                       size_t* n_selected, size_t* n_nodes) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->closing || e->flush_open) { e->err = "sg_window_rank_top while a flush is open"; return SG_ESTATE; }
+    if (const int rc = check_rsel(e, e->cur)) return rc;
+    return node_top_host(e, [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
+        return launch_rank_select(e, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
+    }, out, rank_out, node_index, cap, n_selected, n_nodes);
+}
+int sg_window_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n, void* stream) {
+    if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
+    if (const int rc = check_rsel(e, slot)) return rc;
+    if (const int rc = nsel_reserve(e)) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
+    return launch_rank_select(e, s, slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.

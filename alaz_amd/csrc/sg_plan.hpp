@@ -606,6 +606,61 @@ inline TrendPlan plan_node_trend(u32 ncap, u32 slots, const sg_trend_params& p) 
     return plan_baseline(p, 2 * (u64)ncap, std::max<u64>(ncap, 1) * sizeof(sg_node_trend), slots);
 }
 
+// K11, the culprit ranking (sg_rank.h): parameters and the device memory sg_set_rank allocates — never sg_create or sg_set_nodes.
+// Work is in K9's node-key space (ncap).  k11_edge takes a grid of node ranges of 16 384 (128 KiB of u64 accumulators in LDS) x
+// row slices — about 32 K rows per slice, at most 32 slices and at most 256 workgroups (each writes a 128 KiB partial per pass,
+// and a range's workgroups scan every row of their slice: many ranges take fewer slices); k11_prep and k11_node run a grid-stride
+// grid of 256-thread workgroups, at most 1024 (k11_node sums one seed sum per k11_prep workgroup).  The scratch is shared by the
+// window slots; each slot keeps its rank rows; one staging block serves sg_window_rank's index form and sg_window_rank_top.
+constexpr u32 kRankThreads = 256, kRankRangeNodes = 16384, kRankMaxSlices = 32, kRankSliceRows = 32768, kRankMaxEdgeWgs = 256,
+              kRankMaxWgs = 1024, kRankMaxIters = 64, kRankDefaultIters = 20, kRankDefaultDamping = 218;
+// SG_OK and *out = p with every 0 replaced by its default, or SG_EINVAL
+inline int check_rank(const sg_rank_params& p, sg_rank_params* out) {
+    if (p.struct_size != sizeof(sg_rank_params) || p.reserved != 0 || p.iters > kRankMaxIters || p.damping_q8 > 255 ||
+        p.seed > SG_RANK_SEED_UNIFORM) return SG_EINVAL;
+    sg_rank_params r = p;
+    if (!r.iters) r.iters = kRankDefaultIters;
+    if (!r.damping_q8) r.damping_q8 = kRankDefaultDamping;
+    *out = r;
+    return SG_OK;
+}
+struct RankPlan {
+    u32 ncap = 0;
+    u32 ranges = 0, slices = 0;   // k11_edge's grid = ranges x slices
+    u32 prep_wgs = 0;             // k11_prep: grid-stride over max(max_edges, ncap)
+    u32 node_wgs = 0;             // k11_node: grid-stride over ncap
+    u64 row_bytes = 0;            // one per-row u32 array [max_edges] (src, dst, w: three of them)
+    u64 node_bytes = 0;           // one per-node-key u64 array [ncap] (W, R, base, t: four of them)
+    u64 part_bytes = 0;           // [ranges][slices][16384] u64
+    u64 seed_bytes = 0;           // [1024] u64
+    u64 stage_bytes = 0;          // [ncap] sg_node_rank staging
+    u64 stage_idx_bytes = 0;      // [ncap] u32 staging
+    u64 rows_bytes = 0;           // one window slot's rank rows: [ncap] sg_node_rank
+    u64 lds_bytes = 0;            // k11_edge's dynamic LDS
+    u64 total_bytes = 0;          // the scratch, the staging and every slot's rows, each 256-byte aligned
+};
+inline RankPlan plan_rank(u64 max_edges, u32 ncap, u32 slots) {
+    RankPlan r;
+    const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(ncap, 1);
+    r.ncap = ncap;
+    r.ranges = (u32)((NC + kRankRangeNodes - 1) / kRankRangeNodes);
+    r.slices = (u32)std::max<u64>(1, std::min<u64>(kRankMaxSlices, (ME + kRankSliceRows - 1) / kRankSliceRows));
+    r.slices = std::max<u32>(1, std::min<u32>(r.slices, kRankMaxEdgeWgs / std::max<u32>(r.ranges, 1)));
+    r.prep_wgs = (u32)std::max<u64>(1, std::min<u64>(kRankMaxWgs, (std::max(ME, NC) + 4 * kRankThreads - 1) / (4 * kRankThreads)));
+    r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kRankMaxWgs, (NC + kRankThreads - 1) / kRankThreads));
+    r.row_bytes = trend_align(ME * 4);
+    r.node_bytes = trend_align(NC * 8);
+    r.part_bytes = trend_align((u64)r.ranges * r.slices * kRankRangeNodes * 8);
+    r.seed_bytes = trend_align((u64)kRankMaxWgs * 8);
+    r.stage_bytes = trend_align(NC * sizeof(sg_node_rank));
+    r.stage_idx_bytes = trend_align(NC * 4);
+    r.rows_bytes = trend_align(NC * sizeof(sg_node_rank));
+    r.lds_bytes = (u64)kRankRangeNodes * 8;
+    r.total_bytes = 3 * r.row_bytes + 4 * r.node_bytes + r.part_bytes + r.seed_bytes + r.stage_bytes + r.stage_idx_bytes +
+                    (u64)std::max<u32>(slots, 1) * r.rows_bytes;
+    return r;
+}
+
 // the plan's share of the kernels' argument (Dev, sg_device.h; a template so that the CPU test can fill a struct of the same names)
 template <class D>
 void plan_to_dev(const Plan& p, const sg_config& cfg, D& d) {

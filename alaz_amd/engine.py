@@ -49,6 +49,7 @@ EXPORTS = [
     "sg_flush_window_top_by", "sg_flush_end_top_by", "sg_window_select_by",
     "sg_set_node_trend", "sg_window_node_trend", "sg_window_node_trend_buffer", "sg_node_trend_entries", "sg_node_trend_stats_get",
     "sg_window_nodes_top", "sg_window_nodes_select",
+    "sg_set_rank", "sg_window_rank", "sg_window_rank_buffer", "sg_window_rank_top", "sg_window_rank_select",
 ]
 
 #: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
@@ -62,6 +63,12 @@ NODE_DTYPE = np.dtype([(f"{side}_{f}", "<u8") for f in ("count", "err", "sum_ns"
 #: sg_node_trend (32 bytes) of include/servicegraph.h: one node row's two sides against the node baseline (K10)
 NODE_TREND_DTYPE = np.dtype([(f, "<f4") for f in ("in_lat_dev", "in_err_dev", "out_lat_dev", "out_err_dev", "in_base_mean_us", "out_base_mean_us")]
                             + [("in_seen", "<u4"), ("out_seen", "<u4")])
+#: sg_node_rank (16 bytes) of include/servicegraph.h: one node row's culprit rank (K11); share = rank * 2^-56
+RANK_DTYPE = np.dtype([("rank", "<u8"), ("ref", "<u4"), ("share", "<f4")])
+#: SG_RANK_SEED_*: where the walk restarts
+RANK_SEED = dict(score=0, uniform=1)
+#: sg_rank_params defaults (a 0 in the struct means the same: iters 20, damping_q8 218)
+RANK_DEFAULTS = dict(iters=0, damping_q8=0, seed="score", seed_min_score=0.0)
 #: sg_edge_vanished (64 bytes) of include/servicegraph.h: one baseline entry that went silent (K8's vanished list)
 VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
                            ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4"), ("row", "<u4"), ("reserved", "<u4")])
@@ -122,6 +129,11 @@ class SgTrendParams(C.Structure):
 
 class SgVanishedParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("silent_windows", C.c_uint32), ("min_seen", C.c_uint32), ("max_rows", C.c_uint32)]
+
+
+class SgRankParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iters", C.c_uint32), ("damping_q8", C.c_uint32), ("seed", C.c_uint32),
+                ("seed_min_score", C.c_float), ("reserved", C.c_uint32)]
 
 
 class SgTrendStats(C.Structure):
@@ -230,6 +242,10 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_node_trend_stats_get": (C.c_int, [H, P]),
         "sg_window_nodes_top": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
         "sg_window_nodes_select": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, P, P]),
+        "sg_set_rank": (C.c_int, [H, P]), "sg_window_rank": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
+        "sg_window_rank_buffer": (C.c_int, [H, C.POINTER(C.c_void_p)]),
+        "sg_window_rank_top": (C.c_int, [H, u32, C.c_float, P, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "sg_window_rank_select": (C.c_int, [H, u32, C.c_float, P, P, sz, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -627,6 +643,64 @@ class ServiceGraph:
         window's stream)."""
         self._ck(self._l.sg_window_nodes_select(self._h, self._nby(by), k, min_value, d_out or None, d_index or None, cap, d_n,
                                                 stream or None))
+
+    # ---- culprit ranking (K11): a walk over the window's own graph, mass piling up where the anomalous rows stop ----
+    def set_rank(self, params: Optional[dict] = (), **kw):
+        """Switch the per-window culprit ranking on (sg_set_rank; iters, damping_q8, seed ("score" / "uniform" or SG_RANK_SEED_*),
+        seed_min_score as keywords or a dict — see RANK_DEFAULTS; needs the node rollup on) or off: set_rank(None)."""
+        if params is None:
+            if kw:
+                raise TypeError("set_rank(None) switches the ranking off and takes no parameters")
+            self._ck(self._l.sg_set_rank(self._h, None))
+            return
+        v = dict(RANK_DEFAULTS)
+        v.update(params or {}); v.update(kw)
+        unknown = set(v) - set(RANK_DEFAULTS) - {"struct_size", "reserved"}
+        if unknown:
+            raise TypeError(f"unknown rank parameters: {sorted(unknown)}")
+        seed = v["seed"]
+        if isinstance(seed, str):
+            if seed not in RANK_SEED:
+                raise ValueError(f"seed must be one of {sorted(RANK_SEED)}, not {seed!r}")
+            seed = RANK_SEED[seed]
+        p = SgRankParams(v.get("struct_size", C.sizeof(SgRankParams)), v["iters"], v["damping_q8"], seed, v["seed_min_score"],
+                         v.get("reserved", 0))
+        self._ck(self._l.sg_set_rank(self._h, C.byref(p)))
+
+    def window_rank(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """RANK_DTYPE rows of the last read window (sg_window_rank), row k for node row k of window_nodes(); or the rows of the
+        nodes at `index` (only those cross PCIe)."""
+        return self._window_rows(self._l.sg_window_rank, RANK_DTYPE, index)
+
+    def rank_buffer(self) -> int:
+        """device pointer of the sg_node_rank rows of the window window_run closed last (sg_window_rank_buffer)"""
+        p = C.c_void_p()
+        self._ck(self._l.sg_window_rank_buffer(self._h, C.byref(p)))
+        return p.value
+
+    def window_rank_top(self, k: int, min_share: float = float("-inf"), cap: Optional[int] = None):
+        """(node rows, rank rows, node indices, n_nodes) of a selection over the last read window's rank rows
+        (sg_window_rank_top): k = 0 every node with rank >= 2^24 and share >= min_share in node order, else the k highest such,
+        descending, ties by node position.  cap defaults to k (k > 0) or the window's node count."""
+        if cap is None:
+            if k:
+                cap = k
+            else:
+                n = C.c_size_t(0)
+                self._ck(self._l.sg_window_nodes(self._h, None, 0, C.byref(n)))
+                cap = n.value
+        out = np.zeros(cap, dtype=NODE_DTYPE); rk = np.zeros(cap, dtype=RANK_DTYPE); idx = np.zeros(cap, dtype=np.uint32)
+        ns, nn = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._l.sg_window_rank_top(self._h, k, min_share, out.ctypes.data, rk.ctypes.data, idx.ctypes.data, cap,
+                                            C.byref(ns), C.byref(nn)))
+        m = min(ns.value, cap)
+        return out[:m], rk[:m], idx[:m], nn.value
+
+    def window_rank_select(self, k: int, min_share: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
+        """Select from the rank rows of the window window_run closed last into device memory (sg_window_rank_select): d_out [cap]
+        node rows (0 = none), d_index [cap] u32 (0 = none), d_n one u64 = nodes selected; enqueued on `stream` (0 = that window's
+        stream)."""
+        self._ck(self._l.sg_window_rank_select(self._h, k, min_share, d_out or None, d_index or None, cap, d_n, stream or None))
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

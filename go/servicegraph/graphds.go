@@ -673,6 +673,92 @@ func (g *GraphDS) FlushWindow(windowEndMs int64) ([]EdgeRow, error) {
 	return out, nil
 }
 
+// ---- culprit ranking (K11) ---------------------------------------------------------------------------------------------
+
+// Culprit is one service of a window's culprit ranking: Share of the walk's mass that ended at it (sg_node_rank.share), and the
+// node's own score from the rollup.
+type Culprit struct {
+	Type, UID string
+	Share     float32
+	Score     float32
+}
+
+// SetRank switches the per-window culprit ranking on (the node rollup with it): a walk over each window's own graph, caller to
+// callee along anomalous rows; iters and dampingQ8 0 = the defaults (20, 218).  ClearRank switches it off and keeps the rollup.
+func (g *GraphDS) SetRank(iters, dampingQ8 uint32, uniformSeed bool) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	if rc := C.sg_set_nodes(g.h, 1); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_nodes = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	var rp C.sg_rank_params
+	rp.struct_size = C.uint32_t(unsafe.Sizeof(rp))
+	rp.iters, rp.damping_q8, rp.seed = C.uint32_t(iters), C.uint32_t(dampingQ8), C.SG_RANK_SEED_SCORE
+	if uniformSeed {
+		rp.seed = C.SG_RANK_SEED_UNIFORM
+	}
+	if rc := C.sg_set_rank(g.h, &rp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_rank = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func (g *GraphDS) ClearRank() {
+	g.flushMu.Lock()
+	C.sg_set_rank(g.h, nil)
+	g.flushMu.Unlock()
+}
+
+// WindowCulprits returns the k (1 <= k <= SG_SELECT_MAX_K) highest-ranked services of the window FlushWindow returned last,
+// descending, with share >= minShare (sg_window_rank_top: only they cross PCIe).
+func (g *GraphDS) WindowCulprits(k uint32, minShare float32) ([]Culprit, error) {
+	if k == 0 || k > C.SG_SELECT_MAX_K {
+		return nil, fmt.Errorf("servicegraph: culprits k = %d outside 1..SG_SELECT_MAX_K", k)
+	}
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	nodes := make([]C.sg_node_out, int(k))
+	ranks := make([]C.sg_node_rank, int(k))
+	var nsel, nn C.size_t
+	if rc := C.sg_window_rank_top(g.h, C.uint32_t(k), C.float(minShare), &nodes[0], &ranks[0], nil, C.size_t(k), &nsel, &nn); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_rank_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if nsel > C.size_t(k) {
+		nsel = C.size_t(k)
+	}
+	var nob C.size_t
+	C.sg_window_outbound_ips(g.h, nil, 0, &nob)
+	obips := make([]uint32, int(nob))
+	if nob > 0 {
+		C.sg_window_outbound_ips(g.h, (*C.uint32_t)(unsafe.Pointer(&obips[0])), nob, &nob)
+	}
+	g.lblMu.RLock()
+	names := g.names
+	g.lblMu.RUnlock()
+	out := make([]Culprit, int(nsel))
+	g.idMu.Lock()
+	for i := range out {
+		ref := uint32(ranks[i].ref)
+		t, v := ref>>30, ref&0x3FFFFFFF
+		o := &out[i]
+		o.Type, o.UID = "unknown", ""
+		switch {
+		case t == C.SG_REF_KNOWN && int(v) < len(g.uidOf):
+			o.Type, o.UID = "pod", g.uidOf[v]
+			if g.kindOf[v] == kindService {
+				o.Type = "service"
+			}
+		case t == C.SG_REF_LABEL && int(v) < len(names):
+			o.Type, o.UID = "outbound", names[v]
+		case t == C.SG_REF_OBIP && int(v) < len(obips):
+			o.Type, o.UID = "outbound", ipString(obips[v])
+		}
+		o.Share, o.Score = float32(ranks[i].share), float32(nodes[i].score)
+	}
+	g.idMu.Unlock()
+	return out, nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

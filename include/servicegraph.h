@@ -507,6 +507,63 @@ int sg_window_nodes_top(sg_handle h, uint32_t by, uint32_t k, float min_value, s
 int sg_window_nodes_select(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out,
                            uint32_t* d_index, size_t cap, uint64_t* d_n, void* stream);
 
+/* ---- culprit ranking (K11): each window's likely root-cause services, by a walk over the window's own graph, on the device ---- *
+ * Opt-in (sg_set_rank, on an engine with the node rollup); without it nothing is computed or allocated, and every other row is
+ * the same either way.  A random walk with restart over the window's rows, stepping from caller to callee with probability
+ * proportional to the row's anomaly: mass drains downstream along anomalous rows and piles up where they stop.  Integer
+ * arithmetic only (u64, every intermediate below 2^64), so the result has one correct value.
+ * Over the window's rows j = 0 .. E-1 (canonical order) and its node rows v = 0 .. n-1 (sg_window_nodes order):
+ *   q16(s)  = s > 0 ? min((uint32_t)(s * 65536.0f), 65536) : 0      (NaN: 0; the product is exact, the conversion truncates)
+ *   w_j     = 1 + q16(score_j) for every row (alive-only rows too);  W_u = sum of w_j over the rows with from_ref == u
+ *   seed    SG_RANK_SEED_SCORE: a_v = node.score >= seed_min_score ? q16(node.score) : 0;  SG_RANK_SEED_UNIFORM: a_v = 1;
+ *           A = sum of a_v; A == 0: the seed falls back to uniform (a_v = 1, A = n)
+ *   M = 2^56;  p_v = a_v * floor(M / A);  D = damping_q8 in 1..255 (0 = 218, i.e. 0.85);  R_v = (p_v >> 8) * (256 - D);  r_v = p_v
+ *   one iteration, `iters` times (1..64, 0 = 20; a fixed count, no convergence test):
+ *           m_u = (r_u >> 8) * D;  t_u = W_u ? floor(m_u / W_u) : 0;
+ *           r'_v = R_v + (m_v - t_v * W_v) + sum over the rows j with to_ref == v of t_{from_j} * w_j
+ *           (what the division does not hand out stays at u; a node without out-rows keeps all of m_u: it is a sink, where the
+ *           walk ends; a row with from_ref == to_ref is an ordinary row)
+ *   row v   rank = r_v after the last iteration, ref = the node row's ref, share = (float)((double)rank * 2^-56)
+ * Invariants: sum r' == sum R + sum m exactly, and sum r <= M; hence r_u <= 2^56, (r_u >> 8) * 255 < 2^56, t_u * w_j <= m_u, and
+ * W_u <= 65537 * E.  Selection (K7 over the rank rows): key min(rank >> 24, 0xFFFFFFFF), key 0 is not a candidate, share >=
+ * min_share as a plain float comparison (NaN never), k = 0 every candidate in node order, 1 <= k <= SG_SELECT_MAX_K the highest
+ * keys descending, ties by node position.  Every close path computes it (one call, begin + end, sg_window_run).              */
+#define SG_RANK_SEED_SCORE   0u
+#define SG_RANK_SEED_UNIFORM 1u
+typedef struct sg_rank_params {
+    uint32_t struct_size;       /* sizeof(sg_rank_params)                                       */
+    uint32_t iters;             /* 1..64; 0 = 20                                                */
+    uint32_t damping_q8;        /* 1..255; 0 = 218                                              */
+    uint32_t seed;              /* SG_RANK_SEED_*                                               */
+    float    seed_min_score;    /* SG_RANK_SEED_SCORE: nodes below it seed nothing              */
+    uint32_t reserved;          /* 0                                                            */
+} sg_rank_params;               /* 24 bytes */
+typedef struct sg_node_rank {
+    uint64_t rank;
+    uint32_t ref;
+    float    share;
+} sg_node_rank;                 /* 16 bytes, no padding */
+/* NULL = off (frees its memory); params = on.  Memory is allocated here, never at create.  SG_ESTATE when the node rollup is off
+ * or a flush is open, SG_EINVAL on bad params.  sg_set_nodes(h, 0) switches it off too.  Rank calls on an engine without it:
+ * SG_ESTATE.                                                                                                                 */
+int sg_set_rank(sg_handle h, const sg_rank_params* p);
+/* The rank rows of the last READ window (as sg_window_node_trend): node_index NULL: every node row, *n = nodes; else out[k] = the
+ * row of node node_index[k] (each < nodes, else SG_EINVAL), *n = n_index.  min(*n, cap) rows are written.  SG_ESTATE for a window
+ * closed while the ranking was off, and while a flush is open.                                                               */
+int sg_window_rank(sg_handle h, const uint32_t* node_index, size_t n_index, sg_node_rank* out, size_t cap, size_t* n);
+/* Device sg_node_rank[] of the window sg_window_run closed last (its count is sg_window_nodes_buffer's; valid until the slot is
+ * reused; read it on that window's stream).                                                                                  */
+int sg_window_rank_buffer(sg_handle h, void** d_rank);
+/* Selection over the rank rows of the last READ window, on the engine's read stream; returns when done.  out [cap] node rows
+ * (byte-identical to sg_window_nodes's), rank_out [cap] their rank rows, node_index [cap] their positions (each may be NULL);
+ * *n_selected = nodes selected (may exceed cap), *n_nodes = nodes of the window.  k > SG_SELECT_MAX_K: SG_EINVAL.             */
+int sg_window_rank_top(sg_handle h, uint32_t k, float min_share, sg_node_out* out, sg_node_rank* rank_out,
+                       uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
+/* Device-resident form over the window sg_window_run closed last: d_out [cap] node rows (may be NULL), d_index [cap] u32 (may be
+ * NULL), *d_n (u64) = nodes selected, enqueued on `stream` (NULL = the stream that window ran on), no host sync.                */
+int sg_window_rank_select(sg_handle h, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index,
+                          size_t cap, uint64_t* d_n, void* stream);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
