@@ -1,4 +1,6 @@
 // sg_k1_narrow.h — K1 resolve_aggregate, narrow-record form (the default of variant 0).  Included by sg_kernels.h.
+// What k1a_tile_partition shares with the other two pass-A kernels (join-blob staging, join, cache accumulate, statistics
+// line) is in sg_k1a_shared.h; here are the record format and what is this kernel's own: its fast path, P1-P4 and the copy-out.
 //
 // Same job as k1a_partition / k1b_merge (extractAddressPair + setFromToV2 + ReverseDirection + PersistRequest,
 // aggregator/data.go:1760-1767, 827-870; datastore/dto.go:226-231; backend.go:819-847), different exchange format:
@@ -126,15 +128,6 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
     // the general path and the overflow paths count) is added to the workgroup's LDS line where it happens — six registers less
     // across the fold
     u32 st_acc = 0; u64 st_tmin = ~0ull, st_tmax = 0;
-    auto lflush = [&](const K1Local& x) {
-        if (x.acc) { atomicAdd(&red[WS_ACCEPTED], (u64)x.acc); atomicMin(&red[WS_TMIN], x.tmin); atomicMax(&red[WS_TMAX], x.tmax); }
-        if (x.lost) atomicAdd(&red[WS_PAD], (u64)x.lost);
-        if (x.maxlabel) atomicMax(&red[WS_MAXLABEL], (u64)x.maxlabel);
-        if (x.dsrc) atomicAdd(&red[WS_DROPPED_SRC], (u64)x.dsrc);
-        if (x.dcap) atomicAdd(&red[WS_DROPPED_CAP], (u64)x.dcap);
-        if (x.misr) atomicAdd(&red[WS_MISROUTED], (u64)x.misr);
-    };
-#define K1T_LNEW(L) K1Local L; L.tmin = ~0ull; L.tmax = 0; L.maxlabel = L.dsrc = L.dcap = L.misr = L.acc = L.lost = 0
     const u32 nb = d.nb, nbmask = (1u << nb) - 1u, pshift = nb - d.pb, rbmask = (1u << d.rb) - 1u, bmask = CT / 2 - 1;
     const bool ck_any = d.ck_n != 0;
 
@@ -145,17 +138,12 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
           const uint4* q2 = pe + 2 * (j2 < (cend) ? j2 : (cfirst)); const uint4* q3 = pe + 2 * (j3 < (cend) ? j3 : (cfirst)); \
           gload16_issue(ea0, q0); gload16_issue(eb0, q0 + 1); gload16_issue(ea1, q1); gload16_issue(eb1, q1 + 1);   \
           gload16_issue(ea2, q2); gload16_issue(eb2, q2 + 1); gload16_issue(ea3, q3); gload16_issue(eb3, q3 + 1); }
-#define LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory")   /* LDS-only: does not drain the global stores */
     // cache fold of one accepted event whose bucket the caller has read (k0, k1); returns false when the event must travel
     auto cache_fold = [&](u32 bucket, u64 mk, u64 k0, u64 k1, u64 dur, u32 err) -> bool {
         int slot = k0 == mk ? (int)(2u * bucket) : (k1 == mk ? (int)(2u * bucket + 1u) : -1);
         if (slot < 0 && (k0 == SG_EKEY_EMPTY || k1 == SG_EKEY_EMPTY)) slot = cache_claim(ckey, bucket, mk, k0, k1);
         if (slot < 0) return false;
-        u64 ssq;
-        if ((dur >> 32) == 0) { const u32 us = div1000_u32((u32)dur); ssq = (u64)us * (u64)us; }
-        else { const u64 us = dur / 1000ull; ssq = us * us; }
-        atomicAdd(&cacc[slot * 4], 1ull | ((u64)err << 32)); atomicAdd(&cacc[slot * 4 + 1], dur);
-        atomicMax(&cacc[slot * 4 + 2], dur); atomicAdd(&cacc[slot * 4 + 3], ssq);
+        k1a_cache_add<false>(cacc, (u32)slot, dur, err);
         return true;
     };
     // The general path (rare events: open connections, raw-IP outbound destinations, IPs in both maps or in the residual
@@ -164,30 +152,26 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
     auto general = [&](const v4u_t va, const v4u_t vb, u32* bc, u32& slo, u32& shi, u32& spr) {
         spr = K1T_NONE;
         K1Ev e;
-        K1T_LNEW(L);
+        K1Local L;
         const bool ok = k1_resolve(d, make_uint4(va.x, va.y, va.z, va.w), make_uint4(vb.x, vb.y, vb.z, vb.w), L, e);
-        if (!ok) { lflush(L); return; }
+        if (!ok) { k1_red_add(red, L); return; }
         u32 Lm, Rm;
         sg_kmix(ci_of_ref(d, (u32)(e.key >> 32)), ci_of_ref(d, (u32)e.key), nbmask, &Lm, &Rm);
         const u32 part = Lm >> pshift;
         const u64 mk = ((u64)Lm << nb) | Rm;
-        if (e.alive) { emit_wide(d, fcw, w, part, mk, 0ull, 0u, 1u, L); lflush(L); return; }
+        if (e.alive) { emit_wide(d, fcw, w, part, mk, 0ull, 0u, 1u, L); k1_red_add(red, L); return; }
         const u32 bkt = Rm & bmask;
-        if (cache_fold(bkt, mk, lds_fresh_u64(&ckey[2 * bkt]), lds_fresh_u64(&ckey[2 * bkt + 1]), e.dur, e.err)) { lflush(L); return; }
-        if (e.dur >> 32) { emit_wide(d, fcw, w, part, mk, e.dur, e.err, 0u, L); lflush(L); return; }
+        if (cache_fold(bkt, mk, lds_fresh_u64(&ckey[2 * bkt]), lds_fresh_u64(&ckey[2 * bkt + 1]), e.dur, e.err)) { k1_red_add(red, L); return; }
+        if (e.dur >> 32) { emit_wide(d, fcw, w, part, mk, e.dur, e.err, 0u, L); k1_red_add(red, L); return; }
         const u32 rank = atomicAdd(&bc[part], 1u);
         slo = (u32)e.dur; shi = ((u32)mk & rbmask) | (e.err << 31); spr = part | (rank << K1T_RANK_SHIFT);
-        lflush(L);
+        k1_red_add(red, L);
     };
     constexpr u32 KSH = L2M == 2 ? 14u : 30u, IDM = L2M == 2 ? 0x3FFFu : 0x3FFFFFFFu;   // kind shift / id mask of a level-2 entry as this build reads it
-    auto join = [&](u32 ip) -> u32 {
-        const u32 b = ip >> 8;
-        const u64 e1 = l1[((__umul24(b, SG_JL1_K1)) >> 9) & d.jl1mask], e2 = l1[((__umul24(b, SG_JL1_K2)) >> 11) & d.jl1mask];
-        const u32 blk = (u32)e1 == b ? (u32)(e1 >> 32) : ((u32)e2 == b ? (u32)(e2 >> 32) : 0u);     // block 0 = the all-zero block
-        return L2M == 2 ? (u32)l2h[(blk << 8) | (ip & 255u)] : l2[(blk << 8) | (ip & 255u)];
-    };
+    auto join = [&](u32 ip) -> u32 { return k1a_join<L2M>(l1, l2, l2h, d.jl1mask, ip); };
     // The fast path, one event: branch-free join (two-level block table in LDS), data.go:827-870 as selects, key mix,
-    // read-only cache probe.  `rare` hands the event to the general path instead.
+    // read-only cache probe.  `rare` hands the event to the general path instead.  (The decision is written three times: here, in
+    // K1A_FAST of k1a_partition and in `front2` of k1a_team_partition — sg_k1a_shared.h says why; a rule changes in all three.)
     auto fast = [&](const u64 idx, const u64 cend, const v4u_t va, const v4u_t vb, u32* bc, bool& rare_out, u32& slo, u32& shi, u32& spr) {
         const bool inr = idx < cend;
         const u32 flags = va.w >> 24, label = va.z;
@@ -251,32 +235,9 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
         for (u32 k = t; k < CT; k += K1T_THREADS) ckey[k] = SG_EKEY_EMPTY;
         for (u32 k = t; k < CT * 4; k += K1T_THREADS) cacc[k] = 0;
         if (t < 8) red[t] = t == WS_TMIN ? ~0ull : 0ull;
-        // the join blob: six 16-byte loads per lane at most, issued and waited for in ONE asm statement (see k1a_partition: no
-        // code may sit between a hand-issued load and the wait that names its registers)
-        v4u_t jb0, jb1, jb2, jb3, jb4, jb5;
-        static_assert(K1A_NJ == 6, "written out for 6 blob words per lane");
-        const u32 n16 = d.jstage_bytes >> 4, n1 = (d.jl1mask + 1) >> 1;   // 16-byte words to stage; of them level 1 (always there)
-        const uint4* g1 = reinterpret_cast<const uint4*>(d.jl1); const uint4* g2 = reinterpret_cast<const uint4*>(d.jl2) - n1;
-#define K1T_JIDX(k) ((t + (k) * K1T_THREADS) < n16 ? (t + (k) * K1T_THREADS) : n16 - 1)
-#define K1T_JSRC(k) ((K1T_JIDX(k) < n1 ? g1 : g2) + K1T_JIDX(k))
-        const uint4* js0 = K1T_JSRC(0); const uint4* js1 = K1T_JSRC(1); const uint4* js2 = K1T_JSRC(2);
-        const uint4* js3 = K1T_JSRC(3); const uint4* js4 = K1T_JSRC(4); const uint4* js5 = K1T_JSRC(5);
-        asm volatile("global_load_dwordx4 %0, %6, off\n\tglobal_load_dwordx4 %1, %7, off\n\tglobal_load_dwordx4 %2, %8, off\n\t"
-                     "global_load_dwordx4 %3, %9, off\n\tglobal_load_dwordx4 %4, %10, off\n\tglobal_load_dwordx4 %5, %11, off\n\t"
-                     "s_waitcnt vmcnt(0)"
-                     : "=&v"(jb0), "=&v"(jb1), "=&v"(jb2), "=&v"(jb3), "=&v"(jb4), "=&v"(jb5)
-                     : "v"(js0), "v"(js1), "v"(js2), "v"(js3), "v"(js4), "v"(js5) : "memory");
-        // (level-1 words go in as they are; a level-2 word = four u32 entries kind << 30 | id -> four u16 entries kind << 14 | id)
-#define K1T_P16(x) ((((x) >> 30) << 14) | ((x) & 0x3FFFu))
-#define K1T_JST(k, r) { const u32 i_ = t + (k) * K1T_THREADS;                                                          \
-            if (i_ < n16) { if (L2M == 2 && i_ >= n1) reinterpret_cast<uint2*>(jl + n1)[i_ - n1] = make_uint2(K1T_P16((r).x) | (K1T_P16((r).y) << 16), K1T_P16((r).z) | (K1T_P16((r).w) << 16)); \
-                            else jl[i_] = make_uint4((r).x, (r).y, (r).z, (r).w); } }
-        K1T_JST(0, jb0); K1T_JST(1, jb1); K1T_JST(2, jb2); K1T_JST(3, jb3); K1T_JST(4, jb4); K1T_JST(5, jb5);
-#undef K1T_JST
-#undef K1T_P16
-#undef K1T_JSRC
-#undef K1T_JIDX
-        LDS_BARRIER();
+        // the join blob, behind the LDS set-up: k1a_stage_join's hand-issued loads tolerate no code between issue and wait
+        k1a_stage_join<K1T_THREADS, L2M>(d, jl, t);
+        lds_barrier();
         SG_STAMP(d, 0, 1);
     }
     // PACKB: the partition number rides in the free bits [rb, rb + pb) of a parked record's high word (2 nb <= 31): the copy-out
@@ -302,7 +263,7 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
                 const u32 pos = fcn[b] + (i - boff[b]);
                 const u64 out = (rec & 0xFFFFFFFFull) | ((u64)(hi & strip) << 32);
                 if (pos < d.sn) { if (!SG_ABL(d, 0x1u)) piece8(d, b, w)[pos] = out; }
-                else { K1T_LNEW(L); ovf8_single(d, b, ((u64)b << rb) | (hi & rbmask), rec & 0xFFFFFFFFull, hi >> 31, 0u, L); lflush(L); }
+                else { K1Local L; ovf8_single(d, b, ((u64)b << rb) | (hi & rbmask), rec & 0xFFFFFFFFull, hi >> 31, 0u, L); k1_red_add(red, L); }
             }
         }
     } else {
@@ -315,7 +276,7 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
                 const u64 rec = tile[off + j];
                 const u32 pos = pos0 + j;
                 if (pos < d.sn) { if (!SG_ABL(d, 0x1u)) dst[pos] = rec; }
-                else { K1T_LNEW(L); ovf8_single(d, b, ((u64)b << rb) | ((u32)(rec >> 32) & rbmask), rec & 0xFFFFFFFFull, (u32)(rec >> 63), 0u, L); lflush(L); }
+                else { K1Local L; ovf8_single(d, b, ((u64)b << rb) | ((u32)(rec >> 32) & rbmask), rec & 0xFFFFFFFFull, (u32)(rec >> 63), 0u, L); k1_red_add(red, L); }
             }
         }
     }
@@ -344,7 +305,7 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
             } else { pr4 = pr5 = pr6 = pr7 = K1T_NONE; lo4 = hi4 = lo5 = hi5 = lo6 = hi6 = lo7 = hi7 = 0; }
         }
         const u64 tk1 = SG_ABL(d, 0x100u) ? wall_clock64() : 0ull;
-        LDS_BARRIER();
+        lds_barrier();
         const u64 tk2 = SG_ABL(d, 0x100u) ? wall_clock64() : 0ull;
         tk_p1 += tk1 - tk0; tk_wait += tk2 - tk1;
         {   // P2: exclusive scan of the run lengths by EVERY wave (sixteen identical scans cost less than a barrier behind one: the
@@ -361,10 +322,7 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
                 u32 s = 0;
 #pragma unroll
                 for (u32 k = 0; k < 4; k++) { cq[k] = k < nq ? reinterpret_cast<const uint4*>(bc + b0)[k] : make_uint4(0u, 0u, 0u, 0u); s += cq[k].x + cq[k].y + cq[k].z + cq[k].w; }
-                u32 incl = s;                                        // inclusive scan over the 64 lanes: DPP row_shr 1, 2, 4, 8 (zero fill), then the row totals
-                incl += dpp32<0x111>(incl); incl += dpp32<0x112>(incl); incl += dpp32<0x114>(incl); incl += dpp32<0x118>(incl);
-                const u32 r0 = rdlane32(incl, 15), r1 = rdlane32(incl, 31), r2 = rdlane32(incl, 47);
-                incl += (lane >= 16 ? r0 : 0u) + (lane >= 32 ? r1 : 0u) + (lane >= 48 ? r2 : 0u);
+                const u32 incl = wave_incl_scan_u32(s, lane);
                 u32 run = incl - s;
 #pragma unroll
                 for (u32 k = 0; k < 4; k++) if (k < nq) {
@@ -381,10 +339,7 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
             } else {
                 u32 s = 0;
                 for (u32 k = 0; k < pl; k++) s += bc[b0 + k];
-                u32 incl = s;
-                incl += dpp32<0x111>(incl); incl += dpp32<0x112>(incl); incl += dpp32<0x114>(incl); incl += dpp32<0x118>(incl);
-                const u32 r0 = rdlane32(incl, 15), r1 = rdlane32(incl, 31), r2 = rdlane32(incl, 47);
-                incl += (lane >= 16 ? r0 : 0u) + (lane >= 32 ? r1 : 0u) + (lane >= 48 ? r2 : 0u);
+                const u32 incl = wave_incl_scan_u32(s, lane);
                 u32 run = incl - s;
                 for (u32 k = 0; k < pl; k++) {
                     const u32 c = bc[b0 + k]; boff[b0 + k] = run; run += c;
@@ -400,7 +355,7 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
         if constexpr (NSUB == 2) { K1T_DROP(lo4, hi4, pr4); K1T_DROP(lo5, hi5, pr5); K1T_DROP(lo6, hi6, pr6); K1T_DROP(lo7, hi7, pr7); }
 #undef K1T_DROP
         const u64 tk4 = SG_ABL(d, 0x100u) ? wall_clock64() : 0ull;
-        LDS_BARRIER();
+        lds_barrier();
         const u64 tk5 = SG_ABL(d, 0x100u) ? wall_clock64() : 0ull;
         havep = true; pcur = cur;
         if SG_ABL(d, 0x100u) { tk_scan += tk3 - tk2; tk_p3 += tk4 - tk3; tk_b3 += tk5 - tk4; }
@@ -411,10 +366,10 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
     if (SG_ABL(d, 0x100u) && t == 0 && blockIdx.x < 4096) { u64* g = d.dbg + ((size_t)2 * 4096 + blockIdx.x) * 8; g[0] = tk_p1; g[1] = tk_wait; g[2] = tk_scan; g[3] = tk_p3; g[4] = tk_b3; g[5] = tk_p4; }
 #undef K1T_ISSUE
 #undef K1T_FOLD
-    LDS_BARRIER();
+    lds_barrier();
     SG_STAMP(d, 0, 4);
     // flush the cache: a key seen once leaves as a single record, the others as aggregates
-    K1T_LNEW(L);
+    K1Local L;
     for (u32 s = t; s < CT; s += K1T_THREADS) {
         const u64 k = ckey[s];
         if (k == SG_EKEY_EMPTY) continue;
@@ -427,28 +382,18 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
         } else if ((x0 & 0xFFFFFFFFull) != 0ull) emit_agg8(d, fcw, w, part, k, x0, cacc[s * 4 + 1], cacc[s * 4 + 2], cacc[s * 4 + 3], L, first);
     }
     // workgroup statistics: wave reduce -> LDS -> one thread updates this workgroup's private line
-    lflush(L);
+    k1_red_add(red, L);
     {
         const u64 tmin = wave_min_u64(st_tmin), tmax = wave_max_u64(st_tmax);
         const u32 ac = wave_sum_u32(st_acc);
         if (lane == 0 && ac) { atomicMin(&red[WS_TMIN], tmin); atomicMax(&red[WS_TMAX], tmax); atomicAdd(&red[WS_ACCEPTED], (u64)ac); }
     }
-    LDS_BARRIER();
+    lds_barrier();
     for (u32 p = t; p < NP; p += K1T_THREADS) d.hdr8[(size_t)p * d.nwg + w] = make_uint2(fcn[p], fcw[p]);
     SG_STAMP(d, 0, 5);
-    if (t == 0) {
-        u64* g = d.wgstat + (size_t)(blockIdx.x % SG_MAX_K1_WGS) * WS_WORDS;
-        // accepted = counted by the lanes - dropped afterwards for capacity (a workgroup only drops what it accepted itself)
-        if (red[WS_ACCEPTED]) { atomicMin(&g[WS_TMIN], red[WS_TMIN]); atomicMax(&g[WS_TMAX], red[WS_TMAX]); atomicAdd(&g[WS_ACCEPTED], red[WS_ACCEPTED] - red[WS_PAD]); }
-        if (red[WS_MAXLABEL]) atomicMax(&g[WS_MAXLABEL], red[WS_MAXLABEL]);
-        if (red[WS_DROPPED_SRC]) atomicAdd(&g[WS_DROPPED_SRC], red[WS_DROPPED_SRC]);
-        if (red[WS_DROPPED_CAP]) atomicAdd(&g[WS_DROPPED_CAP], red[WS_DROPPED_CAP]);
-        if (red[WS_MISROUTED]) atomicAdd(&g[WS_MISROUTED], red[WS_MISROUTED]);
-    }
+    if (t == 0) k1_publish_wg(d, red);
     SG_STAMP(d, 0, 6);
     if (clk_me) { atomicAdd(&d.clk[0], __builtin_readcyclecounter() - clk_c0); atomicAdd(&d.clk[1], wall_clock64() - clk_r0); }
-#undef LDS_BARRIER
-#undef K1T_LNEW
 }
 
 // ---- pass B ---------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // sg_k1_team.h — K1 pass A: k1a_team_partition (round 4; one group per tile and sixteen waves since round 6).  Included by sg_kernels.h
-// behind sg_k1_narrow.h (whose record format, pieces, cache and emit_* helpers it shares).
+// behind sg_k1_narrow.h (whose record format, pieces, cache and emit_* helpers it shares); the join-blob staging, the cache accumulate
+// and the statistics line are the pass-A kernels' common code in sg_k1a_shared.h.
 //
 // Same job as k1a_tile_partition (extractAddressPair + setFromToV2 + ReverseDirection + the per-request PersistRequest,
 // aggregator/data.go:1760-1767, 827-870; datastore/dto.go:226-231; backend.go:819-847), built around what the counters and the
@@ -105,24 +106,14 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
     // statistics in registers: accepted events, their time-stamp range, drops for a non-pod source, largest label; what the general path and the
     // overflow paths count goes to the workgroup's LDS line where it happens
     u32 st_acc = 0, st_dsrc = 0, st_maxlabel = 0, st_misr = 0; u64 st_tmin = ~0ull, st_tmax = 0;
-    auto lflush = [&](const K1Local& x) {
-        if (x.acc) { atomicAdd(&red[WS_ACCEPTED], (u64)x.acc); atomicMin(&red[WS_TMIN], x.tmin); atomicMax(&red[WS_TMAX], x.tmax); }
-        if (x.lost) atomicAdd(&red[WS_PAD], (u64)x.lost);
-        if (x.maxlabel) atomicMax(&red[WS_MAXLABEL], (u64)x.maxlabel);
-        if (x.dsrc) atomicAdd(&red[WS_DROPPED_SRC], (u64)x.dsrc);
-        if (x.dcap) atomicAdd(&red[WS_DROPPED_CAP], (u64)x.dcap);
-        if (x.misr) atomicAdd(&red[WS_MISROUTED], (u64)x.misr);
-    };
-#define K1M_LNEW(L) K1Local L; L.tmin = ~0ull; L.tmax = 0; L.maxlabel = L.dsrc = L.dcap = L.misr = L.acc = L.lost = 0
     const u32 nb = d.nb, nbmask = (1u << nb) - 1u, pshift = nb - d.pb, rbmask = (1u << d.rb) - 1u, bmask = CT / 2 - 1, jm = d.jl1mask;
     const u32 max_known = d.max_known, max_labels = d.max_labels, sn = d.sn;
     const bool ck_any = d.ck_n != 0;
-#define K1M_WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory")   /* all 16 waves; LDS-only: does not drain the global stores */
     // The team barrier: a wave's own LDS operations are complete (lgkmcnt(0)), one lane adds 1 to the team's counter, every wave
     // polls it (one broadcast ds_read per trip) until all eight of this round have arrived.  The counter only grows.
     u32 bar_target = 0;
     auto team_barrier = [&]() {
-        if constexpr (TEAMS == 1) { K1M_WG_BARRIER(); return; }
+        if constexpr (TEAMS == 1) { lds_barrier(); return; }         // (one team = all 16 waves: the hardware barrier)
         bar_target += K1M_TW;
         asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
         if (lane == 0) __hip_atomic_fetch_add(mybar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -130,14 +121,6 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
         asm volatile("" : : : "memory");
     };
 
-    // cache fold of one accepted event into a slot it owns
-    auto cache_add = [&](u32 slot, u64 dur, u32 err) {
-        u64 ssq;
-        if ((dur >> 32) == 0) { const u32 us = div1000_u32((u32)dur); ssq = (u64)us * (u64)us; }
-        else { const u64 us = dur / 1000ull; ssq = us * us; }
-        atomicAdd(&cacc[slot * 4], 1ull | ((u64)err << 32)); atomicAdd(&cacc[slot * 4 + 1], dur);
-        atomicMax(&cacc[slot * 4 + 2], dur); atomicAdd(&cacc[slot * 4 + 3], ssq);
-    };
     // The general path (rare events: open connections, raw-IP outbound destinations, IPs in both maps or in the residual
     // cuckoo table, durations of 2^32 ns and more, labels out of range): the full join on the global tables, at the END of the event's tile
     // (where nothing of the batched fast path is live); the event is read again — it is rare and in L2.  Its record does not join the tile:
@@ -147,20 +130,20 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
         const uint4* q2 = pe + 2 * idx;
         const uint4 xa = q2[0], xb = q2[1];
         K1Ev e;
-        K1M_LNEW(L);
+        K1Local L;
         const bool ok = k1_resolve(d, xa, xb, L, e);
-        if (!ok) { lflush(L); return; }
+        if (!ok) { k1_red_add(red, L); return; }
         u32 Lm, Rm;
         sg_kmix(ci_of_ref(d, (u32)(e.key >> 32)), ci_of_ref(d, (u32)e.key), nbmask, &Lm, &Rm);
         const u32 part = Lm >> pshift;
         const u64 mk = ((u64)Lm << nb) | Rm;
-        if (e.alive) { emit_wide(d, fcw, w, part, mk, 0ull, 0u, 1u, L); lflush(L); return; }
+        if (e.alive) { emit_wide(d, fcw, w, part, mk, 0ull, 0u, 1u, L); k1_red_add(red, L); return; }
         const u32 bkt = Rm & bmask;
         const int slot = cache_claim(ckey, bkt, mk, lds_fresh_u64(&ckey[2 * bkt]), lds_fresh_u64(&ckey[2 * bkt + 1]));
-        if (slot >= 0) cache_add((u32)slot, e.dur, e.err);
+        if (slot >= 0) k1a_cache_add<false>(cacc, (u32)slot, e.dur, e.err);
         else if (e.dur >> 32) emit_wide(d, fcw, w, part, mk, e.dur, e.err, 0u, L);
         else emit_narrow_direct(d, fcn, w, part, (u32)mk & rbmask, (u32)e.dur, e.err, L);
-        lflush(L);
+        k1_red_add(red, L);
     };
     constexpr u32 KSH = L2M == 2 ? 14u : 30u, IDM = L2M == 2 ? 0x3FFFu : 0x3FFFFFFFu;   // kind shift / id mask of a level-2 entry as this build reads it
 
@@ -169,7 +152,8 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
 #define K1M_F_ERR 4u
     // ---- a PAIR of events: the batched fast path, in two halves -----------------------------------------------------
     // front: both joins (two-level block table in LDS: level 1 of all four addresses — eight independent ds_read_b64 —, then level 2),
-    //        data.go:827-870 as selects, error rule, time stamps, key mix.  Leaves per event: the mixed key halves, the duration's low word
+    //        data.go:827-870 as selects (the third copy of the decision beside K1A_FAST of k1a_partition and `fast` of k1a_tile_partition: a
+    //        rule changes in all three; sg_k1a_shared.h says why), error rule, time stamps, key mix.  Leaves per event: the mixed key halves, the duration's low word
     //        and three flag bits (a rare event is re-read from memory by the general path).
     // back:  cache bucket reads, claims (one ballot), the run ranks (unconditional returning adds of 0 or 1), folds, parked records.
     // (round 4 batched four events per step — four dependent LDS round trips per group of four — at 168 registers and twelve waves per
@@ -243,7 +227,7 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
 #pragma unroll
         for (int i = 0; i < 2; i++) rank[i] = atomicAdd(&bc[Lm[i] >> pshift], ((fl[i] & K1M_F_ACC) && slot[i] < 0) ? 1u : 0u);
 #pragma unroll
-        for (int i = 0; i < 2; i++) if ((fl[i] & K1M_F_ACC) && slot[i] >= 0) cache_add((u32)slot[i], (u64)dur[i], (fl[i] >> 2) & 1u);
+        for (int i = 0; i < 2; i++) if ((fl[i] & K1M_F_ACC) && slot[i] >= 0) k1a_cache_add<false>(cacc, (u32)slot[i], (u64)dur[i], (fl[i] >> 2) & 1u);
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             const bool travel = (fl[i] & K1M_F_ACC) && slot[i] < 0;
@@ -263,31 +247,9 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
         for (u32 k = t; k < CT * 4; k += K1M_THREADS) cacc[k] = 0;
         if (t < 8) red[t] = t == WS_TMIN ? ~0ull : 0ull;
         if (t < 16) bar[t] = 0u;
-        // the join blob: six 16-byte loads per lane at most, issued and waited for in ONE asm statement (no code may sit between a
-        // hand-issued load and the wait that names its registers)
-        v4u_t jb0, jb1, jb2, jb3, jb4, jb5;
-        static_assert(K1A_NJ == 6, "written out for 6 blob words per lane");
-        const u32 n16 = d.jstage_bytes >> 4, n1 = (d.jl1mask + 1) >> 1;   // 16-byte words to stage; of them level 1 (always there)
-        const uint4* g1 = reinterpret_cast<const uint4*>(d.jl1); const uint4* g2 = reinterpret_cast<const uint4*>(d.jl2) - n1;
-#define K1M_JIDX(k) ((t + (k) * K1M_THREADS) < n16 ? (t + (k) * K1M_THREADS) : n16 - 1)
-#define K1M_JSRC(k) ((K1M_JIDX(k) < n1 ? g1 : g2) + K1M_JIDX(k))
-        const uint4* js0 = K1M_JSRC(0); const uint4* js1 = K1M_JSRC(1); const uint4* js2 = K1M_JSRC(2);
-        const uint4* js3 = K1M_JSRC(3); const uint4* js4 = K1M_JSRC(4); const uint4* js5 = K1M_JSRC(5);
-        asm volatile("global_load_dwordx4 %0, %6, off\n\tglobal_load_dwordx4 %1, %7, off\n\tglobal_load_dwordx4 %2, %8, off\n\t"
-                     "global_load_dwordx4 %3, %9, off\n\tglobal_load_dwordx4 %4, %10, off\n\tglobal_load_dwordx4 %5, %11, off\n\t"
-                     "s_waitcnt vmcnt(0)"
-                     : "=&v"(jb0), "=&v"(jb1), "=&v"(jb2), "=&v"(jb3), "=&v"(jb4), "=&v"(jb5)
-                     : "v"(js0), "v"(js1), "v"(js2), "v"(js3), "v"(js4), "v"(js5) : "memory");
-#define K1M_P16(x) ((((x) >> 30) << 14) | ((x) & 0x3FFFu))
-#define K1M_JST(k, r) { const u32 i_ = t + (k) * K1M_THREADS;                                                          \
-            if (i_ < n16) { if (L2M == 2 && i_ >= n1) reinterpret_cast<uint2*>(jl + n1)[i_ - n1] = make_uint2(K1M_P16((r).x) | (K1M_P16((r).y) << 16), K1M_P16((r).z) | (K1M_P16((r).w) << 16)); \
-                            else jl[i_] = make_uint4((r).x, (r).y, (r).z, (r).w); } }
-        K1M_JST(0, jb0); K1M_JST(1, jb1); K1M_JST(2, jb2); K1M_JST(3, jb3); K1M_JST(4, jb4); K1M_JST(5, jb5);
-#undef K1M_JST
-#undef K1M_P16
-#undef K1M_JSRC
-#undef K1M_JIDX
-        K1M_WG_BARRIER();
+        // the join blob, behind the LDS set-up: k1a_stage_join's hand-issued loads tolerate no code between issue and wait
+        k1a_stage_join<K1M_THREADS, L2M>(d, jl, t);
+        lds_barrier();
         SG_STAMP(d, 0, 1);
     }
     // PACKB: the partition number rides in the free bits [rb, rb + pb) of a parked record's high word (2 nb <= 31): the copy-out
@@ -303,7 +265,7 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
     // piece bases and this tile's run counters are not written before that.
     // (a record beyond its piece's capacity goes to the window's overflow list: a rolled loop behind the copy, so that the eight
     // unrolled copies carry one compare each and no call-sized code)
-    auto ovf_record = [&](const u32 b, const u32 remv, const u32 dur, const u32 err) { const Dev& d = kd(); K1M_LNEW(L); ovf8_single(d, b, ((u64)b << d.rb) | remv, (u64)dur, err, 0u, L); lflush(L); };
+    auto ovf_record = [&](const u32 b, const u32 remv, const u32 dur, const u32 err) { const Dev& d = kd(); K1Local L; ovf8_single(d, b, ((u64)b << d.rb) | remv, (u64)dur, err, 0u, L); k1_red_add(red, L); };
     auto copy_out = [&](const u32 pc) {
         const u32* bc = bcnt + pc * NP;
         if (packb) {
@@ -442,10 +404,7 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
                 u32 s = 0;
 #pragma unroll
                 for (u32 k = 0; k < 4; k++) { cq[k] = k < nq ? reinterpret_cast<const uint4*>(bc + b0)[k] : make_uint4(0u, 0u, 0u, 0u); s += cq[k].x + cq[k].y + cq[k].z + cq[k].w; }
-                u32 incl = s;                                        // inclusive scan over the 64 lanes: DPP row_shr 1, 2, 4, 8 (zero fill), then the row totals
-                incl += dpp32<0x111>(incl); incl += dpp32<0x112>(incl); incl += dpp32<0x114>(incl); incl += dpp32<0x118>(incl);
-                const u32 r0 = rdlane32(incl, 15), r1 = rdlane32(incl, 31), r2 = rdlane32(incl, 47);
-                incl += (lanel >= 16 ? r0 : 0u) + (lanel >= 32 ? r1 : 0u) + (lanel >= 48 ? r2 : 0u);
+                const u32 incl = wave_incl_scan_u32(s, lanel);
                 u32 run = incl - s;
                 // (the owner's returning adds first, ALL in flight together — written behind each quad's offsets they were issued and
                 // waited for one by one: eight LDS round trips per tile in the scan of every owner lane)
@@ -472,10 +431,7 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
             } else {
                 u32 s = 0;
                 for (u32 k = 0; k < pl; k++) s += bc[b0 + k];
-                u32 incl = s;
-                incl += dpp32<0x111>(incl); incl += dpp32<0x112>(incl); incl += dpp32<0x114>(incl); incl += dpp32<0x118>(incl);
-                const u32 r0 = rdlane32(incl, 15), r1 = rdlane32(incl, 31), r2 = rdlane32(incl, 47);
-                incl += (lane >= 16 ? r0 : 0u) + (lane >= 32 ? r1 : 0u) + (lane >= 48 ? r2 : 0u);
+                const u32 incl = wave_incl_scan_u32(s, lane);
                 u32 run = incl - s;
                 for (u32 k = 0; k < pl; k++) {
                     const u32 c = bc[b0 + k]; boff[b0 + k] = run; run += c;
@@ -529,12 +485,12 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
     if (havep) copy_out(pcur);                                       // the last tile's runs
     SG_STAMP(d, 0, 3);
     if (stamp && tt == 0 && blockIdx.x < 2048) { u64* g = d.dbg + ((size_t)2 * 4096 + blockIdx.x * 2 + team) * 8; g[0] = tk_p1; g[1] = tk_wait; g[2] = tk_scan; g[3] = tk_p3; g[4] = tk_b3; g[5] = tk_p4; g[6] = tk_ld; g[7] = tk_fa; }
-    K1M_WG_BARRIER();
+    lds_barrier();
     SG_STAMP(d, 0, 4);
     // flush the cache: a key seen once leaves as a single record, the others as aggregates
     {
     const Dev& d = kd();                                             // (the epilogue's Dev fields are loaded here, not held across the tile loop)
-    K1M_LNEW(L);
+    K1Local L;
     for (u32 s = t; s < CT; s += K1M_THREADS) {
         const u64 k = ckey[s];
         if (k == SG_EKEY_EMPTY) continue;
@@ -547,7 +503,7 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
         } else if ((x0 & 0xFFFFFFFFull) != 0ull) emit_agg8(d, fcw, w, part, k, x0, cacc[s * 4 + 1], cacc[s * 4 + 2], cacc[s * 4 + 3], L, first);
     }
     // workgroup statistics: wave reduce -> LDS -> one thread updates this workgroup's private line
-    lflush(L);
+    k1_red_add(red, L);
     {
         const u64 tmin = wave_min_u64(st_tmin), tmax = wave_max_u64(st_tmax);
         const u32 ac = wave_sum_u32(st_acc), ds = wave_sum_u32(st_dsrc), mr = wave_sum_u32(st_misr);
@@ -559,21 +515,11 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
             if (ml) atomicMax(&red[WS_MAXLABEL], (u64)ml);
         }
     }
-    K1M_WG_BARRIER();
+    lds_barrier();
     for (u32 p = t; p < NP; p += K1M_THREADS) { const u32 c = fcn[p]; d.hdr8[(size_t)p * d.nwg + w] = make_uint2(c < sn ? c : sn, fcw[p]); }
     SG_STAMP(d, 0, 5);
-    if (t == 0) {
-        u64* g = d.wgstat + (size_t)(blockIdx.x % SG_MAX_K1_WGS) * WS_WORDS;
-        // accepted = counted by the lanes - dropped afterwards for capacity (a workgroup only drops what it accepted itself)
-        if (red[WS_ACCEPTED]) { atomicMin(&g[WS_TMIN], red[WS_TMIN]); atomicMax(&g[WS_TMAX], red[WS_TMAX]); atomicAdd(&g[WS_ACCEPTED], red[WS_ACCEPTED] - red[WS_PAD]); }
-        if (red[WS_MAXLABEL]) atomicMax(&g[WS_MAXLABEL], red[WS_MAXLABEL]);
-        if (red[WS_DROPPED_SRC]) atomicAdd(&g[WS_DROPPED_SRC], red[WS_DROPPED_SRC]);
-        if (red[WS_DROPPED_CAP]) atomicAdd(&g[WS_DROPPED_CAP], red[WS_DROPPED_CAP]);
-        if (red[WS_MISROUTED]) atomicAdd(&g[WS_MISROUTED], red[WS_MISROUTED]);
-    }
+    if (t == 0) k1_publish_wg(d, red);
     SG_STAMP(d, 0, 6);
     if (clk_me) { atomicAdd(&d.clk[0], __builtin_readcyclecounter() - clk_c0); atomicAdd(&d.clk[1], wall_clock64() - clk_r0); }
     }
-#undef K1M_WG_BARRIER
-#undef K1M_LNEW
 }

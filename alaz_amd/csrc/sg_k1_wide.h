@@ -1,5 +1,6 @@
 // sg_k1_wide.h — K1 with 16-byte records (k1a_partition + k1b_merge): small windows (BASELINE config 2), the per-edge histogram, k1_variant = 2
 // Part of the kernel translation unit: included by sg_kernels.h (which holds the shared helpers), in this order.
+// What pass A shares with the narrow forms (join-blob addresses and stores, join, cache accumulate, statistics line) is in sg_k1a_shared.h.
 #pragma once
 
 // ---- variant 0: partitioned aggregation, no device-scope atomics on the event path. --------------
@@ -12,16 +13,6 @@
 // Pass B (k1b_merge, at window close): one workgroup per partition merges its pieces in an LDS table and writes each
 // distinct edge once with plain stores.
 #define K1A_G       4         // events per thread per step
-
-// Issue a global load NOW and leave it in flight; a later s_waitcnt (inline asm that names the
-// destination registers as in/out operands) is the matching wait.  Written as inline asm because the
-// compiler puts waits between conditional loads.  vmcnt is in-order for loads, so the compiler's own
-// (unaware) waits can only become stronger, never too weak.  Rule: no loop-carried value and no branch
-// merge between an issue and its wait (a compiler-inserted register copy there would read a register that
-// is still being loaded).
-typedef u32 v4u_t __attribute__((ext_vector_type(4)));
-typedef u32 v2u_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void gload16_issue(v4u_t& dst, const void* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(dst) : "v"(p) : "memory"); }
 
 // Edge-key hash of both passes: 24-bit multiplies (full rate; a murmur finaliser is 4 quarter-rate 32-bit multiplies per
 // key).  Node refs are small integers plus two type bits at the top: the low 24 bits go through the multipliers, the two
@@ -49,8 +40,6 @@ __device__ __forceinline__ void ovf_append(const Dev& d, u32 p, u64 key, u64 a0,
     }
     else { const u32 c = (u32)(a0 & 0xFFFFFFFFull); L.dcap += c; L.lost += c; }     // (the aggregate may carry other lanes' events: not L.acc -= c)
 }
-// exact for every 32-bit duration: floor(x / 1000) = (x * 0x10624DD3) >> 38
-__device__ __forceinline__ u32 div1000_u32(u32 x) { return __umulhi(x, 0x10624DD3u) >> 6; }
 
 // piece (p, w): pslots 16-byte slots; fc[p] = n_single | n_aggregate << 20 is this workgroup's LDS counter for it
 __device__ __forceinline__ uint4* piece_of(const Dev& d, u32 p, u32 w) { return d.slab_s + ((size_t)p * d.nwg + w) * d.pslots; }
@@ -154,7 +143,7 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
           const uint4* q2 = pe + 2 * (j2 < end ? j2 : last); const uint4* q3 = pe + 2 * (j3 < end ? j3 : last);     \
           gload16_issue(ea0, q0); gload16_issue(eb0, q0 + 1); gload16_issue(ea1, q1); gload16_issue(eb1, q1 + 1);   \
           gload16_issue(ea2, q2); gload16_issue(eb2, q2 + 1); gload16_issue(ea3, q3); gload16_issue(eb3, q3 + 1); }
-    K1Local L; L.tmin = ~0ull; L.tmax = 0; L.maxlabel = L.dsrc = L.dcap = L.misr = L.acc = L.lost = 0;
+    K1Local L;
     const u32 pshift = 32u - (u32)__builtin_ctz(d.np), bmask = CT / 2 - 1;
     const bool ck_any = d.ck_n != 0;
 
@@ -168,7 +157,7 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
         const u32 bkt = (hk >> 5) & bmask;
         const int slot = cache_claim(ckey, bkt, e.key, lds_fresh_u64(&ckey[2 * bkt]), lds_fresh_u64(&ckey[2 * bkt + 1]));
         if (slot >= 0) {
-            const u64 us = e.dur / 1000ull;
+            const u64 us = e.dur / 1000ull;                          // (rare events only: one 64-bit divide, no 32-bit arm as in k1a_cache_add)
             atomicAdd(&cacc[slot * 4], 1ull | ((u64)e.err << 32)); atomicAdd(&cacc[slot * 4 + 1], e.dur);
             atomicMax(&cacc[slot * 4 + 2], e.dur); atomicAdd(&cacc[slot * 4 + 3], us * us);
             if (HIST) { const u32 b = hist_bin64(e.dur); atomicAdd(&chist[slot * 8 + (b >> 1)], 1u << ((b & 1u) * 16)); }
@@ -176,12 +165,9 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
     };
     // The fast path, one event: branch-free join (two-level block table in LDS), data.go:827-870 as selects, cheap hash,
     // read-only cache probe.  `rare` hands the event to the general path instead.
-    auto join = [&](u32 ip) -> u32 {
-        const u32 b = ip >> 8;
-        const u64 e1 = l1[((__umul24(b, SG_JL1_K1)) >> 9) & d.jl1mask], e2 = l1[((__umul24(b, SG_JL1_K2)) >> 11) & d.jl1mask];
-        const u32 blk = (u32)e1 == b ? (u32)(e1 >> 32) : ((u32)e2 == b ? (u32)(e2 >> 32) : 0u);     // block 0 = the all-zero block
-        return l2[(blk << 8) | (ip & 255u)];
-    };
+    // (The decision — rare, source must be a pod, Host label, reversal, shard, error, time stamp — is written THREE times: here, in
+    // `fast` of k1a_tile_partition and in `front2` of k1a_team_partition.  A rule changes in all three; sg_k1a_shared.h says why.)
+    auto join = [&](u32 ip) -> u32 { return k1a_join<1>(l1, l2, nullptr, d.jl1mask, ip); };
 #define K1A_FAST(idx, va, vb, rare_out)                                                                             \
         {   const bool inr = (idx) < end;                                                                           \
             const u32 flags = (va).w >> 24, label = (va).z;                                                         \
@@ -211,10 +197,7 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
             if SG_ABL(d, 0x2u) slot = -1;                                                                         \
             if (acc && !SG_ABL(d, 0x8u)) {                                                                        \
                 if (slot >= 0 && !SG_ABL(d, 0x4u)) {                                                              \
-                    const u32 us = div1000_u32(dur);                                                                \
-                    const u64 ssq = (u64)us * (u64)us;                        /* us < 2^23: 24-bit multiplies */             \
-                    atomicAdd(&cacc[slot * 4], 1ull | ((u64)err << 32)); atomicAdd(&cacc[slot * 4 + 1], (u64)dur);  \
-                    atomicMax(&cacc[slot * 4 + 2], (u64)dur); atomicAdd(&cacc[slot * 4 + 3], ssq);                  \
+                    k1a_cache_add<true>(cacc, (u32)slot, (u64)dur, err);      /* dur < 2^32: an event with more is rare */  \
                     if (HIST) { const u32 hb_ = hist_bin32(dur); atomicAdd(&chist[slot * 8 + (hb_ >> 1)], 1u << ((hb_ & 1u) * 16)); } \
                 } else emit_single(d, fc, w, part, key, (u64)dur, err, L);                                          \
             }                                                                                                       \
@@ -233,7 +216,6 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
                   const v4u_t vb = q == 0 ? eb0 : q == 1 ? eb1 : q == 2 ? eb2 : eb3;                                \
                   if (rq) general(va, vb);                                                                          \
               } } }
-#define LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory")   /* LDS-only: does not drain the global stores */
     {
         // piece counters: zero by definition in the first batch of a window (no loads); a later batch reads them with
         // ordinary loads BEFORE anything is issued by hand
@@ -250,10 +232,7 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
         // waited for inside the straight-line region that issued it, so the first group's real loads belong to the loop).
         v4u_t jb0, jb1, jb2, jb3, jb4, jb5; u32 pf;
         static_assert(K1A_NJ == 6, "written out for 6 blob words per lane");
-        const u32 n16 = d.jstage_bytes >> 4, n1 = (d.jl1mask + 1) >> 1;   // 16-byte words to stage; of them level 1 (always there)
-        const uint4* g1 = reinterpret_cast<const uint4*>(d.jl1); const uint4* g2 = reinterpret_cast<const uint4*>(d.jl2) - n1;
-#define K1A_JIDX(k) ((t + (k) * K1A_THREADS) < n16 ? (t + (k) * K1A_THREADS) : n16 - 1)
-#define K1A_JSRC(k) ((K1A_JIDX(k) < n1 ? g1 : g2) + K1A_JIDX(k))
+#define K1A_JSRC(k) k1a_join_src<K1A_THREADS>(d, t, k)
         const uint4* js0 = K1A_JSRC(0); const uint4* js1 = K1A_JSRC(1); const uint4* js2 = K1A_JSRC(2);
         const uint4* js3 = K1A_JSRC(3); const uint4* js4 = K1A_JSRC(4); const uint4* js5 = K1A_JSRC(5);
         const uint4* pf0 = pe + 2 * (i < end ? i : last); const uint4* pf1 = pe + 2 * (i + K1A_THREADS < end ? i + K1A_THREADS : last);
@@ -265,13 +244,12 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
                      "s_waitcnt vmcnt(4)"
                      : "=&v"(jb0), "=&v"(jb1), "=&v"(jb2), "=&v"(jb3), "=&v"(jb4), "=&v"(jb5), "=&v"(pf)
                      : "v"(js0), "v"(js1), "v"(js2), "v"(js3), "v"(js4), "v"(js5), "v"(pf0), "v"(pf1), "v"(pf2), "v"(pf3) : "memory");
-#define K1A_JST(k, r) if (t + (k) * K1A_THREADS < n16) jl[t + (k) * K1A_THREADS] = make_uint4((r).x, (r).y, (r).z, (r).w)
+#define K1A_JST(k, r) k1a_join_store<K1A_THREADS, 0>(d, jl, t, k, r)      /* (this form never packs level 2) */
         K1A_JST(0, jb0); K1A_JST(1, jb1); K1A_JST(2, jb2); K1A_JST(3, jb3); K1A_JST(4, jb4); K1A_JST(5, jb5);
 #undef K1A_JST
 #undef K1A_JSRC
-#undef K1A_JIDX
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(pf) : : "memory");
-        LDS_BARRIER();
+        lds_barrier();
         SG_STAMP(d, 0, 1);
     }
     for (; i < end; i += (u64)K1A_G * K1A_THREADS) {
@@ -283,7 +261,7 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
 #undef K1A_ISSUE
 #undef K1A_FOLD
 #undef K1A_FAST
-    LDS_BARRIER();
+    lds_barrier();
     SG_STAMP(d, 0, 4);
     // flush the cache, singles first (they share the singles region with the loop's records), then the aggregates
     for (u32 s = t; s < CT; s += K1A_THREADS) {
@@ -311,20 +289,11 @@ __global__ __launch_bounds__(K1A_THREADS) void k1a_partition(Dev d, const sg_eve
             if (mr) atomicAdd(&red[WS_MISROUTED], (u64)mr);
         }
     }
-    LDS_BARRIER();
+    lds_barrier();
     for (u32 p = t; p < d.np; p += K1A_THREADS) d.hdr[(size_t)p * d.nwg + w] = fc[p];
     SG_STAMP(d, 0, 5);
-    if (t == 0) {
-        u64* g = d.wgstat + (size_t)(blockIdx.x % SG_MAX_K1_WGS) * WS_WORDS;
-        // accepted = counted by the lanes - dropped afterwards for capacity (a workgroup only drops what it accepted itself)
-        if (red[WS_ACCEPTED]) { atomicMin(&g[WS_TMIN], red[WS_TMIN]); atomicMax(&g[WS_TMAX], red[WS_TMAX]); atomicAdd(&g[WS_ACCEPTED], red[WS_ACCEPTED] - red[WS_PAD]); }
-        if (red[WS_MAXLABEL]) atomicMax(&g[WS_MAXLABEL], red[WS_MAXLABEL]);
-        if (red[WS_DROPPED_SRC]) atomicAdd(&g[WS_DROPPED_SRC], red[WS_DROPPED_SRC]);
-        if (red[WS_DROPPED_CAP]) atomicAdd(&g[WS_DROPPED_CAP], red[WS_DROPPED_CAP]);
-        if (red[WS_MISROUTED]) atomicAdd(&g[WS_MISROUTED], red[WS_MISROUTED]);
-    }
+    if (t == 0) k1_publish_wg(d, red);
     SG_STAMP(d, 0, 6);
-#undef LDS_BARRIER
 }
 
 // Pass B.  Workgroup p owns partition p: it reads the record counts of its nwg pieces (one contiguous line of d.hdr),

@@ -92,10 +92,7 @@ __global__ __launch_bounds__(1024) void kc_prepare(Dev d, u64 n_known, u64 n_lab
         if (wave == 0) {                                             // class sizes -> first positions (four classes per lane)
             const uint4 v = reinterpret_cast<const uint4*>(hb)[lane];
             const u32 sum = v.x + v.y + v.z + v.w;
-            u32 incl = sum;
-            incl += dpp32<0x111>(incl); incl += dpp32<0x112>(incl); incl += dpp32<0x114>(incl); incl += dpp32<0x118>(incl);
-            const u32 r0 = rdlane32(incl, 15), r1 = rdlane32(incl, 31), r2 = rdlane32(incl, 47);
-            incl += (lane >= 16 ? r0 : 0u) + (lane >= 32 ? r1 : 0u) + (lane >= 48 ? r2 : 0u);
+            const u32 incl = wave_incl_scan_u32(sum, lane);
             const u32 ex = incl - sum;
             reinterpret_cast<uint4*>(hb)[lane] = make_uint4(ex, ex + v.x, ex + v.x + v.y, ex + v.x + v.y + v.z);
         }
@@ -894,10 +891,7 @@ __device__ __forceinline__ void k2_row_wave(const Dev& d, const EdgeEmitArgs& ea
         const u32 per = (BW + 63) >> 6, w0 = lane * per < BW ? lane * per : BW, w1 = w0 + per < BW ? w0 + per : BW;
         u32 c = 0;
         for (u32 w = w0; w < w1; w++) c += __popc(bm[w]);
-        u32 incl = c;
-        incl += dpp32<0x111>(incl); incl += dpp32<0x112>(incl); incl += dpp32<0x114>(incl); incl += dpp32<0x118>(incl);   // row_shr 1, 2, 4, 8
-        const u32 r0 = rdlane32(incl, 15), r1 = rdlane32(incl, 31), r2 = rdlane32(incl, 47);
-        incl += (lane >= 16 ? r0 : 0u) + (lane >= 32 ? r1 : 0u) + (lane >= 48 ? r2 : 0u);
+        const u32 incl = wave_incl_scan_u32(c, lane);
         u32 run = incl - c;
         for (u32 w = w0; w < w1; w++) { pf[w] = run; run += __popc(bm[w]); }
     }

@@ -102,6 +102,16 @@ __device__ __forceinline__ u64 wave_min_u64(u64 v) SG_WAVE_REDUCE(u64, dpp64, rd
 __device__ __forceinline__ u64 wave_max_u64(u64 v) SG_WAVE_REDUCE(u64, dpp64, rdlane64, SG_OP_MAX)
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) SG_WAVE_REDUCE(u64, dpp64, rdlane64, SG_OP_ADD)
 __device__ __forceinline__ u32 wave_sum_u32(u32 v) SG_WAVE_REDUCE(u32, dpp32, rdlane32, SG_OP_ADD)
+// inclusive scan over the 64 lanes of a wave (all active), no LDS round trip: DPP row_shr 1, 2, 4, 8 (zero fill) scans each row
+// of 16 lanes, then the totals of rows 0..2 reach the rows behind them through v_readlane.  lane: the caller's lane number.
+// (The halo lists of sg_k6.h spell the same sequence themselves: through this function two K6 kernels came out one instruction longer.)
+__device__ __forceinline__ u32 wave_incl_scan_u32(u32 v, u32 lane) {
+    v += dpp32<0x111>(v); v += dpp32<0x112>(v); v += dpp32<0x114>(v); v += dpp32<0x118>(v);
+    const u32 r0 = rdlane32(v, 15), r1 = rdlane32(v, 31), r2 = rdlane32(v, 47);
+    return v + (lane >= 16 ? r0 : 0u) + (lane >= 32 ? r1 : 0u) + (lane >= 48 ? r2 : 0u);
+}
+// workgroup barrier for LDS traffic only: unlike __syncthreads() it does not drain the global stores in flight
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory"); }
 
 // "error" classification: HTTP/HTTP2 >= 500; POSTGRES/REDIS/MYSQL == 2 (ebpf/c/postgres.c:91,
 // redis.c:10, mysql.c:36).
@@ -169,7 +179,7 @@ __device__ __forceinline__ u32 owner_of_dense(const Dev& d, u32 v, u32 nk, u32 n
 // (aggregator/data.go:1760-1767, 827-870; datastore/dto.go:226-231; backend.go:819-847).
 // Algorithmic bytes: 32 per event read + 32 per distinct edge written.
 // ------------------------------------------------------------------------------------------------
-struct K1Local { u64 tmin, tmax; u32 maxlabel, dsrc, dcap, misr, acc, lost; };   // lost: accepted by a lane of this workgroup, then dropped for capacity
+struct K1Local { u64 tmin = ~0ull, tmax = 0; u32 maxlabel = 0, dsrc = 0, dcap = 0, misr = 0, acc = 0, lost = 0; };   // lost: accepted by a lane of this workgroup, then dropped for capacity
 struct K1Ev { u64 key, dur, wt; u32 err; u32 alive; };
 #define SG_DUR_MAX ((1ull << 62) - 1)      // durations saturate here: bits 62/63 of a single record carry flags
 
@@ -268,7 +278,7 @@ __global__ __launch_bounds__(256) void k_join_apply(u32* blob, const uint2* __re
 // of edges, any degree) but bound by the chip's ~22 G atomics/s and 12 ns per same-sector atomic
 // (profiles/r01_atomic_probe.txt): kept for graphs the partitioned path cannot hold. ----------------
 __global__ __launch_bounds__(256) void k1_resolve_aggregate(Dev d, const sg_event* __restrict__ ev, u64 n) {
-    K1Local L; L.tmin = ~0ull; L.tmax = 0; L.maxlabel = L.dsrc = L.dcap = L.misr = L.acc = L.lost = 0;
+    K1Local L;
     const uint4* __restrict__ p = reinterpret_cast<const uint4*>(ev);
     const u64 stride = (u64)gridDim.x * 256;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
@@ -289,6 +299,7 @@ __global__ __launch_bounds__(256) void k1_resolve_aggregate(Dev d, const sg_even
     k1_publish_stats(d, L);
 }
 
+#include "sg_k1a_shared.h"  // what the three pass-A kernels below share
 #include "sg_k1_wide.h"     // K1 with 16-byte records (small windows, the histogram, k1_variant = 2)
 #include "sg_k1_narrow.h"   // the narrow-record form of both passes (default of variant 0)
 #include "sg_k1_team.h"     // round 4: pass A with two teams per workgroup and a batched join
