@@ -500,11 +500,16 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
     }
     if (dloc.warm && e->plain_left) { e->plain_left--; dloc.warm = 0; }
     if ((size_t)e->cur < e->plain_slot.size()) e->plain_slot[e->cur] = e->d.warm && !dloc.warm;
+    // an engine whose plan folds kc_prepare keeps pass B's counts and order twice: this close works on the half of the slot's window parity
+    const u32 par = e->d.k1b_par & 1u;
+    if (e->plan.prepare_fold && dloc.k1b_order) { dloc.k1b_cnt += (size_t)par * dloc.np; dloc.k1b_order += (size_t)par * dloc.np; }
     const Dev& d = dloc;
     // warm windows: try unless switched off (the device decides whether the try holds)
     bool warm_try = d.warm && e->warm_on;
     const u32 wt = warm_try ? 1u : 0u;
-    {
+    // a folded close (sg_plan.hpp close_folds) launches no kc_prepare: its work is one more workgroup of the warm attempt's launch below
+    const bool fold = sgplan::close_folds(e->plan, d.warm != 0, warm_try, ob_mode);
+    if (!fold) {
         Timed tp(e, s, 2);
         if (ob_mode == 1) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, e->d_ob_list, (const u32*)e->d_ob_n, e->plan.ob_list_cap, 1u, (const u32*)nullptr, 0u, 0u, wt);
         else if (ob_mode == 0) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, const_cast<u32*>(d_union), d_union_n, e->plan.ob_list_cap, 0u, (const u32*)nullptr, 0u, 0u, wt);
@@ -520,7 +525,16 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
         // of group 7: a window's pass B is the SUM of its group-7 records.  (A window such an engine closes the plain way takes k1b.)
         const dim3 grid(d.narrow ? d.npb : d.np), block(e->plan.k1b_threads);
         if (d.warm && warm_try) {
-            hipExtLaunchKernelGGL(e->fn.k1b_try, grid, block, (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db);
+            Dev dt = db; dim3 gt = grid;
+            if (fold) {
+                // the prepare workgroup (the launch's last): kc_prepare's arguments, and the OTHER half of the counts and the order — it sorts the
+                // counts of the window before into the order the next window reads while this window's merge reads and counts in its own half
+                dt.fold = 1u; dt.warm_try = wt; gt.x += 1;
+                dt.pf_n_known = (u64)e->n_known; dt.pf_n_labels_decl = (u64)e->n_labels_decl; dt.pf_list = e->d_ob_list; dt.pf_list_cap = e->plan.ob_list_cap;
+                dt.k1b_cnt_prev = e->d.k1b_order ? e->d.k1b_cnt + (size_t)(par ^ 1u) * d.np : nullptr;
+                dt.k1b_order_next = e->d.k1b_order ? e->d.k1b_order + (size_t)(par ^ 1u) * d.np : nullptr;
+            }
+            hipExtLaunchKernelGGL(e->fn.k1b_try, gt, block, (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, dt);
             if (tk) { TimingRec r; r.a = ta; r.b = tb; r.kernel = 7; e->trecs.push_back(r); ta = get_event(e); tb = get_event(e); }
         }
         hipExtLaunchKernelGGL(d.warm ? e->fn.k1b_cold : e->fn.k1b, grid, block, (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, db);
@@ -576,6 +590,7 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
     e->closed = true;
     e->window_events_in = 0;
     e->closes++;
+    if (e->plan.prepare_fold) e->d.k1b_par ^= 1u;                    // (per slot: e->d is the slot's working copy)
     return SG_OK;
 }
 
@@ -623,6 +638,7 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
 }
 
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
+static_assert(sizeof(KcScratch) <= sgplan::kPrepareLds, "a folded close's prepare workgroup lays KcScratch over pass B's dynamic LDS");
 static_assert(sizeof(sg_edge_vanished) == 64 && sgplan::kTrendThreads == K8_THREADS && sgplan::kTrendMaxWgs <= K8_SCAN_THREADS,
               "plan_trend / plan_vanished size the launches of sg_trend.h");
 // TrendArgs' baseline part of window w + 1's update of t: the window's outbound-IP list, the buffers and scratch, the parameters
@@ -844,9 +860,10 @@ void account_window(sg_engine* e) {
     if (e->d.warm && (size_t)e->cur < e->plain_slot.size() && e->plain_slot[e->cur]) st.windows_plain++;
     else if (e->d.warm) {
         // (counters of the slot that was read: with several windows in flight every slot keeps its own state and its own counts)
-        const bool cold = e->h_ctr[C_COLD] != 0;
+        // (kw_compact's copies: the window reset, which may or may not have run by now, zeroes C_COLD and C_DELTA_N for the next close)
+        const bool cold = e->h_ctr[C_LAST_COLD] != 0;
         if (cold) st.windows_cold++; else st.windows_warm++;
-        if (!cold && e->h_ctr[C_DELTA_N]) { st.windows_delta++; st.last_window_new_edges = e->h_ctr[C_DELTA_N]; }
+        if (!cold && e->h_ctr[C_LAST_DELTA]) { st.windows_delta++; st.last_window_new_edges = e->h_ctr[C_LAST_DELTA]; }
         // (the policy — when to stop trying — reads the device's note at the next close: do_close)
     }
     if (e->h_ctr[C_N_EVENTS]) {
@@ -1230,7 +1247,14 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
         if (w.variant == 0) {
             eslots = std::max<size_t>(ME, (size_t)w.npb * w.pcap);
             if (w.narrow) { LR(dev_alloc(e, &w.slab8, (size_t)w.np * w.nwg * w.punits)); LR(dev_alloc(e, &w.hdr8, (size_t)w.np * w.nwg));
-                            if (P.k1b_order) { LR(dev_alloc(e, &w.k1b_cnt, w.np)); LR(dev_alloc(e, &w.k1b_order, w.np)); } }   // (pass B's largest-first order: sg_k2.h kc_prepare)
+                            if (P.k1b_order) {                      // (pass B's largest-first order: sg_k2.h kc_prepare; twice, by window parity, where closes fold kc_prepare — both orders start as the identity)
+                                const size_t halves = P.prepare_fold ? 2 : 1;
+                                LR(dev_alloc(e, &w.k1b_cnt, halves * w.np)); LR(dev_alloc(e, &w.k1b_order, halves * w.np));
+                                std::vector<u32> ident(halves * w.np);
+                                for (size_t i = 0; i < ident.size(); i++) ident[i] = (u32)(i % w.np);
+                                HIP_TRY(e, hipStreamSynchronize(e->stream));   // (dev_alloc clears on the engine's stream, which the copy below does not order itself behind)
+                                HIP_TRY(e, hipMemcpy(w.k1b_order, ident.data(), ident.size() * sizeof(u32), hipMemcpyHostToDevice));
+                            } }
             else { LR(dev_alloc(e, &w.slab_s, (size_t)w.np * w.nwg * w.pslots)); LR(dev_alloc(e, &w.hdr, (size_t)w.np * w.nwg)); }
             LR(dev_alloc(e, &w.ovf, (size_t)w.ovf_cap * 9));
             LR(dev_alloc(e, &w.ovf_p, (size_t)w.ovf_cap));
@@ -1385,6 +1409,13 @@ int sg_geometry_get(sg_handle e, sg_geometry* out) {
     out->tile_records = p.narrow ? (a.k1a_team ? 4u * a.k1a_nt / a.k1a_teams : K1T_TS(a.k1a_nsub)) : 0u; out->pass_a_teams = p.narrow && a.k1a_team ? a.k1a_teams : 0u; out->endpoint_bits = p.narrow ? p.nb : 0u;
     out->piece_bytes = p.variant != 0 ? 0u : (p.narrow ? p.punits * 8u : p.pslots * 16u);
     out->warm_windows = p.warm;
+    return SG_OK;
+}
+
+int sg_prepare_fold_get(sg_handle e, uint32_t* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = e->plan.prepare_fold ? 1u : 0u;
     return SG_OK;
 }
 

@@ -59,7 +59,7 @@ enum {
     C_ACT_P,          // world > 1: nodes whose score projections this shard needs (local sources + local destinations)
     C_HUB_ITEMS,      // (row, block) work items of the rows with more than SG_MEAN_BLOCK neighbours (k2_rowptr -> k4_gather)
     // warm windows (Dev::warm): the edge set and its CSR order kept from the last cold window
-    C_COLD,           // != 0: this window takes the full rebuild — 1 set by kc_prepare (no usable kept state / the host does not try), 2 by the warm pass B (a table or a partition's key budget ran full, or an edge was dropped)
+    C_COLD,           // != 0: this window takes the full rebuild — 1 set by kc_prepare or, on a folded close, by the warm attempt's workgroup 0 (no usable kept state / the host does not try), 2 by the warm pass B (a table or a partition's key budget ran full, or an edge was dropped)
     C_KEPT_VALID,     // the kept state describes a whole window (no capacity drop, no raw outbound IP when it was captured)
     C_KEPT_E,         // edges of the kept CSR
     C_KEPT_NK,        // N_KNOWN and
@@ -67,9 +67,13 @@ enum {
     C_WARM_WINDOWS,   // windows closed on the warm path / by a full rebuild since create (sg_stats)
     C_COLD_WINDOWS,
     // delta windows (round 6): a warm window whose records brought keys the kept set lacks
-    C_DELTA_N,        // new edges the warm pass B emitted in this window (zeroed by kc_prepare; consumed when the kept buffers are flipped)
+    C_DELTA_N,        // new edges the warm pass B emitted in this window (zeroed by kc_prepare and by the window reset; consumed when the kept buffers are flipped)
     C_KEPT_BUF,       // which of the two kept-CSR buffers (k_col / k_col2 ...) is current; a full rebuild writes buffer 0, a delta window the other one
     C_DELTA_WINDOWS,  // windows closed warm WITH new edges since create
+    // the close without a kc_prepare launch (Dev::fold): what the warm attempt needs at its start is in place before the window closes
+    C_OB_RAW,         // != 0: a raw outbound IP entered obkeys in this window (k1_resolve; zeroed by the window reset)
+    C_LAST_COLD,      // C_COLD and
+    C_LAST_DELTA,     // C_DELTA_N of the last closed window as kw_compact saw them: the window reset zeroes the working words, the host reads these
     C_COUNT = 40
 };
 
@@ -203,6 +207,7 @@ struct Dev {
     u32* deg2;                                // [ncap + 1][SG_DEG_REP] row-degree replicas of the new edges (deg belongs to a full rebuild; zeroed by the window reset)
     u32* k1b_cnt;                             // [np] narrow records pass B read per partition in the LAST window (kc_prepare consumes and zeroes them)
     u32* k1b_order;                           // [np] the partitions by those counts, largest first: pass B's workgroup i takes partition k1b_order[i] (kc_prepare, every window)
+                                              // (an engine whose plan folds kc_prepare holds two of each, [2][np]: the engine's copy points at the pair, a close's at the half of its parity)
     u64* host_note;                           // page-locked HOST memory (mapped): [0] = sequence number of the last window kw_compact closed, [1] = its C_COLD
                                               // and C_N_OBIP << 8 — how the host learns, without ever waiting for the device, which path its windows take
     u32* lb_ticket;                           // [4] self-resetting workgroup tickets of the look-back kernels whose grid exceeds SG_LB_RESIDENT ([0] k2_rowptr, [1] kw_compact)
@@ -239,4 +244,14 @@ struct Dev {
     sg_edge_out* rows;                        // [max_edges]
     const float* W;                           // weights blob
     u32 ncap; u32 layers;
+    // ---- a close without a kc_prepare launch (sg_plan.hpp Plan::prepare_fold; sg_k2.h kc_prepare_rest).  New members go HERE, at the end:
+    // the kernels address the members above by their offsets ----
+    u32 fold;                                 // per launch (k1b_try): 1 = the launch has one workgroup more, which does kc_prepare's work, and every merge workgroup decides warm / cold itself
+    u32 warm_try;                             // per launch: the host wants this window to try the warm path (kc_prepare's argument of the same name)
+    u32 k1b_par;                              // window parity of this slot (closes & 1): which half of k1b_cnt / k1b_order the close's pass B uses
+    u32 pf_list_cap;                          // the prepare workgroup's kc_prepare arguments: capacity of pf_list,
+    u32* pf_list;                             // the outbound-IP list,
+    u64 pf_n_known, pf_n_labels_decl;         // the host's N_KNOWN and declared label count
+    u32* k1b_cnt_prev;                        // the prepare workgroup sorts the counts of the window before (the OTHER half) ...
+    u32* k1b_order_next;                      // ... into the order the next window reads (the other half too), and zeroes them
 };

@@ -427,10 +427,22 @@ __global__ __launch_bounds__(K1T_THREADS) void k1a_tile_partition(Dev d, const s
 // leaves with its accumulators (bit 63 of the max word = touched in this window, all zero otherwise); the image and, per slot, the
 // edge's index in the partition output are left for kw_capture.  The rebuild (K2) then builds the KEPT CSR from these outputs and
 // kw_compact derives the window's CSR from it, exactly as on a warm window.
+// kc_warm_decide by a workgroup that has no kc_prepare in front of it (Dev::fold): the same predicate from the words that are in place before the
+// window closes — the host's warm_try, the kept state's two words, and "no raw outbound IP was inserted" (C_OB_RAW != 0 exactly when obkeys holds
+// a key, i.e. when kc_prepare would count N_OBIP > 0).  Every workgroup of the launch gets the same answer: no launch-mate writes these words.
+__device__ __forceinline__ bool sg_warm_decide(const Dev& d) {
+    return d.warm_try && d.ctr[C_KEPT_VALID] && d.ctr[C_KEPT_E] != 0 && d.ctr[C_OB_RAW] == 0;
+}
+__device__ __forceinline__ void kc_prepare_folded(const Dev& d, unsigned char* lds);   // sg_k2.h: the prepare workgroup of a folded close
 template <int U, int SPT, bool PACK, int WM>
 __device__ __forceinline__ void k1b8_body(const Dev& d) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if constexpr (WM == 1) { if (d.ctr[C_COLD]) return; }             // (uniform: kc_prepare already knows, or another workgroup found a new key)
+    if constexpr (WM == 1) {
+        if (d.fold) {                                                // (uniform) a folded close, sg_k2.h: no kc_prepare ran in front of this launch.  Its work is the last workgroup's,
+            if (blockIdx.x == gridDim.x - 1) { kc_prepare_folded(d, smem); return; }   // beside the merge (nobody waits for it, it waits for nobody) ...
+            if (!sg_warm_decide(d)) return;                          // ... and every workgroup decides for itself (C_COLD is 0 at the start; the last workgroup, which gets the same answer, stores the 1)
+        } else if (d.ctr[C_COLD]) return;                            // (uniform: kc_prepare already knows, or another workgroup found a new key)
+    }
     if constexpr (WM == 2) { if (!d.ctr[C_COLD]) return; }
     const u32 HT = d.k1b_ht, hmask = HT - 1;
     u64* hacc = reinterpret_cast<u64*>(smem);                        // [4][HT]: accumulator j of slot h at j*HT + h
@@ -465,7 +477,8 @@ __device__ __forceinline__ void k1b8_body(const Dev& d) {
         for (int u = 0; u < U; u++) { const u32 r = sub + (u32)u * LPP; xf[u] = piece0[r < pm1 ? r : pm1]; }
     }
     const u64 ovf_n = d.ctr[C_OVF_N];
-    const u32 nk = (u32)d.ctr[C_N_KNOWN], nl = (u32)d.ctr[C_N_LABELS], nob = (u32)d.ctr[C_N_OBIP];
+    // (the warm attempt emits compact ids and never numbers a node: on a folded close the prepare workgroup is writing these words meanwhile)
+    const u32 nk = WM == 1 ? 0u : (u32)d.ctr[C_N_KNOWN], nl = WM == 1 ? 0u : (u32)d.ctr[C_N_LABELS], nob = WM == 1 ? 0u : (u32)d.ctr[C_N_OBIP];
     if constexpr (WM == 1) {
         const u32* img = d.wk_keys + (size_t)oq * HT;                 // (coalesced: 4 HT bytes per workgroup, beside the headers' round trip)
         if (t == 0) *nkeys = 0;

@@ -19,18 +19,31 @@ __device__ __forceinline__ void kc_warm_decide(const Dev& d, u32 warm_try, u64 n
     const bool ok = warm_try && d.ctr[C_KEPT_VALID] && d.ctr[C_KEPT_E] != 0 && nob == 0;
     d.ctr[C_COLD] = ok ? 0ull : 1ull;
 }
-__global__ __launch_bounds__(1024) void kc_prepare(Dev d, u64 n_known, u64 n_labels_decl, u32* list, const u32* n_in, u32 list_cap, u32 collect,
-                                                   const u32* seg, u32 seg_stride, u32 seg_world, u32 warm_try) {
-    __shared__ u64 red[7][16];
-    __shared__ u32 wsum[17];
-    __shared__ u32 cnt;
-    __shared__ u64 nkl;                                              // N_KNOWN + N_LABELS as thread 0 wrote them (no second trip to memory for step (c))
-    __shared__ u64 nl_s;
+// kc_prepare's LDS.  The kernel holds one statically; the prepare workgroup of a folded close (below) lays it over the head of pass B's dynamic
+// LDS, so that k1b_stream_merge's own static LDS stays what it was (none: two of its workgroups share a CU).
+struct KcScratch {
+    u64 red[7][16];
+    u64 nkl;                                                         // N_KNOWN + N_LABELS as thread 0 wrote them (no second trip to memory for step (c))
+    u64 nl_s;
+    __attribute__((aligned(16))) u32 hb[256];
+    u32 wsum[17];
+    u32 cnt, cmax;
+};
+// Steps (a) .. (c) for both callers.  FOLD = false: the kc_prepare kernel, as it always was.  FOLD = true: the LAST workgroup of a folded close's
+// k1b_try launch (Dev::fold, sg_k1_narrow.h) — the warm attempt's merge workgroups run beside it, so it leaves alone what they read or write
+// in that launch: C_COLD (each of them decides for itself, sg_warm_decide), C_DELTA_N (they count; the window reset has zeroed it), the half of
+// k1b_cnt / k1b_order of this window's parity (it sorts cnt_io, the counts of the window before, into order_out, the order of the window after).
+// Nothing it writes is read before the next launch.
+template <bool FOLD>
+__device__ __forceinline__ void kc_prepare_rest(const Dev& d, KcScratch& sc, u64 n_known, u64 n_labels_decl, u32* list, const u32* n_in, u32 list_cap, u32 collect,
+                                                const u32* seg, u32 seg_stride, u32 seg_world, u32 warm_try, u32* cnt_io, u32* order_out) {
+    u64 (&red)[7][16] = sc.red; u32 (&wsum)[17] = sc.wsum; u32& cnt = sc.cnt; u64& nkl = sc.nkl; u64& nl_s = sc.nl_s;
     const u32 t = threadIdx.x, lane = t & 63, wave = t >> 6;
     // (the first stretch of the outbound-IP table travels together with the statistics: one round trip to memory, not two — this
     // kernel is one workgroup, the chip waits for it, and it is nothing but dependent round trips)
-    const u64 ob0 = (collect == 1 && t <= d.obmask) ? d.obkeys[t] : 0ull;
-    const u64 nl_prev = t == 0 ? d.ctr[C_N_LABELS] : 0ull;           // (so does the label count of the windows before: it was a third trip, behind the barrier)
+    // (FOLD: nobody waits for this workgroup — it loads where it needs the value and keeps within the merge's registers)
+    const u64 ob0 = (!FOLD && collect == 1 && t <= d.obmask) ? d.obkeys[t] : 0ull;
+    const u64 nl_prev = (!FOLD && t == 0) ? d.ctr[C_N_LABELS] : 0ull;   // (so does the label count of the windows before: it was a third trip, behind the barrier)
     // (a)
     {
         u64 tmin = ~0ull, tmax = 0, ml = 0, ds = 0, dc = 0, mr = 0, ac = 0;
@@ -48,18 +61,20 @@ __global__ __launch_bounds__(1024) void kc_prepare(Dev d, u64 n_known, u64 n_lab
         if (t == 0) cnt = 0;
         __syncthreads();
         if (t == 0) {
+            constexpr int kFoldUnroll = FOLD ? 1 : 15;               // (FOLD: unrolled, the 105 LDS reads in flight together took 8 registers more than the merge has)
+#pragma unroll kFoldUnroll
             for (int k = 1; k < 16; k++) {
                 red[0][0] = red[0][k] < red[0][0] ? red[0][k] : red[0][0]; red[1][0] = red[1][k] > red[1][0] ? red[1][k] : red[1][0];
                 red[2][0] = red[2][k] > red[2][0] ? red[2][k] : red[2][0];
                 red[3][0] += red[3][k]; red[4][0] += red[4][k]; red[5][0] += red[5][k]; red[6][0] += red[6][k];
             }
             d.ctr[C_TMIN_NS] = red[0][0]; d.ctr[C_TMAX_NS] = red[1][0];
-            u64 nl = nl_prev;                                        // labels are cumulative across windows
+            u64 nl = FOLD ? d.ctr[C_N_LABELS] : nl_prev;              // labels are cumulative across windows
             nl = red[2][0] > nl ? red[2][0] : nl; nl = n_labels_decl > nl ? n_labels_decl : nl;
             d.ctr[C_N_LABELS] = nl; d.ctr[C_N_KNOWN] = n_known; nkl = nl + n_known; nl_s = nl;
             d.ctr[C_DROPPED_SRC] = red[3][0]; d.ctr[C_MISROUTED] = red[5][0]; d.ctr[C_N_EVENTS] = red[6][0];
             d.ctr[C_DROPPED_CAP] = red[4][0];                        // K1b / K2 add their own drops afterwards
-            d.ctr[C_DELTA_N] = 0;                                    // the warm pass B counts the window's new edges
+            if (!FOLD) d.ctr[C_DELTA_N] = 0;                         // the warm pass B counts the window's new edges
             d.ctr[C_N_LONG] = 0;                                     // k2_rowptr's workgroups append to the long-row list
             d.ctr[C_HUB_ITEMS] = 0;                                  // ... and to the hub-block work list
         }
@@ -68,18 +83,17 @@ __global__ __launch_bounds__(1024) void kc_prepare(Dev d, u64 n_known, u64 n_lab
     // so are its partitions (0.7 .. 1.5 x the mean at C3); pass B runs two rounds of workgroups per CU, and a large partition that starts late
     // is the launch's tail.  Measured on one box (profiles/r06_order_ab.txt): pass B 94.5-95.3 us in this order, 97.8-99.5 in block order.  Whatever
     // the counts are, the result is a permutation (within a size class the order is that of arrival: the rows do not depend on it).
-    if (d.narrow && d.k1b_order) {
+    if (d.narrow && order_out) {
         // (a counting sort by 256 size classes: two LDS atomics per partition and one wave's scan — this kernel is one workgroup on the
         // window's critical path; ranking every partition against every other cost it 14 us)
-        __shared__ __attribute__((aligned(16))) u32 hb[256];
-        __shared__ u32 cmax;
+        u32 (&hb)[256] = sc.hb; u32& cmax = sc.cmax;
         const u32 NP = d.np;                                         // (<= 2048: two partitions per thread at most)
         if (t < 256) hb[t] = 0;
         if (t == 0) cmax = 0;
         __syncthreads();
         u32 c[2] = {0u, 0u}, rk[2] = {0u, 0u}, cls[2] = {0u, 0u};
 #pragma unroll
-        for (int k = 0; k < 2; k++) { const u32 i = t + (u32)k * 1024u; if (i < NP) { c[k] = d.k1b_cnt[i]; d.k1b_cnt[i] = 0u; } }
+        for (int k = 0; k < 2; k++) { const u32 i = t + (u32)k * 1024u; if (i < NP) { c[k] = cnt_io[i]; cnt_io[i] = 0u; } }
         { const u32 m = (u32)wave_max_u64((u64)(c[0] > c[1] ? c[0] : c[1])); if (lane == 0 && m) atomicMax(&cmax, m); }
         __syncthreads();
         const float scale = 255.0f / (float)(cmax ? cmax : 1u);
@@ -98,13 +112,13 @@ __global__ __launch_bounds__(1024) void kc_prepare(Dev d, u64 n_known, u64 n_lab
         }
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < 2; k++) { const u32 i = t + (u32)k * 1024u; if (i < NP) d.k1b_order[hb[cls[k]] + rk[k]] = i; }
+        for (int k = 0; k < 2; k++) { const u32 i = t + (u32)k * 1024u; if (i < NP) order_out[hb[cls[k]] + rk[k]] = i; }
     }
     // (b)
     u32 n;
     if (collect == 1) {
         for (u32 i = t; i <= d.obmask; i += 1024) {
-            const u64 k = i == t ? ob0 : d.obkeys[i];
+            const u64 k = (!FOLD && i == t) ? ob0 : d.obkeys[i];
             if (k) { const u32 pos = atomicAdd(&cnt, 1u); if (pos < list_cap) list[pos] = (u32)k; }
         }
         __syncthreads();
@@ -124,7 +138,7 @@ __global__ __launch_bounds__(1024) void kc_prepare(Dev d, u64 n_known, u64 n_lab
         n = *n_in < list_cap ? *n_in : list_cap;
     }
     if (n == 0) {                                                    // (uniform) no raw outbound IP this window: nothing to sort or to number
-        if (t == 0) { d.ctr[C_N_OBIP] = 0; d.ctr[C_N_NODES] = nkl; kc_warm_decide(d, warm_try, n_known, nl_s, 0); }
+        if (t == 0) { d.ctr[C_N_OBIP] = 0; d.ctr[C_N_NODES] = nkl; if (!FOLD) kc_warm_decide(d, warm_try, n_known, nl_s, 0); }
         return;
     }
     u32 np2 = 1; while (np2 < n) np2 <<= 1;
@@ -152,8 +166,21 @@ __global__ __launch_bounds__(1024) void kc_prepare(Dev d, u64 n_known, u64 n_lab
         const u64 nob = total < d.max_obip ? total : d.max_obip;
         d.ctr[C_N_OBIP] = nob;
         d.ctr[C_N_NODES] = nkl + nob;
-        kc_warm_decide(d, warm_try, n_known, nl_s, nob);
+        if (!FOLD) kc_warm_decide(d, warm_try, n_known, nl_s, nob);
     }
+}
+__global__ __launch_bounds__(1024) void kc_prepare(Dev d, u64 n_known, u64 n_labels_decl, u32* list, const u32* n_in, u32 list_cap, u32 collect,
+                                                   const u32* seg, u32 seg_stride, u32 seg_world, u32 warm_try) {
+    __shared__ KcScratch sc;
+    kc_prepare_rest<false>(d, sc, n_known, n_labels_decl, list, n_in, list_cap, collect, seg, seg_stride, seg_world, warm_try, d.k1b_cnt, d.k1b_order);
+}
+// The prepare workgroup of a folded close (out of line: its registers are its own, k1b_stream_merge keeps the ones that let two workgroups share a CU).
+__device__ __forceinline__ void kc_prepare_folded(const Dev& d, unsigned char* lds) {
+    kc_prepare_rest<true>(d, *reinterpret_cast<KcScratch*>(lds), d.pf_n_known, d.pf_n_labels_decl, d.pf_list, nullptr, d.pf_list_cap, 1u, nullptr, 0u, 0u, 0u,
+                          d.k1b_cnt_prev, d.k1b_order_next);
+    // the window is cold up front: the merge workgroups, which reach the same answer from the same words, leave without a store (the window reset
+    // left C_COLD 0, and only a window that merges stores 2)
+    if (threadIdx.x == 0 && !sg_warm_decide(d)) d.ctr[C_COLD] = 1;
 }
 
 // one workgroup: the window's distinct raw outbound IPs into a caller-owned list (sharded driver).

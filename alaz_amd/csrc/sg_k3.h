@@ -56,7 +56,7 @@ __global__ __launch_bounds__(1024) void k3_in_part(Dev d, u32 S, u32 fin) {
     // buffer: flip (nothing in this launch reads the kept state; the next window's pass B and kw_compact do)
     if (g == 0 && t == 0 && d.warm && !d.ctr[C_COLD] && d.ctr[C_DELTA_N]) {
         d.ctr[C_KEPT_E] += (u64)d.dc_rowptr[d.max_known + d.max_labels];
-        d.ctr[C_KEPT_BUF] ^= 1ull;                                    // (C_DELTA_N stays for the window's reader: sg_stats.windows_delta; kc_prepare re-arms it)
+        d.ctr[C_KEPT_BUF] ^= 1ull;                                    // (C_DELTA_N stays until the window reset; the window's reader takes kw_compact's copy, C_LAST_DELTA)
     }
     alive_mark(d, g, G, t);
     const u32 r = g / S, sl = g % S, n0 = r * K3_IN_NR;
@@ -234,6 +234,7 @@ __global__ __launch_bounds__(256) void k_reset_window(Dev d) {
     // path would have consumed and re-armed — the per-workgroup K1 statistics, the overflow and alive lists
     for (u64 i = tid; i < (u64)SG_MAX_K1_WGS * WS_WORDS; i += nt) d.wgstat[i] = (i % WS_WORDS) == WS_TMIN ? ~0ull : 0ull;
     if (tid == 0) { d.ctr[C_OVF_N] = 0; d.ctr[C_ALIVE_N] = 0; d.ctr[C_ALIVE_DROP] = 0; }
+    if (tid == 0) { d.ctr[C_COLD] = 0; d.ctr[C_DELTA_N] = 0; d.ctr[C_OB_RAW] = 0; }   // what a close without kc_prepare finds in place (sg_k2.h; the reader's copies: C_LAST_*)
     if (d.variant == 1 && d.ctr[C_EDGES_FOUND] > d.max_edges) {
         for (u64 i = tid; i <= d.emask; i += nt) {
             d.ekeys[i] = SG_EKEY_EMPTY;

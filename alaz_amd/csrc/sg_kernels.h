@@ -235,6 +235,7 @@ __device__ __forceinline__ bool k1_resolve(const Dev& d, const uint4 a, const ui
     } else {                                                     // outbound, raw IP (:862-863)
         u32 os;
         if (!table_slot(d.obkeys, d.obmask, (u64)daddr | (1ull << 32), 0ull, sg_fmix32(daddr) & d.obmask, os)) { L.dcap++; return false; }
+        d.ctr[C_OB_RAW] = (u64)daddr | (1ull << 32);             // (any value but 0: the key is at hand) the window holds a raw outbound IP: it cannot close warm (sg_warm_decide)
         to = SG_MAKE_REF(SG_REF_OBIP, os); to_owner = owner_hash_obip(daddr);
     }
     if ((flags & SG_EV_REVERSE) && !alive) { u32 t = from; from = to; to = t; t = from_owner; from_owner = to_owner; to_owner = t; }  // dto.go:226-231

@@ -309,6 +309,7 @@ __global__ __launch_bounds__(KW_THREADS) void kw_compact(Dev d, u32 epoch, u64* 
         if (D) d.ctr[C_DELTA_WINDOWS] += 1;
         // for the host's policy (it never waits for the device: it reads this note, a window or two late, when it closes a later window)
         d.host_note[1] = d.ctr[C_COLD] | (d.ctr[C_N_OBIP] ? 0x100ull : 0ull);
+        d.ctr[C_LAST_COLD] = d.ctr[C_COLD]; d.ctr[C_LAST_DELTA] = d.ctr[C_DELTA_N];   // ... and for the window's reader (sg_stats): both are final here, and the window reset zeroes them
         __threadfence_system();
         d.host_note[0] = seq;
     }

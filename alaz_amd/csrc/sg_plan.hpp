@@ -27,6 +27,7 @@ typedef uint64_t u64;
 
 constexpr size_t kLdsBytes = 160 * 1024;  // per workgroup on gfx950
 constexpr int kStageSlots = 32;           // staging ring slots at most (Plan::n_stage of them are allocated)
+constexpr size_t kPrepareLds = 4096;      // at least sizeof(KcScratch) (sg_k2.h; servicegraph.hip asserts it): what a folded close's prepare workgroup takes of pass B's dynamic LDS
 
 inline u32 next_pow2(u64 v) { u64 p = 1; while (p < v) p <<= 1; return (u32)p; }
 inline int grid_for(u64 items, int per_block, int cap = 2048) {
@@ -45,7 +46,7 @@ struct DeviceFacts {
 struct Overrides {
     typedef std::optional<std::string> Knob;
     Knob ablate, np, ht, ct, nwg, nsub, split, warm, k1a, k1_narrow, k1_legacy, k1b_u, k1b_threads, k1b_pack, k1b_no_order,
-         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena;
+         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold;
 };
 struct KnobName { const char* name; Overrides::Knob Overrides::*field; };
 // the one list of knob names (alaz_amd/engine.py DEV_KNOBS is checked against it)
@@ -58,7 +59,7 @@ constexpr KnobName kKnobs[] = {
     {"SG_DH_G", &Overrides::dh_g}, {"SG_K3_SLICES", &Overrides::k3_slices}, {"SG_K3_NO_FUSE", &Overrides::k3_no_fuse},
     {"SG_K4_FUSED", &Overrides::k4_fused}, {"SG_K5_GRID", &Overrides::k5_grid}, {"SG_K6_ONE_WG", &Overrides::k6_one_wg},
     {"SG_DENSE_VALU", &Overrides::dense_valu}, {"SG_COPY_STREAMS", &Overrides::copy_streams}, {"SG_STAGE_SLOTS", &Overrides::stage_slots},
-    {"SG_ARENA", &Overrides::arena},
+    {"SG_ARENA", &Overrides::arena}, {"SG_NO_FOLD", &Overrides::no_fold},
 };
 #ifdef SG_DEV_KNOBS
 inline Overrides from_env() {
@@ -78,6 +79,7 @@ struct Plan {
     bool k1b_pack = false;                    // narrow pass B: count + duration sum of a record in one 64-bit LDS add (sn x nwg < 2^16)
     bool k1b_order = false;                   // narrow pass B takes its partitions largest first (sg_k2.h kc_prepare)
     size_t k1b_lds = 0;                       // pass B's dynamic LDS (variant 0)
+    bool prepare_fold = false;                // a close that tries the warm path launches no kc_prepare: its work rides in the warm attempt's launch (close_folds)
     // table sizes
     u32 ecap = 0, obcap = 0, ob_list_cap = 0, ncap = 0, max_obip = 1, alive_cap = 0, hub_cap = 0, max_blocks = 0;
     u64 kept_edges = 0;                       // arrays the rebuild indexes by KEPT position on a warm engine: max(max_edges, npb x pcap), else max_edges
@@ -239,6 +241,14 @@ inline int make_plan(const sg_config& cfg, const DeviceFacts& dev, const Overrid
     if (ov.k1b_threads) { const u64 x = uval(ov.k1b_threads); if ((x == 256 && !p.narrow) || x == 512 || x == 1024) p.k1b_threads = (u32)x; }
     if (p.narrow && p.k1b_ht / p.k1b_threads > 4) p.k1b_threads = 1024u;    // (the compaction takes at most four table slots per thread)
     p.k1b_order = p.narrow && !ov.k1b_no_order;
+    // Warm closes without the kc_prepare launch (sg_k2.h kc_prepare_rest): one 1 024-thread workgroup, ~7 us of dependent round trips between
+    // pass A and pass B while the rest of the chip waits.  Where the close launches the warm attempt, that workgroup's work becomes one MORE
+    // workgroup of the attempt's launch (it runs beside the merge), every merge workgroup takes the warm / cold decision itself, and the order
+    // of the partitions is one window older (two buffers by window parity).  Only the shape that was built for: a variant-0 narrow engine that
+    // keeps state, unsharded, whose pass B runs 1 024 threads (the prepare workgroup's strides) over an LDS that holds kc_prepare's scratch.
+    // SG_NO_FOLD=1 keeps the separate launch (the A/B twin of tests/test_gpu_prepare_fold.py).
+    p.prepare_fold = p.warm && p.narrow && p.variant == 0 && cfg.world <= 1 && p.k1b_threads == 1024u && p.k1b_lds >= kPrepareLds &&
+                     !(ov.no_fold && ival(ov.no_fold) != 0);
     // join tables: IP blocks of the two-level table (variant 1 probes the cuckoo table only)
     p.max_blocks = p.variant == 0 ? (u32)std::min<u64>(1024, std::max<u64>(64, (u64)cfg.max_ips / 32)) : 2u;
     if (p.variant == 0) p.ecap = K2_TILE;                            // the global edge table is not used
@@ -660,6 +670,11 @@ inline RankPlan plan_rank(u64 max_edges, u32 ncap, u32 slots) {
                     (u64)std::max<u32>(slots, 1) * r.rows_bytes;
     return r;
 }
+
+// Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
+// warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
+// outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).
+inline bool close_folds(const Plan& p, bool warm, bool warm_try, u32 ob_mode) { return p.prepare_fold && warm && warm_try && ob_mode == 1u; }
 
 // the plan's share of the kernels' argument (Dev, sg_device.h; a template so that the CPU test can fill a struct of the same names)
 template <class D>

@@ -22,7 +22,7 @@ LIB_DEV_PATH = os.path.join(_HERE, "lib", "libservicegraph_dev.so")
 #: the knobs the development build reads (csrc/sg_plan.hpp kKnobs); ServiceGraph(dev_knobs=None) picks that build when one of them is set
 DEV_KNOBS = ("SG_ABLATE", "SG_NP", "SG_HT", "SG_CT", "SG_NWG", "SG_NSUB", "SG_SPLIT", "SG_WARM", "SG_K1A", "SG_K1_NARROW", "SG_K1_LEGACY", "SG_K1B_U",
              "SG_K1B_THREADS", "SG_K1B_PACK", "SG_K1B_NO_ORDER", "SG_L2_GLOBAL", "SG_L2_U32", "SG_DH_G", "SG_K3_SLICES", "SG_K3_NO_FUSE", "SG_K4_FUSED", "SG_K5_GRID", "SG_K6_ONE_WG", "SG_DENSE_VALU",
-             "SG_COPY_STREAMS", "SG_STAGE_SLOTS", "SG_ARENA")
+             "SG_COPY_STREAMS", "SG_STAGE_SLOTS", "SG_ARENA", "SG_NO_FOLD")
 
 SG_OK, SG_EINVAL, SG_ENOMEM, SG_ENODEV, SG_ENOSPC, SG_EAGAIN, SG_ESTATE = 0, -22, -12, -19, -28, -11, -71
 SELECT_MAX_K = 16384      # SG_SELECT_MAX_K: the largest k of a top-k selection
@@ -40,7 +40,7 @@ EXPORTS = [
     "sg_window_read", "sg_window_reset", "sg_window_buffers", "sg_window_feat_buffer",
     "sg_halo_build", "sg_halo_pack", "sg_halo_unpack", "sg_window_close_gathered", "sg_halo_build_padded",
     "sg_halo_pack_padded", "sg_halo_unpack_padded", "sg_window_outbound_ips", "sg_stats_get",
-    "sg_timing_enable", "sg_timing_reset", "sg_timing_get", "sg_timing_samples", "sg_timing_stride", "sg_latency_probe", "sg_set_warm", "sg_debug_stamps", "sg_route", "sg_window_hist", "sg_geometry_get",
+    "sg_timing_enable", "sg_timing_reset", "sg_timing_get", "sg_timing_samples", "sg_timing_stride", "sg_latency_probe", "sg_set_warm", "sg_debug_stamps", "sg_route", "sg_window_hist", "sg_geometry_get", "sg_prepare_fold_get",
     "sg_clock_probe", "sg_comm_probe", "sg_window_halo_counts", "sg_comm_unique_id", "sg_comm_create", "sg_comm_destroy", "sg_window_run_sharded", "sg_host_register", "sg_host_unregister", "sg_ingest_pinned", "sg_ingest_bulk",
     "sg_flush_window_top", "sg_flush_end_top", "sg_window_select",
     "sg_set_trend", "sg_window_trend", "sg_window_trend_buffer", "sg_trend_entries", "sg_trend_stats_get",
@@ -220,6 +220,7 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_route": (C.c_int, [H, P, sz, u32, P]),
         "sg_window_hist": (C.c_int, [H, P, sz, C.POINTER(sz)]),
         "sg_geometry_get": (C.c_int, [H, C.POINTER(SgGeometry)]),
+        "sg_prepare_fold_get": (C.c_int, [H, C.POINTER(C.c_uint32)]),
         "sg_comm_unique_id": (C.c_int, [P, sz]), "sg_comm_create": (C.c_int, [P, sz, C.c_int, C.c_int, C.c_int, C.POINTER(P)]),
         "sg_comm_destroy": (C.c_int, [P]), "sg_window_run_sharded": (C.c_int, [H, P, P]),
         "sg_host_register": (C.c_int, [H, P, sz]), "sg_host_unregister": (C.c_int, [H, P]), "sg_ingest_pinned": (C.c_int, [H, P, sz]),
@@ -334,10 +335,12 @@ class ServiceGraph:
             pass
 
     def geometry(self) -> dict:
-        """What sg_create chose for K1 (sg_geometry_get)."""
+        """What sg_create chose for K1 (sg_geometry_get) and, as prepare_fold, whether its warm closes launch no kc_prepare (sg_prepare_fold_get)."""
         g = SgGeometry()
         self._ck(self._l.sg_geometry_get(self._h, C.byref(g)))
-        return {n: int(getattr(g, n)) for n, _ in SgGeometry._fields_}
+        fold = C.c_uint32(0)
+        self._ck(self._l.sg_prepare_fold_get(self._h, C.byref(fold)))
+        return {**{n: int(getattr(g, n)) for n, _ in SgGeometry._fields_}, "prepare_fold": int(fold.value)}
 
     def k1_kernels(self) -> tuple:
         """Names of the two K1 kernels this engine launches (as rocprofv3 lists them), or the single global-table kernel."""

@@ -677,6 +677,9 @@ typedef struct sg_geometry {
     uint32_t warm_windows;      /* 1 = the engine carries the edge set and its CSR order from window to window (SG_CFG_NO_WARM)   */
 } sg_geometry;
 int sg_geometry_get(sg_handle h, sg_geometry* out);
+/* The close's launch plan, beside sg_geometry (whose layout is fixed): *out = 1 when a window close that tries the warm path launches no
+ * kc_prepare — that kernel's work rides in the warm attempt's launch (unsharded engines that keep warm-window state). */
+int sg_prepare_fold_get(sg_handle h, uint32_t* out);
 
 /* Per-kernel timing, measured on the launch stream.  Groups: 1 = K1 pass A (k1a_partition / k1_resolve_aggregate, one record
  * per batch), 7 = K1 pass B (k1b_merge) — both by the dispatch's own begin/end stamps; 2 = K2 csr_build (two records per window:
