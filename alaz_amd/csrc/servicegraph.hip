@@ -1,8 +1,8 @@
 // servicegraph.hip — host engine + C ABI (include/servicegraph.h) of the MI355X ServiceGraph engine.
 //
 // One sg_engine owns one device: the join tables, the open window's edge table, the closed
-// window's CSR / feature / score buffers, a pinned staging ring for host-fed events and one HIP
-// stream.  All kernels live in sg_kernels.h and the per-stage headers it includes.  There is no CPU compute path in this file: every
+// window's CSR / feature / score buffers (per window slot, with the slot's HIP stream) and a pinned
+// staging ring for host-fed events.  All kernels live in sg_kernels.h and the per-stage headers it includes.  There is no CPU compute path in this file: every
 // entry point that produces results launches HIP kernels, and sg_create() fails without a device.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -57,8 +57,6 @@ struct sg_engine {
     sg_config cfg{};
     std::mutex mu;
     std::string err;
-    hipStream_t stream = nullptr;
-    Dev d{};
     // every sizing decision (sg_plan.hpp): made at create from the config and the development build's overrides; pass A's
     // geometry follows the join tables (sync_tables)
     sgplan::Overrides ov;
@@ -106,12 +104,10 @@ struct sg_engine {
     // per stream that has run K4 / K5: an event behind its last such launch (sg_load_weights waits for them before it overwrites d_W)
     std::vector<std::pair<hipStream_t, hipEvent_t>> w_readers;
     u32 n_labels_decl = 0;
-    u32* d_ob_list = nullptr; u32* d_ob_n = nullptr;
 
     sg_stats st{};
     u64 h_ctr[C_COUNT] = {};
     std::vector<u32> last_obips;
-    bool closed = false;       // window_close has run; rows readable after score
     // warm windows (sg_device.h): the host only decides whether a window TRIES the warm path; whether it may is decided on the device
     bool warm_on = true;                      // sg_set_warm
     u32 cold_streak = 0;                      // consecutive windows whose warm attempt met an unknown key (C_COLD = 2), by the device's note
@@ -119,24 +115,27 @@ struct sg_engine {
     u32 in_fused_slices = 0;                  // != 0 between a one-call pipeline's close and its features: the features sum k3_in_part's partials (k3_in_reduce was not launched)
     u64 closes = 0; u32 timing_stride = 1;    // windows closed so far; the dispatch stamps of K1 (groups 1 and 7) are taken on every timing_stride-th window
     u32 obip_streak = 0; u64 plain_left = 0;  // windows in a row that raw outbound IPs kept cold (same note); windows still to be closed without the kept-CSR detour
-    std::vector<char> plain_slot;             // per window slot: its last close was such a plain one (not counted as warm or cold)
-    std::vector<u64*> h_note; std::vector<u64> note_seen;   // per window slot: the device's note (page-locked, mapped) and the sequence number last read from it
-    std::vector<u64*> scr_sum, scr_max; std::vector<double*> scr_mu;   // per window slot: the node statistics the kept-CSR rebuild writes (scratch; row_mu | row_sd in one array)
     // (Measured and rejected, profiles/r05_c_aux*: the rebuild kernels on a second stream beside the warm window's compaction, so that their
     // empty launches cost nothing — the fork / join events and the two streams' kernels slowing each other cost more: 506 vs 490 us per window.)
-    u64 window_events_in = 0;
 
     unsigned timing = 0;       // bit k set: kernel group k is bracketed by HIP events
     hipEvent_t win_ta = nullptr;   // timing group 10: the open window's begin event (recorded in front of its first pass-A launch)
     u32 k6_epoch = 0;          // k6_halo_lists launch counter (same use)
     u32 rp_epoch = 0;          // k2_rowptr launch counter (tags the per-workgroup totals, so they need no reset)
 
-    // windows in flight: every slot has its own window buffers and stream; the members above (d, stream,
-    // d_ob_list, d_ob_n, closed, window_events_in) are the working copy of slot `cur`
-    struct WinSlot { Dev d; hipStream_t stream; u32* ob_list; u32* ob_n; bool closed; u64 events_in; };
-    std::vector<WinSlot> slots;
+    // windows in flight: a slot owns everything of one window — its buffers (d, with the words the host advances per slot: k1a_rot,
+    // k1a_ticket_base, k1b_par), its stream and its outbound-IP list; on an engine that keeps warm-window state also that state's host
+    // side (h_note == nullptr: no kept state).  Slot `cur` is the WORKING one: the window being filled or closed (work()).  `last`
+    // names the window sg_window_run* ran last and the stream it ran on, which may be the caller's (ran(): before any run, the working slot).
+    struct WinSlot {
+        Dev d{}; hipStream_t stream = nullptr; u32* ob_list = nullptr; u32* ob_n = nullptr; u64 events_in = 0;
+        bool closed = false, plain = false;    // window_close has run, rows readable after score; its last close was a plain one (not counted as warm or cold)
+        u64* h_note = nullptr; u64 note_seen = 0;   // the device's note (page-locked, mapped) and the sequence number last read from it
+        u64* scr_sum = nullptr; u64* scr_max = nullptr; double* scr_mu = nullptr;   // the node statistics the kept-CSR rebuild writes (scratch; row_mu | row_sd in one array)
+    };
+    std::vector<WinSlot> slots = std::vector<WinSlot>(1);   // (never empty)
     int cur = 0;
-    sg_edge_out* last_rows = nullptr;
+    struct LastRun { int slot = -1; hipStream_t stream = nullptr; } last;
     std::vector<TimingRec> trecs;
     std::vector<hipEvent_t> ev_pool;
     // sg_window_run_sharded: exchange buffers of the sharded window (allocated at the first call; world = cfg.world)
@@ -148,15 +147,14 @@ struct sg_engine {
     // K7, the selection: scratch allocated at the first selection (sg_plan.hpp plan_select), the host flushes' device staging grown
     // on demand.  Selections on different streams share the scratch.
     struct Sel : SelScratch { sg_edge_out* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; } sel;
-    u64* last_ctr = nullptr; hipStream_t last_stream = nullptr;   // counters and stream of the window last_rows belongs to (sg_window_select)
     // A baseline (sg_trend.h), K8's per-edge one (trend, Row = sg_edge_trend) or K10's per-node one (ntrend, sg_node_trend):
     // allocated at sg_set_trend / sg_set_node_trend (sg_plan.hpp plan_trend / plan_node_trend), one allocation.  The baseline is
     // engine-wide: every update waits for the previous one (ev), whichever slot's stream it runs on.  w = trend windows enqueued.
-    // Per slot: the trend rows; K10's also whether the window in the slot made them (valid).  run_slot is K8's (K10 uses the rollup's).
+    // Per slot: the trend rows; K10's also whether the window in the slot made them (valid).
     template <class Row>
     struct Baseline { bool on = false; sg_trend_params p{}; sgplan::TrendPlan plan; char* mem = nullptr; TrendSoA buf[2] = {}; u64* ctl = nullptr;
                       u32* blk = nullptr; K8Thread* th = nullptr; std::vector<Row*> rows; std::vector<char> valid; u32 w = 0; hipEvent_t ev = nullptr;
-                      bool pending = false; int run_slot = -1; Row* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; };
+                      bool pending = false; Row* stage = nullptr; u32* stage_idx = nullptr; u64 stage_cap = 0; };
     Baseline<sg_edge_trend> trend;
     // K8's vanished list: allocated at sg_set_vanished (sg_plan.hpp plan_vanished), one allocation, freed by any sg_set_trend.  The
     // counts are scratch shared like the baseline; per slot: the list, its count, and whether the window in the slot made one (valid).
@@ -167,7 +165,7 @@ struct sg_engine {
     // node rows and count, and whether the window in the slot was rolled up (valid).
     struct Nodes { bool on = false; sgplan::NodesPlan plan; char* mem = nullptr; u32* dst = nullptr; K9Side* tout = nullptr; K9Side* tin = nullptr;
                    K9Side* part = nullptr; u32* blk = nullptr; std::vector<sg_node_out*> rows; std::vector<u64*> count; std::vector<char> valid;
-                   hipEvent_t ev = nullptr; bool pending = false; int run_slot = -1; } nodes;
+                   hipEvent_t ev = nullptr; bool pending = false; } nodes;
     // K10, the per-node baselines (sg_node_trend.h): a Baseline, freed with the rollup
     Baseline<sg_node_trend> ntrend;
     // node selection (K7 over node rows): scratch of plan_select(ncap) allocated at the first one, with the counter block k10_keys
@@ -183,6 +181,11 @@ struct sg_engine {
 };
 
 namespace {
+
+// the working slot; the slot of the window that ran last (its index: the stages' per-slot rows)
+sg_engine::WinSlot& work(sg_engine* e) { return e->slots[e->cur]; }
+int ran_slot(const sg_engine* e) { return e->last.slot >= 0 ? e->last.slot : e->cur; }
+sg_engine::WinSlot& ran(sg_engine* e) { return e->slots[ran_slot(e)]; }
 
 #define HIP_TRY(e, call)                                                                       \
     do {                                                                                       \
@@ -211,12 +214,14 @@ int dev_alloc(sg_engine* e, T** p, size_t n, int fill = 0) {
         HIP_TRY(e, hipMalloc(&q, bytes));
         e->allocs.push_back(q);
     }
-    HIP_TRY(e, hipMemsetAsync(q, fill, bytes, e->stream));
+    HIP_TRY(e, hipMemsetAsync(q, fill, bytes, e->slots[0].stream));   // (every clear on slot 0's stream: callers that need the zeros synchronise it)
     *p = (T*)q;
     return SG_OK;
 }
 
-hipStream_t pick(sg_engine* e, void* s) { return s ? (hipStream_t)s : e->stream; }
+hipStream_t pick(sg_engine* e, void* s) { return s ? (hipStream_t)s : work(e).stream; }
+// the same for calls on the window that ran last: the stream it ran on
+hipStream_t pick_ran(sg_engine* e, void* s) { return s ? (hipStream_t)s : e->last.slot >= 0 ? e->last.stream : work(e).stream; }
 
 hipEvent_t get_event(sg_engine* e) {
     if (!e->ev_pool.empty()) { hipEvent_t v = e->ev_pool.back(); e->ev_pool.pop_back(); return v; }
@@ -351,7 +356,7 @@ int sync_tables(sg_engine* e, hipStream_t s) {
     }
     HIP_TRY(e, hipEventRecord(e->tab_ev, s));
     e->tab_seq++; e->tab_stream = s;
-    return e->d.variant == 0 ? plan_pass_a(e) : SG_OK;
+    return e->plan.variant == 0 ? plan_pass_a(e) : SG_OK;
 }
 // K1 on stream s reads the tables: after the last modification if that ran on another stream
 int order_after_tables(sg_engine* e, hipStream_t s) {
@@ -366,57 +371,51 @@ int order_after_tables(sg_engine* e, hipStream_t s) {
 }
 
 // make slot (cur + 1) % NW the working window; the closed window keeps running on its own stream
-void rotate_window(sg_engine* e) {
-    if (e->slots.size() < 2) return;
-    sg_engine::WinSlot& a = e->slots[e->cur];
-    a.d = e->d; a.stream = e->stream; a.ob_list = e->d_ob_list; a.ob_n = e->d_ob_n; a.closed = e->closed; a.events_in = e->window_events_in;
-    e->cur = (e->cur + 1) % (int)e->slots.size();
-    const sg_engine::WinSlot& b = e->slots[e->cur];
-    e->d = b.d; e->stream = b.stream; e->d_ob_list = b.ob_list; e->d_ob_n = b.ob_n; e->closed = b.closed; e->window_events_in = b.events_in;
-}
+void rotate_window(sg_engine* e) { e->cur = (e->cur + 1) % (int)e->slots.size(); }
 
 int launch_k1(sg_engine* e, const sg_event* d_ev, size_t n, hipStream_t s) {
     if (n == 0) return SG_OK;
+    sg_engine::WinSlot& w = work(e);
     // the pass-A cache keeps 16-bit histogram bins: a workgroup must see fewer than 65536 events per launch
     const size_t kMaxHist = (size_t)65535 * 256;
-    if (e->d.hist && e->d.variant == 0 && n > kMaxHist) {
+    if (w.d.hist && w.d.variant == 0 && n > kMaxHist) {
         for (size_t o = 0; o < n; o += kMaxHist) { const int rc = launch_k1(e, d_ev + o, std::min(kMaxHist, n - o), s); if (rc) return rc; }
         return SG_OK;
     }
     const size_t kMaxTeam = (size_t)1 << 25;                             // k1a_team_partition addresses a launch's events with byte offsets below 2 GiB
-    if (e->d.variant == 0 && e->d.narrow && e->pa.k1a_team && n > kMaxTeam) {
+    if (w.d.variant == 0 && w.d.narrow && e->pa.k1a_team && n > kMaxTeam) {
         for (size_t o = 0; o < n; o += kMaxTeam) { const int rc = launch_k1(e, d_ev + o, std::min(kMaxTeam, n - o), s); if (rc) return rc; }
         return SG_OK;
     }
     int rc = sync_tables(e, s);
     if (rc) return rc;
     if ((rc = order_after_tables(e, s))) return rc;
-    if (((e->timing >> 10) & 1u) && e->window_events_in == 0 && !e->win_ta) { e->win_ta = get_event(e); hipEventRecord(e->win_ta, s); }   // group 10: the whole window
-    Dev da = e->d;
+    if (((e->timing >> 10) & 1u) && w.events_in == 0 && !e->win_ta) { e->win_ta = get_event(e); hipEventRecord(e->win_ta, s); }   // group 10: the whole window
+    Dev da = w.d;
     join_view(e, da);
-    u32 rot0 = e->d.k1a_rot, tb0 = e->d.k1a_ticket_base;
-    if (e->d.variant == 0) {
+    u32 rot0 = w.d.k1a_rot, tb0 = w.d.k1a_ticket_base;
+    if (w.d.variant == 0) {
         // single-kernel groups are timed by the dispatch's own begin/end stamps (hipExtLaunchKernel start/stop
         // events): the kernel's duration as rocprofv3 reports it, without the event-record round trip
         const bool tk = ((e->timing >> 1) & 1u) && e->closes % e->timing_stride == 0;   // (the window this batch belongs to is the closes-th)
         hipEvent_t ta = tk ? get_event(e) : nullptr, tb = tk ? get_event(e) : nullptr;
-        da.batch_state = e->window_events_in == 0 ? 1u : 0u;     // first batch of this window?
-        da.k1a_rot = e->d.k1a_rot;
-        rot0 = e->d.k1a_rot; tb0 = e->d.k1a_ticket_base;           // (restored below when the launch is refused: the device counter only moves if the kernel runs)
-        if (e->d.narrow && !e->pa.k1a_team) {                           // the next launch's first chunk goes to the workgroup behind this launch's last one
-            const u64 per = (n + e->d.nwg - 1) / e->d.nwg, chunk = per >= 4096 ? 4096 : (per + 1023) / 1024 * 1024;
-            e->d.k1a_rot = (u32)((e->d.k1a_rot + (n + chunk - 1) / chunk) % e->d.nwg);
+        da.batch_state = w.events_in == 0 ? 1u : 0u;     // first batch of this window?
+        da.k1a_rot = w.d.k1a_rot;
+        rot0 = w.d.k1a_rot; tb0 = w.d.k1a_ticket_base;           // (restored below when the launch is refused: the device counter only moves if the kernel runs)
+        if (w.d.narrow && !e->pa.k1a_team) {                           // the next launch's first chunk goes to the workgroup behind this launch's last one
+            const u64 per = (n + w.d.nwg - 1) / w.d.nwg, chunk = per >= 4096 ? 4096 : (per + 1023) / 1024 * 1024;
+            w.d.k1a_rot = (u32)((w.d.k1a_rot + (n + chunk - 1) / chunk) % w.d.nwg);
         }
-        if (e->d.narrow && e->pa.k1a_team) {
-            e->d.k1a_rot = (u32)((e->d.k1a_rot + k1m_tiles(n, e->d.nwg, e->pa.k1a_teams, e->pa.k1a_nt)) % ((u64)e->pa.k1a_teams * e->d.nwg));
-            da.k1a_ticket_base = e->d.k1a_ticket_base;
+        if (w.d.narrow && e->pa.k1a_team) {
+            w.d.k1a_rot = (u32)((w.d.k1a_rot + k1m_tiles(n, w.d.nwg, e->pa.k1a_teams, e->pa.k1a_nt)) % ((u64)e->pa.k1a_teams * w.d.nwg));
+            da.k1a_ticket_base = w.d.k1a_ticket_base;
             {   // what this launch draws from the slot's ticket counter: one per tile beyond every team's first, one failing draw per active team
-                const unsigned long long nt_ = k1m_tiles(n, e->d.nwg, e->pa.k1a_teams, e->pa.k1a_nt), units_ = (unsigned long long)e->pa.k1a_teams * e->d.nwg;
-                if (!(e->d.ablate & 0x4u)) e->d.k1a_ticket_base += (u32)((nt_ > units_ ? nt_ - units_ : 0) + std::min(units_, nt_));
+                const unsigned long long nt_ = k1m_tiles(n, w.d.nwg, e->pa.k1a_teams, e->pa.k1a_nt), units_ = (unsigned long long)e->pa.k1a_teams * w.d.nwg;
+                if (!(w.d.ablate & 0x4u)) w.d.k1a_ticket_base += (u32)((nt_ > units_ ? nt_ - units_ : 0) + std::min(units_, nt_));
             }
         }
-        const u32 threads = !e->d.narrow ? K1A_THREADS : e->pa.k1a_team ? 1024 : K1T_THREADS;
-        hipExtLaunchKernelGGL(e->fn.k1a, dim3(e->d.nwg), dim3(threads), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n);
+        const u32 threads = !w.d.narrow ? K1A_THREADS : e->pa.k1a_team ? 1024 : K1T_THREADS;
+        hipExtLaunchKernelGGL(e->fn.k1a, dim3(w.d.nwg), dim3(threads), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n);
         if (tk) { TimingRec r; r.a = ta; r.b = tb; r.kernel = 1; e->trecs.push_back(r); }
     } else {
         Timed t(e, s, 1);
@@ -429,13 +428,13 @@ int launch_k1(sg_engine* e, const sg_event* d_ev, size_t n, hipStream_t s) {
         // kernel actually runs — a refused launch must leave them where the device still is
         const hipError_t lr = hipGetLastError();
         if (lr != hipSuccess) {
-            e->d.k1a_rot = rot0; e->d.k1a_ticket_base = tb0;
+            w.d.k1a_rot = rot0; w.d.k1a_ticket_base = tb0;
             e->err = std::string("K1 pass A launch: ") + hipGetErrorString(lr);
             return lr == hipErrorOutOfMemory ? SG_ENOMEM : SG_ENODEV;
         }
     }
     e->st.events_in += n;
-    e->window_events_in += n;
+    w.events_in += n;
     return SG_OK;
 }
 
@@ -462,16 +461,18 @@ size_t layer_offset(u32 l) {
 
 // the halo request lists and the active node lists of a sharded window: many workgroups, one launch (SG_K6_ONE_WG=1: the round-3 builder)
 void launch_halo_lists(sg_engine* e, hipStream_t s, u32* req, u32 capp) {
+    sg_engine::WinSlot& w = work(e);
     if (e->plan.k6_one_wg) {
-        if (e->d.ncap <= K6_FLAGS_LDS) hipLaunchKernelGGL(k6_halo_build_padded<true>, dim3(1), dim3(1024), 0, s, e->d, req, capp);
-        else hipLaunchKernelGGL(k6_halo_build_padded<false>, dim3(1), dim3(1024), 0, s, e->d, req, capp);
+        if (w.d.ncap <= K6_FLAGS_LDS) hipLaunchKernelGGL(k6_halo_build_padded<true>, dim3(1), dim3(1024), 0, s, w.d, req, capp);
+        else hipLaunchKernelGGL(k6_halo_build_padded<false>, dim3(1), dim3(1024), 0, s, w.d, req, capp);
         return;
     }
-    hipLaunchKernelGGL(k6_halo_lists, dim3(((size_t)e->d.ncap + 1023) / 1024), dim3(1024), 0, s, e->d, req, capp, ++e->k6_epoch, 1u);
+    hipLaunchKernelGGL(k6_halo_lists, dim3(((size_t)w.d.ncap + 1023) / 1024), dim3(1024), 0, s, w.d, req, capp, ++e->k6_epoch, 1u);
 }
 // ob_mode 1: collect this engine's own raw outbound IPs; 0: caller's union list (d_union, *d_union_n);
 // 2: all-gathered per-shard lists (d_union = [world][stride], element 0 of a row = count)
 int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union_n, u32 ob_mode = 1, u32 stride = 0, u32 gworld = 0, bool fuse_in = false) {
+    sg_engine::WinSlot& w = work(e);
     int rc = sync_tables(e, s);
     if (rc) return rc;
     // When the kept state does not pay, the window is closed as an engine without it does ("plain": the kept state stays as it is, these
@@ -480,13 +481,13 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
     // those nodes are ranks among the window's own, such a window can never close warm and would pay for the kept-CSR detour every time);
     // every window brings edges the kept set lacks (the warm attempt is wasted and the rebuild carries the kept keys as well).  The host
     // learns which path its windows took from the note kw_compact leaves in page-locked memory — it never waits for the device.
-    Dev dloc = e->d;
-    if (dloc.warm && (size_t)e->cur < e->note_seen.size()) {
+    Dev dloc = w.d;
+    if (dloc.warm && w.h_note) {
         // what the device has said since we last looked (this slot's note; page-locked host memory the kw_compact of an earlier window wrote)
-        volatile u64* note = e->h_note[e->cur];
+        volatile u64* note = w.h_note;
         const u64 seq = note[0];
-        if (seq != e->note_seen[e->cur]) {
-            e->note_seen[e->cur] = seq;
+        if (seq != w.note_seen) {
+            w.note_seen = seq;
             const u64 v = note[1];
             const u32 cold = (u32)(v & 0xFFu); const bool obip = (v & 0x100ull) != 0;
             // a warm attempt that ran its merge and THEN met an unknown key is the expensive outcome (the window pays the attempt, the rebuild
@@ -499,9 +500,9 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
         }
     }
     if (dloc.warm && e->plain_left) { e->plain_left--; dloc.warm = 0; }
-    if ((size_t)e->cur < e->plain_slot.size()) e->plain_slot[e->cur] = e->d.warm && !dloc.warm;
+    w.plain = w.d.warm && !dloc.warm;
     // an engine whose plan folds kc_prepare keeps pass B's counts and order twice: this close works on the half of the slot's window parity
-    const u32 par = e->d.k1b_par & 1u;
+    const u32 par = w.d.k1b_par & 1u;
     if (e->plan.prepare_fold && dloc.k1b_order) { dloc.k1b_cnt += (size_t)par * dloc.np; dloc.k1b_order += (size_t)par * dloc.np; }
     const Dev& d = dloc;
     // warm windows: try unless switched off (the device decides whether the try holds)
@@ -511,14 +512,14 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
     const bool fold = sgplan::close_folds(e->plan, d.warm != 0, warm_try, ob_mode);
     if (!fold) {
         Timed tp(e, s, 2);
-        if (ob_mode == 1) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, e->d_ob_list, (const u32*)e->d_ob_n, e->plan.ob_list_cap, 1u, (const u32*)nullptr, 0u, 0u, wt);
+        if (ob_mode == 1) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, w.ob_list, (const u32*)w.ob_n, e->plan.ob_list_cap, 1u, (const u32*)nullptr, 0u, 0u, wt);
         else if (ob_mode == 0) hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, const_cast<u32*>(d_union), d_union_n, e->plan.ob_list_cap, 0u, (const u32*)nullptr, 0u, 0u, wt);
-        else hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, e->d_ob_list, (const u32*)e->d_ob_n, e->plan.ob_list_cap, 2u, d_union, stride, gworld, wt);
+        else hipLaunchKernelGGL(kc_prepare, dim3(1), dim3(1024), 0, s, d, (u64)e->n_known, (u64)e->n_labels_decl, w.ob_list, (const u32*)w.ob_n, e->plan.ob_list_cap, 2u, d_union, stride, gworld, wt);
     }
     if (d.variant == 0) {                                    // group 7 = K1 pass B (k1b_merge), kernel-exact timing as for pass A
         const bool tk = ((e->timing >> 7) & 1u) && e->closes % e->timing_stride == 0;
         hipEvent_t ta = tk ? get_event(e) : nullptr, tb = tk ? get_event(e) : nullptr;
-        Dev db = d; db.batch_state = e->window_events_in == 0 ? 2u : 0u;          // a window without any batch: nothing to merge
+        Dev db = d; db.batch_state = w.events_in == 0 ? 2u : 0u;          // a window without any batch: nothing to merge
         db.kept_compact = d.warm;                                                 // (a warm engine's pass B builds / feeds the kept state: compact node ids, sg_kernels.h sg_kept_compact)
         // warm engines: the warm attempt (WM 1: seeded tables, accumulators straight to their kept positions; returns at once when
         // kc_prepare has already called the window cold), then the cold merge (WM 2: returns at once on a warm window).  Both are records
@@ -530,9 +531,9 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
                 // the prepare workgroup (the launch's last): kc_prepare's arguments, and the OTHER half of the counts and the order — it sorts the
                 // counts of the window before into the order the next window reads while this window's merge reads and counts in its own half
                 dt.fold = 1u; dt.warm_try = wt; gt.x += 1;
-                dt.pf_n_known = (u64)e->n_known; dt.pf_n_labels_decl = (u64)e->n_labels_decl; dt.pf_list = e->d_ob_list; dt.pf_list_cap = e->plan.ob_list_cap;
-                dt.k1b_cnt_prev = e->d.k1b_order ? e->d.k1b_cnt + (size_t)(par ^ 1u) * d.np : nullptr;
-                dt.k1b_order_next = e->d.k1b_order ? e->d.k1b_order + (size_t)(par ^ 1u) * d.np : nullptr;
+                dt.pf_n_known = (u64)e->n_known; dt.pf_n_labels_decl = (u64)e->n_labels_decl; dt.pf_list = w.ob_list; dt.pf_list_cap = e->plan.ob_list_cap;
+                dt.k1b_cnt_prev = w.d.k1b_order ? w.d.k1b_cnt + (size_t)(par ^ 1u) * d.np : nullptr;
+                dt.k1b_order_next = w.d.k1b_order ? w.d.k1b_order + (size_t)(par ^ 1u) * d.np : nullptr;
             }
             hipExtLaunchKernelGGL(e->fn.k1b_try, gt, block, (uint32_t)e->plan.k1b_lds, s, ta, tb, 0u, dt);
             if (tk) { TimingRec r; r.a = ta; r.b = tb; r.kernel = 7; e->trecs.push_back(r); ta = get_event(e); tb = get_event(e); }
@@ -550,7 +551,7 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
         dk.kept_compact = d.warm;
         if (d.warm) {
             dk.rowptr = d.k_rowptr; dk.col = d.k_col; dk.csr_from = d.k_from; dk.acc_csr = d.k_acc; dk.max_edges = (u64)d.npb * d.pcap;
-            dk.st_sum = e->scr_sum[e->cur]; dk.st_max = e->scr_max[e->cur]; dk.row_mu = e->scr_mu[e->cur]; dk.row_sd = e->scr_mu[e->cur] + d.ncap + 1;
+            dk.st_sum = w.scr_sum; dk.st_max = w.scr_max; dk.row_mu = w.scr_mu; dk.row_sd = w.scr_mu + d.ncap + 1;
         }
         if (d.variant == 1) {
             const u32 ntiles = e->plan.ecap / K2_TILE;
@@ -587,15 +588,15 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
         }
     }
     HIP_TRY(e, hipGetLastError());
-    e->closed = true;
-    e->window_events_in = 0;
+    w.closed = true;
+    w.events_in = 0;
     e->closes++;
-    if (e->plan.prepare_fold) e->d.k1b_par ^= 1u;                    // (per slot: e->d is the slot's working copy)
+    if (e->plan.prepare_fold) w.d.k1b_par ^= 1u;
     return SG_OK;
 }
 
 int do_features(sg_engine* e, hipStream_t s) {
-    const Dev& d = e->d;
+    const Dev& d = work(e).d;
     Timed t(e, s, 3);
     const int nbn = grid_for(d.ncap, 128), nbe = grid_for(e->cfg.max_edges, 256, 4096);   // (the edge workgroups capped at 1 280 / 2 560 — whole rounds: no difference, profiles/r06_grids_ab_c3.txt)
     hipLaunchKernelGGL(k3_node_features, dim3(nbn + nbe), dim3(256), 0, s, d, (u32)nbn, e->in_fused_slices);
@@ -621,7 +622,7 @@ int note_w_read(sg_engine* e, hipStream_t s) {
 
 // fuse_proj: the last layer also writes the score head's P and Q (unsharded pipelines only)
 int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
-    const Dev& d = e->d;
+    const Dev& d = work(e).d;
     if (!e->have_w) { e->err = "sg_load_weights not called"; return SG_ESTATE; }
     const float* Wl = e->d_W + layer_offset(l);
     const float* Wh = e->d_W + layer_offset(e->cfg.layers);
@@ -641,12 +642,12 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
 static_assert(sizeof(KcScratch) <= sgplan::kPrepareLds, "a folded close's prepare workgroup lays KcScratch over pass B's dynamic LDS");
 static_assert(sizeof(sg_edge_vanished) == 64 && sgplan::kTrendThreads == K8_THREADS && sgplan::kTrendMaxWgs <= K8_SCAN_THREADS,
               "plan_trend / plan_vanished size the launches of sg_trend.h");
-// TrendArgs' baseline part of window w + 1's update of t: the window's outbound-IP list, the buffers and scratch, the parameters
+// TrendArgs' baseline part of t's next update, by the window in slot w: the window's outbound-IP list, the buffers and scratch, the parameters
 template <class Row>
-TrendArgs baseline_args(const sg_engine* e, const sg_engine::Baseline<Row>& t) {
+TrendArgs baseline_args(const sg_engine::WinSlot& w, const sg_engine::Baseline<Row>& t) {
     const sg_trend_params& p = t.p;
     TrendArgs a{};
-    a.ctr = e->d.ctr; a.ob_sorted = e->d.ob_sorted; a.max_obip = e->d.max_obip;
+    a.ctr = w.d.ctr; a.ob_sorted = w.d.ob_sorted; a.max_obip = w.d.max_obip;
     a.cap = t.plan.entries;
     a.buf[0] = t.buf[0]; a.buf[1] = t.buf[1];
     a.th = t.th; a.blk = t.blk; a.ctl = t.ctl;
@@ -667,9 +668,10 @@ int enqueue_baseline(sg_engine* e, sg_engine::Baseline<Row>& t, hipStream_t s, F
 }
 // enqueue window w's update on stream s; the window's trend rows go to the slot's buffer
 int launch_trend(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
     sg_engine::Baseline<sg_edge_trend>& t = e->trend;
-    TrendArgs a = baseline_args(e, t);
-    a.rows = e->d.rows; a.max_edges = e->cfg.max_edges; a.out = t.rows[e->cur];
+    TrendArgs a = baseline_args(w, t);
+    a.rows = w.d.rows; a.max_edges = e->cfg.max_edges; a.out = t.rows[e->cur];
     sg_engine::Vanished& v = e->vanished;
     return enqueue_baseline(e, t, s, [&] {
         if (v.on) {                                                   // the same three launches with the vanished count
@@ -693,11 +695,12 @@ static_assert(sgplan::kNodesThreads == K9_THREADS && sgplan::kNodesChunk == K9_C
               "plan_nodes sizes the launches of sg_nodes.h");
 // enqueue the rollup of the window in slot cur on stream s, behind the previous rollup (any stream)
 int launch_nodes(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
     sg_engine::Nodes& n = e->nodes;
     const sgplan::NodesPlan& P = n.plan;
     NodesArgs a{};
-    a.rows = e->d.rows; a.ctr = e->d.ctr; a.max_edges = e->cfg.max_edges;
-    a.mk = e->d.max_known; a.ml = e->d.max_labels; a.mob = e->d.max_obip; a.ncap = P.ncap;
+    a.rows = w.d.rows; a.ctr = w.d.ctr; a.max_edges = e->cfg.max_edges;
+    a.mk = w.d.max_known; a.ml = w.d.max_labels; a.mob = w.d.max_obip; a.ncap = P.ncap;
     a.slices = P.slices; a.node_per = P.node_per;
     a.dst = n.dst; a.tout = n.tout; a.tin = n.tin; a.part = n.part; a.blk = n.blk;
     a.out = n.rows[e->cur]; a.count = n.count[e->cur];
@@ -718,9 +721,10 @@ static_assert(sizeof(sg_node_trend) == 32 && sizeof(K10Sample) == 40, "sg_node_t
 // enqueue the node baseline's update by the window in slot cur on stream s (behind its rollup, on the same stream); the window's
 // node trend rows go to the slot's buffer
 int launch_node_trend(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
     sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
     NodeTrendArgs a{};
-    a.t = baseline_args(e, t);
+    a.t = baseline_args(w, t);
     a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur]; a.ncap = e->nodes.plan.ncap; a.out = t.rows[e->cur];
     if (const int rc = enqueue_baseline(e, t, s, [&] {
             hipLaunchKernelGGL(k10_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
@@ -746,11 +750,12 @@ static_assert(sgplan::kRankThreads == K11_THREADS && sgplan::kRankRangeNodes == 
 // enqueue the ranking of the window in slot cur on stream s (behind its rollup, on the same stream) and behind the previous
 // ranking (any stream): 2 * iters + 3 plain launches, the rank rows go to the slot's buffer
 int launch_rank(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
     sg_engine::Rank& r = e->rank;
     const sgplan::RankPlan& P = r.plan;
     RankArgs a{};
-    a.nd.rows = e->d.rows; a.nd.ctr = e->d.ctr; a.nd.max_edges = e->cfg.max_edges;
-    a.nd.mk = e->d.max_known; a.nd.ml = e->d.max_labels; a.nd.mob = e->d.max_obip; a.nd.ncap = P.ncap;
+    a.nd.rows = w.d.rows; a.nd.ctr = w.d.ctr; a.nd.max_edges = e->cfg.max_edges;
+    a.nd.mk = w.d.max_known; a.nd.ml = w.d.max_labels; a.nd.mob = w.d.max_obip; a.nd.ncap = P.ncap;
     a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur];
     a.slices = P.slices; a.prep_wgs = P.prep_wgs; a.damping = r.p.damping_q8; a.seed = r.p.seed; a.seed_min = r.p.seed_min_score;
     a.src = r.src; a.dst = r.dst; a.w = r.w; a.W = r.W; a.R = r.R; a.base = r.base; a.t = r.t; a.part = r.part; a.seed_sum = r.seed_sum;
@@ -801,7 +806,7 @@ void free_trend(sg_engine* e) {
 // proj_done: the last SAGE layer already wrote P and Q.  fuse_reset: fold the window reset into the
 // score kernel (unsharded variant-0 pipelines; saves a launch) — returns true through *did_reset.
 int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool* did_reset) {
-    const Dev& d = e->d;
+    const Dev& d = work(e).d;
     if (!e->have_w) { e->err = "sg_load_weights not called"; return SG_ESTATE; }
     const float* Wh = e->d_W + layer_offset(e->cfg.layers);
     const bool fr = fuse_reset && d.variant == 0;
@@ -826,10 +831,11 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
 }
 
 int do_reset(sg_engine* e, hipStream_t s) {
-    hipLaunchKernelGGL(k_reset_window, dim3(grid_for(std::max<u64>((u64)e->d.ncap * SG_NODE_STAT_SUM_WORDS, e->plan.obcap), 256, 512)), dim3(256), 0, s, e->d);
+    sg_engine::WinSlot& w = work(e);
+    hipLaunchKernelGGL(k_reset_window, dim3(grid_for(std::max<u64>((u64)w.d.ncap * SG_NODE_STAT_SUM_WORDS, e->plan.obcap), 256, 512)), dim3(256), 0, s, w.d);
     HIP_TRY(e, hipGetLastError());
-    e->closed = false;
-    e->window_events_in = 0;            // (an open window that is reset is discarded: the next batch is a first batch again)
+    w.closed = false;
+    w.events_in = 0;            // (an open window that is reset is discarded: the next batch is a first batch again)
     return SG_OK;
 }
 
@@ -844,6 +850,7 @@ void window_timed_end(sg_engine* e, hipStream_t s) {
 
 // the window counters in e->h_ctr -> running statistics (engine lock held)
 void account_window(sg_engine* e) {
+    sg_engine::WinSlot& w = work(e);
     const size_t E = (size_t)e->h_ctr[C_N_EDGES];
     sg_stats& st = e->st;
     st.windows++;
@@ -857,8 +864,8 @@ void account_window(sg_engine* e) {
     st.alive_in += e->h_ctr[C_ALIVE_SEEN];
     st.alive_dropped += e->h_ctr[C_ALIVE_DROPPED];
     st.last_window_new_edges = 0;
-    if (e->d.warm && (size_t)e->cur < e->plain_slot.size() && e->plain_slot[e->cur]) st.windows_plain++;
-    else if (e->d.warm) {
+    if (w.d.warm && w.plain) st.windows_plain++;
+    else if (w.d.warm) {
         // (counters of the slot that was read: with several windows in flight every slot keeps its own state and its own counts)
         // (kw_compact's copies: the window reset, which may or may not have run by now, zeroes C_COLD and C_DELTA_N for the next close)
         const bool cold = e->h_ctr[C_LAST_COLD] != 0;
@@ -886,20 +893,21 @@ int view_reserve(sg_engine* e, size_t E) {
 }
 // view != nullptr: the rows go to the engine's page-locked buffer and *view points at them (out / cap unused)
 int do_read(sg_engine* e, sg_edge_out* out, size_t cap, size_t* n, const sg_edge_out** view = nullptr) {
+    sg_engine::WinSlot& w = work(e);
     HIP_TRY(e, hipDeviceSynchronize());
-    HIP_TRY(e, hipMemcpy(e->h_ctr, e->d.ctr, sizeof(e->h_ctr), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(e->h_ctr, w.d.ctr, sizeof(e->h_ctr), hipMemcpyDeviceToHost));
     const size_t E = (size_t)e->h_ctr[C_N_EDGES];
     if (n) *n = E;
     if (view) {
         { const int rc = view_reserve(e, E); if (rc) return rc; }
-        if (E) HIP_TRY(e, hipMemcpy(e->h_rows, e->d.rows, E * sizeof(sg_edge_out), hipMemcpyDeviceToHost));
+        if (E) HIP_TRY(e, hipMemcpy(e->h_rows, w.d.rows, E * sizeof(sg_edge_out), hipMemcpyDeviceToHost));
         *view = e->h_rows;
     }
     const size_t take = view ? 0 : std::min(E, cap);
-    if (out && take) HIP_TRY(e, hipMemcpy(out, e->d.rows, take * sizeof(sg_edge_out), hipMemcpyDeviceToHost));
+    if (out && take) HIP_TRY(e, hipMemcpy(out, w.d.rows, take * sizeof(sg_edge_out), hipMemcpyDeviceToHost));
     const size_t nob = (size_t)e->h_ctr[C_N_OBIP];
     e->last_obips.resize(nob);
-    if (nob) HIP_TRY(e, hipMemcpy(e->last_obips.data(), e->d.ob_sorted, nob * sizeof(u32), hipMemcpyDeviceToHost));
+    if (nob) HIP_TRY(e, hipMemcpy(e->last_obips.data(), w.d.ob_sorted, nob * sizeof(u32), hipMemcpyDeviceToHost));
     account_window(e);
     return SG_OK;
 }
@@ -980,7 +988,7 @@ int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_scor
 int nsel_reserve(sg_engine* e) {
     sg_engine::NSel& s = e->nsel;
     if (s.keys) return SG_OK;
-    const u64 NC = std::max<u32>(e->d.ncap, 1);
+    const u64 NC = std::max<u32>(e->plan.ncap, 1);
     s.plan = sgplan::plan_select(NC, true);
     const sgplan::SelPlan& p = s.plan;
     const u64 ctr_bytes = sgplan::trend_align(sizeof(e->h_ctr)), idx_bytes = sgplan::trend_align(NC * 4);
@@ -1002,7 +1010,7 @@ int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_
                        u64 cap, u64* d_n, Keys keys, After after) {
     sg_engine::NSel& s = e->nsel;
     const u32 wgs = s.plan.wgs;
-    const u64 NC = std::max<u32>(e->d.ncap, 1);
+    const u64 NC = std::max<u32>(e->plan.ncap, 1);
     SelArgs a{};
     a.rows = nullptr; a.ctr = s.ctr; a.max_edges = NC; a.k = k; a.min_score = min_value;
     sel_scratch_args(a, s);
@@ -1050,7 +1058,7 @@ int node_top_host(sg_engine* e, L launch, sg_node_out* out, sg_node_rank* rank_o
                   size_t* n_nodes) {
     if (const int rc = nsel_reserve(e)) return rc;
     sg_engine::NSel& s = e->nsel;
-    const u64 NC = std::max<u32>(e->d.ncap, 1);
+    const u64 NC = std::max<u32>(e->plan.ncap, 1);
     const u64 stage = std::min<u64>(cap, NC);
     if (const int rc = launch(out ? s.stage : nullptr, rank_out ? e->rank.stage : nullptr, stage, s.n)) return rc;
     u64 cnt = 0;
@@ -1200,10 +1208,12 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
     CR(sgplan::make_plan(*cfg, facts, e->ov, &e->plan, &e->err));
     const sgplan::Plan& P = e->plan;
     CH(hipSetDevice(cfg->device));
-    CH(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    e->slots.resize(P.n_slots);
+    CH(hipStreamCreateWithFlags(&e->slots[0].stream, hipStreamNonBlocking));   // (ahead of the other slots': dev_alloc clears on it)
     CH(hipEventCreateWithFlags(&e->tab_ev, hipEventDisableTiming));
 
-    Dev& d = e->d;
+    // the engine-wide part of every slot's Dev: the plan's fields, the join tables, the weights and the two tables below
+    Dev base{}; Dev& d = base;
     sgplan::plan_to_dev(P, *cfg, d);
     const u64 ME = cfg->max_edges;
     // join tables: word image (join_host.hpp) on the host, one device copy, a pinned ring for word updates
@@ -1240,8 +1250,18 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
     CH(lds_limit(P.k3in_lds, k3_in_part));
     CR(dev_alloc(e, &d.dbg, (size_t)4 * 4096 * 8));
     CR(dev_alloc(e, &d.clk, (size_t)4));
+    CR(dev_alloc(e, &e->d_W, weights_count(cfg->layers)));
+    d.W = e->d_W;
+    {   // (float)log1p((double)i) for small integer counts, by the device's own log1p
+        float* tab = nullptr;
+        CR(dev_alloc(e, &tab, (size_t)SG_L1P_TAB));
+        hipLaunchKernelGGL(k_l1p_table, dim3((SG_L1P_TAB + 255) / 256), dim3(256), 0, e->slots[0].stream, tab);
+        CH(hipStreamSynchronize(e->slots[0].stream));
+        d.l1p_tab = tab;
+    }
     // everything a window owns; allocated once per slot
-    auto alloc_window = [&](Dev& w, u32*& ob_list, u32*& ob_n) -> int {
+    auto alloc_window = [&](sg_engine::WinSlot& slot) -> int {
+        Dev& w = slot.d;
 #define LR(call) do { int _rc = (call); if (_rc) return _rc; } while (0)
         size_t eslots = ME;
         if (w.variant == 0) {
@@ -1252,7 +1272,7 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
                                 LR(dev_alloc(e, &w.k1b_cnt, halves * w.np)); LR(dev_alloc(e, &w.k1b_order, halves * w.np));
                                 std::vector<u32> ident(halves * w.np);
                                 for (size_t i = 0; i < ident.size(); i++) ident[i] = (u32)(i % w.np);
-                                HIP_TRY(e, hipStreamSynchronize(e->stream));   // (dev_alloc clears on the engine's stream, which the copy below does not order itself behind)
+                                HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));   // (dev_alloc clears on slot 0's stream, which the copy below does not order itself behind)
                                 HIP_TRY(e, hipMemcpy(w.k1b_order, ident.data(), ident.size() * sizeof(u32), hipMemcpyHostToDevice));
                             } }
             else { LR(dev_alloc(e, &w.slab_s, (size_t)w.np * w.nwg * w.pslots)); LR(dev_alloc(e, &w.hdr, (size_t)w.np * w.nwg)); }
@@ -1274,15 +1294,12 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
                 LR(dev_alloc(e, &w.dc_rowptr, (size_t)w.ncap + 2)); LR(dev_alloc(e, &w.dc_col, KC)); LR(dev_alloc(e, &w.dc_from, KC)); LR(dev_alloc(e, &w.dc_acc, KC * 4));
                 LR(dev_alloc(e, &w.dc_slot, KC)); LR(dev_alloc(e, &w.dc_ip, KC)); LR(dev_alloc(e, &w.dl_img, KC));
                 LR(dev_alloc(e, &w.deg2, ((size_t)w.ncap + 1) * SG_DEG_REP * SG_DEG_STRIDE));
-                u64* a = nullptr; u64* b = nullptr; double* c = nullptr;
-                LR(dev_alloc(e, &a, (size_t)w.ncap * SG_NODE_STAT_SUM_WORDS)); LR(dev_alloc(e, &b, (size_t)w.ncap * SG_NODE_STAT_MAX_WORDS)); LR(dev_alloc(e, &c, 2 * ((size_t)w.ncap + 1)));
-                e->scr_sum.push_back(a); e->scr_max.push_back(b); e->scr_mu.push_back(c);
-                u64* hn = nullptr; void* dn = nullptr;
-                HIP_TRY(e, hipHostMalloc((void**)&hn, 64, hipHostMallocMapped));
-                hn[0] = hn[1] = 0;
-                HIP_TRY(e, hipHostGetDevicePointer(&dn, hn, 0));
+                LR(dev_alloc(e, &slot.scr_sum, (size_t)w.ncap * SG_NODE_STAT_SUM_WORDS)); LR(dev_alloc(e, &slot.scr_max, (size_t)w.ncap * SG_NODE_STAT_MAX_WORDS)); LR(dev_alloc(e, &slot.scr_mu, 2 * ((size_t)w.ncap + 1)));
+                void* dn = nullptr;
+                HIP_TRY(e, hipHostMalloc((void**)&slot.h_note, 64, hipHostMallocMapped));
+                slot.h_note[0] = slot.h_note[1] = 0;
+                HIP_TRY(e, hipHostGetDevicePointer(&dn, slot.h_note, 0));
                 w.host_note = (u64*)dn;
-                e->h_note.push_back(hn); e->note_seen.push_back(0);
             }
         }
         const size_t KE = P.kept_edges;                               // arrays the rebuild indexes by KEPT position on a warm engine
@@ -1293,8 +1310,8 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
         LR(dev_alloc(e, &w.wgstat, (size_t)SG_MAX_K1_WGS * WS_WORDS));
         LR(dev_alloc(e, &w.ctr, C_COUNT));
         LR(dev_alloc(e, &w.ob_sorted, w.max_obip));
-        LR(dev_alloc(e, &ob_list, P.ob_list_cap));
-        LR(dev_alloc(e, &ob_n, 4));
+        LR(dev_alloc(e, &slot.ob_list, P.ob_list_cap));
+        LR(dev_alloc(e, &slot.ob_n, 4));
         LR(dev_alloc(e, &w.tile_cnt, P.ecap / K2_TILE));
         LR(dev_alloc(e, &w.tile_off, P.ecap / K2_TILE));
         LR(dev_alloc(e, &w.e_slot, ME)); LR(dev_alloc(e, &w.e_from, eslots)); LR(dev_alloc(e, &w.e_to, eslots));
@@ -1323,16 +1340,12 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
 #undef LR
         return SG_OK;
     };
-    CH(hipStreamSynchronize(e->stream));
-    CR(alloc_window(d, e->d_ob_list, e->d_ob_n));
-    CR(dev_alloc(e, &e->d_W, weights_count(cfg->layers)));
-    d.W = e->d_W;
-    {   // (float)log1p((double)i) for small integer counts, by the device's own log1p
-        float* tab = nullptr;
-        CR(dev_alloc(e, &tab, (size_t)SG_L1P_TAB));
-        hipLaunchKernelGGL(k_l1p_table, dim3((SG_L1P_TAB + 255) / 256), dim3(256), 0, e->stream, tab);
-        CH(hipStreamSynchronize(e->stream));
-        d.l1p_tab = tab;
+    CH(hipStreamSynchronize(e->slots[0].stream));
+    // every slot: the same tables and weights, its own window buffers and stream
+    for (sg_engine::WinSlot& slot : e->slots) {
+        slot.d = base;
+        if (!slot.stream) CH(hipStreamCreateWithFlags(&slot.stream, hipStreamNonBlocking));
+        CR(alloc_window(slot));
     }
     CH(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking)); CH(hipStreamCreateWithFlags(&e->copy_stream2, hipStreamNonBlocking));
     CH(hipStreamCreateWithFlags(&e->rd_stream, hipStreamNonBlocking)); CH(hipEventCreateWithFlags(&e->score_ev, hipEventDisableTiming));
@@ -1343,20 +1356,7 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
         CR(dev_alloc(e, &e->d_stage[i], e->cfg.max_batch));
         CH(hipEventCreateWithFlags(&e->stage_ev[i], hipEventDisableTiming));
     }
-    CH(hipStreamSynchronize(e->stream));
-    // further windows in flight: same tables and weights, own window buffers and stream
-    {
-        const u32 nw = P.n_slots;
-        e->slots.resize(nw); e->plain_slot.assign(nw, 0);
-        e->slots[0] = sg_engine::WinSlot{e->d, e->stream, e->d_ob_list, e->d_ob_n, false, 0};
-        for (u32 k = 1; k < nw; k++) {
-            sg_engine::WinSlot& w = e->slots[k];
-            w.d = e->d; w.closed = false; w.events_in = 0; w.ob_list = nullptr; w.ob_n = nullptr; w.stream = nullptr;
-            CH(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-            CR(alloc_window(w.d, w.ob_list, w.ob_n));
-        }
-        CH(hipDeviceSynchronize());
-    }
+    CH(hipDeviceSynchronize());
 #undef CR
 #undef CH
     *out = e;
@@ -1366,8 +1366,7 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
 int sg_destroy(sg_handle e) {
     if (!e) return SG_EINVAL;
     hipDeviceSynchronize();
-    for (size_t k = 0; k < e->slots.size(); k++) if ((int)k != e->cur && e->slots[k].stream) hipStreamDestroy(e->slots[k].stream);
-    for (u64* hn : e->h_note) hipHostFree(hn);
+    for (sg_engine::WinSlot& w : e->slots) { if (w.stream) hipStreamDestroy(w.stream); if (w.h_note) hipHostFree(w.h_note); }
     for (void* p : e->allocs) hipFree(p);
     if (e->h_blob) hipHostFree(e->h_blob);
     for (int i = 0; i < kUpdSlots; i++) { if (e->h_upd[i]) hipHostFree(e->h_upd[i]); if (e->upd_ev[i]) hipEventDestroy(e->upd_ev[i]); }
@@ -1395,7 +1394,6 @@ int sg_destroy(sg_handle e) {
     for (auto& r : e->trecs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto v : e->ev_pool) hipEventDestroy(v);
     if (e->tab_ev) hipEventDestroy(e->tab_ev);
-    if (e->stream) hipStreamDestroy(e->stream);
     delete e;
     return SG_OK;
 }
@@ -1484,15 +1482,16 @@ int stage_take(sg_engine* e) {
 hipStream_t stage_stream(sg_engine* e) { return (e->plan.n_copy == 2 && (e->copy_rr++ & 1)) ? e->copy_stream2 : e->copy_stream; }
 // behind a slot's copy (already enqueued on `cs`, or refused): K1 pass A on the window's stream, the slot handed back (engine lock held)
 int stage_finish(sg_engine* e, int slot, size_t n, hipStream_t cs, bool copy_ok) {
+    sg_engine::WinSlot& w = work(e);
     int rc = SG_OK;
     if (!copy_ok) { e->err = "hipMemcpyAsync (staging ring)"; rc = SG_ENODEV; }
     if (rc == SG_OK) {
         hipEventRecord(e->copied_ev[slot], cs);
-        hipStreamWaitEvent(e->stream, e->copied_ev[slot], 0);
+        hipStreamWaitEvent(w.stream, e->copied_ev[slot], 0);
         e->st.h2d_bytes += n * sizeof(sg_event);
-        rc = launch_k1(e, e->d_stage[slot], n, e->stream);
+        rc = launch_k1(e, e->d_stage[slot], n, w.stream);
     }
-    hipEventRecord(e->stage_ev[slot], e->stream);                        // the slot is free again when pass A has read it
+    hipEventRecord(e->stage_ev[slot], w.stream);                        // the slot is free again when pass A has read it
     e->stage_busy[slot] = false; e->pending_copies--;
     e->cv.notify_all();
     return rc;
@@ -1615,7 +1614,7 @@ int sg_window_obip_list(sg_handle e, uint32_t* d_list, uint32_t cap, uint32_t* d
     if (!e || !d_list || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     hipStream_t s = pick(e, stream);
-    hipLaunchKernelGGL(k2_ob_collect, dim3(1), dim3(1024), 0, s, e->d, d_list, cap, d_n);
+    hipLaunchKernelGGL(k2_ob_collect, dim3(1), dim3(1024), 0, s, work(e).d, d_list, cap, d_n);
     HIP_TRY(e, hipGetLastError());
     return SG_OK;
 }
@@ -1625,9 +1624,10 @@ int sg_window_obip_list(sg_handle e, uint32_t* d_list, uint32_t cap, uint32_t* d
 int sg_bind_buffers(sg_handle e, void* stats_sum, void* stats_max, void* const* feat_rows, uint32_t n_feat) {
     if (!e || n_feat > e->cfg.layers) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (stats_sum) e->d.st_sum = (u64*)stats_sum;
-    if (stats_max) e->d.st_max = (u64*)stats_max;
-    for (u32 l = 0; l < n_feat; l++) if (feat_rows && feat_rows[l]) e->d.h[l + 1] = (float*)feat_rows[l];
+    sg_engine::WinSlot& w = work(e);
+    if (stats_sum) w.d.st_sum = (u64*)stats_sum;
+    if (stats_max) w.d.st_max = (u64*)stats_max;
+    for (u32 l = 0; l < n_feat; l++) if (feat_rows && feat_rows[l]) w.d.h[l + 1] = (float*)feat_rows[l];
     return SG_OK;
 }
 
@@ -1656,7 +1656,7 @@ int sg_halo_build_padded(sg_handle e, uint32_t* d_req, uint32_t capp, void* stre
     std::lock_guard<std::mutex> g(e->mu);
     hipStream_t s = pick(e, stream);
     Timed t(e, s, 6);
-    hipLaunchKernelGGL(k6_halo_mark, dim3(grid_for(e->cfg.max_edges, 256)), dim3(256), 0, s, e->d);
+    hipLaunchKernelGGL(k6_halo_mark, dim3(grid_for(e->cfg.max_edges, 256)), dim3(256), 0, s, work(e).d);
     launch_halo_lists(e, s, d_req, capp);
     HIP_TRY(e, hipGetLastError());
     return SG_OK;
@@ -1666,7 +1666,7 @@ int sg_halo_pack_padded(sg_handle e, uint32_t l, const uint32_t* d_serve, uint32
     std::lock_guard<std::mutex> g(e->mu);
     hipStream_t s = pick(e, stream);
     Timed t(e, s, 6);
-    hipLaunchKernelGGL(k6_pack_padded, dim3(grid_for((u64)e->cfg.world * capp * 16, 256)), dim3(256), 0, s, e->d.h[l], d_serve, capp, e->cfg.world, d_rows);
+    hipLaunchKernelGGL(k6_pack_padded, dim3(grid_for((u64)e->cfg.world * capp * 16, 256)), dim3(256), 0, s, work(e).d.h[l], d_serve, capp, e->cfg.world, d_rows);
     HIP_TRY(e, hipGetLastError());
     return SG_OK;
 }
@@ -1675,7 +1675,7 @@ int sg_halo_unpack_padded(sg_handle e, uint32_t l, const uint32_t* d_req, uint32
     std::lock_guard<std::mutex> g(e->mu);
     hipStream_t s = pick(e, stream);
     Timed t(e, s, 6);
-    hipLaunchKernelGGL(k6_unpack_padded, dim3(grid_for((u64)e->cfg.world * capp * 16, 256)), dim3(256), 0, s, e->d.h[l], d_req, capp, e->cfg.world, d_rows);
+    hipLaunchKernelGGL(k6_unpack_padded, dim3(grid_for((u64)e->cfg.world * capp * 16, 256)), dim3(256), 0, s, work(e).d.h[l], d_req, capp, e->cfg.world, d_rows);
     HIP_TRY(e, hipGetLastError());
     return SG_OK;
 }
@@ -1683,29 +1683,29 @@ int sg_halo_unpack_padded(sg_handle e, uint32_t l, const uint32_t* d_req, uint32
 int sg_window_features(sg_handle e, void* stream) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->closed) { e->err = "sg_window_features before sg_window_close"; return SG_ESTATE; }
+    if (!work(e).closed) { e->err = "sg_window_features before sg_window_close"; return SG_ESTATE; }
     return do_features(e, pick(e, stream));
 }
 int sg_window_layer(sg_handle e, uint32_t l, void* stream) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->closed || l >= e->cfg.layers) { e->err = "sg_window_layer: bad phase or layer"; return SG_ESTATE; }
+    if (!work(e).closed || l >= e->cfg.layers) { e->err = "sg_window_layer: bad phase or layer"; return SG_ESTATE; }
     return do_layer(e, l, pick(e, stream), false);
 }
 int sg_window_score(sg_handle e, void* stream) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->closed) { e->err = "sg_window_score before sg_window_close"; return SG_ESTATE; }
+    if (!work(e).closed) { e->err = "sg_window_score before sg_window_close"; return SG_ESTATE; }
     return do_score(e, pick(e, stream), false, false, nullptr);
 }
 int sg_window_score_reset(sg_handle e, void* stream) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->closed) { e->err = "sg_window_score_reset before sg_window_close"; return SG_ESTATE; }
+    if (!work(e).closed) { e->err = "sg_window_score_reset before sg_window_close"; return SG_ESTATE; }
     bool did = false;
     int rc = do_score(e, pick(e, stream), false, true, &did);
     if (rc) return rc;
-    if (did) { e->closed = false; return SG_OK; }
+    if (did) { work(e).closed = false; return SG_OK; }
     return do_reset(e, pick(e, stream));
 }
 int sg_window_read(sg_handle e, sg_edge_out* out, size_t cap, size_t* n) {
@@ -1713,7 +1713,8 @@ int sg_window_read(sg_handle e, sg_edge_out* out, size_t cap, size_t* n) {
     std::lock_guard<std::mutex> g(e->mu);
     // (after sg_window_score_reset / sg_window_run_sharded the window is open again, but its rows and counters are still in
     // place until the next batch is ingested: readable)
-    if (!e->closed && !(e->last_rows == e->d.rows && e->window_events_in == 0)) { e->err = "sg_window_read before sg_window_close"; return SG_ESTATE; }
+    const sg_engine::WinSlot& w = work(e);
+    if (!w.closed && !(e->last.slot == e->cur && w.events_in == 0)) { e->err = "sg_window_read before sg_window_close"; return SG_ESTATE; }
     return do_read(e, out, cap, n);
 }
 int sg_window_reset(sg_handle e, void* stream) {
@@ -1742,18 +1743,19 @@ int flush_begin_locked(sg_engine* e, std::unique_lock<std::mutex>& g, bool rows_
     e->closing = true;                                                   // later feeders wait instead of slipping batches into the closing window
     e->cv.wait(g, [&] { return e->pending_copies == 0; });
     struct Open { sg_engine* e; ~Open() { e->closing = false; e->cv.notify_all(); } } open{e};
-    hipStream_t s = e->stream;
+    sg_engine::WinSlot& w = work(e);
+    hipStream_t s = w.stream;
     int rc;
     if ((rc = do_close(e, s, nullptr, nullptr, 1u, 0u, 0u, true))) return rc;
     if ((rc = do_features(e, s))) return rc;
     for (u32 l = 0; l < e->cfg.layers; l++) if ((rc = do_layer(e, l, s, true))) return rc;
     bool did = false;
     if ((rc = do_score(e, s, true, true, &did))) return rc;
-    e->fl_rows = e->d.rows; e->fl_ob = e->d.ob_sorted;
+    e->fl_rows = w.d.rows; e->fl_ob = w.d.ob_sorted;
     if (did) {                                                           // the window is open again in stream order: fetch later, unlocked
-        HIP_TRY(e, hipMemcpyAsync(e->h_ctr_pin, e->d.ctr, sizeof(e->h_ctr), hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipMemcpyAsync(e->h_ctr_pin, w.d.ctr, sizeof(e->h_ctr), hipMemcpyDeviceToHost, s));
         HIP_TRY(e, hipEventRecord(e->score_ev, s));
-        e->closed = false;
+        w.closed = false;
         e->flush_async = true;
     } else {                                                             // (variant 1: the reset is its own launch and must follow the read)
         size_t n = 0; const sg_edge_out* v = nullptr;
@@ -1910,11 +1912,9 @@ int sg_window_select(sg_handle e, uint32_t k, float min_score, sg_edge_out* d_ou
     std::lock_guard<std::mutex> g(e->mu);
     if (const int rc = sel_reserve(e, 0)) return rc;
     SelArgs a{};
-    a.rows = e->last_rows ? e->last_rows : e->d.rows;
-    a.ctr = e->last_rows ? e->last_ctr : e->d.ctr;
+    a.rows = ran(e).d.rows; a.ctr = ran(e).d.ctr;
     a.out = d_out; a.out_idx = d_index; a.cap = cap; a.n_out = reinterpret_cast<u64*>(d_n);
-    hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
-    return launch_select(e, s, a, k, min_score);
+    return launch_select(e, pick_ran(e, stream), a, k, min_score);
 }
 
 // ---- K7 by a trend key ------------------------------------------------------------------------------------------------------
@@ -1951,12 +1951,10 @@ int sg_window_select_by(sg_handle e, uint32_t by, uint32_t k, float min_value, s
     if (const int rc = check_by(e, by)) return rc;
     if (const int rc = sel_reserve(e, 0)) return rc;
     SelArgs a{};
-    a.rows = e->last_rows ? e->last_rows : e->d.rows;
-    a.ctr = e->last_rows ? e->last_ctr : e->d.ctr;
+    a.rows = ran(e).d.rows; a.ctr = ran(e).d.ctr;
     a.out = d_out; a.out_idx = d_index; a.cap = cap; a.n_out = reinterpret_cast<u64*>(d_n);
-    const sg_edge_trend* tr = by != SG_SEL_SCORE ? e->trend.rows[e->trend.run_slot >= 0 ? e->trend.run_slot : e->cur] : nullptr;
-    hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
-    return launch_select(e, s, a, k, min_value, by, tr);
+    const sg_edge_trend* tr = by != SG_SEL_SCORE ? e->trend.rows[ran_slot(e)] : nullptr;
+    return launch_select(e, pick_ran(e, stream), a, k, min_value, by, tr);
 }
 
 // ---- K8, the per-edge baselines ------------------------------------------------------------------------------------------------
@@ -1982,7 +1980,7 @@ int sg_window_trend_buffer(sg_handle e, void** d_trend) {
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Baseline<sg_edge_trend>& t = e->trend;
     if (!t.on) { e->err = "sg_window_trend_buffer: the trend is off (sg_set_trend)"; return SG_ESTATE; }
-    *d_trend = t.rows[t.run_slot >= 0 ? t.run_slot : e->cur];
+    *d_trend = t.rows[ran_slot(e)];
     return SG_OK;
 }
 int sg_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
@@ -2009,7 +2007,7 @@ int sg_set_vanished(sg_handle e, const sg_vanished_params* p) {
     free_vanished(e);
     if (!p) return SG_OK;
     sg_engine::Vanished& v = e->vanished;
-    const u32 slots = (u32)std::max<size_t>(e->slots.size(), 1);
+    const u32 slots = (u32)e->slots.size();
     v.p = r;
     v.plan = sgplan::plan_vanished(e->trend.plan, slots, r);
     const sgplan::VanishedPlan& P = v.plan;
@@ -2042,7 +2040,7 @@ int sg_window_vanished_buffer(sg_handle e, void** d_rows, void** d_count) {
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Vanished& v = e->vanished;
     if (!v.on) { e->err = "sg_window_vanished_buffer: the vanished list is off (sg_set_vanished)"; return SG_ESTATE; }
-    const int slot = e->trend.run_slot >= 0 ? e->trend.run_slot : e->cur;
+    const int slot = ran_slot(e);
     if (!v.valid[slot]) { e->err = "sg_window_vanished_buffer: the window was closed while the vanished list was off"; return SG_ESTATE; }
     *d_rows = v.rows[slot]; *d_count = v.count[slot];
     return SG_OK;
@@ -2057,8 +2055,8 @@ int sg_set_nodes(sg_handle e, int on) {
     if (!on) { free_nodes(e); return SG_OK; }
     sg_engine::Nodes& n = e->nodes;
     if (n.on) return SG_OK;
-    const u32 slots = (u32)std::max<size_t>(e->slots.size(), 1);
-    n.plan = sgplan::plan_nodes(e->cfg.max_edges, e->d.ncap, slots);
+    const u32 slots = (u32)e->slots.size();
+    n.plan = sgplan::plan_nodes(e->cfg.max_edges, e->plan.ncap, slots);
     const sgplan::NodesPlan& P = n.plan;
     HIP_TRY(e, lds_limit(P.lds_bytes, k9_in_part));
     HIP_TRY(e, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
@@ -2094,7 +2092,7 @@ int sg_window_nodes_buffer(sg_handle e, void** d_nodes, void** d_count) {
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Nodes& x = e->nodes;
     if (!x.on) { e->err = "sg_window_nodes_buffer: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
-    const int slot = x.run_slot >= 0 ? x.run_slot : e->cur;
+    const int slot = ran_slot(e);
     if (!x.valid[slot]) { e->err = "sg_window_nodes_buffer: the window was closed while the node rollup was off"; return SG_ESTATE; }
     *d_nodes = x.rows[slot]; *d_count = x.count[slot];
     return SG_OK;
@@ -2133,7 +2131,7 @@ int sg_window_node_trend_buffer(sg_handle e, void** d_trend) {
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
     if (!t.on) { e->err = "sg_window_node_trend_buffer: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
-    const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
+    const int slot = ran_slot(e);
     if (!t.valid[slot]) { e->err = "sg_window_node_trend_buffer: the window was closed while the node trend was off"; return SG_ESTATE; }
     *d_trend = t.rows[slot];
     return SG_OK;
@@ -2178,11 +2176,10 @@ int sg_window_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min_value
                            uint64_t* d_n, void* stream) {
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
+    const int slot = ran_slot(e);
     if (const int rc = check_nsel(e, by, slot)) return rc;
     if (const int rc = nsel_reserve(e)) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
-    return launch_node_select_by(e, s, slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return launch_node_select_by(e, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // ---- K11, the culprit ranking ---------------------------------------------------------------------------------------------------
@@ -2196,7 +2193,7 @@ int sg_set_rank(sg_handle e, const sg_rank_params* p) {
     free_rank(e);
     if (!p) return SG_OK;
     sg_engine::Rank& r = e->rank;
-    const u32 slots = (u32)std::max<size_t>(e->slots.size(), 1);
+    const u32 slots = (u32)e->slots.size();
     r.p = q;
     r.plan = sgplan::plan_rank(e->cfg.max_edges, e->nodes.plan.ncap, slots);
     const sgplan::RankPlan& P = r.plan;
@@ -2252,7 +2249,7 @@ int sg_window_rank_buffer(sg_handle e, void** d_rank) {
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Rank& r = e->rank;
     if (!r.on) { e->err = "sg_window_rank_buffer: the ranking is off (sg_set_rank)"; return SG_ESTATE; }
-    const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
+    const int slot = ran_slot(e);
     if (!r.valid[slot]) { e->err = "sg_window_rank_buffer: the window was closed while the ranking was off"; return SG_ESTATE; }
     *d_rank = r.rows[slot];
     return SG_OK;
@@ -2278,11 +2275,10 @@ int sg_window_rank_top(sg_handle e, uint32_t k, float min_share, sg_node_out* ou
 int sg_window_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n, void* stream) {
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const int slot = e->nodes.run_slot >= 0 ? e->nodes.run_slot : e->cur;
+    const int slot = ran_slot(e);
     if (const int rc = check_rsel(e, slot)) return rc;
     if (const int rc = nsel_reserve(e)) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : (e->last_rows ? e->last_stream : e->stream);
-    return launch_rank_select(e, s, slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return launch_rank_select(e, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.
@@ -2347,23 +2343,23 @@ int rc_all_to_all(void* x, const void* send, void* recv, size_t bytes) {        
 }
 struct ShardCtx { sg_engine* e; hipStream_t s; };
 #define SCX ShardCtx* x = (ShardCtx*)p; sg_engine* e = x->e; hipStream_t s = x->s
-int st_obip_list(void* p) { SCX; hipLaunchKernelGGL(k2_ob_collect, dim3(1), dim3(1024), 0, s, e->d, e->xc.ob_local + 1, e->xc.ob_stride - 1, e->xc.ob_local); return hipGetLastError() == hipSuccess ? SG_OK : SG_ENODEV; }
+int st_obip_list(void* p) { SCX; hipLaunchKernelGGL(k2_ob_collect, dim3(1), dim3(1024), 0, s, work(e).d, e->xc.ob_local + 1, e->xc.ob_stride - 1, e->xc.ob_local); return hipGetLastError() == hipSuccess ? SG_OK : SG_ENODEV; }
 int st_close(void* p) { SCX; return do_close(e, s, e->xc.ob_all, nullptr, 2u, e->xc.ob_stride, e->cfg.world); }
 int st_features(void* p) { SCX; return do_features(e, s); }
 int st_halo_build(void* p) {
     SCX; Timed t(e, s, 6);
-    hipLaunchKernelGGL(k6_halo_mark, dim3(grid_for(e->cfg.max_edges, 256)), dim3(256), 0, s, e->d);
+    hipLaunchKernelGGL(k6_halo_mark, dim3(grid_for(e->cfg.max_edges, 256)), dim3(256), 0, s, work(e).d);
     launch_halo_lists(e, s, e->xc.req, e->xc.capp);
     return hipGetLastError() == hipSuccess ? SG_OK : SG_ENODEV;
 }
 int st_layer(void* p, uint32_t l) { SCX; return do_layer(e, l, s, false); }
-int st_pack(void* p, uint32_t l) { SCX; Timed t(e, s, 6); hipLaunchKernelGGL(k6_pack_padded, dim3(grid_for((u64)e->cfg.world * e->xc.capp * 16, 256)), dim3(256), 0, s, e->d.h[l], e->xc.serve, e->xc.capp, e->cfg.world, e->xc.rows_out); return hipGetLastError() == hipSuccess ? SG_OK : SG_ENODEV; }
-int st_unpack(void* p, uint32_t l) { SCX; Timed t(e, s, 6); hipLaunchKernelGGL(k6_unpack_padded, dim3(grid_for((u64)e->cfg.world * e->xc.capp * 16, 256)), dim3(256), 0, s, e->d.h[l], e->xc.req, e->xc.capp, e->cfg.world, e->xc.rows_in); return hipGetLastError() == hipSuccess ? SG_OK : SG_ENODEV; }
+int st_pack(void* p, uint32_t l) { SCX; Timed t(e, s, 6); hipLaunchKernelGGL(k6_pack_padded, dim3(grid_for((u64)e->cfg.world * e->xc.capp * 16, 256)), dim3(256), 0, s, work(e).d.h[l], e->xc.serve, e->xc.capp, e->cfg.world, e->xc.rows_out); return hipGetLastError() == hipSuccess ? SG_OK : SG_ENODEV; }
+int st_unpack(void* p, uint32_t l) { SCX; Timed t(e, s, 6); hipLaunchKernelGGL(k6_unpack_padded, dim3(grid_for((u64)e->cfg.world * e->xc.capp * 16, 256)), dim3(256), 0, s, work(e).d.h[l], e->xc.req, e->xc.capp, e->cfg.world, e->xc.rows_in); return hipGetLastError() == hipSuccess ? SG_OK : SG_ENODEV; }
 int st_score(void* p) {
     SCX; bool did = false;
     int rc = do_score(e, s, false, true, &did);
     if (rc) return rc;
-    if (did) { e->closed = false; return SG_OK; }
+    if (did) { work(e).closed = false; return SG_OK; }
     return do_reset(e, s);
 }
 #undef SCX
@@ -2406,18 +2402,19 @@ int sg_window_run_sharded(sg_handle e, sg_comm* c, void* stream) {
     if (!e || !c || (u32)c->world != e->cfg.world || (u32)c->rank != e->cfg.rank) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
     e->cv.wait(g, [&] { return e->pending_copies == 0; });
+    sg_engine::WinSlot& w = work(e);
     hipStream_t s = pick(e, stream);
     const u32 W = e->cfg.world;
     if (!e->xc.ob_local) {                                           // first call: the exchange buffers
         sg_engine::Xchg& x = e->xc;
-        x.ob_stride = e->d.max_obip + 1;
-        x.capp = std::max<u32>(1, std::min<u32>(e->d.ncap, 2 * ((e->d.ncap + W - 1) / W) + 1024));   // rows one shard may ask ONE owner for: twice an owner's mean share
+        x.ob_stride = w.d.max_obip + 1;
+        x.capp = std::max<u32>(1, std::min<u32>(w.d.ncap, 2 * ((w.d.ncap + W - 1) / W) + 1024));   // rows one shard may ask ONE owner for: twice an owner's mean share
         if ((u64)(x.ob_stride - 1) * W > e->plan.ob_list_cap) { e->err = "gathered outbound-ip lists exceed the engine's list capacity"; return SG_ENOSPC; }
         int rc;
         if ((rc = dev_alloc(e, &x.ob_local, x.ob_stride)) || (rc = dev_alloc(e, &x.ob_all, (size_t)W * x.ob_stride)) ||
             (rc = dev_alloc(e, &x.req, (size_t)W * (x.capp + 1))) || (rc = dev_alloc(e, &x.serve, (size_t)W * (x.capp + 1))) ||
             (rc = dev_alloc(e, &x.rows_out, (size_t)W * x.capp * SG_F_HID)) || (rc = dev_alloc(e, &x.rows_in, (size_t)W * x.capp * SG_F_HID))) return rc;
-        HIP_TRY(e, hipStreamSynchronize(e->stream));                 // (dev_alloc clears on the engine's own stream)
+        HIP_TRY(e, hipStreamSynchronize(e->slots[0].stream));       // (dev_alloc clears on slot 0's stream)
     }
     c->stream = s; c->eng = e;
     ShardCtx cx{e, s};
@@ -2426,17 +2423,15 @@ int sg_window_run_sharded(sg_handle e, sg_comm* c, void* stream) {
     st.obip_list = st_obip_list; st.close_gathered = st_close; st.features = st_features; st.halo_build = st_halo_build;
     st.layer = st_layer; st.pack = st_pack; st.unpack = st_unpack; st.score = st_score;
     st.ob_local = e->xc.ob_local; st.ob_all = e->xc.ob_all; st.ob_bytes = (size_t)e->xc.ob_stride * 4;
-    st.stats_sum = e->d.st_sum; st.stats_sum_words = (size_t)e->d.ncap * SG_NODE_STAT_SUM_WORDS;
-    st.stats_max = e->d.st_max; st.stats_max_words = (size_t)e->d.ncap * SG_NODE_STAT_MAX_WORDS;
+    st.stats_sum = w.d.st_sum; st.stats_sum_words = (size_t)w.d.ncap * SG_NODE_STAT_SUM_WORDS;
+    st.stats_max = w.d.st_max; st.stats_max_words = (size_t)w.d.ncap * SG_NODE_STAT_MAX_WORDS;
     st.req = e->xc.req; st.serve = e->xc.serve; st.list_bytes = (size_t)(e->xc.capp + 1) * 4;
     st.rows_out = e->xc.rows_out; st.rows_in = e->xc.rows_in; st.rows_bytes = (size_t)e->xc.capp * SG_F_HID * 4;
     sg_shard_comm sc{c, rc_all_gather, rc_all_reduce, rc_all_to_all, rc_group_begin, rc_group_end};
     const int rc = sg_run_sharded_window(&st, &sc);
     if (rc) { if (e->err.empty()) e->err = "sg_window_run_sharded: a stage or a collective failed"; return rc; }
     window_timed_end(e, s);
-    e->last_rows = e->d.rows; e->last_ctr = e->d.ctr; e->last_stream = s;
-    e->trend.run_slot = e->cur;
-    e->nodes.run_slot = e->cur;
+    e->last = {e->cur, s};
     return SG_OK;
 }
 
@@ -2453,6 +2448,7 @@ int sg_window_run(sg_handle e, void* stream) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
     e->cv.wait(g, [&] { return e->pending_copies == 0; });
+    sg_engine::WinSlot& w = work(e);
     hipStream_t s = pick(e, stream);
     int rc;
     if ((rc = do_close(e, s, nullptr, nullptr, 1u, 0u, 0u, true))) return rc;
@@ -2460,32 +2456,30 @@ int sg_window_run(sg_handle e, void* stream) {
     for (u32 l = 0; l < e->cfg.layers; l++) if ((rc = do_layer(e, l, s, true))) return rc;
     bool did = false;
     if ((rc = do_score(e, s, true, true, &did))) return rc;
-    if (did) e->closed = false; else if ((rc = do_reset(e, s))) return rc;
+    if (did) w.closed = false; else if ((rc = do_reset(e, s))) return rc;
     window_timed_end(e, s);
-    e->last_rows = e->d.rows; e->last_ctr = e->d.ctr; e->last_stream = s;
-    e->trend.run_slot = e->cur;
-    e->nodes.run_slot = e->cur;
+    e->last = {e->cur, s};
     rotate_window(e);                                    // the next sg_ingest* goes to the next slot (if any)
     return SG_OK;
 }
 
 int sg_window_buffers(sg_handle e, void** stats_sum, void** stats_max, void** counters, size_t* n_nodes_cap) {
     if (!e) return SG_EINVAL;
-    if (stats_sum) *stats_sum = e->d.st_sum;
-    if (stats_max) *stats_max = e->d.st_max;
-    if (counters) *counters = e->d.ctr;
-    if (n_nodes_cap) *n_nodes_cap = e->d.ncap;
+    if (stats_sum) *stats_sum = work(e).d.st_sum;
+    if (stats_max) *stats_max = work(e).d.st_max;
+    if (counters) *counters = work(e).d.ctr;
+    if (n_nodes_cap) *n_nodes_cap = work(e).d.ncap;
     return SG_OK;
 }
 int sg_window_feat_buffer(sg_handle e, uint32_t l, void** rows, size_t* row_floats) {
     if (!e || l > e->cfg.layers) return SG_EINVAL;
-    if (rows) *rows = l == 0 ? (void*)e->d.x0 : (void*)e->d.h[l];
+    if (rows) *rows = l == 0 ? (void*)work(e).d.x0 : (void*)work(e).d.h[l];
     if (row_floats) *row_floats = l == 0 ? SG_F_IN : SG_F_HID;
     return SG_OK;
 }
 int sg_window_rows_buffer(sg_handle e, void** rows) {
     if (!e || !rows) return SG_EINVAL;
-    *rows = e->last_rows ? e->last_rows : e->d.rows;
+    *rows = ran(e).d.rows;
     return SG_OK;
 }
 
@@ -2493,12 +2487,13 @@ int sg_halo_build(sg_handle e, uint32_t* d_ids, uint32_t cap, uint32_t* d_counts
     if (!e || !d_ids || !d_counts) return SG_EINVAL;
     if (e->cfg.world > 8) { e->err = "halo lists support at most 8 shards (one node)"; return SG_EINVAL; }
     std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::WinSlot& w = work(e);
     hipStream_t s = pick(e, stream);
     Timed t(e, s, 6);
-    hipLaunchKernelGGL(k6_halo_mark, dim3(grid_for(e->cfg.max_edges, 256)), dim3(256), 0, s, e->d);
-    if (e->d.ncap <= K6_FLAGS_LDS) hipLaunchKernelGGL(k6_active_lists<true>, dim3(1), dim3(1024), 0, s, e->d);
-    else hipLaunchKernelGGL(k6_active_lists<false>, dim3(1), dim3(1024), 0, s, e->d);
-    hipLaunchKernelGGL(k6_halo_build, dim3(1), dim3(256), 0, s, e->d, d_ids, cap, d_counts);
+    hipLaunchKernelGGL(k6_halo_mark, dim3(grid_for(e->cfg.max_edges, 256)), dim3(256), 0, s, w.d);
+    if (w.d.ncap <= K6_FLAGS_LDS) hipLaunchKernelGGL(k6_active_lists<true>, dim3(1), dim3(1024), 0, s, w.d);
+    else hipLaunchKernelGGL(k6_active_lists<false>, dim3(1), dim3(1024), 0, s, w.d);
+    hipLaunchKernelGGL(k6_halo_build, dim3(1), dim3(256), 0, s, w.d, d_ids, cap, d_counts);
     HIP_TRY(e, hipGetLastError());
     return SG_OK;
 }
@@ -2508,7 +2503,7 @@ int sg_halo_pack(sg_handle e, uint32_t l, const uint32_t* d_ids, uint32_t n, flo
     std::lock_guard<std::mutex> g(e->mu);
     hipStream_t s = pick(e, stream);
     Timed t(e, s, 6);
-    hipLaunchKernelGGL(k6_pack, dim3(grid_for((u64)n * 16, 256)), dim3(256), 0, s, e->d.h[l], d_ids, n, d_rows);
+    hipLaunchKernelGGL(k6_pack, dim3(grid_for((u64)n * 16, 256)), dim3(256), 0, s, work(e).d.h[l], d_ids, n, d_rows);
     HIP_TRY(e, hipGetLastError());
     return SG_OK;
 }
@@ -2518,7 +2513,7 @@ int sg_halo_unpack(sg_handle e, uint32_t l, const uint32_t* d_ids, uint32_t n, c
     std::lock_guard<std::mutex> g(e->mu);
     hipStream_t s = pick(e, stream);
     Timed t(e, s, 6);
-    hipLaunchKernelGGL(k6_unpack, dim3(grid_for((u64)n * 16, 256)), dim3(256), 0, s, e->d.h[l], d_ids, n, d_rows);
+    hipLaunchKernelGGL(k6_unpack, dim3(grid_for((u64)n * 16, 256)), dim3(256), 0, s, work(e).d.h[l], d_ids, n, d_rows);
     HIP_TRY(e, hipGetLastError());
     return SG_OK;
 }
@@ -2534,11 +2529,11 @@ int sg_window_outbound_ips(sg_handle e, uint32_t* ips, size_t cap, size_t* n) {
 int sg_window_hist(sg_handle e, uint32_t* bins, size_t cap_rows, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->d.hist) { e->err = "sg_window_hist: the engine was created without SG_CFG_EDGE_HISTOGRAM"; return SG_ESTATE; }
+    if (!e->plan.hist) { e->err = "sg_window_hist: the engine was created without SG_CFG_EDGE_HISTOGRAM"; return SG_ESTATE; }
     const size_t E = (size_t)e->h_ctr[C_N_EDGES];                      // of the last read window
     if (n) *n = E;
     const size_t take = std::min(E, cap_rows);
-    if (bins && take) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipMemcpy(bins, e->d.hist_csr, take * SG_HIST_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost)); }
+    if (bins && take) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipMemcpy(bins, work(e).d.hist_csr, take * SG_HIST_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost)); }
     return SG_OK;
 }
 
@@ -2575,7 +2570,7 @@ int sg_debug_stamps(sg_handle e, uint64_t* out, size_t n) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     HIP_TRY(e, hipDeviceSynchronize());
-    HIP_TRY(e, hipMemcpy(out, e->d.dbg, std::min<size_t>(n, (size_t)4 * 4096 * 8) * sizeof(u64), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(out, work(e).d.dbg, std::min<size_t>(n, (size_t)4 * 4096 * 8) * sizeof(u64), hipMemcpyDeviceToHost));
     return SG_OK;
 }
 // The shader clock the chip sustains ("fast box / slow box"): spin_mhz from an all-CU integer spin of about
@@ -2584,14 +2579,15 @@ int sg_debug_stamps(sg_handle e, uint64_t* out, size_t n) {
 int sg_clock_probe(sg_handle e, uint32_t spin_us, double* spin_mhz, double* k1a_mhz) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::WinSlot& w = work(e);
     HIP_TRY(e, hipDeviceSynchronize());
     const u32 iters = std::max<u32>(1000u, spin_us * 120u);           // ~20 cycles per trip of the dependent chain at ~2.4 GHz
-    hipLaunchKernelGGL(k_clock_spin, dim3(1024), dim3(256), 0, e->stream, e->d.clk, iters);
+    hipLaunchKernelGGL(k_clock_spin, dim3(1024), dim3(256), 0, w.stream, w.d.clk, iters);
     HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, hipStreamSynchronize(w.stream));
     u64 h[4] = {};
-    HIP_TRY(e, hipMemcpy(h, e->d.clk, sizeof(h), hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemset(e->d.clk, 0, sizeof(h)));
+    HIP_TRY(e, hipMemcpy(h, w.d.clk, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemset(w.d.clk, 0, sizeof(h)));
     if (spin_mhz) *spin_mhz = h[3] ? 100.0 * (double)h[2] / (double)h[3] : 0.0;
     if (k1a_mhz) *k1a_mhz = h[1] ? 100.0 * (double)h[0] / (double)h[1] : 0.0;
     return SG_OK;
@@ -2638,18 +2634,19 @@ int sg_timing_samples(sg_handle e, int kernel, double* us, size_t cap, size_t* n
 int sg_latency_probe(sg_handle e, uint64_t bytes, uint32_t steps, int warm, double* ns_per_load) {
     if (!e || !ns_per_load || bytes < 4096 || steps == 0) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::WinSlot& w = work(e);
     u64 lines = 1; while (lines * 2 * 128 <= bytes) lines *= 2;         // a power of two: x -> a x + c (a % 4 == 1, c odd) visits every line
     if (lines > (1ull << 31)) lines = 1ull << 31;
     u32* buf = nullptr; u64* out = nullptr;
     HIP_TRY(e, hipDeviceSynchronize());
     HIP_TRY(e, hipMalloc((void**)&buf, lines * 128));
     if (hipMalloc((void**)&out, 2 * sizeof(u64)) != hipSuccess) { hipFree(buf); e->err = "sg_latency_probe: hipMalloc"; return SG_ENOMEM; }
-    hipLaunchKernelGGL(k_chase_init, dim3((unsigned)std::min<u64>((lines + 255) / 256, 65535)), dim3(256), 0, e->stream, buf, (u32)(lines - 1));
-    if (warm & 1) hipLaunchKernelGGL(k_chase, dim3(1), dim3(1), 0, e->stream, (const u32*)buf, (u32)lines, out);   // one whole round: every line is in the cache level it fits
-    if (warm & 2) hipLaunchKernelGGL(k_chase, dim3(1024), dim3(64), 0, e->stream, (const u32*)buf, steps, out);    // 65 536 chains in flight: the latency under load
-    else hipLaunchKernelGGL(k_chase, dim3(1), dim3(1), 0, e->stream, (const u32*)buf, steps, out);
+    hipLaunchKernelGGL(k_chase_init, dim3((unsigned)std::min<u64>((lines + 255) / 256, 65535)), dim3(256), 0, w.stream, buf, (u32)(lines - 1));
+    if (warm & 1) hipLaunchKernelGGL(k_chase, dim3(1), dim3(1), 0, w.stream, (const u32*)buf, (u32)lines, out);   // one whole round: every line is in the cache level it fits
+    if (warm & 2) hipLaunchKernelGGL(k_chase, dim3(1024), dim3(64), 0, w.stream, (const u32*)buf, steps, out);    // 65 536 chains in flight: the latency under load
+    else hipLaunchKernelGGL(k_chase, dim3(1), dim3(1), 0, w.stream, (const u32*)buf, steps, out);
     u64 h[2] = {};
-    hipError_t r = hipStreamSynchronize(e->stream);
+    hipError_t r = hipStreamSynchronize(w.stream);
     if (r == hipSuccess) r = hipMemcpy(h, out, sizeof h, hipMemcpyDeviceToHost);
     hipFree(buf); hipFree(out);
     if (r != hipSuccess) { e->err = std::string("sg_latency_probe: ") + hipGetErrorString(r); return SG_ENODEV; }
