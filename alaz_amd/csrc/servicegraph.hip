@@ -28,6 +28,7 @@
 #include "sg_trend.h"
 #include "sg_node_trend.h"
 #include "sg_rank.h"
+#include "sg_incident.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -178,6 +179,14 @@ struct sg_engine {
                   u64* W = nullptr; u64* R = nullptr; u64* base = nullptr; u64* t = nullptr; u64* part = nullptr; u64* seed_sum = nullptr;
                   sg_node_rank* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_node_rank*> rows; std::vector<char> valid;
                   hipEvent_t ev = nullptr; bool pending = false; } rank;
+    // K12, the incidents (sg_incident.h): allocated at sg_set_incidents (sg_plan.hpp plan_incidents), one allocation, freed with the
+    // rollup (and with the edge trend when its key is a trend key).  The per-node-key arrays, the per-incident keys and the head
+    // counts are scratch shared by the window slots: every grouping waits for the previous one (ev), whichever slot's stream it
+    // runs on.  Per slot: the incident rows, their count, the incident per node row, and whether the window in the slot was grouped.
+    struct Incidents { bool on = false; sg_incident_params p{}; sgplan::IncidentPlan plan; char* mem = nullptr; u32* parent = nullptr; u32* flag = nullptr;
+                       u32* lab = nullptr; u32* num = nullptr; u32* kinc = nullptr; K12Keys* keys = nullptr; u32* blk = nullptr; u32* stage = nullptr;
+                       u32* stage_idx = nullptr; std::vector<sg_incident_out*> rows; std::vector<u64*> count; std::vector<u32*> node_inc;
+                       std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } inc;
 };
 
 namespace {
@@ -783,7 +792,50 @@ void free_rank(sg_engine* e) {
     r = sg_engine::Rank{};
 }
 
+// ---- K12, the incidents (engine lock held) -----------------------------------------------------------------------------------------
+static_assert(sgplan::kIncThreads == K12_THREADS && sgplan::kIncMaxWgs == K12_MAX_WGS && sgplan::kIncKeysBytes == sizeof(K12Keys),
+              "plan_incidents sizes the launches of sg_incident.h");
+// enqueue the grouping of the window in slot cur on stream s (behind its trend rows, its rollup and its ranking, on the same stream)
+// and behind the previous grouping (any stream): eight plain launches, the incidents go to the slot's buffers
+int launch_incidents(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
+    sg_engine::Incidents& x = e->inc;
+    const sgplan::IncidentPlan& P = x.plan;
+    IncArgs a{};
+    a.nd.rows = w.d.rows; a.nd.ctr = w.d.ctr; a.nd.max_edges = e->cfg.max_edges;
+    a.nd.mk = w.d.max_known; a.nd.ml = w.d.max_labels; a.nd.mob = w.d.max_obip; a.nd.ncap = P.ncap;
+    a.nd.blk = x.blk; a.nd.count = x.count[e->cur];                  // (k9_scan: the head counts in, their scan and the incident count out)
+    a.nodes = e->nodes.rows[e->cur]; a.ncount = e->nodes.count[e->cur];
+    a.trend = x.p.by != SG_SEL_SCORE ? e->trend.rows[e->cur] : nullptr;
+    a.rank = e->rank.on ? e->rank.rows[e->cur] : nullptr;
+    a.by = x.p.by; a.min_value = x.p.min_value; a.node_per = P.node_per;
+    a.parent = x.parent; a.flag = x.flag; a.lab = x.lab; a.num = x.num; a.kinc = x.kinc; a.keys = x.keys;
+    a.out = x.rows[e->cur]; a.node_inc = x.node_inc[e->cur];
+    if (x.pending) HIP_TRY(e, hipStreamWaitEvent(s, x.ev, 0));
+    const dim3 nt(K12_THREADS), gg(P.grid_wgs), ng(P.node_wgs);
+    hipLaunchKernelGGL(k12_init, gg, nt, 0, s, a);
+    hipLaunchKernelGGL(k12_hook, dim3(P.hook_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k12_label, ng, nt, 0, s, a);
+    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a.nd, P.node_wgs);
+    hipLaunchKernelGGL(k12_number, ng, nt, 0, s, a);
+    hipLaunchKernelGGL(k12_nodes, gg, nt, 0, s, a);
+    hipLaunchKernelGGL(k12_rows, dim3(P.row_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k12_finish, gg, nt, 0, s, a);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(x.ev, s));
+    x.pending = true;
+    x.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_incidents(sg_engine* e) {
+    sg_engine::Incidents& x = e->inc;
+    if (x.mem) { hipDeviceSynchronize(); hipFree(x.mem); }
+    if (x.ev) hipEventDestroy(x.ev);
+    x = sg_engine::Incidents{};
+}
+
 void free_nodes(sg_engine* e) {
+    free_incidents(e);
     free_rank(e);
     free_baseline(e->ntrend);
     sg_engine::Nodes& n = e->nodes;
@@ -825,7 +877,8 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     if (e->nodes.on) {
         if (const int rc = launch_nodes(e, s)) return rc;
         if (e->ntrend.on) { if (const int rc = launch_node_trend(e, s)) return rc; }
-        if (e->rank.on) return launch_rank(e, s);                    // K11 behind K9: the rows, the counters, the node rows and their count
+        if (e->rank.on) { if (const int rc = launch_rank(e, s)) return rc; }   // K11 behind K9: the rows, the counters, the node rows and their count
+        if (e->inc.on) return launch_incidents(e, s);                // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
     }
     return SG_OK;
 }
@@ -1965,8 +2018,9 @@ int sg_set_trend(sg_handle e, const sg_trend_params* p) {
     std::unique_lock<std::mutex> g(e->mu);
     if (e->closing || e->flush_open) { e->err = "sg_set_trend while a flush is open"; return SG_ESTATE; }
     free_trend(e);
-    if (!p) return SG_OK;
-    return baseline_on(e, e->trend, r, sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r), "sg_set_trend", [e] { free_trend(e); });
+    auto drop_incidents = [e] { if (e->inc.on && e->inc.p.by != SG_SEL_SCORE) free_incidents(e); };   // (their key is a trend row's)
+    if (!p) { drop_incidents(); return SG_OK; }
+    return baseline_on(e, e->trend, r, sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r), "sg_set_trend", [e, drop_incidents] { free_trend(e); drop_incidents(); });
 }
 int sg_window_trend(sg_handle e, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
@@ -2279,6 +2333,101 @@ int sg_window_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out*
     if (const int rc = check_rsel(e, slot)) return rc;
     if (const int rc = nsel_reserve(e)) return rc;
     return launch_rank_select(e, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
+}
+
+// ---- K12, the incidents -----------------------------------------------------------------------------------------------------------
+int sg_set_incidents(sg_handle e, const sg_incident_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->nodes.on) { e->err = "sg_set_incidents: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_incidents while a flush is open"; return SG_ESTATE; }
+    sg_incident_params q{};
+    if (p && sgplan::check_incidents(*p, &q)) { e->err = "sg_set_incidents: bad parameters"; return SG_EINVAL; }
+    if (p && q.by != SG_SEL_SCORE && !e->trend.on) { e->err = "sg_set_incidents by a trend key: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    free_incidents(e);
+    if (!p) return SG_OK;
+    sg_engine::Incidents& x = e->inc;
+    const u32 slots = (u32)e->slots.size();
+    x.p = q;
+    x.plan = sgplan::plan_incidents(e->cfg.max_edges, e->nodes.plan.ncap, slots);
+    const sgplan::IncidentPlan& P = x.plan;
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_incidents", [e] { free_incidents(e); })) return rc;
+    char* b = x.mem;                                                  // (every piece is 256-aligned)
+    x.keys = (K12Keys*)b; b += P.keys_bytes;
+    x.parent = (u32*)b; b += P.key_bytes; x.flag = (u32*)b; b += P.key_bytes; x.lab = (u32*)b; b += P.key_bytes;
+    x.num = (u32*)b; b += P.key_bytes; x.kinc = (u32*)b; b += P.key_bytes;
+    x.blk = (u32*)b; b += P.blk_bytes;
+    x.stage = (u32*)b; b += P.stage_bytes; x.stage_idx = (u32*)b; b += P.stage_bytes;
+    for (u32 k = 0; k < slots; k++) {
+        x.rows.push_back((sg_incident_out*)b); b += P.rows_bytes; x.count.push_back((u64*)b); b += P.count_bytes;
+        x.node_inc.push_back((u32*)b); b += P.node_inc_bytes;
+    }
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+namespace {
+// the stage on, no flush open, and the last read window grouped; then its grouping done
+int incidents_ready(sg_engine* e, const char* call) {
+    sg_engine::Incidents& x = e->inc;
+    if (!x.on) { e->err = std::string(call) + ": the incidents are off (sg_set_incidents)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (!x.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while the incidents were off"; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    return SG_OK;
+}
+}  // namespace
+int sg_window_incidents(sg_handle e, sg_incident_out* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = incidents_ready(e, "sg_window_incidents")) return rc;
+    const sg_engine::Incidents& x = e->inc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, x.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    if (n) *n = (size_t)cnt;
+    const size_t take = std::min((size_t)cnt, cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, x.rows[e->cur], take * sizeof(sg_incident_out), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+int sg_window_node_incident(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = incidents_ready(e, "sg_window_node_incident")) return rc;
+    sg_engine::Incidents& x = e->inc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const size_t N = (size_t)cnt;
+    const u32* src = x.node_inc[e->cur];
+    if (!node_index) {
+        if (n) *n = N;
+        const size_t take = std::min(N, cap);
+        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(u32), hipMemcpyDeviceToHost));
+        return SG_OK;
+    }
+    for (size_t k = 0; k < n_index; k++) if (node_index[k] >= N) { e->err = "sg_window_node_incident: a node index beyond the window's nodes"; return SG_EINVAL; }
+    if (n) *n = n_index;
+    const size_t take = std::min(n_index, cap), chunk = std::max<size_t>(x.plan.ncap, 1);
+    if (!out) return SG_OK;
+    for (size_t o = 0; o < take; o += chunk) {                        // (the staging holds ncap values: a longer index goes in pieces)
+        const size_t m = std::min(chunk, take - o);
+        HIP_TRY(e, hipMemcpyAsync(x.stage_idx, node_index + o, m * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
+        hipLaunchKernelGGL(k12_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)x.stage_idx, (u64)m, x.stage);
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipMemcpyAsync(out + o, x.stage, m * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
+        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    }
+    return SG_OK;
+}
+int sg_window_incidents_buffer(sg_handle e, void** d_incidents, void** d_count, void** d_node_incident) {
+    if (!e || !d_incidents || !d_count || !d_node_incident) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Incidents& x = e->inc;
+    if (!x.on) { e->err = "sg_window_incidents_buffer: the incidents are off (sg_set_incidents)"; return SG_ESTATE; }
+    const int slot = ran_slot(e);
+    if (!x.valid[slot]) { e->err = "sg_window_incidents_buffer: the window was closed while the incidents were off"; return SG_ESTATE; }
+    *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
+    return SG_OK;
 }
 
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.

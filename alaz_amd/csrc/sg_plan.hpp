@@ -671,6 +671,60 @@ inline RankPlan plan_rank(u64 max_edges, u32 ncap, u32 slots) {
     return r;
 }
 
+// K12, the incidents (sg_incident.h): parameters and the device memory sg_set_incidents allocates — never sg_create or
+// sg_set_nodes.  Work is in K9's node-key space (ncap): five u32 arrays by node key (parent, flag, label, number, incident) and the
+// max fields' keys by incident (a window has at most as many incidents as node rows) are scratch shared by the window slots, with
+// the head counts k9_scan scans.  k12_label / k12_number take one 256-thread workgroup per block of node_per node rows, at most
+// 1024 blocks (K9's rule); k12_init, k12_nodes and k12_finish run a grid-stride grid over ncap; k12_hook one over max_edges, at
+// most 1024 workgroups; k12_rows at most 256 (every workgroup adds its LDS table to the incidents once: fewer workgroups, fewer
+// device atomics on one incident).  Each slot keeps its incident rows, their count and the incident per node row; one staging
+// block serves sg_window_node_incident's index form.
+constexpr u32 kIncThreads = 256, kIncMaxWgs = 1024, kIncMaxRowWgs = 256, kIncRowsPerThread = 4;
+constexpr u64 kIncKeysBytes = 24;         // worst, top, rmax
+inline int check_incidents(const sg_incident_params& p, sg_incident_params* out) {
+    if (p.struct_size != sizeof(sg_incident_params) || p.reserved != 0 || p.by > SG_SEL_ERR_DEV) return SG_EINVAL;
+    *out = p;
+    return SG_OK;
+}
+struct IncidentPlan {
+    u32 ncap = 0;
+    u32 node_wgs = 0, node_per = 0;   // k12_label / k12_number: workgroups, node rows per workgroup (a multiple of 256)
+    u32 grid_wgs = 0;             // k12_init, k12_nodes, k12_finish: grid-stride over ncap
+    u32 hook_wgs = 0;             // k12_hook: grid-stride over max_edges
+    u32 row_wgs = 0;              // k12_rows: grid-stride over max_edges (and ncap)
+    u64 key_bytes = 0;            // one per-node-key u32 array [ncap] (parent, flag, lab, num, kinc: five of them)
+    u64 keys_bytes = 0;           // [ncap] x 24 bytes: the max fields' keys per incident
+    u64 blk_bytes = 0;            // [2][1024] u32
+    u64 stage_bytes = 0;          // [ncap] u32 staging, and [ncap] u32 for the index (two of them)
+    u64 rows_bytes = 0;           // one window slot's incidents: [ncap] sg_incident_out
+    u64 count_bytes = 0;          // one window slot's incident count (u64)
+    u64 node_inc_bytes = 0;       // one window slot's incident per node row: [ncap] u32
+    u64 total_bytes = 0;          // the scratch, the staging and every slot's buffers, each 256-byte aligned
+};
+inline IncidentPlan plan_incidents(u64 max_edges, u32 ncap, u32 slots) {
+    IncidentPlan r;
+    const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(ncap, 1);
+    r.ncap = ncap;
+    r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kIncMaxWgs, (NC + kIncThreads - 1) / kIncThreads));
+    const u64 per = (NC + r.node_wgs - 1) / r.node_wgs;
+    r.node_per = (u32)((per + kIncThreads - 1) / kIncThreads * kIncThreads);
+    r.node_wgs = (u32)((NC + r.node_per - 1) / r.node_per);
+    r.grid_wgs = (u32)std::max<u64>(1, std::min<u64>(kIncMaxWgs, (NC + kIncThreads - 1) / kIncThreads));
+    const u64 row_blocks = (ME + (u64)kIncRowsPerThread * kIncThreads - 1) / ((u64)kIncRowsPerThread * kIncThreads);
+    r.hook_wgs = (u32)std::max<u64>(1, std::min<u64>(kIncMaxWgs, row_blocks));
+    r.row_wgs = (u32)std::max<u64>(1, std::min<u64>(kIncMaxRowWgs, row_blocks));
+    r.key_bytes = trend_align(NC * 4);
+    r.keys_bytes = trend_align(NC * kIncKeysBytes);
+    r.blk_bytes = trend_align(2ull * kIncMaxWgs * 4);
+    r.stage_bytes = trend_align(NC * 4);
+    r.rows_bytes = trend_align(NC * sizeof(sg_incident_out));
+    r.count_bytes = trend_align(8);
+    r.node_inc_bytes = trend_align(NC * 4);
+    r.total_bytes = 5 * r.key_bytes + r.keys_bytes + r.blk_bytes + 2 * r.stage_bytes +
+                    (u64)std::max<u32>(slots, 1) * (r.rows_bytes + r.count_bytes + r.node_inc_bytes);
+    return r;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

@@ -50,6 +50,7 @@ EXPORTS = [
     "sg_set_node_trend", "sg_window_node_trend", "sg_window_node_trend_buffer", "sg_node_trend_entries", "sg_node_trend_stats_get",
     "sg_window_nodes_top", "sg_window_nodes_select",
     "sg_set_rank", "sg_window_rank", "sg_window_rank_buffer", "sg_window_rank_top", "sg_window_rank_select",
+    "sg_set_incidents", "sg_window_incidents", "sg_window_node_incident", "sg_window_incidents_buffer",
 ]
 
 #: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
@@ -69,6 +70,12 @@ RANK_DTYPE = np.dtype([("rank", "<u8"), ("ref", "<u4"), ("share", "<f4")])
 RANK_SEED = dict(score=0, uniform=1)
 #: sg_rank_params defaults (a 0 in the struct means the same: iters 20, damping_q8 218)
 RANK_DEFAULTS = dict(iters=0, damping_q8=0, seed="score", seed_min_score=0.0)
+#: sg_incident_out (72 bytes) of include/servicegraph.h: one incident of a window (K12), a connected component of its red rows
+INCIDENT_DTYPE = np.dtype([(f, "<u8") for f in ("count", "err", "sum_ns", "score_q32", "rank_sum")]
+                          + [(f, "<u4") for f in ("first_node", "nodes", "edges", "worst_row", "top_node", "culprit_node")]
+                          + [("value_max", "<f4"), ("reserved", "<u4")])
+#: SG_NO_INCIDENT: a node row in no incident; culprit_node with the ranking off
+NO_INCIDENT = 0xFFFFFFFF
 #: sg_edge_vanished (64 bytes) of include/servicegraph.h: one baseline entry that went silent (K8's vanished list)
 VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
                            ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4"), ("row", "<u4"), ("reserved", "<u4")])
@@ -134,6 +141,10 @@ class SgVanishedParams(C.Structure):
 class SgRankParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("iters", C.c_uint32), ("damping_q8", C.c_uint32), ("seed", C.c_uint32),
                 ("seed_min_score", C.c_float), ("reserved", C.c_uint32)]
+
+
+class SgIncidentParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("by", C.c_uint32), ("min_value", C.c_float), ("reserved", C.c_uint32)]
 
 
 class SgTrendStats(C.Structure):
@@ -247,6 +258,9 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_window_rank_buffer": (C.c_int, [H, C.POINTER(C.c_void_p)]),
         "sg_window_rank_top": (C.c_int, [H, u32, C.c_float, P, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
         "sg_window_rank_select": (C.c_int, [H, u32, C.c_float, P, P, sz, P, P]),
+        "sg_set_incidents": (C.c_int, [H, P]), "sg_window_incidents": (C.c_int, [H, P, sz, C.POINTER(sz)]),
+        "sg_window_node_incident": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
+        "sg_window_incidents_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -698,6 +712,47 @@ class ServiceGraph:
                                             C.byref(ns), C.byref(nn)))
         m = min(ns.value, cap)
         return out[:m], rk[:m], idx[:m], nn.value
+
+    # ---- incidents (K12): the window's red rows grouped into connected components ----
+    def set_incidents(self, params: Optional[dict] = (), **kw):
+        """Switch the per-window incident grouping on (sg_set_incidents; by = "score" / "lat_dev" / "err_dev" or SG_SEL_*, min_value
+        as keywords or a dict; needs the node rollup on, and the trend for a trend key) or off: set_incidents(None)."""
+        if params is None:
+            if kw:
+                raise TypeError("set_incidents(None) switches the incidents off and takes no parameters")
+            self._ck(self._l.sg_set_incidents(self._h, None))
+            return
+        v = dict(by="score", min_value=0.0)
+        v.update(params or {}); v.update(kw)
+        unknown = set(v) - {"by", "min_value", "struct_size", "reserved"}
+        if unknown:
+            raise TypeError(f"unknown incident parameters: {sorted(unknown)}")
+        by = v["by"]
+        if isinstance(by, str):
+            by = self._by(by)
+        p = SgIncidentParams(v.get("struct_size", C.sizeof(SgIncidentParams)), by, v["min_value"], v.get("reserved", 0))
+        self._ck(self._l.sg_set_incidents(self._h, C.byref(p)))
+
+    def window_incidents(self) -> np.ndarray:
+        """INCIDENT_DTYPE rows of the last read window (sg_window_incidents), numbered by their smallest node row"""
+        n = C.c_size_t(0)
+        self._ck(self._l.sg_window_incidents(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=INCIDENT_DTYPE)
+        if n.value:
+            self._ck(self._l.sg_window_incidents(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def window_node_incident(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """the incident number (NO_INCIDENT: none) of every node row of the last read window (sg_window_node_incident), or of the
+        nodes at `index`"""
+        return self._window_rows(self._l.sg_window_node_incident, np.dtype("<u4"), index)
+
+    def window_incidents_buffer(self) -> Tuple[int, int, int]:
+        """(device pointer of the sg_incident_out rows, of their u64 count, of the u32 incident per node row) of the window
+        window_run closed last (sg_window_incidents_buffer)"""
+        p, c, q = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._ck(self._l.sg_window_incidents_buffer(self._h, C.byref(p), C.byref(c), C.byref(q)))
+        return p.value, c.value, q.value
 
     def window_rank_select(self, k: int, min_share: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
         """Select from the rank rows of the window window_run closed last into device memory (sg_window_rank_select): d_out [cap]

@@ -759,6 +759,74 @@ func (g *GraphDS) WindowCulprits(k uint32, minShare float32) ([]Culprit, error) 
 	return out, nil
 }
 
+// ---- incidents (K12) ---------------------------------------------------------------------------------------------------
+
+// Incident is one connected component of a window's anomalous rows (sg_incident_out): how many services and rows it spans, the
+// requests and errors on its rows, its worst row, and the positions (in the window's node rows) of its first, its most anomalous
+// and — with the ranking on — its likely culprit service (NoIncident without it).
+type Incident struct {
+	Nodes, Edges                              uint32
+	Count, Err, SumNs                         uint64
+	ValueMax                                  float32
+	WorstRow, FirstNode, TopNode, CulpritNode uint32
+}
+
+// NoIncident is SG_NO_INCIDENT: Incident.CulpritNode when the ranking is off.
+const NoIncident = uint32(C.SG_NO_INCIDENT)
+
+// SetIncidents switches the per-window incident grouping on (the node rollup with it): a row is anomalous when its score is at
+// least minScore.  ClearIncidents switches it off and keeps the rollup.
+func (g *GraphDS) SetIncidents(minScore float32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	if rc := C.sg_set_nodes(g.h, 1); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_nodes = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	var ip C.sg_incident_params
+	ip.struct_size = C.uint32_t(unsafe.Sizeof(ip))
+	ip.by, ip.min_value = C.SG_SEL_SCORE, C.float(minScore)
+	if rc := C.sg_set_incidents(g.h, &ip); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_incidents = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func (g *GraphDS) ClearIncidents() {
+	g.flushMu.Lock()
+	C.sg_set_incidents(g.h, nil)
+	g.flushMu.Unlock()
+}
+
+// WindowIncidents returns the incidents of the window FlushWindow returned last, numbered by their first service
+// (sg_window_incidents: one 72-byte row per incident crosses PCIe).
+func (g *GraphDS) WindowIncidents() ([]Incident, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_incidents(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_incidents = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	incs := make([]C.sg_incident_out, int(n))
+	if rc := C.sg_window_incidents(g.h, &incs[0], C.size_t(len(incs)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_incidents = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(n) < len(incs) {
+		incs = incs[:int(n)]
+	}
+	out := make([]Incident, len(incs))
+	for i := range incs {
+		inc, o := &incs[i], &out[i]
+		o.Nodes, o.Edges = uint32(inc.nodes), uint32(inc.edges)
+		o.Count, o.Err, o.SumNs = uint64(inc.count), uint64(inc.err), uint64(inc.sum_ns)
+		o.ValueMax, o.WorstRow = float32(inc.value_max), uint32(inc.worst_row)
+		o.FirstNode, o.TopNode, o.CulpritNode = uint32(inc.first_node), uint32(inc.top_node), uint32(inc.culprit_node)
+	}
+	return out, nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

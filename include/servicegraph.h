@@ -564,6 +564,58 @@ int sg_window_rank_top(sg_handle h, uint32_t k, float min_share, sg_node_out* ou
 int sg_window_rank_select(sg_handle h, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index,
                           size_t cap, uint64_t* d_n, void* stream);
 
+/* ---- incidents (K12): each window's anomalous rows grouped into connected components, on the device ------------------------- *
+ * Opt-in (sg_set_incidents, on an engine with the node rollup); without it nothing is computed or allocated, and every other row
+ * is the same either way.  Over the window's rows j = 0 .. E-1 (canonical order) and its node rows v = 0 .. n-1 (sg_window_nodes
+ * order):
+ *   value_j  `by` = SG_SEL_SCORE: the row's score; SG_SEL_LAT_DEV / SG_SEL_ERR_DEV: this window's sg_edge_trend.lat_dev / .err_dev
+ *            of the row (what sg_flush_window_top_by selects by)
+ *   red      row j is red iff value_j >= min_value (a plain float comparison, NaN never) and both its from_ref and its to_ref
+ *            have a node row (a ref beyond the engine's id spaces has none: K11 gives such a row weight 0); alive-only rows are
+ *            ordinary rows
+ *   graph    undirected, on the node rows, one edge {from, to} per red row.  A node row is in an incident iff it is an endpoint
+ *            of a red row (a red row with from_ref == to_ref makes its node an incident on its own); the incidents are the
+ *            connected components of those nodes, numbered 0 .. I-1 by ascending first_node, their smallest node row
+ * Incident i:
+ *   first_node, nodes    its smallest node row; its node rows
+ *   edges                its red rows (other rows between its nodes do not count)
+ *   count, err, sum_ns   wrapping u64 sums of the red rows' count, err_count, sum_ns
+ *   score_q32            K9's sum of (uint64_t)((double)score * 2^32) over the red rows (a score that is not > 0 adds 0)
+ *   value_max, worst_row the largest value among its red rows, +0.0 above -0.0; the smallest row index that has it
+ *   top_node             the node row with the largest sg_node_out.score among its nodes (by the order-preserving bits of the
+ *                        score, +0.0 above -0.0), ties to the smallest index
+ *   culprit_node         with the ranking (K11) on for the window: the node row with the largest sg_node_rank.rank, ties to the
+ *   rank_sum             smallest index; the wrapping u64 sum of its nodes' rank.  Ranking off: SG_NO_INCIDENT and 0
+ * Every field is an integer sum, an integer max or a max of order-preserving float bits: the result has one correct value.
+ * Every close path computes it (one call, begin + end, the views, the _top flushes, sg_window_run), behind K8, K9 and K11.   */
+#define SG_NO_INCIDENT 0xFFFFFFFFu
+typedef struct sg_incident_params {
+    uint32_t struct_size;       /* sizeof(sg_incident_params)                                   */
+    uint32_t by;                /* SG_SEL_SCORE, SG_SEL_LAT_DEV or SG_SEL_ERR_DEV; else SG_EINVAL */
+    float    min_value;         /* a row is red iff its value >= min_value                      */
+    uint32_t reserved;          /* 0                                                            */
+} sg_incident_params;           /* 16 bytes */
+typedef struct sg_incident_out {
+    uint64_t count, err, sum_ns, score_q32, rank_sum;
+    uint32_t first_node, nodes, edges, worst_row, top_node, culprit_node;
+    float    value_max;
+    uint32_t reserved;          /* 0 */
+} sg_incident_out;              /* 72 bytes, no padding */
+/* NULL = off (frees its memory); params = on.  Memory is allocated here, never at create.  SG_ESTATE when the node rollup is off,
+ * a flush is open, or `by` is a trend key and the edge trend is off; SG_EINVAL on bad params.  sg_set_nodes(h, 0) switches it off
+ * too; sg_set_trend(h, NULL) does so only when `by` is a trend key.  Incident calls on an engine without it: SG_ESTATE.        */
+int sg_set_incidents(sg_handle h, const sg_incident_params* p);
+/* The incidents of the last READ window (as sg_window_nodes): *n = incidents, min(*n, cap) rows are written.  SG_ESTATE for a
+ * window closed while the stage was off, and while a flush is open.                                                          */
+int sg_window_incidents(sg_handle h, sg_incident_out* out, size_t cap, size_t* n);
+/* The incident number of every node row of the last READ window, SG_NO_INCIDENT for a node in none (as sg_window_rank):
+ * node_index NULL: every node row, *n = nodes; else out[k] = the number of node node_index[k] (each < nodes, else SG_EINVAL),
+ * *n = n_index.  min(*n, cap) values are written.  SG_ESTATE as sg_window_incidents.                                          */
+int sg_window_node_incident(sg_handle h, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n);
+/* Device sg_incident_out[], their count (one uint64_t) and uint32_t[nodes] (the incident per node row) of the window
+ * sg_window_run closed last (valid until its slot is reused; read them on that window's stream).                              */
+int sg_window_incidents_buffer(sg_handle h, void** d_incidents, void** d_count, void** d_node_incident);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
