@@ -131,6 +131,7 @@ struct sg_engine {
     struct WinSlot {
         Dev d{}; hipStream_t stream = nullptr; u32* ob_list = nullptr; u32* ob_n = nullptr; u64 events_in = 0;
         bool closed = false, plain = false;    // window_close has run, rows readable after score; its last close was a plain one (not counted as warm or cold)
+        u64 halo_ovf_seen = 0;                 // ctr[C_HALO_OVF] as account_window saw it last: the device word only ever grows, sg_stats counts its growth
         u64* h_note = nullptr; u64 note_seen = 0;   // the device's note (page-locked, mapped) and the sequence number last read from it
         u64* scr_sum = nullptr; u64* scr_max = nullptr; double* scr_mu = nullptr;   // the node statistics the kept-CSR rebuild writes (scratch; row_mu | row_sd in one array)
     };
@@ -913,7 +914,11 @@ void account_window(sg_engine* e) {
     st.events_dropped_src += e->h_ctr[C_DROPPED_SRC];
     st.events_dropped_cap += e->h_ctr[C_DROPPED_CAP];
     st.events_misrouted += e->h_ctr[C_MISROUTED];
-    st.halo_overflow += e->h_ctr[C_HALO_OVF];
+    {   // (the list builders ADD to the device word and nothing resets it: adding the word itself counted a window's overflow again in every window after it)
+        const u64 h = e->h_ctr[C_HALO_OVF];
+        st.halo_overflow += h - w.halo_ovf_seen;
+        w.halo_ovf_seen = h;
+    }
     st.alive_in += e->h_ctr[C_ALIVE_SEEN];
     st.alive_dropped += e->h_ctr[C_ALIVE_DROPPED];
     st.last_window_new_edges = 0;

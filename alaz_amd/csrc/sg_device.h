@@ -50,7 +50,7 @@ enum {
     C_EDGES_FOUND,    // edges found in the table before clamping
     C_OVF_N,          // records in the partition overflow list (window)
     C_N_LONG,         // rows longer than one wave (row sort work list)
-    C_HALO_OVF,       // halo requests that did not fit the per-pair capacity (must stay 0)
+    C_HALO_OVF,       // halo requests that did not fit the per-pair capacity (must stay 0); since create — never reset, the host counts its growth
     C_ALIVE_N,        // SG_EV_ALIVE records accepted by K1 in the open window (list length, may exceed the capacity)
     C_ALIVE_DROP,     // ... whose endpoint was not listed at close (working counter)
     C_ALIVE_SEEN,     // closed window: records accepted

@@ -64,6 +64,21 @@ def test_dh_g_override_leaves_a_warm_engine_on_degree_atomics(plan_exe):
     assert r["cold"]["plan"]["warm"] == 0 and r["cold"]["plan"]["dh_g"] == 32
 
 
+def test_k6_one_wg_knob_reaches_the_plan_of_a_sharded_engine(plan_exe):
+    """tests/test_gpu_halo.py compares the one-workgroup halo-list builders with k6_halo_lists: that is a comparison of two kernels only
+    while SG_K6_ONE_WG=1 sets plan.k6_one_wg (the one field launch_halo_lists branches on) and nothing else does — at the node
+    capacities either side of the builder's LDS staging that the GPU test uses."""
+    cases = {"small": "max_known_nodes=180 max_labels=3072 max_outbound_ips=512", "big": "max_known_nodes=180 max_labels=50176 max_outbound_ips=512"}
+    lines = [f"{n}_{k} {c} max_edges=16384 layers=2 rank=1 world=8 max_window_events=65536" + (" SG_K6_ONE_WG=1" if k == "on" else "")
+             for n, c in cases.items() for k in ("on", "off")]
+    r = run_plans(plan_exe, lines)
+    for n in cases:
+        assert r[f"{n}_on"]["rc"] == r[f"{n}_off"]["rc"] == 0
+        assert r[f"{n}_on"]["plan"]["k6_one_wg"] == 1 and r[f"{n}_off"]["plan"]["k6_one_wg"] == 0
+        assert {k for k, v in r[f"{n}_on"]["plan"].items() if r[f"{n}_off"]["plan"][k] != v} == {"k6_one_wg"}
+    assert r["small_on"]["plan"]["ncap"] <= 49152 < r["big_on"]["plan"]["ncap"]
+
+
 def test_knob_list_is_the_engines(plan_exe):
     from alaz_amd import engine
     out = subprocess.run([plan_exe, "--knobs"], capture_output=True, text=True, timeout=60, check=True)
