@@ -15,6 +15,17 @@ OR_UID_MAX = 160
 L7_WIRE_SIZE = 1096
 
 
+def _header_value(name: str) -> int:
+    """an unsigned #define of include/servicegraph.h (the header the oracle is compiled against)"""
+    import re
+    with open(os.path.join(_HERE, "..", "include", "servicegraph.h")) as f:
+        return int(re.search(r"^#define\s+%s\s+(\d+)u?\b" % name, f.read(), re.M).group(1))
+
+
+NODE_STAT_SUM_WORDS = _header_value("SG_NODE_STAT_SUM_WORDS")        # u64 words per node of or_node_stats_sum (12 since the alive words)
+NODE_STAT_MAX_WORDS = _header_value("SG_NODE_STAT_MAX_WORDS")
+
+
 def build(force: bool = False) -> str:
     src = [os.path.join(_HERE, f) for f in ("sg_oracle.c", "sockline.c", "http2.c", "kafka.c", "lean_baseline.c", "sg_oracle.h")] + [os.path.join(_HERE, "..", "include", "servicegraph.h")]
     if force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in src):
@@ -480,9 +491,12 @@ class Oracle:
         return np.ctypeslib.as_array(self._l.or_layer_output(self._o, l), shape=(n, 64)).copy()
 
     def node_stats(self):
+        """(st_sum [n][SG_NODE_STAT_SUM_WORDS], st_max [n][SG_NODE_STAT_MAX_WORDS]) u64 of the closed window, words in ST_* order"""
         n = self.n_nodes
-        s = np.ctypeslib.as_array(self._l.or_node_stats_sum(self._o), shape=(n, 10)).copy()
-        m = np.ctypeslib.as_array(self._l.or_node_stats_max(self._o), shape=(n, 2)).copy()
+        if n == 0:
+            return np.zeros((0, NODE_STAT_SUM_WORDS), np.uint64), np.zeros((0, NODE_STAT_MAX_WORDS), np.uint64)
+        s = np.ctypeslib.as_array(self._l.or_node_stats_sum(self._o), shape=(n, NODE_STAT_SUM_WORDS)).copy()
+        m = np.ctypeslib.as_array(self._l.or_node_stats_max(self._o), shape=(n, NODE_STAT_MAX_WORDS)).copy()
         return s, m
 
     def outbound_ips(self) -> np.ndarray:
