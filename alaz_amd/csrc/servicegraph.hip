@@ -29,6 +29,7 @@
 #include "sg_node_trend.h"
 #include "sg_rank.h"
 #include "sg_incident.h"
+#include "sg_track.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -188,6 +189,15 @@ struct sg_engine {
                        u32* lab = nullptr; u32* num = nullptr; u32* kinc = nullptr; K12Keys* keys = nullptr; u32* blk = nullptr; u32* stage = nullptr;
                        u32* stage_idx = nullptr; std::vector<sg_incident_out*> rows; std::vector<u64*> count; std::vector<u32*> node_inc;
                        std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } inc;
+    // K13, the tracks (sg_track.h): allocated at sg_set_tracks (sg_plan.hpp plan_tracks), one allocation, freed with the incidents.
+    // Kept across windows: the members by anchor key, the table and its counters twice (cur: the copy the next window reads).  The
+    // per-incident scratch, the claim words and the workgroup counts are shared by the window slots: the event chains the updates in
+    // window order across the slots' streams.  Per slot: the rows, the ended list, its count, and whether the window was tracked.
+    struct Tracks { bool on = false; sg_track_params p{}; sgplan::TrackPlan plan; char* mem = nullptr; u32* mtrack = nullptr; u32* mlast = nullptr;
+                    sg_track_entry* tab[2] = {nullptr, nullptr}; TrkState* st[2] = {nullptr, nullptr}; u32 cur = 0; u64 w = 0;
+                    u32* cand = nullptr; u32* kept = nullptr; u32* moved = nullptr; u32* joined = nullptr; u32* pos = nullptr; u32* tv = nullptr;
+                    u64* claim = nullptr; u32* blk = nullptr; std::vector<sg_incident_track*> rows; std::vector<sg_track_entry*> ended;
+                    std::vector<u64*> ended_count; std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } trk;
 };
 
 namespace {
@@ -828,7 +838,50 @@ int launch_incidents(sg_engine* e, hipStream_t s) {
     x.valid[e->cur] = 1;
     return SG_OK;
 }
+// ---- K13, the tracks (engine lock held) --------------------------------------------------------------------------------------------
+static_assert(sgplan::kTrkThreads == K13_THREADS && sgplan::kTrkMaxWgs == K13_MAX_WGS && sgplan::kTrkBlkWords == K13_BLK_WORDS &&
+              sgplan::kTrkStateBytes == sizeof(TrkState) && K13_MAX_WGS <= K13_SCAN_THREADS, "plan_tracks sizes the launches of sg_track.h");
+// enqueue the tracking of the window in slot cur on stream s (behind its grouping, on the same stream) and behind the previous
+// window's tracking (any stream): eight plain launches; the rows and the ended list go to the slot's buffers, the state flips
+int launch_tracks(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
+    sg_engine::Tracks& x = e->trk;
+    const sgplan::TrackPlan& P = x.plan;
+    TrkArgs a{};
+    a.nd.mk = w.d.max_known; a.nd.ml = w.d.max_labels; a.nd.mob = w.d.max_obip; a.nd.ncap = P.ncap;
+    a.nodes = e->nodes.rows[e->cur]; a.ncount = e->nodes.count[e->cur];
+    a.inc = e->inc.rows[e->cur]; a.icount = e->inc.count[e->cur]; a.node_inc = e->inc.node_inc[e->cur];
+    a.w = (u32)x.w; a.quiet = x.p.quiet_windows; a.max_tracks = P.max_tracks; a.per = P.per;
+    a.mtrack = x.mtrack; a.mlast = x.mlast;
+    a.told = x.tab[x.cur]; a.tnew = x.tab[x.cur ^ 1]; a.sold = x.st[x.cur]; a.snew = x.st[x.cur ^ 1];
+    a.cand = x.cand; a.kept = x.kept; a.moved = x.moved; a.joined = x.joined; a.pos = x.pos; a.tv = x.tv; a.claim = x.claim; a.blk = x.blk;
+    a.out = x.rows[e->cur]; a.ended = x.ended[e->cur]; a.ended_count = x.ended_count[e->cur];
+    if (x.pending) HIP_TRY(e, hipStreamWaitEvent(s, x.ev, 0));
+    const dim3 nt(K13_THREADS), ng(P.node_wgs), fg(P.fold_wgs), sg(P.wgs);
+    hipLaunchKernelGGL(k13_init, dim3(P.init_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k13_look, fg, nt, 0, s, a);
+    hipLaunchKernelGGL(k13_fold, fg, nt, 0, s, a);
+    hipLaunchKernelGGL(k13_claim, ng, nt, 0, s, a);
+    hipLaunchKernelGGL(k13_count, sg, nt, 0, s, a);
+    hipLaunchKernelGGL(k13_scan, dim3(1), dim3(K13_SCAN_THREADS), 0, s, a, P.wgs);
+    hipLaunchKernelGGL(k13_write, sg, nt, 0, s, a);
+    hipLaunchKernelGGL(k13_members, ng, nt, 0, s, a);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(x.ev, s));
+    x.pending = true;
+    x.valid[e->cur] = 1;
+    x.cur ^= 1; x.w += 1;
+    return SG_OK;
+}
+void free_tracks(sg_engine* e) {
+    sg_engine::Tracks& x = e->trk;
+    if (x.mem) { hipDeviceSynchronize(); hipFree(x.mem); }
+    if (x.ev) hipEventDestroy(x.ev);
+    x = sg_engine::Tracks{};
+}
+
 void free_incidents(sg_engine* e) {
+    free_tracks(e);
     sg_engine::Incidents& x = e->inc;
     if (x.mem) { hipDeviceSynchronize(); hipFree(x.mem); }
     if (x.ev) hipEventDestroy(x.ev);
@@ -879,7 +932,8 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (const int rc = launch_nodes(e, s)) return rc;
         if (e->ntrend.on) { if (const int rc = launch_node_trend(e, s)) return rc; }
         if (e->rank.on) { if (const int rc = launch_rank(e, s)) return rc; }   // K11 behind K9: the rows, the counters, the node rows and their count
-        if (e->inc.on) return launch_incidents(e, s);                // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
+        if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
+        if (e->trk.on) return launch_tracks(e, s);                   // K13 behind K12: the node rows, the incident rows, the incident per node row
     }
     return SG_OK;
 }
@@ -2432,6 +2486,110 @@ int sg_window_incidents_buffer(sg_handle e, void** d_incidents, void** d_count, 
     const int slot = ran_slot(e);
     if (!x.valid[slot]) { e->err = "sg_window_incidents_buffer: the window was closed while the incidents were off"; return SG_ESTATE; }
     *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
+    return SG_OK;
+}
+
+// ---- K13, the tracks ---------------------------------------------------------------------------------------------------------------
+int sg_set_tracks(sg_handle e, const sg_track_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->inc.on) { e->err = "sg_set_tracks: the incidents are off (sg_set_incidents)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_tracks while a flush is open"; return SG_ESTATE; }
+    sg_track_params q{};
+    if (p && sgplan::check_tracks(*p, e->nodes.plan.ncap, &q)) { e->err = "sg_set_tracks: bad parameters"; return SG_EINVAL; }
+    free_tracks(e);
+    if (!p) return SG_OK;
+    sg_engine::Tracks& x = e->trk;
+    const u32 slots = (u32)e->slots.size();
+    x.p = q;
+    x.plan = sgplan::plan_tracks(e->cfg.max_known_nodes, e->cfg.max_labels, e->nodes.plan.ncap, q.max_tracks, slots);
+    const sgplan::TrackPlan& P = x.plan;
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_tracks", [e] { free_tracks(e); })) return rc;
+    char* b = x.mem;                                                  // (every piece is 256-aligned)
+    x.mtrack = (u32*)b; b += P.member_bytes; x.mlast = (u32*)b; b += P.member_bytes;
+    for (int k = 0; k < 2; k++) { x.tab[k] = (sg_track_entry*)b; b += P.table_bytes; }
+    for (int k = 0; k < 2; k++) { x.st[k] = (TrkState*)b; b += P.state_bytes; }
+    x.cand = (u32*)b; b += P.inc_bytes; x.kept = (u32*)b; b += P.inc_bytes; x.moved = (u32*)b; b += P.inc_bytes;
+    x.joined = (u32*)b; b += P.inc_bytes; x.pos = (u32*)b; b += P.inc_bytes; x.tv = (u32*)b; b += P.inc_bytes;
+    x.claim = (u64*)b; b += P.claim_bytes;
+    x.blk = (u32*)b; b += P.blk_bytes;
+    for (u32 k = 0; k < slots; k++) {
+        x.rows.push_back((sg_incident_track*)b); b += P.rows_bytes; x.ended.push_back((sg_track_entry*)b); b += P.ended_bytes;
+        x.ended_count.push_back((u64*)b); b += P.count_bytes;
+    }
+    // an empty state: no member (SG_NO_TRACK everywhere); the block is zeroed: no entry, next id 0
+    hipError_t rc = hipMemset(x.mtrack, 0xFF, P.member_bytes);
+    if (rc == hipSuccess) rc = hipDeviceSynchronize();               // (the slots' streams do not wait for the null stream)
+    if (rc != hipSuccess) { free_tracks(e); e->err = std::string("sg_set_tracks: hipMemset: ") + hipGetErrorString(rc); return SG_ENODEV; }
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+namespace {
+// the stage on, no flush open, and the last read window tracked; then its tracking done
+int tracks_ready(sg_engine* e, const char* call) {
+    sg_engine::Tracks& x = e->trk;
+    if (!x.on) { e->err = std::string(call) + ": tracking is off (sg_set_tracks)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (!x.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while tracking was off"; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    return SG_OK;
+}
+// min(cnt, cap) elements of `bytes` each from device src
+int tracks_copy(sg_engine* e, const u64* d_count, const void* src, size_t bytes, void* out, size_t cap, size_t* n) {
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, d_count, sizeof(u64), hipMemcpyDeviceToHost));
+    if (n) *n = (size_t)cnt;
+    const size_t take = std::min((size_t)cnt, cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * bytes, hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+}  // namespace
+int sg_window_incident_tracks(sg_handle e, sg_incident_track* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = tracks_ready(e, "sg_window_incident_tracks")) return rc;
+    return tracks_copy(e, e->inc.count[e->cur], e->trk.rows[e->cur], sizeof(sg_incident_track), out, cap, n);
+}
+int sg_window_tracks_ended(sg_handle e, sg_track_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = tracks_ready(e, "sg_window_tracks_ended")) return rc;
+    return tracks_copy(e, e->trk.ended_count[e->cur], e->trk.ended[e->cur], sizeof(sg_track_entry), out, cap, n);
+}
+int sg_window_tracks_buffer(sg_handle e, void** d_tracks, void** d_ended, void** d_ended_count) {
+    if (!e || !d_tracks || !d_ended || !d_ended_count) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Tracks& x = e->trk;
+    if (!x.on) { e->err = "sg_window_tracks_buffer: tracking is off (sg_set_tracks)"; return SG_ESTATE; }
+    const int slot = ran_slot(e);
+    if (!x.valid[slot]) { e->err = "sg_window_tracks_buffer: the window was closed while tracking was off"; return SG_ESTATE; }
+    *d_tracks = x.rows[slot]; *d_ended = x.ended[slot]; *d_ended_count = x.ended_count[slot];
+    return SG_OK;
+}
+int sg_track_entries(sg_handle e, sg_track_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::Tracks& x = e->trk;
+    if (!x.on) { e->err = "sg_track_entries: tracking is off (sg_set_tracks)"; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    TrkState st{};
+    HIP_TRY(e, hipMemcpy(&st, x.st[x.cur], sizeof(TrkState), hipMemcpyDeviceToHost));
+    if (n) *n = st.n;
+    const size_t take = std::min((size_t)st.n, cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, x.tab[x.cur], take * sizeof(sg_track_entry), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+int sg_track_stats_get(sg_handle e, sg_track_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::Tracks& x = e->trk;
+    if (!x.on) { e->err = "sg_track_stats_get: tracking is off (sg_set_tracks)"; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    TrkState st{};
+    HIP_TRY(e, hipMemcpy(&st, x.st[x.cur], sizeof(TrkState), hipMemcpyDeviceToHost));
+    out->windows = x.w; out->live = st.n; out->opened = st.opened; out->dropped_cap = st.dropped;
     return SG_OK;
 }
 

@@ -725,6 +725,71 @@ inline IncidentPlan plan_incidents(u64 max_edges, u32 ncap, u32 slots) {
     return r;
 }
 
+// K13, the tracks (sg_track.h): parameters and the device memory sg_set_tracks allocates — never sg_create, sg_set_nodes or
+// sg_set_incidents.  Kept across windows: the members, two u32 arrays by anchor key (max_known + max_labels), the track table
+// twice ([max_tracks] sg_track_entry: one buffer is read and the other written per window) and its counters twice.  Scratch shared
+// by the window slots: six u32 arrays [ncap] (cand, kept, moved, joined, pos by incident; t_v by node row), the claim words
+// [max_tracks] u64 and the workgroup counts k13_scan scans.  k13_count / k13_write take one 256-thread workgroup per span of `per`
+// incidents and table entries, at most 1024 spans; k13_init runs a grid-stride grid over max(ncap, max_tracks); k13_claim and
+// k13_members one over ncap.  The folding passes k13_look and k13_fold take kTrkFoldRounds rounds of 256 node rows per workgroup:
+// every workgroup adds its LDS table to the incidents once, so fewer workgroups mean fewer device atomics on one incident's words (an
+// all-red config-3 window: 8 workgroups, not 59), and a workgroup can meet more distinct incidents than its table has slots, which
+// then go to device memory directly.  Each slot keeps its sg_incident_track rows, its ended list and the list's count.
+constexpr u32 kTrkThreads = 256, kTrkMaxWgs = 1024, kTrkBlkWords = 7 * 1024, kTrkFoldRounds = 8;
+constexpr u64 kTrkStateBytes = 24;        // entries, next_id, opened, dropped
+inline int check_tracks(const sg_track_params& p, u32 ncap, sg_track_params* out) {
+    if (p.struct_size != sizeof(sg_track_params) || p.reserved != 0 || p.quiet_windows > SG_TRACK_MAX_QUIET) return SG_EINVAL;
+    *out = p;
+    if (!p.max_tracks) {
+        const u64 all = (u64)(p.quiet_windows + 1) * std::max<u32>(ncap, 1);
+        if (all > 0x7FFFFFFFull) return SG_EINVAL;                    // (ids and positions are u32)
+        out->max_tracks = (u32)all;
+    }
+    return SG_OK;
+}
+struct TrackPlan {
+    u32 ncap = 0, anchors = 0, max_tracks = 0;
+    u32 wgs = 0, per = 0;         // k13_count / k13_write: workgroups, incidents and entries per workgroup (a multiple of 256)
+    u32 init_wgs = 0;             // k13_init: grid-stride over max(ncap, max_tracks)
+    u32 node_wgs = 0;             // k13_claim, k13_members: grid-stride over ncap
+    u32 fold_wgs = 0;             // k13_look, k13_fold: grid-stride over ncap, kTrkFoldRounds rounds a workgroup
+    u64 member_bytes = 0;         // one member array [anchors] u32 (track, last: two of them)
+    u64 table_bytes = 0;          // one table buffer [max_tracks] sg_track_entry (two of them)
+    u64 state_bytes = 0;          // one copy of the counters (two of them)
+    u64 inc_bytes = 0;            // one scratch u32 array [ncap] (six of them)
+    u64 claim_bytes = 0;          // [max_tracks] u64
+    u64 blk_bytes = 0;            // [7][1024] u32
+    u64 rows_bytes = 0;           // one window slot's rows: [ncap] sg_incident_track
+    u64 ended_bytes = 0;          // one window slot's ended list: [ncap] sg_track_entry
+    u64 count_bytes = 0;          // one window slot's ended count (u64)
+    u64 total_bytes = 0;          // the state, the scratch and every slot's buffers, each 256-byte aligned
+};
+inline TrackPlan plan_tracks(u32 max_known, u32 max_labels, u32 ncap, u32 max_tracks, u32 slots) {
+    TrackPlan r;
+    const u64 NC = std::max<u32>(ncap, 1), MT = std::max<u32>(max_tracks, 1), span = std::max(NC, MT);
+    r.ncap = ncap; r.anchors = max_known + max_labels; r.max_tracks = max_tracks;
+    r.wgs = (u32)std::max<u64>(1, std::min<u64>(kTrkMaxWgs, (span + kTrkThreads - 1) / kTrkThreads));
+    const u64 per = (span + r.wgs - 1) / r.wgs;
+    r.per = (u32)((per + kTrkThreads - 1) / kTrkThreads * kTrkThreads);
+    r.wgs = (u32)((span + r.per - 1) / r.per);
+    r.init_wgs = (u32)std::max<u64>(1, std::min<u64>(kTrkMaxWgs, (span + kTrkThreads - 1) / kTrkThreads));
+    r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kTrkMaxWgs, (NC + kTrkThreads - 1) / kTrkThreads));
+    const u64 fold_rows = (u64)kTrkFoldRounds * kTrkThreads;
+    r.fold_wgs = (u32)std::max<u64>(1, std::min<u64>(kTrkMaxWgs, (NC + fold_rows - 1) / fold_rows));
+    r.member_bytes = trend_align(std::max<u64>(r.anchors, 1) * 4);
+    r.table_bytes = trend_align(MT * sizeof(sg_track_entry));
+    r.state_bytes = trend_align(kTrkStateBytes);
+    r.inc_bytes = trend_align(NC * 4);
+    r.claim_bytes = trend_align(MT * 8);
+    r.blk_bytes = trend_align((u64)kTrkBlkWords * 4);
+    r.rows_bytes = trend_align(NC * sizeof(sg_incident_track));
+    r.ended_bytes = trend_align(NC * sizeof(sg_track_entry));
+    r.count_bytes = trend_align(8);
+    r.total_bytes = 2 * r.member_bytes + 2 * r.table_bytes + 2 * r.state_bytes + 6 * r.inc_bytes + r.claim_bytes + r.blk_bytes +
+                    (u64)std::max<u32>(slots, 1) * (r.rows_bytes + r.ended_bytes + r.count_bytes);
+    return r;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

@@ -51,6 +51,7 @@ EXPORTS = [
     "sg_window_nodes_top", "sg_window_nodes_select",
     "sg_set_rank", "sg_window_rank", "sg_window_rank_buffer", "sg_window_rank_top", "sg_window_rank_select",
     "sg_set_incidents", "sg_window_incidents", "sg_window_node_incident", "sg_window_incidents_buffer",
+    "sg_set_tracks", "sg_window_incident_tracks", "sg_window_tracks_ended", "sg_window_tracks_buffer", "sg_track_entries", "sg_track_stats_get",
 ]
 
 #: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
@@ -76,6 +77,14 @@ INCIDENT_DTYPE = np.dtype([(f, "<u8") for f in ("count", "err", "sum_ns", "score
                           + [("value_max", "<f4"), ("reserved", "<u4")])
 #: SG_NO_INCIDENT: a node row in no incident; culprit_node with the ranking off
 NO_INCIDENT = 0xFFFFFFFF
+#: sg_incident_track (32 bytes) of include/servicegraph.h: the track of one incident of a window (K13)
+TRACK_DTYPE = np.dtype([(f, "<u4") for f in ("track", "parent", "first_window", "windows", "kept_nodes", "moved_nodes", "joined_nodes", "flags")])
+#: sg_track_entry (40 bytes) of include/servicegraph.h: one entry of the track table, and of a window's ended list
+TRACK_ENTRY_DTYPE = np.dtype([(f, "<u4") for f in ("track", "parent", "first_window", "last_window", "windows", "peak_nodes")]
+                             + [("count", "<u8"), ("err", "<u8")])
+#: SG_NO_TRACK: no track (the parent of a track that continues none), and sg_incident_track.flags' SG_TRACK_* bits
+NO_TRACK = 0xFFFFFFFF
+TRACK_NEW, TRACK_SPLIT, TRACK_MERGED = 1, 2, 4
 #: sg_edge_vanished (64 bytes) of include/servicegraph.h: one baseline entry that went silent (K8's vanished list)
 VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
                            ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4"), ("row", "<u4"), ("reserved", "<u4")])
@@ -145,6 +154,14 @@ class SgRankParams(C.Structure):
 
 class SgIncidentParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("by", C.c_uint32), ("min_value", C.c_float), ("reserved", C.c_uint32)]
+
+
+class SgTrackParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("quiet_windows", C.c_uint32), ("max_tracks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SgTrackStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("windows", "live", "opened", "dropped_cap")]
 
 
 class SgTrendStats(C.Structure):
@@ -261,6 +278,10 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_set_incidents": (C.c_int, [H, P]), "sg_window_incidents": (C.c_int, [H, P, sz, C.POINTER(sz)]),
         "sg_window_node_incident": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
         "sg_window_incidents_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+        "sg_set_tracks": (C.c_int, [H, P]), "sg_window_incident_tracks": (C.c_int, [H, P, sz, C.POINTER(sz)]),
+        "sg_window_tracks_ended": (C.c_int, [H, P, sz, C.POINTER(sz)]),
+        "sg_window_tracks_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+        "sg_track_entries": (C.c_int, [H, P, sz, C.POINTER(sz)]), "sg_track_stats_get": (C.c_int, [H, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -753,6 +774,55 @@ class ServiceGraph:
         p, c, q = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._ck(self._l.sg_window_incidents_buffer(self._h, C.byref(p), C.byref(c), C.byref(q)))
         return p.value, c.value, q.value
+
+    # ---- tracks (K13): the incidents followed across windows ----
+    def set_tracks(self, params: Optional[dict] = (), **kw):
+        """Switch the tracking of incidents across windows on (sg_set_tracks; quiet_windows (default 2), max_tracks (0 = never cut)
+        as keywords or a dict; needs the incidents on) or off: set_tracks(None).  Any set_incidents call switches it off."""
+        if params is None:
+            if kw:
+                raise TypeError("set_tracks(None) switches tracking off and takes no parameters")
+            self._ck(self._l.sg_set_tracks(self._h, None))
+            return
+        v = dict(quiet_windows=2, max_tracks=0)
+        v.update(params or {}); v.update(kw)
+        unknown = set(v) - {"quiet_windows", "max_tracks", "struct_size", "reserved"}
+        if unknown:
+            raise TypeError(f"unknown track parameters: {sorted(unknown)}")
+        p = SgTrackParams(v.get("struct_size", C.sizeof(SgTrackParams)), v["quiet_windows"], v["max_tracks"], v.get("reserved", 0))
+        self._ck(self._l.sg_set_tracks(self._h, C.byref(p)))
+
+    def _counted(self, call, dtype) -> np.ndarray:
+        n = C.c_size_t(0)
+        self._ck(call(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=dtype)
+        if n.value:
+            self._ck(call(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def window_incident_tracks(self) -> np.ndarray:
+        """TRACK_DTYPE rows of the last read window (sg_window_incident_tracks): row i is the track of window_incidents()[i]"""
+        return self._counted(self._l.sg_window_incident_tracks, TRACK_DTYPE)
+
+    def window_tracks_ended(self) -> np.ndarray:
+        """TRACK_ENTRY_DTYPE entries of the tracks that went quiet in the last read window (sg_window_tracks_ended), in id order"""
+        return self._counted(self._l.sg_window_tracks_ended, TRACK_ENTRY_DTYPE)
+
+    def window_tracks_buffer(self) -> Tuple[int, int, int]:
+        """(device pointer of the sg_incident_track rows, of the ended sg_track_entry list, of its u64 count) of the window
+        window_run closed last (sg_window_tracks_buffer)"""
+        p, c, q = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._ck(self._l.sg_window_tracks_buffer(self._h, C.byref(p), C.byref(c), C.byref(q)))
+        return p.value, c.value, q.value
+
+    def track_entries(self) -> np.ndarray:
+        """the live track table in id order, TRACK_ENTRY_DTYPE (sg_track_entries)"""
+        return self._counted(self._l.sg_track_entries, TRACK_ENTRY_DTYPE)
+
+    def track_stats(self) -> SgTrackStats:
+        s = SgTrackStats()
+        self._ck(self._l.sg_track_stats_get(self._h, C.byref(s)))
+        return s
 
     def window_rank_select(self, k: int, min_share: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
         """Select from the rank rows of the window window_run closed last into device memory (sg_window_rank_select): d_out [cap]

@@ -827,6 +827,105 @@ func (g *GraphDS) WindowIncidents() ([]Incident, error) {
 	return out, nil
 }
 
+// ---- tracks (K13) ------------------------------------------------------------------------------------------------------
+
+// IncidentTrack is the track of one incident of a window (sg_incident_track): an incident followed over time.  Track never
+// changes and is never reused; Parent is the track an opened one broke off from (NoTrack: none); FirstWindow and Windows count
+// windows since SetTracks; Kept, Moved and Joined say how many of its services were on this track, on another, or on none.
+type IncidentTrack struct {
+	Track, Parent, FirstWindow, Windows uint32
+	Kept, Moved, Joined                 uint32
+	New, Split, Merged                  bool
+}
+
+// TrackEntry is one track as the table holds it (sg_track_entry): what WindowTracksEnded lists when a track goes quiet.
+type TrackEntry struct {
+	Track, Parent, FirstWindow, LastWindow, Windows, PeakNodes uint32
+	Count, Err                                                 uint64
+}
+
+// NoTrack is SG_NO_TRACK: the parent of a track that continues none.
+const NoTrack = uint32(C.SG_NO_TRACK)
+
+// SetTracks switches the tracking of incidents across windows on (SetIncidents first): a track that goes quiet survives
+// quietWindows silent windows (0..15) before its id is forgotten.  maxTracks caps the table (88 bytes of device memory a
+// position); 0 sizes it so that nothing is ever cut, (quietWindows + 1) x the node capacity — on a large shard set it to what the
+// deployment's incident counts need.  Every SetIncidents / ClearIncidents call switches tracking off.
+func (g *GraphDS) SetTracks(quietWindows, maxTracks uint32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var tp C.sg_track_params
+	tp.struct_size = C.uint32_t(unsafe.Sizeof(tp))
+	tp.quiet_windows, tp.max_tracks = C.uint32_t(quietWindows), C.uint32_t(maxTracks)
+	if rc := C.sg_set_tracks(g.h, &tp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_tracks = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func (g *GraphDS) ClearTracks() {
+	g.flushMu.Lock()
+	C.sg_set_tracks(g.h, nil)
+	g.flushMu.Unlock()
+}
+
+// WindowIncidentTracks returns the track of every incident of the window FlushWindow returned last: element i belongs to
+// WindowIncidents()[i] (sg_window_incident_tracks: one 32-byte row per incident crosses PCIe).
+func (g *GraphDS) WindowIncidentTracks() ([]IncidentTrack, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_incident_tracks(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_incident_tracks = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	trs := make([]C.sg_incident_track, int(n))
+	if rc := C.sg_window_incident_tracks(g.h, &trs[0], C.size_t(len(trs)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_incident_tracks = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(n) < len(trs) {
+		trs = trs[:int(n)]
+	}
+	out := make([]IncidentTrack, len(trs))
+	for i := range trs {
+		tr, o := &trs[i], &out[i]
+		o.Track, o.Parent, o.FirstWindow, o.Windows = uint32(tr.track), uint32(tr.parent), uint32(tr.first_window), uint32(tr.windows)
+		o.Kept, o.Moved, o.Joined = uint32(tr.kept_nodes), uint32(tr.moved_nodes), uint32(tr.joined_nodes)
+		o.New, o.Split, o.Merged = tr.flags&C.SG_TRACK_NEW != 0, tr.flags&C.SG_TRACK_SPLIT != 0, tr.flags&C.SG_TRACK_MERGED != 0
+	}
+	return out, nil
+}
+
+// WindowTracksEnded returns the tracks that went quiet in the window FlushWindow returned last, as they stood, in id order
+// (sg_window_tracks_ended): each track is listed once, in its first silent window.
+func (g *GraphDS) WindowTracksEnded() ([]TrackEntry, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_tracks_ended(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_tracks_ended = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	ents := make([]C.sg_track_entry, int(n))
+	if rc := C.sg_window_tracks_ended(g.h, &ents[0], C.size_t(len(ents)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_tracks_ended = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(n) < len(ents) {
+		ents = ents[:int(n)]
+	}
+	out := make([]TrackEntry, len(ents))
+	for i := range ents {
+		en, o := &ents[i], &out[i]
+		o.Track, o.Parent, o.FirstWindow, o.LastWindow = uint32(en.track), uint32(en.parent), uint32(en.first_window), uint32(en.last_window)
+		o.Windows, o.PeakNodes, o.Count, o.Err = uint32(en.windows), uint32(en.peak_nodes), uint64(en.count), uint64(en.err)
+	}
+	return out, nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

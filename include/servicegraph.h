@@ -616,6 +616,87 @@ int sg_window_node_incident(sg_handle h, const uint32_t* node_index, size_t n_in
  * sg_window_run closed last (valid until its slot is reused; read them on that window's stream).                              */
 int sg_window_incidents_buffer(sg_handle h, void** d_incidents, void** d_count, void** d_node_incident);
 
+/* ---- tracks (K13): each window's incidents followed across windows, on the device -------------------------------------------- *
+ * Opt-in (sg_set_tracks, on an engine with the incidents); without it nothing is computed or allocated, and every other row is the
+ * same either way.  A track is an incident followed over time: every incident of every window belongs to exactly one track, and a
+ * track's id never changes and is never reused.  w = the windows closed since sg_set_tracks switched tracking on (the first: 0).
+ * Over the window's node rows v (sg_window_nodes order), its incidents i = 0 .. I-1 and inc[v] (sg_window_node_incident):
+ *   anchor   a node row whose ref is KNOWN or LABEL (those refs mean the same thing in every window; an OBIP ref is an index into
+ *            the window's own outbound-IP list: such a node rides with its incident and carries no membership).  Every row has a
+ *            pod at one end, so every incident has an anchor.
+ * Kept state:
+ *   member   per anchor ref (track, last): the track of the incident the ref was in most recently, and that window's w
+ *   table    ascending by id, sg_track_entry {track, parent, first_window, last_window, windows, peak_nodes, count, err}
+ *   live     an entry with last_window = L is live at w iff w - L - 1 <= quiet_windows; a member (T, l) is live at w iff
+ *            w - l - 1 <= quiet_windows and the table holds a live entry T.  t_v = the track of v's live member; SG_NO_TRACK for a
+ *            node without one and for every node that is no anchor
+ * Per window, in this order:
+ *   1  cand_i = the smallest t_v over the nodes of incident i (ids ascend in time: the oldest track), SG_NO_TRACK if there is none
+ *   2  over the anchors of i: kept_i = those with t_v == cand_i != SG_NO_TRACK; moved_i = those with t_v != SG_NO_TRACK and
+ *      t_v != cand_i; joined_i = those with t_v == SG_NO_TRACK
+ *   3  each track T goes to one claimant: among the incidents with cand_i == T the one with the largest kept_i, ties to the
+ *      smallest i
+ *   4  incident i continues cand_i if it is that track's claimant; otherwise it opens a track.  Ids of opened tracks are next_id +
+ *      rank, the rank taken among the window's opening incidents in incident order; next_id then advances by their number.  The
+ *      opened track's parent is cand_i (SG_NO_TRACK for an incident that touched no live track)
+ *   5  entry: continued: last_window = w, windows += 1, peak_nodes = max(peak_nodes, nodes_i), count += count_i, err += err_i
+ *      (wrapping u64, the incident row's fields); opened: {id, parent, w, w, 1, nodes_i, count_i, err_i}
+ *   6  row i of sg_window_incident_tracks: {track, parent, first_window, windows (after the update), kept_nodes, moved_nodes,
+ *      joined_nodes, flags}; SG_TRACK_NEW: opened this window; SG_TRACK_SPLIT: opened although cand_i != SG_NO_TRACK;
+ *      SG_TRACK_MERGED: moved_i > 0
+ *   7  every anchor of incident i gets member (track_i, w); other members stay as they are
+ *   8  ended list of window w: the entries not continued at w whose last_window == w - 1, as they stood, in id order: a track is
+ *      listed once, in its first silent window; a track absorbed by a merge is listed then too
+ *   9  new table: the old entries that were continued or for which w - last_window <= quiet_windows, in id order, then the opened
+ *      ones in incident order; only the first max_tracks positions are stored.  An opened track beyond them is still reported in
+ *      this window's rows and consumes its id; it is not kept and is counted in dropped_cap.  A member that names an id the table
+ *      lacks is not live.
+ * Every field is an integer sum, an integer max, a min of ids or the max of a (count << 32 | ~index) key: the result has one
+ * correct value.  Every close path computes it (one call, begin + end, the views, the _top flushes, sg_window_run), behind K12; with
+ * several windows in flight the state updates run in window order.  w and the ids are 32 bits wide: re-enable tracking
+ * (sg_set_tracks) before 2^32 - 1 windows were closed or ids were given out — at a window a millisecond, seven weeks — since
+ * first_window and windows lose their meaning when w wraps, and an id must never reach SG_NO_TRACK.                            */
+#define SG_NO_TRACK     0xFFFFFFFFu
+#define SG_TRACK_NEW    1u
+#define SG_TRACK_SPLIT  2u
+#define SG_TRACK_MERGED 4u
+#define SG_TRACK_MAX_QUIET 15u
+typedef struct sg_track_params {
+    uint32_t struct_size;       /* sizeof(sg_track_params)                                      */
+    uint32_t quiet_windows;     /* 0..SG_TRACK_MAX_QUIET; 0: only the directly preceding window continues */
+    uint32_t max_tracks;        /* table capacity; 0 = (quiet_windows + 1) * the rollup's node capacity: nothing is ever cut */
+    uint32_t reserved;          /* 0                                                            */
+} sg_track_params;              /* 16 bytes */
+typedef struct sg_incident_track {
+    uint32_t track, parent, first_window, windows, kept_nodes, moved_nodes, joined_nodes, flags;
+} sg_incident_track;            /* 32 bytes */
+typedef struct sg_track_entry {
+    uint32_t track, parent, first_window, last_window, windows, peak_nodes;
+    uint64_t count, err;
+} sg_track_entry;               /* 40 bytes, no padding */
+typedef struct sg_track_stats {
+    uint64_t windows;           /* windows closed since tracking was (re)enabled                */
+    uint64_t live;              /* entries in the table now                                     */
+    uint64_t opened;            /* tracks opened since then (the next id)                       */
+    uint64_t dropped_cap;       /* opened tracks the table had no room for                      */
+} sg_track_stats;
+/* NULL = off (frees its memory); params = on, and (re)enabling starts an empty state at w = 0, next id 0.  Memory is allocated
+ * here, never at create.  SG_ESTATE when the incidents are off or a flush is open, SG_EINVAL on bad params.  Every
+ * sg_set_incidents call, on or off, switches tracking off and frees it, and so does whatever switches the incidents off
+ * (sg_set_nodes(h, 0), sg_set_trend(h, NULL) under a trend key).  Track calls on an engine without it: SG_ESTATE.               */
+int sg_set_tracks(sg_handle h, const sg_track_params* p);
+/* Row i belongs to incident i of the last READ window (as sg_window_incidents): *n = incidents, min(*n, cap) rows are written.
+ * SG_ESTATE for a window closed while tracking was off, and while a flush is open.                                           */
+int sg_window_incident_tracks(sg_handle h, sg_incident_track* out, size_t cap, size_t* n);
+/* The ended list of the last READ window: *n = entries, min(*n, cap) are written.  SG_ESTATE as sg_window_incident_tracks.    */
+int sg_window_tracks_ended(sg_handle h, sg_track_entry* out, size_t cap, size_t* n);
+/* Device sg_incident_track[] (their count is sg_window_incidents_buffer's), the ended sg_track_entry[] and their count (one
+ * uint64_t) of the window sg_window_run closed last (valid until its slot is reused; read them on that window's stream).        */
+int sg_window_tracks_buffer(sg_handle h, void** d_tracks, void** d_ended, void** d_ended_count);
+/* The live table in id order: min(*n, cap) entries, *n = entries (waits for the updates enqueued so far).                      */
+int sg_track_entries(sg_handle h, sg_track_entry* out, size_t cap, size_t* n);
+int sg_track_stats_get(sg_handle h, sg_track_stats* out);   /* (waits for the updates enqueued so far) */
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
