@@ -18,6 +18,9 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->flush_window_view = reinterpret_cast<decltype(o->flush_window_view)>(dlsym(dl, "sg_flush_window_view"));   // optional
     o->flush_window_top = reinterpret_cast<decltype(o->flush_window_top)>(dlsym(dl, "sg_flush_window_top"));      // optional
     SG_SYM(last_error, "sg_last_error");
+    o->set_groups = reinterpret_cast<decltype(o->set_groups)>(dlsym(dl, "sg_set_groups"));                        // optional (K14)
+    o->group_assign = reinterpret_cast<decltype(o->group_assign)>(dlsym(dl, "sg_group_assign"));
+    o->window_groups = reinterpret_cast<decltype(o->window_groups)>(dlsym(dl, "sg_window_groups"));
 #undef SG_SYM
     return true;
 }
@@ -70,6 +73,81 @@ void GraphDS::BindIP(std::unordered_map<uint32_t, uint32_t>& m, uint32_t ip, uin
     else m.emplace(ip, id);
 }
 
+// ---- the workload groups (id_mu_ held) ----
+uint32_t GraphDS::GroupOfOwner(const std::string& owner) {
+    if (owner.empty()) return kNoId;
+    auto rs = rs_owner_.find(owner);
+    const std::string& top = rs != rs_owner_.end() && !rs->second.empty() ? rs->second : owner;   // ReplicaSet -> its Deployment
+    auto it = gids_.find(top);
+    if (it != gids_.end()) return it->second;
+    if (guid_of_.size() >= max_groups_) { engine_errors_++; return kNoId; }
+    const uint32_t g = (uint32_t)guid_of_.size();
+    guid_of_.push_back(top); gids_.emplace(top, g);
+    return g;
+}
+void GraphDS::AssignGroup(uint32_t id, uint32_t group) {
+    if (id >= node_group_.size()) node_group_.resize(id + 1, kNoId);
+    if (node_group_[id] == group) return;
+    if (api_.group_assign(h_, &id, &group, 1) == SG_OK) node_group_[id] = group; else engine_errors_++;
+}
+int GraphDS::SetWorkloadGroups(uint32_t max_groups) {
+    if (!api_.set_groups || !api_.group_assign) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(id_mu_);
+    sg_group_params p{}; p.struct_size = sizeof p; p.max_groups = max_groups;
+    const int rc = api_.set_groups(h_, &p);
+    if (rc != SG_OK) return rc;
+    groups_on_ = true; max_groups_ = max_groups ? max_groups : max_known_;
+    gids_.clear(); guid_of_.clear(); node_group_.clear();             // the engine's map starts over: the pods known so far, in id order
+    for (uint32_t id = 0; id < uid_of_.size(); id++) {
+        if (kind_of_[id] != SG_NODE_POD || uid_of_[id].empty()) continue;
+        auto po = pod_owner_.find(uid_of_[id]);
+        if (po != pod_owner_.end()) AssignGroup(id, GroupOfOwner(po->second));
+    }
+    return SG_OK;
+}
+int GraphDS::PersistReplicaSet(const datastore::ReplicaSet& rs, const std::string& et) {
+    if (et == datastore::ADD || et == datastore::UPDATE) {
+        std::lock_guard<std::mutex> g(id_mu_);
+        std::string& dep = rs_owner_[rs.UID];
+        if (dep != rs.OwnerID) {
+            dep = rs.OwnerID;
+            if (groups_on_)                                             // its pods came first: they move to the Deployment's group
+                for (const auto& po : pod_owner_) {
+                    if (po.second != rs.UID) continue;
+                    auto it = ids_.find(po.first);
+                    if (it != ids_.end()) AssignGroup(it->second, GroupOfOwner(rs.UID));
+                }
+        }
+    } else if (et == datastore::DELETE_) { std::lock_guard<std::mutex> g(id_mu_); rs_owner_.erase(rs.UID); }   // (its pods keep their group)
+    return inner_->PersistReplicaSet(rs, et);
+}
+long GraphDS::WorkloadEdges(std::vector<WorkloadEdge>* out) {
+    if (!out || !api_.window_groups) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t n = 0;
+    int rc = api_.window_groups(h_, nullptr, 0, &n);
+    if (rc != SG_OK) return rc;
+    std::vector<sg_group_edge> ge(n);
+    if (n && (rc = api_.window_groups(h_, ge.data(), n, &n)) != SG_OK) return rc;
+    out->assign(ge.size(), WorkloadEdge{});
+    std::lock_guard<std::mutex> g(id_mu_);
+    auto name = [&](uint32_t ref, std::string* type, std::string* uid) {
+        const uint32_t t = SG_REF_TYPE(ref), v = SG_REF_VALUE(ref);
+        if (t == SG_REF_GROUP && v < guid_of_.size()) { *type = "workload"; *uid = guid_of_[v]; }
+        else if (t == SG_REF_KNOWN && v < uid_of_.size()) { *type = kind_of_[v] == SG_NODE_SERVICE ? "service" : "pod"; *uid = uid_of_[v]; }
+        else if (t == SG_REF_LABEL && v < last_labels_.size()) { *type = "outbound"; *uid = last_labels_[v]; }
+        else if (t == SG_REF_OBIP && v < last_obips_.size()) { *type = "outbound"; *uid = FormatIPv4(last_obips_[v]); }
+        else { *type = "unknown"; uid->clear(); }
+    };
+    for (size_t i = 0; i < ge.size(); i++) {
+        const sg_group_edge& r = ge[i]; WorkloadEdge& o = (*out)[i];
+        name(r.from_ref, &o.FromType, &o.FromUID); name(r.to_ref, &o.ToType, &o.ToUID);
+        o.Count = r.count; o.ErrCount = r.err_count; o.SumNs = r.sum_ns; o.SumSqUs = r.sumsq_us; o.MaxNs = r.max_ns; o.ScoreQ32 = r.score_q32;
+        o.Edges = r.edges; o.FromNodes = r.from_nodes; o.Alive = r.alive; o.WorstRow = r.worst_row; o.ScoreMax = r.score_max;
+    }
+    return (long)ge.size();
+}
+
 // processPod keeps PodIPToPodUid (aggregator/persist.go:55-71); pods without an IP never reach the
 // datastore (persist.go:37-40), an empty IP here is ignored for the same reason.
 int GraphDS::PersistPod(const datastore::Pod& pod, const std::string& et) {
@@ -81,8 +159,12 @@ int GraphDS::PersistPod(const datastore::Pod& pod, const std::string& et) {
             if (up) {
                 const uint32_t id = Intern(pod.UID, SG_NODE_POD);
                 erc = id == kNoId ? SG_ENOSPC : api_.upsert_pod(h_, ip, id);
-                if (erc == SG_OK) BindIP(pod_ip_id_, ip, id);
-            } else { api_.delete_pod(h_, ip); UnbindIP(pod_ip_id_, ip); }     // (a DELETE never creates an id)
+                if (erc == SG_OK) {
+                    BindIP(pod_ip_id_, ip, id);
+                    pod_owner_[pod.UID] = pod.OwnerID;
+                    if (groups_on_) AssignGroup(id, GroupOfOwner(pod.OwnerID));
+                }
+            } else { api_.delete_pod(h_, ip); UnbindIP(pod_ip_id_, ip); }     // (a DELETE never creates an id; its group goes with the id, in FlushWindow)
         }
         if (erc == SG_OK && (up || et == datastore::DELETE_)) { std::lock_guard<std::mutex> g(pk_mu_); packer_.SetPodIP(ip, up); }
         if (erc != SG_OK) engine_errors_++;
@@ -262,6 +344,7 @@ long GraphDS::FlushWindow(int64_t window_end_ms) {
         obips.resize(no);
         if (no) api_.window_outbound_ips(h_, obips.data(), no, &no);
     }
+    last_labels_ = labels; last_obips_ = obips;        // for WorkloadEdges
     std::vector<EdgeRow> out(n_conv);
     auto name = [&](uint32_t ref, std::string* type, std::string* uid) {
         const uint32_t t = SG_REF_TYPE(ref), v = SG_REF_VALUE(ref);
@@ -286,6 +369,7 @@ long GraphDS::FlushWindow(int64_t window_end_ms) {
             if (refs_[id] != 0 || uid_of_[id].empty()) continue;
             auto it = ids_.find(uid_of_[id]);
             if (it != ids_.end() && it->second == id) ids_.erase(it);
+            if (kind_of_[id] == SG_NODE_POD) { pod_owner_.erase(uid_of_[id]); if (groups_on_) AssignGroup(id, kNoId); }
             uid_of_[id].clear(); kind_of_[id] = 0; free_ids_.push_back(id); live_ids_--;
         }
     }

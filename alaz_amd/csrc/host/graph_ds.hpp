@@ -43,6 +43,10 @@ struct SgApi {
     int (*window_outbound_ips)(sg_handle, uint32_t*, size_t, size_t*) = nullptr;
     int (*flush_window_top)(sg_handle, uint64_t, uint32_t, float, sg_edge_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;   // optional: SetSelection needs it
     const char* (*last_error)(sg_handle) = nullptr;
+    // optional (K14; absent in an older library): SetWorkloadGroups needs the first two, WorkloadEdges the third
+    int (*set_groups)(sg_handle, const sg_group_params*) = nullptr;
+    int (*group_assign)(sg_handle, const uint32_t*, const uint32_t*, size_t) = nullptr;
+    int (*window_groups)(sg_handle, sg_group_edge*, size_t, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -53,6 +57,13 @@ struct EdgeRow {                       // one edge of a closed window, in the re
     float Score = 0, LatZ = 0, ErrRatio = 0;
     uint32_t Alive = 0;                // open connections reported on the edge in the window
     uint32_t P50Us = 0, P99Us = 0;     // latency percentiles off the edge's log2 histogram (0 unless SG_CFG_EDGE_HISTOGRAM)
+};
+
+struct WorkloadEdge {                  // one edge of a closed window's service map contracted to workloads (sg_group_edge)
+    std::string FromType, FromUID, ToType, ToUID;      // type "workload": the UID of the pod's top known owner; else as EdgeRow
+    uint64_t Count = 0, ErrCount = 0, SumNs = 0, SumSqUs = 0, MaxNs = 0, ScoreQ32 = 0;
+    uint32_t Edges = 0, FromNodes = 0, Alive = 0, WorstRow = 0;
+    float ScoreMax = 0;
 };
 
 class EdgeSink {
@@ -75,7 +86,8 @@ public:
 
     int PersistPod(const datastore::Pod& pod, const std::string& eventType) override;
     int PersistService(const datastore::Service& service, const std::string& eventType) override;
-    int PersistReplicaSet(const datastore::ReplicaSet& rs, const std::string& et) override { return inner_->PersistReplicaSet(rs, et); }
+    // forwarded; with the workload groups on, a ReplicaSet that names a Deployment moves its pods into the Deployment's group
+    int PersistReplicaSet(const datastore::ReplicaSet& rs, const std::string& et) override;
     int PersistDeployment(const datastore::Deployment& d, const std::string& et) override { return inner_->PersistDeployment(d, et); }
     int PersistEndpoints(const datastore::Endpoints& e, const std::string& et) override { return inner_->PersistEndpoints(e, et); }
     int PersistContainer(const datastore::Container& c, const std::string& et) override { return inner_->PersistContainer(c, et); }
@@ -109,6 +121,16 @@ public:
     int SetSelection(uint32_t k, float min_score);
     void ClearSelection() { std::lock_guard<std::mutex> g(flush_mu_); select_ = false; }
 
+    // The workload view (sg_set_groups, K14): every pod is assigned to the group of its top known owner — Pod.OwnerID; if that is a
+    // ReplicaSet with a known OwnerID, that Deployment; DaemonSet / StatefulSet owners as they are; a pod without an owner stays
+    // ungrouped.  Owner UIDs are interned to group ids in arrival order (max_groups of them, 0 = max_known_nodes; an owner beyond
+    // them leaves its pods ungrouped and counts as an engine error).  sg_group_assign follows every pod upsert; a deleted pod
+    // leaves its group when its node id is released, after the window that may still name it has been flushed; a ReplicaSet that
+    // arrives after its pods re-assigns them.  SG_EINVAL without sg_set_groups / sg_group_assign in the engine's table.
+    int SetWorkloadGroups(uint32_t max_groups);
+    // the group edges of the last flushed window, group ids resolved back to owner UIDs; < 0 on an engine error
+    long WorkloadEdges(std::vector<WorkloadEdge>* out);
+
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }
     uint64_t EngineErrors() const { return engine_errors_.load(); }   // sg_upsert_* failures (SG_ENOSPC: id space / join table full)
@@ -127,6 +149,9 @@ private:
     void BindIP(std::unordered_map<uint32_t, uint32_t>& m, uint32_t ip, uint32_t id);   // m[ip] = id, reference counts follow
     void UnbindIP(std::unordered_map<uint32_t, uint32_t>& m, uint32_t ip);
     int Append(const sg_event* ev, size_t n);
+    // (id_mu_ held) the group of a pod owned by `owner` (kNoId: none); node id -> group in the engine, if it changed
+    uint32_t GroupOfOwner(const std::string& owner);
+    void AssignGroup(uint32_t id, uint32_t group);
     int FlushShard(Shard& s);                          // s.mu held
 
     datastore::DataStore* inner_;
@@ -140,6 +165,12 @@ private:
     std::unordered_map<uint32_t, uint32_t> pod_ip_id_, svc_ip_id_;   // ip -> id, what the engine's join tables hold
     std::vector<uint32_t> free_ids_, retired_;         // retired_: no IP left, reusable after the next FlushWindow
     size_t live_ids_ = 0;
+    // the workload groups (under id_mu_): what the owners are is kept whether or not the groups are on
+    bool groups_on_ = false; uint32_t max_groups_ = 0;
+    std::unordered_map<std::string, std::string> pod_owner_, rs_owner_;   // pod UID -> OwnerID; ReplicaSet UID -> its Deployment's UID
+    std::unordered_map<std::string, uint32_t> gids_; std::vector<std::string> guid_of_;   // owner UID <-> group id, arrival order
+    std::vector<uint32_t> node_group_;                 // node id -> the group the engine holds for it
+    std::vector<std::string> last_labels_; std::vector<uint32_t> last_obips_;   // of the last flushed window (flush_mu_)
     std::mutex pk_mu_;                                 // packer_ (labels, prepared statements, HPACK state), dto_labels_
     L7Packer packer_;
     std::unordered_map<std::string, uint32_t> dto_labels_;   // labels seen through the PersistRequest tap share the packer's id space

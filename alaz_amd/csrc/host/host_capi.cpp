@@ -26,6 +26,7 @@ struct MockEngine {
     std::vector<std::array<uint32_t, 3>> table_ops;   // {op: 1 upsert_pod 2 delete_pod 3 upsert_svc 4 delete_svc, ip, id}
     uint32_t label_count = 0; uint32_t flushes = 0; uint32_t max_known = 0x3FFFFFFFu;
     uint32_t top_flushes = 0, top_k = 0; float top_min = 0;             // flush_window_top: calls, the last k and min_score
+    std::vector<std::array<uint32_t, 2>> group_ops;   // {node id, group} of every sg_group_assign pair; {0xFFFFFFFE, max_groups} of every sg_set_groups
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
 };
 #define M_LOCK(h) std::lock_guard<std::mutex> _g(reinterpret_cast<MockEngine*>(h)->mu)
@@ -44,6 +45,13 @@ int m_flush_top(sg_handle h, uint64_t, uint32_t k, float min_score, sg_edge_out*
     if (n) *n = 0;
     return SG_OK;
 }
+int m_set_groups(sg_handle h, const sg_group_params* p) { M_LOCK(h); reinterpret_cast<MockEngine*>(h)->group_ops.push_back({0xFFFFFFFEu, p ? p->max_groups : 0xFFFFFFFFu}); return SG_OK; }
+int m_group_assign(sg_handle h, const uint32_t* ids, const uint32_t* gs, size_t n) {
+    M_LOCK(h); auto* m = reinterpret_cast<MockEngine*>(h);
+    for (size_t i = 0; i < n; i++) m->group_ops.push_back({ids[i], gs[i]});
+    return SG_OK;
+}
+int m_window_groups(sg_handle, sg_group_edge*, size_t, size_t* n) { if (n) *n = 0; return SG_OK; }
 int m_obips(sg_handle, uint32_t*, size_t, size_t* n) { if (n) *n = 0; return SG_OK; }
 const char* m_err(sg_handle) { return ""; }
 
@@ -127,6 +135,7 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.create = m_create; c->api.destroy = m_destroy; c->api.upsert_pod = m_upsert_pod; c->api.delete_pod = m_delete_pod;
         c->api.upsert_service = m_upsert_svc; c->api.delete_service = m_delete_svc; c->api.set_label_count = m_labels; c->api.ingest = m_ingest;
         c->api.flush_window = m_flush; c->api.window_outbound_ips = m_obips; c->api.last_error = m_err; c->api.flush_window_top = m_flush_top;
+        c->api.set_groups = m_set_groups; c->api.group_assign = m_group_assign; c->api.window_groups = m_window_groups;
     }
     if (c->api.create(cfg, &c->h) != SG_OK) return nullptr;        // no usable GPU => no GraphDS: there is no CPU fallback
     c->ds = std::make_unique<GraphDS>(&c->inner, c->api, c->h, &c->sink, cfg ? (size_t)cfg->max_edges : 1024, batch ? batch : 4096,
@@ -136,6 +145,34 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
 void sgh_graphds_destroy(void* g) { auto* c = static_cast<HostCtx*>(g); if (!c) return; c->ds.reset(); if (c->h) c->api.destroy(c->h); delete c; }
 int sgh_graphds_persist_pod(void* g, const char* et, const char* uid, const char* ip) { datastore::Pod p; p.UID = uid; p.IP = ip; return static_cast<HostCtx*>(g)->ds->PersistPod(p, et); }
 int sgh_graphds_persist_service(void* g, const char* et, const char* uid, const char* ip) { datastore::Service s; s.UID = uid; if (ip && *ip) s.ClusterIPs.push_back(ip); return static_cast<HostCtx*>(g)->ds->PersistService(s, et); }
+// the workload view (K14): a pod with its owner, a ReplicaSet with its owner, the switch, and the last flushed window's group edges
+int sgh_graphds_persist_pod_owned(void* g, const char* et, const char* uid, const char* ip, const char* owner_id) {
+    datastore::Pod p; p.UID = uid; p.IP = ip; p.OwnerID = owner_id ? owner_id : "";
+    return static_cast<HostCtx*>(g)->ds->PersistPod(p, et);
+}
+int sgh_graphds_persist_replicaset(void* g, const char* et, const char* uid, const char* owner_id) {
+    datastore::ReplicaSet rs; rs.UID = uid; rs.OwnerID = owner_id ? owner_id : "";
+    return static_cast<HostCtx*>(g)->ds->PersistReplicaSet(rs, et);
+}
+int sgh_graphds_set_workload_groups(void* g, uint32_t max_groups) { return static_cast<HostCtx*>(g)->ds->SetWorkloadGroups(max_groups); }
+struct sgh_workload_edge {
+    char from_type[12], to_type[12], from_uid[160], to_uid[160];
+    uint64_t count, err_count, sum_ns, sumsq_us, max_ns, score_q32; uint32_t edges, from_nodes, alive, worst_row; float score_max; uint32_t pad;
+};
+long sgh_graphds_workload_edges(void* g, sgh_workload_edge* out, size_t cap) {
+    std::vector<WorkloadEdge> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadEdges(&v);
+    if (n < 0) return n;
+    for (size_t i = 0; i < std::min(cap, v.size()); i++) {
+        const WorkloadEdge& r = v[i]; sgh_workload_edge& o = out[i];
+        std::memset(&o, 0, sizeof o);
+        std::strncpy(o.from_type, r.FromType.c_str(), sizeof o.from_type - 1); std::strncpy(o.to_type, r.ToType.c_str(), sizeof o.to_type - 1);
+        std::strncpy(o.from_uid, r.FromUID.c_str(), sizeof o.from_uid - 1); std::strncpy(o.to_uid, r.ToUID.c_str(), sizeof o.to_uid - 1);
+        o.count = r.Count; o.err_count = r.ErrCount; o.sum_ns = r.SumNs; o.sumsq_us = r.SumSqUs; o.max_ns = r.MaxNs; o.score_q32 = r.ScoreQ32;
+        o.edges = r.Edges; o.from_nodes = r.FromNodes; o.alive = r.Alive; o.worst_row = r.WorstRow; o.score_max = r.ScoreMax;
+    }
+    return n;
+}
 int sgh_graphds_ingest_wire(void* g, const uint8_t* recs, size_t n, const uint32_t* kafka_msgs) {
     return static_cast<HostCtx*>(g)->ds->IngestWire(recs, n, kafka_msgs);
 }
@@ -406,6 +443,13 @@ void sgh_mock_flushes(void* g, uint32_t out[3], float* min_score) {
     if (!c->mock) return;
     auto* m = reinterpret_cast<MockEngine*>(c->h); std::lock_guard<std::mutex> l(m->mu);
     out[0] = m->flushes; out[1] = m->top_flushes; out[2] = m->top_k; if (min_score) *min_score = m->top_min;
+}
+size_t sgh_mock_group_ops(void* g, uint32_t* out2, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g); if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h); std::lock_guard<std::mutex> l(m->mu);
+    const size_t k = std::min(cap, m->group_ops.size());
+    for (size_t i = 0; i < k; i++) { out2[2 * i] = m->group_ops[i][0]; out2[2 * i + 1] = m->group_ops[i][1]; }
+    return m->group_ops.size();
 }
 uint32_t sgh_mock_label_count(void* g) { auto* c = static_cast<HostCtx*>(g); return c->mock ? reinterpret_cast<MockEngine*>(c->h)->label_count : 0; }
 

@@ -30,6 +30,7 @@
 #include "sg_rank.h"
 #include "sg_incident.h"
 #include "sg_track.h"
+#include "sg_group.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -198,6 +199,16 @@ struct sg_engine {
                     u32* cand = nullptr; u32* kept = nullptr; u32* moved = nullptr; u32* joined = nullptr; u32* pos = nullptr; u32* tv = nullptr;
                     u64* claim = nullptr; u32* blk = nullptr; std::vector<sg_incident_track*> rows; std::vector<sg_track_entry*> ended;
                     std::vector<u64*> ended_count; std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } trk;
+    // K14, the groups (sg_group.h): allocated at sg_set_groups (sg_plan.hpp plan_groups), one allocation; needs none of K8 - K13.  The
+    // group map, the sort's ping-pong buffers, the digit counts, the fold's partials and the head counts are scratch shared by the
+    // window slots: every contraction waits for the previous one (ev), whichever slot's stream it runs on.  The host keeps the map
+    // (h_map) and the range sg_group_assign changed since the last close (dirty): the closing slot uploads it behind that wait, through
+    // a page-locked copy (h_up; up_ev: the previous upload has read it).  Per slot: the group edges, their count, row_group and perm.
+    struct Groups { bool on = false; sg_group_params p{}; sgplan::GroupPlan plan; char* mem = nullptr; u32* map = nullptr; void* keys[2] = {nullptr, nullptr};
+                    u32* idx[2] = {nullptr, nullptr}; u32* hist = nullptr; u32* chunkcnt = nullptr; K14Acc* part = nullptr; uint2* meta = nullptr;
+                    u32* blk = nullptr; u32* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_group_edge*> rows; std::vector<u64*> count;
+                    std::vector<u32*> row_group, perm; std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false;
+                    std::vector<u32> h_map; u32* h_up = nullptr; hipEvent_t up_ev = nullptr; bool up_pending = false; u32 dirty_lo = 0, dirty_hi = 0; } grp;
 };
 
 namespace {
@@ -880,6 +891,68 @@ void free_tracks(sg_engine* e) {
     x = sg_engine::Tracks{};
 }
 
+// ---- K14, the groups (engine lock held) --------------------------------------------------------------------------------------------
+static_assert(sgplan::kGrpThreads == K14_THREADS && sgplan::kGrpTile == K14_TILE && sgplan::kGrpChunk == K14_CHUNK && sgplan::kGrpMaxWgs == K9_MAX_WGS &&
+              sgplan::kGrpKeyRows == K14_THREADS * K14_KEY_ROWS && sgplan::kGrpEdgeBytes == sizeof(K14Acc) && sgplan::kGrpMaxWgs <= K9_SCAN_THREADS,
+              "plan_groups sizes the launches of sg_group.h");
+template <class KT>
+void launch_group_kernels(const sgplan::GroupPlan& P, const GroupArgs& a, void* const keys[2], u32* const idx[2], hipStream_t s) {
+    KT* k[2] = {(KT*)keys[0], (KT*)keys[1]};
+    const dim3 nt(K14_THREADS), tg(P.tiles);
+    hipLaunchKernelGGL(k14_keys<KT>, dim3(P.key_wgs), nt, 0, s, a, k[0], idx[0]);
+    for (u32 i = 0; i < P.passes; i++) {
+        const u32 in = i & 1u, out = in ^ 1u;
+        hipLaunchKernelGGL(k14_hist<KT>, tg, nt, 0, s, a, (const KT*)k[in], 8u * i);
+        hipLaunchKernelGGL(k14_scan, dim3(1), dim3(K14_SCAN_THREADS), 0, s, a);
+        hipLaunchKernelGGL(k14_scatter<KT>, tg, nt, 0, s, a, (const KT*)k[in], (const u32*)idx[in], k[out], i + 1 == P.passes ? a.perm : idx[out], 8u * i);
+    }
+    const KT* sorted = k[P.passes & 1u];
+    hipLaunchKernelGGL(k14_heads<KT>, dim3(P.heads_wgs), nt, 0, s, a, sorted);
+    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a.nd, P.heads_wgs);
+    hipLaunchKernelGGL(k14_fold<KT>, dim3(P.chunks), nt, 0, s, a, sorted);
+    hipLaunchKernelGGL(k14_stitch, dim3(P.stitch_wgs), nt, 0, s, a);
+}
+// enqueue the contraction of the window in slot cur on stream s (behind its score kernel, on the same stream) and behind the previous
+// contraction (any stream): the map words sg_group_assign changed, then 5 + 3 passes plain launches; the group edges, row_group and
+// perm go to the slot's buffers
+int launch_groups(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
+    sg_engine::Groups& x = e->grp;
+    const sgplan::GroupPlan& P = x.plan;
+    GroupArgs a{};
+    a.nd.rows = w.d.rows; a.nd.ctr = w.d.ctr; a.nd.max_edges = e->cfg.max_edges;
+    a.nd.mk = w.d.max_known; a.nd.ml = w.d.max_labels; a.nd.mob = w.d.max_obip; a.nd.ncap = w.d.max_known + w.d.max_labels + w.d.max_obip;
+    a.nd.blk = x.blk; a.nd.count = x.count[e->cur];                  // (k9_scan: the head counts in, their scan and the group edge count out)
+    a.map = x.map; a.max_groups = P.max_groups; a.gk = (u32)P.gk; a.kb = P.kb; a.cpw = P.cpw; a.max_chunks = P.chunks;
+    a.hist = x.hist; a.chunkcnt = x.chunkcnt; a.part = x.part; a.meta = x.meta;
+    a.out = x.rows[e->cur]; a.row_group = x.row_group[e->cur]; a.perm = x.perm[e->cur];
+    if (x.pending) HIP_TRY(e, hipStreamWaitEvent(s, x.ev, 0));
+    if (x.dirty_hi > x.dirty_lo) {                                    // the windows closed before read the map as it was: the upload is behind them
+        if (x.up_pending) HIP_TRY(e, hipEventSynchronize(x.up_ev));
+        const size_t n = x.dirty_hi - x.dirty_lo;
+        std::memcpy(x.h_up + x.dirty_lo, x.h_map.data() + x.dirty_lo, n * sizeof(u32));
+        HIP_TRY(e, hipMemcpyAsync(x.map + x.dirty_lo, x.h_up + x.dirty_lo, n * sizeof(u32), hipMemcpyHostToDevice, s));
+        HIP_TRY(e, hipEventRecord(x.up_ev, s));
+        x.up_pending = true;
+        x.dirty_lo = x.dirty_hi = 0;
+    }
+    if (P.key_bytes == 4) launch_group_kernels<u32>(P, a, x.keys, x.idx, s);
+    else launch_group_kernels<u64>(P, a, x.keys, x.idx, s);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(x.ev, s));
+    x.pending = true;
+    x.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_groups(sg_engine* e) {
+    sg_engine::Groups& x = e->grp;
+    if (x.mem) { hipDeviceSynchronize(); hipFree(x.mem); }
+    if (x.h_up) hipHostFree(x.h_up);
+    if (x.ev) hipEventDestroy(x.ev);
+    if (x.up_ev) hipEventDestroy(x.up_ev);
+    x = sg_engine::Groups{};
+}
+
 void free_incidents(sg_engine* e) {
     free_tracks(e);
     sg_engine::Incidents& x = e->inc;
@@ -933,8 +1006,9 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (e->ntrend.on) { if (const int rc = launch_node_trend(e, s)) return rc; }
         if (e->rank.on) { if (const int rc = launch_rank(e, s)) return rc; }   // K11 behind K9: the rows, the counters, the node rows and their count
         if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
-        if (e->trk.on) return launch_tracks(e, s);                   // K13 behind K12: the node rows, the incident rows, the incident per node row
+        if (e->trk.on) { if (const int rc = launch_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
     }
+    if (e->grp.on) return launch_groups(e, s);                       // K14 behind K5: the rows and the window counters only, whatever else is on
     return SG_OK;
 }
 
@@ -1500,6 +1574,7 @@ int sg_destroy(sg_handle e) {
     if (e->sel.ev) hipEventDestroy(e->sel.ev);
     free_trend(e);
     free_nodes(e);
+    free_groups(e);
     if (e->nsel.mem) hipFree(e->nsel.mem);
     if (e->nsel.h_n) hipHostFree(e->nsel.h_n);
     if (e->nsel.ev) hipEventDestroy(e->nsel.ev);
@@ -2486,6 +2561,130 @@ int sg_window_incidents_buffer(sg_handle e, void** d_incidents, void** d_count, 
     const int slot = ran_slot(e);
     if (!x.valid[slot]) { e->err = "sg_window_incidents_buffer: the window was closed while the incidents were off"; return SG_ESTATE; }
     *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
+    return SG_OK;
+}
+
+// ---- K14, the groups ---------------------------------------------------------------------------------------------------------------
+int sg_set_groups(sg_handle e, const sg_group_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (e->cfg.world > 1) { e->err = "sg_set_groups: not on a sharded engine"; return SG_EINVAL; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_groups while a flush is open"; return SG_ESTATE; }
+    sg_group_params q{};
+    if (p && sgplan::check_groups(*p, e->cfg.max_known_nodes, e->cfg.world, &q)) { e->err = "sg_set_groups: bad parameters"; return SG_EINVAL; }
+    free_groups(e);
+    if (!p) return SG_OK;
+    sg_engine::Groups& x = e->grp;
+    const u32 slots = (u32)e->slots.size();
+    const Dev& d = e->slots[0].d;
+    x.p = q;
+    x.plan = sgplan::plan_groups(e->cfg.max_edges, d.max_known, d.max_known + d.max_labels + d.max_obip, q.max_groups, slots);
+    const sgplan::GroupPlan& P = x.plan;
+    auto release = [e] { free_groups(e); };
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    HIP_TRY(e, hipEventCreateWithFlags(&x.up_ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_groups", release)) return rc;
+    if (hipHostMalloc((void**)&x.h_up, std::max<size_t>(d.max_known, 1) * sizeof(u32)) != hipSuccess) { release(); e->err = "sg_set_groups: hipHostMalloc"; return SG_ENOMEM; }
+    char* b = x.mem;                                                  // (every piece is 256-aligned)
+    x.keys[0] = b; b += P.keys_bytes; x.keys[1] = b; b += P.keys_bytes;
+    x.idx[0] = (u32*)b; b += P.idx_bytes; x.idx[1] = (u32*)b; b += P.idx_bytes;
+    x.map = (u32*)b; b += P.map_bytes; x.hist = (u32*)b; b += P.hist_bytes; x.chunkcnt = (u32*)b; b += P.chunkcnt_bytes;
+    x.part = (K14Acc*)b; b += P.part_bytes; x.meta = (uint2*)b; b += P.meta_bytes; x.blk = (u32*)b; b += P.blk_bytes;
+    x.stage = (u32*)b; b += P.stage_bytes; x.stage_idx = (u32*)b; b += P.stage_bytes;
+    for (u32 k = 0; k < slots; k++) {
+        x.rows.push_back((sg_group_edge*)b); b += P.rows_bytes; x.count.push_back((u64*)b); b += P.count_bytes;
+        x.row_group.push_back((u32*)b); b += P.idx_bytes; x.perm.push_back((u32*)b); b += P.idx_bytes;
+    }
+    HIP_TRY(e, hipMemset(x.map, 0xFF, P.map_bytes));                  // nothing grouped
+    x.h_map.assign(d.max_known, SG_NO_GROUP);
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+int sg_group_assign(sg_handle e, const uint32_t* node_ids, const uint32_t* groups, size_t n) {
+    if (!e || (n && (!node_ids || !groups))) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::Groups& x = e->grp;
+    if (!x.on) { e->err = "sg_group_assign: the groups are off (sg_set_groups)"; return SG_ESTATE; }
+    for (size_t k = 0; k < n; k++)
+        if (node_ids[k] >= x.h_map.size() || (groups[k] >= x.plan.max_groups && groups[k] != SG_NO_GROUP)) { e->err = "sg_group_assign: a node id or a group beyond its range"; return SG_EINVAL; }
+    for (size_t k = 0; k < n; k++) {
+        const u32 id = node_ids[k];
+        if (x.h_map[id] == groups[k]) continue;
+        x.h_map[id] = groups[k];
+        if (x.dirty_hi == x.dirty_lo) { x.dirty_lo = id; x.dirty_hi = id + 1; }
+        else { x.dirty_lo = std::min(x.dirty_lo, id); x.dirty_hi = std::max(x.dirty_hi, id + 1); }
+    }
+    return SG_OK;
+}
+namespace {
+// the stage on, no flush open, and the last read window contracted; then its contraction done
+int groups_ready(sg_engine* e, const char* call) {
+    sg_engine::Groups& x = e->grp;
+    if (!x.on) { e->err = std::string(call) + ": the groups are off (sg_set_groups)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (!x.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while the groups were off"; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    return SG_OK;
+}
+}  // namespace
+int sg_window_groups(sg_handle e, sg_group_edge* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = groups_ready(e, "sg_window_groups")) return rc;
+    const sg_engine::Groups& x = e->grp;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, x.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    if (n) *n = (size_t)cnt;
+    const size_t take = std::min((size_t)cnt, cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, x.rows[e->cur], take * sizeof(sg_group_edge), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+int sg_window_row_group(sg_handle e, const uint32_t* row_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = groups_ready(e, "sg_window_row_group")) return rc;
+    sg_engine::Groups& x = e->grp;
+    const size_t E = (size_t)e->h_ctr[C_N_EDGES];                      // of the last read window
+    const u32* src = x.row_group[e->cur];
+    if (!row_index) {
+        if (n) *n = E;
+        const size_t take = std::min(E, cap);
+        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(u32), hipMemcpyDeviceToHost));
+        return SG_OK;
+    }
+    for (size_t k = 0; k < n_index; k++) if (row_index[k] >= E) { e->err = "sg_window_row_group: a row index beyond the window's edges"; return SG_EINVAL; }
+    if (n) *n = n_index;
+    const size_t take = std::min(n_index, cap), chunk = sgplan::kGrpStage;
+    if (!out) return SG_OK;
+    for (size_t o = 0; o < take; o += chunk) {                        // (the staging holds 65536 values: a longer index goes in pieces)
+        const size_t m = std::min(chunk, take - o);
+        HIP_TRY(e, hipMemcpyAsync(x.stage_idx, row_index + o, m * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
+        hipLaunchKernelGGL(k12_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)x.stage_idx, (u64)m, x.stage);
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipMemcpyAsync(out + o, x.stage, m * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
+        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    }
+    return SG_OK;
+}
+int sg_window_group_perm(sg_handle e, uint32_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = groups_ready(e, "sg_window_group_perm")) return rc;
+    const size_t E = (size_t)e->h_ctr[C_N_EDGES];
+    if (n) *n = E;
+    const size_t take = std::min(E, cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, e->grp.perm[e->cur], take * sizeof(u32), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+int sg_window_groups_buffer(sg_handle e, void** d_edges, void** d_count, void** d_row_group, void** d_perm) {
+    if (!e || !d_edges || !d_count || !d_row_group || !d_perm) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Groups& x = e->grp;
+    if (!x.on) { e->err = "sg_window_groups_buffer: the groups are off (sg_set_groups)"; return SG_ESTATE; }
+    const int slot = ran_slot(e);
+    if (!x.valid[slot]) { e->err = "sg_window_groups_buffer: the window was closed while the groups were off"; return SG_ESTATE; }
+    *d_edges = x.rows[slot]; *d_count = x.count[slot]; *d_row_group = x.row_group[slot]; *d_perm = x.perm[slot];
     return SG_OK;
 }
 

@@ -790,6 +790,77 @@ inline TrackPlan plan_tracks(u32 max_known, u32 max_labels, u32 ncap, u32 max_tr
     return r;
 }
 
+// K14, the groups (sg_group.h): parameters and the device memory sg_set_groups allocates — never sg_create.  The key of a row is
+// gk(from) << kb | gk(to) with kb = bits(GK - 1), GK = max_groups + ncap: 32 bits wide while 2 kb <= 32 (config 3: 15 + 15), else 64;
+// it is sorted in passes = ceil(2 kb / 8) stable radix passes over tiles of 4096 positions.  Scratch shared by the window slots: the
+// keys and the indices twice (ping-pong), the digit counts [256][tiles], the group map [max_known], per fold chunk of 2048 positions
+// its head count, two 80-byte partials and a meta word, the head counts k9_scan scans (k14_heads: cpw chunks per workgroup, at most
+// 1024 workgroups), and the staging of sg_window_row_group's index form.  Each slot keeps its group edges [max_edges], row_group,
+// perm and the count.
+constexpr u32 kGrpThreads = 256, kGrpTile = 4096, kGrpChunk = 2048, kGrpMaxWgs = 1024, kGrpKeyRows = 1024, kGrpStage = 65536;
+constexpr u64 kGrpEdgeBytes = 80, kGrpMaxGroups = 1ull << 30;
+// SG_OK and *out = p with max_groups 0 replaced by max_known, or SG_EINVAL
+inline int check_groups(const sg_group_params& p, u32 max_known, u32 world, sg_group_params* out) {
+    if (world > 1 || p.struct_size != sizeof(sg_group_params) || p.reserved[0] != 0 || p.reserved[1] != 0 || p.max_groups > kGrpMaxGroups) return SG_EINVAL;
+    *out = p;
+    if (!p.max_groups) out->max_groups = max_known;
+    return SG_OK;
+}
+inline u32 bits_of(u64 x) { u32 b = 0; while (x) { b++; x >>= 1; } return b; }
+struct GroupPlan {
+    u32 max_groups = 0;
+    u64 gk = 0;                   // GK = max_groups + ncap: every group key is below it
+    u32 kb = 0;                   // bits(GK - 1), at least 1
+    u32 key_bytes = 0;            // 4 while 2 kb <= 32, else 8
+    u32 passes = 0;               // ceil(2 kb / 8)
+    u32 tiles = 0;                // sort tiles of max_edges: the grid of k14_hist / k14_scatter
+    u32 key_wgs = 0;              // k14_keys: 1024 rows a workgroup
+    u32 chunks = 0;               // fold chunks of max_edges: the grid of k14_fold
+    u32 cpw = 0, heads_wgs = 0;   // k14_heads: chunks per workgroup, workgroups (<= 1024)
+    u32 stitch_wgs = 0;           // k14_stitch: one thread per chunk
+    u64 keys_bytes = 0;           // one key buffer [max_edges] (two of them)
+    u64 idx_bytes = 0;            // one u32 array [max_edges]: an index buffer (two), a slot's row_group, a slot's perm
+    u64 map_bytes = 0;            // [max_known] u32
+    u64 hist_bytes = 0;           // [256][tiles] u32
+    u64 chunkcnt_bytes = 0;       // [chunks] u32
+    u64 part_bytes = 0;           // [chunks][2] x 80 bytes
+    u64 meta_bytes = 0;           // [chunks] x 8 bytes
+    u64 blk_bytes = 0;            // [2][1024] u32
+    u64 stage_bytes = 0;          // [65536] u32 (the gathered values, the index: two of them)
+    u64 rows_bytes = 0;           // one window slot's group edges: [max_edges] sg_group_edge
+    u64 count_bytes = 0;          // one window slot's group edge count (u64)
+    u64 total_bytes = 0;          // the scratch, the staging and every slot's buffers, each 256-byte aligned
+};
+inline GroupPlan plan_groups(u64 max_edges, u32 max_known, u32 ncap, u32 max_groups, u32 slots) {
+    GroupPlan r;
+    const u64 ME = std::max<u64>(max_edges, 1);
+    r.max_groups = max_groups;
+    r.gk = (u64)max_groups + ncap;
+    r.kb = std::max<u32>(1, bits_of(r.gk ? r.gk - 1 : 0));
+    r.key_bytes = 2 * r.kb <= 32 ? 4 : 8;
+    r.passes = (2 * r.kb + 7) / 8;
+    r.tiles = (u32)((ME + kGrpTile - 1) / kGrpTile);
+    r.key_wgs = (u32)((ME + kGrpKeyRows - 1) / kGrpKeyRows);
+    r.chunks = (u32)((ME + kGrpChunk - 1) / kGrpChunk);
+    r.cpw = (r.chunks + kGrpMaxWgs - 1) / kGrpMaxWgs;
+    r.heads_wgs = (r.chunks + r.cpw - 1) / r.cpw;
+    r.stitch_wgs = (r.chunks + kGrpThreads - 1) / kGrpThreads;
+    r.keys_bytes = trend_align(ME * r.key_bytes);
+    r.idx_bytes = trend_align(ME * 4);
+    r.map_bytes = trend_align(std::max<u64>(max_known, 1) * 4);
+    r.hist_bytes = trend_align(256ull * r.tiles * 4);
+    r.chunkcnt_bytes = trend_align((u64)r.chunks * 4);
+    r.part_bytes = trend_align((u64)r.chunks * 2 * kGrpEdgeBytes);
+    r.meta_bytes = trend_align((u64)r.chunks * 8);
+    r.blk_bytes = trend_align(2ull * kGrpMaxWgs * 4);
+    r.stage_bytes = trend_align((u64)kGrpStage * 4);
+    r.rows_bytes = trend_align(ME * kGrpEdgeBytes);
+    r.count_bytes = trend_align(8);
+    r.total_bytes = 2 * r.keys_bytes + 2 * r.idx_bytes + r.map_bytes + r.hist_bytes + r.chunkcnt_bytes + r.part_bytes + r.meta_bytes + r.blk_bytes +
+                    2 * r.stage_bytes + (u64)std::max<u32>(slots, 1) * (r.rows_bytes + 2 * r.idx_bytes + r.count_bytes);
+    return r;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

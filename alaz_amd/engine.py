@@ -52,6 +52,7 @@ EXPORTS = [
     "sg_set_rank", "sg_window_rank", "sg_window_rank_buffer", "sg_window_rank_top", "sg_window_rank_select",
     "sg_set_incidents", "sg_window_incidents", "sg_window_node_incident", "sg_window_incidents_buffer",
     "sg_set_tracks", "sg_window_incident_tracks", "sg_window_tracks_ended", "sg_window_tracks_buffer", "sg_track_entries", "sg_track_stats_get",
+    "sg_set_groups", "sg_group_assign", "sg_window_groups", "sg_window_row_group", "sg_window_group_perm", "sg_window_groups_buffer",
 ]
 
 #: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
@@ -85,6 +86,13 @@ TRACK_ENTRY_DTYPE = np.dtype([(f, "<u4") for f in ("track", "parent", "first_win
 #: SG_NO_TRACK: no track (the parent of a track that continues none), and sg_incident_track.flags' SG_TRACK_* bits
 NO_TRACK = 0xFFFFFFFF
 TRACK_NEW, TRACK_SPLIT, TRACK_MERGED = 1, 2, 4
+#: sg_group_edge (80 bytes) of include/servicegraph.h: one edge of a window's service map contracted to workloads (K14)
+GROUP_EDGE_DTYPE = np.dtype([(f, "<u8") for f in ("count", "err_count", "sum_ns", "sumsq_us", "max_ns", "score_q32")]
+                            + [(f, "<u4") for f in ("from_ref", "to_ref", "edges", "from_nodes", "first", "alive", "worst_row")]
+                            + [("score_max", "<f4")])
+#: SG_NO_GROUP: a node in no group; SG_REF_GROUP: the ref type of a group in sg_group_edge.from_ref / to_ref
+NO_GROUP = 0xFFFFFFFF
+REF_GROUP = 3
 #: sg_edge_vanished (64 bytes) of include/servicegraph.h: one baseline entry that went silent (K8's vanished list)
 VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
                            ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4"), ("row", "<u4"), ("reserved", "<u4")])
@@ -154,6 +162,10 @@ class SgRankParams(C.Structure):
 
 class SgIncidentParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("by", C.c_uint32), ("min_value", C.c_float), ("reserved", C.c_uint32)]
+
+
+class SgGroupParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_groups", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class SgTrackParams(C.Structure):
@@ -282,6 +294,10 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
         "sg_window_tracks_ended": (C.c_int, [H, P, sz, C.POINTER(sz)]),
         "sg_window_tracks_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
         "sg_track_entries": (C.c_int, [H, P, sz, C.POINTER(sz)]), "sg_track_stats_get": (C.c_int, [H, P]),
+        "sg_set_groups": (C.c_int, [H, P]), "sg_group_assign": (C.c_int, [H, P, P, sz]),
+        "sg_window_groups": (C.c_int, [H, P, sz, C.POINTER(sz)]), "sg_window_row_group": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
+        "sg_window_group_perm": (C.c_int, [H, P, sz, C.POINTER(sz)]),
+        "sg_window_groups_buffer": (C.c_int, [H] + [C.POINTER(C.c_void_p)] * 4),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
@@ -823,6 +839,52 @@ class ServiceGraph:
         s = SgTrackStats()
         self._ck(self._l.sg_track_stats_get(self._h, C.byref(s)))
         return s
+
+    # ---- groups (K14): the window's service map contracted to workloads ----
+    def set_groups(self, params: Optional[dict] = (), **kw):
+        """Switch the per-window contraction to workloads on (sg_set_groups; max_groups (0 = max_known_nodes) as a keyword or a
+        dict; needs no other stage) or off: set_groups(None).  Every call starts from a map with nothing grouped."""
+        if params is None:
+            if kw:
+                raise TypeError("set_groups(None) switches the groups off and takes no parameters")
+            self._ck(self._l.sg_set_groups(self._h, None))
+            return
+        v = dict(max_groups=0)
+        v.update(params or {}); v.update(kw)
+        unknown = set(v) - {"max_groups", "struct_size", "reserved"}
+        if unknown:
+            raise TypeError(f"unknown group parameters: {sorted(unknown)}")
+        r = v.get("reserved", 0)
+        r = (r, 0) if isinstance(r, int) else tuple(r)
+        p = SgGroupParams(v.get("struct_size", C.sizeof(SgGroupParams)), v["max_groups"], (C.c_uint32 * 2)(*r))
+        self._ck(self._l.sg_set_groups(self._h, C.byref(p)))
+
+    def group_assign(self, node_ids, groups):
+        """group[node_ids[i]] = groups[i] (sg_group_assign; NO_GROUP takes a node out of its group).  The windows closed from now
+        on are contracted under the new map."""
+        ids = np.ascontiguousarray(node_ids, dtype=np.uint32)
+        gs = np.ascontiguousarray(np.broadcast_to(np.asarray(groups, dtype=np.uint32), ids.shape))
+        self._ck(self._l.sg_group_assign(self._h, ids.ctypes.data, gs.ctypes.data, len(ids)))
+
+    def window_groups(self) -> np.ndarray:
+        """GROUP_EDGE_DTYPE rows of the last read window (sg_window_groups), ascending by (group key of from, group key of to)"""
+        return self._counted(self._l.sg_window_groups, GROUP_EDGE_DTYPE)
+
+    def window_row_group(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """the group edge of every row of the last read window (sg_window_row_group), or of the rows at `index` (gathered on the
+        device)"""
+        return self._window_rows(self._l.sg_window_row_group, np.dtype("<u4"), index)
+
+    def window_group_perm(self) -> np.ndarray:
+        """the rows of the last read window in group order (sg_window_group_perm): row indices, u32"""
+        return self._counted(self._l.sg_window_group_perm, np.dtype("<u4"))
+
+    def window_groups_buffer(self) -> Tuple[int, int, int, int]:
+        """(device pointer of the sg_group_edge rows, of their u64 count, of the u32 row_group, of the u32 perm) of the window
+        window_run closed last (sg_window_groups_buffer)"""
+        p = [C.c_void_p() for _ in range(4)]
+        self._ck(self._l.sg_window_groups_buffer(self._h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
 
     def window_rank_select(self, k: int, min_share: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
         """Select from the rank rows of the window window_run closed last into device memory (sg_window_rank_select): d_out [cap]

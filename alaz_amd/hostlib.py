@@ -15,6 +15,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB = os.path.join(_HERE, "lib", "libsgdatastore.so")
 
 
+#: sgh_workload_edge of host_capi.cpp: one group edge in the reference's vocabulary (GraphDS::WorkloadEdges)
+WORKLOAD_EDGE_DTYPE = np.dtype([("from_type", "S12"), ("to_type", "S12"), ("from_uid", "S160"), ("to_uid", "S160")]
+                               + [(f, "<u8") for f in ("count", "err_count", "sum_ns", "sumsq_us", "max_ns", "score_q32")]
+                               + [(f, "<u4") for f in ("edges", "from_nodes", "alive", "worst_row")] + [("score_max", "<f4"), ("pad", "<u4")])
+
+
 class EdgeRowC(C.Structure):
     _fields_ = [("from_type", C.c_char * 12), ("to_type", C.c_char * 12), ("from_uid", C.c_char * 160), ("to_uid", C.c_char * 160),
                 ("count", C.c_uint32), ("err_count", C.c_uint32), ("sum_ns", C.c_uint64), ("max_ns", C.c_uint64), ("sumsq_us", C.c_uint64),
@@ -94,6 +100,10 @@ def load() -> C.CDLL:
             "sgh_mock_events": (sz, [P, P, sz]), "sgh_mock_table_ops": (sz, [P, P, sz]), "sgh_mock_label_count": (u32, [P]),
             "sgh_graphds_set_selection": (C.c_int, [P, u32, C.c_float]), "sgh_graphds_clear_selection": (None, [P]), "sgh_graphds_sink_rows": (sz, [P]),
             "sgh_mock_flushes": (None, [P, P, C.POINTER(C.c_float)]),
+            "sgh_graphds_persist_pod_owned": (C.c_int, [P, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
+            "sgh_graphds_persist_replicaset": (C.c_int, [P, C.c_char_p, C.c_char_p, C.c_char_p]),
+            "sgh_graphds_set_workload_groups": (C.c_int, [P, u32]), "sgh_graphds_workload_edges": (C.c_long, [P, P, sz]),
+            "sgh_mock_group_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -394,6 +404,33 @@ class GraphDS:
             rows.append((r.from_type.decode(), r.from_uid.decode(), r.to_type.decode(), r.to_uid.decode(), r.count, r.err_count, r.sum_ns,
                          r.max_ns, r.sumsq_us, r.score, r.lat_z, r.err_ratio, r.alive, r.p50_us, r.p99_us))
         return n, rows
+
+    # ---- the workload view (K14) ----
+    def PersistPodOwned(self, uid: str, ip: str, owner_id: str = "", event_type: str = "ADD"):
+        return self._l.sgh_graphds_persist_pod_owned(self._g, event_type.encode(), uid.encode(), ip.encode(), owner_id.encode())
+
+    def PersistReplicaSet(self, uid: str, owner_id: str = "", event_type: str = "ADD"):
+        return self._l.sgh_graphds_persist_replicaset(self._g, event_type.encode(), uid.encode(), owner_id.encode())
+
+    def set_workload_groups(self, max_groups: int = 0) -> int:
+        """GraphDS::SetWorkloadGroups: pods are grouped by their top known owner from now on (rc)"""
+        return self._l.sgh_graphds_set_workload_groups(self._g, max_groups)
+
+    def workload_edges(self) -> np.ndarray:
+        """GraphDS::WorkloadEdges: the last flushed window's group edges, WORKLOAD_EDGE_DTYPE"""
+        n = self._l.sgh_graphds_workload_edges(self._g, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadEdges failed: {n}")
+        out = np.zeros(max(n, 1), dtype=WORKLOAD_EDGE_DTYPE)
+        self._l.sgh_graphds_workload_edges(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    def mock_group_ops(self) -> np.ndarray:
+        """the stand-in engine's group calls in order: (node id, group) per sg_group_assign pair, (0xFFFFFFFE, max_groups) per sg_set_groups"""
+        n = self._l.sgh_mock_group_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 2), dtype=np.uint32)
+        self._l.sgh_mock_group_ops(self._g, out.ctypes.data, n)
+        return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:
         """GraphDS::SetSelection: from the next FlushWindow on only the selected rows reach the sink (rc, SG_EINVAL for k > 16384)."""

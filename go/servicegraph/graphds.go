@@ -926,6 +926,91 @@ func (g *GraphDS) WindowTracksEnded() ([]TrackEntry, error) {
 	return out, nil
 }
 
+// GroupEdge is one edge of a window's service map contracted to workloads (sg_group_edge): every row from a pod of one group
+// (or one ungrouped node) to a pod of another, folded into one.  FromRef / ToRef are group refs: IsGroup(ref) tells a group
+// (its id in the low 30 bits) from the node ref of an ungrouped node.
+type GroupEdge struct {
+	FromRef, ToRef                                 uint32
+	Count, ErrCount, SumNs, SumSqUs, MaxNs, ScoreQ uint64
+	Edges, FromNodes, First, Alive, WorstRow       uint32
+	ScoreMax                                       float32
+}
+
+// NoGroup is SG_NO_GROUP: AssignGroups takes a node out of its group with it.
+const NoGroup = uint32(C.SG_NO_GROUP)
+
+// IsGroup tells whether a GroupEdge ref names a group (then ref & 0x3FFFFFFF is its id) rather than a node.
+func IsGroup(ref uint32) bool { return ref>>30 == uint32(C.SG_REF_GROUP) }
+
+// SetGroups switches the per-window contraction to workloads on (maxGroups = 0: as many groups as node ids) with nothing
+// grouped; ClearGroups switches it off.  It needs none of the other stages.
+func (g *GraphDS) SetGroups(maxGroups uint32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var gp C.sg_group_params
+	gp.struct_size = C.uint32_t(unsafe.Sizeof(gp))
+	gp.max_groups = C.uint32_t(maxGroups)
+	if rc := C.sg_set_groups(g.h, &gp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_groups = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func (g *GraphDS) ClearGroups() {
+	g.flushMu.Lock()
+	C.sg_set_groups(g.h, nil)
+	g.flushMu.Unlock()
+}
+
+// AssignGroups puts node nodeIDs[i] into group groups[i] (NoGroup: into none), in that order; the windows closed from now on
+// see it.  The ids are the node ids PersistPod / PersistService interned (the pod's workload is the caller's to resolve:
+// Pod.OwnerID, its ReplicaSet's OwnerID).
+func (g *GraphDS) AssignGroups(nodeIDs, groups []uint32) error {
+	if len(nodeIDs) != len(groups) {
+		return fmt.Errorf("servicegraph: AssignGroups: %d ids, %d groups", len(nodeIDs), len(groups))
+	}
+	if len(nodeIDs) == 0 {
+		return nil
+	}
+	ids := (*C.uint32_t)(unsafe.Pointer(&nodeIDs[0]))
+	gs := (*C.uint32_t)(unsafe.Pointer(&groups[0]))
+	if rc := C.sg_group_assign(g.h, ids, gs, C.size_t(len(nodeIDs))); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_group_assign = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+// WindowGroupEdges returns the group edges of the window FlushWindow returned last, ascending by (from, to) with the groups
+// first (sg_window_groups: 80 bytes per group edge cross PCIe, not 64 per row).
+func (g *GraphDS) WindowGroupEdges() ([]GroupEdge, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_groups(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_groups = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	ges := make([]C.sg_group_edge, int(n))
+	if rc := C.sg_window_groups(g.h, &ges[0], C.size_t(len(ges)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_groups = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(n) < len(ges) {
+		ges = ges[:int(n)]
+	}
+	out := make([]GroupEdge, len(ges))
+	for i := range ges {
+		ge, o := &ges[i], &out[i]
+		o.FromRef, o.ToRef = uint32(ge.from_ref), uint32(ge.to_ref)
+		o.Count, o.ErrCount, o.SumNs, o.SumSqUs = uint64(ge.count), uint64(ge.err_count), uint64(ge.sum_ns), uint64(ge.sumsq_us)
+		o.MaxNs, o.ScoreQ = uint64(ge.max_ns), uint64(ge.score_q32)
+		o.Edges, o.FromNodes, o.First, o.Alive = uint32(ge.edges), uint32(ge.from_nodes), uint32(ge.first), uint32(ge.alive)
+		o.WorstRow, o.ScoreMax = uint32(ge.worst_row), float32(ge.score_max)
+	}
+	return out, nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

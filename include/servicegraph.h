@@ -697,6 +697,72 @@ int sg_window_tracks_buffer(sg_handle h, void** d_tracks, void** d_ended, void**
 int sg_track_entries(sg_handle h, sg_track_entry* out, size_t cap, size_t* n);
 int sg_track_stats_get(sg_handle h, sg_track_stats* out);   /* (waits for the updates enqueued so far) */
 
+/* ---- groups (K14): each window's service map contracted to workloads, on the device ------------------------------------------- *
+ * Opt-in (sg_set_groups); without it nothing is computed or allocated, and every other row is the same either way.  It needs none
+ * of K8 - K13 and changes none of them.  Every pod is its own node, so a Deployment of 20 replicas calling one service makes 20
+ * rows; the host assigns KNOWN node ids to groups (workloads) and each window's rows are contracted to one row per (group, group).
+ *   group map   group[id] in [0, max_groups) or SG_NO_GROUP (the initial value of every id, and again after every sg_set_groups);
+ *               LABEL and OBIP nodes are never grouped
+ *   group ref   of a node ref r: SG_MAKE_REF(SG_REF_GROUP, g) when r is KNOWN and group[SG_REF_VALUE(r)] = g != SG_NO_GROUP, else r
+ *   group key   gk(r) = g for a grouped node, else max_groups + k with k = K9's node key of r: v (KNOWN), max_known_nodes + v
+ *               (LABEL), max_known_nodes + max_labels + v (OBIP), v = SG_REF_VALUE(r).  gk < GK = max_groups + the engine's node
+ *               capacity.  Ascending gk: the groups by id, then the ungrouped KNOWN nodes by id, then LABEL, then OBIP by index
+ *   perm        over the window's rows r_0 .. r_{E-1} (canonical order): the permutation of 0 .. E-1 ascending by
+ *               (gk(from_ref), gk(to_ref), row index) — one total order, so perm has exactly one correct value
+ *   group edge  a maximal run of perm with equal (gk(from_ref), gk(to_ref)); the group edges come out in that order.  A run with
+ *               gk(from) == gk(to) (traffic inside a workload) is an ordinary group edge
+ * Group edge fields, over the rows of its run:
+ *   count, err_count        u64 sums                        sum_ns, sumsq_us   wrapping u64 sums
+ *   max_ns                  max                             alive              wrapping u32 sum
+ *   score_q32, score_max, worst_row   K9's definitions: the wrapping u64 sum of (uint64_t)((double)score * 2^32) (a score that is
+ *                           not > 0 adds 0); the largest score, +0.0 above -0.0; the smallest row index that has it
+ *   from_ref, to_ref        the group refs of the rows' endpoints
+ *   edges                   rows in the run (alive-only rows included)
+ *   first                   the position in perm of the run's first row
+ *   from_nodes              distinct from_ref in the run: the positions of the run that are its first, or whose row's from_ref
+ *                           differs from the from_ref of the position before.  This counts distinct refs only because perm is
+ *                           stable and the rows are sorted by from first: within a run the row indices ascend, so equal from_refs
+ *                           are adjacent
+ * row_group[j] = the index of the group edge row j belongs to.  Every field is an integer sum, an integer max or a max of a key:
+ * the result has one correct value.  Every close path computes it (one call, begin + end, the views, the _top flushes,
+ * sg_window_run, the staged sg_window_score), behind K5 (and K8 - K13 where they are on).                                     */
+#define SG_REF_GROUP 3u         /* a workload: payload = the group id (sg_group_edge only)      */
+#define SG_NO_GROUP  0xFFFFFFFFu
+typedef struct sg_group_params {
+    uint32_t struct_size;       /* sizeof(sg_group_params)                                      */
+    uint32_t max_groups;        /* group ids are below it, at most 2^30; 0 = max_known_nodes    */
+    uint32_t reserved[2];       /* 0                                                            */
+} sg_group_params;              /* 16 bytes */
+typedef struct sg_group_edge {
+    uint64_t count, err_count, sum_ns, sumsq_us, max_ns, score_q32;
+    uint32_t from_ref, to_ref;  /* group refs                                                   */
+    uint32_t edges;             /* rows in the run (alive-only rows included)                   */
+    uint32_t from_nodes;        /* distinct from_ref in the run                                 */
+    uint32_t first;             /* position in perm of the run's first row                      */
+    uint32_t alive;             /* wrapping u32 sum                                             */
+    uint32_t worst_row;         /* smallest row index among the rows whose score == score_max  */
+    float    score_max;
+} sg_group_edge;                /* 80 bytes, no padding */
+/* NULL = off (frees its memory); params = on.  Memory is allocated here, never at create.  Every call resets the map to "nothing
+ * grouped".  SG_EINVAL on an engine with world > 1, a bad struct_size, non-zero reserved or max_groups > 2^30; SG_ESTATE while a
+ * flush is open.  Group calls on an engine without it: SG_ESTATE.                                                              */
+int sg_set_groups(sg_handle h, const sg_group_params* p);
+/* group[node_ids[i]] = groups[i], i = 0 .. n-1 in that order.  SG_EINVAL for an id >= max_known_nodes or a group >= max_groups that
+ * is not SG_NO_GROUP: then nothing is applied.  A window closed after the call returns is contracted under the new map; a window
+ * closed before it is not, not even one still in flight on another slot.                                                       */
+int sg_group_assign(sg_handle h, const uint32_t* node_ids, const uint32_t* groups, size_t n);
+/* The group edges of the last READ window (as sg_window_incidents): *n = group edges, min(*n, cap) are written.  SG_ESTATE for a
+ * window closed while the groups were off, and while a flush is open.                                                         */
+int sg_window_groups(sg_handle h, sg_group_edge* out, size_t cap, size_t* n);
+/* row_group of the last READ window (as sg_window_trend): row_index NULL: every row, *n = edges; else out[k] = row_group of row
+ * row_index[k] (each < edges, else SG_EINVAL), gathered on the device, *n = n_index.  min(*n, cap) values are written.           */
+int sg_window_row_group(sg_handle h, const uint32_t* row_index, size_t n_index, uint32_t* out, size_t cap, size_t* n);
+/* perm of the last READ window: *n = edges, min(*n, cap) values are written.                                                    */
+int sg_window_group_perm(sg_handle h, uint32_t* out, size_t cap, size_t* n);
+/* Device sg_group_edge[], their count (one uint64_t), uint32_t row_group[edges] and uint32_t perm[edges] of the window
+ * sg_window_run closed last (valid until its slot is reused; read them on that window's stream).                               */
+int sg_window_groups_buffer(sg_handle h, void** d_edges, void** d_count, void** d_row_group, void** d_perm);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
