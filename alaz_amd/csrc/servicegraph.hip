@@ -669,6 +669,37 @@ int do_layer(sg_engine* e, u32 l, hipStream_t s, bool fuse_proj) {
     return fuse_proj ? SG_OK : note_w_read(e, s);           // (the one-call pipelines score on the same stream next: K5's event covers K4)
 }
 
+// ---- the opt-in stages' (K8 - K14) shared launch code (engine lock held) ---------------------------------------------------------
+// Plain functions over the members every stage struct has under the same names: on, mem, ev, pending, valid.
+// In front of a stage's launches on stream s: behind its previous run, whichever stream that was on.  Behind them: a failed launch
+// is the call's error, and the event is what the next run and the host's reads wait for.
+template <class X>
+int stage_wait(sg_engine* e, X& x, hipStream_t s) {
+    if (x.pending) HIP_TRY(e, hipStreamWaitEvent(s, x.ev, 0));
+    return SG_OK;
+}
+template <class X>
+int stage_done(sg_engine* e, X& x, hipStream_t s) {
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(x.ev, s));
+    x.pending = true;
+    return SG_OK;
+}
+// NodesArgs' part every launcher behind K5 fills alike: the window's rows and counters and the id spaces (k9_node, k9_rows_of)
+NodesArgs nodes_view(const sg_engine* e, const sg_engine::WinSlot& w, u32 ncap) {
+    NodesArgs a{};
+    a.rows = w.d.rows; a.ctr = w.d.ctr; a.max_edges = e->cfg.max_edges;
+    a.mk = w.d.max_known; a.ml = w.d.max_labels; a.mob = w.d.max_obip; a.ncap = ncap;
+    return a;
+}
+// a stage off: nothing of it in flight, its block and its event gone, every member as at create
+template <class X>
+void free_stage(X& x) {
+    if (x.mem) { hipDeviceSynchronize(); hipFree(x.mem); }
+    if (x.ev) hipEventDestroy(x.ev);
+    x = X{};
+}
+
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
 static_assert(sizeof(KcScratch) <= sgplan::kPrepareLds, "a folded close's prepare workgroup lays KcScratch over pass B's dynamic LDS");
 static_assert(sizeof(sg_edge_vanished) == 64 && sgplan::kTrendThreads == K8_THREADS && sgplan::kTrendMaxWgs <= K8_SCAN_THREADS,
@@ -689,11 +720,9 @@ TrendArgs baseline_args(const sg_engine::WinSlot& w, const sg_engine::Baseline<R
 // enqueue an update of t on stream s (the launches: launch()) behind the previous update (any stream)
 template <class Row, class F>
 int enqueue_baseline(sg_engine* e, sg_engine::Baseline<Row>& t, hipStream_t s, F launch) {
-    if (t.pending) HIP_TRY(e, hipStreamWaitEvent(s, t.ev, 0));
+    if (const int rc = stage_wait(e, t, s)) return rc;
     launch();
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(t.ev, s));
-    t.pending = true;
+    if (const int rc = stage_done(e, t, s)) return rc;
     t.w++;
     return SG_OK;
 }
@@ -729,21 +758,17 @@ int launch_nodes(sg_engine* e, hipStream_t s) {
     sg_engine::WinSlot& w = work(e);
     sg_engine::Nodes& n = e->nodes;
     const sgplan::NodesPlan& P = n.plan;
-    NodesArgs a{};
-    a.rows = w.d.rows; a.ctr = w.d.ctr; a.max_edges = e->cfg.max_edges;
-    a.mk = w.d.max_known; a.ml = w.d.max_labels; a.mob = w.d.max_obip; a.ncap = P.ncap;
+    NodesArgs a = nodes_view(e, w, P.ncap);
     a.slices = P.slices; a.node_per = P.node_per;
     a.dst = n.dst; a.tout = n.tout; a.tin = n.tin; a.part = n.part; a.blk = n.blk;
     a.out = n.rows[e->cur]; a.count = n.count[e->cur];
-    if (n.pending) HIP_TRY(e, hipStreamWaitEvent(s, n.ev, 0));
+    if (const int rc = stage_wait(e, n, s)) return rc;
     hipLaunchKernelGGL(k9_out, dim3(P.out_wgs), dim3(K9_THREADS), 0, s, a);
     hipLaunchKernelGGL(k9_in_part, dim3(P.ranges * P.slices), dim3(K9_IN_THREADS), (size_t)P.lds_bytes, s, a);
     hipLaunchKernelGGL(k9_count, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
     hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a, P.node_wgs);
     hipLaunchKernelGGL(k9_write, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(n.ev, s));
-    n.pending = true;
+    if (const int rc = stage_done(e, n, s)) return rc;
     n.valid[e->cur] = 1;
     return SG_OK;
 }
@@ -768,11 +793,9 @@ int launch_node_trend(sg_engine* e, hipStream_t s) {
 template <class Row>
 void free_baseline(sg_engine::Baseline<Row>& t) {
     if (t.mem || t.stage) hipDeviceSynchronize();
-    if (t.mem) hipFree(t.mem);
-    if (t.stage) hipFree(t.stage);
+    if (t.stage) hipFree(t.stage);                                    // the readback's staging (baseline_rows), grown on demand
     if (t.stage_idx) hipFree(t.stage_idx);
-    if (t.ev) hipEventDestroy(t.ev);
-    t = sg_engine::Baseline<Row>{};
+    free_stage(t);
 }
 
 // ---- K11, the culprit ranking (engine lock held) ---------------------------------------------------------------------------------
@@ -785,13 +808,12 @@ int launch_rank(sg_engine* e, hipStream_t s) {
     sg_engine::Rank& r = e->rank;
     const sgplan::RankPlan& P = r.plan;
     RankArgs a{};
-    a.nd.rows = w.d.rows; a.nd.ctr = w.d.ctr; a.nd.max_edges = e->cfg.max_edges;
-    a.nd.mk = w.d.max_known; a.nd.ml = w.d.max_labels; a.nd.mob = w.d.max_obip; a.nd.ncap = P.ncap;
+    a.nd = nodes_view(e, w, P.ncap);
     a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur];
     a.slices = P.slices; a.prep_wgs = P.prep_wgs; a.damping = r.p.damping_q8; a.seed = r.p.seed; a.seed_min = r.p.seed_min_score;
     a.src = r.src; a.dst = r.dst; a.w = r.w; a.W = r.W; a.R = r.R; a.base = r.base; a.t = r.t; a.part = r.part; a.seed_sum = r.seed_sum;
     a.out = r.rows[e->cur];
-    if (r.pending) HIP_TRY(e, hipStreamWaitEvent(s, r.ev, 0));
+    if (const int rc = stage_wait(e, r, s)) return rc;
     const dim3 eg(P.ranges * P.slices), et(K11_EDGE_THREADS), ng(P.node_wgs), nt(K11_THREADS);
     hipLaunchKernelGGL(k11_prep, dim3(P.prep_wgs), nt, 0, s, a);
     hipLaunchKernelGGL(k11_edge<true>, eg, et, (size_t)P.lds_bytes, s, a);
@@ -801,18 +823,11 @@ int launch_rank(sg_engine* e, hipStream_t s) {
         if (i < r.p.iters) hipLaunchKernelGGL((k11_node<false, false>), ng, nt, 0, s, a);
         else hipLaunchKernelGGL((k11_node<false, true>), ng, nt, 0, s, a);
     }
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(r.ev, s));
-    r.pending = true;
+    if (const int rc = stage_done(e, r, s)) return rc;
     r.valid[e->cur] = 1;
     return SG_OK;
 }
-void free_rank(sg_engine* e) {
-    sg_engine::Rank& r = e->rank;
-    if (r.mem) { hipDeviceSynchronize(); hipFree(r.mem); }
-    if (r.ev) hipEventDestroy(r.ev);
-    r = sg_engine::Rank{};
-}
+void free_rank(sg_engine* e) { free_stage(e->rank); }
 
 // ---- K12, the incidents (engine lock held) -----------------------------------------------------------------------------------------
 static_assert(sgplan::kIncThreads == K12_THREADS && sgplan::kIncMaxWgs == K12_MAX_WGS && sgplan::kIncKeysBytes == sizeof(K12Keys),
@@ -824,8 +839,7 @@ int launch_incidents(sg_engine* e, hipStream_t s) {
     sg_engine::Incidents& x = e->inc;
     const sgplan::IncidentPlan& P = x.plan;
     IncArgs a{};
-    a.nd.rows = w.d.rows; a.nd.ctr = w.d.ctr; a.nd.max_edges = e->cfg.max_edges;
-    a.nd.mk = w.d.max_known; a.nd.ml = w.d.max_labels; a.nd.mob = w.d.max_obip; a.nd.ncap = P.ncap;
+    a.nd = nodes_view(e, w, P.ncap);
     a.nd.blk = x.blk; a.nd.count = x.count[e->cur];                  // (k9_scan: the head counts in, their scan and the incident count out)
     a.nodes = e->nodes.rows[e->cur]; a.ncount = e->nodes.count[e->cur];
     a.trend = x.p.by != SG_SEL_SCORE ? e->trend.rows[e->cur] : nullptr;
@@ -833,7 +847,7 @@ int launch_incidents(sg_engine* e, hipStream_t s) {
     a.by = x.p.by; a.min_value = x.p.min_value; a.node_per = P.node_per;
     a.parent = x.parent; a.flag = x.flag; a.lab = x.lab; a.num = x.num; a.kinc = x.kinc; a.keys = x.keys;
     a.out = x.rows[e->cur]; a.node_inc = x.node_inc[e->cur];
-    if (x.pending) HIP_TRY(e, hipStreamWaitEvent(s, x.ev, 0));
+    if (const int rc = stage_wait(e, x, s)) return rc;
     const dim3 nt(K12_THREADS), gg(P.grid_wgs), ng(P.node_wgs);
     hipLaunchKernelGGL(k12_init, gg, nt, 0, s, a);
     hipLaunchKernelGGL(k12_hook, dim3(P.hook_wgs), nt, 0, s, a);
@@ -843,9 +857,7 @@ int launch_incidents(sg_engine* e, hipStream_t s) {
     hipLaunchKernelGGL(k12_nodes, gg, nt, 0, s, a);
     hipLaunchKernelGGL(k12_rows, dim3(P.row_wgs), nt, 0, s, a);
     hipLaunchKernelGGL(k12_finish, gg, nt, 0, s, a);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(x.ev, s));
-    x.pending = true;
+    if (const int rc = stage_done(e, x, s)) return rc;
     x.valid[e->cur] = 1;
     return SG_OK;
 }
@@ -859,7 +871,7 @@ int launch_tracks(sg_engine* e, hipStream_t s) {
     sg_engine::Tracks& x = e->trk;
     const sgplan::TrackPlan& P = x.plan;
     TrkArgs a{};
-    a.nd.mk = w.d.max_known; a.nd.ml = w.d.max_labels; a.nd.mob = w.d.max_obip; a.nd.ncap = P.ncap;
+    a.nd = nodes_view(e, w, P.ncap);                                  // (k9_node reads the id spaces only)
     a.nodes = e->nodes.rows[e->cur]; a.ncount = e->nodes.count[e->cur];
     a.inc = e->inc.rows[e->cur]; a.icount = e->inc.count[e->cur]; a.node_inc = e->inc.node_inc[e->cur];
     a.w = (u32)x.w; a.quiet = x.p.quiet_windows; a.max_tracks = P.max_tracks; a.per = P.per;
@@ -867,7 +879,7 @@ int launch_tracks(sg_engine* e, hipStream_t s) {
     a.told = x.tab[x.cur]; a.tnew = x.tab[x.cur ^ 1]; a.sold = x.st[x.cur]; a.snew = x.st[x.cur ^ 1];
     a.cand = x.cand; a.kept = x.kept; a.moved = x.moved; a.joined = x.joined; a.pos = x.pos; a.tv = x.tv; a.claim = x.claim; a.blk = x.blk;
     a.out = x.rows[e->cur]; a.ended = x.ended[e->cur]; a.ended_count = x.ended_count[e->cur];
-    if (x.pending) HIP_TRY(e, hipStreamWaitEvent(s, x.ev, 0));
+    if (const int rc = stage_wait(e, x, s)) return rc;
     const dim3 nt(K13_THREADS), ng(P.node_wgs), fg(P.fold_wgs), sg(P.wgs);
     hipLaunchKernelGGL(k13_init, dim3(P.init_wgs), nt, 0, s, a);
     hipLaunchKernelGGL(k13_look, fg, nt, 0, s, a);
@@ -877,19 +889,12 @@ int launch_tracks(sg_engine* e, hipStream_t s) {
     hipLaunchKernelGGL(k13_scan, dim3(1), dim3(K13_SCAN_THREADS), 0, s, a, P.wgs);
     hipLaunchKernelGGL(k13_write, sg, nt, 0, s, a);
     hipLaunchKernelGGL(k13_members, ng, nt, 0, s, a);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(x.ev, s));
-    x.pending = true;
+    if (const int rc = stage_done(e, x, s)) return rc;
     x.valid[e->cur] = 1;
     x.cur ^= 1; x.w += 1;
     return SG_OK;
 }
-void free_tracks(sg_engine* e) {
-    sg_engine::Tracks& x = e->trk;
-    if (x.mem) { hipDeviceSynchronize(); hipFree(x.mem); }
-    if (x.ev) hipEventDestroy(x.ev);
-    x = sg_engine::Tracks{};
-}
+void free_tracks(sg_engine* e) { free_stage(e->trk); }
 
 // ---- K14, the groups (engine lock held) --------------------------------------------------------------------------------------------
 static_assert(sgplan::kGrpThreads == K14_THREADS && sgplan::kGrpTile == K14_TILE && sgplan::kGrpChunk == K14_CHUNK && sgplan::kGrpMaxWgs == K9_MAX_WGS &&
@@ -920,13 +925,12 @@ int launch_groups(sg_engine* e, hipStream_t s) {
     sg_engine::Groups& x = e->grp;
     const sgplan::GroupPlan& P = x.plan;
     GroupArgs a{};
-    a.nd.rows = w.d.rows; a.nd.ctr = w.d.ctr; a.nd.max_edges = e->cfg.max_edges;
-    a.nd.mk = w.d.max_known; a.nd.ml = w.d.max_labels; a.nd.mob = w.d.max_obip; a.nd.ncap = w.d.max_known + w.d.max_labels + w.d.max_obip;
+    a.nd = nodes_view(e, w, w.d.max_known + w.d.max_labels + w.d.max_obip);
     a.nd.blk = x.blk; a.nd.count = x.count[e->cur];                  // (k9_scan: the head counts in, their scan and the group edge count out)
     a.map = x.map; a.max_groups = P.max_groups; a.gk = (u32)P.gk; a.kb = P.kb; a.cpw = P.cpw; a.max_chunks = P.chunks;
     a.hist = x.hist; a.chunkcnt = x.chunkcnt; a.part = x.part; a.meta = x.meta;
     a.out = x.rows[e->cur]; a.row_group = x.row_group[e->cur]; a.perm = x.perm[e->cur];
-    if (x.pending) HIP_TRY(e, hipStreamWaitEvent(s, x.ev, 0));
+    if (const int rc = stage_wait(e, x, s)) return rc;
     if (x.dirty_hi > x.dirty_lo) {                                    // the windows closed before read the map as it was: the upload is behind them
         if (x.up_pending) HIP_TRY(e, hipEventSynchronize(x.up_ev));
         const size_t n = x.dirty_hi - x.dirty_lo;
@@ -938,41 +942,32 @@ int launch_groups(sg_engine* e, hipStream_t s) {
     }
     if (P.key_bytes == 4) launch_group_kernels<u32>(P, a, x.keys, x.idx, s);
     else launch_group_kernels<u64>(P, a, x.keys, x.idx, s);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(x.ev, s));
-    x.pending = true;
+    if (const int rc = stage_done(e, x, s)) return rc;
     x.valid[e->cur] = 1;
     return SG_OK;
 }
 void free_groups(sg_engine* e) {
     sg_engine::Groups& x = e->grp;
-    if (x.mem) { hipDeviceSynchronize(); hipFree(x.mem); }
+    if (x.mem) hipDeviceSynchronize();                                // (an upload may still read h_up)
     if (x.h_up) hipHostFree(x.h_up);
-    if (x.ev) hipEventDestroy(x.ev);
     if (x.up_ev) hipEventDestroy(x.up_ev);
-    x = sg_engine::Groups{};
+    free_stage(x);
 }
 
 void free_incidents(sg_engine* e) {
     free_tracks(e);
-    sg_engine::Incidents& x = e->inc;
-    if (x.mem) { hipDeviceSynchronize(); hipFree(x.mem); }
-    if (x.ev) hipEventDestroy(x.ev);
-    x = sg_engine::Incidents{};
+    free_stage(e->inc);
 }
 
 void free_nodes(sg_engine* e) {
     free_incidents(e);
     free_rank(e);
     free_baseline(e->ntrend);
-    sg_engine::Nodes& n = e->nodes;
-    if (n.mem) { hipDeviceSynchronize(); hipFree(n.mem); }
-    if (n.ev) hipEventDestroy(n.ev);
-    n = sg_engine::Nodes{};
+    free_stage(e->nodes);
 }
 
 void free_vanished(sg_engine* e) {
-    sg_engine::Vanished& v = e->vanished;
+    sg_engine::Vanished& v = e->vanished;                             // (no event of its own, the trend's: not free_stage)
     if (v.mem) { hipDeviceSynchronize(); hipFree(v.mem); }
     v = sg_engine::Vanished{};
 }
@@ -1208,7 +1203,7 @@ int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_
     enqueue_k7_select(st, a, k, wgs, NC);
     const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, NC) : NC);
     const dim3 grid((unsigned)std::max<u64>(1, std::min<u64>((m + 255) / 256, 1024)));
-    if (d_out) hipLaunchKernelGGL(k10_gather_rows, grid, dim3(256), 0, st, nodes, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
+    if (d_out) hipLaunchKernelGGL(k_gather_sel<sg_node_out>, grid, dim3(256), 0, st, nodes, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
     after(a, grid);
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipEventRecord(s.ev, st));
@@ -1234,7 +1229,7 @@ int launch_rank_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_
         hipLaunchKernelGGL(k11_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, rk, (const u64*)e->nodes.count[slot], e->nsel.ctr);
         return (int)SG_OK;
     }, [&](const SelArgs& a, dim3 grid) {
-        if (d_rank) hipLaunchKernelGGL(k11_gather_sel, grid, dim3(256), 0, st, rk, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_rank);
+        if (d_rank) hipLaunchKernelGGL(k_gather_sel<sg_node_rank>, grid, dim3(256), 0, st, rk, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_rank);
     });
 }
 // the host form of a node selection over the last read window (sg_window_nodes_top, sg_window_rank_top): launch(out_stage,
@@ -1296,36 +1291,83 @@ int baseline_on(sg_engine* e, sg_engine::Baseline<Row>& t, const sg_trend_params
     t.on = true;
     return SG_OK;
 }
-// the trend rows of the last read window (slot cur), N of them: every row, or those at idx (an index >= N: SG_EINVAL, `beyond`),
-// gathered on the device so that only they cross PCIe
-template <class Row>
-int baseline_rows(sg_engine* e, sg_engine::Baseline<Row>& t, size_t N, const u32* idx, size_t n_index, Row* out, size_t cap, size_t* n,
-                  void (*gather)(const Row*, const u32*, u64, Row*), const char* beyond) {
-    const Row* src = t.rows[e->cur];
+// The opt-in stages' shared readback.
+// how a stage's messages name it: "<call>: <off>" and "... was closed while <was>"
+struct StageWords { const char* off; const char* was; };
+constexpr StageWords kNodesWords{"the node rollup is off (sg_set_nodes)", "the node rollup was off"};
+constexpr StageWords kVanishedWords{"the vanished list is off (sg_set_vanished)", "the vanished list was off"};
+constexpr StageWords kNodeTrendWords{"the node trend is off (sg_set_node_trend)", "the node trend was off"};
+constexpr StageWords kRankWords{"the ranking is off (sg_set_rank)", "the ranking was off"};
+constexpr StageWords kIncidentsWords{"the incidents are off (sg_set_incidents)", "the incidents were off"};
+constexpr StageWords kTracksWords{"tracking is off (sg_set_tracks)", "tracking was off"};
+constexpr StageWords kGroupsWords{"the groups are off (sg_set_groups)", "the groups were off"};
+// a host read of stage x's rows of the last read window (slot cur): the stage on, no flush open, the window closed with the stage
+// on; then its kernels done
+template <class X>
+int stage_ready(sg_engine* e, const X& x, const char* call, const StageWords& what) {
+    if (!x.on) { e->err = std::string(call) + ": " + what.off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (!x.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while " + what.was; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    return SG_OK;
+}
+// the *_buffer calls: the stage on and the window that ran last closed with it on; its slot (the caller orders its own stream)
+template <class X>
+int stage_slot(sg_engine* e, const X& x, const char* call, const StageWords& what, int* slot) {
+    if (!x.on) { e->err = std::string(call) + ": " + what.off; return SG_ESTATE; }
+    *slot = ran_slot(e);
+    if (!x.valid[*slot]) { e->err = std::string(call) + ": the window was closed while " + what.was; return SG_ESTATE; }
+    return SG_OK;
+}
+// a list whose count is a device word: *n = the count, min(count, cap) elements of elem_bytes each to out
+int copy_counted(sg_engine* e, const u64* d_count, const void* src, size_t elem_bytes, void* out, size_t cap, size_t* n) {
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, d_count, sizeof(u64), hipMemcpyDeviceToHost));
+    if (n) *n = (size_t)cnt;
+    const size_t take = std::min((size_t)cnt, cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * elem_bytes, hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+// N rows at src: every row (idx NULL), or those at idx (an index >= N: SG_EINVAL and `beyond`, before anything is written), gathered
+// on the device so that only they cross PCIe.  The staging holds `chunk` rows: a longer index goes in pieces.
+template <class T>
+int copy_indexed(sg_engine* e, const T* src, size_t N, const u32* idx, size_t n_index, T* out, size_t cap, size_t* n, T* stage,
+                 u32* stage_idx, size_t chunk, const char* beyond) {
     if (!idx) {
         if (n) *n = N;
         const size_t take = std::min(N, cap);
-        if (out && take) { if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev)); HIP_TRY(e, hipMemcpy(out, src, take * sizeof(Row), hipMemcpyDeviceToHost)); }
+        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(T), hipMemcpyDeviceToHost));
         return SG_OK;
     }
     for (size_t k = 0; k < n_index; k++) if (idx[k] >= N) { e->err = beyond; return SG_EINVAL; }
     if (n) *n = n_index;
+    if (!out) return SG_OK;
     const size_t take = std::min(n_index, cap);
-    if (!out || !take) return SG_OK;
-    if (take > t.stage_cap) {
+    for (size_t o = 0; o < take; o += chunk) {
+        const size_t m = std::min(chunk, take - o);
+        HIP_TRY(e, hipMemcpyAsync(stage_idx, idx + o, m * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
+        hipLaunchKernelGGL(k_gather<T>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)stage_idx, (u64)m, stage);
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipMemcpyAsync(out + o, stage, m * sizeof(T), hipMemcpyDeviceToHost, e->rd_stream));
+        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    }
+    return SG_OK;
+}
+// the trend rows of the last read window (slot cur), N of them, through copy_indexed: the staging is the baseline's own, grown to
+// the index (1024 rows at least), so the gather is one piece
+template <class Row>
+int baseline_rows(sg_engine* e, sg_engine::Baseline<Row>& t, size_t N, const u32* idx, size_t n_index, Row* out, size_t cap, size_t* n,
+                  const char* beyond) {
+    const size_t take = std::min(n_index, cap);
+    if (idx && out && take > t.stage_cap) {
         if (t.stage) { hipFree(t.stage); hipFree(t.stage_idx); t.stage = nullptr; t.stage_idx = nullptr; t.stage_cap = 0; }
         const size_t want = std::max<size_t>(take, 1024);
         HIP_TRY(e, hipMalloc((void**)&t.stage, want * sizeof(Row)));
         HIP_TRY(e, hipMalloc((void**)&t.stage_idx, want * sizeof(u32)));
         t.stage_cap = want;
     }
-    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
-    HIP_TRY(e, hipMemcpyAsync(t.stage_idx, idx, take * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
-    hipLaunchKernelGGL(gather, dim3((unsigned)((take + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)t.stage_idx, (u64)take, t.stage);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipMemcpyAsync(out, t.stage, take * sizeof(Row), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    return SG_OK;
+    if (out && t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    return copy_indexed(e, (const Row*)t.rows[e->cur], N, idx, n_index, out, cap, n, t.stage, t.stage_idx, (size_t)t.stage_cap, beyond);
 }
 // the baseline in key order (sg_trend_entries, sg_node_trend_entries)
 template <class Row>
@@ -2159,15 +2201,15 @@ int sg_set_trend(sg_handle e, const sg_trend_params* p) {
 int sg_window_trend(sg_handle e, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->trend.on) { e->err = "sg_window_trend: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    if (!e->trend.on) { e->err = "sg_window_trend: the trend is off (sg_set_trend)"; return SG_ESTATE; }   // (not stage_ready: neither an open flush nor valid is checked)
     const size_t E = (size_t)e->h_ctr[C_N_EDGES];                      // of the last read window
-    return baseline_rows(e, e->trend, E, row_index, n_index, out, cap, n, k8_gather, "sg_window_trend: a row index beyond the window's edges");
+    return baseline_rows(e, e->trend, E, row_index, n_index, out, cap, n, "sg_window_trend: a row index beyond the window's edges");
 }
 int sg_window_trend_buffer(sg_handle e, void** d_trend) {
     if (!e || !d_trend) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Baseline<sg_edge_trend>& t = e->trend;
-    if (!t.on) { e->err = "sg_window_trend_buffer: the trend is off (sg_set_trend)"; return SG_ESTATE; }
+    if (!t.on) { e->err = "sg_window_trend_buffer: the trend is off (sg_set_trend)"; return SG_ESTATE; }   // (not stage_slot: the edge trend keeps no valid)
     *d_trend = t.rows[ran_slot(e)];
     return SG_OK;
 }
@@ -2215,21 +2257,15 @@ int sg_window_vanished(sg_handle e, sg_edge_vanished* out, size_t cap, size_t* n
     if (!v.on) { e->err = "sg_window_vanished: the vanished list is off (sg_set_vanished)"; return SG_ESTATE; }
     if (e->closing || e->flush_open) { e->err = "sg_window_vanished while a flush is open"; return SG_ESTATE; }
     if (!v.valid[e->cur]) { e->err = "sg_window_vanished: the last read window was closed while the vanished list was off"; return SG_ESTATE; }
-    if (e->trend.pending) HIP_TRY(e, hipEventSynchronize(e->trend.ev));
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, v.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    if (n) *n = (size_t)cnt;
-    const size_t take = (size_t)std::min<u64>(std::min<u64>(cnt, v.plan.rows), cap);
-    if (out && take) HIP_TRY(e, hipMemcpy(out, v.rows[e->cur], take * sizeof(sg_edge_vanished), hipMemcpyDeviceToHost));
-    return SG_OK;
+    if (e->trend.pending) HIP_TRY(e, hipEventSynchronize(e->trend.ev));   // (not stage_ready: the list is written by the trend's launches, the event is theirs)
+    return copy_counted(e, v.count[e->cur], v.rows[e->cur], sizeof(sg_edge_vanished), out, std::min<size_t>(cap, v.plan.rows), n);   // (the count may exceed the rows the list holds)
 }
 int sg_window_vanished_buffer(sg_handle e, void** d_rows, void** d_count) {
     if (!e || !d_rows || !d_count) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Vanished& v = e->vanished;
-    if (!v.on) { e->err = "sg_window_vanished_buffer: the vanished list is off (sg_set_vanished)"; return SG_ESTATE; }
-    const int slot = ran_slot(e);
-    if (!v.valid[slot]) { e->err = "sg_window_vanished_buffer: the window was closed while the vanished list was off"; return SG_ESTATE; }
+    int slot;
+    if (const int rc = stage_slot(e, v, "sg_window_vanished_buffer", kVanishedWords, &slot)) return rc;
     *d_rows = v.rows[slot]; *d_count = v.count[slot];
     return SG_OK;
 }
@@ -2264,24 +2300,15 @@ int sg_window_nodes(sg_handle e, sg_node_out* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Nodes& x = e->nodes;
-    if (!x.on) { e->err = "sg_window_nodes: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_window_nodes while a flush is open"; return SG_ESTATE; }
-    if (!x.valid[e->cur]) { e->err = "sg_window_nodes: the last read window was closed while the node rollup was off"; return SG_ESTATE; }
-    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, x.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    if (n) *n = (size_t)cnt;
-    const size_t take = std::min((size_t)cnt, cap);
-    if (out && take) HIP_TRY(e, hipMemcpy(out, x.rows[e->cur], take * sizeof(sg_node_out), hipMemcpyDeviceToHost));
-    return SG_OK;
+    if (const int rc = stage_ready(e, x, "sg_window_nodes", kNodesWords)) return rc;
+    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_node_out), out, cap, n);
 }
 int sg_window_nodes_buffer(sg_handle e, void** d_nodes, void** d_count) {
     if (!e || !d_nodes || !d_count) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Nodes& x = e->nodes;
-    if (!x.on) { e->err = "sg_window_nodes_buffer: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
-    const int slot = ran_slot(e);
-    if (!x.valid[slot]) { e->err = "sg_window_nodes_buffer: the window was closed while the node rollup was off"; return SG_ESTATE; }
+    int slot;
+    if (const int rc = stage_slot(e, x, "sg_window_nodes_buffer", kNodesWords, &slot)) return rc;
     *d_nodes = x.rows[slot]; *d_count = x.count[slot];
     return SG_OK;
 }
@@ -2306,21 +2333,17 @@ int sg_window_node_trend(sg_handle e, const uint32_t* node_index, size_t n_index
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
-    if (!t.on) { e->err = "sg_window_node_trend: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_window_node_trend while a flush is open"; return SG_ESTATE; }
-    if (!t.valid[e->cur]) { e->err = "sg_window_node_trend: the last read window was closed while the node trend was off"; return SG_ESTATE; }
-    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    if (const int rc = stage_ready(e, t, "sg_window_node_trend", kNodeTrendWords)) return rc;
     u64 cnt = 0;
     HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    return baseline_rows(e, t, (size_t)cnt, node_index, n_index, out, cap, n, k10_gather, "sg_window_node_trend: a node index beyond the window's nodes");
+    return baseline_rows(e, t, (size_t)cnt, node_index, n_index, out, cap, n, "sg_window_node_trend: a node index beyond the window's nodes");
 }
 int sg_window_node_trend_buffer(sg_handle e, void** d_trend) {
     if (!e || !d_trend) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
-    if (!t.on) { e->err = "sg_window_node_trend_buffer: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
-    const int slot = ran_slot(e);
-    if (!t.valid[slot]) { e->err = "sg_window_node_trend_buffer: the window was closed while the node trend was off"; return SG_ESTATE; }
+    int slot;
+    if (const int rc = stage_slot(e, t, "sg_window_node_trend_buffer", kNodeTrendWords, &slot)) return rc;
     *d_trend = t.rows[slot];
     return SG_OK;
 }
@@ -2404,41 +2427,18 @@ int sg_window_rank(sg_handle e, const uint32_t* node_index, size_t n_index, sg_n
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     sg_engine::Rank& r = e->rank;
-    if (!r.on) { e->err = "sg_window_rank: the ranking is off (sg_set_rank)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_window_rank while a flush is open"; return SG_ESTATE; }
-    if (!r.valid[e->cur]) { e->err = "sg_window_rank: the last read window was closed while the ranking was off"; return SG_ESTATE; }
-    if (r.pending) HIP_TRY(e, hipEventSynchronize(r.ev));
+    if (const int rc = stage_ready(e, r, "sg_window_rank", kRankWords)) return rc;
     u64 cnt = 0;
     HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    const size_t N = (size_t)cnt;
-    const sg_node_rank* src = r.rows[e->cur];
-    if (!node_index) {
-        if (n) *n = N;
-        const size_t take = std::min(N, cap);
-        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(sg_node_rank), hipMemcpyDeviceToHost));
-        return SG_OK;
-    }
-    for (size_t k = 0; k < n_index; k++) if (node_index[k] >= N) { e->err = "sg_window_rank: a node index beyond the window's nodes"; return SG_EINVAL; }
-    if (n) *n = n_index;
-    const size_t take = std::min(n_index, cap), chunk = std::max<size_t>(r.plan.ncap, 1);
-    if (!out) return SG_OK;
-    for (size_t o = 0; o < take; o += chunk) {                        // (the staging holds ncap rows: a longer index goes in pieces)
-        const size_t m = std::min(chunk, take - o);
-        HIP_TRY(e, hipMemcpyAsync(r.stage_idx, node_index + o, m * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
-        hipLaunchKernelGGL(k11_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)r.stage_idx, (u64)m, r.stage);
-        HIP_TRY(e, hipGetLastError());
-        HIP_TRY(e, hipMemcpyAsync(out + o, r.stage, m * sizeof(sg_node_rank), hipMemcpyDeviceToHost, e->rd_stream));
-        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    }
-    return SG_OK;
+    return copy_indexed(e, (const sg_node_rank*)r.rows[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, r.stage, r.stage_idx,
+                        std::max<size_t>(r.plan.ncap, 1), "sg_window_rank: a node index beyond the window's nodes");
 }
 int sg_window_rank_buffer(sg_handle e, void** d_rank) {
     if (!e || !d_rank) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Rank& r = e->rank;
-    if (!r.on) { e->err = "sg_window_rank_buffer: the ranking is off (sg_set_rank)"; return SG_ESTATE; }
-    const int slot = ran_slot(e);
-    if (!r.valid[slot]) { e->err = "sg_window_rank_buffer: the window was closed while the ranking was off"; return SG_ESTATE; }
+    int slot;
+    if (const int rc = stage_slot(e, r, "sg_window_rank_buffer", kRankWords, &slot)) return rc;
     *d_rank = r.rows[slot];
     return SG_OK;
 }
@@ -2501,65 +2501,29 @@ int sg_set_incidents(sg_handle e, const sg_incident_params* p) {
     x.on = true;
     return SG_OK;
 }
-namespace {
-// the stage on, no flush open, and the last read window grouped; then its grouping done
-int incidents_ready(sg_engine* e, const char* call) {
-    sg_engine::Incidents& x = e->inc;
-    if (!x.on) { e->err = std::string(call) + ": the incidents are off (sg_set_incidents)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
-    if (!x.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while the incidents were off"; return SG_ESTATE; }
-    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
-    return SG_OK;
-}
-}  // namespace
 int sg_window_incidents(sg_handle e, sg_incident_out* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = incidents_ready(e, "sg_window_incidents")) return rc;
     const sg_engine::Incidents& x = e->inc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, x.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    if (n) *n = (size_t)cnt;
-    const size_t take = std::min((size_t)cnt, cap);
-    if (out && take) HIP_TRY(e, hipMemcpy(out, x.rows[e->cur], take * sizeof(sg_incident_out), hipMemcpyDeviceToHost));
-    return SG_OK;
+    if (const int rc = stage_ready(e, x, "sg_window_incidents", kIncidentsWords)) return rc;
+    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_incident_out), out, cap, n);
 }
 int sg_window_node_incident(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = incidents_ready(e, "sg_window_node_incident")) return rc;
-    sg_engine::Incidents& x = e->inc;
+    const sg_engine::Incidents& x = e->inc;
+    if (const int rc = stage_ready(e, x, "sg_window_node_incident", kIncidentsWords)) return rc;
     u64 cnt = 0;
     HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    const size_t N = (size_t)cnt;
-    const u32* src = x.node_inc[e->cur];
-    if (!node_index) {
-        if (n) *n = N;
-        const size_t take = std::min(N, cap);
-        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(u32), hipMemcpyDeviceToHost));
-        return SG_OK;
-    }
-    for (size_t k = 0; k < n_index; k++) if (node_index[k] >= N) { e->err = "sg_window_node_incident: a node index beyond the window's nodes"; return SG_EINVAL; }
-    if (n) *n = n_index;
-    const size_t take = std::min(n_index, cap), chunk = std::max<size_t>(x.plan.ncap, 1);
-    if (!out) return SG_OK;
-    for (size_t o = 0; o < take; o += chunk) {                        // (the staging holds ncap values: a longer index goes in pieces)
-        const size_t m = std::min(chunk, take - o);
-        HIP_TRY(e, hipMemcpyAsync(x.stage_idx, node_index + o, m * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
-        hipLaunchKernelGGL(k12_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)x.stage_idx, (u64)m, x.stage);
-        HIP_TRY(e, hipGetLastError());
-        HIP_TRY(e, hipMemcpyAsync(out + o, x.stage, m * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
-        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    }
-    return SG_OK;
+    return copy_indexed(e, (const u32*)x.node_inc[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, x.stage, x.stage_idx,
+                        std::max<size_t>(x.plan.ncap, 1), "sg_window_node_incident: a node index beyond the window's nodes");
 }
 int sg_window_incidents_buffer(sg_handle e, void** d_incidents, void** d_count, void** d_node_incident) {
     if (!e || !d_incidents || !d_count || !d_node_incident) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Incidents& x = e->inc;
-    if (!x.on) { e->err = "sg_window_incidents_buffer: the incidents are off (sg_set_incidents)"; return SG_ESTATE; }
-    const int slot = ran_slot(e);
-    if (!x.valid[slot]) { e->err = "sg_window_incidents_buffer: the window was closed while the incidents were off"; return SG_ESTATE; }
+    int slot;
+    if (const int rc = stage_slot(e, x, "sg_window_incidents_buffer", kIncidentsWords, &slot)) return rc;
     *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
     return SG_OK;
 }
@@ -2617,73 +2581,36 @@ int sg_group_assign(sg_handle e, const uint32_t* node_ids, const uint32_t* group
     }
     return SG_OK;
 }
-namespace {
-// the stage on, no flush open, and the last read window contracted; then its contraction done
-int groups_ready(sg_engine* e, const char* call) {
-    sg_engine::Groups& x = e->grp;
-    if (!x.on) { e->err = std::string(call) + ": the groups are off (sg_set_groups)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
-    if (!x.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while the groups were off"; return SG_ESTATE; }
-    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
-    return SG_OK;
-}
-}  // namespace
 int sg_window_groups(sg_handle e, sg_group_edge* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = groups_ready(e, "sg_window_groups")) return rc;
     const sg_engine::Groups& x = e->grp;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, x.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    if (n) *n = (size_t)cnt;
-    const size_t take = std::min((size_t)cnt, cap);
-    if (out && take) HIP_TRY(e, hipMemcpy(out, x.rows[e->cur], take * sizeof(sg_group_edge), hipMemcpyDeviceToHost));
-    return SG_OK;
+    if (const int rc = stage_ready(e, x, "sg_window_groups", kGroupsWords)) return rc;
+    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_group_edge), out, cap, n);
 }
 int sg_window_row_group(sg_handle e, const uint32_t* row_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = groups_ready(e, "sg_window_row_group")) return rc;
-    sg_engine::Groups& x = e->grp;
+    const sg_engine::Groups& x = e->grp;
+    if (const int rc = stage_ready(e, x, "sg_window_row_group", kGroupsWords)) return rc;
     const size_t E = (size_t)e->h_ctr[C_N_EDGES];                      // of the last read window
-    const u32* src = x.row_group[e->cur];
-    if (!row_index) {
-        if (n) *n = E;
-        const size_t take = std::min(E, cap);
-        if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * sizeof(u32), hipMemcpyDeviceToHost));
-        return SG_OK;
-    }
-    for (size_t k = 0; k < n_index; k++) if (row_index[k] >= E) { e->err = "sg_window_row_group: a row index beyond the window's edges"; return SG_EINVAL; }
-    if (n) *n = n_index;
-    const size_t take = std::min(n_index, cap), chunk = sgplan::kGrpStage;
-    if (!out) return SG_OK;
-    for (size_t o = 0; o < take; o += chunk) {                        // (the staging holds 65536 values: a longer index goes in pieces)
-        const size_t m = std::min(chunk, take - o);
-        HIP_TRY(e, hipMemcpyAsync(x.stage_idx, row_index + o, m * sizeof(u32), hipMemcpyHostToDevice, e->rd_stream));
-        hipLaunchKernelGGL(k12_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->rd_stream, src, (const u32*)x.stage_idx, (u64)m, x.stage);
-        HIP_TRY(e, hipGetLastError());
-        HIP_TRY(e, hipMemcpyAsync(out + o, x.stage, m * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
-        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    }
-    return SG_OK;
+    return copy_indexed(e, (const u32*)x.row_group[e->cur], E, row_index, n_index, out, cap, n, x.stage, x.stage_idx, (size_t)sgplan::kGrpStage,
+                        "sg_window_row_group: a row index beyond the window's edges");
 }
 int sg_window_group_perm(sg_handle e, uint32_t* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = groups_ready(e, "sg_window_group_perm")) return rc;
-    const size_t E = (size_t)e->h_ctr[C_N_EDGES];
-    if (n) *n = E;
-    const size_t take = std::min(E, cap);
-    if (out && take) HIP_TRY(e, hipMemcpy(out, e->grp.perm[e->cur], take * sizeof(u32), hipMemcpyDeviceToHost));
-    return SG_OK;
+    const sg_engine::Groups& x = e->grp;
+    if (const int rc = stage_ready(e, x, "sg_window_group_perm", kGroupsWords)) return rc;
+    const size_t E = (size_t)e->h_ctr[C_N_EDGES];                      // (a host-side count, so copy_indexed's form without an index)
+    return copy_indexed<u32>(e, x.perm[e->cur], E, nullptr, 0, out, cap, n, nullptr, nullptr, 0, nullptr);
 }
 int sg_window_groups_buffer(sg_handle e, void** d_edges, void** d_count, void** d_row_group, void** d_perm) {
     if (!e || !d_edges || !d_count || !d_row_group || !d_perm) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Groups& x = e->grp;
-    if (!x.on) { e->err = "sg_window_groups_buffer: the groups are off (sg_set_groups)"; return SG_ESTATE; }
-    const int slot = ran_slot(e);
-    if (!x.valid[slot]) { e->err = "sg_window_groups_buffer: the window was closed while the groups were off"; return SG_ESTATE; }
+    int slot;
+    if (const int rc = stage_slot(e, x, "sg_window_groups_buffer", kGroupsWords, &slot)) return rc;
     *d_edges = x.rows[slot]; *d_count = x.count[slot]; *d_row_group = x.row_group[slot]; *d_perm = x.perm[slot];
     return SG_OK;
 }
@@ -2725,45 +2652,24 @@ int sg_set_tracks(sg_handle e, const sg_track_params* p) {
     x.on = true;
     return SG_OK;
 }
-namespace {
-// the stage on, no flush open, and the last read window tracked; then its tracking done
-int tracks_ready(sg_engine* e, const char* call) {
-    sg_engine::Tracks& x = e->trk;
-    if (!x.on) { e->err = std::string(call) + ": tracking is off (sg_set_tracks)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
-    if (!x.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while tracking was off"; return SG_ESTATE; }
-    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
-    return SG_OK;
-}
-// min(cnt, cap) elements of `bytes` each from device src
-int tracks_copy(sg_engine* e, const u64* d_count, const void* src, size_t bytes, void* out, size_t cap, size_t* n) {
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, d_count, sizeof(u64), hipMemcpyDeviceToHost));
-    if (n) *n = (size_t)cnt;
-    const size_t take = std::min((size_t)cnt, cap);
-    if (out && take) HIP_TRY(e, hipMemcpy(out, src, take * bytes, hipMemcpyDeviceToHost));
-    return SG_OK;
-}
-}  // namespace
 int sg_window_incident_tracks(sg_handle e, sg_incident_track* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = tracks_ready(e, "sg_window_incident_tracks")) return rc;
-    return tracks_copy(e, e->inc.count[e->cur], e->trk.rows[e->cur], sizeof(sg_incident_track), out, cap, n);
+    if (const int rc = stage_ready(e, e->trk, "sg_window_incident_tracks", kTracksWords)) return rc;
+    return copy_counted(e, e->inc.count[e->cur], e->trk.rows[e->cur], sizeof(sg_incident_track), out, cap, n);
 }
 int sg_window_tracks_ended(sg_handle e, sg_track_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = tracks_ready(e, "sg_window_tracks_ended")) return rc;
-    return tracks_copy(e, e->trk.ended_count[e->cur], e->trk.ended[e->cur], sizeof(sg_track_entry), out, cap, n);
+    if (const int rc = stage_ready(e, e->trk, "sg_window_tracks_ended", kTracksWords)) return rc;
+    return copy_counted(e, e->trk.ended_count[e->cur], e->trk.ended[e->cur], sizeof(sg_track_entry), out, cap, n);
 }
 int sg_window_tracks_buffer(sg_handle e, void** d_tracks, void** d_ended, void** d_ended_count) {
     if (!e || !d_tracks || !d_ended || !d_ended_count) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const sg_engine::Tracks& x = e->trk;
-    if (!x.on) { e->err = "sg_window_tracks_buffer: tracking is off (sg_set_tracks)"; return SG_ESTATE; }
-    const int slot = ran_slot(e);
-    if (!x.valid[slot]) { e->err = "sg_window_tracks_buffer: the window was closed while tracking was off"; return SG_ESTATE; }
+    int slot;
+    if (const int rc = stage_slot(e, x, "sg_window_tracks_buffer", kTracksWords, &slot)) return rc;
     *d_tracks = x.rows[slot]; *d_ended = x.ended[slot]; *d_ended_count = x.ended_count[slot];
     return SG_OK;
 }

@@ -56,7 +56,6 @@ struct IncArgs {
     u32* node_inc;                // [ncap] this window's incident per node row
 };
 
-__device__ __forceinline__ u64 k12_nodes_of(const IncArgs& a) { const u64 N = *a.ncount; return N < a.nd.ncap ? N : (u64)a.nd.ncap; }
 // the row's value, and whether it is red
 __device__ __forceinline__ bool k12_red(const IncArgs& a, u64 j, u32 s, u32 d, float score, float& value) {
     value = a.by == SG_SEL_SCORE ? score : a.by == SG_SEL_LAT_DEV ? a.trend[j].lat_dev : a.trend[j].err_dev;
@@ -87,7 +86,7 @@ __device__ __forceinline__ void k12_unite(u32* parent, u32 x, u32 y) {
 }
 
 __global__ __launch_bounds__(K12_THREADS) void k12_init(IncArgs a) {
-    const u64 N = k12_nodes_of(a);
+    const u64 N = sg_nodes_of(a.ncount, a.nd.ncap);
     for (u64 v = (u64)blockIdx.x * K12_THREADS + threadIdx.x; v < N; v += (u64)gridDim.x * K12_THREADS) {
         const u32 k = k9_node(a.nd, a.nodes[v].ref);
         if (k == SG_NONE) continue;                                   // (cannot be: K9 made the row from such a key)
@@ -118,7 +117,7 @@ __device__ __forceinline__ void k12_node_span(const IncArgs& a, u64 N, u64& v0, 
 __global__ __launch_bounds__(K12_THREADS) void k12_label(IncArgs a) {
     __shared__ u32 ws[K12_THREADS / 64];
     const u32 t = threadIdx.x;
-    u64 v0, v1; k12_node_span(a, k12_nodes_of(a), v0, v1);
+    u64 v0, v1; k12_node_span(a, sg_nodes_of(a.ncount, a.nd.ncap), v0, v1);
     u32 c = 0;
     for (u64 v = v0 + t; v < v1; v += K12_THREADS) {
         const u32 k = k9_node(a.nd, a.nodes[v].ref);
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(K12_THREADS) void k12_label(IncArgs a) {
 __global__ __launch_bounds__(K12_THREADS) void k12_number(IncArgs a) {
     __shared__ u32 wsum[K12_THREADS / 64 + 1];
     const u32 t = threadIdx.x;
-    u64 v0, v1; k12_node_span(a, k12_nodes_of(a), v0, v1);
+    u64 v0, v1; k12_node_span(a, sg_nodes_of(a.ncount, a.nd.ncap), v0, v1);
     u32 base = a.nd.blk[K12_MAX_WGS + blockIdx.x];
     for (u64 vb = v0; vb < v1; vb += K12_THREADS) {                 // (uniform: every thread takes every round)
         const u64 v = vb + t;
@@ -188,7 +187,7 @@ __global__ __launch_bounds__(K12_THREADS) void k12_nodes(IncArgs a) {
     const u32 t = threadIdx.x;
     for (u32 s = t; s < K12_SLOTS; s += K12_THREADS) { key[s] = K12_EMPTY; cnt[s] = 0; top[s] = 0; rsum[s] = 0; rmax[s] = 0; }
     __syncthreads();
-    const u64 N = k12_nodes_of(a), stride = (u64)gridDim.x * K12_THREADS;
+    const u64 N = sg_nodes_of(a.ncount, a.nd.ncap), stride = (u64)gridDim.x * K12_THREADS;
     for (u64 vb = (u64)blockIdx.x * K12_THREADS; vb < N; vb += stride) {   // (uniform per wave: the wave reductions see 64 lanes)
         const u64 v = vb + t;
         u32 i = SG_NO_INCIDENT;
@@ -270,7 +269,7 @@ __global__ __launch_bounds__(K12_THREADS) void k12_rows(IncArgs a) {
     }
     // the culprit: the smallest node row whose rank is its incident's largest (k12_nodes, the launch before, found that)
     if (a.rank) {
-        const u64 N = k12_nodes_of(a);
+        const u64 N = sg_nodes_of(a.ncount, a.nd.ncap);
         for (u64 v = (u64)blockIdx.x * K12_THREADS + t; v < N; v += stride) {
             const u32 i = a.node_inc[v];
             if (i != SG_NO_INCIDENT && a.rank[v].rank == a.keys[i].rmax) atomicMin(&a.out[i].culprit_node, (u32)v);
@@ -294,10 +293,4 @@ __global__ __launch_bounds__(K12_THREADS) void k12_finish(IncArgs a) {
         o->value_max = k9_key_score((u32)(k.worst >> 32)); o->worst_row = ~(u32)k.worst;   // (an incident has a red row and a node)
         o->top_node = ~(u32)k.top;
     }
-}
-
-// sg_window_node_incident with an index: the asked-for rows gathered on the device
-__global__ __launch_bounds__(256) void k12_gather(const u32* src, const u32* idx, u64 n, u32* dst) {
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
 }

@@ -102,6 +102,7 @@ __device__ __forceinline__ u64 wave_min_u64(u64 v) SG_WAVE_REDUCE(u64, dpp64, rd
 __device__ __forceinline__ u64 wave_max_u64(u64 v) SG_WAVE_REDUCE(u64, dpp64, rdlane64, SG_OP_MAX)
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) SG_WAVE_REDUCE(u64, dpp64, rdlane64, SG_OP_ADD)
 __device__ __forceinline__ u32 wave_sum_u32(u32 v) SG_WAVE_REDUCE(u32, dpp32, rdlane32, SG_OP_ADD)
+__device__ __forceinline__ u32 wave_min_u32(u32 v) SG_WAVE_REDUCE(u32, dpp32, rdlane32, SG_OP_MIN)
 // inclusive scan over the 64 lanes of a wave (all active), no LDS round trip: DPP row_shr 1, 2, 4, 8 (zero fill) scans each row
 // of 16 lanes, then the totals of rows 0..2 reach the rows behind them through v_readlane.  lane: the caller's lane number.
 // (The halo lists of sg_k6.h spell the same sequence themselves: through this function two K6 kernels came out one instruction longer.)
@@ -112,6 +113,20 @@ __device__ __forceinline__ u32 wave_incl_scan_u32(u32 v, u32 lane) {
 }
 // workgroup barrier for LDS traffic only: unlike __syncthreads() it does not drain the global stores in flight
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory"); }
+
+// The gathers of the opt-in stages' readback, one instantiation per row type.  k_gather: a host call with an index (sg_window_trend,
+// sg_window_rank, ...), dst[i] = src[idx[i]] for i < n, so that only the asked-for rows cross PCIe.  k_gather_sel: the rows a node
+// selection picked, out[j] = src[idx[j]] for j < min(*n, cap).
+template <class T>
+__global__ __launch_bounds__(256) void k_gather(const T* src, const u32* idx, u64 n, T* dst) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[idx[i]];
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_gather_sel(const T* src, const u32* idx, const u64* n, u64 cap, T* out) {
+    const u64 m = *n < cap ? *n : cap;
+    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < m; j += (u64)gridDim.x * 256) out[j] = src[idx[j]];
+}
 
 // "error" classification: HTTP/HTTP2 >= 500; POSTGRES/REDIS/MYSQL == 2 (ebpf/c/postgres.c:91,
 // redis.c:10, mysql.c:36).

@@ -17,7 +17,7 @@
 //
 // Node selection is K7 with a key pass of its own (k10_keys: the node's score or a value of its sg_node_trend) over a count the key
 // pass copies to word C_N_EDGES of a small counter block; K7's passes then select indices only (their row copies are off), and
-// k10_gather_rows copies the selected node rows.  No K7 or K8 kernel changes.
+// k_gather_sel<sg_node_out> (sg_kernels.h) copies the selected node rows.  No K7 or K8 kernel changes.
 #pragma once
 
 struct NodeTrendArgs {
@@ -83,12 +83,6 @@ struct K10Nodes {
 __global__ __launch_bounds__(K8_THREADS) void k10_count(NodeTrendArgs na) { k8_count_t<K10Nodes, false>(na.t, na, VanArgs{}); }
 __global__ __launch_bounds__(K8_THREADS) void k10_write(NodeTrendArgs na) { k8_write_t<K10Nodes, false>(na.t, na, VanArgs{}); }
 
-// sg_window_node_trend with an index: the asked-for rows gathered on the device
-__global__ __launch_bounds__(256) void k10_gather(const sg_node_trend* src, const u32* idx, u64 n, sg_node_trend* dst) {
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
-}
-
 // ---- node selection ---------------------------------------------------------------------------------------------------------
 // k7_keys over node rows: the key of the node's score (byte 132 of a 136-byte row) or of a value of its sg_node_trend (SG_NSEL_*:
 // word by - 1 of 8), or for SG_NSEL_NEW one key for every node with in_seen == 0, out_seen == 0 and a request on either side.
@@ -123,10 +117,4 @@ __global__ __launch_bounds__(K7_THREADS) void k10_keys(SelArgs a, const sg_node_
     }
     __syncthreads();
     a.hist[(size_t)blockIdx.x * 256 + t] = h[t];
-}
-
-// the selected node rows: out[j] = nodes[idx[j]] for j < min(*n, cap)
-__global__ __launch_bounds__(256) void k10_gather_rows(const sg_node_out* nodes, const u32* idx, const u64* n, u64 cap, sg_node_out* out) {
-    const u64 m = *n < cap ? *n : cap;
-    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < m; j += (u64)gridDim.x * 256) out[j] = nodes[idx[j]];
 }

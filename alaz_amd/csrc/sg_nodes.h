@@ -80,6 +80,8 @@ __device__ __forceinline__ bool k9_in_used(const K9Used& u, u32 v) { return v < 
 __device__ __forceinline__ bool k9_range_used(const K9Used& u, u32 n0, u32 n1) {   // [n0, n1) meets one of them
     return (n0 < u.a1) || (n0 < u.b1 && n1 > u.b0) || (n0 < u.c1 && n1 > u.c0);
 }
+// the window's node rows: its node count, at most the capacity (K11 - K13 walk the rows K9 wrote)
+__device__ __forceinline__ u64 sg_nodes_of(const u64* count, u32 ncap) { const u64 N = *count; return N < ncap ? N : (u64)ncap; }
 __device__ __forceinline__ u64 k9_rows_of(const NodesArgs& a) { const u64 E = a.ctr[C_N_EDGES]; return E < a.max_edges ? E : a.max_edges; }
 
 // what a side needs of a row

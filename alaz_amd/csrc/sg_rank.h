@@ -15,7 +15,7 @@
 //               partials of the edge pass before it.  Then, unless LAST, m, t = m / W and base = R + m - t * W for the next
 //               iteration; LAST: the window's sg_node_rank row.
 //   k11_keys    K7's key pass over the rank rows: min(rank >> 24, 2^32 - 1) where share >= min_share; then K7's passes and
-//               k10_gather_rows / k11_gather_sel as the node selection (k11_gather: sg_window_rank with an index).
+//               k_gather_sel (sg_kernels.h) as the node selection (k_gather: sg_window_rank with an index).
 #pragma once
 
 #define K11_THREADS 256           // k11_prep, k11_node
@@ -42,7 +42,6 @@ struct RankArgs {
 };
 
 __device__ __forceinline__ u32 k11_q16(float s) { return s > 0.0f ? (s >= 1.0f ? 65536u : (u32)(s * 65536.0f)) : 0u; }
-__device__ __forceinline__ u64 k11_nodes_of(const RankArgs& a) { const u64 N = *a.count; return N < a.nd.ncap ? N : (u64)a.nd.ncap; }
 __device__ __forceinline__ u64 k11_seed_of(const RankArgs& a, float score) {
     if (a.seed == SG_RANK_SEED_UNIFORM) return 1ull;
     return score >= a.seed_min ? (u64)k11_q16(score) : 0ull;
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(K11_THREADS) void k11_prep(RankArgs a) {
         if (s == SG_NONE || d == SG_NONE) { s = 0; d = 0; w = 0; }    // (a ref beyond the id spaces has no node row: the row carries nothing)
         a.src[j] = s; a.dst[j] = d; a.w[j] = w;
     }
-    const u64 N = k11_nodes_of(a);
+    const u64 N = sg_nodes_of(a.count, a.nd.ncap);
     u64 sum = 0;
     for (u64 v = g0; v < N; v += stride) sum += k11_seed_of(a, a.nodes[v].score);
     if (sum) atomicAdd(&ssum, sum);
@@ -114,7 +113,7 @@ template <bool FIRST, bool LAST>
 __global__ __launch_bounds__(K11_THREADS) void k11_node(RankArgs a) {
     __shared__ u64 sA;
     const u32 t = threadIdx.x;
-    const u64 N = k11_nodes_of(a);
+    const u64 N = sg_nodes_of(a.count, a.nd.ncap);
     u64 A = 0;
     if (FIRST) {
         if (t == 0) sA = 0;
@@ -152,17 +151,6 @@ __global__ __launch_bounds__(K11_THREADS) void k11_node(RankArgs a) {
             a.base[v] = R + (m - tt * W);
         }
     }
-}
-
-// sg_window_rank with an index: the asked-for rows gathered on the device
-__global__ __launch_bounds__(256) void k11_gather(const sg_node_rank* src, const u32* idx, u64 n, sg_node_rank* dst) {
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
-}
-// the selected rank rows: out[j] = src[idx[j]] for j < min(*n, cap)
-__global__ __launch_bounds__(256) void k11_gather_sel(const sg_node_rank* src, const u32* idx, const u64* n, u64 cap, sg_node_rank* out) {
-    const u64 m = *n < cap ? *n : cap;
-    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < m; j += (u64)gridDim.x * 256) out[j] = src[idx[j]];
 }
 
 // k7_keys over rank rows (k10_keys' shape): key = min(rank >> 24, 2^32 - 1) where share >= min_share, else 0.  Workgroup 0 copies

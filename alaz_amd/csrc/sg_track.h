@@ -59,7 +59,6 @@ struct TrkArgs {
     u64* ended_count;
 };
 
-__device__ __forceinline__ u64 k13_nodes_of(const TrkArgs& a) { const u64 N = *a.ncount; return N < a.nd.ncap ? N : (u64)a.nd.ncap; }
 __device__ __forceinline__ u32 k13_incidents_of(const TrkArgs& a) { const u64 I = *a.icount; return (u32)(I < a.nd.ncap ? I : (u64)a.nd.ncap); }
 __device__ __forceinline__ u32 k13_entries_of(const TrkArgs& a) { const u32 n = a.sold->n; return n < a.max_tracks ? n : a.max_tracks; }
 // the anchor key of a node row's ref, K13_NONE for an OBIP ref (and a ref beyond the id spaces)
@@ -70,7 +69,6 @@ __device__ __forceinline__ u32 k13_find(const sg_track_entry* t, u32 n, u32 id) 
     while (lo < hi) { const u32 m = (lo + hi) >> 1; if (t[m].track < id) lo = m + 1; else hi = m; }
     return (lo < n && t[lo].track == id) ? lo : K13_NONE;
 }
-__device__ __forceinline__ u32 wave_min_u32(u32 v) SG_WAVE_REDUCE(u32, dpp32, rdlane32, SG_OP_MIN)
 // p may point to LDS or to device memory; SG_NO_TRACK is "nothing"
 __device__ __forceinline__ void k13_min(u32* p, u32 x) { if (x != SG_NO_TRACK) atomicMin(p, x); }
 
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(K13_THREADS) void k13_look(TrkArgs a) {
     for (u32 s = t; s < K12_SLOTS; s += K13_THREADS) { key[s] = K12_EMPTY; mn[s] = SG_NO_TRACK; jn[s] = 0; }
     __syncthreads();
     const u32 n = k13_entries_of(a);
-    const u64 N = k13_nodes_of(a), stride = (u64)gridDim.x * K13_THREADS;
+    const u64 N = sg_nodes_of(a.ncount, a.nd.ncap), stride = (u64)gridDim.x * K13_THREADS;
     for (u64 vb = (u64)blockIdx.x * K13_THREADS; vb < N; vb += stride) {   // (uniform per wave: the wave reductions see 64 lanes)
         const u64 v = vb + t;
         u32 i = SG_NO_INCIDENT, tv = SG_NO_TRACK;
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(K13_THREADS) void k13_fold(TrkArgs a) {
     const u32 t = threadIdx.x;
     for (u32 s = t; s < K12_SLOTS; s += K13_THREADS) { key[s] = K12_EMPTY; kp[s] = 0; mv[s] = 0; }
     __syncthreads();
-    const u64 N = k13_nodes_of(a), stride = (u64)gridDim.x * K13_THREADS;
+    const u64 N = sg_nodes_of(a.ncount, a.nd.ncap), stride = (u64)gridDim.x * K13_THREADS;
     for (u64 vb = (u64)blockIdx.x * K13_THREADS; vb < N; vb += stride) {   // (uniform per wave)
         const u64 v = vb + t;
         u32 i = SG_NO_INCIDENT, k = 0, x = 0;
@@ -290,7 +288,7 @@ __global__ __launch_bounds__(K13_THREADS) void k13_write(TrkArgs a) {
 }
 
 __global__ __launch_bounds__(K13_THREADS) void k13_members(TrkArgs a) {
-    const u64 N = k13_nodes_of(a);
+    const u64 N = sg_nodes_of(a.ncount, a.nd.ncap);
     for (u64 v = (u64)blockIdx.x * K13_THREADS + threadIdx.x; v < N; v += (u64)gridDim.x * K13_THREADS) {
         const u32 i = a.node_inc[v];
         if (i == SG_NO_INCIDENT) continue;

@@ -323,9 +323,3 @@ __global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan(TrendArgs a, u32 nwg)
 __global__ __launch_bounds__(K8_SCAN_THREADS) void k8_scan_v(TrendArgs a, u32 nwg, VanArgs v) { k8_scan_t<true>(a, nwg, v); }
 __global__ __launch_bounds__(K8_THREADS) void k8_write(TrendArgs a) { k8_write_t<K8Edges, false>(a, a, VanArgs{}); }
 __global__ __launch_bounds__(K8_THREADS) void k8_write_v(TrendArgs a, VanArgs v) { k8_write_t<K8Edges, true>(a, a, v); }
-
-// sg_window_trend with an index: the asked-for rows gathered on the device, so that only they cross PCIe
-__global__ __launch_bounds__(256) void k8_gather(const sg_edge_trend* src, const u32* idx, u64 n, sg_edge_trend* dst) {
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
-}
