@@ -1094,14 +1094,16 @@ int do_read(sg_engine* e, sg_edge_out* out, size_t cap, size_t* n, const sg_edge
 }
 
 // ---- K7, the selection (engine lock held) ---------------------------------------------------------------------------------------
-// the scratch of s.plan carved from b (plan_select's layout), the host count, the event and k7_sort's LDS limit
+// a piece of a stage's block: the plan's offset from the block's base (sg_plan.hpp Block)
+template <class T> T* at(char* mem, u64 off) { return (T*)(mem + off); }
+// the scratch of s.plan at b (plan_select's layout), the host count, the event and k7_sort's LDS limit
 int sel_init(sg_engine* e, sg_engine::SelScratch& s, char* b) {
     const sgplan::SelPlan& p = s.plan;
-    s.pairs = (u64*)b; b += p.pair_bytes;                                     // (the u64 arrays first: every offset stays 8-aligned)
-    s.n = (u64*)b; s.state = (u32*)(b + 8); b += p.state_bytes;
-    s.blk = (u32*)b; b += p.blk_bytes;
-    s.hist = (u32*)b; b += p.hist_bytes;
-    s.keys = (u32*)b;
+    s.pairs = at<u64>(b, p.pair_off);
+    s.n = at<u64>(b, p.n_off); s.state = at<u32>(b, p.state_off);
+    s.blk = at<u32>(b, p.blk_off);
+    s.hist = at<u32>(b, p.hist_off);
+    s.keys = at<u32>(b, p.key_off);
     HIP_TRY(e, hipHostMalloc((void**)&s.h_n, sizeof(u64)));
     HIP_TRY(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
     HIP_TRY(e, lds_limit(sgplan::select_sort_lds(SG_SELECT_MAX_K), k7_sort));
@@ -1169,19 +1171,14 @@ int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_scor
 int nsel_reserve(sg_engine* e) {
     sg_engine::NSel& s = e->nsel;
     if (s.keys) return SG_OK;
-    const u64 NC = std::max<u32>(e->plan.ncap, 1);
-    s.plan = sgplan::plan_select(NC, true);
-    const sgplan::SelPlan& p = s.plan;
-    const u64 ctr_bytes = sgplan::trend_align(sizeof(e->h_ctr)), idx_bytes = sgplan::trend_align(NC * 4);
-    const u64 stage_bytes = sgplan::trend_align(NC * sizeof(sg_node_out));
-    const u64 total = sgplan::trend_align(p.scratch_bytes) + ctr_bytes + idx_bytes + stage_bytes;
-    HIP_TRY(e, hipMalloc((void**)&s.mem, total));
-    HIP_TRY(e, hipMemset(s.mem, 0, total));
-    char* b = s.mem;
-    s.stage = (sg_node_out*)b; b += stage_bytes;                              // (256-aligned pieces first, then plan_select's layout)
-    s.ctr = (u64*)b; b += ctr_bytes;
-    s.idx = (u32*)b; b += idx_bytes;
-    return sel_init(e, s, b);
+    const sgplan::NodeSelPlan P = sgplan::plan_node_select(e->plan.ncap, sizeof(e->h_ctr));
+    s.plan = P.sel;
+    HIP_TRY(e, hipMalloc((void**)&s.mem, P.total_bytes));
+    HIP_TRY(e, hipMemset(s.mem, 0, P.total_bytes));
+    s.stage = at<sg_node_out>(s.mem, P.stage_off);
+    s.ctr = at<u64>(s.mem, P.ctr_off);
+    s.idx = at<u32>(s.mem, P.idx_off);
+    return sel_init(e, s, s.mem + P.sel_off);
 }
 // enqueue a selection over the node rows of slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
 // be NULL), the count to d_n; behind that window's rollup (event) and the previous node selection.  keys(a, wgs) launches the key
@@ -1266,28 +1263,26 @@ int alloc_block(sg_engine* e, char** mem, u64 bytes, const char* call, F release
     HIP_TRY(e, hipMemset(*mem, 0, bytes));
     return SG_OK;
 }
-// switch baseline t on (t freed): parameters r, plan P, one block carved into the two SoA buffers, the control block, the scratch
-// and every slot's trend rows — an empty baseline (B = 0 for both parities), zero statistics and rows
+// switch baseline t on (t freed): parameters r, plan P, one block (the plan's layout: the two SoA buffers, the control block, the
+// scratch and every slot's trend rows) — an empty baseline (B = 0 for both parities), zero statistics and rows
 template <class Row, class F>
 int baseline_on(sg_engine* e, sg_engine::Baseline<Row>& t, const sg_trend_params& r, const sgplan::TrendPlan& P, const char* call, F release) {
     t.p = r;
     t.plan = P;
     HIP_TRY(e, hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
     if (const int rc = alloc_block(e, &t.mem, P.total_bytes, call, release)) return rc;
-    const u64 C = P.entries;
-    char* b = t.mem;
-    for (int k = 0; k < 2; k++) {                                     // (the u64 / fp64 arrays first: every offset stays 8-aligned)
+    for (int k = 0; k < 2; k++) {
         TrendSoA& x = t.buf[k];
-        char* q = b;
-        x.from_key = (u64*)q; q += C * 8; x.to_key = (u64*)q; q += C * 8;
-        x.lat_mean = (double*)q; q += C * 8; x.lat_dev = (double*)q; q += C * 8; x.err_mean = (double*)q; q += C * 8; x.err_dev = (double*)q; q += C * 8;
-        x.n = (u32*)q; q += C * 4; x.last = (u32*)q;
-        b += P.soa_bytes;
+        char* q = t.mem + P.soa_off[k];
+        x.from_key = at<u64>(q, P.soa_from_key); x.to_key = at<u64>(q, P.soa_to_key);
+        x.lat_mean = at<double>(q, P.soa_stat[0]); x.lat_dev = at<double>(q, P.soa_stat[1]);
+        x.err_mean = at<double>(q, P.soa_stat[2]); x.err_dev = at<double>(q, P.soa_stat[3]);
+        x.n = at<u32>(q, P.soa_n); x.last = at<u32>(q, P.soa_last);
     }
-    t.ctl = (u64*)b; b += P.ctl_bytes;
-    t.blk = (u32*)b; b += P.blk_bytes;
-    t.th = (K8Thread*)b; b += P.thread_bytes;
-    for (size_t k = 0; k < e->slots.size(); k++) { t.rows.push_back((Row*)b); b += P.rows_bytes; }
+    t.ctl = at<u64>(t.mem, P.ctl_off);
+    t.blk = at<u32>(t.mem, P.blk_off);
+    t.th = at<K8Thread>(t.mem, P.thread_off);
+    for (size_t k = 0; k < e->slots.size(); k++) t.rows.push_back(at<Row>(t.mem, P.slot.off + k * P.slot.bytes + P.slot_rows));
     t.on = true;
     return SG_OK;
 }
@@ -2242,10 +2237,12 @@ int sg_set_vanished(sg_handle e, const sg_vanished_params* p) {
     v.plan = sgplan::plan_vanished(e->trend.plan, slots, r);
     const sgplan::VanishedPlan& P = v.plan;
     if (const int rc = alloc_block(e, &v.mem, P.total_bytes, "sg_set_vanished", [e] { free_vanished(e); })) return rc;
-    char* b = v.mem;
-    v.th = (u32*)b; b += P.thread_bytes;
-    v.blk = (u32*)b; b += P.blk_bytes;
-    for (u32 k = 0; k < slots; k++) { v.rows.push_back((sg_edge_vanished*)b); b += P.list_bytes; v.count.push_back((u64*)b); b += P.count_bytes; }
+    v.th = at<u32>(v.mem, P.thread_off);
+    v.blk = at<u32>(v.mem, P.blk_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = v.mem + P.slot.off + k * P.slot.bytes;
+        v.rows.push_back(at<sg_edge_vanished>(s, P.slot_list)); v.count.push_back(at<u64>(s, P.slot_count));
+    }
     v.valid.assign(slots, 0);
     v.on = true;
     return SG_OK;
@@ -2285,13 +2282,15 @@ int sg_set_nodes(sg_handle e, int on) {
     HIP_TRY(e, lds_limit(P.lds_bytes, k9_in_part));
     HIP_TRY(e, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
     if (const int rc = alloc_block(e, &n.mem, P.total_bytes, "sg_set_nodes", [e] { free_nodes(e); })) return rc;   // (zeroed: the out table starts at zero, k9_write keeps it so)
-    char* b = n.mem;                                                  // (the 64-byte tables first: every offset stays 256-aligned anyway)
-    n.tout = (K9Side*)b; b += P.table_bytes;
-    n.tin = (K9Side*)b; b += P.table_bytes;
-    n.part = (K9Side*)b; b += P.part_bytes;
-    n.dst = (u32*)b; b += P.dst_bytes;
-    n.blk = (u32*)b; b += P.blk_bytes;
-    for (u32 k = 0; k < slots; k++) { n.rows.push_back((sg_node_out*)b); b += P.rows_bytes; n.count.push_back((u64*)b); b += P.count_bytes; }
+    n.tout = at<K9Side>(n.mem, P.table_off[0]);
+    n.tin = at<K9Side>(n.mem, P.table_off[1]);
+    n.part = at<K9Side>(n.mem, P.part_off);
+    n.dst = at<u32>(n.mem, P.dst_off);
+    n.blk = at<u32>(n.mem, P.blk_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = n.mem + P.slot.off + k * P.slot.bytes;
+        n.rows.push_back(at<sg_node_out>(s, P.slot_rows)); n.count.push_back(at<u64>(s, P.slot_count));
+    }
     n.valid.assign(slots, 0);
     n.on = true;
     return SG_OK;
@@ -2411,14 +2410,13 @@ int sg_set_rank(sg_handle e, const sg_rank_params* p) {
     HIP_TRY(e, lds_limit(P.lds_bytes, k11_edge<true>, k11_edge<false>));
     HIP_TRY(e, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
     if (const int rc = alloc_block(e, &r.mem, P.total_bytes, "sg_set_rank", [e] { free_rank(e); })) return rc;
-    char* b = r.mem;                                                  // (every piece is 256-aligned)
-    r.W = (u64*)b; b += P.node_bytes; r.R = (u64*)b; b += P.node_bytes; r.base = (u64*)b; b += P.node_bytes; r.t = (u64*)b; b += P.node_bytes;
-    r.part = (u64*)b; b += P.part_bytes;
-    r.seed_sum = (u64*)b; b += P.seed_bytes;
-    r.src = (u32*)b; b += P.row_bytes; r.dst = (u32*)b; b += P.row_bytes; r.w = (u32*)b; b += P.row_bytes;
-    r.stage = (sg_node_rank*)b; b += P.stage_bytes;
-    r.stage_idx = (u32*)b; b += P.stage_idx_bytes;
-    for (u32 k = 0; k < slots; k++) { r.rows.push_back((sg_node_rank*)b); b += P.rows_bytes; }
+    r.W = at<u64>(r.mem, P.node_off[0]); r.R = at<u64>(r.mem, P.node_off[1]); r.base = at<u64>(r.mem, P.node_off[2]); r.t = at<u64>(r.mem, P.node_off[3]);
+    r.part = at<u64>(r.mem, P.part_off);
+    r.seed_sum = at<u64>(r.mem, P.seed_off);
+    r.src = at<u32>(r.mem, P.row_off[0]); r.dst = at<u32>(r.mem, P.row_off[1]); r.w = at<u32>(r.mem, P.row_off[2]);
+    r.stage = at<sg_node_rank>(r.mem, P.stage_off);
+    r.stage_idx = at<u32>(r.mem, P.stage_idx_off);
+    for (u32 k = 0; k < slots; k++) r.rows.push_back(at<sg_node_rank>(r.mem, P.slot.off + k * P.slot.bytes + P.slot_rows));
     r.valid.assign(slots, 0);
     r.on = true;
     return SG_OK;
@@ -2487,15 +2485,15 @@ int sg_set_incidents(sg_handle e, const sg_incident_params* p) {
     const sgplan::IncidentPlan& P = x.plan;
     HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
     if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_incidents", [e] { free_incidents(e); })) return rc;
-    char* b = x.mem;                                                  // (every piece is 256-aligned)
-    x.keys = (K12Keys*)b; b += P.keys_bytes;
-    x.parent = (u32*)b; b += P.key_bytes; x.flag = (u32*)b; b += P.key_bytes; x.lab = (u32*)b; b += P.key_bytes;
-    x.num = (u32*)b; b += P.key_bytes; x.kinc = (u32*)b; b += P.key_bytes;
-    x.blk = (u32*)b; b += P.blk_bytes;
-    x.stage = (u32*)b; b += P.stage_bytes; x.stage_idx = (u32*)b; b += P.stage_bytes;
+    x.keys = at<K12Keys>(x.mem, P.keys_off);
+    x.parent = at<u32>(x.mem, P.key_off[0]); x.flag = at<u32>(x.mem, P.key_off[1]); x.lab = at<u32>(x.mem, P.key_off[2]);
+    x.num = at<u32>(x.mem, P.key_off[3]); x.kinc = at<u32>(x.mem, P.key_off[4]);
+    x.blk = at<u32>(x.mem, P.blk_off);
+    x.stage = at<u32>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
     for (u32 k = 0; k < slots; k++) {
-        x.rows.push_back((sg_incident_out*)b); b += P.rows_bytes; x.count.push_back((u64*)b); b += P.count_bytes;
-        x.node_inc.push_back((u32*)b); b += P.node_inc_bytes;
+        char* s = x.mem + P.slot.off + k * P.slot.bytes;
+        x.rows.push_back(at<sg_incident_out>(s, P.slot_rows)); x.count.push_back(at<u64>(s, P.slot_count));
+        x.node_inc.push_back(at<u32>(s, P.slot_node_inc));
     }
     x.valid.assign(slots, 0);
     x.on = true;
@@ -2549,15 +2547,14 @@ int sg_set_groups(sg_handle e, const sg_group_params* p) {
     HIP_TRY(e, hipEventCreateWithFlags(&x.up_ev, hipEventDisableTiming));
     if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_groups", release)) return rc;
     if (hipHostMalloc((void**)&x.h_up, std::max<size_t>(d.max_known, 1) * sizeof(u32)) != hipSuccess) { release(); e->err = "sg_set_groups: hipHostMalloc"; return SG_ENOMEM; }
-    char* b = x.mem;                                                  // (every piece is 256-aligned)
-    x.keys[0] = b; b += P.keys_bytes; x.keys[1] = b; b += P.keys_bytes;
-    x.idx[0] = (u32*)b; b += P.idx_bytes; x.idx[1] = (u32*)b; b += P.idx_bytes;
-    x.map = (u32*)b; b += P.map_bytes; x.hist = (u32*)b; b += P.hist_bytes; x.chunkcnt = (u32*)b; b += P.chunkcnt_bytes;
-    x.part = (K14Acc*)b; b += P.part_bytes; x.meta = (uint2*)b; b += P.meta_bytes; x.blk = (u32*)b; b += P.blk_bytes;
-    x.stage = (u32*)b; b += P.stage_bytes; x.stage_idx = (u32*)b; b += P.stage_bytes;
+    for (int k = 0; k < 2; k++) { x.keys[k] = x.mem + P.keys_off[k]; x.idx[k] = at<u32>(x.mem, P.idx_off[k]); }
+    x.map = at<u32>(x.mem, P.map_off); x.hist = at<u32>(x.mem, P.hist_off); x.chunkcnt = at<u32>(x.mem, P.chunkcnt_off);
+    x.part = at<K14Acc>(x.mem, P.part_off); x.meta = at<uint2>(x.mem, P.meta_off); x.blk = at<u32>(x.mem, P.blk_off);
+    x.stage = at<u32>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
     for (u32 k = 0; k < slots; k++) {
-        x.rows.push_back((sg_group_edge*)b); b += P.rows_bytes; x.count.push_back((u64*)b); b += P.count_bytes;
-        x.row_group.push_back((u32*)b); b += P.idx_bytes; x.perm.push_back((u32*)b); b += P.idx_bytes;
+        char* s = x.mem + P.slot.off + k * P.slot.bytes;
+        x.rows.push_back(at<sg_group_edge>(s, P.slot_rows)); x.count.push_back(at<u64>(s, P.slot_count));
+        x.row_group.push_back(at<u32>(s, P.slot_row_group)); x.perm.push_back(at<u32>(s, P.slot_perm));
     }
     HIP_TRY(e, hipMemset(x.map, 0xFF, P.map_bytes));                  // nothing grouped
     x.h_map.assign(d.max_known, SG_NO_GROUP);
@@ -2632,17 +2629,16 @@ int sg_set_tracks(sg_handle e, const sg_track_params* p) {
     const sgplan::TrackPlan& P = x.plan;
     HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
     if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_tracks", [e] { free_tracks(e); })) return rc;
-    char* b = x.mem;                                                  // (every piece is 256-aligned)
-    x.mtrack = (u32*)b; b += P.member_bytes; x.mlast = (u32*)b; b += P.member_bytes;
-    for (int k = 0; k < 2; k++) { x.tab[k] = (sg_track_entry*)b; b += P.table_bytes; }
-    for (int k = 0; k < 2; k++) { x.st[k] = (TrkState*)b; b += P.state_bytes; }
-    x.cand = (u32*)b; b += P.inc_bytes; x.kept = (u32*)b; b += P.inc_bytes; x.moved = (u32*)b; b += P.inc_bytes;
-    x.joined = (u32*)b; b += P.inc_bytes; x.pos = (u32*)b; b += P.inc_bytes; x.tv = (u32*)b; b += P.inc_bytes;
-    x.claim = (u64*)b; b += P.claim_bytes;
-    x.blk = (u32*)b; b += P.blk_bytes;
+    x.mtrack = at<u32>(x.mem, P.member_off[0]); x.mlast = at<u32>(x.mem, P.member_off[1]);
+    for (int k = 0; k < 2; k++) { x.tab[k] = at<sg_track_entry>(x.mem, P.table_off[k]); x.st[k] = at<TrkState>(x.mem, P.state_off[k]); }
+    x.cand = at<u32>(x.mem, P.inc_off[0]); x.kept = at<u32>(x.mem, P.inc_off[1]); x.moved = at<u32>(x.mem, P.inc_off[2]);
+    x.joined = at<u32>(x.mem, P.inc_off[3]); x.pos = at<u32>(x.mem, P.inc_off[4]); x.tv = at<u32>(x.mem, P.inc_off[5]);
+    x.claim = at<u64>(x.mem, P.claim_off);
+    x.blk = at<u32>(x.mem, P.blk_off);
     for (u32 k = 0; k < slots; k++) {
-        x.rows.push_back((sg_incident_track*)b); b += P.rows_bytes; x.ended.push_back((sg_track_entry*)b); b += P.ended_bytes;
-        x.ended_count.push_back((u64*)b); b += P.count_bytes;
+        char* s = x.mem + P.slot.off + k * P.slot.bytes;
+        x.rows.push_back(at<sg_incident_track>(s, P.slot_rows)); x.ended.push_back(at<sg_track_entry>(s, P.slot_ended));
+        x.ended_count.push_back(at<u64>(s, P.slot_count));
     }
     // an empty state: no member (SG_NO_TRACK everywhere); the block is zeroed: no entry, next id 0
     hipError_t rc = hipMemset(x.mtrack, 0xFF, P.member_bytes);

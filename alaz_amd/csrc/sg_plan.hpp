@@ -5,6 +5,8 @@
 // cache and its teams, warm-window state, the close's slices / splits / grids), each with the measured reason it has.
 // It also chooses the kernel instantiation of every launch site that has several (Kernels) and lists the instantiations the
 // library holds (k*Keys), which servicegraph.hip expands into its kernel tables.
+// It owns the memory layout of every opt-in stage too: each plan_* cuts its stage's one device block with Block and keeps the
+// offsets beside the sizes, so that servicegraph.hip only adds an offset to the block's base.
 // No HIP in this file: tests/micro/plan_test.cpp drives it on the CPU and tests/test_plan.py compares its plans with the
 // ones the engine made before it existed (tests/golden/plans.json).
 #pragma once
@@ -14,8 +16,10 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <optional>
 #include <string>
+#include <vector>
 
 #include "../../include/servicegraph.h"
 #include "sg_sizes.h"
@@ -443,6 +447,37 @@ inline constexpr auto kK1bStreamKeys = concat(product({4, 8}, {1, 2, 4}, {0, 1},
                                               product({kK1bWarmU}, {1, 2, 4}, {0, 1}, {1, 2}, {0, 1}));
 inline constexpr auto kK4LayerKeys = product({32, 64}, {0, 1}, {0, 1}, {0, 1});          // k4_sage_layer<fi, mfma, proj, threads, split>
 
+// ---- the opt-in stages' device blocks -------------------------------------------------------------------------------------------
+// Every opt-in stage behind K5 gets one device block from its sg_set_* call (K7's scratch: at the first selection).  Block cuts it:
+// take() hands out offsets in call order, each aligned, and records the piece; the plan keeps the offsets, Block's end as its
+// total_bytes and the record as its layout (what the CPU drivers under tests/micro print).  slots() cuts the per-slot region: every
+// window slot holds the same pieces in the same order, piece i of slot k at Slots::off + k * Slots::bytes + *SlotPiece::rel.
+constexpr u64 kTrendAlign = 256;
+inline u64 trend_align(u64 b) { return (b + kTrendAlign - 1) / kTrendAlign * kTrendAlign; }
+struct Piece { const char* name; u64 off, bytes; };
+struct Slots { u64 off = 0, bytes = 0; };
+struct SlotPiece { const char* name; u64 bytes; u64* rel; };
+struct Block {
+    u64 align = kTrendAlign, end = 0;
+    std::vector<Piece> pieces;
+    u64 up(u64 b) const { return (b + align - 1) / align * align; }
+    u64 take(const char* name, u64 bytes) {
+        const u64 off = up(end);
+        pieces.push_back({name, off, bytes});
+        end = off + bytes;
+        return off;
+    }
+    Slots slots(u32 n, std::initializer_list<SlotPiece> ps) {
+        Slots s;
+        for (u32 k = 0; k < std::max<u32>(n, 1); k++) {
+            const u64 first = up(end);
+            for (const SlotPiece& p : ps) { const u64 off = take(p.name, p.bytes); if (!k) *p.rel = off - first; }
+            if (!k) { s.off = first; s.bytes = up(end) - first; }
+        }
+        return s;
+    }
+};
+
 // K7, the selection (sg_sel.h): its scratch and grids.  Allocated at an engine's first selection: an engine that never selects
 // asks for nothing (used = false).  Rows are split into `wgs` contiguous spans of at least 2048 (eight rows per lane of a 256-thread
 // workgroup, two such workgroups per CU at 1 M edges); k7_scan scans one count per thread of one 1024-thread workgroup.
@@ -456,6 +491,9 @@ struct SelPlan {
     u64 state_bytes = 0;          // k7 state words + the selected count (u64)
     u64 scratch_bytes = 0;        // all of the above: what sg_window_select needs
     u64 stage_rows = 0;           // device staging of the host flushes' rows: threshold mode may select every row
+    // the scratch's layout, 8-byte aligned: the u64 arrays first (the state piece: the selected count, then the state words)
+    u64 pair_off = 0, n_off = 0, state_off = 0, blk_off = 0, hist_off = 0, key_off = 0;
+    std::vector<Piece> layout;
 };
 inline SelPlan plan_select(u64 max_edges, bool used) {
     SelPlan s;
@@ -466,9 +504,44 @@ inline SelPlan plan_select(u64 max_edges, bool used) {
     s.blk_bytes = (u64)s.wgs * 4 * 4;
     s.pair_bytes = (u64)SG_SELECT_MAX_K * 8;
     s.state_bytes = kSelStateWords * 4 + 8;
-    s.scratch_bytes = s.key_bytes + s.hist_bytes + s.blk_bytes + s.pair_bytes + s.state_bytes;
     s.stage_rows = max_edges;
+    Block b; b.align = 8;
+    s.pair_off = b.take("pairs", s.pair_bytes);
+    s.n_off = b.take("state", s.state_bytes); s.state_off = s.n_off + 8;
+    s.blk_off = b.take("blk", s.blk_bytes);
+    s.hist_off = b.take("hist", s.hist_bytes);
+    s.key_off = b.take("keys", s.key_bytes);
+    s.scratch_bytes = b.end; s.layout = std::move(b.pieces);
     return s;
+}
+// Node selection (K7 over K9's node rows): the whole block of the first node selection — the host form's row staging, the counter
+// block k10_keys / k11_keys fill (counter_bytes: the engine's, the plan includes no device header), an index array, then K7's
+// scratch over ncap rows
+struct NodeSelPlan {
+    SelPlan sel;
+    u64 stage_bytes = 0;          // [ncap] sg_node_out
+    u64 ctr_bytes = 0;            // the counter block
+    u64 idx_bytes = 0;            // [ncap] u32
+    u64 sel_bytes = 0;            // sel.scratch_bytes
+    u64 stage_off = 0, ctr_off = 0, idx_off = 0, sel_off = 0;
+    u64 total_bytes = 0;          // all of it, each piece 256-byte aligned
+    std::vector<Piece> layout;
+};
+inline NodeSelPlan plan_node_select(u32 ncap, u64 counter_bytes) {
+    NodeSelPlan n;
+    const u64 NC = std::max<u32>(ncap, 1);
+    n.sel = plan_select(NC, true);
+    n.stage_bytes = trend_align(NC * sizeof(sg_node_out));
+    n.ctr_bytes = trend_align(counter_bytes);
+    n.idx_bytes = trend_align(NC * 4);
+    n.sel_bytes = trend_align(n.sel.scratch_bytes);
+    Block b;
+    n.stage_off = b.take("stage", n.stage_bytes);
+    n.ctr_off = b.take("ctr", n.ctr_bytes);
+    n.idx_off = b.take("idx", n.idx_bytes);
+    n.sel_off = b.take("sel", n.sel_bytes);
+    n.total_bytes = b.end; n.layout = std::move(b.pieces);
+    return n;
 }
 // k7_sort's LDS: the selected (key, index) pairs padded to a power of two, 8 bytes each
 inline size_t select_sort_lds(u32 k) { return (size_t)next_pow2(std::max<u32>(k, 1)) * 8; }
@@ -479,7 +552,6 @@ inline size_t select_sort_lds(u32 k) { return (size_t)next_pow2(std::max<u32>(k,
 // (at most 1024 workgroups: k8_scan scans one count per thread of one 1024-thread workgroup; beyond that the spans grow).
 constexpr u32 kTrendThreads = 256, kTrendMaxWgs = 1024, kTrendPerThread = 8, kTrendCtlWords = 8;
 constexpr u64 kTrendMaxEntries = 1ull << 31;              // the per-window counts are u32
-constexpr u64 kTrendAlign = 256;
 // SG_OK and *out = p with every 0 replaced by its default, or SG_EINVAL
 inline int check_trend(const sg_trend_params& p, u64 max_edges, sg_trend_params* out) {
     if (p.struct_size != sizeof(sg_trend_params) || p.reserved != 0 || p.shift > 10 || p.max_entries > kTrendMaxEntries) return SG_EINVAL;
@@ -502,8 +574,13 @@ struct TrendPlan {
     u64 thread_bytes = 0;         // [wgs * 256] per-thread split + counts (16 bytes)
     u64 rows_bytes = 0;           // one window slot's trend rows
     u64 total_bytes = 0;          // two baseline buffers, the scratch and every slot's rows, each 256-byte aligned
+    u64 soa_off[2] = {}, ctl_off = 0, blk_off = 0, thread_off = 0;
+    Slots slot; u64 slot_rows = 0;
+    // inside one baseline buffer, back to back, the 64-bit arrays first (8-byte aligned; the u32 arrays 4): the keys, the four fp64
+    // arrays (lat_mean, lat_dev, err_mean, err_dev), n, last
+    u64 soa_from_key = 0, soa_to_key = 0, soa_stat[4] = {}, soa_n = 0, soa_last = 0;
+    std::vector<Piece> layout, soa_layout;
 };
-inline u64 trend_align(u64 b) { return (b + kTrendAlign - 1) / kTrendAlign * kTrendAlign; }
 // a baseline of max_entries entries merged with at most `samples` samples a window, `row_bytes` of trend rows per window slot
 inline TrendPlan plan_baseline(const sg_trend_params& p, u64 samples, u64 row_bytes, u32 slots) {
     TrendPlan t;
@@ -515,7 +592,20 @@ inline TrendPlan plan_baseline(const sg_trend_params& p, u64 samples, u64 row_by
     t.blk_bytes = trend_align((u64)t.wgs * 4 * 4);
     t.thread_bytes = trend_align((u64)t.wgs * kTrendThreads * 16);
     t.rows_bytes = trend_align(row_bytes);
-    t.total_bytes = 2 * t.soa_bytes + t.ctl_bytes + t.blk_bytes + t.thread_bytes + (u64)std::max<u32>(slots, 1) * t.rows_bytes;
+    Block b;
+    t.soa_off[0] = b.take("soa0", t.soa_bytes); t.soa_off[1] = b.take("soa1", t.soa_bytes);
+    t.ctl_off = b.take("ctl", t.ctl_bytes);
+    t.blk_off = b.take("blk", t.blk_bytes);
+    t.thread_off = b.take("thread", t.thread_bytes);
+    t.slot = b.slots(slots, {{"rows", t.rows_bytes, &t.slot_rows}});
+    t.total_bytes = b.end; t.layout = std::move(b.pieces);
+    Block q; q.align = 4;
+    const u64 C = p.max_entries;
+    t.soa_from_key = q.take("from_key", C * 8); t.soa_to_key = q.take("to_key", C * 8);
+    const char* const stat[4] = {"lat_mean", "lat_dev", "err_mean", "err_dev"};
+    for (int k = 0; k < 4; k++) t.soa_stat[k] = q.take(stat[k], C * 8);
+    t.soa_n = q.take("n", C * 4); t.soa_last = q.take("last", C * 4);
+    t.soa_layout = std::move(q.pieces);
     return t;
 }
 // K8: the window's edge rows, [max_edges] sg_edge_trend per slot
@@ -544,6 +634,9 @@ struct VanishedPlan {
     u64 list_bytes = 0;           // one window slot's list: [max_rows] sg_edge_vanished
     u64 count_bytes = 0;          // one window slot's count (u64)
     u64 total_bytes = 0;          // the scratch and every slot's list and count, each 256-byte aligned
+    u64 thread_off = 0, blk_off = 0;
+    Slots slot; u64 slot_list = 0, slot_count = 0;
+    std::vector<Piece> layout;
 };
 inline VanishedPlan plan_vanished(const TrendPlan& t, u32 slots, const sg_vanished_params& p) {
     VanishedPlan v;
@@ -552,7 +645,11 @@ inline VanishedPlan plan_vanished(const TrendPlan& t, u32 slots, const sg_vanish
     v.blk_bytes = trend_align((u64)t.wgs * 4);
     v.list_bytes = trend_align(std::max<u64>(p.max_rows, 1) * sizeof(sg_edge_vanished));
     v.count_bytes = trend_align(8);
-    v.total_bytes = v.thread_bytes + v.blk_bytes + (u64)std::max<u32>(slots, 1) * (v.list_bytes + v.count_bytes);
+    Block b;
+    v.thread_off = b.take("thread", v.thread_bytes);
+    v.blk_off = b.take("blk", v.blk_bytes);
+    v.slot = b.slots(slots, {{"list", v.list_bytes, &v.slot_list}, {"count", v.count_bytes, &v.slot_count}});
+    v.total_bytes = b.end; v.layout = std::move(b.pieces);
     return v;
 }
 
@@ -576,6 +673,9 @@ struct NodesPlan {
     u64 count_bytes = 0;          // one window slot's node count (u64)
     u64 lds_bytes = 0;            // k9_in_part's dynamic LDS
     u64 total_bytes = 0;          // the scratch and every slot's rows and count, each 256-byte aligned
+    u64 table_off[2] = {}, part_off = 0, dst_off = 0, blk_off = 0;   // (table_off: out, in)
+    Slots slot; u64 slot_rows = 0, slot_count = 0;
+    std::vector<Piece> layout;
 };
 inline NodesPlan plan_nodes(u64 max_edges, u32 ncap, u32 slots) {
     NodesPlan n;
@@ -595,7 +695,13 @@ inline NodesPlan plan_nodes(u64 max_edges, u32 ncap, u32 slots) {
     n.rows_bytes = trend_align(NC * sizeof(sg_node_out));
     n.count_bytes = trend_align(8);
     n.lds_bytes = (u64)kNodesRangeNodes * kNodesSideBytes;
-    n.total_bytes = n.dst_bytes + 2 * n.table_bytes + n.part_bytes + n.blk_bytes + (u64)std::max<u32>(slots, 1) * (n.rows_bytes + n.count_bytes);
+    Block b;
+    n.table_off[0] = b.take("table_out", n.table_bytes); n.table_off[1] = b.take("table_in", n.table_bytes);
+    n.part_off = b.take("part", n.part_bytes);
+    n.dst_off = b.take("dst", n.dst_bytes);
+    n.blk_off = b.take("blk", n.blk_bytes);
+    n.slot = b.slots(slots, {{"rows", n.rows_bytes, &n.slot_rows}, {"count", n.count_bytes, &n.slot_count}});
+    n.total_bytes = b.end; n.layout = std::move(b.pieces);
     return n;
 }
 
@@ -648,6 +754,9 @@ struct RankPlan {
     u64 rows_bytes = 0;           // one window slot's rank rows: [ncap] sg_node_rank
     u64 lds_bytes = 0;            // k11_edge's dynamic LDS
     u64 total_bytes = 0;          // the scratch, the staging and every slot's rows, each 256-byte aligned
+    u64 node_off[4] = {}, part_off = 0, seed_off = 0, row_off[3] = {}, stage_off = 0, stage_idx_off = 0;   // (node_off: W, R, base, t; row_off: src, dst, w)
+    Slots slot; u64 slot_rows = 0;
+    std::vector<Piece> layout;
 };
 inline RankPlan plan_rank(u64 max_edges, u32 ncap, u32 slots) {
     RankPlan r;
@@ -666,8 +775,17 @@ inline RankPlan plan_rank(u64 max_edges, u32 ncap, u32 slots) {
     r.stage_idx_bytes = trend_align(NC * 4);
     r.rows_bytes = trend_align(NC * sizeof(sg_node_rank));
     r.lds_bytes = (u64)kRankRangeNodes * 8;
-    r.total_bytes = 3 * r.row_bytes + 4 * r.node_bytes + r.part_bytes + r.seed_bytes + r.stage_bytes + r.stage_idx_bytes +
-                    (u64)std::max<u32>(slots, 1) * r.rows_bytes;
+    Block b;
+    const char* const node[4] = {"W", "R", "base", "t"};
+    const char* const row[3] = {"src", "dst", "w"};
+    for (int k = 0; k < 4; k++) r.node_off[k] = b.take(node[k], r.node_bytes);
+    r.part_off = b.take("part", r.part_bytes);
+    r.seed_off = b.take("seed", r.seed_bytes);
+    for (int k = 0; k < 3; k++) r.row_off[k] = b.take(row[k], r.row_bytes);
+    r.stage_off = b.take("stage", r.stage_bytes);
+    r.stage_idx_off = b.take("stage_idx", r.stage_idx_bytes);
+    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}});
+    r.total_bytes = b.end; r.layout = std::move(b.pieces);
     return r;
 }
 
@@ -700,6 +818,9 @@ struct IncidentPlan {
     u64 count_bytes = 0;          // one window slot's incident count (u64)
     u64 node_inc_bytes = 0;       // one window slot's incident per node row: [ncap] u32
     u64 total_bytes = 0;          // the scratch, the staging and every slot's buffers, each 256-byte aligned
+    u64 keys_off = 0, key_off[5] = {}, blk_off = 0, stage_off = 0, stage_idx_off = 0;   // (key_off: parent, flag, lab, num, kinc)
+    Slots slot; u64 slot_rows = 0, slot_count = 0, slot_node_inc = 0;
+    std::vector<Piece> layout;
 };
 inline IncidentPlan plan_incidents(u64 max_edges, u32 ncap, u32 slots) {
     IncidentPlan r;
@@ -720,8 +841,15 @@ inline IncidentPlan plan_incidents(u64 max_edges, u32 ncap, u32 slots) {
     r.rows_bytes = trend_align(NC * sizeof(sg_incident_out));
     r.count_bytes = trend_align(8);
     r.node_inc_bytes = trend_align(NC * 4);
-    r.total_bytes = 5 * r.key_bytes + r.keys_bytes + r.blk_bytes + 2 * r.stage_bytes +
-                    (u64)std::max<u32>(slots, 1) * (r.rows_bytes + r.count_bytes + r.node_inc_bytes);
+    Block b;
+    const char* const key[5] = {"parent", "flag", "lab", "num", "kinc"};
+    r.keys_off = b.take("keys", r.keys_bytes);
+    for (int k = 0; k < 5; k++) r.key_off[k] = b.take(key[k], r.key_bytes);
+    r.blk_off = b.take("blk", r.blk_bytes);
+    r.stage_off = b.take("stage", r.stage_bytes); r.stage_idx_off = b.take("stage_idx", r.stage_bytes);
+    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}, {"count", r.count_bytes, &r.slot_count},
+                             {"node_inc", r.node_inc_bytes, &r.slot_node_inc}});
+    r.total_bytes = b.end; r.layout = std::move(b.pieces);
     return r;
 }
 
@@ -763,6 +891,9 @@ struct TrackPlan {
     u64 ended_bytes = 0;          // one window slot's ended list: [ncap] sg_track_entry
     u64 count_bytes = 0;          // one window slot's ended count (u64)
     u64 total_bytes = 0;          // the state, the scratch and every slot's buffers, each 256-byte aligned
+    u64 member_off[2] = {}, table_off[2] = {}, state_off[2] = {}, inc_off[6] = {}, claim_off = 0, blk_off = 0;   // (member_off: track, last; inc_off: cand, kept, moved, joined, pos, tv)
+    Slots slot; u64 slot_rows = 0, slot_ended = 0, slot_count = 0;
+    std::vector<Piece> layout;
 };
 inline TrackPlan plan_tracks(u32 max_known, u32 max_labels, u32 ncap, u32 max_tracks, u32 slots) {
     TrackPlan r;
@@ -785,8 +916,17 @@ inline TrackPlan plan_tracks(u32 max_known, u32 max_labels, u32 ncap, u32 max_tr
     r.rows_bytes = trend_align(NC * sizeof(sg_incident_track));
     r.ended_bytes = trend_align(NC * sizeof(sg_track_entry));
     r.count_bytes = trend_align(8);
-    r.total_bytes = 2 * r.member_bytes + 2 * r.table_bytes + 2 * r.state_bytes + 6 * r.inc_bytes + r.claim_bytes + r.blk_bytes +
-                    (u64)std::max<u32>(slots, 1) * (r.rows_bytes + r.ended_bytes + r.count_bytes);
+    Block b;
+    const char* const inc[6] = {"cand", "kept", "moved", "joined", "pos", "tv"};
+    r.member_off[0] = b.take("mtrack", r.member_bytes); r.member_off[1] = b.take("mlast", r.member_bytes);
+    r.table_off[0] = b.take("table0", r.table_bytes); r.table_off[1] = b.take("table1", r.table_bytes);
+    r.state_off[0] = b.take("state0", r.state_bytes); r.state_off[1] = b.take("state1", r.state_bytes);
+    for (int k = 0; k < 6; k++) r.inc_off[k] = b.take(inc[k], r.inc_bytes);
+    r.claim_off = b.take("claim", r.claim_bytes);
+    r.blk_off = b.take("blk", r.blk_bytes);
+    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}, {"ended", r.ended_bytes, &r.slot_ended},
+                             {"ended_count", r.count_bytes, &r.slot_count}});
+    r.total_bytes = b.end; r.layout = std::move(b.pieces);
     return r;
 }
 
@@ -830,6 +970,10 @@ struct GroupPlan {
     u64 rows_bytes = 0;           // one window slot's group edges: [max_edges] sg_group_edge
     u64 count_bytes = 0;          // one window slot's group edge count (u64)
     u64 total_bytes = 0;          // the scratch, the staging and every slot's buffers, each 256-byte aligned
+    u64 keys_off[2] = {}, idx_off[2] = {}, map_off = 0, hist_off = 0, chunkcnt_off = 0, part_off = 0, meta_off = 0, blk_off = 0,
+        stage_off = 0, stage_idx_off = 0;
+    Slots slot; u64 slot_rows = 0, slot_count = 0, slot_row_group = 0, slot_perm = 0;
+    std::vector<Piece> layout;
 };
 inline GroupPlan plan_groups(u64 max_edges, u32 max_known, u32 ncap, u32 max_groups, u32 slots) {
     GroupPlan r;
@@ -856,8 +1000,19 @@ inline GroupPlan plan_groups(u64 max_edges, u32 max_known, u32 ncap, u32 max_gro
     r.stage_bytes = trend_align((u64)kGrpStage * 4);
     r.rows_bytes = trend_align(ME * kGrpEdgeBytes);
     r.count_bytes = trend_align(8);
-    r.total_bytes = 2 * r.keys_bytes + 2 * r.idx_bytes + r.map_bytes + r.hist_bytes + r.chunkcnt_bytes + r.part_bytes + r.meta_bytes + r.blk_bytes +
-                    2 * r.stage_bytes + (u64)std::max<u32>(slots, 1) * (r.rows_bytes + 2 * r.idx_bytes + r.count_bytes);
+    Block b;
+    r.keys_off[0] = b.take("keys0", r.keys_bytes); r.keys_off[1] = b.take("keys1", r.keys_bytes);
+    r.idx_off[0] = b.take("idx0", r.idx_bytes); r.idx_off[1] = b.take("idx1", r.idx_bytes);
+    r.map_off = b.take("map", r.map_bytes);
+    r.hist_off = b.take("hist", r.hist_bytes);
+    r.chunkcnt_off = b.take("chunkcnt", r.chunkcnt_bytes);
+    r.part_off = b.take("part", r.part_bytes);
+    r.meta_off = b.take("meta", r.meta_bytes);
+    r.blk_off = b.take("blk", r.blk_bytes);
+    r.stage_off = b.take("stage", r.stage_bytes); r.stage_idx_off = b.take("stage_idx", r.stage_bytes);
+    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}, {"count", r.count_bytes, &r.slot_count},
+                             {"row_group", r.idx_bytes, &r.slot_row_group}, {"perm", r.idx_bytes, &r.slot_perm}});
+    r.total_bytes = b.end; r.layout = std::move(b.pieces);
     return r;
 }
 

@@ -6,7 +6,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../alaz_amd/csrc/sg_plan.hpp"
+#include "plan_layout.hpp"
 
 using namespace sgplan;
 
@@ -33,6 +33,8 @@ int main() {
                         (unsigned long long)t.chunkcnt_bytes, (unsigned long long)t.part_bytes, (unsigned long long)t.meta_bytes,
                         (unsigned long long)t.blk_bytes, (unsigned long long)t.stage_bytes, (unsigned long long)t.rows_bytes,
                         (unsigned long long)t.count_bytes, (unsigned long long)t.total_bytes, kGrpTile, kGrpChunk, kGrpMaxWgs);
+            put_layout("layout", t.layout);
+            put_slot(t.slot, {{"rows", t.slot_rows}, {"count", t.slot_count}, {"row_group", t.slot_row_group}, {"perm", t.slot_perm}});
         }
         std::printf("}\n");
     }

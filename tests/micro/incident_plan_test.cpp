@@ -6,7 +6,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../alaz_amd/csrc/sg_plan.hpp"
+#include "plan_layout.hpp"
 
 using namespace sgplan;
 
@@ -31,6 +31,7 @@ int main() {
                         (unsigned long long)t.keys_bytes, (unsigned long long)t.blk_bytes, (unsigned long long)t.stage_bytes,
                         (unsigned long long)t.rows_bytes, (unsigned long long)t.count_bytes, (unsigned long long)t.node_inc_bytes,
                         (unsigned long long)t.total_bytes, kIncThreads, kIncMaxWgs, kIncMaxRowWgs);
+            put_layout("layout", t.layout); put_slot(t.slot, {{"rows", t.slot_rows}, {"count", t.slot_count}, {"node_inc", t.slot_node_inc}});
         }
         std::printf("}\n");
     }

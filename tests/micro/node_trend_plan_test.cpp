@@ -1,12 +1,12 @@
 // CPU driver of the per-node baselines' plan in alaz_amd/csrc/sg_plan.hpp (tests/test_node_trend_host.py).  stdin: one
 // "ncap slots struct_size shift warmup ttl max_entries lat_floor_ns err_floor reserved" per line; stdout: one JSON object per line —
-// check_node_trend's verdict, the parameters it resolved and plan_node_trend of them.
+// check_node_trend's verdict (with the block's and one baseline buffer's layout), the parameters it resolved and plan_node_trend of them.
 #include <cstdio>
 #include <iostream>
 #include <sstream>
 #include <string>
 
-#include "../../alaz_amd/csrc/sg_plan.hpp"
+#include "plan_layout.hpp"
 
 using namespace sgplan;
 
@@ -30,6 +30,7 @@ int main() {
                         (unsigned long long)t.entries, t.wgs, (unsigned long long)t.soa_bytes, (unsigned long long)t.ctl_bytes,
                         (unsigned long long)t.blk_bytes, (unsigned long long)t.thread_bytes, (unsigned long long)t.rows_bytes,
                         (unsigned long long)t.total_bytes, kTrendThreads, kTrendMaxWgs, kTrendPerThread);
+            put_layout("layout", t.layout); put_slot(t.slot, {{"rows", t.slot_rows}}); put_layout("soa_layout", t.soa_layout);
         }
         std::printf("}\n");
     }

@@ -5,7 +5,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../alaz_amd/csrc/sg_plan.hpp"
+#include "plan_layout.hpp"
 
 using namespace sgplan;
 
@@ -20,12 +20,14 @@ int main() {
         std::printf("{\"max_edges\": %llu, \"ncap\": %u, \"slots\": %llu, \"node_size\": %zu, \"out_wgs\": %u, \"ranges\": %u, \"slices\": %u, "
                     "\"node_wgs\": %u, \"node_per\": %u, \"dst_bytes\": %llu, \"table_bytes\": %llu, \"part_bytes\": %llu, \"blk_bytes\": %llu, "
                     "\"rows_bytes\": %llu, \"count_bytes\": %llu, \"lds_bytes\": %llu, \"total_bytes\": %llu, \"threads\": %u, \"chunk\": %u, "
-                    "\"range_nodes\": %u, \"max_slices\": %u, \"max_wgs\": %u, \"side_bytes\": %llu}\n",
+                    "\"range_nodes\": %u, \"max_slices\": %u, \"max_wgs\": %u, \"side_bytes\": %llu",
                     me, n.ncap, slots, sizeof(sg_node_out), n.out_wgs, n.ranges, n.slices, n.node_wgs, n.node_per,
                     (unsigned long long)n.dst_bytes, (unsigned long long)n.table_bytes, (unsigned long long)n.part_bytes,
                     (unsigned long long)n.blk_bytes, (unsigned long long)n.rows_bytes, (unsigned long long)n.count_bytes,
                     (unsigned long long)n.lds_bytes, (unsigned long long)n.total_bytes, kNodesThreads, kNodesChunk, kNodesRangeNodes,
                     kNodesMaxSlices, kNodesMaxWgs, (unsigned long long)kNodesSideBytes);
+        put_layout("layout", n.layout); put_slot(n.slot, {{"rows", n.slot_rows}, {"count", n.slot_count}});
+        std::printf("}\n");
     }
     return 0;
 }

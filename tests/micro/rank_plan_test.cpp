@@ -6,7 +6,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../alaz_amd/csrc/sg_plan.hpp"
+#include "plan_layout.hpp"
 
 using namespace sgplan;
 
@@ -32,6 +32,7 @@ int main() {
                         (unsigned long long)t.node_bytes, (unsigned long long)t.part_bytes, (unsigned long long)t.seed_bytes,
                         (unsigned long long)t.stage_bytes, (unsigned long long)t.stage_idx_bytes, (unsigned long long)t.rows_bytes,
                         (unsigned long long)t.lds_bytes, (unsigned long long)t.total_bytes, kRankRangeNodes, kRankMaxWgs, kRankMaxEdgeWgs, kLdsBytes);
+            put_layout("layout", t.layout); put_slot(t.slot, {{"rows", t.slot_rows}});
         }
         std::printf("}\n");
     }

@@ -6,7 +6,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../alaz_amd/csrc/sg_plan.hpp"
+#include "plan_layout.hpp"
 
 using namespace sgplan;
 
@@ -34,6 +34,7 @@ int main() {
                         (unsigned long long)t.claim_bytes, (unsigned long long)t.blk_bytes, (unsigned long long)t.rows_bytes,
                         (unsigned long long)t.ended_bytes, (unsigned long long)t.count_bytes, (unsigned long long)t.total_bytes, kTrkThreads,
                         kTrkMaxWgs);
+            put_layout("layout", t.layout); put_slot(t.slot, {{"rows", t.slot_rows}, {"ended", t.slot_ended}, {"ended_count", t.slot_count}});
         }
         std::printf("}\n");
     }

@@ -6,7 +6,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../alaz_amd/csrc/sg_plan.hpp"
+#include "plan_layout.hpp"
 
 using namespace sgplan;
 
@@ -34,6 +34,7 @@ int main() {
                         r.silent_windows, r.min_seen, r.max_rows, (unsigned long long)v.rows, (unsigned long long)v.thread_bytes,
                         (unsigned long long)v.blk_bytes, (unsigned long long)v.list_bytes, (unsigned long long)v.count_bytes,
                         (unsigned long long)v.total_bytes, kTrendThreads);
+            put_layout("layout", v.layout); put_slot(v.slot, {{"list", v.slot_list}, {"count", v.slot_count}});
         }
         std::printf("}\n");
     }

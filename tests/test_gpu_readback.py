@@ -213,3 +213,64 @@ def test_a_counted_call_with_no_room_and_with_one_row_too_few(eng, name):
     out = _filled(len(want), dtype)                                   # room for none, with somewhere to write: nothing written
     assert call(g._h, out.ctypes.data, 0, C.byref(n)) == engine.SG_OK and n.value == len(want)
     assert out.tobytes() == _filled(len(want), dtype).tobytes()
+
+
+def test_every_stage_block_keeps_its_layout_across_the_slots():
+    """The stage blocks' layout (sg_plan.hpp) seen through the *_buffer calls: three windows in flight, every stage on, one window
+    run per slot.  Inside a slot the pieces lie the same distance apart in all three slots, the slots lie one constant stride
+    apart, every distance is a multiple of 256 bytes, and every piece has room for what this engine's capacities can put into it
+    before the next piece (or the next slot) begins.  Prints the distances (one "layout ..." line per stage).
+
+    max_labels = max_outbound_ips = 0 is the smallest configuration sg_create accepts (the outbound-IP space keeps one id): 5 node keys."""
+    import torch
+    in_flight, mk, me = 3, 4, 8
+    topo = replay.make_topology(2, 2, seed=7, svcs=1)                  # (only the two pods and their ids are used)
+    g = engine.ServiceGraph(max_known_nodes=mk, max_edges=me, layers=2, max_labels=0, max_outbound_ips=0, max_window_events=1 << 10,
+                            max_batch=1 << 10, windows_in_flight=in_flight)
+    g.set_clock(*CLOCK); g.load_weights(weights.make_weights(2))
+    HostShim().apply(g, topo.k8s_ops()); g.set_label_count(0)
+    g.set_trend(warmup=1); g.set_vanished()
+    g.set_nodes(); g.set_node_trend(warmup=1); g.set_rank(iters=2); g.set_incidents(min_value=-float("inf")); g.set_tracks(quiet_windows=0)
+    g.set_groups(); g.group_assign(np.arange(2), np.zeros(2, dtype=np.uint32))
+    ncap = g.window_buffers()[3]
+    assert ncap == mk + 0 + 1
+    e = np.zeros(5, dtype=replay.EVENT_DTYPE)
+    e["saddr"] = topo.pod_ips[0]; e["daddr"] = topo.pod_ips[1]; e["status"] = 200; e["protocol"] = replay.PROTO_HTTP
+    e["duration_ns"] = 1_000_000 + 37 * np.arange(len(e), dtype=np.uint64)
+    e["write_time_ns"] = np.uint64(2_000_000_000) + np.uint64(100) * np.arange(len(e), dtype=np.uint64)
+    dev = torch.from_numpy(e.view(np.uint8).reshape(-1)).cuda()
+    torch.cuda.synchronize()
+    one = lambda f: (lambda: (f(),))                                  # noqa: E731  (a call that returns one pointer)
+    sz = lambda d: d.itemsize                                         # noqa: E731
+    vanished_rows = 2 * me                                            # max_rows: min(65536, max_entries), max_entries: 2 x max_edges
+    # stage -> (the *_buffer call, the bytes each of its pieces must hold at this engine's capacities, in the call's order)
+    stages = {
+        "trend": (one(g.trend_buffer), [me * sz(engine.TREND_DTYPE)]),
+        "vanished": (g.vanished_buffer, [vanished_rows * sz(engine.VANISHED_DTYPE), 8]),
+        "nodes": (g.nodes_buffer, [ncap * sz(engine.NODE_DTYPE), 8]),
+        "node_trend": (one(g.node_trend_buffer), [ncap * sz(engine.NODE_TREND_DTYPE)]),
+        "rank": (one(g.rank_buffer), [ncap * sz(engine.RANK_DTYPE)]),
+        "incidents": (g.window_incidents_buffer, [ncap * sz(engine.INCIDENT_DTYPE), 8, ncap * 4]),                # rows, count, node_incident
+        "tracks": (g.window_tracks_buffer, [ncap * sz(engine.TRACK_DTYPE), ncap * sz(engine.TRACK_ENTRY_DTYPE), 8]),   # tracks, ended, ended_count
+        "groups": (g.window_groups_buffer, [me * sz(engine.GROUP_EDGE_DTYPE), 8, me * 4, me * 4]),              # edges, count, row_group, perm
+    }
+    seen = {name: [] for name in stages}
+    for _ in range(in_flight):
+        g.ingest_device(dev.data_ptr(), len(e), 0)
+        g.window_run(0)
+        for name, (call, _) in stages.items():
+            seen[name].append(tuple(int(p) for p in call()))
+    torch.cuda.synchronize()
+    for name, (_, need) in stages.items():
+        slots = sorted(seen[name])
+        assert len(set(slots)) == in_flight, name                         # every slot has buffers of its own
+        inner = [[p - s[0] for p in s] for s in slots]
+        strides = [b[0] - a[0] for a, b in zip(slots, slots[1:])]
+        print("layout", name, "inside a slot", inner[0], "slot stride", strides[0])
+        assert inner[0] == inner[1] == inner[2], (name, inner)            # the same distances in all three slots
+        assert strides[0] == strides[1], (name, strides)                  # a constant stride
+        assert all(x % 256 == 0 for x in inner[0] + strides), (name, inner[0], strides)
+        order = sorted(range(len(need)), key=lambda i: inner[0][i])       # (the call's order need not be the block's)
+        for a, b in zip(order, order[1:] + [None]):
+            room = (inner[0][b] if b is not None else strides[0]) - inner[0][a]
+            assert room >= need[a], (name, a, room, need[a])             # (the last piece: up to the next slot, so none lies beyond its slot)

@@ -14,6 +14,7 @@ from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.group_ref import group_ref
 from tests.helpers import CLOCK
 from tests.test_gpu_node_trend import churn  # noqa: F401  (the fixture: events only, no engine)
+from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_GROUP
@@ -246,6 +247,10 @@ def test_plan_sizes(group_plan):
         assert r["total_bytes"] == (2 * r["keys_bytes"] + 2 * r["idx_bytes"] + r["map_bytes"] + r["hist_bytes"] + r["chunkcnt_bytes"] + r["part_bytes"]
                                     + r["meta_bytes"] + r["blk_bytes"] + 2 * r["stage_bytes"]
                                     + slots * (r["rows_bytes"] + 2 * r["idx_bytes"] + r["count_bytes"]))
+        check_layout(r, {"keys0": me * r["key_bytes"], "keys1": me * r["key_bytes"], **{k: 4 * me for k in ("idx0", "idx1", "row_group", "perm")},
+                         "map": 4 * r["max_known"], "hist": 1024 * r["tiles"], "chunkcnt": 4 * r["chunks"], "part": 160 * r["chunks"],
+                         "meta": 8 * r["chunks"], "blk": 2 * 1024 * 4, "stage": 4 * 65536, "stage_idx": 4 * 65536, "rows": 80 * me, "count": 8},
+                     per_slot=("rows", "count", "row_group", "perm"))
     c3, = group_plan([_p(1_250_000, 10_000, 15_000)])
     assert (c3["tiles"], c3["chunks"], c3["cpw"], c3["heads_wgs"]) == (306, 611, 1, 611)
     big, = group_plan([_p(1 << 23, 1 << 20, (1 << 20) + 300)])

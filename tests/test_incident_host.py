@@ -16,6 +16,7 @@ from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.helpers import CLOCK
 from tests.incident_ref import QUANTILES, incident_ref, quantile_threshold, red_rows
 from tests.nodes_ref import nodes_ref
+from tests.plan_layout import check_layout
 from tests.rank_ref import rank_ref
 from tests.test_gpu_node_trend import churn  # noqa: F401  (the fixture: events only, no engine)
 
@@ -287,6 +288,8 @@ def test_plan_sizes(incident_plan):
             assert r[k] % 256 == 0
         assert r["total_bytes"] == (5 * r["key_bytes"] + r["keys_bytes"] + r["blk_bytes"] + 2 * r["stage_bytes"]
                                     + slots * (r["rows_bytes"] + r["count_bytes"] + r["node_inc_bytes"]))
+        check_layout(r, {"keys": 24 * nc, **{k: 4 * nc for k in ("parent", "flag", "lab", "num", "kinc", "stage", "stage_idx", "node_inc")},
+                         "blk": 2 * 1024 * 4, "rows": 72 * nc, "count": 8}, per_slot=("rows", "count", "node_inc"))
         # 52 + 76 x slots B a node key, the head counts, and 256 B of rounding for each of the 9 + 3 x slots pieces: nothing per row
         assert r["total_bytes"] <= (52 + 76 * slots) * nc + 8192 + 256 * (9 + 4 * slots)
     c3, = incident_plan([_p(1_250_000, 15_000)])

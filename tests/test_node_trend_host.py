@@ -14,6 +14,7 @@ from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.node_trend_ref import NodeTrendRef, node_samples, ref_select_nodes, x_err
 from tests.nodes_ref import nodes_ref
 from tests.trend_ref import REF_KNOWN, REF_LABEL, REF_OBIP
+from tests.plan_layout import check_layout, check_soa
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -204,7 +205,7 @@ NCAPS = [1, 2, 255, 1024, 1076, 15_000, 1 << 17, (1 << 20) + 3, 1 << 24, 0x3FFFF
 
 
 def test_plan_sizes_fit_every_window(node_trend_plan):
-    lines = [_p(nc, slots) for nc in NCAPS for slots in (1, 3, 8)] + [_p(nc, 1, maxe=m) for nc in NCAPS for m in (1, 7, 1 << 20)]
+    lines = [_p(nc, slots) for nc in NCAPS for slots in (1, 3, 8)] + [_p(nc, 1, maxe=m) for nc in NCAPS for m in (1, 2, 7, 33, 1 << 20)]
     for r in node_trend_plan(lines):
         assert r["rc"] == 0 and r["node_trend_size"] == 32
         nc, C_ = r["ncap"], r["entries"]
@@ -214,6 +215,8 @@ def test_plan_sizes_fit_every_window(node_trend_plan):
         assert r["rows_bytes"] >= 32 * nc and r["rows_bytes"] % 256 == 0     # every node row of every window a slot can close
         assert r["blk_bytes"] >= 16 * r["wgs"] and r["thread_bytes"] >= 16 * 256 * r["wgs"] and r["ctl_bytes"] >= 64
         assert r["total_bytes"] == 2 * r["soa_bytes"] + r["ctl_bytes"] + r["blk_bytes"] + r["thread_bytes"] + r["slots"] * r["rows_bytes"]
+        check_layout(r, {"soa0": 56 * C_, "soa1": 56 * C_, "ctl": 64, "blk": 16 * r["wgs"], "thread": 16 * 256 * r["wgs"], "rows": 32 * nc}, per_slot=("rows",))
+        check_soa(r)
         if r["wgs"] < 1024:                                           # B + 2N merged elements, about eight per thread
             assert r["wgs"] * 256 * r["per_thread"] >= C_ + 2 * nc
     big = {(r["ncap"], r["slots"]): r for r in node_trend_plan([_p(NCAPS[-1], 3)])}[(NCAPS[-1], 3)]

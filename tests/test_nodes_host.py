@@ -11,6 +11,7 @@ import pytest
 from alaz_amd import engine
 from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.nodes_ref import NO_ROW, key_score, nodes_loop, nodes_ref, score_key, score_q32
+from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -142,6 +143,8 @@ def test_plan_fits_every_window(nodes_plan):
         for k in ("dst_bytes", "table_bytes", "part_bytes", "blk_bytes", "rows_bytes", "count_bytes"):
             assert r[k] % 256 == 0
         assert r["total_bytes"] == r["dst_bytes"] + 2 * r["table_bytes"] + r["part_bytes"] + r["blk_bytes"] + r["slots"] * (r["rows_bytes"] + r["count_bytes"])
+        check_layout(r, {"dst": 4 * me, "table_out": 64 * nc, "table_in": 64 * nc, "rows": 136 * nc, "blk": 2 * r["max_wgs"] * 4, "count": 8,
+                         "part": r["ranges"] * r["slices"] * r["range_nodes"] * 64}, per_slot=("rows", "count"))
 
 
 def test_plan_of_config3(nodes_plan):

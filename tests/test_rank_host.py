@@ -14,6 +14,7 @@ from alaz_amd import engine
 from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.nodes_ref import nodes_ref
 from tests.rank_ref import M, q16, rank_keys, rank_ref, ref_select_rank
+from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FE, CART, PAY, DB, CAT, DB2 = range(1, 7)                            # KNOWN refs (type 0): the ref is the id
@@ -238,6 +239,9 @@ def test_plan_sizes(rank_plan):
             assert r[k] % 256 == 0
         assert r["total_bytes"] == (3 * r["row_bytes"] + 4 * r["node_bytes"] + r["part_bytes"] + r["seed_bytes"] + r["stage_bytes"]
                                     + r["stage_idx_bytes"] + slots * r["rows_bytes"])
+        check_layout(r, {**{k: 4 * me for k in ("src", "dst", "w")}, **{k: 8 * nc for k in ("W", "R", "base", "t")}, "rows": 16 * nc,
+                         "stage": 16 * nc, "stage_idx": 4 * nc, "seed": 8 * r["max_wgs"], "part": r["ranges"] * r["slices"] * 16384 * 8},
+                     per_slot=("rows",))
         # 12 B a row, 32 + 20 + 16 x slots B a node key, the partials (at most 256 workgroups x 128 KiB, or one slice per range),
         # the seed sums, and 256 B of rounding for each of the 11 + slots pieces
         assert r["total_bytes"] <= 12 * me + (52 + 16 * slots) * nc + max(256, r["ranges"]) * 16384 * 8 + 8192 + 256 * (11 + slots)

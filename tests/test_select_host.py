@@ -10,6 +10,7 @@ import pytest
 
 from alaz_amd import engine, hostlib
 from alaz_amd.engine import make_config
+from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -77,12 +78,25 @@ def test_select_scratch_covers_every_window(sel_plan):
         assert p["state_bytes"] >= 8 * 4 + 8
         assert p["scratch_bytes"] == sum(p[k] for k in ("key_bytes", "hist_bytes", "blk_bytes", "pair_bytes", "state_bytes"))
         assert p["stage_rows"] >= me                             # threshold mode may select every row
+        k7 = {"pairs": 8 * r["max_k"], "state": 8 * 4 + 8, "blk": p["wgs"] * 16, "hist": p["wgs"] * 256 * 4, "keys": 4 * me}
+        check_layout({**p, "layout": r["layout"]}, k7, align=8, total="scratch_bytes", slots=1, tail_align=4)
         # the rows are split into wgs contiguous spans: below the workgroup cap a span is at most rows_per_wg rows
         if me <= r["max_wgs"] * r["rows_per_wg"]:
             assert p["wgs"] * r["rows_per_wg"] >= me
     # BASELINE config 3: 1 M edges in 512 spans of 2048
     c3 = {r["max_edges"]: r["used"] for r in sel_plan([1 << 20])}[1 << 20]
     assert c3["wgs"] == 512
+
+
+def test_node_selection_block(sel_plan):
+    """plan_node_select over max_edges node rows: the row staging, the counter block, the index array, then K7's scratch at its offset"""
+    for r in sel_plan(SIZES):
+        nc, n = r["max_edges"], r["node"]
+        assert n["sel_layout"] == r["layout"] and n["sel_scratch_bytes"] == r["used"]["scratch_bytes"]   # K7's plan over the node rows
+        check_layout(n, {"stage": nc * 136, "ctr": n["ctr_in"], "idx": nc * 4, "sel": n["sel_scratch_bytes"]}, slots=1)
+        assert [p[0] for p in n["layout"]] == ["stage", "ctr", "idx", "sel"] and n["layout"][3][1] == n["sel_off"]
+        by = {p[0]: p[2] for p in n["layout"]}
+        assert n["total_bytes"] == sum(by.values()) and by["sel"] - n["sel_scratch_bytes"] < 256      # what the engine allocated before the plan had it
 
 
 def test_top_k_sort_fits_a_workgroups_lds(sel_plan):

@@ -17,6 +17,7 @@ from tests.incident_ref import incident_ref, quantile_threshold
 from tests.nodes_ref import nodes_ref
 from tests.test_gpu_node_trend import churn  # noqa: F401  (the fixture: events only, no engine)
 from tests.track_ref import TrackRef, is_anchor
+from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_TRACK
@@ -379,6 +380,9 @@ def test_plan_sizes(track_plan):
             assert r[k] % 256 == 0
         assert r["total_bytes"] == (2 * r["member_bytes"] + 2 * r["table_bytes"] + 2 * r["state_bytes"] + 6 * r["inc_bytes"] + r["claim_bytes"]
                                     + r["blk_bytes"] + slots * (r["rows_bytes"] + r["ended_bytes"] + r["count_bytes"]))
+        check_layout(r, {"mtrack": 4 * r["anchors"], "mlast": 4 * r["anchors"], "table0": 40 * mt, "table1": 40 * mt, "state0": 24, "state1": 24,
+                         **{k: 4 * nc for k in ("cand", "kept", "moved", "joined", "pos", "tv")}, "claim": 8 * mt, "blk": 7 * 1024 * 4,
+                         "rows": 32 * nc, "ended": 40 * nc, "ended_count": 8}, per_slot=("rows", "ended", "ended_count"))
         # 8 B an anchor, 88 B a table position, (24 + 72 x slots) B a node key, the counts, 256 B of rounding a piece
         assert r["total_bytes"] <= 8 * r["anchors"] + 88 * mt + (24 + 72 * slots) * nc + 7 * 4096 + 256 * (14 + 3 * slots)
     c3, = track_plan([_p(12_000, 1000, 15_000)])

@@ -12,6 +12,7 @@ import pytest
 from alaz_amd import engine
 from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.trend_ref import REF_KNOWN, REF_LABEL, REF_OBIP, TrendRef, ref_keys, row_keys, strictly_ascending
+from tests.plan_layout import check_layout, check_soa
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -164,7 +165,7 @@ SIZES = [1, 2, 255, 2047, 2048, 4096, 1 << 15, 1 << 18, (1 << 20) - 1, 1 << 20, 
 
 
 def test_plan_sizes_fit_every_window(trend_plan):
-    lines = [_p(me, slots) for me in SIZES for slots in (1, 2, 8)] + [_p(me, 1, maxe=m) for me in SIZES for m in (1, 7, 1 << 20)]
+    lines = [_p(me, slots) for me in SIZES for slots in (1, 2, 8)] + [_p(me, 1, maxe=m) for me in SIZES for m in (1, 2, 7, 33, 1 << 20)]
     for r in trend_plan(lines):
         assert r["rc"] == 0 and r["params_size"] == 40 and r["edge_trend_size"] == 16 and r["entry_size"] == 56
         me, C_ = r["max_edges"], r["entries"]
@@ -174,6 +175,8 @@ def test_plan_sizes_fit_every_window(trend_plan):
         assert r["rows_bytes"] >= 16 * me                              # every row of every window a slot can close
         assert r["blk_bytes"] >= 16 * r["wgs"] and r["thread_bytes"] >= 16 * 256 * r["wgs"] and r["ctl_bytes"] >= 64
         assert r["total_bytes"] == 2 * r["soa_bytes"] + r["ctl_bytes"] + r["blk_bytes"] + r["thread_bytes"] + r["slots"] * r["rows_bytes"]
+        check_layout(r, {"soa0": 56 * C_, "soa1": 56 * C_, "ctl": 64, "blk": 16 * r["wgs"], "thread": 16 * 256 * r["wgs"], "rows": 16 * me}, per_slot=("rows",))
+        check_soa(r)
         # the merge of B <= max_entries entries and E <= max_edges rows in spans of about eight per thread, below the workgroup cap
         if r["wgs"] < 1024:
             assert r["wgs"] * 256 * r["per_thread"] >= C_ + me

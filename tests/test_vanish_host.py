@@ -15,6 +15,7 @@ from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.select_by_ref import ref_select_by
 from tests.trend_ref import REF_KNOWN, TrendRef
 from tests.vanish_ref import NO_ROW, VanishRef
+from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -159,3 +160,4 @@ def test_plan_memory_for_every_slot(vanish_plan):
         assert r["list_bytes"] >= 64 * r["max_rows"] and r["list_bytes"] % 256 == 0 and r["count_bytes"] >= 8
         assert r["thread_bytes"] >= 4 * r["threads"] * r["wgs"] and r["blk_bytes"] >= 4 * r["wgs"]
         assert r["total_bytes"] == r["thread_bytes"] + r["blk_bytes"] + r["slots"] * (r["list_bytes"] + r["count_bytes"])
+        check_layout(r, {"thread": 4 * r["threads"] * r["wgs"], "blk": 4 * r["wgs"], "list": 64 * r["max_rows"], "count": 8}, per_slot=("list", "count"))
