@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import numpy as np
@@ -29,31 +30,6 @@ SELECT_MAX_K = 16384      # SG_SELECT_MAX_K: the largest k of a top-k selection
 F_IN, F_HID, F_EDGE = 32, 64, 8
 STAT_SUM_WORDS, STAT_MAX_WORDS = 12, 2
 REF_KNOWN, REF_LABEL, REF_OBIP = 0, 1, 2
-
-#: every symbol include/servicegraph.h declares (checked by tests/test_abi.py)
-EXPORTS = [
-    "sg_abi_version", "sg_weights_count", "sg_hash32", "sg_last_error", "sg_create", "sg_destroy",
-    "sg_upsert_pod", "sg_delete_pod", "sg_upsert_service", "sg_delete_service", "sg_set_clock",
-    "sg_set_label_count", "sg_load_weights", "sg_ingest", "sg_ingest_device", "sg_flush_window", "sg_flush_window_view", "sg_flush_begin", "sg_flush_end", "sg_flush_end_view",
-    "sg_window_run", "sg_window_rows_buffer", "sg_window_close", "sg_window_obip_list",
-    "sg_window_close_sharded", "sg_bind_buffers", "sg_window_features", "sg_window_layer", "sg_window_score", "sg_window_score_reset",
-    "sg_window_read", "sg_window_reset", "sg_window_buffers", "sg_window_feat_buffer",
-    "sg_halo_build", "sg_halo_pack", "sg_halo_unpack", "sg_window_close_gathered", "sg_halo_build_padded",
-    "sg_halo_pack_padded", "sg_halo_unpack_padded", "sg_window_outbound_ips", "sg_stats_get",
-    "sg_timing_enable", "sg_timing_reset", "sg_timing_get", "sg_timing_samples", "sg_timing_stride", "sg_latency_probe", "sg_set_warm", "sg_debug_stamps", "sg_route", "sg_window_hist", "sg_geometry_get", "sg_prepare_fold_get",
-    "sg_clock_probe", "sg_comm_probe", "sg_window_halo_counts", "sg_comm_unique_id", "sg_comm_create", "sg_comm_destroy", "sg_window_run_sharded", "sg_host_register", "sg_host_unregister", "sg_ingest_pinned", "sg_ingest_bulk",
-    "sg_flush_window_top", "sg_flush_end_top", "sg_window_select",
-    "sg_set_trend", "sg_window_trend", "sg_window_trend_buffer", "sg_trend_entries", "sg_trend_stats_get",
-    "sg_set_nodes", "sg_window_nodes", "sg_window_nodes_buffer",
-    "sg_set_vanished", "sg_window_vanished", "sg_window_vanished_buffer",
-    "sg_flush_window_top_by", "sg_flush_end_top_by", "sg_window_select_by",
-    "sg_set_node_trend", "sg_window_node_trend", "sg_window_node_trend_buffer", "sg_node_trend_entries", "sg_node_trend_stats_get",
-    "sg_window_nodes_top", "sg_window_nodes_select",
-    "sg_set_rank", "sg_window_rank", "sg_window_rank_buffer", "sg_window_rank_top", "sg_window_rank_select",
-    "sg_set_incidents", "sg_window_incidents", "sg_window_node_incident", "sg_window_incidents_buffer",
-    "sg_set_tracks", "sg_window_incident_tracks", "sg_window_tracks_ended", "sg_window_tracks_buffer", "sg_track_entries", "sg_track_stats_get",
-    "sg_set_groups", "sg_group_assign", "sg_window_groups", "sg_window_row_group", "sg_window_group_perm", "sg_window_groups_buffer",
-]
 
 #: sg_edge_trend (16 bytes) and sg_trend_entry (56 bytes) of include/servicegraph.h
 TREND_DTYPE = np.dtype([("lat_dev", "<f4"), ("err_dev", "<f4"), ("base_mean_us", "<f4"), ("windows_seen", "<u4")])
@@ -78,6 +54,8 @@ INCIDENT_DTYPE = np.dtype([(f, "<u8") for f in ("count", "err", "sum_ns", "score
                           + [("value_max", "<f4"), ("reserved", "<u4")])
 #: SG_NO_INCIDENT: a node row in no incident; culprit_node with the ranking off
 NO_INCIDENT = 0xFFFFFFFF
+#: sg_incident_params defaults
+INCIDENT_DEFAULTS = dict(by="score", min_value=0.0)
 #: sg_incident_track (32 bytes) of include/servicegraph.h: the track of one incident of a window (K13)
 TRACK_DTYPE = np.dtype([(f, "<u4") for f in ("track", "parent", "first_window", "windows", "kept_nodes", "moved_nodes", "joined_nodes", "flags")])
 #: sg_track_entry (40 bytes) of include/servicegraph.h: one entry of the track table, and of a window's ended list
@@ -86,6 +64,8 @@ TRACK_ENTRY_DTYPE = np.dtype([(f, "<u4") for f in ("track", "parent", "first_win
 #: SG_NO_TRACK: no track (the parent of a track that continues none), and sg_incident_track.flags' SG_TRACK_* bits
 NO_TRACK = 0xFFFFFFFF
 TRACK_NEW, TRACK_SPLIT, TRACK_MERGED = 1, 2, 4
+#: sg_track_params defaults (max_tracks 0 = never cut)
+TRACK_DEFAULTS = dict(quiet_windows=2, max_tracks=0)
 #: sg_group_edge (80 bytes) of include/servicegraph.h: one edge of a window's service map contracted to workloads (K14)
 GROUP_EDGE_DTYPE = np.dtype([(f, "<u8") for f in ("count", "err_count", "sum_ns", "sumsq_us", "max_ns", "score_q32")]
                             + [(f, "<u4") for f in ("from_ref", "to_ref", "edges", "from_nodes", "first", "alive", "worst_row")]
@@ -93,6 +73,8 @@ GROUP_EDGE_DTYPE = np.dtype([(f, "<u8") for f in ("count", "err_count", "sum_ns"
 #: SG_NO_GROUP: a node in no group; SG_REF_GROUP: the ref type of a group in sg_group_edge.from_ref / to_ref
 NO_GROUP = 0xFFFFFFFF
 REF_GROUP = 3
+#: sg_group_params defaults (max_groups 0 = max_known_nodes)
+GROUP_DEFAULTS = dict(max_groups=0)
 #: sg_edge_vanished (64 bytes) of include/servicegraph.h: one baseline entry that went silent (K8's vanished list)
 VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("lat_mean", "<f8"), ("lat_dev", "<f8"), ("err_mean", "<f8"),
                            ("err_dev", "<f8"), ("n", "<u4"), ("last", "<u4"), ("row", "<u4"), ("reserved", "<u4")])
@@ -180,11 +162,128 @@ class SgTrendStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("windows", "entries", "inserted", "expired", "dropped")]
 
 
+def _signatures() -> dict:
+    """name -> (result type, argument types) of every function include/servicegraph.h declares"""
+    I, H, P, PP = C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)
+    u32, u64, sz, f32 = C.c_uint32, C.c_uint64, C.c_size_t, C.c_float
+    Psz, Pu64, Pf64 = C.POINTER(sz), C.POINTER(u64), C.POINTER(C.c_double)
+    return {
+        "sg_abi_version": (u32, []), "sg_weights_count": (sz, [u32]), "sg_hash32": (u32, [u32]),
+        "sg_last_error": (C.c_char_p, [H]),
+        "sg_create": (I, [C.POINTER(SgConfig), PP]), "sg_destroy": (I, [H]),
+        "sg_upsert_pod": (I, [H, u32, u32]), "sg_delete_pod": (I, [H, u32]),
+        "sg_upsert_service": (I, [H, u32, u32]), "sg_delete_service": (I, [H, u32]),
+        "sg_set_clock": (I, [H, u64, u64]), "sg_set_label_count": (I, [H, u32]),
+        "sg_load_weights": (I, [H, P, sz]),
+        "sg_ingest": (I, [H, P, sz]), "sg_ingest_device": (I, [H, P, sz, P]),
+        "sg_flush_window": (I, [H, u64, P, sz, Psz]),
+        "sg_flush_window_view": (I, [H, u64, PP, Psz]),
+        "sg_flush_begin": (I, [H, u64]),
+        "sg_flush_end": (I, [H, P, sz, Psz]),
+        "sg_flush_end_view": (I, [H, PP, Psz]),
+        "sg_window_run": (I, [H, P]), "sg_window_rows_buffer": (I, [H, PP]),
+        "sg_window_close": (I, [H, P]),
+        "sg_window_obip_list": (I, [H, P, u32, P, P]),
+        "sg_bind_buffers": (I, [H, P, P, PP, u32]),
+        "sg_window_close_sharded": (I, [H, P, P, P]),
+        "sg_window_features": (I, [H, P]), "sg_window_layer": (I, [H, u32, P]),
+        "sg_window_score": (I, [H, P]), "sg_window_score_reset": (I, [H, P]), "sg_window_read": (I, [H, P, sz, Psz]),
+        "sg_window_reset": (I, [H, P]),
+        "sg_window_buffers": (I, [H, PP, PP, PP, Psz]),
+        "sg_window_feat_buffer": (I, [H, u32, PP, Psz]),
+        "sg_halo_build": (I, [H, P, u32, P, P]), "sg_halo_pack": (I, [H, u32, P, u32, P, P]),
+        "sg_halo_unpack": (I, [H, u32, P, u32, P, P]),
+        "sg_window_close_gathered": (I, [H, P, u32, u32, P]),
+        "sg_halo_build_padded": (I, [H, P, u32, P]), "sg_halo_pack_padded": (I, [H, u32, P, u32, P, P]),
+        "sg_halo_unpack_padded": (I, [H, u32, P, u32, P, P]),
+        "sg_window_outbound_ips": (I, [H, P, sz, Psz]),
+        "sg_stats_get": (I, [H, C.POINTER(SgStats)]),
+        "sg_timing_enable": (I, [H, I]), "sg_timing_reset": (I, [H]),
+        "sg_timing_get": (I, [H, I, Pf64, Pu64]),
+        "sg_set_warm": (I, [H, I]), "sg_timing_stride": (I, [H, u32]),
+        "sg_timing_samples": (I, [H, I, Pf64, sz, Psz]),
+        "sg_latency_probe": (I, [H, u64, u32, I, Pf64]),
+        "sg_debug_stamps": (I, [H, P, sz]),
+        "sg_clock_probe": (I, [H, u32, Pf64, Pf64]),
+        "sg_comm_probe": (I, []), "sg_window_halo_counts": (I, [H, P, sz]),
+        "sg_route": (I, [H, P, sz, u32, P]),
+        "sg_window_hist": (I, [H, P, sz, Psz]),
+        "sg_geometry_get": (I, [H, C.POINTER(SgGeometry)]),
+        "sg_prepare_fold_get": (I, [H, C.POINTER(u32)]),
+        "sg_comm_unique_id": (I, [P, sz]), "sg_comm_create": (I, [P, sz, I, I, I, PP]),
+        "sg_comm_destroy": (I, [P]), "sg_window_run_sharded": (I, [H, P, P]),
+        "sg_host_register": (I, [H, P, sz]), "sg_host_unregister": (I, [H, P]), "sg_ingest_pinned": (I, [H, P, sz]),
+        "sg_ingest_bulk": (I, [H, P, sz, I, Pu64]),
+        "sg_flush_window_top": (I, [H, u64, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_flush_end_top": (I, [H, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_select": (I, [H, u32, f32, P, P, sz, P, P]),
+        "sg_set_trend": (I, [H, P]), "sg_window_trend": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_trend_buffer": (I, [H, PP]), "sg_trend_entries": (I, [H, P, sz, Psz]),
+        "sg_trend_stats_get": (I, [H, P]),
+        "sg_set_nodes": (I, [H, I]), "sg_window_nodes": (I, [H, P, sz, Psz]),
+        "sg_window_nodes_buffer": (I, [H, PP, PP]),
+        "sg_set_vanished": (I, [H, P]), "sg_window_vanished": (I, [H, P, sz, Psz]),
+        "sg_window_vanished_buffer": (I, [H, PP, PP]),
+        "sg_flush_window_top_by": (I, [H, u64, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_flush_end_top_by": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_select_by": (I, [H, u32, u32, f32, P, P, sz, P, P]),
+        "sg_set_node_trend": (I, [H, P]), "sg_window_node_trend": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_node_trend_buffer": (I, [H, PP]), "sg_node_trend_entries": (I, [H, P, sz, Psz]),
+        "sg_node_trend_stats_get": (I, [H, P]),
+        "sg_window_nodes_top": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_nodes_select": (I, [H, u32, u32, f32, P, P, sz, P, P]),
+        "sg_set_rank": (I, [H, P]), "sg_window_rank": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_rank_buffer": (I, [H, PP]),
+        "sg_window_rank_top": (I, [H, u32, f32, P, P, P, sz, Psz, Psz]),
+        "sg_window_rank_select": (I, [H, u32, f32, P, P, sz, P, P]),
+        "sg_set_incidents": (I, [H, P]), "sg_window_incidents": (I, [H, P, sz, Psz]),
+        "sg_window_node_incident": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_incidents_buffer": (I, [H, PP, PP, PP]),
+        "sg_set_tracks": (I, [H, P]), "sg_window_incident_tracks": (I, [H, P, sz, Psz]),
+        "sg_window_tracks_ended": (I, [H, P, sz, Psz]),
+        "sg_window_tracks_buffer": (I, [H, PP, PP, PP]),
+        "sg_track_entries": (I, [H, P, sz, Psz]), "sg_track_stats_get": (I, [H, P]),
+        "sg_set_groups": (I, [H, P]), "sg_group_assign": (I, [H, P, P, sz]),
+        "sg_window_groups": (I, [H, P, sz, Psz]), "sg_window_row_group": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_perm": (I, [H, P, sz, Psz]),
+        "sg_window_groups_buffer": (I, [H] + [PP] * 4),
+    }
+
+
+#: the C ABI, once: load_library applies it to the library, EXPORTS is its names (tests/test_abi.py holds them to the header)
+_SIGNATURES = _signatures()
+EXPORTS = list(_SIGNATURES)
+
+
 class ServiceGraphError(RuntimeError):
     def __init__(self, rc: int, msg: str):
         super().__init__(f"servicegraph rc={rc}: {msg}")
         self.rc = rc
 
+
+def _rank_seed(seed) -> int:
+    """sg_rank_params.seed: a name of RANK_SEED, or SG_RANK_SEED_* as it is"""
+    if not isinstance(seed, str):
+        return seed
+    if seed not in RANK_SEED:
+        raise ValueError(f"seed must be one of {sorted(RANK_SEED)}, not {seed!r}")
+    return RANK_SEED[seed]
+
+
+#: One row per opt-in stage that a params struct switches on (ServiceGraph._set_stage): the C function, its struct (whose fields are
+#: the parameters it accepts), the defaults, the two messages' nouns, and the fields that are translated on their way into the struct.
+_Stage = namedtuple("_Stage", "call struct defaults off noun convert", defaults=({},))
+_STAGES = dict(
+    trend=_Stage("sg_set_trend", SgTrendParams, TREND_DEFAULTS, "set_trend(None) switches the trend off", "trend"),
+    node_trend=_Stage("sg_set_node_trend", SgTrendParams, TREND_DEFAULTS, "set_node_trend(None) switches the node trend off", "node trend"),
+    vanished=_Stage("sg_set_vanished", SgVanishedParams, VANISHED_DEFAULTS, "set_vanished(None) switches the list off", "vanished"),
+    rank=_Stage("sg_set_rank", SgRankParams, RANK_DEFAULTS, "set_rank(None) switches the ranking off", "rank", dict(seed=_rank_seed)),
+    incidents=_Stage("sg_set_incidents", SgIncidentParams, INCIDENT_DEFAULTS, "set_incidents(None) switches the incidents off", "incident",
+                     dict(by=lambda by: ServiceGraph._by(by) if isinstance(by, str) else by)),
+    tracks=_Stage("sg_set_tracks", SgTrackParams, TRACK_DEFAULTS, "set_tracks(None) switches tracking off", "track"),
+    groups=_Stage("sg_set_groups", SgGroupParams, GROUP_DEFAULTS, "set_groups(None) switches the groups off", "group",
+                  dict(reserved=lambda r: (C.c_uint32 * 2)(*((r, 0) if isinstance(r, int) else tuple(r))))),
+)
 
 _lib = None
 _lib_dev = None
@@ -216,90 +315,7 @@ def load_library(path: str = LIB_PATH, dev: bool = False) -> C.CDLL:
     # (the development build is loaded locally: it exports the same names as the shipped library and both may be loaded in one process;
     # both are linked -Bsymbolic, so neither's own calls can land in the other)
     lib = C.CDLL(path, mode=C.RTLD_LOCAL if dev else C.RTLD_GLOBAL)
-    H, P = C.c_void_p, C.c_void_p
-    u32, u64, sz = C.c_uint32, C.c_uint64, C.c_size_t
-    sig = {
-        "sg_abi_version": (u32, []), "sg_weights_count": (sz, [u32]), "sg_hash32": (u32, [u32]),
-        "sg_last_error": (C.c_char_p, [H]),
-        "sg_create": (C.c_int, [C.POINTER(SgConfig), C.POINTER(H)]), "sg_destroy": (C.c_int, [H]),
-        "sg_upsert_pod": (C.c_int, [H, u32, u32]), "sg_delete_pod": (C.c_int, [H, u32]),
-        "sg_upsert_service": (C.c_int, [H, u32, u32]), "sg_delete_service": (C.c_int, [H, u32]),
-        "sg_set_clock": (C.c_int, [H, u64, u64]), "sg_set_label_count": (C.c_int, [H, u32]),
-        "sg_load_weights": (C.c_int, [H, P, sz]),
-        "sg_ingest": (C.c_int, [H, P, sz]), "sg_ingest_device": (C.c_int, [H, P, sz, P]),
-        "sg_flush_window": (C.c_int, [H, u64, P, sz, C.POINTER(sz)]),
-        "sg_flush_window_view": (C.c_int, [H, u64, C.POINTER(C.c_void_p), C.POINTER(sz)]),
-        "sg_flush_begin": (C.c_int, [H, u64]),
-        "sg_flush_end": (C.c_int, [H, C.c_void_p, sz, C.POINTER(sz)]),
-        "sg_flush_end_view": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(sz)]),
-        "sg_window_run": (C.c_int, [H, P]), "sg_window_rows_buffer": (C.c_int, [H, C.POINTER(P)]),
-        "sg_window_close": (C.c_int, [H, P]),
-        "sg_window_obip_list": (C.c_int, [H, P, u32, P, P]),
-        "sg_bind_buffers": (C.c_int, [H, P, P, C.POINTER(P), u32]),
-        "sg_window_close_sharded": (C.c_int, [H, P, P, P]),
-        "sg_window_features": (C.c_int, [H, P]), "sg_window_layer": (C.c_int, [H, u32, P]),
-        "sg_window_score": (C.c_int, [H, P]), "sg_window_score_reset": (C.c_int, [H, P]), "sg_window_read": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_window_reset": (C.c_int, [H, P]),
-        "sg_window_buffers": (C.c_int, [H, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(sz)]),
-        "sg_window_feat_buffer": (C.c_int, [H, u32, C.POINTER(P), C.POINTER(sz)]),
-        "sg_halo_build": (C.c_int, [H, P, u32, P, P]), "sg_halo_pack": (C.c_int, [H, u32, P, u32, P, P]),
-        "sg_halo_unpack": (C.c_int, [H, u32, P, u32, P, P]),
-        "sg_window_close_gathered": (C.c_int, [H, P, u32, u32, P]),
-        "sg_halo_build_padded": (C.c_int, [H, P, u32, P]), "sg_halo_pack_padded": (C.c_int, [H, u32, P, u32, P, P]),
-        "sg_halo_unpack_padded": (C.c_int, [H, u32, P, u32, P, P]),
-        "sg_window_outbound_ips": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_stats_get": (C.c_int, [H, C.POINTER(SgStats)]),
-        "sg_timing_enable": (C.c_int, [H, C.c_int]), "sg_timing_reset": (C.c_int, [H]),
-        "sg_timing_get": (C.c_int, [H, C.c_int, C.POINTER(C.c_double), C.POINTER(u64)]),
-        "sg_set_warm": (C.c_int, [H, C.c_int]), "sg_timing_stride": (C.c_int, [H, C.c_uint32]),
-        "sg_timing_samples": (C.c_int, [H, C.c_int, C.POINTER(C.c_double), sz, C.POINTER(sz)]),
-        "sg_latency_probe": (C.c_int, [H, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
-        "sg_debug_stamps": (C.c_int, [H, P, sz]),
-        "sg_clock_probe": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-        "sg_comm_probe": (C.c_int, []), "sg_window_halo_counts": (C.c_int, [H, P, sz]),
-        "sg_route": (C.c_int, [H, P, sz, u32, P]),
-        "sg_window_hist": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_geometry_get": (C.c_int, [H, C.POINTER(SgGeometry)]),
-        "sg_prepare_fold_get": (C.c_int, [H, C.POINTER(C.c_uint32)]),
-        "sg_comm_unique_id": (C.c_int, [P, sz]), "sg_comm_create": (C.c_int, [P, sz, C.c_int, C.c_int, C.c_int, C.POINTER(P)]),
-        "sg_comm_destroy": (C.c_int, [P]), "sg_window_run_sharded": (C.c_int, [H, P, P]),
-        "sg_host_register": (C.c_int, [H, P, sz]), "sg_host_unregister": (C.c_int, [H, P]), "sg_ingest_pinned": (C.c_int, [H, P, sz]),
-        "sg_ingest_bulk": (C.c_int, [H, P, sz, C.c_int, C.POINTER(u64)]),
-        "sg_flush_window_top": (C.c_int, [H, u64, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
-        "sg_flush_end_top": (C.c_int, [H, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
-        "sg_window_select": (C.c_int, [H, u32, C.c_float, P, P, sz, P, P]),
-        "sg_set_trend": (C.c_int, [H, P]), "sg_window_trend": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
-        "sg_window_trend_buffer": (C.c_int, [H, C.POINTER(C.c_void_p)]), "sg_trend_entries": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_trend_stats_get": (C.c_int, [H, P]),
-        "sg_set_nodes": (C.c_int, [H, C.c_int]), "sg_window_nodes": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_window_nodes_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
-        "sg_set_vanished": (C.c_int, [H, P]), "sg_window_vanished": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_window_vanished_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
-        "sg_flush_window_top_by": (C.c_int, [H, u64, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
-        "sg_flush_end_top_by": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
-        "sg_window_select_by": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, P, P]),
-        "sg_set_node_trend": (C.c_int, [H, P]), "sg_window_node_trend": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
-        "sg_window_node_trend_buffer": (C.c_int, [H, C.POINTER(C.c_void_p)]), "sg_node_trend_entries": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_node_trend_stats_get": (C.c_int, [H, P]),
-        "sg_window_nodes_top": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
-        "sg_window_nodes_select": (C.c_int, [H, u32, u32, C.c_float, P, P, sz, P, P]),
-        "sg_set_rank": (C.c_int, [H, P]), "sg_window_rank": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
-        "sg_window_rank_buffer": (C.c_int, [H, C.POINTER(C.c_void_p)]),
-        "sg_window_rank_top": (C.c_int, [H, u32, C.c_float, P, P, P, sz, C.POINTER(sz), C.POINTER(sz)]),
-        "sg_window_rank_select": (C.c_int, [H, u32, C.c_float, P, P, sz, P, P]),
-        "sg_set_incidents": (C.c_int, [H, P]), "sg_window_incidents": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_window_node_incident": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
-        "sg_window_incidents_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
-        "sg_set_tracks": (C.c_int, [H, P]), "sg_window_incident_tracks": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_window_tracks_ended": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_window_tracks_buffer": (C.c_int, [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
-        "sg_track_entries": (C.c_int, [H, P, sz, C.POINTER(sz)]), "sg_track_stats_get": (C.c_int, [H, P]),
-        "sg_set_groups": (C.c_int, [H, P]), "sg_group_assign": (C.c_int, [H, P, P, sz]),
-        "sg_window_groups": (C.c_int, [H, P, sz, C.POINTER(sz)]), "sg_window_row_group": (C.c_int, [H, P, sz, P, sz, C.POINTER(sz)]),
-        "sg_window_group_perm": (C.c_int, [H, P, sz, C.POINTER(sz)]),
-        "sg_window_groups_buffer": (C.c_int, [H] + [C.POINTER(C.c_void_p)] * 4),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _SIGNATURES.items():
         f = getattr(lib, name)          # AttributeError if the library does not export it
         f.restype = res; f.argtypes = args
     if dev:
@@ -375,6 +391,83 @@ class ServiceGraph:
             raise ServiceGraphError(rc, (self._l.sg_last_error(self._h) or b"").decode())
         return rc
 
+    def _set_stage(self, stage: str, params, kw) -> Optional[dict]:
+        """every set_* with a params struct (_STAGES): call(h, NULL) for params None, else call(h, the struct filled by field name from
+        the defaults, params and kw); returns the merged parameters"""
+        st = _STAGES[stage]
+        call = getattr(self._l, st.call)
+        if params is None:
+            if kw:
+                raise TypeError(f"{st.off} and takes no parameters")
+            self._ck(call(self._h, None))
+            return None
+        v = dict(st.defaults)
+        v.update(params or {}); v.update(kw)
+        unknown = set(v) - {f for f, _ in st.struct._fields_}
+        if unknown:
+            raise TypeError(f"unknown {st.noun} parameters: {sorted(unknown)}")
+        p = st.struct(struct_size=C.sizeof(st.struct))
+        for f, x in v.items():
+            setattr(p, f, st.convert[f](x) if f in st.convert else x)
+        self._ck(call(self._h, C.byref(p)))
+        return v
+
+    def _counted(self, call, dtype, shape_tail=()) -> np.ndarray:
+        """two calls: call(h, NULL, 0, &n) for the count, call(h, out, n, &n) for the rows"""
+        n = C.c_size_t(0)
+        self._ck(call(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value,) + shape_tail, dtype=dtype)
+        if n.value:
+            self._ck(call(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def _window_rows(self, call, dtype, index):
+        """call(h, index, n_index, out, cap, &n): every row of the last read window (index None: the count, then the rows), or those at index"""
+        if index is None:
+            return self._counted(lambda h, out, cap, n: call(h, None, 0, out, cap, n), dtype)
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        out = np.zeros(len(idx), dtype=dtype)
+        if len(idx):
+            self._ck(call(self._h, idx.ctypes.data, len(idx), out.ctypes.data, len(idx), C.byref(C.c_size_t(0))))
+        return out
+
+    def _capped(self, call, cap: Optional[int]) -> np.ndarray:
+        """room for cap rows (None = max_edges), call(out, cap, &n), the min(n, cap) rows that were written"""
+        cap = self.max_edges if cap is None else cap
+        out = np.zeros(cap, dtype=EDGE_OUT_DTYPE); n = C.c_size_t(0)
+        self._ck(call(out.ctypes.data, cap, C.byref(n)))
+        return out[: min(n.value, cap)]
+
+    def _top(self, call, cap: int, *dtypes):
+        """a selection into host memory: one array of cap rows per dtype, call(*arrays, cap, &n_selected, &n_total), the
+        min(n_selected, cap) rows of each that were written and n_total"""
+        outs = [np.zeros(cap, dtype=d) for d in dtypes]
+        ns, nt = C.c_size_t(0), C.c_size_t(0)
+        self._ck(call(*[o.ctypes.data for o in outs], cap, C.byref(ns), C.byref(nt)))
+        m = min(ns.value, cap)
+        return (*[o[:m] for o in outs], nt.value)
+
+    def _node_cap(self, k: int, cap: Optional[int]) -> int:
+        """a node selection's cap: the caller's, else k, else (k = 0) the window's node count — one sg_window_nodes(NULL, 0) call"""
+        if cap is not None:
+            return cap
+        if k:
+            return k
+        n = C.c_size_t(0)
+        self._ck(self._l.sg_window_nodes(self._h, None, 0, C.byref(n)))
+        return n.value
+
+    def _pointers(self, call, n: int) -> tuple:
+        """call(h, &p0 .. &p(n-1)): the n device pointers as ints"""
+        p = [C.c_void_p() for _ in range(n)]
+        self._ck(call(self._h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def _stats(self, call, struct):
+        s = struct()
+        self._ck(call(self._h, C.byref(s)))
+        return s
+
     def close(self):
         if getattr(self, "_h", None):
             self._l.sg_destroy(self._h); self._h = None
@@ -442,11 +535,7 @@ class ServiceGraph:
 
     # ---- window ----
     def flush_window(self, window_end_ms: int = 0, cap: Optional[int] = None) -> np.ndarray:
-        cap = self.max_edges if cap is None else cap
-        out = np.zeros(cap, dtype=EDGE_OUT_DTYPE)
-        n = C.c_size_t(0)
-        self._ck(self._l.sg_flush_window(self._h, window_end_ms, out.ctypes.data, cap, C.byref(n)))
-        return out[: min(n.value, cap)]
+        return self._capped(lambda out, c, n: self._l.sg_flush_window(self._h, window_end_ms, out, c, n), cap)
 
     def flush_window_view(self, window_end_ms: int = 0) -> np.ndarray:
         """The window's rows as a read-only VIEW of the engine's page-locked host buffer (no copy): valid until the next
@@ -467,20 +556,9 @@ class ServiceGraph:
         return self._rows_view(ptr, n)
 
     def flush_end(self, cap: int | None = None) -> np.ndarray:
-        cap = self.max_edges if cap is None else cap
-        out = np.zeros(cap, dtype=EDGE_OUT_DTYPE); n = C.c_size_t(0)
-        self._ck(self._l.sg_flush_end(self._h, out.ctypes.data, cap, C.byref(n)))
-        return out[: min(n.value, cap)]
+        return self._capped(lambda out, c, n: self._l.sg_flush_end(self._h, out, c, n), cap)
 
     # ---- selection (K7): only the selected rows leave the device ----
-    def _top(self, call, k: int, cap: Optional[int]):
-        cap = (k if k else self.max_edges) if cap is None else cap
-        out = np.zeros(cap, dtype=EDGE_OUT_DTYPE); idx = np.zeros(cap, dtype=np.uint32)
-        ns, ne = C.c_size_t(0), C.c_size_t(0)
-        self._ck(call(out.ctypes.data, idx.ctypes.data, cap, C.byref(ns), C.byref(ne)))
-        m = min(ns.value, cap)
-        return out[:m], idx[:m], ne.value
-
     @staticmethod
     def _by(by) -> int:
         if by not in SEL_BY:
@@ -494,16 +572,18 @@ class ServiceGraph:
         defaults to k (k > 0) or max_edges; rows beyond it are counted, not returned.  by = "lat_dev" / "err_dev" / "new" selects
         by the row's trend instead of its score (sg_flush_window_top_by; min_score is then the threshold on that value)."""
         b = self._by(by)
+        cap = (k or self.max_edges) if cap is None else cap
         if b:
-            return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_window_top_by(self._h, window_end_ms, b, k, min_score, o, i, c, ns, ne), k, cap)
-        return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_window_top(self._h, window_end_ms, k, min_score, o, i, c, ns, ne), k, cap)
+            return self._top(lambda *a: self._l.sg_flush_window_top_by(self._h, window_end_ms, b, k, min_score, *a), cap, EDGE_OUT_DTYPE, np.uint32)
+        return self._top(lambda *a: self._l.sg_flush_window_top(self._h, window_end_ms, k, min_score, *a), cap, EDGE_OUT_DTYPE, np.uint32)
 
     def flush_end_top(self, k: int, min_score: float = float("-inf"), cap: Optional[int] = None, by: str = "score"):
         """flush_window_top for the window flush_begin closed (sg_flush_end_top / sg_flush_end_top_by)."""
         b = self._by(by)
+        cap = (k or self.max_edges) if cap is None else cap
         if b:
-            return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_end_top_by(self._h, b, k, min_score, o, i, c, ns, ne), k, cap)
-        return self._top(lambda o, i, c, ns, ne: self._l.sg_flush_end_top(self._h, k, min_score, o, i, c, ns, ne), k, cap)
+            return self._top(lambda *a: self._l.sg_flush_end_top_by(self._h, b, k, min_score, *a), cap, EDGE_OUT_DTYPE, np.uint32)
+        return self._top(lambda *a: self._l.sg_flush_end_top(self._h, k, min_score, *a), cap, EDGE_OUT_DTYPE, np.uint32)
 
     def window_select(self, k: int, min_score: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0, by: str = "score"):
         """Select from the rows of the window window_run closed last into device memory (sg_window_select): d_out [cap] rows,
@@ -519,107 +599,43 @@ class ServiceGraph:
     def set_trend(self, params: Optional[dict] = (), **kw):
         """Switch the per-edge baseline on (sg_set_trend; shift, warmup, ttl, max_entries, lat_floor_ns, err_floor as keywords or a
         dict — see TREND_DEFAULTS; set_trend() = every default; (re)enabling starts an empty baseline) or off: set_trend(None)."""
-        v = self._set_baseline(self._l.sg_set_trend, params, kw, "set_trend(None) switches the trend off", "trend")
+        v = self._set_stage("trend", params, kw)
         if v is not None:
             self._trend_entries = v["max_entries"] or min(1 << 31, 2 * max(self.max_edges, 1))   # the baseline's capacity
-
-    def _set_baseline(self, call, params, kw, off_text: str, what: str):
-        """set_trend / set_node_trend: call(h, NULL) for params None, else call(h, sg_trend_params) and the parameters"""
-        if params is None:
-            if kw:
-                raise TypeError(f"{off_text} and takes no parameters")
-            self._ck(call(self._h, None))
-            return None
-        v = dict(TREND_DEFAULTS)
-        v.update(params or {}); v.update(kw)
-        unknown = set(v) - set(TREND_DEFAULTS) - {"struct_size", "reserved"}
-        if unknown:
-            raise TypeError(f"unknown {what} parameters: {sorted(unknown)}")
-        p = SgTrendParams(v.get("struct_size", C.sizeof(SgTrendParams)), v["shift"], v["warmup"], v["ttl"], v["max_entries"],
-                          v["lat_floor_ns"], v["err_floor"], v.get("reserved", 0))
-        self._ck(call(self._h, C.byref(p)))
-        return v
 
     def window_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
         """TREND_DTYPE rows of the last read window (sg_window_trend): every row, or the rows at `index` (only those cross PCIe)."""
         return self._window_rows(self._l.sg_window_trend, TREND_DTYPE, index)
 
-    def _window_rows(self, call, dtype, index):
-        """window_trend / window_node_trend: every row of the last read window (two calls: the count, the rows), or those at index"""
-        n = C.c_size_t(0)
-        if index is None:
-            self._ck(call(self._h, None, 0, None, 0, C.byref(n)))
-            out = np.zeros(n.value, dtype=dtype)
-            if n.value:
-                self._ck(call(self._h, None, 0, out.ctypes.data, n.value, C.byref(n)))
-            return out
-        idx = np.ascontiguousarray(index, dtype=np.uint32)
-        out = np.zeros(len(idx), dtype=dtype)
-        if len(idx):
-            self._ck(call(self._h, idx.ctypes.data, len(idx), out.ctypes.data, len(idx), C.byref(n)))
-        return out
-
     def trend_buffer(self) -> int:
         """device pointer of the sg_edge_trend rows of the window window_run closed last (sg_window_trend_buffer)"""
-        p = C.c_void_p()
-        self._ck(self._l.sg_window_trend_buffer(self._h, C.byref(p)))
-        return p.value
+        return self._pointers(self._l.sg_window_trend_buffer, 1)[0]
 
     def trend_entries(self) -> np.ndarray:
         """the baseline in key order, TREND_ENTRY_DTYPE (sg_trend_entries)"""
-        return self._entries(self._l.sg_trend_entries)
-
-    def _entries(self, call) -> np.ndarray:
-        """trend_entries / node_trend_entries: the count, then the entries"""
-        n = C.c_size_t(0)
-        self._ck(call(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=TREND_ENTRY_DTYPE)
-        if n.value:
-            self._ck(call(self._h, out.ctypes.data, n.value, C.byref(n)))
-        return out[: n.value]
+        return self._counted(self._l.sg_trend_entries, TREND_ENTRY_DTYPE)
 
     def trend_stats(self) -> SgTrendStats:
-        return self._stats(self._l.sg_trend_stats_get)
-
-    def _stats(self, call) -> SgTrendStats:
-        s = SgTrendStats()
-        self._ck(call(self._h, C.byref(s)))
-        return s
+        return self._stats(self._l.sg_trend_stats_get, SgTrendStats)
 
     def set_vanished(self, params: Optional[dict] = (), **kw):
         """Switch K8's vanished list on (sg_set_vanished; silent_windows, min_seen, max_rows as keywords or a dict — see
         VANISHED_DEFAULTS; needs the trend on) or off: set_vanished(None).  Any set_trend call switches it off."""
-        if params is None:
-            if kw:
-                raise TypeError("set_vanished(None) switches the list off and takes no parameters")
-            self._ck(self._l.sg_set_vanished(self._h, None))
-            return
-        v = dict(VANISHED_DEFAULTS)
-        v.update(params or {}); v.update(kw)
-        unknown = set(v) - set(VANISHED_DEFAULTS) - {"struct_size"}
-        if unknown:
-            raise TypeError(f"unknown vanished parameters: {sorted(unknown)}")
-        p = SgVanishedParams(v.get("struct_size", C.sizeof(SgVanishedParams)), v["silent_windows"], v["min_seen"], v["max_rows"])
-        self._ck(self._l.sg_set_vanished(self._h, C.byref(p)))
-        self._van_rows = v["max_rows"] or min(65536, self._trend_entries)   # (the rows a window's list holds at most)
+        v = self._set_stage("vanished", params, kw)
+        if v is not None:
+            self._van_rows = v["max_rows"] or min(65536, self._trend_entries)   # (the rows a window's list holds at most)
 
     def window_vanished(self, with_count: bool = False):
         """VANISHED_DTYPE list of the last read window (sg_window_vanished), ascending by edge key; with_count: (list, count of
         every vanished entry of the window, which may exceed max_rows)."""
-        n = C.c_size_t(0)
-        self._ck(self._l.sg_window_vanished(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=VANISHED_DTYPE)
-        if n.value:
-            self._ck(self._l.sg_window_vanished(self._h, out.ctypes.data, n.value, C.byref(n)))
-        rows = out[: min(n.value, self._van_rows)]
-        return (rows, n.value) if with_count else rows
+        out = self._counted(self._l.sg_window_vanished, VANISHED_DTYPE)       # (room for the count; max_rows of them are written)
+        rows = out[: self._van_rows]
+        return (rows, len(out)) if with_count else rows
 
     def vanished_buffer(self) -> Tuple[int, int]:
         """(device pointer of the sg_edge_vanished list, device pointer of its u64 count) of the window window_run closed last
         (sg_window_vanished_buffer)"""
-        p, c = C.c_void_p(), C.c_void_p()
-        self._ck(self._l.sg_window_vanished_buffer(self._h, C.byref(p), C.byref(c)))
-        return p.value, c.value
+        return self._pointers(self._l.sg_window_vanished_buffer, 2)
 
     # ---- node rollup (K9): each window's rows reduced per node on the device ----
     def set_nodes(self, on: bool = True):
@@ -628,25 +644,18 @@ class ServiceGraph:
 
     def window_nodes(self) -> np.ndarray:
         """NODE_DTYPE rows of the last read window (sg_window_nodes), ascending by (ref type, ref value)"""
-        n = C.c_size_t(0)
-        self._ck(self._l.sg_window_nodes(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=NODE_DTYPE)
-        if n.value:
-            self._ck(self._l.sg_window_nodes(self._h, out.ctypes.data, n.value, C.byref(n)))
-        return out[: n.value]
+        return self._counted(self._l.sg_window_nodes, NODE_DTYPE)
 
     def nodes_buffer(self) -> Tuple[int, int]:
         """(device pointer of the sg_node_out rows, device pointer of their u64 count) of the window window_run closed last
         (sg_window_nodes_buffer)"""
-        p, c = C.c_void_p(), C.c_void_p()
-        self._ck(self._l.sg_window_nodes_buffer(self._h, C.byref(p), C.byref(c)))
-        return p.value, c.value
+        return self._pointers(self._l.sg_window_nodes_buffer, 2)
 
     # ---- node baselines (K10) and node selection: each service against its own past ----
     def set_node_trend(self, params: Optional[dict] = (), **kw):
         """Switch the per-node baseline on (sg_set_node_trend; the parameters of set_trend, max_entries 0 = 4 x the node capacity;
         needs the node rollup on; (re)enabling starts an empty baseline) or off: set_node_trend(None)."""
-        self._set_baseline(self._l.sg_set_node_trend, params, kw, "set_node_trend(None) switches the node trend off", "node trend")
+        self._set_stage("node_trend", params, kw)
 
     def window_node_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
         """NODE_TREND_DTYPE rows of the last read window (sg_window_node_trend), row k for node row k of window_nodes(); or the rows
@@ -655,16 +664,14 @@ class ServiceGraph:
 
     def node_trend_buffer(self) -> int:
         """device pointer of the sg_node_trend rows of the window window_run closed last (sg_window_node_trend_buffer)"""
-        p = C.c_void_p()
-        self._ck(self._l.sg_window_node_trend_buffer(self._h, C.byref(p)))
-        return p.value
+        return self._pointers(self._l.sg_window_node_trend_buffer, 1)[0]
 
     def node_trend_entries(self) -> np.ndarray:
         """the node baseline in key order, TREND_ENTRY_DTYPE with to_key = side (0 in, 1 out) (sg_node_trend_entries)"""
-        return self._entries(self._l.sg_node_trend_entries)
+        return self._counted(self._l.sg_node_trend_entries, TREND_ENTRY_DTYPE)
 
     def node_trend_stats(self) -> SgTrendStats:
-        return self._stats(self._l.sg_node_trend_stats_get)
+        return self._stats(self._l.sg_node_trend_stats_get, SgTrendStats)
 
     @staticmethod
     def _nby(by) -> int:
@@ -677,18 +684,7 @@ class ServiceGraph:
         every node with value >= min_value in node order, else the k highest such, descending, ties by node position.  by: a key
         of NSEL_BY.  cap defaults to k (k > 0) or the window's node count; nodes beyond it are counted, not returned."""
         b = self._nby(by)
-        if cap is None:
-            if k:
-                cap = k
-            else:
-                n = C.c_size_t(0)
-                self._ck(self._l.sg_window_nodes(self._h, None, 0, C.byref(n)))
-                cap = n.value
-        out = np.zeros(cap, dtype=NODE_DTYPE); idx = np.zeros(cap, dtype=np.uint32)
-        ns, nn = C.c_size_t(0), C.c_size_t(0)
-        self._ck(self._l.sg_window_nodes_top(self._h, b, k, min_value, out.ctypes.data, idx.ctypes.data, cap, C.byref(ns), C.byref(nn)))
-        m = min(ns.value, cap)
-        return out[:m], idx[:m], nn.value
+        return self._top(lambda *a: self._l.sg_window_nodes_top(self._h, b, k, min_value, *a), self._node_cap(k, cap), NODE_DTYPE, np.uint32)
 
     def window_nodes_select(self, k: int, min_value: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0,
                             by: str = "score"):
@@ -702,24 +698,7 @@ class ServiceGraph:
     def set_rank(self, params: Optional[dict] = (), **kw):
         """Switch the per-window culprit ranking on (sg_set_rank; iters, damping_q8, seed ("score" / "uniform" or SG_RANK_SEED_*),
         seed_min_score as keywords or a dict — see RANK_DEFAULTS; needs the node rollup on) or off: set_rank(None)."""
-        if params is None:
-            if kw:
-                raise TypeError("set_rank(None) switches the ranking off and takes no parameters")
-            self._ck(self._l.sg_set_rank(self._h, None))
-            return
-        v = dict(RANK_DEFAULTS)
-        v.update(params or {}); v.update(kw)
-        unknown = set(v) - set(RANK_DEFAULTS) - {"struct_size", "reserved"}
-        if unknown:
-            raise TypeError(f"unknown rank parameters: {sorted(unknown)}")
-        seed = v["seed"]
-        if isinstance(seed, str):
-            if seed not in RANK_SEED:
-                raise ValueError(f"seed must be one of {sorted(RANK_SEED)}, not {seed!r}")
-            seed = RANK_SEED[seed]
-        p = SgRankParams(v.get("struct_size", C.sizeof(SgRankParams)), v["iters"], v["damping_q8"], seed, v["seed_min_score"],
-                         v.get("reserved", 0))
-        self._ck(self._l.sg_set_rank(self._h, C.byref(p)))
+        self._set_stage("rank", params, kw)
 
     def window_rank(self, index: Optional[np.ndarray] = None) -> np.ndarray:
         """RANK_DTYPE rows of the last read window (sg_window_rank), row k for node row k of window_nodes(); or the rows of the
@@ -728,56 +707,30 @@ class ServiceGraph:
 
     def rank_buffer(self) -> int:
         """device pointer of the sg_node_rank rows of the window window_run closed last (sg_window_rank_buffer)"""
-        p = C.c_void_p()
-        self._ck(self._l.sg_window_rank_buffer(self._h, C.byref(p)))
-        return p.value
+        return self._pointers(self._l.sg_window_rank_buffer, 1)[0]
 
     def window_rank_top(self, k: int, min_share: float = float("-inf"), cap: Optional[int] = None):
         """(node rows, rank rows, node indices, n_nodes) of a selection over the last read window's rank rows
         (sg_window_rank_top): k = 0 every node with rank >= 2^24 and share >= min_share in node order, else the k highest such,
         descending, ties by node position.  cap defaults to k (k > 0) or the window's node count."""
-        if cap is None:
-            if k:
-                cap = k
-            else:
-                n = C.c_size_t(0)
-                self._ck(self._l.sg_window_nodes(self._h, None, 0, C.byref(n)))
-                cap = n.value
-        out = np.zeros(cap, dtype=NODE_DTYPE); rk = np.zeros(cap, dtype=RANK_DTYPE); idx = np.zeros(cap, dtype=np.uint32)
-        ns, nn = C.c_size_t(0), C.c_size_t(0)
-        self._ck(self._l.sg_window_rank_top(self._h, k, min_share, out.ctypes.data, rk.ctypes.data, idx.ctypes.data, cap,
-                                            C.byref(ns), C.byref(nn)))
-        m = min(ns.value, cap)
-        return out[:m], rk[:m], idx[:m], nn.value
+        return self._top(lambda *a: self._l.sg_window_rank_top(self._h, k, min_share, *a), self._node_cap(k, cap),
+                         NODE_DTYPE, RANK_DTYPE, np.uint32)
+
+    def window_rank_select(self, k: int, min_share: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
+        """Select from the rank rows of the window window_run closed last into device memory (sg_window_rank_select): d_out [cap]
+        node rows (0 = none), d_index [cap] u32 (0 = none), d_n one u64 = nodes selected; enqueued on `stream` (0 = that window's
+        stream)."""
+        self._ck(self._l.sg_window_rank_select(self._h, k, min_share, d_out or None, d_index or None, cap, d_n, stream or None))
 
     # ---- incidents (K12): the window's red rows grouped into connected components ----
     def set_incidents(self, params: Optional[dict] = (), **kw):
         """Switch the per-window incident grouping on (sg_set_incidents; by = "score" / "lat_dev" / "err_dev" or SG_SEL_*, min_value
         as keywords or a dict; needs the node rollup on, and the trend for a trend key) or off: set_incidents(None)."""
-        if params is None:
-            if kw:
-                raise TypeError("set_incidents(None) switches the incidents off and takes no parameters")
-            self._ck(self._l.sg_set_incidents(self._h, None))
-            return
-        v = dict(by="score", min_value=0.0)
-        v.update(params or {}); v.update(kw)
-        unknown = set(v) - {"by", "min_value", "struct_size", "reserved"}
-        if unknown:
-            raise TypeError(f"unknown incident parameters: {sorted(unknown)}")
-        by = v["by"]
-        if isinstance(by, str):
-            by = self._by(by)
-        p = SgIncidentParams(v.get("struct_size", C.sizeof(SgIncidentParams)), by, v["min_value"], v.get("reserved", 0))
-        self._ck(self._l.sg_set_incidents(self._h, C.byref(p)))
+        self._set_stage("incidents", params, kw)
 
     def window_incidents(self) -> np.ndarray:
         """INCIDENT_DTYPE rows of the last read window (sg_window_incidents), numbered by their smallest node row"""
-        n = C.c_size_t(0)
-        self._ck(self._l.sg_window_incidents(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=INCIDENT_DTYPE)
-        if n.value:
-            self._ck(self._l.sg_window_incidents(self._h, out.ctypes.data, n.value, C.byref(n)))
-        return out[: n.value]
+        return self._counted(self._l.sg_window_incidents, INCIDENT_DTYPE)
 
     def window_node_incident(self, index: Optional[np.ndarray] = None) -> np.ndarray:
         """the incident number (NO_INCIDENT: none) of every node row of the last read window (sg_window_node_incident), or of the
@@ -787,34 +740,13 @@ class ServiceGraph:
     def window_incidents_buffer(self) -> Tuple[int, int, int]:
         """(device pointer of the sg_incident_out rows, of their u64 count, of the u32 incident per node row) of the window
         window_run closed last (sg_window_incidents_buffer)"""
-        p, c, q = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self._ck(self._l.sg_window_incidents_buffer(self._h, C.byref(p), C.byref(c), C.byref(q)))
-        return p.value, c.value, q.value
+        return self._pointers(self._l.sg_window_incidents_buffer, 3)
 
     # ---- tracks (K13): the incidents followed across windows ----
     def set_tracks(self, params: Optional[dict] = (), **kw):
         """Switch the tracking of incidents across windows on (sg_set_tracks; quiet_windows (default 2), max_tracks (0 = never cut)
         as keywords or a dict; needs the incidents on) or off: set_tracks(None).  Any set_incidents call switches it off."""
-        if params is None:
-            if kw:
-                raise TypeError("set_tracks(None) switches tracking off and takes no parameters")
-            self._ck(self._l.sg_set_tracks(self._h, None))
-            return
-        v = dict(quiet_windows=2, max_tracks=0)
-        v.update(params or {}); v.update(kw)
-        unknown = set(v) - {"quiet_windows", "max_tracks", "struct_size", "reserved"}
-        if unknown:
-            raise TypeError(f"unknown track parameters: {sorted(unknown)}")
-        p = SgTrackParams(v.get("struct_size", C.sizeof(SgTrackParams)), v["quiet_windows"], v["max_tracks"], v.get("reserved", 0))
-        self._ck(self._l.sg_set_tracks(self._h, C.byref(p)))
-
-    def _counted(self, call, dtype) -> np.ndarray:
-        n = C.c_size_t(0)
-        self._ck(call(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=dtype)
-        if n.value:
-            self._ck(call(self._h, out.ctypes.data, n.value, C.byref(n)))
-        return out[: n.value]
+        self._set_stage("tracks", params, kw)
 
     def window_incident_tracks(self) -> np.ndarray:
         """TRACK_DTYPE rows of the last read window (sg_window_incident_tracks): row i is the track of window_incidents()[i]"""
@@ -827,37 +759,20 @@ class ServiceGraph:
     def window_tracks_buffer(self) -> Tuple[int, int, int]:
         """(device pointer of the sg_incident_track rows, of the ended sg_track_entry list, of its u64 count) of the window
         window_run closed last (sg_window_tracks_buffer)"""
-        p, c, q = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self._ck(self._l.sg_window_tracks_buffer(self._h, C.byref(p), C.byref(c), C.byref(q)))
-        return p.value, c.value, q.value
+        return self._pointers(self._l.sg_window_tracks_buffer, 3)
 
     def track_entries(self) -> np.ndarray:
         """the live track table in id order, TRACK_ENTRY_DTYPE (sg_track_entries)"""
         return self._counted(self._l.sg_track_entries, TRACK_ENTRY_DTYPE)
 
     def track_stats(self) -> SgTrackStats:
-        s = SgTrackStats()
-        self._ck(self._l.sg_track_stats_get(self._h, C.byref(s)))
-        return s
+        return self._stats(self._l.sg_track_stats_get, SgTrackStats)
 
     # ---- groups (K14): the window's service map contracted to workloads ----
     def set_groups(self, params: Optional[dict] = (), **kw):
         """Switch the per-window contraction to workloads on (sg_set_groups; max_groups (0 = max_known_nodes) as a keyword or a
         dict; needs no other stage) or off: set_groups(None).  Every call starts from a map with nothing grouped."""
-        if params is None:
-            if kw:
-                raise TypeError("set_groups(None) switches the groups off and takes no parameters")
-            self._ck(self._l.sg_set_groups(self._h, None))
-            return
-        v = dict(max_groups=0)
-        v.update(params or {}); v.update(kw)
-        unknown = set(v) - {"max_groups", "struct_size", "reserved"}
-        if unknown:
-            raise TypeError(f"unknown group parameters: {sorted(unknown)}")
-        r = v.get("reserved", 0)
-        r = (r, 0) if isinstance(r, int) else tuple(r)
-        p = SgGroupParams(v.get("struct_size", C.sizeof(SgGroupParams)), v["max_groups"], (C.c_uint32 * 2)(*r))
-        self._ck(self._l.sg_set_groups(self._h, C.byref(p)))
+        self._set_stage("groups", params, kw)
 
     def group_assign(self, node_ids, groups):
         """group[node_ids[i]] = groups[i] (sg_group_assign; NO_GROUP takes a node out of its group).  The windows closed from now
@@ -882,15 +797,7 @@ class ServiceGraph:
     def window_groups_buffer(self) -> Tuple[int, int, int, int]:
         """(device pointer of the sg_group_edge rows, of their u64 count, of the u32 row_group, of the u32 perm) of the window
         window_run closed last (sg_window_groups_buffer)"""
-        p = [C.c_void_p() for _ in range(4)]
-        self._ck(self._l.sg_window_groups_buffer(self._h, *[C.byref(x) for x in p]))
-        return tuple(x.value for x in p)
-
-    def window_rank_select(self, k: int, min_share: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
-        """Select from the rank rows of the window window_run closed last into device memory (sg_window_rank_select): d_out [cap]
-        node rows (0 = none), d_index [cap] u32 (0 = none), d_n one u64 = nodes selected; enqueued on `stream` (0 = that window's
-        stream)."""
-        self._ck(self._l.sg_window_rank_select(self._h, k, min_share, d_out or None, d_index or None, cap, d_n, stream or None))
+        return self._pointers(self._l.sg_window_groups_buffer, 4)
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:
@@ -931,11 +838,7 @@ class ServiceGraph:
         self._ck(self._l.sg_bind_buffers(self._h, stats_sum, stats_max, arr, len(feat_rows)))
 
     def window_read(self, cap: Optional[int] = None) -> np.ndarray:
-        cap = self.max_edges if cap is None else cap
-        out = np.zeros(cap, dtype=EDGE_OUT_DTYPE)
-        n = C.c_size_t(0)
-        self._ck(self._l.sg_window_read(self._h, out.ctypes.data, cap, C.byref(n)))
-        return out[: min(n.value, cap)]
+        return self._capped(lambda out, c, n: self._l.sg_window_read(self._h, out, c, n), cap)
 
     def window_buffers(self):
         a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
@@ -948,9 +851,7 @@ class ServiceGraph:
         return p.value, w.value
 
     def rows_buffer(self) -> int:
-        p = C.c_void_p()
-        self._ck(self._l.sg_window_rows_buffer(self._h, C.byref(p)))
-        return p.value
+        return self._pointers(self._l.sg_window_rows_buffer, 1)[0]
 
     def halo_build(self, d_ids: int, cap: int, d_counts: int, stream: int = 0): self._ck(self._l.sg_halo_build(self._h, d_ids, cap, d_counts, stream or None))
     def halo_pack(self, l: int, d_ids: int, n: int, d_rows: int, stream: int = 0): self._ck(self._l.sg_halo_pack(self._h, l, d_ids, n, d_rows, stream or None))
@@ -964,26 +865,14 @@ class ServiceGraph:
     def halo_unpack_padded(self, l: int, d_req: int, capp: int, d_rows: int, stream: int = 0): self._ck(self._l.sg_halo_unpack_padded(self._h, l, d_req, capp, d_rows, stream or None))
 
     def outbound_ips(self) -> np.ndarray:
-        n = C.c_size_t(0)
-        self._ck(self._l.sg_window_outbound_ips(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=np.uint32)
-        if n.value:
-            self._ck(self._l.sg_window_outbound_ips(self._h, out.ctypes.data, n.value, C.byref(n)))
-        return out
+        return self._counted(self._l.sg_window_outbound_ips, np.uint32)
 
     def window_hist(self) -> np.ndarray:
         """[rows][16] u32 latency histogram bins of the last read window (engine created with edge_histogram=True)."""
-        n = C.c_size_t(0)
-        self._ck(self._l.sg_window_hist(self._h, None, 0, C.byref(n)))
-        out = np.zeros((n.value, 16), dtype=np.uint32)
-        if n.value:
-            self._ck(self._l.sg_window_hist(self._h, out.ctypes.data, n.value, C.byref(n)))
-        return out
+        return self._counted(self._l.sg_window_hist, np.uint32, (16,))
 
     def stats(self) -> SgStats:
-        s = SgStats()
-        self._ck(self._l.sg_stats_get(self._h, C.byref(s)))
-        return s
+        return self._stats(self._l.sg_stats_get, SgStats)
 
     def timing_enable(self, mask: int = 1): self._ck(self._l.sg_timing_enable(self._h, int(mask)))
     def timing_reset(self): self._ck(self._l.sg_timing_reset(self._h))
