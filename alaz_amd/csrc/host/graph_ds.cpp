@@ -2,6 +2,7 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -21,6 +22,11 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->set_groups = reinterpret_cast<decltype(o->set_groups)>(dlsym(dl, "sg_set_groups"));                        // optional (K14)
     o->group_assign = reinterpret_cast<decltype(o->group_assign)>(dlsym(dl, "sg_group_assign"));
     o->window_groups = reinterpret_cast<decltype(o->window_groups)>(dlsym(dl, "sg_window_groups"));
+    o->set_group_trend = reinterpret_cast<decltype(o->set_group_trend)>(dlsym(dl, "sg_set_group_trend"));          // optional (K15)
+    o->window_group_trend = reinterpret_cast<decltype(o->window_group_trend)>(dlsym(dl, "sg_window_group_trend"));
+    o->set_group_vanished = reinterpret_cast<decltype(o->set_group_vanished)>(dlsym(dl, "sg_set_group_vanished"));
+    o->window_group_vanished = reinterpret_cast<decltype(o->window_group_vanished)>(dlsym(dl, "sg_window_group_vanished"));
+    o->window_groups_top = reinterpret_cast<decltype(o->window_groups_top)>(dlsym(dl, "sg_window_groups_top"));
 #undef SG_SYM
     return true;
 }
@@ -131,6 +137,10 @@ long GraphDS::WorkloadEdges(std::vector<WorkloadEdge>* out) {
     if (n && (rc = api_.window_groups(h_, ge.data(), n, &n)) != SG_OK) return rc;
     out->assign(ge.size(), WorkloadEdge{});
     std::lock_guard<std::mutex> g(id_mu_);
+    for (size_t i = 0; i < ge.size(); i++) NameWorkloadEdge(ge[i], &(*out)[i]);
+    return (long)ge.size();
+}
+void GraphDS::NameWorkloadEdge(const sg_group_edge& r, WorkloadEdge* out) const {
     auto name = [&](uint32_t ref, std::string* type, std::string* uid) {
         const uint32_t t = SG_REF_TYPE(ref), v = SG_REF_VALUE(ref);
         if (t == SG_REF_GROUP && v < guid_of_.size()) { *type = "workload"; *uid = guid_of_[v]; }
@@ -139,13 +149,78 @@ long GraphDS::WorkloadEdges(std::vector<WorkloadEdge>* out) {
         else if (t == SG_REF_OBIP && v < last_obips_.size()) { *type = "outbound"; *uid = FormatIPv4(last_obips_[v]); }
         else { *type = "unknown"; uid->clear(); }
     };
-    for (size_t i = 0; i < ge.size(); i++) {
-        const sg_group_edge& r = ge[i]; WorkloadEdge& o = (*out)[i];
-        name(r.from_ref, &o.FromType, &o.FromUID); name(r.to_ref, &o.ToType, &o.ToUID);
-        o.Count = r.count; o.ErrCount = r.err_count; o.SumNs = r.sum_ns; o.SumSqUs = r.sumsq_us; o.MaxNs = r.max_ns; o.ScoreQ32 = r.score_q32;
-        o.Edges = r.edges; o.FromNodes = r.from_nodes; o.Alive = r.alive; o.WorstRow = r.worst_row; o.ScoreMax = r.score_max;
+    WorkloadEdge& o = *out;
+    name(r.from_ref, &o.FromType, &o.FromUID); name(r.to_ref, &o.ToType, &o.ToUID);
+    o.Count = r.count; o.ErrCount = r.err_count; o.SumNs = r.sum_ns; o.SumSqUs = r.sumsq_us; o.MaxNs = r.max_ns; o.ScoreQ32 = r.score_q32;
+    o.Edges = r.edges; o.FromNodes = r.from_nodes; o.Alive = r.alive; o.WorstRow = r.worst_row; o.ScoreMax = r.score_max;
+}
+
+// ---- the workload baselines (K15) ----
+int GraphDS::SetWorkloadTrend(const sg_trend_params& p) {
+    if (!api_.set_group_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);                        // (not beside a FlushWindow: the engine refuses it while a flush is open)
+    const int rc = api_.set_group_trend(h_, &p);
+    if (rc == SG_OK) wl_entries_ = p.max_entries ? p.max_entries : std::min<uint64_t>(1ull << 31, 2 * std::max<uint64_t>(max_edges_, 1));
+    return rc;
+}
+int GraphDS::SetWorkloadVanished(const sg_vanished_params& p) {
+    if (!api_.set_group_vanished) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    const int rc = api_.set_group_vanished(h_, &p);
+    if (rc == SG_OK) wl_van_rows_ = p.max_rows ? p.max_rows : (size_t)std::min<uint64_t>(65536, wl_entries_);   // (sg_vanished_params' default)
+    return rc;
+}
+long GraphDS::WorkloadTrends(std::vector<sg_edge_trend>* out) {
+    if (!out || !api_.window_group_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t n = 0;
+    int rc = api_.window_group_trend(h_, nullptr, 0, nullptr, 0, &n);
+    if (rc != SG_OK) return rc;
+    out->assign(n, sg_edge_trend{});
+    if (n && (rc = api_.window_group_trend(h_, nullptr, 0, out->data(), n, &n)) != SG_OK) return rc;
+    return (long)out->size();
+}
+long GraphDS::WorkloadTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadEdge>* out, std::vector<uint32_t>* index) {
+    if (!out || !api_.window_groups_top) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t sel = 0, total = 0;
+    std::vector<sg_group_edge> ge;
+    std::vector<uint32_t> idx;
+    if (k) { ge.resize(k); idx.resize(k); }                          // at most k are selected; k = 0: the count first
+    int rc = api_.window_groups_top(h_, by, k, min_value, ge.data(), idx.data(), ge.size(), &sel, &total);
+    if (rc != SG_OK) return rc;
+    if (!k && sel) {
+        ge.resize(sel); idx.resize(sel);
+        if ((rc = api_.window_groups_top(h_, by, 0, min_value, ge.data(), idx.data(), ge.size(), &sel, &total)) != SG_OK) return rc;
     }
-    return (long)ge.size();
+    const size_t m = std::min(sel, ge.size());
+    ge.resize(m); idx.resize(m);
+    out->assign(m, WorkloadEdge{});
+    {
+        std::lock_guard<std::mutex> g(id_mu_);
+        for (size_t i = 0; i < m; i++) NameWorkloadEdge(ge[i], &(*out)[i]);
+    }
+    if (index) *index = std::move(idx);
+    return (long)m;
+}
+long GraphDS::WorkloadVanished(std::vector<VanishedWorkload>* out) {
+    if (!out || !api_.window_group_vanished) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t n = 0;
+    int rc = api_.window_group_vanished(h_, nullptr, 0, &n);
+    if (rc != SG_OK) return rc;
+    std::vector<sg_edge_vanished> v(std::min(n, wl_van_rows_));        // n counts every vanished entry; the list holds at most max_rows of them
+    if (!v.empty() && (rc = api_.window_group_vanished(h_, v.data(), v.size(), &n)) != SG_OK) return rc;
+    out->clear();
+    std::lock_guard<std::mutex> g(id_mu_);
+    auto uid = [&](uint64_t key) { return (key >> 32) == 0 && key < guid_of_.size() ? guid_of_[(size_t)key] : std::string(); };
+    for (const sg_edge_vanished& r : v) {
+        VanishedWorkload o;
+        o.FromKey = r.from_key; o.ToKey = r.to_key; o.FromUID = uid(r.from_key); o.ToUID = uid(r.to_key);
+        o.LatMean = r.lat_mean; o.LatDev = r.lat_dev; o.ErrMean = r.err_mean; o.ErrDev = r.err_dev; o.N = r.n; o.Last = r.last; o.Row = r.row;
+        out->push_back(o);
+    }
+    return (long)out->size();
 }
 
 // processPod keeps PodIPToPodUid (aggregator/persist.go:55-71); pods without an IP never reach the

@@ -47,6 +47,13 @@ struct SgApi {
     int (*set_groups)(sg_handle, const sg_group_params*) = nullptr;
     int (*group_assign)(sg_handle, const uint32_t*, const uint32_t*, size_t) = nullptr;
     int (*window_groups)(sg_handle, sg_group_edge*, size_t, size_t*) = nullptr;
+    // optional (K15; absent in an older library): each of SetWorkloadTrend, SetWorkloadVanished, WorkloadTrends, WorkloadVanished and
+    // WorkloadTop needs the entry it forwards to
+    int (*set_group_trend)(sg_handle, const sg_trend_params*) = nullptr;
+    int (*window_group_trend)(sg_handle, const uint32_t*, size_t, sg_edge_trend*, size_t, size_t*) = nullptr;
+    int (*set_group_vanished)(sg_handle, const sg_vanished_params*) = nullptr;
+    int (*window_group_vanished)(sg_handle, sg_edge_vanished*, size_t, size_t*) = nullptr;
+    int (*window_groups_top)(sg_handle, uint32_t, uint32_t, float, sg_group_edge*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -64,6 +71,13 @@ struct WorkloadEdge {                  // one edge of a closed window's service 
     uint64_t Count = 0, ErrCount = 0, SumNs = 0, SumSqUs = 0, MaxNs = 0, ScoreQ32 = 0;
     uint32_t Edges = 0, FromNodes = 0, Alive = 0, WorstRow = 0;
     float ScoreMax = 0;
+};
+
+struct VanishedWorkload {              // one vanished workload dependency of a closed window (sg_edge_vanished over workload keys)
+    uint64_t FromKey = 0, ToKey = 0;                   // the workload keys (include/servicegraph.h, "workload baselines")
+    std::string FromUID, ToUID;                        // key type 0 (a workload): the owner's UID; any other key type: empty, the key stands
+    double LatMean = 0, LatDev = 0, ErrMean = 0, ErrDev = 0;
+    uint32_t N = 0, Last = 0, Row = 0;                 // Row: the window's group edge with the key and no request, else 0xFFFFFFFF
 };
 
 class EdgeSink {
@@ -130,6 +144,18 @@ public:
     int SetWorkloadGroups(uint32_t max_groups);
     // the group edges of the last flushed window, group ids resolved back to owner UIDs; < 0 on an engine error
     long WorkloadEdges(std::vector<WorkloadEdge>* out);
+    // The workload baselines (K15), behind SetWorkloadGroups: each group edge against its own past, keyed by workload, so a rollout
+    // (new pods, new ids) keeps the history.  The two switches forward sg_set_group_trend / sg_set_group_vanished (the engine's
+    // return code; SG_EINVAL without the entry).  WorkloadTrends: row k for edge k of WorkloadEdges.  WorkloadTop: the selection
+    // sg_window_groups_top over the last flushed window (`by` = SG_SEL_*), the edges resolved as WorkloadEdges does, their indices
+    // in `index` (may be NULL) — what WorkloadTrends' rows are indexed by.  WorkloadVanished: the window's vanished workload
+    // dependencies, key type 0 resolved back to the owner's UID through the group table SetWorkloadGroups built.  Each returns
+    // the count (WorkloadTop: the selected edges; WorkloadVanished: the rows the list holds), < 0 on an engine error.
+    int SetWorkloadTrend(const sg_trend_params& p);
+    int SetWorkloadVanished(const sg_vanished_params& p);
+    long WorkloadTrends(std::vector<sg_edge_trend>* out);
+    long WorkloadTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadEdge>* out, std::vector<uint32_t>* index);
+    long WorkloadVanished(std::vector<VanishedWorkload>* out);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }
@@ -152,6 +178,8 @@ private:
     // (id_mu_ held) the group of a pod owned by `owner` (kNoId: none); node id -> group in the engine, if it changed
     uint32_t GroupOfOwner(const std::string& owner);
     void AssignGroup(uint32_t id, uint32_t group);
+    // (id_mu_ held) a group edge in the reference's vocabulary: group ids back to owner UIDs, node refs as the rows' are
+    void NameWorkloadEdge(const sg_group_edge& r, WorkloadEdge* o) const;
     int FlushShard(Shard& s);                          // s.mu held
 
     datastore::DataStore* inner_;
@@ -167,6 +195,7 @@ private:
     size_t live_ids_ = 0;
     // the workload groups (under id_mu_): what the owners are is kept whether or not the groups are on
     bool groups_on_ = false; uint32_t max_groups_ = 0;
+    uint64_t wl_entries_ = 0; size_t wl_van_rows_ = 0; // (flush_mu_) the workload baseline's capacity and the rows its vanished list holds, as the engine resolves a 0
     std::unordered_map<std::string, std::string> pod_owner_, rs_owner_;   // pod UID -> OwnerID; ReplicaSet UID -> its Deployment's UID
     std::unordered_map<std::string, uint32_t> gids_; std::vector<std::string> guid_of_;   // owner UID <-> group id, arrival order
     std::vector<uint32_t> node_group_;                 // node id -> the group the engine holds for it

@@ -27,6 +27,7 @@ struct MockEngine {
     uint32_t label_count = 0; uint32_t flushes = 0; uint32_t max_known = 0x3FFFFFFFu;
     uint32_t top_flushes = 0, top_k = 0; float top_min = 0;             // flush_window_top: calls, the last k and min_score
     std::vector<std::array<uint32_t, 2>> group_ops;   // {node id, group} of every sg_group_assign pair; {0xFFFFFFFE, max_groups} of every sg_set_groups
+    std::vector<std::array<uint64_t, 4>> k15_ops;      // {1, shift, warmup, ttl} per sg_set_group_trend, {2, silent_windows, min_seen, max_rows} per sg_set_group_vanished (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_groups_top
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
 };
 #define M_LOCK(h) std::lock_guard<std::mutex> _g(reinterpret_cast<MockEngine*>(h)->mu)
@@ -52,6 +53,41 @@ int m_group_assign(sg_handle h, const uint32_t* ids, const uint32_t* gs, size_t 
     return SG_OK;
 }
 int m_window_groups(sg_handle, sg_group_edge*, size_t, size_t* n) { if (n) *n = 0; return SG_OK; }
+// K15's stand-ins answer with fixed rows, so that what GraphDS makes of them can be checked: four group edges' trend rows
+// (windows_seen = 1 + the group edge's index); two vanished entries — workload 1 -> workload 0 with row 2, and ungrouped KNOWN 7 ->
+// outbound 10.0.0.1 — of three counted; a selection of group edges 3 and 0 of four (workload 1 -> workload 0, workload 0 -> KNOWN 0)
+int m_set_group_trend(sg_handle h, const sg_trend_params* p) {
+    M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k15_ops.push_back({1u, p ? p->shift : ~0ull, p ? p->warmup : ~0ull, p ? p->ttl : ~0ull}); return SG_OK;
+}
+int m_set_group_vanished(sg_handle h, const sg_vanished_params* p) {
+    M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k15_ops.push_back({2u, p ? p->silent_windows : ~0ull, p ? p->min_seen : ~0ull, p ? p->max_rows : ~0ull}); return SG_OK;
+}
+int m_window_group_trend(sg_handle, const uint32_t* idx, size_t n_idx, sg_edge_trend* out, size_t cap, size_t* n) {
+    const size_t N = idx ? n_idx : 4;
+    if (n) *n = N;
+    for (size_t i = 0; out && i < std::min(N, cap); i++) out[i] = sg_edge_trend{0.5f, -0.25f, 2.0f, 1u + (idx ? idx[i] : (uint32_t)i)};
+    return SG_OK;
+}
+int m_window_group_vanished(sg_handle, sg_edge_vanished* out, size_t cap, size_t* n) {
+    if (n) *n = 3;                                                // (one more than max_rows = 2 holds)
+    const sg_edge_vanished v[2] = {{1ull, 0ull, 1000.0, 10.0, 0.0, 0.0, 5u, 7u, 2u, 0u},
+                                   {(1ull << 32) | 7ull, (3ull << 32) | 0x0A000001ull, 2000.0, 20.0, 1.0, 2.0, 6u, 7u, 0xFFFFFFFFu, 0u}};
+    for (size_t i = 0; out && i < std::min<size_t>(2, cap); i++) out[i] = v[i];
+    return SG_OK;
+}
+int m_window_groups_top(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* idx, size_t cap, size_t* n_sel, size_t* n) {
+    M_LOCK(h);
+    uint32_t bits; std::memcpy(&bits, &min_value, 4);
+    reinterpret_cast<MockEngine*>(h)->k15_ops.push_back({3u, by, k, bits});
+    if (n_sel) *n_sel = 2;
+    if (n) *n = 4;
+    sg_group_edge e[2] = {};
+    e[0].from_ref = SG_MAKE_REF(SG_REF_GROUP, 1); e[0].to_ref = SG_MAKE_REF(SG_REF_GROUP, 0); e[0].count = 9; e[0].score_max = 0.75f;
+    e[1].from_ref = SG_MAKE_REF(SG_REF_GROUP, 0); e[1].to_ref = SG_MAKE_REF(SG_REF_KNOWN, 0); e[1].count = 4; e[1].score_max = 0.5f;
+    const uint32_t at[2] = {3u, 0u};
+    for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
+    return SG_OK;
+}
 int m_obips(sg_handle, uint32_t*, size_t, size_t* n) { if (n) *n = 0; return SG_OK; }
 const char* m_err(sg_handle) { return ""; }
 
@@ -136,6 +172,8 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.upsert_service = m_upsert_svc; c->api.delete_service = m_delete_svc; c->api.set_label_count = m_labels; c->api.ingest = m_ingest;
         c->api.flush_window = m_flush; c->api.window_outbound_ips = m_obips; c->api.last_error = m_err; c->api.flush_window_top = m_flush_top;
         c->api.set_groups = m_set_groups; c->api.group_assign = m_group_assign; c->api.window_groups = m_window_groups;
+        c->api.set_group_trend = m_set_group_trend; c->api.window_group_trend = m_window_group_trend; c->api.set_group_vanished = m_set_group_vanished;
+        c->api.window_group_vanished = m_window_group_vanished; c->api.window_groups_top = m_window_groups_top;
     }
     if (c->api.create(cfg, &c->h) != SG_OK) return nullptr;        // no usable GPU => no GraphDS: there is no CPU fallback
     c->ds = std::make_unique<GraphDS>(&c->inner, c->api, c->h, &c->sink, cfg ? (size_t)cfg->max_edges : 1024, batch ? batch : 4096,
@@ -170,6 +208,53 @@ long sgh_graphds_workload_edges(void* g, sgh_workload_edge* out, size_t cap) {
         std::strncpy(o.from_uid, r.FromUID.c_str(), sizeof o.from_uid - 1); std::strncpy(o.to_uid, r.ToUID.c_str(), sizeof o.to_uid - 1);
         o.count = r.Count; o.err_count = r.ErrCount; o.sum_ns = r.SumNs; o.sumsq_us = r.SumSqUs; o.max_ns = r.MaxNs; o.score_q32 = r.ScoreQ32;
         o.edges = r.Edges; o.from_nodes = r.FromNodes; o.alive = r.Alive; o.worst_row = r.WorstRow; o.score_max = r.ScoreMax;
+    }
+    return n;
+}
+// the workload baselines (K15): the two switches (a parameter 0 = its default), the last flushed window's group trend rows (as
+// sg_edge_trend), a selection over its group edges and its vanished workload dependencies
+int sgh_graphds_set_workload_trend(void* g, uint32_t shift, uint32_t warmup, uint32_t ttl, uint64_t max_entries) {
+    sg_trend_params p{}; p.struct_size = sizeof p; p.shift = shift; p.warmup = warmup; p.ttl = ttl; p.max_entries = max_entries;
+    return static_cast<HostCtx*>(g)->ds->SetWorkloadTrend(p);
+}
+int sgh_graphds_set_workload_vanished(void* g, uint32_t silent_windows, uint32_t min_seen, uint32_t max_rows) {
+    sg_vanished_params p{}; p.struct_size = sizeof p; p.silent_windows = silent_windows; p.min_seen = min_seen; p.max_rows = max_rows;
+    return static_cast<HostCtx*>(g)->ds->SetWorkloadVanished(p);
+}
+long sgh_graphds_workload_trends(void* g, sg_edge_trend* out, size_t cap) {
+    std::vector<sg_edge_trend> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadTrends(&v);
+    if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_edge_trend));
+    return n;
+}
+static void put_workload_edge(const WorkloadEdge& r, sgh_workload_edge* o) {
+    std::memset(o, 0, sizeof *o);
+    std::strncpy(o->from_type, r.FromType.c_str(), sizeof o->from_type - 1); std::strncpy(o->to_type, r.ToType.c_str(), sizeof o->to_type - 1);
+    std::strncpy(o->from_uid, r.FromUID.c_str(), sizeof o->from_uid - 1); std::strncpy(o->to_uid, r.ToUID.c_str(), sizeof o->to_uid - 1);
+    o->count = r.Count; o->err_count = r.ErrCount; o->sum_ns = r.SumNs; o->sumsq_us = r.SumSqUs; o->max_ns = r.MaxNs; o->score_q32 = r.ScoreQ32;
+    o->edges = r.Edges; o->from_nodes = r.FromNodes; o->alive = r.Alive; o->worst_row = r.WorstRow; o->score_max = r.ScoreMax;
+}
+long sgh_graphds_workload_top(void* g, uint32_t by, uint32_t k, float min_value, sgh_workload_edge* out, uint32_t* index, size_t cap) {
+    std::vector<WorkloadEdge> v; std::vector<uint32_t> idx;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadTop(by, k, min_value, &v, &idx);
+    if (n < 0) return n;
+    for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_edge(v[i], out + i); if (index) index[i] = idx[i]; }
+    return n;
+}
+struct sgh_workload_vanished {
+    uint64_t from_key, to_key; char from_uid[160], to_uid[160];
+    double lat_mean, lat_dev, err_mean, err_dev; uint32_t n, last, row, pad;
+};
+long sgh_graphds_workload_vanished(void* g, sgh_workload_vanished* out, size_t cap) {
+    std::vector<VanishedWorkload> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadVanished(&v);
+    if (n < 0) return n;
+    for (size_t i = 0; out && i < std::min(cap, v.size()); i++) {
+        const VanishedWorkload& r = v[i]; sgh_workload_vanished& o = out[i];
+        std::memset(&o, 0, sizeof o);
+        o.from_key = r.FromKey; o.to_key = r.ToKey;
+        std::strncpy(o.from_uid, r.FromUID.c_str(), sizeof o.from_uid - 1); std::strncpy(o.to_uid, r.ToUID.c_str(), sizeof o.to_uid - 1);
+        o.lat_mean = r.LatMean; o.lat_dev = r.LatDev; o.err_mean = r.ErrMean; o.err_dev = r.ErrDev; o.n = r.N; o.last = r.Last; o.row = r.Row;
     }
     return n;
 }
@@ -443,6 +528,14 @@ void sgh_mock_flushes(void* g, uint32_t out[3], float* min_score) {
     if (!c->mock) return;
     auto* m = reinterpret_cast<MockEngine*>(c->h); std::lock_guard<std::mutex> l(m->mu);
     out[0] = m->flushes; out[1] = m->top_flushes; out[2] = m->top_k; if (min_score) *min_score = m->top_min;
+}
+size_t sgh_mock_k15_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k15_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k15_ops[i].data(), 32);
+    return m->k15_ops.size();
 }
 size_t sgh_mock_group_ops(void* g, uint32_t* out2, size_t cap) {
     auto* c = static_cast<HostCtx*>(g); if (!c->mock) return 0;

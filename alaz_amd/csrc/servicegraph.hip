@@ -31,6 +31,7 @@
 #include "sg_incident.h"
 #include "sg_track.h"
 #include "sg_group.h"
+#include "sg_group_trend.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -209,6 +210,13 @@ struct sg_engine {
                     u32* blk = nullptr; u32* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_group_edge*> rows; std::vector<u64*> count;
                     std::vector<u32*> row_group, perm; std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false;
                     std::vector<u32> h_map; u32* h_up = nullptr; hipEvent_t up_ev = nullptr; bool up_pending = false; u32 dirty_lo = 0, dirty_hi = 0; } grp;
+    // K15, the workload baselines (sg_group_trend.h): a Baseline over the group edges (sg_plan.hpp plan_group_trend) and its vanished
+    // list, allocated at sg_set_group_trend / sg_set_group_vanished, freed with the groups
+    Baseline<sg_edge_trend> gtrend;
+    Vanished gvanished;
+    // selection over group edges (K7 over K14's rows): plan_group_select's block, allocated at the first one — K7's scratch over
+    // max_edges keys, the counter block k15_keys fills, an index array and the host form's staging of SG_SELECT_MAX_K group edges
+    struct GSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; sg_group_edge* stage = nullptr; char* mem = nullptr; u64 stage_rows = 0; } gsel;
 };
 
 namespace {
@@ -726,6 +734,13 @@ int enqueue_baseline(sg_engine* e, sg_engine::Baseline<Row>& t, hipStream_t s, F
     t.w++;
     return SG_OK;
 }
+// VanArgs of list v for the window in slot `slot`: the slot's list and count, the shared counts, the parameters
+VanArgs vanished_args(const sg_engine::Vanished& v, int slot) {
+    VanArgs va{};
+    va.out = v.rows[slot]; va.count = v.count[slot]; va.th = v.th; va.blk = v.blk;
+    va.max_rows = v.plan.rows; va.silent = v.p.silent_windows; va.min_seen = v.p.min_seen;
+    return va;
+}
 // enqueue window w's update on stream s; the window's trend rows go to the slot's buffer
 int launch_trend(sg_engine* e, hipStream_t s) {
     sg_engine::WinSlot& w = work(e);
@@ -735,9 +750,7 @@ int launch_trend(sg_engine* e, hipStream_t s) {
     sg_engine::Vanished& v = e->vanished;
     return enqueue_baseline(e, t, s, [&] {
         if (v.on) {                                                   // the same three launches with the vanished count
-            VanArgs va{};
-            va.out = v.rows[e->cur]; va.count = v.count[e->cur]; va.th = v.th; va.blk = v.blk;
-            va.max_rows = v.plan.rows; va.silent = v.p.silent_windows; va.min_seen = v.p.min_seen;
+            const VanArgs va = vanished_args(v, e->cur);
             hipLaunchKernelGGL(k8_count_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
             hipLaunchKernelGGL(k8_scan_v, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs, va);
             hipLaunchKernelGGL(k8_write_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
@@ -946,7 +959,47 @@ int launch_groups(sg_engine* e, hipStream_t s) {
     x.valid[e->cur] = 1;
     return SG_OK;
 }
+// ---- K15, the workload baselines (engine lock held) ------------------------------------------------------------------------------
+static_assert(sizeof(sg_edge_trend) == 16 && sizeof(sg_group_edge) == 80 && offsetof(sg_group_edge, count) == 0 && offsetof(sg_group_edge, err_count) == 8 &&
+              offsetof(sg_group_edge, sum_ns) == 16 && offsetof(sg_group_edge, from_ref) == 48 && offsetof(sg_group_edge, to_ref) == 52 &&
+              offsetof(sg_group_edge, score_max) == 76, "k15_sample and k15_keys read sg_group_edge by word");
+// enqueue the workload baseline's update by the window in slot cur on stream s (behind its contraction, on the same stream); the
+// window's group trend rows go to the slot's buffer, with the list on also its vanished workload dependencies
+int launch_group_trend(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
+    sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
+    sg_engine::Vanished& v = e->gvanished;
+    GroupTrendArgs a{};
+    a.t = baseline_args(w, t);
+    a.groups = e->grp.rows[e->cur]; a.count = e->grp.count[e->cur]; a.max_edges = std::max<u64>(e->cfg.max_edges, 1); a.out = t.rows[e->cur];
+    if (const int rc = enqueue_baseline(e, t, s, [&] {
+            if (v.on) {
+                const VanArgs va = vanished_args(v, e->cur);
+                hipLaunchKernelGGL(k15_count_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
+                hipLaunchKernelGGL(k8_scan_v, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs, va);
+                hipLaunchKernelGGL(k15_write_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
+                v.valid[e->cur] = 1;
+            } else {
+                hipLaunchKernelGGL(k15_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+                hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs);
+                hipLaunchKernelGGL(k15_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            }
+        })) return rc;
+    t.valid[e->cur] = 1;
+    return SG_OK;
+}
+// a vanished list off (K8's or K15's): it has no event of its own, its baseline's — not free_stage
+void free_list(sg_engine::Vanished& v) {
+    if (v.mem) { hipDeviceSynchronize(); hipFree(v.mem); }
+    v = sg_engine::Vanished{};
+}
+void free_group_trend(sg_engine* e) {
+    free_list(e->gvanished);
+    free_baseline(e->gtrend);
+}
+
 void free_groups(sg_engine* e) {
+    free_group_trend(e);
     sg_engine::Groups& x = e->grp;
     if (x.mem) hipDeviceSynchronize();                                // (an upload may still read h_up)
     if (x.h_up) hipHostFree(x.h_up);
@@ -966,11 +1019,7 @@ void free_nodes(sg_engine* e) {
     free_stage(e->nodes);
 }
 
-void free_vanished(sg_engine* e) {
-    sg_engine::Vanished& v = e->vanished;                             // (no event of its own, the trend's: not free_stage)
-    if (v.mem) { hipDeviceSynchronize(); hipFree(v.mem); }
-    v = sg_engine::Vanished{};
-}
+void free_vanished(sg_engine* e) { free_list(e->vanished); }
 
 void free_trend(sg_engine* e) {
     free_vanished(e);
@@ -1003,7 +1052,10 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
         if (e->trk.on) { if (const int rc = launch_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
     }
-    if (e->grp.on) return launch_groups(e, s);                       // K14 behind K5: the rows and the window counters only, whatever else is on
+    if (e->grp.on) {                                                 // K14 behind K5: the rows and the window counters only, whatever else is on
+        if (const int rc = launch_groups(e, s)) return rc;
+        if (e->gtrend.on) return launch_group_trend(e, s);           // K15 behind K14: the group edges, their count, the outbound IPs
+    }
     return SG_OK;
 }
 
@@ -1254,6 +1306,76 @@ int node_top_host(sg_engine* e, L launch, sg_node_out* out, sg_node_rank* rank_o
     return SG_OK;
 }
 
+// ---- selection over group edges (engine lock held) --------------------------------------------------------------------------------
+// the block at the first one (plan_group_select: K7's scratch over max_edges keys, the counter block, indices, the row staging)
+int gsel_reserve(sg_engine* e) {
+    sg_engine::GSel& s = e->gsel;
+    if (s.keys) return SG_OK;
+    const sgplan::GroupSelPlan P = sgplan::plan_group_select(e->cfg.max_edges, sizeof(e->h_ctr));
+    s.plan = P.sel;
+    HIP_TRY(e, hipMalloc((void**)&s.mem, P.total_bytes));
+    HIP_TRY(e, hipMemset(s.mem, 0, P.total_bytes));
+    s.stage = at<sg_group_edge>(s.mem, P.stage_off); s.stage_rows = P.stage_rows;
+    s.ctr = at<u64>(s.mem, P.ctr_off);
+    s.idx = at<u32>(s.mem, P.idx_off);
+    return sel_init(e, s, s.mem + P.sel_off);
+}
+// enqueue a selection over the group edges of slot `slot` on stream st: indices to d_index (NULL: the scratch's), group edges to
+// d_out (may be NULL), the count to d_n; behind that window's contraction, for a trend key its baseline update, and the previous
+// selection over group edges (events).  k15_keys, K7's passes with their row copies off, k_gather_sel.
+int launch_group_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_group_edge* d_out, u32* d_index,
+                        u64 cap, u64* d_n) {
+    sg_engine::GSel& s = e->gsel;
+    const u32 wgs = s.plan.wgs;
+    const u64 ME = std::max<u64>(e->cfg.max_edges, 1);
+    SelArgs a{};
+    a.rows = nullptr; a.ctr = s.ctr; a.max_edges = ME; a.k = k; a.min_score = min_value;
+    sel_scratch_args(a, s);
+    a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, ME); a.n_out = d_n;
+    if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
+    if (e->grp.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->grp.ev, 0));
+    if (by != SG_SEL_SCORE && e->gtrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->gtrend.ev, 0));
+    const sg_group_edge* groups = e->grp.rows[slot];
+    const sg_edge_trend* tr = by != SG_SEL_SCORE ? e->gtrend.rows[slot] : nullptr;
+    hipLaunchKernelGGL(k15_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, groups, (const u64*)e->grp.count[slot], tr, by, s.ctr);
+    enqueue_k7_select(st, a, k, wgs, ME);
+    const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, ME) : ME);
+    const dim3 grid((unsigned)std::max<u64>(1, std::min<u64>((m + 255) / 256, 1024)));
+    if (d_out) hipLaunchKernelGGL(k_gather_sel<sg_group_edge>, grid, dim3(256), 0, st, groups, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(s.ev, st));
+    s.pending = true;
+    return SG_OK;
+}
+// the host form over the last read window (sg_window_groups_top): the indices are selected on the read stream, then the selected
+// group edges are gathered through the staging, in pieces when there are more of them than it holds (k = 0)
+int group_top_host(sg_engine* e, u32 by, u32 k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap, size_t* n_selected,
+                   size_t* n_groups) {
+    if (const int rc = gsel_reserve(e)) return rc;
+    sg_engine::GSel& s = e->gsel;
+    const u64 ME = std::max<u64>(e->cfg.max_edges, 1);
+    if (const int rc = launch_group_select(e, e->rd_stream, e->cur, by, k, min_value, nullptr, nullptr, std::min<u64>(cap, ME), s.n)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipMemcpyAsync(&cnt, e->grp.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    const u64 m = *s.h_n;
+    const size_t take = (size_t)std::min<u64>(m, std::min<u64>(cap, ME));
+    if (group_index && take) HIP_TRY(e, hipMemcpyAsync(group_index, s.idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
+    for (size_t o = 0; out && o < take; o += (size_t)s.stage_rows) {
+        const size_t piece = std::min<size_t>((size_t)s.stage_rows, take - o);
+        hipLaunchKernelGGL(k_gather<sg_group_edge>, dim3((unsigned)((piece + 255) / 256)), dim3(256), 0, e->rd_stream,
+                           (const sg_group_edge*)e->grp.rows[e->cur], (const u32*)(s.idx + o), (u64)piece, s.stage);
+        HIP_TRY(e, hipGetLastError());
+        HIP_TRY(e, hipMemcpyAsync(out + o, s.stage, piece * sizeof(sg_group_edge), hipMemcpyDeviceToHost, e->rd_stream));
+        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));               // (the next piece overwrites the staging)
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    if (n_selected) *n_selected = (size_t)m;
+    if (n_groups) *n_groups = (size_t)cnt;
+    return SG_OK;
+}
+
 // ---- the baselines' and the per-window buffers' shared host code (engine lock held) -----------------------------------------
 // one block of `bytes` for sg_set_*, zeroed; on a failing hipMalloc release() runs and e->err names `call`
 template <class F>
@@ -1296,6 +1418,8 @@ constexpr StageWords kRankWords{"the ranking is off (sg_set_rank)", "the ranking
 constexpr StageWords kIncidentsWords{"the incidents are off (sg_set_incidents)", "the incidents were off"};
 constexpr StageWords kTracksWords{"tracking is off (sg_set_tracks)", "tracking was off"};
 constexpr StageWords kGroupsWords{"the groups are off (sg_set_groups)", "the groups were off"};
+constexpr StageWords kGroupTrendWords{"the group trend is off (sg_set_group_trend)", "the group trend was off"};
+constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
 // a host read of stage x's rows of the last read window (slot cur): the stage on, no flush open, the window closed with the stage
 // on; then its kernels done
 template <class X>
@@ -1393,6 +1517,36 @@ int baseline_stats(sg_engine* e, const sg_engine::Baseline<Row>& t, sg_trend_sta
     out->windows = ctl[K8C_WINDOWS]; out->entries = ctl[K8C_B0 + (t.w & 1u)];
     out->inserted = ctl[K8C_INSERTED]; out->expired = ctl[K8C_EXPIRED]; out->dropped = ctl[K8C_DROPPED];
     return SG_OK;
+}
+// switch vanished list v on (v freed) over the baseline planned as tp: parameters r, one block (plan_vanished's layout: the shared
+// counts, every slot's list and count)
+template <class F>
+int list_on(sg_engine* e, sg_engine::Vanished& v, const sgplan::TrendPlan& tp, const sg_vanished_params& r, const char* call, F release) {
+    const u32 slots = (u32)e->slots.size();
+    v.p = r;
+    v.plan = sgplan::plan_vanished(tp, slots, r);
+    const sgplan::VanishedPlan& P = v.plan;
+    if (const int rc = alloc_block(e, &v.mem, P.total_bytes, call, release)) return rc;
+    v.th = at<u32>(v.mem, P.thread_off);
+    v.blk = at<u32>(v.mem, P.blk_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = v.mem + P.slot.off + k * P.slot.bytes;
+        v.rows.push_back(at<sg_edge_vanished>(s, P.slot_list)); v.count.push_back(at<u64>(s, P.slot_count));
+    }
+    v.valid.assign(slots, 0);
+    v.on = true;
+    return SG_OK;
+}
+// the list of the last read window (slot cur): stage_ready's checks and texts, but the event is the baseline's, whose launches
+// write the list; the count may exceed the rows the list holds
+template <class Row>
+int list_read(sg_engine* e, const sg_engine::Vanished& v, const sg_engine::Baseline<Row>& t, const char* call, const StageWords& what,
+              sg_edge_vanished* out, size_t cap, size_t* n) {
+    if (!v.on) { e->err = std::string(call) + ": " + what.off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (!v.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while " + what.was; return SG_ESTATE; }
+    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    return copy_counted(e, v.count[e->cur], v.rows[e->cur], sizeof(sg_edge_vanished), out, std::min<size_t>(cap, v.plan.rows), n);
 }
 }  // namespace
 
@@ -1615,6 +1769,9 @@ int sg_destroy(sg_handle e) {
     if (e->nsel.mem) hipFree(e->nsel.mem);
     if (e->nsel.h_n) hipHostFree(e->nsel.h_n);
     if (e->nsel.ev) hipEventDestroy(e->nsel.ev);
+    if (e->gsel.mem) hipFree(e->gsel.mem);
+    if (e->gsel.h_n) hipHostFree(e->gsel.h_n);
+    if (e->gsel.ev) hipEventDestroy(e->gsel.ev);
     for (auto& r : e->trecs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto v : e->ev_pool) hipEventDestroy(v);
     if (e->tab_ev) hipEventDestroy(e->tab_ev);
@@ -2231,31 +2388,12 @@ int sg_set_vanished(sg_handle e, const sg_vanished_params* p) {
     if (p && sgplan::check_vanished(*p, e->trend.p, &r)) { e->err = "sg_set_vanished: bad parameters"; return SG_EINVAL; }
     free_vanished(e);
     if (!p) return SG_OK;
-    sg_engine::Vanished& v = e->vanished;
-    const u32 slots = (u32)e->slots.size();
-    v.p = r;
-    v.plan = sgplan::plan_vanished(e->trend.plan, slots, r);
-    const sgplan::VanishedPlan& P = v.plan;
-    if (const int rc = alloc_block(e, &v.mem, P.total_bytes, "sg_set_vanished", [e] { free_vanished(e); })) return rc;
-    v.th = at<u32>(v.mem, P.thread_off);
-    v.blk = at<u32>(v.mem, P.blk_off);
-    for (u32 k = 0; k < slots; k++) {
-        char* s = v.mem + P.slot.off + k * P.slot.bytes;
-        v.rows.push_back(at<sg_edge_vanished>(s, P.slot_list)); v.count.push_back(at<u64>(s, P.slot_count));
-    }
-    v.valid.assign(slots, 0);
-    v.on = true;
-    return SG_OK;
+    return list_on(e, e->vanished, e->trend.plan, r, "sg_set_vanished", [e] { free_vanished(e); });
 }
 int sg_window_vanished(sg_handle e, sg_edge_vanished* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Vanished& v = e->vanished;
-    if (!v.on) { e->err = "sg_window_vanished: the vanished list is off (sg_set_vanished)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_window_vanished while a flush is open"; return SG_ESTATE; }
-    if (!v.valid[e->cur]) { e->err = "sg_window_vanished: the last read window was closed while the vanished list was off"; return SG_ESTATE; }
-    if (e->trend.pending) HIP_TRY(e, hipEventSynchronize(e->trend.ev));   // (not stage_ready: the list is written by the trend's launches, the event is theirs)
-    return copy_counted(e, v.count[e->cur], v.rows[e->cur], sizeof(sg_edge_vanished), out, std::min<size_t>(cap, v.plan.rows), n);   // (the count may exceed the rows the list holds)
+    return list_read(e, e->vanished, e->trend, "sg_window_vanished", kVanishedWords, out, cap, n);
 }
 int sg_window_vanished_buffer(sg_handle e, void** d_rows, void** d_count) {
     if (!e || !d_rows || !d_count) return SG_EINVAL;
@@ -2610,6 +2748,108 @@ int sg_window_groups_buffer(sg_handle e, void** d_edges, void** d_count, void** 
     if (const int rc = stage_slot(e, x, "sg_window_groups_buffer", kGroupsWords, &slot)) return rc;
     *d_edges = x.rows[slot]; *d_count = x.count[slot]; *d_row_group = x.row_group[slot]; *d_perm = x.perm[slot];
     return SG_OK;
+}
+
+// ---- K15, the workload baselines -----------------------------------------------------------------------------------------------
+int sg_set_group_trend(sg_handle e, const sg_trend_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->grp.on) { e->err = "sg_set_group_trend: the groups are off (sg_set_groups)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_group_trend while a flush is open"; return SG_ESTATE; }
+    sg_trend_params r{};
+    if (p && sgplan::check_group_trend(*p, e->cfg.max_edges, &r)) { e->err = "sg_set_group_trend: bad parameters"; return SG_EINVAL; }
+    free_group_trend(e);
+    if (!p) return SG_OK;
+    sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
+    const u32 slots = (u32)e->slots.size();
+    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_trend(e->cfg.max_edges, slots, r), "sg_set_group_trend", [e] { free_group_trend(e); })) return rc;
+    t.valid.assign(slots, 0);
+    return SG_OK;
+}
+int sg_window_group_trend(sg_handle e, const uint32_t* group_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
+    if (const int rc = stage_ready(e, t, "sg_window_group_trend", kGroupTrendWords)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->grp.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    return baseline_rows(e, t, (size_t)cnt, group_index, n_index, out, cap, n, "sg_window_group_trend: a group index beyond the window's group edges");
+}
+int sg_window_group_trend_buffer(sg_handle e, void** d_trend) {
+    if (!e || !d_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
+    int slot;
+    if (const int rc = stage_slot(e, t, "sg_window_group_trend_buffer", kGroupTrendWords, &slot)) return rc;
+    *d_trend = t.rows[slot];
+    return SG_OK;
+}
+int sg_group_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->gtrend.on) { e->err = "sg_group_trend_entries: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
+    return baseline_entries(e, e->gtrend, out, cap, n);
+}
+int sg_group_trend_stats_get(sg_handle e, sg_trend_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->gtrend.on) { e->err = "sg_group_trend_stats_get: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
+    return baseline_stats(e, e->gtrend, out);
+}
+int sg_set_group_vanished(sg_handle e, const sg_vanished_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->gtrend.on) { e->err = "sg_set_group_vanished: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_group_vanished while a flush is open"; return SG_ESTATE; }
+    sg_vanished_params r{};
+    if (p && sgplan::check_vanished(*p, e->gtrend.p, &r)) { e->err = "sg_set_group_vanished: bad parameters"; return SG_EINVAL; }
+    free_list(e->gvanished);
+    if (!p) return SG_OK;
+    return list_on(e, e->gvanished, e->gtrend.plan, r, "sg_set_group_vanished", [e] { free_list(e->gvanished); });
+}
+int sg_window_group_vanished(sg_handle e, sg_edge_vanished* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return list_read(e, e->gvanished, e->gtrend, "sg_window_group_vanished", kGroupVanishedWords, out, cap, n);
+}
+int sg_window_group_vanished_buffer(sg_handle e, void** d_rows, void** d_count) {
+    if (!e || !d_rows || !d_count) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Vanished& v = e->gvanished;
+    int slot;
+    if (const int rc = stage_slot(e, v, "sg_window_group_vanished_buffer", kGroupVanishedWords, &slot)) return rc;
+    *d_rows = v.rows[slot]; *d_count = v.count[slot];
+    return SG_OK;
+}
+
+// ---- selection over group edges -------------------------------------------------------------------------------------------------
+namespace {
+// by > 3: SG_EINVAL; the groups off, or a trend key with the group trend off: SG_ESTATE; then the window in `slot` must have them
+int check_gsel(sg_engine* e, u32 by, int slot) {
+    if (by > SG_SEL_NEW) { e->err = "group selection: unknown key (by > SG_SEL_NEW)"; return SG_EINVAL; }
+    if (!e->grp.on) { e->err = "group selection: the groups are off (sg_set_groups)"; return SG_ESTATE; }
+    if (by != SG_SEL_SCORE && !e->gtrend.on) { e->err = "group selection by a trend key: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
+    if (!e->grp.valid[slot]) { e->err = "group selection: the window was closed while the groups were off"; return SG_ESTATE; }
+    if (by != SG_SEL_SCORE && !e->gtrend.valid[slot]) { e->err = "group selection: the window was closed while the group trend was off"; return SG_ESTATE; }
+    return SG_OK;
+}
+}  // namespace
+int sg_window_groups_top(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap,
+                         size_t* n_selected, size_t* n_groups) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int rc = check_gsel(e, by, e->cur)) return rc;
+    if (e->closing || e->flush_open) { e->err = "sg_window_groups_top while a flush is open"; return SG_ESTATE; }
+    return group_top_host(e, by, k, min_value, out, group_index, cap, n_selected, n_groups);
+}
+int sg_window_groups_select(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_group_edge* d_out, uint32_t* d_index, size_t cap,
+                            uint64_t* d_n, void* stream) {
+    if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int slot = ran_slot(e);
+    if (const int rc = check_gsel(e, by, slot)) return rc;
+    if (const int rc = gsel_reserve(e)) return rc;
+    return launch_group_select(e, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // ---- K13, the tracks ---------------------------------------------------------------------------------------------------------------

@@ -1016,6 +1016,53 @@ inline GroupPlan plan_groups(u64 max_edges, u32 max_known, u32 ncap, u32 max_gro
     return r;
 }
 
+// K15, the workload baselines (sg_group_trend.h): K8's parameters and memory over the group edges — sg_set_group_trend allocates
+// it, never sg_create or sg_set_groups.  A window has at most max_edges group edges, one sample each; max_entries defaults to K8's
+// 2 x max_edges.  The grid is K8's rule over B + max_edges merged elements; the vanished list is plan_vanished over this plan.
+inline int check_group_trend(const sg_trend_params& p, u64 max_edges, sg_trend_params* out) {
+    if (p.struct_size != sizeof(sg_trend_params)) return SG_EINVAL;
+    sg_trend_params q = p;
+    if (!q.max_entries) q.max_entries = std::min<u64>(kTrendMaxEntries, 2 * std::max<u64>(max_edges, 1));
+    return check_trend(q, max_edges, out);
+}
+// K15: one sample per group edge, [max_edges] sg_edge_trend per slot.  GroupTrendPlan names K8's type for the CPU driver
+// tests/micro/group_trend_plan_test.cpp.
+using GroupTrendPlan = TrendPlan;
+inline TrendPlan plan_group_trend(u64 max_edges, u32 slots, const sg_trend_params& p) {
+    return plan_baseline(p, max_edges, std::max<u64>(max_edges, 1) * sizeof(sg_edge_trend), slots);
+}
+// Selection over group edges (K7 over K14's rows): the whole block of the first one — the host form's row staging of
+// SG_SELECT_MAX_K group edges (a longer selection is gathered in pieces through it), the counter block k15_keys fills
+// (counter_bytes: the engine's), an index array over max_edges, then K7's scratch over max_edges keys
+struct GroupSelPlan {
+    SelPlan sel;
+    u64 stage_rows = 0;           // SG_SELECT_MAX_K
+    u64 stage_bytes = 0;          // [stage_rows] sg_group_edge
+    u64 ctr_bytes = 0;            // the counter block
+    u64 idx_bytes = 0;            // [max_edges] u32
+    u64 sel_bytes = 0;            // sel.scratch_bytes
+    u64 stage_off = 0, ctr_off = 0, idx_off = 0, sel_off = 0;
+    u64 total_bytes = 0;          // all of it, each piece 256-byte aligned
+    std::vector<Piece> layout;
+};
+inline GroupSelPlan plan_group_select(u64 max_edges, u64 counter_bytes) {
+    GroupSelPlan n;
+    const u64 ME = std::max<u64>(max_edges, 1);
+    n.sel = plan_select(ME, true);
+    n.stage_rows = SG_SELECT_MAX_K;
+    n.stage_bytes = trend_align(n.stage_rows * kGrpEdgeBytes);
+    n.ctr_bytes = trend_align(counter_bytes);
+    n.idx_bytes = trend_align(ME * 4);
+    n.sel_bytes = trend_align(n.sel.scratch_bytes);
+    Block b;
+    n.stage_off = b.take("stage", n.stage_bytes);
+    n.ctr_off = b.take("ctr", n.ctr_bytes);
+    n.idx_off = b.take("idx", n.idx_bytes);
+    n.sel_off = b.take("sel", n.sel_bytes);
+    n.total_bytes = b.end; n.layout = std::move(b.pieces);
+    return n;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

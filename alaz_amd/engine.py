@@ -247,6 +247,13 @@ def _signatures() -> dict:
         "sg_window_groups": (I, [H, P, sz, Psz]), "sg_window_row_group": (I, [H, P, sz, P, sz, Psz]),
         "sg_window_group_perm": (I, [H, P, sz, Psz]),
         "sg_window_groups_buffer": (I, [H] + [PP] * 4),
+        "sg_set_group_trend": (I, [H, P]), "sg_window_group_trend": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_trend_buffer": (I, [H, PP]), "sg_group_trend_entries": (I, [H, P, sz, Psz]),
+        "sg_group_trend_stats_get": (I, [H, P]),
+        "sg_set_group_vanished": (I, [H, P]), "sg_window_group_vanished": (I, [H, P, sz, Psz]),
+        "sg_window_group_vanished_buffer": (I, [H, PP, PP]),
+        "sg_window_groups_top": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_groups_select": (I, [H, u32, u32, f32, P, P, sz, P, P]),
     }
 
 
@@ -283,6 +290,9 @@ _STAGES = dict(
     tracks=_Stage("sg_set_tracks", SgTrackParams, TRACK_DEFAULTS, "set_tracks(None) switches tracking off", "track"),
     groups=_Stage("sg_set_groups", SgGroupParams, GROUP_DEFAULTS, "set_groups(None) switches the groups off", "group",
                   dict(reserved=lambda r: (C.c_uint32 * 2)(*((r, 0) if isinstance(r, int) else tuple(r))))),
+    group_trend=_Stage("sg_set_group_trend", SgTrendParams, TREND_DEFAULTS, "set_group_trend(None) switches the group trend off", "group trend"),
+    group_vanished=_Stage("sg_set_group_vanished", SgVanishedParams, VANISHED_DEFAULTS, "set_group_vanished(None) switches the list off",
+                          "group vanished"),
 )
 
 _lib = None
@@ -798,6 +808,65 @@ class ServiceGraph:
         """(device pointer of the sg_group_edge rows, of their u64 count, of the u32 row_group, of the u32 perm) of the window
         window_run closed last (sg_window_groups_buffer)"""
         return self._pointers(self._l.sg_window_groups_buffer, 4)
+
+    # ---- workload baselines (K15): each group edge against its own past; they survive a rollout, the pod-level ones do not ----
+    def set_group_trend(self, params: Optional[dict] = (), **kw):
+        """Switch the per-workload-edge baseline on (sg_set_group_trend; the parameters of set_trend; needs the groups on;
+        (re)enabling starts an empty baseline) or off: set_group_trend(None).  Any set_groups call switches it off."""
+        v = self._set_stage("group_trend", params, kw)
+        if v is not None:
+            self._gtrend_entries = v["max_entries"] or min(1 << 31, 2 * max(self.max_edges, 1))   # the baseline's capacity
+
+    def window_group_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """TREND_DTYPE rows of the last read window (sg_window_group_trend), row k for group edge k of window_groups(); or the rows
+        of the group edges at `index` (window_groups_top's indices; only those cross PCIe)."""
+        return self._window_rows(self._l.sg_window_group_trend, TREND_DTYPE, index)
+
+    def window_group_trend_buffer(self) -> int:
+        """device pointer of the group trend rows of the window window_run closed last (sg_window_group_trend_buffer)"""
+        return self._pointers(self._l.sg_window_group_trend_buffer, 1)[0]
+
+    def group_trend_entries(self) -> np.ndarray:
+        """the workload baseline in key order, TREND_ENTRY_DTYPE with workload keys (sg_group_trend_entries)"""
+        return self._counted(self._l.sg_group_trend_entries, TREND_ENTRY_DTYPE)
+
+    def group_trend_stats(self) -> SgTrendStats:
+        return self._stats(self._l.sg_group_trend_stats_get, SgTrendStats)
+
+    def set_group_vanished(self, params: Optional[dict] = (), **kw):
+        """Switch the list of vanished workload dependencies on (sg_set_group_vanished; the parameters of set_vanished; needs the
+        group trend on) or off: set_group_vanished(None).  Any set_group_trend call switches it off."""
+        v = self._set_stage("group_vanished", params, kw)
+        if v is not None:
+            self._gvan_rows = v["max_rows"] or min(65536, self._gtrend_entries)   # (the rows a window's list holds at most)
+
+    def window_group_vanished(self, with_count: bool = False):
+        """VANISHED_DTYPE list of the last read window (sg_window_group_vanished), ascending by workload key pair; with_count:
+        (list, count of every vanished entry of the window, which may exceed max_rows)."""
+        out = self._counted(self._l.sg_window_group_vanished, VANISHED_DTYPE)  # (room for the count; max_rows of them are written)
+        rows = out[: self._gvan_rows]
+        return (rows, len(out)) if with_count else rows
+
+    def window_group_vanished_buffer(self) -> Tuple[int, int]:
+        """(device pointer of the sg_edge_vanished list, of its u64 count) of the window window_run closed last
+        (sg_window_group_vanished_buffer)"""
+        return self._pointers(self._l.sg_window_group_vanished_buffer, 2)
+
+    def window_groups_top(self, k: int, min_value: float = float("-inf"), by: str = "score", cap: Optional[int] = None):
+        """(group edges, group-edge indices, n_groups) of a selection over the last read window's group edges
+        (sg_window_groups_top): k = 0 every group edge with value >= min_value in group-edge order, else the k highest such,
+        descending, ties by position.  by: a key of SEL_BY (score = score_max).  cap defaults to k (k > 0) or max_edges."""
+        b = self._by(by)
+        cap = (k or self.max_edges) if cap is None else cap
+        return self._top(lambda *a: self._l.sg_window_groups_top(self._h, b, k, min_value, *a), cap, GROUP_EDGE_DTYPE, np.uint32)
+
+    def window_groups_select(self, k: int, min_value: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0,
+                             by: str = "score"):
+        """Select from the group edges of the window window_run closed last into device memory (sg_window_groups_select): d_out
+        [cap] group edges (0 = none), d_index [cap] u32 (0 = none), d_n one u64 = group edges selected; enqueued on `stream` (0 =
+        that window's stream)."""
+        self._ck(self._l.sg_window_groups_select(self._h, self._by(by), k, min_value, d_out or None, d_index or None, cap, d_n,
+                                                 stream or None))
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

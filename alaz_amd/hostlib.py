@@ -32,6 +32,12 @@ class SockInfoC(C.Structure):
     _fields_ = [("pid", C.c_uint32), ("fd", C.c_uint64), ("saddr", C.c_uint32), ("sport", C.c_uint16), ("daddr", C.c_uint32), ("dport", C.c_uint16)]
 
 
+#: sgh_workload_vanished of host_capi.cpp: one vanished workload dependency (GraphDS::WorkloadVanished); a uid is empty unless its
+#: key is a workload's (key type 0)
+WORKLOAD_VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("from_uid", "S160"), ("to_uid", "S160")]
+                                   + [(f, "<f8") for f in ("lat_mean", "lat_dev", "err_mean", "err_dev")]
+                                   + [(f, "<u4") for f in ("n", "last", "row", "pad")])
+
 _lib = None
 
 
@@ -104,6 +110,11 @@ def load() -> C.CDLL:
             "sgh_graphds_persist_replicaset": (C.c_int, [P, C.c_char_p, C.c_char_p, C.c_char_p]),
             "sgh_graphds_set_workload_groups": (C.c_int, [P, u32]), "sgh_graphds_workload_edges": (C.c_long, [P, P, sz]),
             "sgh_mock_group_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_workload_trend": (C.c_int, [P, u32, u32, u32, C.c_uint64]),
+            "sgh_graphds_set_workload_vanished": (C.c_int, [P, u32, u32, u32]),
+            "sgh_graphds_workload_trends": (C.c_long, [P, P, sz]),
+            "sgh_graphds_workload_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]),
+            "sgh_graphds_workload_vanished": (C.c_long, [P, P, sz]), "sgh_mock_k15_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -430,6 +441,50 @@ class GraphDS:
         n = self._l.sgh_mock_group_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 2), dtype=np.uint32)
         self._l.sgh_mock_group_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the workload baselines (K15) ----
+    def set_workload_trend(self, shift: int = 0, warmup: int = 0, ttl: int = 0, max_entries: int = 0) -> int:
+        """GraphDS::SetWorkloadTrend: the per-workload-edge baseline on (a 0 = the parameter's default; rc)"""
+        return self._l.sgh_graphds_set_workload_trend(self._g, shift, warmup, ttl, max_entries)
+
+    def set_workload_vanished(self, silent_windows: int = 0, min_seen: int = 0, max_rows: int = 0) -> int:
+        """GraphDS::SetWorkloadVanished: the list of vanished workload dependencies on (rc)"""
+        return self._l.sgh_graphds_set_workload_vanished(self._g, silent_windows, min_seen, max_rows)
+
+    def _rows(self, what, call, dtype, *lead):
+        """call(g, *lead, NULL, 0) for the count, then the rows"""
+        n = call(self._g, *lead, None, 0)
+        if n < 0:
+            raise RuntimeError(f"{what} failed: {n}")
+        out = np.zeros(max(n, 1), dtype=dtype)
+        call(self._g, *lead, out.ctypes.data, n)
+        return out[:n]
+
+    def workload_trends(self) -> np.ndarray:
+        """GraphDS::WorkloadTrends: the last flushed window's group trend rows (engine.TREND_DTYPE), row k for edge k of workload_edges()"""
+        from .engine import TREND_DTYPE
+        return self._rows("WorkloadTrends", self._l.sgh_graphds_workload_trends, TREND_DTYPE)
+
+    def workload_vanished(self) -> np.ndarray:
+        """GraphDS::WorkloadVanished: the last flushed window's vanished workload dependencies, WORKLOAD_VANISHED_DTYPE"""
+        return self._rows("WorkloadVanished", self._l.sgh_graphds_workload_vanished, WORKLOAD_VANISHED_DTYPE)
+
+    def workload_top(self, by: int, k: int, min_value: float = float("-inf")):
+        """GraphDS::WorkloadTop: (the selected group edges as WORKLOAD_EDGE_DTYPE, their indices) — by = SG_SEL_*"""
+        n = self._l.sgh_graphds_workload_top(self._g, by, k, min_value, None, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadTop failed: {n}")
+        out, idx = np.zeros(max(n, 1), dtype=WORKLOAD_EDGE_DTYPE), np.zeros(max(n, 1), dtype=np.uint32)
+        self._l.sgh_graphds_workload_top(self._g, by, k, min_value, out.ctypes.data, idx.ctypes.data, n)
+        return out[:n], idx[:n]
+
+    def mock_k15_ops(self) -> np.ndarray:
+        """the stand-in engine's K15 calls in order, four u64 each: (1, shift, warmup, ttl) per sg_set_group_trend, (2, silent_windows,
+        min_seen, max_rows) per sg_set_group_vanished, (3, by, k, the bits of min_value) per sg_window_groups_top"""
+        n = self._l.sgh_mock_k15_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k15_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

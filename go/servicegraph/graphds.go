@@ -101,6 +101,10 @@ type GraphDS struct {
 	next    atomic.Uint32
 	flushMu sync.Mutex
 
+	// (flushMu) the workload baseline's capacity and the rows its vanished list holds, as the engine resolves a 0
+	wlEntries uint64
+	wlVanRows int
+
 	maxEdges int     // sg_config.max_edges
 	selOn    bool    // SetSelection (under flushMu): FlushWindow returns the selected rows only
 	selK     uint32
@@ -999,6 +1003,10 @@ func (g *GraphDS) WindowGroupEdges() ([]GroupEdge, error) {
 	if int(n) < len(ges) {
 		ges = ges[:int(n)]
 	}
+	return goGroupEdges(ges), nil
+}
+
+func goGroupEdges(ges []C.sg_group_edge) []GroupEdge {
 	out := make([]GroupEdge, len(ges))
 	for i := range ges {
 		ge, o := &ges[i], &out[i]
@@ -1008,7 +1016,158 @@ func (g *GraphDS) WindowGroupEdges() ([]GroupEdge, error) {
 		o.Edges, o.FromNodes, o.First, o.Alive = uint32(ge.edges), uint32(ge.from_nodes), uint32(ge.first), uint32(ge.alive)
 		o.WorstRow, o.ScoreMax = uint32(ge.worst_row), float32(ge.score_max)
 	}
+	return out
+}
+
+// EdgeTrend is one group edge against its own past (sg_edge_trend): the deviations of this window's latency and error share from
+// the workload baseline in units of its mean absolute deviation, the baseline's mean latency, and the windows it has seen.
+type EdgeTrend struct {
+	LatDev, ErrDev, BaseMeanUs float32
+	WindowsSeen                uint32
+}
+
+// VanishedWorkload is one workload dependency that went silent (sg_edge_vanished over workload keys): a key below 2^32 is a group
+// id, any other (1 + ref type) << 32 | value of an ungrouped node.  Row is the window's group edge with the key and no request
+// (open connections only), or 0xFFFFFFFF.
+type VanishedWorkload struct {
+	FromKey, ToKey                    uint64
+	LatMean, LatDev, ErrMean, ErrDev float64
+	N, Last, Row                      uint32
+}
+
+// The keys of WindowWorkloadsTop (SG_SEL_*).
+const (
+	ByScore  = uint32(C.SG_SEL_SCORE)
+	ByLatDev = uint32(C.SG_SEL_LAT_DEV)
+	ByErrDev = uint32(C.SG_SEL_ERR_DEV)
+	ByNew    = uint32(C.SG_SEL_NEW)
+)
+
+// SetWorkloadTrend switches the per-workload-edge baseline on, behind SetGroups (a 0 is the parameter's default: shift 4, warmup 4,
+// ttl 64, maxEntries 2 x max_edges); it starts empty.  The baseline is keyed by workload, so it survives a rollout that gives a
+// Deployment new pods.  Any SetGroups call switches it off.
+func (g *GraphDS) SetWorkloadTrend(shift, warmup, ttl uint32, maxEntries uint64) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var tp C.sg_trend_params
+	tp.struct_size = C.uint32_t(unsafe.Sizeof(tp))
+	tp.shift, tp.warmup, tp.ttl, tp.max_entries = C.uint32_t(shift), C.uint32_t(warmup), C.uint32_t(ttl), C.uint64_t(maxEntries)
+	if rc := C.sg_set_group_trend(g.h, &tp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_group_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if g.wlEntries = maxEntries; maxEntries == 0 {
+		if g.wlEntries = 2 * uint64(g.maxEdges); g.wlEntries == 0 {
+			g.wlEntries = 2
+		} else if g.wlEntries > 1<<31 {
+			g.wlEntries = 1 << 31
+		}
+	}
+	return nil
+}
+
+// SetWorkloadVanished switches the list of vanished workload dependencies on, behind SetWorkloadTrend (a 0 is the parameter's
+// default: silent for 1 window, seen in warmup windows, 65536 rows).  Any SetWorkloadTrend call switches it off.
+func (g *GraphDS) SetWorkloadVanished(silentWindows, minSeen, maxRows uint32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var vp C.sg_vanished_params
+	vp.struct_size = C.uint32_t(unsafe.Sizeof(vp))
+	vp.silent_windows, vp.min_seen, vp.max_rows = C.uint32_t(silentWindows), C.uint32_t(minSeen), C.uint32_t(maxRows)
+	if rc := C.sg_set_group_vanished(g.h, &vp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_group_vanished = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if g.wlVanRows = int(maxRows); maxRows == 0 { // (sg_vanished_params' default)
+		if g.wlVanRows = 65536; g.wlEntries < 65536 {
+			g.wlVanRows = int(g.wlEntries)
+		}
+	}
+	return nil
+}
+
+// WindowWorkloadTrend returns the trend rows of the window FlushWindow returned last: row k for group edge k of WindowGroupEdges,
+// or, with an index (WindowWorkloadsTop's), the rows of those group edges only.
+func (g *GraphDS) WindowWorkloadTrend(index []uint32) ([]EdgeTrend, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	var idx *C.uint32_t
+	if index != nil {
+		if len(index) == 0 {
+			return nil, nil
+		}
+		idx, n = (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index))
+	} else if rc := C.sg_window_group_trend(g.h, nil, 0, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	ts := make([]C.sg_edge_trend, int(n))
+	if rc := C.sg_window_group_trend(g.h, idx, C.size_t(len(index)), &ts[0], C.size_t(len(ts)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	out := make([]EdgeTrend, len(ts))
+	for i := range ts {
+		out[i] = EdgeTrend{float32(ts[i].lat_dev), float32(ts[i].err_dev), float32(ts[i].base_mean_us), uint32(ts[i].windows_seen)}
+	}
 	return out, nil
+}
+
+// WindowWorkloadsTop selects from the group edges of the window FlushWindow returned last on the device (sg_window_groups_top):
+// the k group edges with the highest value >= minValue, descending, ties by position (k = 0: every such group edge, in order),
+// and their indices.  by: ByScore (the group edge's ScoreMax; it needs SetGroups only), ByLatDev, ByErrDev, ByNew (group edges
+// with requests that the baseline has not seen).
+func (g *GraphDS) WindowWorkloadsTop(by, k uint32, minValue float32) ([]GroupEdge, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_groups_top(g.h, C.uint32_t(by), 0, C.float(minValue), nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, fmt.Errorf("servicegraph: sg_window_groups_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil
+	}
+	ges, index := make([]C.sg_group_edge, room), make([]uint32, room)
+	if rc := C.sg_window_groups_top(g.h, C.uint32_t(by), C.uint32_t(k), C.float(minValue), &ges[0], (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, fmt.Errorf("servicegraph: sg_window_groups_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		ges, index = ges[:int(sel)], index[:int(sel)]
+	}
+	return goGroupEdges(ges), index, nil
+}
+
+// WindowWorkloadsVanished returns the workload dependencies that went silent in the window FlushWindow returned last, ascending by
+// key, and the count of all of them (the list holds at most the maxRows of SetWorkloadVanished).
+func (g *GraphDS) WindowWorkloadsVanished() ([]VanishedWorkload, int, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_group_vanished(g.h, nil, 0, &n); rc != 0 {
+		return nil, 0, fmt.Errorf("servicegraph: sg_window_group_vanished = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 || g.wlVanRows == 0 {
+		return nil, int(n), nil
+	}
+	room := int(n) // n counts every vanished entry; the list holds at most maxRows of them
+	if room > g.wlVanRows {
+		room = g.wlVanRows
+	}
+	vs := make([]C.sg_edge_vanished, room)
+	if rc := C.sg_window_group_vanished(g.h, &vs[0], C.size_t(len(vs)), &n); rc != 0 {
+		return nil, 0, fmt.Errorf("servicegraph: sg_window_group_vanished = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	out := make([]VanishedWorkload, 0, len(vs))
+	for i := range vs {
+		v := &vs[i]
+		out = append(out, VanishedWorkload{uint64(v.from_key), uint64(v.to_key), float64(v.lat_mean), float64(v.lat_dev),
+			float64(v.err_mean), float64(v.err_dev), uint32(v.n), uint32(v.last), uint32(v.row)})
+	}
+	return out, int(n), nil
 }
 
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of

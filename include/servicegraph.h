@@ -763,6 +763,64 @@ int sg_window_group_perm(sg_handle h, uint32_t* out, size_t cap, size_t* n);
  * sg_window_run closed last (valid until its slot is reused; read them on that window's stream).                               */
 int sg_window_groups_buffer(sg_handle h, void** d_edges, void** d_count, void** d_row_group, void** d_perm);
 
+/* ---- workload baselines (K15): each group edge against its own past, vanished workload dependencies, selection ---------------- *
+ * Opt-in (sg_set_group_trend), behind the groups; without it nothing is allocated or launched.  It needs none of K8 - K13 and
+ * changes none of them.  K8's baseline is keyed by pod refs, so a rollout (new pods, new ids) makes every row of the workload a
+ * "new dependency"; this one is keyed by workload and survives it.
+ *   workload key  of a group ref r, a uint64_t: wk(r) = g when SG_REF_TYPE(r) == SG_REF_GROUP (key type 0); otherwise
+ *                 wk(r) = (uint64_t)(1 + SG_REF_TYPE(r)) << 32 | x, x = SG_REF_VALUE(r), or the IPv4 address from the window's
+ *                 outbound-IP list for an OBIP ref (the edge trend's key rule, one type up).  An OBIP endpoint keeps its entry when
+ *                 its index in the list moves
+ *   ordering      ascending wk is ascending gk: the groups by id, then the ungrouped KNOWN nodes by id, then LABEL, then OBIP — whose
+ *                 index order is address order, the outbound-IP list being ascending.  A window's group edges come out ascending by
+ *                 (gk(from), gk(to)) and no two share that pair, so they are STRICTLY ascending in (wk(from_ref), wk(to_ref)): the
+ *                 window's samples are a sorted list, and the update is the edge trend's merge over them
+ *   sample        of a group edge with count > 0, exact integers in fp64 (the counts are u64: the node baselines' two functions):
+ *                 x_lat = min(floor(sum_ns / count), 2^52) on the wrapping u64 sum_ns; x_err = floor(err_count * 2^20 / count) by
+ *                 long division (no overflow).  A group edge with count == 0 (it folds alive-only rows only) neither creates nor
+ *                 refreshes an entry
+ * Entry update, expiry, capacity cut and the per-sample output are the edge trend's, word for word; the parameters are
+ * sg_trend_params with max_entries 0 = min(2^31, 2 x max_edges); the stage counts its own trend windows.  Row k of the output is
+ * an sg_edge_trend for group edge k of sg_window_groups, from the entry as it stood before the window.
+ * Vanished workload dependencies (sg_set_group_vanished) are sg_set_vanished's rule word for word over these entries:
+ * sg_vanished_params, sg_edge_vanished rows with from_key / to_key workload keys and row = the index of the window's group edge
+ * with the entry's key and count == 0, else 0xFFFFFFFF.
+ * Selection is the row selection's semantics with "row" read as "group edge": by = SG_SEL_SCORE keys score_max of the group edge
+ * (it needs the groups only), SG_SEL_LAT_DEV / SG_SEL_ERR_DEV its trend row's values, SG_SEL_NEW = windows_seen == 0 and count > 0;
+ * ties go by group-edge position; the selected rows are byte-identical to sg_window_groups' and the indices can be passed to
+ * sg_window_group_trend.
+ * State: sg_set_group_trend is SG_ESTATE with the groups off or while a flush is open, SG_EINVAL on bad parameters; (re)enabling
+ * starts an empty baseline; NULL = off.  ANY sg_set_groups call switches the group trend and its vanished list off and frees them
+ * (it resets the map: the keys mean something else afterwards).  sg_group_assign does not touch the baseline: entries under keys
+ * that no longer occur go silent, are listed once as vanished and expire by ttl.  Any sg_set_group_trend call switches the group
+ * vanished list off.  Reads of a window closed while the stage was off: SG_ESTATE.                                               */
+int sg_set_group_trend(sg_handle h, const sg_trend_params* p);
+/* The group trend rows of the last READ window (as sg_window_trend): group_index NULL: every group edge, *n = group edges; else
+ * out[k] = the row of group edge group_index[k] (each < group edges, else SG_EINVAL), gathered on the device, *n = n_index.       */
+int sg_window_group_trend(sg_handle h, const uint32_t* group_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n);
+/* Device sg_edge_trend[group edges] of the window sg_window_run closed last (read it on that window's stream).                  */
+int sg_window_group_trend_buffer(sg_handle h, void** d_trend);
+/* The workload baseline in key order / its running statistics (both wait for the updates enqueued so far).                      */
+int sg_group_trend_entries(sg_handle h, sg_trend_entry* out, size_t cap, size_t* n);
+int sg_group_trend_stats_get(sg_handle h, sg_trend_stats* out);
+/* NULL = off; SG_ESTATE with the group trend off or while a flush is open, SG_EINVAL on bad parameters (sg_set_vanished's rules
+ * against the group trend's parameters).                                                                                        */
+int sg_set_group_vanished(sg_handle h, const sg_vanished_params* p);
+/* The vanished workload dependencies of the last READ window, ascending by key: *n = every vanished entry of the window (may
+ * exceed max_rows), min(*n, cap, max_rows) are written.                                                                          */
+int sg_window_group_vanished(sg_handle h, sg_edge_vanished* out, size_t cap, size_t* n);
+int sg_window_group_vanished_buffer(sg_handle h, void** d_rows, void** d_count);
+/* Selection over the group edges of the last READ window into host memory: min(*n_selected, cap) group edges to out and their
+ * indices to group_index (either may be NULL), *n_selected = group edges selected (may exceed cap), *n_groups = group edges of the
+ * window.  by > SG_SEL_NEW or k > SG_SELECT_MAX_K: SG_EINVAL; the groups off, a trend key with the group trend off, a window closed
+ * without them, or an open flush: SG_ESTATE.                                                                                    */
+int sg_window_groups_top(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* group_index,
+                         size_t cap, size_t* n_selected, size_t* n_groups);
+/* The same over the window sg_window_run closed last, into device memory, enqueued on `stream` (NULL = that window's stream):
+ * d_out [cap] group edges (may be NULL), d_index [cap] uint32_t (may be NULL), *d_n = group edges selected.                     */
+int sg_window_groups_select(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_group_edge* d_out, uint32_t* d_index,
+                            size_t cap, uint64_t* d_n, void* stream);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
