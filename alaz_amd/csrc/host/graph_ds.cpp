@@ -27,6 +27,11 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->set_group_vanished = reinterpret_cast<decltype(o->set_group_vanished)>(dlsym(dl, "sg_set_group_vanished"));
     o->window_group_vanished = reinterpret_cast<decltype(o->window_group_vanished)>(dlsym(dl, "sg_window_group_vanished"));
     o->window_groups_top = reinterpret_cast<decltype(o->window_groups_top)>(dlsym(dl, "sg_window_groups_top"));
+    o->set_group_nodes = reinterpret_cast<decltype(o->set_group_nodes)>(dlsym(dl, "sg_set_group_nodes"));          // optional (K16)
+    o->window_group_nodes = reinterpret_cast<decltype(o->window_group_nodes)>(dlsym(dl, "sg_window_group_nodes"));
+    o->set_group_node_trend = reinterpret_cast<decltype(o->set_group_node_trend)>(dlsym(dl, "sg_set_group_node_trend"));
+    o->window_group_node_trend = reinterpret_cast<decltype(o->window_group_node_trend)>(dlsym(dl, "sg_window_group_node_trend"));
+    o->window_group_nodes_top = reinterpret_cast<decltype(o->window_group_nodes_top)>(dlsym(dl, "sg_window_group_nodes_top"));
 #undef SG_SYM
     return true;
 }
@@ -140,17 +145,17 @@ long GraphDS::WorkloadEdges(std::vector<WorkloadEdge>* out) {
     for (size_t i = 0; i < ge.size(); i++) NameWorkloadEdge(ge[i], &(*out)[i]);
     return (long)ge.size();
 }
+void GraphDS::NameRef(uint32_t ref, std::string* type, std::string* uid) const {
+    const uint32_t t = SG_REF_TYPE(ref), v = SG_REF_VALUE(ref);
+    if (t == SG_REF_GROUP && v < guid_of_.size()) { *type = "workload"; *uid = guid_of_[v]; }
+    else if (t == SG_REF_KNOWN && v < uid_of_.size()) { *type = kind_of_[v] == SG_NODE_SERVICE ? "service" : "pod"; *uid = uid_of_[v]; }
+    else if (t == SG_REF_LABEL && v < last_labels_.size()) { *type = "outbound"; *uid = last_labels_[v]; }
+    else if (t == SG_REF_OBIP && v < last_obips_.size()) { *type = "outbound"; *uid = FormatIPv4(last_obips_[v]); }
+    else { *type = "unknown"; uid->clear(); }
+}
 void GraphDS::NameWorkloadEdge(const sg_group_edge& r, WorkloadEdge* out) const {
-    auto name = [&](uint32_t ref, std::string* type, std::string* uid) {
-        const uint32_t t = SG_REF_TYPE(ref), v = SG_REF_VALUE(ref);
-        if (t == SG_REF_GROUP && v < guid_of_.size()) { *type = "workload"; *uid = guid_of_[v]; }
-        else if (t == SG_REF_KNOWN && v < uid_of_.size()) { *type = kind_of_[v] == SG_NODE_SERVICE ? "service" : "pod"; *uid = uid_of_[v]; }
-        else if (t == SG_REF_LABEL && v < last_labels_.size()) { *type = "outbound"; *uid = last_labels_[v]; }
-        else if (t == SG_REF_OBIP && v < last_obips_.size()) { *type = "outbound"; *uid = FormatIPv4(last_obips_[v]); }
-        else { *type = "unknown"; uid->clear(); }
-    };
     WorkloadEdge& o = *out;
-    name(r.from_ref, &o.FromType, &o.FromUID); name(r.to_ref, &o.ToType, &o.ToUID);
+    NameRef(r.from_ref, &o.FromType, &o.FromUID); NameRef(r.to_ref, &o.ToType, &o.ToUID);
     o.Count = r.count; o.ErrCount = r.err_count; o.SumNs = r.sum_ns; o.SumSqUs = r.sumsq_us; o.MaxNs = r.max_ns; o.ScoreQ32 = r.score_q32;
     o.Edges = r.edges; o.FromNodes = r.from_nodes; o.Alive = r.alive; o.WorstRow = r.worst_row; o.ScoreMax = r.score_max;
 }
@@ -221,6 +226,63 @@ long GraphDS::WorkloadVanished(std::vector<VanishedWorkload>* out) {
         out->push_back(o);
     }
     return (long)out->size();
+}
+
+// ---- the workload rows (K16) ----
+int GraphDS::SetWorkloadNodes(bool on) {
+    if (!api_.set_group_nodes) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);                        // (not beside a FlushWindow: the engine refuses it while a flush is open)
+    return api_.set_group_nodes(h_, on ? 1 : 0);
+}
+int GraphDS::SetWorkloadNodeTrend(const sg_trend_params& p) {
+    if (!api_.set_group_node_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_group_node_trend(h_, &p);
+}
+void GraphDS::NameWorkloadNodes(const std::vector<sg_node_out>& rows, std::vector<WorkloadNode>* out) {
+    out->assign(rows.size(), WorkloadNode{});
+    std::lock_guard<std::mutex> g(id_mu_);
+    for (size_t i = 0; i < rows.size(); i++) { NameRef(rows[i].ref, &(*out)[i].Type, &(*out)[i].UID); (*out)[i].Row = rows[i]; }
+}
+long GraphDS::WorkloadNodes(std::vector<WorkloadNode>* out) {
+    if (!out || !api_.window_group_nodes) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t n = 0;
+    int rc = api_.window_group_nodes(h_, nullptr, 0, &n);
+    if (rc != SG_OK) return rc;
+    std::vector<sg_node_out> rows(n);
+    if (n && (rc = api_.window_group_nodes(h_, rows.data(), n, &n)) != SG_OK) return rc;
+    NameWorkloadNodes(rows, out);
+    return (long)rows.size();
+}
+long GraphDS::WorkloadNodeTrends(std::vector<sg_node_trend>* out) {
+    if (!out || !api_.window_group_node_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t n = 0;
+    int rc = api_.window_group_node_trend(h_, nullptr, 0, nullptr, 0, &n);
+    if (rc != SG_OK) return rc;
+    out->assign(n, sg_node_trend{});
+    if (n && (rc = api_.window_group_node_trend(h_, nullptr, 0, out->data(), n, &n)) != SG_OK) return rc;
+    return (long)out->size();
+}
+long GraphDS::WorkloadNodesTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
+    if (!out || !api_.window_group_nodes_top) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t sel = 0, total = 0;
+    std::vector<sg_node_out> rows;
+    std::vector<uint32_t> idx;
+    if (k) { rows.resize(k); idx.resize(k); }                        // at most k are selected; k = 0: the count first
+    int rc = api_.window_group_nodes_top(h_, by, k, min_value, rows.data(), idx.data(), rows.size(), &sel, &total);
+    if (rc != SG_OK) return rc;
+    if (!k && sel) {
+        rows.resize(sel); idx.resize(sel);
+        if ((rc = api_.window_group_nodes_top(h_, by, 0, min_value, rows.data(), idx.data(), rows.size(), &sel, &total)) != SG_OK) return rc;
+    }
+    const size_t m = std::min(sel, rows.size());
+    rows.resize(m); idx.resize(m);
+    NameWorkloadNodes(rows, out);
+    if (index) *index = std::move(idx);
+    return (long)m;
 }
 
 // processPod keeps PodIPToPodUid (aggregator/persist.go:55-71); pods without an IP never reach the

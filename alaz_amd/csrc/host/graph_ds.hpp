@@ -54,6 +54,13 @@ struct SgApi {
     int (*set_group_vanished)(sg_handle, const sg_vanished_params*) = nullptr;
     int (*window_group_vanished)(sg_handle, sg_edge_vanished*, size_t, size_t*) = nullptr;
     int (*window_groups_top)(sg_handle, uint32_t, uint32_t, float, sg_group_edge*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
+    // optional (K16; absent in an older library): each of SetWorkloadNodes, WorkloadNodes, SetWorkloadNodeTrend, WorkloadNodeTrends
+    // and WorkloadNodesTop needs the entry it forwards to
+    int (*set_group_nodes)(sg_handle, int) = nullptr;
+    int (*window_group_nodes)(sg_handle, sg_node_out*, size_t, size_t*) = nullptr;
+    int (*set_group_node_trend)(sg_handle, const sg_trend_params*) = nullptr;
+    int (*window_group_node_trend)(sg_handle, const uint32_t*, size_t, sg_node_trend*, size_t, size_t*) = nullptr;
+    int (*window_group_nodes_top)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -78,6 +85,11 @@ struct VanishedWorkload {              // one vanished workload dependency of a 
     std::string FromUID, ToUID;                        // key type 0 (a workload): the owner's UID; any other key type: empty, the key stands
     double LatMean = 0, LatDev = 0, ErrMean = 0, ErrDev = 0;
     uint32_t N = 0, Last = 0, Row = 0;                 // Row: the window's group edge with the key and no request, else 0xFFFFFFFF
+};
+
+struct WorkloadNode {                  // one workload row of a closed window (K16): who it is, and the engine's row as it is
+    std::string Type, UID;                             // "workload" (UID = the owner's UID), or pod / service / outbound as the rows' are
+    sg_node_out Row{};
 };
 
 class EdgeSink {
@@ -156,6 +168,17 @@ public:
     long WorkloadTrends(std::vector<sg_edge_trend>* out);
     long WorkloadTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadEdge>* out, std::vector<uint32_t>* index);
     long WorkloadVanished(std::vector<VanishedWorkload>* out);
+    // The workload rows (K16), behind SetWorkloadGroups: the last flushed window's group edges rolled up per workload, in the order
+    // of the group key (the workloads first).  SetWorkloadNodes / SetWorkloadNodeTrend forward sg_set_group_nodes /
+    // sg_set_group_node_trend (the engine's return code; SG_EINVAL without the entry).  WorkloadNodes: one row per workload, group
+    // ids resolved back to owner UIDs as WorkloadEdges does.  WorkloadNodeTrends: row k for row k of WorkloadNodes.
+    // WorkloadNodesTop: the selection sg_window_group_nodes_top (`by` = SG_NSEL_*), the rows' indices in `index` (may be NULL).
+    // Each returns the count, < 0 on an engine error.
+    int SetWorkloadNodes(bool on);
+    int SetWorkloadNodeTrend(const sg_trend_params& p);
+    long WorkloadNodes(std::vector<WorkloadNode>* out);
+    long WorkloadNodeTrends(std::vector<sg_node_trend>* out);
+    long WorkloadNodesTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }
@@ -180,6 +203,8 @@ private:
     void AssignGroup(uint32_t id, uint32_t group);
     // (id_mu_ held) a group edge in the reference's vocabulary: group ids back to owner UIDs, node refs as the rows' are
     void NameWorkloadEdge(const sg_group_edge& r, WorkloadEdge* o) const;
+    void NameRef(uint32_t ref, std::string* type, std::string* uid) const;   // (id_mu_ held) one group ref
+    void NameWorkloadNodes(const std::vector<sg_node_out>& rows, std::vector<WorkloadNode>* out);   // (takes id_mu_)
     int FlushShard(Shard& s);                          // s.mu held
 
     datastore::DataStore* inner_;

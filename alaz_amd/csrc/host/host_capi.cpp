@@ -28,6 +28,7 @@ struct MockEngine {
     uint32_t top_flushes = 0, top_k = 0; float top_min = 0;             // flush_window_top: calls, the last k and min_score
     std::vector<std::array<uint32_t, 2>> group_ops;   // {node id, group} of every sg_group_assign pair; {0xFFFFFFFE, max_groups} of every sg_set_groups
     std::vector<std::array<uint64_t, 4>> k15_ops;      // {1, shift, warmup, ttl} per sg_set_group_trend, {2, silent_windows, min_seen, max_rows} per sg_set_group_vanished (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_groups_top
+    std::vector<std::array<uint64_t, 4>> k16_ops;      // {1, on, 0, 0} per sg_set_group_nodes, {2, shift, warmup, ttl} per sg_set_group_node_trend (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_group_nodes_top
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
 };
 #define M_LOCK(h) std::lock_guard<std::mutex> _g(reinterpret_cast<MockEngine*>(h)->mu)
@@ -85,6 +86,45 @@ int m_window_groups_top(sg_handle h, uint32_t by, uint32_t k, float min_value, s
     e[0].from_ref = SG_MAKE_REF(SG_REF_GROUP, 1); e[0].to_ref = SG_MAKE_REF(SG_REF_GROUP, 0); e[0].count = 9; e[0].score_max = 0.75f;
     e[1].from_ref = SG_MAKE_REF(SG_REF_GROUP, 0); e[1].to_ref = SG_MAKE_REF(SG_REF_KNOWN, 0); e[1].count = 4; e[1].score_max = 0.5f;
     const uint32_t at[2] = {3u, 0u};
+    for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
+    return SG_OK;
+}
+// K16's stand-ins answer with fixed rows: three workload rows — workload 1, workload 0 (note: the order of the group key is the
+// engine's, the stand-in's is arbitrary) and ungrouped KNOWN 0 — their trend rows (in_seen = 1 + the row's index), and a selection
+// of rows 2 and 0 of three
+static sg_node_out m_node(uint32_t ref, uint64_t out_count, uint64_t in_count, uint32_t out_edges, uint32_t in_edges, float score) {
+    sg_node_out o{}; o.ref = ref; o.out_count = out_count; o.in_count = in_count; o.out_edges = out_edges; o.in_edges = in_edges; o.score = score;
+    o.out_worst_row = o.in_worst_row = 0xFFFFFFFFu;
+    return o;
+}
+int m_set_group_nodes(sg_handle h, int on) { M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k16_ops.push_back({1u, (uint64_t)on, 0u, 0u}); return SG_OK; }
+int m_set_group_node_trend(sg_handle h, const sg_trend_params* p) {
+    M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k16_ops.push_back({2u, p ? p->shift : ~0ull, p ? p->warmup : ~0ull, p ? p->ttl : ~0ull}); return SG_OK;
+}
+int m_window_group_nodes(sg_handle, sg_node_out* out, size_t cap, size_t* n) {
+    const sg_node_out v[3] = {m_node(SG_MAKE_REF(SG_REF_GROUP, 1), 9, 0, 2, 0, 0.75f), m_node(SG_MAKE_REF(SG_REF_GROUP, 0), 4, 9, 1, 1, 0.5f),
+                              m_node(SG_MAKE_REF(SG_REF_KNOWN, 0), 0, 4, 0, 1, 0.25f)};
+    if (n) *n = 3;
+    for (size_t i = 0; out && i < std::min<size_t>(3, cap); i++) out[i] = v[i];
+    return SG_OK;
+}
+int m_window_group_node_trend(sg_handle, const uint32_t* idx, size_t n_idx, sg_node_trend* out, size_t cap, size_t* n) {
+    const size_t N = idx ? n_idx : 3;
+    if (n) *n = N;
+    for (size_t i = 0; out && i < std::min(N, cap); i++) {
+        sg_node_trend t{}; t.in_lat_dev = 0.5f; t.out_lat_dev = -0.25f; t.in_seen = 1u + (idx ? idx[i] : (uint32_t)i); t.out_seen = 7u;
+        out[i] = t;
+    }
+    return SG_OK;
+}
+int m_window_group_nodes_top(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* idx, size_t cap, size_t* n_sel, size_t* n) {
+    M_LOCK(h);
+    uint32_t bits; std::memcpy(&bits, &min_value, 4);
+    reinterpret_cast<MockEngine*>(h)->k16_ops.push_back({3u, by, k, bits});
+    if (n_sel) *n_sel = 2;
+    if (n) *n = 3;
+    const sg_node_out e[2] = {m_node(SG_MAKE_REF(SG_REF_KNOWN, 0), 0, 4, 0, 1, 0.25f), m_node(SG_MAKE_REF(SG_REF_GROUP, 1), 9, 0, 2, 0, 0.75f)};
+    const uint32_t at[2] = {2u, 0u};
     for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
     return SG_OK;
 }
@@ -174,6 +214,8 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.set_groups = m_set_groups; c->api.group_assign = m_group_assign; c->api.window_groups = m_window_groups;
         c->api.set_group_trend = m_set_group_trend; c->api.window_group_trend = m_window_group_trend; c->api.set_group_vanished = m_set_group_vanished;
         c->api.window_group_vanished = m_window_group_vanished; c->api.window_groups_top = m_window_groups_top;
+        c->api.set_group_nodes = m_set_group_nodes; c->api.window_group_nodes = m_window_group_nodes; c->api.set_group_node_trend = m_set_group_node_trend;
+        c->api.window_group_node_trend = m_window_group_node_trend; c->api.window_group_nodes_top = m_window_group_nodes_top;
     }
     if (c->api.create(cfg, &c->h) != SG_OK) return nullptr;        // no usable GPU => no GraphDS: there is no CPU fallback
     c->ds = std::make_unique<GraphDS>(&c->inner, c->api, c->h, &c->sink, cfg ? (size_t)cfg->max_edges : 1024, batch ? batch : 4096,
@@ -256,6 +298,40 @@ long sgh_graphds_workload_vanished(void* g, sgh_workload_vanished* out, size_t c
         std::strncpy(o.from_uid, r.FromUID.c_str(), sizeof o.from_uid - 1); std::strncpy(o.to_uid, r.ToUID.c_str(), sizeof o.to_uid - 1);
         o.lat_mean = r.LatMean; o.lat_dev = r.LatDev; o.err_mean = r.ErrMean; o.err_dev = r.ErrDev; o.n = r.N; o.last = r.Last; o.row = r.Row;
     }
+    return n;
+}
+// the workload rows (K16): the two switches (a parameter 0 = its default), the last flushed window's workload rows (who each is,
+// then the engine's sg_node_out), their trend rows (as sg_node_trend) and a selection over them
+int sgh_graphds_set_workload_nodes(void* g, int on) { return static_cast<HostCtx*>(g)->ds->SetWorkloadNodes(on != 0); }
+int sgh_graphds_set_workload_node_trend(void* g, uint32_t shift, uint32_t warmup, uint32_t ttl, uint64_t max_entries) {
+    sg_trend_params p{}; p.struct_size = sizeof p; p.shift = shift; p.warmup = warmup; p.ttl = ttl; p.max_entries = max_entries;
+    return static_cast<HostCtx*>(g)->ds->SetWorkloadNodeTrend(p);
+}
+struct sgh_workload_node { char type[16]; char uid[160]; sg_node_out row; };
+static_assert(sizeof(sgh_workload_node) == 16 + 160 + 136, "sgh_workload_node: the names, then sg_node_out");
+static void put_workload_node(const WorkloadNode& r, sgh_workload_node* o) {
+    std::memset(o, 0, sizeof *o);
+    std::strncpy(o->type, r.Type.c_str(), sizeof o->type - 1); std::strncpy(o->uid, r.UID.c_str(), sizeof o->uid - 1);
+    o->row = r.Row;
+}
+long sgh_graphds_workload_nodes(void* g, sgh_workload_node* out, size_t cap) {
+    std::vector<WorkloadNode> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadNodes(&v);
+    if (n < 0) return n;
+    for (size_t i = 0; out && i < std::min(cap, v.size()); i++) put_workload_node(v[i], out + i);
+    return n;
+}
+long sgh_graphds_workload_node_trends(void* g, sg_node_trend* out, size_t cap) {
+    std::vector<sg_node_trend> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadNodeTrends(&v);
+    if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_node_trend));
+    return n;
+}
+long sgh_graphds_workload_nodes_top(void* g, uint32_t by, uint32_t k, float min_value, sgh_workload_node* out, uint32_t* index, size_t cap) {
+    std::vector<WorkloadNode> v; std::vector<uint32_t> idx;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadNodesTop(by, k, min_value, &v, &idx);
+    if (n < 0) return n;
+    for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_node(v[i], out + i); if (index) index[i] = idx[i]; }
     return n;
 }
 int sgh_graphds_ingest_wire(void* g, const uint8_t* recs, size_t n, const uint32_t* kafka_msgs) {
@@ -536,6 +612,14 @@ size_t sgh_mock_k15_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k15_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k15_ops[i].data(), 32);
     return m->k15_ops.size();
+}
+size_t sgh_mock_k16_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k16_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k16_ops[i].data(), 32);
+    return m->k16_ops.size();
 }
 size_t sgh_mock_group_ops(void* g, uint32_t* out2, size_t cap) {
     auto* c = static_cast<HostCtx*>(g); if (!c->mock) return 0;

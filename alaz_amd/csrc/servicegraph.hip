@@ -32,6 +32,7 @@
 #include "sg_track.h"
 #include "sg_group.h"
 #include "sg_group_trend.h"
+#include "sg_group_nodes.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -209,7 +210,8 @@ struct sg_engine {
                     u32* idx[2] = {nullptr, nullptr}; u32* hist = nullptr; u32* chunkcnt = nullptr; K14Acc* part = nullptr; uint2* meta = nullptr;
                     u32* blk = nullptr; u32* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_group_edge*> rows; std::vector<u64*> count;
                     std::vector<u32*> row_group, perm; std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false;
-                    std::vector<u32> h_map; u32* h_up = nullptr; hipEvent_t up_ev = nullptr; bool up_pending = false; u32 dirty_lo = 0, dirty_hi = 0; } grp;
+                    std::vector<u32> h_map; u32* h_up = nullptr; hipEvent_t up_ev = nullptr; bool up_pending = false; u32 dirty_lo = 0, dirty_hi = 0;
+                    u32 hi_group = 0; } grp;                          // (hi_group: one past the largest group id assigned, beside h_map: K16's used group ranges)
     // K15, the workload baselines (sg_group_trend.h): a Baseline over the group edges (sg_plan.hpp plan_group_trend) and its vanished
     // list, allocated at sg_set_group_trend / sg_set_group_vanished, freed with the groups
     Baseline<sg_edge_trend> gtrend;
@@ -217,6 +219,16 @@ struct sg_engine {
     // selection over group edges (K7 over K14's rows): plan_group_select's block, allocated at the first one — K7's scratch over
     // max_edges keys, the counter block k15_keys fills, an index array and the host form's staging of SG_SELECT_MAX_K group edges
     struct GSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; sg_group_edge* stage = nullptr; char* mem = nullptr; u64 stage_rows = 0; } gsel;
+    // K16, the workload rows (sg_group_nodes.h): allocated at sg_set_group_nodes (sg_plan.hpp plan_group_nodes), one allocation, freed
+    // with the groups.  The tables over the group keys are scratch shared by the window slots: every rollup waits for the previous
+    // one (ev).  Per slot: the workload rows and their count, and whether the window in the slot was rolled up (valid).
+    struct GroupNodes { bool on = false; sgplan::GroupNodesPlan plan; char* mem = nullptr; u32* dst = nullptr; K9Side* tout = nullptr; K9Side* tin = nullptr;
+                        K9Side* part = nullptr; u32* blk = nullptr; std::vector<sg_node_out*> rows; std::vector<u64*> count; std::vector<char> valid;
+                        hipEvent_t ev = nullptr; bool pending = false; } gnodes;
+    // its baseline (K10's walk under workload keys), allocated at sg_set_group_node_trend, and the selection over workload rows:
+    // plan_group_node_select's block, allocated at the first one, freed with the workload rows (its sizes are theirs)
+    Baseline<sg_node_trend> gntrend;
+    NSel gnsel;
 };
 
 namespace {
@@ -998,7 +1010,65 @@ void free_group_trend(sg_engine* e) {
     free_baseline(e->gtrend);
 }
 
+// ---- K16, the workload rows (engine lock held) -------------------------------------------------------------------------------------
+static_assert(offsetof(sg_group_edge, edges) == 56 && offsetof(sg_group_edge, alive) == 68 && offsetof(sg_group_edge, worst_row) == 72 &&
+              offsetof(sg_group_edge, sumsq_us) == 24 && offsetof(sg_group_edge, max_ns) == 32 && offsetof(sg_group_edge, score_q32) == 40,
+              "k16_load reads sg_group_edge by word");
+// enqueue the rollup of the group edges of the window in slot cur on stream s (behind its contraction, on the same stream) and behind
+// the previous rollup (any stream): five plain launches, the workload rows and their count go to the slot's buffers
+int launch_group_nodes(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
+    sg_engine::GroupNodes& n = e->gnodes;
+    const sgplan::GroupNodesPlan& P = n.plan;
+    GroupNodesArgs a{};
+    a.nd = nodes_view(e, w, P.ncap);
+    a.nd.max_edges = std::max<u64>(e->cfg.max_edges, 1);
+    a.nd.slices = P.slices; a.nd.node_per = P.node_per;
+    a.nd.dst = n.dst; a.nd.tout = n.tout; a.nd.tin = n.tin; a.nd.part = n.part; a.nd.blk = n.blk;
+    a.nd.out = n.rows[e->cur]; a.nd.count = n.count[e->cur];
+    a.groups = e->grp.rows[e->cur]; a.gcount = e->grp.count[e->cur];
+    a.max_groups = P.max_groups; a.gk = (u32)P.gk; a.hi_group = e->grp.hi_group; a.nc = P.nc;
+    if (const int rc = stage_wait(e, n, s)) return rc;
+    hipLaunchKernelGGL(k16_out, dim3(P.out_wgs), dim3(K9_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k16_in_part, dim3(P.ranges * P.slices), dim3(K9_IN_THREADS), (size_t)P.lds_bytes, s, a);
+    hipLaunchKernelGGL(k16_count, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a.nd, P.node_wgs);
+    hipLaunchKernelGGL(k16_write, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
+    if (const int rc = stage_done(e, n, s)) return rc;
+    n.valid[e->cur] = 1;
+    return SG_OK;
+}
+// enqueue the workload-row baseline's update by the window in slot cur on stream s (behind its rollup, on the same stream)
+int launch_group_node_trend(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
+    sg_engine::Baseline<sg_node_trend>& t = e->gntrend;
+    NodeTrendArgs a{};
+    a.t = baseline_args(w, t);
+    a.nodes = e->gnodes.rows[e->cur]; a.count = e->gnodes.count[e->cur]; a.ncap = e->gnodes.plan.nc; a.out = t.rows[e->cur];
+    if (const int rc = enqueue_baseline(e, t, s, [&] {
+            hipLaunchKernelGGL(k16_tcount, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs);
+            hipLaunchKernelGGL(k16_twrite, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+        })) return rc;
+    t.valid[e->cur] = 1;
+    return SG_OK;
+}
+// a selection scratch block off (the workload rows': its sizes are the stage's)
+void free_nsel(sg_engine::NSel& s) {
+    if (s.mem || s.h_n) hipDeviceSynchronize();
+    if (s.mem) hipFree(s.mem);
+    if (s.h_n) hipHostFree(s.h_n);
+    if (s.ev) hipEventDestroy(s.ev);
+    s = sg_engine::NSel{};
+}
+void free_group_nodes(sg_engine* e) {
+    free_nsel(e->gnsel);
+    free_baseline(e->gntrend);
+    free_stage(e->gnodes);
+}
+
 void free_groups(sg_engine* e) {
+    free_group_nodes(e);
     free_group_trend(e);
     sg_engine::Groups& x = e->grp;
     if (x.mem) hipDeviceSynchronize();                                // (an upload may still read h_up)
@@ -1054,7 +1124,11 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     }
     if (e->grp.on) {                                                 // K14 behind K5: the rows and the window counters only, whatever else is on
         if (const int rc = launch_groups(e, s)) return rc;
-        if (e->gtrend.on) return launch_group_trend(e, s);           // K15 behind K14: the group edges, their count, the outbound IPs
+        if (e->gtrend.on) { if (const int rc = launch_group_trend(e, s)) return rc; }   // K15 behind K14: the group edges, their count, the outbound IPs
+        if (e->gnodes.on) {                                          // K16 behind K14: the group edges and their count; its baseline behind it
+            if (const int rc = launch_group_nodes(e, s)) return rc;
+            if (e->gntrend.on) return launch_group_node_trend(e, s);
+        }
     }
     return SG_OK;
 }
@@ -1232,22 +1306,42 @@ int nsel_reserve(sg_engine* e) {
     s.idx = at<u32>(s.mem, P.idx_off);
     return sel_init(e, s, s.mem + P.sel_off);
 }
-// enqueue a selection over the node rows of slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
+// the same for the selection over workload rows (K16): plan_group_node_select over the stage's row capacity
+int gnsel_reserve(sg_engine* e) {
+    sg_engine::NSel& s = e->gnsel;
+    if (s.keys) return SG_OK;
+    const sgplan::NodeSelPlan P = sgplan::plan_group_node_select(e->gnodes.plan.nc, sizeof(e->h_ctr));
+    s.plan = P.sel;
+    HIP_TRY(e, hipMalloc((void**)&s.mem, P.total_bytes));
+    HIP_TRY(e, hipMemset(s.mem, 0, P.total_bytes));
+    s.stage = at<sg_node_out>(s.mem, P.stage_off);
+    s.ctr = at<u64>(s.mem, P.ctr_off);
+    s.idx = at<u32>(s.mem, P.idx_off);
+    return sel_init(e, s, s.mem + P.sel_off);
+}
+// what a selection over node rows works on: K9's node rows (nsel, ncap) or K16's workload rows (gnsel, their row capacity) —
+// the scratch, the row capacity, every slot's rows and counts, and the event of the stage that writes them
+struct NodeRowsView { sg_engine::NSel* sel; u64 cap; sg_node_out* const* rows; u64* const* count; hipEvent_t ev; bool pending; };
+NodeRowsView node_rows(sg_engine* e) { return {&e->nsel, std::max<u32>(e->plan.ncap, 1), e->nodes.rows.data(), e->nodes.count.data(), e->nodes.ev, e->nodes.pending}; }
+NodeRowsView group_node_rows(sg_engine* e) {
+    return {&e->gnsel, std::max<u32>(e->gnodes.plan.nc, 1), e->gnodes.rows.data(), e->gnodes.count.data(), e->gnodes.ev, e->gnodes.pending};
+}
+// enqueue a selection over the node rows v of slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
 // be NULL), the count to d_n; behind that window's rollup (event) and the previous node selection.  keys(a, wgs) launches the key
 // pass (k10_keys, k11_keys) and waits for what it reads; after(a, grid) launches what else gathers by the selected indices.
 template <class Keys, class After>
-int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
+int launch_node_select(sg_engine* e, const NodeRowsView& v, hipStream_t st, int slot, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
                        u64 cap, u64* d_n, Keys keys, After after) {
-    sg_engine::NSel& s = e->nsel;
+    sg_engine::NSel& s = *v.sel;
     const u32 wgs = s.plan.wgs;
-    const u64 NC = std::max<u32>(e->plan.ncap, 1);
+    const u64 NC = v.cap;
     SelArgs a{};
     a.rows = nullptr; a.ctr = s.ctr; a.max_edges = NC; a.k = k; a.min_score = min_value;
     sel_scratch_args(a, s);
     a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, NC); a.n_out = d_n;
     if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
-    if (e->nodes.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->nodes.ev, 0));
-    const sg_node_out* nodes = e->nodes.rows[slot];
+    if (v.pending) HIP_TRY(e, hipStreamWaitEvent(st, v.ev, 0));
+    const sg_node_out* nodes = v.rows[slot];
     if (const int rc = keys(a, wgs)) return rc;
     enqueue_k7_select(st, a, k, wgs, NC);
     const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, NC) : NC);
@@ -1262,10 +1356,20 @@ int launch_node_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_
 // by a key of SG_NSEL_*: k10_keys over the node rows and, for a trend key, the window's node trend rows (behind its update)
 int launch_node_select_by(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
                           u64 cap, u64* d_n) {
-    return launch_node_select(e, st, slot, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+    return launch_node_select(e, node_rows(e), st, slot, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
         if (by != SG_NSEL_SCORE && e->ntrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->ntrend.ev, 0));
         const sg_node_trend* tr = by != SG_NSEL_SCORE ? e->ntrend.rows[slot] : nullptr;
         hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, (const sg_node_out*)e->nodes.rows[slot], (const u64*)e->nodes.count[slot], tr, by, e->nsel.ctr);
+        return (int)SG_OK;
+    }, [](const SelArgs&, dim3) {});
+}
+// the same over the workload rows (K16) and, for a trend key, the window's workload trend rows
+int launch_group_node_select_by(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
+                                u64 cap, u64* d_n) {
+    return launch_node_select(e, group_node_rows(e), st, slot, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+        if (by != SG_NSEL_SCORE && e->gntrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->gntrend.ev, 0));
+        const sg_node_trend* tr = by != SG_NSEL_SCORE ? e->gntrend.rows[slot] : nullptr;
+        hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, (const sg_node_out*)e->gnodes.rows[slot], (const u64*)e->gnodes.count[slot], tr, by, e->gnsel.ctr);
         return (int)SG_OK;
     }, [](const SelArgs&, dim3) {});
 }
@@ -1273,7 +1377,7 @@ int launch_node_select_by(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k,
 int launch_rank_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_share, sg_node_out* d_out, sg_node_rank* d_rank, u32* d_index,
                        u64 cap, u64* d_n) {
     const sg_node_rank* rk = e->rank.rows[slot];
-    return launch_node_select(e, st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+    return launch_node_select(e, node_rows(e), st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
         if (e->rank.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->rank.ev, 0));
         hipLaunchKernelGGL(k11_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, rk, (const u64*)e->nodes.count[slot], e->nsel.ctr);
         return (int)SG_OK;
@@ -1281,19 +1385,19 @@ int launch_rank_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_
         if (d_rank) hipLaunchKernelGGL(k_gather_sel<sg_node_rank>, grid, dim3(256), 0, st, rk, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_rank);
     });
 }
-// the host form of a node selection over the last read window (sg_window_nodes_top, sg_window_rank_top): launch(out_stage,
-// rank_stage, cap, d_n) enqueues it on the read stream; the selected rows, rank rows and indices come back, then the counts
+// the host form of a node selection over the last read window (sg_window_nodes_top, sg_window_rank_top, sg_window_group_nodes_top;
+// v's scratch reserved): launch(out_stage, rank_stage, cap, d_n) enqueues it on the read stream; the selected rows, rank rows and
+// indices come back, then the counts
 template <class L>
-int node_top_host(sg_engine* e, L launch, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap, size_t* n_selected,
-                  size_t* n_nodes) {
-    if (const int rc = nsel_reserve(e)) return rc;
-    sg_engine::NSel& s = e->nsel;
-    const u64 NC = std::max<u32>(e->plan.ncap, 1);
+int node_top_host(sg_engine* e, const NodeRowsView& v, L launch, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap,
+                  size_t* n_selected, size_t* n_nodes) {
+    sg_engine::NSel& s = *v.sel;
+    const u64 NC = v.cap;
     const u64 stage = std::min<u64>(cap, NC);
     if (const int rc = launch(out ? s.stage : nullptr, rank_out ? e->rank.stage : nullptr, stage, s.n)) return rc;
     u64 cnt = 0;
     HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipMemcpyAsync(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipMemcpyAsync(&cnt, v.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
     HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
     const u64 m = *s.h_n;
     const size_t take = (size_t)std::min<u64>(m, stage);
@@ -1419,6 +1523,8 @@ constexpr StageWords kIncidentsWords{"the incidents are off (sg_set_incidents)",
 constexpr StageWords kTracksWords{"tracking is off (sg_set_tracks)", "tracking was off"};
 constexpr StageWords kGroupsWords{"the groups are off (sg_set_groups)", "the groups were off"};
 constexpr StageWords kGroupTrendWords{"the group trend is off (sg_set_group_trend)", "the group trend was off"};
+constexpr StageWords kGroupNodesWords{"the workload rows are off (sg_set_group_nodes)", "the workload rows were off"};
+constexpr StageWords kGroupNodeTrendWords{"the workload trend is off (sg_set_group_node_trend)", "the workload trend was off"};
 constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
 // a host read of stage x's rows of the last read window (slot cur): the stage on, no flush open, the window closed with the stage
 // on; then its kernels done
@@ -2516,7 +2622,8 @@ int sg_window_nodes_top(sg_handle e, uint32_t by, uint32_t k, float min_value, s
     if (by > SG_NSEL_NEW) { e->err = "node selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
     if (e->closing || e->flush_open) { e->err = "sg_window_nodes_top while a flush is open"; return SG_ESTATE; }
     if (const int rc = check_nsel(e, by, e->cur)) return rc;
-    return node_top_host(e, [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
+    if (const int rc = nsel_reserve(e)) return rc;
+    return node_top_host(e, node_rows(e), [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
         return launch_node_select_by(e, e->rd_stream, e->cur, by, k, min_value, d_out, nullptr, stage, d_n);
     }, out, nullptr, node_index, cap, n_selected, n_nodes);
 }
@@ -2592,7 +2699,8 @@ int sg_window_rank_top(sg_handle e, uint32_t k, float min_share, sg_node_out* ou
     std::lock_guard<std::mutex> g(e->mu);
     if (e->closing || e->flush_open) { e->err = "sg_window_rank_top while a flush is open"; return SG_ESTATE; }
     if (const int rc = check_rsel(e, e->cur)) return rc;
-    return node_top_host(e, [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
+    if (const int rc = nsel_reserve(e)) return rc;
+    return node_top_host(e, node_rows(e), [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
         return launch_rank_select(e, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
     }, out, rank_out, node_index, cap, n_selected, n_nodes);
 }
@@ -2711,6 +2819,7 @@ int sg_group_assign(sg_handle e, const uint32_t* node_ids, const uint32_t* group
         const u32 id = node_ids[k];
         if (x.h_map[id] == groups[k]) continue;
         x.h_map[id] = groups[k];
+        if (groups[k] != SG_NO_GROUP) x.hi_group = std::max(x.hi_group, groups[k] + 1);
         if (x.dirty_hi == x.dirty_lo) { x.dirty_lo = id; x.dirty_hi = id + 1; }
         else { x.dirty_lo = std::min(x.dirty_lo, id); x.dirty_hi = std::max(x.dirty_hi, id + 1); }
     }
@@ -2850,6 +2959,133 @@ int sg_window_groups_select(sg_handle e, uint32_t by, uint32_t k, float min_valu
     if (const int rc = check_gsel(e, by, slot)) return rc;
     if (const int rc = gsel_reserve(e)) return rc;
     return launch_group_select(e, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
+}
+
+// ---- K16, the workload rows ------------------------------------------------------------------------------------------------------
+int sg_set_group_nodes(sg_handle e, int on) {
+    if (!e || (on != 0 && on != 1)) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->grp.on) { e->err = "sg_set_group_nodes: the groups are off (sg_set_groups)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_group_nodes while a flush is open"; return SG_ESTATE; }
+    if (!on) { free_group_nodes(e); return SG_OK; }
+    sg_engine::GroupNodes& n = e->gnodes;
+    if (n.on) return SG_OK;
+    const Dev& d = e->slots[0].d;
+    const u32 ncap = d.max_known + d.max_labels + d.max_obip, slots = (u32)e->slots.size();
+    if (sgplan::check_group_nodes(e->grp.plan.max_groups, ncap)) {
+        e->err = "sg_set_group_nodes: max_groups + the node capacity exceeds 2^21 group keys: pass a tighter max_groups to sg_set_groups";
+        return SG_EINVAL;
+    }
+    n.plan = sgplan::plan_group_nodes(e->cfg.max_edges, ncap, e->grp.plan.max_groups, slots);
+    const sgplan::GroupNodesPlan& P = n.plan;
+    HIP_TRY(e, lds_limit(P.lds_bytes, k16_in_part));
+    HIP_TRY(e, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &n.mem, P.total_bytes, "sg_set_group_nodes", [e] { free_group_nodes(e); })) return rc;   // (zeroed: the out table starts at zero, k16_write keeps it so)
+    n.tout = at<K9Side>(n.mem, P.table_off[0]);
+    n.tin = at<K9Side>(n.mem, P.table_off[1]);
+    n.part = at<K9Side>(n.mem, P.part_off);
+    n.dst = at<u32>(n.mem, P.dst_off);
+    n.blk = at<u32>(n.mem, P.blk_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = n.mem + P.slot.off + k * P.slot.bytes;
+        n.rows.push_back(at<sg_node_out>(s, P.slot_rows)); n.count.push_back(at<u64>(s, P.slot_count));
+    }
+    n.valid.assign(slots, 0);
+    n.on = true;
+    return SG_OK;
+}
+int sg_window_group_nodes(sg_handle e, sg_node_out* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::GroupNodes& x = e->gnodes;
+    if (const int rc = stage_ready(e, x, "sg_window_group_nodes", kGroupNodesWords)) return rc;
+    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_node_out), out, cap, n);
+}
+int sg_window_group_nodes_buffer(sg_handle e, void** d_nodes, void** d_count) {
+    if (!e || !d_nodes || !d_count) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::GroupNodes& x = e->gnodes;
+    int slot;
+    if (const int rc = stage_slot(e, x, "sg_window_group_nodes_buffer", kGroupNodesWords, &slot)) return rc;
+    *d_nodes = x.rows[slot]; *d_count = x.count[slot];
+    return SG_OK;
+}
+int sg_set_group_node_trend(sg_handle e, const sg_trend_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->gnodes.on) { e->err = "sg_set_group_node_trend: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_group_node_trend while a flush is open"; return SG_ESTATE; }
+    sg_trend_params r{};
+    if (p && sgplan::check_group_node_trend(*p, e->gnodes.plan.nc, &r)) { e->err = "sg_set_group_node_trend: bad parameters"; return SG_EINVAL; }
+    sg_engine::Baseline<sg_node_trend>& t = e->gntrend;
+    free_baseline(t);
+    if (!p) return SG_OK;
+    const u32 slots = (u32)e->slots.size();
+    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_node_trend(e->gnodes.plan.nc, slots, r), "sg_set_group_node_trend", [&t] { free_baseline(t); })) return rc;
+    t.valid.assign(slots, 0);
+    return SG_OK;
+}
+int sg_window_group_node_trend(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::Baseline<sg_node_trend>& t = e->gntrend;
+    if (const int rc = stage_ready(e, t, "sg_window_group_node_trend", kGroupNodeTrendWords)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->gnodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    return baseline_rows(e, t, (size_t)cnt, node_index, n_index, out, cap, n, "sg_window_group_node_trend: a node index beyond the window's workload rows");
+}
+int sg_window_group_node_trend_buffer(sg_handle e, void** d_trend) {
+    if (!e || !d_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Baseline<sg_node_trend>& t = e->gntrend;
+    int slot;
+    if (const int rc = stage_slot(e, t, "sg_window_group_node_trend_buffer", kGroupNodeTrendWords, &slot)) return rc;
+    *d_trend = t.rows[slot];
+    return SG_OK;
+}
+int sg_group_node_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->gntrend.on) { e->err = "sg_group_node_trend_entries: the workload trend is off (sg_set_group_node_trend)"; return SG_ESTATE; }
+    return baseline_entries(e, e->gntrend, out, cap, n);
+}
+int sg_group_node_trend_stats_get(sg_handle e, sg_trend_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->gntrend.on) { e->err = "sg_group_node_trend_stats_get: the workload trend is off (sg_set_group_node_trend)"; return SG_ESTATE; }
+    return baseline_stats(e, e->gntrend, out);
+}
+namespace {
+// by > 5: SG_EINVAL; the workload rows off, or a trend key with their trend off: SG_ESTATE; then the window in `slot` must have them
+int check_gnsel(sg_engine* e, u32 by, int slot) {
+    if (by > SG_NSEL_NEW) { e->err = "workload selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
+    if (!e->gnodes.on) { e->err = "workload selection: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
+    if (by != SG_NSEL_SCORE && !e->gntrend.on) { e->err = "workload selection by a trend key: the workload trend is off (sg_set_group_node_trend)"; return SG_ESTATE; }
+    if (!e->gnodes.valid[slot]) { e->err = "workload selection: the window was closed while the workload rows were off"; return SG_ESTATE; }
+    if (by != SG_NSEL_SCORE && !e->gntrend.valid[slot]) { e->err = "workload selection: the window was closed while the workload trend was off"; return SG_ESTATE; }
+    return SG_OK;
+}
+}  // namespace
+int sg_window_group_nodes_top(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
+                              size_t* n_selected, size_t* n_nodes) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (by > SG_NSEL_NEW) { e->err = "workload selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
+    if (e->closing || e->flush_open) { e->err = "sg_window_group_nodes_top while a flush is open"; return SG_ESTATE; }
+    if (const int rc = check_gnsel(e, by, e->cur)) return rc;
+    if (const int rc = gnsel_reserve(e)) return rc;
+    return node_top_host(e, group_node_rows(e), [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
+        return launch_group_node_select_by(e, e->rd_stream, e->cur, by, k, min_value, d_out, nullptr, stage, d_n);
+    }, out, nullptr, node_index, cap, n_selected, n_nodes);
+}
+int sg_window_group_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out, uint32_t* d_index, size_t cap,
+                                 uint64_t* d_n, void* stream) {
+    if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int slot = ran_slot(e);
+    if (const int rc = check_gnsel(e, by, slot)) return rc;
+    if (const int rc = gnsel_reserve(e)) return rc;
+    return launch_group_node_select_by(e, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // ---- K13, the tracks ---------------------------------------------------------------------------------------------------------------

@@ -1063,6 +1063,72 @@ inline GroupSelPlan plan_group_select(u64 max_edges, u64 counter_bytes) {
     return n;
 }
 
+// K16, the workload rows (sg_group_nodes.h): the device memory sg_set_group_nodes allocates — never sg_create or sg_set_groups.
+// Nodes are keyed by K14's group key below GK = max_groups + ncap, at most 2^21: the tables are per key (two of 64 bytes a key and
+// the in side's partials: 256 MB + 128 MB at 2^21 keys).  k16_out takes chunks of 2048 group edges; k16_in_part a grid of key ranges
+// of 2048 (128 KiB of LDS each) x slices of about 32 K group edges — at most 16 slices, and at most about 1024 workgroups: a
+// range's workgroups scan every group edge of their slice, so many ranges take fewer slices, as K11.  k16_count / k16_write follow
+// K9's rule over GK.  A window of E group edges has at most min(GK, 2 E) nodes: NC workload rows per slot.
+constexpr u64 kGrpNodesMaxKeys = 1ull << 21;
+constexpr u32 kGrpNodesMaxInWgs = 1024;
+inline int check_group_nodes(u32 max_groups, u32 ncap) { return (u64)max_groups + ncap > kGrpNodesMaxKeys ? SG_EINVAL : SG_OK; }
+struct GroupNodesPlan {
+    u64 gk = 0;                   // max_groups + ncap
+    u32 max_groups = 0, ncap = 0;
+    u32 nc = 0;                   // workload rows per window slot: min(GK, 2 x max_edges)
+    u32 out_wgs = 0;              // workgroups of k16_out: chunks of max_edges
+    u32 ranges = 0, slices = 0;   // k16_in_part's grid = ranges x slices
+    u32 node_wgs = 0, node_per = 0;   // k16_count / k16_write: workgroups, keys per workgroup (a multiple of 256)
+    u64 dst_bytes = 0;            // [max_edges] u32 destination key per group edge
+    u64 table_bytes = 0;          // one side's table: [GK] x 64 bytes (out and in: two of them)
+    u64 part_bytes = 0;           // [ranges][slices][2048] x 64 bytes
+    u64 blk_bytes = 0;            // [2][1024] u32
+    u64 rows_bytes = 0;           // one window slot's workload rows: [NC] sg_node_out
+    u64 count_bytes = 0;          // one window slot's node count (u64)
+    u64 lds_bytes = 0;            // k16_in_part's dynamic LDS
+    u64 total_bytes = 0;          // the scratch and every slot's rows and count, each 256-byte aligned
+    u64 table_off[2] = {}, part_off = 0, dst_off = 0, blk_off = 0;   // (table_off: out, in)
+    Slots slot; u64 slot_rows = 0, slot_count = 0;
+    std::vector<Piece> layout;
+};
+inline GroupNodesPlan plan_group_nodes(u64 max_edges, u32 ncap, u32 max_groups, u32 slots) {
+    GroupNodesPlan n;
+    const u64 ME = std::max<u64>(max_edges, 1), GK = std::max<u64>((u64)max_groups + ncap, 1);
+    n.gk = (u64)max_groups + ncap; n.max_groups = max_groups; n.ncap = ncap;
+    n.nc = (u32)std::min<u64>(GK, 2 * ME);
+    n.out_wgs = (u32)((ME + kNodesChunk - 1) / kNodesChunk);
+    n.ranges = (u32)((GK + kNodesRangeNodes - 1) / kNodesRangeNodes);
+    n.slices = (u32)std::max<u64>(1, std::min<u64>(std::min<u64>(kNodesMaxSlices, (ME + kNodesSliceRows - 1) / kNodesSliceRows),
+                                                   std::max<u32>(1, kGrpNodesMaxInWgs / n.ranges)));
+    n.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kNodesMaxWgs, (GK + kNodesThreads - 1) / kNodesThreads));
+    const u64 per = (GK + n.node_wgs - 1) / n.node_wgs;
+    n.node_per = (u32)((per + kNodesThreads - 1) / kNodesThreads * kNodesThreads);
+    n.node_wgs = (u32)((GK + n.node_per - 1) / n.node_per);           // (the rounding can leave the last blocks without keys)
+    n.dst_bytes = trend_align(ME * 4);
+    n.table_bytes = trend_align(GK * kNodesSideBytes);
+    n.part_bytes = trend_align((u64)n.ranges * n.slices * kNodesRangeNodes * kNodesSideBytes);
+    n.blk_bytes = trend_align(2ull * kNodesMaxWgs * 4);
+    n.rows_bytes = trend_align((u64)n.nc * sizeof(sg_node_out));
+    n.count_bytes = trend_align(8);
+    n.lds_bytes = (u64)kNodesRangeNodes * kNodesSideBytes;
+    Block b;
+    n.table_off[0] = b.take("table_out", n.table_bytes); n.table_off[1] = b.take("table_in", n.table_bytes);
+    n.part_off = b.take("part", n.part_bytes);
+    n.dst_off = b.take("dst", n.dst_bytes);
+    n.blk_off = b.take("blk", n.blk_bytes);
+    n.slot = b.slots(slots, {{"rows", n.rows_bytes, &n.slot_rows}, {"count", n.count_bytes, &n.slot_count}});
+    n.total_bytes = b.end; n.layout = std::move(b.pieces);
+    return n;
+}
+// K16's baseline: K10's over the workload rows — two samples per row, [NC] sg_node_trend per slot; max_entries defaults to 4 x NC
+inline int check_group_node_trend(const sg_trend_params& p, u32 nc, sg_trend_params* out) { return check_node_trend(p, nc, out); }
+using GroupNodeTrendPlan = TrendPlan;
+inline TrendPlan plan_group_node_trend(u32 nc, u32 slots, const sg_trend_params& p) {
+    return plan_baseline(p, 2 * (u64)nc, std::max<u64>(nc, 1) * sizeof(sg_node_trend), slots);
+}
+// the selection over workload rows: plan_node_select over NC rows
+inline NodeSelPlan plan_group_node_select(u32 nc, u64 counter_bytes) { return plan_node_select(nc, counter_bytes); }
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

@@ -254,6 +254,13 @@ def _signatures() -> dict:
         "sg_window_group_vanished_buffer": (I, [H, PP, PP]),
         "sg_window_groups_top": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
         "sg_window_groups_select": (I, [H, u32, u32, f32, P, P, sz, P, P]),
+        "sg_set_group_nodes": (I, [H, I]), "sg_window_group_nodes": (I, [H, P, sz, Psz]),
+        "sg_window_group_nodes_buffer": (I, [H, PP, PP]),
+        "sg_set_group_node_trend": (I, [H, P]), "sg_window_group_node_trend": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_node_trend_buffer": (I, [H, PP]), "sg_group_node_trend_entries": (I, [H, P, sz, Psz]),
+        "sg_group_node_trend_stats_get": (I, [H, P]),
+        "sg_window_group_nodes_top": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_group_nodes_select": (I, [H, u32, u32, f32, P, P, sz, P, P]),
     }
 
 
@@ -293,6 +300,8 @@ _STAGES = dict(
     group_trend=_Stage("sg_set_group_trend", SgTrendParams, TREND_DEFAULTS, "set_group_trend(None) switches the group trend off", "group trend"),
     group_vanished=_Stage("sg_set_group_vanished", SgVanishedParams, VANISHED_DEFAULTS, "set_group_vanished(None) switches the list off",
                           "group vanished"),
+    group_node_trend=_Stage("sg_set_group_node_trend", SgTrendParams, TREND_DEFAULTS,
+                            "set_group_node_trend(None) switches the workload trend off", "workload trend"),
 )
 
 _lib = None
@@ -457,14 +466,15 @@ class ServiceGraph:
         m = min(ns.value, cap)
         return (*[o[:m] for o in outs], nt.value)
 
-    def _node_cap(self, k: int, cap: Optional[int]) -> int:
-        """a node selection's cap: the caller's, else k, else (k = 0) the window's node count — one sg_window_nodes(NULL, 0) call"""
+    def _node_cap(self, k: int, cap: Optional[int], count=None) -> int:
+        """a node selection's cap: the caller's, else k, else (k = 0) the window's node count — one count(h, NULL, 0, &n) call
+        (sg_window_nodes; sg_window_group_nodes for the workload rows)"""
         if cap is not None:
             return cap
         if k:
             return k
         n = C.c_size_t(0)
-        self._ck(self._l.sg_window_nodes(self._h, None, 0, C.byref(n)))
+        self._ck((count or self._l.sg_window_nodes)(self._h, None, 0, C.byref(n)))
         return n.value
 
     def _pointers(self, call, n: int) -> tuple:
@@ -867,6 +877,60 @@ class ServiceGraph:
         that window's stream)."""
         self._ck(self._l.sg_window_groups_select(self._h, self._by(by), k, min_value, d_out or None, d_index or None, cap, d_n,
                                                  stream or None))
+
+    # ---- workload rows (K16): the group edges rolled up per workload, their baselines and selection ----
+    def set_group_nodes(self, on: bool = True):
+        """Switch the per-window workload rows on (sg_set_group_nodes: allocates its buffers; needs the groups on) or off (frees them
+        and the workload trend).  Any set_groups call switches them off."""
+        self._ck(self._l.sg_set_group_nodes(self._h, 1 if on else 0))
+
+    def window_group_nodes(self) -> np.ndarray:
+        """NODE_DTYPE rows of the last read window (sg_window_group_nodes), one per workload, ascending by group key: the groups by
+        id, then the ungrouped KNOWN nodes, LABEL, OBIP — not by the raw ref word"""
+        return self._counted(self._l.sg_window_group_nodes, NODE_DTYPE)
+
+    def window_group_nodes_buffer(self) -> Tuple[int, int]:
+        """(device pointer of the sg_node_out workload rows, of their u64 count) of the window window_run closed last
+        (sg_window_group_nodes_buffer)"""
+        return self._pointers(self._l.sg_window_group_nodes_buffer, 2)
+
+    def set_group_node_trend(self, params: Optional[dict] = (), **kw):
+        """Switch the per-workload baseline on (sg_set_group_node_trend; the parameters of set_trend, max_entries 0 = 4 x the row
+        capacity; needs the workload rows on; (re)enabling starts an empty baseline) or off: set_group_node_trend(None)."""
+        self._set_stage("group_node_trend", params, kw)
+
+    def window_group_node_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """NODE_TREND_DTYPE rows of the last read window (sg_window_group_node_trend), row k for row k of window_group_nodes(); or
+        the rows at `index` (window_group_nodes_top's indices; only those cross PCIe)."""
+        return self._window_rows(self._l.sg_window_group_node_trend, NODE_TREND_DTYPE, index)
+
+    def window_group_node_trend_buffer(self) -> int:
+        """device pointer of the workload trend rows of the window window_run closed last (sg_window_group_node_trend_buffer)"""
+        return self._pointers(self._l.sg_window_group_node_trend_buffer, 1)[0]
+
+    def group_node_trend_entries(self) -> np.ndarray:
+        """the workload baseline in key order, TREND_ENTRY_DTYPE with from_key = the workload key, to_key = side (0 in, 1 out)
+        (sg_group_node_trend_entries)"""
+        return self._counted(self._l.sg_group_node_trend_entries, TREND_ENTRY_DTYPE)
+
+    def group_node_trend_stats(self) -> SgTrendStats:
+        return self._stats(self._l.sg_group_node_trend_stats_get, SgTrendStats)
+
+    def window_group_nodes_top(self, k: int, min_value: float = float("-inf"), by: str = "score", cap: Optional[int] = None):
+        """(workload rows, row indices, n_nodes) of a selection over the last read window's workload rows
+        (sg_window_group_nodes_top): window_nodes_top with "node row" read as "workload row".  by: a key of NSEL_BY.  cap defaults
+        to k (k > 0) or the window's row count."""
+        b = self._nby(by)
+        return self._top(lambda *a: self._l.sg_window_group_nodes_top(self._h, b, k, min_value, *a),
+                         self._node_cap(k, cap, self._l.sg_window_group_nodes), NODE_DTYPE, np.uint32)
+
+    def window_group_nodes_select(self, k: int, min_value: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0,
+                                  by: str = "score"):
+        """Select from the workload rows of the window window_run closed last into device memory (sg_window_group_nodes_select):
+        d_out [cap] rows (0 = none), d_index [cap] u32 (0 = none), d_n one u64 = rows selected; enqueued on `stream` (0 = that
+        window's stream)."""
+        self._ck(self._l.sg_window_group_nodes_select(self._h, self._nby(by), k, min_value, d_out or None, d_index or None, cap, d_n,
+                                                      stream or None))
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

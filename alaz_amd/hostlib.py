@@ -38,6 +38,13 @@ WORKLOAD_VANISHED_DTYPE = np.dtype([("from_key", "<u8"), ("to_key", "<u8"), ("fr
                                    + [(f, "<f8") for f in ("lat_mean", "lat_dev", "err_mean", "err_dev")]
                                    + [(f, "<u4") for f in ("n", "last", "row", "pad")])
 
+#: sgh_workload_node of host_capi.cpp: one workload row (GraphDS::WorkloadNodes) — who it is ("workload" with the owner's UID, or
+#: pod / service / outbound), then the engine's sg_node_out as engine.NODE_DTYPE has it
+def _workload_node_dtype():
+    from .engine import NODE_DTYPE
+    return np.dtype([("type", "S16"), ("uid", "S160"), ("row", NODE_DTYPE)])
+
+
 _lib = None
 
 
@@ -115,6 +122,10 @@ def load() -> C.CDLL:
             "sgh_graphds_workload_trends": (C.c_long, [P, P, sz]),
             "sgh_graphds_workload_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]),
             "sgh_graphds_workload_vanished": (C.c_long, [P, P, sz]), "sgh_mock_k15_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_workload_nodes": (C.c_int, [P, C.c_int]),
+            "sgh_graphds_set_workload_node_trend": (C.c_int, [P, u32, u32, u32, C.c_uint64]),
+            "sgh_graphds_workload_nodes": (C.c_long, [P, P, sz]), "sgh_graphds_workload_node_trends": (C.c_long, [P, P, sz]),
+            "sgh_graphds_workload_nodes_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]), "sgh_mock_k16_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -485,6 +496,41 @@ class GraphDS:
         n = self._l.sgh_mock_k15_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k15_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the workload rows (K16) ----
+    def set_workload_nodes(self, on: bool = True) -> int:
+        """GraphDS::SetWorkloadNodes: the per-window workload rows on or off (rc)"""
+        return self._l.sgh_graphds_set_workload_nodes(self._g, 1 if on else 0)
+
+    def set_workload_node_trend(self, shift: int = 0, warmup: int = 0, ttl: int = 0, max_entries: int = 0) -> int:
+        """GraphDS::SetWorkloadNodeTrend: the per-workload baseline on (a 0 = the parameter's default; rc)"""
+        return self._l.sgh_graphds_set_workload_node_trend(self._g, shift, warmup, ttl, max_entries)
+
+    def workload_nodes(self) -> np.ndarray:
+        """GraphDS::WorkloadNodes: the last flushed window's workload rows — type, uid and row (engine.NODE_DTYPE)"""
+        return self._rows("WorkloadNodes", self._l.sgh_graphds_workload_nodes, _workload_node_dtype())
+
+    def workload_node_trends(self) -> np.ndarray:
+        """GraphDS::WorkloadNodeTrends: engine.NODE_TREND_DTYPE, row k for row k of workload_nodes()"""
+        from .engine import NODE_TREND_DTYPE
+        return self._rows("WorkloadNodeTrends", self._l.sgh_graphds_workload_node_trends, NODE_TREND_DTYPE)
+
+    def workload_nodes_top(self, by: int, k: int, min_value: float = float("-inf")):
+        """GraphDS::WorkloadNodesTop: (the selected workload rows as workload_nodes() gives them, their indices) — by = SG_NSEL_*"""
+        n = self._l.sgh_graphds_workload_nodes_top(self._g, by, k, min_value, None, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadNodesTop failed: {n}")
+        out, idx = np.zeros(max(n, 1), dtype=_workload_node_dtype()), np.zeros(max(n, 1), dtype=np.uint32)
+        self._l.sgh_graphds_workload_nodes_top(self._g, by, k, min_value, out.ctypes.data, idx.ctypes.data, n)
+        return out[:n], idx[:n]
+
+    def mock_k16_ops(self) -> np.ndarray:
+        """the stand-in engine's K16 calls in order, four u64 each: (1, on, 0, 0) per sg_set_group_nodes, (2, shift, warmup, ttl) per
+        sg_set_group_node_trend, (3, by, k, the bits of min_value) per sg_window_group_nodes_top"""
+        n = self._l.sgh_mock_k16_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k16_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

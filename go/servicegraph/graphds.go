@@ -1170,6 +1170,157 @@ func (g *GraphDS) WindowWorkloadsVanished() ([]VanishedWorkload, int, error) {
 	return out, int(n), nil
 }
 
+// WorkloadNode is one workload row of a window (sg_node_out over group edges, K16): Ref is a group ref — type 3 and the group id,
+// or the node's own ref when it is ungrouped.  The Out fields reduce the group edges the workload calls through, the In fields
+// those it is called through; Edges count peer workloads, not rows; WorstRow is a row index of the window's rows.
+type WorkloadNode struct {
+	Ref                                                                  uint32
+	OutCount, InCount, OutErr, InErr, OutSumNs, InSumNs                  uint64
+	OutSumSqUs, InSumSqUs, OutMaxNs, InMaxNs, OutScoreQ32, InScoreQ32    uint64
+	OutEdges, InEdges, OutAlive, InAlive, OutWorstRow, InWorstRow        uint32
+	OutScoreMax, InScoreMax, Score                                       float32
+}
+
+// NodeTrend is one workload row against its own past (sg_node_trend), a side each for the calls it receives and those it makes.
+type NodeTrend struct {
+	InLatDev, InErrDev, OutLatDev, OutErrDev, InBaseMeanUs, OutBaseMeanUs float32
+	InSeen, OutSeen                                                       uint32
+}
+
+// The keys of WindowWorkloadNodesTop (SG_NSEL_*).
+const (
+	NodeByScore     = uint32(C.SG_NSEL_SCORE)
+	NodeByInLatDev  = uint32(C.SG_NSEL_IN_LAT_DEV)
+	NodeByInErrDev  = uint32(C.SG_NSEL_IN_ERR_DEV)
+	NodeByOutLatDev = uint32(C.SG_NSEL_OUT_LAT_DEV)
+	NodeByOutErrDev = uint32(C.SG_NSEL_OUT_ERR_DEV)
+	NodeByNew       = uint32(C.SG_NSEL_NEW)
+)
+
+// SetWorkloadNodes switches the per-window workload rows on or off, behind SetGroups: every window's group edges rolled up per
+// workload on the device.  Any SetGroups call switches them off.
+func (g *GraphDS) SetWorkloadNodes(on bool) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.sg_set_group_nodes(g.h, v); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_group_nodes = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+// SetWorkloadNodeTrend switches the per-workload baseline on, behind SetWorkloadNodes (a 0 is the parameter's default: shift 4,
+// warmup 4, ttl 64, maxEntries 4 x the row capacity); it starts empty.  It is keyed by workload and survives a rollout.
+func (g *GraphDS) SetWorkloadNodeTrend(shift, warmup, ttl uint32, maxEntries uint64) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var tp C.sg_trend_params
+	tp.struct_size = C.uint32_t(unsafe.Sizeof(tp))
+	tp.shift, tp.warmup, tp.ttl, tp.max_entries = C.uint32_t(shift), C.uint32_t(warmup), C.uint32_t(ttl), C.uint64_t(maxEntries)
+	if rc := C.sg_set_group_node_trend(g.h, &tp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_group_node_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func goWorkloadNodes(ns []C.sg_node_out) []WorkloadNode {
+	out := make([]WorkloadNode, len(ns))
+	for i := range ns {
+		n, o := &ns[i], &out[i]
+		o.Ref = uint32(n.ref)
+		o.OutCount, o.InCount, o.OutErr, o.InErr = uint64(n.out_count), uint64(n.in_count), uint64(n.out_err), uint64(n.in_err)
+		o.OutSumNs, o.InSumNs, o.OutSumSqUs, o.InSumSqUs = uint64(n.out_sum_ns), uint64(n.in_sum_ns), uint64(n.out_sumsq_us), uint64(n.in_sumsq_us)
+		o.OutMaxNs, o.InMaxNs, o.OutScoreQ32, o.InScoreQ32 = uint64(n.out_max_ns), uint64(n.in_max_ns), uint64(n.out_score_q32), uint64(n.in_score_q32)
+		o.OutEdges, o.InEdges, o.OutAlive, o.InAlive = uint32(n.out_edges), uint32(n.in_edges), uint32(n.out_alive), uint32(n.in_alive)
+		o.OutWorstRow, o.InWorstRow = uint32(n.out_worst_row), uint32(n.in_worst_row)
+		o.OutScoreMax, o.InScoreMax, o.Score = float32(n.out_score_max), float32(n.in_score_max), float32(n.score)
+	}
+	return out
+}
+
+// WindowWorkloadNodes returns the workload rows of the window FlushWindow returned last, ascending by group key: the workloads by
+// id, then the ungrouped nodes.
+func (g *GraphDS) WindowWorkloadNodes() ([]WorkloadNode, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_group_nodes(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_nodes = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	ns := make([]C.sg_node_out, int(n))
+	if rc := C.sg_window_group_nodes(g.h, &ns[0], C.size_t(len(ns)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_nodes = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(n) < len(ns) {
+		ns = ns[:int(n)]
+	}
+	return goWorkloadNodes(ns), nil
+}
+
+// WindowWorkloadNodeTrend returns the trend rows of the window FlushWindow returned last: row k for row k of WindowWorkloadNodes,
+// or, with an index (WindowWorkloadNodesTop's), the rows of those workloads only.
+func (g *GraphDS) WindowWorkloadNodeTrend(index []uint32) ([]NodeTrend, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	var idx *C.uint32_t
+	if index != nil {
+		if len(index) == 0 {
+			return nil, nil
+		}
+		idx, n = (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index))
+	} else if rc := C.sg_window_group_node_trend(g.h, nil, 0, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_node_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	ts := make([]C.sg_node_trend, int(n))
+	if rc := C.sg_window_group_node_trend(g.h, idx, C.size_t(len(index)), &ts[0], C.size_t(len(ts)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_node_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	out := make([]NodeTrend, len(ts))
+	for i := range ts {
+		t := &ts[i]
+		out[i] = NodeTrend{float32(t.in_lat_dev), float32(t.in_err_dev), float32(t.out_lat_dev), float32(t.out_err_dev),
+			float32(t.in_base_mean_us), float32(t.out_base_mean_us), uint32(t.in_seen), uint32(t.out_seen)}
+	}
+	return out, nil
+}
+
+// WindowWorkloadNodesTop selects from the workload rows of the window FlushWindow returned last on the device
+// (sg_window_group_nodes_top): the k rows with the highest value >= minValue, descending, ties by position (k = 0: every such
+// row, in order), and their indices.  by: NodeByScore (it needs SetWorkloadNodes only) or a key of the baseline.
+func (g *GraphDS) WindowWorkloadNodesTop(by, k uint32, minValue float32) ([]WorkloadNode, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_group_nodes_top(g.h, C.uint32_t(by), 0, C.float(minValue), nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, fmt.Errorf("servicegraph: sg_window_group_nodes_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil
+	}
+	ns, index := make([]C.sg_node_out, room), make([]uint32, room)
+	if rc := C.sg_window_group_nodes_top(g.h, C.uint32_t(by), C.uint32_t(k), C.float(minValue), &ns[0], (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, fmt.Errorf("servicegraph: sg_window_group_nodes_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		ns, index = ns[:int(sel)], index[:int(sel)]
+	}
+	return goWorkloadNodes(ns), index, nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

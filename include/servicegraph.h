@@ -821,6 +821,60 @@ int sg_window_groups_top(sg_handle h, uint32_t by, uint32_t k, float min_value, 
 int sg_window_groups_select(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_group_edge* d_out, uint32_t* d_index,
                             size_t cap, uint64_t* d_n, void* stream);
 
+/* ---- workload rows (K16): the window's group edges rolled up per workload, their baselines and selection ---------------------- *
+ * Opt-in (sg_set_group_nodes), behind the groups; without it nothing is allocated or launched.  It needs none of K8 - K13 or K15
+ * and changes none of them.  There is no new struct and no new constant: the rows are sg_node_out, the trend rows sg_node_trend,
+ * the entries sg_trend_entry, the parameters sg_trend_params, the selection keys SG_NSEL_*.
+ *   node set   of a window: every from_ref and to_ref of its group edges — group refs: SG_REF_GROUP | g, or the node's own ref when
+ *              it is ungrouped.  One sg_node_out per node
+ *   order      ascending by the group key gk of sg_window_groups: the groups by id, then the ungrouped KNOWN nodes by id, then
+ *              LABEL, then OBIP by index.  This is NOT ascending by the raw ref word: SG_REF_GROUP is type 3, and the groups come
+ *              first
+ *   fields     for node x the out_* fields reduce the group edges with from_ref == x, the in_* fields those with to_ref == x; a
+ *              group edge inside a workload (from_ref == to_ref) counts on both sides.
+ *                *_edges      the number of GROUP EDGES on that side (distinct peer workloads), not rows
+ *                *_count, *_err, *_sum_ns, *_sumsq_us, *_score_q32
+ *                             wrapping u64 sums of count, err_count, sum_ns, sumsq_us, score_q32
+ *                *_max_ns     max of max_ns;   *_alive: wrapping u32 sum of alive
+ *                *_score_max, *_worst_row
+ *                             from the max of the 64-bit key (order-preserving key of score_max << 32 | ~worst_row) over the
+ *                             side's group edges: the largest score among the underlying ROWS and the smallest row index that has
+ *                             it — a row index of the window's rows, as in the node rollup; row_group[worst_row] names the group
+ *                             edge.  A side without group edges: 0.0f and 0xFFFFFFFF
+ *                score        max(out_score_max, in_score_max);   ref: the group ref
+ *              Every field is an integer sum, an integer max or the max of a key: the result has one value, and it equals the node
+ *              rollup's definition over the window's rows with each ref replaced by its group ref, but for *_edges and the order.
+ * sg_set_group_nodes(h, 1 / 0): SG_ESTATE with the groups off or while a flush is open; SG_EINVAL when max_groups + the node
+ * capacity (max_known_nodes + max_labels + max_obip) exceeds 2^21 group keys — pass a tighter max_groups to sg_set_groups: the
+ * tables are per key (256 MB and 128 MB of partials at 2^21 keys).  It allocates here, never at sg_create or sg_set_groups.  ANY
+ * sg_set_groups call frees this stage and everything behind it.  A window has at most min(2^21 keys, 2 x max_edges) rows.       */
+int sg_set_group_nodes(sg_handle h, int on);
+/* The workload rows of the last READ window: *n = rows of the window, min(*n, cap) are written (sg_window_nodes' rules).  SG_ESTATE
+ * with the stage off, while a flush is open, or when that window was closed while the stage was off.                            */
+int sg_window_group_nodes(sg_handle h, sg_node_out* out, size_t cap, size_t* n);
+/* Device sg_node_out[] and its uint64_t count of the window sg_window_run closed last (valid until its slot is reused; read them
+ * on that window's stream).                                                                                                     */
+int sg_window_group_nodes_buffer(sg_handle h, void** d_nodes, void** d_count);
+/* Baselines per workload and side: the node baselines word for word, with the key (wk(ref), side) — wk the workload key of the
+ * group trend (the group id for a group, otherwise the edge trend's ref key one type up, the IPv4 address for an OBIP ref).
+ * Ascending gk is ascending wk, so a window's 2 N samples (sample 2 k + side of row k, side 0 = in, 1 = out) are strictly ascending
+ * and the update is the edge trend's merge.  max_entries 0 = min(2^31, 4 x the row capacity); the stage counts its own trend
+ * windows; a side with count 0 neither creates nor refreshes an entry; sg_group_assign does not touch the baseline: a workload
+ * keeps its entry through a rollout.  NULL = off; sg_set_group_nodes(h, 0) and any sg_set_groups call switch it off.  SG_ESTATE
+ * with the workload rows off or while a flush is open, SG_EINVAL on bad parameters.                                             */
+int sg_set_group_node_trend(sg_handle h, const sg_trend_params* p);
+int sg_window_group_node_trend(sg_handle h, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n);
+int sg_window_group_node_trend_buffer(sg_handle h, void** d_trend);
+int sg_group_node_trend_entries(sg_handle h, sg_trend_entry* out, size_t cap, size_t* n);
+int sg_group_node_trend_stats_get(sg_handle h, sg_trend_stats* out);
+/* Selection: sg_window_nodes_top / sg_window_nodes_select with "node row" read as "workload row" — the SG_NSEL_* keys, the tie rule
+ * (by row position) and the error codes are the same; SG_NSEL_SCORE needs the workload rows only.  The selected rows are
+ * byte-identical to sg_window_group_nodes' and the indices can be passed to sg_window_group_node_trend.                         */
+int sg_window_group_nodes_top(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index,
+                              size_t cap, size_t* n_selected, size_t* n_nodes);
+int sg_window_group_nodes_select(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out, uint32_t* d_index,
+                                 size_t cap, uint64_t* d_n, void* stream);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
