@@ -166,12 +166,16 @@ struct sg_engine {
     // counts are scratch shared like the baseline; per slot: the list, its count, and whether the window in the slot made one (valid).
     struct Vanished { bool on = false; sg_vanished_params p{}; sgplan::VanishedPlan plan; char* mem = nullptr; u32* th = nullptr; u32* blk = nullptr;
                       std::vector<sg_edge_vanished*> rows; std::vector<u64*> count; std::vector<char> valid; } vanished;
-    // K9, the node rollup (sg_nodes.h): allocated at sg_set_nodes (sg_plan.hpp plan_nodes), one allocation.  The tables are scratch
+    // The rollup (sg_nodes.h), K9's over the edge rows (nodes, sg_plan.hpp plan_nodes) or K16's over the group edges (gnodes,
+    // plan_group_nodes; sg_group_nodes.h): allocated at sg_set_nodes / sg_set_group_nodes, one allocation.  The tables are scratch
     // shared by the window slots: every rollup waits for the previous one (ev), whichever slot's stream it runs on.  Per slot: the
     // node rows and count, and whether the window in the slot was rolled up (valid).
-    struct Nodes { bool on = false; sgplan::NodesPlan plan; char* mem = nullptr; u32* dst = nullptr; K9Side* tout = nullptr; K9Side* tin = nullptr;
-                   K9Side* part = nullptr; u32* blk = nullptr; std::vector<sg_node_out*> rows; std::vector<u64*> count; std::vector<char> valid;
-                   hipEvent_t ev = nullptr; bool pending = false; } nodes;
+    struct RollupState { bool on = false; char* mem = nullptr; u32* dst = nullptr; K9Side* tout = nullptr; K9Side* tin = nullptr;
+                         K9Side* part = nullptr; u32* blk = nullptr; std::vector<sg_node_out*> rows; std::vector<u64*> count; std::vector<char> valid;
+                         hipEvent_t ev = nullptr; bool pending = false; };
+    template <class Plan>
+    struct Rollup : RollupState { Plan plan; };
+    Rollup<sgplan::NodesPlan> nodes;
     // K10, the per-node baselines (sg_node_trend.h): a Baseline, freed with the rollup
     Baseline<sg_node_trend> ntrend;
     // node selection (K7 over node rows): scratch of plan_select(ncap) allocated at the first one, with the counter block k10_keys
@@ -219,12 +223,8 @@ struct sg_engine {
     // selection over group edges (K7 over K14's rows): plan_group_select's block, allocated at the first one — K7's scratch over
     // max_edges keys, the counter block k15_keys fills, an index array and the host form's staging of SG_SELECT_MAX_K group edges
     struct GSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; sg_group_edge* stage = nullptr; char* mem = nullptr; u64 stage_rows = 0; } gsel;
-    // K16, the workload rows (sg_group_nodes.h): allocated at sg_set_group_nodes (sg_plan.hpp plan_group_nodes), one allocation, freed
-    // with the groups.  The tables over the group keys are scratch shared by the window slots: every rollup waits for the previous
-    // one (ev).  Per slot: the workload rows and their count, and whether the window in the slot was rolled up (valid).
-    struct GroupNodes { bool on = false; sgplan::GroupNodesPlan plan; char* mem = nullptr; u32* dst = nullptr; K9Side* tout = nullptr; K9Side* tin = nullptr;
-                        K9Side* part = nullptr; u32* blk = nullptr; std::vector<sg_node_out*> rows; std::vector<u64*> count; std::vector<char> valid;
-                        hipEvent_t ev = nullptr; bool pending = false; } gnodes;
+    // K16, the workload rows: the rollup over the group keys, freed with the groups
+    Rollup<sgplan::GroupNodesPlan> gnodes;
     // its baseline (K10's walk under workload keys), allocated at sg_set_group_node_trend, and the selection over workload rows:
     // plan_group_node_select's block, allocated at the first one, freed with the workload rows (its sizes are theirs)
     Baseline<sg_node_trend> gntrend;
@@ -719,6 +719,30 @@ void free_stage(X& x) {
     if (x.ev) hipEventDestroy(x.ev);
     x = X{};
 }
+// how a stage's messages name it: "<call>: <off>" and "... was closed while <was>"
+struct StageWords { const char* off; const char* was; };
+constexpr StageWords kNodesWords{"the node rollup is off (sg_set_nodes)", "the node rollup was off"};
+constexpr StageWords kVanishedWords{"the vanished list is off (sg_set_vanished)", "the vanished list was off"};
+constexpr StageWords kNodeTrendWords{"the node trend is off (sg_set_node_trend)", "the node trend was off"};
+constexpr StageWords kRankWords{"the ranking is off (sg_set_rank)", "the ranking was off"};
+constexpr StageWords kIncidentsWords{"the incidents are off (sg_set_incidents)", "the incidents were off"};
+constexpr StageWords kTracksWords{"tracking is off (sg_set_tracks)", "tracking was off"};
+constexpr StageWords kGroupsWords{"the groups are off (sg_set_groups)", "the groups were off"};
+constexpr StageWords kGroupTrendWords{"the group trend is off (sg_set_group_trend)", "the group trend was off"};
+constexpr StageWords kGroupNodesWords{"the workload rows are off (sg_set_group_nodes)", "the workload rows were off"};
+constexpr StageWords kGroupNodeTrendWords{"the workload trend is off (sg_set_group_node_trend)", "the workload trend was off"};
+constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
+// A node space: what the baseline, the selection and the readbacks over node rows work on — K9's nodes or K16's workloads.  Its
+// rollup, its baseline, its selection scratch, the rows a window can have, and how its messages name it: the rollup, the baseline,
+// "<sel>: ..." of a selection, "... beyond the window's <rows_of>".
+struct NodeSpace {
+    sg_engine::RollupState* roll; sg_engine::Baseline<sg_node_trend>* trend; sg_engine::NSel* sel; u32 cap;
+    StageWords roll_w, trend_w; const char* sel_w; const char* rows_of;
+};
+NodeSpace node_space(sg_engine* e) { return {&e->nodes, &e->ntrend, &e->nsel, e->plan.ncap, kNodesWords, kNodeTrendWords, "node selection", "nodes"}; }
+NodeSpace workload_space(sg_engine* e) {
+    return {&e->gnodes, &e->gntrend, &e->gnsel, e->gnodes.plan.nc, kGroupNodesWords, kGroupNodeTrendWords, "workload selection", "workload rows"};
+}
 
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
 static_assert(sizeof(KcScratch) <= sgplan::kPrepareLds, "a folded close's prepare workgroup lays KcScratch over pass B's dynamic LDS");
@@ -778,39 +802,41 @@ int launch_trend(sg_engine* e, hipStream_t s) {
 static_assert(sgplan::kNodesThreads == K9_THREADS && sgplan::kNodesChunk == K9_CHUNK && sgplan::kNodesRangeNodes == K9_IN_NR &&
               sgplan::kNodesMaxWgs == K9_MAX_WGS && sgplan::kNodesMaxWgs <= K9_SCAN_THREADS && sgplan::kNodesSideBytes == sizeof(K9Side),
               "plan_nodes sizes the launches of sg_nodes.h");
-// enqueue the rollup of the window in slot cur on stream s, behind the previous rollup (any stream)
-int launch_nodes(sg_engine* e, hipStream_t s) {
-    sg_engine::WinSlot& w = work(e);
-    sg_engine::Nodes& n = e->nodes;
-    const sgplan::NodesPlan& P = n.plan;
-    NodesArgs a = nodes_view(e, w, P.ncap);
-    a.slices = P.slices; a.node_per = P.node_per;
-    a.dst = n.dst; a.tout = n.tout; a.tin = n.tin; a.part = n.part; a.blk = n.blk;
-    a.out = n.rows[e->cur]; a.count = n.count[e->cur];
+// enqueue a rollup of the window in slot cur on stream s, behind the previous one of n (any stream): nd, the NodesArgs inside the
+// argument a, gets the plan's grid and n's tables and slot buffers; five plain launches, the source's four kernels around k9_scan
+template <class Args>
+int launch_rollup(sg_engine* e, sg_engine::RollupState& n, const sgplan::NodesPlan& P, hipStream_t s, Args& a, NodesArgs& nd,
+                  void (*out)(Args), void (*in_part)(Args), void (*count)(Args), void (*write)(Args)) {
+    nd.slices = P.slices; nd.node_per = P.node_per;
+    nd.dst = n.dst; nd.tout = n.tout; nd.tin = n.tin; nd.part = n.part; nd.blk = n.blk;
+    nd.out = n.rows[e->cur]; nd.count = n.count[e->cur];
     if (const int rc = stage_wait(e, n, s)) return rc;
-    hipLaunchKernelGGL(k9_out, dim3(P.out_wgs), dim3(K9_THREADS), 0, s, a);
-    hipLaunchKernelGGL(k9_in_part, dim3(P.ranges * P.slices), dim3(K9_IN_THREADS), (size_t)P.lds_bytes, s, a);
-    hipLaunchKernelGGL(k9_count, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
-    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a, P.node_wgs);
-    hipLaunchKernelGGL(k9_write, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
+    hipLaunchKernelGGL(out, dim3(P.out_wgs), dim3(K9_THREADS), 0, s, a);
+    hipLaunchKernelGGL(in_part, dim3(P.ranges * P.slices), dim3(K9_IN_THREADS), (size_t)P.lds_bytes, s, a);
+    hipLaunchKernelGGL(count, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, nd, P.node_wgs);
+    hipLaunchKernelGGL(write, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
     if (const int rc = stage_done(e, n, s)) return rc;
     n.valid[e->cur] = 1;
     return SG_OK;
 }
+int launch_nodes(sg_engine* e, hipStream_t s) {
+    NodesArgs a = nodes_view(e, work(e), e->nodes.plan.ncap);
+    return launch_rollup(e, e->nodes, e->nodes.plan, s, a, a, k9_out, k9_in_part, k9_count, k9_write);
+}
 // ---- K10, the per-node baselines (engine lock held) ------------------------------------------------------------------------------
 static_assert(sizeof(sg_node_trend) == 32 && sizeof(K10Sample) == 40, "sg_node_trend layout");
-// enqueue the node baseline's update by the window in slot cur on stream s (behind its rollup, on the same stream); the window's
-// node trend rows go to the slot's buffer
-int launch_node_trend(sg_engine* e, hipStream_t s) {
-    sg_engine::WinSlot& w = work(e);
-    sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
+// enqueue the update of node space ns's baseline by the window in slot cur on stream s (behind its rollup, on the same stream);
+// the window's trend rows go to the slot's buffer.  count / write: the walk under the space's keys (k10_*, k16_t*)
+int launch_node_trend(sg_engine* e, const NodeSpace& ns, hipStream_t s, void (*count)(NodeTrendArgs), void (*write)(NodeTrendArgs)) {
+    sg_engine::Baseline<sg_node_trend>& t = *ns.trend;
     NodeTrendArgs a{};
-    a.t = baseline_args(w, t);
-    a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur]; a.ncap = e->nodes.plan.ncap; a.out = t.rows[e->cur];
+    a.t = baseline_args(work(e), t);
+    a.nodes = ns.roll->rows[e->cur]; a.count = ns.roll->count[e->cur]; a.ncap = ns.cap; a.out = t.rows[e->cur];
     if (const int rc = enqueue_baseline(e, t, s, [&] {
-            hipLaunchKernelGGL(k10_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
             hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs);
-            hipLaunchKernelGGL(k10_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
         })) return rc;
     t.valid[e->cur] = 1;
     return SG_OK;
@@ -1014,44 +1040,16 @@ void free_group_trend(sg_engine* e) {
 static_assert(offsetof(sg_group_edge, edges) == 56 && offsetof(sg_group_edge, alive) == 68 && offsetof(sg_group_edge, worst_row) == 72 &&
               offsetof(sg_group_edge, sumsq_us) == 24 && offsetof(sg_group_edge, max_ns) == 32 && offsetof(sg_group_edge, score_q32) == 40,
               "k16_load reads sg_group_edge by word");
-// enqueue the rollup of the group edges of the window in slot cur on stream s (behind its contraction, on the same stream) and behind
-// the previous rollup (any stream): five plain launches, the workload rows and their count go to the slot's buffers
+// enqueue the rollup of the group edges of the window in slot cur on stream s (behind its contraction, on the same stream): the
+// workload rows and their count go to the slot's buffers
 int launch_group_nodes(sg_engine* e, hipStream_t s) {
-    sg_engine::WinSlot& w = work(e);
-    sg_engine::GroupNodes& n = e->gnodes;
-    const sgplan::GroupNodesPlan& P = n.plan;
+    const sgplan::GroupNodesPlan& P = e->gnodes.plan;
     GroupNodesArgs a{};
-    a.nd = nodes_view(e, w, P.ncap);
+    a.nd = nodes_view(e, work(e), P.ncap);
     a.nd.max_edges = std::max<u64>(e->cfg.max_edges, 1);
-    a.nd.slices = P.slices; a.nd.node_per = P.node_per;
-    a.nd.dst = n.dst; a.nd.tout = n.tout; a.nd.tin = n.tin; a.nd.part = n.part; a.nd.blk = n.blk;
-    a.nd.out = n.rows[e->cur]; a.nd.count = n.count[e->cur];
     a.groups = e->grp.rows[e->cur]; a.gcount = e->grp.count[e->cur];
     a.max_groups = P.max_groups; a.gk = (u32)P.gk; a.hi_group = e->grp.hi_group; a.nc = P.nc;
-    if (const int rc = stage_wait(e, n, s)) return rc;
-    hipLaunchKernelGGL(k16_out, dim3(P.out_wgs), dim3(K9_THREADS), 0, s, a);
-    hipLaunchKernelGGL(k16_in_part, dim3(P.ranges * P.slices), dim3(K9_IN_THREADS), (size_t)P.lds_bytes, s, a);
-    hipLaunchKernelGGL(k16_count, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
-    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a.nd, P.node_wgs);
-    hipLaunchKernelGGL(k16_write, dim3(P.node_wgs), dim3(K9_THREADS), 0, s, a);
-    if (const int rc = stage_done(e, n, s)) return rc;
-    n.valid[e->cur] = 1;
-    return SG_OK;
-}
-// enqueue the workload-row baseline's update by the window in slot cur on stream s (behind its rollup, on the same stream)
-int launch_group_node_trend(sg_engine* e, hipStream_t s) {
-    sg_engine::WinSlot& w = work(e);
-    sg_engine::Baseline<sg_node_trend>& t = e->gntrend;
-    NodeTrendArgs a{};
-    a.t = baseline_args(w, t);
-    a.nodes = e->gnodes.rows[e->cur]; a.count = e->gnodes.count[e->cur]; a.ncap = e->gnodes.plan.nc; a.out = t.rows[e->cur];
-    if (const int rc = enqueue_baseline(e, t, s, [&] {
-            hipLaunchKernelGGL(k16_tcount, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-            hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs);
-            hipLaunchKernelGGL(k16_twrite, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-        })) return rc;
-    t.valid[e->cur] = 1;
-    return SG_OK;
+    return launch_rollup(e, e->gnodes, P, s, a, a.nd, k16_out, k16_in_part, k16_count, k16_write);
 }
 // a selection scratch block off (the workload rows': its sizes are the stage's)
 void free_nsel(sg_engine::NSel& s) {
@@ -1117,7 +1115,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     // K9 behind them: it reads the rows and the window counters only; K10 behind K9: the node rows, their count, the outbound IPs
     if (e->nodes.on) {
         if (const int rc = launch_nodes(e, s)) return rc;
-        if (e->ntrend.on) { if (const int rc = launch_node_trend(e, s)) return rc; }
+        if (e->ntrend.on) { if (const int rc = launch_node_trend(e, node_space(e), s, k10_count, k10_write)) return rc; }
         if (e->rank.on) { if (const int rc = launch_rank(e, s)) return rc; }   // K11 behind K9: the rows, the counters, the node rows and their count
         if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
         if (e->trk.on) { if (const int rc = launch_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
@@ -1127,7 +1125,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (e->gtrend.on) { if (const int rc = launch_group_trend(e, s)) return rc; }   // K15 behind K14: the group edges, their count, the outbound IPs
         if (e->gnodes.on) {                                          // K16 behind K14: the group edges and their count; its baseline behind it
             if (const int rc = launch_group_nodes(e, s)) return rc;
-            if (e->gntrend.on) return launch_group_node_trend(e, s);
+            if (e->gntrend.on) return launch_node_trend(e, workload_space(e), s, k16_tcount, k16_twrite);
         }
     }
     return SG_OK;
@@ -1293,11 +1291,11 @@ int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_scor
 }
 
 // ---- node selection (engine lock held) ------------------------------------------------------------------------------------------
-// the scratch at the first node selection (plan_select over the node capacity, the counter block, indices and staging)
-int nsel_reserve(sg_engine* e) {
-    sg_engine::NSel& s = e->nsel;
+// the scratch at the first selection over node space ns (plan_select over its row capacity, the counter block, indices and staging)
+int nsel_reserve(sg_engine* e, const NodeSpace& ns) {
+    sg_engine::NSel& s = *ns.sel;
     if (s.keys) return SG_OK;
-    const sgplan::NodeSelPlan P = sgplan::plan_node_select(e->plan.ncap, sizeof(e->h_ctr));
+    const sgplan::NodeSelPlan P = sgplan::plan_node_select(ns.cap, sizeof(e->h_ctr));
     s.plan = P.sel;
     HIP_TRY(e, hipMalloc((void**)&s.mem, P.total_bytes));
     HIP_TRY(e, hipMemset(s.mem, 0, P.total_bytes));
@@ -1306,42 +1304,22 @@ int nsel_reserve(sg_engine* e) {
     s.idx = at<u32>(s.mem, P.idx_off);
     return sel_init(e, s, s.mem + P.sel_off);
 }
-// the same for the selection over workload rows (K16): plan_group_node_select over the stage's row capacity
-int gnsel_reserve(sg_engine* e) {
-    sg_engine::NSel& s = e->gnsel;
-    if (s.keys) return SG_OK;
-    const sgplan::NodeSelPlan P = sgplan::plan_group_node_select(e->gnodes.plan.nc, sizeof(e->h_ctr));
-    s.plan = P.sel;
-    HIP_TRY(e, hipMalloc((void**)&s.mem, P.total_bytes));
-    HIP_TRY(e, hipMemset(s.mem, 0, P.total_bytes));
-    s.stage = at<sg_node_out>(s.mem, P.stage_off);
-    s.ctr = at<u64>(s.mem, P.ctr_off);
-    s.idx = at<u32>(s.mem, P.idx_off);
-    return sel_init(e, s, s.mem + P.sel_off);
-}
-// what a selection over node rows works on: K9's node rows (nsel, ncap) or K16's workload rows (gnsel, their row capacity) —
-// the scratch, the row capacity, every slot's rows and counts, and the event of the stage that writes them
-struct NodeRowsView { sg_engine::NSel* sel; u64 cap; sg_node_out* const* rows; u64* const* count; hipEvent_t ev; bool pending; };
-NodeRowsView node_rows(sg_engine* e) { return {&e->nsel, std::max<u32>(e->plan.ncap, 1), e->nodes.rows.data(), e->nodes.count.data(), e->nodes.ev, e->nodes.pending}; }
-NodeRowsView group_node_rows(sg_engine* e) {
-    return {&e->gnsel, std::max<u32>(e->gnodes.plan.nc, 1), e->gnodes.rows.data(), e->gnodes.count.data(), e->gnodes.ev, e->gnodes.pending};
-}
-// enqueue a selection over the node rows v of slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
+// enqueue a selection over the rows of node space v in slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
 // be NULL), the count to d_n; behind that window's rollup (event) and the previous node selection.  keys(a, wgs) launches the key
 // pass (k10_keys, k11_keys) and waits for what it reads; after(a, grid) launches what else gathers by the selected indices.
 template <class Keys, class After>
-int launch_node_select(sg_engine* e, const NodeRowsView& v, hipStream_t st, int slot, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
+int launch_node_select(sg_engine* e, const NodeSpace& v, hipStream_t st, int slot, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
                        u64 cap, u64* d_n, Keys keys, After after) {
     sg_engine::NSel& s = *v.sel;
     const u32 wgs = s.plan.wgs;
-    const u64 NC = v.cap;
+    const u64 NC = std::max<u32>(v.cap, 1);
     SelArgs a{};
     a.rows = nullptr; a.ctr = s.ctr; a.max_edges = NC; a.k = k; a.min_score = min_value;
     sel_scratch_args(a, s);
     a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, NC); a.n_out = d_n;
     if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
-    if (v.pending) HIP_TRY(e, hipStreamWaitEvent(st, v.ev, 0));
-    const sg_node_out* nodes = v.rows[slot];
+    if (v.roll->pending) HIP_TRY(e, hipStreamWaitEvent(st, v.roll->ev, 0));
+    const sg_node_out* nodes = v.roll->rows[slot];
     if (const int rc = keys(a, wgs)) return rc;
     enqueue_k7_select(st, a, k, wgs, NC);
     const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, NC) : NC);
@@ -1353,23 +1331,13 @@ int launch_node_select(sg_engine* e, const NodeRowsView& v, hipStream_t st, int 
     s.pending = true;
     return SG_OK;
 }
-// by a key of SG_NSEL_*: k10_keys over the node rows and, for a trend key, the window's node trend rows (behind its update)
-int launch_node_select_by(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
-                          u64 cap, u64* d_n) {
-    return launch_node_select(e, node_rows(e), st, slot, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
-        if (by != SG_NSEL_SCORE && e->ntrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->ntrend.ev, 0));
-        const sg_node_trend* tr = by != SG_NSEL_SCORE ? e->ntrend.rows[slot] : nullptr;
-        hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, (const sg_node_out*)e->nodes.rows[slot], (const u64*)e->nodes.count[slot], tr, by, e->nsel.ctr);
-        return (int)SG_OK;
-    }, [](const SelArgs&, dim3) {});
-}
-// the same over the workload rows (K16) and, for a trend key, the window's workload trend rows
-int launch_group_node_select_by(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
-                                u64 cap, u64* d_n) {
-    return launch_node_select(e, group_node_rows(e), st, slot, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
-        if (by != SG_NSEL_SCORE && e->gntrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->gntrend.ev, 0));
-        const sg_node_trend* tr = by != SG_NSEL_SCORE ? e->gntrend.rows[slot] : nullptr;
-        hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, (const sg_node_out*)e->gnodes.rows[slot], (const u64*)e->gnodes.count[slot], tr, by, e->gnsel.ctr);
+// by a key of SG_NSEL_*: k10_keys over the space's rows and, for a trend key, the window's trend rows (behind the baseline's update)
+int launch_node_select_by(sg_engine* e, const NodeSpace& ns, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out,
+                          u32* d_index, u64 cap, u64* d_n) {
+    return launch_node_select(e, ns, st, slot, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+        if (by != SG_NSEL_SCORE && ns.trend->pending) HIP_TRY(e, hipStreamWaitEvent(st, ns.trend->ev, 0));
+        const sg_node_trend* tr = by != SG_NSEL_SCORE ? ns.trend->rows[slot] : nullptr;
+        hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, (const sg_node_out*)ns.roll->rows[slot], (const u64*)ns.roll->count[slot], tr, by, ns.sel->ctr);
         return (int)SG_OK;
     }, [](const SelArgs&, dim3) {});
 }
@@ -1377,7 +1345,7 @@ int launch_group_node_select_by(sg_engine* e, hipStream_t st, int slot, u32 by, 
 int launch_rank_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_share, sg_node_out* d_out, sg_node_rank* d_rank, u32* d_index,
                        u64 cap, u64* d_n) {
     const sg_node_rank* rk = e->rank.rows[slot];
-    return launch_node_select(e, node_rows(e), st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+    return launch_node_select(e, node_space(e), st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
         if (e->rank.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->rank.ev, 0));
         hipLaunchKernelGGL(k11_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, rk, (const u64*)e->nodes.count[slot], e->nsel.ctr);
         return (int)SG_OK;
@@ -1389,15 +1357,15 @@ int launch_rank_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_
 // v's scratch reserved): launch(out_stage, rank_stage, cap, d_n) enqueues it on the read stream; the selected rows, rank rows and
 // indices come back, then the counts
 template <class L>
-int node_top_host(sg_engine* e, const NodeRowsView& v, L launch, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap,
+int node_top_host(sg_engine* e, const NodeSpace& v, L launch, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap,
                   size_t* n_selected, size_t* n_nodes) {
     sg_engine::NSel& s = *v.sel;
-    const u64 NC = v.cap;
+    const u64 NC = std::max<u32>(v.cap, 1);
     const u64 stage = std::min<u64>(cap, NC);
     if (const int rc = launch(out ? s.stage : nullptr, rank_out ? e->rank.stage : nullptr, stage, s.n)) return rc;
     u64 cnt = 0;
     HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipMemcpyAsync(&cnt, v.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipMemcpyAsync(&cnt, v.roll->count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
     HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
     const u64 m = *s.h_n;
     const size_t take = (size_t)std::min<u64>(m, stage);
@@ -1512,20 +1480,28 @@ int baseline_on(sg_engine* e, sg_engine::Baseline<Row>& t, const sg_trend_params
     t.on = true;
     return SG_OK;
 }
-// The opt-in stages' shared readback.
-// how a stage's messages name it: "<call>: <off>" and "... was closed while <was>"
-struct StageWords { const char* off; const char* was; };
-constexpr StageWords kNodesWords{"the node rollup is off (sg_set_nodes)", "the node rollup was off"};
-constexpr StageWords kVanishedWords{"the vanished list is off (sg_set_vanished)", "the vanished list was off"};
-constexpr StageWords kNodeTrendWords{"the node trend is off (sg_set_node_trend)", "the node trend was off"};
-constexpr StageWords kRankWords{"the ranking is off (sg_set_rank)", "the ranking was off"};
-constexpr StageWords kIncidentsWords{"the incidents are off (sg_set_incidents)", "the incidents were off"};
-constexpr StageWords kTracksWords{"tracking is off (sg_set_tracks)", "tracking was off"};
-constexpr StageWords kGroupsWords{"the groups are off (sg_set_groups)", "the groups were off"};
-constexpr StageWords kGroupTrendWords{"the group trend is off (sg_set_group_trend)", "the group trend was off"};
-constexpr StageWords kGroupNodesWords{"the workload rows are off (sg_set_group_nodes)", "the workload rows were off"};
-constexpr StageWords kGroupNodeTrendWords{"the workload trend is off (sg_set_group_node_trend)", "the workload trend was off"};
-constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
+// switch rollup n on (the caller's preconditions passed, P planned into n.plan): the event, one block, the tables and every slot's
+// rows and count carved from it
+template <class K, class F>
+int rollup_on(sg_engine* e, sg_engine::RollupState& n, const sgplan::NodesPlan& P, K in_part, const char* call, F release) {
+    const u32 slots = (u32)e->slots.size();
+    HIP_TRY(e, lds_limit(P.lds_bytes, in_part));
+    HIP_TRY(e, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &n.mem, P.total_bytes, call, release)) return rc;   // (zeroed: the out table starts at zero, the write pass keeps it so)
+    n.tout = at<K9Side>(n.mem, P.table_off[0]);
+    n.tin = at<K9Side>(n.mem, P.table_off[1]);
+    n.part = at<K9Side>(n.mem, P.part_off);
+    n.dst = at<u32>(n.mem, P.dst_off);
+    n.blk = at<u32>(n.mem, P.blk_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = n.mem + P.slot.off + k * P.slot.bytes;
+        n.rows.push_back(at<sg_node_out>(s, P.slot_rows)); n.count.push_back(at<u64>(s, P.slot_count));
+    }
+    n.valid.assign(slots, 0);
+    n.on = true;
+    return SG_OK;
+}
+// The opt-in stages' shared readback (StageWords: in front of the stages' launch code).
 // a host read of stage x's rows of the last read window (slot cur): the stage on, no flush open, the window closed with the stage
 // on; then its kernels done
 template <class X>
@@ -2511,130 +2487,144 @@ int sg_window_vanished_buffer(sg_handle e, void** d_rows, void** d_count) {
     return SG_OK;
 }
 
-// ---- K9, the node rollup ----------------------------------------------------------------------------------------------------
+// ---- K9 and K16: the rollup, its baseline and its selection, once over a node space ---------------------------------------------
+namespace {
+// the readbacks of the rows (engine lock held)
+int nodes_read(sg_engine* e, const NodeSpace& ns, const char* call, sg_node_out* out, size_t cap, size_t* n) {
+    const sg_engine::RollupState& x = *ns.roll;
+    if (const int rc = stage_ready(e, x, call, ns.roll_w)) return rc;
+    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_node_out), out, cap, n);
+}
+int nodes_buffer(sg_engine* e, const NodeSpace& ns, const char* call, void** d_nodes, void** d_count) {
+    const sg_engine::RollupState& x = *ns.roll;
+    int slot;
+    if (const int rc = stage_slot(e, x, call, ns.roll_w, &slot)) return rc;
+    *d_nodes = x.rows[slot]; *d_count = x.count[slot];
+    return SG_OK;
+}
+// the baseline: on with parameters p (NULL: off), its rows, its buffer, its entries and statistics
+int node_trend_set(sg_engine* e, const NodeSpace& ns, const char* call, const sg_trend_params* p) {
+    if (!ns.roll->on) { e->err = std::string(call) + ": " + ns.roll_w.off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    sg_trend_params r{};
+    if (p && sgplan::check_node_trend(*p, ns.cap, &r)) { e->err = std::string(call) + ": bad parameters"; return SG_EINVAL; }
+    sg_engine::Baseline<sg_node_trend>& t = *ns.trend;
+    free_baseline(t);
+    if (!p) return SG_OK;
+    const u32 slots = (u32)e->slots.size();
+    if (const int rc = baseline_on(e, t, r, sgplan::plan_node_trend(ns.cap, slots, r), call, [&t] { free_baseline(t); })) return rc;
+    t.valid.assign(slots, 0);
+    return SG_OK;
+}
+int node_trend_read(sg_engine* e, const NodeSpace& ns, const char* call, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
+    sg_engine::Baseline<sg_node_trend>& t = *ns.trend;
+    if (const int rc = stage_ready(e, t, call, ns.trend_w)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, ns.roll->count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const std::string beyond = std::string(call) + ": a node index beyond the window's " + ns.rows_of;
+    return baseline_rows(e, t, (size_t)cnt, node_index, n_index, out, cap, n, beyond.c_str());
+}
+int node_trend_buffer(sg_engine* e, const NodeSpace& ns, const char* call, void** d_trend) {
+    const sg_engine::Baseline<sg_node_trend>& t = *ns.trend;
+    int slot;
+    if (const int rc = stage_slot(e, t, call, ns.trend_w, &slot)) return rc;
+    *d_trend = t.rows[slot];
+    return SG_OK;
+}
+int node_trend_entries(sg_engine* e, const NodeSpace& ns, const char* call, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (!ns.trend->on) { e->err = std::string(call) + ": " + ns.trend_w.off; return SG_ESTATE; }
+    return baseline_entries(e, *ns.trend, out, cap, n);
+}
+int node_trend_stats(sg_engine* e, const NodeSpace& ns, const char* call, sg_trend_stats* out) {
+    if (!ns.trend->on) { e->err = std::string(call) + ": " + ns.trend_w.off; return SG_ESTATE; }
+    return baseline_stats(e, *ns.trend, out);
+}
+// the selection.  by > 5: SG_EINVAL; the rollup off, or a trend key with the baseline off: SG_ESTATE; then the window in `slot` must have them
+int check_nsel(sg_engine* e, const NodeSpace& ns, u32 by, int slot) {
+    const std::string sel = ns.sel_w;
+    if (by > SG_NSEL_NEW) { e->err = sel + ": unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
+    if (!ns.roll->on) { e->err = sel + ": " + ns.roll_w.off; return SG_ESTATE; }
+    if (by != SG_NSEL_SCORE && !ns.trend->on) { e->err = sel + " by a trend key: " + ns.trend_w.off; return SG_ESTATE; }
+    if (!ns.roll->valid[slot]) { e->err = sel + ": the window was closed while " + ns.roll_w.was; return SG_ESTATE; }
+    if (by != SG_NSEL_SCORE && !ns.trend->valid[slot]) { e->err = sel + ": the window was closed while " + ns.trend_w.was; return SG_ESTATE; }
+    return SG_OK;
+}
+int nodes_top(sg_engine* e, const NodeSpace& ns, const char* call, u32 by, u32 k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
+              size_t* n_selected, size_t* n_nodes) {
+    if (by > SG_NSEL_NEW) { e->err = std::string(ns.sel_w) + ": unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (const int rc = check_nsel(e, ns, by, e->cur)) return rc;
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    return node_top_host(e, ns, [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
+        return launch_node_select_by(e, ns, e->rd_stream, e->cur, by, k, min_value, d_out, nullptr, stage, d_n);
+    }, out, nullptr, node_index, cap, n_selected, n_nodes);
+}
+int nodes_select(sg_engine* e, const NodeSpace& ns, u32 by, u32 k, float min_value, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n,
+                 void* stream) {
+    const int slot = ran_slot(e);
+    if (const int rc = check_nsel(e, ns, by, slot)) return rc;
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    return launch_node_select_by(e, ns, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
+}
+}  // namespace
+
+// ---- K9, the node rollup; K10, the per-node baselines; node selection -------------------------------------------------------------
 int sg_set_nodes(sg_handle e, int on) {
     if (!e || (on != 0 && on != 1)) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
     if (e->cfg.world > 1) { e->err = "sg_set_nodes: the node rollup of a sharded engine is not supported"; return SG_EINVAL; }
     if (e->closing || e->flush_open) { e->err = "sg_set_nodes while a flush is open"; return SG_ESTATE; }
     if (!on) { free_nodes(e); return SG_OK; }
-    sg_engine::Nodes& n = e->nodes;
-    if (n.on) return SG_OK;
-    const u32 slots = (u32)e->slots.size();
-    n.plan = sgplan::plan_nodes(e->cfg.max_edges, e->plan.ncap, slots);
-    const sgplan::NodesPlan& P = n.plan;
-    HIP_TRY(e, lds_limit(P.lds_bytes, k9_in_part));
-    HIP_TRY(e, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
-    if (const int rc = alloc_block(e, &n.mem, P.total_bytes, "sg_set_nodes", [e] { free_nodes(e); })) return rc;   // (zeroed: the out table starts at zero, k9_write keeps it so)
-    n.tout = at<K9Side>(n.mem, P.table_off[0]);
-    n.tin = at<K9Side>(n.mem, P.table_off[1]);
-    n.part = at<K9Side>(n.mem, P.part_off);
-    n.dst = at<u32>(n.mem, P.dst_off);
-    n.blk = at<u32>(n.mem, P.blk_off);
-    for (u32 k = 0; k < slots; k++) {
-        char* s = n.mem + P.slot.off + k * P.slot.bytes;
-        n.rows.push_back(at<sg_node_out>(s, P.slot_rows)); n.count.push_back(at<u64>(s, P.slot_count));
-    }
-    n.valid.assign(slots, 0);
-    n.on = true;
-    return SG_OK;
+    if (e->nodes.on) return SG_OK;
+    e->nodes.plan = sgplan::plan_nodes(e->cfg.max_edges, e->plan.ncap, (u32)e->slots.size());
+    return rollup_on(e, e->nodes, e->nodes.plan, k9_in_part, "sg_set_nodes", [e] { free_nodes(e); });
 }
 int sg_window_nodes(sg_handle e, sg_node_out* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Nodes& x = e->nodes;
-    if (const int rc = stage_ready(e, x, "sg_window_nodes", kNodesWords)) return rc;
-    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_node_out), out, cap, n);
+    return nodes_read(e, node_space(e), "sg_window_nodes", out, cap, n);
 }
 int sg_window_nodes_buffer(sg_handle e, void** d_nodes, void** d_count) {
     if (!e || !d_nodes || !d_count) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Nodes& x = e->nodes;
-    int slot;
-    if (const int rc = stage_slot(e, x, "sg_window_nodes_buffer", kNodesWords, &slot)) return rc;
-    *d_nodes = x.rows[slot]; *d_count = x.count[slot];
-    return SG_OK;
+    return nodes_buffer(e, node_space(e), "sg_window_nodes_buffer", d_nodes, d_count);
 }
-
-// ---- K10, the per-node baselines ---------------------------------------------------------------------------------------------
 int sg_set_node_trend(sg_handle e, const sg_trend_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->nodes.on) { e->err = "sg_set_node_trend: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_node_trend while a flush is open"; return SG_ESTATE; }
-    sg_trend_params r{};
-    if (p && sgplan::check_node_trend(*p, e->nodes.plan.ncap, &r)) { e->err = "sg_set_node_trend: bad parameters"; return SG_EINVAL; }
-    sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
-    free_baseline(t);
-    if (!p) return SG_OK;
-    const u32 slots = (u32)e->slots.size();
-    if (const int rc = baseline_on(e, t, r, sgplan::plan_node_trend(e->nodes.plan.ncap, slots, r), "sg_set_node_trend", [&t] { free_baseline(t); })) return rc;
-    t.valid.assign(slots, 0);
-    return SG_OK;
+    return node_trend_set(e, node_space(e), "sg_set_node_trend", p);
 }
 int sg_window_node_trend(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
-    if (const int rc = stage_ready(e, t, "sg_window_node_trend", kNodeTrendWords)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    return baseline_rows(e, t, (size_t)cnt, node_index, n_index, out, cap, n, "sg_window_node_trend: a node index beyond the window's nodes");
+    return node_trend_read(e, node_space(e), "sg_window_node_trend", node_index, n_index, out, cap, n);
 }
 int sg_window_node_trend_buffer(sg_handle e, void** d_trend) {
     if (!e || !d_trend) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Baseline<sg_node_trend>& t = e->ntrend;
-    int slot;
-    if (const int rc = stage_slot(e, t, "sg_window_node_trend_buffer", kNodeTrendWords, &slot)) return rc;
-    *d_trend = t.rows[slot];
-    return SG_OK;
+    return node_trend_buffer(e, node_space(e), "sg_window_node_trend_buffer", d_trend);
 }
 int sg_node_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->ntrend.on) { e->err = "sg_node_trend_entries: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
-    return baseline_entries(e, e->ntrend, out, cap, n);
+    return node_trend_entries(e, node_space(e), "sg_node_trend_entries", out, cap, n);
 }
 int sg_node_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->ntrend.on) { e->err = "sg_node_trend_stats_get: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
-    return baseline_stats(e, e->ntrend, out);
+    return node_trend_stats(e, node_space(e), "sg_node_trend_stats_get", out);
 }
-
-// ---- node selection ---------------------------------------------------------------------------------------------------------
-namespace {
-// by > 5: SG_EINVAL; the rollup off, or a trend key with the node trend off: SG_ESTATE; then the window in `slot` must have them
-int check_nsel(sg_engine* e, u32 by, int slot) {
-    if (by > SG_NSEL_NEW) { e->err = "node selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
-    if (!e->nodes.on) { e->err = "node selection: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
-    if (by != SG_NSEL_SCORE && !e->ntrend.on) { e->err = "node selection by a trend key: the node trend is off (sg_set_node_trend)"; return SG_ESTATE; }
-    if (!e->nodes.valid[slot]) { e->err = "node selection: the window was closed while the node rollup was off"; return SG_ESTATE; }
-    if (by != SG_NSEL_SCORE && !e->ntrend.valid[slot]) { e->err = "node selection: the window was closed while the node trend was off"; return SG_ESTATE; }
-    return SG_OK;
-}
-}  // namespace
 int sg_window_nodes_top(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
                         size_t* n_selected, size_t* n_nodes) {
     if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (by > SG_NSEL_NEW) { e->err = "node selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
-    if (e->closing || e->flush_open) { e->err = "sg_window_nodes_top while a flush is open"; return SG_ESTATE; }
-    if (const int rc = check_nsel(e, by, e->cur)) return rc;
-    if (const int rc = nsel_reserve(e)) return rc;
-    return node_top_host(e, node_rows(e), [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
-        return launch_node_select_by(e, e->rd_stream, e->cur, by, k, min_value, d_out, nullptr, stage, d_n);
-    }, out, nullptr, node_index, cap, n_selected, n_nodes);
+    return nodes_top(e, node_space(e), "sg_window_nodes_top", by, k, min_value, out, node_index, cap, n_selected, n_nodes);
 }
 int sg_window_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out, uint32_t* d_index, size_t cap,
                            uint64_t* d_n, void* stream) {
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const int slot = ran_slot(e);
-    if (const int rc = check_nsel(e, by, slot)) return rc;
-    if (const int rc = nsel_reserve(e)) return rc;
-    return launch_node_select_by(e, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return nodes_select(e, node_space(e), by, k, min_value, d_out, d_index, cap, d_n, stream);
 }
 
 // ---- K11, the culprit ranking ---------------------------------------------------------------------------------------------------
@@ -2699,8 +2689,8 @@ int sg_window_rank_top(sg_handle e, uint32_t k, float min_share, sg_node_out* ou
     std::lock_guard<std::mutex> g(e->mu);
     if (e->closing || e->flush_open) { e->err = "sg_window_rank_top while a flush is open"; return SG_ESTATE; }
     if (const int rc = check_rsel(e, e->cur)) return rc;
-    if (const int rc = nsel_reserve(e)) return rc;
-    return node_top_host(e, node_rows(e), [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
+    if (const int rc = nsel_reserve(e, node_space(e))) return rc;
+    return node_top_host(e, node_space(e), [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
         return launch_rank_select(e, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
     }, out, rank_out, node_index, cap, n_selected, n_nodes);
 }
@@ -2709,7 +2699,7 @@ int sg_window_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out*
     std::lock_guard<std::mutex> g(e->mu);
     const int slot = ran_slot(e);
     if (const int rc = check_rsel(e, slot)) return rc;
-    if (const int rc = nsel_reserve(e)) return rc;
+    if (const int rc = nsel_reserve(e, node_space(e))) return rc;
     return launch_rank_select(e, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
@@ -2961,131 +2951,69 @@ int sg_window_groups_select(sg_handle e, uint32_t by, uint32_t k, float min_valu
     return launch_group_select(e, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
-// ---- K16, the workload rows ------------------------------------------------------------------------------------------------------
+// ---- K16, the workload rows: K9's, K10's and the node selection's code over the workload space --------------------------------------
 int sg_set_group_nodes(sg_handle e, int on) {
     if (!e || (on != 0 && on != 1)) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
     if (!e->grp.on) { e->err = "sg_set_group_nodes: the groups are off (sg_set_groups)"; return SG_ESTATE; }
     if (e->closing || e->flush_open) { e->err = "sg_set_group_nodes while a flush is open"; return SG_ESTATE; }
     if (!on) { free_group_nodes(e); return SG_OK; }
-    sg_engine::GroupNodes& n = e->gnodes;
-    if (n.on) return SG_OK;
+    if (e->gnodes.on) return SG_OK;
     const Dev& d = e->slots[0].d;
-    const u32 ncap = d.max_known + d.max_labels + d.max_obip, slots = (u32)e->slots.size();
+    const u32 ncap = d.max_known + d.max_labels + d.max_obip;
     if (sgplan::check_group_nodes(e->grp.plan.max_groups, ncap)) {
         e->err = "sg_set_group_nodes: max_groups + the node capacity exceeds 2^21 group keys: pass a tighter max_groups to sg_set_groups";
         return SG_EINVAL;
     }
-    n.plan = sgplan::plan_group_nodes(e->cfg.max_edges, ncap, e->grp.plan.max_groups, slots);
-    const sgplan::GroupNodesPlan& P = n.plan;
-    HIP_TRY(e, lds_limit(P.lds_bytes, k16_in_part));
-    HIP_TRY(e, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
-    if (const int rc = alloc_block(e, &n.mem, P.total_bytes, "sg_set_group_nodes", [e] { free_group_nodes(e); })) return rc;   // (zeroed: the out table starts at zero, k16_write keeps it so)
-    n.tout = at<K9Side>(n.mem, P.table_off[0]);
-    n.tin = at<K9Side>(n.mem, P.table_off[1]);
-    n.part = at<K9Side>(n.mem, P.part_off);
-    n.dst = at<u32>(n.mem, P.dst_off);
-    n.blk = at<u32>(n.mem, P.blk_off);
-    for (u32 k = 0; k < slots; k++) {
-        char* s = n.mem + P.slot.off + k * P.slot.bytes;
-        n.rows.push_back(at<sg_node_out>(s, P.slot_rows)); n.count.push_back(at<u64>(s, P.slot_count));
-    }
-    n.valid.assign(slots, 0);
-    n.on = true;
-    return SG_OK;
+    e->gnodes.plan = sgplan::plan_group_nodes(e->cfg.max_edges, ncap, e->grp.plan.max_groups, (u32)e->slots.size());
+    return rollup_on(e, e->gnodes, e->gnodes.plan, k16_in_part, "sg_set_group_nodes", [e] { free_group_nodes(e); });
 }
 int sg_window_group_nodes(sg_handle e, sg_node_out* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::GroupNodes& x = e->gnodes;
-    if (const int rc = stage_ready(e, x, "sg_window_group_nodes", kGroupNodesWords)) return rc;
-    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_node_out), out, cap, n);
+    return nodes_read(e, workload_space(e), "sg_window_group_nodes", out, cap, n);
 }
 int sg_window_group_nodes_buffer(sg_handle e, void** d_nodes, void** d_count) {
     if (!e || !d_nodes || !d_count) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::GroupNodes& x = e->gnodes;
-    int slot;
-    if (const int rc = stage_slot(e, x, "sg_window_group_nodes_buffer", kGroupNodesWords, &slot)) return rc;
-    *d_nodes = x.rows[slot]; *d_count = x.count[slot];
-    return SG_OK;
+    return nodes_buffer(e, workload_space(e), "sg_window_group_nodes_buffer", d_nodes, d_count);
 }
 int sg_set_group_node_trend(sg_handle e, const sg_trend_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->gnodes.on) { e->err = "sg_set_group_node_trend: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_group_node_trend while a flush is open"; return SG_ESTATE; }
-    sg_trend_params r{};
-    if (p && sgplan::check_group_node_trend(*p, e->gnodes.plan.nc, &r)) { e->err = "sg_set_group_node_trend: bad parameters"; return SG_EINVAL; }
-    sg_engine::Baseline<sg_node_trend>& t = e->gntrend;
-    free_baseline(t);
-    if (!p) return SG_OK;
-    const u32 slots = (u32)e->slots.size();
-    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_node_trend(e->gnodes.plan.nc, slots, r), "sg_set_group_node_trend", [&t] { free_baseline(t); })) return rc;
-    t.valid.assign(slots, 0);
-    return SG_OK;
+    return node_trend_set(e, workload_space(e), "sg_set_group_node_trend", p);
 }
 int sg_window_group_node_trend(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::Baseline<sg_node_trend>& t = e->gntrend;
-    if (const int rc = stage_ready(e, t, "sg_window_group_node_trend", kGroupNodeTrendWords)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, e->gnodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    return baseline_rows(e, t, (size_t)cnt, node_index, n_index, out, cap, n, "sg_window_group_node_trend: a node index beyond the window's workload rows");
+    return node_trend_read(e, workload_space(e), "sg_window_group_node_trend", node_index, n_index, out, cap, n);
 }
 int sg_window_group_node_trend_buffer(sg_handle e, void** d_trend) {
     if (!e || !d_trend) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Baseline<sg_node_trend>& t = e->gntrend;
-    int slot;
-    if (const int rc = stage_slot(e, t, "sg_window_group_node_trend_buffer", kGroupNodeTrendWords, &slot)) return rc;
-    *d_trend = t.rows[slot];
-    return SG_OK;
+    return node_trend_buffer(e, workload_space(e), "sg_window_group_node_trend_buffer", d_trend);
 }
 int sg_group_node_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->gntrend.on) { e->err = "sg_group_node_trend_entries: the workload trend is off (sg_set_group_node_trend)"; return SG_ESTATE; }
-    return baseline_entries(e, e->gntrend, out, cap, n);
+    return node_trend_entries(e, workload_space(e), "sg_group_node_trend_entries", out, cap, n);
 }
 int sg_group_node_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->gntrend.on) { e->err = "sg_group_node_trend_stats_get: the workload trend is off (sg_set_group_node_trend)"; return SG_ESTATE; }
-    return baseline_stats(e, e->gntrend, out);
+    return node_trend_stats(e, workload_space(e), "sg_group_node_trend_stats_get", out);
 }
-namespace {
-// by > 5: SG_EINVAL; the workload rows off, or a trend key with their trend off: SG_ESTATE; then the window in `slot` must have them
-int check_gnsel(sg_engine* e, u32 by, int slot) {
-    if (by > SG_NSEL_NEW) { e->err = "workload selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
-    if (!e->gnodes.on) { e->err = "workload selection: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
-    if (by != SG_NSEL_SCORE && !e->gntrend.on) { e->err = "workload selection by a trend key: the workload trend is off (sg_set_group_node_trend)"; return SG_ESTATE; }
-    if (!e->gnodes.valid[slot]) { e->err = "workload selection: the window was closed while the workload rows were off"; return SG_ESTATE; }
-    if (by != SG_NSEL_SCORE && !e->gntrend.valid[slot]) { e->err = "workload selection: the window was closed while the workload trend was off"; return SG_ESTATE; }
-    return SG_OK;
-}
-}  // namespace
 int sg_window_group_nodes_top(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
                               size_t* n_selected, size_t* n_nodes) {
     if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (by > SG_NSEL_NEW) { e->err = "workload selection: unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
-    if (e->closing || e->flush_open) { e->err = "sg_window_group_nodes_top while a flush is open"; return SG_ESTATE; }
-    if (const int rc = check_gnsel(e, by, e->cur)) return rc;
-    if (const int rc = gnsel_reserve(e)) return rc;
-    return node_top_host(e, group_node_rows(e), [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
-        return launch_group_node_select_by(e, e->rd_stream, e->cur, by, k, min_value, d_out, nullptr, stage, d_n);
-    }, out, nullptr, node_index, cap, n_selected, n_nodes);
+    return nodes_top(e, workload_space(e), "sg_window_group_nodes_top", by, k, min_value, out, node_index, cap, n_selected, n_nodes);
 }
 int sg_window_group_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out, uint32_t* d_index, size_t cap,
                                  uint64_t* d_n, void* stream) {
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const int slot = ran_slot(e);
-    if (const int rc = check_gnsel(e, by, slot)) return rc;
-    if (const int rc = gnsel_reserve(e)) return rc;
-    return launch_group_node_select_by(e, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return nodes_select(e, workload_space(e), by, k, min_value, d_out, d_index, cap, d_n, stream);
 }
 
 // ---- K13, the tracks ---------------------------------------------------------------------------------------------------------------

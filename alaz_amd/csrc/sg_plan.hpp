@@ -660,39 +660,41 @@ inline VanishedPlan plan_vanished(const TrendPlan& t, u32 slots, const sg_vanish
 constexpr u32 kNodesThreads = 256, kNodesChunk = 2048, kNodesRangeNodes = 2048, kNodesMaxSlices = 16, kNodesSliceRows = 32768,
               kNodesMaxWgs = 1024;
 constexpr u64 kNodesSideBytes = 64;       // one side of a node: a table entry, an LDS entry, a partial
+// The rollup exists in two key spaces — K9's node ids and K16's group keys (below) — with one plan: plan_rollup sizes and lays out
+// the block of either from the row capacity of the input, the key count, the rows a window slot holds and a cap on the in side's grid.
 struct NodesPlan {
-    u32 ncap = 0;
-    u32 out_wgs = 0;              // workgroups of k9_out: chunks of max_edges
-    u32 ranges = 0, slices = 0;   // k9_in_part's grid = ranges x slices
-    u32 node_wgs = 0, node_per = 0;   // k9_count / k9_write: workgroups, nodes per workgroup (a multiple of 256)
-    u64 dst_bytes = 0;            // [max_edges] u32 destination node per row
-    u64 table_bytes = 0;          // one side's table: [ncap] x 64 bytes (out and in: two of them)
+    u32 ncap = 0;                 // K9's node id space (K9's key count; K16's keys are max_groups + ncap)
+    u32 out_wgs = 0;              // workgroups of the out side: chunks of max_edges
+    u32 ranges = 0, slices = 0;   // the in side's grid = ranges x slices
+    u32 node_wgs = 0, node_per = 0;   // the count / write passes: workgroups, keys per workgroup (a multiple of 256)
+    u64 dst_bytes = 0;            // [max_edges] u32 destination key per row
+    u64 table_bytes = 0;          // one side's table: [keys] x 64 bytes (out and in: two of them)
     u64 part_bytes = 0;           // [ranges][slices][2048] x 64 bytes
     u64 blk_bytes = 0;            // [2][1024] u32
-    u64 rows_bytes = 0;           // one window slot's node rows: [ncap] sg_node_out
-    u64 count_bytes = 0;          // one window slot's node count (u64)
-    u64 lds_bytes = 0;            // k9_in_part's dynamic LDS
+    u64 rows_bytes = 0;           // one window slot's rows: [rows] sg_node_out
+    u64 count_bytes = 0;          // one window slot's row count (u64)
+    u64 lds_bytes = 0;            // the in side's dynamic LDS
     u64 total_bytes = 0;          // the scratch and every slot's rows and count, each 256-byte aligned
     u64 table_off[2] = {}, part_off = 0, dst_off = 0, blk_off = 0;   // (table_off: out, in)
     Slots slot; u64 slot_rows = 0, slot_count = 0;
     std::vector<Piece> layout;
 };
-inline NodesPlan plan_nodes(u64 max_edges, u32 ncap, u32 slots) {
-    NodesPlan n;
-    const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(ncap, 1);
-    n.ncap = ncap;
+// max_in_wgs: at most about that many workgroups on the in side (0: no cap) — a range's workgroups scan every row of their slice
+inline void plan_rollup(NodesPlan& n, u64 max_edges, u64 keys, u64 rows, u32 max_in_wgs, u32 slots) {
+    const u64 ME = std::max<u64>(max_edges, 1), NK = std::max<u64>(keys, 1);
     n.out_wgs = (u32)((ME + kNodesChunk - 1) / kNodesChunk);
-    n.ranges = (u32)((NC + kNodesRangeNodes - 1) / kNodesRangeNodes);
+    n.ranges = (u32)((NK + kNodesRangeNodes - 1) / kNodesRangeNodes);
     n.slices = (u32)std::max<u64>(1, std::min<u64>(kNodesMaxSlices, (ME + kNodesSliceRows - 1) / kNodesSliceRows));
-    n.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kNodesMaxWgs, (NC + kNodesThreads - 1) / kNodesThreads));
-    const u64 per = (NC + n.node_wgs - 1) / n.node_wgs;
+    if (max_in_wgs) n.slices = std::min<u32>(n.slices, std::max<u32>(1, max_in_wgs / n.ranges));
+    n.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kNodesMaxWgs, (NK + kNodesThreads - 1) / kNodesThreads));
+    const u64 per = (NK + n.node_wgs - 1) / n.node_wgs;
     n.node_per = (u32)((per + kNodesThreads - 1) / kNodesThreads * kNodesThreads);
-    n.node_wgs = (u32)((NC + n.node_per - 1) / n.node_per);           // (the rounding can leave the last blocks without nodes)
+    n.node_wgs = (u32)((NK + n.node_per - 1) / n.node_per);           // (the rounding can leave the last blocks without keys)
     n.dst_bytes = trend_align(ME * 4);
-    n.table_bytes = trend_align(NC * kNodesSideBytes);
+    n.table_bytes = trend_align(NK * kNodesSideBytes);
     n.part_bytes = trend_align((u64)n.ranges * n.slices * kNodesRangeNodes * kNodesSideBytes);
     n.blk_bytes = trend_align(2ull * kNodesMaxWgs * 4);
-    n.rows_bytes = trend_align(NC * sizeof(sg_node_out));
+    n.rows_bytes = trend_align(std::max<u64>(rows, 1) * sizeof(sg_node_out));
     n.count_bytes = trend_align(8);
     n.lds_bytes = (u64)kNodesRangeNodes * kNodesSideBytes;
     Block b;
@@ -702,6 +704,11 @@ inline NodesPlan plan_nodes(u64 max_edges, u32 ncap, u32 slots) {
     n.blk_off = b.take("blk", n.blk_bytes);
     n.slot = b.slots(slots, {{"rows", n.rows_bytes, &n.slot_rows}, {"count", n.count_bytes, &n.slot_count}});
     n.total_bytes = b.end; n.layout = std::move(b.pieces);
+}
+inline NodesPlan plan_nodes(u64 max_edges, u32 ncap, u32 slots) {
+    NodesPlan n;
+    n.ncap = ncap;
+    plan_rollup(n, max_edges, ncap, ncap, 0, slots);
     return n;
 }
 
@@ -1072,52 +1079,16 @@ inline GroupSelPlan plan_group_select(u64 max_edges, u64 counter_bytes) {
 constexpr u64 kGrpNodesMaxKeys = 1ull << 21;
 constexpr u32 kGrpNodesMaxInWgs = 1024;
 inline int check_group_nodes(u32 max_groups, u32 ncap) { return (u64)max_groups + ncap > kGrpNodesMaxKeys ? SG_EINVAL : SG_OK; }
-struct GroupNodesPlan {
+struct GroupNodesPlan : NodesPlan {
     u64 gk = 0;                   // max_groups + ncap
-    u32 max_groups = 0, ncap = 0;
+    u32 max_groups = 0;
     u32 nc = 0;                   // workload rows per window slot: min(GK, 2 x max_edges)
-    u32 out_wgs = 0;              // workgroups of k16_out: chunks of max_edges
-    u32 ranges = 0, slices = 0;   // k16_in_part's grid = ranges x slices
-    u32 node_wgs = 0, node_per = 0;   // k16_count / k16_write: workgroups, keys per workgroup (a multiple of 256)
-    u64 dst_bytes = 0;            // [max_edges] u32 destination key per group edge
-    u64 table_bytes = 0;          // one side's table: [GK] x 64 bytes (out and in: two of them)
-    u64 part_bytes = 0;           // [ranges][slices][2048] x 64 bytes
-    u64 blk_bytes = 0;            // [2][1024] u32
-    u64 rows_bytes = 0;           // one window slot's workload rows: [NC] sg_node_out
-    u64 count_bytes = 0;          // one window slot's node count (u64)
-    u64 lds_bytes = 0;            // k16_in_part's dynamic LDS
-    u64 total_bytes = 0;          // the scratch and every slot's rows and count, each 256-byte aligned
-    u64 table_off[2] = {}, part_off = 0, dst_off = 0, blk_off = 0;   // (table_off: out, in)
-    Slots slot; u64 slot_rows = 0, slot_count = 0;
-    std::vector<Piece> layout;
 };
 inline GroupNodesPlan plan_group_nodes(u64 max_edges, u32 ncap, u32 max_groups, u32 slots) {
     GroupNodesPlan n;
-    const u64 ME = std::max<u64>(max_edges, 1), GK = std::max<u64>((u64)max_groups + ncap, 1);
     n.gk = (u64)max_groups + ncap; n.max_groups = max_groups; n.ncap = ncap;
-    n.nc = (u32)std::min<u64>(GK, 2 * ME);
-    n.out_wgs = (u32)((ME + kNodesChunk - 1) / kNodesChunk);
-    n.ranges = (u32)((GK + kNodesRangeNodes - 1) / kNodesRangeNodes);
-    n.slices = (u32)std::max<u64>(1, std::min<u64>(std::min<u64>(kNodesMaxSlices, (ME + kNodesSliceRows - 1) / kNodesSliceRows),
-                                                   std::max<u32>(1, kGrpNodesMaxInWgs / n.ranges)));
-    n.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kNodesMaxWgs, (GK + kNodesThreads - 1) / kNodesThreads));
-    const u64 per = (GK + n.node_wgs - 1) / n.node_wgs;
-    n.node_per = (u32)((per + kNodesThreads - 1) / kNodesThreads * kNodesThreads);
-    n.node_wgs = (u32)((GK + n.node_per - 1) / n.node_per);           // (the rounding can leave the last blocks without keys)
-    n.dst_bytes = trend_align(ME * 4);
-    n.table_bytes = trend_align(GK * kNodesSideBytes);
-    n.part_bytes = trend_align((u64)n.ranges * n.slices * kNodesRangeNodes * kNodesSideBytes);
-    n.blk_bytes = trend_align(2ull * kNodesMaxWgs * 4);
-    n.rows_bytes = trend_align((u64)n.nc * sizeof(sg_node_out));
-    n.count_bytes = trend_align(8);
-    n.lds_bytes = (u64)kNodesRangeNodes * kNodesSideBytes;
-    Block b;
-    n.table_off[0] = b.take("table_out", n.table_bytes); n.table_off[1] = b.take("table_in", n.table_bytes);
-    n.part_off = b.take("part", n.part_bytes);
-    n.dst_off = b.take("dst", n.dst_bytes);
-    n.blk_off = b.take("blk", n.blk_bytes);
-    n.slot = b.slots(slots, {{"rows", n.rows_bytes, &n.slot_rows}, {"count", n.count_bytes, &n.slot_count}});
-    n.total_bytes = b.end; n.layout = std::move(b.pieces);
+    n.nc = (u32)std::min<u64>(std::max<u64>(n.gk, 1), 2 * std::max<u64>(max_edges, 1));
+    plan_rollup(n, max_edges, n.gk, n.nc, kGrpNodesMaxInWgs, slots);
     return n;
 }
 // K16's baseline: K10's over the workload rows — two samples per row, [NC] sg_node_trend per slot; max_entries defaults to 4 x NC

@@ -18,6 +18,7 @@ from tests.node_trend_ref import NodeTrendRef
 from tests.nodes_ref import nodes_ref
 from tests.test_gpu_groups import _grouped, _map, _pairs, _pods_engine
 from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixtures)
+from tests.test_gpu_nodes import RUNS
 from tests.test_gpu_rank import _d2h, _hip
 
 pytestmark = pytest.mark.gpu
@@ -127,9 +128,8 @@ def wide():
     return topo, g, mk, gmap
 
 
-# (group edges in front of the long run, its length): a run inside a span, cut by spans, ending on a chunk end (8 + 2040, 6 + 2042),
-# crossing one, beginning at one (2048 in front), and passing THROUGH a whole chunk (6 + 4097 covers [2048, 4096))
-RUNS = [(6, 1), (6, 7), (6, 8), (6, 9), (6, 2047), (6, 2048), (6, 2049), (6, 4097), (8, 2040), (6, 2042), (2048, 9), (2047, 2049), (5, 3)]
+# RUNS (tests/test_gpu_nodes.py, K9's out side over the same list) = (group edges in front of the long run, its length): a run
+# inside a span, cut by spans, ending on a chunk end, crossing one, beginning at one, and passing THROUGH a whole chunk
 
 
 @pytest.mark.parametrize("front,D", RUNS)

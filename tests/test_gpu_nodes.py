@@ -248,6 +248,40 @@ def test_hub_destination_and_a_source_across_many_chunks():
     assert hub["in_worst_row"] == np.flatnonzero(to_hub & (rows["score"] == hub["in_score_max"]))[0]
 
 
+@pytest.fixture(scope="module")
+def wide():
+    """4200 pods, pod i with node id i, no groups: pod 5 is the caller of the long run, pods 0..4 come before it in row order"""
+    from tests.test_gpu_groups import _pods_engine                    # (that module imports this one)
+    topo, g, mk = _pods_engine(n_pods=4200)
+    g.set_nodes()
+    return topo, g
+
+
+# (rows in front of the long run, its length): a run inside a span of K9_ROWS = 8, cut by spans, ending on an end of a chunk of
+# K9_CHUNK = 2048 (8 + 2040, 6 + 2042), crossing one, beginning at one (2048 in front), and passing THROUGH a whole chunk (6 + 4097
+# covers [2048, 4096)).  tests/test_gpu_group_nodes.py holds K16's out side to the same list.
+RUNS = [(6, 1), (6, 7), (6, 8), (6, 9), (6, 2047), (6, 2048), (6, 2049), (6, 4097), (8, 2040), (6, 2042), (2048, 9), (2047, 2049), (5, 3)]
+
+
+@pytest.mark.parametrize("front,D", RUNS)
+def test_out_side_runs_at_the_span_and_chunk_boundaries(wide, front, D):
+    topo, g = wide
+    f = np.arange(front)                                              # pods 0..4 call `front` pods between them
+    src = np.concatenate([f % 5, np.full(D, 5), [50, 50, 51]])
+    dst = np.concatenate([60 + f // 5, np.arange(D) + 100, [7, 8, 7]])
+    e = np.zeros(len(src), dtype=replay.EVENT_DTYPE)
+    e["saddr"] = topo.pod_ips[src]; e["daddr"] = topo.pod_ips[dst]
+    e["status"] = 200; e["protocol"] = replay.PROTO_HTTP; e["duration_ns"] = 1_000_000
+    e["write_time_ns"] = np.uint64(2_000_000_000) + np.uint64(100) * np.arange(len(e), dtype=np.uint64)
+    g.ingest_bulk(e)
+    rows = g.flush_window().copy()
+    n = _check(g, rows)
+    assert len(rows) == front + D + 3
+    assert rows["from_ref"][front] == 5 == rows["from_ref"][front + D - 1] and rows["from_ref"][front - 1] == 4 and rows["from_ref"][front + D] == 50
+    w = n[n["ref"] == 5][0]
+    assert w["out_edges"] == D and w["out_count"] == D and w["in_edges"] == 0
+
+
 def test_empty_window_and_states(churn):
     topo, labels, wins = churn
     g = _engine(topo, labels)
