@@ -32,6 +32,8 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->set_group_node_trend = reinterpret_cast<decltype(o->set_group_node_trend)>(dlsym(dl, "sg_set_group_node_trend"));
     o->window_group_node_trend = reinterpret_cast<decltype(o->window_group_node_trend)>(dlsym(dl, "sg_window_group_node_trend"));
     o->window_group_nodes_top = reinterpret_cast<decltype(o->window_group_nodes_top)>(dlsym(dl, "sg_window_group_nodes_top"));
+    o->set_group_rank = reinterpret_cast<decltype(o->set_group_rank)>(dlsym(dl, "sg_set_group_rank"));             // optional (K17)
+    o->window_group_rank_top = reinterpret_cast<decltype(o->window_group_rank_top)>(dlsym(dl, "sg_window_group_rank_top"));
 #undef SG_SYM
     return true;
 }
@@ -281,6 +283,36 @@ long GraphDS::WorkloadNodesTop(uint32_t by, uint32_t k, float min_value, std::ve
     const size_t m = std::min(sel, rows.size());
     rows.resize(m); idx.resize(m);
     NameWorkloadNodes(rows, out);
+    if (index) *index = std::move(idx);
+    return (long)m;
+}
+
+// ---- the workload ranking (K17) ----
+int GraphDS::SetWorkloadRank(const sg_rank_params* p) {
+    if (!api_.set_group_rank) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_group_rank(h_, p);
+}
+long GraphDS::WorkloadCulprits(uint32_t k, float min_share, std::vector<WorkloadCulprit>* out, std::vector<uint32_t>* index) {
+    if (!out || !api_.window_group_rank_top) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t sel = 0, total = 0;
+    std::vector<sg_node_out> rows;
+    std::vector<sg_node_rank> ranks;
+    std::vector<uint32_t> idx;
+    if (k) { rows.resize(k); ranks.resize(k); idx.resize(k); }       // at most k are selected; k = 0: the count first
+    int rc = api_.window_group_rank_top(h_, k, min_share, rows.data(), ranks.data(), idx.data(), rows.size(), &sel, &total);
+    if (rc != SG_OK) return rc;
+    if (!k && sel) {
+        rows.resize(sel); ranks.resize(sel); idx.resize(sel);
+        if ((rc = api_.window_group_rank_top(h_, 0, min_share, rows.data(), ranks.data(), idx.data(), rows.size(), &sel, &total)) != SG_OK) return rc;
+    }
+    const size_t m = std::min(sel, rows.size());
+    rows.resize(m); idx.resize(m);
+    std::vector<WorkloadNode> named;
+    NameWorkloadNodes(rows, &named);
+    out->assign(m, WorkloadCulprit{});
+    for (size_t i = 0; i < m; i++) { (*out)[i].Node = std::move(named[i]); (*out)[i].Rank = ranks[i]; }
     if (index) *index = std::move(idx);
     return (long)m;
 }

@@ -61,6 +61,9 @@ struct SgApi {
     int (*set_group_node_trend)(sg_handle, const sg_trend_params*) = nullptr;
     int (*window_group_node_trend)(sg_handle, const uint32_t*, size_t, sg_node_trend*, size_t, size_t*) = nullptr;
     int (*window_group_nodes_top)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
+    // optional (K17; absent in an older library): SetWorkloadRank and WorkloadCulprits each need the entry they forward to
+    int (*set_group_rank)(sg_handle, const sg_rank_params*) = nullptr;
+    int (*window_group_rank_top)(sg_handle, uint32_t, float, sg_node_out*, sg_node_rank*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -90,6 +93,11 @@ struct VanishedWorkload {              // one vanished workload dependency of a 
 struct WorkloadNode {                  // one workload row of a closed window (K16): who it is, and the engine's row as it is
     std::string Type, UID;                             // "workload" (UID = the owner's UID), or pod / service / outbound as the rows' are
     sg_node_out Row{};
+};
+
+struct WorkloadCulprit {               // one selected workload of a closed window's ranking (K17): the workload row named, and its rank row
+    WorkloadNode Node;
+    sg_node_rank Rank{};
 };
 
 class EdgeSink {
@@ -179,6 +187,12 @@ public:
     long WorkloadNodes(std::vector<WorkloadNode>* out);
     long WorkloadNodeTrends(std::vector<sg_node_trend>* out);
     long WorkloadNodesTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
+    // The workload ranking (K17), behind SetWorkloadNodes: the last flushed window's likely root-cause workloads.  SetWorkloadRank
+    // forwards sg_set_group_rank (p NULL: off; the engine's return code; SG_EINVAL without the entry).  WorkloadCulprits: the
+    // selection sg_window_group_rank_top — the rows named as WorkloadNodes names them, each with its rank row, the rows' indices in
+    // `index` (may be NULL).  It returns the count, < 0 on an engine error.
+    int SetWorkloadRank(const sg_rank_params* p);
+    long WorkloadCulprits(uint32_t k, float min_share, std::vector<WorkloadCulprit>* out, std::vector<uint32_t>* index);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }

@@ -29,6 +29,7 @@ struct MockEngine {
     std::vector<std::array<uint32_t, 2>> group_ops;   // {node id, group} of every sg_group_assign pair; {0xFFFFFFFE, max_groups} of every sg_set_groups
     std::vector<std::array<uint64_t, 4>> k15_ops;      // {1, shift, warmup, ttl} per sg_set_group_trend, {2, silent_windows, min_seen, max_rows} per sg_set_group_vanished (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_groups_top
     std::vector<std::array<uint64_t, 4>> k16_ops;      // {1, on, 0, 0} per sg_set_group_nodes, {2, shift, warmup, ttl} per sg_set_group_node_trend (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_group_nodes_top
+    std::vector<std::array<uint64_t, 4>> k17_ops;      // {1, iters, damping_q8, seed} per sg_set_group_rank (NULL: ~0 in the three), {2, k, the bits of min_share, cap} per sg_window_group_rank_top
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
 };
 #define M_LOCK(h) std::lock_guard<std::mutex> _g(reinterpret_cast<MockEngine*>(h)->mu)
@@ -128,6 +129,24 @@ int m_window_group_nodes_top(sg_handle h, uint32_t by, uint32_t k, float min_val
     for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
     return SG_OK;
 }
+// K17's stand-ins: the switch recorded, and a selection of rows 1 and 2 of three (workload 0 with three quarters of the mass, then
+// ungrouped KNOWN 0)
+int m_set_group_rank(sg_handle h, const sg_rank_params* p) {
+    M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k17_ops.push_back({1u, p ? p->iters : ~0ull, p ? p->damping_q8 : ~0ull, p ? p->seed : ~0ull}); return SG_OK;
+}
+int m_window_group_rank_top(sg_handle h, uint32_t k, float min_share, sg_node_out* out, sg_node_rank* rank_out, uint32_t* idx, size_t cap, size_t* n_sel,
+                            size_t* n) {
+    M_LOCK(h);
+    uint32_t bits; std::memcpy(&bits, &min_share, 4);
+    reinterpret_cast<MockEngine*>(h)->k17_ops.push_back({2u, k, bits, (uint64_t)cap});
+    if (n_sel) *n_sel = 2;
+    if (n) *n = 3;
+    const sg_node_out e[2] = {m_node(SG_MAKE_REF(SG_REF_GROUP, 0), 4, 9, 1, 1, 0.5f), m_node(SG_MAKE_REF(SG_REF_KNOWN, 0), 0, 4, 0, 1, 0.25f)};
+    const sg_node_rank r[2] = {{3ull << 54, SG_MAKE_REF(SG_REF_GROUP, 0), 0.75f}, {1ull << 53, SG_MAKE_REF(SG_REF_KNOWN, 0), 0.125f}};
+    const uint32_t at[2] = {1u, 2u};
+    for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (rank_out) rank_out[i] = r[i]; if (idx) idx[i] = at[i]; }
+    return SG_OK;
+}
 int m_obips(sg_handle, uint32_t*, size_t, size_t* n) { if (n) *n = 0; return SG_OK; }
 const char* m_err(sg_handle) { return ""; }
 
@@ -216,6 +235,7 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.window_group_vanished = m_window_group_vanished; c->api.window_groups_top = m_window_groups_top;
         c->api.set_group_nodes = m_set_group_nodes; c->api.window_group_nodes = m_window_group_nodes; c->api.set_group_node_trend = m_set_group_node_trend;
         c->api.window_group_node_trend = m_window_group_node_trend; c->api.window_group_nodes_top = m_window_group_nodes_top;
+        c->api.set_group_rank = m_set_group_rank; c->api.window_group_rank_top = m_window_group_rank_top;
     }
     if (c->api.create(cfg, &c->h) != SG_OK) return nullptr;        // no usable GPU => no GraphDS: there is no CPU fallback
     c->ds = std::make_unique<GraphDS>(&c->inner, c->api, c->h, &c->sink, cfg ? (size_t)cfg->max_edges : 1024, batch ? batch : 4096,
@@ -332,6 +352,24 @@ long sgh_graphds_workload_nodes_top(void* g, uint32_t by, uint32_t k, float min_
     const long n = static_cast<HostCtx*>(g)->ds->WorkloadNodesTop(by, k, min_value, &v, &idx);
     if (n < 0) return n;
     for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_node(v[i], out + i); if (index) index[i] = idx[i]; }
+    return n;
+}
+// the workload ranking (K17): the switch (on = 0: off; a parameter 0 = its default) and the selection over the last flushed window's
+// rank rows — the workload rows as sgh_graphds_workload_nodes gives them, then each one's sg_node_rank
+int sgh_graphds_set_workload_rank(void* g, int on, uint32_t iters, uint32_t damping_q8, uint32_t seed, float seed_min_score) {
+    sg_rank_params p{}; p.struct_size = sizeof p; p.iters = iters; p.damping_q8 = damping_q8; p.seed = seed; p.seed_min_score = seed_min_score;
+    return static_cast<HostCtx*>(g)->ds->SetWorkloadRank(on ? &p : nullptr);
+}
+struct sgh_workload_culprit { sgh_workload_node node; sg_node_rank rank; };
+static_assert(sizeof(sgh_workload_culprit) == 16 + 160 + 136 + 16, "sgh_workload_culprit: sgh_workload_node, then sg_node_rank");
+long sgh_graphds_workload_culprits(void* g, uint32_t k, float min_share, sgh_workload_culprit* out, uint32_t* index, size_t cap) {
+    std::vector<WorkloadCulprit> v; std::vector<uint32_t> idx;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadCulprits(k, min_share, &v, &idx);
+    if (n < 0) return n;
+    for (size_t i = 0; i < std::min(cap, v.size()); i++) {
+        if (out) { put_workload_node(v[i].Node, &out[i].node); out[i].rank = v[i].Rank; }
+        if (index) index[i] = idx[i];
+    }
     return n;
 }
 int sgh_graphds_ingest_wire(void* g, const uint8_t* recs, size_t n, const uint32_t* kafka_msgs) {
@@ -620,6 +658,14 @@ size_t sgh_mock_k16_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k16_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k16_ops[i].data(), 32);
     return m->k16_ops.size();
+}
+size_t sgh_mock_k17_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k17_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k17_ops[i].data(), 32);
+    return m->k17_ops.size();
 }
 size_t sgh_mock_group_ops(void* g, uint32_t* out2, size_t cap) {
     auto* c = static_cast<HostCtx*>(g); if (!c->mock) return 0;

@@ -33,6 +33,7 @@
 #include "sg_group.h"
 #include "sg_group_trend.h"
 #include "sg_group_nodes.h"
+#include "sg_group_rank.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -229,6 +230,14 @@ struct sg_engine {
     // plan_group_node_select's block, allocated at the first one, freed with the workload rows (its sizes are theirs)
     Baseline<sg_node_trend> gntrend;
     NSel gnsel;
+    // K17, the workload ranking (sg_group_rank.h): allocated at sg_set_group_rank (sg_plan.hpp plan_group_rank), one allocation, freed
+    // with the workload rows.  The position table, the per-group-edge and per-row arrays and the partials are scratch shared by the
+    // window slots: every ranking waits for the previous one (ev), whichever slot's stream it runs on.  Per slot: the rank rows, and
+    // whether the window in the slot was ranked.
+    struct GroupRank { bool on = false; sg_rank_params p{}; sgplan::GroupRankPlan plan; char* mem = nullptr; u32* pos = nullptr; u32* src = nullptr;
+                       u32* dst = nullptr; u64* w = nullptr; u64* W = nullptr; u64* R = nullptr; u64* base = nullptr; u64* t = nullptr; u64* part = nullptr;
+                       u64* seed_sum = nullptr; sg_node_rank* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_node_rank*> rows;
+                       std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } grank;
 };
 
 namespace {
@@ -731,6 +740,7 @@ constexpr StageWords kGroupsWords{"the groups are off (sg_set_groups)", "the gro
 constexpr StageWords kGroupTrendWords{"the group trend is off (sg_set_group_trend)", "the group trend was off"};
 constexpr StageWords kGroupNodesWords{"the workload rows are off (sg_set_group_nodes)", "the workload rows were off"};
 constexpr StageWords kGroupNodeTrendWords{"the workload trend is off (sg_set_group_node_trend)", "the workload trend was off"};
+constexpr StageWords kGroupRankWords{"the workload ranking is off (sg_set_group_rank)", "the workload ranking was off"};
 constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
 // A node space: what the baseline, the selection and the readbacks over node rows work on — K9's nodes or K16's workloads.  Its
 // rollup, its baseline, its selection scratch, the rows a window can have, and how its messages name it: the rollup, the baseline,
@@ -1051,6 +1061,42 @@ int launch_group_nodes(sg_engine* e, hipStream_t s) {
     a.max_groups = P.max_groups; a.gk = (u32)P.gk; a.hi_group = e->grp.hi_group; a.nc = P.nc;
     return launch_rollup(e, e->gnodes, P, s, a, a.nd, k16_out, k16_in_part, k16_count, k16_write);
 }
+// ---- K17, the workload ranking (engine lock held) ----------------------------------------------------------------------------------
+static_assert(sgplan::kGrpRankThreads == K17_THREADS && sgplan::kGrpRankRangeRows == K17_NR && sgplan::kGrpRankMaxWgs == K17_MAX_WGS &&
+              sgplan::kGrpRankNodeRows == K17_NODE_ROWS && K17_THREADS % K17_NODE_ROWS == 0 &&
+              2 * sgplan::kGrpRankRangeRows * 8 <= sgplan::kLdsBytes, "plan_group_rank sizes the launches of sg_group_rank.h");
+// enqueue the ranking of the workload rows of the window in slot cur on stream s (behind its contraction, its workload rows and their
+// baseline, on the same stream) and behind the previous ranking (any stream): 2 * iters + 4 plain launches, the rank rows go to
+// the slot's buffer
+int launch_group_rank(sg_engine* e, hipStream_t s) {
+    sg_engine::GroupRank& r = e->grank;
+    const sgplan::GroupRankPlan& P = r.plan;
+    const sgplan::GroupNodesPlan& N = e->gnodes.plan;
+    GroupRankArgs a{};
+    a.g.nd = nodes_view(e, work(e), N.ncap);
+    a.g.nd.max_edges = std::max<u64>(e->cfg.max_edges, 1);
+    a.g.groups = e->grp.rows[e->cur]; a.g.gcount = e->grp.count[e->cur];
+    a.g.max_groups = N.max_groups; a.g.gk = (u32)N.gk; a.g.hi_group = e->grp.hi_group; a.g.nc = N.nc;
+    a.nodes = e->gnodes.rows[e->cur]; a.count = e->gnodes.count[e->cur];
+    a.slices = P.slices; a.pos_wgs = P.pos_wgs; a.damping = r.p.damping_q8; a.seed = r.p.seed; a.seed_min = r.p.seed_min_score;
+    a.pos = r.pos; a.src = r.src; a.dst = r.dst; a.w = r.w; a.W = r.W; a.R = r.R; a.base = r.base; a.t = r.t; a.part = r.part; a.seed_sum = r.seed_sum;
+    a.out = r.rows[e->cur];
+    if (const int rc = stage_wait(e, r, s)) return rc;
+    const dim3 eg(P.ranges * P.slices), et(K17_EDGE_THREADS), ng(P.node_wgs), nt(K17_THREADS);
+    hipLaunchKernelGGL(k17_pos, dim3(P.pos_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k17_prep, dim3(P.prep_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k17_edge<true>, eg, et, (size_t)P.lds_bytes, s, a);
+    hipLaunchKernelGGL((k17_node<true, false>), ng, nt, 0, s, a);
+    for (u32 i = 1; i <= r.p.iters; i++) {
+        hipLaunchKernelGGL(k17_edge<false>, eg, et, (size_t)P.lds_bytes, s, a);
+        if (i < r.p.iters) hipLaunchKernelGGL((k17_node<false, false>), ng, nt, 0, s, a);
+        else hipLaunchKernelGGL((k17_node<false, true>), ng, nt, 0, s, a);
+    }
+    if (const int rc = stage_done(e, r, s)) return rc;
+    r.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_group_rank(sg_engine* e) { free_stage(e->grank); }
 // a selection scratch block off (the workload rows': its sizes are the stage's)
 void free_nsel(sg_engine::NSel& s) {
     if (s.mem || s.h_n) hipDeviceSynchronize();
@@ -1060,6 +1106,7 @@ void free_nsel(sg_engine::NSel& s) {
     s = sg_engine::NSel{};
 }
 void free_group_nodes(sg_engine* e) {
+    free_group_rank(e);
     free_nsel(e->gnsel);
     free_baseline(e->gntrend);
     free_stage(e->gnodes);
@@ -1125,7 +1172,8 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (e->gtrend.on) { if (const int rc = launch_group_trend(e, s)) return rc; }   // K15 behind K14: the group edges, their count, the outbound IPs
         if (e->gnodes.on) {                                          // K16 behind K14: the group edges and their count; its baseline behind it
             if (const int rc = launch_group_nodes(e, s)) return rc;
-            if (e->gntrend.on) return launch_node_trend(e, workload_space(e), s, k16_tcount, k16_twrite);
+            if (e->gntrend.on) { if (const int rc = launch_node_trend(e, workload_space(e), s, k16_tcount, k16_twrite)) return rc; }
+            if (e->grank.on) { if (const int rc = launch_group_rank(e, s)) return rc; }   // K17 behind K16 and its baseline: the group edges, the workload rows and their count
         }
     }
     return SG_OK;
@@ -1341,28 +1389,30 @@ int launch_node_select_by(sg_engine* e, const NodeSpace& ns, hipStream_t st, int
         return (int)SG_OK;
     }, [](const SelArgs&, dim3) {});
 }
-// by the culprit rank: k11_keys over the window's rank rows (behind its ranking); d_rank (may be NULL) gets the selected rank rows
-int launch_rank_select(sg_engine* e, hipStream_t st, int slot, u32 k, float min_share, sg_node_out* d_out, sg_node_rank* d_rank, u32* d_index,
-                       u64 cap, u64* d_n) {
-    const sg_node_rank* rk = e->rank.rows[slot];
-    return launch_node_select(e, node_space(e), st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
-        if (e->rank.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->rank.ev, 0));
-        hipLaunchKernelGGL(k11_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, rk, (const u64*)e->nodes.count[slot], e->nsel.ctr);
+// by the culprit rank: k11_keys over the window's rank rows of ranking r over node space ns (K11 over the nodes, K17 over the workloads;
+// behind that ranking); d_rank (may be NULL) gets the selected rank rows
+template <class R>
+int launch_rank_select(sg_engine* e, const NodeSpace& ns, const R& r, hipStream_t st, int slot, u32 k, float min_share, sg_node_out* d_out,
+                       sg_node_rank* d_rank, u32* d_index, u64 cap, u64* d_n) {
+    const sg_node_rank* rk = r.rows[slot];
+    return launch_node_select(e, ns, st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+        if (r.pending) HIP_TRY(e, hipStreamWaitEvent(st, r.ev, 0));
+        hipLaunchKernelGGL(k11_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, rk, (const u64*)ns.roll->count[slot], ns.sel->ctr);
         return (int)SG_OK;
     }, [&](const SelArgs& a, dim3 grid) {
         if (d_rank) hipLaunchKernelGGL(k_gather_sel<sg_node_rank>, grid, dim3(256), 0, st, rk, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_rank);
     });
 }
-// the host form of a node selection over the last read window (sg_window_nodes_top, sg_window_rank_top, sg_window_group_nodes_top;
-// v's scratch reserved): launch(out_stage, rank_stage, cap, d_n) enqueues it on the read stream; the selected rows, rank rows and
-// indices come back, then the counts
+// the host form of a node selection over the last read window (sg_window_nodes_top, sg_window_rank_top, sg_window_group_nodes_top,
+// sg_window_group_rank_top; v's scratch reserved): launch(out_stage, rank_stage, cap, d_n) enqueues it on the read stream; the selected
+// rows, rank rows (through rank_stage, the ranking's staging; NULL without rank_out) and indices come back, then the counts
 template <class L>
-int node_top_host(sg_engine* e, const NodeSpace& v, L launch, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap,
-                  size_t* n_selected, size_t* n_nodes) {
+int node_top_host(sg_engine* e, const NodeSpace& v, L launch, sg_node_out* out, sg_node_rank* rank_out, sg_node_rank* rank_stage,
+                  uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes) {
     sg_engine::NSel& s = *v.sel;
     const u64 NC = std::max<u32>(v.cap, 1);
     const u64 stage = std::min<u64>(cap, NC);
-    if (const int rc = launch(out ? s.stage : nullptr, rank_out ? e->rank.stage : nullptr, stage, s.n)) return rc;
+    if (const int rc = launch(out ? s.stage : nullptr, rank_out ? rank_stage : nullptr, stage, s.n)) return rc;
     u64 cnt = 0;
     HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
     HIP_TRY(e, hipMemcpyAsync(&cnt, v.roll->count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
@@ -1370,7 +1420,7 @@ int node_top_host(sg_engine* e, const NodeSpace& v, L launch, sg_node_out* out, 
     const u64 m = *s.h_n;
     const size_t take = (size_t)std::min<u64>(m, stage);
     if (out && take) HIP_TRY(e, hipMemcpyAsync(out, s.stage, take * sizeof(sg_node_out), hipMemcpyDeviceToHost, e->rd_stream));
-    if (rank_out && take) HIP_TRY(e, hipMemcpyAsync(rank_out, e->rank.stage, take * sizeof(sg_node_rank), hipMemcpyDeviceToHost, e->rd_stream));
+    if (rank_out && take) HIP_TRY(e, hipMemcpyAsync(rank_out, rank_stage, take * sizeof(sg_node_rank), hipMemcpyDeviceToHost, e->rd_stream));
     if (node_index && take) HIP_TRY(e, hipMemcpyAsync(node_index, s.idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
     HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
     if (n_selected) *n_selected = (size_t)m;
@@ -2557,7 +2607,7 @@ int nodes_top(sg_engine* e, const NodeSpace& ns, const char* call, u32 by, u32 k
     if (const int rc = nsel_reserve(e, ns)) return rc;
     return node_top_host(e, ns, [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
         return launch_node_select_by(e, ns, e->rd_stream, e->cur, by, k, min_value, d_out, nullptr, stage, d_n);
-    }, out, nullptr, node_index, cap, n_selected, n_nodes);
+    }, out, nullptr, nullptr, node_index, cap, n_selected, n_nodes);
 }
 int nodes_select(sg_engine* e, const NodeSpace& ns, u32 by, u32 k, float min_value, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n,
                  void* stream) {
@@ -2691,8 +2741,8 @@ int sg_window_rank_top(sg_handle e, uint32_t k, float min_share, sg_node_out* ou
     if (const int rc = check_rsel(e, e->cur)) return rc;
     if (const int rc = nsel_reserve(e, node_space(e))) return rc;
     return node_top_host(e, node_space(e), [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
-        return launch_rank_select(e, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
-    }, out, rank_out, node_index, cap, n_selected, n_nodes);
+        return launch_rank_select(e, node_space(e), e->rank, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
+    }, out, rank_out, e->rank.stage, node_index, cap, n_selected, n_nodes);
 }
 int sg_window_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n, void* stream) {
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
@@ -2700,7 +2750,7 @@ int sg_window_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out*
     const int slot = ran_slot(e);
     if (const int rc = check_rsel(e, slot)) return rc;
     if (const int rc = nsel_reserve(e, node_space(e))) return rc;
-    return launch_rank_select(e, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return launch_rank_select(e, node_space(e), e->rank, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // ---- K12, the incidents -----------------------------------------------------------------------------------------------------------
@@ -3014,6 +3064,86 @@ int sg_window_group_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     return nodes_select(e, workload_space(e), by, k, min_value, d_out, d_index, cap, d_n, stream);
+}
+
+// ---- K17, the workload ranking -----------------------------------------------------------------------------------------------------
+int sg_set_group_rank(sg_handle e, const sg_rank_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->gnodes.on) { e->err = "sg_set_group_rank: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_group_rank while a flush is open"; return SG_ESTATE; }
+    sg_rank_params q{};
+    if (p && sgplan::check_rank(*p, &q)) { e->err = "sg_set_group_rank: bad parameters"; return SG_EINVAL; }
+    free_group_rank(e);
+    if (!p) return SG_OK;
+    sg_engine::GroupRank& r = e->grank;
+    const u32 slots = (u32)e->slots.size();
+    r.p = q;
+    r.plan = sgplan::plan_group_rank(e->cfg.max_edges, e->gnodes.plan.nc, e->gnodes.plan.gk, slots);
+    const sgplan::GroupRankPlan& P = r.plan;
+    HIP_TRY(e, lds_limit(P.lds_bytes, k17_edge<true>, k17_edge<false>));
+    HIP_TRY(e, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &r.mem, P.total_bytes, "sg_set_group_rank", [e] { free_group_rank(e); })) return rc;
+    r.W = at<u64>(r.mem, P.node_off[0]); r.R = at<u64>(r.mem, P.node_off[1]); r.base = at<u64>(r.mem, P.node_off[2]); r.t = at<u64>(r.mem, P.node_off[3]);
+    r.part = at<u64>(r.mem, P.part_off);
+    r.seed_sum = at<u64>(r.mem, P.seed_off);
+    r.pos = at<u32>(r.mem, P.pos_off);
+    r.src = at<u32>(r.mem, P.edge_off[0]); r.dst = at<u32>(r.mem, P.edge_off[1]); r.w = at<u64>(r.mem, P.w_off);
+    r.stage = at<sg_node_rank>(r.mem, P.stage_off);
+    r.stage_idx = at<u32>(r.mem, P.stage_idx_off);
+    for (u32 k = 0; k < slots; k++) r.rows.push_back(at<sg_node_rank>(r.mem, P.slot.off + k * P.slot.bytes + P.slot_rows));
+    r.valid.assign(slots, 0);
+    r.on = true;
+    return SG_OK;
+}
+int sg_window_group_rank(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_rank* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    sg_engine::GroupRank& r = e->grank;
+    if (const int rc = stage_ready(e, r, "sg_window_group_rank", kGroupRankWords)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->gnodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    return copy_indexed(e, (const sg_node_rank*)r.rows[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, r.stage, r.stage_idx,
+                        std::max<size_t>(r.plan.nc, 1), "sg_window_group_rank: a node index beyond the window's workload rows");
+}
+int sg_window_group_rank_buffer(sg_handle e, void** d_rank) {
+    if (!e || !d_rank) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::GroupRank& r = e->grank;
+    int slot;
+    if (const int rc = stage_slot(e, r, "sg_window_group_rank_buffer", kGroupRankWords, &slot)) return rc;
+    *d_rank = r.rows[slot];
+    return SG_OK;
+}
+namespace {
+int check_grsel(sg_engine* e, int slot) {
+    if (!e->gnodes.on) { e->err = "workload rank selection: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
+    if (!e->grank.on) { e->err = "workload rank selection: the workload ranking is off (sg_set_group_rank)"; return SG_ESTATE; }
+    if (!e->gnodes.valid[slot] || !e->grank.valid[slot]) { e->err = "workload rank selection: the window was closed while the workload ranking was off"; return SG_ESTATE; }
+    return SG_OK;
+}
+}  // namespace
+int sg_window_group_rank_top(sg_handle e, uint32_t k, float min_share, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap,
+                             size_t* n_selected, size_t* n_nodes) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->closing || e->flush_open) { e->err = "sg_window_group_rank_top while a flush is open"; return SG_ESTATE; }
+    if (const int rc = check_grsel(e, e->cur)) return rc;
+    const NodeSpace ns = workload_space(e);
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    return node_top_host(e, ns, [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
+        return launch_rank_select(e, ns, e->grank, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
+    }, out, rank_out, e->grank.stage, node_index, cap, n_selected, n_nodes);
+}
+int sg_window_group_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n,
+                                void* stream) {
+    if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int slot = ran_slot(e);
+    if (const int rc = check_grsel(e, slot)) return rc;
+    const NodeSpace ns = workload_space(e);
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    return launch_rank_select(e, ns, e->grank, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // ---- K13, the tracks ---------------------------------------------------------------------------------------------------------------

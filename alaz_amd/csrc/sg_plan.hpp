@@ -1100,6 +1100,85 @@ inline TrendPlan plan_group_node_trend(u32 nc, u32 slots, const sg_trend_params&
 // the selection over workload rows: plan_node_select over NC rows
 inline NodeSelPlan plan_group_node_select(u32 nc, u64 counter_bytes) { return plan_node_select(nc, counter_bytes); }
 
+// K17, the workload ranking (sg_group_rank.h): the device memory sg_set_group_rank allocates — never sg_create, sg_set_groups or
+// sg_set_group_nodes; the parameters are K11's (check_rank).  Work is in ROW-INDEX space: K16's rows are dense, so the per-node
+// arrays are [NC] by row position and k17_edge's live ranges are the first ceil(n / 8192) of a window with n rows.
+//   range   8192 rows = 64 KiB of u64 accumulators: two 1024-thread workgroups fit a CU's 160 KiB of LDS (K11's 128 KiB range
+//           fits one), and a workload window of a few thousand rows is one live range either way
+//   slices  one per 2048 group edges, at most 256: the live range of a window with about 590 k group edges and 5.6 k rows then
+//           runs 256 workgroups — one per CU — where K11's 32 K rows a slice and 256-workgroup cap give 32.  Each workgroup
+//           scans about 2.3 k group edges (under one trip of 1024 threads x 4) and writes min(8192, n) words
+//   budget  the partials are [ranges][slices][8192] u64 whether a range is live or not, so slices are cut until they fit in
+//           128 MiB (K16's partials at its 2^21-key limit take as much): 256 ranges leave 8 slices, up to 8 ranges all 256
+// k17_pos and k17_prep run a grid-stride grid of 256-thread workgroups, at most 1024 (k17_node sums one seed sum per k17_pos
+// workgroup); k17_node takes 32 rows a workgroup and round, eight threads sharing the up to 256 partials of a row: a row a thread
+// made 22 workgroups of 256 serial loads each on the 5.6 k-row window, 23 us a pass against the edge pass's 9.  The scratch is shared by the window slots; each slot keeps its rank rows; one staging block serves
+// sg_window_group_rank's index form and sg_window_group_rank_top.
+constexpr u32 kGrpRankThreads = 256, kGrpRankRangeRows = 8192, kGrpRankSliceEdges = 2048, kGrpRankMaxSlices = 256, kGrpRankMaxWgs = 1024,
+              kGrpRankNodeRows = 32;
+constexpr u64 kGrpRankPartBudget = 128ull << 20;
+struct GroupRankPlan {
+    u32 nc = 0;                   // workload rows per window slot (GroupNodesPlan::nc)
+    u64 gk = 0;                   // group keys (GroupNodesPlan::gk)
+    u32 ranges = 0, slices = 0;   // k17_edge's grid = ranges x slices
+    u32 pos_wgs = 0;              // k17_pos: grid-stride over nc
+    u32 prep_wgs = 0;             // k17_prep: grid-stride over max_edges
+    u32 node_wgs = 0;             // k17_node: blocks of 32 rows, grid-stride over nc
+    u64 pos_bytes = 0;            // [gk] u32 row position by group key
+    u64 edge_bytes = 0;           // one per-group-edge u32 array [max_edges] (src, dst: two of them)
+    u64 w_bytes = 0;              // [max_edges] u64 weights
+    u64 node_bytes = 0;           // one per-row u64 array [nc] (W, R, base, t: four of them)
+    u64 part_bytes = 0;           // [ranges][slices][8192] u64
+    u64 seed_bytes = 0;           // [1024] u64
+    u64 stage_bytes = 0;          // [nc] sg_node_rank staging
+    u64 stage_idx_bytes = 0;      // [nc] u32 staging
+    u64 rows_bytes = 0;           // one window slot's rank rows: [nc] sg_node_rank
+    u64 lds_bytes = 0;            // k17_edge's dynamic LDS
+    u64 total_bytes = 0;          // the scratch, the staging and every slot's rows, each 256-byte aligned
+    u64 node_off[4] = {}, part_off = 0, seed_off = 0, pos_off = 0, edge_off[2] = {}, w_off = 0, stage_off = 0, stage_idx_off = 0;   // (node_off: W, R, base, t; edge_off: src, dst)
+    Slots slot; u64 slot_rows = 0;
+    std::vector<Piece> layout;
+};
+// the workgroups of k17_edge that work on a window of n rows (the others exit at once)
+inline u32 group_rank_live_wgs(const GroupRankPlan& r, u64 n) {
+    return (u32)std::min<u64>(r.ranges, (n + kGrpRankRangeRows - 1) / kGrpRankRangeRows) * r.slices;
+}
+inline GroupRankPlan plan_group_rank(u64 max_edges, u32 nc, u64 gk, u32 slots) {
+    GroupRankPlan r;
+    const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(nc, 1), GK = std::max<u64>(gk, 1);
+    r.nc = nc; r.gk = gk;
+    r.ranges = (u32)((NC + kGrpRankRangeRows - 1) / kGrpRankRangeRows);
+    r.slices = (u32)std::max<u64>(1, std::min<u64>(kGrpRankMaxSlices, (ME + kGrpRankSliceEdges - 1) / kGrpRankSliceEdges));
+    r.slices = (u32)std::max<u64>(1, std::min<u64>(r.slices, kGrpRankPartBudget / ((u64)r.ranges * kGrpRankRangeRows * 8)));
+    r.pos_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpRankMaxWgs, (NC + kGrpRankThreads - 1) / kGrpRankThreads));
+    r.prep_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpRankMaxWgs, (ME + 4 * kGrpRankThreads - 1) / (4 * kGrpRankThreads)));
+    r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpRankMaxWgs, (NC + kGrpRankNodeRows - 1) / kGrpRankNodeRows));
+    r.pos_bytes = trend_align(GK * 4);
+    r.edge_bytes = trend_align(ME * 4);
+    r.w_bytes = trend_align(ME * 8);
+    r.node_bytes = trend_align(NC * 8);
+    r.part_bytes = trend_align((u64)r.ranges * r.slices * kGrpRankRangeRows * 8);
+    r.seed_bytes = trend_align((u64)kGrpRankMaxWgs * 8);
+    r.stage_bytes = trend_align(NC * sizeof(sg_node_rank));
+    r.stage_idx_bytes = trend_align(NC * 4);
+    r.rows_bytes = trend_align(NC * sizeof(sg_node_rank));
+    r.lds_bytes = (u64)kGrpRankRangeRows * 8;
+    Block b;
+    const char* const node[4] = {"W", "R", "base", "t"};
+    const char* const edge[2] = {"src", "dst"};
+    for (int k = 0; k < 4; k++) r.node_off[k] = b.take(node[k], r.node_bytes);
+    r.part_off = b.take("part", r.part_bytes);
+    r.seed_off = b.take("seed", r.seed_bytes);
+    r.pos_off = b.take("pos", r.pos_bytes);
+    for (int k = 0; k < 2; k++) r.edge_off[k] = b.take(edge[k], r.edge_bytes);
+    r.w_off = b.take("w", r.w_bytes);
+    r.stage_off = b.take("stage", r.stage_bytes);
+    r.stage_idx_off = b.take("stage_idx", r.stage_idx_bytes);
+    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}});
+    r.total_bytes = b.end; r.layout = std::move(b.pieces);
+    return r;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

@@ -261,6 +261,10 @@ def _signatures() -> dict:
         "sg_group_node_trend_stats_get": (I, [H, P]),
         "sg_window_group_nodes_top": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
         "sg_window_group_nodes_select": (I, [H, u32, u32, f32, P, P, sz, P, P]),
+        "sg_set_group_rank": (I, [H, P]), "sg_window_group_rank": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_rank_buffer": (I, [H, PP]),
+        "sg_window_group_rank_top": (I, [H, u32, f32, P, P, P, sz, Psz, Psz]),
+        "sg_window_group_rank_select": (I, [H, u32, f32, P, P, sz, P, P]),
     }
 
 
@@ -302,6 +306,8 @@ _STAGES = dict(
                           "group vanished"),
     group_node_trend=_Stage("sg_set_group_node_trend", SgTrendParams, TREND_DEFAULTS,
                             "set_group_node_trend(None) switches the workload trend off", "workload trend"),
+    group_rank=_Stage("sg_set_group_rank", SgRankParams, RANK_DEFAULTS, "set_group_rank(None) switches the workload ranking off",
+                      "workload rank", dict(seed=_rank_seed)),
 )
 
 _lib = None
@@ -931,6 +937,34 @@ class ServiceGraph:
         window's stream)."""
         self._ck(self._l.sg_window_group_nodes_select(self._h, self._nby(by), k, min_value, d_out or None, d_index or None, cap, d_n,
                                                       stream or None))
+
+    # ---- workload ranking (K17): K11's walk over the group edges and the workload rows ----
+    def set_group_rank(self, params: Optional[dict] = (), **kw):
+        """Switch the per-window workload ranking on (sg_set_group_rank; set_rank's parameters — see RANK_DEFAULTS; needs the workload
+        rows on; independent of set_rank) or off: set_group_rank(None)."""
+        self._set_stage("group_rank", params, kw)
+
+    def window_group_rank(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """RANK_DTYPE rows of the last read window (sg_window_group_rank), row k for row k of window_group_nodes(); or the rows at
+        `index` (only those cross PCIe)."""
+        return self._window_rows(self._l.sg_window_group_rank, RANK_DTYPE, index)
+
+    def window_group_rank_buffer(self) -> int:
+        """device pointer of the workload rank rows of the window window_run closed last (sg_window_group_rank_buffer)"""
+        return self._pointers(self._l.sg_window_group_rank_buffer, 1)[0]
+
+    def window_group_rank_top(self, k: int, min_share: float = float("-inf"), cap: Optional[int] = None):
+        """(workload rows, rank rows, row indices, n_nodes) of a selection over the last read window's workload rank rows
+        (sg_window_group_rank_top): window_rank_top with "node row" read as "workload row".  cap defaults to k (k > 0) or the
+        window's row count."""
+        return self._top(lambda *a: self._l.sg_window_group_rank_top(self._h, k, min_share, *a),
+                         self._node_cap(k, cap, self._l.sg_window_group_nodes), NODE_DTYPE, RANK_DTYPE, np.uint32)
+
+    def window_group_rank_select(self, k: int, min_share: float, d_out: int, d_index: int, cap: int, d_n: int, stream: int = 0):
+        """Select from the workload rank rows of the window window_run closed last into device memory
+        (sg_window_group_rank_select): d_out [cap] workload rows (0 = none), d_index [cap] u32 (0 = none), d_n one u64 = rows
+        selected; enqueued on `stream` (0 = that window's stream)."""
+        self._ck(self._l.sg_window_group_rank_select(self._h, k, min_share, d_out or None, d_index or None, cap, d_n, stream or None))
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

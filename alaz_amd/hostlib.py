@@ -45,6 +45,13 @@ def _workload_node_dtype():
     return np.dtype([("type", "S16"), ("uid", "S160"), ("row", NODE_DTYPE)])
 
 
+#: sgh_workload_culprit of host_capi.cpp: one selected workload of the ranking (GraphDS::WorkloadCulprits) — the workload row as
+#: _workload_node_dtype has it, then the engine's sg_node_rank as engine.RANK_DTYPE has it
+def _workload_culprit_dtype():
+    from .engine import RANK_DTYPE
+    return np.dtype([("node", _workload_node_dtype()), ("rank", RANK_DTYPE)])
+
+
 _lib = None
 
 
@@ -126,6 +133,8 @@ def load() -> C.CDLL:
             "sgh_graphds_set_workload_node_trend": (C.c_int, [P, u32, u32, u32, C.c_uint64]),
             "sgh_graphds_workload_nodes": (C.c_long, [P, P, sz]), "sgh_graphds_workload_node_trends": (C.c_long, [P, P, sz]),
             "sgh_graphds_workload_nodes_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]), "sgh_mock_k16_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_workload_rank": (C.c_int, [P, C.c_int, u32, u32, u32, C.c_float]),
+            "sgh_graphds_workload_culprits": (C.c_long, [P, u32, C.c_float, P, P, sz]), "sgh_mock_k17_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -531,6 +540,29 @@ class GraphDS:
         n = self._l.sgh_mock_k16_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k16_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the workload ranking (K17) ----
+    def set_workload_rank(self, on: bool = True, iters: int = 0, damping_q8: int = 0, seed: int = 0, seed_min_score: float = 0.0) -> int:
+        """GraphDS::SetWorkloadRank: the per-window workload ranking on (a 0 = the parameter's default) or off (rc)"""
+        return self._l.sgh_graphds_set_workload_rank(self._g, 1 if on else 0, iters, damping_q8, seed, seed_min_score)
+
+    def workload_culprits(self, k: int, min_share: float = float("-inf")):
+        """GraphDS::WorkloadCulprits: (the selected workloads — node: the row as workload_nodes() gives it, rank: engine.RANK_DTYPE —
+        and their indices)"""
+        n = self._l.sgh_graphds_workload_culprits(self._g, k, min_share, None, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadCulprits failed: {n}")
+        out, idx = np.zeros(max(n, 1), dtype=_workload_culprit_dtype()), np.zeros(max(n, 1), dtype=np.uint32)
+        self._l.sgh_graphds_workload_culprits(self._g, k, min_share, out.ctypes.data, idx.ctypes.data, n)
+        return out[:n], idx[:n]
+
+    def mock_k17_ops(self) -> np.ndarray:
+        """the stand-in engine's K17 calls in order, four u64 each: (1, iters, damping_q8, seed) per sg_set_group_rank (all ones in the
+        three for NULL), (2, k, the bits of min_share, cap) per sg_window_group_rank_top"""
+        n = self._l.sgh_mock_k17_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k17_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

@@ -1321,6 +1321,72 @@ func (g *GraphDS) WindowWorkloadNodesTop(by, k uint32, minValue float32) ([]Work
 	return goWorkloadNodes(ns), index, nil
 }
 
+// ---- workload ranking (K17) ----------------------------------------------------------------------------------------------
+
+// WorkloadCulprit is one workload of a window's workload ranking: its row as WindowWorkloadNodes gives it, the walk's mass that
+// ended at it (sg_node_rank.rank, of 2^56) and that as a share.
+type WorkloadCulprit struct {
+	Node  WorkloadNode
+	Rank  uint64
+	Share float32
+}
+
+// SetWorkloadRank switches the per-window workload ranking on, behind SetWorkloadNodes: K11's walk over the window's group edges and
+// workload rows, so that the answer is a workload and survives a rollout; iters and dampingQ8 0 = the defaults (20, 218).  It is
+// independent of SetRank.  ClearWorkloadRank switches it off; SetWorkloadNodes(false) and any SetGroups call do so too.
+func (g *GraphDS) SetWorkloadRank(iters, dampingQ8 uint32, uniformSeed bool, seedMinScore float32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var rp C.sg_rank_params
+	rp.struct_size = C.uint32_t(unsafe.Sizeof(rp))
+	rp.iters, rp.damping_q8, rp.seed, rp.seed_min_score = C.uint32_t(iters), C.uint32_t(dampingQ8), C.SG_RANK_SEED_SCORE, C.float(seedMinScore)
+	if uniformSeed {
+		rp.seed = C.SG_RANK_SEED_UNIFORM
+	}
+	if rc := C.sg_set_group_rank(g.h, &rp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_group_rank = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func (g *GraphDS) ClearWorkloadRank() {
+	g.flushMu.Lock()
+	C.sg_set_group_rank(g.h, nil)
+	g.flushMu.Unlock()
+}
+
+// WindowWorkloadCulprits selects from the workload rank rows of the window FlushWindow returned last on the device
+// (sg_window_group_rank_top): the k highest-ranked workloads with share >= minShare, descending, ties by position (k = 0: every
+// such workload, in row order), and their indices into WindowWorkloadNodes.  Only they cross PCIe.
+func (g *GraphDS) WindowWorkloadCulprits(k uint32, minShare float32) ([]WorkloadCulprit, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_group_rank_top(g.h, 0, C.float(minShare), nil, nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, fmt.Errorf("servicegraph: sg_window_group_rank_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil
+	}
+	ns, rs, index := make([]C.sg_node_out, room), make([]C.sg_node_rank, room), make([]uint32, room)
+	if rc := C.sg_window_group_rank_top(g.h, C.uint32_t(k), C.float(minShare), &ns[0], &rs[0], (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, fmt.Errorf("servicegraph: sg_window_group_rank_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		ns, rs, index = ns[:int(sel)], rs[:int(sel)], index[:int(sel)]
+	}
+	nodes := goWorkloadNodes(ns)
+	out := make([]WorkloadCulprit, len(nodes))
+	for i := range out {
+		out[i] = WorkloadCulprit{nodes[i], uint64(rs[i].rank), float32(rs[i].share)}
+	}
+	return out, index, nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

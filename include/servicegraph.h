@@ -875,6 +875,52 @@ int sg_window_group_nodes_top(sg_handle h, uint32_t by, uint32_t k, float min_va
 int sg_window_group_nodes_select(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* d_out, uint32_t* d_index,
                                  size_t cap, uint64_t* d_n, void* stream);
 
+/* ---- workload ranking (K17): each window's likely root-cause workloads, by K11's walk over the contracted graph, on the device -- *
+ * Opt-in (sg_set_group_rank, on an engine with the workload rows); without it nothing is computed or allocated, and every other row
+ * is the same either way.  It is independent of sg_set_rank: both may be on, and neither reads the other.  K11 ranks pods: a
+ * Deployment of 20 replicas is 20 nodes of its walk, the mass that reaches the workload is split 20 ways, a rollout renames all of
+ * them and the answer is a pod.  This stage walks the workload map instead.  There is no new struct and no new constant: the
+ * parameters are sg_rank_params (K11's defaults and checks), the rows sg_node_rank, the seeds SG_RANK_SEED_*.  Integer arithmetic
+ * only (u64, every intermediate below 2^64), so the result has one correct value.
+ * Over the window's group edges j = 0 .. G-1 (sg_window_groups order, G = min(count, max_edges)) and its workload rows v = 0 .. n-1
+ * (sg_window_group_nodes order, ascending group key):
+ *   w_j     = edges_j + min(score_q32_j >> 16, 65536 * edges_j), a uint64_t, at most 65537 * edges_j: what the group edge carries
+ *             of its rows' 1 + q16(score).  A group edge that folds one row has exactly K11's w of that row.  A group edge whose
+ *             from_ref or to_ref has no group key (a ref beyond the id spaces; no window has one) carries w_j = 0.  A group edge
+ *             inside a workload (from_ref == to_ref) and an alive-only group edge are ordinary edges
+ *   W_u     = sum of w_j over the group edges with from_ref == row u's ref (at most 65537 * E rows, as K11)
+ *   seed    K11's rule over the workload rows: SG_RANK_SEED_SCORE: a_v = row.score >= seed_min_score ? q16(row.score) : 0;
+ *           SG_RANK_SEED_UNIFORM: a_v = 1;  A = sum of a_v; A == 0: the seed falls back to uniform (a_v = 1, A = n)
+ *   M = 2^56;  p_v = a_v * floor(M / A);  D = damping_q8;  R_v = (p_v >> 8) * (256 - D);  r_v = p_v
+ *   one iteration, `iters` times:
+ *           m_u = (r_u >> 8) * D;  t_u = W_u ? floor(m_u / W_u) : 0;
+ *           r'_v = R_v + (m_v - t_v * W_v) + sum over the group edges j with to_ref == row v's ref of t_{from_j} * w_j
+ *   row v   rank = r_v after the last iteration, ref = the workload row's group ref, share = (float)((double)rank * 2^-56)
+ * Invariants (K11's, unchanged): sum r' == sum R + sum m exactly, and sum r <= M; hence t_u * w_j <= m_u < 2^56.
+ * Under a map that groups nothing the workload rows are the node rows and every group edge is one row: the rank rows then equal
+ * sg_window_rank's of the same window byte for byte (floor(s * 2^32) >> 16 == floor(s * 2^16) for every score).
+ * Selection is K11's over these rank rows: key min(rank >> 24, 0xFFFFFFFF), key 0 is not a candidate, share >= min_share, k = 0
+ * every candidate in row order, 1 <= k <= SG_SELECT_MAX_K the highest keys descending, ties by row position; the selected rows are
+ * byte-identical to sg_window_group_nodes'.
+ * State: sg_set_group_rank is SG_ESTATE with the workload rows off (sg_set_group_nodes) or while a flush is open, SG_EINVAL on bad
+ * parameters; NULL = off (frees its memory).  Memory is allocated there, never at sg_create, sg_set_groups or sg_set_group_nodes.
+ * sg_set_group_nodes(h, 0) and ANY sg_set_groups call switch it off and free it; sg_group_assign does not touch it.  Reads of a
+ * window closed while it was off: SG_ESTATE.  Every close path computes it (one call, begin + end, the views, the _top flushes,
+ * sg_window_run, the staged sg_window_score), behind K16 and K16's baseline on the window's stream.                              */
+int sg_set_group_rank(sg_handle h, const sg_rank_params* p);
+/* The rank rows of the last READ window (as sg_window_rank): node_index NULL: every workload row, *n = workload rows; else out[k] =
+ * the row of workload row node_index[k] (each < workload rows, else SG_EINVAL), *n = n_index.  min(*n, cap) rows are written.      */
+int sg_window_group_rank(sg_handle h, const uint32_t* node_index, size_t n_index, sg_node_rank* out, size_t cap, size_t* n);
+/* Device sg_node_rank[] of the window sg_window_run closed last (its count is sg_window_group_nodes_buffer's; valid until the slot
+ * is reused; read it on that window's stream).                                                                                   */
+int sg_window_group_rank_buffer(sg_handle h, void** d_rank);
+/* sg_window_rank_top / sg_window_rank_select with "node row" read as "workload row": out [cap] workload rows, rank_out [cap] their
+ * rank rows, node_index [cap] their positions (each may be NULL).  k > SG_SELECT_MAX_K: SG_EINVAL.                                */
+int sg_window_group_rank_top(sg_handle h, uint32_t k, float min_share, sg_node_out* out, sg_node_rank* rank_out,
+                             uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
+int sg_window_group_rank_select(sg_handle h, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index,
+                                size_t cap, uint64_t* d_n, void* stream);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.

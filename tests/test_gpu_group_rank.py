@@ -1,0 +1,445 @@
+"""K17, the workload ranking (sg_set_group_rank / sg_window_group_rank / sg_window_group_rank_buffer / sg_window_group_rank_top /
+sg_window_group_rank_select): the rank rows of every window against the pure-Python reference tests/group_rank_ref.py run on the
+device's own window_groups() and window_group_nodes() of that window — byte for byte, the contract is integer; under the map that
+groups nothing against K11's rows of the same engine; an engine with it against a twin without it; tiny windows at the boundaries of
+the row ranges (8192 rows) and of the group-edge slices; every close path and sg_window_run with three windows in flight; the
+selection against ref_select_rank; the lifecycle; and a rollout where the culprit workload keeps its name while K11's pods change."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from alaz_amd import engine, replay, weights
+from tests.group_rank_ref import group_rank_ref, seed_sum
+from tests.helpers import CLOCK, HostShim
+from tests.probe_weights import offsets
+from tests.rank_ref import M, ref_select_rank
+from tests.test_gpu_group_nodes import _events, _send
+from tests.test_gpu_groups import _grouped, _pods_engine
+from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixtures)
+from tests.test_gpu_rank import _d2h, _hip
+
+pytestmark = pytest.mark.gpu
+
+NO = engine.NO_GROUP
+NR = 8192                                                             # K17_NR: workload rows per range of k17_edge
+INF = float("inf")
+EXT = 0x5DB8D800                                                      # addresses outside the cluster
+
+
+def G(g):
+    return (engine.REF_GROUP << 30) | g
+
+
+def _check(g, ge=None, gn=None, got=None, **params):
+    """the last read window's workload rank rows (or `got`) against the reference over the device's own group edges and workload
+    rows; the mass invariant on the device result"""
+    ge = g.window_groups() if ge is None else ge
+    gn = g.window_group_nodes() if gn is None else gn
+    got = g.window_group_rank() if got is None else got
+    want = group_rank_ref(ge, gn, **params)
+    assert len(got) == len(gn) == len(want)
+    assert got["rank"].tobytes() == want["rank"].tobytes()
+    assert got.tobytes() == want.tobytes()
+    if len(got):
+        total = sum(int(x) for x in got["rank"])
+        assert 0 < total <= M and int(got["rank"].max()) <= M
+        assert (got["ref"] == gn["ref"]).all()
+    return got
+
+
+# ---- 1. the churn ------------------------------------------------------------------------------------------------------------------
+# the parameters of the churn's windows in turn: iters 1 / 20 / 64, both seeds, damping 1 / 131 / 255, and a seed threshold no
+# workload reaches (A == 0: the uniform fallback)
+CHURN_PARAMS = (dict(iters=1, damping_q8=1), dict(iters=20, damping_q8=131, seed="uniform"),
+                dict(iters=64, damping_q8=255, seed_min_score=2.0), dict(), dict(iters=3, seed_min_score=0.5), dict(iters=2, seed="uniform"))
+
+
+@pytest.mark.parametrize("kind", ["none", "blocks", "one"])
+def test_churn_under_three_maps(churn, kind):
+    """every window under each map; "none" with K11 on as well and the same parameters: the workload rank rows are K11's"""
+    topo, labels, wins = churn
+    g, gmap, mk = _grouped(topo, labels, kind)
+    g.set_group_nodes()
+    if kind == "none":
+        g.set_nodes()
+    sizes, fell_back = set(), 0
+    for i, w in enumerate(wins):
+        p = CHURN_PARAMS[i % len(CHURN_PARAMS)]
+        g.set_group_rank(**p)
+        if kind == "none":
+            g.set_rank(**p)
+        _feed(g, w)
+        rows = g.flush_window()
+        n_rows = len(rows)
+        ge, gn = g.window_groups(), g.window_group_nodes()
+        rk = _check(g, ge, gn, **p)
+        sizes.add(len(rk))
+        fell_back += seed_sum(gn, p.get("seed", "score"), p.get("seed_min_score", 0.0)) == 0
+        if kind == "none":
+            assert len(ge) == n_rows and rk.tobytes() == g.window_rank().tobytes()
+        else:
+            assert len(ge) < n_rows and gn["ref"][0] == G(0)
+    assert fell_back >= 2 and len(sizes) > (1 if kind == "one" else 3)
+
+
+def test_a_twin_without_it_is_unchanged(churn):
+    """rows, group edges, K15's output, workload rows and their trend of an engine with the ranking against a twin without it"""
+    topo, labels, wins = churn
+    (g, _, mk), (twin, _, _) = _grouped(topo, labels, "blocks"), _grouped(topo, labels, "blocks")
+    for x in (g, twin):
+        x.set_group_trend(shift=3, warmup=2, ttl=3); x.set_group_vanished(silent_windows=1, min_seen=1)
+        x.set_group_nodes(); x.set_group_node_trend(shift=3, warmup=2, ttl=2)
+    p = dict(iters=3, damping_q8=131, seed_min_score=0.5)
+    g.set_group_rank(**p)
+    for w in wins[:8]:
+        _feed(g, w); _feed(twin, w)
+        assert g.flush_window().tobytes() == twin.flush_window().tobytes()
+        assert g.window_groups().tobytes() == twin.window_groups().tobytes()
+        assert g.window_row_group().tobytes() == twin.window_row_group().tobytes()
+        assert g.window_group_trend().tobytes() == twin.window_group_trend().tobytes()
+        assert g.window_group_vanished().tobytes() == twin.window_group_vanished().tobytes()
+        assert g.window_group_nodes().tobytes() == twin.window_group_nodes().tobytes()
+        assert g.window_group_node_trend().tobytes() == twin.window_group_node_trend().tobytes()
+        _check(g, **p)
+    assert g.group_trend_entries().tobytes() == twin.group_trend_entries().tobytes()
+    assert g.group_node_trend_entries().tobytes() == twin.group_node_trend_entries().tobytes()
+    assert _rc(twin.window_group_rank) == engine.SG_ESTATE
+
+
+# ---- 2. boundary shapes -------------------------------------------------------------------------------------------------------------
+MG = 3000                                                             # max_groups: KNOWN ids 2999, 3000, 3001 lie on either side of it
+N_PODS = 16_500
+P2 = dict(iters=2)
+
+
+@pytest.fixture(scope="module")
+def big():
+    """16 500 pods, max_edges 32 768: plan_group_rank has 16 slices and 3 ranges of 8192 rows (about 19.6 k group keys).  Workload 5 = pods 0, 1; workloads
+    0 .. 2 = pods 2, 3, 4; everything else is ungrouped"""
+    topo = replay.make_topology(N_PODS, 4 * N_PODS, seed=7, svcs=4)
+    mk = topo.n_nodes + 8
+    g = engine.ServiceGraph(max_known_nodes=mk, max_edges=1 << 15, layers=2, max_labels=16, max_outbound_ips=64, max_window_events=1 << 16,
+                            max_batch=1 << 14)
+    g.set_clock(*CLOCK); g.load_weights(weights.make_weights(2))
+    HostShim().apply(g, topo.k8s_ops()); g.set_label_count(2)
+    g.set_groups(max_groups=MG); g.group_assign([0, 1, 2, 3, 4], [5, 5, 0, 1, 2])
+    g.set_group_nodes(); g.set_group_rank(**P2)
+    return topo, g, mk
+
+
+SLICES = 16                                                           # ceil(32 768 / 2048)
+
+
+def test_windows_of_no_and_of_one_group_edge(big):
+    topo, g, mk = big
+    none = np.zeros(0, np.int64)
+    _send(topo, g, none, none)
+    assert len(_check(g, **P2)) == 0 and len(g.window_groups()) == 0
+    assert [len(x) for x in g.window_group_rank_top(3)[:3]] == [0, 0, 0]
+    _send(topo, g, [0, 1], [1, 0])                                    # one group edge INSIDE workload 5: one row, an ordinary edge
+    rk = _check(g, **P2)
+    assert len(g.window_groups()) == 1 and rk["ref"].tolist() == [G(5)] and M - int(rk["rank"][0]) < 1 << 17
+    _send(topo, g, [9], [10])                                         # one group edge, a source and a sink
+    rk = _check(g, **P2)
+    assert rk["ref"].tolist() == [9, 10] and rk["rank"][1] > rk["rank"][0]
+
+
+def test_a_window_of_alive_only_group_edges(big):
+    topo, g, mk = big
+    src = np.arange(100, 400); dst = 100 + (np.arange(300) * 7 + 1) % 300
+    rows = _send(topo, g, src, dst, alive=np.ones(300, bool))
+    assert (rows["count"] == 0).all() and len(rows) == 300
+    _check(g, **P2)
+
+
+@pytest.mark.parametrize("n", [NR - 1, NR, NR + 1, 2 * NR + 1])
+def test_row_counts_around_the_range_size(big, n):
+    """a path over n ungrouped pods (n - 1 group edges, n workload rows) and edges from the first and the last range into the others"""
+    topo, g, mk = big
+    lo = 10
+    path_s = np.arange(lo, lo + n - 1)
+    far_s = np.array([lo, lo, lo + n - 1, lo + n - 1, lo + n // 2])
+    far_d = np.array([lo + n - 1, lo + n // 2, lo, lo + n // 2, lo + 2])
+    _send(topo, g, np.concatenate([path_s, far_s]), np.concatenate([path_s + 1, far_d]))
+    rk = _check(g, **P2)
+    assert len(rk) == n and len(g.window_groups()) == n - 1 + 5
+
+
+@pytest.mark.parametrize("edges", [SLICES - 1, SLICES, SLICES + 1, SLICES * 40 + 1])
+def test_group_edge_counts_around_the_slice_count(big, edges):
+    """fewer group edges than slices (empty slices), as many, one more (a per-slice span of 2, the last slices empty), and one more
+    than a multiple of the span"""
+    topo, g, mk = big
+    src = 50 + np.arange(edges) // 3
+    dst = 50 + (np.arange(edges) // 3 + 1 + np.arange(edges) % 3) % (edges // 3 + 4)
+    _send(topo, g, src, dst)
+    _check(g, **P2)
+    assert len(g.window_groups()) == edges
+
+
+def test_one_callee_and_one_caller_hold_every_group_edge(big):
+    topo, g, mk = big
+    _send(topo, g, np.arange(100, 3100), np.full(3000, 7))           # one LDS address takes every add of the by-destination pass
+    rk = _check(g, **P2)
+    assert len(rk) == 3001 and rk["ref"][np.argmax(rk["rank"])] == 7
+    _send(topo, g, np.full(3000, 7), np.arange(100, 3100))           # ... and of the out-weight pass
+    rk = _check(g, iters=2)
+    assert len(rk) == 3001
+    _send(topo, g, np.concatenate([np.arange(100, 3100), [0, 1]]), np.concatenate([np.full(3000, 2), [1, 2]]))   # into workload 0, an edge inside workload 5 beside it
+    rk = _check(g, **P2)
+    assert rk["ref"][0] == G(0) and rk["ref"][1] == G(5) and np.argmax(rk["rank"]) == 0
+
+
+def test_label_obip_and_known_ids_on_either_side_of_max_groups(big):
+    topo, g, mk = big
+    rng = np.random.default_rng(3)
+    ids = np.array([MG - 1, MG, MG + 1, 5, 6, 0, 1, 2, 3, 4])
+    pod = _events(topo, np.concatenate([ids, rng.integers(0, 6000, 2000)]), topo.pod_ips[np.concatenate([np.roll(ids, 3), rng.integers(0, 6000, 2000)])],
+                  status=np.where(np.arange(2010) % 5 == 0, 503, 200))
+    ext = _events(topo, rng.integers(0, 6000, 300), EXT + rng.integers(0, 2, 300).astype(np.uint32), label=np.repeat([1, 2, 0], 100))
+    g.ingest_bulk(np.concatenate([pod, ext]))
+    g.flush_window()
+    rk = _check(g, **P2)
+    t = rk["ref"] >> 30
+    assert {0, 1, 2, 3} == set(t.tolist())                            # KNOWN, LABEL, OBIP and GROUP rows
+    for ref in (MG - 1, MG, MG + 1, G(5), G(0)):
+        assert (rk["ref"] == ref).any(), ref
+
+
+# ---- 3. close paths ----------------------------------------------------------------------------------------------------------------
+def test_every_close_path_gives_the_same_rows(churn):
+    topo, labels, wins = churn
+    g, gmap, mk = _grouped(topo, labels, "blocks")
+    g.set_group_nodes(); g.set_group_node_trend(shift=3, warmup=2, ttl=2); g.set_group_rank(iters=3)
+    for i, w in enumerate(wins[:7]):
+        _feed(g, w)
+        if i == 0:
+            g.flush_begin()
+            for call in (g.window_group_rank, g.set_group_rank):
+                assert _rc(call) == engine.SG_ESTATE                   # a flush is open
+            assert _rc(g.set_group_rank, None) == engine.SG_ESTATE and _rc(g.window_group_rank_top, 1) == engine.SG_ESTATE
+            g.flush_end()
+        elif i == 1:
+            g.flush_window_view()
+        elif i == 2:
+            g.flush_begin(); g.flush_end_view()
+        elif i == 3:
+            g.flush_window_top(3)
+        elif i == 4:
+            g.window_run(); g.window_read()
+        elif i == 5:
+            g.window_close(); g.window_features()
+            for l in range(2):
+                g.window_layer(l)
+            g.window_score(); g.window_read(); g.window_reset()
+        else:
+            g.flush_window()
+        rk = _check(g, iters=3)
+        assert len(rk) > 40 and len(g.window_group_node_trend()) == len(rk)   # (the staged score runs K16's baseline AND the ranking)
+
+
+def test_window_run_in_flight_under_a_changing_map(churn):
+    """sg_window_run with three windows in flight, the map changing between the closes: each window's rank rows, read from the
+    device buffers after the round was enqueued, against the reference over a one-call engine's group edges and workload rows"""
+    import torch
+    topo, labels, wins = churn
+    g, one = _engine(topo, labels, windows_in_flight=3), _engine(topo, labels)
+    for x in (g, one):
+        x.set_groups(); x.set_group_nodes()
+    p = dict(iters=4, seed="uniform")
+    g.set_group_rank(**p)
+    hip = _hip()
+    dev = [torch.from_numpy(np.ascontiguousarray(w).view(np.uint8).reshape(-1)).cuda() for w in wins[:9]]
+    torch.cuda.synchronize()
+    pending, sizes = [], []
+    for i, w in enumerate(wins[:9]):
+        lo = 30 * i
+        for x in (g, one):
+            x.group_assign(np.arange(lo, lo + 40), np.arange(lo, lo + 40) // (3 + i % 4))
+        _feed(one, w)
+        one.flush_window()
+        ge, gn = one.window_groups(), one.window_group_nodes()
+        g.ingest_device(dev[i].data_ptr(), len(w), 0)
+        g.window_run(0)
+        pending.append((ge, gn, g.window_group_nodes_buffer(), g.window_group_rank_buffer()))
+        if len(pending) == 3:
+            torch.cuda.synchronize()
+            for ge, gn, (np_, cp), rp in pending:
+                assert int(_d2h(hip, cp, 1, np.uint64)[0]) == len(gn)
+                assert _d2h(hip, np_, len(gn), engine.NODE_DTYPE).tobytes() == gn.tobytes()
+                _check(g, ge, gn, got=_d2h(hip, rp, len(gn), engine.RANK_DTYPE), **p)
+                sizes.append(len(gn))
+            pending = []
+    assert len(sizes) == 9 and len(set(sizes)) > 3
+
+
+# ---- 4. selection ------------------------------------------------------------------------------------------------------------------
+def _check_top(g, gn, rk, k, t, cap=None):
+    sel, rsel, idx, nn = g.window_group_rank_top(k, t, cap=cap)
+    want = ref_select_rank(rk, k, t)
+    if cap is not None:
+        want = want[:cap]
+    assert nn == len(gn)
+    assert idx.tolist() == want.tolist(), (k, t)
+    assert sel.tobytes() == gn[want].tobytes() and rsel.tobytes() == rk[want].tobytes()
+    return want
+
+
+def test_selection_host_and_device_forms_and_index_reads(churn):
+    import torch
+    topo, labels, wins = churn
+    g, gmap, mk = _grouped(topo, labels, "blocks")
+    g.set_group_nodes(); g.set_group_rank()
+    g.set_nodes(); g.set_rank()                                       # K11 beside it: its selection keeps its own scratch and staging
+    cap = 4096
+    d_out = torch.zeros(cap * engine.NODE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_idx = torch.zeros(cap, dtype=torch.int32, device="cuda")
+    d_n = torch.zeros(1, dtype=torch.int64, device="cuda")
+    checked = 0
+    for w in wins[:2]:
+        _feed(g, w)
+        g.flush_window()
+        gn = g.window_group_nodes()
+        rk = _check(g)
+        n = len(gn)
+        assert n > 40
+        for t in (-INF, 0.0, float(np.median(rk["share"])), float(rk["share"].max()), INF):
+            for k in (0, 1, 10, n + 5):
+                want = _check_top(g, gn, rk, k, t)
+                checked += len(want) > 0
+                g.window_group_rank_select(k, t, d_out.data_ptr(), d_idx.data_ptr(), cap, d_n.data_ptr(), 0)
+                torch.cuda.synchronize()
+                assert int(d_n.cpu()[0]) == len(want), (k, t)
+                assert d_idx.cpu().numpy()[:len(want)].astype(np.uint32).tolist() == want.tolist()
+                assert d_out.cpu().numpy()[: len(want) * engine.NODE_DTYPE.itemsize].tobytes() == gn[want].tobytes()
+        for k in (0, 30):
+            _check_top(g, gn, rk, k, 0.0, cap=7)                       # a cap below the selection
+        assert len(g.window_group_rank_top(5, float("nan"))[2]) == 0
+        g.window_group_rank_select(5, -INF, d_out.data_ptr(), 0, cap, d_n.data_ptr(), 0)      # rows only
+        torch.cuda.synchronize()
+        want = ref_select_rank(rk, 5)
+        assert d_out.cpu().numpy()[: 5 * engine.NODE_DTYPE.itemsize].tobytes() == gn[want].tobytes()
+        # K11's selection on the same engine and window is its own
+        prk, pn = g.window_rank(), g.window_nodes()
+        sel, rsel, idx, nn = g.window_rank_top(10)
+        pw = ref_select_rank(prk, 10)
+        assert nn == len(pn) and idx.tolist() == pw.tolist() and sel.tobytes() == pn[pw].tobytes() and rsel.tobytes() == prk[pw].tobytes()
+        # the index form
+        rep = np.array([5, 5, 0, n - 1, 5], np.uint32)
+        assert g.window_group_rank(rep).tobytes() == rk[rep].tobytes()
+        assert len(g.window_group_rank(np.zeros(0, np.uint32))) == 0
+        assert _rc(g.window_group_rank, np.array([0, n], np.uint32)) == engine.SG_EINVAL
+        out = np.full(5, 0xFF, np.uint8).repeat(16).view(engine.RANK_DTYPE)   # cap below the count: the first cap rows only
+        cnt = C.c_size_t(0)
+        assert g._l.sg_window_group_rank(g._h, rep.ctypes.data, 5, out.ctypes.data, 3, C.byref(cnt)) == 0
+        assert cnt.value == 5 and out[:3].tobytes() == rk[rep[:3]].tobytes() and out[3:].tobytes() == b"\xff" * 32
+    assert checked > 20
+    assert g._l.sg_window_group_rank_top(g._h, engine.SELECT_MAX_K + 1, 0.0, None, None, None, 0, None, None) == engine.SG_EINVAL
+    assert g._l.sg_window_group_rank_select(g._h, engine.SELECT_MAX_K + 1, 0.0, None, None, 0, d_n.data_ptr(), None) == engine.SG_EINVAL
+    assert g._l.sg_window_group_rank_select(g._h, 1, 0.0, None, None, 0, None, None) == engine.SG_EINVAL   # no count word
+
+
+# ---- 5. lifecycle --------------------------------------------------------------------------------------------------------------------
+def test_lifecycle_and_error_codes(churn):
+    topo, labels, wins = churn
+    g = _engine(topo, labels)
+    reads = (g.window_group_rank, g.window_group_rank_buffer)
+    assert _rc(g.set_group_rank) == engine.SG_ESTATE and _rc(g.set_group_rank, None) == engine.SG_ESTATE   # the groups are off
+    g.set_groups(); g.group_assign(np.arange(topo.n_pods), np.arange(topo.n_pods) // 7)
+    assert _rc(g.set_group_rank) == engine.SG_ESTATE                   # the workload rows are off
+    for call in reads:
+        assert _rc(call) == engine.SG_ESTATE
+    assert _rc(g.window_group_rank_top, 1) == engine.SG_ESTATE
+    g.set_group_nodes()
+    assert _rc(g.window_group_rank) == engine.SG_ESTATE                # the ranking is off
+    for bad in (dict(iters=65), dict(damping_q8=256), dict(seed=2), dict(struct_size=20), dict(reserved=1)):
+        assert _rc(g.set_group_rank, **bad) == engine.SG_EINVAL
+    _feed(g, wins[0]); g.flush_window()
+    g.set_group_rank()
+    for call in reads:
+        assert _rc(call) == engine.SG_ESTATE                           # the read window was closed while it was off
+    assert _rc(g.window_group_rank_top, 1) == engine.SG_ESTATE
+    d_n = C.c_uint64(0)
+    assert g._l.sg_window_group_rank_select(g._h, 1, 0.0, None, None, 0, C.addressof(d_n), None) == engine.SG_ESTATE
+    _feed(g, wins[1]); g.flush_window()
+    _check(g)
+    g.group_assign([0, 1], [5, NO])                                   # the map does not touch it
+    g.set_nodes(); g.set_rank(iters=2); g.set_nodes(False)            # nor do K9 and K11: independent stages
+    _feed(g, wins[2]); g.flush_window()
+    _check(g)
+    g.set_group_rank(iters=3)                                         # new parameters: the windows from here on
+    assert _rc(g.window_group_rank) == engine.SG_ESTATE
+    _feed(g, wins[3]); g.flush_window()
+    _check(g, iters=3)
+    g.set_group_rank(None)
+    for call in reads:
+        assert _rc(call) == engine.SG_ESTATE
+    g.set_group_rank()
+    g.set_group_nodes(False)                                          # the workload rows off take the ranking with them
+    assert _rc(g.window_group_rank) == engine.SG_ESTATE and _rc(g.set_group_rank) == engine.SG_ESTATE
+    g.set_group_nodes()
+    _feed(g, wins[4]); g.flush_window()
+    assert _rc(g.window_group_rank) == engine.SG_ESTATE and len(g.window_group_nodes()) > 0
+    g.set_group_rank(iters=2)                                         # re-enabled
+    _feed(g, wins[5]); g.flush_window()
+    _check(g, iters=2)
+    g.set_groups()                                                    # any sg_set_groups call frees it
+    for call in reads:
+        assert _rc(call) == engine.SG_ESTATE
+    assert _rc(g.set_group_rank) == engine.SG_ESTATE
+    _feed(g, wins[6]); g.flush_window()
+    assert len(g.window_groups()) > 0
+
+
+def test_sharded_engine_is_refused():
+    g = engine.ServiceGraph(max_known_nodes=1024, max_edges=4096, layers=1, max_labels=16, max_outbound_ips=64, rank=0, world=2)
+    assert _rc(g.set_groups) == engine.SG_EINVAL
+    assert _rc(g.set_group_rank) == engine.SG_ESTATE and _rc(g.window_group_rank) == engine.SG_ESTATE
+
+
+# ---- 6. what it is for ---------------------------------------------------------------------------------------------------------------
+def test_the_culprit_workload_keeps_its_name_through_a_rollout():
+    """frontend (3 pods) -> checkout (2) -> payments (4) -> db (1), every request of every hop failing, under a blob whose score is
+    sigmoid(c * err_ratio - c / 2) and nothing else: the four workload scores tie, the ranking names db.  After a rollout — the same
+    services on new pods, the same groups — the culprit's ref and rank position are the same; K11 on the same engine names a pod,
+    and another one after the rollout"""
+    L, c = 2, 8.0
+    o = offsets(L)
+    blob = np.zeros(weights.weights_count(L), dtype=np.float32)
+    blob[o["We"] + 4 * weights.F_HID] = c                              # edge feature 4 (err_ratio) into hidden unit 0
+    blob[o["w2"]] = 1.0
+    blob[o["b2"]] = -c / 2
+    topo = replay.make_topology(48, 60, seed=7)
+    g = engine.ServiceGraph(max_known_nodes=topo.n_nodes + 8, max_edges=4096, layers=L, max_labels=16, max_outbound_ips=64)
+    g.set_clock(*CLOCK); g.load_weights(blob)
+    HostShim().apply(g, topo.k8s_ops()); g.set_label_count(0)
+    sizes = (3, 2, 4, 1)
+
+    def tiers(first):
+        out, nxt = [], first
+        for s in sizes:
+            out.append(list(range(nxt, nxt + s))); nxt += s
+        return out
+    g.set_groups(); g.set_group_nodes(); g.set_group_rank()
+    g.set_nodes(); g.set_rank()
+    named, pods = [], []
+    for first in (0, 20):                                             # the rollout: pods 20 .. 29 take over from pods 0 .. 9
+        ids = tiers(first)
+        for grp, tier in enumerate(ids):
+            g.group_assign(tier, [grp] * len(tier))
+        src = [a for up, down in zip(ids, ids[1:]) for a in up for _ in down]
+        dst = [b for up, down in zip(ids, ids[1:]) for _ in up for b in down]
+        rows = _send(topo, g, np.repeat(src, 10), np.repeat(dst, 10), status=503)
+        assert len(rows) == 18 and (rows["err_ratio"] == 1.0).all()
+        gn = g.window_group_nodes()
+        rk = _check(g)
+        assert gn["ref"].tolist() == [G(0), G(1), G(2), G(3)]
+        assert len(set(gn["score"].view(np.uint32).tolist())) == 1 and gn["score"][0] > 0.9   # the scores tie
+        sel, rsel, idx, nn = g.window_group_rank_top(4)
+        assert nn == 4 and idx[0] == 3 and sel["ref"][0] == G(3) == rsel["ref"][0]
+        named.append((int(rsel["ref"][0]), idx.tolist()))
+        psel, prsel, pidx, _ = g.window_rank_top(1)
+        pods.append(int(psel["ref"][0]))
+    assert named[0] == named[1]                                        # the same workload at the same rank positions
+    assert pods == [9, 29]                                             # K11: db's pod, a different one after the rollout
