@@ -34,6 +34,9 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->window_group_nodes_top = reinterpret_cast<decltype(o->window_group_nodes_top)>(dlsym(dl, "sg_window_group_nodes_top"));
     o->set_group_rank = reinterpret_cast<decltype(o->set_group_rank)>(dlsym(dl, "sg_set_group_rank"));             // optional (K17)
     o->window_group_rank_top = reinterpret_cast<decltype(o->window_group_rank_top)>(dlsym(dl, "sg_window_group_rank_top"));
+    o->set_group_incidents = reinterpret_cast<decltype(o->set_group_incidents)>(dlsym(dl, "sg_set_group_incidents"));   // optional (K18)
+    o->window_group_incidents = reinterpret_cast<decltype(o->window_group_incidents)>(dlsym(dl, "sg_window_group_incidents"));
+    o->window_group_node_incident = reinterpret_cast<decltype(o->window_group_node_incident)>(dlsym(dl, "sg_window_group_node_incident"));
 #undef SG_SYM
     return true;
 }
@@ -315,6 +318,29 @@ long GraphDS::WorkloadCulprits(uint32_t k, float min_share, std::vector<Workload
     for (size_t i = 0; i < m; i++) { (*out)[i].Node = std::move(named[i]); (*out)[i].Rank = ranks[i]; }
     if (index) *index = std::move(idx);
     return (long)m;
+}
+
+// ---- the workload incidents (K18) ----
+int GraphDS::SetWorkloadIncidents(const sg_incident_params* p) {
+    if (!api_.set_group_incidents) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_group_incidents(h_, p);
+}
+long GraphDS::WorkloadIncidents(std::vector<sg_incident_out>* out, std::vector<uint32_t>* node_incident) {
+    if (!out || !api_.window_group_incidents || (node_incident && !api_.window_group_node_incident)) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t n = 0;
+    int rc = api_.window_group_incidents(h_, nullptr, 0, &n);
+    if (rc != SG_OK) return rc;
+    out->assign(n, sg_incident_out{});
+    if (n && (rc = api_.window_group_incidents(h_, out->data(), n, &n)) != SG_OK) return rc;
+    if (node_incident) {
+        size_t m = 0;
+        if ((rc = api_.window_group_node_incident(h_, nullptr, 0, nullptr, 0, &m)) != SG_OK) return rc;
+        node_incident->assign(m, SG_NO_INCIDENT);
+        if (m && (rc = api_.window_group_node_incident(h_, nullptr, 0, node_incident->data(), m, &m)) != SG_OK) return rc;
+    }
+    return (long)out->size();
 }
 
 // processPod keeps PodIPToPodUid (aggregator/persist.go:55-71); pods without an IP never reach the

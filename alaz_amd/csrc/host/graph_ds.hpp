@@ -64,6 +64,10 @@ struct SgApi {
     // optional (K17; absent in an older library): SetWorkloadRank and WorkloadCulprits each need the entry they forward to
     int (*set_group_rank)(sg_handle, const sg_rank_params*) = nullptr;
     int (*window_group_rank_top)(sg_handle, uint32_t, float, sg_node_out*, sg_node_rank*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
+    // optional (K18; absent in an older library): SetWorkloadIncidents and WorkloadIncidents each need the entry they forward to
+    int (*set_group_incidents)(sg_handle, const sg_incident_params*) = nullptr;
+    int (*window_group_incidents)(sg_handle, sg_incident_out*, size_t, size_t*) = nullptr;
+    int (*window_group_node_incident)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -193,6 +197,13 @@ public:
     // `index` (may be NULL).  It returns the count, < 0 on an engine error.
     int SetWorkloadRank(const sg_rank_params* p);
     long WorkloadCulprits(uint32_t k, float min_share, std::vector<WorkloadCulprit>* out, std::vector<uint32_t>* index);
+    // The workload incidents (K18), behind SetWorkloadNodes: the last flushed window's red group edges grouped into connected
+    // components of workload rows.  SetWorkloadIncidents forwards sg_set_group_incidents (p NULL: off; the engine's return code;
+    // SG_EINVAL without the entry).  WorkloadIncidents: the incident rows (first_node, top_node and culprit_node index
+    // WorkloadNodes, worst_row indexes WorkloadEdges) and, in `node_incident` (may be NULL), the incident of every row of
+    // WorkloadNodes (SG_NO_INCIDENT: none).  It returns the incident count, < 0 on an engine error.
+    int SetWorkloadIncidents(const sg_incident_params* p);
+    long WorkloadIncidents(std::vector<sg_incident_out>* out, std::vector<uint32_t>* node_incident);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }

@@ -30,6 +30,7 @@ struct MockEngine {
     std::vector<std::array<uint64_t, 4>> k15_ops;      // {1, shift, warmup, ttl} per sg_set_group_trend, {2, silent_windows, min_seen, max_rows} per sg_set_group_vanished (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_groups_top
     std::vector<std::array<uint64_t, 4>> k16_ops;      // {1, on, 0, 0} per sg_set_group_nodes, {2, shift, warmup, ttl} per sg_set_group_node_trend (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_group_nodes_top
     std::vector<std::array<uint64_t, 4>> k17_ops;      // {1, iters, damping_q8, seed} per sg_set_group_rank (NULL: ~0 in the three), {2, k, the bits of min_share, cap} per sg_window_group_rank_top
+    std::vector<std::array<uint64_t, 4>> k18_ops;      // {1, by, the bits of min_value, reserved} per sg_set_group_incidents (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incidents, {3, n_index, cap, 0} per sg_window_group_node_incident
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
 };
 #define M_LOCK(h) std::lock_guard<std::mutex> _g(reinterpret_cast<MockEngine*>(h)->mu)
@@ -147,6 +148,34 @@ int m_window_group_rank_top(sg_handle h, uint32_t k, float min_share, sg_node_ou
     for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (rank_out) rank_out[i] = r[i]; if (idx) idx[i] = at[i]; }
     return SG_OK;
 }
+// K18's stand-ins: the switch recorded; two incidents over three workload rows (rows 0 and 2 in incident 0 with culprit 2, row 1
+// alone in incident 1 without a culprit)
+int m_set_group_incidents(sg_handle h, const sg_incident_params* p) {
+    M_LOCK(h);
+    uint32_t bits = 0; if (p) std::memcpy(&bits, &p->min_value, 4);
+    reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({1u, p ? p->by : ~0ull, p ? bits : ~0ull, p ? p->reserved : ~0ull}); return SG_OK;
+}
+int m_window_group_incidents(sg_handle h, sg_incident_out* out, size_t cap, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({2u, (uint64_t)cap, 0u, 0u});
+    if (n) *n = 2;
+    sg_incident_out e[2] = {};
+    e[0].count = 9; e[0].err = 2; e[0].sum_ns = 900; e[0].score_q32 = 3ull << 31; e[0].rank_sum = 3ull << 54; e[0].first_node = 0; e[0].nodes = 2;
+    e[0].edges = 2; e[0].worst_row = 1; e[0].top_node = 2; e[0].culprit_node = 2; e[0].value_max = 0.75f;
+    e[1].count = 4; e[1].first_node = 1; e[1].nodes = 1; e[1].edges = 1; e[1].worst_row = 2; e[1].top_node = 1; e[1].culprit_node = SG_NO_INCIDENT;
+    e[1].value_max = 0.5f;
+    for (size_t i = 0; out && i < std::min<size_t>(2, cap); i++) out[i] = e[i];
+    return SG_OK;
+}
+int m_window_group_node_incident(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({3u, (uint64_t)n_idx, (uint64_t)cap, 0u});
+    const uint32_t inc[3] = {0u, 1u, 0u};
+    const size_t m = idx ? n_idx : 3;
+    if (n) *n = m;
+    for (size_t i = 0; out && i < std::min(m, cap); i++) { const uint32_t v = idx ? idx[i] : (uint32_t)i; if (v >= 3) return SG_EINVAL; out[i] = inc[v]; }
+    return SG_OK;
+}
 int m_obips(sg_handle, uint32_t*, size_t, size_t* n) { if (n) *n = 0; return SG_OK; }
 const char* m_err(sg_handle) { return ""; }
 
@@ -236,6 +265,8 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.set_group_nodes = m_set_group_nodes; c->api.window_group_nodes = m_window_group_nodes; c->api.set_group_node_trend = m_set_group_node_trend;
         c->api.window_group_node_trend = m_window_group_node_trend; c->api.window_group_nodes_top = m_window_group_nodes_top;
         c->api.set_group_rank = m_set_group_rank; c->api.window_group_rank_top = m_window_group_rank_top;
+        c->api.set_group_incidents = m_set_group_incidents; c->api.window_group_incidents = m_window_group_incidents;
+        c->api.window_group_node_incident = m_window_group_node_incident;
     }
     if (c->api.create(cfg, &c->h) != SG_OK) return nullptr;        // no usable GPU => no GraphDS: there is no CPU fallback
     c->ds = std::make_unique<GraphDS>(&c->inner, c->api, c->h, &c->sink, cfg ? (size_t)cfg->max_edges : 1024, batch ? batch : 4096,
@@ -370,6 +401,21 @@ long sgh_graphds_workload_culprits(void* g, uint32_t k, float min_share, sgh_wor
         if (out) { put_workload_node(v[i].Node, &out[i].node); out[i].rank = v[i].Rank; }
         if (index) index[i] = idx[i];
     }
+    return n;
+}
+// the workload incidents (K18): the switch (on = 0: off) and the last flushed window's incident rows (sg_incident_out as the engine
+// gives them) with the incident of every workload row
+int sgh_graphds_set_workload_incidents(void* g, int on, uint32_t by, float min_value) {
+    sg_incident_params p{}; p.struct_size = sizeof p; p.by = by; p.min_value = min_value;
+    return static_cast<HostCtx*>(g)->ds->SetWorkloadIncidents(on ? &p : nullptr);
+}
+long sgh_graphds_workload_incidents(void* g, sg_incident_out* out, size_t cap, uint32_t* node_incident, size_t node_cap, size_t* n_nodes) {
+    std::vector<sg_incident_out> v; std::vector<uint32_t> ni;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadIncidents(&v, &ni);
+    if (n < 0) return n;
+    if (out && !v.empty()) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_incident_out));
+    if (node_incident && !ni.empty()) std::memcpy(node_incident, ni.data(), std::min(node_cap, ni.size()) * sizeof(uint32_t));
+    if (n_nodes) *n_nodes = ni.size();
     return n;
 }
 int sgh_graphds_ingest_wire(void* g, const uint8_t* recs, size_t n, const uint32_t* kafka_msgs) {
@@ -666,6 +712,14 @@ size_t sgh_mock_k17_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k17_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k17_ops[i].data(), 32);
     return m->k17_ops.size();
+}
+size_t sgh_mock_k18_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k18_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k18_ops[i].data(), 32);
+    return m->k18_ops.size();
 }
 size_t sgh_mock_group_ops(void* g, uint32_t* out2, size_t cap) {
     auto* c = static_cast<HostCtx*>(g); if (!c->mock) return 0;

@@ -34,6 +34,7 @@
 #include "sg_group_trend.h"
 #include "sg_group_nodes.h"
 #include "sg_group_rank.h"
+#include "sg_group_incident.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -238,6 +239,16 @@ struct sg_engine {
                        u32* dst = nullptr; u64* w = nullptr; u64* W = nullptr; u64* R = nullptr; u64* base = nullptr; u64* t = nullptr; u64* part = nullptr;
                        u64* seed_sum = nullptr; sg_node_rank* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_node_rank*> rows;
                        std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } grank;
+    // K18, the workload incidents (sg_group_incident.h): allocated at sg_set_group_incidents (sg_plan.hpp plan_group_incidents), one
+    // allocation, freed with the workload rows (and with the group trend when its key is a trend key).  The position table, the
+    // per-row arrays, esrc, the per-incident keys and the head counts are scratch shared by the window slots: every grouping waits
+    // for the previous one (ev), whichever slot's stream it runs on.  Per slot: the incident rows, their count, the incident per
+    // workload row, and whether the window in the slot was grouped.
+    struct GroupIncidents { bool on = false; sg_incident_params p{}; sgplan::GroupIncidentPlan plan; char* mem = nullptr; u32* pos = nullptr;
+                            u32* parent = nullptr; u32* flag = nullptr; u32* lab = nullptr; u32* num = nullptr; u32* esrc = nullptr;
+                            K12Keys* keys = nullptr; u32* blk = nullptr; u32* stage = nullptr; u32* stage_idx = nullptr;
+                            std::vector<sg_incident_out*> rows; std::vector<u64*> count; std::vector<u32*> node_inc; std::vector<char> valid;
+                            hipEvent_t ev = nullptr; bool pending = false; } ginc;
 };
 
 namespace {
@@ -741,6 +752,7 @@ constexpr StageWords kGroupTrendWords{"the group trend is off (sg_set_group_tren
 constexpr StageWords kGroupNodesWords{"the workload rows are off (sg_set_group_nodes)", "the workload rows were off"};
 constexpr StageWords kGroupNodeTrendWords{"the workload trend is off (sg_set_group_node_trend)", "the workload trend was off"};
 constexpr StageWords kGroupRankWords{"the workload ranking is off (sg_set_group_rank)", "the workload ranking was off"};
+constexpr StageWords kGroupIncidentsWords{"the workload incidents are off (sg_set_group_incidents)", "the workload incidents were off"};
 constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
 // A node space: what the baseline, the selection and the readbacks over node rows work on — K9's nodes or K16's workloads.  Its
 // rollup, its baseline, its selection scratch, the rows a window can have, and how its messages name it: the rollup, the baseline,
@@ -1097,6 +1109,43 @@ int launch_group_rank(sg_engine* e, hipStream_t s) {
     return SG_OK;
 }
 void free_group_rank(sg_engine* e) { free_stage(e->grank); }
+// ---- K18, the workload incidents (engine lock held) --------------------------------------------------------------------------------
+static_assert(sgplan::kGrpIncThreads == K18_THREADS && sgplan::kGrpIncMaxWgs == K18_MAX_WGS && sgplan::kGrpIncSlots == K12_SLOTS &&
+              sgplan::kIncKeysBytes == sizeof(K12Keys), "plan_group_incidents sizes the launches of sg_group_incident.h");
+// enqueue the grouping of the group edges of the window in slot cur on stream s (behind its contraction, its group trend rows, its
+// workload rows and its workload ranking, on the same stream) and behind the previous grouping (any stream): eight plain launches,
+// the incidents go to the slot's buffers
+int launch_group_incidents(sg_engine* e, hipStream_t s) {
+    sg_engine::GroupIncidents& x = e->ginc;
+    const sgplan::GroupIncidentPlan& P = x.plan;
+    const sgplan::GroupNodesPlan& N = e->gnodes.plan;
+    GroupIncArgs a{};
+    a.g.nd = nodes_view(e, work(e), N.ncap);
+    a.g.nd.max_edges = std::max<u64>(e->cfg.max_edges, 1);
+    a.g.nd.blk = x.blk; a.g.nd.count = x.count[e->cur];              // (k9_scan: the head counts in, their scan and the incident count out)
+    a.g.groups = e->grp.rows[e->cur]; a.g.gcount = e->grp.count[e->cur];
+    a.g.max_groups = N.max_groups; a.g.gk = (u32)N.gk; a.g.hi_group = e->grp.hi_group; a.g.nc = N.nc;
+    a.nodes = e->gnodes.rows[e->cur]; a.ncount = e->gnodes.count[e->cur];
+    a.trend = x.p.by != SG_SEL_SCORE ? e->gtrend.rows[e->cur] : nullptr;
+    a.rank = e->grank.on ? e->grank.rows[e->cur] : nullptr;
+    a.by = x.p.by; a.min_value = x.p.min_value; a.node_per = P.node_per;
+    a.pos = x.pos; a.parent = x.parent; a.flag = x.flag; a.lab = x.lab; a.num = x.num; a.esrc = x.esrc; a.keys = x.keys;
+    a.out = x.rows[e->cur]; a.node_inc = x.node_inc[e->cur];
+    if (const int rc = stage_wait(e, x, s)) return rc;
+    const dim3 nt(K18_THREADS), gg(P.grid_wgs), ng(P.node_wgs);
+    hipLaunchKernelGGL(k18_init, gg, nt, 0, s, a);
+    hipLaunchKernelGGL(k18_hook, dim3(P.hook_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k18_label, ng, nt, 0, s, a);
+    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a.g.nd, P.node_wgs);
+    hipLaunchKernelGGL(k18_number, ng, nt, 0, s, a);
+    hipLaunchKernelGGL(k18_nodes, dim3(P.fold_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k18_rows, dim3(P.row_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k18_finish, gg, nt, 0, s, a);
+    if (const int rc = stage_done(e, x, s)) return rc;
+    x.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_group_incidents(sg_engine* e) { free_stage(e->ginc); }
 // a selection scratch block off (the workload rows': its sizes are the stage's)
 void free_nsel(sg_engine::NSel& s) {
     if (s.mem || s.h_n) hipDeviceSynchronize();
@@ -1106,6 +1155,7 @@ void free_nsel(sg_engine::NSel& s) {
     s = sg_engine::NSel{};
 }
 void free_group_nodes(sg_engine* e) {
+    free_group_incidents(e);
     free_group_rank(e);
     free_nsel(e->gnsel);
     free_baseline(e->gntrend);
@@ -1174,6 +1224,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
             if (const int rc = launch_group_nodes(e, s)) return rc;
             if (e->gntrend.on) { if (const int rc = launch_node_trend(e, workload_space(e), s, k16_tcount, k16_twrite)) return rc; }
             if (e->grank.on) { if (const int rc = launch_group_rank(e, s)) return rc; }   // K17 behind K16 and its baseline: the group edges, the workload rows and their count
+            if (e->ginc.on) { if (const int rc = launch_group_incidents(e, s)) return rc; }   // K18 behind K15, K16 and K17: the group trend rows, the workload rows, the rank rows
         }
     }
     return SG_OK;
@@ -2908,10 +2959,11 @@ int sg_set_group_trend(sg_handle e, const sg_trend_params* p) {
     sg_trend_params r{};
     if (p && sgplan::check_group_trend(*p, e->cfg.max_edges, &r)) { e->err = "sg_set_group_trend: bad parameters"; return SG_EINVAL; }
     free_group_trend(e);
-    if (!p) return SG_OK;
+    auto drop_incidents = [e] { if (e->ginc.on && e->ginc.p.by != SG_SEL_SCORE) free_group_incidents(e); };   // (their key is a group trend row's)
+    if (!p) { drop_incidents(); return SG_OK; }
     sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
     const u32 slots = (u32)e->slots.size();
-    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_trend(e->cfg.max_edges, slots, r), "sg_set_group_trend", [e] { free_group_trend(e); })) return rc;
+    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_trend(e->cfg.max_edges, slots, r), "sg_set_group_trend", [e, drop_incidents] { free_group_trend(e); drop_incidents(); })) return rc;
     t.valid.assign(slots, 0);
     return SG_OK;
 }
@@ -3144,6 +3196,67 @@ int sg_window_group_rank_select(sg_handle e, uint32_t k, float min_share, sg_nod
     const NodeSpace ns = workload_space(e);
     if (const int rc = nsel_reserve(e, ns)) return rc;
     return launch_rank_select(e, ns, e->grank, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
+}
+
+// ---- K18, the workload incidents ---------------------------------------------------------------------------------------------------
+int sg_set_group_incidents(sg_handle e, const sg_incident_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (!e->gnodes.on) { e->err = "sg_set_group_incidents: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_group_incidents while a flush is open"; return SG_ESTATE; }
+    sg_incident_params q{};
+    if (p && sgplan::check_incidents(*p, &q)) { e->err = "sg_set_group_incidents: bad parameters"; return SG_EINVAL; }
+    if (p && q.by != SG_SEL_SCORE && !e->gtrend.on) { e->err = "sg_set_group_incidents by a trend key: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
+    free_group_incidents(e);
+    if (!p) return SG_OK;
+    sg_engine::GroupIncidents& x = e->ginc;
+    const u32 slots = (u32)e->slots.size();
+    x.p = q;
+    x.plan = sgplan::plan_group_incidents(e->cfg.max_edges, e->gnodes.plan.nc, e->gnodes.plan.gk, slots);
+    const sgplan::GroupIncidentPlan& P = x.plan;
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_group_incidents", [e] { free_group_incidents(e); })) return rc;
+    x.keys = at<K12Keys>(x.mem, P.keys_off);
+    x.pos = at<u32>(x.mem, P.pos_off);
+    x.parent = at<u32>(x.mem, P.node_off[0]); x.flag = at<u32>(x.mem, P.node_off[1]); x.lab = at<u32>(x.mem, P.node_off[2]);
+    x.num = at<u32>(x.mem, P.node_off[3]);
+    x.esrc = at<u32>(x.mem, P.esrc_off);
+    x.blk = at<u32>(x.mem, P.blk_off);
+    x.stage = at<u32>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = x.mem + P.slot.off + k * P.slot.bytes;
+        x.rows.push_back(at<sg_incident_out>(s, P.slot_rows)); x.count.push_back(at<u64>(s, P.slot_count));
+        x.node_inc.push_back(at<u32>(s, P.slot_node_inc));
+    }
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+int sg_window_group_incidents(sg_handle e, sg_incident_out* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::GroupIncidents& x = e->ginc;
+    if (const int rc = stage_ready(e, x, "sg_window_group_incidents", kGroupIncidentsWords)) return rc;
+    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_incident_out), out, cap, n);
+}
+int sg_window_group_node_incident(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::GroupIncidents& x = e->ginc;
+    if (const int rc = stage_ready(e, x, "sg_window_group_node_incident", kGroupIncidentsWords)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->gnodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    return copy_indexed(e, (const u32*)x.node_inc[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, x.stage, x.stage_idx,
+                        std::max<size_t>(x.plan.nc, 1), "sg_window_group_node_incident: a node index beyond the window's workload rows");
+}
+int sg_window_group_incidents_buffer(sg_handle e, void** d_incidents, void** d_count, void** d_node_incident) {
+    if (!e || !d_incidents || !d_count || !d_node_incident) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::GroupIncidents& x = e->ginc;
+    int slot;
+    if (const int rc = stage_slot(e, x, "sg_window_group_incidents_buffer", kGroupIncidentsWords, &slot)) return rc;
+    *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
+    return SG_OK;
 }
 
 // ---- K13, the tracks ---------------------------------------------------------------------------------------------------------------

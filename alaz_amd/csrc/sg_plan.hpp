@@ -1179,6 +1179,84 @@ inline GroupRankPlan plan_group_rank(u64 max_edges, u32 nc, u64 gk, u32 slots) {
     return r;
 }
 
+// K18, the workload incidents (sg_group_incident.h): the device memory sg_set_group_incidents allocates — never sg_create,
+// sg_set_groups or sg_set_group_nodes; the parameters are K12's (check_incidents).  Work is in ROW-INDEX space: the row position by
+// group key (pos [GK], the stage's own: K17 is optional), four u32 arrays by row position (parent, flag, lab, num), the source
+// position of every red group edge (esrc [max_edges]), the max fields' keys by incident and the head counts k9_scan scans are
+// scratch shared by the window slots.  k18_label / k18_number take one 256-thread workgroup per block of node_per rows, at most 1024
+// blocks (K9's rule); k18_init and k18_finish run a grid-stride grid over NC; k18_hook one over max_edges, at most 1024 workgroups;
+// k18_rows at most 256 (K12's reason: every workgroup adds its LDS table to the incidents once); k18_nodes takes kGrpIncFoldRounds
+// rounds of 256 rows per workgroup (K13's precedent: fewer workgroups, fewer device atomics on one incident's words, and a
+// workgroup can meet more distinct incidents than its table has slots, which then go to device memory directly).  Each slot keeps
+// its incident rows, their count and the incident per workload row; one staging block serves sg_window_group_node_incident's index
+// form.  Config 3's engine (max_edges 1.25 M, GK = NC = 30 000, two slots): 10.6 MiB in all — 4.8 MiB of esrc, 2 x 2.2 MiB of
+// incident rows and node_inc, 0.7 MiB of keys, 0.8 MiB for pos, the four row arrays and the staging.  At K16's limit (2^21 keys,
+// max_edges 4 M, two slots) it is 430 MiB, 288 of them the two slots' [NC] incident rows.
+constexpr u32 kGrpIncThreads = 256, kGrpIncMaxWgs = 1024, kGrpIncMaxRowWgs = 256, kGrpIncRowsPerThread = 4, kGrpIncFoldRounds = 8,
+              kGrpIncSlots = 512;
+struct GroupIncidentPlan {
+    u32 nc = 0;                   // workload rows per window slot (GroupNodesPlan::nc)
+    u64 gk = 0;                   // group keys (GroupNodesPlan::gk)
+    u32 node_wgs = 0, node_per = 0;   // k18_label / k18_number: workgroups, rows per workgroup (a multiple of 256)
+    u32 grid_wgs = 0;             // k18_init, k18_finish: grid-stride over nc
+    u32 fold_wgs = 0;             // k18_nodes: grid-stride over nc, kGrpIncFoldRounds rounds a workgroup
+    u32 hook_wgs = 0;             // k18_hook: grid-stride over max_edges
+    u32 row_wgs = 0;              // k18_rows: grid-stride over max_edges (and nc)
+    u64 pos_bytes = 0;            // [gk] u32 row position by group key
+    u64 node_bytes = 0;           // one per-row u32 array [nc] (parent, flag, lab, num: four of them)
+    u64 esrc_bytes = 0;           // [max_edges] u32
+    u64 keys_bytes = 0;           // [nc] x 24 bytes: the max fields' keys per incident
+    u64 blk_bytes = 0;            // [2][1024] u32
+    u64 stage_bytes = 0;          // [nc] u32 staging, and [nc] u32 for the index (two of them)
+    u64 rows_bytes = 0;           // one window slot's incidents: [nc] sg_incident_out
+    u64 count_bytes = 0;          // one window slot's incident count (u64)
+    u64 node_inc_bytes = 0;       // one window slot's incident per workload row: [nc] u32
+    u64 total_bytes = 0;          // the scratch, the staging and every slot's buffers, each 256-byte aligned
+    u64 keys_off = 0, pos_off = 0, node_off[4] = {}, esrc_off = 0, blk_off = 0, stage_off = 0, stage_idx_off = 0;   // (node_off: parent, flag, lab, num)
+    Slots slot; u64 slot_rows = 0, slot_count = 0, slot_node_inc = 0;
+    std::vector<Piece> layout;
+};
+// the distinct incidents one workgroup of k18_nodes / k18_rows can meet in a window of n workload rows that are all their own
+// incident's pair (rows 2i, 2i + 1) / of g group edges each an incident of its own: what the workgroup strides over
+inline u64 group_incident_fold_rows(const GroupIncidentPlan& r, u64 n) { return (n + r.fold_wgs - 1) / r.fold_wgs; }
+inline u64 group_incident_row_edges(const GroupIncidentPlan& r, u64 g) { return (g + r.row_wgs - 1) / r.row_wgs; }
+inline GroupIncidentPlan plan_group_incidents(u64 max_edges, u32 nc, u64 gk, u32 slots) {
+    GroupIncidentPlan r;
+    const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(nc, 1), GK = std::max<u64>(gk, 1);
+    r.nc = nc; r.gk = gk;
+    r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxWgs, (NC + kGrpIncThreads - 1) / kGrpIncThreads));
+    const u64 per = (NC + r.node_wgs - 1) / r.node_wgs;
+    r.node_per = (u32)((per + kGrpIncThreads - 1) / kGrpIncThreads * kGrpIncThreads);
+    r.node_wgs = (u32)((NC + r.node_per - 1) / r.node_per);
+    r.grid_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxWgs, (NC + kGrpIncThreads - 1) / kGrpIncThreads));
+    const u64 fold_rows = (u64)kGrpIncFoldRounds * kGrpIncThreads;
+    r.fold_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxWgs, (NC + fold_rows - 1) / fold_rows));
+    const u64 row_blocks = (ME + (u64)kGrpIncRowsPerThread * kGrpIncThreads - 1) / ((u64)kGrpIncRowsPerThread * kGrpIncThreads);
+    r.hook_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxWgs, row_blocks));
+    r.row_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxRowWgs, row_blocks));
+    r.pos_bytes = trend_align(GK * 4);
+    r.node_bytes = trend_align(NC * 4);
+    r.esrc_bytes = trend_align(ME * 4);
+    r.keys_bytes = trend_align(NC * kIncKeysBytes);
+    r.blk_bytes = trend_align(2ull * kGrpIncMaxWgs * 4);
+    r.stage_bytes = trend_align(NC * 4);
+    r.rows_bytes = trend_align(NC * sizeof(sg_incident_out));
+    r.count_bytes = trend_align(8);
+    r.node_inc_bytes = trend_align(NC * 4);
+    Block b;
+    const char* const node[4] = {"parent", "flag", "lab", "num"};
+    r.keys_off = b.take("keys", r.keys_bytes);
+    r.pos_off = b.take("pos", r.pos_bytes);
+    for (int k = 0; k < 4; k++) r.node_off[k] = b.take(node[k], r.node_bytes);
+    r.esrc_off = b.take("esrc", r.esrc_bytes);
+    r.blk_off = b.take("blk", r.blk_bytes);
+    r.stage_off = b.take("stage", r.stage_bytes); r.stage_idx_off = b.take("stage_idx", r.stage_bytes);
+    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}, {"count", r.count_bytes, &r.slot_count},
+                             {"node_inc", r.node_inc_bytes, &r.slot_node_inc}});
+    r.total_bytes = b.end; r.layout = std::move(b.pieces);
+    return r;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

@@ -265,6 +265,9 @@ def _signatures() -> dict:
         "sg_window_group_rank_buffer": (I, [H, PP]),
         "sg_window_group_rank_top": (I, [H, u32, f32, P, P, P, sz, Psz, Psz]),
         "sg_window_group_rank_select": (I, [H, u32, f32, P, P, sz, P, P]),
+        "sg_set_group_incidents": (I, [H, P]), "sg_window_group_incidents": (I, [H, P, sz, Psz]),
+        "sg_window_group_node_incident": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_incidents_buffer": (I, [H, PP, PP, PP]),
     }
 
 
@@ -308,6 +311,9 @@ _STAGES = dict(
                             "set_group_node_trend(None) switches the workload trend off", "workload trend"),
     group_rank=_Stage("sg_set_group_rank", SgRankParams, RANK_DEFAULTS, "set_group_rank(None) switches the workload ranking off",
                       "workload rank", dict(seed=_rank_seed)),
+    group_incidents=_Stage("sg_set_group_incidents", SgIncidentParams, INCIDENT_DEFAULTS,
+                           "set_group_incidents(None) switches the workload incidents off", "workload incident",
+                           dict(by=lambda by: ServiceGraph._by(by) if isinstance(by, str) else by)),
 )
 
 _lib = None
@@ -965,6 +971,28 @@ class ServiceGraph:
         (sg_window_group_rank_select): d_out [cap] workload rows (0 = none), d_index [cap] u32 (0 = none), d_n one u64 = rows
         selected; enqueued on `stream` (0 = that window's stream)."""
         self._ck(self._l.sg_window_group_rank_select(self._h, k, min_share, d_out or None, d_index or None, cap, d_n, stream or None))
+
+    # ---- workload incidents (K18): the window's red group edges grouped into connected components of workload rows ----
+    def set_group_incidents(self, params: Optional[dict] = (), **kw):
+        """Switch the per-window workload incident grouping on (sg_set_group_incidents; set_incidents' parameters: by = "score" /
+        "lat_dev" / "err_dev" or SG_SEL_*, min_value; needs the workload rows on, and the group trend for a trend key; independent
+        of set_incidents) or off: set_group_incidents(None)."""
+        self._set_stage("group_incidents", params, kw)
+
+    def window_group_incidents(self) -> np.ndarray:
+        """INCIDENT_DTYPE rows of the last read window (sg_window_group_incidents), numbered by their smallest workload row; the node
+        fields index window_group_nodes(), worst_row indexes window_groups()"""
+        return self._counted(self._l.sg_window_group_incidents, INCIDENT_DTYPE)
+
+    def window_group_node_incident(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """the incident number (NO_INCIDENT: none) of every workload row of the last read window (sg_window_group_node_incident), or
+        of the rows at `index` (only those cross PCIe)"""
+        return self._window_rows(self._l.sg_window_group_node_incident, np.dtype("<u4"), index)
+
+    def window_group_incidents_buffer(self) -> Tuple[int, int, int]:
+        """(device pointer of the sg_incident_out rows, of their u64 count, of the u32 incident per workload row) of the window
+        window_run closed last (sg_window_group_incidents_buffer)"""
+        return self._pointers(self._l.sg_window_group_incidents_buffer, 3)
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

@@ -135,6 +135,8 @@ def load() -> C.CDLL:
             "sgh_graphds_workload_nodes_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]), "sgh_mock_k16_ops": (sz, [P, P, sz]),
             "sgh_graphds_set_workload_rank": (C.c_int, [P, C.c_int, u32, u32, u32, C.c_float]),
             "sgh_graphds_workload_culprits": (C.c_long, [P, u32, C.c_float, P, P, sz]), "sgh_mock_k17_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_workload_incidents": (C.c_int, [P, C.c_int, u32, C.c_float]),
+            "sgh_graphds_workload_incidents": (C.c_long, [P, P, sz, P, sz, P]), "sgh_mock_k18_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -563,6 +565,32 @@ class GraphDS:
         n = self._l.sgh_mock_k17_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k17_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the workload incidents (K18) ----
+    def set_workload_incidents(self, on: bool = True, by: int = 0, min_value: float = 0.0) -> int:
+        """GraphDS::SetWorkloadIncidents: the per-window workload incident grouping on (by: engine.SG_SEL_*) or off (rc)"""
+        return self._l.sgh_graphds_set_workload_incidents(self._g, 1 if on else 0, by, min_value)
+
+    def workload_incidents(self):
+        """GraphDS::WorkloadIncidents: (engine.INCIDENT_DTYPE rows of the last flushed window, the u32 incident of every row of
+        workload_nodes())"""
+        from .engine import INCIDENT_DTYPE
+        nn = C.c_size_t(0)
+        n = self._l.sgh_graphds_workload_incidents(self._g, None, 0, None, 0, C.byref(nn))
+        if n < 0:
+            raise RuntimeError(f"WorkloadIncidents failed: {n}")
+        out, ni = np.zeros(max(n, 1), dtype=INCIDENT_DTYPE), np.zeros(max(nn.value, 1), dtype=np.uint32)
+        self._l.sgh_graphds_workload_incidents(self._g, out.ctypes.data, n, ni.ctypes.data, nn.value, C.byref(nn))
+        return out[:n], ni[:nn.value]
+
+    def mock_k18_ops(self) -> np.ndarray:
+        """the stand-in engine's K18 calls in order, four u64 each: (1, by, the bits of min_value, reserved) per sg_set_group_incidents
+        (all ones in the three for NULL), (2, cap, 0, 0) per sg_window_group_incidents, (3, n_index, cap, 0) per
+        sg_window_group_node_incident"""
+        n = self._l.sgh_mock_k18_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k18_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

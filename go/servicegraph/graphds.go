@@ -1387,6 +1387,71 @@ func (g *GraphDS) WindowWorkloadCulprits(k uint32, minShare float32) ([]Workload
 	return out, index, nil
 }
 
+// ---- workload incidents (K18) --------------------------------------------------------------------------------------------
+
+// SetWorkloadIncidents switches the per-window workload incident grouping on, behind SetWorkloadNodes: K12's grouping over the
+// window's group edges and workload rows.  A group edge is anomalous when its value is at least minValue; by is "score" (the group
+// edge's largest score), "lat_dev" or "err_dev" (the workload baseline's deviation, SetGroupTrend first: it survives a rollout).
+// It is independent of SetIncidents.  ClearWorkloadIncidents switches it off; SetWorkloadNodes(false) and any SetGroups call do so too.
+func (g *GraphDS) SetWorkloadIncidents(by string, minValue float32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var ip C.sg_incident_params
+	ip.struct_size = C.uint32_t(unsafe.Sizeof(ip))
+	ip.min_value = C.float(minValue)
+	switch by {
+	case "", "score":
+		ip.by = C.SG_SEL_SCORE
+	case "lat_dev":
+		ip.by = C.SG_SEL_LAT_DEV
+	case "err_dev":
+		ip.by = C.SG_SEL_ERR_DEV
+	default:
+		return fmt.Errorf("servicegraph: SetWorkloadIncidents by %q: score, lat_dev or err_dev", by)
+	}
+	if rc := C.sg_set_group_incidents(g.h, &ip); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_group_incidents = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func (g *GraphDS) ClearWorkloadIncidents() {
+	g.flushMu.Lock()
+	C.sg_set_group_incidents(g.h, nil)
+	g.flushMu.Unlock()
+}
+
+// WindowWorkloadIncidents returns the workload incidents of the window FlushWindow returned last, numbered by their first workload
+// (sg_window_group_incidents: one 72-byte row per incident crosses PCIe).  FirstNode, TopNode and CulpritNode (NoIncident without
+// SetWorkloadRank) index WindowWorkloadNodes; WorstRow indexes the window's group edges.
+func (g *GraphDS) WindowWorkloadIncidents() ([]Incident, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_group_incidents(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_incidents = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	incs := make([]C.sg_incident_out, int(n))
+	if rc := C.sg_window_group_incidents(g.h, &incs[0], C.size_t(len(incs)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_incidents = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(n) < len(incs) {
+		incs = incs[:int(n)]
+	}
+	out := make([]Incident, len(incs))
+	for i := range incs {
+		inc, o := &incs[i], &out[i]
+		o.Nodes, o.Edges = uint32(inc.nodes), uint32(inc.edges)
+		o.Count, o.Err, o.SumNs = uint64(inc.count), uint64(inc.err), uint64(inc.sum_ns)
+		o.ValueMax, o.WorstRow = float32(inc.value_max), uint32(inc.worst_row)
+		o.FirstNode, o.TopNode, o.CulpritNode = uint32(inc.first_node), uint32(inc.top_node), uint32(inc.culprit_node)
+	}
+	return out, nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

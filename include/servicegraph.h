@@ -921,6 +921,59 @@ int sg_window_group_rank_top(sg_handle h, uint32_t k, float min_share, sg_node_o
 int sg_window_group_rank_select(sg_handle h, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index,
                                 size_t cap, uint64_t* d_n, void* stream);
 
+/* ---- workload incidents (K18): each window's anomalous group edges grouped into connected components, on the device ------------ *
+ * Opt-in (sg_set_group_incidents, on an engine with the workload rows); without it nothing is computed or allocated, and every other
+ * row is the same either way.  It is independent of sg_set_incidents: both may be on, and neither reads the other.  K12 groups pods:
+ * its trend keys read K8's baseline, which a rollout forgets; its fields are node rows and its culprit K11's; and two pods of one
+ * workload failing towards two callees are two incidents.  This stage is K12's definition over the contracted graph, valued by K15
+ * and carrying K17's culprit.  There is no new struct and no new constant: the parameters are sg_incident_params (K12's checks), the
+ * rows sg_incident_out, "no incident" SG_NO_INCIDENT.
+ * Over the window's group edges j = 0 .. G-1 (sg_window_groups order, G = min(count, max_edges)) and its workload rows v = 0 .. n-1
+ * (sg_window_group_nodes order, cut at the slot's row capacity):
+ *   value_j  `by` = SG_SEL_SCORE: the group edge's score_max (what sg_window_groups_top keys); SG_SEL_LAT_DEV / SG_SEL_ERR_DEV: this
+ *            window's sg_window_group_trend row j, .lat_dev / .err_dev.  Any other `by`: SG_EINVAL
+ *   red      group edge j is red iff value_j >= min_value (a plain float comparison, NaN never) and both its from_ref and its
+ *            to_ref have a workload row at a position < n (a ref without a group key, or whose row was cut at the capacity, makes
+ *            the group edge not red).  Alive-only group edges and group edges inside a workload are ordinary group edges
+ *   graph    K12's: undirected, on the workload rows, one edge {from, to} per red group edge.  A workload row is in an incident
+ *            iff it is an endpoint of a red group edge (a red group edge with from_ref == to_ref makes its row an incident on its
+ *            own); the incidents are the connected components of those rows, numbered 0 .. I-1 by ascending first_node
+ * Incident i (sg_incident_out):
+ *   first_node, nodes    its smallest workload row (an index into sg_window_group_nodes); its workload rows
+ *   top_node             the workload row with the largest sg_node_out.score among them (by the order-preserving bits of the
+ *                        score, +0.0 above -0.0), ties to the smallest index
+ *   edges                its red GROUP EDGES (other group edges between its rows do not count)
+ *   count, err, sum_ns,  wrapping u64 sums of those group edges' count, err_count, sum_ns and score_q32: the group edge's fields as
+ *   score_q32            they stand, so every row folded into a red group edge counts, whether or not it would be red on its own
+ *   value_max, worst_row the largest value_j among its red group edges, +0.0 above -0.0; the smallest GROUP-EDGE INDEX that has it:
+ *                        worst_row indexes sg_window_groups, and that group edge's own worst_row leads on to the pod row
+ *   culprit_node         with the workload ranking (K17, sg_set_group_rank) on for the window: the workload row with the largest
+ *   rank_sum             sg_node_rank.rank among its rows, ties to the smallest index; the wrapping u64 sum of its rows' rank.
+ *                        K17 off: SG_NO_INCIDENT and 0.  K11 (sg_set_rank) is never read
+ *   reserved             0
+ * Every field is an integer sum, an integer max or a max of (order-preserving float bits << 32 | ~index): the result has one
+ * correct value.  Under a map that groups nothing the workload rows are the node rows and every group edge is one row: with
+ * `by` = SG_SEL_SCORE the incidents then equal sg_window_incidents' of the same window byte for byte, culprit_node and rank_sum
+ * too when K11 and K17 run with the same parameters.
+ * State: sg_set_group_incidents is SG_ESTATE with the workload rows off (sg_set_group_nodes), while a flush is open, or when `by`
+ * is a trend key and the group trend (sg_set_group_trend) is off; SG_EINVAL on bad parameters (struct_size, `by`, a non-zero
+ * reserved); NULL = off (frees its memory).  Memory is allocated there, never at sg_create, sg_set_groups or sg_set_group_nodes.
+ * sg_set_group_nodes(h, 0) and ANY sg_set_groups call switch it off and free it; sg_set_group_trend(h, NULL) does so only when `by`
+ * is a trend key; sg_group_assign, sg_set_group_rank, sg_set_incidents and sg_set_tracks do not touch it, and it touches none of
+ * them.  Reads of a window closed while it was off, and while a flush is open: SG_ESTATE.  Every close path computes it (one call,
+ * begin + end, the views, the _top flushes, sg_window_run, the staged sg_window_score), behind K15 (a trend key), K16 and its
+ * baseline, and K17 on the window's stream.                                                                                    */
+int sg_set_group_incidents(sg_handle h, const sg_incident_params* p);
+/* The workload incidents of the last READ window (as sg_window_incidents): *n = incidents, min(*n, cap) rows are written.       */
+int sg_window_group_incidents(sg_handle h, sg_incident_out* out, size_t cap, size_t* n);
+/* The incident number of every workload row of the last READ window, SG_NO_INCIDENT for a row in none (as sg_window_node_incident):
+ * node_index NULL: every workload row, *n = workload rows; else out[k] = the number of workload row node_index[k] (each < workload
+ * rows, else SG_EINVAL), *n = n_index.  min(*n, cap) values are written.                                                        */
+int sg_window_group_node_incident(sg_handle h, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n);
+/* Device sg_incident_out[], their count (one uint64_t) and uint32_t[workload rows] (the incident per workload row) of the window
+ * sg_window_run closed last (valid until its slot is reused; read them on that window's stream).                                */
+int sg_window_group_incidents_buffer(sg_handle h, void** d_incidents, void** d_count, void** d_node_incident);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
