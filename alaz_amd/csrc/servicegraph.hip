@@ -183,21 +183,32 @@ struct sg_engine {
     // node selection (K7 over node rows): scratch of plan_select(ncap) allocated at the first one, with the counter block k10_keys
     // fills, an index array and the host form's row staging (ncap each), in a block of its own (mem).
     struct NSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; sg_node_out* stage = nullptr; char* mem = nullptr; } nsel;
-    // K11, the culprit ranking (sg_rank.h): allocated at sg_set_rank (sg_plan.hpp plan_rank), one allocation, freed with the rollup.
-    // The per-row and per-node-key arrays and the partials are scratch shared by the window slots: every ranking waits for the
-    // previous one (ev), whichever slot's stream it runs on.  Per slot: the rank rows, and whether the window in the slot was ranked.
-    struct Rank { bool on = false; sg_rank_params p{}; sgplan::RankPlan plan; char* mem = nullptr; u32* src = nullptr; u32* dst = nullptr; u32* w = nullptr;
-                  u64* W = nullptr; u64* R = nullptr; u64* base = nullptr; u64* t = nullptr; u64* part = nullptr; u64* seed_sum = nullptr;
-                  sg_node_rank* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_node_rank*> rows; std::vector<char> valid;
-                  hipEvent_t ev = nullptr; bool pending = false; } rank;
-    // K12, the incidents (sg_incident.h): allocated at sg_set_incidents (sg_plan.hpp plan_incidents), one allocation, freed with the
-    // rollup (and with the edge trend when its key is a trend key).  The per-node-key arrays, the per-incident keys and the head
-    // counts are scratch shared by the window slots: every grouping waits for the previous one (ev), whichever slot's stream it
-    // runs on.  Per slot: the incident rows, their count, the incident per node row, and whether the window in the slot was grouped.
-    struct Incidents { bool on = false; sg_incident_params p{}; sgplan::IncidentPlan plan; char* mem = nullptr; u32* parent = nullptr; u32* flag = nullptr;
-                       u32* lab = nullptr; u32* num = nullptr; u32* kinc = nullptr; K12Keys* keys = nullptr; u32* blk = nullptr; u32* stage = nullptr;
-                       u32* stage_idx = nullptr; std::vector<sg_incident_out*> rows; std::vector<u64*> count; std::vector<u32*> node_inc;
-                       std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } inc;
+    // The ranking (sg_rank.h), K11's over the node rows (rank, sg_plan.hpp plan_rank) or K17's over the workload rows (grank,
+    // plan_group_rank; sg_group_rank.h): allocated at sg_set_rank / sg_set_group_rank, one allocation, freed with its rollup.  The
+    // per-edge and per-node arrays and the partials (K17: and the position table pos, null in K11) are scratch shared by the window
+    // slots: every ranking waits for the previous one (ev), whichever slot's stream it runs on.  Per slot: the rank rows, and whether
+    // the window in the slot was ranked.  The plan types the weights w: u32 by row in K11, u64 by group edge in K17.
+    struct RankState { bool on = false; sg_rank_params p{}; char* mem = nullptr; u32* pos = nullptr; u32* src = nullptr; u32* dst = nullptr;
+                       u64* W = nullptr; u64* R = nullptr; u64* base = nullptr; u64* t = nullptr; u64* part = nullptr; u64* seed_sum = nullptr;
+                       sg_node_rank* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_node_rank*> rows; std::vector<char> valid;
+                       hipEvent_t ev = nullptr; bool pending = false; };
+    template <class Plan>
+    struct Rank : RankState { Plan plan; typename Plan::Weight* w = nullptr; };
+    Rank<sgplan::RankPlan> rank;
+    // The incidents (sg_incident.h), K12's over the node rows (inc, sg_plan.hpp plan_incidents) or K18's over the workload rows
+    // (ginc, plan_group_incidents; sg_group_incident.h): allocated at sg_set_incidents / sg_set_group_incidents, one allocation, freed
+    // with its rollup (and with its space's edge baseline when its key is a trend key).  The per-node arrays, the per-incident keys
+    // and the head counts (K12: and kinc; K18: and the position table pos and esrc; null in the other) are scratch shared by the
+    // window slots: every grouping waits for the previous one (ev), whichever slot's stream it runs on.  Per slot: the incident rows,
+    // their count, the incident per node row, and whether the window in the slot was grouped.
+    struct IncidentState { bool on = false; sg_incident_params p{}; char* mem = nullptr; u32* pos = nullptr; u32* parent = nullptr;
+                           u32* flag = nullptr; u32* lab = nullptr; u32* num = nullptr; u32* kinc = nullptr; u32* esrc = nullptr;
+                           K12Keys* keys = nullptr; u32* blk = nullptr; u32* stage = nullptr; u32* stage_idx = nullptr;
+                           std::vector<sg_incident_out*> rows; std::vector<u64*> count; std::vector<u32*> node_inc; std::vector<char> valid;
+                           hipEvent_t ev = nullptr; bool pending = false; };
+    template <class Plan>
+    struct Incidents : IncidentState { Plan plan; };
+    Incidents<sgplan::IncidentPlan> inc;
     // K13, the tracks (sg_track.h): allocated at sg_set_tracks (sg_plan.hpp plan_tracks), one allocation, freed with the incidents.
     // Kept across windows: the members by anchor key, the table and its counters twice (cur: the copy the next window reads).  The
     // per-incident scratch, the claim words and the workgroup counts are shared by the window slots: the event chains the updates in
@@ -231,24 +242,9 @@ struct sg_engine {
     // plan_group_node_select's block, allocated at the first one, freed with the workload rows (its sizes are theirs)
     Baseline<sg_node_trend> gntrend;
     NSel gnsel;
-    // K17, the workload ranking (sg_group_rank.h): allocated at sg_set_group_rank (sg_plan.hpp plan_group_rank), one allocation, freed
-    // with the workload rows.  The position table, the per-group-edge and per-row arrays and the partials are scratch shared by the
-    // window slots: every ranking waits for the previous one (ev), whichever slot's stream it runs on.  Per slot: the rank rows, and
-    // whether the window in the slot was ranked.
-    struct GroupRank { bool on = false; sg_rank_params p{}; sgplan::GroupRankPlan plan; char* mem = nullptr; u32* pos = nullptr; u32* src = nullptr;
-                       u32* dst = nullptr; u64* w = nullptr; u64* W = nullptr; u64* R = nullptr; u64* base = nullptr; u64* t = nullptr; u64* part = nullptr;
-                       u64* seed_sum = nullptr; sg_node_rank* stage = nullptr; u32* stage_idx = nullptr; std::vector<sg_node_rank*> rows;
-                       std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } grank;
-    // K18, the workload incidents (sg_group_incident.h): allocated at sg_set_group_incidents (sg_plan.hpp plan_group_incidents), one
-    // allocation, freed with the workload rows (and with the group trend when its key is a trend key).  The position table, the
-    // per-row arrays, esrc, the per-incident keys and the head counts are scratch shared by the window slots: every grouping waits
-    // for the previous one (ev), whichever slot's stream it runs on.  Per slot: the incident rows, their count, the incident per
-    // workload row, and whether the window in the slot was grouped.
-    struct GroupIncidents { bool on = false; sg_incident_params p{}; sgplan::GroupIncidentPlan plan; char* mem = nullptr; u32* pos = nullptr;
-                            u32* parent = nullptr; u32* flag = nullptr; u32* lab = nullptr; u32* num = nullptr; u32* esrc = nullptr;
-                            K12Keys* keys = nullptr; u32* blk = nullptr; u32* stage = nullptr; u32* stage_idx = nullptr;
-                            std::vector<sg_incident_out*> rows; std::vector<u64*> count; std::vector<u32*> node_inc; std::vector<char> valid;
-                            hipEvent_t ev = nullptr; bool pending = false; } ginc;
+    // K17, the workload ranking, and K18, the workload incidents: the ranking and the incidents over the workload rows, freed with them
+    Rank<sgplan::GroupRankPlan> grank;
+    Incidents<sgplan::GroupIncidentPlan> ginc;
 };
 
 namespace {
@@ -754,16 +750,28 @@ constexpr StageWords kGroupNodeTrendWords{"the workload trend is off (sg_set_gro
 constexpr StageWords kGroupRankWords{"the workload ranking is off (sg_set_group_rank)", "the workload ranking was off"};
 constexpr StageWords kGroupIncidentsWords{"the workload incidents are off (sg_set_group_incidents)", "the workload incidents were off"};
 constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
-// A node space: what the baseline, the selection and the readbacks over node rows work on — K9's nodes or K16's workloads.  Its
-// rollup, its baseline, its selection scratch, the rows a window can have, and how its messages name it: the rollup, the baseline,
-// "<sel>: ..." of a selection, "... beyond the window's <rows_of>".
+// A node space: what the baseline, the selection, the ranking, the incidents and the readbacks over node rows work on — K9's nodes
+// or K16's workloads.  Its rollup, its baseline, its selection scratch, the rows a window can have, and how its messages name it:
+// the rollup, the baseline, "<sel>: ..." of a selection, "... beyond the window's <rows_of>".  Then its ranking and its incidents
+// (K11 and K12, or K17 and K18) with how they go off (K12 takes K13 with it) and their words, "<rsel>: ..." of a selection by rank,
+// and the edge baseline the incidents' trend key reads (K8's or K15's) with "... by a trend key: <edge_trend_off>".
+void free_incidents(sg_engine* e);
+void free_group_incidents(sg_engine* e);
 struct NodeSpace {
     sg_engine::RollupState* roll; sg_engine::Baseline<sg_node_trend>* trend; sg_engine::NSel* sel; u32 cap;
     StageWords roll_w, trend_w; const char* sel_w; const char* rows_of;
+    sg_engine::RankState* rank; sg_engine::IncidentState* inc; void (*inc_off)(sg_engine*);
+    StageWords rank_w, inc_w; const char* rsel_w;
+    const sg_engine::Baseline<sg_edge_trend>* edge_trend; const char* edge_trend_off;
 };
-NodeSpace node_space(sg_engine* e) { return {&e->nodes, &e->ntrend, &e->nsel, e->plan.ncap, kNodesWords, kNodeTrendWords, "node selection", "nodes"}; }
+NodeSpace node_space(sg_engine* e) {
+    return {&e->nodes, &e->ntrend, &e->nsel, e->plan.ncap, kNodesWords, kNodeTrendWords, "node selection", "nodes",
+            &e->rank, &e->inc, free_incidents, kRankWords, kIncidentsWords, "rank selection", &e->trend, "the trend is off (sg_set_trend)"};
+}
 NodeSpace workload_space(sg_engine* e) {
-    return {&e->gnodes, &e->gntrend, &e->gnsel, e->gnodes.plan.nc, kGroupNodesWords, kGroupNodeTrendWords, "workload selection", "workload rows"};
+    return {&e->gnodes, &e->gntrend, &e->gnsel, e->gnodes.plan.nc, kGroupNodesWords, kGroupNodeTrendWords, "workload selection", "workload rows",
+            &e->grank, &e->ginc, free_group_incidents, kGroupRankWords, kGroupIncidentsWords, "workload rank selection", &e->gtrend,
+            kGroupTrendWords.off};
 }
 
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
@@ -871,68 +879,87 @@ void free_baseline(sg_engine::Baseline<Row>& t) {
     free_stage(t);
 }
 
-// ---- K11, the culprit ranking (engine lock held) ---------------------------------------------------------------------------------
+// ---- K11 and K17, the ranking (engine lock held) ------------------------------------------------------------------------------------
 static_assert(sgplan::kRankThreads == K11_THREADS && sgplan::kRankRangeNodes == K11_NR && sgplan::kRankMaxWgs == K11_MAX_WGS &&
               sgplan::kRankRangeNodes * 8 <= sgplan::kLdsBytes, "plan_rank sizes the launches of sg_rank.h");
-// enqueue the ranking of the window in slot cur on stream s (behind its rollup, on the same stream) and behind the previous
-// ranking (any stream): 2 * iters + 3 plain launches, the rank rows go to the slot's buffer
-int launch_rank(sg_engine* e, hipStream_t s) {
-    sg_engine::WinSlot& w = work(e);
-    sg_engine::Rank& r = e->rank;
-    const sgplan::RankPlan& P = r.plan;
-    RankArgs a{};
-    a.nd = nodes_view(e, w, P.ncap);
-    a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur];
-    a.slices = P.slices; a.prep_wgs = P.prep_wgs; a.damping = r.p.damping_q8; a.seed = r.p.seed; a.seed_min = r.p.seed_min_score;
-    a.src = r.src; a.dst = r.dst; a.w = r.w; a.W = r.W; a.R = r.R; a.base = r.base; a.t = r.t; a.part = r.part; a.seed_sum = r.seed_sum;
+static_assert(K17_THREADS == K11_THREADS && K17_EDGE_THREADS == K11_EDGE_THREADS, "launch_ranking launches both rankings' kernels");
+// enqueue the ranking of node space ns's rows of the window in slot cur on stream s (behind their rollup, on the same stream) and
+// behind the previous ranking (any stream): a gets the space's rows, the parameters, r's arrays but w and the slot's rank rows;
+// front(nt) launches the passes in front (a prep pass of P.prep_wgs workgroups of nt threads the last), then 2 * iters + 2 plain
+// launches: the first edge and node pass, and iters rounds whose last node pass writes the rank rows
+template <class Args, class Front>
+int launch_ranking(sg_engine* e, const NodeSpace& ns, const sgplan::RankBlock& P, hipStream_t s, Args& a, Front front, void (*edge_first)(Args),
+                   void (*node_first)(Args), void (*edge)(Args), void (*node)(Args), void (*node_last)(Args)) {
+    sg_engine::RankState& r = *ns.rank;
+    a.nodes = ns.roll->rows[e->cur]; a.count = ns.roll->count[e->cur];
+    a.slices = P.slices; a.damping = r.p.damping_q8; a.seed = r.p.seed; a.seed_min = r.p.seed_min_score;
+    a.src = r.src; a.dst = r.dst; a.W = r.W; a.R = r.R; a.base = r.base; a.t = r.t; a.part = r.part; a.seed_sum = r.seed_sum;
     a.out = r.rows[e->cur];
     if (const int rc = stage_wait(e, r, s)) return rc;
     const dim3 eg(P.ranges * P.slices), et(K11_EDGE_THREADS), ng(P.node_wgs), nt(K11_THREADS);
-    hipLaunchKernelGGL(k11_prep, dim3(P.prep_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k11_edge<true>, eg, et, (size_t)P.lds_bytes, s, a);
-    hipLaunchKernelGGL((k11_node<true, false>), ng, nt, 0, s, a);
+    front(nt);
+    hipLaunchKernelGGL(edge_first, eg, et, (size_t)P.lds_bytes, s, a);
+    hipLaunchKernelGGL(node_first, ng, nt, 0, s, a);
     for (u32 i = 1; i <= r.p.iters; i++) {
-        hipLaunchKernelGGL(k11_edge<false>, eg, et, (size_t)P.lds_bytes, s, a);
-        if (i < r.p.iters) hipLaunchKernelGGL((k11_node<false, false>), ng, nt, 0, s, a);
-        else hipLaunchKernelGGL((k11_node<false, true>), ng, nt, 0, s, a);
+        hipLaunchKernelGGL(edge, eg, et, (size_t)P.lds_bytes, s, a);
+        void (*const pass)(Args) = i < r.p.iters ? node : node_last;
+        hipLaunchKernelGGL(pass, ng, nt, 0, s, a);
     }
     if (const int rc = stage_done(e, r, s)) return rc;
     r.valid[e->cur] = 1;
     return SG_OK;
 }
+// K11: 2 * iters + 3 launches, k11_prep in front
+int launch_rank(sg_engine* e, hipStream_t s) {
+    const sgplan::RankPlan& P = e->rank.plan;
+    RankArgs a{};
+    a.nd = nodes_view(e, work(e), P.ncap);
+    a.prep_wgs = P.prep_wgs; a.w = e->rank.w;
+    return launch_ranking(e, node_space(e), P, s, a, [&](dim3 nt) { hipLaunchKernelGGL(k11_prep, dim3(P.prep_wgs), nt, 0, s, a); },
+                          k11_edge<true>, k11_node<true, false>, k11_edge<false>, k11_node<false, false>, k11_node<false, true>);
+}
 void free_rank(sg_engine* e) { free_stage(e->rank); }
 
-// ---- K12, the incidents (engine lock held) -----------------------------------------------------------------------------------------
+// ---- K12 and K18, the incidents (engine lock held) -----------------------------------------------------------------------------------
 static_assert(sgplan::kIncThreads == K12_THREADS && sgplan::kIncMaxWgs == K12_MAX_WGS && sgplan::kIncKeysBytes == sizeof(K12Keys),
               "plan_incidents sizes the launches of sg_incident.h");
-// enqueue the grouping of the window in slot cur on stream s (behind its trend rows, its rollup and its ranking, on the same stream)
-// and behind the previous grouping (any stream): eight plain launches, the incidents go to the slot's buffers
-int launch_incidents(sg_engine* e, hipStream_t s) {
-    sg_engine::WinSlot& w = work(e);
-    sg_engine::Incidents& x = e->inc;
-    const sgplan::IncidentPlan& P = x.plan;
-    IncArgs a{};
-    a.nd = nodes_view(e, w, P.ncap);
-    a.nd.blk = x.blk; a.nd.count = x.count[e->cur];                  // (k9_scan: the head counts in, their scan and the incident count out)
-    a.nodes = e->nodes.rows[e->cur]; a.ncount = e->nodes.count[e->cur];
-    a.trend = x.p.by != SG_SEL_SCORE ? e->trend.rows[e->cur] : nullptr;
-    a.rank = e->rank.on ? e->rank.rows[e->cur] : nullptr;
+static_assert(K18_THREADS == K12_THREADS, "launch_grouping launches both groupings' kernels");
+// enqueue the grouping of node space ns's rows of the window in slot cur on stream s (behind the space's edge trend rows, its rollup
+// and its ranking, on the same stream) and behind the previous grouping (any stream): a gets the space's rows, trend rows and rank
+// rows, the parameters, x's arrays but the stage's own and the slot's buffers; nd, the NodesArgs inside a, the head counts and the
+// slot's count for k9_scan; eight plain launches, the *_nodes pass on nodes_wgs workgroups
+template <class Args>
+int launch_grouping(sg_engine* e, const NodeSpace& ns, const sgplan::IncidentBlock& P, hipStream_t s, Args& a, NodesArgs& nd, u32 nodes_wgs,
+                    void (*init)(Args), void (*hook)(Args), void (*label)(Args), void (*number)(Args), void (*nodes)(Args),
+                    void (*rows)(Args), void (*finish)(Args)) {
+    sg_engine::IncidentState& x = *ns.inc;
+    nd.blk = x.blk; nd.count = x.count[e->cur];                      // (k9_scan: the head counts in, their scan and the incident count out)
+    a.nodes = ns.roll->rows[e->cur]; a.ncount = ns.roll->count[e->cur];
+    a.trend = x.p.by != SG_SEL_SCORE ? ns.edge_trend->rows[e->cur] : nullptr;
+    a.rank = ns.rank->on ? ns.rank->rows[e->cur] : nullptr;
     a.by = x.p.by; a.min_value = x.p.min_value; a.node_per = P.node_per;
-    a.parent = x.parent; a.flag = x.flag; a.lab = x.lab; a.num = x.num; a.kinc = x.kinc; a.keys = x.keys;
+    a.parent = x.parent; a.flag = x.flag; a.lab = x.lab; a.num = x.num; a.keys = x.keys;
     a.out = x.rows[e->cur]; a.node_inc = x.node_inc[e->cur];
     if (const int rc = stage_wait(e, x, s)) return rc;
     const dim3 nt(K12_THREADS), gg(P.grid_wgs), ng(P.node_wgs);
-    hipLaunchKernelGGL(k12_init, gg, nt, 0, s, a);
-    hipLaunchKernelGGL(k12_hook, dim3(P.hook_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k12_label, ng, nt, 0, s, a);
-    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a.nd, P.node_wgs);
-    hipLaunchKernelGGL(k12_number, ng, nt, 0, s, a);
-    hipLaunchKernelGGL(k12_nodes, gg, nt, 0, s, a);
-    hipLaunchKernelGGL(k12_rows, dim3(P.row_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k12_finish, gg, nt, 0, s, a);
+    hipLaunchKernelGGL(init, gg, nt, 0, s, a);
+    hipLaunchKernelGGL(hook, dim3(P.hook_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(label, ng, nt, 0, s, a);
+    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, nd, P.node_wgs);
+    hipLaunchKernelGGL(number, ng, nt, 0, s, a);
+    hipLaunchKernelGGL(nodes, dim3(nodes_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(rows, dim3(P.row_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(finish, gg, nt, 0, s, a);
     if (const int rc = stage_done(e, x, s)) return rc;
     x.valid[e->cur] = 1;
     return SG_OK;
+}
+int launch_incidents(sg_engine* e, hipStream_t s) {
+    const sgplan::IncidentPlan& P = e->inc.plan;
+    IncArgs a{};
+    a.nd = nodes_view(e, work(e), P.ncap);
+    a.kinc = e->inc.kinc;
+    return launch_grouping(e, node_space(e), P, s, a, a.nd, P.grid_wgs, k12_init, k12_hook, k12_label, k12_number, k12_nodes, k12_rows, k12_finish);
 }
 // ---- K13, the tracks (engine lock held) --------------------------------------------------------------------------------------------
 static_assert(sgplan::kTrkThreads == K13_THREADS && sgplan::kTrkMaxWgs == K13_MAX_WGS && sgplan::kTrkBlkWords == K13_BLK_WORDS &&
@@ -1062,88 +1089,50 @@ void free_group_trend(sg_engine* e) {
 static_assert(offsetof(sg_group_edge, edges) == 56 && offsetof(sg_group_edge, alive) == 68 && offsetof(sg_group_edge, worst_row) == 72 &&
               offsetof(sg_group_edge, sumsq_us) == 24 && offsetof(sg_group_edge, max_ns) == 32 && offsetof(sg_group_edge, score_q32) == 40,
               "k16_load reads sg_group_edge by word");
-// enqueue the rollup of the group edges of the window in slot cur on stream s (behind its contraction, on the same stream): the
-// workload rows and their count go to the slot's buffers
-int launch_group_nodes(sg_engine* e, hipStream_t s) {
+// GroupNodesArgs of the window in slot cur, as K16, K17 and K18 read it: the id spaces, the group edges and their count, the key space
+GroupNodesArgs group_nodes_view(sg_engine* e) {
     const sgplan::GroupNodesPlan& P = e->gnodes.plan;
     GroupNodesArgs a{};
     a.nd = nodes_view(e, work(e), P.ncap);
     a.nd.max_edges = std::max<u64>(e->cfg.max_edges, 1);
     a.groups = e->grp.rows[e->cur]; a.gcount = e->grp.count[e->cur];
     a.max_groups = P.max_groups; a.gk = (u32)P.gk; a.hi_group = e->grp.hi_group; a.nc = P.nc;
-    return launch_rollup(e, e->gnodes, P, s, a, a.nd, k16_out, k16_in_part, k16_count, k16_write);
+    return a;
+}
+// enqueue the rollup of the group edges of the window in slot cur on stream s (behind its contraction, on the same stream): the
+// workload rows and their count go to the slot's buffers
+int launch_group_nodes(sg_engine* e, hipStream_t s) {
+    GroupNodesArgs a = group_nodes_view(e);
+    return launch_rollup(e, e->gnodes, e->gnodes.plan, s, a, a.nd, k16_out, k16_in_part, k16_count, k16_write);
 }
 // ---- K17, the workload ranking (engine lock held) ----------------------------------------------------------------------------------
 static_assert(sgplan::kGrpRankThreads == K17_THREADS && sgplan::kGrpRankRangeRows == K17_NR && sgplan::kGrpRankMaxWgs == K17_MAX_WGS &&
               sgplan::kGrpRankNodeRows == K17_NODE_ROWS && K17_THREADS % K17_NODE_ROWS == 0 &&
               2 * sgplan::kGrpRankRangeRows * 8 <= sgplan::kLdsBytes, "plan_group_rank sizes the launches of sg_group_rank.h");
-// enqueue the ranking of the workload rows of the window in slot cur on stream s (behind its contraction, its workload rows and their
-// baseline, on the same stream) and behind the previous ranking (any stream): 2 * iters + 4 plain launches, the rank rows go to
-// the slot's buffer
+// launch_ranking over the workload rows (behind the contraction, the workload rows and their baseline, on the same stream):
+// 2 * iters + 4 launches, k17_pos and k17_prep in front
 int launch_group_rank(sg_engine* e, hipStream_t s) {
-    sg_engine::GroupRank& r = e->grank;
-    const sgplan::GroupRankPlan& P = r.plan;
-    const sgplan::GroupNodesPlan& N = e->gnodes.plan;
+    const sgplan::GroupRankPlan& P = e->grank.plan;
     GroupRankArgs a{};
-    a.g.nd = nodes_view(e, work(e), N.ncap);
-    a.g.nd.max_edges = std::max<u64>(e->cfg.max_edges, 1);
-    a.g.groups = e->grp.rows[e->cur]; a.g.gcount = e->grp.count[e->cur];
-    a.g.max_groups = N.max_groups; a.g.gk = (u32)N.gk; a.g.hi_group = e->grp.hi_group; a.g.nc = N.nc;
-    a.nodes = e->gnodes.rows[e->cur]; a.count = e->gnodes.count[e->cur];
-    a.slices = P.slices; a.pos_wgs = P.pos_wgs; a.damping = r.p.damping_q8; a.seed = r.p.seed; a.seed_min = r.p.seed_min_score;
-    a.pos = r.pos; a.src = r.src; a.dst = r.dst; a.w = r.w; a.W = r.W; a.R = r.R; a.base = r.base; a.t = r.t; a.part = r.part; a.seed_sum = r.seed_sum;
-    a.out = r.rows[e->cur];
-    if (const int rc = stage_wait(e, r, s)) return rc;
-    const dim3 eg(P.ranges * P.slices), et(K17_EDGE_THREADS), ng(P.node_wgs), nt(K17_THREADS);
-    hipLaunchKernelGGL(k17_pos, dim3(P.pos_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k17_prep, dim3(P.prep_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k17_edge<true>, eg, et, (size_t)P.lds_bytes, s, a);
-    hipLaunchKernelGGL((k17_node<true, false>), ng, nt, 0, s, a);
-    for (u32 i = 1; i <= r.p.iters; i++) {
-        hipLaunchKernelGGL(k17_edge<false>, eg, et, (size_t)P.lds_bytes, s, a);
-        if (i < r.p.iters) hipLaunchKernelGGL((k17_node<false, false>), ng, nt, 0, s, a);
-        else hipLaunchKernelGGL((k17_node<false, true>), ng, nt, 0, s, a);
-    }
-    if (const int rc = stage_done(e, r, s)) return rc;
-    r.valid[e->cur] = 1;
-    return SG_OK;
+    a.g = group_nodes_view(e);
+    a.pos_wgs = P.pos_wgs; a.pos = e->grank.pos; a.w = e->grank.w;
+    return launch_ranking(e, workload_space(e), P, s, a, [&](dim3 nt) {
+        hipLaunchKernelGGL(k17_pos, dim3(P.pos_wgs), nt, 0, s, a);
+        hipLaunchKernelGGL(k17_prep, dim3(P.prep_wgs), nt, 0, s, a);
+    }, k17_edge<true>, k17_node<true, false>, k17_edge<false>, k17_node<false, false>, k17_node<false, true>);
 }
 void free_group_rank(sg_engine* e) { free_stage(e->grank); }
 // ---- K18, the workload incidents (engine lock held) --------------------------------------------------------------------------------
 static_assert(sgplan::kGrpIncThreads == K18_THREADS && sgplan::kGrpIncMaxWgs == K18_MAX_WGS && sgplan::kGrpIncSlots == K12_SLOTS &&
               sgplan::kIncKeysBytes == sizeof(K12Keys), "plan_group_incidents sizes the launches of sg_group_incident.h");
-// enqueue the grouping of the group edges of the window in slot cur on stream s (behind its contraction, its group trend rows, its
-// workload rows and its workload ranking, on the same stream) and behind the previous grouping (any stream): eight plain launches,
-// the incidents go to the slot's buffers
+// launch_grouping over the workload rows (behind the contraction, the group trend rows, the workload rows and the workload ranking,
+// on the same stream): k18_nodes on its fold grid
 int launch_group_incidents(sg_engine* e, hipStream_t s) {
-    sg_engine::GroupIncidents& x = e->ginc;
-    const sgplan::GroupIncidentPlan& P = x.plan;
-    const sgplan::GroupNodesPlan& N = e->gnodes.plan;
+    const sgplan::GroupIncidentPlan& P = e->ginc.plan;
     GroupIncArgs a{};
-    a.g.nd = nodes_view(e, work(e), N.ncap);
-    a.g.nd.max_edges = std::max<u64>(e->cfg.max_edges, 1);
-    a.g.nd.blk = x.blk; a.g.nd.count = x.count[e->cur];              // (k9_scan: the head counts in, their scan and the incident count out)
-    a.g.groups = e->grp.rows[e->cur]; a.g.gcount = e->grp.count[e->cur];
-    a.g.max_groups = N.max_groups; a.g.gk = (u32)N.gk; a.g.hi_group = e->grp.hi_group; a.g.nc = N.nc;
-    a.nodes = e->gnodes.rows[e->cur]; a.ncount = e->gnodes.count[e->cur];
-    a.trend = x.p.by != SG_SEL_SCORE ? e->gtrend.rows[e->cur] : nullptr;
-    a.rank = e->grank.on ? e->grank.rows[e->cur] : nullptr;
-    a.by = x.p.by; a.min_value = x.p.min_value; a.node_per = P.node_per;
-    a.pos = x.pos; a.parent = x.parent; a.flag = x.flag; a.lab = x.lab; a.num = x.num; a.esrc = x.esrc; a.keys = x.keys;
-    a.out = x.rows[e->cur]; a.node_inc = x.node_inc[e->cur];
-    if (const int rc = stage_wait(e, x, s)) return rc;
-    const dim3 nt(K18_THREADS), gg(P.grid_wgs), ng(P.node_wgs);
-    hipLaunchKernelGGL(k18_init, gg, nt, 0, s, a);
-    hipLaunchKernelGGL(k18_hook, dim3(P.hook_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k18_label, ng, nt, 0, s, a);
-    hipLaunchKernelGGL(k9_scan, dim3(1), dim3(K9_SCAN_THREADS), 0, s, a.g.nd, P.node_wgs);
-    hipLaunchKernelGGL(k18_number, ng, nt, 0, s, a);
-    hipLaunchKernelGGL(k18_nodes, dim3(P.fold_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k18_rows, dim3(P.row_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k18_finish, gg, nt, 0, s, a);
-    if (const int rc = stage_done(e, x, s)) return rc;
-    x.valid[e->cur] = 1;
-    return SG_OK;
+    a.g = group_nodes_view(e);
+    a.pos = e->ginc.pos; a.esrc = e->ginc.esrc;
+    return launch_grouping(e, workload_space(e), P, s, a, a.g.nd, P.fold_wgs, k18_init, k18_hook, k18_label, k18_number, k18_nodes, k18_rows, k18_finish);
 }
 void free_group_incidents(sg_engine* e) { free_stage(e->ginc); }
 // a selection scratch block off (the workload rows': its sizes are the stage's)
@@ -1185,6 +1174,9 @@ void free_nodes(sg_engine* e) {
 }
 
 void free_vanished(sg_engine* e) { free_list(e->vanished); }
+
+// an edge baseline switched off (or failing to come on) takes its space's incidents with it when their key is a trend row's
+void drop_incidents(sg_engine* e, const NodeSpace& ns) { if (ns.inc->on && ns.inc->p.by != SG_SEL_SCORE) ns.inc_off(e); }
 
 void free_trend(sg_engine* e) {
     free_vanished(e);
@@ -1440,11 +1432,11 @@ int launch_node_select_by(sg_engine* e, const NodeSpace& ns, hipStream_t st, int
         return (int)SG_OK;
     }, [](const SelArgs&, dim3) {});
 }
-// by the culprit rank: k11_keys over the window's rank rows of ranking r over node space ns (K11 over the nodes, K17 over the workloads;
+// by the culprit rank: k11_keys over the window's rank rows of node space ns's ranking (K11 over the nodes, K17 over the workloads;
 // behind that ranking); d_rank (may be NULL) gets the selected rank rows
-template <class R>
-int launch_rank_select(sg_engine* e, const NodeSpace& ns, const R& r, hipStream_t st, int slot, u32 k, float min_share, sg_node_out* d_out,
+int launch_rank_select(sg_engine* e, const NodeSpace& ns, hipStream_t st, int slot, u32 k, float min_share, sg_node_out* d_out,
                        sg_node_rank* d_rank, u32* d_index, u64 cap, u64* d_n) {
+    const sg_engine::RankState& r = *ns.rank;
     const sg_node_rank* rk = r.rows[slot];
     return launch_node_select(e, ns, st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
         if (r.pending) HIP_TRY(e, hipStreamWaitEvent(st, r.ev, 0));
@@ -1730,6 +1722,128 @@ int list_read(sg_engine* e, const sg_engine::Vanished& v, const sg_engine::Basel
     if (!v.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while " + what.was; return SG_ESTATE; }
     if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
     return copy_counted(e, v.count[e->cur], v.rows[e->cur], sizeof(sg_edge_vanished), out, std::min<size_t>(cap, v.plan.rows), n);
+}
+// ---- K11 and K17, K12 and K18: the ranking and the incidents, once over a node space (engine lock held) --------------------------------
+// the ranking r of node space ns on with parameters p (NULL: off): plan(slots) plans it, edge_first / edge are its kernels with
+// dynamic LDS; one block — the node arrays, the partials, the seed sums, the staging and every slot's rank rows, and what
+// carve(r, P) takes: the space's own per-edge arrays
+template <class R, class K, class MakePlan, class Carve>
+int rank_set(sg_engine* e, const NodeSpace& ns, const char* call, R& r, const sg_rank_params* p, K edge_first, K edge, MakePlan plan, Carve carve) {
+    if (!ns.roll->on) { e->err = std::string(call) + ": " + ns.roll_w.off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    sg_rank_params q{};
+    if (p && sgplan::check_rank(*p, &q)) { e->err = std::string(call) + ": bad parameters"; return SG_EINVAL; }
+    free_stage(r);
+    if (!p) return SG_OK;
+    const u32 slots = (u32)e->slots.size();
+    r.p = q;
+    r.plan = plan(slots);
+    const auto& P = r.plan;
+    HIP_TRY(e, lds_limit(P.lds_bytes, edge_first, edge));
+    HIP_TRY(e, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &r.mem, P.total_bytes, call, [&r] { free_stage(r); })) return rc;
+    r.W = at<u64>(r.mem, P.node_off[0]); r.R = at<u64>(r.mem, P.node_off[1]); r.base = at<u64>(r.mem, P.node_off[2]); r.t = at<u64>(r.mem, P.node_off[3]);
+    r.part = at<u64>(r.mem, P.part_off);
+    r.seed_sum = at<u64>(r.mem, P.seed_off);
+    carve(r, P);
+    r.stage = at<sg_node_rank>(r.mem, P.stage_off);
+    r.stage_idx = at<u32>(r.mem, P.stage_idx_off);
+    for (u32 k = 0; k < slots; k++) r.rows.push_back(at<sg_node_rank>(r.mem, P.slot.off + k * P.slot.bytes + P.slot_rows));
+    r.valid.assign(slots, 0);
+    r.on = true;
+    return SG_OK;
+}
+// the rank rows of the last read window: every row, or those at node_index
+int rank_read(sg_engine* e, const NodeSpace& ns, const char* call, const uint32_t* node_index, size_t n_index, sg_node_rank* out, size_t cap, size_t* n) {
+    sg_engine::RankState& r = *ns.rank;
+    if (const int rc = stage_ready(e, r, call, ns.rank_w)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, ns.roll->count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const std::string beyond = std::string(call) + ": a node index beyond the window's " + ns.rows_of;
+    return copy_indexed(e, (const sg_node_rank*)r.rows[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, r.stage, r.stage_idx,
+                        std::max<size_t>(ns.cap, 1), beyond.c_str());
+}
+int rank_buffer(sg_engine* e, const NodeSpace& ns, const char* call, void** d_rank) {
+    const sg_engine::RankState& r = *ns.rank;
+    int slot;
+    if (const int rc = stage_slot(e, r, call, ns.rank_w, &slot)) return rc;
+    *d_rank = r.rows[slot];
+    return SG_OK;
+}
+// the selection by rank: the rollup and the ranking on, and the window in `slot` closed with them on
+int check_rsel(sg_engine* e, const NodeSpace& ns, int slot) {
+    const std::string sel = ns.rsel_w;
+    if (!ns.roll->on) { e->err = sel + ": " + ns.roll_w.off; return SG_ESTATE; }
+    if (!ns.rank->on) { e->err = sel + ": " + ns.rank_w.off; return SG_ESTATE; }
+    if (!ns.roll->valid[slot] || !ns.rank->valid[slot]) { e->err = sel + ": the window was closed while " + ns.rank_w.was; return SG_ESTATE; }
+    return SG_OK;
+}
+int rank_top(sg_engine* e, const NodeSpace& ns, const char* call, u32 k, float min_share, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index,
+             size_t cap, size_t* n_selected, size_t* n_nodes) {
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (const int rc = check_rsel(e, ns, e->cur)) return rc;
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    return node_top_host(e, ns, [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
+        return launch_rank_select(e, ns, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
+    }, out, rank_out, ns.rank->stage, node_index, cap, n_selected, n_nodes);
+}
+int rank_select(sg_engine* e, const NodeSpace& ns, u32 k, float min_share, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n, void* stream) {
+    const int slot = ran_slot(e);
+    if (const int rc = check_rsel(e, ns, slot)) return rc;
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    return launch_rank_select(e, ns, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
+}
+// the incidents x of node space ns on with parameters p (NULL: off): plan(slots) plans them; one block — the keys, the head counts,
+// the staging and every slot's rows, count and incident per node row, and what carve(x, P) takes: the space's own arrays
+template <class X, class MakePlan, class Carve>
+int incidents_set(sg_engine* e, const NodeSpace& ns, const char* call, X& x, const sg_incident_params* p, MakePlan plan, Carve carve) {
+    if (!ns.roll->on) { e->err = std::string(call) + ": " + ns.roll_w.off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    sg_incident_params q{};
+    if (p && sgplan::check_incidents(*p, &q)) { e->err = std::string(call) + ": bad parameters"; return SG_EINVAL; }
+    if (p && q.by != SG_SEL_SCORE && !ns.edge_trend->on) { e->err = std::string(call) + " by a trend key: " + ns.edge_trend_off; return SG_ESTATE; }
+    ns.inc_off(e);
+    if (!p) return SG_OK;
+    const u32 slots = (u32)e->slots.size();
+    x.p = q;
+    x.plan = plan(slots);
+    const auto& P = x.plan;
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, call, [e, &ns] { ns.inc_off(e); })) return rc;
+    x.keys = at<K12Keys>(x.mem, P.keys_off);
+    carve(x, P);
+    x.blk = at<u32>(x.mem, P.blk_off);
+    x.stage = at<u32>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = x.mem + P.slot.off + k * P.slot.bytes;
+        x.rows.push_back(at<sg_incident_out>(s, P.slot_rows)); x.count.push_back(at<u64>(s, P.slot_count));
+        x.node_inc.push_back(at<u32>(s, P.slot_node_inc));
+    }
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+int incidents_read(sg_engine* e, const NodeSpace& ns, const char* call, sg_incident_out* out, size_t cap, size_t* n) {
+    const sg_engine::IncidentState& x = *ns.inc;
+    if (const int rc = stage_ready(e, x, call, ns.inc_w)) return rc;
+    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_incident_out), out, cap, n);
+}
+// the incident per node row of the last read window: every row's, or those at node_index
+int node_incident_read(sg_engine* e, const NodeSpace& ns, const char* call, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    const sg_engine::IncidentState& x = *ns.inc;
+    if (const int rc = stage_ready(e, x, call, ns.inc_w)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, ns.roll->count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const std::string beyond = std::string(call) + ": a node index beyond the window's " + ns.rows_of;
+    return copy_indexed(e, (const u32*)x.node_inc[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, x.stage, x.stage_idx,
+                        std::max<size_t>(ns.cap, 1), beyond.c_str());
+}
+int incidents_buffer(sg_engine* e, const NodeSpace& ns, const char* call, void** d_incidents, void** d_count, void** d_node_incident) {
+    const sg_engine::IncidentState& x = *ns.inc;
+    int slot;
+    if (const int rc = stage_slot(e, x, call, ns.inc_w, &slot)) return rc;
+    *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
+    return SG_OK;
 }
 }  // namespace
 
@@ -2529,9 +2643,8 @@ int sg_set_trend(sg_handle e, const sg_trend_params* p) {
     std::unique_lock<std::mutex> g(e->mu);
     if (e->closing || e->flush_open) { e->err = "sg_set_trend while a flush is open"; return SG_ESTATE; }
     free_trend(e);
-    auto drop_incidents = [e] { if (e->inc.on && e->inc.p.by != SG_SEL_SCORE) free_incidents(e); };   // (their key is a trend row's)
-    if (!p) { drop_incidents(); return SG_OK; }
-    return baseline_on(e, e->trend, r, sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r), "sg_set_trend", [e, drop_incidents] { free_trend(e); drop_incidents(); });
+    if (!p) { drop_incidents(e, node_space(e)); return SG_OK; }
+    return baseline_on(e, e->trend, r, sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r), "sg_set_trend", [e] { free_trend(e); drop_incidents(e, node_space(e)); });
 }
 int sg_window_trend(sg_handle e, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
@@ -2732,135 +2845,59 @@ int sg_window_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min_value
 int sg_set_rank(sg_handle e, const sg_rank_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->nodes.on) { e->err = "sg_set_rank: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_rank while a flush is open"; return SG_ESTATE; }
-    sg_rank_params q{};
-    if (p && sgplan::check_rank(*p, &q)) { e->err = "sg_set_rank: bad parameters"; return SG_EINVAL; }
-    free_rank(e);
-    if (!p) return SG_OK;
-    sg_engine::Rank& r = e->rank;
-    const u32 slots = (u32)e->slots.size();
-    r.p = q;
-    r.plan = sgplan::plan_rank(e->cfg.max_edges, e->nodes.plan.ncap, slots);
-    const sgplan::RankPlan& P = r.plan;
-    HIP_TRY(e, lds_limit(P.lds_bytes, k11_edge<true>, k11_edge<false>));
-    HIP_TRY(e, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
-    if (const int rc = alloc_block(e, &r.mem, P.total_bytes, "sg_set_rank", [e] { free_rank(e); })) return rc;
-    r.W = at<u64>(r.mem, P.node_off[0]); r.R = at<u64>(r.mem, P.node_off[1]); r.base = at<u64>(r.mem, P.node_off[2]); r.t = at<u64>(r.mem, P.node_off[3]);
-    r.part = at<u64>(r.mem, P.part_off);
-    r.seed_sum = at<u64>(r.mem, P.seed_off);
-    r.src = at<u32>(r.mem, P.row_off[0]); r.dst = at<u32>(r.mem, P.row_off[1]); r.w = at<u32>(r.mem, P.row_off[2]);
-    r.stage = at<sg_node_rank>(r.mem, P.stage_off);
-    r.stage_idx = at<u32>(r.mem, P.stage_idx_off);
-    for (u32 k = 0; k < slots; k++) r.rows.push_back(at<sg_node_rank>(r.mem, P.slot.off + k * P.slot.bytes + P.slot_rows));
-    r.valid.assign(slots, 0);
-    r.on = true;
-    return SG_OK;
+    return rank_set(e, node_space(e), "sg_set_rank", e->rank, p, k11_edge<true>, k11_edge<false>,
+                    [e](u32 slots) { return sgplan::plan_rank(e->cfg.max_edges, e->nodes.plan.ncap, slots); },
+                    [](auto& r, const sgplan::RankPlan& P) {
+                        r.src = at<u32>(r.mem, P.row_off[0]); r.dst = at<u32>(r.mem, P.row_off[1]); r.w = at<u32>(r.mem, P.row_off[2]);
+                    });
 }
 int sg_window_rank(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_rank* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::Rank& r = e->rank;
-    if (const int rc = stage_ready(e, r, "sg_window_rank", kRankWords)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    return copy_indexed(e, (const sg_node_rank*)r.rows[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, r.stage, r.stage_idx,
-                        std::max<size_t>(r.plan.ncap, 1), "sg_window_rank: a node index beyond the window's nodes");
+    return rank_read(e, node_space(e), "sg_window_rank", node_index, n_index, out, cap, n);
 }
 int sg_window_rank_buffer(sg_handle e, void** d_rank) {
     if (!e || !d_rank) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Rank& r = e->rank;
-    int slot;
-    if (const int rc = stage_slot(e, r, "sg_window_rank_buffer", kRankWords, &slot)) return rc;
-    *d_rank = r.rows[slot];
-    return SG_OK;
+    return rank_buffer(e, node_space(e), "sg_window_rank_buffer", d_rank);
 }
-namespace {
-int check_rsel(sg_engine* e, int slot) {
-    if (!e->nodes.on) { e->err = "rank selection: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
-    if (!e->rank.on) { e->err = "rank selection: the ranking is off (sg_set_rank)"; return SG_ESTATE; }
-    if (!e->nodes.valid[slot] || !e->rank.valid[slot]) { e->err = "rank selection: the window was closed while the ranking was off"; return SG_ESTATE; }
-    return SG_OK;
-}
-}  // namespace
 int sg_window_rank_top(sg_handle e, uint32_t k, float min_share, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap,
                        size_t* n_selected, size_t* n_nodes) {
     if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->closing || e->flush_open) { e->err = "sg_window_rank_top while a flush is open"; return SG_ESTATE; }
-    if (const int rc = check_rsel(e, e->cur)) return rc;
-    if (const int rc = nsel_reserve(e, node_space(e))) return rc;
-    return node_top_host(e, node_space(e), [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
-        return launch_rank_select(e, node_space(e), e->rank, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
-    }, out, rank_out, e->rank.stage, node_index, cap, n_selected, n_nodes);
+    return rank_top(e, node_space(e), "sg_window_rank_top", k, min_share, out, rank_out, node_index, cap, n_selected, n_nodes);
 }
 int sg_window_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n, void* stream) {
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const int slot = ran_slot(e);
-    if (const int rc = check_rsel(e, slot)) return rc;
-    if (const int rc = nsel_reserve(e, node_space(e))) return rc;
-    return launch_rank_select(e, node_space(e), e->rank, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return rank_select(e, node_space(e), k, min_share, d_out, d_index, cap, d_n, stream);
 }
 
 // ---- K12, the incidents -----------------------------------------------------------------------------------------------------------
 int sg_set_incidents(sg_handle e, const sg_incident_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->nodes.on) { e->err = "sg_set_incidents: the node rollup is off (sg_set_nodes)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_incidents while a flush is open"; return SG_ESTATE; }
-    sg_incident_params q{};
-    if (p && sgplan::check_incidents(*p, &q)) { e->err = "sg_set_incidents: bad parameters"; return SG_EINVAL; }
-    if (p && q.by != SG_SEL_SCORE && !e->trend.on) { e->err = "sg_set_incidents by a trend key: the trend is off (sg_set_trend)"; return SG_ESTATE; }
-    free_incidents(e);
-    if (!p) return SG_OK;
-    sg_engine::Incidents& x = e->inc;
-    const u32 slots = (u32)e->slots.size();
-    x.p = q;
-    x.plan = sgplan::plan_incidents(e->cfg.max_edges, e->nodes.plan.ncap, slots);
-    const sgplan::IncidentPlan& P = x.plan;
-    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
-    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_incidents", [e] { free_incidents(e); })) return rc;
-    x.keys = at<K12Keys>(x.mem, P.keys_off);
-    x.parent = at<u32>(x.mem, P.key_off[0]); x.flag = at<u32>(x.mem, P.key_off[1]); x.lab = at<u32>(x.mem, P.key_off[2]);
-    x.num = at<u32>(x.mem, P.key_off[3]); x.kinc = at<u32>(x.mem, P.key_off[4]);
-    x.blk = at<u32>(x.mem, P.blk_off);
-    x.stage = at<u32>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
-    for (u32 k = 0; k < slots; k++) {
-        char* s = x.mem + P.slot.off + k * P.slot.bytes;
-        x.rows.push_back(at<sg_incident_out>(s, P.slot_rows)); x.count.push_back(at<u64>(s, P.slot_count));
-        x.node_inc.push_back(at<u32>(s, P.slot_node_inc));
-    }
-    x.valid.assign(slots, 0);
-    x.on = true;
-    return SG_OK;
+    return incidents_set(e, node_space(e), "sg_set_incidents", e->inc, p,
+                         [e](u32 slots) { return sgplan::plan_incidents(e->cfg.max_edges, e->nodes.plan.ncap, slots); },
+                         [](auto& x, const sgplan::IncidentPlan& P) {
+                             x.parent = at<u32>(x.mem, P.key_off[0]); x.flag = at<u32>(x.mem, P.key_off[1]); x.lab = at<u32>(x.mem, P.key_off[2]);
+                             x.num = at<u32>(x.mem, P.key_off[3]); x.kinc = at<u32>(x.mem, P.key_off[4]);
+                         });
 }
 int sg_window_incidents(sg_handle e, sg_incident_out* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Incidents& x = e->inc;
-    if (const int rc = stage_ready(e, x, "sg_window_incidents", kIncidentsWords)) return rc;
-    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_incident_out), out, cap, n);
+    return incidents_read(e, node_space(e), "sg_window_incidents", out, cap, n);
 }
 int sg_window_node_incident(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Incidents& x = e->inc;
-    if (const int rc = stage_ready(e, x, "sg_window_node_incident", kIncidentsWords)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, e->nodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    return copy_indexed(e, (const u32*)x.node_inc[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, x.stage, x.stage_idx,
-                        std::max<size_t>(x.plan.ncap, 1), "sg_window_node_incident: a node index beyond the window's nodes");
+    return node_incident_read(e, node_space(e), "sg_window_node_incident", node_index, n_index, out, cap, n);
 }
 int sg_window_incidents_buffer(sg_handle e, void** d_incidents, void** d_count, void** d_node_incident) {
     if (!e || !d_incidents || !d_count || !d_node_incident) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Incidents& x = e->inc;
-    int slot;
-    if (const int rc = stage_slot(e, x, "sg_window_incidents_buffer", kIncidentsWords, &slot)) return rc;
-    *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
-    return SG_OK;
+    return incidents_buffer(e, node_space(e), "sg_window_incidents_buffer", d_incidents, d_count, d_node_incident);
 }
 
 // ---- K14, the groups ---------------------------------------------------------------------------------------------------------------
@@ -2959,11 +2996,10 @@ int sg_set_group_trend(sg_handle e, const sg_trend_params* p) {
     sg_trend_params r{};
     if (p && sgplan::check_group_trend(*p, e->cfg.max_edges, &r)) { e->err = "sg_set_group_trend: bad parameters"; return SG_EINVAL; }
     free_group_trend(e);
-    auto drop_incidents = [e] { if (e->ginc.on && e->ginc.p.by != SG_SEL_SCORE) free_group_incidents(e); };   // (their key is a group trend row's)
-    if (!p) { drop_incidents(); return SG_OK; }
+    if (!p) { drop_incidents(e, workload_space(e)); return SG_OK; }
     sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
     const u32 slots = (u32)e->slots.size();
-    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_trend(e->cfg.max_edges, slots, r), "sg_set_group_trend", [e, drop_incidents] { free_group_trend(e); drop_incidents(); })) return rc;
+    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_trend(e->cfg.max_edges, slots, r), "sg_set_group_trend", [e] { free_group_trend(e); drop_incidents(e, workload_space(e)); })) return rc;
     t.valid.assign(slots, 0);
     return SG_OK;
 }
@@ -3118,145 +3154,67 @@ int sg_window_group_nodes_select(sg_handle e, uint32_t by, uint32_t k, float min
     return nodes_select(e, workload_space(e), by, k, min_value, d_out, d_index, cap, d_n, stream);
 }
 
-// ---- K17, the workload ranking -----------------------------------------------------------------------------------------------------
+// ---- K17, the workload ranking: K11's code over the workload space ------------------------------------------------------------------
 int sg_set_group_rank(sg_handle e, const sg_rank_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->gnodes.on) { e->err = "sg_set_group_rank: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_group_rank while a flush is open"; return SG_ESTATE; }
-    sg_rank_params q{};
-    if (p && sgplan::check_rank(*p, &q)) { e->err = "sg_set_group_rank: bad parameters"; return SG_EINVAL; }
-    free_group_rank(e);
-    if (!p) return SG_OK;
-    sg_engine::GroupRank& r = e->grank;
-    const u32 slots = (u32)e->slots.size();
-    r.p = q;
-    r.plan = sgplan::plan_group_rank(e->cfg.max_edges, e->gnodes.plan.nc, e->gnodes.plan.gk, slots);
-    const sgplan::GroupRankPlan& P = r.plan;
-    HIP_TRY(e, lds_limit(P.lds_bytes, k17_edge<true>, k17_edge<false>));
-    HIP_TRY(e, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
-    if (const int rc = alloc_block(e, &r.mem, P.total_bytes, "sg_set_group_rank", [e] { free_group_rank(e); })) return rc;
-    r.W = at<u64>(r.mem, P.node_off[0]); r.R = at<u64>(r.mem, P.node_off[1]); r.base = at<u64>(r.mem, P.node_off[2]); r.t = at<u64>(r.mem, P.node_off[3]);
-    r.part = at<u64>(r.mem, P.part_off);
-    r.seed_sum = at<u64>(r.mem, P.seed_off);
-    r.pos = at<u32>(r.mem, P.pos_off);
-    r.src = at<u32>(r.mem, P.edge_off[0]); r.dst = at<u32>(r.mem, P.edge_off[1]); r.w = at<u64>(r.mem, P.w_off);
-    r.stage = at<sg_node_rank>(r.mem, P.stage_off);
-    r.stage_idx = at<u32>(r.mem, P.stage_idx_off);
-    for (u32 k = 0; k < slots; k++) r.rows.push_back(at<sg_node_rank>(r.mem, P.slot.off + k * P.slot.bytes + P.slot_rows));
-    r.valid.assign(slots, 0);
-    r.on = true;
-    return SG_OK;
+    return rank_set(e, workload_space(e), "sg_set_group_rank", e->grank, p, k17_edge<true>, k17_edge<false>,
+                    [e](u32 slots) { return sgplan::plan_group_rank(e->cfg.max_edges, e->gnodes.plan.nc, e->gnodes.plan.gk, slots); },
+                    [](auto& r, const sgplan::GroupRankPlan& P) {
+                        r.pos = at<u32>(r.mem, P.pos_off);
+                        r.src = at<u32>(r.mem, P.edge_off[0]); r.dst = at<u32>(r.mem, P.edge_off[1]); r.w = at<u64>(r.mem, P.w_off);
+                    });
 }
 int sg_window_group_rank(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_rank* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::GroupRank& r = e->grank;
-    if (const int rc = stage_ready(e, r, "sg_window_group_rank", kGroupRankWords)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, e->gnodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    return copy_indexed(e, (const sg_node_rank*)r.rows[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, r.stage, r.stage_idx,
-                        std::max<size_t>(r.plan.nc, 1), "sg_window_group_rank: a node index beyond the window's workload rows");
+    return rank_read(e, workload_space(e), "sg_window_group_rank", node_index, n_index, out, cap, n);
 }
 int sg_window_group_rank_buffer(sg_handle e, void** d_rank) {
     if (!e || !d_rank) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::GroupRank& r = e->grank;
-    int slot;
-    if (const int rc = stage_slot(e, r, "sg_window_group_rank_buffer", kGroupRankWords, &slot)) return rc;
-    *d_rank = r.rows[slot];
-    return SG_OK;
+    return rank_buffer(e, workload_space(e), "sg_window_group_rank_buffer", d_rank);
 }
-namespace {
-int check_grsel(sg_engine* e, int slot) {
-    if (!e->gnodes.on) { e->err = "workload rank selection: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
-    if (!e->grank.on) { e->err = "workload rank selection: the workload ranking is off (sg_set_group_rank)"; return SG_ESTATE; }
-    if (!e->gnodes.valid[slot] || !e->grank.valid[slot]) { e->err = "workload rank selection: the window was closed while the workload ranking was off"; return SG_ESTATE; }
-    return SG_OK;
-}
-}  // namespace
 int sg_window_group_rank_top(sg_handle e, uint32_t k, float min_share, sg_node_out* out, sg_node_rank* rank_out, uint32_t* node_index, size_t cap,
                              size_t* n_selected, size_t* n_nodes) {
     if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->closing || e->flush_open) { e->err = "sg_window_group_rank_top while a flush is open"; return SG_ESTATE; }
-    if (const int rc = check_grsel(e, e->cur)) return rc;
-    const NodeSpace ns = workload_space(e);
-    if (const int rc = nsel_reserve(e, ns)) return rc;
-    return node_top_host(e, ns, [&](sg_node_out* d_out, sg_node_rank* d_rank, u64 stage, u64* d_n) {
-        return launch_rank_select(e, ns, e->grank, e->rd_stream, e->cur, k, min_share, d_out, d_rank, nullptr, stage, d_n);
-    }, out, rank_out, e->grank.stage, node_index, cap, n_selected, n_nodes);
+    return rank_top(e, workload_space(e), "sg_window_group_rank_top", k, min_share, out, rank_out, node_index, cap, n_selected, n_nodes);
 }
 int sg_window_group_rank_select(sg_handle e, uint32_t k, float min_share, sg_node_out* d_out, uint32_t* d_index, size_t cap, uint64_t* d_n,
                                 void* stream) {
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const int slot = ran_slot(e);
-    if (const int rc = check_grsel(e, slot)) return rc;
-    const NodeSpace ns = workload_space(e);
-    if (const int rc = nsel_reserve(e, ns)) return rc;
-    return launch_rank_select(e, ns, e->grank, pick_ran(e, stream), slot, k, min_share, d_out, nullptr, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return rank_select(e, workload_space(e), k, min_share, d_out, d_index, cap, d_n, stream);
 }
 
-// ---- K18, the workload incidents ---------------------------------------------------------------------------------------------------
+// ---- K18, the workload incidents: K12's code over the workload space -------------------------------------------------------------------
 int sg_set_group_incidents(sg_handle e, const sg_incident_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->gnodes.on) { e->err = "sg_set_group_incidents: the workload rows are off (sg_set_group_nodes)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_group_incidents while a flush is open"; return SG_ESTATE; }
-    sg_incident_params q{};
-    if (p && sgplan::check_incidents(*p, &q)) { e->err = "sg_set_group_incidents: bad parameters"; return SG_EINVAL; }
-    if (p && q.by != SG_SEL_SCORE && !e->gtrend.on) { e->err = "sg_set_group_incidents by a trend key: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
-    free_group_incidents(e);
-    if (!p) return SG_OK;
-    sg_engine::GroupIncidents& x = e->ginc;
-    const u32 slots = (u32)e->slots.size();
-    x.p = q;
-    x.plan = sgplan::plan_group_incidents(e->cfg.max_edges, e->gnodes.plan.nc, e->gnodes.plan.gk, slots);
-    const sgplan::GroupIncidentPlan& P = x.plan;
-    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
-    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_group_incidents", [e] { free_group_incidents(e); })) return rc;
-    x.keys = at<K12Keys>(x.mem, P.keys_off);
-    x.pos = at<u32>(x.mem, P.pos_off);
-    x.parent = at<u32>(x.mem, P.node_off[0]); x.flag = at<u32>(x.mem, P.node_off[1]); x.lab = at<u32>(x.mem, P.node_off[2]);
-    x.num = at<u32>(x.mem, P.node_off[3]);
-    x.esrc = at<u32>(x.mem, P.esrc_off);
-    x.blk = at<u32>(x.mem, P.blk_off);
-    x.stage = at<u32>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
-    for (u32 k = 0; k < slots; k++) {
-        char* s = x.mem + P.slot.off + k * P.slot.bytes;
-        x.rows.push_back(at<sg_incident_out>(s, P.slot_rows)); x.count.push_back(at<u64>(s, P.slot_count));
-        x.node_inc.push_back(at<u32>(s, P.slot_node_inc));
-    }
-    x.valid.assign(slots, 0);
-    x.on = true;
-    return SG_OK;
+    return incidents_set(e, workload_space(e), "sg_set_group_incidents", e->ginc, p,
+                         [e](u32 slots) { return sgplan::plan_group_incidents(e->cfg.max_edges, e->gnodes.plan.nc, e->gnodes.plan.gk, slots); },
+                         [](auto& x, const sgplan::GroupIncidentPlan& P) {
+                             x.pos = at<u32>(x.mem, P.pos_off);
+                             x.parent = at<u32>(x.mem, P.node_off[0]); x.flag = at<u32>(x.mem, P.node_off[1]); x.lab = at<u32>(x.mem, P.node_off[2]);
+                             x.num = at<u32>(x.mem, P.node_off[3]);
+                             x.esrc = at<u32>(x.mem, P.esrc_off);
+                         });
 }
 int sg_window_group_incidents(sg_handle e, sg_incident_out* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::GroupIncidents& x = e->ginc;
-    if (const int rc = stage_ready(e, x, "sg_window_group_incidents", kGroupIncidentsWords)) return rc;
-    return copy_counted(e, x.count[e->cur], x.rows[e->cur], sizeof(sg_incident_out), out, cap, n);
+    return incidents_read(e, workload_space(e), "sg_window_group_incidents", out, cap, n);
 }
 int sg_window_group_node_incident(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::GroupIncidents& x = e->ginc;
-    if (const int rc = stage_ready(e, x, "sg_window_group_node_incident", kGroupIncidentsWords)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, e->gnodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    return copy_indexed(e, (const u32*)x.node_inc[e->cur], (size_t)cnt, node_index, n_index, out, cap, n, x.stage, x.stage_idx,
-                        std::max<size_t>(x.plan.nc, 1), "sg_window_group_node_incident: a node index beyond the window's workload rows");
+    return node_incident_read(e, workload_space(e), "sg_window_group_node_incident", node_index, n_index, out, cap, n);
 }
 int sg_window_group_incidents_buffer(sg_handle e, void** d_incidents, void** d_count, void** d_node_incident) {
     if (!e || !d_incidents || !d_count || !d_node_incident) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::GroupIncidents& x = e->ginc;
-    int slot;
-    if (const int rc = stage_slot(e, x, "sg_window_group_incidents_buffer", kGroupIncidentsWords, &slot)) return rc;
-    *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
-    return SG_OK;
+    return incidents_buffer(e, workload_space(e), "sg_window_group_incidents_buffer", d_incidents, d_count, d_node_incident);
 }
 
 // ---- K13, the tracks ---------------------------------------------------------------------------------------------------------------

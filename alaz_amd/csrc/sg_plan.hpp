@@ -747,23 +747,52 @@ inline int check_rank(const sg_rank_params& p, sg_rank_params* out) {
     *out = r;
     return SG_OK;
 }
-struct RankPlan {
-    u32 ncap = 0;
-    u32 ranges = 0, slices = 0;   // k11_edge's grid = ranges x slices
-    u32 prep_wgs = 0;             // k11_prep: grid-stride over max(max_edges, ncap)
-    u32 node_wgs = 0;             // k11_node: grid-stride over ncap
-    u64 row_bytes = 0;            // one per-row u32 array [max_edges] (src, dst, w: three of them)
-    u64 node_bytes = 0;           // one per-node-key u64 array [ncap] (W, R, base, t: four of them)
-    u64 part_bytes = 0;           // [ranges][slices][16384] u64
+// The ranking exists in two spaces — K11's over the node keys and K17's over the workload rows (below).  What their blocks share
+// is sized and laid out once, by plan_rank_block: four u64 arrays by node (W, R, base, t), the edge pass's partials, the seed sums,
+// the staging of the index reads and every slot's rank rows.  The grids are each plan's own: their rules differ.
+struct RankBlock {
+    u32 ranges = 0, slices = 0;   // the edge pass's grid = ranges x slices
+    u32 prep_wgs = 0;             // the prep pass: grid-stride over the rows it reads
+    u32 node_wgs = 0;             // the node pass: grid-stride over the node arrays
+    u64 node_bytes = 0;           // one per-node u64 array (W, R, base, t: four of them)
+    u64 part_bytes = 0;           // [ranges][slices][a range's nodes] u64
     u64 seed_bytes = 0;           // [1024] u64
-    u64 stage_bytes = 0;          // [ncap] sg_node_rank staging
-    u64 stage_idx_bytes = 0;      // [ncap] u32 staging
-    u64 rows_bytes = 0;           // one window slot's rank rows: [ncap] sg_node_rank
-    u64 lds_bytes = 0;            // k11_edge's dynamic LDS
+    u64 stage_bytes = 0;          // one sg_node_rank per node: staging
+    u64 stage_idx_bytes = 0;      // one u32 per node: staging
+    u64 rows_bytes = 0;           // one window slot's rank rows: one sg_node_rank per node
+    u64 lds_bytes = 0;            // the edge pass's dynamic LDS: a range of u64 accumulators
     u64 total_bytes = 0;          // the scratch, the staging and every slot's rows, each 256-byte aligned
-    u64 node_off[4] = {}, part_off = 0, seed_off = 0, row_off[3] = {}, stage_off = 0, stage_idx_off = 0;   // (node_off: W, R, base, t; row_off: src, dst, w)
+    u64 node_off[4] = {}, part_off = 0, seed_off = 0, stage_off = 0, stage_idx_off = 0;   // (node_off: W, R, base, t)
     Slots slot; u64 slot_rows = 0;
     std::vector<Piece> layout;
+};
+// r.ranges and r.slices set: the sizes over `nodes` node keys or rows in ranges of range_nodes, and the block — the node arrays, the
+// partials and the seed sums, then the plan's own per-row arrays (own(b) takes them), the staging and the slots
+template <class Own>
+inline void plan_rank_block(RankBlock& r, u64 nodes, u32 range_nodes, u32 slots, Own own) {
+    r.node_bytes = trend_align(nodes * 8);
+    r.part_bytes = trend_align((u64)r.ranges * r.slices * range_nodes * 8);
+    r.seed_bytes = trend_align((u64)kRankMaxWgs * 8);
+    r.stage_bytes = trend_align(nodes * sizeof(sg_node_rank));
+    r.stage_idx_bytes = trend_align(nodes * 4);
+    r.rows_bytes = trend_align(nodes * sizeof(sg_node_rank));
+    r.lds_bytes = (u64)range_nodes * 8;
+    Block b;
+    const char* const node[4] = {"W", "R", "base", "t"};
+    for (int k = 0; k < 4; k++) r.node_off[k] = b.take(node[k], r.node_bytes);
+    r.part_off = b.take("part", r.part_bytes);
+    r.seed_off = b.take("seed", r.seed_bytes);
+    own(b);
+    r.stage_off = b.take("stage", r.stage_bytes);
+    r.stage_idx_off = b.take("stage_idx", r.stage_idx_bytes);
+    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}});
+    r.total_bytes = b.end; r.layout = std::move(b.pieces);
+}
+struct RankPlan : RankBlock {     // (k11_edge, k11_prep over max(max_edges, ncap), k11_node over ncap)
+    typedef u32 Weight;           // an element of w
+    u32 ncap = 0;
+    u64 row_bytes = 0;            // one per-row u32 array [max_edges] (src, dst, w: three of them)
+    u64 row_off[3] = {};          // (src, dst, w)
 };
 inline RankPlan plan_rank(u64 max_edges, u32 ncap, u32 slots) {
     RankPlan r;
@@ -775,24 +804,10 @@ inline RankPlan plan_rank(u64 max_edges, u32 ncap, u32 slots) {
     r.prep_wgs = (u32)std::max<u64>(1, std::min<u64>(kRankMaxWgs, (std::max(ME, NC) + 4 * kRankThreads - 1) / (4 * kRankThreads)));
     r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kRankMaxWgs, (NC + kRankThreads - 1) / kRankThreads));
     r.row_bytes = trend_align(ME * 4);
-    r.node_bytes = trend_align(NC * 8);
-    r.part_bytes = trend_align((u64)r.ranges * r.slices * kRankRangeNodes * 8);
-    r.seed_bytes = trend_align((u64)kRankMaxWgs * 8);
-    r.stage_bytes = trend_align(NC * sizeof(sg_node_rank));
-    r.stage_idx_bytes = trend_align(NC * 4);
-    r.rows_bytes = trend_align(NC * sizeof(sg_node_rank));
-    r.lds_bytes = (u64)kRankRangeNodes * 8;
-    Block b;
-    const char* const node[4] = {"W", "R", "base", "t"};
-    const char* const row[3] = {"src", "dst", "w"};
-    for (int k = 0; k < 4; k++) r.node_off[k] = b.take(node[k], r.node_bytes);
-    r.part_off = b.take("part", r.part_bytes);
-    r.seed_off = b.take("seed", r.seed_bytes);
-    for (int k = 0; k < 3; k++) r.row_off[k] = b.take(row[k], r.row_bytes);
-    r.stage_off = b.take("stage", r.stage_bytes);
-    r.stage_idx_off = b.take("stage_idx", r.stage_idx_bytes);
-    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}});
-    r.total_bytes = b.end; r.layout = std::move(b.pieces);
+    plan_rank_block(r, NC, kRankRangeNodes, slots, [&r](Block& b) {
+        const char* const row[3] = {"src", "dst", "w"};
+        for (int k = 0; k < 3; k++) r.row_off[k] = b.take(row[k], r.row_bytes);
+    });
     return r;
 }
 
@@ -811,28 +826,30 @@ inline int check_incidents(const sg_incident_params& p, sg_incident_params* out)
     *out = p;
     return SG_OK;
 }
-struct IncidentPlan {
-    u32 ncap = 0;
-    u32 node_wgs = 0, node_per = 0;   // k12_label / k12_number: workgroups, node rows per workgroup (a multiple of 256)
-    u32 grid_wgs = 0;             // k12_init, k12_nodes, k12_finish: grid-stride over ncap
-    u32 hook_wgs = 0;             // k12_hook: grid-stride over max_edges
-    u32 row_wgs = 0;              // k12_rows: grid-stride over max_edges (and ncap)
-    u64 key_bytes = 0;            // one per-node-key u32 array [ncap] (parent, flag, lab, num, kinc: five of them)
-    u64 keys_bytes = 0;           // [ncap] x 24 bytes: the max fields' keys per incident
+// The incidents exist in two spaces — K12's over the node keys and K18's over the workload rows (below).  What their plans share
+// is sized and laid out once, by plan_incident_block: the grids but the *_nodes pass's, the max fields' keys by incident, the head
+// counts, the staging of the index reads and every slot's incident rows, count and incident per node.
+struct IncidentBlock {
+    u32 node_wgs = 0, node_per = 0;   // the label / number passes: workgroups, nodes per workgroup (a multiple of 256)
+    u32 grid_wgs = 0;             // the init and finish passes (and k12_nodes): grid-stride over the nodes
+    u32 hook_wgs = 0;             // the hook pass: grid-stride over max_edges
+    u32 row_wgs = 0;              // the rows pass: grid-stride over max_edges (and the nodes)
+    u64 keys_bytes = 0;           // one node x 24 bytes: the max fields' keys per incident
     u64 blk_bytes = 0;            // [2][1024] u32
-    u64 stage_bytes = 0;          // [ncap] u32 staging, and [ncap] u32 for the index (two of them)
-    u64 rows_bytes = 0;           // one window slot's incidents: [ncap] sg_incident_out
+    u64 stage_bytes = 0;          // one u32 per node: staging, and as much for the index (two of them)
+    u64 rows_bytes = 0;           // one window slot's incidents: one sg_incident_out per node
     u64 count_bytes = 0;          // one window slot's incident count (u64)
-    u64 node_inc_bytes = 0;       // one window slot's incident per node row: [ncap] u32
+    u64 node_inc_bytes = 0;       // one window slot's incident per node: one u32 each
     u64 total_bytes = 0;          // the scratch, the staging and every slot's buffers, each 256-byte aligned
-    u64 keys_off = 0, key_off[5] = {}, blk_off = 0, stage_off = 0, stage_idx_off = 0;   // (key_off: parent, flag, lab, num, kinc)
+    u64 keys_off = 0, blk_off = 0, stage_off = 0, stage_idx_off = 0;
     Slots slot; u64 slot_rows = 0, slot_count = 0, slot_node_inc = 0;
     std::vector<Piece> layout;
 };
-inline IncidentPlan plan_incidents(u64 max_edges, u32 ncap, u32 slots) {
-    IncidentPlan r;
-    const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(ncap, 1);
-    r.ncap = ncap;
+// the grids and sizes over `nodes` node keys or rows, and the block: the keys, then the plan's own per-node and per-edge arrays
+// (own(b) takes them), the head counts, the staging and the slots
+template <class Own>
+inline void plan_incident_block(IncidentBlock& r, u64 max_edges, u64 nodes, u32 slots, Own own) {
+    const u64 ME = std::max<u64>(max_edges, 1), NC = nodes;
     r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kIncMaxWgs, (NC + kIncThreads - 1) / kIncThreads));
     const u64 per = (NC + r.node_wgs - 1) / r.node_wgs;
     r.node_per = (u32)((per + kIncThreads - 1) / kIncThreads * kIncThreads);
@@ -841,7 +858,6 @@ inline IncidentPlan plan_incidents(u64 max_edges, u32 ncap, u32 slots) {
     const u64 row_blocks = (ME + (u64)kIncRowsPerThread * kIncThreads - 1) / ((u64)kIncRowsPerThread * kIncThreads);
     r.hook_wgs = (u32)std::max<u64>(1, std::min<u64>(kIncMaxWgs, row_blocks));
     r.row_wgs = (u32)std::max<u64>(1, std::min<u64>(kIncMaxRowWgs, row_blocks));
-    r.key_bytes = trend_align(NC * 4);
     r.keys_bytes = trend_align(NC * kIncKeysBytes);
     r.blk_bytes = trend_align(2ull * kIncMaxWgs * 4);
     r.stage_bytes = trend_align(NC * 4);
@@ -849,14 +865,28 @@ inline IncidentPlan plan_incidents(u64 max_edges, u32 ncap, u32 slots) {
     r.count_bytes = trend_align(8);
     r.node_inc_bytes = trend_align(NC * 4);
     Block b;
-    const char* const key[5] = {"parent", "flag", "lab", "num", "kinc"};
     r.keys_off = b.take("keys", r.keys_bytes);
-    for (int k = 0; k < 5; k++) r.key_off[k] = b.take(key[k], r.key_bytes);
+    own(b);
     r.blk_off = b.take("blk", r.blk_bytes);
     r.stage_off = b.take("stage", r.stage_bytes); r.stage_idx_off = b.take("stage_idx", r.stage_bytes);
     r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}, {"count", r.count_bytes, &r.slot_count},
                              {"node_inc", r.node_inc_bytes, &r.slot_node_inc}});
     r.total_bytes = b.end; r.layout = std::move(b.pieces);
+}
+struct IncidentPlan : IncidentBlock {
+    u32 ncap = 0;
+    u64 key_bytes = 0;            // one per-node-key u32 array [ncap] (parent, flag, lab, num, kinc: five of them)
+    u64 key_off[5] = {};          // (parent, flag, lab, num, kinc)
+};
+inline IncidentPlan plan_incidents(u64 max_edges, u32 ncap, u32 slots) {
+    IncidentPlan r;
+    const u64 NC = std::max<u32>(ncap, 1);
+    r.ncap = ncap;
+    r.key_bytes = trend_align(NC * 4);
+    plan_incident_block(r, max_edges, NC, slots, [&r](Block& b) {
+        const char* const key[5] = {"parent", "flag", "lab", "num", "kinc"};
+        for (int k = 0; k < 5; k++) r.key_off[k] = b.take(key[k], r.key_bytes);
+    });
     return r;
 }
 
@@ -1117,27 +1147,16 @@ inline NodeSelPlan plan_group_node_select(u32 nc, u64 counter_bytes) { return pl
 constexpr u32 kGrpRankThreads = 256, kGrpRankRangeRows = 8192, kGrpRankSliceEdges = 2048, kGrpRankMaxSlices = 256, kGrpRankMaxWgs = 1024,
               kGrpRankNodeRows = 32;
 constexpr u64 kGrpRankPartBudget = 128ull << 20;
-struct GroupRankPlan {
+static_assert(kGrpRankMaxWgs == kRankMaxWgs, "plan_rank_block sizes the seed sums of both rankings");
+struct GroupRankPlan : RankBlock {    // (k17_edge, k17_prep over max_edges, k17_node in blocks of 32 rows over nc)
+    typedef unsigned long long Weight;   // an element of w (64 bits, as the device code spells them)
     u32 nc = 0;                   // workload rows per window slot (GroupNodesPlan::nc)
     u64 gk = 0;                   // group keys (GroupNodesPlan::gk)
-    u32 ranges = 0, slices = 0;   // k17_edge's grid = ranges x slices
     u32 pos_wgs = 0;              // k17_pos: grid-stride over nc
-    u32 prep_wgs = 0;             // k17_prep: grid-stride over max_edges
-    u32 node_wgs = 0;             // k17_node: blocks of 32 rows, grid-stride over nc
     u64 pos_bytes = 0;            // [gk] u32 row position by group key
     u64 edge_bytes = 0;           // one per-group-edge u32 array [max_edges] (src, dst: two of them)
     u64 w_bytes = 0;              // [max_edges] u64 weights
-    u64 node_bytes = 0;           // one per-row u64 array [nc] (W, R, base, t: four of them)
-    u64 part_bytes = 0;           // [ranges][slices][8192] u64
-    u64 seed_bytes = 0;           // [1024] u64
-    u64 stage_bytes = 0;          // [nc] sg_node_rank staging
-    u64 stage_idx_bytes = 0;      // [nc] u32 staging
-    u64 rows_bytes = 0;           // one window slot's rank rows: [nc] sg_node_rank
-    u64 lds_bytes = 0;            // k17_edge's dynamic LDS
-    u64 total_bytes = 0;          // the scratch, the staging and every slot's rows, each 256-byte aligned
-    u64 node_off[4] = {}, part_off = 0, seed_off = 0, pos_off = 0, edge_off[2] = {}, w_off = 0, stage_off = 0, stage_idx_off = 0;   // (node_off: W, R, base, t; edge_off: src, dst)
-    Slots slot; u64 slot_rows = 0;
-    std::vector<Piece> layout;
+    u64 pos_off = 0, edge_off[2] = {}, w_off = 0;   // (edge_off: src, dst)
 };
 // the workgroups of k17_edge that work on a window of n rows (the others exit at once)
 inline u32 group_rank_live_wgs(const GroupRankPlan& r, u64 n) {
@@ -1156,26 +1175,12 @@ inline GroupRankPlan plan_group_rank(u64 max_edges, u32 nc, u64 gk, u32 slots) {
     r.pos_bytes = trend_align(GK * 4);
     r.edge_bytes = trend_align(ME * 4);
     r.w_bytes = trend_align(ME * 8);
-    r.node_bytes = trend_align(NC * 8);
-    r.part_bytes = trend_align((u64)r.ranges * r.slices * kGrpRankRangeRows * 8);
-    r.seed_bytes = trend_align((u64)kGrpRankMaxWgs * 8);
-    r.stage_bytes = trend_align(NC * sizeof(sg_node_rank));
-    r.stage_idx_bytes = trend_align(NC * 4);
-    r.rows_bytes = trend_align(NC * sizeof(sg_node_rank));
-    r.lds_bytes = (u64)kGrpRankRangeRows * 8;
-    Block b;
-    const char* const node[4] = {"W", "R", "base", "t"};
-    const char* const edge[2] = {"src", "dst"};
-    for (int k = 0; k < 4; k++) r.node_off[k] = b.take(node[k], r.node_bytes);
-    r.part_off = b.take("part", r.part_bytes);
-    r.seed_off = b.take("seed", r.seed_bytes);
-    r.pos_off = b.take("pos", r.pos_bytes);
-    for (int k = 0; k < 2; k++) r.edge_off[k] = b.take(edge[k], r.edge_bytes);
-    r.w_off = b.take("w", r.w_bytes);
-    r.stage_off = b.take("stage", r.stage_bytes);
-    r.stage_idx_off = b.take("stage_idx", r.stage_idx_bytes);
-    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}});
-    r.total_bytes = b.end; r.layout = std::move(b.pieces);
+    plan_rank_block(r, NC, kGrpRankRangeRows, slots, [&r](Block& b) {
+        const char* const edge[2] = {"src", "dst"};
+        r.pos_off = b.take("pos", r.pos_bytes);
+        for (int k = 0; k < 2; k++) r.edge_off[k] = b.take(edge[k], r.edge_bytes);
+        r.w_off = b.take("w", r.w_bytes);
+    });
     return r;
 }
 
@@ -1192,29 +1197,17 @@ inline GroupRankPlan plan_group_rank(u64 max_edges, u32 nc, u64 gk, u32 slots) {
 // form.  Config 3's engine (max_edges 1.25 M, GK = NC = 30 000, two slots): 10.6 MiB in all — 4.8 MiB of esrc, 2 x 2.2 MiB of
 // incident rows and node_inc, 0.7 MiB of keys, 0.8 MiB for pos, the four row arrays and the staging.  At K16's limit (2^21 keys,
 // max_edges 4 M, two slots) it is 430 MiB, 288 of them the two slots' [NC] incident rows.
-constexpr u32 kGrpIncThreads = 256, kGrpIncMaxWgs = 1024, kGrpIncMaxRowWgs = 256, kGrpIncRowsPerThread = 4, kGrpIncFoldRounds = 8,
-              kGrpIncSlots = 512;
-struct GroupIncidentPlan {
+constexpr u32 kGrpIncThreads = 256, kGrpIncMaxWgs = 1024, kGrpIncMaxRowWgs = 256, kGrpIncFoldRounds = 8, kGrpIncSlots = 512;
+static_assert(kGrpIncThreads == kIncThreads && kGrpIncMaxWgs == kIncMaxWgs && kGrpIncMaxRowWgs == kIncMaxRowWgs,
+              "plan_incident_block sizes the grids of both groupings");
+struct GroupIncidentPlan : IncidentBlock {
     u32 nc = 0;                   // workload rows per window slot (GroupNodesPlan::nc)
     u64 gk = 0;                   // group keys (GroupNodesPlan::gk)
-    u32 node_wgs = 0, node_per = 0;   // k18_label / k18_number: workgroups, rows per workgroup (a multiple of 256)
-    u32 grid_wgs = 0;             // k18_init, k18_finish: grid-stride over nc
     u32 fold_wgs = 0;             // k18_nodes: grid-stride over nc, kGrpIncFoldRounds rounds a workgroup
-    u32 hook_wgs = 0;             // k18_hook: grid-stride over max_edges
-    u32 row_wgs = 0;              // k18_rows: grid-stride over max_edges (and nc)
     u64 pos_bytes = 0;            // [gk] u32 row position by group key
     u64 node_bytes = 0;           // one per-row u32 array [nc] (parent, flag, lab, num: four of them)
     u64 esrc_bytes = 0;           // [max_edges] u32
-    u64 keys_bytes = 0;           // [nc] x 24 bytes: the max fields' keys per incident
-    u64 blk_bytes = 0;            // [2][1024] u32
-    u64 stage_bytes = 0;          // [nc] u32 staging, and [nc] u32 for the index (two of them)
-    u64 rows_bytes = 0;           // one window slot's incidents: [nc] sg_incident_out
-    u64 count_bytes = 0;          // one window slot's incident count (u64)
-    u64 node_inc_bytes = 0;       // one window slot's incident per workload row: [nc] u32
-    u64 total_bytes = 0;          // the scratch, the staging and every slot's buffers, each 256-byte aligned
-    u64 keys_off = 0, pos_off = 0, node_off[4] = {}, esrc_off = 0, blk_off = 0, stage_off = 0, stage_idx_off = 0;   // (node_off: parent, flag, lab, num)
-    Slots slot; u64 slot_rows = 0, slot_count = 0, slot_node_inc = 0;
-    std::vector<Piece> layout;
+    u64 pos_off = 0, node_off[4] = {}, esrc_off = 0;   // (node_off: parent, flag, lab, num)
 };
 // the distinct incidents one workgroup of k18_nodes / k18_rows can meet in a window of n workload rows that are all their own
 // incident's pair (rows 2i, 2i + 1) / of g group edges each an incident of its own: what the workgroup strides over
@@ -1224,36 +1217,17 @@ inline GroupIncidentPlan plan_group_incidents(u64 max_edges, u32 nc, u64 gk, u32
     GroupIncidentPlan r;
     const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(nc, 1), GK = std::max<u64>(gk, 1);
     r.nc = nc; r.gk = gk;
-    r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxWgs, (NC + kGrpIncThreads - 1) / kGrpIncThreads));
-    const u64 per = (NC + r.node_wgs - 1) / r.node_wgs;
-    r.node_per = (u32)((per + kGrpIncThreads - 1) / kGrpIncThreads * kGrpIncThreads);
-    r.node_wgs = (u32)((NC + r.node_per - 1) / r.node_per);
-    r.grid_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxWgs, (NC + kGrpIncThreads - 1) / kGrpIncThreads));
     const u64 fold_rows = (u64)kGrpIncFoldRounds * kGrpIncThreads;
     r.fold_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxWgs, (NC + fold_rows - 1) / fold_rows));
-    const u64 row_blocks = (ME + (u64)kGrpIncRowsPerThread * kGrpIncThreads - 1) / ((u64)kGrpIncRowsPerThread * kGrpIncThreads);
-    r.hook_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxWgs, row_blocks));
-    r.row_wgs = (u32)std::max<u64>(1, std::min<u64>(kGrpIncMaxRowWgs, row_blocks));
     r.pos_bytes = trend_align(GK * 4);
     r.node_bytes = trend_align(NC * 4);
     r.esrc_bytes = trend_align(ME * 4);
-    r.keys_bytes = trend_align(NC * kIncKeysBytes);
-    r.blk_bytes = trend_align(2ull * kGrpIncMaxWgs * 4);
-    r.stage_bytes = trend_align(NC * 4);
-    r.rows_bytes = trend_align(NC * sizeof(sg_incident_out));
-    r.count_bytes = trend_align(8);
-    r.node_inc_bytes = trend_align(NC * 4);
-    Block b;
-    const char* const node[4] = {"parent", "flag", "lab", "num"};
-    r.keys_off = b.take("keys", r.keys_bytes);
-    r.pos_off = b.take("pos", r.pos_bytes);
-    for (int k = 0; k < 4; k++) r.node_off[k] = b.take(node[k], r.node_bytes);
-    r.esrc_off = b.take("esrc", r.esrc_bytes);
-    r.blk_off = b.take("blk", r.blk_bytes);
-    r.stage_off = b.take("stage", r.stage_bytes); r.stage_idx_off = b.take("stage_idx", r.stage_bytes);
-    r.slot = b.slots(slots, {{"rows", r.rows_bytes, &r.slot_rows}, {"count", r.count_bytes, &r.slot_count},
-                             {"node_inc", r.node_inc_bytes, &r.slot_node_inc}});
-    r.total_bytes = b.end; r.layout = std::move(b.pieces);
+    plan_incident_block(r, max_edges, NC, slots, [&r](Block& b) {
+        const char* const node[4] = {"parent", "flag", "lab", "num"};
+        r.pos_off = b.take("pos", r.pos_bytes);
+        for (int k = 0; k < 4; k++) r.node_off[k] = b.take(node[k], r.node_bytes);
+        r.esrc_off = b.take("esrc", r.esrc_bytes);
+    });
     return r;
 }
 
