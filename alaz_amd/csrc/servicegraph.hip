@@ -180,9 +180,13 @@ struct sg_engine {
     Rollup<sgplan::NodesPlan> nodes;
     // K10, the per-node baselines (sg_node_trend.h): a Baseline, freed with the rollup
     Baseline<sg_node_trend> ntrend;
-    // node selection (K7 over node rows): scratch of plan_select(ncap) allocated at the first one, with the counter block k10_keys
-    // fills, an index array and the host form's row staging (ncap each), in a block of its own (mem).
-    struct NSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; sg_node_out* stage = nullptr; char* mem = nullptr; } nsel;
+    // An index selection (K7 over rows that are not the edge rows; sg_plan.hpp plan_index_select): K7's scratch over the space's row
+    // capacity, allocated at the first one, with the counter block the key pass fills, an index array and the host form's staging
+    // of stage_rows rows, in a block of its own (mem).  nsel: over the node rows (plan_node_select, every row staged).
+    template <class Row>
+    struct IdxSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; Row* stage = nullptr; char* mem = nullptr; u64 stage_rows = 0; };
+    using NSel = IdxSel<sg_node_out>;
+    NSel nsel;
     // The ranking (sg_rank.h), K11's over the node rows (rank, sg_plan.hpp plan_rank) or K17's over the workload rows (grank,
     // plan_group_rank; sg_group_rank.h): allocated at sg_set_rank / sg_set_group_rank, one allocation, freed with its rollup.  The
     // per-edge and per-node arrays and the partials (K17: and the position table pos, null in K11) are scratch shared by the window
@@ -233,9 +237,8 @@ struct sg_engine {
     // list, allocated at sg_set_group_trend / sg_set_group_vanished, freed with the groups
     Baseline<sg_edge_trend> gtrend;
     Vanished gvanished;
-    // selection over group edges (K7 over K14's rows): plan_group_select's block, allocated at the first one — K7's scratch over
-    // max_edges keys, the counter block k15_keys fills, an index array and the host form's staging of SG_SELECT_MAX_K group edges
-    struct GSel : SelScratch { u64* ctr = nullptr; u32* idx = nullptr; sg_group_edge* stage = nullptr; char* mem = nullptr; u64 stage_rows = 0; } gsel;
+    // selection over group edges (K7 over K14's rows): plan_group_select's block — max_edges keys, a staging of SG_SELECT_MAX_K group edges
+    IdxSel<sg_group_edge> gsel;
     // K16, the workload rows: the rollup over the group keys, freed with the groups
     Rollup<sgplan::GroupNodesPlan> gnodes;
     // its baseline (K10's walk under workload keys), allocated at sg_set_group_node_trend, and the selection over workload rows:
@@ -738,6 +741,7 @@ void free_stage(X& x) {
 // how a stage's messages name it: "<call>: <off>" and "... was closed while <was>"
 struct StageWords { const char* off; const char* was; };
 constexpr StageWords kNodesWords{"the node rollup is off (sg_set_nodes)", "the node rollup was off"};
+constexpr StageWords kTrendWords{"the trend is off (sg_set_trend)", "the trend was off"};   // (K8 keeps no valid: no message says "was")
 constexpr StageWords kVanishedWords{"the vanished list is off (sg_set_vanished)", "the vanished list was off"};
 constexpr StageWords kNodeTrendWords{"the node trend is off (sg_set_node_trend)", "the node trend was off"};
 constexpr StageWords kRankWords{"the ranking is off (sg_set_rank)", "the ranking was off"};
@@ -766,13 +770,21 @@ struct NodeSpace {
 };
 NodeSpace node_space(sg_engine* e) {
     return {&e->nodes, &e->ntrend, &e->nsel, e->plan.ncap, kNodesWords, kNodeTrendWords, "node selection", "nodes",
-            &e->rank, &e->inc, free_incidents, kRankWords, kIncidentsWords, "rank selection", &e->trend, "the trend is off (sg_set_trend)"};
+            &e->rank, &e->inc, free_incidents, kRankWords, kIncidentsWords, "rank selection", &e->trend, kTrendWords.off};
 }
 NodeSpace workload_space(sg_engine* e) {
     return {&e->gnodes, &e->gntrend, &e->gnsel, e->gnodes.plan.nc, kGroupNodesWords, kGroupNodeTrendWords, "workload selection", "workload rows",
             &e->grank, &e->ginc, free_group_incidents, kGroupRankWords, kGroupIncidentsWords, "workload rank selection", &e->gtrend,
             kGroupTrendWords.off};
 }
+// An edge space: what an edge baseline, its vanished list and their readbacks work on — the service map's edges (K8) or K14's group
+// edges (K15).  Its baseline, its list, how their messages name them, and the node space over it: the one whose incidents may key
+// a trend row of this baseline (drop_incidents).  The calls' own names come from the entry points, as the node spaces' do.
+struct EdgeSpace {
+    sg_engine::Baseline<sg_edge_trend>* trend; sg_engine::Vanished* van; StageWords trend_w, van_w; NodeSpace (*nodes)(sg_engine*);
+};
+EdgeSpace edge_space(sg_engine* e) { return {&e->trend, &e->vanished, kTrendWords, kVanishedWords, node_space}; }
+EdgeSpace group_edge_space(sg_engine* e) { return {&e->gtrend, &e->gvanished, kGroupTrendWords, kGroupVanishedWords, workload_space}; }
 
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
 static_assert(sizeof(KcScratch) <= sgplan::kPrepareLds, "a folded close's prepare workgroup lays KcScratch over pass B's dynamic LDS");
@@ -807,26 +819,35 @@ VanArgs vanished_args(const sg_engine::Vanished& v, int slot) {
     va.max_rows = v.plan.rows; va.silent = v.p.silent_windows; va.min_seen = v.p.min_seen;
     return va;
 }
-// enqueue window w's update on stream s; the window's trend rows go to the slot's buffer
-int launch_trend(sg_engine* e, hipStream_t s) {
-    sg_engine::WinSlot& w = work(e);
-    sg_engine::Baseline<sg_edge_trend>& t = e->trend;
-    TrendArgs a = baseline_args(w, t);
-    a.rows = w.d.rows; a.max_edges = e->cfg.max_edges; a.out = t.rows[e->cur];
-    sg_engine::Vanished& v = e->vanished;
+// enqueue the update of edge space es's baseline by the window in slot cur on stream s: three plain launches, the source's count
+// and write around k8_scan on ta, the TrendArgs inside the argument a; with the list on their _v forms, which also make the
+// slot's vanished list
+template <class Args>
+int launch_edge_trend(sg_engine* e, const EdgeSpace& es, hipStream_t s, const Args& a, const TrendArgs& ta, void (*count)(Args),
+                      void (*write)(Args), void (*count_v)(Args, VanArgs), void (*write_v)(Args, VanArgs)) {
+    sg_engine::Baseline<sg_edge_trend>& t = *es.trend;
+    sg_engine::Vanished& v = *es.van;
     return enqueue_baseline(e, t, s, [&] {
         if (v.on) {                                                   // the same three launches with the vanished count
             const VanArgs va = vanished_args(v, e->cur);
-            hipLaunchKernelGGL(k8_count_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
-            hipLaunchKernelGGL(k8_scan_v, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs, va);
-            hipLaunchKernelGGL(k8_write_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
+            hipLaunchKernelGGL(count_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
+            hipLaunchKernelGGL(k8_scan_v, dim3(1), dim3(K8_SCAN_THREADS), 0, s, ta, t.plan.wgs, va);
+            hipLaunchKernelGGL(write_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
             v.valid[e->cur] = 1;
         } else {
-            hipLaunchKernelGGL(k8_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-            hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a, t.plan.wgs);
-            hipLaunchKernelGGL(k8_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, ta, t.plan.wgs);
+            hipLaunchKernelGGL(write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
         }
     });
+}
+// K8: window w's rows against the per-edge baseline; the window's trend rows go to the slot's buffer.  (K8 keeps no valid: its two
+// reads check none, sg_window_trend / sg_window_trend_buffer.)
+int launch_trend(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
+    TrendArgs a = baseline_args(w, e->trend);
+    a.rows = w.d.rows; a.max_edges = e->cfg.max_edges; a.out = e->trend.rows[e->cur];
+    return launch_edge_trend(e, edge_space(e), s, a, a, k8_count, k8_write, k8_count_v, k8_write_v);
 }
 // ---- K9, the node rollup (engine lock held) ---------------------------------------------------------------------------------
 static_assert(sgplan::kNodesThreads == K9_THREADS && sgplan::kNodesChunk == K9_CHUNK && sgplan::kNodesRangeNodes == K9_IN_NR &&
@@ -1053,26 +1074,12 @@ static_assert(sizeof(sg_edge_trend) == 16 && sizeof(sg_group_edge) == 80 && offs
 // enqueue the workload baseline's update by the window in slot cur on stream s (behind its contraction, on the same stream); the
 // window's group trend rows go to the slot's buffer, with the list on also its vanished workload dependencies
 int launch_group_trend(sg_engine* e, hipStream_t s) {
-    sg_engine::WinSlot& w = work(e);
     sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
-    sg_engine::Vanished& v = e->gvanished;
     GroupTrendArgs a{};
-    a.t = baseline_args(w, t);
+    a.t = baseline_args(work(e), t);
     a.groups = e->grp.rows[e->cur]; a.count = e->grp.count[e->cur]; a.max_edges = std::max<u64>(e->cfg.max_edges, 1); a.out = t.rows[e->cur];
-    if (const int rc = enqueue_baseline(e, t, s, [&] {
-            if (v.on) {
-                const VanArgs va = vanished_args(v, e->cur);
-                hipLaunchKernelGGL(k15_count_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
-                hipLaunchKernelGGL(k8_scan_v, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs, va);
-                hipLaunchKernelGGL(k15_write_v, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a, va);
-                v.valid[e->cur] = 1;
-            } else {
-                hipLaunchKernelGGL(k15_count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-                hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.t, t.plan.wgs);
-                hipLaunchKernelGGL(k15_write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
-            }
-        })) return rc;
-    t.valid[e->cur] = 1;
+    if (const int rc = launch_edge_trend(e, group_edge_space(e), s, a, a.t, k15_count, k15_write, k15_count_v, k15_write_v)) return rc;
+    t.valid[e->cur] = 1;                                              // (K15's reads check it, stage_ready / stage_slot; K8 keeps none)
     return SG_OK;
 }
 // a vanished list off (K8's or K15's): it has no event of its own, its baseline's — not free_stage
@@ -1080,9 +1087,10 @@ void free_list(sg_engine::Vanished& v) {
     if (v.mem) { hipDeviceSynchronize(); hipFree(v.mem); }
     v = sg_engine::Vanished{};
 }
-void free_group_trend(sg_engine* e) {
-    free_list(e->gvanished);
-    free_baseline(e->gtrend);
+// an edge space's baseline off, its list first
+void free_edge_trend(const EdgeSpace& es) {
+    free_list(*es.van);
+    free_baseline(*es.trend);
 }
 
 // ---- K16, the workload rows (engine lock held) -------------------------------------------------------------------------------------
@@ -1135,25 +1143,26 @@ int launch_group_incidents(sg_engine* e, hipStream_t s) {
     return launch_grouping(e, workload_space(e), P, s, a, a.g.nd, P.fold_wgs, k18_init, k18_hook, k18_label, k18_number, k18_nodes, k18_rows, k18_finish);
 }
 void free_group_incidents(sg_engine* e) { free_stage(e->ginc); }
-// a selection scratch block off (the workload rows': its sizes are the stage's)
-void free_nsel(sg_engine::NSel& s) {
+// an index selection's block off (the workload rows': its sizes are the stage's; every one at sg_destroy)
+template <class Row>
+void free_idxsel(sg_engine::IdxSel<Row>& s) {
     if (s.mem || s.h_n) hipDeviceSynchronize();
     if (s.mem) hipFree(s.mem);
     if (s.h_n) hipHostFree(s.h_n);
     if (s.ev) hipEventDestroy(s.ev);
-    s = sg_engine::NSel{};
+    s = sg_engine::IdxSel<Row>{};
 }
 void free_group_nodes(sg_engine* e) {
     free_group_incidents(e);
     free_group_rank(e);
-    free_nsel(e->gnsel);
+    free_idxsel(e->gnsel);
     free_baseline(e->gntrend);
     free_stage(e->gnodes);
 }
 
 void free_groups(sg_engine* e) {
     free_group_nodes(e);
-    free_group_trend(e);
+    free_edge_trend(group_edge_space(e));
     sg_engine::Groups& x = e->grp;
     if (x.mem) hipDeviceSynchronize();                                // (an upload may still read h_up)
     if (x.h_up) hipHostFree(x.h_up);
@@ -1173,14 +1182,10 @@ void free_nodes(sg_engine* e) {
     free_stage(e->nodes);
 }
 
-void free_vanished(sg_engine* e) { free_list(e->vanished); }
-
-// an edge baseline switched off (or failing to come on) takes its space's incidents with it when their key is a trend row's
-void drop_incidents(sg_engine* e, const NodeSpace& ns) { if (ns.inc->on && ns.inc->p.by != SG_SEL_SCORE) ns.inc_off(e); }
-
-void free_trend(sg_engine* e) {
-    free_vanished(e);
-    free_baseline(e->trend);
+// an edge baseline switched off (or failing to come on) takes the incidents of the node space over it with it when their key is a trend row's
+void drop_incidents(sg_engine* e, const EdgeSpace& es) {
+    const NodeSpace ns = es.nodes(e);
+    if (ns.inc->on && ns.inc->p.by != SG_SEL_SCORE) ns.inc_off(e);
 }
 
 // proj_done: the last SAGE layer already wrote P and Q.  fuse_reset: fold the window reset into the
@@ -1381,164 +1386,148 @@ int launch_select(sg_engine* e, hipStream_t st, SelArgs a, u32 k, float min_scor
     return SG_OK;
 }
 
-// ---- node selection (engine lock held) ------------------------------------------------------------------------------------------
-// the scratch at the first selection over node space ns (plan_select over its row capacity, the counter block, indices and staging)
-int nsel_reserve(sg_engine* e, const NodeSpace& ns) {
-    sg_engine::NSel& s = *ns.sel;
+// ---- index selections: K7 over node rows, workload rows or group edges (engine lock held) -------------------------------------------
+// the block of s at its first selection, by plan(), its IndexSelPlan: K7's scratch over the row capacity, the counter block, indices, staging
+template <class Row, class MakePlan>
+int idxsel_reserve(sg_engine* e, sg_engine::IdxSel<Row>& s, MakePlan plan) {
     if (s.keys) return SG_OK;
-    const sgplan::NodeSelPlan P = sgplan::plan_node_select(ns.cap, sizeof(e->h_ctr));
+    const sgplan::IndexSelPlan P = plan();
     s.plan = P.sel;
     HIP_TRY(e, hipMalloc((void**)&s.mem, P.total_bytes));
     HIP_TRY(e, hipMemset(s.mem, 0, P.total_bytes));
-    s.stage = at<sg_node_out>(s.mem, P.stage_off);
+    s.stage = at<Row>(s.mem, P.stage_off); s.stage_rows = P.stage_rows;
     s.ctr = at<u64>(s.mem, P.ctr_off);
     s.idx = at<u32>(s.mem, P.idx_off);
     return sel_init(e, s, s.mem + P.sel_off);
 }
-// enqueue a selection over the rows of node space v in slot `slot` on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may
-// be NULL), the count to d_n; behind that window's rollup (event) and the previous node selection.  keys(a, wgs) launches the key
-// pass (k10_keys, k11_keys) and waits for what it reads; after(a, grid) launches what else gathers by the selected indices.
-template <class Keys, class After>
-int launch_node_select(sg_engine* e, const NodeSpace& v, hipStream_t st, int slot, u32 k, float min_value, sg_node_out* d_out, u32* d_index,
-                       u64 cap, u64* d_n, Keys keys, After after) {
-    sg_engine::NSel& s = *v.sel;
+int nsel_reserve(sg_engine* e, const NodeSpace& ns) { return idxsel_reserve(e, *ns.sel, [&] { return sgplan::plan_node_select(ns.cap, sizeof(e->h_ctr)); }); }
+int gsel_reserve(sg_engine* e) { return idxsel_reserve(e, e->gsel, [&] { return sgplan::plan_group_select(e->cfg.max_edges, sizeof(e->h_ctr)); }); }
+// what an index selection reads: its scratch, the rows a window can have, the rows and the count of the window in a slot, and the
+// event of the stage that makes them (null: nothing of it in flight) — a node space's rollup, or the contraction
+template <class Row>
+struct SelView { sg_engine::IdxSel<Row>* sel; u64 cap; const Row* rows; const u64* count; hipEvent_t ev; };
+SelView<sg_node_out> node_sel_view(const NodeSpace& ns, int slot) {
+    return {ns.sel, std::max<u32>(ns.cap, 1), ns.roll->rows[slot], ns.roll->count[slot], ns.roll->pending ? ns.roll->ev : nullptr};
+}
+SelView<sg_group_edge> group_sel_view(sg_engine* e, int slot) {
+    return {&e->gsel, std::max<u64>(e->cfg.max_edges, 1), e->grp.rows[slot], e->grp.count[slot], e->grp.pending ? e->grp.ev : nullptr};
+}
+// enqueue a selection over the rows of v on stream st: indices to d_index (NULL: the scratch's), rows to d_out (may be NULL), the
+// count to d_n; behind the stage that makes the rows (event) and the previous selection on this scratch.  keys(a, wgs) launches the
+// key pass (k10_keys, k11_keys, k15_keys) and waits for what else it reads; then K7's passes with their row copies off and
+// k_gather_sel; after(a, grid) launches what else gathers by the selected indices.
+template <class Row, class Keys, class After>
+int launch_index_select(sg_engine* e, const SelView<Row>& v, hipStream_t st, u32 k, float min_value, Row* d_out, u32* d_index, u64 cap,
+                        u64* d_n, Keys keys, After after) {
+    sg_engine::IdxSel<Row>& s = *v.sel;
     const u32 wgs = s.plan.wgs;
-    const u64 NC = std::max<u32>(v.cap, 1);
     SelArgs a{};
-    a.rows = nullptr; a.ctr = s.ctr; a.max_edges = NC; a.k = k; a.min_score = min_value;
+    a.rows = nullptr; a.ctr = s.ctr; a.max_edges = v.cap; a.k = k; a.min_score = min_value;
     sel_scratch_args(a, s);
-    a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, NC); a.n_out = d_n;
+    a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, v.cap); a.n_out = d_n;
     if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
-    if (v.roll->pending) HIP_TRY(e, hipStreamWaitEvent(st, v.roll->ev, 0));
-    const sg_node_out* nodes = v.roll->rows[slot];
+    if (v.ev) HIP_TRY(e, hipStreamWaitEvent(st, v.ev, 0));
     if (const int rc = keys(a, wgs)) return rc;
-    enqueue_k7_select(st, a, k, wgs, NC);
-    const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, NC) : NC);
+    enqueue_k7_select(st, a, k, wgs, v.cap);
+    const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, v.cap) : v.cap);
     const dim3 grid((unsigned)std::max<u64>(1, std::min<u64>((m + 255) / 256, 1024)));
-    if (d_out) hipLaunchKernelGGL(k_gather_sel<sg_node_out>, grid, dim3(256), 0, st, nodes, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
+    if (d_out) hipLaunchKernelGGL(k_gather_sel<Row>, grid, dim3(256), 0, st, v.rows, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
     after(a, grid);
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, hipEventRecord(s.ev, st));
     s.pending = true;
     return SG_OK;
 }
-// by a key of SG_NSEL_*: k10_keys over the space's rows and, for a trend key, the window's trend rows (behind the baseline's update)
+// over node space ns by a key of SG_NSEL_*: k10_keys over the space's rows and, for a trend key, the window's trend rows (behind the
+// baseline's update)
 int launch_node_select_by(sg_engine* e, const NodeSpace& ns, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_node_out* d_out,
                           u32* d_index, u64 cap, u64* d_n) {
-    return launch_node_select(e, ns, st, slot, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+    const SelView<sg_node_out> v = node_sel_view(ns, slot);
+    return launch_index_select(e, v, st, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
         if (by != SG_NSEL_SCORE && ns.trend->pending) HIP_TRY(e, hipStreamWaitEvent(st, ns.trend->ev, 0));
         const sg_node_trend* tr = by != SG_NSEL_SCORE ? ns.trend->rows[slot] : nullptr;
-        hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, (const sg_node_out*)ns.roll->rows[slot], (const u64*)ns.roll->count[slot], tr, by, ns.sel->ctr);
+        hipLaunchKernelGGL(k10_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, v.rows, v.count, tr, by, v.sel->ctr);
         return (int)SG_OK;
     }, [](const SelArgs&, dim3) {});
 }
-// by the culprit rank: k11_keys over the window's rank rows of node space ns's ranking (K11 over the nodes, K17 over the workloads;
-// behind that ranking); d_rank (may be NULL) gets the selected rank rows
+// over node space ns by the culprit rank: k11_keys over the window's rank rows of the space's ranking (K11 over the nodes, K17 over
+// the workloads; behind that ranking); d_rank (may be NULL) gets the selected rank rows
 int launch_rank_select(sg_engine* e, const NodeSpace& ns, hipStream_t st, int slot, u32 k, float min_share, sg_node_out* d_out,
                        sg_node_rank* d_rank, u32* d_index, u64 cap, u64* d_n) {
     const sg_engine::RankState& r = *ns.rank;
     const sg_node_rank* rk = r.rows[slot];
-    return launch_node_select(e, ns, st, slot, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+    const SelView<sg_node_out> v = node_sel_view(ns, slot);
+    return launch_index_select(e, v, st, k, min_share, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
         if (r.pending) HIP_TRY(e, hipStreamWaitEvent(st, r.ev, 0));
-        hipLaunchKernelGGL(k11_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, rk, (const u64*)ns.roll->count[slot], ns.sel->ctr);
+        hipLaunchKernelGGL(k11_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, rk, v.count, v.sel->ctr);
         return (int)SG_OK;
     }, [&](const SelArgs& a, dim3 grid) {
         if (d_rank) hipLaunchKernelGGL(k_gather_sel<sg_node_rank>, grid, dim3(256), 0, st, rk, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_rank);
     });
 }
-// the host form of a node selection over the last read window (sg_window_nodes_top, sg_window_rank_top, sg_window_group_nodes_top,
-// sg_window_group_rank_top; v's scratch reserved): launch(out_stage, rank_stage, cap, d_n) enqueues it on the read stream; the selected
-// rows, rank rows (through rank_stage, the ranking's staging; NULL without rank_out) and indices come back, then the counts
-template <class L>
-int node_top_host(sg_engine* e, const NodeSpace& v, L launch, sg_node_out* out, sg_node_rank* rank_out, sg_node_rank* rank_stage,
-                  uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes) {
-    sg_engine::NSel& s = *v.sel;
-    const u64 NC = std::max<u32>(v.cap, 1);
-    const u64 stage = std::min<u64>(cap, NC);
-    if (const int rc = launch(out ? s.stage : nullptr, rank_out ? rank_stage : nullptr, stage, s.n)) return rc;
+// over the group edges by a key of SG_SEL_*: k15_keys over them and, for a trend key, the window's group trend rows (behind K15's update)
+int launch_group_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_group_edge* d_out, u32* d_index,
+                        u64 cap, u64* d_n) {
+    const SelView<sg_group_edge> v = group_sel_view(e, slot);
+    return launch_index_select(e, v, st, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+        if (by != SG_SEL_SCORE && e->gtrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->gtrend.ev, 0));
+        const sg_edge_trend* tr = by != SG_SEL_SCORE ? e->gtrend.rows[slot] : nullptr;
+        hipLaunchKernelGGL(k15_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, v.rows, v.count, tr, by, v.sel->ctr);
+        return (int)SG_OK;
+    }, [](const SelArgs&, dim3) {});
+}
+// What the host forms share, over the last read window (slot cur; v's scratch reserved): launch() enqueues the selection on the read stream;
+// the selected count and the row count are read, at most `stage` rows taken, their indices and — rows_back(take) — the rows come back, then the counts
+template <class Row, class L, class RowsBack>
+int index_top_host(sg_engine* e, const SelView<Row>& v, u64 stage, L launch, RowsBack rows_back, uint32_t* index, size_t* n_selected, size_t* n_rows) {
+    sg_engine::IdxSel<Row>& s = *v.sel;
+    if (const int rc = launch()) return rc;
     u64 cnt = 0;
     HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipMemcpyAsync(&cnt, v.roll->count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipMemcpyAsync(&cnt, v.count, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
     HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
     const u64 m = *s.h_n;
     const size_t take = (size_t)std::min<u64>(m, stage);
-    if (out && take) HIP_TRY(e, hipMemcpyAsync(out, s.stage, take * sizeof(sg_node_out), hipMemcpyDeviceToHost, e->rd_stream));
-    if (rank_out && take) HIP_TRY(e, hipMemcpyAsync(rank_out, rank_stage, take * sizeof(sg_node_rank), hipMemcpyDeviceToHost, e->rd_stream));
-    if (node_index && take) HIP_TRY(e, hipMemcpyAsync(node_index, s.idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
+    if (index && take) HIP_TRY(e, hipMemcpyAsync(index, s.idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
+    if (const int rc = rows_back(take)) return rc;
     HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
     if (n_selected) *n_selected = (size_t)m;
-    if (n_nodes) *n_nodes = (size_t)cnt;
+    if (n_rows) *n_rows = (size_t)cnt;
     return SG_OK;
 }
-
-// ---- selection over group edges (engine lock held) --------------------------------------------------------------------------------
-// the block at the first one (plan_group_select: K7's scratch over max_edges keys, the counter block, indices, the row staging)
-int gsel_reserve(sg_engine* e) {
-    sg_engine::GSel& s = e->gsel;
-    if (s.keys) return SG_OK;
-    const sgplan::GroupSelPlan P = sgplan::plan_group_select(e->cfg.max_edges, sizeof(e->h_ctr));
-    s.plan = P.sel;
-    HIP_TRY(e, hipMalloc((void**)&s.mem, P.total_bytes));
-    HIP_TRY(e, hipMemset(s.mem, 0, P.total_bytes));
-    s.stage = at<sg_group_edge>(s.mem, P.stage_off); s.stage_rows = P.stage_rows;
-    s.ctr = at<u64>(s.mem, P.ctr_off);
-    s.idx = at<u32>(s.mem, P.idx_off);
-    return sel_init(e, s, s.mem + P.sel_off);
+// over a node space (sg_window_nodes_top, sg_window_rank_top and their workload twins): the selection itself gathers — launch(out_stage,
+// rank_stage, cap, d_n) — into the scratch's staging of every row and rank_stage, the ranking's (NULL without rank_out); one copy each
+template <class L>
+int node_top_host(sg_engine* e, const NodeSpace& ns, L launch, sg_node_out* out, sg_node_rank* rank_out, sg_node_rank* rank_stage,
+                  uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes) {
+    const SelView<sg_node_out> v = node_sel_view(ns, e->cur);
+    sg_engine::NSel& s = *v.sel;
+    const u64 stage = std::min<u64>(cap, v.cap);
+    return index_top_host(e, v, stage, [&] { return launch(out ? s.stage : nullptr, rank_out ? rank_stage : nullptr, stage, s.n); }, [&](size_t take) {
+        if (out && take) HIP_TRY(e, hipMemcpyAsync(out, s.stage, take * sizeof(sg_node_out), hipMemcpyDeviceToHost, e->rd_stream));
+        if (rank_out && take) HIP_TRY(e, hipMemcpyAsync(rank_out, rank_stage, take * sizeof(sg_node_rank), hipMemcpyDeviceToHost, e->rd_stream));
+        return (int)SG_OK;
+    }, node_index, n_selected, n_nodes);
 }
-// enqueue a selection over the group edges of slot `slot` on stream st: indices to d_index (NULL: the scratch's), group edges to
-// d_out (may be NULL), the count to d_n; behind that window's contraction, for a trend key its baseline update, and the previous
-// selection over group edges (events).  k15_keys, K7's passes with their row copies off, k_gather_sel.
-int launch_group_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_group_edge* d_out, u32* d_index,
-                        u64 cap, u64* d_n) {
-    sg_engine::GSel& s = e->gsel;
-    const u32 wgs = s.plan.wgs;
-    const u64 ME = std::max<u64>(e->cfg.max_edges, 1);
-    SelArgs a{};
-    a.rows = nullptr; a.ctr = s.ctr; a.max_edges = ME; a.k = k; a.min_score = min_value;
-    sel_scratch_args(a, s);
-    a.out = nullptr; a.out_idx = d_index ? d_index : s.idx; a.cap = d_index ? cap : std::min<u64>(cap, ME); a.n_out = d_n;
-    if (s.pending) HIP_TRY(e, hipStreamWaitEvent(st, s.ev, 0));
-    if (e->grp.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->grp.ev, 0));
-    if (by != SG_SEL_SCORE && e->gtrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->gtrend.ev, 0));
-    const sg_group_edge* groups = e->grp.rows[slot];
-    const sg_edge_trend* tr = by != SG_SEL_SCORE ? e->gtrend.rows[slot] : nullptr;
-    hipLaunchKernelGGL(k15_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, groups, (const u64*)e->grp.count[slot], tr, by, s.ctr);
-    enqueue_k7_select(st, a, k, wgs, ME);
-    const u64 m = std::min<u64>(a.cap, k ? std::min<u64>(k, ME) : ME);
-    const dim3 grid((unsigned)std::max<u64>(1, std::min<u64>((m + 255) / 256, 1024)));
-    if (d_out) hipLaunchKernelGGL(k_gather_sel<sg_group_edge>, grid, dim3(256), 0, st, groups, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_out);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(s.ev, st));
-    s.pending = true;
-    return SG_OK;
-}
-// the host form over the last read window (sg_window_groups_top): the indices are selected on the read stream, then the selected
-// group edges are gathered through the staging, in pieces when there are more of them than it holds (k = 0)
+// over the group edges (sg_window_groups_top): the indices alone are selected, then the selected group edges are gathered through
+// the staging of SG_SELECT_MAX_K, in pieces when there are more of them than it holds (k = 0)
 int group_top_host(sg_engine* e, u32 by, u32 k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap, size_t* n_selected,
                    size_t* n_groups) {
     if (const int rc = gsel_reserve(e)) return rc;
-    sg_engine::GSel& s = e->gsel;
-    const u64 ME = std::max<u64>(e->cfg.max_edges, 1);
-    if (const int rc = launch_group_select(e, e->rd_stream, e->cur, by, k, min_value, nullptr, nullptr, std::min<u64>(cap, ME), s.n)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpyAsync(s.h_n, s.n, sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipMemcpyAsync(&cnt, e->grp.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost, e->rd_stream));
-    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    const u64 m = *s.h_n;
-    const size_t take = (size_t)std::min<u64>(m, std::min<u64>(cap, ME));
-    if (group_index && take) HIP_TRY(e, hipMemcpyAsync(group_index, s.idx, take * sizeof(u32), hipMemcpyDeviceToHost, e->rd_stream));
-    for (size_t o = 0; out && o < take; o += (size_t)s.stage_rows) {
-        const size_t piece = std::min<size_t>((size_t)s.stage_rows, take - o);
-        hipLaunchKernelGGL(k_gather<sg_group_edge>, dim3((unsigned)((piece + 255) / 256)), dim3(256), 0, e->rd_stream,
-                           (const sg_group_edge*)e->grp.rows[e->cur], (const u32*)(s.idx + o), (u64)piece, s.stage);
-        HIP_TRY(e, hipGetLastError());
-        HIP_TRY(e, hipMemcpyAsync(out + o, s.stage, piece * sizeof(sg_group_edge), hipMemcpyDeviceToHost, e->rd_stream));
-        HIP_TRY(e, hipStreamSynchronize(e->rd_stream));               // (the next piece overwrites the staging)
-    }
-    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
-    if (n_selected) *n_selected = (size_t)m;
-    if (n_groups) *n_groups = (size_t)cnt;
-    return SG_OK;
+    const SelView<sg_group_edge> v = group_sel_view(e, e->cur);
+    sg_engine::IdxSel<sg_group_edge>& s = *v.sel;
+    const u64 stage = std::min<u64>(cap, v.cap);
+    return index_top_host(e, v, stage, [&] { return launch_group_select(e, e->rd_stream, e->cur, by, k, min_value, nullptr, nullptr, stage, s.n); }, [&](size_t take) {
+        for (size_t o = 0; out && o < take; o += (size_t)s.stage_rows) {
+            const size_t piece = std::min<size_t>((size_t)s.stage_rows, take - o);
+            hipLaunchKernelGGL(k_gather<sg_group_edge>, dim3((unsigned)((piece + 255) / 256)), dim3(256), 0, e->rd_stream, v.rows,
+                               (const u32*)(s.idx + o), (u64)piece, s.stage);
+            HIP_TRY(e, hipGetLastError());
+            HIP_TRY(e, hipMemcpyAsync(out + o, s.stage, piece * sizeof(sg_group_edge), hipMemcpyDeviceToHost, e->rd_stream));
+            HIP_TRY(e, hipStreamSynchronize(e->rd_stream));               // (the next piece overwrites the staging)
+        }
+        return (int)SG_OK;
+    }, group_index, n_selected, n_groups);
 }
 
 // ---- the baselines' and the per-window buffers' shared host code (engine lock held) -----------------------------------------
@@ -1663,9 +1652,11 @@ int baseline_rows(sg_engine* e, sg_engine::Baseline<Row>& t, size_t N, const u32
     if (out && t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
     return copy_indexed(e, (const Row*)t.rows[e->cur], N, idx, n_index, out, cap, n, t.stage, t.stage_idx, (size_t)t.stage_cap, beyond);
 }
-// the baseline in key order (sg_trend_entries, sg_node_trend_entries)
+// the baseline in key order (the four *_trend_entries): refused as `call` when it is off
 template <class Row>
-int baseline_entries(sg_engine* e, const sg_engine::Baseline<Row>& t, sg_trend_entry* out, size_t cap, size_t* n) {
+int baseline_entries(sg_engine* e, const sg_engine::Baseline<Row>& t, const char* call, const StageWords& what, sg_trend_entry* out, size_t cap,
+                     size_t* n) {
+    if (!t.on) { e->err = std::string(call) + ": " + what.off; return SG_ESTATE; }
     if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
     u64 ctl[K8C_WORDS];
     HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
@@ -1683,9 +1674,10 @@ int baseline_entries(sg_engine* e, const sg_engine::Baseline<Row>& t, sg_trend_e
     for (size_t i = 0; i < take; i++) out[i] = sg_trend_entry{fk[i], tk[i], lm[i], ld[i], em[i], ed[i], cn[i], ls[i]};
     return SG_OK;
 }
-// the baseline's running statistics (sg_trend_stats_get, sg_node_trend_stats_get)
+// the baseline's running statistics (the four *_trend_stats_get), likewise
 template <class Row>
-int baseline_stats(sg_engine* e, const sg_engine::Baseline<Row>& t, sg_trend_stats* out) {
+int baseline_stats(sg_engine* e, const sg_engine::Baseline<Row>& t, const char* call, const StageWords& what, sg_trend_stats* out) {
+    if (!t.on) { e->err = std::string(call) + ": " + what.off; return SG_ESTATE; }
     if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
     u64 ctl[K8C_WORDS];
     HIP_TRY(e, hipMemcpy(ctl, t.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
@@ -1712,16 +1704,33 @@ int list_on(sg_engine* e, sg_engine::Vanished& v, const sgplan::TrendPlan& tp, c
     v.on = true;
     return SG_OK;
 }
+// ---- K8's and K15's vanished list, once over an edge space (engine lock held) ---------------------------------------------------------
+// the list of es on with parameters p (NULL: off), over the space's baseline
+int list_set(sg_engine* e, const EdgeSpace& es, const char* call, const sg_vanished_params* p) {
+    if (!es.trend->on) { e->err = std::string(call) + ": " + es.trend_w.off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    sg_vanished_params r{};
+    if (p && sgplan::check_vanished(*p, es.trend->p, &r)) { e->err = std::string(call) + ": bad parameters"; return SG_EINVAL; }
+    free_list(*es.van);
+    if (!p) return SG_OK;
+    return list_on(e, *es.van, es.trend->plan, r, call, [&es] { free_list(*es.van); });
+}
 // the list of the last read window (slot cur): stage_ready's checks and texts, but the event is the baseline's, whose launches
 // write the list; the count may exceed the rows the list holds
-template <class Row>
-int list_read(sg_engine* e, const sg_engine::Vanished& v, const sg_engine::Baseline<Row>& t, const char* call, const StageWords& what,
-              sg_edge_vanished* out, size_t cap, size_t* n) {
-    if (!v.on) { e->err = std::string(call) + ": " + what.off; return SG_ESTATE; }
+int list_read(sg_engine* e, const EdgeSpace& es, const char* call, sg_edge_vanished* out, size_t cap, size_t* n) {
+    const sg_engine::Vanished& v = *es.van;
+    if (!v.on) { e->err = std::string(call) + ": " + es.van_w.off; return SG_ESTATE; }
     if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
-    if (!v.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while " + what.was; return SG_ESTATE; }
-    if (t.pending) HIP_TRY(e, hipEventSynchronize(t.ev));
+    if (!v.valid[e->cur]) { e->err = std::string(call) + ": the last read window was closed while " + es.van_w.was; return SG_ESTATE; }
+    if (es.trend->pending) HIP_TRY(e, hipEventSynchronize(es.trend->ev));
     return copy_counted(e, v.count[e->cur], v.rows[e->cur], sizeof(sg_edge_vanished), out, std::min<size_t>(cap, v.plan.rows), n);
+}
+int list_buffer(sg_engine* e, const EdgeSpace& es, const char* call, void** d_rows, void** d_count) {
+    const sg_engine::Vanished& v = *es.van;
+    int slot;
+    if (const int rc = stage_slot(e, v, call, es.van_w, &slot)) return rc;
+    *d_rows = v.rows[slot]; *d_count = v.count[slot];
+    return SG_OK;
 }
 // ---- K11 and K17, K12 and K18: the ranking and the incidents, once over a node space (engine lock held) --------------------------------
 // the ranking r of node space ns on with parameters p (NULL: off): plan(slots) plans it, edge_first / edge are its kernels with
@@ -2060,15 +2069,11 @@ int sg_destroy(sg_handle e) {
     if (e->sel.stage_idx) hipFree(e->sel.stage_idx);
     if (e->sel.h_n) hipHostFree(e->sel.h_n);
     if (e->sel.ev) hipEventDestroy(e->sel.ev);
-    free_trend(e);
+    free_edge_trend(edge_space(e));
     free_nodes(e);
     free_groups(e);
-    if (e->nsel.mem) hipFree(e->nsel.mem);
-    if (e->nsel.h_n) hipHostFree(e->nsel.h_n);
-    if (e->nsel.ev) hipEventDestroy(e->nsel.ev);
-    if (e->gsel.mem) hipFree(e->gsel.mem);
-    if (e->gsel.h_n) hipHostFree(e->gsel.h_n);
-    if (e->gsel.ev) hipEventDestroy(e->gsel.ev);
+    free_idxsel(e->nsel);
+    free_idxsel(e->gsel);
     for (auto& r : e->trecs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (auto v : e->ev_pool) hipEventDestroy(v);
     if (e->tab_ev) hipEventDestroy(e->tab_ev);
@@ -2636,15 +2641,18 @@ int sg_window_select_by(sg_handle e, uint32_t by, uint32_t k, float min_value, s
 }
 
 // ---- K8, the per-edge baselines ------------------------------------------------------------------------------------------------
+// (sg_set_trend and sg_set_group_trend stay two: this one checks its parameters before it takes the lock and has no stage below it
+// to find off, K15's checks the groups and the flush first — the order of the refusals is the caller's to see)
 int sg_set_trend(sg_handle e, const sg_trend_params* p) {
     if (!e) return SG_EINVAL;
     sg_trend_params r{};
     if (p && sgplan::check_trend(*p, e->cfg.max_edges, &r)) { e->err = "sg_set_trend: bad parameters"; return SG_EINVAL; }
     std::unique_lock<std::mutex> g(e->mu);
     if (e->closing || e->flush_open) { e->err = "sg_set_trend while a flush is open"; return SG_ESTATE; }
-    free_trend(e);
-    if (!p) { drop_incidents(e, node_space(e)); return SG_OK; }
-    return baseline_on(e, e->trend, r, sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r), "sg_set_trend", [e] { free_trend(e); drop_incidents(e, node_space(e)); });
+    const EdgeSpace es = edge_space(e);
+    free_edge_trend(es);
+    if (!p) { drop_incidents(e, es); return SG_OK; }
+    return baseline_on(e, e->trend, r, sgplan::plan_trend(e->cfg.max_edges, (u32)e->slots.size(), r), "sg_set_trend", [&] { free_edge_trend(es); drop_incidents(e, es); });
 }
 int sg_window_trend(sg_handle e, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
@@ -2664,41 +2672,29 @@ int sg_window_trend_buffer(sg_handle e, void** d_trend) {
 int sg_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->trend.on) { e->err = "sg_trend_entries: the trend is off (sg_set_trend)"; return SG_ESTATE; }
-    return baseline_entries(e, e->trend, out, cap, n);
+    return baseline_entries(e, e->trend, "sg_trend_entries", kTrendWords, out, cap, n);
 }
 int sg_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->trend.on) { e->err = "sg_trend_stats_get: the trend is off (sg_set_trend)"; return SG_ESTATE; }
-    return baseline_stats(e, e->trend, out);
+    return baseline_stats(e, e->trend, "sg_trend_stats_get", kTrendWords, out);
 }
 
 // ---- K8's vanished list ---------------------------------------------------------------------------------------------------
 int sg_set_vanished(sg_handle e, const sg_vanished_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->trend.on) { e->err = "sg_set_vanished: the trend is off (sg_set_trend)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_vanished while a flush is open"; return SG_ESTATE; }
-    sg_vanished_params r{};
-    if (p && sgplan::check_vanished(*p, e->trend.p, &r)) { e->err = "sg_set_vanished: bad parameters"; return SG_EINVAL; }
-    free_vanished(e);
-    if (!p) return SG_OK;
-    return list_on(e, e->vanished, e->trend.plan, r, "sg_set_vanished", [e] { free_vanished(e); });
+    return list_set(e, edge_space(e), "sg_set_vanished", p);
 }
 int sg_window_vanished(sg_handle e, sg_edge_vanished* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    return list_read(e, e->vanished, e->trend, "sg_window_vanished", kVanishedWords, out, cap, n);
+    return list_read(e, edge_space(e), "sg_window_vanished", out, cap, n);
 }
 int sg_window_vanished_buffer(sg_handle e, void** d_rows, void** d_count) {
     if (!e || !d_rows || !d_count) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Vanished& v = e->vanished;
-    int slot;
-    if (const int rc = stage_slot(e, v, "sg_window_vanished_buffer", kVanishedWords, &slot)) return rc;
-    *d_rows = v.rows[slot]; *d_count = v.count[slot];
-    return SG_OK;
+    return list_buffer(e, edge_space(e), "sg_window_vanished_buffer", d_rows, d_count);
 }
 
 // ---- K9 and K16: the rollup, its baseline and its selection, once over a node space ---------------------------------------------
@@ -2744,14 +2740,6 @@ int node_trend_buffer(sg_engine* e, const NodeSpace& ns, const char* call, void*
     if (const int rc = stage_slot(e, t, call, ns.trend_w, &slot)) return rc;
     *d_trend = t.rows[slot];
     return SG_OK;
-}
-int node_trend_entries(sg_engine* e, const NodeSpace& ns, const char* call, sg_trend_entry* out, size_t cap, size_t* n) {
-    if (!ns.trend->on) { e->err = std::string(call) + ": " + ns.trend_w.off; return SG_ESTATE; }
-    return baseline_entries(e, *ns.trend, out, cap, n);
-}
-int node_trend_stats(sg_engine* e, const NodeSpace& ns, const char* call, sg_trend_stats* out) {
-    if (!ns.trend->on) { e->err = std::string(call) + ": " + ns.trend_w.off; return SG_ESTATE; }
-    return baseline_stats(e, *ns.trend, out);
 }
 // the selection.  by > 5: SG_EINVAL; the rollup off, or a trend key with the baseline off: SG_ESTATE; then the window in `slot` must have them
 int check_nsel(sg_engine* e, const NodeSpace& ns, u32 by, int slot) {
@@ -2821,12 +2809,12 @@ int sg_window_node_trend_buffer(sg_handle e, void** d_trend) {
 int sg_node_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    return node_trend_entries(e, node_space(e), "sg_node_trend_entries", out, cap, n);
+    return baseline_entries(e, e->ntrend, "sg_node_trend_entries", kNodeTrendWords, out, cap, n);
 }
 int sg_node_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    return node_trend_stats(e, node_space(e), "sg_node_trend_stats_get", out);
+    return baseline_stats(e, e->ntrend, "sg_node_trend_stats_get", kNodeTrendWords, out);
 }
 int sg_window_nodes_top(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
                         size_t* n_selected, size_t* n_nodes) {
@@ -2995,11 +2983,12 @@ int sg_set_group_trend(sg_handle e, const sg_trend_params* p) {
     if (e->closing || e->flush_open) { e->err = "sg_set_group_trend while a flush is open"; return SG_ESTATE; }
     sg_trend_params r{};
     if (p && sgplan::check_group_trend(*p, e->cfg.max_edges, &r)) { e->err = "sg_set_group_trend: bad parameters"; return SG_EINVAL; }
-    free_group_trend(e);
-    if (!p) { drop_incidents(e, workload_space(e)); return SG_OK; }
+    const EdgeSpace es = group_edge_space(e);
+    free_edge_trend(es);
+    if (!p) { drop_incidents(e, es); return SG_OK; }
     sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
     const u32 slots = (u32)e->slots.size();
-    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_trend(e->cfg.max_edges, slots, r), "sg_set_group_trend", [e] { free_group_trend(e); drop_incidents(e, workload_space(e)); })) return rc;
+    if (const int rc = baseline_on(e, t, r, sgplan::plan_group_trend(e->cfg.max_edges, slots, r), "sg_set_group_trend", [&] { free_edge_trend(es); drop_incidents(e, es); })) return rc;
     t.valid.assign(slots, 0);
     return SG_OK;
 }
@@ -3024,44 +3013,33 @@ int sg_window_group_trend_buffer(sg_handle e, void** d_trend) {
 int sg_group_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->gtrend.on) { e->err = "sg_group_trend_entries: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
-    return baseline_entries(e, e->gtrend, out, cap, n);
+    return baseline_entries(e, e->gtrend, "sg_group_trend_entries", kGroupTrendWords, out, cap, n);
 }
 int sg_group_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (!e->gtrend.on) { e->err = "sg_group_trend_stats_get: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
-    return baseline_stats(e, e->gtrend, out);
+    return baseline_stats(e, e->gtrend, "sg_group_trend_stats_get", kGroupTrendWords, out);
 }
 int sg_set_group_vanished(sg_handle e, const sg_vanished_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->gtrend.on) { e->err = "sg_set_group_vanished: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_group_vanished while a flush is open"; return SG_ESTATE; }
-    sg_vanished_params r{};
-    if (p && sgplan::check_vanished(*p, e->gtrend.p, &r)) { e->err = "sg_set_group_vanished: bad parameters"; return SG_EINVAL; }
-    free_list(e->gvanished);
-    if (!p) return SG_OK;
-    return list_on(e, e->gvanished, e->gtrend.plan, r, "sg_set_group_vanished", [e] { free_list(e->gvanished); });
+    return list_set(e, group_edge_space(e), "sg_set_group_vanished", p);
 }
 int sg_window_group_vanished(sg_handle e, sg_edge_vanished* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    return list_read(e, e->gvanished, e->gtrend, "sg_window_group_vanished", kGroupVanishedWords, out, cap, n);
+    return list_read(e, group_edge_space(e), "sg_window_group_vanished", out, cap, n);
 }
 int sg_window_group_vanished_buffer(sg_handle e, void** d_rows, void** d_count) {
     if (!e || !d_rows || !d_count) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Vanished& v = e->gvanished;
-    int slot;
-    if (const int rc = stage_slot(e, v, "sg_window_group_vanished_buffer", kGroupVanishedWords, &slot)) return rc;
-    *d_rows = v.rows[slot]; *d_count = v.count[slot];
-    return SG_OK;
+    return list_buffer(e, group_edge_space(e), "sg_window_group_vanished_buffer", d_rows, d_count);
 }
 
 // ---- selection over group edges -------------------------------------------------------------------------------------------------
 namespace {
 // by > 3: SG_EINVAL; the groups off, or a trend key with the group trend off: SG_ESTATE; then the window in `slot` must have them
+// (not shared with check_by, K7's over the edge rows: that one has no stage below it and no valid to look at, and its host form is a flush)
 int check_gsel(sg_engine* e, u32 by, int slot) {
     if (by > SG_SEL_NEW) { e->err = "group selection: unknown key (by > SG_SEL_NEW)"; return SG_EINVAL; }
     if (!e->grp.on) { e->err = "group selection: the groups are off (sg_set_groups)"; return SG_ESTATE; }
@@ -3134,12 +3112,12 @@ int sg_window_group_node_trend_buffer(sg_handle e, void** d_trend) {
 int sg_group_node_trend_entries(sg_handle e, sg_trend_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    return node_trend_entries(e, workload_space(e), "sg_group_node_trend_entries", out, cap, n);
+    return baseline_entries(e, e->gntrend, "sg_group_node_trend_entries", kGroupNodeTrendWords, out, cap, n);
 }
 int sg_group_node_trend_stats_get(sg_handle e, sg_trend_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    return node_trend_stats(e, workload_space(e), "sg_group_node_trend_stats_get", out);
+    return baseline_stats(e, e->gntrend, "sg_group_node_trend_stats_get", kGroupNodeTrendWords, out);
 }
 int sg_window_group_nodes_top(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
                               size_t* n_selected, size_t* n_nodes) {

@@ -514,26 +514,27 @@ inline SelPlan plan_select(u64 max_edges, bool used) {
     s.scratch_bytes = b.end; s.layout = std::move(b.pieces);
     return s;
 }
-// Node selection (K7 over K9's node rows): the whole block of the first node selection — the host form's row staging, the counter
-// block k10_keys / k11_keys fill (counter_bytes: the engine's, the plan includes no device header), an index array, then K7's
-// scratch over ncap rows
-struct NodeSelPlan {
+// An index selection (K7 over rows that are not the edge rows: K9's node rows, K16's workload rows, K14's group edges): the whole
+// block of the first one — the host form's staging of stage_rows rows of row_bytes each, the counter block the key pass fills
+// (counter_bytes: the engine's, the plan includes no device header), an index array over the rows, then K7's scratch over `rows` keys
+struct IndexSelPlan {
     SelPlan sel;
-    u64 stage_bytes = 0;          // [ncap] sg_node_out
+    u64 stage_rows = 0;           // rows the host form's staging holds
+    u64 stage_bytes = 0;          // [stage_rows] rows
     u64 ctr_bytes = 0;            // the counter block
-    u64 idx_bytes = 0;            // [ncap] u32
+    u64 idx_bytes = 0;            // [rows] u32
     u64 sel_bytes = 0;            // sel.scratch_bytes
     u64 stage_off = 0, ctr_off = 0, idx_off = 0, sel_off = 0;
     u64 total_bytes = 0;          // all of it, each piece 256-byte aligned
     std::vector<Piece> layout;
 };
-inline NodeSelPlan plan_node_select(u32 ncap, u64 counter_bytes) {
-    NodeSelPlan n;
-    const u64 NC = std::max<u32>(ncap, 1);
-    n.sel = plan_select(NC, true);
-    n.stage_bytes = trend_align(NC * sizeof(sg_node_out));
+inline IndexSelPlan plan_index_select(u64 rows, u64 stage_rows, u64 row_bytes, u64 counter_bytes) {
+    IndexSelPlan n;
+    n.sel = plan_select(rows, true);
+    n.stage_rows = stage_rows;
+    n.stage_bytes = trend_align(stage_rows * row_bytes);
     n.ctr_bytes = trend_align(counter_bytes);
-    n.idx_bytes = trend_align(NC * 4);
+    n.idx_bytes = trend_align(rows * 4);
     n.sel_bytes = trend_align(n.sel.scratch_bytes);
     Block b;
     n.stage_off = b.take("stage", n.stage_bytes);
@@ -542,6 +543,12 @@ inline NodeSelPlan plan_node_select(u32 ncap, u64 counter_bytes) {
     n.sel_off = b.take("sel", n.sel_bytes);
     n.total_bytes = b.end; n.layout = std::move(b.pieces);
     return n;
+}
+// Node selection (K7 over K9's node rows, k10_keys / k11_keys): over ncap rows, every one of them staged
+using NodeSelPlan = IndexSelPlan;
+inline NodeSelPlan plan_node_select(u32 ncap, u64 counter_bytes) {
+    const u64 NC = std::max<u32>(ncap, 1);
+    return plan_index_select(NC, NC, sizeof(sg_node_out), counter_bytes);
 }
 // k7_sort's LDS: the selected (key, index) pairs padded to a power of two, 8 bytes each
 inline size_t select_sort_lds(u32 k) { return (size_t)next_pow2(std::max<u32>(k, 1)) * 8; }
@@ -1068,36 +1075,11 @@ using GroupTrendPlan = TrendPlan;
 inline TrendPlan plan_group_trend(u64 max_edges, u32 slots, const sg_trend_params& p) {
     return plan_baseline(p, max_edges, std::max<u64>(max_edges, 1) * sizeof(sg_edge_trend), slots);
 }
-// Selection over group edges (K7 over K14's rows): the whole block of the first one — the host form's row staging of
-// SG_SELECT_MAX_K group edges (a longer selection is gathered in pieces through it), the counter block k15_keys fills
-// (counter_bytes: the engine's), an index array over max_edges, then K7's scratch over max_edges keys
-struct GroupSelPlan {
-    SelPlan sel;
-    u64 stage_rows = 0;           // SG_SELECT_MAX_K
-    u64 stage_bytes = 0;          // [stage_rows] sg_group_edge
-    u64 ctr_bytes = 0;            // the counter block
-    u64 idx_bytes = 0;            // [max_edges] u32
-    u64 sel_bytes = 0;            // sel.scratch_bytes
-    u64 stage_off = 0, ctr_off = 0, idx_off = 0, sel_off = 0;
-    u64 total_bytes = 0;          // all of it, each piece 256-byte aligned
-    std::vector<Piece> layout;
-};
+// Selection over group edges (K7 over K14's rows, k15_keys): over max_edges keys, with a staging of SG_SELECT_MAX_K group edges (a
+// longer selection is gathered in pieces through it)
+using GroupSelPlan = IndexSelPlan;
 inline GroupSelPlan plan_group_select(u64 max_edges, u64 counter_bytes) {
-    GroupSelPlan n;
-    const u64 ME = std::max<u64>(max_edges, 1);
-    n.sel = plan_select(ME, true);
-    n.stage_rows = SG_SELECT_MAX_K;
-    n.stage_bytes = trend_align(n.stage_rows * kGrpEdgeBytes);
-    n.ctr_bytes = trend_align(counter_bytes);
-    n.idx_bytes = trend_align(ME * 4);
-    n.sel_bytes = trend_align(n.sel.scratch_bytes);
-    Block b;
-    n.stage_off = b.take("stage", n.stage_bytes);
-    n.ctr_off = b.take("ctr", n.ctr_bytes);
-    n.idx_off = b.take("idx", n.idx_bytes);
-    n.sel_off = b.take("sel", n.sel_bytes);
-    n.total_bytes = b.end; n.layout = std::move(b.pieces);
-    return n;
+    return plan_index_select(std::max<u64>(max_edges, 1), SG_SELECT_MAX_K, kGrpEdgeBytes, counter_bytes);
 }
 
 // K16, the workload rows (sg_group_nodes.h): the device memory sg_set_group_nodes allocates — never sg_create or sg_set_groups.
