@@ -903,7 +903,7 @@ void free_baseline(sg_engine::Baseline<Row>& t) {
 // ---- K11 and K17, the ranking (engine lock held) ------------------------------------------------------------------------------------
 static_assert(sgplan::kRankThreads == K11_THREADS && sgplan::kRankRangeNodes == K11_NR && sgplan::kRankMaxWgs == K11_MAX_WGS &&
               sgplan::kRankRangeNodes * 8 <= sgplan::kLdsBytes, "plan_rank sizes the launches of sg_rank.h");
-static_assert(K17_THREADS == K11_THREADS && K17_EDGE_THREADS == K11_EDGE_THREADS, "launch_ranking launches both rankings' kernels");
+static_assert(K17_THREADS == K11_THREADS, "launch_ranking launches both rankings' kernels");
 // enqueue the ranking of node space ns's rows of the window in slot cur on stream s (behind their rollup, on the same stream) and
 // behind the previous ranking (any stream): a gets the space's rows, the parameters, r's arrays but w and the slot's rank rows;
 // front(nt) launches the passes in front (a prep pass of P.prep_wgs workgroups of nt threads the last), then 2 * iters + 2 plain
@@ -944,7 +944,6 @@ void free_rank(sg_engine* e) { free_stage(e->rank); }
 // ---- K12 and K18, the incidents (engine lock held) -----------------------------------------------------------------------------------
 static_assert(sgplan::kIncThreads == K12_THREADS && sgplan::kIncMaxWgs == K12_MAX_WGS && sgplan::kIncKeysBytes == sizeof(K12Keys),
               "plan_incidents sizes the launches of sg_incident.h");
-static_assert(K18_THREADS == K12_THREADS, "launch_grouping launches both groupings' kernels");
 // enqueue the grouping of node space ns's rows of the window in slot cur on stream s (behind the space's edge trend rows, its rollup
 // and its ranking, on the same stream) and behind the previous grouping (any stream): a gets the space's rows, trend rows and rank
 // rows, the parameters, x's arrays but the stage's own and the slot's buffers; nd, the NodesArgs inside a, the head counts and the
@@ -1131,7 +1130,7 @@ int launch_group_rank(sg_engine* e, hipStream_t s) {
 }
 void free_group_rank(sg_engine* e) { free_stage(e->grank); }
 // ---- K18, the workload incidents (engine lock held) --------------------------------------------------------------------------------
-static_assert(sgplan::kGrpIncThreads == K18_THREADS && sgplan::kGrpIncMaxWgs == K18_MAX_WGS && sgplan::kGrpIncSlots == K12_SLOTS &&
+static_assert(sgplan::kGrpIncThreads == K12_THREADS && sgplan::kGrpIncMaxWgs == K12_MAX_WGS && sgplan::kGrpIncSlots == K12_SLOTS &&
               sgplan::kIncKeysBytes == sizeof(K12Keys), "plan_group_incidents sizes the launches of sg_group_incident.h");
 // launch_grouping over the workload rows (behind the contraction, the group trend rows, the workload rows and the workload ranking,
 // on the same stream): k18_nodes on its fold grid

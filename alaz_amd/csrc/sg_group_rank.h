@@ -1,6 +1,6 @@
 // sg_group_rank.h — K17: each window's likely root-cause workloads ranked on the device (include/servicegraph.h, "workload ranking").
-// Included after sg_group_nodes.h: it reuses K16's group key (k16_gk), K11's seed rule (k11_seed_of's q16), k11_keys, K7's passes and
-// the gathers unchanged, and adds kernels of its own.
+// Included after sg_group_nodes.h: it reuses K16's group key (k16_gk), K11's seed rule (k11_seed_of), K11's edge pass (k_rank_edge_t,
+// over K17Space below), k11_keys, K7's passes and the gathers unchanged, and adds kernels of its own.
 //
 // K11's walk with "row" read as "group edge" and "node row" read as "workload row", in u64 integer arithmetic only.  K11 works in
 // node-key space; K16's rows are dense and ascending by group key, so this stage works in ROW-INDEX space: every per-node array is
@@ -12,7 +12,7 @@
 //   k17_pos     per workload row v: pos[gk(ref_v)] = v; the seed a_v, summed per workgroup
 //   k17_prep    per group edge j: src[j] = pos[gk(from)], dst[j] = pos[gk(to)] and the weight w[j] = edges + min(score_q32 >> 16,
 //               65536 * edges) as a u64 (16 bytes a group edge for the iterations instead of the 80-byte rows)
-//   k17_edge    k11_edge's pattern over row indices: workgroup (range, slice) holds K17_NR u64 accumulators in LDS (8192 rows = 64 KiB:
+//   k17_edge    k11_edge's body over row indices: workgroup (range, slice) holds K17_NR u64 accumulators in LDS (8192 rows = 64 KiB:
 //               two workgroups a CU) and scans its slice of the group edges; BY_SRC: acc[src] += w (the out-weight W, once a window);
 //               else acc[dst] += t[src] * w (once an iteration) with LDS integer atomics.  A range at or beyond the window's row count
 //               exits; the partial written is min(K17_NR, n - n0) words
@@ -23,9 +23,7 @@
 #pragma once
 
 #define K17_THREADS 256           // k17_pos, k17_prep, k17_node
-#define K17_EDGE_THREADS 1024     // k17_edge
-#define K17_NR 8192               // rows per range: 8192 x 8 B = 64 KiB of LDS
-#define K17_Q 4                   // group edges per thread and trip of k17_edge
+#define K17_NR 8192               // rows per range: 8192 x 8 B = 64 KiB of LDS (k17_edge: K11_EDGE_THREADS threads, K11_Q group edges a trip)
 #define K17_MAX_WGS 1024          // k17_pos's grid at most (k17_node sums one seed sum per workgroup)
 #define K17_NODE_ROWS 32          // rows per workgroup and round of k17_node
 #define K17_NODE_SPLIT (K17_THREADS / K17_NODE_ROWS)   // threads that share a row's slices
@@ -46,11 +44,8 @@ struct GroupRankArgs {
 };
 
 __device__ __forceinline__ u64 k17_rows_of(const GroupRankArgs& a) { return sg_nodes_of(a.count, a.g.nc); }
-__device__ __forceinline__ u64 k17_seed_of(const GroupRankArgs& a, float score) {
-    if (a.seed == SG_RANK_SEED_UNIFORM) return 1ull;
-    return score >= a.seed_min ? (u64)k11_q16(score) : 0ull;
-}
 
+// (k17_pos + k17_prep stay K17's own against k11_prep: the rows' positions must be complete before a group edge can look them up)
 __global__ __launch_bounds__(K17_THREADS) void k17_pos(GroupRankArgs a) {
     __shared__ u64 ssum;
     const u32 t = threadIdx.x;
@@ -62,7 +57,7 @@ __global__ __launch_bounds__(K17_THREADS) void k17_pos(GroupRankArgs a) {
         const sg_node_out* nrow = a.nodes + v;
         const u32 k = k16_gk(a.g, nrow->ref);
         if (k != SG_NONE && k < a.g.gk) a.pos[k] = (u32)v;           // (cannot fail: K16 made the row from such a key)
-        sum += k17_seed_of(a, nrow->score);
+        sum += k11_seed_of(a.seed, a.seed_min, nrow->score);
     }
     if (sum) atomicAdd(&ssum, sum);
     __syncthreads();
@@ -85,36 +80,21 @@ __global__ __launch_bounds__(K17_THREADS) void k17_prep(GroupRankArgs a) {
     }
 }
 
-template <bool BY_SRC>
-__global__ __launch_bounds__(K17_EDGE_THREADS) void k17_edge(GroupRankArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    u64* acc = reinterpret_cast<u64*>(smem);
-    const u32 S = a.slices, g = blockIdx.x, t = threadIdx.x;
-    const u32 rg = g / S, sl = g % S;
-    const u64 N = k17_rows_of(a), n0 = (u64)rg * K17_NR;
-    if (n0 >= N) return;                                             // (uniform: k17_node reads no partial of such a range)
-    const u32 nr = N - n0 < K17_NR ? (u32)(N - n0) : K17_NR;
-    for (u32 i = t; i < nr; i += K17_EDGE_THREADS) acc[i] = 0;
-    __syncthreads();
-    const u64 G = k16_edges_of(a.g);
-    const u64 per = (G + S - 1) / S, p0 = (u64)sl * per < G ? (u64)sl * per : G, p1 = p0 + per < G ? p0 + per : G;
-    const u32* key = BY_SRC ? a.src : a.dst;
-    for (u64 pb = p0 + t; pb < p1; pb += (u64)K17_EDGE_THREADS * K17_Q) {
-        u32 k[K17_Q];
-#pragma unroll
-        for (int q = 0; q < K17_Q; q++) { const u64 p = pb + (u64)q * K17_EDGE_THREADS; k[q] = p < p1 ? key[p] - (u32)n0 : 0xFFFFFFFFu; }
-#pragma unroll
-        for (int q = 0; q < K17_Q; q++) if (k[q] < nr) {
-            const u64 p = pb + (u64)q * K17_EDGE_THREADS;
-            const u64 w = a.w[p];
-            const u64 x = BY_SRC ? w : (w ? a.t[a.src[p]] * w : 0ull);   // (group edges ascend by source: t[src] is a cached, mostly uniform load)
-            if (x) atomicAdd(&acc[k[q]], x);
-        }
+// K17's space for K11's edge pass (sg_rank.h): ranges of K17_NR row indices, and only those below the window's row count run
+struct K17Space {
+    typedef GroupRankArgs Args;
+    static constexpr u32 NR = K17_NR;
+    static constexpr bool SKIP_T_OF_ZERO_W = true;
+    static __device__ __forceinline__ u64 edges(const GroupRankArgs& a) { return k16_edges_of(a.g); }
+    static __device__ __forceinline__ bool range(const GroupRankArgs& a, u32 rg, u32& n0, u32& nr) {
+        const u64 N = k17_rows_of(a), first = (u64)rg * K17_NR;
+        if (first >= N) return false;
+        n0 = (u32)first; nr = N - first < K17_NR ? (u32)(N - first) : K17_NR;
+        return true;
     }
-    __syncthreads();
-    u64* out = a.part + ((size_t)rg * S + sl) * K17_NR;
-    for (u32 i = t; i < nr; i += K17_EDGE_THREADS) out[i] = acc[i];
-}
+};
+template <bool BY_SRC>
+__global__ __launch_bounds__(K11_EDGE_THREADS) void k17_edge(GroupRankArgs a) { k_rank_edge_t<K17Space, BY_SRC>(a); }
 
 // the partials of row v in the slices first, first + K17_NODE_SPLIT, ... summed
 __device__ __forceinline__ u64 k17_part_sum(const GroupRankArgs& a, u64 v, u32 first) {
@@ -127,6 +107,7 @@ __device__ __forceinline__ u64 k17_part_sum(const GroupRankArgs& a, u64 v, u32 f
     return s;
 }
 
+// (k17_node stays K17's own: it works by row and eight threads share a row's slices; k11_node goes through k9_node, a thread a row)
 template <bool FIRST, bool LAST>
 __global__ __launch_bounds__(K17_THREADS) void k17_node(GroupRankArgs a) {
     __shared__ u64 sA;
@@ -157,7 +138,7 @@ __global__ __launch_bounds__(K17_THREADS) void k17_node(GroupRankArgs a) {
         if (g != 0 || v >= N) continue;
         u64 r, W = 0, R = 0;
         if (FIRST) {
-            const u64 av = A ? k17_seed_of(a, a.nodes[v].score) : 1ull;   // A == 0: the uniform seed
+            const u64 av = A ? k11_seed_of(a.seed, a.seed_min, a.nodes[v].score) : 1ull;   // A == 0: the uniform seed
             const u64 p = av * (M / (A ? A : N));
             W = ps;
             R = (p >> 8) * (256 - D);

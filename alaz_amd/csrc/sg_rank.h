@@ -10,7 +10,8 @@
 //               bytes a row for the iterations instead of the 64-byte rows); per node row: the seed a, summed per workgroup
 //   k11_edge    k9_in_part's pattern: workgroup (range, slice) holds K11_NR u64 accumulators in LDS (16 384 nodes = 128 KiB) and
 //               scans its slice of the rows; BY_SRC: acc[src] += w (the out-weight W, once a window); else acc[dst] += t[src] * w
-//               (the mass handed along the rows, once an iteration) with LDS integer atomics; it writes its LDS to its slice's partial
+//               (the mass handed along the rows, once an iteration) with LDS integer atomics; it writes its LDS to its slice's partial.
+//               One body with k17_edge: k_rank_edge_t over K11Space / K17Space
 //   k11_node    per node row: FIRST: A from the workgroups' seed sums, W from the partials, p, R and r = p; else r = base + the
 //               partials of the edge pass before it.  Then, unless LAST, m, t = m / W and base = R + m - t * W for the next
 //               iteration; LAST: the window's sg_node_rank row.
@@ -19,9 +20,9 @@
 #pragma once
 
 #define K11_THREADS 256           // k11_prep, k11_node
-#define K11_EDGE_THREADS 1024     // k11_edge
+#define K11_EDGE_THREADS 1024     // k11_edge, k17_edge
 #define K11_NR 16384              // nodes per range: 16384 x 8 B = 128 KiB of LDS
-#define K11_Q 4                   // rows per thread and trip of k11_edge
+#define K11_Q 4                   // rows per thread and trip of k11_edge, k17_edge
 #define K11_MAX_WGS 1024          // k11_prep's grid at most (k11_node sums one seed sum per workgroup)
 #define K11_M_LOG2 56             // M = 2^56
 
@@ -42,11 +43,13 @@ struct RankArgs {
 };
 
 __device__ __forceinline__ u32 k11_q16(float s) { return s > 0.0f ? (s >= 1.0f ? 65536u : (u32)(s * 65536.0f)) : 0u; }
-__device__ __forceinline__ u64 k11_seed_of(const RankArgs& a, float score) {
-    if (a.seed == SG_RANK_SEED_UNIFORM) return 1ull;
-    return score >= a.seed_min ? (u64)k11_q16(score) : 0ull;
+// the seed of a node row (K11) or a workload row (K17) under SG_RANK_SEED_* seed
+__device__ __forceinline__ u64 k11_seed_of(u32 seed, float seed_min, float score) {
+    if (seed == SG_RANK_SEED_UNIFORM) return 1ull;
+    return score >= seed_min ? (u64)k11_q16(score) : 0ull;
 }
 
+// (k11_prep stays K11's own: K17 needs pos before its rows can be prepared and splits the work into k17_pos + k17_prep)
 __global__ __launch_bounds__(K11_THREADS) void k11_prep(RankArgs a) {
     __shared__ u64 ssum;
     const u32 t = threadIdx.x;
@@ -63,24 +66,39 @@ __global__ __launch_bounds__(K11_THREADS) void k11_prep(RankArgs a) {
     }
     const u64 N = sg_nodes_of(a.count, a.nd.ncap);
     u64 sum = 0;
-    for (u64 v = g0; v < N; v += stride) sum += k11_seed_of(a, a.nodes[v].score);
+    for (u64 v = g0; v < N; v += stride) sum += k11_seed_of(a.seed, a.seed_min, a.nodes[v].score);
     if (sum) atomicAdd(&ssum, sum);
     __syncthreads();
     if (t == 0) a.seed_sum[blockIdx.x] = ssum;
 }
 
-template <bool BY_SRC>
-__global__ __launch_bounds__(K11_EDGE_THREADS) void k11_edge(RankArgs a) {
+// The edge pass of K11 and of K17 (sg_group_rank.h) is one body over a space policy: the nodes per range, the edge count, which
+// node indices [n0, n0 + nr) workgroup range rg accumulates (false: it has nothing to do, and the node pass reads no partial of
+// it), and whether an edge of weight 0 skips the load of t[src].  The weights' type comes with the space's Args (u32 here, u64 in K17).
+struct K11Space {
+    typedef RankArgs Args;
+    static constexpr u32 NR = K11_NR;
+    static constexpr bool SKIP_T_OF_ZERO_W = false;                  // (k11_prep gives a row that carries nothing src = 0, a valid key)
+    static __device__ __forceinline__ u64 edges(const RankArgs& a) { return k9_rows_of(a.nd); }
+    static __device__ __forceinline__ bool range(const RankArgs& a, u32 rg, u32& n0, u32& nr) {
+        n0 = rg * K11_NR;
+        if (n0 >= a.nd.ncap) return false;
+        nr = a.nd.ncap - n0 < K11_NR ? a.nd.ncap - n0 : K11_NR;
+        return k9_range_used(k9_used(a.nd), n0, n0 + nr);            // (no node row has a key in an unused range)
+    }
+};
+
+template <class SP, bool BY_SRC>
+__device__ __forceinline__ void k_rank_edge_t(const typename SP::Args& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64* acc = reinterpret_cast<u64*>(smem);
     const u32 S = a.slices, g = blockIdx.x, t = threadIdx.x;
-    const u32 rg = g / S, sl = g % S, n0 = rg * K11_NR;
-    if (n0 >= a.nd.ncap) return;
-    const u32 nr = a.nd.ncap - n0 < K11_NR ? a.nd.ncap - n0 : K11_NR;
-    if (!k9_range_used(k9_used(a.nd), n0, n0 + nr)) return;         // (no node row has a key in such a range: k11_node reads no partial of it)
+    const u32 rg = g / S, sl = g % S;
+    u32 n0, nr;
+    if (!SP::range(a, rg, n0, nr)) return;                           // (uniform)
     for (u32 i = t; i < nr; i += K11_EDGE_THREADS) acc[i] = 0;
     __syncthreads();
-    const u64 E = k9_rows_of(a.nd);
+    const u64 E = SP::edges(a);
     const u64 per = (E + S - 1) / S, p0 = (u64)sl * per < E ? (u64)sl * per : E, p1 = p0 + per < E ? p0 + per : E;
     const u32* key = BY_SRC ? a.src : a.dst;
     for (u64 pb = p0 + t; pb < p1; pb += (u64)K11_EDGE_THREADS * K11_Q) {
@@ -91,14 +109,17 @@ __global__ __launch_bounds__(K11_EDGE_THREADS) void k11_edge(RankArgs a) {
         for (int q = 0; q < K11_Q; q++) if (k[q] < nr) {
             const u64 p = pb + (u64)q * K11_EDGE_THREADS;
             const u64 w = a.w[p];
-            const u64 x = BY_SRC ? w : a.t[a.src[p]] * w;          // (rows are sorted by source: t[src] is a cached, mostly uniform load)
+            u64 x = w;                                               // (edges are sorted by source: t[src] is a cached, mostly uniform load)
+            if constexpr (!BY_SRC) x = SP::SKIP_T_OF_ZERO_W && !w ? 0ull : a.t[a.src[p]] * w;
             if (x) atomicAdd(&acc[k[q]], x);
         }
     }
     __syncthreads();
-    u64* out = a.part + ((size_t)rg * S + sl) * K11_NR;
+    u64* out = a.part + ((size_t)rg * S + sl) * SP::NR;
     for (u32 i = t; i < nr; i += K11_EDGE_THREADS) out[i] = acc[i];
 }
+template <bool BY_SRC>
+__global__ __launch_bounds__(K11_EDGE_THREADS) void k11_edge(RankArgs a) { k_rank_edge_t<K11Space, BY_SRC>(a); }
 
 // the slices' partials of node key v summed
 __device__ __forceinline__ u64 k11_part_sum(const RankArgs& a, u32 v) {
@@ -109,6 +130,7 @@ __device__ __forceinline__ u64 k11_part_sum(const RankArgs& a, u32 v) {
     return s;
 }
 
+// (k11_node stays K11's own: it goes through k9_node, one thread a node row; k17_node splits a row's slices over eight threads)
 template <bool FIRST, bool LAST>
 __global__ __launch_bounds__(K11_THREADS) void k11_node(RankArgs a) {
     __shared__ u64 sA;
@@ -131,7 +153,7 @@ __global__ __launch_bounds__(K11_THREADS) void k11_node(RankArgs a) {
         if (v == SG_NONE) continue;                                   // (cannot be: K9 made the row from such a key)
         u64 r, W = 0, R = 0;
         if (FIRST) {
-            const u64 av = A ? k11_seed_of(a, nrow->score) : 1ull;   // A == 0: the uniform seed
+            const u64 av = A ? k11_seed_of(a.seed, a.seed_min, nrow->score) : 1ull;   // A == 0: the uniform seed
             const u64 p = av * (M / (A ? A : N));
             W = k11_part_sum(a, v);
             R = (p >> 8) * (256 - D);

@@ -271,9 +271,9 @@ def test_window_run_and_read(churn):
 
 
 # ---- constructed windows with known answers: pod-to-pod events only and min_value = -inf, so every row is red ---------------------
-def _pods_engine(n_pods, max_known=None):
+def _pods_engine(n_pods, max_known=None, max_edges=1 << 14):
     topo = replay.make_topology(n_pods, 4 * n_pods, seed=7, svcs=4)    # (only the pods and their ids are used)
-    g = engine.ServiceGraph(max_known_nodes=max_known or topo.n_nodes + 8, max_edges=1 << 14, layers=2, max_labels=16, max_outbound_ips=64,
+    g = engine.ServiceGraph(max_known_nodes=max_known or topo.n_nodes + 8, max_edges=max_edges, layers=2, max_labels=16, max_outbound_ips=64,
                             max_window_events=1 << 16, max_batch=1 << 14)
     g.set_clock(*CLOCK); g.load_weights(weights.make_weights(2))
     HostShim().apply(g, topo.k8s_ops()); g.set_label_count(0)
@@ -342,3 +342,31 @@ def test_one_pod_calling_5000_others(max_known):
     assert len(got) == 1 and (got["first_node"][0], got["nodes"][0], got["edges"][0]) == (0, n, n - 1)
     assert (inc == 0).all()
     assert got["top_node"][0] == int(np.flatnonzero(nodes["score"] == nodes["score"].max())[0])
+
+
+@pytest.mark.parametrize("n", [255, 256, 257, 513])
+def test_node_row_counts_around_the_node_span(n):
+    """n node rows in red pairs and one triple: plan_incidents gives k12_label / k12_number 256 node rows a workgroup (any node
+    capacity up to 262 144), so the incidents' heads lie on either side of a workgroup's rows"""
+    topo, g = _pods_engine(600)
+    ids = 50 + np.arange(n)
+    src = ids[:-1][::2] if n % 2 == 0 else np.concatenate([ids[:-1][::2], [ids[-2]]])
+    rows, nodes, got, inc = _close(topo, g, src, src + 1)
+    assert len(nodes) == n and len(got) == n // 2
+    assert got["first_node"].tolist() == list(range(0, 2 * (n // 2), 2))
+
+
+def test_more_incidents_through_one_workgroup_of_the_rows_pass_than_its_table_has_slots():
+    """max_edges 4096 over 8200 pods: 4096 disjoint red pairs 2i -> 2i + 1 are 4096 incidents; each of the four workgroups of
+    k12_rows takes 1024 rows — 1024 distinct incidents against 512 table slots (tests/test_incident_host.py holds the plan to
+    that), and no wave names one incident.  Ranked: the culprit loop runs beside it"""
+    # (k12_nodes' direct path is out of reach here: its grid is one round of 256 node rows a workgroup up to 262 144 node rows, 128
+    #  pairs against 512 slots.  The node fold is one body for both spaces, and K18's instance takes eight rounds a workgroup in
+    #  tests/test_gpu_group_incidents.py::test_more_incidents_through_one_workgroup_than_its_table_has_slots: its direct path runs there)
+    topo, g = _pods_engine(8200, max_edges=4096)
+    src = 2 * np.arange(4096)
+    rows, nodes, got, inc = _close(topo, g, src, src + 1)
+    assert len(got) == 4096 and (got["nodes"] == 2).all() and (got["edges"] == 1).all()
+    assert got["worst_row"].tolist() == list(range(4096))
+    assert inc.tolist() == np.repeat(np.arange(4096), 2).tolist()
+    assert (got["culprit_node"] != NO).all()

@@ -298,6 +298,16 @@ def test_plan_sizes(incident_plan):
     assert (toy["node_wgs"], toy["grid_wgs"], toy["hook_wgs"], toy["row_wgs"]) == (5, 5, 4, 4)
 
 
+def test_the_small_gpu_engine_overflows_the_rows_table(incident_plan):
+    """tests/test_gpu_incidents.py: max_edges 4096 over about 8200 pods, 4096 disjoint red pairs 2i -> 2i + 1 — each of the four
+    workgroups of k12_rows takes 1024 rows, each its own incident, against the 512 slots of its LDS table (K12_SLOTS; the
+    engine's static_asserts tie it to the plan's kGrpIncSlots, which tests/test_group_incident_host.py reads as 512).  k12_nodes
+    takes one round of 256 node rows a workgroup — 128 pairs: its table holds them"""
+    r, = incident_plan([_p(4096, 8200 + 4 + 8 + 16 + 64)])
+    assert (r["row_wgs"], r["node_per"]) == (4, 256) and r["grid_wgs"] * 256 >= r["ncap"]
+    assert (4096 + r["row_wgs"] - 1) // r["row_wgs"] == 1024 > 512
+
+
 def test_plan_parameter_checks(incident_plan):
     ok = incident_plan([_p(1000, 100, by=b) for b in (0, 1, 2)])
     assert [r["rc"] for r in ok] == [0] * 3 and [r["by"] for r in ok] == [0, 1, 2] and ok[0]["min_value"] == 0.5
