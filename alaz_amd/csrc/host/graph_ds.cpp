@@ -37,6 +37,9 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->set_group_incidents = reinterpret_cast<decltype(o->set_group_incidents)>(dlsym(dl, "sg_set_group_incidents"));   // optional (K18)
     o->window_group_incidents = reinterpret_cast<decltype(o->window_group_incidents)>(dlsym(dl, "sg_window_group_incidents"));
     o->window_group_node_incident = reinterpret_cast<decltype(o->window_group_node_incident)>(dlsym(dl, "sg_window_group_node_incident"));
+    o->set_group_tracks = reinterpret_cast<decltype(o->set_group_tracks)>(dlsym(dl, "sg_set_group_tracks"));   // optional (K19)
+    o->window_group_incident_tracks = reinterpret_cast<decltype(o->window_group_incident_tracks)>(dlsym(dl, "sg_window_group_incident_tracks"));
+    o->window_group_tracks_ended = reinterpret_cast<decltype(o->window_group_tracks_ended)>(dlsym(dl, "sg_window_group_tracks_ended"));
 #undef SG_SYM
     return true;
 }
@@ -341,6 +344,33 @@ long GraphDS::WorkloadIncidents(std::vector<sg_incident_out>* out, std::vector<u
         if (m && (rc = api_.window_group_node_incident(h_, nullptr, 0, node_incident->data(), m, &m)) != SG_OK) return rc;
     }
     return (long)out->size();
+}
+
+// ---- the workload tracks (K19) ----
+int GraphDS::SetWorkloadTracks(const sg_track_params* p) {
+    if (!api_.set_group_tracks) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_group_tracks(h_, p);
+}
+// a counted list of the last flushed window: the count first, then the rows
+template <class Row>
+static long counted_rows(sg_handle h, int (*read)(sg_handle, Row*, size_t, size_t*), std::vector<Row>* out) {
+    size_t n = 0;
+    int rc = read(h, nullptr, 0, &n);
+    if (rc != SG_OK) return rc;
+    out->assign(n, Row{});
+    if (n && (rc = read(h, out->data(), n, &n)) != SG_OK) return rc;
+    return (long)out->size();
+}
+long GraphDS::WorkloadIncidentTracks(std::vector<sg_incident_track>* out) {
+    if (!out || !api_.window_group_incident_tracks) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return counted_rows(h_, api_.window_group_incident_tracks, out);
+}
+long GraphDS::WorkloadTracksEnded(std::vector<sg_track_entry>* out) {
+    if (!out || !api_.window_group_tracks_ended) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return counted_rows(h_, api_.window_group_tracks_ended, out);
 }
 
 // processPod keeps PodIPToPodUid (aggregator/persist.go:55-71); pods without an IP never reach the

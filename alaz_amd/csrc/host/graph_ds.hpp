@@ -68,6 +68,11 @@ struct SgApi {
     int (*set_group_incidents)(sg_handle, const sg_incident_params*) = nullptr;
     int (*window_group_incidents)(sg_handle, sg_incident_out*, size_t, size_t*) = nullptr;
     int (*window_group_node_incident)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
+    // optional (K19; absent in an older library): SetWorkloadTracks, WorkloadIncidentTracks and WorkloadTracksEnded each need the
+    // entry they forward to
+    int (*set_group_tracks)(sg_handle, const sg_track_params*) = nullptr;
+    int (*window_group_incident_tracks)(sg_handle, sg_incident_track*, size_t, size_t*) = nullptr;
+    int (*window_group_tracks_ended)(sg_handle, sg_track_entry*, size_t, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -204,6 +209,13 @@ public:
     // WorkloadNodes (SG_NO_INCIDENT: none).  It returns the incident count, < 0 on an engine error.
     int SetWorkloadIncidents(const sg_incident_params* p);
     long WorkloadIncidents(std::vector<sg_incident_out>* out, std::vector<uint32_t>* node_incident);
+    // The workload tracks (K19; needs SetWorkloadIncidents): the workload incidents followed across windows, so that an incident keeps
+    // its id through a rollout.  SetWorkloadTracks forwards sg_set_group_tracks (p NULL: off; the engine's return code; SG_EINVAL
+    // without the entry).  WorkloadIncidentTracks: row i is the track of WorkloadIncidents' row i of the last flushed window;
+    // WorkloadTracksEnded: the tracks that went quiet in it, as they stood.  Both: the count, or a negative SG_* code.
+    int SetWorkloadTracks(const sg_track_params* p);
+    long WorkloadIncidentTracks(std::vector<sg_incident_track>* out);
+    long WorkloadTracksEnded(std::vector<sg_track_entry>* out);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }

@@ -30,6 +30,7 @@ struct MockEngine {
     std::vector<std::array<uint64_t, 4>> k15_ops;      // {1, shift, warmup, ttl} per sg_set_group_trend, {2, silent_windows, min_seen, max_rows} per sg_set_group_vanished (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_groups_top
     std::vector<std::array<uint64_t, 4>> k16_ops;      // {1, on, 0, 0} per sg_set_group_nodes, {2, shift, warmup, ttl} per sg_set_group_node_trend (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_group_nodes_top
     std::vector<std::array<uint64_t, 4>> k17_ops;      // {1, iters, damping_q8, seed} per sg_set_group_rank (NULL: ~0 in the three), {2, k, the bits of min_share, cap} per sg_window_group_rank_top
+    std::vector<std::array<uint64_t, 4>> k19_ops;      // {1, quiet_windows, max_tracks, reserved} per sg_set_group_tracks (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incident_tracks, {3, cap, 0, 0} per sg_window_group_tracks_ended
     std::vector<std::array<uint64_t, 4>> k18_ops;      // {1, by, the bits of min_value, reserved} per sg_set_group_incidents (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incidents, {3, n_index, cap, 0} per sg_window_group_node_incident
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
 };
@@ -167,6 +168,28 @@ int m_window_group_incidents(sg_handle h, sg_incident_out* out, size_t cap, size
     for (size_t i = 0; out && i < std::min<size_t>(2, cap); i++) out[i] = e[i];
     return SG_OK;
 }
+// K19's stand-ins: the switch recorded; the tracks of K18's two incidents (track 4 continued into its third window, track 7 opened
+// as a split of it) and one ended entry
+int m_set_group_tracks(sg_handle h, const sg_track_params* p) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k19_ops.push_back({1u, p ? p->quiet_windows : ~0ull, p ? p->max_tracks : ~0ull, p ? p->reserved : ~0ull}); return SG_OK;
+}
+int m_window_group_incident_tracks(sg_handle h, sg_incident_track* out, size_t cap, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k19_ops.push_back({2u, (uint64_t)cap, 0u, 0u});
+    if (n) *n = 2;
+    const sg_incident_track e[2] = {{4u, SG_NO_TRACK, 1u, 3u, 2u, 0u, 0u, 0u}, {7u, 4u, 3u, 1u, 0u, 0u, 1u, SG_TRACK_NEW | SG_TRACK_SPLIT}};
+    for (size_t i = 0; out && i < std::min<size_t>(2, cap); i++) out[i] = e[i];
+    return SG_OK;
+}
+int m_window_group_tracks_ended(sg_handle h, sg_track_entry* out, size_t cap, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k19_ops.push_back({3u, (uint64_t)cap, 0u, 0u});
+    if (n) *n = 1;
+    const sg_track_entry e = {5u, 4u, 1u, 2u, 2u, 3u, 17ull, 2ull};
+    if (out && cap) out[0] = e;
+    return SG_OK;
+}
 int m_window_group_node_incident(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
     M_LOCK(h);
     reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({3u, (uint64_t)n_idx, (uint64_t)cap, 0u});
@@ -265,6 +288,8 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.set_group_nodes = m_set_group_nodes; c->api.window_group_nodes = m_window_group_nodes; c->api.set_group_node_trend = m_set_group_node_trend;
         c->api.window_group_node_trend = m_window_group_node_trend; c->api.window_group_nodes_top = m_window_group_nodes_top;
         c->api.set_group_rank = m_set_group_rank; c->api.window_group_rank_top = m_window_group_rank_top;
+        c->api.set_group_tracks = m_set_group_tracks; c->api.window_group_incident_tracks = m_window_group_incident_tracks;
+        c->api.window_group_tracks_ended = m_window_group_tracks_ended;
         c->api.set_group_incidents = m_set_group_incidents; c->api.window_group_incidents = m_window_group_incidents;
         c->api.window_group_node_incident = m_window_group_node_incident;
     }
@@ -416,6 +441,23 @@ long sgh_graphds_workload_incidents(void* g, sg_incident_out* out, size_t cap, u
     if (out && !v.empty()) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_incident_out));
     if (node_incident && !ni.empty()) std::memcpy(node_incident, ni.data(), std::min(node_cap, ni.size()) * sizeof(uint32_t));
     if (n_nodes) *n_nodes = ni.size();
+    return n;
+}
+// the workload tracks (K19): the switch (on = 0: off) and the last flushed window's track rows and ended list as the engine gives them
+int sgh_graphds_set_workload_tracks(void* g, int on, uint32_t quiet_windows, uint32_t max_tracks) {
+    sg_track_params p{}; p.struct_size = sizeof p; p.quiet_windows = quiet_windows; p.max_tracks = max_tracks;
+    return static_cast<HostCtx*>(g)->ds->SetWorkloadTracks(on ? &p : nullptr);
+}
+long sgh_graphds_workload_incident_tracks(void* g, sg_incident_track* out, size_t cap) {
+    std::vector<sg_incident_track> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadIncidentTracks(&v);
+    if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_incident_track));
+    return n;
+}
+long sgh_graphds_workload_tracks_ended(void* g, sg_track_entry* out, size_t cap) {
+    std::vector<sg_track_entry> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadTracksEnded(&v);
+    if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_track_entry));
     return n;
 }
 int sgh_graphds_ingest_wire(void* g, const uint8_t* recs, size_t n, const uint32_t* kafka_msgs) {
@@ -720,6 +762,14 @@ size_t sgh_mock_k18_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k18_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k18_ops[i].data(), 32);
     return m->k18_ops.size();
+}
+size_t sgh_mock_k19_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k19_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k19_ops[i].data(), 32);
+    return m->k19_ops.size();
 }
 size_t sgh_mock_group_ops(void* g, uint32_t* out2, size_t cap) {
     auto* c = static_cast<HostCtx*>(g); if (!c->mock) return 0;

@@ -35,6 +35,7 @@
 #include "sg_group_nodes.h"
 #include "sg_group_rank.h"
 #include "sg_group_incident.h"
+#include "sg_group_track.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -213,7 +214,8 @@ struct sg_engine {
     template <class Plan>
     struct Incidents : IncidentState { Plan plan; };
     Incidents<sgplan::IncidentPlan> inc;
-    // K13, the tracks (sg_track.h): allocated at sg_set_tracks (sg_plan.hpp plan_tracks), one allocation, freed with the incidents.
+    // The tracks (sg_track.h), K13's over the incidents (trk, sg_plan.hpp plan_tracks) or K19's over the workload incidents (gtrk,
+    // plan_group_tracks; sg_group_track.h): allocated at sg_set_tracks / sg_set_group_tracks, one allocation, freed with its incidents.
     // Kept across windows: the members by anchor key, the table and its counters twice (cur: the copy the next window reads).  The
     // per-incident scratch, the claim words and the workgroup counts are shared by the window slots: the event chains the updates in
     // window order across the slots' streams.  Per slot: the rows, the ended list, its count, and whether the window was tracked.
@@ -221,7 +223,8 @@ struct sg_engine {
                     sg_track_entry* tab[2] = {nullptr, nullptr}; TrkState* st[2] = {nullptr, nullptr}; u32 cur = 0; u64 w = 0;
                     u32* cand = nullptr; u32* kept = nullptr; u32* moved = nullptr; u32* joined = nullptr; u32* pos = nullptr; u32* tv = nullptr;
                     u64* claim = nullptr; u32* blk = nullptr; std::vector<sg_incident_track*> rows; std::vector<sg_track_entry*> ended;
-                    std::vector<u64*> ended_count; std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } trk;
+                    std::vector<u64*> ended_count; std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; };
+    Tracks trk;
     // K14, the groups (sg_group.h): allocated at sg_set_groups (sg_plan.hpp plan_groups), one allocation; needs none of K8 - K13.  The
     // group map, the sort's ping-pong buffers, the digit counts, the fold's partials and the head counts are scratch shared by the
     // window slots: every contraction waits for the previous one (ev), whichever slot's stream it runs on.  The host keeps the map
@@ -248,6 +251,8 @@ struct sg_engine {
     // K17, the workload ranking, and K18, the workload incidents: the ranking and the incidents over the workload rows, freed with them
     Rank<sgplan::GroupRankPlan> grank;
     Incidents<sgplan::GroupIncidentPlan> ginc;
+    // K19, the workload tracks: the tracks over the workload incidents, freed with them
+    Tracks gtrk;
 };
 
 namespace {
@@ -753,12 +758,14 @@ constexpr StageWords kGroupNodesWords{"the workload rows are off (sg_set_group_n
 constexpr StageWords kGroupNodeTrendWords{"the workload trend is off (sg_set_group_node_trend)", "the workload trend was off"};
 constexpr StageWords kGroupRankWords{"the workload ranking is off (sg_set_group_rank)", "the workload ranking was off"};
 constexpr StageWords kGroupIncidentsWords{"the workload incidents are off (sg_set_group_incidents)", "the workload incidents were off"};
+constexpr StageWords kGroupTracksWords{"workload tracking is off (sg_set_group_tracks)", "workload tracking was off"};
 constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
 // A node space: what the baseline, the selection, the ranking, the incidents and the readbacks over node rows work on — K9's nodes
 // or K16's workloads.  Its rollup, its baseline, its selection scratch, the rows a window can have, and how its messages name it:
 // the rollup, the baseline, "<sel>: ..." of a selection, "... beyond the window's <rows_of>".  Then its ranking and its incidents
 // (K11 and K12, or K17 and K18) with how they go off (K12 takes K13 with it) and their words, "<rsel>: ..." of a selection by rank,
-// and the edge baseline the incidents' trend key reads (K8's or K15's) with "... by a trend key: <edge_trend_off>".
+// and the edge baseline the incidents' trend key reads (K8's or K15's) with "... by a trend key: <edge_trend_off>".  Last its
+// tracks (K13 or K19) and their words.
 void free_incidents(sg_engine* e);
 void free_group_incidents(sg_engine* e);
 struct NodeSpace {
@@ -767,15 +774,17 @@ struct NodeSpace {
     sg_engine::RankState* rank; sg_engine::IncidentState* inc; void (*inc_off)(sg_engine*);
     StageWords rank_w, inc_w; const char* rsel_w;
     const sg_engine::Baseline<sg_edge_trend>* edge_trend; const char* edge_trend_off;
+    sg_engine::Tracks* trk; StageWords trk_w;
 };
 NodeSpace node_space(sg_engine* e) {
     return {&e->nodes, &e->ntrend, &e->nsel, e->plan.ncap, kNodesWords, kNodeTrendWords, "node selection", "nodes",
-            &e->rank, &e->inc, free_incidents, kRankWords, kIncidentsWords, "rank selection", &e->trend, kTrendWords.off};
+            &e->rank, &e->inc, free_incidents, kRankWords, kIncidentsWords, "rank selection", &e->trend, kTrendWords.off,
+            &e->trk, kTracksWords};
 }
 NodeSpace workload_space(sg_engine* e) {
     return {&e->gnodes, &e->gntrend, &e->gnsel, e->gnodes.plan.nc, kGroupNodesWords, kGroupNodeTrendWords, "workload selection", "workload rows",
             &e->grank, &e->ginc, free_group_incidents, kGroupRankWords, kGroupIncidentsWords, "workload rank selection", &e->gtrend,
-            kGroupTrendWords.off};
+            kGroupTrendWords.off, &e->gtrk, kGroupTracksWords};
 }
 // An edge space: what an edge baseline, its vanished list and their readbacks work on — the service map's edges (K8) or K14's group
 // edges (K15).  Its baseline, its list, how their messages name them, and the node space over it: the one whose incidents may key
@@ -981,19 +990,21 @@ int launch_incidents(sg_engine* e, hipStream_t s) {
     a.kinc = e->inc.kinc;
     return launch_grouping(e, node_space(e), P, s, a, a.nd, P.grid_wgs, k12_init, k12_hook, k12_label, k12_number, k12_nodes, k12_rows, k12_finish);
 }
-// ---- K13, the tracks (engine lock held) --------------------------------------------------------------------------------------------
+// ---- K13 and K19, the tracks (engine lock held) ------------------------------------------------------------------------------------
 static_assert(sgplan::kTrkThreads == K13_THREADS && sgplan::kTrkMaxWgs == K13_MAX_WGS && sgplan::kTrkBlkWords == K13_BLK_WORDS &&
               sgplan::kTrkStateBytes == sizeof(TrkState) && K13_MAX_WGS <= K13_SCAN_THREADS, "plan_tracks sizes the launches of sg_track.h");
-// enqueue the tracking of the window in slot cur on stream s (behind its grouping, on the same stream) and behind the previous
-// window's tracking (any stream): eight plain launches; the rows and the ended list go to the slot's buffers, the state flips
-int launch_tracks(sg_engine* e, hipStream_t s) {
+// enqueue the tracking of node space ns's incidents of the window in slot cur on stream s (behind its grouping, on the same stream)
+// and behind the space's previous tracking (any stream): eight plain launches, look(grid, threads, a) and members(grid, threads, a)
+// the two that know the space's anchors; the rows and the ended list go to the slot's buffers, the state flips
+template <class Look, class Members>
+int launch_tracks(sg_engine* e, const NodeSpace& ns, hipStream_t s, Look look, Members members) {
     sg_engine::WinSlot& w = work(e);
-    sg_engine::Tracks& x = e->trk;
+    sg_engine::Tracks& x = *ns.trk;
     const sgplan::TrackPlan& P = x.plan;
     TrkArgs a{};
-    a.nd = nodes_view(e, w, P.ncap);                                  // (k9_node reads the id spaces only)
-    a.nodes = e->nodes.rows[e->cur]; a.ncount = e->nodes.count[e->cur];
-    a.inc = e->inc.rows[e->cur]; a.icount = e->inc.count[e->cur]; a.node_inc = e->inc.node_inc[e->cur];
+    a.nd = nodes_view(e, w, P.ncap);                                  // (the anchor keys read the id spaces only; ncap: the space's rows)
+    a.nodes = ns.roll->rows[e->cur]; a.ncount = ns.roll->count[e->cur];
+    a.inc = ns.inc->rows[e->cur]; a.icount = ns.inc->count[e->cur]; a.node_inc = ns.inc->node_inc[e->cur];
     a.w = (u32)x.w; a.quiet = x.p.quiet_windows; a.max_tracks = P.max_tracks; a.per = P.per;
     a.mtrack = x.mtrack; a.mlast = x.mlast;
     a.told = x.tab[x.cur]; a.tnew = x.tab[x.cur ^ 1]; a.sold = x.st[x.cur]; a.snew = x.st[x.cur ^ 1];
@@ -1002,17 +1013,21 @@ int launch_tracks(sg_engine* e, hipStream_t s) {
     if (const int rc = stage_wait(e, x, s)) return rc;
     const dim3 nt(K13_THREADS), ng(P.node_wgs), fg(P.fold_wgs), sg(P.wgs);
     hipLaunchKernelGGL(k13_init, dim3(P.init_wgs), nt, 0, s, a);
-    hipLaunchKernelGGL(k13_look, fg, nt, 0, s, a);
+    look(fg, nt, a);
     hipLaunchKernelGGL(k13_fold, fg, nt, 0, s, a);
     hipLaunchKernelGGL(k13_claim, ng, nt, 0, s, a);
     hipLaunchKernelGGL(k13_count, sg, nt, 0, s, a);
     hipLaunchKernelGGL(k13_scan, dim3(1), dim3(K13_SCAN_THREADS), 0, s, a, P.wgs);
     hipLaunchKernelGGL(k13_write, sg, nt, 0, s, a);
-    hipLaunchKernelGGL(k13_members, ng, nt, 0, s, a);
+    members(ng, nt, a);
     if (const int rc = stage_done(e, x, s)) return rc;
     x.valid[e->cur] = 1;
     x.cur ^= 1; x.w += 1;
     return SG_OK;
+}
+int launch_node_tracks(sg_engine* e, hipStream_t s) {
+    return launch_tracks(e, node_space(e), s, [s](dim3 g, dim3 nt, const TrkArgs& a) { hipLaunchKernelGGL(k13_look, g, nt, 0, s, a); },
+                         [s](dim3 g, dim3 nt, const TrkArgs& a) { hipLaunchKernelGGL(k13_members, g, nt, 0, s, a); });
 }
 void free_tracks(sg_engine* e) { free_stage(e->trk); }
 
@@ -1141,7 +1156,18 @@ int launch_group_incidents(sg_engine* e, hipStream_t s) {
     a.pos = e->ginc.pos; a.esrc = e->ginc.esrc;
     return launch_grouping(e, workload_space(e), P, s, a, a.g.nd, P.fold_wgs, k18_init, k18_hook, k18_label, k18_number, k18_nodes, k18_rows, k18_finish);
 }
-void free_group_incidents(sg_engine* e) { free_stage(e->ginc); }
+// ---- K19, the workload tracks (engine lock held) -----------------------------------------------------------------------------------
+// launch_tracks over the workload incidents (behind K18 on the same stream): k19_look and k19_members know the workload anchors
+int launch_group_tracks(sg_engine* e, hipStream_t s) {
+    const u32 mg = e->gnodes.plan.max_groups;
+    return launch_tracks(e, workload_space(e), s, [s, mg](dim3 g, dim3 nt, const TrkArgs& a) { hipLaunchKernelGGL(k19_look, g, nt, 0, s, a, mg); },
+                         [s, mg](dim3 g, dim3 nt, const TrkArgs& a) { hipLaunchKernelGGL(k19_members, g, nt, 0, s, a, mg); });
+}
+void free_group_tracks(sg_engine* e) { free_stage(e->gtrk); }
+void free_group_incidents(sg_engine* e) {
+    free_group_tracks(e);
+    free_stage(e->ginc);
+}
 // an index selection's block off (the workload rows': its sizes are the stage's; every one at sg_destroy)
 template <class Row>
 void free_idxsel(sg_engine::IdxSel<Row>& s) {
@@ -1211,7 +1237,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (e->ntrend.on) { if (const int rc = launch_node_trend(e, node_space(e), s, k10_count, k10_write)) return rc; }
         if (e->rank.on) { if (const int rc = launch_rank(e, s)) return rc; }   // K11 behind K9: the rows, the counters, the node rows and their count
         if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
-        if (e->trk.on) { if (const int rc = launch_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
+        if (e->trk.on) { if (const int rc = launch_node_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
     }
     if (e->grp.on) {                                                 // K14 behind K5: the rows and the window counters only, whatever else is on
         if (const int rc = launch_groups(e, s)) return rc;
@@ -1221,6 +1247,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
             if (e->gntrend.on) { if (const int rc = launch_node_trend(e, workload_space(e), s, k16_tcount, k16_twrite)) return rc; }
             if (e->grank.on) { if (const int rc = launch_group_rank(e, s)) return rc; }   // K17 behind K16 and its baseline: the group edges, the workload rows and their count
             if (e->ginc.on) { if (const int rc = launch_group_incidents(e, s)) return rc; }   // K18 behind K15, K16 and K17: the group trend rows, the workload rows, the rank rows
+            if (e->gtrk.on) { if (const int rc = launch_group_tracks(e, s)) return rc; }   // K19 behind K18: the workload rows, the incident rows, the incident per workload row
         }
     }
     return SG_OK;
@@ -1851,6 +1878,83 @@ int incidents_buffer(sg_engine* e, const NodeSpace& ns, const char* call, void**
     int slot;
     if (const int rc = stage_slot(e, x, call, ns.inc_w, &slot)) return rc;
     *d_incidents = x.rows[slot]; *d_count = x.count[slot]; *d_node_incident = x.node_inc[slot];
+    return SG_OK;
+}
+// the tracks of node space ns on with parameters p (NULL: off) over rows of capacity ncap: plan(max_tracks, slots) plans them; one
+// block — the members, the table and its counters twice, the scratch and every slot's rows, ended list and count; an empty state
+template <class MakePlan>
+int tracks_set(sg_engine* e, const NodeSpace& ns, const char* call, const sg_track_params* p, u32 ncap, MakePlan plan) {
+    if (!ns.inc->on) { e->err = std::string(call) + ": " + ns.inc_w.off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    sg_track_params q{};
+    if (p && sgplan::check_tracks(*p, ncap, &q)) { e->err = std::string(call) + ": bad parameters"; return SG_EINVAL; }
+    sg_engine::Tracks& x = *ns.trk;
+    free_stage(x);
+    if (!p) return SG_OK;
+    const u32 slots = (u32)e->slots.size();
+    x.p = q;
+    x.plan = plan(q.max_tracks, slots);
+    const sgplan::TrackPlan& P = x.plan;
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, call, [&x] { free_stage(x); })) return rc;
+    x.mtrack = at<u32>(x.mem, P.member_off[0]); x.mlast = at<u32>(x.mem, P.member_off[1]);
+    for (int k = 0; k < 2; k++) { x.tab[k] = at<sg_track_entry>(x.mem, P.table_off[k]); x.st[k] = at<TrkState>(x.mem, P.state_off[k]); }
+    x.cand = at<u32>(x.mem, P.inc_off[0]); x.kept = at<u32>(x.mem, P.inc_off[1]); x.moved = at<u32>(x.mem, P.inc_off[2]);
+    x.joined = at<u32>(x.mem, P.inc_off[3]); x.pos = at<u32>(x.mem, P.inc_off[4]); x.tv = at<u32>(x.mem, P.inc_off[5]);
+    x.claim = at<u64>(x.mem, P.claim_off);
+    x.blk = at<u32>(x.mem, P.blk_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = x.mem + P.slot.off + k * P.slot.bytes;
+        x.rows.push_back(at<sg_incident_track>(s, P.slot_rows)); x.ended.push_back(at<sg_track_entry>(s, P.slot_ended));
+        x.ended_count.push_back(at<u64>(s, P.slot_count));
+    }
+    // an empty state: no member (SG_NO_TRACK everywhere); the block is zeroed: no entry, next id 0
+    hipError_t rc = hipMemset(x.mtrack, 0xFF, P.member_bytes);
+    if (rc == hipSuccess) rc = hipDeviceSynchronize();               // (the slots' streams do not wait for the null stream)
+    if (rc != hipSuccess) { free_stage(x); e->err = std::string(call) + ": hipMemset: " + hipGetErrorString(rc); return SG_ENODEV; }
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+// row i belongs to incident i of the last read window
+int tracks_read(sg_engine* e, const NodeSpace& ns, const char* call, sg_incident_track* out, size_t cap, size_t* n) {
+    const sg_engine::Tracks& x = *ns.trk;
+    if (const int rc = stage_ready(e, x, call, ns.trk_w)) return rc;
+    return copy_counted(e, ns.inc->count[e->cur], x.rows[e->cur], sizeof(sg_incident_track), out, cap, n);
+}
+int tracks_ended(sg_engine* e, const NodeSpace& ns, const char* call, sg_track_entry* out, size_t cap, size_t* n) {
+    const sg_engine::Tracks& x = *ns.trk;
+    if (const int rc = stage_ready(e, x, call, ns.trk_w)) return rc;
+    return copy_counted(e, x.ended_count[e->cur], x.ended[e->cur], sizeof(sg_track_entry), out, cap, n);
+}
+int tracks_buffer(sg_engine* e, const NodeSpace& ns, const char* call, void** d_tracks, void** d_ended, void** d_ended_count) {
+    const sg_engine::Tracks& x = *ns.trk;
+    int slot;
+    if (const int rc = stage_slot(e, x, call, ns.trk_w, &slot)) return rc;
+    *d_tracks = x.rows[slot]; *d_ended = x.ended[slot]; *d_ended_count = x.ended_count[slot];
+    return SG_OK;
+}
+// the counters of the table the next window reads, behind the updates enqueued so far
+int track_state(sg_engine* e, const NodeSpace& ns, const char* call, TrkState* st) {
+    sg_engine::Tracks& x = *ns.trk;
+    if (!x.on) { e->err = std::string(call) + ": " + ns.trk_w.off; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    HIP_TRY(e, hipMemcpy(st, x.st[x.cur], sizeof(TrkState), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+int track_entries(sg_engine* e, const NodeSpace& ns, const char* call, sg_track_entry* out, size_t cap, size_t* n) {
+    TrkState st{};
+    if (const int rc = track_state(e, ns, call, &st)) return rc;
+    const sg_engine::Tracks& x = *ns.trk;
+    if (n) *n = st.n;
+    const size_t take = std::min((size_t)st.n, cap);
+    if (out && take) HIP_TRY(e, hipMemcpy(out, x.tab[x.cur], take * sizeof(sg_track_entry), hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+int track_stats(sg_engine* e, const NodeSpace& ns, const char* call, sg_track_stats* out) {
+    TrkState st{};
+    if (const int rc = track_state(e, ns, call, &st)) return rc;
+    out->windows = ns.trk->w; out->live = st.n; out->opened = st.opened; out->dropped_cap = st.dropped;
     return SG_OK;
 }
 }  // namespace
@@ -3198,82 +3302,69 @@ int sg_window_group_incidents_buffer(sg_handle e, void** d_incidents, void** d_c
 int sg_set_tracks(sg_handle e, const sg_track_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
-    if (!e->inc.on) { e->err = "sg_set_tracks: the incidents are off (sg_set_incidents)"; return SG_ESTATE; }
-    if (e->closing || e->flush_open) { e->err = "sg_set_tracks while a flush is open"; return SG_ESTATE; }
-    sg_track_params q{};
-    if (p && sgplan::check_tracks(*p, e->nodes.plan.ncap, &q)) { e->err = "sg_set_tracks: bad parameters"; return SG_EINVAL; }
-    free_tracks(e);
-    if (!p) return SG_OK;
-    sg_engine::Tracks& x = e->trk;
-    const u32 slots = (u32)e->slots.size();
-    x.p = q;
-    x.plan = sgplan::plan_tracks(e->cfg.max_known_nodes, e->cfg.max_labels, e->nodes.plan.ncap, q.max_tracks, slots);
-    const sgplan::TrackPlan& P = x.plan;
-    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
-    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_tracks", [e] { free_tracks(e); })) return rc;
-    x.mtrack = at<u32>(x.mem, P.member_off[0]); x.mlast = at<u32>(x.mem, P.member_off[1]);
-    for (int k = 0; k < 2; k++) { x.tab[k] = at<sg_track_entry>(x.mem, P.table_off[k]); x.st[k] = at<TrkState>(x.mem, P.state_off[k]); }
-    x.cand = at<u32>(x.mem, P.inc_off[0]); x.kept = at<u32>(x.mem, P.inc_off[1]); x.moved = at<u32>(x.mem, P.inc_off[2]);
-    x.joined = at<u32>(x.mem, P.inc_off[3]); x.pos = at<u32>(x.mem, P.inc_off[4]); x.tv = at<u32>(x.mem, P.inc_off[5]);
-    x.claim = at<u64>(x.mem, P.claim_off);
-    x.blk = at<u32>(x.mem, P.blk_off);
-    for (u32 k = 0; k < slots; k++) {
-        char* s = x.mem + P.slot.off + k * P.slot.bytes;
-        x.rows.push_back(at<sg_incident_track>(s, P.slot_rows)); x.ended.push_back(at<sg_track_entry>(s, P.slot_ended));
-        x.ended_count.push_back(at<u64>(s, P.slot_count));
-    }
-    // an empty state: no member (SG_NO_TRACK everywhere); the block is zeroed: no entry, next id 0
-    hipError_t rc = hipMemset(x.mtrack, 0xFF, P.member_bytes);
-    if (rc == hipSuccess) rc = hipDeviceSynchronize();               // (the slots' streams do not wait for the null stream)
-    if (rc != hipSuccess) { free_tracks(e); e->err = std::string("sg_set_tracks: hipMemset: ") + hipGetErrorString(rc); return SG_ENODEV; }
-    x.valid.assign(slots, 0);
-    x.on = true;
-    return SG_OK;
+    return tracks_set(e, node_space(e), "sg_set_tracks", p, e->nodes.plan.ncap, [e](u32 max_tracks, u32 slots) {
+        return sgplan::plan_tracks(e->cfg.max_known_nodes, e->cfg.max_labels, e->nodes.plan.ncap, max_tracks, slots);
+    });
 }
 int sg_window_incident_tracks(sg_handle e, sg_incident_track* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = stage_ready(e, e->trk, "sg_window_incident_tracks", kTracksWords)) return rc;
-    return copy_counted(e, e->inc.count[e->cur], e->trk.rows[e->cur], sizeof(sg_incident_track), out, cap, n);
+    return tracks_read(e, node_space(e), "sg_window_incident_tracks", out, cap, n);
 }
 int sg_window_tracks_ended(sg_handle e, sg_track_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = stage_ready(e, e->trk, "sg_window_tracks_ended", kTracksWords)) return rc;
-    return copy_counted(e, e->trk.ended_count[e->cur], e->trk.ended[e->cur], sizeof(sg_track_entry), out, cap, n);
+    return tracks_ended(e, node_space(e), "sg_window_tracks_ended", out, cap, n);
 }
 int sg_window_tracks_buffer(sg_handle e, void** d_tracks, void** d_ended, void** d_ended_count) {
     if (!e || !d_tracks || !d_ended || !d_ended_count) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    const sg_engine::Tracks& x = e->trk;
-    int slot;
-    if (const int rc = stage_slot(e, x, "sg_window_tracks_buffer", kTracksWords, &slot)) return rc;
-    *d_tracks = x.rows[slot]; *d_ended = x.ended[slot]; *d_ended_count = x.ended_count[slot];
-    return SG_OK;
+    return tracks_buffer(e, node_space(e), "sg_window_tracks_buffer", d_tracks, d_ended, d_ended_count);
 }
 int sg_track_entries(sg_handle e, sg_track_entry* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::Tracks& x = e->trk;
-    if (!x.on) { e->err = "sg_track_entries: tracking is off (sg_set_tracks)"; return SG_ESTATE; }
-    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
-    TrkState st{};
-    HIP_TRY(e, hipMemcpy(&st, x.st[x.cur], sizeof(TrkState), hipMemcpyDeviceToHost));
-    if (n) *n = st.n;
-    const size_t take = std::min((size_t)st.n, cap);
-    if (out && take) HIP_TRY(e, hipMemcpy(out, x.tab[x.cur], take * sizeof(sg_track_entry), hipMemcpyDeviceToHost));
-    return SG_OK;
+    return track_entries(e, node_space(e), "sg_track_entries", out, cap, n);
 }
 int sg_track_stats_get(sg_handle e, sg_track_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::Tracks& x = e->trk;
-    if (!x.on) { e->err = "sg_track_stats_get: tracking is off (sg_set_tracks)"; return SG_ESTATE; }
-    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
-    TrkState st{};
-    HIP_TRY(e, hipMemcpy(&st, x.st[x.cur], sizeof(TrkState), hipMemcpyDeviceToHost));
-    out->windows = x.w; out->live = st.n; out->opened = st.opened; out->dropped_cap = st.dropped;
-    return SG_OK;
+    return track_stats(e, node_space(e), "sg_track_stats_get", out);
+}
+
+// ---- K19, the workload tracks: K13's code over the workload space ---------------------------------------------------------------
+int sg_set_group_tracks(sg_handle e, const sg_track_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    return tracks_set(e, workload_space(e), "sg_set_group_tracks", p, e->gnodes.plan.nc, [e](u32 max_tracks, u32 slots) {
+        const Dev& d = work(e).d;                                     // (the id spaces k19_look and k19_members bound the keys by)
+        return sgplan::plan_group_tracks(e->gnodes.plan.max_groups, d.max_known, d.max_labels, e->gnodes.plan.nc, max_tracks, slots);
+    });
+}
+int sg_window_group_incident_tracks(sg_handle e, sg_incident_track* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return tracks_read(e, workload_space(e), "sg_window_group_incident_tracks", out, cap, n);
+}
+int sg_window_group_tracks_ended(sg_handle e, sg_track_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return tracks_ended(e, workload_space(e), "sg_window_group_tracks_ended", out, cap, n);
+}
+int sg_window_group_tracks_buffer(sg_handle e, void** d_tracks, void** d_ended, void** d_ended_count) {
+    if (!e || !d_tracks || !d_ended || !d_ended_count) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return tracks_buffer(e, workload_space(e), "sg_window_group_tracks_buffer", d_tracks, d_ended, d_ended_count);
+}
+int sg_group_track_entries(sg_handle e, sg_track_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return track_entries(e, workload_space(e), "sg_group_track_entries", out, cap, n);
+}
+int sg_group_track_stats_get(sg_handle e, sg_track_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return track_stats(e, workload_space(e), "sg_group_track_stats_get", out);
 }
 
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.

@@ -939,10 +939,11 @@ struct TrackPlan {
     Slots slot; u64 slot_rows = 0, slot_ended = 0, slot_count = 0;
     std::vector<Piece> layout;
 };
-inline TrackPlan plan_tracks(u32 max_known, u32 max_labels, u32 ncap, u32 max_tracks, u32 slots) {
+// the tracks over rows of capacity ncap whose anchor keys are [0, anchors): K13's (plan_tracks) and K19's (plan_group_tracks)
+inline TrackPlan plan_track_block(u64 anchors, u32 ncap, u32 max_tracks, u32 slots) {
     TrackPlan r;
     const u64 NC = std::max<u32>(ncap, 1), MT = std::max<u32>(max_tracks, 1), span = std::max(NC, MT);
-    r.ncap = ncap; r.anchors = max_known + max_labels; r.max_tracks = max_tracks;
+    r.ncap = ncap; r.anchors = (u32)anchors; r.max_tracks = max_tracks;
     r.wgs = (u32)std::max<u64>(1, std::min<u64>(kTrkMaxWgs, (span + kTrkThreads - 1) / kTrkThreads));
     const u64 per = (span + r.wgs - 1) / r.wgs;
     r.per = (u32)((per + kTrkThreads - 1) / kTrkThreads * kTrkThreads);
@@ -951,7 +952,7 @@ inline TrackPlan plan_tracks(u32 max_known, u32 max_labels, u32 ncap, u32 max_tr
     r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kTrkMaxWgs, (NC + kTrkThreads - 1) / kTrkThreads));
     const u64 fold_rows = (u64)kTrkFoldRounds * kTrkThreads;
     r.fold_wgs = (u32)std::max<u64>(1, std::min<u64>(kTrkMaxWgs, (NC + fold_rows - 1) / fold_rows));
-    r.member_bytes = trend_align(std::max<u64>(r.anchors, 1) * 4);
+    r.member_bytes = trend_align(std::max<u64>(anchors, 1) * 4);
     r.table_bytes = trend_align(MT * sizeof(sg_track_entry));
     r.state_bytes = trend_align(kTrkStateBytes);
     r.inc_bytes = trend_align(NC * 4);
@@ -972,6 +973,9 @@ inline TrackPlan plan_tracks(u32 max_known, u32 max_labels, u32 ncap, u32 max_tr
                              {"ended_count", r.count_bytes, &r.slot_count}});
     r.total_bytes = b.end; r.layout = std::move(b.pieces);
     return r;
+}
+inline TrackPlan plan_tracks(u32 max_known, u32 max_labels, u32 ncap, u32 max_tracks, u32 slots) {
+    return plan_track_block(max_known + max_labels, ncap, max_tracks, slots);
 }
 
 // K14, the groups (sg_group.h): parameters and the device memory sg_set_groups allocates — never sg_create.  The key of a row is
@@ -1211,6 +1215,15 @@ inline GroupIncidentPlan plan_group_incidents(u64 max_edges, u32 nc, u64 gk, u32
         r.esrc_off = b.take("esrc", r.esrc_bytes);
     });
     return r;
+}
+
+// K19, the workload tracks (sg_group_track.h): K13's plan over the workload rows — sg_set_group_tracks allocates it, never
+// sg_set_groups, sg_set_group_nodes or sg_set_group_incidents.  The rows, the incident capacity and the ended capacity are K16's nc
+// (check_tracks with nc: max_tracks 0 = (quiet_windows + 1) * nc); the members are two u32 arrays by K16's group key below the
+// outbound IPs, anchors = max_groups + max_known + max_labels keys, counted in 64 bits: max_groups may reach 2^30, where one array
+// alone takes 4 GiB.
+inline TrackPlan plan_group_tracks(u32 max_groups, u32 max_known, u32 max_labels, u32 nc, u32 max_tracks, u32 slots) {
+    return plan_track_block((u64)max_groups + max_known + max_labels, nc, max_tracks, slots);
 }
 
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);

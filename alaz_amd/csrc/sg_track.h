@@ -24,6 +24,11 @@
 // k13_look and k13_fold fold as k12_nodes does: a wave whose active lanes name one incident reduces in registers, every
 // contribution then goes to an LDS table keyed by incident, and a workgroup touches device memory once per field and distinct
 // incident; only an incident that finds no slot is folded into device memory directly.
+//
+// Six of the eight see the space only through the row count and the capacities (nd.ncap); k13_look and k13_members also ask which
+// rows anchor.  k13_look's body is a template over a space policy (k13_look_t): sp.anchor(a, ref) is the anchor key of a row's ref,
+// K13_NONE for a row that is no anchor.  K13Space below is this stage's; K19's is in sg_group_track.h, beside its own k19_members
+// (k13_members as a template did not compile to the same code, so it stays as it was, written out).
 #pragma once
 
 #define K13_THREADS 256
@@ -63,6 +68,10 @@ __device__ __forceinline__ u32 k13_incidents_of(const TrkArgs& a) { const u64 I 
 __device__ __forceinline__ u32 k13_entries_of(const TrkArgs& a) { const u32 n = a.sold->n; return n < a.max_tracks ? n : a.max_tracks; }
 // the anchor key of a node row's ref, K13_NONE for an OBIP ref (and a ref beyond the id spaces)
 __device__ __forceinline__ u32 k13_anchor(const TrkArgs& a, u32 ref) { const u32 k = k9_node(a.nd, ref); return k < a.nd.mk + a.nd.ml ? k : K13_NONE; }
+// K13's space: K9's node keys
+struct K13Space {
+    __device__ __forceinline__ u32 anchor(const TrkArgs& a, u32 ref) const { return k13_anchor(a, ref); }
+};
 // the table position of track id, K13_NONE when the table lacks it
 __device__ __forceinline__ u32 k13_find(const sg_track_entry* t, u32 n, u32 id) {
     u32 lo = 0, hi = n;
@@ -80,7 +89,8 @@ __global__ __launch_bounds__(K13_THREADS) void k13_init(TrkArgs a) {
     }
 }
 
-__global__ __launch_bounds__(K13_THREADS) void k13_look(TrkArgs a) {
+template <class S>
+__device__ __forceinline__ void k13_look_t(TrkArgs a, S sp) {
     __shared__ u32 key[K12_SLOTS], mn[K12_SLOTS], jn[K12_SLOTS];
     const u32 t = threadIdx.x;
     for (u32 s = t; s < K12_SLOTS; s += K13_THREADS) { key[s] = K12_EMPTY; mn[s] = SG_NO_TRACK; jn[s] = 0; }
@@ -92,7 +102,7 @@ __global__ __launch_bounds__(K13_THREADS) void k13_look(TrkArgs a) {
         u32 i = SG_NO_INCIDENT, tv = SG_NO_TRACK;
         if (v < N) {
             const u32 ii = a.node_inc[v];
-            const u32 k = ii != SG_NO_INCIDENT ? k13_anchor(a, a.nodes[v].ref) : K13_NONE;
+            const u32 k = ii != SG_NO_INCIDENT ? sp.anchor(a, a.nodes[v].ref) : K13_NONE;
             if (k != K13_NONE) {
                 i = ii;
                 const u32 T = a.mtrack[k];
@@ -121,6 +131,8 @@ __global__ __launch_bounds__(K13_THREADS) void k13_look(TrkArgs a) {
         k13_min(&a.cand[i], mn[s]); k12_add(&a.joined[i], jn[s]);
     }
 }
+
+__global__ __launch_bounds__(K13_THREADS) void k13_look(TrkArgs a) { k13_look_t(a, K13Space{}); }
 
 __global__ __launch_bounds__(K13_THREADS) void k13_fold(TrkArgs a) {
     __shared__ u32 key[K12_SLOTS], kp[K12_SLOTS], mv[K12_SLOTS];

@@ -268,6 +268,10 @@ def _signatures() -> dict:
         "sg_set_group_incidents": (I, [H, P]), "sg_window_group_incidents": (I, [H, P, sz, Psz]),
         "sg_window_group_node_incident": (I, [H, P, sz, P, sz, Psz]),
         "sg_window_group_incidents_buffer": (I, [H, PP, PP, PP]),
+        "sg_set_group_tracks": (I, [H, P]), "sg_window_group_incident_tracks": (I, [H, P, sz, Psz]),
+        "sg_window_group_tracks_ended": (I, [H, P, sz, Psz]),
+        "sg_window_group_tracks_buffer": (I, [H, PP, PP, PP]),
+        "sg_group_track_entries": (I, [H, P, sz, Psz]), "sg_group_track_stats_get": (I, [H, P]),
     }
 
 
@@ -314,6 +318,8 @@ _STAGES = dict(
     group_incidents=_Stage("sg_set_group_incidents", SgIncidentParams, INCIDENT_DEFAULTS,
                            "set_group_incidents(None) switches the workload incidents off", "workload incident",
                            dict(by=lambda by: ServiceGraph._by(by) if isinstance(by, str) else by)),
+    group_tracks=_Stage("sg_set_group_tracks", SgTrackParams, TRACK_DEFAULTS, "set_group_tracks(None) switches workload tracking off",
+                        "workload track"),
 )
 
 _lib = None
@@ -993,6 +999,35 @@ class ServiceGraph:
         """(device pointer of the sg_incident_out rows, of their u64 count, of the u32 incident per workload row) of the window
         window_run closed last (sg_window_group_incidents_buffer)"""
         return self._pointers(self._l.sg_window_group_incidents_buffer, 3)
+
+    # ---- workload tracks (K19): the workload incidents followed across windows ----
+    def set_group_tracks(self, params: Optional[dict] = (), **kw):
+        """Switch the tracking of workload incidents across windows on (sg_set_group_tracks; set_tracks' parameters: quiet_windows
+        (default 2), max_tracks (0 = never cut); needs the workload incidents on; independent of set_tracks) or off:
+        set_group_tracks(None).  Any set_group_incidents call switches it off."""
+        self._set_stage("group_tracks", params, kw)
+
+    def window_group_incident_tracks(self) -> np.ndarray:
+        """TRACK_DTYPE rows of the last read window (sg_window_group_incident_tracks): row i is the track of
+        window_group_incidents()[i]"""
+        return self._counted(self._l.sg_window_group_incident_tracks, TRACK_DTYPE)
+
+    def window_group_tracks_ended(self) -> np.ndarray:
+        """TRACK_ENTRY_DTYPE entries of the workload tracks that went quiet in the last read window (sg_window_group_tracks_ended),
+        in id order"""
+        return self._counted(self._l.sg_window_group_tracks_ended, TRACK_ENTRY_DTYPE)
+
+    def window_group_tracks_buffer(self) -> Tuple[int, int, int]:
+        """(device pointer of the sg_incident_track rows, of the ended sg_track_entry list, of its u64 count) of the window
+        window_run closed last (sg_window_group_tracks_buffer)"""
+        return self._pointers(self._l.sg_window_group_tracks_buffer, 3)
+
+    def group_track_entries(self) -> np.ndarray:
+        """the live workload track table in id order, TRACK_ENTRY_DTYPE (sg_group_track_entries)"""
+        return self._counted(self._l.sg_group_track_entries, TRACK_ENTRY_DTYPE)
+
+    def group_track_stats(self) -> SgTrackStats:
+        return self._stats(self._l.sg_group_track_stats_get, SgTrackStats)
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

@@ -137,6 +137,9 @@ def load() -> C.CDLL:
             "sgh_graphds_workload_culprits": (C.c_long, [P, u32, C.c_float, P, P, sz]), "sgh_mock_k17_ops": (sz, [P, P, sz]),
             "sgh_graphds_set_workload_incidents": (C.c_int, [P, C.c_int, u32, C.c_float]),
             "sgh_graphds_workload_incidents": (C.c_long, [P, P, sz, P, sz, P]), "sgh_mock_k18_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_workload_tracks": (C.c_int, [P, C.c_int, u32, u32]),
+            "sgh_graphds_workload_incident_tracks": (C.c_long, [P, P, sz]), "sgh_graphds_workload_tracks_ended": (C.c_long, [P, P, sz]),
+            "sgh_mock_k19_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -591,6 +594,39 @@ class GraphDS:
         n = self._l.sgh_mock_k18_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k18_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the workload tracks (K19) ----
+    def set_workload_tracks(self, on: bool = True, quiet_windows: int = 2, max_tracks: int = 0) -> int:
+        """GraphDS::SetWorkloadTracks: the workload incidents followed across windows, on or off (rc)"""
+        return self._l.sgh_graphds_set_workload_tracks(self._g, 1 if on else 0, quiet_windows, max_tracks)
+
+    def _track_rows(self, read, dtype, what):
+        n = read(self._g, None, 0)
+        if n < 0:
+            raise RuntimeError(f"{what} failed: {n}")
+        out = np.zeros(max(n, 1), dtype=dtype)
+        read(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    def workload_incident_tracks(self) -> np.ndarray:
+        """GraphDS::WorkloadIncidentTracks: engine.TRACK_DTYPE rows of the last flushed window, row i the track of workload_incidents()'
+        row i"""
+        from .engine import TRACK_DTYPE
+        return self._track_rows(self._l.sgh_graphds_workload_incident_tracks, TRACK_DTYPE, "WorkloadIncidentTracks")
+
+    def workload_tracks_ended(self) -> np.ndarray:
+        """GraphDS::WorkloadTracksEnded: engine.TRACK_ENTRY_DTYPE entries of the workload tracks that went quiet in the last flushed window"""
+        from .engine import TRACK_ENTRY_DTYPE
+        return self._track_rows(self._l.sgh_graphds_workload_tracks_ended, TRACK_ENTRY_DTYPE, "WorkloadTracksEnded")
+
+    def mock_k19_ops(self) -> np.ndarray:
+        """the stand-in engine's K19 calls in order, four u64 each: (1, quiet_windows, max_tracks, reserved) per sg_set_group_tracks
+        (all ones in the three for NULL), (2, cap, 0, 0) per sg_window_group_incident_tracks, (3, cap, 0, 0) per
+        sg_window_group_tracks_ended"""
+        n = self._l.sgh_mock_k19_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k19_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

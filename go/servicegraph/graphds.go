@@ -892,6 +892,11 @@ func (g *GraphDS) WindowIncidentTracks() ([]IncidentTrack, error) {
 	if int(n) < len(trs) {
 		trs = trs[:int(n)]
 	}
+	return incidentTracksOf(trs), nil
+}
+
+// incidentTracksOf turns sg_incident_track rows, K13's or K19's, into IncidentTracks.
+func incidentTracksOf(trs []C.sg_incident_track) []IncidentTrack {
 	out := make([]IncidentTrack, len(trs))
 	for i := range trs {
 		tr, o := &trs[i], &out[i]
@@ -899,7 +904,7 @@ func (g *GraphDS) WindowIncidentTracks() ([]IncidentTrack, error) {
 		o.Kept, o.Moved, o.Joined = uint32(tr.kept_nodes), uint32(tr.moved_nodes), uint32(tr.joined_nodes)
 		o.New, o.Split, o.Merged = tr.flags&C.SG_TRACK_NEW != 0, tr.flags&C.SG_TRACK_SPLIT != 0, tr.flags&C.SG_TRACK_MERGED != 0
 	}
-	return out, nil
+	return out
 }
 
 // WindowTracksEnded returns the tracks that went quiet in the window FlushWindow returned last, as they stood, in id order
@@ -921,13 +926,18 @@ func (g *GraphDS) WindowTracksEnded() ([]TrackEntry, error) {
 	if int(n) < len(ents) {
 		ents = ents[:int(n)]
 	}
+	return trackEntriesOf(ents), nil
+}
+
+// trackEntriesOf turns sg_track_entry rows, K13's or K19's, into TrackEntries.
+func trackEntriesOf(ents []C.sg_track_entry) []TrackEntry {
 	out := make([]TrackEntry, len(ents))
 	for i := range ents {
 		en, o := &ents[i], &out[i]
 		o.Track, o.Parent, o.FirstWindow, o.LastWindow = uint32(en.track), uint32(en.parent), uint32(en.first_window), uint32(en.last_window)
 		o.Windows, o.PeakNodes, o.Count, o.Err = uint32(en.windows), uint32(en.peak_nodes), uint64(en.count), uint64(en.err)
 	}
-	return out, nil
+	return out
 }
 
 // GroupEdge is one edge of a window's service map contracted to workloads (sg_group_edge): every row from a pod of one group
@@ -1450,6 +1460,76 @@ func (g *GraphDS) WindowWorkloadIncidents() ([]Incident, error) {
 		o.FirstNode, o.TopNode, o.CulpritNode = uint32(inc.first_node), uint32(inc.top_node), uint32(inc.culprit_node)
 	}
 	return out, nil
+}
+
+// ---- workload tracks (K19) -----------------------------------------------------------------------------------------------
+
+// SetWorkloadTracks switches the tracking of workload incidents across windows on, behind SetWorkloadIncidents: K13's tracking
+// over the workload incidents and workload rows, so that an incident keeps its track when a rollout replaces every pod of a
+// Deployment.  quietWindows and maxTracks are SetTracks' (maxTracks 0: (quietWindows + 1) x the workload rows' capacity).  It is
+// independent of SetTracks.  ClearWorkloadTracks switches it off; every SetWorkloadIncidents / ClearWorkloadIncidents call,
+// SetWorkloadNodes(false) and any SetGroups call do so too.  A pod that moves to another workload does not take its membership
+// along: the old workload's fades after quietWindows.
+func (g *GraphDS) SetWorkloadTracks(quietWindows, maxTracks uint32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var tp C.sg_track_params
+	tp.struct_size = C.uint32_t(unsafe.Sizeof(tp))
+	tp.quiet_windows, tp.max_tracks = C.uint32_t(quietWindows), C.uint32_t(maxTracks)
+	if rc := C.sg_set_group_tracks(g.h, &tp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_group_tracks = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func (g *GraphDS) ClearWorkloadTracks() {
+	g.flushMu.Lock()
+	C.sg_set_group_tracks(g.h, nil)
+	g.flushMu.Unlock()
+}
+
+// WindowWorkloadIncidentTracks returns the track of every workload incident of the window FlushWindow returned last: element i
+// belongs to WindowWorkloadIncidents()[i] (sg_window_group_incident_tracks: one 32-byte row per incident crosses PCIe).
+func (g *GraphDS) WindowWorkloadIncidentTracks() ([]IncidentTrack, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_group_incident_tracks(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_incident_tracks = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	trs := make([]C.sg_incident_track, int(n))
+	if rc := C.sg_window_group_incident_tracks(g.h, &trs[0], C.size_t(len(trs)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_incident_tracks = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(n) < len(trs) {
+		trs = trs[:int(n)]
+	}
+	return incidentTracksOf(trs), nil
+}
+
+// WindowWorkloadTracksEnded returns the workload tracks that went quiet in the window FlushWindow returned last, as they stood, in
+// id order (sg_window_group_tracks_ended): each track is listed once, in its first silent window.
+func (g *GraphDS) WindowWorkloadTracksEnded() ([]TrackEntry, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_group_tracks_ended(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_tracks_ended = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	ents := make([]C.sg_track_entry, int(n))
+	if rc := C.sg_window_group_tracks_ended(g.h, &ents[0], C.size_t(len(ents)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_tracks_ended = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(n) < len(ents) {
+		ents = ents[:int(n)]
+	}
+	return trackEntriesOf(ents), nil
 }
 
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of

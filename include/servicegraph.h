@@ -974,6 +974,47 @@ int sg_window_group_node_incident(sg_handle h, const uint32_t* node_index, size_
  * sg_window_run closed last (valid until its slot is reused; read them on that window's stream).                                */
 int sg_window_group_incidents_buffer(sg_handle h, void** d_incidents, void** d_count, void** d_node_incident);
 
+/* ---- workload tracks (K19): each window's workload incidents followed across windows, on the device --------------------------- *
+ * Opt-in (sg_set_group_tracks, on an engine with the workload incidents); without it nothing is launched or allocated, and every
+ * other output is byte for byte the same either way.  K13 follows pod incidents: its members are keyed by pod and service node ids,
+ * so a rollout, which replaces every pod of a Deployment, makes the incident reappear as new tracks with parent == SG_NO_TRACK.  This
+ * stage is the "tracks" section above, steps 1 - 9 word for word, with "incident" read as "workload incident" (K18:
+ * sg_window_group_incidents, sg_window_group_node_incident) and "node row" read as "workload row" (K16: sg_window_group_nodes).  There
+ * is no new struct and no new constant: the parameters are sg_track_params (K13's checks), the rows sg_incident_track, the table and
+ * the ended list sg_track_entry, the counters sg_track_stats, "no track" SG_NO_TRACK, the flags SG_TRACK_*.  The differences:
+ *   anchor      a workload row whose ref is a GROUP, KNOWN or LABEL ref; an OBIP ref is no anchor.  The anchor key is K16's group key:
+ *               a group's id, max_groups + id for an ungrouped pod or service, max_groups + max_known_nodes + id for a label; the
+ *               outbound IPs' keys lie above those and never anchor, and a ref beyond the id spaces has no key.  A workload row has
+ *               a pod, a service or a workload at one end, so every workload incident has an anchor
+ *   members     kept by that key: max_groups + max_known_nodes + max_labels of them.  A member belongs to the KEY, not to the pods
+ *               behind it: nothing migrates a member when sg_group_assign moves a pod from one group to another or out of every
+ *               group.  The row then appears under its new key, which has a member of its own or none, and the old key's member
+ *               simply ages out after quiet_windows
+ *   w           the windows closed since sg_set_group_tracks switched it on (the first: 0)
+ *   capacities  the incidents and the ended list of a window are cut at the workload rows' capacity (min(max_groups + node
+ *               capacity, 2 x max_edges)); max_tracks 0 = (quiet_windows + 1) * that capacity: nothing is ever cut
+ * State: sg_set_group_tracks is SG_ESTATE with the workload incidents off (sg_set_group_incidents) or while a flush is open, SG_EINVAL
+ * on bad parameters; NULL = off (frees its memory); (re)enabling starts an empty state at w = 0, next id 0.  Memory is allocated
+ * there, never at sg_create or at any other sg_set_group_* call.  EVERY sg_set_group_incidents call, on or off, switches it off and
+ * frees it, and so does whatever frees the workload incidents: sg_set_group_nodes(h, 0), any sg_set_groups call,
+ * sg_set_group_trend(h, NULL) under a trend key.  It is independent of sg_set_tracks: both may be on in one engine, each with its
+ * own members, table, w and ids, and neither reads the other.  Reads of a window closed while it was off, and while a flush is
+ * open: SG_ESTATE.  Every close path computes it, behind K18 on the window's stream; with several windows in flight the state
+ * updates run in window order.  Under a map that groups nothing the workload rows are the node rows, and with the same parameters
+ * and both stages switched on before the same window the rows, ended lists, tables and counters equal K13's byte for byte.         */
+int sg_set_group_tracks(sg_handle h, const sg_track_params* p);
+/* Row i belongs to workload incident i of the last READ window (as sg_window_incident_tracks).                                  */
+int sg_window_group_incident_tracks(sg_handle h, sg_incident_track* out, size_t cap, size_t* n);
+/* The ended list of the last READ window (as sg_window_tracks_ended).                                                           */
+int sg_window_group_tracks_ended(sg_handle h, sg_track_entry* out, size_t cap, size_t* n);
+/* Device sg_incident_track[] (their count is sg_window_group_incidents_buffer's), the ended sg_track_entry[] and their count (one
+ * uint64_t) of the window sg_window_run closed last (valid until its slot is reused; read them on that window's stream).        */
+int sg_window_group_tracks_buffer(sg_handle h, void** d_tracks, void** d_ended, void** d_ended_count);
+/* The live table in id order (as sg_track_entries) and the counters (as sg_track_stats_get); both wait for the updates enqueued
+ * so far.                                                                                                                     */
+int sg_group_track_entries(sg_handle h, sg_track_entry* out, size_t cap, size_t* n);
+int sg_group_track_stats_get(sg_handle h, sg_track_stats* out);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
