@@ -40,6 +40,10 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->set_group_tracks = reinterpret_cast<decltype(o->set_group_tracks)>(dlsym(dl, "sg_set_group_tracks"));   // optional (K19)
     o->window_group_incident_tracks = reinterpret_cast<decltype(o->window_group_incident_tracks)>(dlsym(dl, "sg_window_group_incident_tracks"));
     o->window_group_tracks_ended = reinterpret_cast<decltype(o->window_group_tracks_ended)>(dlsym(dl, "sg_window_group_tracks_ended"));
+    o->set_quantiles = reinterpret_cast<decltype(o->set_quantiles)>(dlsym(dl, "sg_set_quantiles"));   // optional (K20)
+    o->window_node_quantiles = reinterpret_cast<decltype(o->window_node_quantiles)>(dlsym(dl, "sg_window_node_quantiles"));
+    o->window_group_quantiles = reinterpret_cast<decltype(o->window_group_quantiles)>(dlsym(dl, "sg_window_group_quantiles"));
+    o->window_group_node_quantiles = reinterpret_cast<decltype(o->window_group_node_quantiles)>(dlsym(dl, "sg_window_group_node_quantiles"));
 #undef SG_SYM
     return true;
 }
@@ -371,6 +375,36 @@ long GraphDS::WorkloadTracksEnded(std::vector<sg_track_entry>* out) {
     if (!out || !api_.window_group_tracks_ended) return SG_EINVAL;
     std::lock_guard<std::mutex> fg(flush_mu_);
     return counted_rows(h_, api_.window_group_tracks_ended, out);
+}
+
+// ---- the latency percentiles (K20) ----
+int GraphDS::SetQuantiles(uint32_t spaces, const uint32_t* permille, size_t n_q) {
+    if (!api_.set_quantiles) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    const int rc = api_.set_quantiles(h_, spaces, permille, n_q);
+    if (rc == SG_OK) n_q_ = n_q ? n_q : 2;
+    return rc;
+}
+// the quantiles of the last flushed window, `words` u32 an entity: the count first (no index), then the rows
+long GraphDS::LatencyRows(int (*read)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*), const uint32_t* index, size_t n_index,
+                          size_t words, std::vector<uint32_t>* out_us) {
+    if (!out_us || !read) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t n = index ? n_index : 0;
+    int rc;
+    if (!index && (rc = read(h_, nullptr, 0, nullptr, 0, &n)) != SG_OK) return rc;
+    out_us->assign(n * words, 0u);
+    if (n && (rc = read(h_, index, n_index, out_us->data(), n, &n)) != SG_OK) return rc;
+    return (long)n;
+}
+long GraphDS::NodeLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us) {
+    return LatencyRows(api_.window_node_quantiles, index, n_index, 2 * n_q_, out_us);
+}
+long GraphDS::WorkloadEdgeLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us) {
+    return LatencyRows(api_.window_group_quantiles, index, n_index, n_q_, out_us);
+}
+long GraphDS::WorkloadLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us) {
+    return LatencyRows(api_.window_group_node_quantiles, index, n_index, 2 * n_q_, out_us);
 }
 
 // processPod keeps PodIPToPodUid (aggregator/persist.go:55-71); pods without an IP never reach the

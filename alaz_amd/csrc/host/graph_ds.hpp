@@ -73,6 +73,11 @@ struct SgApi {
     int (*set_group_tracks)(sg_handle, const sg_track_params*) = nullptr;
     int (*window_group_incident_tracks)(sg_handle, sg_incident_track*, size_t, size_t*) = nullptr;
     int (*window_group_tracks_ended)(sg_handle, sg_track_entry*, size_t, size_t*) = nullptr;
+    // optional (K20; absent in an older library): SetQuantiles and the three latency reads each need the entry they forward to
+    int (*set_quantiles)(sg_handle, uint32_t, const uint32_t*, size_t) = nullptr;
+    int (*window_node_quantiles)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
+    int (*window_group_quantiles)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
+    int (*window_group_node_quantiles)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -216,6 +221,15 @@ public:
     int SetWorkloadTracks(const sg_track_params* p);
     long WorkloadIncidentTracks(std::vector<sg_incident_track>* out);
     long WorkloadTracksEnded(std::vector<sg_track_entry>* out);
+    // The latency percentiles (K20; the engine was created with SG_CFG_EDGE_HISTOGRAM): SetQuantiles forwards sg_set_quantiles
+    // (spaces: SG_Q_* bits, 0 = off; n_q 0: {500, 990}; the engine's return code; SG_EINVAL without the entry).  NodeLatency,
+    // WorkloadEdgeLatency and WorkloadLatency read the last flushed window's quantiles in microseconds — per node row [2][n_q]
+    // (out side, in side), per group edge [n_q], per workload row [2][n_q] — of every entity (index NULL) or of those at index,
+    // into out_us; they return the entity count, or a negative SG_* code.
+    int SetQuantiles(uint32_t spaces, const uint32_t* permille, size_t n_q);
+    long NodeLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us);
+    long WorkloadEdgeLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us);
+    long WorkloadLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }
@@ -265,6 +279,9 @@ private:
     std::mutex pk_mu_;                                 // packer_ (labels, prepared statements, HPACK state), dto_labels_
     L7Packer packer_;
     std::unordered_map<std::string, uint32_t> dto_labels_;   // labels seen through the PersistRequest tap share the packer's id space
+    size_t n_q_ = 2;                                   // quantiles per entity and side, as SetQuantiles set them last
+    long LatencyRows(int (*read)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*), const uint32_t* index, size_t n_index,
+                     size_t words, std::vector<uint32_t>* out_us);
     std::mutex flush_mu_;                              // one FlushWindow at a time; the selection below
     bool select_ = false; uint32_t sel_k_ = 0; float sel_min_ = 0;
     std::atomic<uint64_t> offered_{0}, batches_dropped_{0}, engine_errors_{0};

@@ -30,6 +30,8 @@ struct MockEngine {
     std::vector<std::array<uint64_t, 4>> k15_ops;      // {1, shift, warmup, ttl} per sg_set_group_trend, {2, silent_windows, min_seen, max_rows} per sg_set_group_vanished (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_groups_top
     std::vector<std::array<uint64_t, 4>> k16_ops;      // {1, on, 0, 0} per sg_set_group_nodes, {2, shift, warmup, ttl} per sg_set_group_node_trend (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_group_nodes_top
     std::vector<std::array<uint64_t, 4>> k17_ops;      // {1, iters, damping_q8, seed} per sg_set_group_rank (NULL: ~0 in the three), {2, k, the bits of min_share, cap} per sg_window_group_rank_top
+    std::vector<std::array<uint64_t, 4>> k20_ops;      // {1, spaces, n_q, the first four per-mille 16 bits each} per sg_set_quantiles, {2 / 3 / 4, n_index (~0: no index), cap, 0} per sg_window_node_quantiles / sg_window_group_quantiles / sg_window_group_node_quantiles
+    size_t k20_nq = 2;
     std::vector<std::array<uint64_t, 4>> k19_ops;      // {1, quiet_windows, max_tracks, reserved} per sg_set_group_tracks (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incident_tracks, {3, cap, 0, 0} per sg_window_group_tracks_ended
     std::vector<std::array<uint64_t, 4>> k18_ops;      // {1, by, the bits of min_value, reserved} per sg_set_group_incidents (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incidents, {3, n_index, cap, 0} per sg_window_group_node_incident
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
@@ -190,6 +192,29 @@ int m_window_group_tracks_ended(sg_handle h, sg_track_entry* out, size_t cap, si
     if (out && cap) out[0] = e;
     return SG_OK;
 }
+// K20's stand-ins: the switch recorded; three entities without an index, word k of the rows = 10 * which + k
+int m_set_quantiles(sg_handle h, uint32_t spaces, const uint32_t* permille, size_t n_q) {
+    M_LOCK(h);
+    auto* m = reinterpret_cast<MockEngine*>(h);
+    uint64_t packed = 0;
+    for (size_t k = 0; k < std::min<size_t>(n_q, 4); k++) packed |= (uint64_t)(permille[k] & 0xFFFFu) << (16 * k);
+    m->k20_ops.push_back({1u, spaces, (uint64_t)n_q, packed});
+    if (n_q > SG_Q_MAX) return SG_EINVAL;
+    m->k20_nq = n_q ? n_q : 2;
+    return SG_OK;
+}
+int m_quantile_rows(sg_handle h, uint64_t which, size_t sides, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
+    M_LOCK(h);
+    auto* m = reinterpret_cast<MockEngine*>(h);
+    m->k20_ops.push_back({which, idx ? (uint64_t)n_idx : ~0ull, (uint64_t)cap, 0u});
+    const size_t rows = idx ? n_idx : 3;
+    if (n) *n = rows;
+    for (size_t k = 0; out && k < std::min(rows, cap) * sides * m->k20_nq; k++) out[k] = (uint32_t)(10 * which + k);
+    return SG_OK;
+}
+int m_window_node_quantiles(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) { return m_quantile_rows(h, 2, 2, idx, n_idx, out, cap, n); }
+int m_window_group_quantiles(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) { return m_quantile_rows(h, 3, 1, idx, n_idx, out, cap, n); }
+int m_window_group_node_quantiles(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) { return m_quantile_rows(h, 4, 2, idx, n_idx, out, cap, n); }
 int m_window_group_node_incident(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
     M_LOCK(h);
     reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({3u, (uint64_t)n_idx, (uint64_t)cap, 0u});
@@ -290,6 +315,8 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.set_group_rank = m_set_group_rank; c->api.window_group_rank_top = m_window_group_rank_top;
         c->api.set_group_tracks = m_set_group_tracks; c->api.window_group_incident_tracks = m_window_group_incident_tracks;
         c->api.window_group_tracks_ended = m_window_group_tracks_ended;
+        c->api.set_quantiles = m_set_quantiles; c->api.window_node_quantiles = m_window_node_quantiles;
+        c->api.window_group_quantiles = m_window_group_quantiles; c->api.window_group_node_quantiles = m_window_group_node_quantiles;
         c->api.set_group_incidents = m_set_group_incidents; c->api.window_group_incidents = m_window_group_incidents;
         c->api.window_group_node_incident = m_window_group_node_incident;
     }
@@ -458,6 +485,20 @@ long sgh_graphds_workload_tracks_ended(void* g, sg_track_entry* out, size_t cap)
     std::vector<sg_track_entry> v;
     const long n = static_cast<HostCtx*>(g)->ds->WorkloadTracksEnded(&v);
     if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_track_entry));
+    return n;
+}
+// the latency percentiles (K20): the switch (spaces 0: off) and the last flushed window's quantiles in microseconds; which = 0 the
+// node rows, 1 the group edges, 2 the workload rows; cap counts u32 words of out
+int sgh_graphds_set_quantiles(void* g, uint32_t spaces, const uint32_t* permille, size_t n_q) {
+    return static_cast<HostCtx*>(g)->ds->SetQuantiles(spaces, permille, n_q);
+}
+long sgh_graphds_latency(void* g, int which, const uint32_t* index, size_t n_index, uint32_t* out, size_t cap, size_t* words) {
+    std::vector<uint32_t> v;
+    GraphDS* ds = static_cast<HostCtx*>(g)->ds.get();
+    const long n = which == 0 ? ds->NodeLatency(index, n_index, &v) : which == 1 ? ds->WorkloadEdgeLatency(index, n_index, &v)
+                                                                                    : ds->WorkloadLatency(index, n_index, &v);
+    if (words) *words = v.size();
+    if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(uint32_t));
     return n;
 }
 int sgh_graphds_ingest_wire(void* g, const uint8_t* recs, size_t n, const uint32_t* kafka_msgs) {
@@ -762,6 +803,14 @@ size_t sgh_mock_k18_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k18_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k18_ops[i].data(), 32);
     return m->k18_ops.size();
+}
+size_t sgh_mock_k20_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k20_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k20_ops[i].data(), 32);
+    return m->k20_ops.size();
 }
 size_t sgh_mock_k19_ops(void* g, uint64_t* out4, size_t cap) {
     auto* c = static_cast<HostCtx*>(g);

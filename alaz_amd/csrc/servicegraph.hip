@@ -36,6 +36,7 @@
 #include "sg_group_rank.h"
 #include "sg_group_incident.h"
 #include "sg_group_track.h"
+#include "sg_quantiles.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -253,6 +254,14 @@ struct sg_engine {
     Incidents<sgplan::GroupIncidentPlan> ginc;
     // K19, the workload tracks: the tracks over the workload incidents, freed with them
     Tracks gtrk;
+    // K20, the latency percentiles (sg_quantiles.h): a space (nodes, group edges, workloads) is a stage of its own — one block
+    // (sg_plan.hpp plan_quantiles), allocated at sg_set_quantiles, freed with its base stage.  The row positions, the target arrays,
+    // the partials and the staging are scratch shared by the window slots: every fold of the space waits for the previous one (ev),
+    // whichever slot's stream it runs on.  Per slot: the histograms, the quantiles, and whether the window in the slot was folded.
+    struct QuantSpace { bool on = false; char* mem = nullptr; u32* pos = nullptr; u32* tgt[2] = {nullptr, nullptr}; u64* part = nullptr;
+                        unsigned char* stage = nullptr; u32* stage_idx = nullptr; std::vector<u64*> hist; std::vector<u32*> quant;
+                        std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; };
+    struct Quantiles { sgplan::QuantPlan plan; u32 n_q = 0; u32 qm[SG_Q_MAX] = {}; QuantSpace sp[3]; } qnt;
 };
 
 namespace {
@@ -1168,6 +1177,76 @@ void free_group_incidents(sg_engine* e) {
     free_group_tracks(e);
     free_stage(e->ginc);
 }
+// ---- K20, the latency percentiles (engine lock held) -------------------------------------------------------------------------------
+static_assert(sgplan::kQThreads == K20_THREADS && sgplan::kQFoldThreads == K20_FOLD_THREADS && sgplan::kQRange == K20_NR &&
+              sgplan::kQMaxWgs == K20_MAX_WGS && sgplan::kQBins == SG_HIST_BINS && sgplan::kQMax == SG_Q_MAX,
+              "plan_quantiles sizes the launches of sg_quantiles.h");
+static_assert(offsetof(sg_node_out, out_max_ns) == 64 && offsetof(sg_node_out, in_max_ns) == 72 && sizeof(sg_node_out) % 8 == 0 &&
+              sizeof(sg_group_edge) % 8 == 0, "k20_finish reads an entity's max_ns as one aligned 8-byte word");
+enum { kQNodes = 0, kQGroups = 1, kQWorkloads = 2 };
+constexpr StageWords kQuantWords[3] = {
+    {"the node percentiles are off (sg_set_quantiles, SG_Q_NODES)", "the node percentiles were off"},
+    {"the group percentiles are off (sg_set_quantiles, SG_Q_GROUPS)", "the group percentiles were off"},
+    {"the workload percentiles are off (sg_set_quantiles, SG_Q_GROUP_NODES)", "the workload percentiles were off"}};
+// one side of space k of the window in slot cur on stream s: the fold over the side's targets (through perm where the side has
+// one), then the finish from the entities' rows at ent (max_ns at max_off of every stride bytes)
+void launch_quantile_side(sg_engine* e, int k, u32 side, const u32* perm, const u64* tcount, const void* ent, u32 stride, u32 max_off, hipStream_t s) {
+    const sgplan::QuantSpace& P = e->qnt.plan.sp[k];
+    const sg_engine::QuantSpace& x = e->qnt.sp[k];
+    const sgplan::QuantSide& g = side == 0 ? P.sorted : P.scattered;   // (the out side and the group edges: targets ascend along the scan)
+    const sg_engine::WinSlot& w = work(e);
+    const u32 tcap = (u32)std::min<u64>(P.cap, 0xFFFFFFFFull);
+    QuantFoldArgs f{};
+    f.bins = w.d.hist_csr; f.perm = perm; f.tgt = x.tgt[side]; f.ctr = w.d.ctr; f.max_edges = std::max<u64>(e->cfg.max_edges, 1);
+    f.tcount = tcount; f.tcap = tcap; f.slices = g.slices; f.sorted = side == 0; f.part = x.part;
+    hipLaunchKernelGGL(k20_fold, dim3(g.ranges * g.slices), dim3(K20_FOLD_THREADS), (size_t)e->qnt.plan.lds_bytes, s, f);
+    QuantFinishArgs q{};
+    q.part = x.part; q.slices = g.slices; q.tcount = tcount; q.tcap = tcap;
+    q.ent = static_cast<const unsigned char*>(ent); q.stride = stride; q.max_off = max_off;
+    q.hist = x.hist[e->cur]; q.quant = x.quant[e->cur]; q.sides = P.sides; q.side = side; q.n_q = e->qnt.n_q;
+    for (u32 j = 0; j < e->qnt.n_q; j++) q.qm[j >> 2] |= (u64)e->qnt.qm[j] << (16 * (j & 3u));
+    hipLaunchKernelGGL(k20_finish, dim3(P.finish_wgs), dim3(K20_THREADS), 0, s, q);
+}
+// enqueue the percentiles of space k of the window in slot cur on stream s (behind the space's base stage, on the same stream) and
+// behind the space's previous fold (any stream): the positions and the targets, then a fold and a finish per side
+int launch_quantiles(sg_engine* e, int k, hipStream_t s) {
+    const sgplan::QuantSpace& P = e->qnt.plan.sp[k];
+    sg_engine::QuantSpace& x = e->qnt.sp[k];
+    if (const int rc = stage_wait(e, x, s)) return rc;
+    const dim3 nt(K20_THREADS);
+    if (k == kQNodes) {
+        const NodesArgs nd = nodes_view(e, work(e), e->plan.ncap);
+        const sg_node_out* rows = e->nodes.rows[e->cur];
+        const u64* count = e->nodes.count[e->cur];
+        hipLaunchKernelGGL(k20_pos_nodes, dim3(P.pos_wgs), nt, 0, s, nd, rows, count, x.pos);
+        hipLaunchKernelGGL(k20_tgt_nodes, dim3(P.tgt_wgs), nt, 0, s, nd, count, (const u32*)x.pos, x.tgt[0], x.tgt[1]);
+        launch_quantile_side(e, k, 0, nullptr, count, rows, sizeof(sg_node_out), offsetof(sg_node_out, out_max_ns), s);
+        launch_quantile_side(e, k, 1, nullptr, count, rows, sizeof(sg_node_out), offsetof(sg_node_out, in_max_ns), s);
+    } else {
+        const GroupNodesArgs g = group_nodes_view(e);                // (K16 off: the rows, the counters, the group edges and their count are all K20 reads of it)
+        const u32* perm = e->grp.perm[e->cur];
+        const u32* row_group = e->grp.row_group[e->cur];
+        if (k == kQGroups) {
+            hipLaunchKernelGGL(k20_tgt_groups, dim3(P.tgt_wgs), nt, 0, s, g, perm, row_group, x.tgt[0]);
+            launch_quantile_side(e, k, 0, perm, g.gcount, g.groups, sizeof(sg_group_edge), offsetof(sg_group_edge, max_ns), s);
+        } else {
+            const sg_node_out* rows = e->gnodes.rows[e->cur];
+            const u64* count = e->gnodes.count[e->cur];
+            hipLaunchKernelGGL(k20_pos_groups, dim3(P.pos_wgs), nt, 0, s, g, rows, count, x.pos);
+            hipLaunchKernelGGL(k20_tgt_group_nodes, dim3(P.tgt_wgs), nt, 0, s, g, perm, row_group, count, (const u32*)x.pos, x.tgt[0], x.tgt[1]);
+            launch_quantile_side(e, k, 0, perm, count, rows, sizeof(sg_node_out), offsetof(sg_node_out, out_max_ns), s);
+            launch_quantile_side(e, k, 1, perm, count, rows, sizeof(sg_node_out), offsetof(sg_node_out, in_max_ns), s);
+        }
+    }
+    if (const int rc = stage_done(e, x, s)) return rc;
+    x.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_quantiles(sg_engine* e, int k) {
+    free_stage(e->qnt.sp[k]);
+    e->qnt.plan.sp[k] = sgplan::QuantSpace{};
+    e->qnt.plan.spaces &= ~(1u << k);
+}
 // an index selection's block off (the workload rows': its sizes are the stage's; every one at sg_destroy)
 template <class Row>
 void free_idxsel(sg_engine::IdxSel<Row>& s) {
@@ -1178,6 +1257,7 @@ void free_idxsel(sg_engine::IdxSel<Row>& s) {
     s = sg_engine::IdxSel<Row>{};
 }
 void free_group_nodes(sg_engine* e) {
+    free_quantiles(e, kQWorkloads);
     free_group_incidents(e);
     free_group_rank(e);
     free_idxsel(e->gnsel);
@@ -1187,6 +1267,7 @@ void free_group_nodes(sg_engine* e) {
 
 void free_groups(sg_engine* e) {
     free_group_nodes(e);
+    free_quantiles(e, kQGroups);
     free_edge_trend(group_edge_space(e));
     sg_engine::Groups& x = e->grp;
     if (x.mem) hipDeviceSynchronize();                                // (an upload may still read h_up)
@@ -1201,6 +1282,7 @@ void free_incidents(sg_engine* e) {
 }
 
 void free_nodes(sg_engine* e) {
+    free_quantiles(e, kQNodes);
     free_incidents(e);
     free_rank(e);
     free_baseline(e->ntrend);
@@ -1238,16 +1320,19 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (e->rank.on) { if (const int rc = launch_rank(e, s)) return rc; }   // K11 behind K9: the rows, the counters, the node rows and their count
         if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
         if (e->trk.on) { if (const int rc = launch_node_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
+        if (e->qnt.sp[kQNodes].on) { if (const int rc = launch_quantiles(e, kQNodes, s)) return rc; }   // K20 behind K9: the rows, their histograms, the node rows
     }
     if (e->grp.on) {                                                 // K14 behind K5: the rows and the window counters only, whatever else is on
         if (const int rc = launch_groups(e, s)) return rc;
         if (e->gtrend.on) { if (const int rc = launch_group_trend(e, s)) return rc; }   // K15 behind K14: the group edges, their count, the outbound IPs
+        if (e->qnt.sp[kQGroups].on) { if (const int rc = launch_quantiles(e, kQGroups, s)) return rc; }   // K20 behind K14: the histograms, perm, row_group, the group edges
         if (e->gnodes.on) {                                          // K16 behind K14: the group edges and their count; its baseline behind it
             if (const int rc = launch_group_nodes(e, s)) return rc;
             if (e->gntrend.on) { if (const int rc = launch_node_trend(e, workload_space(e), s, k16_tcount, k16_twrite)) return rc; }
             if (e->grank.on) { if (const int rc = launch_group_rank(e, s)) return rc; }   // K17 behind K16 and its baseline: the group edges, the workload rows and their count
             if (e->ginc.on) { if (const int rc = launch_group_incidents(e, s)) return rc; }   // K18 behind K15, K16 and K17: the group trend rows, the workload rows, the rank rows
             if (e->gtrk.on) { if (const int rc = launch_group_tracks(e, s)) return rc; }   // K19 behind K18: the workload rows, the incident rows, the incident per workload row
+            if (e->qnt.sp[kQWorkloads].on) { if (const int rc = launch_quantiles(e, kQWorkloads, s)) return rc; }   // K20 behind K16: and the workload rows
         }
     }
     return SG_OK;
@@ -1803,6 +1888,68 @@ int rank_buffer(sg_engine* e, const NodeSpace& ns, const char* call, void** d_ra
     int slot;
     if (const int rc = stage_slot(e, r, call, ns.rank_w, &slot)) return rc;
     *d_rank = r.rows[slot];
+    return SG_OK;
+}
+// ---- K20, the latency percentiles: switching a space on, the reads (engine lock held) ----------------------------------------------
+// an entity's entry as the gathers move it: SIDES sides of 16 u64 bins, or of SG_Q_MAX u32 quantiles (the first n_q set)
+template <int SIDES> struct QHist { u64 b[SIDES][SG_HIST_BINS]; };
+template <int SIDES> struct QQuant { u32 q[SIDES][SG_Q_MAX]; };
+// space k on over its plan (e->qnt.plan.sp[k]): the event, one block, the scratch and every slot's tables carved from it
+int quantiles_on(sg_engine* e, int k) {
+    const sgplan::QuantSpace& P = e->qnt.plan.sp[k];
+    sg_engine::QuantSpace& x = e->qnt.sp[k];
+    const u32 slots = (u32)e->slots.size();
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, "sg_set_quantiles", [] {})) return rc;
+    if (P.pos_bytes) x.pos = at<u32>(x.mem, P.pos_off);
+    for (u32 i = 0; i < P.sides; i++) x.tgt[i] = at<u32>(x.mem, P.tgt_off[i]);
+    x.part = at<u64>(x.mem, P.part_off);
+    x.stage = at<unsigned char>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
+    for (u32 s = 0; s < slots; s++) {
+        char* b = x.mem + P.slot.off + s * P.slot.bytes;
+        x.hist.push_back(at<u64>(b, P.slot_hist)); x.quant.push_back(at<u32>(b, P.slot_quant));
+    }
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+// the entities of space k in the last read window (slot cur): the base stage's count, at most the space's capacity
+int quantile_entities(sg_engine* e, int k, size_t* N) {
+    const u64* d = k == kQNodes ? e->nodes.count[e->cur] : k == kQGroups ? e->grp.count[e->cur] : e->gnodes.count[e->cur];
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, d, sizeof(u64), hipMemcpyDeviceToHost));
+    *N = (size_t)std::min<u64>(cnt, e->qnt.plan.sp[k].cap);
+    return SG_OK;
+}
+const char* const kQuantBeyond[3] = {": a node index beyond the window's nodes", ": a group index beyond the window's group edges",
+                                     ": a node index beyond the window's workload rows"};
+// the histograms of space k of the last read window: every entity, or those at index
+template <int SIDES>
+int quantile_hist_read(sg_engine* e, int k, const char* call, const uint32_t* index, size_t n_index, uint64_t* out, size_t cap, size_t* n) {
+    sg_engine::QuantSpace& x = e->qnt.sp[k];
+    if (const int rc = stage_ready(e, x, call, kQuantWords[k])) return rc;
+    size_t N = 0;
+    if (const int rc = quantile_entities(e, k, &N)) return rc;
+    typedef QHist<SIDES> T;
+    const std::string beyond = std::string(call) + kQuantBeyond[k];
+    return copy_indexed(e, (const T*)x.hist[e->cur], N, index, n_index, (T*)out, cap, n, (T*)x.stage, x.stage_idx, (size_t)sgplan::kQStageRows, beyond.c_str());
+}
+// the quantiles likewise: the device keeps SG_Q_MAX words an entity and side, the caller gets the n_q that are set
+template <int SIDES>
+int quantile_read(sg_engine* e, int k, const char* call, const uint32_t* index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    sg_engine::QuantSpace& x = e->qnt.sp[k];
+    if (const int rc = stage_ready(e, x, call, kQuantWords[k])) return rc;
+    size_t N = 0;
+    if (const int rc = quantile_entities(e, k, &N)) return rc;
+    typedef QQuant<SIDES> T;
+    const std::string beyond = std::string(call) + kQuantBeyond[k];
+    const size_t take = std::min(index ? n_index : N, cap);
+    std::vector<T> tmp(out ? take : 0);
+    if (const int rc = copy_indexed(e, (const T*)x.quant[e->cur], N, index, n_index, out ? tmp.data() : nullptr, take, n, (T*)x.stage, x.stage_idx,
+                                    (size_t)sgplan::kQStageRows, beyond.c_str())) return rc;
+    const u32 nq = e->qnt.n_q;
+    for (size_t i = 0; i < tmp.size(); i++)
+        for (int s = 0; s < SIDES; s++) std::memcpy(out + (i * SIDES + s) * nq, tmp[i].q[s], nq * sizeof(u32));
     return SG_OK;
 }
 // the selection by rank: the rollup and the ranking on, and the window in `slot` closed with them on
@@ -3609,6 +3756,76 @@ int sg_window_outbound_ips(sg_handle e, uint32_t* ips, size_t cap, size_t* n) {
     std::lock_guard<std::mutex> g(e->mu);
     if (n) *n = e->last_obips.size();
     if (ips) std::memcpy(ips, e->last_obips.data(), std::min(cap, e->last_obips.size()) * sizeof(u32));
+    return SG_OK;
+}
+
+// ---- K20, the latency percentiles: the C ABI ---------------------------------------------------------------------------------------
+int sg_set_quantiles(sg_handle e, uint32_t spaces, const uint32_t* permille, size_t n_q) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    u32 qm[SG_Q_MAX] = {}, nq = 0;
+    if (sgplan::check_quantiles(spaces, permille, n_q, e->cfg.world, qm, &nq)) {
+        e->err = "sg_set_quantiles: unknown space bits, more than SG_Q_MAX quantiles, a per-mille outside 1 .. 1000, or an engine with world > 1";
+        return SG_EINVAL;
+    }
+    if (!e->plan.hist) { e->err = "sg_set_quantiles: the engine was created without SG_CFG_EDGE_HISTOGRAM"; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = "sg_set_quantiles while a flush is open"; return SG_ESTATE; }
+    if ((spaces & SG_Q_NODES) && !e->nodes.on) { e->err = std::string("sg_set_quantiles: ") + kNodesWords.off; return SG_ESTATE; }
+    if ((spaces & SG_Q_GROUPS) && !e->grp.on) { e->err = std::string("sg_set_quantiles: ") + kGroupsWords.off; return SG_ESTATE; }
+    if ((spaces & SG_Q_GROUP_NODES) && !e->gnodes.on) { e->err = std::string("sg_set_quantiles: ") + kGroupNodesWords.off; return SG_ESTATE; }
+    const u64 gk = e->gnodes.on ? e->gnodes.plan.gk : 0;
+    if (sgplan::check_quantile_keys(spaces, e->plan.ncap, gk)) { e->err = "sg_set_quantiles: more than 2^21 node keys"; return SG_EINVAL; }
+    for (int k = 0; k < 3; k++) free_quantiles(e, k);
+    if (!spaces) return SG_OK;
+    e->qnt.plan = sgplan::plan_quantiles(e->cfg.max_edges, e->plan.ncap, gk, e->gnodes.on ? e->gnodes.plan.nc : 0, spaces, (u32)e->slots.size());
+    e->qnt.n_q = nq;
+    std::memcpy(e->qnt.qm, qm, sizeof(qm));
+    HIP_TRY(e, lds_limit(e->qnt.plan.lds_bytes, k20_fold));
+    for (int k = 0; k < 3; k++) {
+        if (!e->qnt.plan.sp[k].on) continue;
+        if (const int rc = quantiles_on(e, k)) { const std::string msg = e->err; for (int j = 0; j < 3; j++) free_quantiles(e, j); e->err = msg; return rc; }
+    }
+    return SG_OK;
+}
+int sg_window_node_hist(sg_handle e, const uint32_t* node_index, size_t n_index, uint64_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return quantile_hist_read<2>(e, kQNodes, "sg_window_node_hist", node_index, n_index, out, cap, n);
+}
+int sg_window_node_quantiles(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out_us, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return quantile_read<2>(e, kQNodes, "sg_window_node_quantiles", node_index, n_index, out_us, cap, n);
+}
+int sg_window_group_hist(sg_handle e, const uint32_t* group_index, size_t n_index, uint64_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return quantile_hist_read<1>(e, kQGroups, "sg_window_group_hist", group_index, n_index, out, cap, n);
+}
+int sg_window_group_quantiles(sg_handle e, const uint32_t* group_index, size_t n_index, uint32_t* out_us, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return quantile_read<1>(e, kQGroups, "sg_window_group_quantiles", group_index, n_index, out_us, cap, n);
+}
+int sg_window_group_node_hist(sg_handle e, const uint32_t* node_index, size_t n_index, uint64_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return quantile_hist_read<2>(e, kQWorkloads, "sg_window_group_node_hist", node_index, n_index, out, cap, n);
+}
+int sg_window_group_node_quantiles(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out_us, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return quantile_read<2>(e, kQWorkloads, "sg_window_group_node_quantiles", node_index, n_index, out_us, cap, n);
+}
+int sg_window_quantiles_buffer(sg_handle e, uint32_t space, void** d_hist, void** d_quantiles) {
+    if (!e || !d_hist || !d_quantiles) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = space == SG_Q_NODES ? kQNodes : space == SG_Q_GROUPS ? kQGroups : space == SG_Q_GROUP_NODES ? kQWorkloads : -1;
+    if (k < 0) { e->err = "sg_window_quantiles_buffer: space is one of SG_Q_NODES, SG_Q_GROUPS, SG_Q_GROUP_NODES"; return SG_EINVAL; }
+    const sg_engine::QuantSpace& x = e->qnt.sp[k];
+    int slot;
+    if (const int rc = stage_slot(e, x, "sg_window_quantiles_buffer", kQuantWords[k], &slot)) return rc;
+    *d_hist = x.hist[slot]; *d_quantiles = x.quant[slot];
     return SG_OK;
 }
 

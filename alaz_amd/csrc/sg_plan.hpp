@@ -1226,6 +1226,106 @@ inline TrackPlan plan_group_tracks(u32 max_groups, u32 max_known, u32 max_labels
     return plan_track_block((u64)max_groups + max_known + max_labels, nc, max_tracks, slots);
 }
 
+// K20, the latency percentiles (sg_quantiles.h): the device memory sg_set_quantiles allocates — never sg_create or any other
+// sg_set_* call.  One block a space, so that a space goes with its base stage.  Work is in ROW-INDEX space.  Shared by the window slots: the row position by key (pos: [ncap] for the nodes, [gk]
+// for the workloads — key spaces, at most 2^21 keys each, K16's rule), one 4-byte target array [max_edges] per side (nodes two,
+// group edges one, workloads two) and the partials.  k20_fold runs a grid of ranges of 512 targets (64 KiB of u64 bins in LDS, two
+// workgroups a CU) x slices:
+//   scattered   (the in sides) every range scans every position of its slice: one slice per 8192 positions, at most 64
+//   sorted      (the out sides, the group edges) a range scans its own span only; the slices spread the spans — a few thousand workload
+//               rows are a dozen live ranges, and a dozen workgroups would fold a million rows — one per 2048 positions, at most 64
+//   budget      a space's partial buffer serves its sides in turn, [ranges][slices][512][16] u64 of the larger side; each side's
+//               slices are cut until its partials fit 256 MiB (the group edges of an engine with max_edges 1.25 M: 2442 ranges, one slice)
+// Per slot: the histograms (16 u64 an entity and side) and the quantiles (SG_Q_MAX u32 an entity and side) of each space that is
+// on.  The group edges' table is 128 + 32 bytes x max_edges a slot: group_slot_bytes reports it, and each space is asked for by
+// its own bit because of it.  One staging block of kQStageRows entries serves the index forms of the six reads.
+constexpr u32 kQThreads = 256, kQFoldThreads = 512, kQRange = 512, kQMaxWgs = 1024, kQBins = 16, kQMax = 8, kQSliceItems = 8192,
+              kQSortedSliceItems = 2048, kQMaxSlices = 64, kQStageRows = 1024;
+constexpr u64 kQPartBudget = 256ull << 20, kQMaxKeys = 1ull << 21, kQRangeBytes = (u64)kQRange * kQBins * 8;
+static_assert(2 * kQRangeBytes <= kLdsBytes, "two k20_fold workgroups a CU");
+// spaces: SG_Q_* bits; the per-mille (n_q == 0: {500, 990}) checked into out[SG_Q_MAX], *n_out of them
+inline int check_quantiles(u32 spaces, const u32* permille, u64 n_q, u32 world, u32* out, u32* n_out) {
+    if ((spaces & ~(SG_Q_NODES | SG_Q_GROUPS | SG_Q_GROUP_NODES)) || n_q > SG_Q_MAX || world > 1 || (n_q && !permille)) return SG_EINVAL;
+    const u32 dflt[2] = {500, 990};
+    const u32* p = n_q ? permille : dflt;
+    const u32 n = n_q ? (u32)n_q : 2u;
+    for (u32 k = 0; k < n; k++) { if (p[k] < 1 || p[k] > 1000) return SG_EINVAL; out[k] = p[k]; }
+    *n_out = n;
+    return SG_OK;
+}
+struct QuantSide { u32 ranges = 0, slices = 0; };   // k20_fold's grid of one side: ranges x slices workgroups
+struct QuantSpace {
+    bool on = false;
+    u64 cap = 0;                  // entities per window slot
+    u32 sides = 0;                // 2 (out, in) or 1 (group edges)
+    QuantSide sorted, scattered;  // the out side / the group edges; the in side
+    u32 finish_wgs = 0, pos_wgs = 0, tgt_wgs = 0;
+    u64 pos_bytes = 0, pos_off = 0, tgt_off[2] = {};
+    u64 part_bytes = 0, part_off = 0;   // [ranges][slices of the larger side][512][16] u64: the sides use it in turn
+    u64 stage_off = 0, stage_idx_off = 0;
+    u64 hist_bytes = 0, quant_bytes = 0, slot_hist = 0, slot_quant = 0;   // per slot; offsets within the slot
+    Slots slot;
+    u64 total_bytes = 0;
+    std::vector<Piece> layout;
+};
+struct QuantPlan {
+    u32 spaces = 0;
+    u64 max_edges = 0;
+    QuantSpace sp[3];             // nodes, group edges, workloads: a device block each, freed with its base stage
+    u64 tgt_bytes = 0;            // one target array
+    u64 group_slot_bytes = 0;     // the group edges' tables per slot (0: the space is off)
+    u32 lds_bytes = 0;
+    u64 total_bytes = 0;          // of the spaces that are on
+};
+inline int check_quantile_keys(u32 spaces, u32 ncap, u64 gk) {
+    if ((spaces & SG_Q_NODES) && ncap > kQMaxKeys) return SG_EINVAL;
+    if ((spaces & SG_Q_GROUP_NODES) && gk > kQMaxKeys) return SG_EINVAL;
+    return SG_OK;
+}
+inline QuantSide plan_quantile_side(u64 cap, u64 max_edges, bool sorted) {
+    QuantSide s;
+    s.ranges = (u32)((std::max<u64>(cap, 1) + kQRange - 1) / kQRange);
+    const u64 per = sorted ? kQSortedSliceItems : kQSliceItems;
+    const u64 want = std::min<u64>(kQMaxSlices, (max_edges + per - 1) / per);
+    s.slices = (u32)std::max<u64>(1, std::min<u64>(want, kQPartBudget / ((u64)s.ranges * kQRangeBytes)));
+    return s;
+}
+// ncap: the node capacity; gk, nc: K16's group keys and workload rows a slot (read only for SG_Q_GROUP_NODES)
+inline QuantPlan plan_quantiles(u64 max_edges, u32 ncap, u64 gk, u32 nc, u32 spaces, u32 slots) {
+    QuantPlan q;
+    const u64 ME = std::max<u64>(max_edges, 1);
+    q.spaces = spaces; q.max_edges = ME;
+    q.lds_bytes = (u32)kQRangeBytes;
+    q.tgt_bytes = trend_align(ME * 4);
+    const u64 caps[3] = {std::max<u32>(ncap, 1), ME, std::max<u32>(nc, 1)}, keys[3] = {std::max<u32>(ncap, 1), 0, std::max<u64>(gk, 1)};
+    const char* const tgt_name[2] = {"tgt_out", "tgt_in"};
+    for (int k = 0; k < 3; k++) {
+        QuantSpace& s = q.sp[k];
+        s.on = (spaces >> k) & 1u;
+        if (!s.on) continue;
+        Block b;
+        s.cap = caps[k]; s.sides = k == 1 ? 1 : 2;
+        s.sorted = plan_quantile_side(s.cap, ME, true);
+        if (s.sides == 2) s.scattered = plan_quantile_side(s.cap, ME, false);
+        s.finish_wgs = (u32)std::max<u64>(1, std::min<u64>(kQMaxWgs, (s.cap + kQThreads / kQBins - 1) / (kQThreads / kQBins)));
+        s.pos_wgs = (u32)std::max<u64>(1, std::min<u64>(kQMaxWgs, (s.cap + kQThreads - 1) / kQThreads));
+        s.tgt_wgs = (u32)std::max<u64>(1, std::min<u64>(kQMaxWgs, (ME + 4 * kQThreads - 1) / (4 * kQThreads)));
+        if (keys[k]) { s.pos_bytes = trend_align(keys[k] * 4); s.pos_off = b.take("pos", s.pos_bytes); }
+        for (u32 i = 0; i < s.sides; i++) s.tgt_off[i] = b.take(tgt_name[i], q.tgt_bytes);
+        s.part_bytes = (u64)s.sorted.ranges * std::max(s.sorted.slices, s.scattered.slices) * kQRangeBytes;
+        s.part_off = b.take("part", s.part_bytes);
+        s.stage_off = b.take("stage", (u64)kQStageRows * s.sides * kQBins * 8);
+        s.stage_idx_off = b.take("stage_idx", (u64)kQStageRows * 4);
+        s.hist_bytes = trend_align(s.cap * s.sides * kQBins * 8);
+        s.quant_bytes = trend_align(s.cap * s.sides * kQMax * 4);
+        s.slot = b.slots(slots, {{"hist", s.hist_bytes, &s.slot_hist}, {"quantiles", s.quant_bytes, &s.slot_quant}});
+        s.total_bytes = b.up(b.end); s.layout = std::move(b.pieces);
+        q.total_bytes += s.total_bytes;
+    }
+    q.group_slot_bytes = q.sp[1].on ? q.sp[1].hist_bytes + q.sp[1].quant_bytes : 0;
+    return q;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

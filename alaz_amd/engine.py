@@ -87,6 +87,9 @@ SEL_BY = dict(score=0, lat_dev=1, err_dev=2, new=3)
 NSEL_BY = dict(score=0, in_lat_dev=1, in_err_dev=2, out_lat_dev=3, out_err_dev=4, new=5)
 #: sg_trend_params defaults (a 0 in the struct means the same)
 TREND_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, lat_floor_ns=1000, err_floor=10486)
+#: SG_Q_*: the spaces of the latency percentiles (K20), and SG_Q_MAX, the quantiles per entity and side at most
+Q_SPACES = dict(nodes=1, groups=2, group_nodes=4)
+Q_MAX = 8
 
 
 class SgConfig(C.Structure):
@@ -272,6 +275,11 @@ def _signatures() -> dict:
         "sg_window_group_tracks_ended": (I, [H, P, sz, Psz]),
         "sg_window_group_tracks_buffer": (I, [H, PP, PP, PP]),
         "sg_group_track_entries": (I, [H, P, sz, Psz]), "sg_group_track_stats_get": (I, [H, P]),
+        "sg_set_quantiles": (I, [H, u32, P, sz]),
+        "sg_window_node_hist": (I, [H, P, sz, P, sz, Psz]), "sg_window_node_quantiles": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_hist": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_quantiles": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_node_hist": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_node_quantiles": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_quantiles_buffer": (I, [H, u32, PP, PP]),
     }
 
 
@@ -1028,6 +1036,60 @@ class ServiceGraph:
 
     def group_track_stats(self) -> SgTrackStats:
         return self._stats(self._l.sg_group_track_stats_get, SgTrackStats)
+
+    # ---- latency percentiles (K20): histograms and percentiles per node row, group edge and workload row ----
+    def set_quantiles(self, spaces=("nodes",), permille=(500, 990)):
+        """Switch the per-window latency histograms and percentiles on (sg_set_quantiles; the engine was created with
+        edge_histogram=True): spaces is an iterable of "nodes" / "groups" / "group_nodes" (each needs its base stage on:
+        set_nodes / set_groups / set_group_nodes) or the SG_Q_* bits as an int; permille up to Q_MAX values in 1 .. 1000.
+        set_quantiles(None) or spaces=0 switches the stage off."""
+        bits = 0 if spaces is None else spaces if isinstance(spaces, int) else self._qbits(spaces)
+        qm = np.ascontiguousarray(permille, dtype=np.uint32)
+        self._ck(self._l.sg_set_quantiles(self._h, bits, qm.ctypes.data if len(qm) else None, len(qm)))
+        self._n_q = len(qm) if len(qm) else 2
+
+    @staticmethod
+    def _qbits(spaces) -> int:
+        bits = 0
+        for sp in ([spaces] if isinstance(spaces, str) else spaces):
+            if sp not in Q_SPACES:
+                raise ValueError(f"unknown quantile space {sp!r}: one of {sorted(Q_SPACES)}")
+            bits |= Q_SPACES[sp]
+        return bits
+
+    def _quantile_dtype(self, sides: int) -> np.dtype:
+        return np.dtype(("<u4", (sides, getattr(self, "_n_q", 2)) if sides == 2 else (getattr(self, "_n_q", 2),)))
+
+    def window_node_hist(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, 2, 16) u64 bins of the last read window (sg_window_node_hist): entry k for row k of window_nodes(), out side then in
+        side; or the entries at `index` (only those cross PCIe)."""
+        return self._window_rows(self._l.sg_window_node_hist, np.dtype(("<u8", (2, 16))), index)
+
+    def window_node_quantiles(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, 2, n_q) u32 microseconds (sg_window_node_quantiles), in set_quantiles' permille order"""
+        return self._window_rows(self._l.sg_window_node_quantiles, self._quantile_dtype(2), index)
+
+    def window_group_hist(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, 16) u64 bins (sg_window_group_hist): entry k for group edge k of window_groups()"""
+        return self._window_rows(self._l.sg_window_group_hist, np.dtype(("<u8", (16,))), index)
+
+    def window_group_quantiles(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, n_q) u32 microseconds (sg_window_group_quantiles)"""
+        return self._window_rows(self._l.sg_window_group_quantiles, self._quantile_dtype(1), index)
+
+    def window_group_node_hist(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, 2, 16) u64 bins (sg_window_group_node_hist): entry k for row k of window_group_nodes()"""
+        return self._window_rows(self._l.sg_window_group_node_hist, np.dtype(("<u8", (2, 16))), index)
+
+    def window_group_node_quantiles(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, 2, n_q) u32 microseconds (sg_window_group_node_quantiles)"""
+        return self._window_rows(self._l.sg_window_group_node_quantiles, self._quantile_dtype(2), index)
+
+    def window_quantiles_buffer(self, space) -> Tuple[int, int]:
+        """(device pointer of the u64 histograms, of the u32 quantiles — Q_MAX words an entity and side) of one space of the window
+        window_run closed last (sg_window_quantiles_buffer)"""
+        bits = space if isinstance(space, int) else self._qbits(space)
+        return self._pointers(lambda h, *a: self._l.sg_window_quantiles_buffer(h, bits, *a), 2)
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

@@ -140,6 +140,8 @@ def load() -> C.CDLL:
             "sgh_graphds_set_workload_tracks": (C.c_int, [P, C.c_int, u32, u32]),
             "sgh_graphds_workload_incident_tracks": (C.c_long, [P, P, sz]), "sgh_graphds_workload_tracks_ended": (C.c_long, [P, P, sz]),
             "sgh_mock_k19_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_quantiles": (C.c_int, [P, u32, P, sz]),
+            "sgh_graphds_latency": (C.c_long, [P, C.c_int, P, sz, P, sz, P]), "sgh_mock_k20_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -627,6 +629,45 @@ class GraphDS:
         n = self._l.sgh_mock_k19_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k19_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the latency percentiles (K20) ----
+    def set_quantiles(self, spaces: int = 1, permille=(500, 990)) -> int:
+        """GraphDS::SetQuantiles: spaces as SG_Q_* bits (engine.Q_SPACES; 0 = off), up to engine.Q_MAX per-mille values (rc)"""
+        qm = np.ascontiguousarray(permille, dtype=np.uint32)
+        return self._l.sgh_graphds_set_quantiles(self._g, spaces, qm.ctypes.data if len(qm) else None, len(qm))
+
+    def _latency(self, which: int, sides: int, index, what: str) -> np.ndarray:
+        idx = None if index is None else np.ascontiguousarray(index, dtype=np.uint32)
+        ip, ni = (None, 0) if idx is None else (idx.ctypes.data, len(idx))
+        words = C.c_size_t(0)
+        n = self._l.sgh_graphds_latency(self._g, which, ip, ni, None, 0, C.byref(words))
+        if n < 0:
+            raise RuntimeError(f"{what} failed: {n}")
+        out = np.zeros(max(words.value, 1), dtype=np.uint32)
+        self._l.sgh_graphds_latency(self._g, which, ip, ni, out.ctypes.data, words.value, None)
+        out = out[:words.value]
+        return out.reshape((n, sides, -1) if sides == 2 else (n, -1)) if n else out.reshape((0, sides, 0) if sides == 2 else (0, 0))
+
+    def node_latency(self, index=None) -> np.ndarray:
+        """GraphDS::NodeLatency: (n, 2, n_q) u32 microseconds of the last flushed window's node rows (out side, in side)"""
+        return self._latency(0, 2, index, "NodeLatency")
+
+    def workload_edge_latency(self, index=None) -> np.ndarray:
+        """GraphDS::WorkloadEdgeLatency: (n, n_q) u32 microseconds of the last flushed window's group edges"""
+        return self._latency(1, 1, index, "WorkloadEdgeLatency")
+
+    def workload_latency(self, index=None) -> np.ndarray:
+        """GraphDS::WorkloadLatency: (n, 2, n_q) u32 microseconds of the last flushed window's workload rows"""
+        return self._latency(2, 2, index, "WorkloadLatency")
+
+    def mock_k20_ops(self) -> np.ndarray:
+        """the stand-in engine's K20 calls in order, four u64 each: (1, spaces, n_q, the first four per-mille 16 bits each) per
+        sg_set_quantiles, (2 / 3 / 4, n_index or all ones without an index, cap, 0) per sg_window_node_quantiles /
+        sg_window_group_quantiles / sg_window_group_node_quantiles"""
+        n = self._l.sgh_mock_k20_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k20_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

@@ -100,6 +100,7 @@ type GraphDS struct {
 	shards  [nShards]shard
 	next    atomic.Uint32
 	flushMu sync.Mutex
+	nQ      int // quantiles per entity and side, as SetQuantiles set them last (K20; guarded by flushMu)
 
 	// (flushMu) the workload baseline's capacity and the rows its vanished list holds, as the engine resolves a 0
 	wlEntries uint64
@@ -1530,6 +1531,86 @@ func (g *GraphDS) WindowWorkloadTracksEnded() ([]TrackEntry, error) {
 		ents = ents[:int(n)]
 	}
 	return trackEntriesOf(ents), nil
+}
+
+// ---- latency percentiles (K20) -------------------------------------------------------------------------------------------
+
+// The spaces of SetQuantiles (SG_Q_*).
+const (
+	QuantileNodes     uint32 = 1
+	QuantileWorkEdges uint32 = 2
+	QuantileWorkloads uint32 = 4
+)
+
+// SetQuantiles switches the per-window latency histograms and percentiles on for the spaces given (QuantileNodes needs
+// SetNodes, QuantileWorkEdges SetGroups, QuantileWorkloads SetWorkloadNodes; the engine was created with the edge histogram):
+// percentiles do not average, so a service's or a workload's p99 comes from the merged histogram of its rows only.  permille
+// holds up to eight values in 1 .. 1000; none means {500, 990}.  spaces 0 switches the stage off.
+func (g *GraphDS) SetQuantiles(spaces uint32, permille ...uint32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var p *C.uint32_t
+	if len(permille) > 0 {
+		p = (*C.uint32_t)(unsafe.Pointer(&permille[0]))
+	}
+	if rc := C.sg_set_quantiles(g.h, C.uint32_t(spaces), p, C.size_t(len(permille))); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_quantiles = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	g.nQ = len(permille)
+	if g.nQ == 0 {
+		g.nQ = 2
+	}
+	return nil
+}
+
+// latencyRows reads one space's quantiles of the window FlushWindow returned last: words uint32 per entity, every entity
+// (index nil) or those at index (only they cross PCIe).
+func (g *GraphDS) latencyRows(which int, index []uint32, words int) ([]uint32, int, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	read := func(idx *C.uint32_t, nIdx C.size_t, out *C.uint32_t, cap C.size_t, n *C.size_t) C.int {
+		switch which {
+		case 0:
+			return C.sg_window_node_quantiles(g.h, idx, nIdx, out, cap, n)
+		case 1:
+			return C.sg_window_group_quantiles(g.h, idx, nIdx, out, cap, n)
+		}
+		return C.sg_window_group_node_quantiles(g.h, idx, nIdx, out, cap, n)
+	}
+	var idx *C.uint32_t
+	n := C.size_t(len(index))
+	if index == nil {
+		if rc := read(nil, 0, nil, 0, &n); rc != 0 {
+			return nil, 0, fmt.Errorf("servicegraph: latency read = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+	} else if len(index) > 0 {
+		idx = (*C.uint32_t)(unsafe.Pointer(&index[0]))
+	}
+	if n == 0 {
+		return nil, 0, nil
+	}
+	out := make([]uint32, int(n)*words)
+	if rc := read(idx, C.size_t(len(index)), (*C.uint32_t)(unsafe.Pointer(&out[0])), n, &n); rc != 0 {
+		return nil, 0, fmt.Errorf("servicegraph: latency read = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return out, int(n), nil
+}
+
+// NodeLatency returns the quantiles, in microseconds, of the node rows of the window FlushWindow returned last: element
+// [k*2*nQ + side*nQ + j] is quantile j of side (0 out, 1 in) of node row k (sg_window_node_quantiles); nQ is the number of
+// per-mille values SetQuantiles took.  index nil: every node row.
+func (g *GraphDS) NodeLatency(index []uint32) (us []uint32, rows int, err error) {
+	return g.latencyRows(0, index, 2*g.nQ)
+}
+
+// WorkloadEdgeLatency returns the quantiles of the group edges: element [k*nQ + j] (sg_window_group_quantiles).
+func (g *GraphDS) WorkloadEdgeLatency(index []uint32) (us []uint32, rows int, err error) {
+	return g.latencyRows(1, index, g.nQ)
+}
+
+// WorkloadLatency returns the quantiles of the workload rows, laid out as NodeLatency's (sg_window_group_node_quantiles).
+func (g *GraphDS) WorkloadLatency(index []uint32) (us []uint32, rows int, err error) {
+	return g.latencyRows(2, index, 2*g.nQ)
 }
 
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of

@@ -1015,6 +1015,55 @@ int sg_window_group_tracks_buffer(sg_handle h, void** d_tracks, void** d_ended, 
 int sg_group_track_entries(sg_handle h, sg_track_entry* out, size_t cap, size_t* n);
 int sg_group_track_stats_get(sg_handle h, sg_track_stats* out);
 
+/* ---- latency percentiles (K20): histograms and percentiles per node row, group edge and workload row, on the device ----------- *
+ * Opt-in (sg_set_quantiles, on an engine created with SG_CFG_EDGE_HISTOGRAM); without it nothing is launched or allocated, and
+ * every other output is byte for byte the same either way.  Percentiles do not average: a node's, a group edge's or a workload's
+ * p99 follows from the MERGED histogram of its rows only.  Let H_r[16] be the bins of row r as sg_window_hist returns them.  Three
+ * spaces, each with histograms of uint64_t bins (a sum of up to 2^32 uint32_t bins cannot wrap):
+ *   nodes        (SG_Q_NODES; needs sg_set_nodes) for node row x of sg_window_nodes: out[b] = sum of H_r[b] over the rows with
+ *                from_ref == x's ref, in[b] over the rows with to_ref == x's ref.  A self-loop counts on both sides, as in K9
+ *   group edges  (SG_Q_GROUPS; needs sg_set_groups) for group edge g of sg_window_groups: B[b] = sum of H_r[b] over the rows of its
+ *                run, perm[first .. first + edges)
+ *   workloads    (SG_Q_GROUP_NODES; needs sg_set_group_nodes) for workload row x of sg_window_group_nodes: the nodes' definition
+ *                with every ref replaced by its group ref; equally, the sum over the group edges on that side
+ * The quantile Q(B, max_ns, qm) of a histogram B at qm per-mille (1 .. 1000):
+ *   total = sum of B (every bin of a row's histogram counts one request of the row, so total equals the entity's count /
+ *   out_count / in_count; the definition is the sum of the bins).  total == 0: Q = 0.  Otherwise
+ *   rank = max(1, (total / 1000) * qm + ceil((total % 1000) * qm / 1000)) — ceil(total * qm / 1000) without overflow;
+ *   b = the first bin whose cumulative count reaches rank; edge_ns = (b == 15) ? max_ns : 2^(17 + b), then capped at max_ns;
+ *   Q = edge_ns / 1000 (floor), saturated to uint32_t.
+ * max_ns is the entity's own: sg_group_edge.max_ns, sg_node_out.out_max_ns / in_max_ns of the side.  At qm = 500 and 990 this is
+ * the rule of a row's p50_us / p99_us: a group edge of one row has that row's percentiles.  Every value is an integer sum or follows
+ * from one: the result has one correct value.  Every close path computes it (one call, begin + end, the views, the _top / _top_by
+ * flushes, sg_window_run, the staged sg_window_score), behind K9 / K14 / K16 on the window's stream.
+ * State: sg_set_quantiles(h, spaces, permille, n_q) — spaces == 0 switches the stage off and frees its memory; n_q == 0 means
+ * {500, 990}.  SG_EINVAL for unknown bits, n_q > SG_Q_MAX, a per-mille outside 1 .. 1000, or an engine with world > 1; SG_ESTATE on
+ * an engine without SG_CFG_EDGE_HISTOGRAM, for a space whose base stage is off, or while a flush is open.  Memory is allocated
+ * there, never at sg_create: the group edges' table alone is 128 bytes x max_edges per window slot, which is why each space is
+ * asked for by its own bit.  Every call replaces the previous setting.  Switching a base stage off frees this stage's space with
+ * it: sg_set_nodes(h, 0) the nodes', any sg_set_groups call the group edges' and the workloads', sg_set_group_nodes(h, 0) the
+ * workloads'.  Reads of a window closed while the space was off, and while a flush is open: SG_ESTATE.                            */
+#define SG_Q_NODES        1u
+#define SG_Q_GROUPS       2u
+#define SG_Q_GROUP_NODES  4u
+#define SG_Q_MAX          8u    /* quantiles per entity and side at most                          */
+int sg_set_quantiles(sg_handle h, uint32_t spaces, const uint32_t* permille, size_t n_q);
+/* The histograms and the quantiles of the last READ window (as sg_window_node_trend): index NULL: every entity of the space, *n =
+ * their count; else out[k] = the entry of entity index[k] (each < the count, else SG_EINVAL), gathered on the device, *n = n_index.
+ * cap counts entities; min(*n, cap) entries are written.  An entry of sg_window_node_hist / sg_window_group_node_hist is [2][16]
+ * uint64_t (out side, then in side), of sg_window_group_hist [16]; of sg_window_node_quantiles / sg_window_group_node_quantiles
+ * [2][n_q] uint32_t microseconds, of sg_window_group_quantiles [n_q], in the order of sg_set_quantiles' permille.                */
+int sg_window_node_hist(sg_handle h, const uint32_t* node_index, size_t n_index, uint64_t* out, size_t cap, size_t* n);
+int sg_window_node_quantiles(sg_handle h, const uint32_t* node_index, size_t n_index, uint32_t* out_us, size_t cap, size_t* n);
+int sg_window_group_hist(sg_handle h, const uint32_t* group_index, size_t n_index, uint64_t* out, size_t cap, size_t* n);
+int sg_window_group_quantiles(sg_handle h, const uint32_t* group_index, size_t n_index, uint32_t* out_us, size_t cap, size_t* n);
+int sg_window_group_node_hist(sg_handle h, const uint32_t* node_index, size_t n_index, uint64_t* out, size_t cap, size_t* n);
+int sg_window_group_node_quantiles(sg_handle h, const uint32_t* node_index, size_t n_index, uint32_t* out_us, size_t cap, size_t* n);
+/* Device tables of space `space` (one SG_Q_* bit) of the window sg_window_run closed last (valid until its slot is reused; read
+ * them on that window's stream): the histograms as the reads above lay them out, and the quantiles with SG_Q_MAX uint32_t per
+ * entity and side, the first n_q of them set.  The entity count is the space's own (sg_window_nodes_buffer, ...).               */
+int sg_window_quantiles_buffer(sg_handle h, uint32_t space, void** d_hist, void** d_quantiles);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
