@@ -44,6 +44,11 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->window_node_quantiles = reinterpret_cast<decltype(o->window_node_quantiles)>(dlsym(dl, "sg_window_node_quantiles"));
     o->window_group_quantiles = reinterpret_cast<decltype(o->window_group_quantiles)>(dlsym(dl, "sg_window_group_quantiles"));
     o->window_group_node_quantiles = reinterpret_cast<decltype(o->window_group_node_quantiles)>(dlsym(dl, "sg_window_group_node_quantiles"));
+    o->set_quantile_trend = reinterpret_cast<decltype(o->set_quantile_trend)>(dlsym(dl, "sg_set_quantile_trend"));   // optional (K21)
+    o->window_node_quantile_trend = reinterpret_cast<decltype(o->window_node_quantile_trend)>(dlsym(dl, "sg_window_node_quantile_trend"));
+    o->window_group_quantile_trend = reinterpret_cast<decltype(o->window_group_quantile_trend)>(dlsym(dl, "sg_window_group_quantile_trend"));
+    o->window_group_node_quantile_trend = reinterpret_cast<decltype(o->window_group_node_quantile_trend)>(dlsym(dl, "sg_window_group_node_quantile_trend"));
+    o->window_group_nodes_top_tail = reinterpret_cast<decltype(o->window_group_nodes_top_tail)>(dlsym(dl, "sg_window_group_nodes_top_tail"));
 #undef SG_SYM
     return true;
 }
@@ -278,17 +283,21 @@ long GraphDS::WorkloadNodeTrends(std::vector<sg_node_trend>* out) {
     return (long)out->size();
 }
 long GraphDS::WorkloadNodesTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
-    if (!out || !api_.window_group_nodes_top) return SG_EINVAL;
+    return WorkloadNodesTopBy(api_.window_group_nodes_top, by, k, min_value, out, index);
+}
+long GraphDS::WorkloadNodesTopBy(int (*top)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*), uint32_t by,
+                                 uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
+    if (!out || !top) return SG_EINVAL;
     std::lock_guard<std::mutex> fg(flush_mu_);
     size_t sel = 0, total = 0;
     std::vector<sg_node_out> rows;
     std::vector<uint32_t> idx;
     if (k) { rows.resize(k); idx.resize(k); }                        // at most k are selected; k = 0: the count first
-    int rc = api_.window_group_nodes_top(h_, by, k, min_value, rows.data(), idx.data(), rows.size(), &sel, &total);
+    int rc = top(h_, by, k, min_value, rows.data(), idx.data(), rows.size(), &sel, &total);
     if (rc != SG_OK) return rc;
     if (!k && sel) {
         rows.resize(sel); idx.resize(sel);
-        if ((rc = api_.window_group_nodes_top(h_, by, 0, min_value, rows.data(), idx.data(), rows.size(), &sel, &total)) != SG_OK) return rc;
+        if ((rc = top(h_, by, 0, min_value, rows.data(), idx.data(), rows.size(), &sel, &total)) != SG_OK) return rc;
     }
     const size_t m = std::min(sel, rows.size());
     rows.resize(m); idx.resize(m);
@@ -385,6 +394,19 @@ int GraphDS::SetQuantiles(uint32_t spaces, const uint32_t* permille, size_t n_q)
     if (rc == SG_OK) n_q_ = n_q ? n_q : 2;
     return rc;
 }
+// ---- the tail baselines (K21) ----
+int GraphDS::SetTailTrend(uint32_t spaces, uint32_t permille, const sg_trend_params* p) {
+    if (!api_.set_quantile_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_quantile_trend(h_, spaces, permille, p);
+}
+long GraphDS::NodeTailTrends(std::vector<sg_node_trend>* out) { return TrendRows(api_.window_node_quantile_trend, out); }
+long GraphDS::WorkloadEdgeTailTrends(std::vector<sg_edge_trend>* out) { return TrendRows(api_.window_group_quantile_trend, out); }
+long GraphDS::WorkloadTailTrends(std::vector<sg_node_trend>* out) { return TrendRows(api_.window_group_node_quantile_trend, out); }
+long GraphDS::WorkloadTailTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
+    return WorkloadNodesTopBy(api_.window_group_nodes_top_tail, by, k, min_value, out, index);
+}
+
 // the quantiles of the last flushed window, `words` u32 an entity: the count first (no index), then the rows
 long GraphDS::LatencyRows(int (*read)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*), const uint32_t* index, size_t n_index,
                           size_t words, std::vector<uint32_t>* out_us) {

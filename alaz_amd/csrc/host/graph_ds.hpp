@@ -78,6 +78,12 @@ struct SgApi {
     int (*window_node_quantiles)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
     int (*window_group_quantiles)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
     int (*window_group_node_quantiles)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
+    // optional (K21; absent in an older library): SetTailTrend, the three tail reads and WorkloadTailTop each need the entry they forward to
+    int (*set_quantile_trend)(sg_handle, uint32_t, uint32_t, const sg_trend_params*) = nullptr;
+    int (*window_node_quantile_trend)(sg_handle, const uint32_t*, size_t, sg_node_trend*, size_t, size_t*) = nullptr;
+    int (*window_group_quantile_trend)(sg_handle, const uint32_t*, size_t, sg_edge_trend*, size_t, size_t*) = nullptr;
+    int (*window_group_node_quantile_trend)(sg_handle, const uint32_t*, size_t, sg_node_trend*, size_t, size_t*) = nullptr;
+    int (*window_group_nodes_top_tail)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -230,6 +236,17 @@ public:
     long NodeLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us);
     long WorkloadEdgeLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us);
     long WorkloadLatency(const uint32_t* index, size_t n_index, std::vector<uint32_t>* out_us);
+    // The tail baselines (K21; behind SetQuantiles over the same spaces): each entity's tracked quantile against its own past.
+    // SetTailTrend forwards sg_set_quantile_trend (spaces: SG_Q_* bits, 0 or p NULL = off; permille: one of those SetQuantiles gave;
+    // the engine's return code; SG_EINVAL without the entry).  NodeTailTrends, WorkloadEdgeTailTrends and WorkloadTailTrends read
+    // the last flushed window's tail rows: row k for node row k, for edge k of WorkloadEdges, for row k of WorkloadNodes.
+    // WorkloadTailTop: the selection sg_window_group_nodes_top_tail (`by` = SG_NSEL_*, ranked by the tail rows), its rows named as
+    // WorkloadNodesTop names them, their indices in `index` (may be NULL).  Each returns the count, or a negative SG_* code.
+    int SetTailTrend(uint32_t spaces, uint32_t permille, const sg_trend_params* p);
+    long NodeTailTrends(std::vector<sg_node_trend>* out);
+    long WorkloadEdgeTailTrends(std::vector<sg_edge_trend>* out);
+    long WorkloadTailTrends(std::vector<sg_node_trend>* out);
+    long WorkloadTailTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }
@@ -257,6 +274,21 @@ private:
     void NameRef(uint32_t ref, std::string* type, std::string* uid) const;   // (id_mu_ held) one group ref
     void NameWorkloadNodes(const std::vector<sg_node_out>& rows, std::vector<WorkloadNode>* out);   // (takes id_mu_)
     int FlushShard(Shard& s);                          // s.mu held
+    // a selection over the workload rows through `top` (sg_window_group_nodes_top or its _tail twin): WorkloadNodesTop's body
+    long WorkloadNodesTopBy(int (*top)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*), uint32_t by,
+                            uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
+    // every trend row of the last flushed window through an indexed read (index NULL): the count first, then the rows
+    template <class Row>
+    long TrendRows(int (*read)(sg_handle, const uint32_t*, size_t, Row*, size_t, size_t*), std::vector<Row>* out) {
+        if (!out || !read) return SG_EINVAL;
+        std::lock_guard<std::mutex> fg(flush_mu_);
+        size_t n = 0;
+        int rc = read(h_, nullptr, 0, nullptr, 0, &n);
+        if (rc != SG_OK) return rc;
+        out->assign(n, Row{});
+        if (n && (rc = read(h_, nullptr, 0, out->data(), n, &n)) != SG_OK) return rc;
+        return (long)out->size();
+    }
 
     datastore::DataStore* inner_;
     SgApi api_; sg_handle h_; EdgeSink* sink_;

@@ -30,6 +30,7 @@ struct MockEngine {
     std::vector<std::array<uint64_t, 4>> k15_ops;      // {1, shift, warmup, ttl} per sg_set_group_trend, {2, silent_windows, min_seen, max_rows} per sg_set_group_vanished (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_groups_top
     std::vector<std::array<uint64_t, 4>> k16_ops;      // {1, on, 0, 0} per sg_set_group_nodes, {2, shift, warmup, ttl} per sg_set_group_node_trend (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_group_nodes_top
     std::vector<std::array<uint64_t, 4>> k17_ops;      // {1, iters, damping_q8, seed} per sg_set_group_rank (NULL: ~0 in the three), {2, k, the bits of min_share, cap} per sg_window_group_rank_top
+    std::vector<std::array<uint64_t, 4>> k21_ops;      // {1, spaces, permille, shift (NULL: ~0)} per sg_set_quantile_trend, {2 / 3 / 4, cap, 0, 0} per sg_window_node_quantile_trend / sg_window_group_quantile_trend / sg_window_group_node_quantile_trend, {5, by, k, the bits of min_value} per sg_window_group_nodes_top_tail
     std::vector<std::array<uint64_t, 4>> k20_ops;      // {1, spaces, n_q, the first four per-mille 16 bits each} per sg_set_quantiles, {2 / 3 / 4, n_index (~0: no index), cap, 0} per sg_window_node_quantiles / sg_window_group_quantiles / sg_window_group_node_quantiles
     size_t k20_nq = 2;
     std::vector<std::array<uint64_t, 4>> k19_ops;      // {1, quiet_windows, max_tracks, reserved} per sg_set_group_tracks (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incident_tracks, {3, cap, 0, 0} per sg_window_group_tracks_ended
@@ -215,6 +216,36 @@ int m_quantile_rows(sg_handle h, uint64_t which, size_t sides, const uint32_t* i
 int m_window_node_quantiles(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) { return m_quantile_rows(h, 2, 2, idx, n_idx, out, cap, n); }
 int m_window_group_quantiles(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) { return m_quantile_rows(h, 3, 1, idx, n_idx, out, cap, n); }
 int m_window_group_node_quantiles(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) { return m_quantile_rows(h, 4, 2, idx, n_idx, out, cap, n); }
+// K21's stand-ins: the switch recorded; three rows a space (in_seen / windows_seen = 10 * which + the row's index, lat_dev 8 + which);
+// the tail selection is K16's with rows 1 and 2 of three
+int m_set_quantile_trend(sg_handle h, uint32_t spaces, uint32_t permille, const sg_trend_params* p) {
+    M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k21_ops.push_back({1u, spaces, permille, p ? p->shift : ~0ull}); return spaces > 7u ? SG_EINVAL : SG_OK;
+}
+static int m_tail_node_rows(sg_handle h, uint64_t which, sg_node_trend* out, size_t cap, size_t* n) {
+    M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k21_ops.push_back({which, (uint64_t)cap, 0u, 0u});
+    if (n) *n = 3;
+    for (size_t i = 0; out && i < std::min<size_t>(3, cap); i++) { sg_node_trend t{}; t.in_lat_dev = 8.f + (float)which; t.in_seen = (uint32_t)(10 * which + i); out[i] = t; }
+    return SG_OK;
+}
+int m_window_node_quantile_trend(sg_handle h, const uint32_t*, size_t, sg_node_trend* out, size_t cap, size_t* n) { return m_tail_node_rows(h, 2, out, cap, n); }
+int m_window_group_node_quantile_trend(sg_handle h, const uint32_t*, size_t, sg_node_trend* out, size_t cap, size_t* n) { return m_tail_node_rows(h, 4, out, cap, n); }
+int m_window_group_quantile_trend(sg_handle h, const uint32_t*, size_t, sg_edge_trend* out, size_t cap, size_t* n) {
+    M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k21_ops.push_back({3u, (uint64_t)cap, 0u, 0u});
+    if (n) *n = 3;
+    for (size_t i = 0; out && i < std::min<size_t>(3, cap); i++) { sg_edge_trend t{}; t.lat_dev = 11.f; t.windows_seen = (uint32_t)(30 + i); out[i] = t; }
+    return SG_OK;
+}
+int m_window_group_nodes_top_tail(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* idx, size_t cap, size_t* n_sel, size_t* n) {
+    M_LOCK(h);
+    uint32_t bits; std::memcpy(&bits, &min_value, 4);
+    reinterpret_cast<MockEngine*>(h)->k21_ops.push_back({5u, by, k, bits});
+    if (n_sel) *n_sel = 2;
+    if (n) *n = 3;
+    const sg_node_out e[2] = {m_node(SG_MAKE_REF(SG_REF_GROUP, 0), 4, 9, 1, 1, 0.5f), m_node(SG_MAKE_REF(SG_REF_KNOWN, 0), 0, 4, 0, 1, 0.25f)};
+    const uint32_t at[2] = {1u, 2u};
+    for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
+    return SG_OK;
+}
 int m_window_group_node_incident(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
     M_LOCK(h);
     reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({3u, (uint64_t)n_idx, (uint64_t)cap, 0u});
@@ -317,6 +348,9 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.window_group_tracks_ended = m_window_group_tracks_ended;
         c->api.set_quantiles = m_set_quantiles; c->api.window_node_quantiles = m_window_node_quantiles;
         c->api.window_group_quantiles = m_window_group_quantiles; c->api.window_group_node_quantiles = m_window_group_node_quantiles;
+        c->api.set_quantile_trend = m_set_quantile_trend; c->api.window_node_quantile_trend = m_window_node_quantile_trend;
+        c->api.window_group_quantile_trend = m_window_group_quantile_trend; c->api.window_group_node_quantile_trend = m_window_group_node_quantile_trend;
+        c->api.window_group_nodes_top_tail = m_window_group_nodes_top_tail;
         c->api.set_group_incidents = m_set_group_incidents; c->api.window_group_incidents = m_window_group_incidents;
         c->api.window_group_node_incident = m_window_group_node_incident;
     }
@@ -499,6 +533,33 @@ long sgh_graphds_latency(void* g, int which, const uint32_t* index, size_t n_ind
                                                                                     : ds->WorkloadLatency(index, n_index, &v);
     if (words) *words = v.size();
     if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(uint32_t));
+    return n;
+}
+// the tail baselines (K21): the switch (on = 0: off; a parameter 0 = its default), the last flushed window's tail rows — which = 0 the
+// node rows and 2 the workload rows (sg_node_trend), 1 the group edges (sg_edge_trend); cap counts rows of out — and the selection
+// over the workload rows by their tail rows, as sgh_graphds_workload_nodes_top gives it
+int sgh_graphds_set_tail_trend(void* g, uint32_t spaces, uint32_t permille, int on, uint32_t shift, uint32_t warmup, uint32_t ttl, uint64_t max_entries) {
+    sg_trend_params p{}; p.struct_size = sizeof p; p.shift = shift; p.warmup = warmup; p.ttl = ttl; p.max_entries = max_entries;
+    return static_cast<HostCtx*>(g)->ds->SetTailTrend(spaces, permille, on ? &p : nullptr);
+}
+long sgh_graphds_tail_trends(void* g, int which, void* out, size_t cap) {
+    GraphDS* ds = static_cast<HostCtx*>(g)->ds.get();
+    if (which == 1) {
+        std::vector<sg_edge_trend> v;
+        const long n = ds->WorkloadEdgeTailTrends(&v);
+        if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_edge_trend));
+        return n;
+    }
+    std::vector<sg_node_trend> v;
+    const long n = which == 0 ? ds->NodeTailTrends(&v) : ds->WorkloadTailTrends(&v);
+    if (n > 0 && out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_node_trend));
+    return n;
+}
+long sgh_graphds_workload_tail_top(void* g, uint32_t by, uint32_t k, float min_value, sgh_workload_node* out, uint32_t* index, size_t cap) {
+    std::vector<WorkloadNode> v; std::vector<uint32_t> idx;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadTailTop(by, k, min_value, &v, &idx);
+    if (n < 0) return n;
+    for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_node(v[i], out + i); if (index) index[i] = idx[i]; }
     return n;
 }
 int sgh_graphds_ingest_wire(void* g, const uint8_t* recs, size_t n, const uint32_t* kafka_msgs) {
@@ -803,6 +864,14 @@ size_t sgh_mock_k18_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k18_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k18_ops[i].data(), 32);
     return m->k18_ops.size();
+}
+size_t sgh_mock_k21_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k21_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k21_ops[i].data(), 32);
+    return m->k21_ops.size();
 }
 size_t sgh_mock_k20_ops(void* g, uint64_t* out4, size_t cap) {
     auto* c = static_cast<HostCtx*>(g);

@@ -37,6 +37,7 @@
 #include "sg_group_incident.h"
 #include "sg_group_track.h"
 #include "sg_quantiles.h"
+#include "sg_quantile_trend.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -262,6 +263,10 @@ struct sg_engine {
                         unsigned char* stage = nullptr; u32* stage_idx = nullptr; std::vector<u64*> hist; std::vector<u32*> quant;
                         std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; };
     struct Quantiles { sgplan::QuantPlan plan; u32 n_q = 0; u32 qm[SG_Q_MAX] = {}; QuantSpace sp[3]; } qnt;
+    // K21, the tail baselines (sg_quantile_trend.h): per K20 space a Baseline of its own fed the tracked quantile (index qi of the
+    // slot's quantile table), allocated at sg_set_quantile_trend (sg_plan.hpp plan_quantile_trend), freed with its K20 space and by
+    // any sg_set_quantiles
+    struct QuantTrend { u32 qi = 0; Baseline<sg_node_trend> nodes; Baseline<sg_edge_trend> groups; Baseline<sg_node_trend> workloads; } qtr;
 };
 
 namespace {
@@ -803,6 +808,22 @@ struct EdgeSpace {
 };
 EdgeSpace edge_space(sg_engine* e) { return {&e->trend, &e->vanished, kTrendWords, kVanishedWords, node_space}; }
 EdgeSpace group_edge_space(sg_engine* e) { return {&e->gtrend, &e->gvanished, kGroupTrendWords, kGroupVanishedWords, workload_space}; }
+// K21's words by K20 space, and the node spaces as the tail baselines see them: the space with the tail baseline as its baseline,
+// so that the node baselines' readbacks and the node selection serve the tail rows as they are
+constexpr StageWords kQuantTrendWords[3] = {
+    {"the node tail baseline is off (sg_set_quantile_trend, SG_Q_NODES)", "the node tail baseline was off"},
+    {"the group tail baseline is off (sg_set_quantile_trend, SG_Q_GROUPS)", "the group tail baseline was off"},
+    {"the workload tail baseline is off (sg_set_quantile_trend, SG_Q_GROUP_NODES)", "the workload tail baseline was off"}};
+NodeSpace tail_node_space(sg_engine* e) {
+    NodeSpace ns = node_space(e);
+    ns.trend = &e->qtr.nodes; ns.trend_w = kQuantTrendWords[0]; ns.sel_w = "node tail selection";
+    return ns;
+}
+NodeSpace tail_workload_space(sg_engine* e) {
+    NodeSpace ns = workload_space(e);
+    ns.trend = &e->qtr.workloads; ns.trend_w = kQuantTrendWords[2]; ns.sel_w = "workload tail selection";
+    return ns;
+}
 
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
 static_assert(sizeof(KcScratch) <= sgplan::kPrepareLds, "a folded close's prepare workgroup lays KcScratch over pass B's dynamic LDS");
@@ -1242,7 +1263,43 @@ int launch_quantiles(sg_engine* e, int k, hipStream_t s) {
     x.valid[e->cur] = 1;
     return SG_OK;
 }
+// ---- K21, the tail baselines (engine lock held) -------------------------------------------------------------------------------------
+static_assert(sizeof(K21Sample) == 48 && SG_Q_MAX == 8, "sg_quantile_trend.h reads SG_Q_MAX words an entity and side");
+// enqueue the update of tail baseline t of K20 space k by the window in slot cur on stream s, behind the space's fold on the same
+// stream: a (its base part filled by the caller) gets the slot's quantile table and the tracked index; K8's three launches
+template <class Row, class Args>
+int launch_tail(sg_engine* e, sg_engine::Baseline<Row>& t, int k, hipStream_t s, Args& a, void (*count)(Args), void (*write)(Args)) {
+    a.quant = e->qnt.sp[k].quant[e->cur]; a.qi = e->qtr.qi;
+    if (const int rc = enqueue_baseline(e, t, s, [&] {
+            hipLaunchKernelGGL(count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, a.b.t, t.plan.wgs);
+            hipLaunchKernelGGL(write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+        })) return rc;
+    t.valid[e->cur] = 1;
+    return SG_OK;
+}
+// over a node space (ns: tail_node_space / tail_workload_space), K10's arguments as launch_node_trend fills them
+int launch_node_tail(sg_engine* e, const NodeSpace& ns, int k, hipStream_t s, void (*count)(NodeQTrendArgs), void (*write)(NodeQTrendArgs)) {
+    sg_engine::Baseline<sg_node_trend>& t = *ns.trend;
+    NodeQTrendArgs a{};
+    a.b.t = baseline_args(work(e), t);
+    a.b.nodes = ns.roll->rows[e->cur]; a.b.count = ns.roll->count[e->cur]; a.b.ncap = ns.cap; a.b.out = t.rows[e->cur];
+    return launch_tail(e, t, k, s, a, count, write);
+}
+// over the group edges, K15's arguments as launch_group_trend fills them
+int launch_group_tail(sg_engine* e, hipStream_t s) {
+    sg_engine::Baseline<sg_edge_trend>& t = e->qtr.groups;
+    GroupQTrendArgs a{};
+    a.b.t = baseline_args(work(e), t);
+    a.b.groups = e->grp.rows[e->cur]; a.b.count = e->grp.count[e->cur]; a.b.max_edges = std::max<u64>(e->cfg.max_edges, 1); a.b.out = t.rows[e->cur];
+    return launch_tail(e, t, kQGroups, s, a, k21_gcount, k21_gwrite);
+}
+void free_quantile_trend(sg_engine* e, int k) {
+    if (k == kQGroups) free_baseline(e->qtr.groups);
+    else free_baseline(k == kQNodes ? e->qtr.nodes : e->qtr.workloads);
+}
 void free_quantiles(sg_engine* e, int k) {
+    free_quantile_trend(e, k);                                        // (the tail baseline reads the space's table)
     free_stage(e->qnt.sp[k]);
     e->qnt.plan.sp[k] = sgplan::QuantSpace{};
     e->qnt.plan.spaces &= ~(1u << k);
@@ -1321,11 +1378,13 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
         if (e->trk.on) { if (const int rc = launch_node_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
         if (e->qnt.sp[kQNodes].on) { if (const int rc = launch_quantiles(e, kQNodes, s)) return rc; }   // K20 behind K9: the rows, their histograms, the node rows
+        if (e->qtr.nodes.on) { if (const int rc = launch_node_tail(e, tail_node_space(e), kQNodes, s, k21_ncount, k21_nwrite)) return rc; }   // K21 behind K20: the node rows, the quantiles
     }
     if (e->grp.on) {                                                 // K14 behind K5: the rows and the window counters only, whatever else is on
         if (const int rc = launch_groups(e, s)) return rc;
         if (e->gtrend.on) { if (const int rc = launch_group_trend(e, s)) return rc; }   // K15 behind K14: the group edges, their count, the outbound IPs
         if (e->qnt.sp[kQGroups].on) { if (const int rc = launch_quantiles(e, kQGroups, s)) return rc; }   // K20 behind K14: the histograms, perm, row_group, the group edges
+        if (e->qtr.groups.on) { if (const int rc = launch_group_tail(e, s)) return rc; }   // K21 behind K20: the group edges, the quantiles
         if (e->gnodes.on) {                                          // K16 behind K14: the group edges and their count; its baseline behind it
             if (const int rc = launch_group_nodes(e, s)) return rc;
             if (e->gntrend.on) { if (const int rc = launch_node_trend(e, workload_space(e), s, k16_tcount, k16_twrite)) return rc; }
@@ -1333,6 +1392,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
             if (e->ginc.on) { if (const int rc = launch_group_incidents(e, s)) return rc; }   // K18 behind K15, K16 and K17: the group trend rows, the workload rows, the rank rows
             if (e->gtrk.on) { if (const int rc = launch_group_tracks(e, s)) return rc; }   // K19 behind K18: the workload rows, the incident rows, the incident per workload row
             if (e->qnt.sp[kQWorkloads].on) { if (const int rc = launch_quantiles(e, kQWorkloads, s)) return rc; }   // K20 behind K16: and the workload rows
+            if (e->qtr.workloads.on) { if (const int rc = launch_node_tail(e, tail_workload_space(e), kQWorkloads, s, k21_wcount, k21_wwrite)) return rc; }   // K21 behind K20
         }
     }
     return SG_OK;
@@ -1576,13 +1636,14 @@ int launch_rank_select(sg_engine* e, const NodeSpace& ns, hipStream_t st, int sl
         if (d_rank) hipLaunchKernelGGL(k_gather_sel<sg_node_rank>, grid, dim3(256), 0, st, rk, (const u32*)a.out_idx, (const u64*)d_n, a.cap, d_rank);
     });
 }
-// over the group edges by a key of SG_SEL_*: k15_keys over them and, for a trend key, the window's group trend rows (behind K15's update)
-int launch_group_select(sg_engine* e, hipStream_t st, int slot, u32 by, u32 k, float min_value, sg_group_edge* d_out, u32* d_index,
-                        u64 cap, u64* d_n) {
+// over the group edges by a key of SG_SEL_*: k15_keys over them and, for a trend key, the window's group trend rows of baseline t
+// (K15's, or K21's over the group edges; behind its update)
+int launch_group_select(sg_engine* e, const sg_engine::Baseline<sg_edge_trend>& t, hipStream_t st, int slot, u32 by, u32 k, float min_value,
+                        sg_group_edge* d_out, u32* d_index, u64 cap, u64* d_n) {
     const SelView<sg_group_edge> v = group_sel_view(e, slot);
     return launch_index_select(e, v, st, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
-        if (by != SG_SEL_SCORE && e->gtrend.pending) HIP_TRY(e, hipStreamWaitEvent(st, e->gtrend.ev, 0));
-        const sg_edge_trend* tr = by != SG_SEL_SCORE ? e->gtrend.rows[slot] : nullptr;
+        if (by != SG_SEL_SCORE && t.pending) HIP_TRY(e, hipStreamWaitEvent(st, t.ev, 0));
+        const sg_edge_trend* tr = by != SG_SEL_SCORE ? t.rows[slot] : nullptr;
         hipLaunchKernelGGL(k15_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, v.rows, v.count, tr, by, v.sel->ctr);
         return (int)SG_OK;
     }, [](const SelArgs&, dim3) {});
@@ -1622,13 +1683,13 @@ int node_top_host(sg_engine* e, const NodeSpace& ns, L launch, sg_node_out* out,
 }
 // over the group edges (sg_window_groups_top): the indices alone are selected, then the selected group edges are gathered through
 // the staging of SG_SELECT_MAX_K, in pieces when there are more of them than it holds (k = 0)
-int group_top_host(sg_engine* e, u32 by, u32 k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap, size_t* n_selected,
-                   size_t* n_groups) {
+int group_top_host(sg_engine* e, const sg_engine::Baseline<sg_edge_trend>& t, u32 by, u32 k, float min_value, sg_group_edge* out,
+                   uint32_t* group_index, size_t cap, size_t* n_selected, size_t* n_groups) {
     if (const int rc = gsel_reserve(e)) return rc;
     const SelView<sg_group_edge> v = group_sel_view(e, e->cur);
     sg_engine::IdxSel<sg_group_edge>& s = *v.sel;
     const u64 stage = std::min<u64>(cap, v.cap);
-    return index_top_host(e, v, stage, [&] { return launch_group_select(e, e->rd_stream, e->cur, by, k, min_value, nullptr, nullptr, stage, s.n); }, [&](size_t take) {
+    return index_top_host(e, v, stage, [&] { return launch_group_select(e, t, e->rd_stream, e->cur, by, k, min_value, nullptr, nullptr, stage, s.n); }, [&](size_t take) {
         for (size_t o = 0; out && o < take; o += (size_t)s.stage_rows) {
             const size_t piece = std::min<size_t>((size_t)s.stage_rows, take - o);
             hipLaunchKernelGGL(k_gather<sg_group_edge>, dim3((unsigned)((piece + 255) / 256)), dim3(256), 0, e->rd_stream, v.rows,
@@ -3226,6 +3287,17 @@ int sg_window_groups_buffer(sg_handle e, void** d_edges, void** d_count, void** 
 }
 
 // ---- K15, the workload baselines -----------------------------------------------------------------------------------------------
+namespace {
+// the group trend rows of baseline t (K15's, or K21's over the group edges) of the last read window (engine lock held)
+int group_trend_read(sg_engine* e, sg_engine::Baseline<sg_edge_trend>& t, const char* call, const StageWords& what, const uint32_t* group_index,
+                     size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
+    if (const int rc = stage_ready(e, t, call, what)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->grp.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const std::string beyond = std::string(call) + ": a group index beyond the window's group edges";
+    return baseline_rows(e, t, (size_t)cnt, group_index, n_index, out, cap, n, beyond.c_str());
+}
+}  // namespace
 int sg_set_group_trend(sg_handle e, const sg_trend_params* p) {
     if (!e) return SG_EINVAL;
     std::unique_lock<std::mutex> g(e->mu);
@@ -3245,11 +3317,7 @@ int sg_set_group_trend(sg_handle e, const sg_trend_params* p) {
 int sg_window_group_trend(sg_handle e, const uint32_t* group_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
     if (!e) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    sg_engine::Baseline<sg_edge_trend>& t = e->gtrend;
-    if (const int rc = stage_ready(e, t, "sg_window_group_trend", kGroupTrendWords)) return rc;
-    u64 cnt = 0;
-    HIP_TRY(e, hipMemcpy(&cnt, e->grp.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
-    return baseline_rows(e, t, (size_t)cnt, group_index, n_index, out, cap, n, "sg_window_group_trend: a group index beyond the window's group edges");
+    return group_trend_read(e, e->gtrend, "sg_window_group_trend", kGroupTrendWords, group_index, n_index, out, cap, n);
 }
 int sg_window_group_trend_buffer(sg_handle e, void** d_trend) {
     if (!e || !d_trend) return SG_EINVAL;
@@ -3290,12 +3358,13 @@ int sg_window_group_vanished_buffer(sg_handle e, void** d_rows, void** d_count) 
 namespace {
 // by > 3: SG_EINVAL; the groups off, or a trend key with the group trend off: SG_ESTATE; then the window in `slot` must have them
 // (not shared with check_by, K7's over the edge rows: that one has no stage below it and no valid to look at, and its host form is a flush)
-int check_gsel(sg_engine* e, u32 by, int slot) {
-    if (by > SG_SEL_NEW) { e->err = "group selection: unknown key (by > SG_SEL_NEW)"; return SG_EINVAL; }
-    if (!e->grp.on) { e->err = "group selection: the groups are off (sg_set_groups)"; return SG_ESTATE; }
-    if (by != SG_SEL_SCORE && !e->gtrend.on) { e->err = "group selection by a trend key: the group trend is off (sg_set_group_trend)"; return SG_ESTATE; }
-    if (!e->grp.valid[slot]) { e->err = "group selection: the window was closed while the groups were off"; return SG_ESTATE; }
-    if (by != SG_SEL_SCORE && !e->gtrend.valid[slot]) { e->err = "group selection: the window was closed while the group trend was off"; return SG_ESTATE; }
+// t, tw: the baseline whose rows a trend key reads and its words (K15's; K21's for the tail selection, named `sel`)
+int check_gsel(sg_engine* e, const sg_engine::Baseline<sg_edge_trend>& t, const StageWords& tw, const std::string& sel, u32 by, int slot) {
+    if (by > SG_SEL_NEW) { e->err = sel + ": unknown key (by > SG_SEL_NEW)"; return SG_EINVAL; }
+    if (!e->grp.on) { e->err = sel + ": the groups are off (sg_set_groups)"; return SG_ESTATE; }
+    if (by != SG_SEL_SCORE && !t.on) { e->err = sel + " by a trend key: " + tw.off; return SG_ESTATE; }
+    if (!e->grp.valid[slot]) { e->err = sel + ": the window was closed while the groups were off"; return SG_ESTATE; }
+    if (by != SG_SEL_SCORE && !t.valid[slot]) { e->err = sel + ": the window was closed while " + tw.was; return SG_ESTATE; }
     return SG_OK;
 }
 }  // namespace
@@ -3303,18 +3372,18 @@ int sg_window_groups_top(sg_handle e, uint32_t by, uint32_t k, float min_value, 
                          size_t* n_selected, size_t* n_groups) {
     if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
-    if (const int rc = check_gsel(e, by, e->cur)) return rc;
+    if (const int rc = check_gsel(e, e->gtrend, kGroupTrendWords, "group selection", by, e->cur)) return rc;
     if (e->closing || e->flush_open) { e->err = "sg_window_groups_top while a flush is open"; return SG_ESTATE; }
-    return group_top_host(e, by, k, min_value, out, group_index, cap, n_selected, n_groups);
+    return group_top_host(e, e->gtrend, by, k, min_value, out, group_index, cap, n_selected, n_groups);
 }
 int sg_window_groups_select(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_group_edge* d_out, uint32_t* d_index, size_t cap,
                             uint64_t* d_n, void* stream) {
     if (!e || k > SG_SELECT_MAX_K || !d_n) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     const int slot = ran_slot(e);
-    if (const int rc = check_gsel(e, by, slot)) return rc;
+    if (const int rc = check_gsel(e, e->gtrend, kGroupTrendWords, "group selection", by, slot)) return rc;
     if (const int rc = gsel_reserve(e)) return rc;
-    return launch_group_select(e, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
+    return launch_group_select(e, e->gtrend, pick_ran(e, stream), slot, by, k, min_value, d_out, d_index, cap, reinterpret_cast<u64*>(d_n));
 }
 
 // ---- K16, the workload rows: K9's, K10's and the node selection's code over the workload space --------------------------------------
@@ -3827,6 +3896,115 @@ int sg_window_quantiles_buffer(sg_handle e, uint32_t space, void** d_hist, void*
     if (const int rc = stage_slot(e, x, "sg_window_quantiles_buffer", kQuantWords[k], &slot)) return rc;
     *d_hist = x.hist[slot]; *d_quantiles = x.quant[slot];
     return SG_OK;
+}
+
+// ---- K21, the tail baselines: the C ABI ---------------------------------------------------------------------------------------------
+namespace {
+int quantile_space(uint32_t space) { return space == SG_Q_NODES ? kQNodes : space == SG_Q_GROUPS ? kQGroups : space == SG_Q_GROUP_NODES ? kQWorkloads : -1; }
+int bad_space(sg_engine* e, const char* call) { e->err = std::string(call) + ": space is one of SG_Q_NODES, SG_Q_GROUPS, SG_Q_GROUP_NODES"; return SG_EINVAL; }
+// the tail selections refuse a window without tail rows whatever the key (the plain selections serve SG_*SEL_SCORE without them)
+int tail_sel_ready(sg_engine* e, bool on, const std::vector<char>& valid, int k, const char* call, int slot) {
+    if (!on) { e->err = std::string(call) + ": " + kQuantTrendWords[k].off; return SG_ESTATE; }
+    if (!valid[slot]) { e->err = std::string(call) + ": the window was closed while " + kQuantTrendWords[k].was; return SG_ESTATE; }
+    return SG_OK;
+}
+int nodes_top_tail(sg_engine* e, const NodeSpace& ns, int k, const char* call, u32 by, u32 kk, float min_value, sg_node_out* out, uint32_t* node_index,
+                   size_t cap, size_t* n_selected, size_t* n_nodes) {
+    if (by > SG_NSEL_NEW) { e->err = std::string(ns.sel_w) + ": unknown key (by > SG_NSEL_NEW)"; return SG_EINVAL; }
+    if (const int rc = tail_sel_ready(e, ns.trend->on, ns.trend->valid, k, call, e->cur)) return rc;
+    return nodes_top(e, ns, call, by, kk, min_value, out, node_index, cap, n_selected, n_nodes);
+}
+}  // namespace
+int sg_set_quantile_trend(sg_handle e, uint32_t spaces, uint32_t permille, const sg_trend_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    if (e->closing || e->flush_open) { e->err = "sg_set_quantile_trend while a flush is open"; return SG_ESTATE; }
+    if (!spaces || !p) { for (int k = 0; k < 3; k++) free_quantile_trend(e, k); return SG_OK; }
+    u32 on = 0;
+    for (int k = 0; k < 3; k++) on |= e->qnt.sp[k].on ? 1u << k : 0u;
+    const u32 slots = (u32)e->slots.size();
+    sgplan::QuantTrendPlan P;
+    const int prc = sgplan::plan_quantile_trend(*p, spaces, on, permille, e->qnt.qm, e->qnt.n_q, e->plan.ncap, e->cfg.max_edges,
+                                                e->gnodes.on ? e->gnodes.plan.nc : 0, slots, &P);
+    if (prc == SG_ESTATE) {
+        for (int k = 0; k < 3; k++) if ((spaces >> k & 1u) && !e->qnt.sp[k].on) { e->err = std::string("sg_set_quantile_trend: ") + kQuantWords[k].off; break; }
+        return SG_ESTATE;
+    }
+    if (prc) { e->err = "sg_set_quantile_trend: unknown space bits, bad parameters, or a per-mille sg_set_quantiles was not given"; return SG_EINVAL; }
+    for (int k = 0; k < 3; k++) free_quantile_trend(e, k);
+    auto release = [e] { for (int k = 0; k < 3; k++) free_quantile_trend(e, k); };
+    e->qtr.qi = P.qi;
+    int rc = SG_OK;
+    if (!rc && (spaces & SG_Q_NODES)) { rc = baseline_on(e, e->qtr.nodes, P.params[kQNodes], P.sp[kQNodes], "sg_set_quantile_trend", release); if (!rc) e->qtr.nodes.valid.assign(slots, 0); }
+    if (!rc && (spaces & SG_Q_GROUPS)) { rc = baseline_on(e, e->qtr.groups, P.params[kQGroups], P.sp[kQGroups], "sg_set_quantile_trend", release); if (!rc) e->qtr.groups.valid.assign(slots, 0); }
+    if (!rc && (spaces & SG_Q_GROUP_NODES)) { rc = baseline_on(e, e->qtr.workloads, P.params[kQWorkloads], P.sp[kQWorkloads], "sg_set_quantile_trend", release); if (!rc) e->qtr.workloads.valid.assign(slots, 0); }
+    if (rc) { const std::string msg = e->err; release(); e->err = msg; }
+    return rc;
+}
+int sg_window_node_quantile_trend(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return node_trend_read(e, tail_node_space(e), "sg_window_node_quantile_trend", node_index, n_index, out, cap, n);
+}
+int sg_window_group_quantile_trend(sg_handle e, const uint32_t* group_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return group_trend_read(e, e->qtr.groups, "sg_window_group_quantile_trend", kQuantTrendWords[kQGroups], group_index, n_index, out, cap, n);
+}
+int sg_window_group_node_quantile_trend(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return node_trend_read(e, tail_workload_space(e), "sg_window_group_node_quantile_trend", node_index, n_index, out, cap, n);
+}
+int sg_window_quantile_trend_buffer(sg_handle e, uint32_t space, void** d_trend) {
+    if (!e || !d_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = quantile_space(space);
+    if (k < 0) return bad_space(e, "sg_window_quantile_trend_buffer");
+    if (k != kQGroups) return node_trend_buffer(e, k == kQNodes ? tail_node_space(e) : tail_workload_space(e), "sg_window_quantile_trend_buffer", d_trend);
+    int slot;
+    if (const int rc = stage_slot(e, e->qtr.groups, "sg_window_quantile_trend_buffer", kQuantTrendWords[k], &slot)) return rc;
+    *d_trend = e->qtr.groups.rows[slot];
+    return SG_OK;
+}
+int sg_quantile_trend_entries(sg_handle e, uint32_t space, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = quantile_space(space);
+    if (k < 0) return bad_space(e, "sg_quantile_trend_entries");
+    if (k == kQGroups) return baseline_entries(e, e->qtr.groups, "sg_quantile_trend_entries", kQuantTrendWords[k], out, cap, n);
+    return baseline_entries(e, k == kQNodes ? e->qtr.nodes : e->qtr.workloads, "sg_quantile_trend_entries", kQuantTrendWords[k], out, cap, n);
+}
+int sg_quantile_trend_stats_get(sg_handle e, uint32_t space, sg_trend_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = quantile_space(space);
+    if (k < 0) return bad_space(e, "sg_quantile_trend_stats_get");
+    if (k == kQGroups) return baseline_stats(e, e->qtr.groups, "sg_quantile_trend_stats_get", kQuantTrendWords[k], out);
+    return baseline_stats(e, k == kQNodes ? e->qtr.nodes : e->qtr.workloads, "sg_quantile_trend_stats_get", kQuantTrendWords[k], out);
+}
+int sg_window_nodes_top_tail(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
+                             size_t* n_selected, size_t* n_nodes) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return nodes_top_tail(e, tail_node_space(e), kQNodes, "sg_window_nodes_top_tail", by, k, min_value, out, node_index, cap, n_selected, n_nodes);
+}
+int sg_window_groups_top_tail(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap,
+                              size_t* n_selected, size_t* n_groups) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Baseline<sg_edge_trend>& t = e->qtr.groups;
+    if (by > SG_SEL_NEW) { e->err = "group tail selection: unknown key (by > SG_SEL_NEW)"; return SG_EINVAL; }
+    if (const int rc = tail_sel_ready(e, t.on, t.valid, kQGroups, "sg_window_groups_top_tail", e->cur)) return rc;
+    if (const int rc = check_gsel(e, t, kQuantTrendWords[kQGroups], "group tail selection", by, e->cur)) return rc;
+    if (e->closing || e->flush_open) { e->err = "sg_window_groups_top_tail while a flush is open"; return SG_ESTATE; }
+    return group_top_host(e, t, by, k, min_value, out, group_index, cap, n_selected, n_groups);
+}
+int sg_window_group_nodes_top_tail(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
+                                   size_t* n_selected, size_t* n_nodes) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return nodes_top_tail(e, tail_workload_space(e), kQWorkloads, "sg_window_group_nodes_top_tail", by, k, min_value, out, node_index, cap, n_selected, n_nodes);
 }
 
 int sg_window_hist(sg_handle e, uint32_t* bins, size_t cap_rows, size_t* n) {

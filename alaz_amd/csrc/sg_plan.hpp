@@ -1326,6 +1326,40 @@ inline QuantPlan plan_quantiles(u64 max_edges, u32 ncap, u64 gk, u32 nc, u32 spa
     return q;
 }
 
+// K21, the tail baselines (sg_quantile_trend.h): per requested K20 space the baseline its mean baseline would get — K10's plan over
+// the node rows, K15's over the group edges, K16's over the workload rows: the same capacity default, grid, scratch and per-slot
+// row table — fed one tracked quantile of K20's table.  sg_set_quantile_trend allocates it, never sg_create or sg_set_quantiles.
+// the position of `permille` among the n_q per-mille sg_set_quantiles was last given (the first, if it is there twice), or -1
+inline int quantile_index(const u32* qm, u32 n_q, u32 permille) {
+    for (u32 k = 0; k < n_q && k < kQMax; k++) if (qm[k] == permille) return (int)k;
+    return -1;
+}
+struct QuantTrendPlan {
+    u32 spaces = 0, qi = 0;       // the SG_Q_* bits that are on; the tracked quantile's index
+    sg_trend_params params[3] = {};   // the resolved parameters of each space (max_entries defaults differ)
+    TrendPlan sp[3];              // nodes, group edges, workloads: a device block each
+    u64 total_bytes = 0;          // of the spaces that are on
+};
+// spaces: the SG_Q_* bits asked for, all of them among `on` (the spaces K20 has on: else SG_ESTATE); qm / n_q: K20's per-mille; ncap,
+// max_edges, nc: the capacities the three mean baselines are planned over.  SG_OK and *out, SG_EINVAL or SG_ESTATE
+inline int plan_quantile_trend(const sg_trend_params& p, u32 spaces, u32 on, u32 permille, const u32* qm, u32 n_q, u32 ncap, u64 max_edges,
+                               u32 nc, u32 slots, QuantTrendPlan* out) {
+    if (!spaces || (spaces & ~(SG_Q_NODES | SG_Q_GROUPS | SG_Q_GROUP_NODES))) return SG_EINVAL;
+    QuantTrendPlan q;
+    if (check_node_trend(p, ncap, &q.params[0]) || check_group_trend(p, max_edges, &q.params[1]) ||
+        check_group_node_trend(p, nc, &q.params[2])) return SG_EINVAL;
+    const int qi = quantile_index(qm, n_q, permille);
+    if (qi < 0) return SG_EINVAL;
+    if (spaces & ~on) return SG_ESTATE;
+    q.spaces = spaces; q.qi = (u32)qi;
+    if (spaces & SG_Q_NODES) q.sp[0] = plan_node_trend(ncap, slots, q.params[0]);
+    if (spaces & SG_Q_GROUPS) q.sp[1] = plan_group_trend(max_edges, slots, q.params[1]);
+    if (spaces & SG_Q_GROUP_NODES) q.sp[2] = plan_group_node_trend(nc, slots, q.params[2]);
+    for (int k = 0; k < 3; k++) q.total_bytes += q.sp[k].total_bytes;
+    *out = q;
+    return SG_OK;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

@@ -134,6 +134,13 @@ __device__ __forceinline__ void k8_span(u64 T, u64& d0, u64& d1) {
     if (d1 > T) d1 = T;
 }
 
+// How the walk counts the old entries it keeps and expires.  Written as `if (keep) kept++; else expired++;` the compiler folds the
+// two bumps into one indexed bump of a private array: 12 bytes of scratch a lane and two scratch accesses per old entry, in every
+// instantiation without the vanished count.  A source that says flat_counts adds the two conditions instead and keeps the counters
+// in registers (K21's, sg_quantile_trend.h).  K8, K10, K15 and K16 stay as they were measured: their code does not change.
+template <class S, class = void> struct K8FlatCounts { static constexpr bool value = false; };
+template <class S> struct K8FlatCounts<S, decltype((void)S::flat_counts)> { static constexpr bool value = S::flat_counts; };
+
 // The walk of one thread's span over source S's samples, shared by both passes.  WRITE = false: trend rows + counts; true: the
 // merged entries.  VAN (edges only): also count (and with WRITE write) the vanished entries: van counts them, vb = the position of
 // this thread's first one.
@@ -186,10 +193,12 @@ __device__ __forceinline__ void k8_walk_t(const TrendArgs& a, const typename S::
                         o.n[p] = cnt; o.last[p] = ls;
                     }
                 }
-                kb++; kept++;
+                kb++;
+                if constexpr (!K8FlatCounts<S>::value) kept++;
             } else {
-                expired++;
+                if constexpr (!K8FlatCounts<S>::value) expired++;
             }
+            if constexpr (K8FlatCounts<S>::value) { kept += keep ? 1u : 0u; expired += keep ? 0u : 1u; }
             pk = ak; i++;
             if (i < g.B) ak = k8_entry_key(A, i);
         } else {                                        // a sample

@@ -280,6 +280,14 @@ def _signatures() -> dict:
         "sg_window_group_hist": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_quantiles": (I, [H, P, sz, P, sz, Psz]),
         "sg_window_group_node_hist": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_node_quantiles": (I, [H, P, sz, P, sz, Psz]),
         "sg_window_quantiles_buffer": (I, [H, u32, PP, PP]),
+        "sg_set_quantile_trend": (I, [H, u32, u32, P]),
+        "sg_window_node_quantile_trend": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_quantile_trend": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_node_quantile_trend": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_quantile_trend_buffer": (I, [H, u32, PP]),
+        "sg_quantile_trend_entries": (I, [H, u32, P, sz, Psz]), "sg_quantile_trend_stats_get": (I, [H, u32, P]),
+        "sg_window_nodes_top_tail": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_groups_top_tail": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_group_nodes_top_tail": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
     }
 
 
@@ -328,6 +336,8 @@ _STAGES = dict(
                            dict(by=lambda by: ServiceGraph._by(by) if isinstance(by, str) else by)),
     group_tracks=_Stage("sg_set_group_tracks", SgTrackParams, TRACK_DEFAULTS, "set_group_tracks(None) switches workload tracking off",
                         "workload track"),
+    quantile_trend=_Stage("sg_set_quantile_trend", SgTrendParams, TREND_DEFAULTS, "set_quantile_trend(params=None) switches the tail baselines off",
+                          "tail trend"),
 )
 
 _lib = None
@@ -436,15 +446,15 @@ class ServiceGraph:
             raise ServiceGraphError(rc, (self._l.sg_last_error(self._h) or b"").decode())
         return rc
 
-    def _set_stage(self, stage: str, params, kw) -> Optional[dict]:
-        """every set_* with a params struct (_STAGES): call(h, NULL) for params None, else call(h, the struct filled by field name from
-        the defaults, params and kw); returns the merged parameters"""
+    def _set_stage(self, stage: str, params, kw, *lead) -> Optional[dict]:
+        """every set_* with a params struct (_STAGES): call(h, *lead, NULL) for params None, else call(h, *lead, the struct filled by
+        field name from the defaults, params and kw); returns the merged parameters"""
         st = _STAGES[stage]
         call = getattr(self._l, st.call)
         if params is None:
             if kw:
                 raise TypeError(f"{st.off} and takes no parameters")
-            self._ck(call(self._h, None))
+            self._ck(call(self._h, *lead, None))
             return None
         v = dict(st.defaults)
         v.update(params or {}); v.update(kw)
@@ -454,7 +464,7 @@ class ServiceGraph:
         p = st.struct(struct_size=C.sizeof(st.struct))
         for f, x in v.items():
             setattr(p, f, st.convert[f](x) if f in st.convert else x)
-        self._ck(call(self._h, C.byref(p)))
+        self._ck(call(self._h, *lead, C.byref(p)))
         return v
 
     def _counted(self, call, dtype, shape_tail=()) -> np.ndarray:
@@ -1090,6 +1100,65 @@ class ServiceGraph:
         window_run closed last (sg_window_quantiles_buffer)"""
         bits = space if isinstance(space, int) else self._qbits(space)
         return self._pointers(lambda h, *a: self._l.sg_window_quantiles_buffer(h, bits, *a), 2)
+
+    # ---- tail baselines (K21): each entity's tracked quantile against its own past ----
+    def set_quantile_trend(self, spaces=("nodes",), permille: int = 990, params: Optional[dict] = (), **kw):
+        """Switch the tail baselines on (sg_set_quantile_trend): a baseline of the `permille` quantile — one of those set_quantiles
+        was last given — per space, each among the spaces set_quantiles has on ("nodes" / "groups" / "group_nodes", or the SG_Q_*
+        bits as an int); the parameters of set_trend as keywords or a dict, max_entries 0 = the default of the mean baseline of
+        each space.  Every call starts empty baselines.  spaces None / 0 or params=None switches the stage off; so does any
+        set_quantiles call."""
+        bits = 0 if spaces is None else spaces if isinstance(spaces, int) else self._qbits(spaces)
+        self._set_stage("quantile_trend", params, kw, bits, int(permille))
+
+    def _qbit(self, space) -> int:
+        return space if isinstance(space, int) else self._qbits(space)
+
+    def window_node_quantile_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """NODE_TREND_DTYPE tail rows of the last read window (sg_window_node_quantile_trend), row k for node row k of
+        window_nodes(): lat_dev and base_mean_us of the tracked quantile, err_dev as the node trend's; or the rows at `index`."""
+        return self._window_rows(self._l.sg_window_node_quantile_trend, NODE_TREND_DTYPE, index)
+
+    def window_group_quantile_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """TREND_DTYPE tail rows (sg_window_group_quantile_trend), row k for group edge k of window_groups(); or those at `index`."""
+        return self._window_rows(self._l.sg_window_group_quantile_trend, TREND_DTYPE, index)
+
+    def window_group_node_quantile_trend(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """NODE_TREND_DTYPE tail rows (sg_window_group_node_quantile_trend), row k for row k of window_group_nodes(); or those at `index`."""
+        return self._window_rows(self._l.sg_window_group_node_quantile_trend, NODE_TREND_DTYPE, index)
+
+    def window_quantile_trend_buffer(self, space) -> int:
+        """device pointer of the tail rows of one space of the window window_run closed last (sg_window_quantile_trend_buffer)"""
+        bits = self._qbit(space)
+        return self._pointers(lambda h, *a: self._l.sg_window_quantile_trend_buffer(h, bits, *a), 1)[0]
+
+    def quantile_trend_entries(self, space) -> np.ndarray:
+        """the tail baseline of one space in key order, TREND_ENTRY_DTYPE with the keys of the mean baseline of that space and
+        lat_mean / lat_dev of the tracked quantile in ns (sg_quantile_trend_entries)"""
+        bits = self._qbit(space)
+        return self._counted(lambda h, *a: self._l.sg_quantile_trend_entries(h, bits, *a), TREND_ENTRY_DTYPE)
+
+    def quantile_trend_stats(self, space) -> SgTrendStats:
+        bits = self._qbit(space)
+        return self._stats(lambda h, *a: self._l.sg_quantile_trend_stats_get(h, bits, *a), SgTrendStats)
+
+    def window_nodes_top_tail(self, k: int, min_value: float = float("-inf"), by: str = "in_lat_dev", cap: Optional[int] = None):
+        """window_nodes_top with the tail rows as the trend source (sg_window_nodes_top_tail): by "in_lat_dev" ranks the in side's
+        deviation of the tracked quantile, and so on through NSEL_BY."""
+        b = self._nby(by)
+        return self._top(lambda *a: self._l.sg_window_nodes_top_tail(self._h, b, k, min_value, *a), self._node_cap(k, cap), NODE_DTYPE, np.uint32)
+
+    def window_groups_top_tail(self, k: int, min_value: float = float("-inf"), by: str = "lat_dev", cap: Optional[int] = None):
+        """window_groups_top with the tail rows as the trend source (sg_window_groups_top_tail); by: a key of SEL_BY."""
+        b = self._by(by)
+        cap = (k or self.max_edges) if cap is None else cap
+        return self._top(lambda *a: self._l.sg_window_groups_top_tail(self._h, b, k, min_value, *a), cap, GROUP_EDGE_DTYPE, np.uint32)
+
+    def window_group_nodes_top_tail(self, k: int, min_value: float = float("-inf"), by: str = "in_lat_dev", cap: Optional[int] = None):
+        """window_group_nodes_top with the tail rows as the trend source (sg_window_group_nodes_top_tail); by: a key of NSEL_BY."""
+        b = self._nby(by)
+        return self._top(lambda *a: self._l.sg_window_group_nodes_top_tail(self._h, b, k, min_value, *a),
+                         self._node_cap(k, cap, self._l.sg_window_group_nodes), NODE_DTYPE, np.uint32)
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

@@ -142,6 +142,9 @@ def load() -> C.CDLL:
             "sgh_mock_k19_ops": (sz, [P, P, sz]),
             "sgh_graphds_set_quantiles": (C.c_int, [P, u32, P, sz]),
             "sgh_graphds_latency": (C.c_long, [P, C.c_int, P, sz, P, sz, P]), "sgh_mock_k20_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_tail_trend": (C.c_int, [P, u32, u32, C.c_int, u32, u32, u32, C.c_uint64]),
+            "sgh_graphds_tail_trends": (C.c_long, [P, C.c_int, P, sz]),
+            "sgh_graphds_workload_tail_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]), "sgh_mock_k21_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -668,6 +671,50 @@ class GraphDS:
         n = self._l.sgh_mock_k20_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k20_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the tail baselines (K21) ----
+    def set_tail_trend(self, spaces: int = 1, permille: int = 990, on: bool = True, shift: int = 0, warmup: int = 0, ttl: int = 0,
+                       max_entries: int = 0) -> int:
+        """GraphDS::SetTailTrend: a baseline of the `permille` quantile per space (SG_Q_* bits; 0 or on=False: off; a parameter 0 =
+        its default; rc)"""
+        return self._l.sgh_graphds_set_tail_trend(self._g, spaces, permille, 1 if on else 0, shift, warmup, ttl, max_entries)
+
+    def _tail_trends(self, which: int, dtype, what: str) -> np.ndarray:
+        return self._rows(what, self._l.sgh_graphds_tail_trends, dtype, which)
+
+    def node_tail_trends(self) -> np.ndarray:
+        """GraphDS::NodeTailTrends: engine.NODE_TREND_DTYPE, row k for node row k of the last flushed window"""
+        from .engine import NODE_TREND_DTYPE
+        return self._tail_trends(0, NODE_TREND_DTYPE, "NodeTailTrends")
+
+    def workload_edge_tail_trends(self) -> np.ndarray:
+        """GraphDS::WorkloadEdgeTailTrends: engine.TREND_DTYPE, row k for edge k of workload_edges()"""
+        from .engine import TREND_DTYPE
+        return self._tail_trends(1, TREND_DTYPE, "WorkloadEdgeTailTrends")
+
+    def workload_tail_trends(self) -> np.ndarray:
+        """GraphDS::WorkloadTailTrends: engine.NODE_TREND_DTYPE, row k for row k of workload_nodes()"""
+        from .engine import NODE_TREND_DTYPE
+        return self._tail_trends(2, NODE_TREND_DTYPE, "WorkloadTailTrends")
+
+    def workload_tail_top(self, by: int, k: int, min_value: float = float("-inf")):
+        """GraphDS::WorkloadTailTop: (the selected workload rows as workload_nodes() gives them, their indices) — by = SG_NSEL_*,
+        ranked by the tail rows"""
+        n = self._l.sgh_graphds_workload_tail_top(self._g, by, k, min_value, None, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadTailTop failed: {n}")
+        out, idx = np.zeros(max(n, 1), dtype=_workload_node_dtype()), np.zeros(max(n, 1), dtype=np.uint32)
+        self._l.sgh_graphds_workload_tail_top(self._g, by, k, min_value, out.ctypes.data, idx.ctypes.data, n)
+        return out[:n], idx[:n]
+
+    def mock_k21_ops(self) -> np.ndarray:
+        """the stand-in engine's K21 calls in order, four u64 each: (1, spaces, permille, shift or all ones for NULL) per
+        sg_set_quantile_trend, (2 / 3 / 4, cap, 0, 0) per sg_window_node_quantile_trend / sg_window_group_quantile_trend /
+        sg_window_group_node_quantile_trend, (5, by, k, the bits of min_value) per sg_window_group_nodes_top_tail"""
+        n = self._l.sgh_mock_k21_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k21_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

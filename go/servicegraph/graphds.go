@@ -1613,6 +1613,78 @@ func (g *GraphDS) WorkloadLatency(index []uint32) (us []uint32, rows int, err er
 	return g.latencyRows(2, index, 2*g.nQ)
 }
 
+// ---- tail baselines (K21) ------------------------------------------------------------------------------------------------
+
+// SetTailTrend switches the tail baselines on for the spaces given (QuantileNodes, QuantileWorkEdges, QuantileWorkloads; each
+// among those SetQuantiles has on): an exponentially weighted baseline of ONE quantile — permille, one of the values SetQuantiles
+// took — per service side, workload edge and workload side, with the keys of the mean baseline of that space, so a workload's
+// history survives a rollout.  A 0 is the parameter's default (shift 4, warmup 4, ttl 64, maxEntries as the mean baseline of the
+// space).  Every call starts empty baselines; any SetQuantiles call switches the stage off.
+func (g *GraphDS) SetTailTrend(spaces, permille, shift, warmup, ttl uint32, maxEntries uint64) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var tp C.sg_trend_params
+	tp.struct_size = C.uint32_t(unsafe.Sizeof(tp))
+	tp.shift, tp.warmup, tp.ttl, tp.max_entries = C.uint32_t(shift), C.uint32_t(warmup), C.uint32_t(ttl), C.uint64_t(maxEntries)
+	if rc := C.sg_set_quantile_trend(g.h, C.uint32_t(spaces), C.uint32_t(permille), &tp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_quantile_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+// ClearTailTrend switches the tail baselines off and frees them.
+func (g *GraphDS) ClearTailTrend() error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	if rc := C.sg_set_quantile_trend(g.h, 0, 0, nil); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_quantile_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+// WindowTailRegressions answers "which workloads' tail latency left its own normal band" for the window FlushWindow returned
+// last, on the device (sg_window_group_nodes_top_tail): the k workload rows with the highest value >= minValue of key by
+// (NodeByInLatDev: the deviation of the tracked quantile of the calls the workload receives; any NodeBy* key), descending, with
+// their tail rows (sg_window_group_node_quantile_trend at the selected indices) and their indices into WindowWorkloadNodes.
+// k = 0: every such row, in order.  It needs SetTailTrend over QuantileWorkloads.
+func (g *GraphDS) WindowTailRegressions(by, k uint32, minValue float32) ([]WorkloadNode, []NodeTrend, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_group_nodes_top_tail(g.h, C.uint32_t(by), 0, C.float(minValue), nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_nodes_top_tail = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil, nil
+	}
+	ns, index := make([]C.sg_node_out, room), make([]uint32, room)
+	if rc := C.sg_window_group_nodes_top_tail(g.h, C.uint32_t(by), C.uint32_t(k), C.float(minValue), &ns[0], (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_nodes_top_tail = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		ns, index = ns[:int(sel)], index[:int(sel)]
+	}
+	if len(index) == 0 {
+		return nil, nil, nil, nil
+	}
+	var n C.size_t
+	ts := make([]C.sg_node_trend, len(index))
+	if rc := C.sg_window_group_node_quantile_trend(g.h, (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index)), &ts[0], C.size_t(len(ts)), &n); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_node_quantile_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	trends := make([]NodeTrend, len(ts))
+	for i := range ts {
+		t := &ts[i]
+		trends[i] = NodeTrend{float32(t.in_lat_dev), float32(t.in_err_dev), float32(t.out_lat_dev), float32(t.out_err_dev),
+			float32(t.in_base_mean_us), float32(t.out_base_mean_us), uint32(t.in_seen), uint32(t.out_seen)}
+	}
+	return goWorkloadNodes(ns), trends, index, nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

@@ -1064,6 +1064,50 @@ int sg_window_group_node_quantiles(sg_handle h, const uint32_t* node_index, size
  * entity and side, the first n_q of them set.  The entity count is the space's own (sg_window_nodes_buffer, ...).               */
 int sg_window_quantiles_buffer(sg_handle h, uint32_t space, void** d_hist, void** d_quantiles);
 
+/* ---- tail baselines (K21): each entity's tracked quantile against its own past, on the device -------------------------------------- *
+ * Opt-in (sg_set_quantile_trend, on an engine on which sg_set_quantiles has switched the requested spaces on); without it nothing
+ * is launched or allocated, and every other output is byte for byte the same either way.  For each requested K20 space there is
+ * one baseline with a trend-window counter of its own.  Its keys and its sample order are those of the mean baseline of that space:
+ *   SG_Q_NODES        sample 2 * node + side, side 0 = in, 1 = out; key (nk, side), the node baselines'; rows sg_node_trend
+ *   SG_Q_GROUPS       sample = group edge j; key (wk(from_ref), wk(to_ref)), the group baselines'; rows sg_edge_trend
+ *   SG_Q_GROUP_NODES  sample 2 * row + side; key (wk(ref), side), the workload baselines'; rows sg_node_trend
+ * The sample of an entity side with count c > 0 (c the count the mean baseline of the space reads: in_count / out_count of the node
+ * row, count of the group edge): x_lat = 1000.0 * Q, Q the uint32_t microsecond value K20 wrote for the tracked per-mille of that
+ * entity and side in this window — exact in fp64 (Q < 2^32, x_lat < 2^52); x_err is the space's own error sample, unchanged: the
+ * long division floor(err * 2^20 / c).  A side with c == 0 neither creates nor refreshes an entry.
+ * Side order: K20's tables hold a node's sides as [0] = out, [1] = in, the node baselines' samples are side 0 = in, 1 = out: the
+ * sample of side s reads K20 side 1 - s.
+ * Entry update, expiry (ttl), the capacity cut, the statistics and the row rule are the trend's (sg_set_trend) word for word: rows
+ * are scored from the entry as it stood before the window's update, zero below warmup or when c == 0, base_mean_us = (float)
+ * (lat_mean / 1000).  In a row lat_dev is the deviation of the tracked quantile, err_dev the error-rate deviation as in the mean
+ * baseline, base_mean_us the baseline of the quantile.  max_entries == 0 resolves to the default of the mean baseline of the
+ * space: 4 x the node rows (workload rows) a window can have for the two node-shaped spaces, 2 x max_edges for the group edges.
+ * Every close path computes it, behind K20 of the same window on the window's stream; with several windows in flight the state
+ * updates run in window order.
+ * State: sg_set_quantile_trend(h, spaces, permille, p) — spaces == 0 or p == NULL switches the stage off and frees it; every call
+ * replaces the previous setting and starts empty baselines; one sg_trend_params serves all requested spaces.  SG_EINVAL for
+ * unknown space bits, bad parameters (sg_set_trend's checks) or a permille that is not among the per-mille sg_set_quantiles was
+ * last given (the tracked quantile's index is its position there); SG_ESTATE for a space K20 has not on, or while a flush is
+ * open.  Memory is allocated there, never at sg_create.  ANY sg_set_quantiles call that is not refused switches this stage
+ * off and frees it (the quantile's index may have moved), and whatever frees a K20 space frees this stage's baseline of that space
+ * with it: sg_set_nodes(h, 0), any sg_set_groups call, sg_set_group_nodes(h, 0).  It does not touch the mean baselines, nor they it. */
+int sg_set_quantile_trend(sg_handle h, uint32_t spaces, uint32_t permille, const sg_trend_params* p);
+/* The tail rows of the last READ window, the buffer, the entries and the statistics: exactly sg_window_node_trend,
+ * sg_window_node_trend_buffer, sg_node_trend_entries and sg_node_trend_stats_get over the tail baseline of the space (SG_ESTATE for
+ * a window closed while it was off).  `space` is exactly one SG_Q_* bit, else SG_EINVAL.                                           */
+int sg_window_node_quantile_trend(sg_handle h, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n);
+int sg_window_group_quantile_trend(sg_handle h, const uint32_t* group_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n);
+int sg_window_group_node_quantile_trend(sg_handle h, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n);
+int sg_window_quantile_trend_buffer(sg_handle h, uint32_t space, void** d_trend);
+int sg_quantile_trend_entries(sg_handle h, uint32_t space, sg_trend_entry* out, size_t cap, size_t* n);
+int sg_quantile_trend_stats_get(sg_handle h, uint32_t space, sg_trend_stats* out);
+/* sg_window_nodes_top / sg_window_groups_top / sg_window_group_nodes_top with the TAIL rows as the trend source: the same `by`
+ * keys (SG_NSEL_* for the node-shaped spaces, SG_SEL_* for the group edges), the same selection, row bytes and index outputs.
+ * SG_ESTATE when the space's tail baseline is off or the window was closed while it was.                                          */
+int sg_window_nodes_top_tail(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
+int sg_window_groups_top_tail(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap, size_t* n_selected, size_t* n_groups);
+int sg_window_group_nodes_top_tail(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
