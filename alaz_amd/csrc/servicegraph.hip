@@ -335,6 +335,7 @@ template <class FnT, const auto& Keys> struct Family { typedef FnT Fn; static co
 struct K1aWide : Family<K1aFn, sgplan::kK1aWideKeys> { template <size_t I> static Fn at() { constexpr auto k = keys[I]; return k1a_partition<(bool)k[0], (bool)k[1], (bool)k[2]>; } };
 struct K1aTile : Family<K1aFn, sgplan::kK1aTileKeys> { template <size_t I> static Fn at() { constexpr auto k = keys[I]; return k1a_tile_partition<k[0], (bool)k[1], k[2]>; } };
 struct K1aTeam : Family<K1aFn, sgplan::kK1aTeamKeys> { template <size_t I> static Fn at() { constexpr auto k = keys[I]; return k1a_team_partition<k[0], (bool)k[1], 2, 1024, k[2]>; } };
+struct K1aTeamPair : Family<K1aFn, sgplan::kK1aTeamPairKeys> { template <size_t I> static Fn at() { constexpr auto k = keys[I]; return k1a_team_partition<k[0], (bool)k[1], 2, 1024, k[2], 1>; } };
 struct K1bMerge : Family<K1bFn, sgplan::kK1bMergeKeys> { template <size_t I> static Fn at() {
     constexpr auto k = keys[I]; if constexpr (k[2]) return k1b_merge<k[0], (bool)k[1]>; else return k1b_merge_wide<k[0], (bool)k[1]>; } };
 struct K1bStream : Family<K1bFn, sgplan::kK1bStreamKeys> { template <size_t I> static Fn at() {
@@ -378,7 +379,7 @@ int plan_pass_a(sg_engine* e) {
     if (!sgplan::plan_pass_a(e->plan, e->jt.l1_entries, e->jt.blocks_bytes(), e->ov, &pa)) { e->err = "K1 pass A: the join tables' level 1 and the piece counters do not fit a CU's LDS (fewer partitions / IP blocks needed)"; return SG_ENOSPC; }
     const sgplan::PassAKernel k = sgplan::choose_pass_a(e->plan, pa, e->cfg);
     bool ok = true;
-    const K1aFn f = k.family == sgplan::K1A_TEAM ? kernel_of<K1aTeam>(ok, k.l2, k.sharded, k.pb)
+    const K1aFn f = k.family == sgplan::K1A_TEAM ? (k.pair ? kernel_of<K1aTeamPair>(ok, k.l2, k.sharded, k.pb) : kernel_of<K1aTeam>(ok, k.l2, k.sharded, k.pb))
                   : k.family == sgplan::K1A_TILE ? kernel_of<K1aTile>(ok, k.l2, k.sharded, k.nsub) : kernel_of<K1aWide>(ok, k.l2, k.sharded, k.hist);
     if (!ok) { e->err = "K1 pass A: the library holds no kernel for family " + std::to_string(k.family) + ", level 2 mode " + std::to_string(k.l2); return SG_ENODEV; }
     e->pa = pa; e->kn.k1a = k; e->fn.k1a = f;
@@ -504,7 +505,7 @@ int launch_k1(sg_engine* e, const sg_event* d_ev, size_t n, hipStream_t s) {
             }
         }
         const u32 threads = !w.d.narrow ? K1A_THREADS : e->pa.k1a_team ? 1024 : K1T_THREADS;
-        hipExtLaunchKernelGGL(e->fn.k1a, dim3(w.d.nwg), dim3(threads), (uint32_t)e->pa.k1a_lds, s, ta, tb, 0u, da, d_ev, (u64)n);
+        hipExtLaunchKernelGGL(e->fn.k1a, dim3(w.d.nwg), dim3(threads), (uint32_t)(e->pa.k1a_lds + e->pa.k1a_pair_lds), s, ta, tb, 0u, da, d_ev, (u64)n);
         if (tk) { TimingRec r; r.a = ta; r.b = tb; r.kernel = 1; e->trecs.push_back(r); }
     } else {
         Timed t(e, s, 1);
@@ -2233,7 +2234,7 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
     }
     if (d.variant == 0) {
         CR(plan_pass_a(e));
-        CH(lds_limit_all<K1aWide>(kLdsBytes)); CH(lds_limit_all<K1aTile>(kLdsBytes)); CH(lds_limit_all<K1aTeam>(kLdsBytes));
+        CH(lds_limit_all<K1aWide>(kLdsBytes)); CH(lds_limit_all<K1aTile>(kLdsBytes)); CH(lds_limit_all<K1aTeam>(kLdsBytes)); CH(lds_limit_all<K1aTeamPair>(kLdsBytes));
         CH(lds_limit_all<K1bMerge>(P.k1b_lds)); CH(lds_limit_all<K1bStream>(P.k1b_lds));
         CH(lds_limit((size_t)KW_ROWS * 5 * sizeof(u64), kw_compact));
     }
@@ -2408,6 +2409,13 @@ int sg_prepare_fold_get(sg_handle e, uint32_t* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     *out = e->plan.prepare_fold ? 1u : 0u;
+    return SG_OK;
+}
+
+int sg_pass_a_pair_get(sg_handle e, uint32_t* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = e->plan.narrow && e->pa.k1a_team && e->pa.k1a_pair ? 1u : 0u;
     return SG_OK;
 }
 

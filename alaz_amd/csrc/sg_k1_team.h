@@ -40,7 +40,11 @@ static inline unsigned long long k1m_tiles(unsigned long long n, unsigned nwg, u
 // NPB: log2 of the partition count, a compile-time constant: every counter array then sits at a constant LDS offset and the scan is
 // straight-line code (with a run-time count the scan's quad loop branched per quad and its piece bases were spilled to scratch — whose
 // reload waits for vmcnt(0), i.e. for the previous tile's copy-out stores to reach memory: 3 us per scan).
-template <int L2M, bool SHARDED, int TEAMS, int NT, int NPB>
+// PAIR: 1 = a team sorts TWO tiles it draws one behind the other into one LDS tile of twice the records and copies them out together:
+// a partition's run in a copy-out is then twice as long (4 096 records over 512 partitions: 8 records = one 64-byte write request
+// instead of two of 32 — a scattered store costs its request, not its bytes).  See the tile loop.  Only where a parked record carries
+// its partition number (PACKB; sg_plan.hpp plan_pass_a picks PAIR nowhere else) and NPB is one of the quad-scan sizes.
+template <int L2M, bool SHARDED, int TEAMS, int NT, int NPB, int PAIR = 0>
 __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* __restrict__ ev, u64 n) {
     constexpr u32 K1M_THREADS = NT;
     constexpr u32 K1M_TILE_ALL = 4 * NT;                             // records in the workgroup's tile(s)
@@ -49,6 +53,8 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
     constexpr u32 K1M_GROUP = 4 * K1M_TT;                            // events per group at most: four per thread of a team
     constexpr u32 K1M_TS = K1M_TILE_ALL / TEAMS;                     // records per team tile: one group
     constexpr u32 K1M_NR = 4;                                        // records a thread parks per tile
+    constexpr u32 K1M_TILE = (PAIR ? 2u : 1u) * K1M_TS;              // records of a team's LDS tile (PAIR: two tiles' records)
+    static_assert(!PAIR || (((1u << NPB) >> 6) % 4u == 0 && ((1u << NPB) >> 6) <= 16u), "PAIR: the quad scan only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const u32 CT = d.k1a_ct;
     constexpr u32 NP = 1u << NPB;
@@ -58,8 +64,8 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
     u32* tcnt = fcw + NP;                                            // [TEAMS][4][np]: run lengths (two sets, alternating tiles) | run offsets | piece base of the run
     u64* red = reinterpret_cast<u64*>(tcnt + 4 * TEAMS * NP);        // [8] workgroup statistics (WS_* order)
     u32* bar = reinterpret_cast<u32*>(red + 8);                      // [16] team barrier counters (team k: word 8 k)
-    u64* tiles = reinterpret_cast<u64*>(bar + 16);                   // [TEAMS][K1M_TS + 2]: a team's tile, then its trash word (+ pad: 16-byte alignment)
-    uint4* jl = reinterpret_cast<uint4*>(tiles + K1M_TILE_ALL + 4);  // LDS copy of the join blob: jl1 | jl2 (L2M != 0), d.jstage_bytes (a multiple of 16)
+    u64* tiles = reinterpret_cast<u64*>(bar + 16);                   // [TEAMS][K1M_TILE + 2]: a team's tile, then its trash word (+ pad: 16-byte alignment)
+    uint4* jl = reinterpret_cast<uint4*>(tiles + TEAMS * K1M_TILE + 4);   // LDS copy of the join blob: jl1 | jl2 (L2M != 0), d.jstage_bytes (a multiple of 16)
     const u32 jl1_bytes = (d.jl1mask + 1) * 8u;                      // the blob's LDS footprint: level 1 as it is, level 2 (if staged) as u32 or packed to u16 entries
     const u32 jlds = L2M == 2 ? jl1_bytes + ((d.jstage_bytes - jl1_bytes) >> 1) : d.jstage_bytes;
     u64* ckey = reinterpret_cast<u64*>(reinterpret_cast<unsigned char*>(jl) + ((jlds + 15u) & ~15u));   // [CT] mixed keys     (shared by the teams)
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
     u32* bcnt = tcnt + team * 4 * NP;                                // this team's [2][np] run lengths
     u32* boff = bcnt + 2 * NP;                                       // [np] run offsets inside the tile
     u32* pbase = boff + NP;                                          // [np] first piece position of the tile's run
-    u64* tile = tiles + team * (K1M_TS + 2);
+    u64* tile = tiles + team * (K1M_TILE + 2);
     u32* mybar = bar + 8 * team;
     const uint4* __restrict__ pe = reinterpret_cast<const uint4*>(ev);
     // The batch is cut into groups of g <= 2048 events (a multiple of 512: up to four events per thread of a team); a tile = one
@@ -266,25 +272,22 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
     // (a record beyond its piece's capacity goes to the window's overflow list: a rolled loop behind the copy, so that the eight
     // unrolled copies carry one compare each and no call-sized code)
     auto ovf_record = [&](const u32 b, const u32 remv, const u32 dur, const u32 err) { const Dev& d = kd(); K1Local L; ovf8_single(d, b, ((u64)b << d.rb) | remv, (u64)dur, err, 0u, L); k1_red_add(red, L); };
-    auto copy_out = [&](const u32 pc) {
-        const u32* bc = bcnt + pc * NP;
-        if (packb) {
-            // all eight tile positions of a thread together: eight ds_read_b64 (one base register, immediate offsets), sixteen ds_read_b32
-            // (piece base and run offset of each record's partition), then the stores — no branch between the LDS reads.  (tq: the thread's
-            // index made opaque per call, or the compiler hoists the eight position constants out of the tile loop and SPILLS them)
-            u32 tq = tt; asm volatile("" : "+v"(tq));
-            const u32 total = boff[NP - 1] + bc[NP - 1];             // records in the tile
+    // all four positions a thread has in one tile's worth of the LDS tile together (from position `base` on): four ds_read_b64 (one base
+    // register, immediate offsets), eight ds_read_b32 (piece base and run offset of each record's partition), then the stores — no branch
+    // between the LDS reads.
+    auto copy_half = [&](const u32 tq, const u32 total, const u32 base) {
+        {
             const u32 pbm = (1u << d.pb) - 1u, strip = ~(pbm << rb); // partition bits of a parked record's high word (bit 31 = error stays)
             constexpr u32 NPOS = K1M_TS / K1M_TT;
             u64 rec[NPOS]; u32 pb_[NPOS], bo_[NPOS];
 #pragma unroll
-            for (u32 k = 0; k < NPOS; k++) rec[k] = tile[tq + k * K1M_TT];
+            for (u32 k = 0; k < NPOS; k++) rec[k] = tile[tq + base + k * K1M_TT];
 #pragma unroll
             for (u32 k = 0; k < NPOS; k++) { const u32 b = ((u32)(rec[k] >> 32) >> rb) & pbm; pb_[k] = pbase[b]; bo_[k] = boff[b]; }
             u32 ovm = 0;
 #pragma unroll
             for (u32 k = 0; k < NPOS; k++) {
-                const u32 i = tq + k * K1M_TT, h = (u32)(rec[k] >> 32), b = (h >> rb) & pbm;
+                const u32 i = tq + base + k * K1M_TT, h = (u32)(rec[k] >> 32), b = (h >> rb) & pbm;
                 const u32 pos = pb_[k] + (i - bo_[k]);
                 const bool valid = i < total;
                 if SG_ABL(d, 0x2u) { if (valid & (pos < sn)) slab_w[(u64)b * nwpun + pos] = (rec[k] & 0xFFFFFFFFull) | ((u64)(h & strip) << 32); }
@@ -295,11 +298,23 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
             if (__builtin_amdgcn_ballot_w64(ovm != 0)) {
 #pragma unroll 1
                 for (u32 k = 0; k < NPOS; k++) if ((ovm >> k) & 1u) {
-                    const u64 r = tile[tq + k * K1M_TT];
+                    const u64 r = tile[tq + base + k * K1M_TT];
                     const u32 h = (u32)(r >> 32);
                     ovf_record((h >> rb) & pbm, h & rbmask, (u32)r, h >> 31);
                 }
             }
+        }
+    };
+    auto copy_out = [&](const u32 pc) {
+        const u32* bc = bcnt + pc * NP;
+        if (packb) {
+            // (tq: the thread's index made opaque per call, or the compiler hoists the position constants out of the tile loop and SPILLS them)
+            u32 tq = tt; asm volatile("" : "+v"(tq));
+            const u32 total = boff[NP - 1] + bc[NP - 1];             // records in the tile
+            copy_half(tq, total, 0u);
+            // PAIR: the second tile's worth of positions — a partition's run is adjacent positions of this ONE pass over the pair's records,
+            // twice as long as a single tile's.  (A team's odd last tile, or a batch of one tile per team, left alone: nothing beyond K1M_TS.)
+            if constexpr (PAIR) { if ((u32)__builtin_amdgcn_readfirstlane((int)total) > K1M_TS) copy_half(tq, total, K1M_TS); }
         } else {
             const u32 bpw = NP / K1M_TW;                             // partitions whose runs a wave writes out (np >= 64; NT = 1024 only: the host does not pick 768 threads here): four per step, 16 lanes each
 #pragma unroll 1
@@ -342,22 +357,17 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
     // closer to the top of the tile)
     u32* nxt2 = bar + 8 * team + 4;
     const u32 ntile32 = (u32)ntile;
-    for (u32 j = unit; j < ntile32; cur ^= 1u) {
-        u32* bc = bcnt + cur * NP;
-        u32 lo[K1M_NR], hi[K1M_NR], pr[K1M_NR];
-        // the thread's indices, opaque per tile: whatever is derived from them (tile / counter / event addresses) is then computed where it is
-        // used — hoisted out of this loop as loop invariants they were SPILLED (45 dwords) and every reload's vmcnt(0) also waited for the
-        // event loads in flight
-        u32 ttl = tt, lanel = lane; asm volatile("" : "+v"(ttl), "+v"(lanel));
-        const u64 tk0 = stamp ? wall_clock64() : 0ull;
-        {   // P1: one group of up to four events per thread.
-            // The previous tile's records leave FIRST, then the eight loads and the ticket go out and are waited for with vmcnt(0): a
+    auto next_tile = [&](const u32 j, const u32 sel) { return dyn ? (u32)__builtin_amdgcn_readfirstlane((int)lds_fresh_u32(nxt2 + sel)) : j + units; };
+    // ---- the phases of a tile (the two loops below string them together) --------------------------------------------------------------
+    // P1 of tile j: one group of up to four events per thread, ranked in the run counters bc; the ticket it draws goes to word sel.
+    auto p1 = [&](const u32 j, const u32 sel, u32* bc, const u32 ttl, const u32 lanel, u32 (&lo)[K1M_NR], u32 (&hi)[K1M_NR], u32 (&pr)[K1M_NR]) {
+        {
+            // The records parked in LDS leave FIRST (the caller's copy_out), then the eight loads and the ticket go out and are waited for with vmcnt(0): a
             // vmcnt(N) that lets the copy's stores fly behind the loads would have to assume that loads and stores retire in order with
             // each other and that a store whose lanes are all out of range still counts — measured: every tile but a workgroup's first read
             // its events before they had landed.  The latency this team no longer hides is the other team's issue time.  (Keeping a set of
             // loads in flight ACROSS the tile loop's back edge was tried in round 4: the compiler spills the in-flight registers there —
             // tools/check_asm_loads.py.)
-            if (havep) { const u64 tq = stamp ? wall_clock64() : 0ull; copy_out(pcur); if (stamp) tk_p4 += wall_clock64() - tq; }
             u32 f0, c0;
             gbounds(j, f0, c0);
             v4u_t eaa0, eba0, eaa1, eba1, eaa2, eba2, eaa3, eba3;
@@ -375,7 +385,7 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
             const u64 tl0 = stamp ? wall_clock64() : 0ull;
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(eaa0), "+v"(eba0), "+v"(eaa1), "+v"(eba1), "+v"(eaa2), "+v"(eba2), "+v"(eaa3), "+v"(eba3), "+v"(tkv) : : "memory");
             if (stamp) tk_ld += wall_clock64() - tl0;
-            if (drawer) { asm volatile("" : "+v"(tkv)); nxt2[cur] = tkv - d.k1a_ticket_base + units; }
+            if (drawer) { asm volatile("" : "+v"(tkv)); nxt2[sel] = tkv - d.k1a_ticket_base + units; }
             {
                 u32 Lm[2], Rm[2], du[2], fl[2];
                 front2(ttl, 0u, c0, eaa0, eba0, eaa1, eba1, Lm, Rm, du, fl);
@@ -388,17 +398,33 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
                 back2(Lm, Rm, du, fl, bc, lo + 2, hi + 2, pr + 2);
             }
         }
-        const u64 tk1 = stamp ? wall_clock64() : 0ull;
-        team_barrier();
-        const u64 tk2 = stamp ? wall_clock64() : 0ull;
-        tk_p1 += tk1 - tk0; tk_wait += tk2 - tk1;
-        {   // P2: exclusive scan of the run lengths by EVERY wave of the team (eight identical scans cost less than a barrier behind one).
-            // Lane l owns the np / 64 consecutive partitions from l * np / 64; the wave that owns a partition (wave = partition / (np / 8)) also
-            // takes the run's piece positions (a returning add on the piece counter the two teams share) and re-arms the other set of run counters.
+    };
+    // P2: exclusive scan of the run lengths bc by EVERY wave of the team (eight identical scans cost less than a barrier behind one).
+    // Lane l owns the np / 64 consecutive partitions from l * np / 64; the wave that owns a partition (wave = partition / (np / 8)) also
+    // takes the run's piece positions (a returning add on the piece counter the two teams share) and re-arms the other set of run counters.
+    // (PAIR, first: the lengths of a pair's first tile alone — only their offsets, into the OTHER set of run counters, which a pair does
+    // not count in (bprev: its offa); returns the tile's records.  The piece positions are taken once per pair, by the scan of the
+    // combined lengths, and the pair re-arms the other set itself, behind the last read of those offsets.)
+    auto scan = [&](const u32* bc, u32* bprev, const u32 lanel, auto first) -> u32 {
+        {
+            constexpr bool FIRST = decltype(first)::value;
             constexpr u32 pl = NP >> 6; const u32 b0 = lanel * pl;
-            const bool own = (lanel % K1M_TW) == wv;                 // (any disjoint cover of the 64 lanes' partition blocks by the team's waves)
-            u32* bprev = bcnt + (cur ^ 1u) * NP;                     // tile k - 1's set: read for the last time in its copy-out, every wave of the team is past that
-            if constexpr ((pl & 3u) == 0 && pl <= 16) {
+            const bool own = !FIRST && (lanel % K1M_TW) == wv;       // (any disjoint cover of the 64 lanes' partition blocks by the team's waves)
+            if constexpr (FIRST) {
+                constexpr u32 nq = pl >> 2;
+                uint4 cq[4];
+                u32 s = 0;
+#pragma unroll
+                for (u32 k = 0; k < 4; k++) { cq[k] = k < nq ? reinterpret_cast<const uint4*>(bc + b0)[k] : make_uint4(0u, 0u, 0u, 0u); s += cq[k].x + cq[k].y + cq[k].z + cq[k].w; }
+                const u32 incl = wave_incl_scan_u32(s, lanel);
+                u32 run = incl - s;
+#pragma unroll
+                for (u32 k = 0; k < 4; k++) if (k < nq) {
+                    uint4 o; o.x = run; run += cq[k].x; o.y = run; run += cq[k].y; o.z = run; run += cq[k].z; o.w = run; run += cq[k].w;
+                    reinterpret_cast<uint4*>(bprev + b0)[k] = o;
+                }
+                return (u32)__builtin_amdgcn_readlane((int)incl, 63);
+            } else if constexpr ((pl & 3u) == 0 && pl <= 16) {
                 constexpr u32 nq = pl >> 2;                          // 1, 2 or 4 quads per lane (np = 256, 512, 1024)
                 uint4 cq[4];
                 u32 s = 0;
@@ -425,7 +451,7 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
 #pragma unroll
                     for (u32 k = 0; k < 4; k++) if (k < nq) {
                         reinterpret_cast<uint4*>(pbase + b0)[k] = pbv[k];
-                        reinterpret_cast<uint4*>(bprev + b0)[k] = make_uint4(0u, 0u, 0u, 0u);
+                        if constexpr (!PAIR) reinterpret_cast<uint4*>(bprev + b0)[k] = make_uint4(0u, 0u, 0u, 0u);
                     }
                 }
             } else {
@@ -439,23 +465,26 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
                 }
             }
         }
-        const u64 tk3 = stamp ? wall_clock64() : 0ull;
-        // P3: every thread drops its records at offset + rank (PACKB: with the partition number in the free bits of the high word): the eight
-        // offset reads together, then eight unconditional stores — a slot without a travelling record writes to the trash word behind the tile
+        return 0u;
+    };
+    // P3: every thread drops its records at offset + rank (PACKB: with the partition number in the free bits of the high word): the four
+    // offset reads (offs: boff, or a pair's first tile's offsets) together, then four unconditional stores — a slot without a travelling
+    // record writes to the trash word behind the tile
+    auto place = [&](const u32* offs, const u32 (&lo)[K1M_NR], const u32 (&hi)[K1M_NR], const u32 (&pr)[K1M_NR]) {
         {
             u32 of_[K1M_NR];
 #pragma unroll
-            for (int i = 0; i < (int)K1M_NR; i++) of_[i] = boff[pr[i] < K1M_RARE ? (pr[i] & ((1u << K1T_RANK_SHIFT) - 1u)) : 0u];
+            for (int i = 0; i < (int)K1M_NR; i++) of_[i] = offs[pr[i] < K1M_RARE ? (pr[i] & ((1u << K1T_RANK_SHIFT) - 1u)) : 0u];
 #pragma unroll
             for (int i = 0; i < (int)K1M_NR; i++) {
                 const u32 pt_ = pr[i] & ((1u << K1T_RANK_SHIFT) - 1u);
-                const u32 at = pr[i] < K1M_RARE ? of_[i] + (pr[i] >> K1T_RANK_SHIFT) : K1M_TS;
+                const u32 at = pr[i] < K1M_RARE ? of_[i] + (pr[i] >> K1T_RANK_SHIFT) : K1M_TILE;
                 tile[at] = (u64)lo[i] | ((u64)(hi[i] | (packb ? pt_ << rb : 0u)) << 32);
             }
         }
-        const u64 tk4 = stamp ? wall_clock64() : 0ull;
-        team_barrier();
-        const u64 tk5 = stamp ? wall_clock64() : 0ull;
+    };
+    // behind a tile's records: its rare events, then the lanes' statistics
+    auto tile_tail = [&](const u32 j, const u32 ttl, const u32 lanel, const u32 (&pr)[K1M_NR]) {
         {   // the tile's rare events: the general path, one event at a time (nothing of P1 is live here)
             u32 rmask = 0;
 #pragma unroll
@@ -478,11 +507,123 @@ __global__ __launch_bounds__(NT) void k1a_team_partition(Dev d, const sg_event* 
             }
             st_acc = st_dsrc = st_maxlabel = st_misr = 0; st_tmin = ~0ull; st_tmax = 0;
         }
+    };
+    if constexpr (!PAIR) {
+    for (u32 j = unit; j < ntile32; cur ^= 1u) {
+        u32* bc = bcnt + cur * NP;
+        u32 lo[K1M_NR], hi[K1M_NR], pr[K1M_NR];
+        // the thread's indices, opaque per tile: whatever is derived from them (tile / counter / event addresses) is then computed where it is
+        // used — hoisted out of this loop as loop invariants they were SPILLED (45 dwords) and every reload's vmcnt(0) also waited for the
+        // event loads in flight
+        u32 ttl = tt, lanel = lane; asm volatile("" : "+v"(ttl), "+v"(lanel));
+        const u64 tk0 = stamp ? wall_clock64() : 0ull;
+        if (havep) { const u64 tq = stamp ? wall_clock64() : 0ull; copy_out(pcur); if (stamp) tk_p4 += wall_clock64() - tq; }
+        p1(j, cur, bc, ttl, lanel, lo, hi, pr);
+        const u64 tk1 = stamp ? wall_clock64() : 0ull;
+        team_barrier();
+        const u64 tk2 = stamp ? wall_clock64() : 0ull;
+        tk_p1 += tk1 - tk0; tk_wait += tk2 - tk1;
+        scan(bc, bcnt + (cur ^ 1u) * NP, lanel, std::false_type{});  // (the other set is tile k - 1's: read for the last time in its copy-out, every wave of the team is past that)
+        const u64 tk3 = stamp ? wall_clock64() : 0ull;
+        place(boff, lo, hi, pr);
+        const u64 tk4 = stamp ? wall_clock64() : 0ull;
+        team_barrier();
+        const u64 tk5 = stamp ? wall_clock64() : 0ull;
+        tile_tail(j, ttl, lanel, pr);
         havep = true; pcur = cur;
         if (stamp) { tk_scan += tk3 - tk2; tk_p3 += tk4 - tk3; tk_b3 += tk5 - tk4; }
-        j = dyn ? (u32)__builtin_amdgcn_readfirstlane((int)lds_fresh_u32(nxt2 + cur)) : j + units;   // (written before this tile's first barrier, read behind its second)
+        j = next_tile(j, cur);                                       // (written before this tile's first barrier, read behind its second)
     }
-    if (havep) copy_out(pcur);                                       // the last tile's runs
+    } else {
+    // PAIR: a team sorts the two tiles it draws one behind the other into ONE LDS tile and copies them out together.
+    //   tile A: P1 as ever (ranks from the run counters bc), team barrier, the scan of A's lengths (offsets only, to offa: the other set of
+    //           run counters, which no tile counts in while a pair counts in bc.  It still holds the pair before's combined lengths — that
+    //           pair's copy-out, at the top of this one, reads its total there — and every wave's scan overwrites all of it behind the
+    //           barrier.  2 KiB a C3 engine's LDS does not have to spare), A's records to
+    //           their compact positions in the lower half, team barrier (B's ranks change the lengths every wave scans for itself); A's
+    //           rare events and statistics.  No copy-out, no piece positions, bc stays.
+    //   tile B: P1 on the SAME counters — B's rank in partition p begins at A's run length —, team barrier, the scan of the COMBINED lengths
+    //           (offsets to boff, one returning add of the combined length per partition on the piece counter);
+    //           every thread reads four of A's records and their new places boff[p] + (i - offa[p]), team barrier (the move goes to
+    //           higher addresses, over records another thread has yet to read), A's records and B's (from registers, boff[p] + rank)
+    //           are written and offa is zeroed — it is the NEXT pair's bc, as this pair's bc is the next one's offa —, team barrier.
+    //           The copy-out of all 4 096 positions sits where a single tile's does: at the top of the team's next tile, ahead of its
+    //           loads (p1's comment says why not behind them).
+    // Five team barriers per two tiles, one more than without pairs.  A pair never outlives its launch: when A's ticket names no tile (the team's
+    // odd last tile, a batch of one tile per team) there is no B — the second scan runs over A's lengths alone, its offsets are A's,
+    // nothing moves, and the tile leaves alone as it would without pairs (it is the team's last: nothing is left to re-arm for).
+    // Tickets: every TILE draws one (the host's accounting is per tile), into the two words in turn (tsel flips per tile, not per
+    // pair).  A's word is written ahead of the pair's first barrier and read behind it; the drawer writes that word again in the NEXT
+    // pair's A, i.e. behind this pair's later barriers, which no wave of the team passes before it has read the word (the read
+    // stands ahead of them in program order and its value is consumed, by readfirstlane, on the spot).  B's word is written ahead of
+    // the barrier behind B's P1 and read behind the pair's last barrier; it is written again in the next pair's B, behind the next
+    // pair's first barrier, which every wave reaches only with that read behind it.  In between the drawer writes only the OTHER
+    // word.  So a late wave cannot see a later pair's ticket in either word.  (Without a B the failing ticket is A's; every later
+    // draw would fail as well — the counter only grows —, and the team leaves having drawn its one failing ticket, as the host counts.)
+    u32 tsel = 0;
+    for (u32 j = unit; j < ntile32; cur ^= 1u) {
+        u32* bc = bcnt + cur * NP;
+        u32* offa = bcnt + (cur ^ 1u) * NP;                          // (the pair before's bc: its combined lengths until this pair's first scan)
+        u32 lo[K1M_NR], hi[K1M_NR], pr[K1M_NR];
+        u32 ttl = tt, lanel = lane; asm volatile("" : "+v"(ttl), "+v"(lanel));   // (opaque per pair: see the loop without pairs)
+        // (SG_K1_PHASE_STAMPS, a pair's phases in the single tile's columns: both P1s | the barriers behind them | both scans | placing and
+        // the move | the other three barriers | the copy-out)
+        const u64 tk0 = stamp ? wall_clock64() : 0ull;
+        if (havep) { copy_out(pcur); if (stamp) tk_p4 += wall_clock64() - tk0; }
+        const u64 tka = stamp ? wall_clock64() : 0ull;
+        p1(j, tsel, bc, ttl, lanel, lo, hi, pr);
+        const u64 tk1 = stamp ? wall_clock64() : 0ull;
+        team_barrier();
+        const u64 tk2 = stamp ? wall_clock64() : 0ull;
+        const u32 tot_a = scan(bc, offa, lanel, std::true_type{});
+        const u64 tk3 = stamp ? wall_clock64() : 0ull;
+        place(offa, lo, hi, pr);
+        const u64 tk4 = stamp ? wall_clock64() : 0ull;
+        team_barrier();                                              // (B's ranks go to the counters every wave has just scanned: none may still be reading A's lengths)
+        if (stamp) { tk_p1 += tk1 - tka; tk_wait += tk2 - tk1; tk_scan += tk3 - tk2; tk_p3 += tk4 - tk3; tk_b3 += wall_clock64() - tk4; }
+        tile_tail(j, ttl, lanel, pr);
+        const u32 jb = next_tile(j, tsel);
+        tsel ^= 1u;
+        const bool hasb = jb < ntile32;                              // (the same in every wave of the team)
+        if (hasb) {
+            asm volatile("" : "+v"(ttl), "+v"(lanel));
+            const u64 tb0 = stamp ? wall_clock64() : 0ull;
+            p1(jb, tsel, bc, ttl, lanel, lo, hi, pr);
+            const u64 tb1 = stamp ? wall_clock64() : 0ull;
+            team_barrier();
+            if (stamp) { tk_p1 += tb1 - tb0; tk_wait += wall_clock64() - tb1; }
+        }
+        const u64 tk5 = stamp ? wall_clock64() : 0ull;
+        scan(bc, nullptr, lanel, std::false_type{});
+        const u64 tk6 = stamp ? wall_clock64() : 0ull;
+        u64 tk_mv = 0;
+        if (hasb) {
+            u64 ra[K1M_NR]; u32 ob_[K1M_NR], oa_[K1M_NR];
+#pragma unroll
+            for (u32 k = 0; k < K1M_NR; k++) ra[k] = tile[ttl + k * K1M_TT];
+#pragma unroll
+            for (u32 k = 0; k < K1M_NR; k++) { const u32 b = ((u32)(ra[k] >> 32) >> rb) & (NP - 1u); ob_[k] = boff[b]; oa_[k] = offa[b]; }   // (a position beyond A's records: any partition, ignored)
+            const u64 tm0 = stamp ? wall_clock64() : 0ull;
+            team_barrier();
+            if (stamp) tk_mv = wall_clock64() - tm0;
+#pragma unroll
+            for (u32 k = 0; k < K1M_NR; k++) { const u32 i = ttl + k * K1M_TT; tile[i < tot_a ? ob_[k] + (i - oa_[k]) : K1M_TILE] = ra[k]; }
+            place(boff, lo, hi, pr);
+            if ((lanel % K1M_TW) == wv) {                            // (the scan's owner lanes: a disjoint cover of the partitions)
+                constexpr u32 pl = NP >> 6;
+#pragma unroll
+                for (u32 k = 0; k < pl / 4; k++) reinterpret_cast<uint4*>(offa + lanel * pl)[k] = make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+        const u64 tk7 = stamp ? wall_clock64() : 0ull;
+        team_barrier();
+        if (stamp) { tk_scan += tk6 - tk5; tk_p3 += tk7 - tk6 - tk_mv; tk_b3 += tk_mv + (wall_clock64() - tk7); }
+        havep = true; pcur = cur;
+        if (hasb) { tile_tail(jb, ttl, lanel, pr); j = next_tile(jb, tsel); tsel ^= 1u; }
+        else j = jb;
+    }
+    }
+    if (havep) copy_out(pcur);                                       // the last tile's (PAIR: pair's) runs
     SG_STAMP(d, 0, 3);
     if (stamp && tt == 0 && blockIdx.x < 2048) { u64* g = d.dbg + ((size_t)2 * 4096 + blockIdx.x * 2 + team) * 8; g[0] = tk_p1; g[1] = tk_wait; g[2] = tk_scan; g[3] = tk_p3; g[4] = tk_b3; g[5] = tk_p4; g[6] = tk_ld; g[7] = tk_fa; }
     lds_barrier();

@@ -50,7 +50,7 @@ struct DeviceFacts {
 struct Overrides {
     typedef std::optional<std::string> Knob;
     Knob ablate, np, ht, ct, nwg, nsub, split, warm, k1a, k1_narrow, k1_legacy, k1b_u, k1b_threads, k1b_pack, k1b_no_order,
-         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold;
+         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold, k1a_pair;
 };
 struct KnobName { const char* name; Overrides::Knob Overrides::*field; };
 // the one list of knob names (alaz_amd/engine.py DEV_KNOBS is checked against it)
@@ -63,7 +63,7 @@ constexpr KnobName kKnobs[] = {
     {"SG_DH_G", &Overrides::dh_g}, {"SG_K3_SLICES", &Overrides::k3_slices}, {"SG_K3_NO_FUSE", &Overrides::k3_no_fuse},
     {"SG_K4_FUSED", &Overrides::k4_fused}, {"SG_K5_GRID", &Overrides::k5_grid}, {"SG_K6_ONE_WG", &Overrides::k6_one_wg},
     {"SG_DENSE_VALU", &Overrides::dense_valu}, {"SG_COPY_STREAMS", &Overrides::copy_streams}, {"SG_STAGE_SLOTS", &Overrides::stage_slots},
-    {"SG_ARENA", &Overrides::arena}, {"SG_NO_FOLD", &Overrides::no_fold},
+    {"SG_ARENA", &Overrides::arena}, {"SG_NO_FOLD", &Overrides::no_fold}, {"SG_K1A_PAIR", &Overrides::k1a_pair},
 };
 #ifdef SG_DEV_KNOBS
 inline Overrides from_env() {
@@ -110,6 +110,10 @@ struct PassA {
     bool l2_u16 = false, k1a_team = false, l2_in_lds = false;
     u32 k1a_nsub = 2, k1a_teams = 2, k1a_nt = 1024, k1a_ct = 2048;
     size_t k1a_lds = 0;
+    // the team kernel's paired form (sg_k1_team.h PAIR): a team copies two tiles out together.  k1a_lds stays the sum of the layout both
+    // forms share; k1a_pair_lds is what the paired form's second tile per team takes on top (0 without): a launch asks for both
+    bool k1a_pair = false;
+    size_t k1a_pair_lds = 0;
 };
 
 // struct_size / ABI / range checks and the config's defaults (0 = max_batch / max_known_nodes / max_batch)
@@ -310,6 +314,8 @@ inline int make_plan(const sg_config& cfg, const DeviceFacts& dev, const Overrid
 // Pass A's geometry for join tables of l1_entries level-1 entries and l2_bytes of level-2 blocks: does level 2 fit LDS beside the
 // edge cache (and, narrow path, the tile)?  Returns false when no legal geometry exists (the engine fails the call with a message
 // instead of launching a kernel that asks for more than a CU's LDS).
+// Does the plan take the team kernel's paired form where it fits?  Set by the same-box A/B of profiles/pair_tiles_ab_c3.txt.
+constexpr bool kK1aPairDefault = true;
 inline bool plan_pass_a(const Plan& p, uint32_t l1_entries, size_t l2_bytes, const Overrides& ov, PassA* out) {
     PassA a;
     const size_t lds_cap = kLdsBytes;
@@ -353,6 +359,25 @@ inline bool plan_pass_a(const Plan& p, uint32_t l1_entries, size_t l2_bytes, con
         if (!ct || l1b > stage_max) return false;
         a.k1a_ct = ct;
         a.k1a_lds = (size_t)ct * 40 + fixed + (a.l2_in_lds ? l2lds : 0);
+        // the paired form: only BESIDE what was chosen above — the same cache, the same level-2 placement —, where a parked record carries
+        // its partition number (2 nb <= 31: the move of a pair's first tile reads it there), for the partition counts it is instantiated
+        // for, and by default only beside a cache of 512 slots or more.  The default never trades the cache for the second tile: a cache
+        // the join tables have pushed below 512 slots leaves no 32 KiB anyway, and the one trade there is to make — 1 024 slots for 512 —
+        // was measured at 1 024 partitions only (profiles/pair_tiles_ab_c3.txt).  SG_K1A_PAIR=1 takes pairs wherever they fit, with that
+        // trade where it makes them fit (no SG_CT beside it); =0 takes them nowhere.
+        {
+            const size_t extra = K1M_LDS_PAIR_EXTRA(p.np, teams, nt);
+            const bool able = a.k1a_team && 2 * p.nb <= 31 && (p.np == 256 || p.np == 512 || p.np == 1024);
+            const bool forced = ov.k1a_pair && ival(ov.k1a_pair) != 0;
+            if (able && forced && !ov.ct && ct > 512 && a.k1a_lds + extra > lds_cap && a.k1a_lds - (size_t)(ct - 512) * 40 + extra <= lds_cap) {
+                a.k1a_lds -= (size_t)(ct - 512) * 40; ct = 512; a.k1a_ct = ct;
+            }
+            const bool fits = able && a.k1a_lds + extra <= lds_cap;
+            // (1 024 partitions by name only: pairs were measured there as records arriving split, and lost)
+            const bool want = ov.k1a_pair ? forced : (kK1aPairDefault && ct >= 512 && p.np <= 512);
+            a.k1a_pair = fits && want;
+            a.k1a_pair_lds = a.k1a_pair ? extra : 0;
+        }
         *out = a;
         return true;
     }
@@ -383,6 +408,7 @@ struct PassAKernel {
     int l2 = 0;                               // level 2 of the join tables: 0 = global memory, 1 = LDS, 2 = LDS as u16 entries (tile, team)
     bool sharded = false, hist = false;       // (hist: k1a_partition only)
     int nsub = 0, pb = 0;                     // tile: sub-tiles (1, 2); team: log2 of the partitions (8, 9, 10)
+    bool pair = false;                        // team: the paired form (kK1aTeamPairKeys)
 };
 struct Kernels {
     PassAKernel k1a;
@@ -400,7 +426,7 @@ inline PassAKernel choose_pass_a(const Plan& p, const PassA& a, const sg_config&
     k.sharded = cfg.world > 1;
     if (!p.narrow) { k.family = K1A_WIDE; k.l2 = a.l2_in_lds ? 1 : 0; k.hist = p.hist != 0; return k; }
     k.l2 = a.l2_in_lds ? (a.l2_u16 ? 2 : 1) : 0;
-    if (a.k1a_team) { k.family = K1A_TEAM; k.pb = p.np == 256 ? 8 : p.np == 512 ? 9 : 10; }
+    if (a.k1a_team) { k.family = K1A_TEAM; k.pb = p.np == 256 ? 8 : p.np == 512 ? 9 : 10; k.pair = a.k1a_pair; }
     else { k.family = K1A_TILE; k.nsub = a.k1a_nsub == 2 ? 2 : 1; }
     return k;
 }
@@ -442,6 +468,7 @@ int find_key(const std::array<Key<N>, M>& dom, const Key<N>& k) { for (size_t i 
 inline constexpr auto kK1aWideKeys = product({0, 1}, {0, 1}, {0, 1});                    // k1a_partition<l2, sharded, hist>
 inline constexpr auto kK1aTileKeys = product({0, 1, 2}, {0, 1}, {1, 2});                 // k1a_tile_partition<l2, sharded, nsub>
 inline constexpr auto kK1aTeamKeys = product({0, 1, 2}, {0, 1}, {8, 9, 10});             // k1a_team_partition<l2, sharded, 2, 1024, pb>
+inline constexpr auto kK1aTeamPairKeys = product({0, 1, 2}, {0, 1}, {8, 9, 10});           // k1a_team_partition<l2, sharded, 2, 1024, pb, 1>: the paired form
 inline constexpr auto kK1bMergeKeys = concat(product({4, 8}, {0}, {0, 1}), product({4}, {1}, {0, 1}));   // k1b_merge[_wide]<u, hist>, share
 inline constexpr auto kK1bStreamKeys = concat(product({4, 8}, {1, 2, 4}, {0, 1}, {0}, {0, 1}),           // k1b_stream_merge[_wide]<u, spt, pack, wm>, share
                                               product({kK1bWarmU}, {1, 2, 4}, {0, 1}, {1, 2}, {0, 1}));

@@ -14,6 +14,8 @@
 // K1 pass A, two teams per workgroup (sg_k1_team.h)
 // LDS besides the cache and the join tables: piece counters + per team 4 counter arrays, statistics + barrier words, tile(s) of 4 records per thread (+ trash words)
 #define K1M_LDS_FIXED(np, teams, nt) ((size_t)(np) * 4 * (2 + 4 * (teams)) + 128 + ((size_t)(nt) * 4 + 4) * 8)
+// ... and what the paired form (PAIR = 1) takes on top: a second tile's worth of records per team
+#define K1M_LDS_PAIR_EXTRA(np, teams, nt) ((size_t)(nt) * 4 * 8)
 
 // K2 (sg_k2.h)
 #define K2_TILE 2048   // table slots per workgroup (256 threads x 8)

@@ -1224,6 +1224,9 @@ int sg_geometry_get(sg_handle h, sg_geometry* out);
 /* The close's launch plan, beside sg_geometry (whose layout is fixed): *out = 1 when a window close that tries the warm path launches no
  * kc_prepare — that kernel's work rides in the warm attempt's launch (unsharded engines that keep warm-window state). */
 int sg_prepare_fold_get(sg_handle h, uint32_t* out);
+/* Pass A's tile pairs, beside sg_geometry likewise: *out = 1 when a team of k1a_team_partition copies two tiles of tile_records records out
+ * together (runs of twice the length per partition).  Follows the join tables like the rest of pass A's geometry. */
+int sg_pass_a_pair_get(sg_handle h, uint32_t* out);
 
 /* Per-kernel timing, measured on the launch stream.  Groups: 1 = K1 pass A (k1a_partition / k1_resolve_aggregate, one record
  * per batch), 7 = K1 pass B (k1b_merge) — both by the dispatch's own begin/end stamps; 2 = K2 csr_build (two records per window:
