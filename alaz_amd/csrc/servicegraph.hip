@@ -346,7 +346,8 @@ struct K4Layer : Family<K4LayerFn, sgplan::kK4LayerKeys> { template <size_t I> s
 constexpr K2RowptrFn kK2Rowptr[2] = {k2_rowptr<K2_RP_ROWS, false>, k2_rowptr<K2_RP_ROWS_DH, true>};    // [over the degree histograms]
 constexpr K4GatherFn kK4Gather[2] = {k4_gather<32>, k4_gather<64>};                                    // [layer > 0]
 constexpr K5ProjFn kK5Proj[2] = {k5_node_proj<false>, k5_node_proj<true>};                             // [MFMA]
-constexpr K5ScoreFn kK5Score[2] = {k5_edge_score<false>, k5_edge_score<true>};                         // [fused reset]
+constexpr K5ScoreFn kK5Score[2][2] = {{k5_edge_score<false>, k5_edge_score<true>}, {k5_edge_score_lanes<false>, k5_edge_score_lanes<true>}};   // [form][fused reset]
+static_assert(sgplan::kK5LanesWgLds == 4 * K5L_WAVE_LDS, "sg_plan.hpp's copy of form 1's LDS per workgroup");
 template <class F, size_t... I>
 const std::array<typename F::Fn, sizeof...(I)>& kernel_table(std::index_sequence<I...>) {
     static const std::array<typename F::Fn, sizeof...(I)> t{{F::template at<I>()...}};
@@ -1363,7 +1364,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     {
         Timed t(e, s, 5);
         if (!(proj_done && d.world == 1)) hipLaunchKernelGGL(e->fn.k5_proj, dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
-        hipLaunchKernelGGL(kK5Score[fr], dim3((int)e->plan.k5_grid), dim3(256), 0, s, d, Wh);   // one round of workgroups (sg_plan.hpp)
+        hipLaunchKernelGGL(kK5Score[e->kn.k5_form][fr], dim3((int)e->plan.k5_grid), dim3(256), 0, s, d, Wh);   // one round of workgroups (sg_plan.hpp)
     }
     if (did_reset) *did_reset = fr;
     HIP_TRY(e, hipGetLastError());
@@ -2416,6 +2417,13 @@ int sg_pass_a_pair_get(sg_handle e, uint32_t* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     *out = e->plan.narrow && e->pa.k1a_team && e->pa.k1a_pair ? 1u : 0u;
+    return SG_OK;
+}
+
+int sg_k5_form_get(sg_handle e, uint32_t* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = (uint32_t)e->kn.k5_form;
     return SG_OK;
 }
 

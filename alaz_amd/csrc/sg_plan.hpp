@@ -50,7 +50,7 @@ struct DeviceFacts {
 struct Overrides {
     typedef std::optional<std::string> Knob;
     Knob ablate, np, ht, ct, nwg, nsub, split, warm, k1a, k1_narrow, k1_legacy, k1b_u, k1b_threads, k1b_pack, k1b_no_order,
-         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold, k1a_pair;
+         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold, k1a_pair, k5_form;
 };
 struct KnobName { const char* name; Overrides::Knob Overrides::*field; };
 // the one list of knob names (alaz_amd/engine.py DEV_KNOBS is checked against it)
@@ -64,6 +64,7 @@ constexpr KnobName kKnobs[] = {
     {"SG_K4_FUSED", &Overrides::k4_fused}, {"SG_K5_GRID", &Overrides::k5_grid}, {"SG_K6_ONE_WG", &Overrides::k6_one_wg},
     {"SG_DENSE_VALU", &Overrides::dense_valu}, {"SG_COPY_STREAMS", &Overrides::copy_streams}, {"SG_STAGE_SLOTS", &Overrides::stage_slots},
     {"SG_ARENA", &Overrides::arena}, {"SG_NO_FOLD", &Overrides::no_fold}, {"SG_K1A_PAIR", &Overrides::k1a_pair},
+    {"SG_K5_FORM", &Overrides::k5_form},
 };
 #ifdef SG_DEV_KNOBS
 inline Overrides from_env() {
@@ -94,6 +95,7 @@ struct Plan {
     u32 k2_sortw = 0, dh_g = 0, dh_ppw = 0, dh_ns = 0;
     bool k4_split = false;                    // K4 in two launches per layer (gather, then the dense tiles)
     u32 k5_grid = 0;
+    u32 k5_form = 0;                          // k5_edge_score: 0 = sixteen lanes per edge, 1 = one lane per edge (k5_edge_score_lanes); k5_grid is the form's own
     bool k3_fuse_allowed = true;              // the one-call pipelines may fold k3_in_reduce into k3_in_part's launch
     bool k6_one_wg = false;                   // the round-3 single-workgroup halo-list builder
     bool use_mfma = true;
@@ -135,6 +137,15 @@ inline int check_config(const sg_config& in, sg_config* out) {
 }
 
 // cfg: as check_config left it
+// k5_edge_score's form (sg_k5.h).  Where nobody asks by name the plan takes form 1 where it was measured to win — unsharded engines of
+// a million edges and more, the C3 shape (same-box A/B: profiles/k5_lanes_ab_c3.txt) — and form 0 everywhere else: C2 and the C5
+// shards are not measured yet.  Form 1's footprint: LDS per workgroup (4 waves x K5L_WAVE_LDS) and the waves per SIMD its registers
+// allow (amdgpu_waves_per_eu).
+constexpr u64 kK5LanesMinEdges = 1ull << 20;
+inline u32 k5_form_default(const sg_config& cfg) { return cfg.world <= 1 && cfg.max_edges >= kK5LanesMinEdges ? 1u : 0u; }
+constexpr size_t kK5LanesWgLds = 4 * 8192;
+constexpr int kK5LanesWaves = 3;
+constexpr int k5_lanes_wgs_per_cu() { return (int)std::min<size_t>(kLdsBytes / kK5LanesWgLds, (size_t)kK5LanesWaves); }
 inline int make_plan(const sg_config& cfg, const DeviceFacts& dev, const Overrides& ov, Plan* out, std::string* why) {
     sg_config chk;
     if (check_config(cfg, &chk) != SG_OK) { if (why) *why = "invalid config"; return SG_EINVAL; }
@@ -300,8 +311,17 @@ inline int make_plan(const sg_config& cfg, const DeviceFacts& dev, const Overrid
     // K5: ONE round of workgroups: the kernel runs 3 waves per SIMD (144 registers, amdgpu_waves_per_eu(3)) = 3 workgroups of 256 threads per CU at a
     // time, and its waves stride over the edges — 2 048 workgroups were 2.67 rounds, the last one two-thirds empty.  Same box, C3, two
     // repetitions: K5 61.1 us at 2 048, 61.7 at 1 024, 58.9 at 1 536, 57.8-57.9 at 768 (profiles/r06_grids_ab_c3.txt)
-    p.k5_grid = (u32)grid_for(cfg.max_edges, 32, 3 * (int)p.cus);
-    if (ov.k5_grid) { const int x = ival(ov.k5_grid); if (x >= 1 && x <= 65535) p.k5_grid = (u32)std::min(grid_for(cfg.max_edges, 32, 65535), x); }
+    p.k5_form = k5_form_default(cfg);
+    if (ov.k5_form) {                                                // (an unknown form is refused, not ignored: an A/B that silently ran one form twice would look like a tie)
+        if (*ov.k5_form != "0" && *ov.k5_form != "1") { if (why) *why = "SG_K5_FORM: 0 (sixteen lanes per edge) or 1 (one lane per edge)"; return SG_EINVAL; }
+        p.k5_form = (u32)ival(ov.k5_form);
+    }
+    if ((u64)p.ncap * 256u > (1ull << 32)) p.k5_form = 0;            // form 1 addresses a P / Q row by a 32-bit byte offset
+    // form 0: 32 edges per workgroup and step, 3 workgroups per CU.  Form 1: 256 edges per workgroup and step; a CU holds
+    // min(LDS / kK5LanesWgLds, kK5LanesWaves) of its workgroups (4 waves each, one per SIMD): one round of those
+    const int k5_per_wg = p.k5_form ? 256 : 32, k5_round = (p.k5_form ? k5_lanes_wgs_per_cu() : 3) * (int)p.cus;
+    p.k5_grid = (u32)grid_for(cfg.max_edges, k5_per_wg, k5_round);
+    if (ov.k5_grid) { const int x = ival(ov.k5_grid); if (x >= 1 && x <= 65535) p.k5_grid = (u32)std::min(grid_for(cfg.max_edges, k5_per_wg, 65535), x); }
     p.k3_fuse_allowed = !ov.k3_no_fuse;                              // (development build: the two-launch form beside the fused one on one box)
     p.k6_one_wg = (bool)ov.k6_one_wg;
     if (ov.copy_streams) p.n_copy = ival(ov.copy_streams) == 2 ? 2 : 1;
@@ -419,6 +439,7 @@ struct Kernels {
     bool k2_dh = false;                       // k2_rowptr over the degree histograms
     bool k4_split = false, k4_mfma = true;    // k4_sage_layer (input width, projection and threads follow the layer at launch)
     bool k5_mfma = true;                      // k5_node_proj (k5_edge_score's fused reset is the caller's argument)
+    int k5_form = 0;                          // k5_edge_score (0) or k5_edge_score_lanes (1)
 };
 inline PassAKernel choose_pass_a(const Plan& p, const PassA& a, const sg_config& cfg) {
     PassAKernel k;
@@ -442,7 +463,7 @@ inline Kernels choose_kernels(const Plan& p, const PassA& a, const sg_config& cf
         else { k.k1b_family = K1B_MERGE; k.k1b_hist = p.hist != 0; if (k.k1b_hist) k.k1b_u = 4; }
     }
     k.k2_dh = p.dh_g != 0;
-    k.k4_split = p.k4_split; k.k4_mfma = p.use_mfma; k.k5_mfma = p.use_mfma;
+    k.k4_split = p.k4_split; k.k4_mfma = p.use_mfma; k.k5_mfma = p.use_mfma; k.k5_form = (int)p.k5_form;
     return k;
 }
 

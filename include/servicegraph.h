@@ -1227,6 +1227,9 @@ int sg_prepare_fold_get(sg_handle h, uint32_t* out);
 /* Pass A's tile pairs, beside sg_geometry likewise: *out = 1 when a team of k1a_team_partition copies two tiles of tile_records records out
  * together (runs of twice the length per partition).  Follows the join tables like the rest of pass A's geometry. */
 int sg_pass_a_pair_get(sg_handle h, uint32_t* out);
+/* The score kernel's form, beside sg_geometry likewise: *out = 0 when k5_edge_score gives sixteen lanes to an edge, 1 when one lane
+ * owns an edge and the P and Q rows pass through LDS (k5_edge_score_lanes).  Both write the same rows, bit for bit. */
+int sg_k5_form_get(sg_handle h, uint32_t* out);
 
 /* Per-kernel timing, measured on the launch stream.  Groups: 1 = K1 pass A (k1a_partition / k1_resolve_aggregate, one record
  * per batch), 7 = K1 pass B (k1b_merge) — both by the dispatch's own begin/end stamps; 2 = K2 csr_build (two records per window:
