@@ -40,6 +40,8 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->set_group_tracks = reinterpret_cast<decltype(o->set_group_tracks)>(dlsym(dl, "sg_set_group_tracks"));   // optional (K19)
     o->window_group_incident_tracks = reinterpret_cast<decltype(o->window_group_incident_tracks)>(dlsym(dl, "sg_window_group_incident_tracks"));
     o->window_group_tracks_ended = reinterpret_cast<decltype(o->window_group_tracks_ended)>(dlsym(dl, "sg_window_group_tracks_ended"));
+    o->set_group_impact = reinterpret_cast<decltype(o->set_group_impact)>(dlsym(dl, "sg_set_group_impact"));   // optional (K22)
+    o->window_group_impact = reinterpret_cast<decltype(o->window_group_impact)>(dlsym(dl, "sg_window_group_impact"));
     o->set_quantiles = reinterpret_cast<decltype(o->set_quantiles)>(dlsym(dl, "sg_set_quantiles"));   // optional (K20)
     o->window_node_quantiles = reinterpret_cast<decltype(o->window_node_quantiles)>(dlsym(dl, "sg_window_node_quantiles"));
     o->window_group_quantiles = reinterpret_cast<decltype(o->window_group_quantiles)>(dlsym(dl, "sg_window_group_quantiles"));
@@ -131,7 +133,72 @@ int GraphDS::SetWorkloadGroups(uint32_t max_groups) {
         auto po = pod_owner_.find(uid_of_[id]);
         if (po != pod_owner_.end()) AssignGroup(id, GroupOfOwner(po->second));
     }
+    if (bind_on_) BindAllServices();
     return SG_OK;
+}
+// ---- the service binding (id_mu_ held) ----
+static std::string ServiceKey(const std::string& ns, const std::string& name) { return ns + "/" + name; }
+void GraphDS::BindService(const std::string& key) {
+    auto sv = svc_uid_.find(key);
+    if (sv == svc_uid_.end()) return;
+    auto sid = ids_.find(sv->second);
+    if (sid == ids_.end() || kind_of_[sid->second] != SG_NODE_SERVICE) return;   // (no ClusterIP here: no node id to assign)
+    uint32_t group = kNoId;
+    bool any = false, one = true;
+    auto ep = ep_pods_.find(key);
+    if (bind_on_ && groups_on_ && ep != ep_pods_.end())
+        for (const std::string& pod : ep->second) {
+            auto p = ids_.find(pod);
+            if (p == ids_.end() || kind_of_[p->second] != SG_NODE_POD || refs_[p->second] == 0) continue;   // a pod the store does not know
+            const uint32_t g = p->second < node_group_.size() ? node_group_[p->second] : kNoId;
+            if (g == kNoId || (any && g != group)) one = false;       // an ungrouped pod among them, or two workloads behind it
+            group = g; any = true;
+        }
+    const uint32_t want = any && one ? group : kNoId;
+    if (want == kNoId && sid->second >= node_group_.size()) return;    // (never assigned: nothing to take back)
+    AssignGroup(sid->second, want);
+}
+void GraphDS::BindServicesOfPod(const std::string& pod_uid) {
+    auto it = pod_eps_.find(pod_uid);
+    if (it == pod_eps_.end()) return;
+    for (const std::string& key : it->second) BindService(key);
+}
+void GraphDS::BindAllServices() {
+    for (const auto& kv : svc_uid_) BindService(kv.first);
+}
+int GraphDS::SetServiceBinding(bool on) {
+    if (!api_.group_assign) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(id_mu_);
+    if (!groups_on_) return SG_ESTATE;
+    bind_on_ = on;
+    BindAllServices();
+    return SG_OK;
+}
+int GraphDS::PersistEndpoints(const datastore::Endpoints& e, const std::string& et) {
+    const bool up = et == datastore::ADD || et == datastore::UPDATE;
+    if (up || et == datastore::DELETE_) {
+        std::lock_guard<std::mutex> g(id_mu_);
+        const std::string key = ServiceKey(e.Namespace, e.Name);
+        auto old = ep_pods_.find(key);
+        if (old != ep_pods_.end()) {
+            for (const std::string& pod : old->second) {
+                auto pe = pod_eps_.find(pod);
+                if (pe == pod_eps_.end()) continue;
+                pe->second.erase(std::remove(pe->second.begin(), pe->second.end(), key), pe->second.end());
+                if (pe->second.empty()) pod_eps_.erase(pe);
+            }
+            ep_pods_.erase(old);
+        }
+        if (up) {
+            std::vector<std::string>& pods = ep_pods_[key];
+            for (const datastore::Address& a : e.Addresses)
+                for (const datastore::AddressIP& ip : a.IPs)      // (TargetRef's kind and UID, aggregator/persist.go:247-267)
+                    if (ip.Type == "Pod" && !ip.ID.empty() && std::find(pods.begin(), pods.end(), ip.ID) == pods.end()) pods.push_back(ip.ID);
+            for (const std::string& pod : pods) pod_eps_[pod].push_back(key);
+        }
+        BindService(key);
+    }
+    return inner_->PersistEndpoints(e, et);
 }
 int GraphDS::PersistReplicaSet(const datastore::ReplicaSet& rs, const std::string& et) {
     if (et == datastore::ADD || et == datastore::UPDATE) {
@@ -143,7 +210,7 @@ int GraphDS::PersistReplicaSet(const datastore::ReplicaSet& rs, const std::strin
                 for (const auto& po : pod_owner_) {
                     if (po.second != rs.UID) continue;
                     auto it = ids_.find(po.first);
-                    if (it != ids_.end()) AssignGroup(it->second, GroupOfOwner(rs.UID));
+                    if (it != ids_.end()) { AssignGroup(it->second, GroupOfOwner(rs.UID)); BindServicesOfPod(po.first); }
                 }
         }
     } else if (et == datastore::DELETE_) { std::lock_guard<std::mutex> g(id_mu_); rs_owner_.erase(rs.UID); }   // (its pods keep their group)
@@ -386,6 +453,25 @@ long GraphDS::WorkloadTracksEnded(std::vector<sg_track_entry>* out) {
     return counted_rows(h_, api_.window_group_tracks_ended, out);
 }
 
+// ---- the workload impact (K22) ----
+int GraphDS::SetWorkloadImpact(uint32_t max_incidents, uint32_t max_hops) {
+    if (!api_.set_group_impact) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_group_impact(h_, max_incidents, max_hops);
+}
+long GraphDS::WorkloadImpact(std::vector<sg_incident_out>* incidents, std::vector<uint64_t>* impact) {
+    if (!incidents || !impact || !api_.window_group_incidents || !api_.window_group_impact) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    const long rc = counted_rows(h_, api_.window_group_incidents, incidents);
+    if (rc < 0) return rc;
+    size_t n = 0;
+    int r = api_.window_group_impact(h_, nullptr, 0, &n);
+    if (r != SG_OK) return r;
+    impact->assign(n * SG_IMPACT_WORDS, 0);
+    if (n && (r = api_.window_group_impact(h_, impact->data(), n, &n)) != SG_OK) return r;
+    return (long)n;
+}
+
 // ---- the latency percentiles (K20) ----
 int GraphDS::SetQuantiles(uint32_t spaces, const uint32_t* permille, size_t n_q) {
     if (!api_.set_quantiles) return SG_EINVAL;
@@ -444,8 +530,9 @@ int GraphDS::PersistPod(const datastore::Pod& pod, const std::string& et) {
                     BindIP(pod_ip_id_, ip, id);
                     pod_owner_[pod.UID] = pod.OwnerID;
                     if (groups_on_) AssignGroup(id, GroupOfOwner(pod.OwnerID));
+                    BindServicesOfPod(pod.UID);
                 }
-            } else { api_.delete_pod(h_, ip); UnbindIP(pod_ip_id_, ip); }     // (a DELETE never creates an id; its group goes with the id, in FlushWindow)
+            } else { api_.delete_pod(h_, ip); UnbindIP(pod_ip_id_, ip); BindServicesOfPod(pod.UID); }     // (a DELETE never creates an id; its group goes with the id, in FlushWindow)
         }
         if (erc == SG_OK && (up || et == datastore::DELETE_)) { std::lock_guard<std::mutex> g(pk_mu_); packer_.SetPodIP(ip, up); }
         if (erc != SG_OK) engine_errors_++;
@@ -466,8 +553,22 @@ int GraphDS::PersistService(const datastore::Service& svc, const std::string& et
             if (up) {
                 const uint32_t id = Intern(svc.UID, SG_NODE_SERVICE);
                 erc = id == kNoId ? SG_ENOSPC : api_.upsert_service(h_, ip, id);
-                if (erc == SG_OK) BindIP(svc_ip_id_, ip, id);
-            } else { api_.delete_service(h_, ip); UnbindIP(svc_ip_id_, ip); }
+                if (erc == SG_OK) {
+                    BindIP(svc_ip_id_, ip, id);
+                    if (!svc.Name.empty()) { const std::string key = svc.Namespace + "/" + svc.Name; svc_uid_[key] = svc.UID; BindService(key); }
+                }
+            } else {
+                if (!svc.Name.empty()) {                             // forget the entry: a bound Service leaves its group first
+                    const std::string key = svc.Namespace + "/" + svc.Name;
+                    auto sv = svc_uid_.find(key);
+                    if (sv != svc_uid_.end()) {
+                        auto sid = ids_.find(sv->second);
+                        if (sid != ids_.end() && sid->second < node_group_.size()) AssignGroup(sid->second, kNoId);
+                        svc_uid_.erase(sv);
+                    }
+                }
+                api_.delete_service(h_, ip); UnbindIP(svc_ip_id_, ip);
+            }
         }
         if (erc == SG_OK && (up || et == datastore::DELETE_)) { std::lock_guard<std::mutex> g(pk_mu_); packer_.SetServiceIP(ip, up); }
         if (erc != SG_OK) engine_errors_++;
@@ -651,6 +752,7 @@ long GraphDS::FlushWindow(int64_t window_end_ms) {
             auto it = ids_.find(uid_of_[id]);
             if (it != ids_.end() && it->second == id) ids_.erase(it);
             if (kind_of_[id] == SG_NODE_POD) { pod_owner_.erase(uid_of_[id]); if (groups_on_) AssignGroup(id, kNoId); }
+            else if (groups_on_ && id < node_group_.size()) AssignGroup(id, kNoId);   // (a Service that was bound; never assigned: no call)
             uid_of_[id].clear(); kind_of_[id] = 0; free_ids_.push_back(id); live_ids_--;
         }
     }

@@ -73,6 +73,9 @@ struct SgApi {
     int (*set_group_tracks)(sg_handle, const sg_track_params*) = nullptr;
     int (*window_group_incident_tracks)(sg_handle, sg_incident_track*, size_t, size_t*) = nullptr;
     int (*window_group_tracks_ended)(sg_handle, sg_track_entry*, size_t, size_t*) = nullptr;
+    // optional (K22; absent in an older library): SetWorkloadImpact and WorkloadImpact each need the entry they forward to
+    int (*set_group_impact)(sg_handle, uint32_t, uint32_t) = nullptr;
+    int (*window_group_impact)(sg_handle, uint64_t*, size_t, size_t*) = nullptr;
     // optional (K20; absent in an older library): SetQuantiles and the three latency reads each need the entry they forward to
     int (*set_quantiles)(sg_handle, uint32_t, const uint32_t*, size_t) = nullptr;
     int (*window_node_quantiles)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
@@ -143,7 +146,8 @@ public:
     // forwarded; with the workload groups on, a ReplicaSet that names a Deployment moves its pods into the Deployment's group
     int PersistReplicaSet(const datastore::ReplicaSet& rs, const std::string& et) override;
     int PersistDeployment(const datastore::Deployment& d, const std::string& et) override { return inner_->PersistDeployment(d, et); }
-    int PersistEndpoints(const datastore::Endpoints& e, const std::string& et) override { return inner_->PersistEndpoints(e, et); }
+    // forwarded unchanged; the pods behind (namespace, name) are remembered for SetServiceBinding
+    int PersistEndpoints(const datastore::Endpoints& e, const std::string& et) override;
     int PersistContainer(const datastore::Container& c, const std::string& et) override { return inner_->PersistContainer(c, et); }
     int PersistDaemonSet(const datastore::DaemonSet& ds, const std::string& et) override { return inner_->PersistDaemonSet(ds, et); }
     int PersistStatefulSet(const datastore::StatefulSet& ss, const std::string& et) override { return inner_->PersistStatefulSet(ss, et); }
@@ -182,6 +186,16 @@ public:
     // leaves its group when its node id is released, after the window that may still name it has been flushed; a ReplicaSet that
     // arrives after its pods re-assigns them.  SG_EINVAL without sg_set_groups / sg_group_assign in the engine's table.
     int SetWorkloadGroups(uint32_t max_groups);
+    // Service binding (off by default; needs SetWorkloadGroups, else SG_ESTATE; SG_EINVAL without sg_group_assign): a Service's node
+    // id joins the workload behind it, so that pod -> ClusterIP traffic contracts to workload -> workload and call chains run
+    // through Services.  (namespace, name) -> Service comes from PersistService, (namespace, name) -> pod UIDs from PersistEndpoints
+    // (the addresses of Type "Pod" with a non-empty ID); DELETE forgets the entry.  A Service is in group g iff its Endpoints name
+    // at least one pod that has an IP here, and every such pod is in the same group g (two ReplicaSets of one Deployment are one
+    // g); otherwise — no Endpoints, no known pod, an ungrouped pod among them, two workloads behind it — it is in none.  The rule is
+    // re-evaluated whenever an input changes (an Endpoints or Service event, a pod added, removed or re-owned, a ReplicaSet's owner
+    // learned, SetWorkloadGroups, this switch) and sent as one sg_group_assign only when the value changes; off un-assigns every
+    // bound Service.  A window already in flight keeps the map it was closed under.
+    int SetServiceBinding(bool on);
     // the group edges of the last flushed window, group ids resolved back to owner UIDs; < 0 on an engine error
     long WorkloadEdges(std::vector<WorkloadEdge>* out);
     // The workload baselines (K15), behind SetWorkloadGroups: each group edge against its own past, keyed by workload, so a rollout
@@ -227,6 +241,12 @@ public:
     int SetWorkloadTracks(const sg_track_params* p);
     long WorkloadIncidentTracks(std::vector<sg_incident_track>* out);
     long WorkloadTracksEnded(std::vector<sg_track_entry>* out);
+    // The workload impact (K22; needs SetWorkloadIncidents): who depends on each workload incident.  SetWorkloadImpact forwards
+    // sg_set_group_impact (0, 0: off; the engine's return code; SG_EINVAL without the entry).  WorkloadImpact: the last flushed
+    // window's incident rows as WorkloadIncidents gives them and, in `impact`, SG_IMPACT_WORDS words per covered incident — row i
+    // belongs to incident i; the row in FAR's low half indexes WorkloadNodes.  It returns the covered count, or a negative SG_* code.
+    int SetWorkloadImpact(uint32_t max_incidents, uint32_t max_hops);
+    long WorkloadImpact(std::vector<sg_incident_out>* incidents, std::vector<uint64_t>* impact);
     // The latency percentiles (K20; the engine was created with SG_CFG_EDGE_HISTOGRAM): SetQuantiles forwards sg_set_quantiles
     // (spaces: SG_Q_* bits, 0 = off; n_q 0: {500, 990}; the engine's return code; SG_EINVAL without the entry).  NodeLatency,
     // WorkloadEdgeLatency and WorkloadLatency read the last flushed window's quantiles in microseconds — per node row [2][n_q]
@@ -269,6 +289,10 @@ private:
     // (id_mu_ held) the group of a pod owned by `owner` (kNoId: none); node id -> group in the engine, if it changed
     uint32_t GroupOfOwner(const std::string& owner);
     void AssignGroup(uint32_t id, uint32_t group);
+    // (id_mu_ held) the binding rule for the Service at key "namespace/name"; for every Service whose Endpoints name the pod; for all
+    void BindService(const std::string& key);
+    void BindServicesOfPod(const std::string& pod_uid);
+    void BindAllServices();
     // (id_mu_ held) a group edge in the reference's vocabulary: group ids back to owner UIDs, node refs as the rows' are
     void NameWorkloadEdge(const sg_group_edge& r, WorkloadEdge* o) const;
     void NameRef(uint32_t ref, std::string* type, std::string* uid) const;   // (id_mu_ held) one group ref
@@ -307,6 +331,11 @@ private:
     std::unordered_map<std::string, std::string> pod_owner_, rs_owner_;   // pod UID -> OwnerID; ReplicaSet UID -> its Deployment's UID
     std::unordered_map<std::string, uint32_t> gids_; std::vector<std::string> guid_of_;   // owner UID <-> group id, arrival order
     std::vector<uint32_t> node_group_;                 // node id -> the group the engine holds for it
+    // the service binding (under id_mu_): what the Services and Endpoints are is kept whether or not the binding is on
+    bool bind_on_ = false;
+    std::unordered_map<std::string, std::string> svc_uid_;                  // "namespace/name" -> Service UID
+    std::unordered_map<std::string, std::vector<std::string>> ep_pods_;     // "namespace/name" -> the pod UIDs behind it
+    std::unordered_map<std::string, std::vector<std::string>> pod_eps_;     // pod UID -> the keys whose Endpoints name it
     std::vector<std::string> last_labels_; std::vector<uint32_t> last_obips_;   // of the last flushed window (flush_mu_)
     std::mutex pk_mu_;                                 // packer_ (labels, prepared statements, HPACK state), dto_labels_
     L7Packer packer_;

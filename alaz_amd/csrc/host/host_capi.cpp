@@ -35,6 +35,7 @@ struct MockEngine {
     size_t k20_nq = 2;
     std::vector<std::array<uint64_t, 4>> k19_ops;      // {1, quiet_windows, max_tracks, reserved} per sg_set_group_tracks (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incident_tracks, {3, cap, 0, 0} per sg_window_group_tracks_ended
     std::vector<std::array<uint64_t, 4>> k18_ops;      // {1, by, the bits of min_value, reserved} per sg_set_group_incidents (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incidents, {3, n_index, cap, 0} per sg_window_group_node_incident
+    std::vector<std::array<uint64_t, 4>> k22_ops;      // {1, max_incidents, max_hops, 0} per sg_set_group_impact, {2, cap, 0, 0} per sg_window_group_impact
     std::mutex mu;                                     // like the real engine, the stand-in serialises the calls on one handle
 };
 #define M_LOCK(h) std::lock_guard<std::mutex> _g(reinterpret_cast<MockEngine*>(h)->mu)
@@ -169,6 +170,19 @@ int m_window_group_incidents(sg_handle h, sg_incident_out* out, size_t cap, size
     e[1].count = 4; e[1].first_node = 1; e[1].nodes = 1; e[1].edges = 1; e[1].worst_row = 2; e[1].top_node = 1; e[1].culprit_node = SG_NO_INCIDENT;
     e[1].value_max = 0.5f;
     for (size_t i = 0; out && i < std::min<size_t>(2, cap); i++) out[i] = e[i];
+    return SG_OK;
+}
+// K22's stand-ins: the switch recorded; the impact rows of K18's two incidents (incident 0: one exposed row, row 1, one hop away,
+// which is an entry; incident 1: nothing exposed)
+int m_set_group_impact(sg_handle h, uint32_t max_incidents, uint32_t max_hops) {
+    M_LOCK(h); reinterpret_cast<MockEngine*>(h)->k22_ops.push_back({1u, max_incidents, max_hops, 0u}); return SG_OK;
+}
+int m_window_group_impact(sg_handle h, uint64_t* out, size_t cap, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k22_ops.push_back({2u, (uint64_t)cap, 0u, 0u});
+    if (n) *n = 2;
+    const uint64_t e[2][SG_IMPACT_WORDS] = {{1, 1, 1ull << 32 | 1, 1, 40, 3, 7, 2}, {0, 0, 0xFFFFFFFFull, 1, 4, 0, 0, 0}};
+    for (size_t i = 0; out && i < std::min<size_t>(2, cap); i++) std::memcpy(out + i * SG_IMPACT_WORDS, e[i], sizeof e[i]);
     return SG_OK;
 }
 // K19's stand-ins: the switch recorded; the tracks of K18's two incidents (track 4 continued into its third window, track 7 opened
@@ -353,6 +367,7 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.window_group_nodes_top_tail = m_window_group_nodes_top_tail;
         c->api.set_group_incidents = m_set_group_incidents; c->api.window_group_incidents = m_window_group_incidents;
         c->api.window_group_node_incident = m_window_group_node_incident;
+        c->api.set_group_impact = m_set_group_impact; c->api.window_group_impact = m_window_group_impact;
     }
     if (c->api.create(cfg, &c->h) != SG_OK) return nullptr;        // no usable GPU => no GraphDS: there is no CPU fallback
     c->ds = std::make_unique<GraphDS>(&c->inner, c->api, c->h, &c->sink, cfg ? (size_t)cfg->max_edges : 1024, batch ? batch : 4096,
@@ -372,6 +387,20 @@ int sgh_graphds_persist_replicaset(void* g, const char* et, const char* uid, con
     return static_cast<HostCtx*>(g)->ds->PersistReplicaSet(rs, et);
 }
 int sgh_graphds_set_workload_groups(void* g, uint32_t max_groups) { return static_cast<HostCtx*>(g)->ds->SetWorkloadGroups(max_groups); }
+// the service binding: a Service with its name and namespace, the Endpoints of (namespace, name) as n (type, id) address pairs, the switch
+int sgh_graphds_persist_service_named(void* g, const char* et, const char* uid, const char* ip, const char* name, const char* ns) {
+    datastore::Service s; s.UID = uid; s.Name = name ? name : ""; s.Namespace = ns ? ns : "";
+    if (ip && *ip) s.ClusterIPs.push_back(ip);
+    return static_cast<HostCtx*>(g)->ds->PersistService(s, et);
+}
+int sgh_graphds_persist_endpoints(void* g, const char* et, const char* name, const char* ns, const char* const* types, const char* const* ids, size_t n) {
+    datastore::Endpoints e; e.Name = name ? name : ""; e.Namespace = ns ? ns : "";
+    datastore::Address a;
+    for (size_t i = 0; i < n; i++) { datastore::AddressIP ip; ip.Type = types[i] ? types[i] : ""; ip.ID = ids[i] ? ids[i] : ""; a.IPs.push_back(ip); }
+    if (n) e.Addresses.push_back(a);
+    return static_cast<HostCtx*>(g)->ds->PersistEndpoints(e, et);
+}
+int sgh_graphds_set_service_binding(void* g, int on) { return static_cast<HostCtx*>(g)->ds->SetServiceBinding(on != 0); }
 struct sgh_workload_edge {
     char from_type[12], to_type[12], from_uid[160], to_uid[160];
     uint64_t count, err_count, sum_ns, sumsq_us, max_ns, score_q32; uint32_t edges, from_nodes, alive, worst_row; float score_max; uint32_t pad;
@@ -502,6 +531,17 @@ long sgh_graphds_workload_incidents(void* g, sg_incident_out* out, size_t cap, u
     if (out && !v.empty()) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(sg_incident_out));
     if (node_incident && !ni.empty()) std::memcpy(node_incident, ni.data(), std::min(node_cap, ni.size()) * sizeof(uint32_t));
     if (n_nodes) *n_nodes = ni.size();
+    return n;
+}
+// the workload impact (K22): the switch (0, 0: off) and the last flushed window's incident rows with their impact rows
+int sgh_graphds_set_workload_impact(void* g, uint32_t max_incidents, uint32_t max_hops) { return static_cast<HostCtx*>(g)->ds->SetWorkloadImpact(max_incidents, max_hops); }
+long sgh_graphds_workload_impact(void* g, sg_incident_out* incidents, size_t inc_cap, size_t* n_incidents, uint64_t* impact, size_t cap_rows) {
+    std::vector<sg_incident_out> v; std::vector<uint64_t> w;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadImpact(&v, &w);
+    if (n < 0) return n;
+    if (incidents && !v.empty()) std::memcpy(incidents, v.data(), std::min(inc_cap, v.size()) * sizeof(sg_incident_out));
+    if (n_incidents) *n_incidents = v.size();
+    if (impact && n) std::memcpy(impact, w.data(), std::min(cap_rows, (size_t)n) * SG_IMPACT_WORDS * sizeof(uint64_t));
     return n;
 }
 // the workload tracks (K19): the switch (on = 0: off) and the last flushed window's track rows and ended list as the engine gives them
@@ -864,6 +904,14 @@ size_t sgh_mock_k18_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k18_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k18_ops[i].data(), 32);
     return m->k18_ops.size();
+}
+size_t sgh_mock_k22_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k22_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k22_ops[i].data(), 32);
+    return m->k22_ops.size();
 }
 size_t sgh_mock_k21_ops(void* g, uint64_t* out4, size_t cap) {
     auto* c = static_cast<HostCtx*>(g);

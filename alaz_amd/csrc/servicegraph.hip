@@ -35,6 +35,7 @@
 #include "sg_group_nodes.h"
 #include "sg_group_rank.h"
 #include "sg_group_incident.h"
+#include "sg_group_impact.h"
 #include "sg_group_track.h"
 #include "sg_quantiles.h"
 #include "sg_quantile_trend.h"
@@ -255,6 +256,14 @@ struct sg_engine {
     Incidents<sgplan::GroupIncidentPlan> ginc;
     // K19, the workload tracks: the tracks over the workload incidents, freed with them
     Tracks gtrk;
+    // K22, the workload impact (sg_group_impact.h): allocated at sg_set_group_impact (sg_plan.hpp plan_group_impact), one allocation,
+    // freed with the workload incidents.  The position table, the two round buffers, the call edges' ends, the arrival marks, the
+    // round counters and the staging are scratch shared by the window slots: every search waits for the previous one (ev), whichever
+    // slot's stream it runs on.  Per slot: the mask rows (the search's `have`), the impact rows, the hops, the covered count.
+    struct Impact { bool on = false; u32 max_hops = 0; sgplan::GroupImpactPlan plan; char* mem = nullptr; u32* pos = nullptr; u64* fresh = nullptr;
+                    u64* next = nullptr; u64* ends = nullptr; u32* arrive = nullptr; u32* cnt = nullptr; u32* stage = nullptr; u32* stage_idx = nullptr;
+                    std::vector<u64*> mask, rows, count; std::vector<u32*> hops; std::vector<char> valid; hipEvent_t ev = nullptr;
+                    bool pending = false; } gimp;
     // K20, the latency percentiles (sg_quantiles.h): a space (nodes, group edges, workloads) is a stage of its own — one block
     // (sg_plan.hpp plan_quantiles), allocated at sg_set_quantiles, freed with its base stage.  The row positions, the target arrays,
     // the partials and the staging are scratch shared by the window slots: every fold of the space waits for the previous one (ev),
@@ -775,6 +784,7 @@ constexpr StageWords kGroupNodeTrendWords{"the workload trend is off (sg_set_gro
 constexpr StageWords kGroupRankWords{"the workload ranking is off (sg_set_group_rank)", "the workload ranking was off"};
 constexpr StageWords kGroupIncidentsWords{"the workload incidents are off (sg_set_group_incidents)", "the workload incidents were off"};
 constexpr StageWords kGroupTracksWords{"workload tracking is off (sg_set_group_tracks)", "workload tracking was off"};
+constexpr StageWords kGroupImpactWords{"the workload impact is off (sg_set_group_impact)", "the workload impact was off"};
 constexpr StageWords kGroupVanishedWords{"the group vanished list is off (sg_set_group_vanished)", "the group vanished list was off"};
 // A node space: what the baseline, the selection, the ranking, the incidents and the readbacks over node rows work on — K9's nodes
 // or K16's workloads.  Its rollup, its baseline, its selection scratch, the rows a window can have, and how its messages name it:
@@ -1196,8 +1206,38 @@ int launch_group_tracks(sg_engine* e, hipStream_t s) {
                          [s, mg](dim3 g, dim3 nt, const TrkArgs& a) { hipLaunchKernelGGL(k19_members, g, nt, 0, s, a, mg); });
 }
 void free_group_tracks(sg_engine* e) { free_stage(e->gtrk); }
+// ---- K22, the workload impact (engine lock held) -----------------------------------------------------------------------------------
+static_assert(sgplan::kImpThreads == K12_THREADS, "plan_group_impact sizes the launches of sg_group_impact.h");
+// enqueue the search of the window in slot cur on stream s (behind K18, on the same stream) and behind the previous search (any
+// stream): 2 max_hops + 4 plain launches; of K18 only the slot's incident count and incident per workload row are read
+int launch_group_impact(sg_engine* e, hipStream_t s) {
+    sg_engine::Impact& x = e->gimp;
+    const sgplan::GroupImpactPlan& P = x.plan;
+    ImpactArgs a{};
+    a.g = group_nodes_view(e);
+    a.nodes = e->gnodes.rows[e->cur]; a.ncount = e->gnodes.count[e->cur];
+    a.icount = e->ginc.count[e->cur]; a.node_inc = e->ginc.node_inc[e->cur];
+    a.max_inc = P.max_incidents; a.max_hops = x.max_hops; a.W = P.words;
+    a.pos = x.pos; a.fresh = x.fresh; a.next = x.next; a.ends = x.ends; a.arrive = x.arrive; a.cnt = x.cnt;
+    a.have = x.mask[e->cur]; a.out = x.rows[e->cur]; a.hops = x.hops[e->cur]; a.count = x.count[e->cur];
+    if (const int rc = stage_wait(e, x, s)) return rc;
+    const dim3 nt(K12_THREADS), ng(P.node_wgs), eg(P.edge_wgs);
+    hipLaunchKernelGGL(k22_seed, ng, nt, 0, s, a);
+    hipLaunchKernelGGL(k22_ends, eg, nt, 0, s, a);
+    hipLaunchKernelGGL(k22_pull, ng, nt, 0, s, a, 0u);
+    for (u32 r = 1; r <= x.max_hops; r++) {
+        hipLaunchKernelGGL(k22_push, eg, nt, 0, s, a, r);
+        hipLaunchKernelGGL(k22_pull, ng, nt, 0, s, a, r);
+    }
+    hipLaunchKernelGGL(k22_finish, dim3(P.finish_wgs), nt, 0, s, a);
+    if (const int rc = stage_done(e, x, s)) return rc;
+    x.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_group_impact(sg_engine* e) { free_stage(e->gimp); }
 void free_group_incidents(sg_engine* e) {
     free_group_tracks(e);
+    free_group_impact(e);
     free_stage(e->ginc);
 }
 // ---- K20, the latency percentiles (engine lock held) -------------------------------------------------------------------------------
@@ -1393,6 +1433,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
             if (e->grank.on) { if (const int rc = launch_group_rank(e, s)) return rc; }   // K17 behind K16 and its baseline: the group edges, the workload rows and their count
             if (e->ginc.on) { if (const int rc = launch_group_incidents(e, s)) return rc; }   // K18 behind K15, K16 and K17: the group trend rows, the workload rows, the rank rows
             if (e->gtrk.on) { if (const int rc = launch_group_tracks(e, s)) return rc; }   // K19 behind K18: the workload rows, the incident rows, the incident per workload row
+            if (e->gimp.on) { if (const int rc = launch_group_impact(e, s)) return rc; }   // K22 behind K18: the group edges, the workload rows, the incident count and the incident per workload row
             if (e->qnt.sp[kQWorkloads].on) { if (const int rc = launch_quantiles(e, kQWorkloads, s)) return rc; }   // K20 behind K16: and the workload rows
             if (e->qtr.workloads.on) { if (const int rc = launch_node_tail(e, tail_workload_space(e), kQWorkloads, s, k21_wcount, k21_wwrite)) return rc; }   // K21 behind K20
         }
@@ -3597,6 +3638,73 @@ int sg_group_track_stats_get(sg_handle e, sg_track_stats* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     return track_stats(e, workload_space(e), "sg_group_track_stats_get", out);
+}
+
+// ---- K22, the workload impact ------------------------------------------------------------------------------------------------------
+int sg_set_group_impact(sg_handle e, uint32_t max_incidents, uint32_t max_hops) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    const char* call = "sg_set_group_impact";
+    if (!e->ginc.on) { e->err = std::string(call) + ": " + kGroupIncidentsWords.off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    const bool off = max_incidents == 0 && max_hops == 0;
+    if (!off && sgplan::check_group_impact(max_incidents, max_hops)) { e->err = std::string(call) + ": bad parameters"; return SG_EINVAL; }
+    free_group_impact(e);
+    if (off) return SG_OK;
+    sg_engine::Impact& x = e->gimp;
+    const u32 slots = (u32)e->slots.size();
+    x.max_hops = max_hops;
+    x.plan = sgplan::plan_group_impact(e->cfg.max_edges, e->gnodes.plan.nc, e->gnodes.plan.gk, slots, max_incidents);
+    const sgplan::GroupImpactPlan& P = x.plan;
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, call, [e] { free_group_impact(e); })) return rc;
+    x.pos = at<u32>(x.mem, P.pos_off); x.fresh = at<u64>(x.mem, P.fresh_off); x.next = at<u64>(x.mem, P.next_off);
+    x.ends = at<u64>(x.mem, P.ends_off); x.arrive = at<u32>(x.mem, P.arrive_off); x.cnt = at<u32>(x.mem, P.cnt_off);
+    x.stage = at<u32>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
+    for (u32 k = 0; k < slots; k++) {
+        char* s = x.mem + P.slot.off + k * P.slot.bytes;
+        x.mask.push_back(at<u64>(s, P.slot_mask)); x.rows.push_back(at<u64>(s, P.slot_rows));
+        x.hops.push_back(at<u32>(s, P.slot_hops)); x.count.push_back(at<u64>(s, P.slot_count));
+    }
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+int sg_window_group_impact(sg_handle e, uint64_t* out, size_t cap_rows, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Impact& x = e->gimp;
+    if (const int rc = stage_ready(e, x, "sg_window_group_impact", kGroupImpactWords)) return rc;
+    return copy_counted(e, x.count[e->cur], x.rows[e->cur], SG_IMPACT_WORDS * sizeof(u64), out, cap_rows, n);
+}
+int sg_window_group_node_hops(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Impact& x = e->gimp;
+    if (const int rc = stage_ready(e, x, "sg_window_group_node_hops", kGroupImpactWords)) return rc;
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, e->gnodes.count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const size_t N = (size_t)std::min<u64>(cnt, x.plan.nc);
+    return copy_indexed(e, (const u32*)x.hops[e->cur], N, node_index, n_index, out, cap, n, x.stage, x.stage_idx, std::max<size_t>(x.plan.nc, 1),
+                        "sg_window_group_node_hops: a node index beyond the window's workload rows");
+}
+int sg_window_group_impact_mask(sg_handle e, uint64_t* out, size_t cap_rows, size_t* n, uint32_t* words) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Impact& x = e->gimp;
+    if (const int rc = stage_ready(e, x, "sg_window_group_impact_mask", kGroupImpactWords)) return rc;
+    if (words) *words = x.plan.words;
+    // (the mask is read whole: W words a row, no index form)
+    return copy_counted(e, e->gnodes.count[e->cur], x.mask[e->cur], x.plan.words * sizeof(u64), out, cap_rows, n);
+}
+int sg_window_group_impact_buffer(sg_handle e, void** d_impact, void** d_count, void** d_hops, void** d_mask) {
+    if (!e || !d_impact || !d_count || !d_hops || !d_mask) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const sg_engine::Impact& x = e->gimp;
+    int slot;
+    if (const int rc = stage_slot(e, x, "sg_window_group_impact_buffer", kGroupImpactWords, &slot)) return rc;
+    *d_impact = x.rows[slot]; *d_count = x.count[slot]; *d_hops = x.hops[slot]; *d_mask = x.mask[slot];
+    return SG_OK;
 }
 
 // enqueue-only variant of the whole window pipeline (no read-back, no host sync): what bench.py times.

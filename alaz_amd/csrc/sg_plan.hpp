@@ -1274,6 +1274,67 @@ inline TrackPlan plan_group_tracks(u32 max_groups, u32 max_known, u32 max_labels
     return plan_track_block((u64)max_groups + max_known + max_labels, nc, max_tracks, slots);
 }
 
+// K22, the workload impact (sg_group_impact.h): the device memory sg_set_group_impact allocates — never sg_create or any other
+// sg_set_* call.  Work is in ROW-INDEX space.  W = ceil(max_incidents / 64) u64 mask words per workload row.  Scratch shared by the
+// window slots: the row position by group key (pos [GK], the stage's own), the two round buffers fresh and next ([NC][W] u64 each),
+// the call edges' ends ([max_edges] u64), "a call edge arrives here" ([NC] u32), the round counters and the staging of
+// sg_window_group_node_hops' index form.  Each slot keeps its mask rows ([NC][W] u64: the search's `have`), its impact rows
+// ([max_incidents][8] u64), its hops ([NC] u32) and the covered count.  k22_seed, k22_pull run a grid-stride grid over NC, k22_ends
+// and k22_push one over max_edges (4 group edges a thread), each at most 1024 workgroups of 256 threads; k22_finish one over
+// max_incidents.  Config 3's engine (max_edges 1.25 M, GK = NC = 30 000, two slots) at the defaults (256 incidents, W = 4): 13.9 MiB
+// in all — 9.5 MiB of ends, 2 x 0.9 MiB of fresh / next, 2 x 1.0 MiB of slots; at K16's limit (2^21 keys, max_edges 4 M, two slots)
+// with 1024 incidents (W = 16) it is 1.1 GiB, 1 GiB of it the four [NC][16] u64 arrays.
+constexpr u32 kImpThreads = 256, kImpMaxWgs = 1024, kImpEdgesPerThread = 4;
+inline int check_group_impact(u32 max_incidents, u32 max_hops) {
+    return (max_incidents >= 1 && max_incidents <= SG_IMPACT_MAX_INCIDENTS && max_hops >= 1 && max_hops <= SG_IMPACT_MAX_HOPS) ? SG_OK : SG_EINVAL;
+}
+struct GroupImpactPlan {
+    u32 nc = 0;                   // workload rows per window slot (GroupNodesPlan::nc)
+    u64 gk = 0;                   // group keys (GroupNodesPlan::gk)
+    u32 max_incidents = 0, words = 0;   // words = W
+    u32 node_wgs = 0;             // k22_seed, k22_pull: grid-stride over nc
+    u32 edge_wgs = 0;             // k22_ends, k22_push: grid-stride over max_edges
+    u32 finish_wgs = 0;           // k22_finish: over max_incidents
+    u64 pos_bytes = 0;            // [gk] u32
+    u64 mask_bytes = 0;           // one [nc][W] u64 array (fresh, next; per slot: mask)
+    u64 ends_bytes = 0;           // [max_edges] u64
+    u64 node_bytes = 0;           // one [nc] u32 array (arrive, stage, stage_idx; per slot: hops)
+    u64 cnt_bytes = 0;            // [SG_IMPACT_MAX_HOPS + 1] u32
+    u64 rows_bytes = 0;           // one window slot's impact rows: [max_incidents][8] u64
+    u64 count_bytes = 0;          // one window slot's covered count (u64)
+    u64 total_bytes = 0;
+    u64 pos_off = 0, fresh_off = 0, next_off = 0, ends_off = 0, arrive_off = 0, cnt_off = 0, stage_off = 0, stage_idx_off = 0;
+    Slots slot; u64 slot_mask = 0, slot_rows = 0, slot_hops = 0, slot_count = 0;
+    std::vector<Piece> layout;
+};
+inline GroupImpactPlan plan_group_impact(u64 max_edges, u32 nc, u64 gk, u32 slots, u32 max_incidents) {
+    GroupImpactPlan r;
+    const u64 ME = std::max<u64>(max_edges, 1), NC = std::max<u32>(nc, 1), GK = std::max<u64>(gk, 1), MI = std::max<u32>(max_incidents, 1);
+    r.nc = nc; r.gk = gk; r.max_incidents = max_incidents; r.words = (u32)((MI + 63) / 64);
+    r.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kImpMaxWgs, (NC + kImpThreads - 1) / kImpThreads));
+    const u64 per = (u64)kImpEdgesPerThread * kImpThreads;
+    r.edge_wgs = (u32)std::max<u64>(1, std::min<u64>(kImpMaxWgs, (ME + per - 1) / per));
+    r.finish_wgs = (u32)((MI + kImpThreads - 1) / kImpThreads);
+    r.pos_bytes = trend_align(GK * 4);
+    r.mask_bytes = trend_align(NC * r.words * 8);
+    r.ends_bytes = trend_align(ME * 8);
+    r.node_bytes = trend_align(NC * 4);
+    r.cnt_bytes = trend_align(((u64)SG_IMPACT_MAX_HOPS + 1) * 4);
+    r.rows_bytes = trend_align(MI * SG_IMPACT_WORDS * 8);
+    r.count_bytes = trend_align(8);
+    Block b;
+    r.pos_off = b.take("pos", r.pos_bytes);
+    r.fresh_off = b.take("fresh", r.mask_bytes); r.next_off = b.take("next", r.mask_bytes);
+    r.ends_off = b.take("ends", r.ends_bytes);
+    r.arrive_off = b.take("arrive", r.node_bytes);
+    r.cnt_off = b.take("cnt", r.cnt_bytes);
+    r.stage_off = b.take("stage", r.node_bytes); r.stage_idx_off = b.take("stage_idx", r.node_bytes);
+    r.slot = b.slots(slots, {{"mask", r.mask_bytes, &r.slot_mask}, {"rows", r.rows_bytes, &r.slot_rows}, {"hops", r.node_bytes, &r.slot_hops},
+                             {"count", r.count_bytes, &r.slot_count}});
+    r.total_bytes = b.end; r.layout = std::move(b.pieces);
+    return r;
+}
+
 // K20, the latency percentiles (sg_quantiles.h): the device memory sg_set_quantiles allocates — never sg_create or any other
 // sg_set_* call.  One block a space, so that a space goes with its base stage.  Work is in ROW-INDEX space.  Shared by the window slots: the row position by key (pos: [ncap] for the nodes, [gk]
 // for the workloads — key spaces, at most 2^21 keys each, K16's rule), one 4-byte target array [max_edges] per side (nodes two,

@@ -90,6 +90,14 @@ TREND_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, lat_floor_ns=100
 #: SG_Q_*: the spaces of the latency percentiles (K20), and SG_Q_MAX, the quantiles per entity and side at most
 Q_SPACES = dict(nodes=1, groups=2, group_nodes=4)
 Q_MAX = 8
+#: SG_IMPACT_*: an impact row of the workload impact (K22) is IMPACT_WORDS u64 words, named by IMPACT_FIELDS in word order; the
+#: parameters' limits; SG_NO_HOPS: a workload row no covered incident reaches within max_hops
+IMPACT_WORDS = 8
+IMPACT_MAX_INCIDENTS = 1024
+IMPACT_MAX_HOPS = 64
+NO_HOPS = 0xFFFFFFFF
+IMPACT_FIELDS = ("exposed", "direct", "far", "entries", "entry_count", "entry_err", "into_count", "into_err")
+IMPACT_EXPOSED, IMPACT_DIRECT, IMPACT_FAR, IMPACT_ENTRIES, IMPACT_ENTRY_COUNT, IMPACT_ENTRY_ERR, IMPACT_INTO_COUNT, IMPACT_INTO_ERR = range(8)
 
 
 class SgConfig(C.Structure):
@@ -277,6 +285,10 @@ def _signatures() -> dict:
         "sg_window_group_tracks_ended": (I, [H, P, sz, Psz]),
         "sg_window_group_tracks_buffer": (I, [H, PP, PP, PP]),
         "sg_group_track_entries": (I, [H, P, sz, Psz]), "sg_group_track_stats_get": (I, [H, P]),
+        "sg_set_group_impact": (I, [H, u32, u32]), "sg_window_group_impact": (I, [H, P, sz, Psz]),
+        "sg_window_group_node_hops": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_impact_mask": (I, [H, P, sz, Psz, C.POINTER(u32)]),
+        "sg_window_group_impact_buffer": (I, [H, PP, PP, PP, PP]),
         "sg_set_quantiles": (I, [H, u32, P, sz]),
         "sg_window_node_hist": (I, [H, P, sz, P, sz, Psz]), "sg_window_node_quantiles": (I, [H, P, sz, P, sz, Psz]),
         "sg_window_group_hist": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_quantiles": (I, [H, P, sz, P, sz, Psz]),
@@ -1052,6 +1064,40 @@ class ServiceGraph:
 
     def group_track_stats(self) -> SgTrackStats:
         return self._stats(self._l.sg_group_track_stats_get, SgTrackStats)
+
+    # ---- workload impact (K22): who depends on each workload incident ----
+    def set_group_impact(self, max_incidents: Optional[int] = 256, max_hops: int = 8):
+        """Switch the per-window upstream impact of the workload incidents on (sg_set_group_impact: the first max_incidents
+        incidents are covered, 1 .. IMPACT_MAX_INCIDENTS; the search is cut at max_hops call edges, 1 .. IMPACT_MAX_HOPS; needs the
+        workload incidents on) or off: set_group_impact(None).  Any set_group_incidents call switches it off."""
+        if max_incidents is None:
+            max_incidents, max_hops = 0, 0
+        self._ck(self._l.sg_set_group_impact(self._h, max_incidents, max_hops))
+
+    def window_group_impact(self) -> np.ndarray:
+        """the impact rows of the last read window (sg_window_group_impact), (n, IMPACT_WORDS) <u8: row i belongs to
+        window_group_incidents()[i], the words are IMPACT_FIELDS"""
+        return self._counted(self._l.sg_window_group_impact, np.dtype("<u8"), (IMPACT_WORDS,))
+
+    def window_group_node_hops(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """the fewest call edges from every workload row of the last read window to a covered incident (0: a member; NO_HOPS: none
+        within max_hops; sg_window_group_node_hops), or of the rows at index"""
+        return self._window_rows(self._l.sg_window_group_node_hops, np.dtype("<u4"), index)
+
+    def window_group_impact_mask(self) -> np.ndarray:
+        """the mask rows of the last read window (sg_window_group_impact_mask), (workload rows, W) <u8: bit b of word w of row v is
+        set iff incident 64 w + b is covered and reaches v within max_hops (its members included)"""
+        n, w = C.c_size_t(0), C.c_uint32(0)
+        self._ck(self._l.sg_window_group_impact_mask(self._h, None, 0, C.byref(n), C.byref(w)))
+        out = np.zeros((n.value, w.value), dtype=np.dtype("<u8"))
+        if n.value:
+            self._ck(self._l.sg_window_group_impact_mask(self._h, out.ctypes.data, n.value, C.byref(n), C.byref(w)))
+        return out[: n.value]
+
+    def window_group_impact_buffer(self) -> Tuple[int, int, int, int]:
+        """(device pointer of the impact rows, of their u64 count, of the u32 hops per workload row, of the mask rows) of the window
+        window_run closed last (sg_window_group_impact_buffer)"""
+        return self._pointers(self._l.sg_window_group_impact_buffer, 4)
 
     # ---- latency percentiles (K20): histograms and percentiles per node row, group edge and workload row ----
     def set_quantiles(self, spaces=("nodes",), permille=(500, 990)):

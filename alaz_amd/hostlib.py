@@ -124,6 +124,11 @@ def load() -> C.CDLL:
             "sgh_graphds_persist_replicaset": (C.c_int, [P, C.c_char_p, C.c_char_p, C.c_char_p]),
             "sgh_graphds_set_workload_groups": (C.c_int, [P, u32]), "sgh_graphds_workload_edges": (C.c_long, [P, P, sz]),
             "sgh_mock_group_ops": (sz, [P, P, sz]),
+            "sgh_graphds_persist_service_named": (C.c_int, [P, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
+            "sgh_graphds_persist_endpoints": (C.c_int, [P, C.c_char_p, C.c_char_p, C.c_char_p, P, P, sz]),
+            "sgh_graphds_set_service_binding": (C.c_int, [P, C.c_int]),
+            "sgh_graphds_set_workload_impact": (C.c_int, [P, u32, u32]),
+            "sgh_graphds_workload_impact": (C.c_long, [P, P, sz, P, P, sz]), "sgh_mock_k22_ops": (sz, [P, P, sz]),
             "sgh_graphds_set_workload_trend": (C.c_int, [P, u32, u32, u32, C.c_uint64]),
             "sgh_graphds_set_workload_vanished": (C.c_int, [P, u32, u32, u32]),
             "sgh_graphds_workload_trends": (C.c_long, [P, P, sz]),
@@ -453,6 +458,21 @@ class GraphDS:
     def PersistReplicaSet(self, uid: str, owner_id: str = "", event_type: str = "ADD"):
         return self._l.sgh_graphds_persist_replicaset(self._g, event_type.encode(), uid.encode(), owner_id.encode())
 
+    def PersistServiceNamed(self, uid: str, ip: str, name: str, namespace: str = "", event_type: str = "ADD"):
+        """PersistService with the Service's name and namespace: what the service binding looks its Endpoints up by"""
+        return self._l.sgh_graphds_persist_service_named(self._g, event_type.encode(), uid.encode(), ip.encode(), name.encode(), namespace.encode())
+
+    def PersistEndpoints(self, name: str, namespace: str = "", addresses=(), event_type: str = "ADD"):
+        """PersistEndpoints of (namespace, name): addresses = [(type, id), ...], ("Pod", pod UID) for a pod behind the Service"""
+        n = len(addresses)
+        types = (C.c_char_p * max(n, 1))(*[t.encode() for t, _ in addresses])
+        ids = (C.c_char_p * max(n, 1))(*[i.encode() for _, i in addresses])
+        return self._l.sgh_graphds_persist_endpoints(self._g, event_type.encode(), name.encode(), namespace.encode(), types, ids, n)
+
+    def set_service_binding(self, on: bool = True) -> int:
+        """GraphDS::SetServiceBinding: Services join the workload behind them, on or off (rc; needs set_workload_groups)"""
+        return self._l.sgh_graphds_set_service_binding(self._g, 1 if on else 0)
+
     def set_workload_groups(self, max_groups: int = 0) -> int:
         """GraphDS::SetWorkloadGroups: pods are grouped by their top known owner from now on (rc)"""
         return self._l.sgh_graphds_set_workload_groups(self._g, max_groups)
@@ -599,6 +619,31 @@ class GraphDS:
         n = self._l.sgh_mock_k18_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k18_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the workload impact (K22) ----
+    def set_workload_impact(self, max_incidents: int = 256, max_hops: int = 8) -> int:
+        """GraphDS::SetWorkloadImpact: the upstream impact of the workload incidents on, or off with (0, 0) (rc)"""
+        return self._l.sgh_graphds_set_workload_impact(self._g, max_incidents, max_hops)
+
+    def workload_impact(self):
+        """GraphDS::WorkloadImpact: (engine.INCIDENT_DTYPE rows of the last flushed window, (covered, engine.IMPACT_WORDS) u64 impact
+        rows: row i belongs to incident i)"""
+        from .engine import IMPACT_WORDS, INCIDENT_DTYPE
+        ni = C.c_size_t(0)
+        n = self._l.sgh_graphds_workload_impact(self._g, None, 0, C.byref(ni), None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadImpact failed: {n}")
+        inc, rows = np.zeros(max(ni.value, 1), dtype=INCIDENT_DTYPE), np.zeros((max(n, 1), IMPACT_WORDS), dtype=np.uint64)
+        self._l.sgh_graphds_workload_impact(self._g, inc.ctypes.data, ni.value, C.byref(ni), rows.ctypes.data, n)
+        return inc[:ni.value], rows[:n]
+
+    def mock_k22_ops(self) -> np.ndarray:
+        """the stand-in engine's K22 calls in order, four u64 each: (1, max_incidents, max_hops, 0) per sg_set_group_impact,
+        (2, cap, 0, 0) per sg_window_group_impact"""
+        n = self._l.sgh_mock_k22_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k22_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     # ---- the workload tracks (K19) ----

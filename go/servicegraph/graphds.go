@@ -106,6 +106,13 @@ type GraphDS struct {
 	wlEntries uint64
 	wlVanRows int
 
+	// the service binding (idMu): the groups AssignGroups was told, the Services by "namespace/name", the pods behind each, and back
+	bindOn    bool
+	nodeGroup map[uint32]uint32
+	svcUID    map[string]string
+	epPods    map[string][]string
+	podEps    map[string][]string
+
 	maxEdges int     // sg_config.max_edges
 	selOn    bool    // SetSelection (under flushMu): FlushWindow returns the selected rows only
 	selK     uint32
@@ -156,7 +163,8 @@ func New(inner datastore.DataStore, c Config) (*GraphDS, error) {
 		cfg.flags |= C.SG_CFG_EDGE_HISTOGRAM
 	}
 	g := &GraphDS{inner: inner, divert: c.Divert, ids: map[string]uint32{}, podIP: map[uint32]uint32{}, svcIP: map[uint32]uint32{},
-		labels: map[string]uint32{}, maxKnown: c.MaxKnownNodes, maxEdges: int(c.MaxEdges)}
+		labels: map[string]uint32{}, maxKnown: c.MaxKnownNodes, maxEdges: int(c.MaxEdges),
+		nodeGroup: map[uint32]uint32{}, svcUID: map[string]string{}, epPods: map[string][]string{}, podEps: map[string][]string{}}
 	if rc := C.sg_create(&cfg, &g.h); rc != 0 {
 		return nil, fmt.Errorf("servicegraph: sg_create = %d (no usable gfx950 device, or bad config)", int(rc))
 	}
@@ -290,6 +298,9 @@ func (g *GraphDS) upsertOrDelete(svc bool, uid, ipStr, eventType string) {
 
 func (g *GraphDS) PersistPod(pod datastore.Pod, eventType string) error {
 	g.upsertOrDelete(false, pod.UID, pod.IP, eventType)
+	g.idMu.Lock()
+	g.bindServicesOfPod(pod.UID) // a pod added or removed: the Services it stands behind
+	g.idMu.Unlock()
 	return g.inner.PersistPod(pod, eventType)
 }
 
@@ -300,13 +311,152 @@ func (g *GraphDS) PersistService(service datastore.Service, eventType string) er
 	if len(service.ClusterIPs) > 0 {
 		ip = service.ClusterIPs[0]
 	}
+	if service.Name != "" && eventType == "DELETE" { // forget the entry: a bound Service leaves its group first
+		key := service.Namespace + "/" + service.Name
+		g.idMu.Lock()
+		if uid, ok := g.svcUID[key]; ok {
+			if id, ok := g.ids[uid]; ok {
+				g.assignLocked(id, NoGroup)
+			}
+			delete(g.svcUID, key)
+		}
+		g.idMu.Unlock()
+	}
 	g.upsertOrDelete(true, service.UID, ip, eventType)
+	if service.Name != "" && (eventType == "ADD" || eventType == "UPDATE") {
+		key := service.Namespace + "/" + service.Name
+		g.idMu.Lock()
+		g.svcUID[key] = service.UID
+		g.bindService(key)
+		g.idMu.Unlock()
+	}
 	return g.inner.PersistService(service, eventType)
+}
+
+// ---- the service binding (idMu held) -----------------------------------------------------------------------------------
+
+// assignLocked sends one sg_group_assign when the engine does not hold the value already.
+func (g *GraphDS) assignLocked(id, group uint32) {
+	cur, ok := g.nodeGroup[id]
+	if !ok {
+		cur = NoGroup
+	}
+	if cur == group {
+		return
+	}
+	cid, cg := C.uint32_t(id), C.uint32_t(group)
+	if rc := C.sg_group_assign(g.h, &cid, &cg, 1); rc != 0 {
+		g.EngineErrors.Add(1)
+		return
+	}
+	if group == NoGroup {
+		delete(g.nodeGroup, id)
+	} else {
+		g.nodeGroup[id] = group
+	}
+}
+
+// bindService applies the rule to the Service at key: group g iff its Endpoints name at least one pod that has an IP here and
+// every such pod is in g; otherwise none.
+func (g *GraphDS) bindService(key string) {
+	uid, ok := g.svcUID[key]
+	if !ok {
+		return
+	}
+	sid, ok := g.ids[uid]
+	if !ok || g.kindOf[sid] != kindService {
+		return
+	}
+	group, some, one := NoGroup, false, true
+	if g.bindOn {
+		for _, pod := range g.epPods[key] {
+			pid, ok := g.ids[pod]
+			if !ok || g.kindOf[pid] != kindPod || g.refs[pid] == 0 {
+				continue // a pod the store does not know
+			}
+			pg, ok := g.nodeGroup[pid]
+			if !ok || (some && pg != group) {
+				one = false // an ungrouped pod among them, or two workloads behind it
+			}
+			group, some = pg, true
+		}
+	}
+	if !some || !one {
+		group = NoGroup
+	}
+	g.assignLocked(sid, group)
+}
+
+func (g *GraphDS) bindServicesOfPod(podUID string) {
+	for _, key := range g.podEps[podUID] {
+		g.bindService(key)
+	}
+}
+
+func (g *GraphDS) bindAllServices() {
+	for key := range g.svcUID {
+		g.bindService(key)
+	}
+}
+
+// SetServiceBinding switches the service binding on or off (off by default; behind SetGroups).  With it on, a Service's node id
+// joins the group of the pods behind it, so that pod -> ClusterIP traffic contracts to workload -> workload and call chains run
+// through Services: (namespace, name) -> Service comes from PersistService, (namespace, name) -> pod UIDs from PersistEndpoints
+// (addresses of Type "Pod" with an ID), the pods' groups from AssignGroups.  A Service is in group g iff its Endpoints name at
+// least one pod that has an IP here and every such pod is in g; no Endpoints, no known pod, an ungrouped pod among them or two
+// workloads behind it leave it in none.  Every change of an input re-evaluates it, and one sg_group_assign is sent only when the
+// value changes.  Off un-assigns every bound Service.
+func (g *GraphDS) SetServiceBinding(on bool) {
+	g.idMu.Lock()
+	g.bindOn = on
+	g.bindAllServices()
+	g.idMu.Unlock()
 }
 
 func (g *GraphDS) PersistReplicaSet(rs datastore.ReplicaSet, eventType string) error { return g.inner.PersistReplicaSet(rs, eventType) }
 func (g *GraphDS) PersistDeployment(d datastore.Deployment, eventType string) error  { return g.inner.PersistDeployment(d, eventType) }
-func (g *GraphDS) PersistEndpoints(e datastore.Endpoints, eventType string) error    { return g.inner.PersistEndpoints(e, eventType) }
+
+// PersistEndpoints is forwarded unchanged; the pods behind (namespace, name) are remembered for SetServiceBinding (the addresses
+// whose Type is "Pod" with a non-empty ID: TargetRef's, aggregator/persist.go:247-267).  DELETE forgets the entry.
+func (g *GraphDS) PersistEndpoints(e datastore.Endpoints, eventType string) error {
+	if eventType == "ADD" || eventType == "UPDATE" || eventType == "DELETE" {
+		key := e.Namespace + "/" + e.Name
+		g.idMu.Lock()
+		for _, pod := range g.epPods[key] {
+			keys := g.podEps[pod][:0]
+			for _, k := range g.podEps[pod] {
+				if k != key {
+					keys = append(keys, k)
+				}
+			}
+			if len(keys) == 0 {
+				delete(g.podEps, pod)
+			} else {
+				g.podEps[pod] = keys
+			}
+		}
+		delete(g.epPods, key)
+		if eventType != "DELETE" {
+			seen := map[string]bool{}
+			var pods []string
+			for _, a := range e.Addresses {
+				for _, ip := range a.IPs {
+					if ip.Type == "Pod" && ip.ID != "" && !seen[ip.ID] {
+						seen[ip.ID] = true
+						pods = append(pods, ip.ID)
+					}
+				}
+			}
+			g.epPods[key] = pods
+			for _, pod := range pods {
+				g.podEps[pod] = append(g.podEps[pod], key)
+			}
+		}
+		g.bindService(key)
+		g.idMu.Unlock()
+	}
+	return g.inner.PersistEndpoints(e, eventType)
+}
 func (g *GraphDS) PersistContainer(c datastore.Container, eventType string) error    { return g.inner.PersistContainer(c, eventType) }
 func (g *GraphDS) PersistDaemonSet(ds datastore.DaemonSet, eventType string) error   { return g.inner.PersistDaemonSet(ds, eventType) }
 func (g *GraphDS) PersistStatefulSet(ss datastore.StatefulSet, eventType string) error {
@@ -671,6 +821,9 @@ func (g *GraphDS) FlushWindow(windowEndMs int64) ([]EdgeRow, error) {
 		if cur, ok := g.ids[g.uidOf[id]]; ok && cur == id {
 			delete(g.ids, g.uidOf[id])
 		}
+		if g.kindOf[id] == kindService {
+			g.assignLocked(id, NoGroup) // a Service that was bound leaves its group with its id (never assigned: no call)
+		}
 		g.uidOf[id], g.kindOf[id] = "", 0
 		g.freeIDs = append(g.freeIDs, id)
 	}
@@ -968,6 +1121,9 @@ func (g *GraphDS) SetGroups(maxGroups uint32) error {
 	if rc := C.sg_set_groups(g.h, &gp); rc != 0 {
 		return fmt.Errorf("servicegraph: sg_set_groups = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
 	}
+	g.idMu.Lock()
+	g.nodeGroup = map[uint32]uint32{} // the engine's map starts over
+	g.idMu.Unlock()
 	return nil
 }
 
@@ -975,6 +1131,9 @@ func (g *GraphDS) ClearGroups() {
 	g.flushMu.Lock()
 	C.sg_set_groups(g.h, nil)
 	g.flushMu.Unlock()
+	g.idMu.Lock()
+	g.nodeGroup = map[uint32]uint32{}
+	g.idMu.Unlock()
 }
 
 // AssignGroups puts node nodeIDs[i] into group groups[i] (NoGroup: into none), in that order; the windows closed from now on
@@ -989,8 +1148,22 @@ func (g *GraphDS) AssignGroups(nodeIDs, groups []uint32) error {
 	}
 	ids := (*C.uint32_t)(unsafe.Pointer(&nodeIDs[0]))
 	gs := (*C.uint32_t)(unsafe.Pointer(&groups[0]))
+	g.idMu.Lock()
+	defer g.idMu.Unlock()
 	if rc := C.sg_group_assign(g.h, ids, gs, C.size_t(len(nodeIDs))); rc != 0 {
 		return fmt.Errorf("servicegraph: sg_group_assign = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	for i, id := range nodeIDs { // what the engine holds now; the Services behind which a re-grouped pod stands follow it
+		if groups[i] == NoGroup {
+			delete(g.nodeGroup, id)
+		} else {
+			g.nodeGroup[id] = groups[i]
+		}
+	}
+	for _, id := range nodeIDs {
+		if int(id) < len(g.uidOf) && g.kindOf[id] == kindPod {
+			g.bindServicesOfPod(g.uidOf[id])
+		}
 	}
 	return nil
 }
@@ -1464,6 +1637,58 @@ func (g *GraphDS) WindowWorkloadIncidents() ([]Incident, error) {
 }
 
 // ---- workload tracks (K19) -----------------------------------------------------------------------------------------------
+
+// WorkloadImpact is one impact row of the workload impact (K22): who depends on a workload incident.  FarHops / FarRow: the
+// largest distance among the exposed workloads and the smallest workload row that has it (FarRow = NoIncident when nothing is
+// exposed; FarHops equal to SetWorkloadImpact's maxHops: the search may have been cut).
+type WorkloadImpact struct {
+	Exposed, Direct, Entries, EntryCount, EntryErr, IntoCount, IntoErr uint64
+	FarHops, FarRow                                                    uint32
+}
+
+// SetWorkloadImpact switches the upstream impact of the workload incidents on, behind SetWorkloadIncidents: the first maxIncidents
+// incidents of a window are covered (1 .. 1024) and the search against the call edges is cut at maxHops (1 .. 64).
+// ClearWorkloadImpact switches it off; every SetWorkloadIncidents / ClearWorkloadIncidents call does so too.
+func (g *GraphDS) SetWorkloadImpact(maxIncidents, maxHops uint32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	if rc := C.sg_set_group_impact(g.h, C.uint32_t(maxIncidents), C.uint32_t(maxHops)); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_group_impact = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func (g *GraphDS) ClearWorkloadImpact() {
+	g.flushMu.Lock()
+	C.sg_set_group_impact(g.h, 0, 0)
+	g.flushMu.Unlock()
+}
+
+// WindowWorkloadImpact returns the impact rows of the window FlushWindow returned last: row i belongs to
+// WindowWorkloadIncidents()[i] (sg_window_group_impact: 64 bytes per covered incident cross PCIe, no group edge does).
+func (g *GraphDS) WindowWorkloadImpact() ([]WorkloadImpact, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var n C.size_t
+	if rc := C.sg_window_group_impact(g.h, nil, 0, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_impact = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	w := make([]uint64, int(n)*int(C.SG_IMPACT_WORDS))
+	if rc := C.sg_window_group_impact(g.h, (*C.uint64_t)(unsafe.Pointer(&w[0])), n, &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_group_impact = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	out := make([]WorkloadImpact, int(n))
+	for i := range out {
+		r := w[i*int(C.SG_IMPACT_WORDS):]
+		out[i] = WorkloadImpact{Exposed: r[C.SG_IMPACT_EXPOSED], Direct: r[C.SG_IMPACT_DIRECT], FarHops: uint32(r[C.SG_IMPACT_FAR] >> 32),
+			FarRow: uint32(r[C.SG_IMPACT_FAR]), Entries: r[C.SG_IMPACT_ENTRIES], EntryCount: r[C.SG_IMPACT_ENTRY_COUNT],
+			EntryErr: r[C.SG_IMPACT_ENTRY_ERR], IntoCount: r[C.SG_IMPACT_INTO_COUNT], IntoErr: r[C.SG_IMPACT_INTO_ERR]}
+	}
+	return out, nil
+}
 
 // SetWorkloadTracks switches the tracking of workload incidents across windows on, behind SetWorkloadIncidents: K13's tracking
 // over the workload incidents and workload rows, so that an incident keeps its track when a rollout replaces every pod of a

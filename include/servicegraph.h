@@ -1015,6 +1015,64 @@ int sg_window_group_tracks_buffer(sg_handle h, void** d_tracks, void** d_ended, 
 int sg_group_track_entries(sg_handle h, sg_track_entry* out, size_t cap, size_t* n);
 int sg_group_track_stats_get(sg_handle h, sg_track_stats* out);
 
+/* ---- workload impact (K22): who depends on each workload incident, and what entered through them, on the device --------------- *
+ * Opt-in (sg_set_group_impact, on an engine with the workload incidents); without it nothing is launched or allocated, and every
+ * other output is byte for byte the same either way.  Given an incident at `db`: which workloads call it, directly or through
+ * others, and how much traffic entered the system through workloads upstream of it?  A capped selection cannot answer that (the
+ * callers of an incident are mostly not red), and a host search needs every group edge copied out first.  Workload space only: in
+ * pod space a row's source is always a pod, so a Service node has no outgoing row and nothing is more than one hop upstream.
+ * There is no new struct: the rows are plain uint64_t / uint32_t arrays.  Over the last closed window's group edges j
+ * (sg_window_groups order), its workload rows v (sg_window_group_nodes order), its workload incidents i < I
+ * (sg_window_group_incidents) and inc[v] (sg_window_group_node_incident):
+ *   covered     incident i is covered iff i < min(I, max_incidents); W = ceil(max_incidents / 64) mask words per workload row
+ *   call edge   a group edge with count > 0 whose from_ref and to_ref both have workload rows u != v: "u calls v".  Alive-only
+ *               group edges, traffic inside one workload and an endpoint cut at the row capacity never count
+ *   d_i(x)      0 if inc[x] == i; otherwise the fewest call edges on a directed path from x to a member of i, infinite without one
+ *   exposed     x is exposed to i iff 1 <= d_i(x) <= max_hops;  reach_i = the members of i and its exposed rows
+ *   entry row   a workload row at which no call edge arrives
+ * Impact row i (SG_IMPACT_WORDS uint64_t words):
+ *   EXPOSED     the exposed rows                          DIRECT   the rows with d_i == 1
+ *   FAR         hops << 32 | row: the largest d_i among the exposed rows and the smallest row that has it; 0x00000000FFFFFFFF when
+ *               nothing is exposed.  hops == max_hops: the search may have been cut
+ *   ENTRIES     the entry rows in reach_i                 ENTRY_COUNT, ENTRY_ERR   the wrapping sums of their out_count, out_err
+ *   INTO_COUNT, INTO_ERR   the wrapping sums of count and err_count over the call edges with inc[to] == i and inc[from] != i
+ * Per workload row v: hops[v] = the smallest d_i(v) over the covered incidents if that is at most max_hops (a member: 0), else
+ * SG_NO_HOPS; mask[v][w] bit b is set iff incident 64 w + b is covered and d_i(v) <= max_hops (members included).  Every value is
+ * an integer sum or the max of a key: the result has one correct value.  Every close path computes it, behind K18 on the window's
+ * stream: 2 max_hops + 4 launches, most of which return at their first load once a round reaches no new row.
+ * State: sg_set_group_impact(h, max_incidents, max_hops) — 0, 0 switches it off and frees its memory; on needs
+ * 1 <= max_incidents <= SG_IMPACT_MAX_INCIDENTS and 1 <= max_hops <= SG_IMPACT_MAX_HOPS, anything else is SG_EINVAL; SG_ESTATE with
+ * the workload incidents off (sg_set_group_incidents) or while a flush is open.  Memory is allocated there, never at sg_create or at
+ * any other sg_set_* call.  EVERY sg_set_group_incidents call, on or off, switches it off and frees it, and so does whatever frees
+ * the workload incidents (as the workload tracks).  Reads of a window closed while it was off, and while a flush is open: SG_ESTATE. */
+#define SG_IMPACT_WORDS          8u
+#define SG_IMPACT_MAX_INCIDENTS  1024u
+#define SG_IMPACT_MAX_HOPS       64u
+#define SG_NO_HOPS               0xFFFFFFFFu
+/* word indices of an impact row */
+#define SG_IMPACT_EXPOSED     0u
+#define SG_IMPACT_DIRECT      1u
+#define SG_IMPACT_FAR         2u
+#define SG_IMPACT_ENTRIES     3u
+#define SG_IMPACT_ENTRY_COUNT 4u
+#define SG_IMPACT_ENTRY_ERR   5u
+#define SG_IMPACT_INTO_COUNT  6u
+#define SG_IMPACT_INTO_ERR    7u
+int sg_set_group_impact(sg_handle h, uint32_t max_incidents, uint32_t max_hops);
+/* The impact rows of the last READ window: *n = min(I, max_incidents) rows, min(*n, cap_rows) rows of SG_IMPACT_WORDS words each
+ * are written; row i belongs to sg_window_group_incidents' row i.                                                              */
+int sg_window_group_impact(sg_handle h, uint64_t* out, size_t cap_rows, size_t* n);
+/* hops of every workload row of the last READ window (as sg_window_group_node_incident): node_index NULL: every workload row,
+ * *n = workload rows; else out[k] = hops of workload row node_index[k] (each < workload rows, else SG_EINVAL), *n = n_index.
+ * min(*n, cap) values are written.                                                                                             */
+int sg_window_group_node_hops(sg_handle h, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n);
+/* The mask rows of the last READ window: *n = workload rows, *words = W, min(*n, cap_rows) rows of W words each are written.     */
+int sg_window_group_impact_mask(sg_handle h, uint64_t* out, size_t cap_rows, size_t* n, uint32_t* words);
+/* Device impact rows (uint64_t[max_incidents][SG_IMPACT_WORDS]), the covered count (one uint64_t), uint32_t hops[workload rows]
+ * and the mask rows (uint64_t[workload rows][W]) of the window sg_window_run closed last (valid until its slot is reused; read
+ * them on that window's stream).                                                                                               */
+int sg_window_group_impact_buffer(sg_handle h, void** d_impact, void** d_count, void** d_hops, void** d_mask);
+
 /* ---- latency percentiles (K20): histograms and percentiles per node row, group edge and workload row, on the device ----------- *
  * Opt-in (sg_set_quantiles, on an engine created with SG_CFG_EDGE_HISTOGRAM); without it nothing is launched or allocated, and
  * every other output is byte for byte the same either way.  Percentiles do not average: a node's, a group edge's or a workload's

@@ -1,0 +1,129 @@
+"""K22 at BASELINE config 3 (1 M edges, 10 M events, L = 2): what the workload impact costs.
+
+Two engines of one configuration, both with the groups, the group trend (K15), the workload rows and their baseline (K16), the
+workload ranking (K17) and the workload incidents (K18) on and their pods in blocks of --block (20: a Deployment of 20 replicas), one
+of them with the workload impact on at --max-incidents / --max-hops (the defaults), close the same windows alternately (A B A B
+...): sg_flush_window_view is timed on the host for each, and the difference of the medians is the stage's cost on the close path.
+Two phases of --windows windows each: the threshold at the 0.99 quantile of a window's own score_max ("p99"), and every group edge
+red ("all": min_value = -inf).  After each window of the K22 engine, window_group_impact() is timed against window_groups() (every
+group edge, 80 bytes each, over PCIe, to search the call graph on the host: the only way to an incident's callers without this
+stage).  The last window's rows of each phase are held to the reference (tests/impact_ref.py) unless --no-check.  For the device
+time per kernel run it under `rocprofv3 --kernel-trace --stats -- python tools/group_impact_probe.py --windows 3 --only-on
+--no-check` (the k22_* rows of the stats).  The stage's memory is the plan's to say (tests/micro/group_impact_plan_test.cpp prints
+plan_group_impact).  Prints one JSON line; --out also writes it to a file."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from alaz_amd import engine, replay, weights  # noqa: E402
+from tests.helpers import CLOCK, HostShim  # noqa: E402
+
+MAX_EDGES = 1_250_000
+INF = float("inf")
+
+
+def _engine(topo, ev, labels, L, block, iters):
+    g = engine.ServiceGraph(max_known_nodes=topo.n_nodes, max_edges=MAX_EDGES, layers=L, max_labels=128, max_outbound_ips=128,
+                            max_window_events=len(ev))
+    g.set_clock(*CLOCK); g.load_weights(weights.make_weights(L))
+    HostShim().apply(g, topo.k8s_ops()); g.set_label_count(len(labels))
+    pods = np.arange(topo.n_pods, dtype=np.uint32)                    # node ids 0 .. P-1 are the pods (Topology.k8s_ops)
+    g.set_groups(max_groups=int(topo.n_pods // block) + 1)            # a tight max_groups: the tables are per group key
+    g.group_assign(pods, pods // block)
+    g.set_group_trend(warmup=1)
+    g.set_group_nodes(); g.set_group_node_trend(warmup=1)
+    g.set_group_rank(iters=iters)
+    return g
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=8)
+    ap.add_argument("--block", type=int, default=20, help="pods per group")
+    ap.add_argument("--iters", type=int, default=20, help="K17's iterations, on both engines")
+    ap.add_argument("--max-incidents", type=int, default=256)
+    ap.add_argument("--max-hops", type=int, default=8)
+    ap.add_argument("--only-on", action="store_true", help="the K22 engine alone (profiler runs)")
+    ap.add_argument("--no-check", action="store_true", help="skip the reference over the last window of each phase (slow in Python)")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    topo, ev, labels, L = replay.make_config(3)
+    on = _engine(topo, ev, labels, L, a.block, a.iters)
+    off = None if a.only_on else _engine(topo, ev, labels, L, a.block, a.iters)
+    med = lambda x: {"median": float(np.median(x)), "min": float(np.min(x)), "max": float(np.max(x))}   # noqa: E731
+    rng = np.random.default_rng(17)
+    res = {"config": 3, "windows": a.windows, "block": a.block, "iters": a.iters, "max_incidents": a.max_incidents, "max_hops": a.max_hops}
+    w = 0
+
+    def close(timed):
+        nonlocal w
+        e = ev.copy()                                                 # latency drifts, so that the windows are not all one
+        e["duration_ns"] = (e["duration_ns"].astype(np.float64) * (1.0 + 0.1 * w * rng.random(len(e)))).astype(np.uint64)
+        w += 1
+        for g, acc in ((on, timed[0]), (off, timed[1])):
+            if g is None:
+                continue
+            g.ingest_bulk(e)
+            t0 = time.perf_counter()
+            g.flush_window_view()
+            acc.append((time.perf_counter() - t0) * 1e3)
+
+    def switch(thr):
+        for g in (on, off):
+            if g is not None:
+                g.set_group_incidents(by="score", min_value=thr)
+        on.set_group_impact(a.max_incidents, a.max_hops)
+
+    switch(INF)
+    close(([], []))                                                   # warm-up, and the window whose score_max sets the p99 threshold
+    v = on.window_groups()["score_max"]
+    p99 = float(np.sort(v[~np.isnan(v)])[int(0.99 * (len(v) - 1))])
+    for phase, thr in (("p99", p99), ("all", -INF)):
+        switch(thr)
+        close(([], []))                                               # (the first close after the switch is left out)
+        t_on, t_off, imp_ms, all_ms = [], [], [], []
+        for _ in range(a.windows):
+            close((t_on, t_off))
+            t0 = time.perf_counter()
+            imp = on.window_group_impact()
+            imp_ms.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            ge = on.window_groups()
+            all_ms.append((time.perf_counter() - t0) * 1e3)
+        n, incs, hops = on.window_group_nodes(), on.window_group_incidents(), on.window_group_node_hops()
+        far = imp[:, engine.IMPACT_FAR] >> np.uint64(32) if len(imp) else np.zeros(0, np.uint64)
+        far = far[far != 0] if len(far) else far
+        r = {"min_value": thr, "group_edges": int(len(ge)), "workload_rows": int(len(n)), "incidents": int(len(incs)), "covered": int(len(imp)),
+             "exposed_rows_sum": int(imp[:, engine.IMPACT_EXPOSED].sum()) if len(imp) else 0,
+             "rows_within_reach": int((hops != engine.NO_HOPS).sum()), "deepest_hops": int(far.max()) if len(far) else 0,
+             "flush_view_k22_on_ms": med(t_on), "window_group_impact_ms": med(imp_ms), "window_groups_all_ms": med(all_ms),
+             "group_edge_bytes": int(ge.nbytes), "impact_bytes": int(imp.nbytes)}
+        print(f"[{phase}] timed {a.windows} windows", file=sys.stderr, flush=True)
+        if not a.no_check:
+            from tests.impact_ref import impact_ref
+            t0 = time.perf_counter()
+            want = impact_ref(ge, n, len(incs), on.window_group_node_incident(), a.max_incidents, a.max_hops)
+            r["reference_s"] = time.perf_counter() - t0
+            got = (imp, hops, on.window_group_impact_mask())
+            r["equals_reference"] = bool(all(x.tobytes() == y.tobytes() for x, y in zip(got, want)))
+        if off is not None:
+            r["flush_view_k22_off_ms"] = med(t_off)
+            r["k22_cost_ms"] = r["flush_view_k22_on_ms"]["median"] - r["flush_view_k22_off_ms"]["median"]
+        res[phase] = r
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
