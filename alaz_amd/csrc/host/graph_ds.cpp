@@ -51,6 +51,8 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->window_group_quantile_trend = reinterpret_cast<decltype(o->window_group_quantile_trend)>(dlsym(dl, "sg_window_group_quantile_trend"));
     o->window_group_node_quantile_trend = reinterpret_cast<decltype(o->window_group_node_quantile_trend)>(dlsym(dl, "sg_window_group_node_quantile_trend"));
     o->window_group_nodes_top_tail = reinterpret_cast<decltype(o->window_group_nodes_top_tail)>(dlsym(dl, "sg_window_group_nodes_top_tail"));
+    o->set_traffic_trend = reinterpret_cast<decltype(o->set_traffic_trend)>(dlsym(dl, "sg_set_traffic_trend"));   // optional (K23)
+    o->window_group_nodes_top_traffic = reinterpret_cast<decltype(o->window_group_nodes_top_traffic)>(dlsym(dl, "sg_window_group_nodes_top_traffic"));
 #undef SG_SYM
     return true;
 }
@@ -491,6 +493,15 @@ long GraphDS::WorkloadEdgeTailTrends(std::vector<sg_edge_trend>* out) { return T
 long GraphDS::WorkloadTailTrends(std::vector<sg_node_trend>* out) { return TrendRows(api_.window_group_node_quantile_trend, out); }
 long GraphDS::WorkloadTailTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
     return WorkloadNodesTopBy(api_.window_group_nodes_top_tail, by, k, min_value, out, index);
+}
+// ---- the traffic baselines (K23) ----
+int GraphDS::SetTrafficTrend(uint32_t spaces, const sg_traffic_params* p) {
+    if (!api_.set_traffic_trend) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_traffic_trend(h_, spaces, p);
+}
+long GraphDS::WorkloadTrafficTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
+    return WorkloadNodesTopBy(api_.window_group_nodes_top_traffic, by, k, min_value, out, index);
 }
 
 // the quantiles of the last flushed window, `words` u32 an entity: the count first (no index), then the rows

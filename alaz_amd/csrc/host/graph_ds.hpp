@@ -87,6 +87,9 @@ struct SgApi {
     int (*window_group_quantile_trend)(sg_handle, const uint32_t*, size_t, sg_edge_trend*, size_t, size_t*) = nullptr;
     int (*window_group_node_quantile_trend)(sg_handle, const uint32_t*, size_t, sg_node_trend*, size_t, size_t*) = nullptr;
     int (*window_group_nodes_top_tail)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
+    // optional (K23; absent in an older library): SetTrafficTrend and WorkloadTrafficTop each need the entry they forward to
+    int (*set_traffic_trend)(sg_handle, uint32_t, const sg_traffic_params*) = nullptr;
+    int (*window_group_nodes_top_traffic)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -267,6 +270,13 @@ public:
     long WorkloadEdgeTailTrends(std::vector<sg_edge_trend>* out);
     long WorkloadTailTrends(std::vector<sg_node_trend>* out);
     long WorkloadTailTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
+    // The traffic baselines (K23): each entity's request rate and load against its own past.  SetTrafficTrend forwards
+    // sg_set_traffic_trend (spaces: SG_T_* bits, 0 or p NULL = off; the engine's return code; SG_EINVAL without the entry).
+    // WorkloadTrafficTop: the selection sg_window_group_nodes_top_traffic (`by` = SG_TSEL_SURGE .. SG_TSEL_LOAD_DOWN ORed with
+    // SG_TSEL_IN or SG_TSEL_OUT: SG_TSEL_DROP | SG_TSEL_IN = the workloads whose inbound traffic fell furthest), its rows named as
+    // WorkloadNodesTop names them, their indices in `index` (may be NULL).  Returns the count, or a negative SG_* code.
+    int SetTrafficTrend(uint32_t spaces, const sg_traffic_params* p);
+    long WorkloadTrafficTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }

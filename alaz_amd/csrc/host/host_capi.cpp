@@ -31,6 +31,7 @@ struct MockEngine {
     std::vector<std::array<uint64_t, 4>> k16_ops;      // {1, on, 0, 0} per sg_set_group_nodes, {2, shift, warmup, ttl} per sg_set_group_node_trend (NULL: ~0 in the three), {3, by, k, the bits of min_value} per sg_window_group_nodes_top
     std::vector<std::array<uint64_t, 4>> k17_ops;      // {1, iters, damping_q8, seed} per sg_set_group_rank (NULL: ~0 in the three), {2, k, the bits of min_share, cap} per sg_window_group_rank_top
     std::vector<std::array<uint64_t, 4>> k21_ops;      // {1, spaces, permille, shift (NULL: ~0)} per sg_set_quantile_trend, {2 / 3 / 4, cap, 0, 0} per sg_window_node_quantile_trend / sg_window_group_quantile_trend / sg_window_group_node_quantile_trend, {5, by, k, the bits of min_value} per sg_window_group_nodes_top_tail
+    std::vector<std::array<uint64_t, 4>> k23_ops;      // {1, spaces, shift (NULL: ~0), rate_floor | load_floor_ns << 32} per sg_set_traffic_trend, {2, by, k, the bits of min_value} per sg_window_group_nodes_top_traffic
     std::vector<std::array<uint64_t, 4>> k20_ops;      // {1, spaces, n_q, the first four per-mille 16 bits each} per sg_set_quantiles, {2 / 3 / 4, n_index (~0: no index), cap, 0} per sg_window_node_quantiles / sg_window_group_quantiles / sg_window_group_node_quantiles
     size_t k20_nq = 2;
     std::vector<std::array<uint64_t, 4>> k19_ops;      // {1, quiet_windows, max_tracks, reserved} per sg_set_group_tracks (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incident_tracks, {3, cap, 0, 0} per sg_window_group_tracks_ended
@@ -260,6 +261,23 @@ int m_window_group_nodes_top_tail(sg_handle h, uint32_t by, uint32_t k, float mi
     for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
     return SG_OK;
 }
+// K23's stand-ins: the switch recorded; the traffic selection is K16's with rows 1 and 2 of three
+int m_set_traffic_trend(sg_handle h, uint32_t spaces, const sg_traffic_params* p) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k23_ops.push_back({1u, spaces, p ? p->shift : ~0ull, p ? (uint64_t)p->rate_floor | p->load_floor_ns << 32 : 0u});
+    return spaces > 15u ? SG_EINVAL : SG_OK;
+}
+int m_window_group_nodes_top_traffic(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* idx, size_t cap, size_t* n_sel, size_t* n) {
+    M_LOCK(h);
+    uint32_t bits; std::memcpy(&bits, &min_value, 4);
+    reinterpret_cast<MockEngine*>(h)->k23_ops.push_back({2u, by, k, bits});
+    if (n_sel) *n_sel = 2;
+    if (n) *n = 3;
+    const sg_node_out e[2] = {m_node(SG_MAKE_REF(SG_REF_GROUP, 0), 4, 9, 1, 1, 0.5f), m_node(SG_MAKE_REF(SG_REF_KNOWN, 0), 0, 4, 0, 1, 0.25f)};
+    const uint32_t at[2] = {1u, 2u};
+    for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
+    return SG_OK;
+}
 int m_window_group_node_incident(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
     M_LOCK(h);
     reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({3u, (uint64_t)n_idx, (uint64_t)cap, 0u});
@@ -365,6 +383,7 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.set_quantile_trend = m_set_quantile_trend; c->api.window_node_quantile_trend = m_window_node_quantile_trend;
         c->api.window_group_quantile_trend = m_window_group_quantile_trend; c->api.window_group_node_quantile_trend = m_window_group_node_quantile_trend;
         c->api.window_group_nodes_top_tail = m_window_group_nodes_top_tail;
+        c->api.set_traffic_trend = m_set_traffic_trend; c->api.window_group_nodes_top_traffic = m_window_group_nodes_top_traffic;
         c->api.set_group_incidents = m_set_group_incidents; c->api.window_group_incidents = m_window_group_incidents;
         c->api.window_group_node_incident = m_window_group_node_incident;
         c->api.set_group_impact = m_set_group_impact; c->api.window_group_impact = m_window_group_impact;
@@ -598,6 +617,21 @@ long sgh_graphds_tail_trends(void* g, int which, void* out, size_t cap) {
 long sgh_graphds_workload_tail_top(void* g, uint32_t by, uint32_t k, float min_value, sgh_workload_node* out, uint32_t* index, size_t cap) {
     std::vector<WorkloadNode> v; std::vector<uint32_t> idx;
     const long n = static_cast<HostCtx*>(g)->ds->WorkloadTailTop(by, k, min_value, &v, &idx);
+    if (n < 0) return n;
+    for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_node(v[i], out + i); if (index) index[i] = idx[i]; }
+    return n;
+}
+// the traffic baselines (K23): the switch (on = 0: off; a parameter 0 = its default) and the selection over the workload rows by
+// their traffic rows, as sgh_graphds_workload_nodes_top gives it
+int sgh_graphds_set_traffic_trend(void* g, uint32_t spaces, int on, uint32_t shift, uint32_t warmup, uint32_t ttl, uint64_t max_entries,
+                                  uint32_t rate_floor, uint64_t load_floor_ns) {
+    sg_traffic_params p{}; p.struct_size = sizeof p; p.shift = shift; p.warmup = warmup; p.ttl = ttl; p.max_entries = max_entries;
+    p.rate_floor = rate_floor; p.load_floor_ns = load_floor_ns;
+    return static_cast<HostCtx*>(g)->ds->SetTrafficTrend(spaces, on ? &p : nullptr);
+}
+long sgh_graphds_workload_traffic_top(void* g, uint32_t by, uint32_t k, float min_value, sgh_workload_node* out, uint32_t* index, size_t cap) {
+    std::vector<WorkloadNode> v; std::vector<uint32_t> idx;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadTrafficTop(by, k, min_value, &v, &idx);
     if (n < 0) return n;
     for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_node(v[i], out + i); if (index) index[i] = idx[i]; }
     return n;
@@ -920,6 +954,14 @@ size_t sgh_mock_k21_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k21_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k21_ops[i].data(), 32);
     return m->k21_ops.size();
+}
+size_t sgh_mock_k23_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k23_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k23_ops[i].data(), 32);
+    return m->k23_ops.size();
 }
 size_t sgh_mock_k20_ops(void* g, uint64_t* out4, size_t cap) {
     auto* c = static_cast<HostCtx*>(g);

@@ -33,6 +33,7 @@
 #include "sg_group.h"
 #include "sg_group_trend.h"
 #include "sg_group_nodes.h"
+#include "sg_traffic_trend.h"
 #include "sg_group_rank.h"
 #include "sg_group_incident.h"
 #include "sg_group_impact.h"
@@ -276,6 +277,11 @@ struct sg_engine {
     // slot's quantile table), allocated at sg_set_quantile_trend (sg_plan.hpp plan_quantile_trend), freed with its K20 space and by
     // any sg_set_quantiles
     struct QuantTrend { u32 qi = 0; Baseline<sg_node_trend> nodes; Baseline<sg_edge_trend> groups; Baseline<sg_node_trend> workloads; } qtr;
+    // K23, the traffic baselines (sg_traffic_trend.h): per requested space a Baseline of its own fed the request count and the busy
+    // time, allocated at sg_set_traffic_trend (sg_plan.hpp plan_traffic_trend), each freed with the rows of its space.  The floors
+    // are the stage's (rate_floor, load_floor_ns as the walk gets them), not sg_trend_params'.
+    struct Traffic { double lat_floor = 0, err_floor = 0; Baseline<sg_edge_trend> edges; Baseline<sg_node_trend> nodes; Baseline<sg_edge_trend> groups;
+                     Baseline<sg_node_trend> workloads; } trf;
 };
 
 namespace {
@@ -836,6 +842,27 @@ NodeSpace tail_workload_space(sg_engine* e) {
     ns.trend = &e->qtr.workloads; ns.trend_w = kQuantTrendWords[2]; ns.sel_w = "workload tail selection";
     return ns;
 }
+// K23's words by space (bit order: edges, nodes, group edges, workloads), and the spaces as the traffic baselines see them: the
+// space with the traffic baseline as its baseline, so that the mean baselines' readbacks serve the traffic rows as they are.  The
+// edge spaces have no vanished list here (van = null: nothing of K23 reads it)
+constexpr StageWords kTrafficWords[4] = {
+    {"the edge traffic baseline is off (sg_set_traffic_trend, SG_T_EDGES)", "the edge traffic baseline was off"},
+    {"the node traffic baseline is off (sg_set_traffic_trend, SG_T_NODES)", "the node traffic baseline was off"},
+    {"the group traffic baseline is off (sg_set_traffic_trend, SG_T_GROUPS)", "the group traffic baseline was off"},
+    {"the workload traffic baseline is off (sg_set_traffic_trend, SG_T_GROUP_NODES)", "the workload traffic baseline was off"}};
+enum { kTEdges = 0, kTNodes = 1, kTGroups = 2, kTWorkloads = 3 };
+NodeSpace traffic_node_space(sg_engine* e) {
+    NodeSpace ns = node_space(e);
+    ns.trend = &e->trf.nodes; ns.trend_w = kTrafficWords[kTNodes]; ns.sel_w = "node traffic selection";
+    return ns;
+}
+NodeSpace traffic_workload_space(sg_engine* e) {
+    NodeSpace ns = workload_space(e);
+    ns.trend = &e->trf.workloads; ns.trend_w = kTrafficWords[kTWorkloads]; ns.sel_w = "workload traffic selection";
+    return ns;
+}
+EdgeSpace traffic_edge_space(sg_engine* e) { return {&e->trf.edges, nullptr, kTrafficWords[kTEdges], kVanishedWords, node_space}; }
+EdgeSpace traffic_group_edge_space(sg_engine* e) { return {&e->trf.groups, nullptr, kTrafficWords[kTGroups], kGroupVanishedWords, workload_space}; }
 
 // ---- K8, the per-edge baselines (engine lock held) -----------------------------------------------------------------------------
 static_assert(sizeof(KcScratch) <= sgplan::kPrepareLds, "a folded close's prepare workgroup lays KcScratch over pass B's dynamic LDS");
@@ -1336,6 +1363,49 @@ int launch_group_tail(sg_engine* e, hipStream_t s) {
     a.b.groups = e->grp.rows[e->cur]; a.b.count = e->grp.count[e->cur]; a.b.max_edges = std::max<u64>(e->cfg.max_edges, 1); a.b.out = t.rows[e->cur];
     return launch_tail(e, t, kQGroups, s, a, k21_gcount, k21_gwrite);
 }
+// ---- K23, the traffic baselines (engine lock held) ----------------------------------------------------------------------------------
+// enqueue the update of traffic baseline t by the window in slot cur on stream s, behind the rows of its space on the same stream:
+// a (filled by the caller as the space's mean baseline fills it; ta the TrendArgs inside it) gets the stage's floors; K8's three
+// launches
+template <class Row, class Args>
+int launch_traffic(sg_engine* e, sg_engine::Baseline<Row>& t, hipStream_t s, Args& a, TrendArgs& ta, void (*count)(Args), void (*write)(Args)) {
+    ta.lat_floor = e->trf.lat_floor; ta.err_floor = e->trf.err_floor;
+    if (const int rc = enqueue_baseline(e, t, s, [&] {
+            hipLaunchKernelGGL(count, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k8_scan, dim3(1), dim3(K8_SCAN_THREADS), 0, s, ta, t.plan.wgs);
+            hipLaunchKernelGGL(write, dim3(t.plan.wgs), dim3(K8_THREADS), 0, s, a);
+        })) return rc;
+    t.valid[e->cur] = 1;
+    return SG_OK;
+}
+// over the window's rows, K8's arguments as launch_trend fills them
+int launch_edge_traffic(sg_engine* e, hipStream_t s) {
+    sg_engine::WinSlot& w = work(e);
+    sg_engine::Baseline<sg_edge_trend>& t = *traffic_edge_space(e).trend;
+    TrendArgs a = baseline_args(w, t);
+    a.rows = w.d.rows; a.max_edges = e->cfg.max_edges; a.out = t.rows[e->cur];
+    return launch_traffic(e, t, s, a, a, k23_ecount, k23_ewrite);
+}
+// over a node space (ns: traffic_node_space / traffic_workload_space), K10's arguments as launch_node_trend fills them
+int launch_node_traffic(sg_engine* e, const NodeSpace& ns, hipStream_t s, void (*count)(NodeTrendArgs), void (*write)(NodeTrendArgs)) {
+    sg_engine::Baseline<sg_node_trend>& t = *ns.trend;
+    NodeTrendArgs a{};
+    a.t = baseline_args(work(e), t);
+    a.nodes = ns.roll->rows[e->cur]; a.count = ns.roll->count[e->cur]; a.ncap = ns.cap; a.out = t.rows[e->cur];
+    return launch_traffic(e, t, s, a, a.t, count, write);
+}
+// over the group edges, K15's arguments as launch_group_trend fills them
+int launch_group_traffic(sg_engine* e, hipStream_t s) {
+    sg_engine::Baseline<sg_edge_trend>& t = *traffic_group_edge_space(e).trend;
+    GroupTrendArgs a{};
+    a.t = baseline_args(work(e), t);
+    a.groups = e->grp.rows[e->cur]; a.count = e->grp.count[e->cur]; a.max_edges = std::max<u64>(e->cfg.max_edges, 1); a.out = t.rows[e->cur];
+    return launch_traffic(e, t, s, a, a.t, k23_gcount, k23_gwrite);
+}
+void free_traffic(sg_engine* e, int k) {
+    if (k == kTEdges || k == kTGroups) free_baseline(k == kTEdges ? e->trf.edges : e->trf.groups);
+    else free_baseline(k == kTNodes ? e->trf.nodes : e->trf.workloads);
+}
 void free_quantile_trend(sg_engine* e, int k) {
     if (k == kQGroups) free_baseline(e->qtr.groups);
     else free_baseline(k == kQNodes ? e->qtr.nodes : e->qtr.workloads);
@@ -1356,6 +1426,7 @@ void free_idxsel(sg_engine::IdxSel<Row>& s) {
     s = sg_engine::IdxSel<Row>{};
 }
 void free_group_nodes(sg_engine* e) {
+    free_traffic(e, kTWorkloads);                                     // (the traffic baseline reads the workload rows)
     free_quantiles(e, kQWorkloads);
     free_group_incidents(e);
     free_group_rank(e);
@@ -1366,6 +1437,7 @@ void free_group_nodes(sg_engine* e) {
 
 void free_groups(sg_engine* e) {
     free_group_nodes(e);
+    free_traffic(e, kTGroups);                                        // (the traffic baseline reads the group edges)
     free_quantiles(e, kQGroups);
     free_edge_trend(group_edge_space(e));
     sg_engine::Groups& x = e->grp;
@@ -1381,6 +1453,7 @@ void free_incidents(sg_engine* e) {
 }
 
 void free_nodes(sg_engine* e) {
+    free_traffic(e, kTNodes);                                         // (the traffic baseline reads the node rows)
     free_quantiles(e, kQNodes);
     free_incidents(e);
     free_rank(e);
@@ -1412,10 +1485,12 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     // K8 right behind K5: every pipeline scores here.  The rows, the counters and the outbound-IP list survive K5's fused reset and
     // the separate one (sg_k5.h, sg_k3.h k_reset_window), and the next window's K1 queues behind K8 on this stream.
     if (e->trend.on) { const int rc = launch_trend(e, s); if (rc) return rc; }
+    if (e->trf.edges.on) { if (const int rc = launch_edge_traffic(e, s)) return rc; }   // K23 behind K5: the rows, the counters, the outbound IPs
     // K9 behind them: it reads the rows and the window counters only; K10 behind K9: the node rows, their count, the outbound IPs
     if (e->nodes.on) {
         if (const int rc = launch_nodes(e, s)) return rc;
         if (e->ntrend.on) { if (const int rc = launch_node_trend(e, node_space(e), s, k10_count, k10_write)) return rc; }
+        if (e->trf.nodes.on) { if (const int rc = launch_node_traffic(e, traffic_node_space(e), s, k23_ncount, k23_nwrite)) return rc; }   // K23 behind K9: the node rows, their count
         if (e->rank.on) { if (const int rc = launch_rank(e, s)) return rc; }   // K11 behind K9: the rows, the counters, the node rows and their count
         if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
         if (e->trk.on) { if (const int rc = launch_node_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
@@ -1425,11 +1500,13 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     if (e->grp.on) {                                                 // K14 behind K5: the rows and the window counters only, whatever else is on
         if (const int rc = launch_groups(e, s)) return rc;
         if (e->gtrend.on) { if (const int rc = launch_group_trend(e, s)) return rc; }   // K15 behind K14: the group edges, their count, the outbound IPs
+        if (e->trf.groups.on) { if (const int rc = launch_group_traffic(e, s)) return rc; }   // K23 behind K14: the same
         if (e->qnt.sp[kQGroups].on) { if (const int rc = launch_quantiles(e, kQGroups, s)) return rc; }   // K20 behind K14: the histograms, perm, row_group, the group edges
         if (e->qtr.groups.on) { if (const int rc = launch_group_tail(e, s)) return rc; }   // K21 behind K20: the group edges, the quantiles
         if (e->gnodes.on) {                                          // K16 behind K14: the group edges and their count; its baseline behind it
             if (const int rc = launch_group_nodes(e, s)) return rc;
             if (e->gntrend.on) { if (const int rc = launch_node_trend(e, workload_space(e), s, k16_tcount, k16_twrite)) return rc; }
+            if (e->trf.workloads.on) { if (const int rc = launch_node_traffic(e, traffic_workload_space(e), s, k23_wcount, k23_wwrite)) return rc; }   // K23 behind K16: the workload rows, their count
             if (e->grank.on) { if (const int rc = launch_group_rank(e, s)) return rc; }   // K17 behind K16 and its baseline: the group edges, the workload rows and their count
             if (e->ginc.on) { if (const int rc = launch_group_incidents(e, s)) return rc; }   // K18 behind K15, K16 and K17: the group trend rows, the workload rows, the rank rows
             if (e->gtrk.on) { if (const int rc = launch_group_tracks(e, s)) return rc; }   // K19 behind K18: the workload rows, the incident rows, the incident per workload row
@@ -1726,13 +1803,14 @@ int node_top_host(sg_engine* e, const NodeSpace& ns, L launch, sg_node_out* out,
 }
 // over the group edges (sg_window_groups_top): the indices alone are selected, then the selected group edges are gathered through
 // the staging of SG_SELECT_MAX_K, in pieces when there are more of them than it holds (k = 0)
-int group_top_host(sg_engine* e, const sg_engine::Baseline<sg_edge_trend>& t, u32 by, u32 k, float min_value, sg_group_edge* out,
-                   uint32_t* group_index, size_t cap, size_t* n_selected, size_t* n_groups) {
+// launch(stage, d_n) enqueues the selection of the indices on the read stream (launch_group_select, or K23's by a traffic row)
+template <class L>
+int group_top_host_by(sg_engine* e, L launch, sg_group_edge* out, uint32_t* group_index, size_t cap, size_t* n_selected, size_t* n_groups) {
     if (const int rc = gsel_reserve(e)) return rc;
     const SelView<sg_group_edge> v = group_sel_view(e, e->cur);
     sg_engine::IdxSel<sg_group_edge>& s = *v.sel;
     const u64 stage = std::min<u64>(cap, v.cap);
-    return index_top_host(e, v, stage, [&] { return launch_group_select(e, t, e->rd_stream, e->cur, by, k, min_value, nullptr, nullptr, stage, s.n); }, [&](size_t take) {
+    return index_top_host(e, v, stage, [&] { return launch(stage, s.n); }, [&](size_t take) {
         for (size_t o = 0; out && o < take; o += (size_t)s.stage_rows) {
             const size_t piece = std::min<size_t>((size_t)s.stage_rows, take - o);
             hipLaunchKernelGGL(k_gather<sg_group_edge>, dim3((unsigned)((piece + 255) / 256)), dim3(256), 0, e->rd_stream, v.rows,
@@ -1743,6 +1821,23 @@ int group_top_host(sg_engine* e, const sg_engine::Baseline<sg_edge_trend>& t, u3
         }
         return (int)SG_OK;
     }, group_index, n_selected, n_groups);
+}
+int group_top_host(sg_engine* e, const sg_engine::Baseline<sg_edge_trend>& t, u32 by, u32 k, float min_value, sg_group_edge* out,
+                   uint32_t* group_index, size_t cap, size_t* n_selected, size_t* n_groups) {
+    return group_top_host_by(e, [&](u64 stage, u64* d_n) { return launch_group_select(e, t, e->rd_stream, e->cur, by, k, min_value, nullptr, nullptr, stage, d_n); },
+                             out, group_index, cap, n_selected, n_groups);
+}
+// over the rows of v by word `word` (its sign flipped: neg) of the window's traffic rows of baseline t (K23; behind its update):
+// k23_keys reads the traffic rows and the row count alone
+template <class Row, class TRow>
+int launch_traffic_select(sg_engine* e, const SelView<Row>& v, const sg_engine::Baseline<TRow>& t, hipStream_t st, int slot, u32 word, u32 neg, u32 k,
+                          float min_value, Row* d_out, u32* d_index, u64 cap, u64* d_n) {
+    return launch_index_select(e, v, st, k, min_value, d_out, d_index, cap, d_n, [&](const SelArgs& a, u32 wgs) {
+        if (t.pending) HIP_TRY(e, hipStreamWaitEvent(st, t.ev, 0));
+        hipLaunchKernelGGL(k23_keys, dim3(wgs), dim3(K7_THREADS), 0, st, a, v.count, reinterpret_cast<const u32*>(t.rows[slot]), (u32)(sizeof(TRow) / 4),
+                           word, neg, v.sel->ctr);
+        return (int)SG_OK;
+    }, [](const SelArgs&, dim3) {});
 }
 
 // ---- the baselines' and the per-window buffers' shared host code (engine lock held) -----------------------------------------
@@ -2424,6 +2519,7 @@ int sg_destroy(sg_handle e) {
     if (e->sel.h_n) hipHostFree(e->sel.h_n);
     if (e->sel.ev) hipEventDestroy(e->sel.ev);
     free_edge_trend(edge_space(e));
+    free_traffic(e, kTEdges);
     free_nodes(e);
     free_groups(e);
     free_idxsel(e->nsel);
@@ -4129,6 +4225,167 @@ int sg_window_group_nodes_top_tail(sg_handle e, uint32_t by, uint32_t k, float m
     if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     return nodes_top_tail(e, tail_workload_space(e), kQWorkloads, "sg_window_group_nodes_top_tail", by, k, min_value, out, node_index, cap, n_selected, n_nodes);
+}
+
+// ---- K23, the traffic baselines: the C ABI --------------------------------------------------------------------------------------------
+namespace {
+static_assert(sizeof(sg_traffic_params) == 40 && sizeof(sg_edge_trend) == 16 && sizeof(sg_node_trend) == 32, "k23_keys reads 4 or 8 words a traffic row");
+int traffic_space(uint32_t space) {
+    return space == SG_T_EDGES ? kTEdges : space == SG_T_NODES ? kTNodes : space == SG_T_GROUPS ? kTGroups : space == SG_T_GROUP_NODES ? kTWorkloads : -1;
+}
+int bad_traffic_space(sg_engine* e, const char* call) {
+    e->err = std::string(call) + ": space is one of SG_T_EDGES, SG_T_NODES, SG_T_GROUPS, SG_T_GROUP_NODES";
+    return SG_EINVAL;
+}
+// the switch: off (spaces 0 or p NULL), or the requested spaces on with empty baselines; a refused call leaves the stage as it was
+int traffic_set(sg_engine* e, u32 spaces, const sg_traffic_params* p) {
+    const char* call = "sg_set_traffic_trend";
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    auto release = [e] { for (int k = 0; k < 4; k++) free_traffic(e, k); };
+    if (!spaces || !p) { release(); return SG_OK; }
+    const u32 on = SG_T_EDGES | (e->nodes.on ? SG_T_NODES : 0u) | (e->grp.on ? SG_T_GROUPS : 0u) | (e->gnodes.on ? SG_T_GROUP_NODES : 0u);
+    const u32 slots = (u32)e->slots.size();
+    sgplan::TrafficPlan P;
+    const int prc = sgplan::plan_traffic_trend(*p, spaces, on, e->cfg.max_edges, e->plan.ncap, e->gnodes.on ? e->gnodes.plan.nc : 0, slots, &P);
+    if (prc == SG_ESTATE) {
+        const StageWords* const rows[4] = {nullptr, &kNodesWords, &kGroupsWords, &kGroupNodesWords};
+        for (int k = 1; k < 4; k++) if ((spaces & ~on) >> k & 1u) { e->err = std::string(call) + ": " + rows[k]->off; break; }
+        return SG_ESTATE;
+    }
+    if (prc) { e->err = std::string(call) + ": unknown space bits or bad parameters"; return SG_EINVAL; }
+    release();
+    e->trf.lat_floor = P.lat_floor; e->trf.err_floor = P.err_floor;
+    int rc = SG_OK;
+    auto on_space = [&](auto& t, int k) {
+        if (rc || !(spaces >> k & 1u)) return;
+        rc = baseline_on(e, t, P.params[k], P.sp[k], call, release);
+        if (!rc) t.valid.assign(slots, 0);
+    };
+    on_space(e->trf.edges, kTEdges); on_space(e->trf.nodes, kTNodes); on_space(e->trf.groups, kTGroups); on_space(e->trf.workloads, kTWorkloads);
+    if (rc) { const std::string msg = e->err; release(); e->err = msg; }
+    return rc;
+}
+// the pod-edge rows, as sg_window_trend reads K8's (neither an open flush nor valid is checked: K8's preconditions)
+int edge_traffic_read(sg_engine* e, const EdgeSpace& es, const char* call, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
+    if (!es.trend->on) { e->err = std::string(call) + ": " + es.trend_w.off; return SG_ESTATE; }
+    const size_t E = (size_t)e->h_ctr[C_N_EDGES];                      // of the last read window
+    const std::string beyond = std::string(call) + ": a row index beyond the window's edges";
+    return baseline_rows(e, *es.trend, E, row_index, n_index, out, cap, n, beyond.c_str());
+}
+int traffic_buffer(sg_engine* e, int k, const char* call, void** d_rows) {
+    if (k == kTNodes || k == kTWorkloads) return node_trend_buffer(e, k == kTNodes ? traffic_node_space(e) : traffic_workload_space(e), call, d_rows);
+    const EdgeSpace es = k == kTEdges ? traffic_edge_space(e) : traffic_group_edge_space(e);
+    if (k == kTEdges) {                                               // (as sg_window_trend_buffer: the edge rows keep no valid to refuse by)
+        if (!es.trend->on) { e->err = std::string(call) + ": " + es.trend_w.off; return SG_ESTATE; }
+        *d_rows = es.trend->rows[ran_slot(e)];
+        return SG_OK;
+    }
+    int slot;
+    if (const int rc = stage_slot(e, *es.trend, call, es.trend_w, &slot)) return rc;
+    *d_rows = es.trend->rows[slot];
+    return SG_OK;
+}
+int traffic_entries(sg_engine* e, int k, const char* call, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (k == kTEdges || k == kTGroups) return baseline_entries(e, k == kTEdges ? e->trf.edges : e->trf.groups, call, kTrafficWords[k], out, cap, n);
+    return baseline_entries(e, k == kTNodes ? e->trf.nodes : e->trf.workloads, call, kTrafficWords[k], out, cap, n);
+}
+int traffic_stats(sg_engine* e, int k, const char* call, sg_trend_stats* out) {
+    if (k == kTEdges || k == kTGroups) return baseline_stats(e, k == kTEdges ? e->trf.edges : e->trf.groups, call, kTrafficWords[k], out);
+    return baseline_stats(e, k == kTNodes ? e->trf.nodes : e->trf.workloads, call, kTrafficWords[k], out);
+}
+// a traffic key: SG_TSEL_SURGE .. SG_TSEL_LOAD_DOWN, on a node-shaped space (sided) ORed with exactly one of SG_TSEL_IN / SG_TSEL_OUT,
+// on the group edges with neither -> the word of the traffic row (lat_dev / err_dev of the side) and whether its sign flips
+bool traffic_key(u32 by, bool sided, u32* word, u32* neg) {
+    const u32 side = by & (SG_TSEL_IN | SG_TSEL_OUT), dir = by & 3u;
+    if ((by & ~15u) || (sided ? side != SG_TSEL_IN && side != SG_TSEL_OUT : side != 0u)) return false;
+    *word = (side == SG_TSEL_OUT ? 2u : 0u) + (dir >> 1);
+    *neg = dir & 1u;
+    return true;
+}
+int nodes_top_traffic(sg_engine* e, const NodeSpace& ns, const char* call, u32 by, u32 k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
+                      size_t* n_selected, size_t* n_nodes) {
+    u32 word, neg;
+    if (!traffic_key(by, true, &word, &neg)) { e->err = std::string(ns.sel_w) + ": by is a key of SG_TSEL_* ORed with SG_TSEL_IN or SG_TSEL_OUT"; return SG_EINVAL; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (const int rc = check_nsel(e, ns, SG_NSEL_IN_LAT_DEV, e->cur)) return rc;   // (a trend key: the rows and the traffic baseline on, the window has both)
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    return node_top_host(e, ns, [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
+        return launch_traffic_select(e, node_sel_view(ns, e->cur), *ns.trend, e->rd_stream, e->cur, word, neg, k, min_value, d_out, (u32*)nullptr, stage, d_n);
+    }, out, nullptr, nullptr, node_index, cap, n_selected, n_nodes);
+}
+int groups_top_traffic(sg_engine* e, const EdgeSpace& es, const char* call, u32 by, u32 k, float min_value, sg_group_edge* out, uint32_t* group_index,
+                       size_t cap, size_t* n_selected, size_t* n_groups) {
+    u32 word, neg;
+    if (!traffic_key(by, false, &word, &neg)) { e->err = "group traffic selection: by is SG_TSEL_SURGE, SG_TSEL_DROP, SG_TSEL_LOAD_UP or SG_TSEL_LOAD_DOWN"; return SG_EINVAL; }
+    if (const int rc = check_gsel(e, *es.trend, es.trend_w, "group traffic selection", SG_SEL_LAT_DEV, e->cur)) return rc;
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    return group_top_host_by(e, [&](u64 stage, u64* d_n) {
+        return launch_traffic_select(e, group_sel_view(e, e->cur), *es.trend, e->rd_stream, e->cur, word, neg, k, min_value, (sg_group_edge*)nullptr,
+                                     (u32*)nullptr, stage, d_n);
+    }, out, group_index, cap, n_selected, n_groups);
+}
+}  // namespace
+int sg_set_traffic_trend(sg_handle e, uint32_t spaces, const sg_traffic_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    return traffic_set(e, spaces, p);
+}
+int sg_window_traffic(sg_handle e, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return edge_traffic_read(e, traffic_edge_space(e), "sg_window_traffic", row_index, n_index, out, cap, n);
+}
+int sg_window_node_traffic(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return node_trend_read(e, traffic_node_space(e), "sg_window_node_traffic", node_index, n_index, out, cap, n);
+}
+int sg_window_group_traffic(sg_handle e, const uint32_t* group_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const EdgeSpace es = traffic_group_edge_space(e);
+    return group_trend_read(e, *es.trend, "sg_window_group_traffic", es.trend_w, group_index, n_index, out, cap, n);
+}
+int sg_window_group_node_traffic(sg_handle e, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return node_trend_read(e, traffic_workload_space(e), "sg_window_group_node_traffic", node_index, n_index, out, cap, n);
+}
+int sg_window_traffic_buffer(sg_handle e, uint32_t space, void** d_rows) {
+    if (!e || !d_rows) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = traffic_space(space);
+    return k < 0 ? bad_traffic_space(e, "sg_window_traffic_buffer") : traffic_buffer(e, k, "sg_window_traffic_buffer", d_rows);
+}
+int sg_traffic_trend_entries(sg_handle e, uint32_t space, sg_trend_entry* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = traffic_space(space);
+    return k < 0 ? bad_traffic_space(e, "sg_traffic_trend_entries") : traffic_entries(e, k, "sg_traffic_trend_entries", out, cap, n);
+}
+int sg_traffic_trend_stats_get(sg_handle e, uint32_t space, sg_trend_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = traffic_space(space);
+    return k < 0 ? bad_traffic_space(e, "sg_traffic_trend_stats_get") : traffic_stats(e, k, "sg_traffic_trend_stats_get", out);
+}
+int sg_window_nodes_top_traffic(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
+                                size_t* n_selected, size_t* n_nodes) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return nodes_top_traffic(e, traffic_node_space(e), "sg_window_nodes_top_traffic", by, k, min_value, out, node_index, cap, n_selected, n_nodes);
+}
+int sg_window_groups_top_traffic(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap,
+                                 size_t* n_selected, size_t* n_groups) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return groups_top_traffic(e, traffic_group_edge_space(e), "sg_window_groups_top_traffic", by, k, min_value, out, group_index, cap, n_selected, n_groups);
+}
+int sg_window_group_nodes_top_traffic(sg_handle e, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap,
+                                      size_t* n_selected, size_t* n_nodes) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return nodes_top_traffic(e, traffic_workload_space(e), "sg_window_group_nodes_top_traffic", by, k, min_value, out, node_index, cap, n_selected, n_nodes);
 }
 
 int sg_window_hist(sg_handle e, uint32_t* bins, size_t cap_rows, size_t* n) {

@@ -1469,6 +1469,44 @@ inline int plan_quantile_trend(const sg_trend_params& p, u32 spaces, u32 on, u32
     return SG_OK;
 }
 
+// K23, the traffic baselines (sg_traffic_trend.h): per requested space the baseline its mean baseline gets — K8's plan over the
+// window's rows, K10's over the node rows, K15's over the group edges, K16's over the workload rows: the same capacity default,
+// grid, scratch and per-slot row table — fed the request count and the busy time.  sg_set_traffic_trend allocates it, never
+// sg_create.  The spaces in bit order: 0 edges, 1 nodes, 2 group edges, 3 workloads.
+constexpr u32 kTrafficSpaces = 4, kTrafficRateFloor = 8;
+constexpr u64 kTrafficLoadFloorNs = 1000000, kTrafficMaxLoadFloorNs = 1ull << 52;
+struct TrafficPlan {
+    u32 spaces = 0;               // the SG_T_* bits that are on
+    double lat_floor = 0, err_floor = 0;   // the floors as the walk gets them: 1000.0 * rate_floor, (double) load_floor_ns
+    u32 rate_floor = 0; u64 load_floor_ns = 0;   // resolved
+    sg_trend_params params[kTrafficSpaces] = {};   // the resolved walk parameters of each space (max_entries defaults differ; the floors are not these)
+    TrendPlan sp[kTrafficSpaces];   // a device block each
+    u64 total_bytes = 0;          // of the spaces that are on
+};
+// spaces: the SG_T_* bits asked for, all of them among `on` (the spaces whose rows are on; the edges always: else SG_ESTATE);
+// max_edges, ncap, nc: the capacities the four mean baselines are planned over.  SG_OK and *out, SG_EINVAL or SG_ESTATE
+inline int plan_traffic_trend(const sg_traffic_params& p, u32 spaces, u32 on, u64 max_edges, u32 ncap, u32 nc, u32 slots, TrafficPlan* out) {
+    if (!spaces || (spaces & ~(SG_T_EDGES | SG_T_NODES | SG_T_GROUPS | SG_T_GROUP_NODES))) return SG_EINVAL;
+    if (p.struct_size != sizeof(sg_traffic_params) || p.reserved != 0 || p.load_floor_ns > kTrafficMaxLoadFloorNs) return SG_EINVAL;
+    sg_trend_params t{};
+    t.struct_size = sizeof(sg_trend_params); t.shift = p.shift; t.warmup = p.warmup; t.ttl = p.ttl; t.max_entries = p.max_entries;
+    TrafficPlan q;
+    if (check_trend(t, max_edges, &q.params[0]) || check_node_trend(t, ncap, &q.params[1]) || check_group_trend(t, max_edges, &q.params[2]) ||
+        check_group_node_trend(t, nc, &q.params[3])) return SG_EINVAL;
+    if (spaces & ~on) return SG_ESTATE;
+    q.spaces = spaces;
+    q.rate_floor = p.rate_floor ? p.rate_floor : kTrafficRateFloor;
+    q.load_floor_ns = p.load_floor_ns ? p.load_floor_ns : kTrafficLoadFloorNs;
+    q.lat_floor = 1000.0 * (double)q.rate_floor; q.err_floor = (double)q.load_floor_ns;
+    if (spaces & SG_T_EDGES) q.sp[0] = plan_trend(max_edges, slots, q.params[0]);
+    if (spaces & SG_T_NODES) q.sp[1] = plan_node_trend(ncap, slots, q.params[1]);
+    if (spaces & SG_T_GROUPS) q.sp[2] = plan_group_trend(max_edges, slots, q.params[2]);
+    if (spaces & SG_T_GROUP_NODES) q.sp[3] = plan_group_node_trend(nc, slots, q.params[3]);
+    for (u32 k = 0; k < kTrafficSpaces; k++) q.total_bytes += q.sp[k].total_bytes;
+    *out = q;
+    return SG_OK;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

@@ -90,6 +90,13 @@ TREND_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, lat_floor_ns=100
 #: SG_Q_*: the spaces of the latency percentiles (K20), and SG_Q_MAX, the quantiles per entity and side at most
 Q_SPACES = dict(nodes=1, groups=2, group_nodes=4)
 Q_MAX = 8
+#: SG_T_*: the spaces of the traffic baselines (K23); SG_TSEL_*: the key of a selection by a traffic row — a direction, on the
+#: node-shaped spaces ORed with a side; sg_traffic_params defaults (a 0 in the struct means the same: rate_floor 8 requests,
+#: load_floor_ns 1 000 000)
+T_SPACES = dict(edges=1, nodes=2, groups=4, group_nodes=8)
+TSEL_BY = dict(surge=0, drop=1, load_up=2, load_down=3)
+TSEL_SIDE = {"in": 4, "out": 8}
+TRAFFIC_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, load_floor_ns=1000000, rate_floor=8)
 #: SG_IMPACT_*: an impact row of the workload impact (K22) is IMPACT_WORDS u64 words, named by IMPACT_FIELDS in word order; the
 #: parameters' limits; SG_NO_HOPS: a workload row no covered incident reaches within max_hops
 IMPACT_WORDS = 8
@@ -142,6 +149,12 @@ class SgStats(C.Structure):
 class SgTrendParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("shift", C.c_uint32), ("warmup", C.c_uint32), ("ttl", C.c_uint32),
                 ("max_entries", C.c_uint64), ("lat_floor_ns", C.c_uint64), ("err_floor", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TrafficParams(C.Structure):
+    """sg_traffic_params (K23); tests/test_traffic_host.py holds its layout to the header with the compiler"""
+    _fields_ = [("struct_size", C.c_uint32), ("shift", C.c_uint32), ("warmup", C.c_uint32), ("ttl", C.c_uint32),
+                ("max_entries", C.c_uint64), ("load_floor_ns", C.c_uint64), ("rate_floor", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class SgVanishedParams(C.Structure):
@@ -302,6 +315,14 @@ def _signatures() -> dict:
         "sg_window_nodes_top_tail": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
         "sg_window_groups_top_tail": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
         "sg_window_group_nodes_top_tail": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_set_traffic_trend": (I, [H, u32, P]),
+        "sg_window_traffic": (I, [H, P, sz, P, sz, Psz]), "sg_window_node_traffic": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_group_traffic": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_node_traffic": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_traffic_buffer": (I, [H, u32, PP]),
+        "sg_traffic_trend_entries": (I, [H, u32, P, sz, Psz]), "sg_traffic_trend_stats_get": (I, [H, u32, P]),
+        "sg_window_nodes_top_traffic": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_groups_top_traffic": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_window_group_nodes_top_traffic": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
     }
 
 
@@ -352,6 +373,8 @@ _STAGES = dict(
                         "workload track"),
     quantile_trend=_Stage("sg_set_quantile_trend", SgTrendParams, TREND_DEFAULTS, "set_quantile_trend(params=None) switches the tail baselines off",
                           "tail trend"),
+    traffic_trend=_Stage("sg_set_traffic_trend", TrafficParams, TRAFFIC_DEFAULTS, "set_traffic_trend(params=None) switches the traffic baselines off",
+                         "traffic trend"),
 )
 
 _lib = None
@@ -1210,6 +1233,88 @@ class ServiceGraph:
         """window_group_nodes_top with the tail rows as the trend source (sg_window_group_nodes_top_tail); by: a key of NSEL_BY."""
         b = self._nby(by)
         return self._top(lambda *a: self._l.sg_window_group_nodes_top_tail(self._h, b, k, min_value, *a),
+                         self._node_cap(k, cap, self._l.sg_window_group_nodes), NODE_DTYPE, np.uint32)
+
+    # ---- traffic baselines (K23): each entity's request rate and load against its own past ----
+    def set_traffic_trend(self, spaces=("nodes",), params: Optional[dict] = (), **kw):
+        """Switch the traffic baselines on (sg_set_traffic_trend): per space ("edges" / "nodes" / "groups" / "group_nodes", or the
+        SG_T_* bits as an int; each but "edges" needs its rows on: set_nodes / set_groups / set_group_nodes) a baseline of the
+        request count and the busy time of every entity side; TRAFFIC_DEFAULTS' parameters as keywords or a dict, max_entries 0 =
+        the default of the mean baseline of each space.  Every call starts empty baselines.  spaces None / 0 or params=None
+        switches the stage off."""
+        bits = 0 if spaces is None else spaces if isinstance(spaces, int) else self._tbits(spaces)
+        self._set_stage("traffic_trend", params, kw, bits)
+
+    @staticmethod
+    def _tbits(spaces) -> int:
+        bits = 0
+        for sp in ([spaces] if isinstance(spaces, str) else spaces):
+            if sp not in T_SPACES:
+                raise ValueError(f"unknown traffic space {sp!r}: one of {sorted(T_SPACES)}")
+            bits |= T_SPACES[sp]
+        return bits
+
+    def _tbit(self, space) -> int:
+        return space if isinstance(space, int) else self._tbits(space)
+
+    @staticmethod
+    def _tby(by, side=None) -> int:
+        """SG_TSEL_*: an int as it is; else a direction of TSEL_BY, with side "in" / "out" (TSEL_SIDE) ORed in"""
+        if isinstance(by, int):
+            return by
+        if by not in TSEL_BY or (side is not None and side not in TSEL_SIDE):
+            raise ValueError(f"unknown traffic key {by!r} / side {side!r}: one of {sorted(TSEL_BY)}, {sorted(TSEL_SIDE)}")
+        return TSEL_BY[by] | (TSEL_SIDE[side] if side is not None else 0)
+
+    def window_traffic(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """TREND_DTYPE traffic rows of the last read window (sg_window_traffic), row k for row k of the window: lat_dev is the RATE
+        deviation, err_dev the LOAD deviation, base_mean_us the baseline rate in requests per window; or the rows at `index`."""
+        return self._window_rows(self._l.sg_window_traffic, TREND_DTYPE, index)
+
+    def window_node_traffic(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """NODE_TREND_DTYPE traffic rows (sg_window_node_traffic), row k for node row k of window_nodes(); or those at `index`."""
+        return self._window_rows(self._l.sg_window_node_traffic, NODE_TREND_DTYPE, index)
+
+    def window_group_traffic(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """TREND_DTYPE traffic rows (sg_window_group_traffic), row k for group edge k of window_groups(); or those at `index`."""
+        return self._window_rows(self._l.sg_window_group_traffic, TREND_DTYPE, index)
+
+    def window_group_node_traffic(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """NODE_TREND_DTYPE traffic rows (sg_window_group_node_traffic), row k for row k of window_group_nodes(); or those at `index`."""
+        return self._window_rows(self._l.sg_window_group_node_traffic, NODE_TREND_DTYPE, index)
+
+    def window_traffic_buffer(self, space) -> int:
+        """device pointer of the traffic rows of one space of the window window_run closed last (sg_window_traffic_buffer)"""
+        bits = self._tbit(space)
+        return self._pointers(lambda h, *a: self._l.sg_window_traffic_buffer(h, bits, *a), 1)[0]
+
+    def traffic_trend_entries(self, space) -> np.ndarray:
+        """the traffic baseline of one space in key order, TREND_ENTRY_DTYPE with the keys of the mean baseline of that space;
+        lat_mean / lat_dev are 1000 x the request count, err_mean / err_dev the busy time in ns (sg_traffic_trend_entries)"""
+        bits = self._tbit(space)
+        return self._counted(lambda h, *a: self._l.sg_traffic_trend_entries(h, bits, *a), TREND_ENTRY_DTYPE)
+
+    def traffic_trend_stats(self, space) -> SgTrendStats:
+        bits = self._tbit(space)
+        return self._stats(lambda h, *a: self._l.sg_traffic_trend_stats_get(h, bits, *a), SgTrendStats)
+
+    def window_nodes_top_traffic(self, k: int, min_value: float = float("-inf"), by="drop", side="in", cap: Optional[int] = None):
+        """(the selected node rows, their indices) by a traffic row (sg_window_nodes_top_traffic): by "surge" / "drop" / "load_up" /
+        "load_down" of side "in" / "out" (or by as the SG_TSEL_* int), the signed value descending, k = 0 every row >= min_value."""
+        b = self._tby(by, side)
+        return self._top(lambda *a: self._l.sg_window_nodes_top_traffic(self._h, b, k, min_value, *a), self._node_cap(k, cap), NODE_DTYPE, np.uint32)
+
+    def window_groups_top_traffic(self, k: int, min_value: float = float("-inf"), by="drop", cap: Optional[int] = None):
+        """(the selected group edges, their indices) by a traffic row (sg_window_groups_top_traffic); by: a direction of TSEL_BY."""
+        b = self._tby(by)
+        cap = (k or self.max_edges) if cap is None else cap
+        return self._top(lambda *a: self._l.sg_window_groups_top_traffic(self._h, b, k, min_value, *a), cap, GROUP_EDGE_DTYPE, np.uint32)
+
+    def window_group_nodes_top_traffic(self, k: int, min_value: float = float("-inf"), by="drop", side="in", cap: Optional[int] = None):
+        """(the selected workload rows, their indices) by a traffic row (sg_window_group_nodes_top_traffic); by, side as
+        window_nodes_top_traffic: "the 20 workloads whose inbound traffic fell furthest" is (20, by="drop", side="in")."""
+        b = self._tby(by, side)
+        return self._top(lambda *a: self._l.sg_window_group_nodes_top_traffic(self._h, b, k, min_value, *a),
                          self._node_cap(k, cap, self._l.sg_window_group_nodes), NODE_DTYPE, np.uint32)
 
     @staticmethod

@@ -150,6 +150,8 @@ def load() -> C.CDLL:
             "sgh_graphds_set_tail_trend": (C.c_int, [P, u32, u32, C.c_int, u32, u32, u32, C.c_uint64]),
             "sgh_graphds_tail_trends": (C.c_long, [P, C.c_int, P, sz]),
             "sgh_graphds_workload_tail_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]), "sgh_mock_k21_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_traffic_trend": (C.c_int, [P, u32, C.c_int, u32, u32, u32, C.c_uint64, u32, C.c_uint64]),
+            "sgh_graphds_workload_traffic_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]), "sgh_mock_k23_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -760,6 +762,31 @@ class GraphDS:
         n = self._l.sgh_mock_k21_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k21_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the traffic baselines (K23) ----
+    def set_traffic_trend(self, spaces: int = 2, on: bool = True, shift: int = 0, warmup: int = 0, ttl: int = 0, max_entries: int = 0,
+                          rate_floor: int = 0, load_floor_ns: int = 0) -> int:
+        """GraphDS::SetTrafficTrend: a baseline of the request rate and the load per space (SG_T_* bits; 0 or on=False: off; a
+        parameter 0 = its default; rc)"""
+        return self._l.sgh_graphds_set_traffic_trend(self._g, spaces, 1 if on else 0, shift, warmup, ttl, max_entries, rate_floor, load_floor_ns)
+
+    def workload_traffic_top(self, by: int, k: int, min_value: float = float("-inf")):
+        """GraphDS::WorkloadTrafficTop: (the selected workload rows as workload_nodes() gives them, their indices) — by = a
+        direction of SG_TSEL_* ORed with SG_TSEL_IN or SG_TSEL_OUT, ranked by the signed traffic deviation"""
+        n = self._l.sgh_graphds_workload_traffic_top(self._g, by, k, min_value, None, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadTrafficTop failed: {n}")
+        out, idx = np.zeros(max(n, 1), dtype=_workload_node_dtype()), np.zeros(max(n, 1), dtype=np.uint32)
+        self._l.sgh_graphds_workload_traffic_top(self._g, by, k, min_value, out.ctypes.data, idx.ctypes.data, n)
+        return out[:n], idx[:n]
+
+    def mock_k23_ops(self) -> np.ndarray:
+        """the stand-in engine's K23 calls in order, four u64 each: (1, spaces, shift or all ones for NULL, rate_floor |
+        load_floor_ns << 32) per sg_set_traffic_trend, (2, by, k, the bits of min_value) per sg_window_group_nodes_top_traffic"""
+        n = self._l.sgh_mock_k23_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k23_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

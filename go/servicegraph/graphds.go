@@ -1910,6 +1910,229 @@ func (g *GraphDS) WindowTailRegressions(by, k uint32, minValue float32) ([]Workl
 	return goWorkloadNodes(ns), trends, index, nil
 }
 
+// ---- traffic baselines (K23) ---------------------------------------------------------------------------------------------
+
+// The spaces of the traffic baselines (SG_T_*), the directions of a selection by a traffic row and the side they are ORed with on
+// services and workloads (SG_TSEL_*).
+const (
+	TrafficEdges     = uint32(C.SG_T_EDGES)
+	TrafficNodes     = uint32(C.SG_T_NODES)
+	TrafficWorkEdges = uint32(C.SG_T_GROUPS)
+	TrafficWorkloads = uint32(C.SG_T_GROUP_NODES)
+
+	TrafficSurge    = uint32(C.SG_TSEL_SURGE)
+	TrafficDrop     = uint32(C.SG_TSEL_DROP)
+	TrafficLoadUp   = uint32(C.SG_TSEL_LOAD_UP)
+	TrafficLoadDown = uint32(C.SG_TSEL_LOAD_DOWN)
+	TrafficIn       = uint32(C.SG_TSEL_IN)
+	TrafficOut      = uint32(C.SG_TSEL_OUT)
+)
+
+// TrafficStats is the running statistics of one traffic baseline (sg_trend_stats).
+type TrafficStats struct {
+	Windows, Entries, Inserted, Expired, Dropped uint64
+}
+
+// SetTrafficTrend switches the traffic baselines on for the spaces given (TrafficEdges needs nothing, TrafficNodes SetNodes,
+// TrafficWorkEdges SetGroups, TrafficWorkloads SetWorkloadNodes): an exponentially weighted baseline of HOW MUCH traffic each edge,
+// service side, workload edge and workload side carries — its requests per window and its busy time — with the keys of the mean
+// baseline of that space, so a workload's history survives a rollout.  A partial drop or a surge shows here while latency and
+// error ratio stay calm; windows are assumed to be of equal length.  A 0 is the parameter's default (shift 4, warmup 4, ttl 64,
+// maxEntries as the mean baseline of the space, rateFloor 8 requests, loadFloorNs 1 ms).  Every call starts empty baselines.
+func (g *GraphDS) SetTrafficTrend(spaces, shift, warmup, ttl uint32, maxEntries uint64, rateFloor uint32, loadFloorNs uint64) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var tp C.sg_traffic_params
+	tp.struct_size = C.uint32_t(unsafe.Sizeof(tp))
+	tp.shift, tp.warmup, tp.ttl, tp.max_entries = C.uint32_t(shift), C.uint32_t(warmup), C.uint32_t(ttl), C.uint64_t(maxEntries)
+	tp.rate_floor, tp.load_floor_ns = C.uint32_t(rateFloor), C.uint64_t(loadFloorNs)
+	if rc := C.sg_set_traffic_trend(g.h, C.uint32_t(spaces), &tp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_traffic_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+// ClearTrafficTrend switches the traffic baselines off and frees them.
+func (g *GraphDS) ClearTrafficTrend() error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	if rc := C.sg_set_traffic_trend(g.h, 0, nil); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_traffic_trend = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func goNodeTrends(ts []C.sg_node_trend) []NodeTrend {
+	out := make([]NodeTrend, len(ts))
+	for i := range ts {
+		t := &ts[i]
+		out[i] = NodeTrend{float32(t.in_lat_dev), float32(t.in_err_dev), float32(t.out_lat_dev), float32(t.out_err_dev),
+			float32(t.in_base_mean_us), float32(t.out_base_mean_us), uint32(t.in_seen), uint32(t.out_seen)}
+	}
+	return out
+}
+
+func goEdgeTrends(ts []C.sg_edge_trend) []EdgeTrend {
+	out := make([]EdgeTrend, len(ts))
+	for i := range ts {
+		out[i] = EdgeTrend{float32(ts[i].lat_dev), float32(ts[i].err_dev), float32(ts[i].base_mean_us), uint32(ts[i].windows_seen)}
+	}
+	return out
+}
+
+// WindowTrafficShifts answers "which workloads' traffic left its own normal band" for the window FlushWindow returned last, on the
+// device (sg_window_group_nodes_top_traffic): the k workload rows with the highest signed value >= minValue of key by — a
+// direction ORed with a side: TrafficDrop | TrafficIn ranks the workloads whose inbound request rate fell furthest — descending,
+// with their traffic rows (sg_window_group_node_traffic at the selected indices: InLatDev is the rate deviation, InErrDev the load
+// deviation, InBaseMeanUs the baseline rate in requests per window) and their indices into WindowWorkloadNodes.  k = 0: every
+// such row, in order.  It needs SetTrafficTrend over TrafficWorkloads.
+func (g *GraphDS) WindowTrafficShifts(by, k uint32, minValue float32) ([]WorkloadNode, []NodeTrend, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_group_nodes_top_traffic(g.h, C.uint32_t(by), 0, C.float(minValue), nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_nodes_top_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil, nil
+	}
+	ns, index := make([]C.sg_node_out, room), make([]uint32, room)
+	if rc := C.sg_window_group_nodes_top_traffic(g.h, C.uint32_t(by), C.uint32_t(k), C.float(minValue), &ns[0], (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_nodes_top_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		ns, index = ns[:int(sel)], index[:int(sel)]
+	}
+	if len(index) == 0 {
+		return nil, nil, nil, nil
+	}
+	var n C.size_t
+	ts := make([]C.sg_node_trend, len(index))
+	if rc := C.sg_window_group_node_traffic(g.h, (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index)), &ts[0], C.size_t(len(ts)), &n); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_node_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return goWorkloadNodes(ns), goNodeTrends(ts), index, nil
+}
+
+// WindowWorkloadEdgeTrafficShifts is WindowTrafficShifts over the workload edges (sg_window_groups_top_traffic; by is a direction
+// alone: an edge has one side): the selected group edges, their traffic rows (sg_window_group_traffic) and their indices into
+// WindowGroupEdges.  It needs SetTrafficTrend over TrafficWorkEdges.
+func (g *GraphDS) WindowWorkloadEdgeTrafficShifts(by, k uint32, minValue float32) ([]GroupEdge, []EdgeTrend, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_groups_top_traffic(g.h, C.uint32_t(by), 0, C.float(minValue), nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_groups_top_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil, nil
+	}
+	ges, index := make([]C.sg_group_edge, room), make([]uint32, room)
+	if rc := C.sg_window_groups_top_traffic(g.h, C.uint32_t(by), C.uint32_t(k), C.float(minValue), &ges[0], (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_groups_top_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		ges, index = ges[:int(sel)], index[:int(sel)]
+	}
+	if len(index) == 0 {
+		return nil, nil, nil, nil
+	}
+	var n C.size_t
+	ts := make([]C.sg_edge_trend, len(index))
+	if rc := C.sg_window_group_traffic(g.h, (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index)), &ts[0], C.size_t(len(ts)), &n); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return goGroupEdges(ges), goEdgeTrends(ts), index, nil
+}
+
+// WindowServiceTrafficTop selects the services of the window FlushWindow returned last by a traffic key (sg_window_nodes_top_traffic;
+// by as WindowTrafficShifts takes it): the indices of the selected node rows and their traffic rows (sg_window_node_traffic).  It
+// needs SetTrafficTrend over TrafficNodes.
+func (g *GraphDS) WindowServiceTrafficTop(by, k uint32, minValue float32) ([]NodeTrend, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_nodes_top_traffic(g.h, C.uint32_t(by), 0, C.float(minValue), nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, fmt.Errorf("servicegraph: sg_window_nodes_top_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil
+	}
+	index := make([]uint32, room)
+	if rc := C.sg_window_nodes_top_traffic(g.h, C.uint32_t(by), C.uint32_t(k), C.float(minValue), nil, (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, fmt.Errorf("servicegraph: sg_window_nodes_top_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		index = index[:int(sel)]
+	}
+	if len(index) == 0 {
+		return nil, nil, nil
+	}
+	var n C.size_t
+	ts := make([]C.sg_node_trend, len(index))
+	if rc := C.sg_window_node_traffic(g.h, (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index)), &ts[0], C.size_t(len(ts)), &n); rc != 0 {
+		return nil, nil, fmt.Errorf("servicegraph: sg_window_node_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return goNodeTrends(ts), index, nil
+}
+
+// WindowEdgeTraffic returns the traffic rows of the edge rows at index (the row indices another selection gave; the pod-edge space
+// has no selection of its own) of the window FlushWindow returned last (sg_window_traffic).  It needs SetTrafficTrend over
+// TrafficEdges.
+func (g *GraphDS) WindowEdgeTraffic(index []uint32) ([]EdgeTrend, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	if len(index) == 0 {
+		return nil, nil
+	}
+	var n C.size_t
+	ts := make([]C.sg_edge_trend, len(index))
+	if rc := C.sg_window_traffic(g.h, (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index)), &ts[0], C.size_t(len(ts)), &n); rc != 0 {
+		return nil, fmt.Errorf("servicegraph: sg_window_traffic = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return goEdgeTrends(ts), nil
+}
+
+// TrafficTrendStats returns the running statistics of the traffic baseline of one space (a Traffic* constant) and the number of
+// entries it holds (sg_traffic_trend_stats_get, sg_traffic_trend_entries).
+func (g *GraphDS) TrafficTrendStats(space uint32) (TrafficStats, int, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var tst C.sg_trend_stats
+	if rc := C.sg_traffic_trend_stats_get(g.h, C.uint32_t(space), &tst); rc != 0 {
+		return TrafficStats{}, 0, fmt.Errorf("servicegraph: sg_traffic_trend_stats_get = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	var n C.size_t
+	if rc := C.sg_traffic_trend_entries(g.h, C.uint32_t(space), nil, 0, &n); rc != 0 {
+		return TrafficStats{}, 0, fmt.Errorf("servicegraph: sg_traffic_trend_entries = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return TrafficStats{uint64(tst.windows), uint64(tst.entries), uint64(tst.inserted), uint64(tst.expired), uint64(tst.dropped)}, int(n), nil
+}
+
+// WindowTrafficBuffer returns the device address of the traffic rows of one space of the window that ran last
+// (sg_window_traffic_buffer), for a consumer that reads them on the device.
+func (g *GraphDS) WindowTrafficBuffer(space uint32) (uintptr, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var p unsafe.Pointer
+	if rc := C.sg_window_traffic_buffer(g.h, C.uint32_t(space), &p); rc != 0 {
+		return 0, fmt.Errorf("servicegraph: sg_window_traffic_buffer = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return uintptr(p), nil
+}
+
 // Run closes a window every `every` until ctx is done and hands its rows to sink (e.g. a POST of the /edges/ payload of
 // INTEGRATION.md §4 through the inner store's HTTP client).
 func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(windowEndMs int64, rows []EdgeRow)) {

@@ -1166,6 +1166,89 @@ int sg_window_nodes_top_tail(sg_handle h, uint32_t by, uint32_t k, float min_val
 int sg_window_groups_top_tail(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap, size_t* n_selected, size_t* n_groups);
 int sg_window_group_nodes_top_tail(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
 
+/* ---- traffic baselines (K23): each entity's request rate and load against its own past, on the device ------------------------------ *
+ * Opt-in (sg_set_traffic_trend); without it nothing is launched or allocated, and every other output is byte for byte the same
+ * either way.  Every other baseline judges a window by latency or error ratio; this one by HOW MUCH traffic an entity carried: a
+ * partial drop (an upstream failure cuts off most of the requests, the ones that still arrive are fast and succeed) or a surge (a
+ * retry storm, a new client) shows here while lat_dev, err_dev and the scores stay calm.
+ * Four bits select the spaces; each requested space gets one baseline with a trend-window counter of its own, with the keys, the
+ * sample order and the row type of the MEAN baseline of that space:
+ *   SG_T_EDGES        sample = row j of the window; key (from_key, to_key), the trend's (sg_set_trend); rows sg_edge_trend
+ *   SG_T_NODES        sample 2 * node + side, side 0 = in, 1 = out; key (nk, side), the node baselines'; rows sg_node_trend
+ *   SG_T_GROUPS       sample = group edge j; key (wk(from_ref), wk(to_ref)), the group baselines'; rows sg_edge_trend
+ *   SG_T_GROUP_NODES  sample 2 * row + side; key (wk(ref), side), the workload baselines'; rows sg_node_trend
+ * A space needs only its rows: SG_T_NODES needs sg_set_nodes, SG_T_GROUPS sg_set_groups, SG_T_GROUP_NODES sg_set_group_nodes
+ * (SG_ESTATE otherwise), SG_T_EDGES nothing.  The stage needs neither the mean baselines nor K20 and does not touch them, nor
+ * they it.  Whatever frees a space's rows frees this stage's baseline of that space with it: sg_set_nodes(h, 0), any
+ * sg_set_groups call, sg_set_group_nodes(h, 0).
+ * Samples.  An entity side has the count c the mean baseline of the space reads (count of the row or group edge, in_count /
+ * out_count of the node or workload row) and its sum_ns.  With c > 0 its two samples are exact integers in fp64:
+ *   x_rate = 1000.0 * min(c, 2^42)       so that base_mean_us = (float)(mean / 1000) reads as REQUESTS PER WINDOW
+ *   x_load = (double) min(sum_ns, 2^52)  the side's busy time, requests x latency: by Little's law the concurrency the callee
+ *                                        carried over the window
+ * x_rate feeds the lat_* half of the entry (sg_trend_entry.lat_mean / lat_dev) and of the row, x_load the err_* half.  In a row
+ *   lat_dev       is the RATE deviation, (x_rate - mean) / max(dev, 1000.0 * rate_floor)
+ *   err_dev       is the LOAD deviation, (x_load - mean) / max(dev, load_floor_ns)
+ *   base_mean_us  is the baseline RATE in requests per window
+ *   windows_seen  (in_seen / out_seen) keeps its name and meaning
+ * and for the node-shaped rows in_* / out_* are the two sides as in sg_node_trend.  A drop is a negative deviation.
+ * Absent entities.  A side with c == 0, or an entity without a row in the window, neither creates, refreshes nor scores an entry,
+ * as in every other baseline.  COMPLETE silence stays the business of the vanished lists (sg_set_vanished, sg_set_group_vanished):
+ * this stage is about partial drops and surges.  Windows are ASSUMED TO BE OF EQUAL LENGTH: the samples are per window, not per
+ * second, and a host that closes windows of varying length sees that as a change of rate.
+ * Entry update, expiry (ttl), the capacity cut, the statistics and the row rule are the trend's (sg_set_trend) word for word: rows
+ * are scored from the entry as it stood before the window's update, zero below warmup or when c == 0.
+ * Every close path computes it, behind the space's rows of the same window on the window's stream; with several windows in flight
+ * the state updates run in window order.                                                                                          */
+#define SG_T_EDGES        1u
+#define SG_T_NODES        2u
+#define SG_T_GROUPS       4u
+#define SG_T_GROUP_NODES  8u
+typedef struct sg_traffic_params {
+    uint32_t struct_size;       /* sizeof(sg_traffic_params)                                                                */
+    uint32_t shift;             /* alpha = 2^-shift, 1..10 (0 = 4)                                                           */
+    uint32_t warmup;            /* windows an entry must have seen before its rows report deviations (0 = 4)                 */
+    uint32_t ttl;               /* windows an entry survives without a sample (0 = 64)                                       */
+    uint64_t max_entries;       /* capacity of each space's baseline, at most 2^31 (0 = the default of the mean baseline of
+                                 * that space: 2 x max_edges for the two edge-shaped spaces, 4 x the rows a window can have for
+                                 * the two node-shaped ones)                                                                 */
+    uint64_t load_floor_ns;     /* load deviation floor in ns of busy time, at most 2^52 (0 = 1 000 000)                     */
+    uint32_t rate_floor;        /* rate deviation floor in requests (0 = 8)                                                  */
+    uint32_t reserved;          /* 0                                                                                         */
+} sg_traffic_params;            /* 40 bytes, no padding */
+/* spaces == 0 or p == NULL switches the stage off and frees it; every call replaces the previous setting and starts empty
+ * baselines; one sg_traffic_params serves all requested spaces.  SG_EINVAL for unknown space bits or bad parameters; SG_ESTATE for
+ * a space whose rows are off, or while a flush is open.  Memory is allocated here, never at sg_create.                           */
+int sg_set_traffic_trend(sg_handle h, uint32_t spaces, const sg_traffic_params* p);
+/* The traffic rows of the last READ window, one call per space: exactly sg_window_trend, sg_window_node_trend,
+ * sg_window_group_trend and sg_window_group_node_trend over the traffic baseline of the space.                                   */
+int sg_window_traffic(sg_handle h, const uint32_t* row_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n);
+int sg_window_node_traffic(sg_handle h, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n);
+int sg_window_group_traffic(sg_handle h, const uint32_t* group_index, size_t n_index, sg_edge_trend* out, size_t cap, size_t* n);
+int sg_window_group_node_traffic(sg_handle h, const uint32_t* node_index, size_t n_index, sg_node_trend* out, size_t cap, size_t* n);
+/* The device rows of one space of the window sg_window_run closed last (as sg_window_trend_buffer and its twins), the baseline in
+ * key order and its statistics (as sg_trend_entries / sg_trend_stats_get).  `space` is exactly one SG_T_* bit, else SG_EINVAL.   */
+int sg_window_traffic_buffer(sg_handle h, uint32_t space, void** d_rows);
+int sg_traffic_trend_entries(sg_handle h, uint32_t space, sg_trend_entry* out, size_t cap, size_t* n);
+int sg_traffic_trend_stats_get(sg_handle h, uint32_t space, sg_trend_stats* out);
+/* Selections over the traffic rows of the last READ window, with the argument lists, the row bytes and the index outputs of their
+ * _top_tail twins.  `by` is one of the four keys below — the SIGNED value is what is ranked, so a drop is selected by its size —
+ * and on the two node-shaped spaces it is ORed with exactly one of SG_TSEL_IN / SG_TSEL_OUT (the side; on the group edges with
+ * neither); anything else is SG_EINVAL.  min_value and the tie rule (by row position, -0.0 == +0.0) are the other selections',
+ * applied to the signed value: SG_TSEL_DROP with min_value 3 selects the rows whose rate fell by more than three deviations.
+ * There is no "new" key: SG_NSEL_NEW / SG_SEL_NEW over the mean baselines answer that.  The pod-edge space (SG_T_EDGES) has no
+ * _top_traffic: its host form would be a flush; read its rows with sg_window_traffic at the indices another selection gave.
+ * SG_ESTATE when the space's traffic baseline is off or the window was closed while it was.                                      */
+#define SG_TSEL_SURGE      0u   /* +rate deviation */
+#define SG_TSEL_DROP       1u   /* -rate deviation */
+#define SG_TSEL_LOAD_UP    2u   /* +load deviation */
+#define SG_TSEL_LOAD_DOWN  3u   /* -load deviation */
+#define SG_TSEL_IN         4u   /* the in side of a node or workload row: the calls it receives */
+#define SG_TSEL_OUT        8u   /* the out side: the calls it makes */
+int sg_window_nodes_top_traffic(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
+int sg_window_groups_top_traffic(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap, size_t* n_selected, size_t* n_groups);
+int sg_window_group_nodes_top_traffic(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
