@@ -1,6 +1,17 @@
-"""numpy reference of the selection by a trend key (sg_flush_window_top_by, include/servicegraph.h): the positions K7 selects when
-the key is a row's sg_edge_trend value instead of its score."""
+"""numpy references of the selection (sg_flush_window_top / sg_flush_window_top_by, include/servicegraph.h): the positions K7 selects
+by a row's score, or when the key is a row's sg_edge_trend value instead."""
 import numpy as np
+
+
+def ref_select(rows, k, min_score):
+    """positions sg_flush_window_top selects from `rows` (canonical order)"""
+    s = rows["score"]
+    with np.errstate(invalid="ignore"):
+        ci = np.flatnonzero(s >= np.float32(min_score))
+    if k == 0:
+        return ci.astype(np.uint32)
+    cs = s[ci].astype(np.float64) + 0.0                               # -0.0 == +0.0
+    return ci[np.lexsort((ci, -cs))][:k].astype(np.uint32)
 
 
 def ref_select_by(rows, trend, by, k, min_value):

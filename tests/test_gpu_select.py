@@ -9,21 +9,11 @@ import pytest
 
 from alaz_amd import engine, replay, weights
 from tests.helpers import CLOCK, HostShim
+from tests.select_by_ref import ref_select
 
 pytestmark = pytest.mark.gpu
 
 NEG_INF = float("-inf")
-
-
-def ref_select(rows, k, min_score):
-    """positions sg_flush_window_top selects from `rows` (canonical order)"""
-    s = rows["score"]
-    with np.errstate(invalid="ignore"):
-        ci = np.flatnonzero(s >= np.float32(min_score))
-    if k == 0:
-        return ci.astype(np.uint32)
-    cs = s[ci].astype(np.float64) + 0.0                               # -0.0 == +0.0
-    return ci[np.lexsort((ci, -cs))][:k].astype(np.uint32)
 
 
 def _engine(nodes, max_edges, layers, *, variant=0, w=None, **kw):
