@@ -361,7 +361,8 @@ struct K4Layer : Family<K4LayerFn, sgplan::kK4LayerKeys> { template <size_t I> s
 constexpr K2RowptrFn kK2Rowptr[2] = {k2_rowptr<K2_RP_ROWS, false>, k2_rowptr<K2_RP_ROWS_DH, true>};    // [over the degree histograms]
 constexpr K4GatherFn kK4Gather[2] = {k4_gather<32>, k4_gather<64>};                                    // [layer > 0]
 constexpr K5ProjFn kK5Proj[2] = {k5_node_proj<false>, k5_node_proj<true>};                             // [MFMA]
-constexpr K5ScoreFn kK5Score[2][2] = {{k5_edge_score<false>, k5_edge_score<true>}, {k5_edge_score_lanes<false>, k5_edge_score_lanes<true>}};   // [form][fused reset]
+constexpr K5ScoreFn kK5Score[2][2][2] = {{{k5_edge_score<false>, k5_edge_score<true>}, {k5_edge_score_lanes<false, false>, k5_edge_score_lanes<true, false>}},
+                                         {{nullptr, nullptr}, {k5_edge_score_lanes<false, true>, k5_edge_score_lanes<true, true>}}};   // [features inline][form][fused reset]
 static_assert(sgplan::kK5LanesWgLds == 4 * K5L_WAVE_LDS, "sg_plan.hpp's copy of form 1's LDS per workgroup");
 template <class F, size_t... I>
 const std::array<typename F::Fn, sizeof...(I)>& kernel_table(std::index_sequence<I...>) {
@@ -704,7 +705,9 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
 int do_features(sg_engine* e, hipStream_t s) {
     const Dev& d = work(e).d;
     Timed t(e, s, 3);
-    const int nbn = grid_for(d.ncap, 128), nbe = grid_for(e->cfg.max_edges, 256, 4096);   // (the edge workgroups capped at 1 280 / 2 560 — whole rounds: no difference, profiles/r06_grids_ab_c3.txt)
+    // (the edge workgroups capped at 1 280 / 2 560 — whole rounds: no difference, profiles/r06_grids_ab_c3.txt; none where the score kernel
+    // computes the edge features itself: Plan::k5_efeat)
+    const int nbn = grid_for(d.ncap, 128), nbe = e->plan.k5_efeat ? 0 : grid_for(e->cfg.max_edges, 256, 4096);
     hipLaunchKernelGGL(k3_node_features, dim3(nbn + nbe), dim3(256), 0, s, d, (u32)nbn, e->in_fused_slices);
     e->in_fused_slices = 0;
     HIP_TRY(e, hipGetLastError());
@@ -1477,7 +1480,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
     {
         Timed t(e, s, 5);
         if (!(proj_done && d.world == 1)) hipLaunchKernelGGL(e->fn.k5_proj, dim3(grid_for(d.ncap, 16)), dim3(256), 0, s, d, d.h[e->cfg.layers], Wh);
-        hipLaunchKernelGGL(kK5Score[e->kn.k5_form][fr], dim3((int)e->plan.k5_grid), dim3(256), 0, s, d, Wh);   // one round of workgroups (sg_plan.hpp)
+        hipLaunchKernelGGL(kK5Score[e->kn.k5_efeat][e->kn.k5_form][fr], dim3((int)e->plan.k5_grid), dim3(256), 0, s, d, Wh);   // one round of workgroups (sg_plan.hpp)
     }
     if (did_reset) *did_reset = fr;
     HIP_TRY(e, hipGetLastError());
@@ -2459,7 +2462,7 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
         LR(dev_alloc(e, &w.P, (size_t)w.ncap * SG_F_HID)); LR(dev_alloc(e, &w.Q, (size_t)w.ncap * SG_F_HID));
         LR(dev_alloc(e, &w.nmean, (size_t)w.ncap * SG_F_HID));
         LR(dev_alloc(e, &w.hub_items, w.hub_cap)); LR(dev_alloc(e, &w.hub_base, (size_t)w.ncap + 1)); LR(dev_alloc(e, &w.hub_part, (size_t)w.hub_cap * SG_F_HID));
-        LR(dev_alloc(e, &w.efeat, ME * SG_F_EDGE)); LR(dev_alloc(e, &w.latz, ME)); LR(dev_alloc(e, &w.errr, ME));
+        if (!P.k5_efeat) { LR(dev_alloc(e, &w.efeat, ME * SG_F_EDGE)); LR(dev_alloc(e, &w.latz, ME)); LR(dev_alloc(e, &w.errr, ME)); }   // (else: values that live in k5_edge_score_lanes' registers)
         LR(dev_alloc(e, &w.row_mu, (size_t)w.ncap + 1)); LR(dev_alloc(e, &w.row_sd, (size_t)w.ncap + 1));
         LR(dev_alloc(e, &w.rows, ME));
         LR(dev_alloc(e, &w.in_part, (size_t)P.k3_ranges * P.k3_slices * K3_IN_NR * 6));
@@ -2561,6 +2564,13 @@ int sg_k5_form_get(sg_handle e, uint32_t* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     *out = (uint32_t)e->kn.k5_form;
+    return SG_OK;
+}
+
+int sg_k5_efeat_get(sg_handle e, uint32_t* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = (uint32_t)e->kn.k5_efeat;
     return SG_OK;
 }
 

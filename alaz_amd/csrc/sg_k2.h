@@ -608,11 +608,14 @@ __device__ __forceinline__ double sg_log1p_pos(double x) {
     const double sm = x * (1.0 - x * (0.5 - x * (1.0 / 3.0 - 0.25 * x)));
     return x < 1e-4 ? sm : r;
 }
-// e_uv, lat_z, err_ratio of edge `pos` from its accumulators and its row's out-statistics
-__device__ __forceinline__ void edge_features(const Dev& d, u32 pos) {
-    const ulonglong2* a = reinterpret_cast<const ulonglong2*>(d.acc_csr + (size_t)pos * 4);
-    const ulonglong2 x = a[0], y = a[1];
-    const u32 from = d.csr_from[pos];
+// e_uv, lat_z, err_ratio of an edge from its accumulators (x: count | errors << 32, sum_ns; y: max_ns, sumsq_us) and its row's
+// out-statistics.  The ONE copy of the arithmetic: k3_node_features' edge workgroups store the values (edge_features below),
+// k5_edge_score_lanes<.., true> computes them for the lane's own edge and keeps them in registers (sg_k5.h).  Both ends are the
+// caller's: `row_stats(mu, sd)` gives row_mu[from] / row_sd[from] where the arithmetic first needs them — the store form loads them
+// there, a caller that has fetched them ahead of time hands them over —, and `out` takes the two feature words, then lat_z and
+// err_ratio, in the order the store form has always written them (begin(): where that form works out its address).
+template <class RowStats, class Out>
+__device__ __forceinline__ void edge_feature_values(const Dev& d, const ulonglong2 x, const ulonglong2 y, RowStats row_stats, Out& out) {
     const u64 cnt = x.x & 0xFFFFFFFFull, err = x.x >> 32, sum = x.y, mx = y.x, ssq = y.y;
     const double rc = cnt ? sg_rcp((double)cnt) : 0.0, dc = (double)cnt;
     // mean and standard deviation in us (mean_us / std_us with the division above: the features and lat_z take them to fp32)
@@ -620,18 +623,41 @@ __device__ __forceinline__ void edge_features(const Dev& d, u32 pos) {
     double m_e = sum_us * rc; m_e = cnt ? fma(fma(-dc, m_e, sum_us), rc, m_e) : 0.0;
     double q_e = (double)ssq * rc; q_e = cnt ? fma(fma(-dc, q_e, (double)ssq), rc, q_e) : 0.0;
     const double var = q_e - m_e * m_e, s_e = var > 0.0 ? sqrt(var) : 0.0;
-    const double mu = d.row_mu[from], sd = d.row_sd[from];           // mean_us / std_us of the row's out-statistics: computed once per row by the row sort
+    double mu, sd; row_stats(mu, sd);                                // mean_us / std_us of the row's out-statistics: computed once per row by the row sort
     const double z = sd > 1.0 ? sg_div(m_e - mu, sd) : m_e - mu;
     const float lat_z = (float)z;
     // err / cnt correctly rounded to fp32: for integers below 2^24 the fp32 division IS (float)((double) err / (double) cnt) (rounding
     // twice through a format of at least 2 x 24 + 2 bits is innocuous for a quotient); the fp64 division beyond
     const float err_ratio = !cnt ? 0.0f : ((cnt | err) < (1ull << 24) ? (float)(u32)err / (float)(u32)cnt : (float)((double)err / (double)cnt));
     const float zc = lat_z < -8.0f ? -8.0f : (lat_z > 8.0f ? 8.0f : lat_z);
-    float4* e = reinterpret_cast<float4*>(d.efeat + (size_t)pos * SG_F_EDGE);
-    e[0] = make_float4(log1p_count(d, cnt), (float)sg_log1p_pos(m_e * 1e-3), (float)sg_log1p_pos(s_e * 1e-3), (float)sg_log1p_pos((double)mx * 1e-6));
-    e[1] = make_float4(err_ratio, log1p_count(d, err), zc * 0.125f, 1.0f);
-    d.latz[pos] = lat_z; d.errr[pos] = err_ratio;
+    out.begin();
+    out.e0(make_float4(log1p_count(d, cnt), (float)sg_log1p_pos(m_e * 1e-3), (float)sg_log1p_pos(s_e * 1e-3), (float)sg_log1p_pos((double)mx * 1e-6)));
+    out.e1(make_float4(err_ratio, log1p_count(d, err), zc * 0.125f, 1.0f));
+    out.tail(lat_z, err_ratio);
 }
+// the store form (k3_node_features' edge workgroups): efeat, latz, errr of edge `pos`
+struct EdgeFeatStore {
+    const Dev& d; u32 pos; float4* e;
+    __device__ __forceinline__ void begin() { e = reinterpret_cast<float4*>(d.efeat + (size_t)pos * SG_F_EDGE); }
+    __device__ __forceinline__ void e0(float4 v) const { e[0] = v; }
+    __device__ __forceinline__ void e1(float4 v) const { e[1] = v; }
+    __device__ __forceinline__ void tail(float lat_z, float err_ratio) const { d.latz[pos] = lat_z; d.errr[pos] = err_ratio; }
+};
+__device__ __forceinline__ void edge_features(const Dev& d, u32 pos) {
+    const ulonglong2* a = reinterpret_cast<const ulonglong2*>(d.acc_csr + (size_t)pos * 4);
+    const ulonglong2 x = a[0], y = a[1];
+    const u32 from = d.csr_from[pos];
+    EdgeFeatStore out{d, pos, nullptr};
+    edge_feature_values(d, x, y, [&](double& mu, double& sd) { mu = d.row_mu[from]; sd = d.row_sd[from]; }, out);
+}
+// ... and the register form (k5_edge_score_lanes)
+struct EdgeFeat {
+    float4 w0, w1; float lat_z, err_ratio;
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void e0(float4 v) { w0 = v; }
+    __device__ __forceinline__ void e1(float4 v) { w1 = v; }
+    __device__ __forceinline__ void tail(float z, float r) { lat_z = z; err_ratio = r; }
+};
 
 #define K2_LONG_WGS 1024
 #define K2_WAVE_ROW 512          // rows of up to this many edges are sorted by ONE wave (bitmap rank in a wave-private slice of the LDS arrays)

@@ -239,6 +239,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 //   products, q and q+16 by a fused multiply-add onto them; the two pair sums and every later level are plain adds.
 //   Rows leave as form 0's do: every lane writes its 64-byte row into the (then idle) tile, word w at slot 4 r + (w ^ ((r >> 1) & 3)),
 //   the wave reads it back in 8-byte words and issues eight 512-byte buffer stores whose range drops the rows beyond E.
+//   EFEAT (Plan::k5_efeat): the lane computes e_uv, lat_z and err_ratio of its own edge itself — edge_feature_values(), sg_k2.h, the
+//   arithmetic k3_node_features' edge workgroups run elsewhere — from the accumulators and `from` it loads anyway; no efeat / latz /
+//   errr access remains (the arrays do not exist for such an engine).  The feature code keeps its own (default) contraction: the
+//   pragma below is lexical.  Same rows, byte for byte (tests/test_gpu_k5_efeat.py).
 // ------------------------------------------------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef u32 v4u_t __attribute__((ext_vector_type(4)));
@@ -246,7 +250,7 @@ typedef u32 v4u_t __attribute__((ext_vector_type(4)));
 // orders the wave's LDS traffic for the compiler (the hardware runs a wave's DS instructions in order)
 __device__ __forceinline__ void k5l_lds_order() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
-template <bool RESET>
+template <bool RESET, bool EFEAT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k5_edge_score_lanes(Dev d, const float* __restrict__ Wh) {
 #pragma clang fp contract(off)
     static_assert(SG_F_HID == 64 && SG_F_EDGE == 8, "k5_edge_score_lanes: 64 hidden units in four quarters, eight edge features");
@@ -265,17 +269,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         const u32 rx = (lane >> 2) & 3u;                            // reads: this lane's row is `lane`
         const u32 ox = (lane >> 1) & 3u;                            // row tile (out): swizzle of this lane's row
         const u32 rb = (((lane >> 3) * 4 + (((lane & 7u) >> 1) ^ ((lane >> 4) & 3u))) << 1) | (lane & 1u);   // read-back: 8-byte word lane & 7 of row 8 j + lane / 8
+        // EFEAT: these lane-derived values are worked out again where they are used, from a lane number the optimiser cannot see through
+        // (relane), so that they are not kept in registers across the batch loop — a dozen registers that the fp64 chains of the features need
+        // to fit the 168 of three waves per SIMD without scratch.  The other instantiations keep the values above (and their code).
+        auto relane = [&]() -> u32 { u32 l = lane; asm volatile("" : "+v"(l)); return l; };
         u32 gu[4], gv[4];
         f32x4 R[8];
         auto load_ids = [&](u32 p0) {
+            u32 subl = 0;
+            if constexpr (EFEAT) subl = relane() >> 2;
 #pragma unroll
-            for (int i = 0; i < 4; i++) { const u32 p = p0 + i * 16 + sub, c = p < E ? p : last; gu[i] = d.csr_from[c]; gv[i] = d.col[c]; }
+            for (int i = 0; i < 4; i++) { const u32 p = EFEAT ? p0 + i * 16 + subl : p0 + i * 16 + sub, c = p < E ? p : last; gu[i] = d.csr_from[c]; gv[i] = d.col[c]; }
         };
         // (32-bit byte offsets from P and Q: one register per gather address, the base in scalar registers — the plan takes this form only
         // where a row's offset fits 32 bits, sg_plan.hpp)
         auto row_offsets = [&]() {
+            u32 pc_ = pc;
+            if constexpr (EFEAT) pc_ = relane() & 3u;
 #pragma unroll
-            for (int i = 0; i < 4; i++) { gu[i] = gu[i] * (SG_F_HID * 4u) + pc * 16u; gv[i] = gv[i] * (SG_F_HID * 4u) + pc * 16u; }
+            for (int i = 0; i < 4; i++) { gu[i] = gu[i] * (SG_F_HID * 4u) + pc_ * 16u; gv[i] = gv[i] * (SG_F_HID * 4u) + pc_ * 16u; }
         };
         auto issue = [&](int c) {                                   // the gathers of quarter c for the ids at hand
 #pragma unroll
@@ -294,8 +306,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         // packed FMA: the offset goes through an asm the optimiser cannot see through, and scheduling barriers fence every block.
         auto quarter = [&](int c, float (&out)[4]) {
             f32x4 pq[4];                                             // P[u] + Q[v], units 4c + w + 16 m at [w][m]
+            u32 rd = lane * 4 + rx;
+            if (EFEAT) { const u32 l = relane(); rd = l * 4 + ((l >> 2) & 3u); }
 #pragma unroll
-            for (int w = 0; w < 4; w++) pq[w] = tile[(lane * 4 + rx) ^ (u32)w] + tile[256 + ((lane * 4 + rx) ^ (u32)w)];
+            for (int w = 0; w < 4; w++) pq[w] = tile[rd ^ (u32)w] + tile[256 + (rd ^ (u32)w)];
             f32x4 W[2][4], w2v[4];
             auto wload = [&](int blk, f32x4 (&dst)[4]) {
                 u32 o = (u32)((blk & 1) * 4 * SG_F_HID + 16 * (blk >> 1) + 4 * c);
@@ -336,29 +350,53 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
             out[0] = sa.x; out[1] = sa.y; out[2] = sb.x; out[3] = sb.y;
         };
         u32 b = wave;
-        if (b < nbatch) { load_ids(b * 64u); row_offsets(); issue(0); }
+        // EFEAT: what edge_feature_values() takes for this lane's edge of the batch at hand — its accumulators and its row's mean / deviation —,
+        // fetched a batch ahead: `from` beside the next batch's ids (quarter 1), the rest behind it, late in the row's assembly.  The
+        // dependent round trips (from, then row_mu / row_sd) are over before the batch that needs them has staged its quarter 0.
+        u32 nfrom = 0; ulonglong2 nx = {0, 0}, ny = {0, 0}; double nmu = 0.0, nsd = 0.0;
+        auto load_own = [&](u32 c) {
+            nx = reinterpret_cast<const ulonglong2*>(d.acc_csr + (size_t)c * 4)[0]; ny = reinterpret_cast<const ulonglong2*>(d.acc_csr + (size_t)c * 4)[1];
+            nmu = d.row_mu[nfrom]; nsd = d.row_sd[nfrom];
+        };
+        if (b < nbatch) {
+            if (EFEAT) { const u32 c0 = b * 64u + lane < E ? b * 64u + lane : last; nfrom = d.csr_from[c0]; load_own(c0); }
+            load_ids(b * 64u); row_offsets(); issue(0);
+        }
         for (; b < nbatch; b += nw) {
             const u32 p0 = b * 64u;
             const u32 er = p0 + lane, ec = er < E ? er : last;
             const u32 np0 = b + nw < nbatch ? (b + nw) * 64u : last;            // the next batch of this wave (beyond the last: clamped, dropped)
             // this lane's own edge: 32 bytes of features, 32 of accumulators, five dwords — all coalesced across the wave
-            const f32x4 e0 = reinterpret_cast<const f32x4*>(d.efeat + (size_t)ec * SG_F_EDGE)[0], e1 = reinterpret_cast<const f32x4*>(d.efeat + (size_t)ec * SG_F_EDGE)[1];
+            const u32 nec = EFEAT ? (np0 + lane < E ? np0 + lane : last) : 0u;                 // (EFEAT: this lane's edge of the next batch)
+            f32x4 e0, e1; u32 wer, wlz;
+            if (!EFEAT) { e0 = reinterpret_cast<const f32x4*>(d.efeat + (size_t)ec * SG_F_EDGE)[0]; e1 = reinterpret_cast<const f32x4*>(d.efeat + (size_t)ec * SG_F_EDGE)[1]; }
             float T[4];
             // quarters 0, 2, 1, 3: stage the quarter whose gathers are in the registers, send the next one's, compute
 #define K5L_STAGE(C, NEXT) { k5l_lds_order();                                                                                \
-                _Pragma("unroll") for (int i = 0; i < 4; i++) { tile[64 * i + wslot] = R[i]; tile[256 + 64 * i + wslot] = R[4 + i]; } \
+                u32 ws_ = wslot; if (EFEAT) { const u32 l = relane(), s_ = l >> 2; ws_ = s_ * 4 + ((l & 3u) ^ ((s_ >> 2) & 3u)); }           \
+                _Pragma("unroll") for (int i = 0; i < 4; i++) { tile[64 * i + ws_] = R[i]; tile[256 + 64 * i + ws_] = R[4 + i]; } \
                 k5l_lds_order(); NEXT; __builtin_amdgcn_sched_barrier(0); }
-            K5L_STAGE(0, issue(2))
+            // EFEAT: the features of the lane's own edge go between quarter 0's staging and quarter 2's gathers — the one place of the batch
+            // where the eight gather registers R are dead, which is what the fp64 chains need to fit the 168 registers of three waves per SIMD
+            auto features = [&]() {
+                EdgeFeat f;
+                edge_feature_values(d, nx, ny, [&](double& mu_, double& sd_) { mu_ = nmu; sd_ = nsd; }, f);
+                e0 = (f32x4){ f.w0.x, f.w0.y, f.w0.z, f.w0.w }; e1 = (f32x4){ f.w1.x, f.w1.y, f.w1.z, f.w1.w };
+                wlz = __float_as_uint(f.lat_z); wer = __float_as_uint(f.err_ratio);
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            K5L_STAGE(0, { if (EFEAT) features(); issue(2); })
             ek[0] = e0[0]; ek[1] = e0[1]; ek[2] = e0[2]; ek[3] = e0[3]; ek[4] = e1[0]; ek[5] = e1[1]; ek[6] = e1[2]; ek[7] = e1[3];
             { float o[4]; quarter(0, o); S[0] = o[0]; S[1] = o[1]; S[2] = o[2]; S[3] = o[3]; }
             K5L_STAGE(2, issue(1))
             { float o[4]; quarter(2, o); for (int i = 0; i < 4; i++) S[i] = S[i] + o[i]; }                  // stride 8: units 0..3 with 8..11
-            K5L_STAGE(1, { issue(3); load_ids(np0); })
+            K5L_STAGE(1, { issue(3); load_ids(np0); if (EFEAT) nfrom = d.csr_from[nec]; })
             { float o[4]; quarter(1, o); S[4] = o[0]; S[5] = o[1]; S[6] = o[2]; S[7] = o[3]; }
             // ... the accumulators and five dwords of it: wanted at the end only, fetched beside the last quarter's arithmetic
             const ulonglong2 a01 = reinterpret_cast<const ulonglong2*>(d.acc_csr + (size_t)ec * 4)[0], a23 = reinterpret_cast<const ulonglong2*>(d.acc_csr + (size_t)ec * 4)[1];
             const u32 mu = d.csr_from[ec], mv = d.col[ec];
-            const u32 wer = reinterpret_cast<const u32*>(d.errr)[ec], wlz = reinterpret_cast<const u32*>(d.latz)[ec], wal = d.alive_csr[ec];
+            if (!EFEAT) { wer = reinterpret_cast<const u32*>(d.errr)[ec]; wlz = reinterpret_cast<const u32*>(d.latz)[ec]; }
+            const u32 wal = d.alive_csr[ec];
             K5L_STAGE(3, { row_offsets(); issue(0); })                                                                      // (the next batch's first quarter)
             { float o[4]; quarter(3, o); for (int i = 0; i < 4; i++) S[4 + i] = S[4 + i] + o[i]; }          // stride 8: units 4..7 with 12..15
 #undef K5L_STAGE
@@ -372,12 +410,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
             if (d.hist) pct = k5_percentiles(d, ec, (u32)(a01.x & 0xFFFFFFFFull), a23.x);
             // the row: words 0..2 sum_ns, max_ns, sumsq_us = accumulators 1..3; 3 from_ref | to_ref; 4 count | err = accumulator 0;
             // 5 score | lat_z; 6 err_ratio | alive; 7 p50_us | p99_us
+            // (the next batch's accumulators and row statistics go out HERE: behind the percentiles, the registers' high-water mark of the
+            // row's assembly, and with the row's staging and eight stores still between them and their use)
+            if (EFEAT) load_own(nec);
             v4u_t* const ot = reinterpret_cast<v4u_t*>(tile);
+            u32 ln = lane, ox_ = ox, rb_ = rb;
+            if (EFEAT) { ln = relane(); ox_ = (ln >> 1) & 3u; rb_ = (((ln >> 3) * 4 + (((ln & 7u) >> 1) ^ ((ln >> 4) & 3u))) << 1) | (ln & 1u); }
             k5l_lds_order();
-            ot[(lane * 4 + ox) ^ 0u] = (v4u_t){ (u32)a01.y, (u32)(a01.y >> 32), (u32)a23.x, (u32)(a23.x >> 32) };
-            ot[(lane * 4 + ox) ^ 1u] = (v4u_t){ (u32)a23.y, (u32)(a23.y >> 32), (u32)refs, (u32)(refs >> 32) };
-            ot[(lane * 4 + ox) ^ 2u] = (v4u_t){ (u32)a01.x, (u32)(a01.x >> 32), score, wlz };
-            ot[(lane * 4 + ox) ^ 3u] = (v4u_t){ wer, wal, (u32)pct, (u32)(pct >> 32) };
+            ot[(ln * 4 + ox_) ^ 0u] = (v4u_t){ (u32)a01.y, (u32)(a01.y >> 32), (u32)a23.x, (u32)(a23.x >> 32) };
+            ot[(ln * 4 + ox_) ^ 1u] = (v4u_t){ (u32)a23.y, (u32)(a23.y >> 32), (u32)refs, (u32)(refs >> 32) };
+            ot[(ln * 4 + ox_) ^ 2u] = (v4u_t){ (u32)a01.x, (u32)(a01.x >> 32), score, wlz };
+            ot[(ln * 4 + ox_) ^ 3u] = (v4u_t){ wer, wal, (u32)pct, (u32)(pct >> 32) };
             k5l_lds_order();
             {
                 const u32 p0u = (u32)__builtin_amdgcn_readfirstlane((int)p0);
@@ -385,7 +428,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
                 const __amdgpu_buffer_rsrc_t rr_ = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<u64*>(d.rows) + (size_t)p0u * 8, 0, (int)(nrow * 64u), 0x00020000);
                 const v2u_t* const rt = reinterpret_cast<const v2u_t*>(tile);
 #pragma unroll
-                for (int j = 0; j < 8; j++) __builtin_amdgcn_raw_buffer_store_b64(rt[64 * j + rb], rr_, (u32)j * 512u + lane * 8u, 0, 0);
+                for (int j = 0; j < 8; j++) __builtin_amdgcn_raw_buffer_store_b64(rt[64 * j + rb_], rr_, (u32)j * 512u + ln * 8u, 0, 0);
             }
         }
     }

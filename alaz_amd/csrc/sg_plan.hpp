@@ -50,7 +50,7 @@ struct DeviceFacts {
 struct Overrides {
     typedef std::optional<std::string> Knob;
     Knob ablate, np, ht, ct, nwg, nsub, split, warm, k1a, k1_narrow, k1_legacy, k1b_u, k1b_threads, k1b_pack, k1b_no_order,
-         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold, k1a_pair, k5_form;
+         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold, k1a_pair, k5_form, k5_efeat;
 };
 struct KnobName { const char* name; Overrides::Knob Overrides::*field; };
 // the one list of knob names (alaz_amd/engine.py DEV_KNOBS is checked against it)
@@ -64,7 +64,7 @@ constexpr KnobName kKnobs[] = {
     {"SG_K4_FUSED", &Overrides::k4_fused}, {"SG_K5_GRID", &Overrides::k5_grid}, {"SG_K6_ONE_WG", &Overrides::k6_one_wg},
     {"SG_DENSE_VALU", &Overrides::dense_valu}, {"SG_COPY_STREAMS", &Overrides::copy_streams}, {"SG_STAGE_SLOTS", &Overrides::stage_slots},
     {"SG_ARENA", &Overrides::arena}, {"SG_NO_FOLD", &Overrides::no_fold}, {"SG_K1A_PAIR", &Overrides::k1a_pair},
-    {"SG_K5_FORM", &Overrides::k5_form},
+    {"SG_K5_FORM", &Overrides::k5_form}, {"SG_K5_EFEAT", &Overrides::k5_efeat},
 };
 #ifdef SG_DEV_KNOBS
 inline Overrides from_env() {
@@ -96,6 +96,7 @@ struct Plan {
     bool k4_split = false;                    // K4 in two launches per layer (gather, then the dense tiles)
     u32 k5_grid = 0;
     u32 k5_form = 0;                          // k5_edge_score: 0 = sixteen lanes per edge, 1 = one lane per edge (k5_edge_score_lanes); k5_grid is the form's own
+    u32 k5_efeat = 0;                         // form 1 only: the score kernel computes the edge features itself — k3_node_features launches no edge workgroups, efeat / latz / errr do not exist
     bool k3_fuse_allowed = true;              // the one-call pipelines may fold k3_in_reduce into k3_in_part's launch
     bool k6_one_wg = false;                   // the round-3 single-workgroup halo-list builder
     bool use_mfma = true;
@@ -143,6 +144,9 @@ inline int check_config(const sg_config& in, sg_config* out) {
 // allow (amdgpu_waves_per_eu).
 constexpr u64 kK5LanesMinEdges = 1ull << 20;
 inline u32 k5_form_default(const sg_config& cfg) { return cfg.world <= 1 && cfg.max_edges >= kK5LanesMinEdges ? 1u : 0u; }
+// Form 1 with the edge features inline (k5_edge_score_lanes<.., true>): what an engine of form 1 takes unasked, set by the same-box A/B
+// of profiles/k5_efeat_ab_c3.txt; SG_K5_EFEAT=0/1 names it in the development build.  It exists for form 1 only.
+constexpr bool kK5EfeatDefault = true;
 constexpr size_t kK5LanesWgLds = 4 * 8192;
 constexpr int kK5LanesWaves = 3;
 constexpr int k5_lanes_wgs_per_cu() { return (int)std::min<size_t>(kLdsBytes / kK5LanesWgLds, (size_t)kK5LanesWaves); }
@@ -317,6 +321,13 @@ inline int make_plan(const sg_config& cfg, const DeviceFacts& dev, const Overrid
         p.k5_form = (u32)ival(ov.k5_form);
     }
     if ((u64)p.ncap * 256u > (1ull << 32)) p.k5_form = 0;            // form 1 addresses a P / Q row by a 32-bit byte offset
+    // the features inline: the default follows the form; refused by name with form 0, which has no such kernel
+    p.k5_efeat = p.k5_form && kK5EfeatDefault ? 1u : 0u;
+    if (ov.k5_efeat) {
+        if (*ov.k5_efeat != "0" && *ov.k5_efeat != "1") { if (why) *why = "SG_K5_EFEAT: 0 (k3_node_features stores the edge features) or 1 (k5_edge_score_lanes computes them)"; return SG_EINVAL; }
+        p.k5_efeat = (u32)ival(ov.k5_efeat);
+        if (p.k5_efeat && !p.k5_form) { if (why) *why = "SG_K5_EFEAT=1 needs form 1 of k5_edge_score (SG_K5_FORM)"; return SG_EINVAL; }
+    }
     // form 0: 32 edges per workgroup and step, 3 workgroups per CU.  Form 1: 256 edges per workgroup and step; a CU holds
     // min(LDS / kK5LanesWgLds, kK5LanesWaves) of its workgroups (4 waves each, one per SIMD): one round of those
     const int k5_per_wg = p.k5_form ? 256 : 32, k5_round = (p.k5_form ? k5_lanes_wgs_per_cu() : 3) * (int)p.cus;
@@ -440,6 +451,7 @@ struct Kernels {
     bool k4_split = false, k4_mfma = true;    // k4_sage_layer (input width, projection and threads follow the layer at launch)
     bool k5_mfma = true;                      // k5_node_proj (k5_edge_score's fused reset is the caller's argument)
     int k5_form = 0;                          // k5_edge_score (0) or k5_edge_score_lanes (1)
+    int k5_efeat = 0;                         // k5_edge_score_lanes<.., EFEAT>: the edge features computed inline
 };
 inline PassAKernel choose_pass_a(const Plan& p, const PassA& a, const sg_config& cfg) {
     PassAKernel k;
@@ -463,7 +475,7 @@ inline Kernels choose_kernels(const Plan& p, const PassA& a, const sg_config& cf
         else { k.k1b_family = K1B_MERGE; k.k1b_hist = p.hist != 0; if (k.k1b_hist) k.k1b_u = 4; }
     }
     k.k2_dh = p.dh_g != 0;
-    k.k4_split = p.k4_split; k.k4_mfma = p.use_mfma; k.k5_mfma = p.use_mfma; k.k5_form = (int)p.k5_form;
+    k.k4_split = p.k4_split; k.k4_mfma = p.use_mfma; k.k5_mfma = p.use_mfma; k.k5_form = (int)p.k5_form; k.k5_efeat = (int)p.k5_efeat;
     return k;
 }
 

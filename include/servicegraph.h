@@ -1371,6 +1371,10 @@ int sg_pass_a_pair_get(sg_handle h, uint32_t* out);
 /* The score kernel's form, beside sg_geometry likewise: *out = 0 when k5_edge_score gives sixteen lanes to an edge, 1 when one lane
  * owns an edge and the P and Q rows pass through LDS (k5_edge_score_lanes).  Both write the same rows, bit for bit. */
 int sg_k5_form_get(sg_handle h, uint32_t* out);
+/* Where the edge features are computed, beside sg_geometry likewise: *out = 0 when k3_node_features stores them for the score kernel,
+ * 1 when k5_edge_score_lanes computes them for its own edge (form 1 only; the engine then holds no feature arrays).  Same rows, bit
+ * for bit. */
+int sg_k5_efeat_get(sg_handle h, uint32_t* out);
 
 /* Per-kernel timing, measured on the launch stream.  Groups: 1 = K1 pass A (k1a_partition / k1_resolve_aggregate, one record
  * per batch), 7 = K1 pass B (k1b_merge) — both by the dispatch's own begin/end stamps; 2 = K2 csr_build (two records per window:
