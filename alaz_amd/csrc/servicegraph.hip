@@ -62,6 +62,7 @@ typedef void (*K4GatherFn)(Dev, const float*);
 typedef void (*K4LayerFn)(Dev, const float*, float*, const float*, const float*);
 typedef void (*K5ProjFn)(Dev, const float*, const float*);
 typedef void (*K5ScoreFn)(Dev, const float*);
+typedef void (*K3Fn)(Dev, u32, u32);
 
 }  // namespace
 
@@ -363,6 +364,8 @@ constexpr K4GatherFn kK4Gather[2] = {k4_gather<32>, k4_gather<64>};             
 constexpr K5ProjFn kK5Proj[2] = {k5_node_proj<false>, k5_node_proj<true>};                             // [MFMA]
 constexpr K5ScoreFn kK5Score[2][2][2] = {{{k5_edge_score<false>, k5_edge_score<true>}, {k5_edge_score_lanes<false, false>, k5_edge_score_lanes<true, false>}},
                                          {{nullptr, nullptr}, {k5_edge_score_lanes<false, true>, k5_edge_score_lanes<true, true>}}};   // [features inline][form][fused reset]
+constexpr K3Fn kK3InPart[2] = {k3_in_part<0>, k3_in_part<1>};                                           // [a trip's loads issued together]
+constexpr K3Fn kK3Feat[2] = {k3_node_features, k3_node_features_lanes};                                // [eight lanes per node: the node-only launch]
 static_assert(sgplan::kK5LanesWgLds == 4 * K5L_WAVE_LDS, "sg_plan.hpp's copy of form 1's LDS per workgroup");
 template <class F, size_t... I>
 const std::array<typename F::Fn, sizeof...(I)>& kernel_table(std::index_sequence<I...>) {
@@ -686,10 +689,10 @@ int do_close(sg_engine* e, hipStream_t s, const u32* d_union, const u32* d_union
             // the one-call pipelines (nothing reads the in-statistics between the close and the features): the features sum the partials, the
             // finishing work rides at the end of k3_in_part's launch — fifteen launches per window instead of sixteen
             const u32 finp = d.warm ? (fin + 3) / 4 : 1u;        // (1024-thread workgroups there)
-            hipLaunchKernelGGL(k3_in_part, dim3(e->plan.k3_ranges * e->plan.k3_slices + finp), dim3(1024), e->plan.k3in_lds, s, d, e->plan.k3_slices, finp);
+            hipLaunchKernelGGL(kK3InPart[e->kn.k3_in_form], dim3(e->plan.k3_ranges * e->plan.k3_slices + finp), dim3(1024), e->plan.k3in_lds, s, d, e->plan.k3_slices, finp);
             e->in_fused_slices = e->plan.k3_slices;
         } else {
-            hipLaunchKernelGGL(k3_in_part, dim3(e->plan.k3_ranges * e->plan.k3_slices), dim3(1024), e->plan.k3in_lds, s, d, e->plan.k3_slices, 0u);
+            hipLaunchKernelGGL(kK3InPart[e->kn.k3_in_form], dim3(e->plan.k3_ranges * e->plan.k3_slices), dim3(1024), e->plan.k3in_lds, s, d, e->plan.k3_slices, 0u);
             hipLaunchKernelGGL(k3_in_reduce, dim3(grid_for((u64)d.ncap * 6, 256, 1024) + fin), dim3(256), 0, s, d, e->plan.k3_slices, fin);
             e->in_fused_slices = 0;
         }
@@ -707,8 +710,9 @@ int do_features(sg_engine* e, hipStream_t s) {
     Timed t(e, s, 3);
     // (the edge workgroups capped at 1 280 / 2 560 — whole rounds: no difference, profiles/r06_grids_ab_c3.txt; none where the score kernel
     // computes the edge features itself: Plan::k5_efeat)
-    const int nbn = grid_for(d.ncap, 128), nbe = e->plan.k5_efeat ? 0 : grid_for(e->cfg.max_edges, 256, 4096);
-    hipLaunchKernelGGL(k3_node_features, dim3(nbn + nbe), dim3(256), 0, s, d, (u32)nbn, e->in_fused_slices);
+    // (Plan::k3_feat_lanes: eight lanes per node, 32 nodes per workgroup — the node-only launch)
+    const int nbn = grid_for(d.ncap, e->kn.k3_feat_lanes ? 32 : 128), nbe = e->plan.k5_efeat ? 0 : grid_for(e->cfg.max_edges, 256, 4096);
+    hipLaunchKernelGGL(kK3Feat[e->kn.k3_feat_lanes], dim3(nbn + nbe), dim3(256), 0, s, d, (u32)nbn, e->in_fused_slices);
     e->in_fused_slices = 0;
     HIP_TRY(e, hipGetLastError());
     return SG_OK;
@@ -2382,7 +2386,7 @@ int sg_create(const sg_config* cfg_in, sg_handle* out) {
     CR(resolve_kernels(e));
     CH(lds_limit(2 * (size_t)d.k2_sortw * sizeof(u32), k2_rowsort_gather));
     if (d.dh_g) CH(lds_limit(((size_t)d.ncap + 1) * sizeof(u32), k2_deg_hist));
-    CH(lds_limit(P.k3in_lds, k3_in_part));
+    CH(lds_limit(P.k3in_lds, kK3InPart[0], kK3InPart[1]));
     CR(dev_alloc(e, &d.dbg, (size_t)4 * 4096 * 8));
     CR(dev_alloc(e, &d.clk, (size_t)4));
     CR(dev_alloc(e, &e->d_W, weights_count(cfg->layers)));
@@ -2571,6 +2575,13 @@ int sg_k5_efeat_get(sg_handle e, uint32_t* out) {
     if (!e || !out) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     *out = (uint32_t)e->kn.k5_efeat;
+    return SG_OK;
+}
+
+int sg_k3_forms_get(sg_handle e, uint32_t* in_form, uint32_t* feat_lanes) {
+    if (!e || !in_form || !feat_lanes) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    *in_form = (uint32_t)e->kn.k3_in_form; *feat_lanes = (uint32_t)e->kn.k3_feat_lanes;
     return SG_OK;
 }
 

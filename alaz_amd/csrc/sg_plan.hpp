@@ -50,7 +50,7 @@ struct DeviceFacts {
 struct Overrides {
     typedef std::optional<std::string> Knob;
     Knob ablate, np, ht, ct, nwg, nsub, split, warm, k1a, k1_narrow, k1_legacy, k1b_u, k1b_threads, k1b_pack, k1b_no_order,
-         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold, k1a_pair, k5_form, k5_efeat;
+         l2_global, l2_u32, dh_g, k3_slices, k3_no_fuse, k4_fused, k5_grid, k6_one_wg, dense_valu, copy_streams, stage_slots, arena, no_fold, k1a_pair, k5_form, k5_efeat, k3_in_form, k3_feat_lanes;
 };
 struct KnobName { const char* name; Overrides::Knob Overrides::*field; };
 // the one list of knob names (alaz_amd/engine.py DEV_KNOBS is checked against it)
@@ -65,6 +65,7 @@ constexpr KnobName kKnobs[] = {
     {"SG_DENSE_VALU", &Overrides::dense_valu}, {"SG_COPY_STREAMS", &Overrides::copy_streams}, {"SG_STAGE_SLOTS", &Overrides::stage_slots},
     {"SG_ARENA", &Overrides::arena}, {"SG_NO_FOLD", &Overrides::no_fold}, {"SG_K1A_PAIR", &Overrides::k1a_pair},
     {"SG_K5_FORM", &Overrides::k5_form}, {"SG_K5_EFEAT", &Overrides::k5_efeat},
+    {"SG_K3_IN_FORM", &Overrides::k3_in_form}, {"SG_K3_FEAT_LANES", &Overrides::k3_feat_lanes},
 };
 #ifdef SG_DEV_KNOBS
 inline Overrides from_env() {
@@ -97,6 +98,8 @@ struct Plan {
     u32 k5_grid = 0;
     u32 k5_form = 0;                          // k5_edge_score: 0 = sixteen lanes per edge, 1 = one lane per edge (k5_edge_score_lanes); k5_grid is the form's own
     u32 k5_efeat = 0;                         // form 1 only: the score kernel computes the edge features itself — k3_node_features launches no edge workgroups, efeat / latz / errr do not exist
+    u32 k3_in_form = 0;                       // k3_in_part: 0 = the loads of a trip under their tests, 1 = all of a trip's loads unconditional and issued together (k3_in_part<1>)
+    u32 k3_feat_lanes = 0;                    // k5_efeat only (no edge workgroups): k3_node_features_lanes — eight lanes per node, the partials in one round trip
     bool k3_fuse_allowed = true;              // the one-call pipelines may fold k3_in_reduce into k3_in_part's launch
     bool k6_one_wg = false;                   // the round-3 single-workgroup halo-list builder
     bool use_mfma = true;
@@ -147,6 +150,12 @@ inline u32 k5_form_default(const sg_config& cfg) { return cfg.world <= 1 && cfg.
 // Form 1 with the edge features inline (k5_edge_score_lanes<.., true>): what an engine of form 1 takes unasked, set by the same-box A/B
 // of profiles/k5_efeat_ab_c3.txt; SG_K5_EFEAT=0/1 names it in the development build.  It exists for form 1 only.
 constexpr bool kK5EfeatDefault = true;
+// K3's batched loads, each behind its own constant, set by the same-box A/B of profiles/k3_forms_ab_c3.txt.  k3_in_part<1>: lower in every
+// round there, so an engine of the measured shape takes it unasked — the shape of K5's form 1 (C3); C2 and a config-5 shard were not
+// measured and keep form 0.  k3_node_features_lanes (node-only launches, k5_efeat): its kernel is shorter but the window was not lower in
+// every round, so it stays behind SG_K3_FEAT_LANES=1 in the development build.
+constexpr bool kK3InFormDefault = true, kK3FeatLanesDefault = false;
+inline u32 k3_in_form_default(const sg_config& cfg) { return kK3InFormDefault && k5_form_default(cfg) ? 1u : 0u; }
 constexpr size_t kK5LanesWgLds = 4 * 8192;
 constexpr int kK5LanesWaves = 3;
 constexpr int k5_lanes_wgs_per_cu() { return (int)std::min<size_t>(kLdsBytes / kK5LanesWgLds, (size_t)kK5LanesWaves); }
@@ -333,6 +342,18 @@ inline int make_plan(const sg_config& cfg, const DeviceFacts& dev, const Overrid
     const int k5_per_wg = p.k5_form ? 256 : 32, k5_round = (p.k5_form ? k5_lanes_wgs_per_cu() : 3) * (int)p.cus;
     p.k5_grid = (u32)grid_for(cfg.max_edges, k5_per_wg, k5_round);
     if (ov.k5_grid) { const int x = ival(ov.k5_grid); if (x >= 1 && x <= 65535) p.k5_grid = (u32)std::min(grid_for(cfg.max_edges, k5_per_wg, 65535), x); }
+    // K3's two batched-load forms: each behind its own default, set by the same-box A/B of profiles/k3_forms_ab_c3.txt
+    p.k3_in_form = k3_in_form_default(cfg);
+    if (ov.k3_in_form) {
+        if (*ov.k3_in_form != "0" && *ov.k3_in_form != "1") { if (why) *why = "SG_K3_IN_FORM: 0 (a trip's loads under their tests) or 1 (issued together)"; return SG_EINVAL; }
+        p.k3_in_form = (u32)ival(ov.k3_in_form);
+    }
+    p.k3_feat_lanes = p.k5_efeat && kK3FeatLanesDefault ? 1u : 0u;
+    if (ov.k3_feat_lanes) {
+        if (*ov.k3_feat_lanes != "0" && *ov.k3_feat_lanes != "1") { if (why) *why = "SG_K3_FEAT_LANES: 0 (k3_node_features, two lanes per node) or 1 (k3_node_features_lanes, eight)"; return SG_EINVAL; }
+        p.k3_feat_lanes = (u32)ival(ov.k3_feat_lanes);
+        if (p.k3_feat_lanes && !p.k5_efeat) { if (why) *why = "SG_K3_FEAT_LANES=1 needs the edge features in the score kernel (SG_K5_EFEAT): the eight-lane kernel has no edge workgroups"; return SG_EINVAL; }
+    }
     p.k3_fuse_allowed = !ov.k3_no_fuse;                              // (development build: the two-launch form beside the fused one on one box)
     p.k6_one_wg = (bool)ov.k6_one_wg;
     if (ov.copy_streams) p.n_copy = ival(ov.copy_streams) == 2 ? 2 : 1;
@@ -452,6 +473,7 @@ struct Kernels {
     bool k5_mfma = true;                      // k5_node_proj (k5_edge_score's fused reset is the caller's argument)
     int k5_form = 0;                          // k5_edge_score (0) or k5_edge_score_lanes (1)
     int k5_efeat = 0;                         // k5_edge_score_lanes<.., EFEAT>: the edge features computed inline
+    int k3_in_form = 0, k3_feat_lanes = 0;    // k3_in_part<FORM>; k3_node_features (0) or k3_node_features_lanes (1)
 };
 inline PassAKernel choose_pass_a(const Plan& p, const PassA& a, const sg_config& cfg) {
     PassAKernel k;
@@ -476,6 +498,7 @@ inline Kernels choose_kernels(const Plan& p, const PassA& a, const sg_config& cf
     }
     k.k2_dh = p.dh_g != 0;
     k.k4_split = p.k4_split; k.k4_mfma = p.use_mfma; k.k5_mfma = p.use_mfma; k.k5_form = (int)p.k5_form; k.k5_efeat = (int)p.k5_efeat;
+    k.k3_in_form = (int)p.k3_in_form; k.k3_feat_lanes = (int)p.k3_feat_lanes;
     return k;
 }
 

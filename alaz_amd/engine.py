@@ -23,7 +23,7 @@ LIB_DEV_PATH = os.path.join(_HERE, "lib", "libservicegraph_dev.so")
 #: the knobs the development build reads (csrc/sg_plan.hpp kKnobs); ServiceGraph(dev_knobs=None) picks that build when one of them is set
 DEV_KNOBS = ("SG_ABLATE", "SG_NP", "SG_HT", "SG_CT", "SG_NWG", "SG_NSUB", "SG_SPLIT", "SG_WARM", "SG_K1A", "SG_K1_NARROW", "SG_K1_LEGACY", "SG_K1B_U",
              "SG_K1B_THREADS", "SG_K1B_PACK", "SG_K1B_NO_ORDER", "SG_L2_GLOBAL", "SG_L2_U32", "SG_DH_G", "SG_K3_SLICES", "SG_K3_NO_FUSE", "SG_K4_FUSED", "SG_K5_GRID", "SG_K6_ONE_WG", "SG_DENSE_VALU",
-             "SG_COPY_STREAMS", "SG_STAGE_SLOTS", "SG_ARENA", "SG_NO_FOLD", "SG_K1A_PAIR", "SG_K5_FORM", "SG_K5_EFEAT")
+             "SG_COPY_STREAMS", "SG_STAGE_SLOTS", "SG_ARENA", "SG_NO_FOLD", "SG_K1A_PAIR", "SG_K5_FORM", "SG_K5_EFEAT", "SG_K3_IN_FORM", "SG_K3_FEAT_LANES")
 
 SG_OK, SG_EINVAL, SG_ENOMEM, SG_ENODEV, SG_ENOSPC, SG_EAGAIN, SG_ESTATE = 0, -22, -12, -19, -28, -11, -71
 SELECT_MAX_K = 16384      # SG_SELECT_MAX_K: the largest k of a top-k selection
@@ -237,6 +237,7 @@ def _signatures() -> dict:
         "sg_pass_a_pair_get": (I, [H, C.POINTER(u32)]),
         "sg_k5_form_get": (I, [H, C.POINTER(u32)]),
         "sg_k5_efeat_get": (I, [H, C.POINTER(u32)]),
+        "sg_k3_forms_get": (I, [H, C.POINTER(u32), C.POINTER(u32)]),
         "sg_comm_unique_id": (I, [P, sz]), "sg_comm_create": (I, [P, sz, I, I, I, PP]),
         "sg_comm_destroy": (I, [P]), "sg_window_run_sharded": (I, [H, P, P]),
         "sg_host_register": (I, [H, P, sz]), "sg_host_unregister": (I, [H, P]), "sg_ingest_pinned": (I, [H, P, sz]),
@@ -584,8 +585,10 @@ class ServiceGraph:
         self._ck(self._l.sg_k5_form_get(self._h, C.byref(form)))
         efeat = C.c_uint32(0)
         self._ck(self._l.sg_k5_efeat_get(self._h, C.byref(efeat)))
+        k3in, k3feat = C.c_uint32(0), C.c_uint32(0)
+        self._ck(self._l.sg_k3_forms_get(self._h, C.byref(k3in), C.byref(k3feat)))
         return {**{n: int(getattr(g, n)) for n, _ in SgGeometry._fields_}, "prepare_fold": int(fold.value), "pass_a_pair": int(pair.value), "k5_form": int(form.value),
-                "k5_efeat": int(efeat.value)}
+                "k5_efeat": int(efeat.value), "k3_in_form": int(k3in.value), "k3_feat_lanes": int(k3feat.value)}
 
     def k1_kernels(self) -> tuple:
         """Names of the two K1 kernels this engine launches (as rocprofv3 lists them), or the single global-table kernel."""

@@ -1375,6 +1375,10 @@ int sg_k5_form_get(sg_handle h, uint32_t* out);
  * 1 when k5_edge_score_lanes computes them for its own edge (form 1 only; the engine then holds no feature arrays).  Same rows, bit
  * for bit. */
 int sg_k5_efeat_get(sg_handle h, uint32_t* out);
+/* K3's forms, beside sg_geometry likewise: *in_form = 1 when k3_in_part issues all loads of a trip together (0: under their tests, one
+ * by one), *feat_lanes = 1 when the node features run eight lanes per node (k3_node_features_lanes; node-only launches, i.e. beside
+ * sg_k5_efeat_get = 1).  Same statistics and features, bit for bit. */
+int sg_k3_forms_get(sg_handle h, uint32_t* in_form, uint32_t* feat_lanes);
 
 /* Per-kernel timing, measured on the launch stream.  Groups: 1 = K1 pass A (k1a_partition / k1_resolve_aggregate, one record
  * per batch), 7 = K1 pass B (k1b_merge) — both by the dispatch's own begin/end stamps; 2 = K2 csr_build (two records per window:
