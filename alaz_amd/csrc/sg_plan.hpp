@@ -7,7 +7,7 @@
 // library holds (k*Keys), which servicegraph.hip expands into its kernel tables.
 // It owns the memory layout of every opt-in stage too: each plan_* cuts its stage's one device block with Block and keeps the
 // offsets beside the sizes, so that servicegraph.hip only adds an offset to the block's base.
-// No HIP in this file: tests/micro/plan_test.cpp drives it on the CPU and tests/test_plan.py compares its plans with the
+// No HIP in this file: tests/micro/plan_driver.cpp, stage plan, drives it on the CPU and tests/test_plan.py compares its plans with the
 // ones the engine made before it existed (tests/golden/plans.json).
 #pragma once
 #include <algorithm>
@@ -503,7 +503,7 @@ inline Kernels choose_kernels(const Plan& p, const PassA& a, const sg_config& cf
 }
 
 // The instantiations the library holds, per family: one key per kernel, its template arguments in the kernel's own order (pass B's
-// last element: share).  servicegraph.hip expands these into its kernel tables; plan_test --domains prints them.
+// last element: share).  servicegraph.hip expands these into its kernel tables; plan_driver plan --domains prints them.
 template <size_t N> using Key = std::array<int, N>;
 template <size_t... L>
 constexpr std::array<Key<sizeof...(L)>, (L * ...)> product(const int (&... v)[L]) {      // every combination of one value per list
@@ -813,7 +813,7 @@ inline int check_node_trend(const sg_trend_params& p, u32 ncap, sg_trend_params*
     return check_trend(q, 0, out);
 }
 // K10: two samples per node row, [ncap] sg_node_trend per slot.  The node plan is K8's type; NodeTrendPlan names it for the CPU
-// driver tests/micro/node_trend_plan_test.cpp.
+// driver tests/micro/plan_driver.cpp, stage node_trend.
 using NodeTrendPlan = TrendPlan;
 inline TrendPlan plan_node_trend(u32 ncap, u32 slots, const sg_trend_params& p) {
     return plan_baseline(p, 2 * (u64)ncap, std::max<u64>(ncap, 1) * sizeof(sg_node_trend), slots);
@@ -1157,7 +1157,7 @@ inline int check_group_trend(const sg_trend_params& p, u64 max_edges, sg_trend_p
     return check_trend(q, max_edges, out);
 }
 // K15: one sample per group edge, [max_edges] sg_edge_trend per slot.  GroupTrendPlan names K8's type for the CPU driver
-// tests/micro/group_trend_plan_test.cpp.
+// tests/micro/plan_driver.cpp, stage group_trend.
 using GroupTrendPlan = TrendPlan;
 inline TrendPlan plan_group_trend(u64 max_edges, u32 slots, const sg_trend_params& p) {
     return plan_baseline(p, max_edges, std::max<u64>(max_edges, 1) * sizeof(sg_edge_trend), slots);

@@ -10,7 +10,9 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from alaz_amd import engine as eng
+from alaz_amd import replay
 from alaz_amd.replay import ip_str
+from oracle.pyoracle import TCP_WIRE_SIZE
 
 CLOCK = (1_000_000_000, 1_700_000_000_000_000_000)   # FirstKernelTime, FirstUserspaceTime
 
@@ -77,3 +79,39 @@ def compare_edge_dicts(got: dict, want: dict, score_tol: float = 1e-5, percentil
             assert g[9:11] == w[9:11], f"p50/p99 differ on {k}: {g[9:11]} vs {w[9:11]}"
         worst = max(worst, abs(g[5] - w[5]))
     return worst
+
+
+def ref(t, v):
+    return (t << 30) | v
+
+
+def G(g):
+    return (eng.REF_GROUP << 30) | g
+
+
+# ---- wire records ----------------------------------------------------------------------------------------------------------------
+def _wire(saddr, daddr, *, proto=1, method=1, status=200, dur=50, wt=0, payload=b"GET /user HTTP1.1", tls=0, sport=40000, dport=80):
+    r = bytearray(replay.L7_WIRE_SIZE)
+    r[0:8] = (7).to_bytes(8, "little"); r[8:16] = wt.to_bytes(8, "little"); r[16:20] = (99).to_bytes(4, "little")
+    r[20:24] = status.to_bytes(4, "little"); r[24:32] = dur.to_bytes(8, "little"); r[32] = proto; r[33] = method
+    r[36:36 + len(payload)] = payload; r[1060:1064] = len(payload).to_bytes(4, "little"); r[1064] = 1; r[1066] = tls
+    r[1076:1080] = saddr.to_bytes(4, "little"); r[1080:1082] = sport.to_bytes(2, "little")
+    r[1084:1088] = daddr.to_bytes(4, "little"); r[1088:1090] = dport.to_bytes(2, "little")
+    return bytes(r)
+
+
+def _tcp_wire(recs):
+    """BpfTcpEvent records (ebpf/tcp_state/tcp.go:63-72)."""
+    buf = np.zeros((len(recs), TCP_WIRE_SIZE), dtype=np.uint8)
+    for i, (typ, pid, fd, ts, saddr, sport, daddr, dport) in enumerate(recs):
+        r = buf[i]
+        r[0:8] = np.frombuffer(np.uint64(fd).tobytes(), np.uint8); r[8:16] = np.frombuffer(np.uint64(ts).tobytes(), np.uint8)
+        r[16:20] = np.frombuffer(np.uint32(typ).tobytes(), np.uint8); r[20:24] = np.frombuffer(np.uint32(pid).tobytes(), np.uint8)
+        r[24:26] = np.frombuffer(np.uint16(sport).tobytes(), np.uint8); r[26:28] = np.frombuffer(np.uint16(dport).tobytes(), np.uint8)
+        r[28:32] = [int(x) for x in saddr.split(".")]; r[44:48] = [int(x) for x in daddr.split(".")]
+    return buf.tobytes()
+
+
+def _ip(s):
+    a, b, c, d = (int(x) for x in s.split("."))
+    return (a << 24) | (b << 16) | (c << 8) | d

@@ -1,5 +1,5 @@
 """What the CPU tests of the opt-in stages' plans share: the checks of a stage block's memory layout as its driver under tests/micro
-prints it (tests/micro/plan_layout.hpp) — "layout": [[name, off, bytes], ...] in the order sg_plan.hpp's Block handed the pieces
+prints it (tests/micro/plan_json.hpp) — "layout": [[name, off, bytes], ...] in the order sg_plan.hpp's Block handed the pieces
 out, "slot": [off, bytes] and "slot_rel": {name: offset inside a slot} for the per-slot region.  servicegraph.hip adds exactly these
 offsets to the block's base, so a piece that overlaps its neighbour, runs past total_bytes or is smaller than what a kernel writes
 fails here, on the CPU."""

@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine
-from tests import test_engine_front as front
-from tests.test_abi import LAYOUTS
+from tests.abi_layouts import LAYOUTS
+from tests import engine_front as front
 
 U4, same, pattern, INF = front.U4, front.same, front.pattern, front.INF
 H, I, F, O, S, SO, Out = front.H, front.I, front.F, front.O, front.S, front.SO, front.Out
@@ -23,17 +23,7 @@ NEW_ABI = {
 _TREND = [("shift", 4), ("warmup", 4), ("ttl", 64), ("max_entries", 0), ("lat_floor_ns", 1000), ("err_floor", 10486)]
 
 
-@pytest.fixture
-def g(monkeypatch):
-    monkeypatch.setattr(front, "ABI", {**front.ABI, **NEW_ABI})
-    spans = []
-    monkeypatch.setattr(engine, "np", front.Numpy(spans))
-    g = object.__new__(engine.ServiceGraph)
-    g._h = C.c_void_p(0x5A5A)
-    g.layers, g.max_edges, g.max_batch, g.rank, g.world = 2, 100, 1 << 16, 0, 1
-    g._l = front.Lib(g._h, spans)
-    yield g
-    g._h = None
+g = front.abi_fixture(NEW_ABI)
 
 
 def _trend_bytes(**over):

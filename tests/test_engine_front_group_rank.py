@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine
-from tests import test_engine_front as front
-from tests.test_abi import LAYOUTS
+from tests.abi_layouts import LAYOUTS
+from tests import engine_front as front
 
 U4, same, pattern, INF = front.U4, front.same, front.pattern, front.INF
 H, I, F, O, S, Out = front.H, front.I, front.F, front.O, front.S, front.Out
@@ -21,17 +21,7 @@ NEW_ABI = {
 _RANK = [("iters", 0), ("damping_q8", 0), ("seed", 0), ("seed_min_score", 0.0)]
 
 
-@pytest.fixture
-def g(monkeypatch):
-    monkeypatch.setattr(front, "ABI", {**front.ABI, **NEW_ABI})
-    spans = []
-    monkeypatch.setattr(engine, "np", front.Numpy(spans))
-    g = object.__new__(engine.ServiceGraph)
-    g._h = C.c_void_p(0x5A5A)
-    g.layers, g.max_edges, g.max_batch, g.rank, g.world = 2, 100, 1 << 16, 0, 1
-    g._l = front.Lib(g._h, spans)
-    yield g
-    g._h = None
+g = front.abi_fixture(NEW_ABI)
 
 
 def _rank_bytes(**over):

@@ -1,12 +1,11 @@
 """The front end's methods of the workload tracks (K19) against the recording stand-in of tests/test_engine_front.py: the C calls
 they make, what they return and the texts of their errors."""
-import ctypes as C
 import struct
 
 import pytest
 
 from alaz_amd import engine
-from tests import test_engine_front as front
+from tests import engine_front as front
 
 same, pattern = front.same, front.pattern
 H, O, S, SO = front.H, front.O, front.S, front.SO
@@ -20,17 +19,7 @@ TWIN = {"sg_set_group_tracks": "sg_set_tracks", "sg_window_group_incident_tracks
         "sg_group_track_entries": "sg_track_entries", "sg_group_track_stats_get": "sg_track_stats_get"}
 
 
-@pytest.fixture
-def g(monkeypatch):
-    monkeypatch.setattr(front, "ABI", {**front.ABI, **NEW_ABI})
-    spans = []
-    monkeypatch.setattr(engine, "np", front.Numpy(spans))
-    g = object.__new__(engine.ServiceGraph)
-    g._h = C.c_void_p(0x5A5A)
-    g.layers, g.max_edges, g.max_batch, g.rank, g.world = 2, 100, 1 << 16, 0, 1
-    g._l = front.Lib(g._h, spans)
-    yield g
-    g._h = None
+g = front.abi_fixture(NEW_ABI)
 
 
 def _bytes(**over):

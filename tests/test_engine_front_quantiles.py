@@ -1,13 +1,12 @@
 """The front end's methods of the latency percentiles (K20) against the recording stand-in of tests/test_engine_front.py: the C calls
 they make (argument order, buffers inside numpy arrays), the shapes and dtypes they return, the default {500, 990}, and the texts of
 their errors."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine
-from tests import test_engine_front as front
+from tests import engine_front as front
 
 same, pattern = front.same, front.pattern
 H, I, O, U4 = front.H, front.I, front.O, front.U4
@@ -23,17 +22,7 @@ NEW_ABI = {
 }
 
 
-@pytest.fixture
-def g(monkeypatch):
-    monkeypatch.setattr(front, "ABI", {**front.ABI, **NEW_ABI})
-    spans = []
-    monkeypatch.setattr(engine, "np", front.Numpy(spans))
-    g = object.__new__(engine.ServiceGraph)
-    g._h = C.c_void_p(0x5A5A)
-    g.layers, g.max_edges, g.max_batch, g.rank, g.world = 2, 100, 1 << 16, 0, 1
-    g._l = front.Lib(g._h, spans)
-    yield g
-    g._h = None
+g = front.abi_fixture(NEW_ABI)
 
 
 def test_the_new_c_functions_are_in_the_signature_table():

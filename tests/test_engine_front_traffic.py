@@ -7,7 +7,7 @@ import struct
 import pytest
 
 from alaz_amd import engine
-from tests import test_engine_front as front
+from tests import engine_front as front
 
 same, pattern, INF = front.same, front.pattern, front.INF
 H, I, F, O, S, SO, U4, Out = front.H, front.I, front.F, front.O, front.S, front.SO, front.U4, front.Out
@@ -35,17 +35,7 @@ def _packed(**over):
     return struct.pack("<4I2Q2I", 40, *[over.get(f, d) for f, d in _FIELDS], 0)
 
 
-@pytest.fixture
-def g(monkeypatch):
-    monkeypatch.setattr(front, "ABI", {**front.ABI, **NEW_ABI})
-    spans = []
-    monkeypatch.setattr(engine, "np", front.Numpy(spans))
-    g = object.__new__(engine.ServiceGraph)
-    g._h = C.c_void_p(0x5A5A)
-    g.layers, g.max_edges, g.max_batch, g.rank, g.world = 2, 100, 1 << 16, 0, 1
-    g._l = front.Lib(g._h, spans)
-    yield g
-    g._h = None
+g = front.abi_fixture(NEW_ABI)
 
 
 def test_eleven_functions_one_struct_three_constant_sets():

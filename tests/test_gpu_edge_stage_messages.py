@@ -10,7 +10,7 @@ import pytest
 
 from alaz_amd import engine, replay
 from alaz_amd.engine import SG_EINVAL, SG_ESTATE, SG_OK
-from tests.test_gpu_node_trend import _engine, _feed
+from tests.gpu_scaffold import _engine, _feed
 
 pytestmark = pytest.mark.gpu
 

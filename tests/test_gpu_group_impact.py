@@ -13,13 +13,12 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine
+from tests.gpu_scaffold import _d2h, _engine, _events, _feed, _grouped, _hip, _pods_engine, _rc
 from tests.group_ref import group_ref
+from tests.helpers import G
 from tests.impact_ref import impact_ref
 from tests.incident_ref import quantile_threshold
-from tests.test_gpu_group_nodes import _events
-from tests.test_gpu_groups import _grouped, _pods_engine
-from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +28,6 @@ NOH = engine.NO_HOPS
 INF = float("inf")
 FAST, SLOW = 1_000_000, 200_000_000
 (EXPOSED, DIRECT, FAR, ENTRIES, ENTRY_COUNT, ENTRY_ERR, INTO_COUNT, INTO_ERR) = range(8)
-
-
-def G(g):
-    return (engine.REF_GROUP << 30) | g
 
 
 def _check(g, mi, mh, ge=None, gn=None, incs=None, inc=None, got=None):

@@ -12,13 +12,11 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _d2h, _engine, _events, _feed, _grouped, _hip, _pairs, _pods_engine, _rc, _send
 from tests.group_incident_ref import group_incident_ref, group_values
-from tests.helpers import CLOCK, HostShim
+from tests.helpers import CLOCK, G, HostShim
 from tests.incident_ref import quantile_threshold
-from tests.test_gpu_group_nodes import _events, _send
-from tests.test_gpu_groups import _grouped, _pairs, _pods_engine
-from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +26,6 @@ INF = float("inf")
 EXT = 0x5DB8D800                                                      # addresses outside the cluster
 TREND = dict(shift=3, warmup=2, ttl=4)
 BYS = ("score", "lat_dev", "err_dev")
-
-
-def G(g):
-    return (engine.REF_GROUP << 30) | g
 
 
 def _check(g, by="score", thr=0.0, ranked=False, ge=None, gn=None, trend=None, rank=None, got=None, ginc=None):

@@ -11,15 +11,13 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import EXT, RUNS, _d2h, _engine, _events, _feed, _grouped, _hip, _map, _pairs, _pods_engine, _rc, _send
 from tests.group_nodes_ref import GroupNodeTrendRef, gk_of_refs, group_nodes_ref, group_nodes_rows, ref_select_group_nodes
 from tests.group_ref import group_ref
-from tests.helpers import CLOCK, HostShim
+from tests.helpers import CLOCK, G, HostShim
 from tests.node_trend_ref import NodeTrendRef
 from tests.nodes_ref import nodes_ref
-from tests.test_gpu_groups import _grouped, _map, _pairs, _pods_engine
-from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixtures)
-from tests.test_gpu_nodes import RUNS
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +26,6 @@ ML = 256                                                              # max_labe
 PARAMS = dict(shift=3, warmup=2, ttl=2)
 STATS = ("windows", "entries", "inserted", "expired", "dropped")
 INF = float("inf")
-EXT = 0x5DB8D800                                                      # addresses outside the cluster
-
-
-def G(g):
-    return (engine.REF_GROUP << 30) | g
 
 
 def _check(g, mg, mk, ml, rows=None, gmap=None):
@@ -91,30 +84,6 @@ def test_churn_is_exact_and_a_twin_without_it_is_unchanged(churn, kind):
 
 
 # ---- constructed windows ---------------------------------------------------------------------------------------------------------
-def _events(topo, src, daddr, dur=1_000_000, alive=None, status=None, label=None):
-    """one request (or, where alive, one alive record) per (src pod, destination address) pair"""
-    src = np.asarray(src, dtype=np.int64)
-    e = np.zeros(len(src), dtype=replay.EVENT_DTYPE)
-    e["saddr"] = topo.pod_ips[src]; e["daddr"] = daddr
-    e["status"] = 200 if status is None else status
-    e["protocol"] = replay.PROTO_HTTP
-    e["duration_ns"] = dur
-    e["write_time_ns"] = np.uint64(2_000_000_000) + np.uint64(100) * np.arange(len(e), dtype=np.uint64)
-    if label is not None:
-        e["host_label"] = label
-    if alive is not None:
-        a = np.asarray(alive, bool)
-        e["flags"][a] = replay.EV_ALIVE
-        e["status"][a] = 0; e["protocol"][a] = 0; e["duration_ns"][a] = 0
-    return e
-
-
-def _send(topo, g, src, dst, **kw):
-    e = _events(topo, src, topo.pod_ips[np.asarray(dst, dtype=np.int64)], **kw)
-    if len(e):
-        g.ingest_bulk(e)
-    return g.flush_window().copy()
-
 
 # ---- 2. the out side ----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")

@@ -10,14 +10,12 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _d2h, _engine, _events, _feed, _grouped, _hip, _pods_engine, _rc, _send
 from tests.group_rank_ref import group_rank_ref, seed_sum
-from tests.helpers import CLOCK, HostShim
+from tests.helpers import CLOCK, G, HostShim
 from tests.probe_weights import offsets
 from tests.rank_ref import M, ref_select_rank
-from tests.test_gpu_group_nodes import _events, _send
-from tests.test_gpu_groups import _grouped, _pods_engine
-from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +23,6 @@ NO = engine.NO_GROUP
 NR = 8192                                                             # K17_NR: workload rows per range of k17_edge
 INF = float("inf")
 EXT = 0x5DB8D800                                                      # addresses outside the cluster
-
-
-def G(g):
-    return (engine.REF_GROUP << 30) | g
 
 
 def _check(g, ge=None, gn=None, got=None, **params):

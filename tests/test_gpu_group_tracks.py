@@ -9,13 +9,11 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _d2h, _engine, _events, _feed, _grouped, _hip, _rc, _send
 from tests.group_track_ref import GroupTrackRef
-from tests.helpers import CLOCK, HostShim
+from tests.helpers import CLOCK, G, HostShim
 from tests.incident_ref import quantile_threshold
-from tests.test_gpu_group_nodes import _events, _send
-from tests.test_gpu_groups import _grouped
-from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +25,6 @@ TREND = dict(shift=3, warmup=2, ttl=4)
 ALL = dict(by="score", min_value=-INF)                                # every group edge is red (a score is never NaN here)
 EXT = 0x5DB8D800                                                      # addresses outside the cluster
 LABEL, OBIP = 1 << 30, 2 << 30
-
-
-def G(g):
-    return (engine.REF_GROUP << 30) | g
 
 
 def _nc(g, max_groups):

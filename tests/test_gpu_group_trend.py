@@ -10,12 +10,11 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _d2h, _engine, _feed, _grouped, _hip, _map, _pairs, _path, _pods_engine, _rc
 from tests.group_ref import group_ref
 from tests.group_trend_ref import GroupTrendRef, GroupVanishRef, ref_select_groups
 from tests.helpers import CLOCK, HostShim
-from tests.test_gpu_groups import _grouped, _map, _pairs, _pods_engine
-from tests.test_gpu_node_trend import _engine, _feed, _path, _rc, churn, warm_stream  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn, warm_stream  # noqa: F401  (the fixtures)
 from tests.vanish_ref import NO_ROW
 
 pytestmark = pytest.mark.gpu

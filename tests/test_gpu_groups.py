@@ -6,12 +6,11 @@ the radix sort (4096-position tiles, 2048-position fold chunks, odd and even pas
 import numpy as np
 import pytest
 
-from alaz_amd import engine, replay, weights
+from alaz_amd import engine, replay
+from tests.gpu_scaffold import _d2h, _engine, _feed, _grouped, _hip, _map, _pairs, _path, _pods_engine, _rc
 from tests.group_ref import group_ref
-from tests.helpers import CLOCK, HostShim
 from tests.nodes_ref import nodes_ref
-from tests.test_gpu_node_trend import _engine, _feed, _path, _rc, churn, warm_stream  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn, warm_stream  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,24 +33,6 @@ def _check(g, rows, gmap, mg, mk, ml=ML, got=None, rng=None):
         assert g.window_row_group(idx).tolist() == wrg[idx].tolist()
         assert _rc(g.window_row_group, np.array([len(rows)], np.uint32)) == engine.SG_EINVAL
     return ge
-
-
-def _map(kind, mk, n_pods):
-    m = np.full(mk, NO, np.uint32)
-    if kind == "blocks":
-        m[:n_pods] = np.arange(n_pods) // 7
-    elif kind == "one":
-        m[:n_pods] = 0
-    return m
-
-
-def _grouped(topo, labels, kind, **kw):
-    g = _engine(topo, labels, **kw)
-    mk = topo.n_nodes + 8
-    gmap = _map(kind, mk, topo.n_pods)
-    g.set_groups()
-    g.group_assign(np.arange(mk), gmap)
-    return g, gmap, mk
 
 
 @pytest.mark.parametrize("kind", ["none", "blocks", "one"])
@@ -83,24 +64,6 @@ def test_warm_delta_and_cold_windows(warm_stream, kind):
 
 
 # ---- constructed windows: pod-to-pod events only, one request per (src pod, dst pod) pair ------------------------------------------
-N_PODS = 150                                                          # 22 350 ordered pairs: windows of up to 3 tiles + 1 rows
-
-
-def _pods_engine(max_known=None, max_groups=0, n_pods=N_PODS, **kw):
-    topo = replay.make_topology(n_pods, 4 * n_pods, seed=7, svcs=4)    # (only the pods and their ids are used)
-    mk = max_known or topo.n_nodes + 8
-    g = engine.ServiceGraph(max_known_nodes=mk, max_edges=1 << 14, layers=2, max_labels=kw.pop("max_labels", 16),
-                            max_outbound_ips=kw.pop("max_outbound_ips", 64), max_window_events=1 << 16, max_batch=1 << 14, **kw)
-    g.set_clock(*CLOCK); g.load_weights(weights.make_weights(2))
-    HostShim().apply(g, topo.k8s_ops()); g.set_label_count(0)
-    return topo, g, mk
-
-
-def _pairs(n_pods, E, seed):
-    """E distinct (src, dst) pairs, src != dst, from a seeded permutation of all of them"""
-    allp = np.array([(i, j) for i in range(n_pods) for j in range(n_pods) if i != j])
-    p = allp[np.random.default_rng(seed).permutation(len(allp))[:E]]
-    return p[:, 0], p[:, 1]
 
 
 def _close(topo, g, src, dst):

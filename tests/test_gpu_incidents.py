@@ -7,37 +7,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from alaz_amd import engine, replay, weights
-from tests.helpers import CLOCK, HostShim
+from alaz_amd import engine
+from tests.gpu_scaffold import _check_incidents as _check, _d2h, _engine, _feed, _hip, _incident_close as _close, _incident_pods_engine as _pods_engine, _path, _rc
 from tests.incident_ref import QUANTILES, incident_ref, quantile_threshold, row_values
 from tests.nodes_ref import nodes_ref
-from tests.test_gpu_node_trend import _engine, _feed, _path, _rc, churn, warm_stream  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn, warm_stream  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
 INF = float("inf")
 NO = engine.NO_INCIDENT
 TREND = dict(shift=3, warmup=2, ttl=4)
-
-
-def _check(g, rows, by="score", thr=0.0, nodes=None, got=None, ginc=None):
-    """the last read window's incidents (or `got`, `ginc`) against the reference over `rows`, the window's node rows and — where the
-    engine has them — its trend and rank rows"""
-    nodes = g.window_nodes() if nodes is None else nodes
-    trend = g.window_trend() if by != "score" else None
-    try:
-        rank = g.window_rank()
-    except engine.ServiceGraphError:
-        rank = None                                                   # the ranking is off
-    want, winc = incident_ref(rows, nodes, by, thr, trend=trend, rank=rank)
-    got = g.window_incidents() if got is None else got
-    ginc = g.window_node_incident() if ginc is None else ginc
-    assert len(got) == len(want), (len(got), len(want), by, thr)
-    assert got.tobytes() == want.tobytes(), (by, thr)
-    assert ginc.tobytes() == winc.tobytes()
-    assert (got["culprit_node"] == NO).all() == (rank is None or len(got) == 0)
-    return got
 
 
 @pytest.mark.parametrize("by,ranked", [("score", False), ("score", True), ("lat_dev", False), ("err_dev", True)])
@@ -271,31 +251,6 @@ def test_window_run_and_read(churn):
 
 
 # ---- constructed windows with known answers: pod-to-pod events only and min_value = -inf, so every row is red ---------------------
-def _pods_engine(n_pods, max_known=None, max_edges=1 << 14):
-    topo = replay.make_topology(n_pods, 4 * n_pods, seed=7, svcs=4)    # (only the pods and their ids are used)
-    g = engine.ServiceGraph(max_known_nodes=max_known or topo.n_nodes + 8, max_edges=max_edges, layers=2, max_labels=16, max_outbound_ips=64,
-                            max_window_events=1 << 16, max_batch=1 << 14)
-    g.set_clock(*CLOCK); g.load_weights(weights.make_weights(2))
-    HostShim().apply(g, topo.k8s_ops()); g.set_label_count(0)
-    g.set_nodes(); g.set_rank(iters=2); g.set_incidents(min_value=-INF)
-    return topo, g
-
-
-def _close(topo, g, src, dst):
-    """one request per (src pod, dst pod) pair; the window's rows, its incidents and the incident per node row (checked against
-    the reference); pod i has node id i, so its KNOWN ref is i and the node rows are ascending in pod id"""
-    src, dst = np.asarray(src), np.asarray(dst)
-    e = np.zeros(len(src), dtype=replay.EVENT_DTYPE)
-    e["saddr"] = topo.pod_ips[src]; e["daddr"] = topo.pod_ips[dst]; e["status"] = np.where(np.arange(len(e)) % 3 == 0, 503, 200)
-    e["protocol"] = replay.PROTO_HTTP
-    e["duration_ns"] = 1_000_000 + 37 * np.arange(len(e), dtype=np.uint64)
-    e["write_time_ns"] = np.uint64(2_000_000_000) + np.uint64(100) * np.arange(len(e), dtype=np.uint64)
-    g.ingest_bulk(e)
-    rows = g.flush_window().copy()
-    assert len(rows) == len(e) and sorted(zip(rows["from_ref"].tolist(), rows["to_ref"].tolist())) == sorted(zip(src.tolist(), dst.tolist()))
-    nodes = g.window_nodes()
-    got = _check(g, rows, "score", -INF, nodes)
-    return rows, nodes, got, g.window_node_incident()
 
 
 @pytest.mark.parametrize("max_known", [None, 40_000])

@@ -27,11 +27,9 @@ import numpy as np
 import pytest
 
 from alaz_amd import replay, weights
-from tests import model_ref as mr
+from tests.gpu_model_scaffold import C_COUNT, C_N_NODES, MAX_LABELS, STATS, _check_oracle, _feed, _mixed, _on_edges, _oracle_windows, _sorted, _topo, bits, check_rows, check_stats, check_x0, dev_read, dev_write, knobs, oracle, trace
 from tests.helpers import CLOCK, HostShim
-from tests.test_gpu_k5_forms import _check_oracle, _feed, _mixed, _oracle_windows
-from tests.test_gpu_model_stages import C_COUNT, C_N_NODES, bits, check_rows, check_stats, check_x0, dev_read, dev_write, knobs, oracle, trace
-from tests.test_gpu_pair_tiles import MAX_LABELS, STATS, _on_edges, _sorted, _topo
+from tests import model_ref as mr
 
 pytestmark = pytest.mark.gpu
 

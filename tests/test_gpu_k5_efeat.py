@@ -22,9 +22,8 @@ import numpy as np
 import pytest
 
 from alaz_amd import replay, weights
+from tests.gpu_model_scaffold import MAX_LABELS, STATS, _check_oracle, _close, _feed, _mixed, _on_edges, _oracle_windows, _sorted, _topo
 from tests.helpers import CLOCK, HostShim
-from tests.test_gpu_k5_forms import _check_oracle, _close, _feed, _mixed, _oracle_windows
-from tests.test_gpu_pair_tiles import MAX_LABELS, STATS, _on_edges, _sorted, _topo
 
 pytestmark = pytest.mark.gpu
 

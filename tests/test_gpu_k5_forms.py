@@ -13,13 +13,11 @@ import os
 import numpy as np
 import pytest
 
-from alaz_amd import replay, weights
-from tests.helpers import CLOCK, HostShim, compare_edge_dicts, engine_edge_dict
-from tests.test_gpu_pair_tiles import MAX_LABELS, STATS, _on_edges, _sorted, _topo
+from alaz_amd import weights
+from tests.gpu_model_scaffold import MAX_LABELS, STATS, _check_oracle, _close, _feed, _mixed, _on_edges, _oracle_windows, _sorted, _topo
+from tests.helpers import CLOCK, HostShim
 
 pytestmark = pytest.mark.gpu
-
-_ORACLE = {}
 
 
 def _engine(form, layers=1, max_edges=65536, **kw):
@@ -36,27 +34,6 @@ def _engine(form, layers=1, max_edges=65536, **kw):
     g.set_label_count(len(labels))
     assert g.geometry()["k5_form"] == form
     return g, shim
-
-
-def _feed(g, ev):
-    if len(ev):
-        while g.ingest(ev) != 0:
-            pass
-
-
-def _close(g, how, layers):
-    if how == "flush":
-        return g.flush_window().copy()
-    if how == "run":                                                 # the one-call pipeline: k5_edge_score<RESET = true>
-        g.window_run()
-        return g.window_read().copy()
-    g.window_close(); g.window_features()                            # the staged calls: RESET = false, sg_window_reset behind them
-    for l in range(layers):
-        g.window_layer(l)
-    g.window_score()
-    rows = g.window_read().copy()
-    g.window_reset()
-    return rows
 
 
 def _windows(form, windows, how="flush", layers=1, **kw):
@@ -84,40 +61,6 @@ def _both(windows, **kw):
             d = np.flatnonzero(ra["score"].view(np.uint32) != rb["score"].view(np.uint32))
             raise AssertionError(f"window {i}: form 1's rows differ from form 0's in {bad}; {len(d)} of {len(ra)} scores, first {ra['score'][d[:3]]} vs {rb['score'][d[:3]]}")
     return a, shim
-
-
-def _mixed(lo=0, hi=65536):
-    """the mixed trace of test_gpu_pair_tiles (Host labels, raw outbound IPs, reversed events), every 53rd event an open connection
-    from a pod"""
-    if ("mixed", lo, hi) not in _ORACLE:
-        topo, _, ev, _, _ = _topo()
-        ev = ev[lo:hi].copy()
-        at = np.arange(7, len(ev), 53)
-        ev["flags"][at] = replay.EV_ALIVE
-        ev["saddr"][at] = topo.pod_ips[topo.edge_src[at % len(topo.edge_src)]]
-        _ORACLE[("mixed", lo, hi)] = ev
-    return _ORACLE[("mixed", lo, hi)]
-
-
-def _oracle_windows(key, windows, layers):
-    if key not in _ORACLE:
-        from oracle import pyoracle
-        _, ops, _, _, labels = _topo()
-        o = pyoracle.Oracle(*CLOCK); o.apply_ops(ops)
-        W = weights.make_weights(layers)
-        res = []
-        for ev in windows:
-            o.packed(ev, labels); o.window_close(W, layers)
-            res.append((o.edge_dict(), o.edge_rows().copy()))
-        _ORACLE[key] = res
-    return _ORACLE[key]
-
-
-def _check_oracle(res, shim, ref):
-    labels = _topo()[4]
-    for (rows, _, ob), (edict, orow) in zip(res, ref):
-        compare_edge_dicts(engine_edge_dict(rows, shim, labels, ob), edict)
-        assert np.array_equal(rows["from_ref"], orow["from_ref"]) and np.array_equal(rows["to_ref"], orow["to_ref"])
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1000])

@@ -6,105 +6,20 @@ sg_window_score equal the oracle's.  The one-call pipelines (sg_flush_window, sg
 also project) leave the same x0 and h[l] as the staged one.  On the adversarial trace and on model_ref.boundary_trace, for every K1
 variant, both depths, both dense paths, both K4 forms, slice counts that hit every tail loop, a warm engine, node capacities beyond
 one trip of the K4 tiles (32 768) and of k3_node_features (262 144), and over buffers filled with NaN."""
-import contextlib
-import ctypes
-import os
 
 import numpy as np
 import pytest
 
 from alaz_amd import replay, weights
-from tests import model_ref as mr
-from tests import probe_weights as pw
+from tests.gpu_model_scaffold import C_COUNT, C_N_NODES, TRACES, _sync, bits, check_rows, check_stats, check_x0, dev_read, dev_write, knobs, oracle, trace
 from tests.helpers import CLOCK, HostShim
+from tests import model_ref as mr
 
 pytestmark = pytest.mark.gpu
-
-C_N_NODES, C_COUNT = 10, 40                                          # alaz_amd/csrc/sg_device.h
-SCORE_BAR = 1e-5                                                      # DESIGN.md §5
-INT_FIELDS = ("from_ref", "to_ref", "count", "err_count", "sum_ns", "max_ns", "sumsq_us", "alive")
-
-
-def _boundary_half():
-    topo, ev, labels = mr.boundary_trace()
-    return topo, ev[::2].copy(), labels
-
-
-#: name -> (trace, max_edges of its engines)
-TRACES = {
-    "adversarial": (pw.adversarial_trace, 16384),
-    "boundary": (mr.boundary_trace, 32768),
-    "boundary_known": (lambda: mr.boundary_trace(False), 32768),      # no raw outbound IPs: every window after the first may close warm
-    "boundary_half": (_boundary_half, 32768),
-    "sparse33k": (lambda: mr.sparse_trace(33_000, 32_700, 6000, seed=0x5A33), 8192),
-}
-_TRACE = {}
-
-
-def trace(name):
-    if name not in _TRACE:
-        _TRACE[name] = TRACES[name][0]()
-    return _TRACE[name]
-
-
-def oracle(name, layers):
-    """the oracle's window of the trace (closed once per process) with the float64 references of its statistics and features"""
-    o = mr.oracle_window(name, lambda: trace(name), layers, CLOCK)
-    if "ref_stats" not in o:
-        o["ref_stats"] = mr.node_stats_ref(o["rows"], o["n"], o["u"], o["v"])
-        o["ref_x0"] = mr.node_features_ref(o["ref_stats"], o["kind"])
-        o["csr"] = mr.csr_of(o["u"], o["v"], o["n"])
-    return o
-
 
 # ------------------------------------------------------------------------------------------------
 # device memory
 # ------------------------------------------------------------------------------------------------
-_HIP = []
-
-
-def _hip():
-    if not _HIP:
-        import torch  # noqa: F401  (the HIP runtime the engine shares)
-        hip = ctypes.CDLL(None)
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        hip.hipMemcpy.restype = ctypes.c_int
-        _HIP.append(hip)
-    return _HIP[0]
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def dev_read(ptr, shape, dtype):
-    _sync()
-    buf = np.empty(shape, dtype=dtype)
-    assert _hip().hipMemcpy(buf.ctypes.data, ctypes.c_void_p(ptr), buf.nbytes, 2) == 0
-    return buf
-
-
-def dev_write(ptr, arr):
-    _sync()
-    a = np.ascontiguousarray(arr)
-    assert _hip().hipMemcpy(ctypes.c_void_p(ptr), a.ctypes.data, a.nbytes, 1) == 0
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-@contextlib.contextmanager
-def knobs(**kv):
-    """SG_* knobs of the development build, set while its engines are created"""
-    for k, v in kv.items():
-        os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k in kv:
-            os.environ.pop(k, None)
 
 
 class Eng:
@@ -149,37 +64,6 @@ class Eng:
 # ------------------------------------------------------------------------------------------------
 # the checks
 # ------------------------------------------------------------------------------------------------
-def check_rows(rows, want, tag):
-    assert len(rows) == len(want), tag
-    for f in INT_FIELDS:
-        assert np.array_equal(rows[f], want[f]), (tag, f)
-    d = np.abs(rows["score"].astype(np.float64) - want["score"])
-    assert d.max() <= SCORE_BAR, (tag, float(d.max()), int(np.argmax(d)))
-
-
-def check_stats(E, o, tag):
-    N = o["n"]
-    assert E.n_nodes() == N, tag
-    s, m = E.stats()
-    for ref_s, ref_m in (o["stats"], o["ref_stats"]):
-        bad = np.argwhere(s[:N] != ref_s)
-        assert len(bad) == 0, (tag, "st_sum", bad[:4].tolist(), s[:N][tuple(bad[0])], ref_s[tuple(bad[0])])
-        bad = np.argwhere(m[:N] != ref_m)
-        assert len(bad) == 0, (tag, "st_max", bad[:4].tolist())
-    assert not s[N:].any() and not m[N:].any(), (tag, "statistics beyond the window's nodes")
-
-
-def check_x0(x0, o, tag):
-    """x0[:N] within 1 ulp of the oracle's and of the float64 reference; -> is it bit-equal to the oracle's everywhere"""
-    assert np.isfinite(x0).all(), tag
-    counts = []
-    for what, ref in (("the oracle", o["x0"]), ("the float64 reference", o["ref_x0"])):
-        d = mr.ulp_distance(x0, ref)
-        counts.append(int((d != 0).sum()))
-        print(f"{tag}: {counts[-1]} of {d.size} elements of x0 are not bit-equal to {what} (max {int(d.max())} ulp)")
-        assert d.max() <= 1, (tag, what, int(d.max()), np.argwhere(d > 1)[:4].tolist())
-    assert np.all(bits(x0[:, 18:]) == 0) and np.all(x0[:, 15] == 1.0), tag
-    return counts[0] == 0 and np.array_equal(bits(x0), bits(o["x0"]))
 
 
 def check_layer_bound(hin, hout, o, l, tag):

@@ -1,91 +1,21 @@
 """K10, the per-node baselines (sg_set_node_trend / sg_window_node_trend / sg_window_node_trend_buffer / sg_node_trend_entries): the
 node trend rows and the whole node baseline after every window against the numpy reference tests/node_trend_ref.py, run on the node
 rows and outbound IPs of the same windows — byte for byte, as K8's — and an engine with it against a twin without it."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import PARAMS, _d2h, _engine, _feed, _hip, _ncap, _path, _rc
 from tests.helpers import CLOCK, HostShim
 from tests.node_trend_ref import NodeTrendRef
 from tests.nodes_ref import nodes_ref
+from tests.traces import _drift
+from tests.traces import churn, warm_stream  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
 ME = 1 << 15
-PARAMS = dict(shift=3, warmup=2, ttl=3, max_entries=700)       # a small ttl, and a capacity the churn overflows
-
-
-def _engine(topo, labels, layers=2, *, variant=0, max_edges=ME, max_obip=512, **kw):
-    if variant == 0:                                                  # the 8-byte-record path with the warm state kept
-        kw.setdefault("warm", True)
-        variant = 3
-    g = engine.ServiceGraph(max_known_nodes=topo.n_nodes + 8, max_edges=max_edges, layers=layers, max_labels=256,
-                            max_outbound_ips=max_obip, k1_variant=variant, max_window_events=kw.pop("max_window_events", 300_000),
-                            max_batch=1 << 14, **kw)
-    g.set_clock(*CLOCK)
-    g.load_weights(weights.make_weights(layers))
-    HostShim().apply(g, topo.k8s_ops()); g.set_label_count(len(labels))
-    return g
-
-
-def _ncap(g):
-    return g.window_buffers()[3]                                      # the node capacity (sg_window_buffers)
-
-
-def _feed(g, ev):
-    if len(ev):
-        g.ingest_bulk(np.ascontiguousarray(ev))
-
-
-def _rc(call, *a, **kw):
-    with pytest.raises(engine.ServiceGraphError) as ei:
-        call(*a, **kw)
-    return ei.value.rc
-
-
-def _drift(ev, i, rng):
-    """window i's events with latency drifting up and a growing share of errors"""
-    e = ev.copy()
-    e["duration_ns"] = (e["duration_ns"].astype(np.float64) * (1.0 + 0.15 * i)).astype(np.uint64)
-    bad = rng.random(len(e)) < 0.02 * (i % 5)
-    e["status"][bad & (e["protocol"] == 1)] = 503
-    return e
-
-
-@pytest.fixture(scope="module")
-def churn():
-    """12 windows over one topology: whole groups of edges (and so nodes) missing from some windows, raw outbound IPs that come and
-    go (the outbound-IP list changes), Host labels, reversed events, alive-only records, latency and error drift"""
-    topo = replay.make_topology(300, 6000, seed=81)
-    ev, labels = replay.make_events(topo, 360_000, seed=82, mixed=True, with_raw_outbound=True, with_reverse=True)
-    rng = np.random.default_rng(83)
-    al = np.zeros(3000, dtype=replay.EVENT_DTYPE)
-    al["flags"] = replay.EV_ALIVE
-    al["saddr"] = topo.pod_ips[rng.integers(0, topo.n_pods, len(al))]
-    pick = rng.random(len(al))
-    al["daddr"] = np.where(pick < 0.5, topo.svc_ips[rng.integers(0, topo.n_svcs, len(al))],
-                           np.where(pick < 0.8, topo.pod_ips[rng.integers(0, topo.n_pods, len(al))], 0x5DB8D800 + rng.integers(0, 40, len(al)))).astype(np.uint32)
-    group = ((ev["saddr"].astype(np.uint64) * 2654435761 + ev["daddr"].astype(np.uint64) * 40503) >> 7) % 6
-    wins = []
-    for i in range(12):
-        part = ev[i * 30_000:(i + 1) * 30_000]
-        gp = group[i * 30_000:(i + 1) * 30_000]
-        keep = (gp != (i % 6)) & ((gp != 5) | (i < 4) | (i > 8))        # group i % 6 absent for one window; group 5 for five
-        a = al[rng.random(len(al)) < 0.3]
-        wins.append(np.concatenate([_drift(part[keep], i, rng), a]))
-    return topo, labels, wins
-
-
-@pytest.fixture(scope="module")
-def warm_stream():
-    """windows without raw outbound IPs: cold, warm (a subset), delta (another draw), warm, delta — with drift"""
-    topo = replay.make_topology(400, 30_000, seed=91)
-    (e0, labels), (e1, _), (e2, _) = (replay.make_events(topo, 150_000, seed=92 + k, fixed_labels=True) for k in range(3))
-    rng = np.random.default_rng(97)
-    wins = [_drift(w, i, rng) for i, w in enumerate([e0, e0[::3], e1, e0, e2, e1[::2], e0, e2[::2]])]
-    return topo, labels, wins
 
 
 def _check(g, ref, nodes, trend=None):
@@ -97,13 +27,6 @@ def _check(g, ref, nodes, trend=None):
     s = g.node_trend_stats()
     assert (s.windows, s.entries, s.inserted, s.expired, s.dropped) == tuple(ref.stats[k] for k in ("windows", "entries", "inserted", "expired", "dropped"))
     return want
-
-
-def _path(before, after):
-    d = {k: getattr(after, k) - getattr(before, k) for k in ("windows_cold", "windows_warm", "windows_delta", "windows_plain")}
-    if d["windows_delta"]:
-        return "delta"
-    return "warm" if d["windows_warm"] else "cold" if d["windows_cold"] else "plain" if d["windows_plain"] else "none"
 
 
 def test_churn_is_exact_and_a_twin_without_it_is_unchanged(churn):
@@ -178,19 +101,6 @@ def test_begin_end_and_index_gather(churn):
         idx = rng.integers(0, len(nodes), 37).astype(np.uint32)
         assert g.window_node_trend(idx).tobytes() == t[idx].tobytes()
         assert _rc(g.window_node_trend, np.array([len(nodes)], np.uint32)) == engine.SG_EINVAL
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
-
-
-def _d2h(hip, ptr, n, dtype):
-    out = np.zeros(n, dtype=dtype)
-    if n:
-        assert hip.hipMemcpy(out.ctypes.data, ctypes.c_void_p(ptr), out.nbytes, 2) == 0
-    return out
 
 
 @pytest.mark.parametrize("in_flight", [1, 3])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import RUNS, _feed, _hip, _path, _pods_engine
 from tests.helpers import CLOCK, HostShim
 from tests.nodes_ref import nodes_ref
 
@@ -29,11 +30,6 @@ def _engine(topo, labels, layers=2, *, variant=0, max_edges=ME, **kw):
     g.load_weights(weights.make_weights(layers))
     HostShim().apply(g, topo.k8s_ops()); g.set_label_count(len(labels))
     return g
-
-
-def _feed(g, ev):
-    if len(ev):
-        g.ingest_bulk(np.ascontiguousarray(ev))
 
 
 def _check(g, rows):
@@ -82,13 +78,6 @@ def warm_stream():
     (e0, labels), (e1, _), (e2, _) = (replay.make_events(topo, 150_000, seed=92 + k, fixed_labels=True) for k in range(3))
     wins = [e0, e0[::3], e1, e0, e2, e1[::2]]
     return topo, labels, wins
-
-
-def _path(before, after):
-    d = {k: getattr(after, k) - getattr(before, k) for k in ("windows_cold", "windows_warm", "windows_delta", "windows_plain")}
-    if d["windows_delta"]:
-        return "delta"
-    return "warm" if d["windows_warm"] else "cold" if d["windows_cold"] else "plain" if d["windows_plain"] else "none"
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 3])
@@ -174,12 +163,6 @@ def test_split_flush_with_the_next_window_fed_beside_it(churn):
         _check(g, rows)
 
 
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
-
-
 @pytest.mark.parametrize("in_flight", [1, 2])
 def test_window_run_in_flight_through_the_device_buffer(churn, in_flight):
     import torch
@@ -251,16 +234,9 @@ def test_hub_destination_and_a_source_across_many_chunks():
 @pytest.fixture(scope="module")
 def wide():
     """4200 pods, pod i with node id i, no groups: pod 5 is the caller of the long run, pods 0..4 come before it in row order"""
-    from tests.test_gpu_groups import _pods_engine                    # (that module imports this one)
     topo, g, mk = _pods_engine(n_pods=4200)
     g.set_nodes()
     return topo, g
-
-
-# (rows in front of the long run, its length): a run inside a span of K9_ROWS = 8, cut by spans, ending on an end of a chunk of
-# K9_CHUNK = 2048 (8 + 2040, 6 + 2042), crossing one, beginning at one (2048 in front), and passing THROUGH a whole chunk (6 + 4097
-# covers [2048, 4096)).  tests/test_gpu_group_nodes.py holds K16's out side to the same list.
-RUNS = [(6, 1), (6, 7), (6, 8), (6, 9), (6, 2047), (6, 2048), (6, 2049), (6, 4097), (8, 2040), (6, 2042), (2048, 9), (2047, 2049), (5, 3)]
 
 
 @pytest.mark.parametrize("front,D", RUNS)

@@ -7,18 +7,13 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine
+from tests.gpu_scaffold import PARAMS, _engine, _feed, _hip, _rc
 from tests.node_trend_ref import ref_select_nodes
-from tests.test_gpu_node_trend import PARAMS, _engine, _feed, _rc, churn  # noqa: F401  (the fixture)
+from tests.traces import churn  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 BY = list(engine.NSEL_BY)
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
 
 
 def _ks(n_cand):

@@ -14,32 +14,16 @@ import numpy as np
 import pytest
 
 from alaz_amd import replay, weights
+from tests.gpu_model_scaffold import MAX_LABELS, STATS, _CACHE, _on_edges, _sorted, _topo
 from tests.helpers import CLOCK, HostShim, compare_edge_dicts, engine_edge_dict
 
 pytestmark = pytest.mark.gpu
 
 LAYERS = 1
-MAX_LABELS = 64
+
 UNITS, TILE = 16, 2048
 KNOBS = ("SG_NP", "SG_NWG", "SG_K1A", "SG_K1A_PAIR", "SG_CT", "SG_SPLIT", "SG_HT")
 SPLIT_KNOBS = dict(SG_SPLIT="1", SG_HT="2048", SG_CT="512")          # beside SG_NP=1024 (the cache a C3 engine has left there beside pairs)
-STATS = ("last_window_events", "last_window_edges", "last_window_nodes", "last_window_tmin_ms", "last_window_tmax_ms", "events_dropped_src",
-         "events_dropped_cap", "events_dropped_ring", "events_misrouted", "alive_in", "alive_dropped")
-_CACHE = {}
-
-
-def _topo():
-    if "topo" not in _CACHE:
-        topo = replay.make_topology(2000, 36_000, seed=231)
-        # one IP in both maps: a service with pod 1's address (the service wins as destination, data.go:840-849)
-        ops = topo.k8s_ops() + [("svc", "ADD", "svc-shadowing-pod1", replay.ip_str(int(topo.pod_ips[1])))]
-        ev, labels = replay.make_events(topo, 160_000, 232, mixed=True, with_raw_outbound=True, with_reverse=True)
-        assert len(labels) <= MAX_LABELS
-        known = np.isin(ev["daddr"], np.concatenate([topo.pod_ips, topo.svc_ips])) & (ev["daddr"] != topo.pod_ips[1])
-        plain = ev[known & (ev["duration_ns"] < (1 << 32)) & ((ev["flags"] & replay.EV_ALIVE) == 0)]
-        assert len(plain) > 100_000
-        _CACHE["topo"] = (topo, ops, ev, plain, labels)
-    return _CACHE["topo"]
 
 
 def _oracle(key, ev):
@@ -51,10 +35,6 @@ def _oracle(key, ev):
         o.packed(ev, labels); o.window_close(weights.make_weights(LAYERS), LAYERS)
         _CACHE[("oracle", key)] = o
     return _CACHE[("oracle", key)]
-
-
-def _sorted(rows):
-    return rows[np.lexsort((rows["to_ref"], rows["from_ref"]))]
 
 
 def _run_windows(windows, pair, np_=256, warm=False, rebuild=False, **knobs):
@@ -154,16 +134,6 @@ def _kmix_partition(cf, ct, nb, pb):
     l, r = cf, ct
     r ^= f(l, 0x9E3779); l ^= f(r, 0x85EBCB); r ^= f(l, 0xC2B2AF)
     return l >> (nb - pb)
-
-
-def _on_edges(e, rng):
-    """one plain request per entry of e, on that topology edge"""
-    topo, _, _, plain, _ = _topo()
-    ev = np.repeat(plain[:1], len(e))
-    ev["flags"] = 0; ev["host_label"] = 0
-    ev["saddr"] = topo.pod_ips[topo.edge_src[e]]; ev["daddr"] = topo.node_ip(topo.edge_dst[e])
-    ev["duration_ns"] = rng.integers(1, 1 << 30, len(e)); ev["status"] = np.where(rng.random(len(e)) < 0.1, 503, 200)
-    return ev
 
 
 def _hot_trace(n_hot):

@@ -593,7 +593,7 @@ def test_cpp_graphds_end_to_end_from_wire_records():
     compare_edge_dicts(got, o.edge_dict())
     assert g.dropped_parse == o.dropped_parse > 0 and g.labels == o.labels
     # f-2, second window: TCP connect records -> socket lines -> sweep -> alive connections beside the requests
-    from tests.test_sockline import _tcp_wire
+    from tests.helpers import _tcp_wire
     rng = np.random.default_rng(5)
     ips = [replay.ip_str(int(x)) for x in topo.pod_ips[:20]] + [replay.ip_str(int(x)) for x in topo.svc_ips[:10]] + ["93.184.216.34", "172.16.5.5"]
     recs = []
@@ -610,7 +610,7 @@ def test_cpp_graphds_end_to_end_from_wire_records():
     compare_edge_dicts(got, o.edge_dict())
     assert sum(v[8] for v in got.values()) == o.alive_count() > 0
     # f-4, third window: real HTTP/2 frames (HPACK) and Kafka payloads (record batches, compressed) decoded on the host
-    from tests.test_http2 import _h2_trace
+    from tests.h2_builder import _h2_trace
     from tests import kafka_builder as kb
     h2_wire, pids = _h2_trace(topo, 300, seed=8)
     rk = np.random.default_rng(9); krecs = []

@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 
 from alaz_amd import replay, weights
-from tests import probe_weights as pw
+from tests.gpu_scaffold import _hip
 from tests.helpers import CLOCK, HostShim, compare_edge_dicts, engine_edge_dict
+from tests import probe_weights as pw
 
 pytestmark = pytest.mark.gpu
 
@@ -207,12 +208,6 @@ def _oracle_dicts(topo, ev, labels, layers, blobs):
         out.append((o.edge_dict(), o.edge_rows()))
     o.close()
     return out
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
 
 
 def _device_rows(hip, ptr, n):

@@ -9,14 +9,13 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine
-from tests import quantile_ref as qr
+from tests.gpu_scaffold import _d2h, _engine, _feed, _hip, _map, _pairs, _pods_engine, _rc, _send
 from tests.group_trend_ref import ref_select_groups
+from tests.helpers import G
 from tests.node_trend_ref import ref_select_nodes
+from tests import quantile_ref as qr
 from tests.quantile_trend_ref import GroupTailRef, NodeTailRef, WorkloadTailRef
-from tests.test_gpu_group_nodes import G, _send
-from tests.test_gpu_groups import _map, _pairs, _pods_engine
-from tests.test_gpu_node_trend import _engine, _feed, _rc, churn, warm_stream  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn, warm_stream  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 

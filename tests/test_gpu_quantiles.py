@@ -7,11 +7,10 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay
+from tests.gpu_scaffold import EXT, _d2h, _engine, _events, _feed, _hip, _pods_engine, _rc
+from tests.helpers import G
 from tests import quantile_ref as qr
-from tests.test_gpu_group_nodes import EXT, G, _events
-from tests.test_gpu_groups import _pods_engine
-from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixture)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 

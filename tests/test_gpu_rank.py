@@ -2,17 +2,17 @@
 rank rows of every window against the pure-Python reference tests/rank_ref.py run on the same window's rows and node rows — byte
 for byte, the contract is integer — on every close path, an engine with it against a twin without it, the selection against
 ref_select_rank, and one trace where the ranking names the cause among services with equal scores."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _d2h, _engine, _feed, _hip, _path, _rc
 from tests.helpers import CLOCK, HostShim
 from tests.nodes_ref import nodes_ref
 from tests.probe_weights import offsets
 from tests.rank_ref import M, rank_ref, ref_select_rank
-from tests.test_gpu_node_trend import _engine, _feed, _path, _rc, churn, warm_stream  # noqa: F401  (the fixtures)
+from tests.traces import churn, warm_stream  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -131,19 +131,6 @@ def test_begin_end_view_top_and_index_gather(churn):
         idx = rng.integers(0, len(rk), 37).astype(np.uint32)
         assert g.window_rank(idx).tobytes() == rk[idx].tobytes()
         assert _rc(g.window_rank, np.array([len(rk)], np.uint32)) == engine.SG_EINVAL
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
-
-
-def _d2h(hip, ptr, n, dtype):
-    out = np.zeros(n, dtype=dtype)
-    if n:
-        assert hip.hipMemcpy(out.ctypes.data, ctypes.c_void_p(ptr), out.nbytes, 2) == 0
-    return out
 
 
 @pytest.mark.parametrize("in_flight", [1, 3, 8])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _feed, _hip
 from tests.helpers import CLOCK, HostShim
 from tests.select_by_ref import ref_select
 
@@ -32,11 +33,6 @@ def _twins(topo, labels, layers, **kw):
     for g in (a, b):
         HostShim().apply(g, topo.k8s_ops()); g.set_label_count(len(labels))
     return a, b
-
-
-def _feed(g, ev):
-    if len(ev):
-        g.ingest_bulk(np.ascontiguousarray(ev))
 
 
 def _check(rows, idx, n_edges, want_rows, k, min_score, cap=None):
@@ -199,12 +195,6 @@ def test_split_flush_selects_the_closed_window_while_the_next_one_is_fed(trace):
         rows, idx, n = a.flush_end_top(1000, NEG_INF)
         for t in ths: t.join()
         _check(rows, idx, n, want[i], 1000, NEG_INF)
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
 
 
 @pytest.mark.parametrize("in_flight", [1, 2])

@@ -1,14 +1,14 @@
 """K7 by a trend key (sg_flush_window_top_by / sg_flush_end_top_by / sg_window_select_by): the selected rows against a numpy selection
 (tests/select_by_ref.py) over a TWIN engine's plain flush plus its window_trend().  A selection moves rows and computes nothing, so
 every comparison is exact: row bytes, indices and counts."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine, replay
+from tests.gpu_scaffold import _feed, _hip, _trend_engine as _engine
 from tests.select_by_ref import ref_select_by
-from tests.test_gpu_trend import _engine, _feed, churn  # noqa: F401
+from tests.traces import trend_churn as churn  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -83,12 +83,6 @@ def test_cap_below_the_selection(churn):
         want = b.flush_window(); tr = b.window_trend()
         pos = ref_select_by(want, tr, "err_dev", 0, NEG_INF)
         assert len(pos) > 100 and np.array_equal(idx, pos[:100]) and sel.tobytes() == want[pos[:100]].tobytes()
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
 
 
 @pytest.mark.parametrize("in_flight", [1, 2])

@@ -19,11 +19,11 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
-from tests import select_cases as sc
+from tests.gpu_model_scaffold import MAX_LABELS, _on_edges, _topo
 from tests.helpers import CLOCK, HostShim
 from tests.node_trend_ref import ref_select_nodes
 from tests.select_by_ref import ref_select, ref_select_by
-from tests.test_gpu_pair_tiles import MAX_LABELS, _on_edges, _topo
+from tests import select_cases as sc
 from tests.traffic_ref import ref_select_traffic
 
 pytestmark = pytest.mark.gpu

@@ -9,7 +9,8 @@ import pytest
 
 from alaz_amd import engine
 from alaz_amd.engine import SG_EINVAL, SG_ESTATE, SG_OK
-from tests.test_gpu_node_trend import _engine, _feed, churn  # noqa: F401  (the fixture)
+from tests.gpu_scaffold import _engine, _feed
+from tests.traces import churn  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 

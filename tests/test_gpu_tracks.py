@@ -6,10 +6,9 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine
+from tests.gpu_scaffold import _d2h, _engine, _feed, _hip, _incident_close as _close, _incident_pods_engine as _pods_engine, _ncap, _rc
 from tests.incident_ref import quantile_threshold
-from tests.test_gpu_incidents import _close, _pods_engine
-from tests.test_gpu_node_trend import _engine, _feed, _rc, churn  # noqa: F401  (the fixtures)
-from tests.test_gpu_rank import _d2h, _hip
+from tests.traces import churn  # noqa: F401  (the fixtures)
 from tests.track_ref import TrackRef
 
 pytestmark = pytest.mark.gpu
@@ -18,10 +17,6 @@ INF = float("inf")
 NO = engine.NO_TRACK
 NEW, SPLIT, MERGED = engine.TRACK_NEW, engine.TRACK_SPLIT, engine.TRACK_MERGED
 TREND = dict(shift=3, warmup=2, ttl=4)
-
-
-def _ncap(g):
-    return g.window_buffers()[3]
 
 
 def _check(g, ref):

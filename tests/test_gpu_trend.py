@@ -8,55 +8,15 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _feed, _hip, _trend_engine as _engine
 from tests.helpers import CLOCK, HostShim
+from tests.traces import trend_churn as churn  # noqa: F401  (the fixture)
 from tests.trend_ref import TrendRef, row_keys, strictly_ascending
 
 pytestmark = pytest.mark.gpu
 
 ME = 1 << 15
 PARAMS = dict(shift=3, warmup=2, ttl=3)
-
-
-def _engine(topo, labels, layers=2, *, variant=0, max_edges=ME, **kw):
-    if variant == 0:                                                  # the 8-byte-record path with the warm state kept
-        kw.setdefault("warm", True)
-        variant = 3
-    g = engine.ServiceGraph(max_known_nodes=topo.n_nodes + 8, max_edges=max_edges, layers=layers, max_labels=256,
-                            max_outbound_ips=512, k1_variant=variant, max_window_events=kw.pop("max_window_events", 300_000),
-                            max_batch=1 << 14, **kw)
-    g.set_clock(*CLOCK)
-    g.load_weights(weights.make_weights(layers))
-    HostShim().apply(g, topo.k8s_ops()); g.set_label_count(len(labels))
-    return g
-
-
-def _feed(g, ev):
-    if len(ev):
-        g.ingest_bulk(np.ascontiguousarray(ev))
-
-
-@pytest.fixture(scope="module")
-def churn():
-    """12 windows over one topology: whole groups of edges missing from some windows (they expire and come back), raw outbound IPs,
-    Host labels, reversed events and open-connection (alive-only) records"""
-    topo = replay.make_topology(300, 6000, seed=81)
-    ev, labels = replay.make_events(topo, 360_000, seed=82, mixed=True, with_raw_outbound=True, with_reverse=True)
-    rng = np.random.default_rng(83)
-    al = np.zeros(3000, dtype=replay.EVENT_DTYPE)
-    al["flags"] = replay.EV_ALIVE
-    al["saddr"] = topo.pod_ips[rng.integers(0, topo.n_pods, len(al))]
-    pick = rng.random(len(al))
-    al["daddr"] = np.where(pick < 0.5, topo.svc_ips[rng.integers(0, topo.n_svcs, len(al))],
-                           np.where(pick < 0.8, topo.pod_ips[rng.integers(0, topo.n_pods, len(al))], 0x5DB8D800 + rng.integers(0, 40, len(al)))).astype(np.uint32)
-    group = ((ev["saddr"].astype(np.uint64) * 2654435761 + ev["daddr"].astype(np.uint64) * 40503) >> 7) % 6
-    wins = []
-    for i in range(12):
-        part = ev[i * 30_000:(i + 1) * 30_000]
-        gp = group[i * 30_000:(i + 1) * 30_000]
-        keep = (gp != (i % 6)) & ((gp != 5) | (i < 4) | (i > 8))        # group i % 6 absent for one window; group 5 for five
-        a = al[rng.random(len(al)) < 0.3]
-        wins.append(np.concatenate([part[keep], a]))
-    return topo, labels, wins
 
 
 def _check(g, ref, rows, trend=None):
@@ -125,12 +85,6 @@ def test_begin_end_and_top_with_an_index(churn):
     with pytest.raises(engine.ServiceGraphError) as ei:
         b.window_trend(index=np.array([n], dtype=np.uint32))          # beyond the window's rows
     assert ei.value.rc == engine.SG_EINVAL
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
 
 
 @pytest.mark.parametrize("in_flight", [2, 4])

@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _feed, _hip, _rc, _trend_engine as _engine
 from tests.helpers import CLOCK, HostShim
-from tests.test_gpu_trend import _engine, _feed, churn  # noqa: F401  (the churn trace: groups of edges missing for 1 and 5 windows)
+from tests.traces import trend_churn as churn  # noqa: F401  (the churn trace: groups of edges missing for 1 and 5 windows)
 from tests.trend_ref import TrendRef
 from tests.vanish_ref import NO_ROW, VanishRef
 
@@ -16,12 +17,6 @@ pytestmark = pytest.mark.gpu
 
 ME = 1 << 15
 PARAMS = dict(shift=3, warmup=2, ttl=6)
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
 
 
 def _check(g, vref, rows, got=None):
@@ -142,12 +137,6 @@ def test_window_run_sharded_world_1(churn):
     finally:
         comm.close()
     assert total > 0
-
-
-def _rc(call, *a, **kw):
-    with pytest.raises(engine.ServiceGraphError) as ei:
-        call(*a, **kw)
-    return ei.value.rc
 
 
 def test_states_invalid_parameters_and_set_trend_resets(churn):

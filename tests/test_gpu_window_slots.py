@@ -15,12 +15,12 @@ working slot has run a window.
 
 The graph is the smallest at which a slot mix-up shows: 36 nodes, 1 500 events a window, one layer, four windows of different
 events."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
+from tests.gpu_scaffold import _d2h, _hip, _rc
 from tests.helpers import CLOCK, HostShim
 
 pytestmark = pytest.mark.gpu
@@ -32,26 +32,6 @@ SEL_K = 50
 CAP = 2048                                                            # = max_edges: no selection is cut
 KINDS = {"warm3": dict(k1_variant=3, warm=True), "table1": dict(k1_variant=1)}
 NEG_INF = float("-inf")
-
-
-def _hip():
-    hip = ctypes.CDLL(None)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    return hip
-
-
-def _d2h(hip, ptr, n, dtype):
-    out = np.zeros(n, dtype=dtype)
-    if n:
-        assert hip.hipMemcpy(out.ctypes.data, ctypes.c_void_p(ptr), out.nbytes, 2) == 0
-    return out
-
-
-def _rc(call, *a, **kw):
-    with pytest.raises(engine.ServiceGraphError) as ei:
-        call(*a, **kw)
-    return ei.value.rc
-
 
 _TRACE = {}
 

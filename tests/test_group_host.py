@@ -1,10 +1,8 @@
 """K14, the groups, on the host: the pure-Python reference tests/group_ref.py against a formulation written apart from it (numpy
 lexsort + reduceat, from_nodes as a count of distinct refs), the dtype against the header's layout, and the plan in
-alaz_amd/csrc/sg_plan.hpp (tests/micro/group_plan_test.cpp)."""
+alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage group)."""
 import ctypes as C
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,8 +11,10 @@ from alaz_amd import engine, weights
 from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.group_ref import group_ref
 from tests.helpers import CLOCK
-from tests.test_gpu_node_trend import churn  # noqa: F401  (the fixture: events only, no engine)
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
+from tests.traces import _random_map, _random_rows
+from tests.traces import churn  # noqa: F401  (the fixture: events only, no engine)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_GROUP
@@ -76,37 +76,6 @@ def _agree(rows, gmap, mg, mk, ml):
     assert a[0].tobytes() == b[0].tobytes()
     assert a[1].tolist() == b[1].tolist() and a[2].tolist() == b[2].tolist()
     return a
-
-
-def _random_rows(rng, mk, ml, n_rows):
-    """canonical rows over Known, Label and outbound-IP refs with self-loops, NaN, -0.0, equal and negative scores, alive-only rows
-    and sums that wrap"""
-    def refs(n):
-        t = rng.choice(np.array([0, 0, 0, 1, 2], dtype=np.uint32), n)
-        v = np.where(t == 0, rng.integers(0, mk, n), np.where(t == 1, rng.integers(0, ml, n), rng.integers(0, 40, n))).astype(np.uint32)
-        return (t << np.uint32(30)) | v
-    f = refs(n_rows) & np.uint32(0x3FFFFFFF)                          # a source is a pod
-    t = np.where(rng.random(n_rows) < 0.05, f, refs(n_rows))
-    pairs = np.unique(np.stack([f, t], 1), axis=0)
-    r = np.zeros(len(pairs), dtype=EDGE_OUT_DTYPE)
-    r["from_ref"], r["to_ref"] = pairs[:, 0], pairs[:, 1]
-    s = rng.choice(np.array([0.0, -0.0, 0.25, 0.5, 1.0, -1.0, np.nan], dtype=np.float32), len(r))
-    r["score"] = np.where(rng.random(len(r)) < 0.5, rng.random(len(r)).astype(np.float32), s).astype(np.float32)
-    r["count"] = rng.integers(0, 1 << 32, len(r)); r["err_count"] = rng.integers(0, 1 << 20, len(r))
-    r["sum_ns"] = rng.integers(0, 1 << 63, len(r), dtype=np.uint64) * np.uint64(2)
-    r["sumsq_us"] = rng.integers(0, 1 << 63, len(r), dtype=np.uint64) * np.uint64(2)
-    r["max_ns"] = rng.integers(0, 1 << 40, len(r)); r["alive"] = rng.integers(0, 1 << 32, len(r))
-    quiet = rng.random(len(r)) < 0.1                                  # alive-only rows
-    for f_ in ("count", "err_count", "sum_ns", "sumsq_us", "max_ns"):
-        r[f_][quiet] = 0
-    return r
-
-
-def _random_map(rng, mk, mg, share=0.7, block=None):
-    m = np.full(mk, NO, dtype=np.uint32)
-    pick = rng.random(mk) < share
-    m[pick] = (np.arange(mk)[pick] // block) % mg if block else rng.integers(0, mg, int(pick.sum()))
-    return m
 
 
 @pytest.mark.parametrize("seed", range(10))
@@ -198,16 +167,7 @@ def test_dtype_and_struct_sizes():
 
 
 # ---- the plan -----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def group_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("grpplan") / "group_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "group_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+group_plan = plan_fixture("group")
 
 
 def _p(me, mk, nc, mg=0, slots=1, world=1, ss=16, r0=0, r1=0):

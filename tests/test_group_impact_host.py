@@ -1,8 +1,7 @@
 """CPU tests of the workload impact (K22): the reference tests/impact_ref.py against a second statement of the contract written
 apart from it (distances by repeated boolean matrix products) over random windows made with the existing references, hand cases,
-the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/group_impact_plan_test.cpp) — layout, sizes at config 3 and at 2^21 keys,
+the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage group_impact) — layout, sizes at config 3 and at 2^21 keys,
 parameter checks — and the header's constants against engine.py."""
-import json
 import os
 import subprocess
 
@@ -11,10 +10,12 @@ import pytest
 
 from alaz_amd import engine
 from tests.group_incident_ref import group_incident_ref
+from tests.helpers import G
+from tests.host_scaffold import contract, incident_rows_of as rows_of
 from tests.impact_ref import call_edges, impact_ref
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
-from tests.test_group_host import _random_map, _random_rows
-from tests.test_group_incident_host import G, contract, rows_of
+from tests.traces import _random_map, _random_rows
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -174,16 +175,7 @@ def test_word_boundaries_and_uncovered_incidents():
 
 
 # ---- the plan -------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("gimpplan") / "group_impact_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "group_impact_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+plan = plan_fixture("group_impact")
 
 
 ENGINES = [(1 << 14, 300, 300), (4096, 8192 + 88, 8192 + 8), (1_250_000, 15_000, 15_000), (0, 0, 0), (1000, 50, 1 << 20)]

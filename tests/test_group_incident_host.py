@@ -1,59 +1,32 @@
 """CPU tests of the workload incidents (K18): the reference tests/group_incident_ref.py against a breadth-first search written
 apart from it, against K12's reference where the map groups nothing, against K12's incidents under maps that group (every pod
 incident lies inside one workload incident), hand cases, and the plan in alaz_amd/csrc/sg_plan.hpp
-(tests/micro/group_incident_plan_test.cpp) — layout, sizes at config 3 and at 2^21 keys, the direct path's reach on the small GPU
+(tests/micro/plan_driver.cpp, stage group_incident) — layout, sizes at config 3 and at 2^21 keys, the direct path's reach on the small GPU
 engine, parameter checks."""
-import json
 import os
-import struct
-import subprocess
 from collections import deque
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine, weights
-from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.group_incident_ref import group_incident_ref, red_groups
-from tests.group_nodes_ref import group_nodes_ref
 from tests.group_rank_ref import group_rank_ref
-from tests.group_ref import group_of_ref, group_ref
-from tests.helpers import CLOCK
+from tests.group_ref import group_of_ref
+from tests.helpers import CLOCK, G
+from tests.host_scaffold import _okey, contract, incident_rows_of as rows_of
 from tests.incident_ref import QUANTILES, incident_ref, quantile_threshold
 from tests.nodes_ref import nodes_ref
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
 from tests.rank_ref import rank_ref
-from tests.test_gpu_node_trend import churn  # noqa: F401  (the fixture: events only, no engine)
-from tests.test_group_host import _random_map, _random_rows
+from tests.traces import _random_map, _random_rows
+from tests.traces import churn  # noqa: F401  (the fixture: events only, no engine)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_INCIDENT
 NOG = engine.NO_GROUP
 INF = float("inf")
-
-
-def G(g):
-    return (engine.REF_GROUP << 30) | g
-
-
-def rows_of(*edges):
-    """canonical-order rows from (from_ref, to_ref, score) tuples (sorted here); count, err_count and sum_ns tell the rows apart"""
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for i, (f, t, s) in enumerate(sorted(edges, key=lambda e: (e[0], e[1]))):
-        r[i]["from_ref"], r[i]["to_ref"], r[i]["score"] = f, t, s
-        r[i]["count"], r[i]["err_count"], r[i]["sum_ns"] = 10 + i, i, 1000 * (i + 1)
-    return r
-
-
-def contract(rows, gmap, mg, mk, ml):
-    ge, _, _ = group_ref(rows, np.asarray(gmap, np.uint32), mg, mk, ml)
-    return ge, group_nodes_ref(ge, mg, mk, ml)
-
-
-def _okey(x):
-    """total order of float32 bit patterns: -0.0 below +0.0 (written apart from nodes_ref.score_key)"""
-    b, = struct.unpack("<I", struct.pack("<f", x))
-    return (1 << 31) + b if b < (1 << 31) else (1 << 32) - 1 - b
 
 
 def incidents_bfs(ge, gn, values, min_value, rank=None):
@@ -289,16 +262,7 @@ def test_ties_go_to_the_smallest_index_and_worst_row_is_a_group_edge_index():
 
 
 # ---- the plan -----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("gincplan") / "group_incident_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "group_incident_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+plan = plan_fixture("group_incident")
 
 
 def _p(me, ncap, mg, slots=1, rows=0, ge=0, ss=16, by=0, res=0):

@@ -1,10 +1,9 @@
 """CPU tests of the workload rows (K16): the two references of tests/group_nodes_ref.py held together (numpy over the group edges;
 plain Python over the window's rows), against the node rollup's reference where the map groups nothing, the ordering claim the
 baseline's merge rests on (ascending group key is strictly ascending workload key), the baseline reference against a hand-computed
-rollout, the selection reference, and the plans in alaz_amd/csrc/sg_plan.hpp (tests/micro/group_nodes_plan_test.cpp)."""
+rollout, the selection reference, and the plans in alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage group_nodes)."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,19 +13,17 @@ from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.group_nodes_ref import (GroupNodeTrendRef, gk_of_refs, group_nodes_ref, group_nodes_rows, ref_select_group_nodes)
 from tests.group_ref import group_ref
 from tests.group_trend_ref import workload_keys
+from tests.helpers import ref
 from tests.node_trend_ref import NodeTrendRef
 from tests.nodes_ref import NO_ROW, nodes_ref
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout, check_soa
-from tests.test_group_host import _random_map, _random_rows
+from tests.traces import _random_map, _random_rows
 from tests.trend_ref import REF_KNOWN, REF_LABEL, REF_OBIP
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_GROUP
 NOOB = np.zeros(0, np.uint32)
-
-
-def ref(t, v):
-    return (t << 30) | v
 
 
 def G(g):
@@ -202,16 +199,7 @@ def test_selection_reference():
 
 
 # ---- the plans -----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("groupnodesplan") / "group_nodes_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "group_nodes_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+plan = plan_fixture("group_nodes")
 
 
 def _p(me, ncap, mg, slots=1, maxe=0, cb=512):

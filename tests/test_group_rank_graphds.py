@@ -5,9 +5,7 @@ import numpy as np
 
 from alaz_amd import engine, hostlib
 
-
-def G(g):
-    return (engine.REF_GROUP << 30) | g
+from tests.helpers import G
 
 
 def _bits(x):

@@ -1,45 +1,25 @@
 """CPU tests of the workload ranking (K17): the reference tests/group_rank_ref.py against K11's reference where the map groups
 nothing, against an exact-rational walk, against a hand-computed rollout chain and the weight clamp, and the plan in
-alaz_amd/csrc/sg_plan.hpp (tests/micro/group_rank_plan_test.cpp) — layout, sizes at config 3 and at 2^21 keys, the working
+alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage group_rank) — layout, sizes at config 3 and at 2^21 keys, the working
 workgroups of a config-3-sized workload window and the partials' budget, parameter checks and defaults."""
-import json
 import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine
-from alaz_amd.replay import EDGE_OUT_DTYPE
-from tests.group_nodes_ref import group_nodes_ref
 from tests.group_rank_ref import group_rank_ref, group_weight, seed_sum
-from tests.group_ref import group_ref
+from tests.helpers import G
+from tests.host_scaffold import contract, rank_rows_of as rows_of
 from tests.nodes_ref import nodes_ref
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
 from tests.rank_ref import M, q16, rank_ref, ref_select_rank
-from tests.test_group_host import _random_map, _random_rows
+from tests.traces import _random_map, _random_rows
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_GROUP
-
-
-def G(g):
-    return (engine.REF_GROUP << 30) | g
-
-
-def rows_of(*edges):
-    """canonical-order rows from (from_ref, to_ref, score) tuples (sorted here), one request each"""
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for i, (f, t, s) in enumerate(sorted(edges)):
-        r[i]["from_ref"], r[i]["to_ref"], r[i]["score"], r[i]["count"] = f, t, s, 1
-    return r
-
-
-def contract(rows, gmap, mg, mk, ml):
-    ge, _, _ = group_ref(rows, np.asarray(gmap, np.uint32), mg, mk, ml)
-    return ge, group_nodes_ref(ge, mg, mk, ml)
-
 
 # ---- under the identity map the result is K11's ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed", range(6))
@@ -209,16 +189,7 @@ def test_seed_fallback_and_empty_window():
 
 
 # ---- the plan -----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("grankplan") / "group_rank_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "group_rank_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+plan = plan_fixture("group_rank")
 
 
 def _p(me, ncap, mg, slots=1, rows=0, ss=24, iters=0, damp=0, seed=0, res=0):

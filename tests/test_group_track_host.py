@@ -1,19 +1,18 @@
 """K19, the workload tracks, on the CPU: the reference tests/group_track_ref.py against K13's (tests/track_ref.py) where no ref is a
 group's, against a second formulation written apart from it (every track owns a set of refs) over random sequences of windows that
 mix group, known, label and outbound-IP refs, hand-written known answers for every rule of the contract, and the plan in
-alaz_amd/csrc/sg_plan.hpp (tests/micro/group_track_plan_test.cpp)."""
-import json
+alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage group_track)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine
-from tests import test_track_host as k13
 from tests.group_incident_ref import group_incident_ref
 from tests.group_nodes_ref import group_nodes_ref
 from tests.group_track_ref import GroupTrackRef, is_group_anchor
+from tests import host_scaffold as k13
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
 from tests.track_ref import TrackRef
 
@@ -309,16 +308,7 @@ def test_the_table_is_cut_at_max_tracks():
 
 
 # ---- the plan ---------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("gtrkplan") / "group_track_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "group_track_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+plan = plan_fixture("group_track")
 
 
 def _p(mg, mk, ml, nc, slots=1, ss=16, quiet=2, mt=0, res=0):

@@ -1,35 +1,31 @@
 """CPU tests of the workload baselines (K15): the numpy reference tests/group_trend_ref.py against hand-computed sequences, the
 ordering claim the merge rests on (a window's group edges are strictly ascending in their workload keys), the rollout sequence on
 reference rows (the pod-level baseline forgets, the workload-level one does not), the plans in alaz_amd/csrc/sg_plan.hpp
-(tests/micro/group_trend_plan_test.cpp), and the front end's new methods against the recording stand-in of
+(tests/micro/plan_driver.cpp, stage group_trend), and the front end's new methods against the recording stand-in of
 tests/test_engine_front.py."""
 import ctypes as C
-import json
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine
-from alaz_amd.replay import EDGE_OUT_DTYPE
-from tests import test_engine_front as front
+from tests.abi_layouts import LAYOUTS
+from tests import engine_front as front
 from tests.group_ref import group_ref
 from tests.group_trend_ref import GroupTrendRef, GroupVanishRef, group_keys, ref_select_groups, workload_keys
+from tests.helpers import ref
+from tests.host_scaffold import node_trend_rows_of as rows_of
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout, check_soa
-from tests.test_abi import LAYOUTS
-from tests.test_group_host import _random_map, _random_rows
+from tests.traces import _random_map, _random_rows
 from tests.trend_ref import REF_KNOWN, REF_LABEL, REF_OBIP, TrendRef, strictly_ascending
 from tests.vanish_ref import NO_ROW
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_GROUP
 NOOB = np.zeros(0, np.uint32)
-
-
-def ref(t, v):
-    return (t << 30) | v
 
 
 def G(g):
@@ -40,14 +36,6 @@ def edges_of(*edges):
     """group edges from (from_ref, to_ref, count, err_count, sum_ns) tuples, in the order given (the caller's: key order)"""
     r = np.zeros(len(edges), dtype=engine.GROUP_EDGE_DTYPE)
     for i, (f, t, c, e, s) in enumerate(edges):
-        r[i]["from_ref"], r[i]["to_ref"], r[i]["count"], r[i]["err_count"], r[i]["sum_ns"] = f, t, c, e, s
-    return r
-
-
-def rows_of(*edges):
-    """canonical-order rows from (from_ref, to_ref, count, err_count, sum_ns) tuples (sorted here)"""
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for i, (f, t, c, e, s) in enumerate(sorted(edges)):
         r[i]["from_ref"], r[i]["to_ref"], r[i]["count"], r[i]["err_count"], r[i]["sum_ns"] = f, t, c, e, s
     return r
 
@@ -232,16 +220,7 @@ def test_a_rollout_resets_the_pod_baseline_and_not_the_workload_baseline():
 
 
 # ---- the plans ------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def group_trend_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("grouptrendplan") / "group_trend_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "group_trend_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+group_trend_plan = plan_fixture("group_trend")
 
 
 def _p(me, slots=1, ss=40, shift=0, warmup=0, ttl=0, maxe=0, lf=0, ef=0, res=0, vss=16, silent=0, seen=0, rows=0, cb=512):
@@ -314,17 +293,7 @@ NEW_ABI = {
 _TREND = [("shift", 4), ("warmup", 4), ("ttl", 64), ("max_entries", 0), ("lat_floor_ns", 1000), ("err_floor", 10486)]
 
 
-@pytest.fixture
-def g(monkeypatch):
-    monkeypatch.setattr(front, "ABI", {**front.ABI, **NEW_ABI})
-    spans = []
-    monkeypatch.setattr(engine, "np", front.Numpy(spans))
-    g = object.__new__(engine.ServiceGraph)
-    g._h = C.c_void_p(0x5A5A)
-    g.layers, g.max_edges, g.max_batch, g.rank, g.world = 2, 100, 1 << 16, 0, 1
-    g._l = front.Lib(g._h, spans)
-    yield g
-    g._h = None
+g = front.abi_fixture(NEW_ABI)
 
 
 def _trend_bytes(**over):

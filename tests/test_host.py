@@ -5,7 +5,7 @@ import pytest
 
 from alaz_amd import build, engine, hostlib, replay, weights
 from oracle import pyoracle
-from tests.test_oracle_golden import _wire
+from tests.helpers import _wire
 
 CLOCK = (1_000_000_000, 1_700_000_000_000_000_000)
 
@@ -189,7 +189,7 @@ def test_packwire_in_place_equals_the_full_copy_path_on_every_protocol():
     it must give the same packed events, labels and drop counts as DecodeWire(full 1 KiB copy) + Pack, record for record —
     on a stream that mixes every protocol, stale payload bytes from the previous record included."""
     from tests import h2_builder as hb, kafka_builder as kb
-    from tests.test_http2 import _h2_trace
+    from tests.h2_builder import _h2_trace
     topo = replay.make_topology(60, 400, seed=31)
     ev, labels = replay.make_events(topo, 6000, seed=32, mixed=True, with_raw_outbound=True, with_reverse=True)
     base = replay.to_wire(ev, labels)
@@ -262,7 +262,7 @@ def test_graphds_is_safe_under_concurrent_callers():
 
 
 def _rec(proto, method, payload, *, fd=7, pid=99, prep=0, wt=1000, status=1):
-    from tests.test_oracle_golden import _wire
+    from tests.helpers import _wire
     r = bytearray(_wire(0x0A000001, 0x0A000002, proto=proto, method=method, status=status, payload=payload, wt=wt))
     r[0:8] = fd.to_bytes(8, "little"); r[16:20] = pid.to_bytes(4, "little"); r[1072:1076] = prep.to_bytes(4, "little")
     return bytes(r)
@@ -397,7 +397,7 @@ def test_datastore_tap_is_additive_unless_diverted():
 def test_process_exit_forgets_the_prepared_statements_of_the_pid():
     """processExit (data.go:363-401) deletes every pgStmts key that starts with the pid — also of connections whose
     close was never seen."""
-    from tests.test_oracle_golden import _wire as w
+    from tests.helpers import _wire as w
     pk = hostlib.Packer()
     parse = b"P" + (4 + 3 + 9 + 2).to_bytes(4, "big") + b"s1\x00" + b"SELECT 1\x00" + b"\x00\x00"
     A, S = 0x0A000001, 0x0A600001

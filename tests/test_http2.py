@@ -16,6 +16,7 @@ import pytest
 from alaz_amd import build, engine, hostlib, replay, weights
 from oracle import pyoracle
 from tests import h2_builder as hb
+from tests.h2_builder import _h2_trace
 
 H = lambda s: bytes.fromhex(s.replace(" ", "").replace("\n", ""))
 CLOCK = (1_000_000_000, 1_700_000_000_000_000_000)
@@ -367,32 +368,6 @@ def test_assembler_differential_random_traces():
 
 
 # ------------------------------------------------------------------------------------------------ through the packer
-def _h2_trace(topo, n_streams, seed):
-    """wire records of n_streams request/response pairs over a few connections between known pods, services and
-    outbound hosts (named by :authority), interleaved with plain HTTP events."""
-    rng = random.Random(seed)
-    pods = [int(x) for x in topo.pod_ips[:20]]; svcs = [int(x) for x in topo.svc_ips[:8]]
-    ext = [0x08080808, 0x08080404, 0x01010101]
-    conns = []
-    for c in range(12):
-        dst = ext[c % 3] if c < 4 else rng.choice(svcs + pods + ext)
-        conns.append(dict(pid=100 + c % 4, fd=3 + c, s=rng.choice(pods), d=dst, ce=hb.Encoder(), se=hb.Encoder(), next=1, tls=int(rng.random() < 0.3), last=0,
-                          auth=[b"api.example.com", b"db.example.org:443", b"", b"api.example.com"][c % 4] if dst in ext else b"in-cluster"))
-    recs = []; t = 10_000_000
-    for _ in range(n_streams):
-        c = rng.choice(conns); sid = c["next"]; c["next"] += 2
-        grpc = rng.random() < 0.4
-        req = c["ce"].block([(b":method", b"POST" if grpc else b"GET"), (b":scheme", b"http"), (b":path", rng.choice([b"/", b"/pkg.Svc/Call", b"/v1/items"]))] +
-                            ([(b":authority", c["auth"])] if c["auth"] else []) + ([(b"content-type", b"application/grpc")] if grpc else []), huffman=rng.random() < 0.5)
-        rsp = c["se"].block([(b":status", rng.choice([b"200", b"200", b"500", b"503"]))] + ([(b"grpc-status", rng.choice([b"0", b"13"]))] if grpc else []), huffman=rng.random() < 0.5)
-        t += rng.randrange(1000, 90_000); lat = rng.randrange(10_000, 5_000_000)
-        lat = max(lat, c["last"] + 1 - t); c["last"] = t + lat          # responses of one connection leave in encoder order
-        recs.append((t, hb.l7_record(c["pid"], c["fd"], CLIENT, hb.frame(hb.HEADERS, sid, req), t, c["s"], c["d"], tls=c["tls"])))
-        recs.append((t + lat, hb.l7_record(c["pid"], c["fd"], SERVER, hb.frame(hb.DATA, sid, b"..", flags=0) + hb.frame(hb.HEADERS, sid, rsp), t + lat, c["s"], c["d"], tls=c["tls"])))
-        if rng.random() < 0.5:
-            recs.append((t + 5, hb.l7_record(c["pid"], 99, 1, b"GET /user HTTP1.1\r\nHost: plain.example\r\n\r\n", t + 5, c["s"], rng.choice(svcs + ext), proto=1, status=200, dur=777)))
-    recs.sort(key=lambda r: r[0])
-    return b"".join(r for _, r in recs), sorted({c["pid"] for c in conns})
 
 
 def test_http2_records_through_packer_equal_the_oracle_wire_path():

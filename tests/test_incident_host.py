@@ -1,11 +1,8 @@
 """CPU tests of the incidents (K12): the reference tests/incident_ref.py against an independent breadth-first implementation on
 random row sets, hand cases that pin the contract, the reference's invariants over the oracle's rows of the churn windows (and what
-the GPU tests' quantile thresholds cover there), and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/incident_plan_test.cpp)."""
+the GPU tests' quantile thresholds cover there), and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage incident)."""
 import ctypes as C
-import json
 import os
-import struct
-import subprocess
 from collections import deque
 
 import numpy as np
@@ -14,30 +11,17 @@ import pytest
 from alaz_amd import engine, weights
 from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.helpers import CLOCK
+from tests.host_scaffold import _okey, incident_rows_of as rows_of
 from tests.incident_ref import QUANTILES, incident_ref, quantile_threshold, red_rows
 from tests.nodes_ref import nodes_ref
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
 from tests.rank_ref import rank_ref
-from tests.test_gpu_node_trend import churn  # noqa: F401  (the fixture: events only, no engine)
+from tests.traces import churn  # noqa: F401  (the fixture: events only, no engine)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_INCIDENT
 INF = float("inf")
-
-
-def rows_of(*edges):
-    """canonical-order rows from (from_ref, to_ref, score) tuples (sorted here); count, err_count and sum_ns tell the rows apart"""
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for i, (f, t, s) in enumerate(sorted(edges, key=lambda e: (e[0], e[1]))):
-        r[i]["from_ref"], r[i]["to_ref"], r[i]["score"] = f, t, s
-        r[i]["count"], r[i]["err_count"], r[i]["sum_ns"] = 10 + i, i, 1000 * (i + 1)
-    return r
-
-
-def _okey(x):
-    """total order of float32 bit patterns: -0.0 below +0.0 (written apart from nodes_ref.score_key)"""
-    b, = struct.unpack("<I", struct.pack("<f", x))
-    return (1 << 31) + b if b < (1 << 31) else (1 << 32) - 1 - b
 
 
 def incidents_bfs(rows, nodes, values, min_value, rank=None):
@@ -254,16 +238,7 @@ def test_what_the_quantile_thresholds_cover(oracle_windows):
     assert any(c > 3 and b >= 3 for q in QUANTILES for c, b in zip(counts[q], big[q])), (counts, big)
 
 
-@pytest.fixture(scope="module")
-def incident_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("incplan") / "incident_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "incident_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+incident_plan = plan_fixture("incident")
 
 
 def _p(me, nc, slots=1, ss=16, by=0, res=0):

@@ -4,9 +4,9 @@ are checked here on the oracle's rows.  No GPU."""
 import numpy as np
 import pytest
 
+from tests.helpers import CLOCK
 from tests import model_ref as mr
 from tests import probe_weights as pw
-from tests.helpers import CLOCK
 
 TRACES = {"adversarial": pw.adversarial_trace, "boundary": mr.boundary_trace}
 

@@ -1,35 +1,21 @@
 """CPU tests of the per-node baselines (K10): the numpy reference tests/node_trend_ref.py against hand-computed sequences, the node
-selection's reference, and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/node_trend_plan_test.cpp) — parameter checks and
+selection's reference, and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage node_trend) — parameter checks and
 defaults, and memory for every window an engine can close."""
 import ctypes as C
-import json
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 from alaz_amd import engine
-from alaz_amd.replay import EDGE_OUT_DTYPE
+from tests.helpers import ref
+from tests.host_scaffold import node_trend_rows_of as rows_of
 from tests.node_trend_ref import NodeTrendRef, node_samples, ref_select_nodes, x_err
 from tests.nodes_ref import nodes_ref
-from tests.trend_ref import REF_KNOWN, REF_LABEL, REF_OBIP
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout, check_soa
+from tests.trend_ref import REF_KNOWN, REF_LABEL, REF_OBIP
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def ref(t, v):
-    return (t << 30) | v
-
-
-def rows_of(*edges):
-    """canonical-order rows from (from_ref, to_ref, count, err_count, sum_ns) tuples (sorted here)"""
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for i, (f, t, c, e, s) in enumerate(sorted(edges)):
-        r[i]["from_ref"], r[i]["to_ref"], r[i]["count"], r[i]["err_count"], r[i]["sum_ns"] = f, t, c, e, s
-    return r
-
 
 A, B_, C_ = ref(REF_KNOWN, 1), ref(REF_KNOWN, 2), ref(REF_KNOWN, 3)
 NOOB = np.zeros(0, np.uint32)
@@ -185,16 +171,7 @@ def test_node_selection_reference():
     assert list(ref_select_nodes(n, tr, "new", 1, 0.0)) == [0]
 
 
-@pytest.fixture(scope="module")
-def node_trend_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("nodetrendplan") / "node_trend_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "node_trend_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+node_trend_plan = plan_fixture("node_trend")
 
 
 def _p(nc, slots=1, ss=40, shift=0, warmup=0, ttl=0, maxe=0, lf=0, ef=0, res=0):

@@ -1,24 +1,20 @@
 """CPU tests of the node rollup (K9): the numpy reference tests/nodes_ref.py against a plain Python loop, NODE_DTYPE against the
-header's sg_node_out, and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/nodes_plan_test.cpp) — memory and grids for every
+header's sg_node_out, and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage nodes) — memory and grids for every
 window an engine can close."""
-import json
 import os
 import subprocess
 
 import numpy as np
-import pytest
 
 from alaz_amd import engine
 from alaz_amd.replay import EDGE_OUT_DTYPE
+from tests.helpers import ref
 from tests.nodes_ref import NO_ROW, key_score, nodes_loop, nodes_ref, score_key, score_q32
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-def ref(t, v):
-    return (t << 30) | v
 
 
 def random_rows(seed, n, n_known=40, n_labels=6, n_obip=5):
@@ -107,16 +103,7 @@ def test_node_dtype_matches_the_header(tmp_path):
         assert out[f] == (off, dt.itemsize), f
 
 
-@pytest.fixture(scope="module")
-def nodes_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("nodesplan") / "nodes_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "nodes_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+nodes_plan = plan_fixture("nodes")
 
 
 def _around(*xs):

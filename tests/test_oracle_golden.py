@@ -9,6 +9,8 @@ import pytest
 from alaz_amd import replay, weights
 from oracle import pyoracle, score_np
 
+from tests.helpers import _wire
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CLOCK = (1_000_000_000, 1_700_000_000_000_000_000)
 
@@ -56,16 +58,6 @@ def test_int_to_ipv4():
     assert pyoracle.int_to_ipv4(0x0A000001) == "10.0.0.1"
     assert pyoracle.int_to_ipv4(0xAC10FF02) == "172.16.255.2"
     assert pyoracle.int_to_ipv4(0) == "0.0.0.0"
-
-
-def _wire(saddr, daddr, *, proto=1, method=1, status=200, dur=50, wt=0, payload=b"GET /user HTTP1.1", tls=0, sport=40000, dport=80):
-    r = bytearray(replay.L7_WIRE_SIZE)
-    r[0:8] = (7).to_bytes(8, "little"); r[8:16] = wt.to_bytes(8, "little"); r[16:20] = (99).to_bytes(4, "little")
-    r[20:24] = status.to_bytes(4, "little"); r[24:32] = dur.to_bytes(8, "little"); r[32] = proto; r[33] = method
-    r[36:36 + len(payload)] = payload; r[1060:1064] = len(payload).to_bytes(4, "little"); r[1064] = 1; r[1066] = tls
-    r[1076:1080] = saddr.to_bytes(4, "little"); r[1080:1082] = sport.to_bytes(2, "little")
-    r[1084:1088] = daddr.to_bytes(4, "little"); r[1088:1090] = dport.to_bytes(2, "little")
-    return bytes(r)
 
 
 def test_simulator_trace_known_answer():

@@ -1,27 +1,17 @@
-"""The engine's launch plan (alaz_amd/csrc/sg_plan.hpp) on the CPU: tests/micro/plan_test.cpp prints the plan of every case of
+"""The engine's launch plan (alaz_amd/csrc/sg_plan.hpp) on the CPU: tests/micro/plan_driver.cpp, stage plan, prints the plan of every case of
 tests/golden/plans.json, which holds the sizing decisions the engine made at commit 38499a0 — before the planner existed —
 recorded on an MI355X from that commit's own sg_create, with and without the development build's SG_* overrides."""
 import json
 import os
-import subprocess
 
-import pytest
+from tests import plan_driver
+from tests.plan_driver import run_named as run_plans, stage_fixture
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "plans.json")
 
 
-@pytest.fixture(scope="module")
-def plan_exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("plan") / "plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "plan_test.cpp")])
-    return str(exe)
-
-
-def run_plans(exe, lines):
-    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return {r["name"]: r for r in map(json.loads, out.stdout.splitlines())}
+plan_exe = stage_fixture("plan")
 
 
 def planner_input(case):
@@ -81,8 +71,8 @@ def test_k6_one_wg_knob_reaches_the_plan_of_a_sharded_engine(plan_exe):
 
 def test_knob_list_is_the_engines(plan_exe):
     from alaz_amd import engine
-    out = subprocess.run([plan_exe, "--knobs"], capture_output=True, text=True, timeout=60, check=True)
-    assert tuple(out.stdout.split()) == engine.DEV_KNOBS
+    out = plan_driver.run_text(plan_exe, args=("--knobs",))
+    assert tuple(out.split()) == engine.DEV_KNOBS
 
 
 K1A_GLOBAL, K1A_WIDE, K1A_TILE, K1A_TEAM = range(4)
@@ -152,8 +142,7 @@ def test_kernel_choice_is_the_launch_ladders(plan_exe):
     ladder_choice, and every kernel it may launch inside the instantiations the library enumerates"""
     cases = json.load(open(GOLDEN))["cases"]
     got = run_plans(plan_exe, [planner_input(c) for c in cases])
-    out = subprocess.run([plan_exe, "--domains"], capture_output=True, text=True, timeout=60, check=True)
-    domains = json.loads(out.stdout)
+    domains, = plan_driver.run(plan_exe, (), args=("--domains",))
     warm_u = domains.pop("k1b_warm_u")
     # the instantiation counts of the library: k1b_merge and k1b_stream_merge each with a _wide twin
     assert {f: len(v) for f, v in domains.items()} == dict(k1a_wide=8, k1a_tile=12, k1a_team=18, k1b_merge=2 * 3, k1b_stream=2 * 24,

@@ -1,5 +1,5 @@
 """K3's two batched-load forms in the plan (alaz_amd/csrc/sg_plan.hpp: Plan::k3_in_form / k3_feat_lanes, Kernels likewise), on the CPU:
-tests/micro/plan_k3_forms_test.cpp prints the plan's choice for a config line.
+tests/micro/plan_driver.cpp, stage k3_forms, prints the plan's choice for a config line.
 
 k3_in_form = 1: k3_in_part<1> issues every load of a trip before its first wait.  k3_feat_lanes = 1: the node-only feature launch runs
 k3_node_features_lanes, eight lanes per node; it exists only where the score kernel computes the edge features (k5_efeat), because it
@@ -7,29 +7,15 @@ has no edge workgroups.  Unasked, the in-form follows k3_in_form_default (the sh
 profiles/k3_forms_ab_c3.txt was run) and the lanes follow k5_efeat, each only while its constant (kK3InFormDefault,
 kK3FeatLanesDefault) says the A/B passed the rule.  SG_K3_IN_FORM / SG_K3_FEAT_LANES name them in the development build; any value
 but 0 and 1 is refused by name, and so is SG_K3_FEAT_LANES=1 beside k5_efeat = 0.  Neither moves the slices, the ranges or K5's plan."""
-import json
-import os
-import subprocess
-
 import pytest
 
-from tests.test_plan_k5_form import C2, C3, C5_SHARD
+from tests.plan_driver import run_named as run, stage_fixture
+from tests.traces import C2, C3, C5_SHARD
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = [("c2", C2), ("c3", C3), ("c5_shard", C5_SHARD), ("c3_sharded", f"{C3} world=4 rank=1")]
 
 
-@pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("k3forms") / "plan_k3_forms_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(out), os.path.join(HERE, "micro", "plan_k3_forms_test.cpp")])
-    return str(out)
-
-
-def run(exe, lines):
-    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return {r["name"]: r for r in map(json.loads, out.stdout.splitlines())}
+exe = stage_fixture("k3_forms")
 
 
 def test_the_defaults_per_configuration_line(exe):

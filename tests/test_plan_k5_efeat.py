@@ -1,33 +1,19 @@
 """Where the edge features are computed, in the plan (alaz_amd/csrc/sg_plan.hpp: Plan::k5_efeat, Kernels::k5_efeat), on the CPU:
-tests/micro/plan_k5_efeat_test.cpp prints the plan's choice for a config line.
+tests/micro/plan_driver.cpp, stage k5_efeat, prints the plan's choice for a config line.
 
 k5_efeat = 1: k5_edge_score_lanes computes e_uv, lat_z and err_ratio of its own edge, k3_node_features launches no edge workgroups
 and the engine holds no feature arrays.  It exists for form 1 only.  Unasked, an engine of form 1 takes it when kK5EfeatDefault says
 so (the A/B of profiles/k5_efeat_ab_c3.txt) and an engine of form 0 never; SG_K5_EFEAT=0/1 names it in the development build, any
 other value is refused, and so is 1 beside form 0.  k5_grid does not depend on it."""
-import json
-import os
-import subprocess
-
 import pytest
 
-from tests.test_plan_k5_form import C2, C3, C5_SHARD
+from tests.plan_driver import run_named as run, stage_fixture
+from tests.traces import C2, C3, C5_SHARD
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = [("c2", C2), ("c3", C3), ("c5_shard", C5_SHARD), ("c3_sharded", f"{C3} world=4 rank=1")]
 
 
-@pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("k5efeat") / "plan_k5_efeat_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(out), os.path.join(HERE, "micro", "plan_k5_efeat_test.cpp")])
-    return str(out)
-
-
-def run(exe, lines):
-    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return {r["name"]: r for r in map(json.loads, out.stdout.splitlines())}
+exe = stage_fixture("k5_efeat")
 
 
 def test_the_default_follows_the_form(exe):

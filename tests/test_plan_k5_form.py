@@ -1,34 +1,18 @@
 """k5_edge_score's form in the plan (alaz_amd/csrc/sg_plan.hpp: Plan::k5_form, Plan::k5_grid, Kernels::k5_form), on the CPU:
-tests/micro/plan_k5_form_test.cpp prints the plan's choice for a config line.
+tests/micro/plan_driver.cpp, stage k5_form, prints the plan's choice for a config line.
 
 Form 0 gives sixteen lanes to an edge (32 edges per workgroup and step, three workgroups per CU), form 1 one lane (256 edges per
 workgroup and step; a CU holds as many of its workgroups as its LDS — 32 KiB each — and its registers — three waves per SIMD —
 allow).  k5_grid is one round of the chosen form's workgroups, or fewer where max_edges needs fewer."""
-import json
-import os
-import subprocess
-
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests.plan_driver import run_named as run, stage_fixture
+from tests.traces import C2, C3, C5_SHARD
 
-C2 = "max_known_nodes=1500 max_edges=66596 layers=1 max_labels=64 max_window_events=1000000 k1_variant=3"
-C3 = "max_known_nodes=15000 max_edges=1254096 layers=2 max_labels=64 max_window_events=10000000"                  # the flagship shape
-C5_SHARD = "max_known_nodes=150000 max_edges=785346 layers=2 max_labels=64 max_window_events=625000 flags=2"
 SHAPES = [("c2", C2), ("c3", C3), ("c5_shard", C5_SHARD)]
 
 
-@pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("k5form") / "plan_k5_form_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(out), os.path.join(HERE, "micro", "plan_k5_form_test.cpp")])
-    return str(out)
-
-
-def run(exe, lines):
-    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return {r["name"]: r for r in map(json.loads, out.stdout.splitlines())}
+exe = stage_fixture("k5_form")
 
 
 def grid(r, form):

@@ -1,17 +1,15 @@
 """Pass A's tile pairs in the plan (alaz_amd/csrc/sg_plan.hpp: PassA::k1a_pair / k1a_pair_lds, PassAKernel::pair), on the CPU:
-tests/micro/plan_pair_test.cpp prints pass A's choice for a config line and the join tables' sizes.
+tests/micro/plan_driver.cpp, stage pair, prints pass A's choice for a config line and the join tables' sizes.
 
 The paired form of k1a_team_partition (sg_k1_team.h, PAIR = 1) keeps a second tile's worth of records per team in LDS.  The plan takes it only BESIDE the geometry it chose without pairs — the same cache,
 the same level-2 placement —, so every size recorded in tests/golden/plans.json stays what it was; a launch asks for k1a_lds +
 k1a_pair_lds bytes.  kernel_lds() below restates the kernel's own carve of that LDS (the pointer arithmetic at the top of
 k1a_team_partition), not the plan's sum."""
-import json
-import os
-import subprocess
-
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests import plan_driver
+from tests.plan_driver import run_named as run, stage_fixture
+
 LDS_CAP = 160 * 1024
 K1A_TEAM = 3
 
@@ -25,17 +23,7 @@ C3_FULL = f"{C3} l1=512 l2=62464"
 C3_SPLIT = f"{C3_FULL} SG_NP=1024 SG_SPLIT=1 SG_HT=2048"
 
 
-@pytest.fixture(scope="module")
-def pair_exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("pair") / "plan_pair_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "plan_pair_test.cpp")])
-    return str(exe)
-
-
-def run(exe, lines):
-    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return {r["name"]: r for r in map(json.loads, out.stdout.splitlines())}
+pair_exe = stage_fixture("pair")
 
 
 def kernel_lds(r, pair):
@@ -133,8 +121,7 @@ def test_arriving_split_takes_pairs_by_name_beside_half_the_cache(pair_exe):
 
 
 def test_every_key_the_plan_can_choose_is_instantiated(pair_exe):
-    out = subprocess.run([pair_exe, "--domains"], capture_output=True, text=True, timeout=60, check=True)
-    dom = json.loads(out.stdout)
+    dom, = plan_driver.run(pair_exe, (), args=("--domains",))
     assert len(dom["k1a_team"]) == 18 and len(dom["k1a_team_pair"]) == 18
     lines = []
     for n, line in SHAPES:

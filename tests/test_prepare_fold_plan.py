@@ -1,32 +1,17 @@
 """Which window closes launch no kc_prepare (alaz_amd/csrc/sg_plan.hpp: Plan::prepare_fold for the engine, close_folds for one close),
-on the CPU: tests/micro/prepare_fold_plan_test.cpp prints the choice for a config line.
+on the CPU: tests/micro/plan_driver.cpp, stage prepare_fold, prints the choice for a config line.
 
 The fold is for one shape only — a variant-0 narrow engine that keeps warm-window state, unsharded, whose pass B runs 1 024 threads —
 and, per close, for the closes that launch the warm attempt (the close keeps state, the host tries the warm path) with the engine's
 own outbound-IP collection (mode 1).  Everything else keeps the separate launch.  The engine reports Plan::prepare_fold as
 geometry()["prepare_fold"] (sg_prepare_fold_get): tests/test_gpu_prepare_fold.py reads it there."""
-import json
-import os
-import subprocess
+from tests.plan_driver import run_named as run, stage_fixture
 
-import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 C3 = "max_known_nodes=15000 max_edges=1254096 layers=2 max_labels=64 max_window_events=10000000"     # the flagship shape
 SMALL = "max_known_nodes=112 max_edges=2048 layers=1 max_labels=256 max_window_events=65536"           # the GPU test's shape
 
 
-@pytest.fixture(scope="module")
-def fold_exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("fold") / "prepare_fold_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "prepare_fold_plan_test.cpp")])
-    return str(exe)
-
-
-def run(exe, lines):
-    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return {r["name"]: r for r in map(json.loads, out.stdout.splitlines())}
+fold_exe = stage_fixture("prepare_fold")
 
 
 # (name, config line, the plan folds, why)

@@ -3,8 +3,8 @@ layer outputs and a float64 restatement of the edge features, within the readout
 import numpy as np
 import pytest
 
-from tests import probe_weights as pw
 from tests.helpers import CLOCK
+from tests import probe_weights as pw
 
 
 @pytest.fixture(scope="module")

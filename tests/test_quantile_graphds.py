@@ -4,11 +4,9 @@ import numpy as np
 
 from alaz_amd import engine, hostlib
 
+from tests.host_scaffold import _ds
+
 ONES = (1 << 64) - 1
-
-
-def _ds():
-    return hostlib.GraphDS(engine.make_config(max_known_nodes=64, max_edges=256), engine_lib=None)
 
 
 def _ops(ds):

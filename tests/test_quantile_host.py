@@ -1,23 +1,22 @@
 """The latency percentiles (K20) on the CPU: tests/quantile_ref.py against a second formulation written apart from it (sorted lists of
 bin indices, plain Python over the rows), against the oracle's or_percentile_us, and against hand-computed answers for every clause
-of Q; the identities between the spaces; and the plan in alaz_amd/csrc/sg_plan.hpp through tests/micro/quantile_plan_test.cpp."""
+of Q; the identities between the spaces; and the plan in alaz_amd/csrc/sg_plan.hpp through tests/micro/plan_driver.cpp, stage quantile."""
 import ctypes as C
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine, replay, weights
 from oracle import pyoracle
-from tests import quantile_ref as qr
 from tests.group_nodes_ref import group_nodes_ref
 from tests.group_ref import group_of_ref, group_ref
 from tests.helpers import CLOCK
 from tests.nodes_ref import nodes_ref
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
-from tests.test_group_host import _random_map, _random_rows
+from tests import quantile_ref as qr
+from tests.traces import _random_map, _random_rows
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_GROUP
@@ -153,17 +152,7 @@ def test_every_clause_of_q_by_hand():
 
 
 # ---- the plan ------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("qplan") / "quantile_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(HERE, "..", "include"), "-o", str(exe),
-                           os.path.join(HERE, "micro", "quantile_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+plan = plan_fixture("quantile")
 
 
 def _p(me, ncap, mg, slots=1, spaces=7, world=1, permille=()):

@@ -1,25 +1,24 @@
 """CPU tests of the tail baselines (K21): the numpy references of tests/quantile_trend_ref.py against a second formulation written
 apart from them (a dict keyed by (from_key, to_key), plain Python floats, one sample at a time), against hand-computed answers and
 against the mean baselines' references (the error half is theirs), the scenario the stage is for — a tail regression the mean
-baseline does not see — and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/quantile_trend_plan_test.cpp)."""
-import json
+baseline does not see — and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage quantile_trend)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine
 from alaz_amd.engine import GROUP_EDGE_DTYPE, NODE_DTYPE, NO_GROUP as NO
-from tests import quantile_ref as qr
 from tests.group_nodes_ref import GroupNodeTrendRef, group_nodes_ref
 from tests.group_ref import group_ref
 from tests.group_trend_ref import GroupTrendRef, group_keys, workload_keys
 from tests.node_trend_ref import NodeTrendRef
 from tests.nodes_ref import nodes_ref
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout, check_soa
+from tests import quantile_ref as qr
 from tests.quantile_trend_ref import GroupTailRef, NodeTailRef, WorkloadTailRef
-from tests.test_group_host import _random_map, _random_rows
+from tests.traces import _random_map, _random_rows
 from tests.trend_ref import ref_keys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -301,16 +300,7 @@ def test_a_tail_regression_the_mean_baseline_does_not_see():
 
 
 # ---- the plan --------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("quantiletrendplan") / "quantile_trend_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "quantile_trend_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+plan = plan_fixture("quantile_trend")
 
 
 def _p(spaces=7, on=7, permille=990, qm=(500, 990), ncap=1000, me=4096, nc=1500, slots=1, ss=40, shift=0, warmup=0, ttl=0, maxe=0, lf=0, ef=0, res=0):

@@ -1,10 +1,8 @@
 """CPU tests of the culprit ranking (K11): the reference tests/rank_ref.py against hand-worked cases that pin what the ranking
-means, the selection's reference, and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/rank_plan_test.cpp) — sizes for every
+means, the selection's reference, and the plan in alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage rank) — sizes for every
 engine, parameter checks and defaults."""
 import ctypes as C
-import json
 import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -12,20 +10,14 @@ import pytest
 
 from alaz_amd import engine
 from alaz_amd.replay import EDGE_OUT_DTYPE
+from tests.host_scaffold import rank_rows_of as rows_of
 from tests.nodes_ref import nodes_ref
-from tests.rank_ref import M, q16, rank_keys, rank_ref, ref_select_rank
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
+from tests.rank_ref import M, q16, rank_keys, rank_ref, ref_select_rank
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FE, CART, PAY, DB, CAT, DB2 = range(1, 7)                            # KNOWN refs (type 0): the ref is the id
-
-
-def rows_of(*edges):
-    """canonical-order rows from (from_ref, to_ref, score) tuples (sorted here), one request each"""
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for i, (f, t, s) in enumerate(sorted(edges)):
-        r[i]["from_ref"], r[i]["to_ref"], r[i]["score"], r[i]["count"] = f, t, s, 1
-    return r
 
 
 def walk(rows, nodes, iters=20, D=218, seed="score", smin=0.0):
@@ -204,16 +196,7 @@ def test_selection_reference():
     assert ref_select_rank(rk, 2, float("nan")).tolist() == []
 
 
-@pytest.fixture(scope="module")
-def rank_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("rankplan") / "rank_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "rank_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+rank_plan = plan_fixture("rank")
 
 
 def _p(me, nc, slots=1, ss=24, iters=0, damp=0, seed=0, res=0):

@@ -5,8 +5,8 @@ walk is reached on every shape that test runs, and every case whose title names 
 import numpy as np
 import pytest
 
-from tests import select_cases as sc
 from tests.select_by_ref import ref_select
+from tests import select_cases as sc
 
 #: every (rows, workgroups) a GPU test selects over: the edge rows and the node rows of each shape
 SHAPES = sorted({(s.E, s.spans) for s in sc.EDGE_SHAPES} | {(s.N, s.node_spans) for s in sc.NODE_SHAPES})

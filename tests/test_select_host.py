@@ -1,15 +1,13 @@
 """CPU tests of the selection (K7) plumbing: GraphDS::SetSelection reaches the engine's sg_flush_window_top (through the recording
 stand-in of alaz_amd/csrc/host/host_capi.cpp), and the selection's plan in alaz_amd/csrc/sg_plan.hpp sizes its scratch for every
-window an engine can close (tests/micro/select_plan_test.cpp)."""
-import json
+window an engine can close (tests/micro/plan_driver.cpp, stage select)."""
 import math
 import os
-import subprocess
 
-import pytest
 
 from alaz_amd import engine, hostlib
 from alaz_amd.engine import make_config
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,16 +51,7 @@ def test_graphds_without_a_selection_never_calls_flush_window_top():
         g.close()
 
 
-@pytest.fixture(scope="module")
-def sel_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("selplan") / "select_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "select_plan_test.cpp")])
-
-    def run(sizes):
-        out = subprocess.run([str(exe)], input="\n".join(map(str, sizes)) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+sel_plan = plan_fixture("select")
 
 
 SIZES = [1, 2, 255, 2047, 2048, 2049, 4096, 1 << 15, 1 << 18, (1 << 20) - 1, 1 << 20, 2_000_000, 1 << 21, (1 << 21) + 1, 1 << 22, 1 << 24]

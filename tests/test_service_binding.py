@@ -12,12 +12,10 @@ import pytest
 
 from alaz_amd import engine, hostlib
 
+from tests.host_scaffold import _ds
+
 NO = engine.NO_GROUP
 SET = 0xFFFFFFFE                                                      # mock_group_ops' marker of an sg_set_groups call
-
-
-def _ds():
-    return hostlib.GraphDS(engine.make_config(max_known_nodes=64, max_edges=256), engine_lib=None)
 
 
 def _final(ds):

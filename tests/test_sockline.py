@@ -11,6 +11,8 @@ import pytest
 from oracle import pyoracle
 from oracle.pyoracle import SockLine, sockinfo
 
+from tests.helpers import _ip, _tcp_wire, _wire
+
 
 def test_kat_second_open_is_found_after_its_timestamp():
     """sock_line_test.go:443-476 (TestXxx2): AddValue(0, yy); AddValue(247453008321477, xx); GetValue(247453008321499) -> xx"""
@@ -88,18 +90,6 @@ def test_getvalue_special_cases():
     assert [v[2] is None for v in nl.values()] == [True, False]
 
 
-def _tcp_wire(recs):
-    """BpfTcpEvent records (ebpf/tcp_state/tcp.go:63-72)."""
-    buf = np.zeros((len(recs), pyoracle.TCP_WIRE_SIZE), dtype=np.uint8)
-    for i, (typ, pid, fd, ts, saddr, sport, daddr, dport) in enumerate(recs):
-        r = buf[i]
-        r[0:8] = np.frombuffer(np.uint64(fd).tobytes(), np.uint8); r[8:16] = np.frombuffer(np.uint64(ts).tobytes(), np.uint8)
-        r[16:20] = np.frombuffer(np.uint32(typ).tobytes(), np.uint8); r[20:24] = np.frombuffer(np.uint32(pid).tobytes(), np.uint8)
-        r[24:26] = np.frombuffer(np.uint16(sport).tobytes(), np.uint8); r[26:28] = np.frombuffer(np.uint16(dport).tobytes(), np.uint8)
-        r[28:32] = [int(x) for x in saddr.split(".")]; r[44:48] = [int(x) for x in daddr.split(".")]
-    return buf.tobytes()
-
-
 def test_tcp_events_to_alive_connections():
     """processTcpConnect (data.go:404-506) + one clearSocketLines tick (:1628-1716): localhost filtered, a close
     without a line dropped, only lines whose last value is an open socket report, the source must be a pod,
@@ -135,9 +125,6 @@ def test_tcp_events_to_alive_connections():
 
 
 # ---- the C++ host implementation against the oracle ---------------------------------------------
-def _ip(s):
-    a, b, c, d = (int(x) for x in s.split("."))
-    return (a << 24) | (b << 16) | (c << 8) | d
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6])
@@ -223,7 +210,6 @@ def test_tcp_close_forgets_the_connections_prepared_statements_by_key_prefix():
     """aggregator/data.go:496-503: on CLOSED every pgStmts key with the *string prefix* "pid-fd" is deleted — the keys are
     "pid-fd-name" (:1619-1621), so closing fd 7 also clears the statements of fds 70..79 of that pid.  Oracle and packer."""
     from alaz_amd import hostlib
-    from tests.test_oracle_golden import _wire
     def parse(fd, name):                     # extended-query Parse message: 'P' len name\0 query\0 ...
         body = name + b"\x00" + b"SELECT * FROM t WHERE id = $1\x00\x00\x00"
         r = bytearray(_wire(0x0A000001, 0x0A000002, proto=3, method=3, status=1, payload=b"P" + (len(body) + 4).to_bytes(4, "big") + body))

@@ -18,7 +18,7 @@ import pytest
 
 from oracle import pyoracle
 from oracle.pyoracle import SockLine
-from tests.test_sockline import _ip, _tcp_wire
+from tests.helpers import _ip, _tcp_wire
 
 HEADER = "  sl  local_address rem_address   st tx_queue rx_queue tr tm->when retrnsmt   uid  timeout inode"
 REF_LINE = "   0: 7038A8C0:A24A C28D640A:0050 01 00000000:00000000 02:000002E0 00000000     0        0 5276530 2 ffff8e8be7a0bd40 20 4 24 10 -1"
@@ -225,7 +225,7 @@ def test_process_exit_forgets_the_process_lines_and_statements_by_pid_prefix():
     """data.go:363-398 + cluster.go:97-110.  pid 12 exits: its lines go, those of 123 stay (SocketMaps is indexed by the
     number) — but the Postgres statements and HTTP/2 parsers of 123 go too (string prefix "12")."""
     from alaz_amd import engine
-    from tests.test_oracle_golden import _wire
+    from tests.helpers import _wire
     hl = _host()
     E = pyoracle.TCP_ESTABLISHED
     o = pyoracle.Oracle(0, 0, log_limit=100)

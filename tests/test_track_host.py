@@ -1,45 +1,25 @@
 """K13, the tracks, on the CPU: the pure-Python reference tests/track_ref.py against a second formulation written apart from it (sets
 of refs per track and a sort instead of the min / claim arithmetic) over random sequences of windows, hand-written known answers for
 every rule of the contract, invariants over the oracle's churn windows, and the plan in alaz_amd/csrc/sg_plan.hpp
-(tests/micro/track_plan_test.cpp)."""
+(tests/micro/plan_driver.cpp, stage track)."""
 import ctypes as C
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine, weights
-from alaz_amd.replay import EDGE_OUT_DTYPE
 from tests.helpers import CLOCK
+from tests.host_scaffold import LABEL, MERGED, NEW, OBIP, SPLIT, _coverage, chain, random_sequence, window_of
 from tests.incident_ref import incident_ref, quantile_threshold
 from tests.nodes_ref import nodes_ref
-from tests.test_gpu_node_trend import churn  # noqa: F401  (the fixture: events only, no engine)
-from tests.track_ref import TrackRef, is_anchor
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout
+from tests.traces import churn  # noqa: F401  (the fixture: events only, no engine)
+from tests.track_ref import TrackRef, is_anchor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NO = engine.NO_TRACK
-NEW, SPLIT, MERGED = engine.TRACK_NEW, engine.TRACK_SPLIT, engine.TRACK_MERGED
-OBIP = 2 << 30
-LABEL = 1 << 30
-
-
-def window_of(edges):
-    """(node rows, incident per node row, incident rows) of a window whose red rows are exactly `edges`, (from_ref, to_ref) pairs"""
-    edges = sorted(set(edges))
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for j, (f, t) in enumerate(edges):
-        r[j]["from_ref"], r[j]["to_ref"], r[j]["score"] = f, t, 0.9
-        r[j]["count"], r[j]["err_count"], r[j]["sum_ns"] = 10 + j, j % 3, 1000 * (j + 1)
-    nodes = nodes_ref(r)
-    inc, node_inc = incident_ref(r, nodes, "score", 0.5)
-    return nodes, node_inc, inc
-
-
-def chain(*ids):
-    return list(zip(ids[:-1], ids[1:]))
 
 
 def by_ref(win, rows):
@@ -114,50 +94,6 @@ class TrackSets:
 
     def entries(self):
         return self._arr(self.tracks)
-
-
-def random_sequence(seed, windows=30, n_nodes=40):
-    """edge sets that drift: a few edges die and a few are born per window, now and then a burst of deaths or an empty window; refs
-    are pods, a few labels and a few outbound IPs (whose index means another address in every window)"""
-    rng = np.random.default_rng(7000 + seed)
-    refs = list(range(n_nodes - 6)) + [LABEL | k for k in range(3)] + [OBIP | k for k in range(3)]
-    pods = n_nodes - 6
-    alive = set()
-    out = []
-    for w in range(windows):
-        mode = rng.random()
-        if mode < 0.12:
-            out.append([]); continue                                  # a silent window: the edges come back afterwards
-        if mode < 0.22:
-            alive = {e for e in alive if rng.random() < 0.3}
-        alive = {e for e in alive if rng.random() < 0.8}
-        for _ in range(int(rng.integers(2, 7))):
-            a = int(rng.integers(0, pods))                            # (a pod at one end of every row)
-            b = refs[int(rng.integers(0, len(refs)))]
-            alive.add((a, b) if rng.random() < 0.8 or b >= LABEL else (b, a))
-        out.append(sorted(alive))
-    return out
-
-
-def _coverage(ref_before, rows, ended, table_after, w, quiet):
-    met = set()
-    flags = rows["flags"]
-    if (flags & MERGED).any():
-        met.add("merged")
-    old = {e["track"]: e for e in ref_before}
-    for r in rows:
-        if r["flags"] & SPLIT:
-            claimant = [x for x in rows if x["track"] == r["parent"]]
-            if claimant:
-                met.add("split_kept" if claimant[0]["kept_nodes"] > r["kept_nodes"] else "split_tie")
-        if not r["flags"] & NEW and old[r["track"]]["last_window"] < w - 1:
-            met.add("revival")
-    if len(ended):
-        met.add("ended")
-    now = {e["track"] for e in table_after}
-    if any(t not in now for t in old):
-        met.add("expiry")
-    return met
 
 
 @pytest.mark.parametrize("quiet", [0, 1, 3])
@@ -342,16 +278,7 @@ def test_invariants_over_the_oracle_windows(oracle_windows, quiet):
 
 
 # ---- the plan ---------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def track_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("trkplan") / "track_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "track_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+track_plan = plan_fixture("track")
 
 
 def _p(mk, ml, nc, slots=1, ss=16, quiet=2, mt=0, res=0):

@@ -1,9 +1,8 @@
 """CPU tests of the traffic baselines (K23): the numpy references of tests/traffic_ref.py against a second formulation written apart
 from them (a dict keyed by (from_key, to_key), plain Python floats, one sample at a time), against hand-computed answers, the
 scenario the stage is for — a drop of traffic that latency and error ratio do not see — the plan in alaz_amd/csrc/sg_plan.hpp
-(tests/micro/traffic_trend_plan_test.cpp) and the header's constants against alaz_amd/engine.py."""
+(tests/micro/plan_driver.cpp, stage traffic_trend) and the header's constants against alaz_amd/engine.py."""
 import ctypes as C
-import json
 import os
 import re
 import subprocess
@@ -17,8 +16,9 @@ from tests.group_nodes_ref import GroupNodeTrendRef, group_nodes_ref
 from tests.group_ref import group_ref
 from tests.group_trend_ref import group_keys, workload_keys
 from tests.nodes_ref import nodes_ref
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout, check_soa
-from tests.test_group_host import _random_map, _random_rows
+from tests.traces import _random_map, _random_rows
 from tests.traffic_ref import (EdgeTrafficRef, GroupTrafficRef, NodeTrafficRef, WorkloadTrafficRef, ref_select_traffic,
                                traffic_column)
 from tests.trend_ref import ref_keys, row_keys
@@ -317,16 +317,7 @@ SCENARIO_DESIGN_VALUES = (-0.13, -26.0)                                  # (the 
 
 
 # ---- the plan --------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("trafficplan") / "traffic_trend_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "traffic_trend_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+plan = plan_fixture("traffic_trend")
 
 
 def _p(spaces=15, on=15, me=4096, ncap=1000, nc=1500, slots=1, ss=40, shift=0, warmup=0, ttl=0, maxe=0, lf=0, rf=0, res=0):
@@ -395,14 +386,14 @@ def test_the_headers_constants_and_struct_are_the_front_ends(tmp_path):
         assert re.search(r"^int " + fn + r"\(", h, re.M) and fn in engine._SIGNATURES, fn
     assert engine.ABI_VERSION == 6 and "#define SG_ABI_VERSION 6u" in h        # additive: the version does not move
     # the struct's size, every field's offset, size and kind, and the constants, by the compiler: tests/test_abi.py's own check
-    from tests import test_abi
+    from tests import abi_layouts
     src = tmp_path / "traffic_layout_check.c"
     consts = {**{"SG_T_" + k.upper(): v for k, v in engine.T_SPACES.items()}, **{"SG_TSEL_" + k.upper(): v for k, v in engine.TSEL_BY.items()},
               **{"SG_TSEL_" + k.upper(): v for k, v in engine.TSEL_SIDE.items()}}
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(test_abi, "LAYOUTS", {"sg_traffic_params": engine.TrafficParams})
-        mp.setattr(test_abi, "CONSTANTS", consts)
-        src.write_text(test_abi.layout_check_source())
+        mp.setattr(abi_layouts, "LAYOUTS", {"sg_traffic_params": engine.TrafficParams})
+        mp.setattr(abi_layouts, "CONSTANTS", consts)
+        src.write_text(abi_layouts.layout_check_source())
     assert "offsetof(sg_traffic_params, rate_floor) == 32" in src.read_text() and "SG_TSEL_OUT) == 8LL" in src.read_text()
     r = subprocess.run(["gcc", "-std=c11", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr

@@ -1,33 +1,19 @@
 """CPU tests of the per-edge baselines (K8): the numpy reference tests/trend_ref.py against hand-computed sequences, and the plan
-in alaz_amd/csrc/sg_plan.hpp (tests/micro/trend_plan_test.cpp) — parameter checks and defaults, and memory for every window an
+in alaz_amd/csrc/sg_plan.hpp (tests/micro/plan_driver.cpp, stage trend) — parameter checks and defaults, and memory for every window an
 engine can close."""
 import ctypes as C
-import json
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 from alaz_amd import engine
-from alaz_amd.replay import EDGE_OUT_DTYPE
-from tests.trend_ref import REF_KNOWN, REF_LABEL, REF_OBIP, TrendRef, ref_keys, row_keys, strictly_ascending
+from tests.helpers import ref
+from tests.host_scaffold import trend_rows_of as rows_of
+from tests.plan_driver import plan_fixture
 from tests.plan_layout import check_layout, check_soa
+from tests.trend_ref import REF_KNOWN, REF_LABEL, REF_OBIP, TrendRef, ref_keys, row_keys, strictly_ascending
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def ref(t, v):
-    return (t << 30) | v
-
-
-def rows_of(*edges):
-    """rows from (from_ref, to_ref, count, err_count, sum_ns) tuples"""
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for i, (f, t, c, e, s) in enumerate(edges):
-        r[i]["from_ref"], r[i]["to_ref"], r[i]["count"], r[i]["err_count"], r[i]["sum_ns"] = f, t, c, e, s
-    return r
-
 
 A, B_, C_ = ref(REF_KNOWN, 1), ref(REF_KNOWN, 2), ref(REF_KNOWN, 3)
 NOOB = np.zeros(0, np.uint32)
@@ -145,16 +131,7 @@ def test_reversed_direction_and_outbound_ip_keys():
     assert int(ref_keys([ref(REF_OBIP, 3)], ob2)[0]) == (2 << 32) | 0xC0A80001
 
 
-@pytest.fixture(scope="module")
-def trend_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("trendplan") / "trend_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "trend_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+trend_plan = plan_fixture("trend")
 
 
 def _p(me, slots=1, ss=40, shift=0, warmup=0, ttl=0, maxe=0, lf=0, ef=0, res=0):

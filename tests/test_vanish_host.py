@@ -1,38 +1,26 @@
 """CPU tests of K8's vanished list and of the selection by a trend key: the numpy reference tests/vanish_ref.py against hand-computed
 sequences, the Python dtypes and constants against include/servicegraph.h, and the plan in alaz_amd/csrc/sg_plan.hpp
-(tests/micro/vanish_plan_test.cpp) — parameter checks and defaults, and memory for every window slot."""
+(tests/micro/plan_driver.cpp, stage vanish) — parameter checks and defaults, and memory for every window slot."""
 import ctypes as C
-import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from alaz_amd import engine
 from alaz_amd.replay import EDGE_OUT_DTYPE
+from tests.helpers import ref
+from tests.host_scaffold import trend_rows_of as rows_of
+from tests.plan_driver import plan_fixture
+from tests.plan_layout import check_layout
 from tests.select_by_ref import ref_select_by
 from tests.trend_ref import REF_KNOWN, TrendRef
 from tests.vanish_ref import NO_ROW, VanishRef
-from tests.plan_layout import check_layout
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 NOOB = np.zeros(0, np.uint32)
-
-
-def ref(t, v):
-    return (t << 30) | v
-
-
-def rows_of(*edges):
-    """rows from (from_ref, to_ref, count, err_count, sum_ns) tuples"""
-    r = np.zeros(len(edges), dtype=EDGE_OUT_DTYPE)
-    for i, (f, t, c, e, s) in enumerate(edges):
-        r[i]["from_ref"], r[i]["to_ref"], r[i]["count"], r[i]["err_count"], r[i]["sum_ns"] = f, t, c, e, s
-    return r
-
 
 A, B_, C_, D_ = (ref(REF_KNOWN, v) for v in (1, 2, 3, 4))
 AB, AC, AD = (A, B_, 1, 0, 1000), (A, C_, 1, 0, 2000), (A, D_, 1, 0, 3000)
@@ -117,16 +105,7 @@ def test_selection_keys_by_trend_value():
     assert list(ref_select_by(rows, tr, "new", 2, 0.0)) == [0, 1]
 
 
-@pytest.fixture(scope="module")
-def vanish_plan(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("vanishplan") / "vanish_plan_test"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), os.path.join(HERE, "micro", "vanish_plan_test.cpp")])
-
-    def run(lines):
-        out = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, l)) for l in lines) + "\n", capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0, out.stderr
-        return [json.loads(l) for l in out.stdout.splitlines()]
-    return run
+vanish_plan = plan_fixture("vanish")
 
 
 def _p(me, slots=1, warmup=0, ttl=0, maxe=0, ss=16, silent=0, seen=0, rows=0):

@@ -9,7 +9,7 @@ red ("all": min_value = -inf).  After each window of the K22 engine, window_grou
 group edge, 80 bytes each, over PCIe, to search the call graph on the host: the only way to an incident's callers without this
 stage).  The last window's rows of each phase are held to the reference (tests/impact_ref.py) unless --no-check.  For the device
 time per kernel run it under `rocprofv3 --kernel-trace --stats -- python tools/group_impact_probe.py --windows 3 --only-on
---no-check` (the k22_* rows of the stats).  The stage's memory is the plan's to say (tests/micro/group_impact_plan_test.cpp prints
+--no-check` (the k22_* rows of the stats).  The stage's memory is the plan's to say (tests/micro/plan_driver.cpp, stage group_impact, prints
 plan_group_impact).  Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
 

@@ -9,7 +9,7 @@ engine, window_group_incidents() is timed against window_groups() (every group e
 on the host: the only way to workload incidents without this stage).  The last window's incidents of each phase are held to the
 reference (tests/group_incident_ref.py) unless --no-check.  For the device time per kernel run it under `rocprofv3 --kernel-trace
 --stats -- python tools/group_incident_probe.py --windows 3 --only-on --no-check` (the k18_* rows of the stats).  The stage's memory
-is the plan's to say (tests/micro/group_incident_plan_test.cpp prints plan_group_incidents).  Prints one JSON line; --out also
+is the plan's to say (tests/micro/plan_driver.cpp, stage group_incident, prints plan_group_incidents).  Prints one JSON line; --out also
 writes it to a file."""
 from __future__ import annotations
 

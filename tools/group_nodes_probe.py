@@ -6,7 +6,7 @@ Deployment of 20 replicas), one of them with the workload rows and their baselin
 After each window of the K16 engine, window_group_nodes_top(k = --k) is timed against window_groups() (every group edge, 80 bytes
 each, over PCIe: the only way to workload rows without this stage) and against window_group_nodes().  For the device time per
 kernel run it under `rocprofv3 --kernel-trace --stats -- python tools/group_nodes_probe.py --windows 3 --only-on` (the k16_* rows
-of the stats).  The stage's memory is the plan's to say (tests/micro/group_nodes_plan_test.cpp prints plan_group_nodes,
+of the stats).  The stage's memory is the plan's to say (tests/micro/plan_driver.cpp, stage group_nodes, prints plan_group_nodes,
 plan_group_node_trend and plan_group_node_select).  Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
 

@@ -8,7 +8,7 @@ window_groups() (every group edge, 80 bytes each, over PCIe, to walk on the host
 stage) and against window_group_rank() of every row.  The last window's rank rows are held to the reference (tests/group_rank_ref.py)
 unless --no-check.  For the device time per kernel run it under `rocprofv3 --kernel-trace --stats -- python
 tools/group_rank_probe.py --windows 3 --only-on --no-check` (the k17_* rows of the stats).  The stage's memory and its working
-workgroups are the plan's to say (tests/micro/group_rank_plan_test.cpp prints plan_group_rank).  Prints one JSON line; --out also
+workgroups are the plan's to say (tests/micro/plan_driver.cpp, stage group_rank, prints plan_group_rank).  Prints one JSON line; --out also
 writes it to a file."""
 from __future__ import annotations
 

@@ -10,7 +10,7 @@ match components on the host: the only way to workload tracks without K18 and th
 held to the reference (tests/group_track_ref.py, fed every window of the phase) unless --no-check.  For the device time per kernel
 run it under `rocprofv3 --kernel-trace --stats -- python tools/group_track_probe.py --windows 3 --only-on --no-check` (the k13_* and
 k19_* rows of the stats; K13 itself is off here, so the k13_* rows are this stage's).  The stage's memory is the plan's to say
-(tests/micro/group_track_plan_test.cpp prints plan_group_tracks).  Prints one JSON line; --out also writes it to a file."""
+(tests/micro/plan_driver.cpp, stage group_track, prints plan_group_tracks).  Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
 
 import argparse

@@ -7,7 +7,7 @@ window_groups_top(k = --k, by lat_dev) is timed against window_groups() (every g
 window_group_trend() once.  For the device time per kernel run it under
 `rocprofv3 --kernel-trace --stats -- python tools/group_trend_probe.py --windows 3 --only-on` (the k15_* rows of the stats and
 k8_scan: this engine has no edge or node trend, so every k8_scan launch is K15's).
-The stage's memory is the plan's to say (tests/micro/group_trend_plan_test.cpp prints plan_group_trend, plan_vanished and
+The stage's memory is the plan's to say (tests/micro/plan_driver.cpp, stage group_trend, prints plan_group_trend, plan_vanished and
 plan_group_select for a max_edges).  Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
 

@@ -6,7 +6,7 @@ sg_flush_window_view is timed on the host for each, and the difference of the me
 each window of the K20 engine the p99 of --k workloads (window_group_node_quantiles with an index) is timed against the only way to
 them without this stage: window_hist() plus the rows already in hand.  For the device time per kernel run it under
 `rocprofv3 --kernel-trace --stats -- python tools/quantile_probe.py --windows 3 --only-on` (the k20_* rows of the stats).  The
-stage's memory is the plan's to say (tests/micro/quantile_plan_test.cpp prints plan_quantiles).  Prints one JSON line; --out also
+stage's memory is the plan's to say (tests/micro/plan_driver.cpp, stage quantile, prints plan_quantiles).  Prints one JSON line; --out also
 writes it to a file."""
 from __future__ import annotations
 

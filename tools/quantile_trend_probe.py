@@ -9,7 +9,7 @@ against the only way to it without this stage: the p99 of every workload (window
 host.  For the device time per kernel run it under `rocprofv3 --kernel-trace --stats -- python tools/quantile_trend_probe.py
 --windows 3 --only-on`: the k21_* rows of the stats beside k10_count / k10_write, k15_count / k15_write and k16_tcount /
 k16_twrite of the same run, the mean baselines of the same spaces on the same inputs.  The stage's memory is the plan's to say
-(tests/micro/quantile_trend_plan_test.cpp prints plan_quantile_trend).  Prints one JSON line; --out also writes it to a file."""
+(tests/micro/plan_driver.cpp, stage quantile_trend, prints plan_quantile_trend).  Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
 
 import argparse

@@ -10,7 +10,7 @@ the mean baselines' rows run beside them (window_nodes_top, window_groups_top, w
 has k23_keys next to k10_keys / k15_keys over the same rows.  For the device time per kernel run it under `rocprofv3
 --kernel-trace --stats -- python tools/traffic_probe.py --windows 3 --only-on`: the k23_* rows of the stats beside k8_count /
 k8_write, k10_count / k10_write, k15_count / k15_write and k16_tcount / k16_twrite of the same run, the mean baselines of the same
-spaces on the same inputs.  The stage's memory is the plan's to say (tests/micro/traffic_trend_plan_test.cpp prints
+spaces on the same inputs.  The stage's memory is the plan's to say (tests/micro/plan_driver.cpp, stage traffic_trend, prints
 plan_traffic_trend).  Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
 
