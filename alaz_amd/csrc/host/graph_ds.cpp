@@ -53,6 +53,10 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->window_group_nodes_top_tail = reinterpret_cast<decltype(o->window_group_nodes_top_tail)>(dlsym(dl, "sg_window_group_nodes_top_tail"));
     o->set_traffic_trend = reinterpret_cast<decltype(o->set_traffic_trend)>(dlsym(dl, "sg_set_traffic_trend"));   // optional (K23)
     o->window_group_nodes_top_traffic = reinterpret_cast<decltype(o->window_group_nodes_top_traffic)>(dlsym(dl, "sg_window_group_nodes_top_traffic"));
+    o->set_slo = reinterpret_cast<decltype(o->set_slo)>(dlsym(dl, "sg_set_slo"));   // optional (K24)
+    o->slo_assign = reinterpret_cast<decltype(o->slo_assign)>(dlsym(dl, "sg_slo_assign"));
+    o->window_group_node_slo = reinterpret_cast<decltype(o->window_group_node_slo)>(dlsym(dl, "sg_window_group_node_slo"));
+    o->window_group_nodes_top_slo = reinterpret_cast<decltype(o->window_group_nodes_top_slo)>(dlsym(dl, "sg_window_group_nodes_top_slo"));
 #undef SG_SYM
     return true;
 }
@@ -354,8 +358,9 @@ long GraphDS::WorkloadNodeTrends(std::vector<sg_node_trend>* out) {
 long GraphDS::WorkloadNodesTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
     return WorkloadNodesTopBy(api_.window_group_nodes_top, by, k, min_value, out, index);
 }
-long GraphDS::WorkloadNodesTopBy(int (*top)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*), uint32_t by,
-                                 uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
+template <class V>
+long GraphDS::WorkloadNodesTopBy(int (*top)(sg_handle, uint32_t, uint32_t, V, sg_node_out*, uint32_t*, size_t, size_t*, size_t*), uint32_t by,
+                                 uint32_t k, V min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
     if (!out || !top) return SG_EINVAL;
     std::lock_guard<std::mutex> fg(flush_mu_);
     size_t sel = 0, total = 0;
@@ -502,6 +507,37 @@ int GraphDS::SetTrafficTrend(uint32_t spaces, const sg_traffic_params* p) {
 }
 long GraphDS::WorkloadTrafficTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
     return WorkloadNodesTopBy(api_.window_group_nodes_top_traffic, by, k, min_value, out, index);
+}
+// ---- the SLO burn rates (K24) ----
+int GraphDS::SetSLO(uint32_t spaces, const sg_slo_params* p) {
+    if (!api_.set_slo) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_slo(h_, spaces, p);
+}
+int GraphDS::SetWorkloadSLO(const std::string& workload, uint32_t objective) {
+    if (!api_.slo_assign) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    uint32_t ref;
+    {
+        std::lock_guard<std::mutex> g(id_mu_);
+        auto it = gids_.find(workload);
+        if (it == gids_.end()) return SG_EINVAL;
+        ref = SG_MAKE_REF(SG_REF_GROUP, it->second);
+    }
+    return api_.slo_assign(h_, SG_Q_GROUP_NODES, &ref, &objective, 1);
+}
+long GraphDS::WorkloadSLO(std::vector<uint64_t>* out) {
+    if (!out || !api_.window_group_node_slo) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t n = 0;
+    int rc = api_.window_group_node_slo(h_, nullptr, 0, nullptr, 0, &n);
+    if (rc != SG_OK) return rc;
+    out->assign(n * SG_SLO_WORDS, 0ull);
+    if (n && (rc = api_.window_group_node_slo(h_, nullptr, 0, out->data(), n, &n)) != SG_OK) return rc;
+    return (long)n;
+}
+long GraphDS::WorkloadSLOTop(uint32_t by, uint32_t k, uint32_t min_value_q10, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
+    return WorkloadNodesTopBy(api_.window_group_nodes_top_slo, by, k, min_value_q10, out, index);
 }
 
 // the quantiles of the last flushed window, `words` u32 an entity: the count first (no index), then the rows

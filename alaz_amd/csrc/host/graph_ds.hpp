@@ -90,6 +90,11 @@ struct SgApi {
     // optional (K23; absent in an older library): SetTrafficTrend and WorkloadTrafficTop each need the entry they forward to
     int (*set_traffic_trend)(sg_handle, uint32_t, const sg_traffic_params*) = nullptr;
     int (*window_group_nodes_top_traffic)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
+    // optional (K24; absent in an older library): SetSLO, SetWorkloadSLO, WorkloadSLO and WorkloadSLOTop each need the entry they forward to
+    int (*set_slo)(sg_handle, uint32_t, const sg_slo_params*) = nullptr;
+    int (*slo_assign)(sg_handle, uint32_t, const uint32_t*, const uint32_t*, size_t) = nullptr;
+    int (*window_group_node_slo)(sg_handle, const uint32_t*, size_t, uint64_t*, size_t, size_t*) = nullptr;
+    int (*window_group_nodes_top_slo)(sg_handle, uint32_t, uint32_t, uint32_t, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -277,6 +282,17 @@ public:
     // WorkloadNodesTop names them, their indices in `index` (may be NULL).  Returns the count, or a negative SG_* code.
     int SetTrafficTrend(uint32_t spaces, const sg_traffic_params* p);
     long WorkloadTrafficTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
+    // The SLO burn rates (K24; needs SetLatencyQuantiles for the space): each service's and workload's error budget over a short
+    // and a long span of windows.  SetSLO forwards sg_set_slo (spaces: SG_Q_NODES | SG_Q_GROUP_NODES, 0 or p NULL = off; the engine's
+    // return code; SG_EINVAL without the entry).  SetWorkloadSLO: the objective word (SG_SLO_OBJECTIVE; 0 = the defaults) of the
+    // workload with this owner UID, SG_EINVAL for an owner no pod has named yet.  WorkloadSLO: the last flushed window's SLO rows,
+    // SG_SLO_WORDS words a row, row k for row k of WorkloadNodes.  WorkloadSLOTop: the selection sg_window_group_nodes_top_slo
+    // (`by` = SG_SLOSEL_ERR or SG_SLOSEL_SLOW ORed with SG_SLOSEL_IN or SG_SLOSEL_OUT; min_value_q10 in 1/1024 of "on budget"), its
+    // rows named as WorkloadNodesTop names them, their indices in `index` (may be NULL).  The count, or a negative SG_* code.
+    int SetSLO(uint32_t spaces, const sg_slo_params* p);
+    int SetWorkloadSLO(const std::string& workload, uint32_t objective);
+    long WorkloadSLO(std::vector<uint64_t>* out);
+    long WorkloadSLOTop(uint32_t by, uint32_t k, uint32_t min_value_q10, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }
@@ -309,8 +325,10 @@ private:
     void NameWorkloadNodes(const std::vector<sg_node_out>& rows, std::vector<WorkloadNode>* out);   // (takes id_mu_)
     int FlushShard(Shard& s);                          // s.mu held
     // a selection over the workload rows through `top` (sg_window_group_nodes_top or its _tail twin): WorkloadNodesTop's body
-    long WorkloadNodesTopBy(int (*top)(sg_handle, uint32_t, uint32_t, float, sg_node_out*, uint32_t*, size_t, size_t*, size_t*), uint32_t by,
-                            uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
+    // (V: the threshold's type — float, or K24's uint32_t)
+    template <class V>
+    long WorkloadNodesTopBy(int (*top)(sg_handle, uint32_t, uint32_t, V, sg_node_out*, uint32_t*, size_t, size_t*, size_t*), uint32_t by,
+                            uint32_t k, V min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
     // every trend row of the last flushed window through an indexed read (index NULL): the count first, then the rows
     template <class Row>
     long TrendRows(int (*read)(sg_handle, const uint32_t*, size_t, Row*, size_t, size_t*), std::vector<Row>* out) {

@@ -32,6 +32,7 @@ struct MockEngine {
     std::vector<std::array<uint64_t, 4>> k17_ops;      // {1, iters, damping_q8, seed} per sg_set_group_rank (NULL: ~0 in the three), {2, k, the bits of min_share, cap} per sg_window_group_rank_top
     std::vector<std::array<uint64_t, 4>> k21_ops;      // {1, spaces, permille, shift (NULL: ~0)} per sg_set_quantile_trend, {2 / 3 / 4, cap, 0, 0} per sg_window_node_quantile_trend / sg_window_group_quantile_trend / sg_window_group_node_quantile_trend, {5, by, k, the bits of min_value} per sg_window_group_nodes_top_tail
     std::vector<std::array<uint64_t, 4>> k23_ops;      // {1, spaces, shift (NULL: ~0), rate_floor | load_floor_ns << 32} per sg_set_traffic_trend, {2, by, k, the bits of min_value} per sg_window_group_nodes_top_traffic
+    std::vector<std::array<uint64_t, 4>> k24_ops;      // {1, spaces, latency_bin | long_windows << 32 (NULL: ~0), min_requests} per sg_set_slo, {2, space, ref, objective} per ref of sg_slo_assign, {3, cap, 0, 0} per sg_window_group_node_slo, {4, by, k, min_value_q10} per sg_window_group_nodes_top_slo
     std::vector<std::array<uint64_t, 4>> k20_ops;      // {1, spaces, n_q, the first four per-mille 16 bits each} per sg_set_quantiles, {2 / 3 / 4, n_index (~0: no index), cap, 0} per sg_window_node_quantiles / sg_window_group_quantiles / sg_window_group_node_quantiles
     size_t k20_nq = 2;
     std::vector<std::array<uint64_t, 4>> k19_ops;      // {1, quiet_windows, max_tracks, reserved} per sg_set_group_tracks (NULL: ~0 in the three), {2, cap, 0, 0} per sg_window_group_incident_tracks, {3, cap, 0, 0} per sg_window_group_tracks_ended
@@ -278,6 +279,35 @@ int m_window_group_nodes_top_traffic(sg_handle h, uint32_t by, uint32_t k, float
     for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
     return SG_OK;
 }
+// K24's stand-ins: the switch and the objectives recorded; three SLO rows, row j's word w = 100 j + w; the selection is K16's with
+// rows 1 and 2 of three
+int m_set_slo(sg_handle h, uint32_t spaces, const sg_slo_params* p) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k24_ops.push_back({1u, spaces, p ? (uint64_t)p->latency_bin | (uint64_t)p->long_windows << 32 : ~0ull, p ? p->min_requests : 0u});
+    return (spaces & ~5u) ? SG_EINVAL : SG_OK;
+}
+int m_slo_assign(sg_handle h, uint32_t space, const uint32_t* refs, const uint32_t* obj, size_t n) {
+    M_LOCK(h);
+    for (size_t i = 0; i < n; i++) reinterpret_cast<MockEngine*>(h)->k24_ops.push_back({2u, space, refs[i], obj[i]});
+    return SG_OK;
+}
+int m_window_group_node_slo(sg_handle h, const uint32_t*, size_t, uint64_t* out, size_t cap, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k24_ops.push_back({3u, (uint64_t)cap, 0u, 0u});
+    if (n) *n = 3;
+    for (size_t j = 0; out && j < std::min<size_t>(3, cap); j++) for (size_t w = 0; w < SG_SLO_WORDS; w++) out[j * SG_SLO_WORDS + w] = 100 * j + w;
+    return SG_OK;
+}
+int m_window_group_nodes_top_slo(sg_handle h, uint32_t by, uint32_t k, uint32_t min_value_q10, sg_node_out* out, uint32_t* idx, size_t cap, size_t* n_sel, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k24_ops.push_back({4u, by, k, min_value_q10});
+    if (n_sel) *n_sel = 2;
+    if (n) *n = 3;
+    const sg_node_out e[2] = {m_node(SG_MAKE_REF(SG_REF_GROUP, 0), 4, 9, 1, 1, 0.5f), m_node(SG_MAKE_REF(SG_REF_KNOWN, 0), 0, 4, 0, 1, 0.25f)};
+    const uint32_t at[2] = {1u, 2u};
+    for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
+    return SG_OK;
+}
 int m_window_group_node_incident(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
     M_LOCK(h);
     reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({3u, (uint64_t)n_idx, (uint64_t)cap, 0u});
@@ -384,6 +414,8 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.window_group_quantile_trend = m_window_group_quantile_trend; c->api.window_group_node_quantile_trend = m_window_group_node_quantile_trend;
         c->api.window_group_nodes_top_tail = m_window_group_nodes_top_tail;
         c->api.set_traffic_trend = m_set_traffic_trend; c->api.window_group_nodes_top_traffic = m_window_group_nodes_top_traffic;
+        c->api.set_slo = m_set_slo; c->api.slo_assign = m_slo_assign; c->api.window_group_node_slo = m_window_group_node_slo;
+        c->api.window_group_nodes_top_slo = m_window_group_nodes_top_slo;
         c->api.set_group_incidents = m_set_group_incidents; c->api.window_group_incidents = m_window_group_incidents;
         c->api.window_group_node_incident = m_window_group_node_incident;
         c->api.set_group_impact = m_set_group_impact; c->api.window_group_impact = m_window_group_impact;
@@ -632,6 +664,32 @@ int sgh_graphds_set_traffic_trend(void* g, uint32_t spaces, int on, uint32_t shi
 long sgh_graphds_workload_traffic_top(void* g, uint32_t by, uint32_t k, float min_value, sgh_workload_node* out, uint32_t* index, size_t cap) {
     std::vector<WorkloadNode> v; std::vector<uint32_t> idx;
     const long n = static_cast<HostCtx*>(g)->ds->WorkloadTrafficTop(by, k, min_value, &v, &idx);
+    if (n < 0) return n;
+    for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_node(v[i], out + i); if (index) index[i] = idx[i]; }
+    return n;
+}
+// the SLO burn rates (K24): the switch (on = 0: off), a workload's objective word by its owner UID, the SLO rows (SG_SLO_WORDS u64
+// each; the count, min(count, cap) rows written) and the selection by a burn rate, as sgh_graphds_workload_nodes_top gives it
+int sgh_graphds_set_slo(void* g, uint32_t spaces, int on, uint32_t latency_bin, uint32_t latency_target_ppm, uint32_t error_target_ppm,
+                        uint32_t short_windows, uint32_t long_windows, uint32_t min_burn_q10, uint64_t min_requests) {
+    sg_slo_params p{}; p.struct_size = sizeof p; p.latency_bin = latency_bin; p.latency_target_ppm = latency_target_ppm;
+    p.error_target_ppm = error_target_ppm; p.short_windows = short_windows; p.long_windows = long_windows; p.min_burn_q10 = min_burn_q10;
+    p.min_requests = min_requests;
+    return static_cast<HostCtx*>(g)->ds->SetSLO(spaces, on ? &p : nullptr);
+}
+int sgh_graphds_set_workload_slo(void* g, const char* workload, uint32_t objective) {
+    return static_cast<HostCtx*>(g)->ds->SetWorkloadSLO(workload ? workload : "", objective);
+}
+long sgh_graphds_workload_slo(void* g, uint64_t* out, size_t cap) {
+    std::vector<uint64_t> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadSLO(&v);
+    if (n < 0) return n;
+    if (out) std::memcpy(out, v.data(), std::min(cap, (size_t)n) * SG_SLO_WORDS * sizeof(uint64_t));
+    return n;
+}
+long sgh_graphds_workload_slo_top(void* g, uint32_t by, uint32_t k, uint32_t min_value_q10, sgh_workload_node* out, uint32_t* index, size_t cap) {
+    std::vector<WorkloadNode> v; std::vector<uint32_t> idx;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadSLOTop(by, k, min_value_q10, &v, &idx);
     if (n < 0) return n;
     for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_node(v[i], out + i); if (index) index[i] = idx[i]; }
     return n;
@@ -962,6 +1020,14 @@ size_t sgh_mock_k23_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k23_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k23_ops[i].data(), 32);
     return m->k23_ops.size();
+}
+size_t sgh_mock_k24_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k24_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k24_ops[i].data(), 32);
+    return m->k24_ops.size();
 }
 size_t sgh_mock_k20_ops(void* g, uint64_t* out4, size_t cap) {
     auto* c = static_cast<HostCtx*>(g);

@@ -40,6 +40,7 @@
 #include "sg_group_track.h"
 #include "sg_quantiles.h"
 #include "sg_quantile_trend.h"
+#include "sg_slo.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -283,6 +284,14 @@ struct sg_engine {
     // are the stage's (rate_floor, load_floor_ns as the walk gets them), not sg_trend_params'.
     struct Traffic { double lat_floor = 0, err_floor = 0; Baseline<sg_edge_trend> edges; Baseline<sg_node_trend> nodes; Baseline<sg_edge_trend> groups;
                      Baseline<sg_node_trend> workloads; } trf;
+    // K24, the SLO burn rates (sg_slo.h): per requested space (0: the nodes, 1: the workloads) one block (sg_plan.hpp plan_slo),
+    // allocated at sg_set_slo, freed in front of its K20 space.  The ring, the sums and the objective words are state kept across
+    // windows, indexed by key: the event chains the updates in window order across the slots' streams (w = windows enqueued).  The
+    // host keeps the objective words it uploaded (h_obj).  Per slot: the rows, and whether the window in the slot made them.
+    struct SloSpace { bool on = false; char* mem = nullptr; u64* ring = nullptr; u64* sums = nullptr; u32* obj = nullptr; u64* ctl = nullptr;
+                      u64* stage = nullptr; u32* stage_idx = nullptr; std::vector<u64*> rows; std::vector<char> valid; u64 w = 0;
+                      std::vector<u32> h_obj; hipEvent_t ev = nullptr; bool pending = false; };
+    struct Slo { sg_slo_params p{}; sgplan::SloPlan plan; SloSpace sp[2]; } slo;
 };
 
 namespace {
@@ -1413,11 +1422,52 @@ void free_traffic(sg_engine* e, int k) {
     if (k == kTEdges || k == kTGroups) free_baseline(k == kTEdges ? e->trf.edges : e->trf.groups);
     else free_baseline(k == kTNodes ? e->trf.nodes : e->trf.workloads);
 }
+// ---- K24, the SLO burn rates (engine lock held) --------------------------------------------------------------------------------------
+static_assert(sgplan::kSloThreads == K24_THREADS && sgplan::kSloMaxWgs == K24_MAX_WGS && sgplan::kSloCtlWords == K24C_WORDS &&
+              sgplan::kSloMaxKeys <= sgplan::kQMaxKeys, "plan_slo sizes the launches of sg_slo.h");
+enum { kSNodes = 0, kSWorkloads = 1 };
+constexpr StageWords kSloWords[2] = {
+    {"the node SLO stage is off (sg_set_slo, SG_Q_NODES)", "the node SLO stage was off"},
+    {"the workload SLO stage is off (sg_set_slo, SG_Q_GROUP_NODES)", "the workload SLO stage was off"}};
+// enqueue the update of SLO space k by the window in slot cur on stream s (behind the space's K20 fold, on the same stream) and
+// behind the previous update (any stream): the slices that leave the spans, then the window's samples and rows
+int launch_slo(sg_engine* e, int k, hipStream_t s) {
+    sg_engine::SloSpace& x = e->slo.sp[k];
+    const sgplan::SloSpace& P = e->slo.plan.sp[k];
+    const sg_slo_params& p = e->slo.p;
+    SloArgs a{};
+    if (k == kSNodes) {
+        a.g.nd = nodes_view(e, work(e), e->plan.ncap);
+        a.nodes = e->nodes.rows[e->cur]; a.count = e->nodes.count[e->cur];
+    } else {
+        a.g = group_nodes_view(e);
+        a.nodes = e->gnodes.rows[e->cur]; a.count = e->gnodes.count[e->cur];
+    }
+    a.cap = (u32)P.cap; a.workload = k == kSWorkloads;
+    a.hist = e->qnt.sp[k == kSNodes ? kQNodes : kQWorkloads].hist[e->cur];
+    a.keys = (u32)P.keys; a.S = p.short_windows; a.L = p.long_windows; a.w = x.w;
+    a.bin = p.latency_bin; a.lat_budget = e->slo.plan.lat_budget; a.err_budget = e->slo.plan.err_budget; a.min_burn = p.min_burn_q10;
+    a.min_requests = p.min_requests;
+    a.ring = x.ring; a.sums = x.sums; a.obj = x.obj; a.ctl = x.ctl; a.out = x.rows[e->cur];
+    if (const int rc = stage_wait(e, x, s)) return rc;
+    hipLaunchKernelGGL(k24_retire, dim3(P.key_wgs), dim3(K24_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k24_update, dim3(P.row_wgs), dim3(K24_THREADS), 0, s, a);
+    if (const int rc = stage_done(e, x, s)) return rc;
+    x.w++;
+    x.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_slo(sg_engine* e, int k) {
+    free_stage(e->slo.sp[k]);
+    e->slo.plan.sp[k] = sgplan::SloSpace{};
+    e->slo.plan.spaces &= ~(k == kSNodes ? SG_Q_NODES : SG_Q_GROUP_NODES);
+}
 void free_quantile_trend(sg_engine* e, int k) {
     if (k == kQGroups) free_baseline(e->qtr.groups);
     else free_baseline(k == kQNodes ? e->qtr.nodes : e->qtr.workloads);
 }
 void free_quantiles(sg_engine* e, int k) {
+    if (k != kQGroups) free_slo(e, k == kQNodes ? kSNodes : kSWorkloads);   // (K24 reads the space's histograms)
     free_quantile_trend(e, k);                                        // (the tail baseline reads the space's table)
     free_stage(e->qnt.sp[k]);
     e->qnt.plan.sp[k] = sgplan::QuantSpace{};
@@ -1502,6 +1552,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
         if (e->inc.on) { if (const int rc = launch_incidents(e, s)) return rc; }   // K12 behind K8, K9 and K11: the trend rows, the node rows, the rank rows
         if (e->trk.on) { if (const int rc = launch_node_tracks(e, s)) return rc; }   // K13 behind K12: the node rows, the incident rows, the incident per node row
         if (e->qnt.sp[kQNodes].on) { if (const int rc = launch_quantiles(e, kQNodes, s)) return rc; }   // K20 behind K9: the rows, their histograms, the node rows
+        if (e->slo.sp[kSNodes].on) { if (const int rc = launch_slo(e, kSNodes, s)) return rc; }   // K24 behind K20: the node rows, their count, the histograms
         if (e->qtr.nodes.on) { if (const int rc = launch_node_tail(e, tail_node_space(e), kQNodes, s, k21_ncount, k21_nwrite)) return rc; }   // K21 behind K20: the node rows, the quantiles
     }
     if (e->grp.on) {                                                 // K14 behind K5: the rows and the window counters only, whatever else is on
@@ -1519,6 +1570,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
             if (e->gtrk.on) { if (const int rc = launch_group_tracks(e, s)) return rc; }   // K19 behind K18: the workload rows, the incident rows, the incident per workload row
             if (e->gimp.on) { if (const int rc = launch_group_impact(e, s)) return rc; }   // K22 behind K18: the group edges, the workload rows, the incident count and the incident per workload row
             if (e->qnt.sp[kQWorkloads].on) { if (const int rc = launch_quantiles(e, kQWorkloads, s)) return rc; }   // K20 behind K16: and the workload rows
+            if (e->slo.sp[kSWorkloads].on) { if (const int rc = launch_slo(e, kSWorkloads, s)) return rc; }   // K24 behind K20: the workload rows, their count, the histograms
             if (e->qtr.workloads.on) { if (const int rc = launch_node_tail(e, tail_workload_space(e), kQWorkloads, s, k21_wcount, k21_wwrite)) return rc; }   // K21 behind K20
         }
     }
@@ -4407,6 +4459,205 @@ int sg_window_group_nodes_top_traffic(sg_handle e, uint32_t by, uint32_t k, floa
     if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     return nodes_top_traffic(e, traffic_workload_space(e), "sg_window_group_nodes_top_traffic", by, k, min_value, out, node_index, cap, n_selected, n_nodes);
+}
+
+// ---- K24, the SLO burn rates: the C ABI -------------------------------------------------------------------------------------------------
+namespace {
+static_assert(sizeof(sg_slo_params) == 40 && sizeof(sg_slo_stats) == 32, "the layouts include/servicegraph.h states");
+struct SloRow { u64 w[SG_SLO_WORDS]; };   // a row as the gathers move it
+int slo_space(uint32_t space) { return space == SG_Q_NODES ? kSNodes : space == SG_Q_GROUP_NODES ? kSWorkloads : -1; }
+int bad_slo_space(sg_engine* e, const char* call) { e->err = std::string(call) + ": space is SG_Q_NODES or SG_Q_GROUP_NODES"; return SG_EINVAL; }
+NodeSpace slo_node_space(sg_engine* e, int k) { return k == kSNodes ? node_space(e) : workload_space(e); }
+// the switch: off (spaces 0 or p NULL), or the requested spaces on with empty state; a refused call leaves the stage as it was, a
+// failed allocation leaves it off with nothing of the call kept
+int slo_set(sg_engine* e, u32 spaces, const sg_slo_params* p) {
+    const char* call = "sg_set_slo";
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    auto release = [e] { for (int k = 0; k < 2; k++) free_slo(e, k); };
+    if (!spaces || !p) { release(); return SG_OK; }
+    const u32 on = (e->qnt.sp[kQNodes].on ? SG_Q_NODES : 0u) | (e->qnt.sp[kQWorkloads].on ? SG_Q_GROUP_NODES : 0u);
+    const u32 slots = (u32)e->slots.size();
+    sgplan::SloPlan P;
+    const int prc = sgplan::plan_slo(*p, spaces, on, e->cfg.max_known_nodes, e->cfg.max_labels, e->gnodes.on ? e->gnodes.plan.max_groups : 0, e->plan.ncap,
+                                     e->gnodes.on ? e->gnodes.plan.nc : 0, slots, &P);
+    if (prc == SG_ESTATE) {
+        e->err = std::string(call) + ": " + kQuantWords[(spaces & ~on) & SG_Q_NODES ? kQNodes : kQWorkloads].off;
+        return SG_ESTATE;
+    }
+    if (prc) { e->err = std::string(call) + ": unknown space bits, bad parameters or more than 2^21 keys"; return SG_EINVAL; }
+    release();
+    e->slo.p = *p; e->slo.plan = P;
+    for (int k = 0; k < 2; k++) {
+        const sgplan::SloSpace& S = P.sp[k];
+        if (!S.on) continue;
+        sg_engine::SloSpace& x = e->slo.sp[k];
+        HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+        if (const int rc = alloc_block(e, &x.mem, S.total_bytes, call, release)) {   // (zeroed: empty sums, ring and objectives)
+            e->slo.p = sg_slo_params{}; e->slo.plan = sgplan::SloPlan{};
+            return rc;
+        }
+        x.ring = at<u64>(x.mem, S.ring_off); x.sums = at<u64>(x.mem, S.sums_off); x.obj = at<u32>(x.mem, S.obj_off); x.ctl = at<u64>(x.mem, S.ctl_off);
+        x.stage = at<u64>(x.mem, S.stage_off); x.stage_idx = at<u32>(x.mem, S.stage_idx_off);
+        for (u32 s = 0; s < slots; s++) x.rows.push_back(at<u64>(x.mem, S.slot.off + s * S.slot.bytes + S.slot_rows));
+        x.valid.assign(slots, 0);
+        x.h_obj.assign((size_t)S.keys, 0u);
+        x.on = true;
+    }
+    return SG_OK;
+}
+// the key of a ref sg_slo_assign admits in space k, or SG_NONE: the device's k24_key over the engine's id spaces
+u32 slo_key(const sg_engine* e, int k, u32 ref) {
+    const u32 t = SG_REF_TYPE(ref), v = SG_REF_VALUE(ref), mk = e->cfg.max_known_nodes, ml = e->cfg.max_labels;
+    const u32 mg = k == kSWorkloads ? e->gnodes.plan.max_groups : 0u;
+    if (t == SG_REF_GROUP) return k == kSWorkloads && v < mg ? v : SG_NONE;
+    if (t == SG_REF_KNOWN) return v < mk ? mg + v : SG_NONE;
+    if (t == SG_REF_LABEL) return v < ml ? mg + mk + v : SG_NONE;
+    return SG_NONE;
+}
+int slo_assign(sg_engine* e, int k, const uint32_t* refs, const uint32_t* objectives, size_t n) {
+    const char* call = "sg_slo_assign";
+    sg_engine::SloSpace& x = e->slo.sp[k];
+    if (!x.on) { e->err = std::string(call) + ": " + kSloWords[k].off; return SG_ESTATE; }
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    u32 lo = 0xFFFFFFFFu, hi = 0;
+    for (size_t i = 0; i < n; i++) {
+        const u32 key = slo_key(e, k, refs[i]);
+        if (key == SG_NONE || !sgplan::slo_objective_ok(objectives[i])) {
+            e->err = std::string(call) + ": a ref that is no KNOWN, LABEL or GROUP ref of the space, or an objective word that is none";
+            return SG_EINVAL;
+        }
+        lo = std::min(lo, key); hi = std::max(hi, key + 1);
+    }
+    if (lo >= hi) return SG_OK;
+    for (size_t i = 0; i < n; i++) x.h_obj[slo_key(e, k, refs[i])] = objectives[i];
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));              // (the updates enqueued so far read the words as they were)
+    HIP_TRY(e, hipMemcpy(x.obj + lo, x.h_obj.data() + lo, (size_t)(hi - lo) * sizeof(u32), hipMemcpyHostToDevice));
+    return SG_OK;
+}
+int slo_read(sg_engine* e, int k, const char* call, const uint32_t* index, size_t n_index, uint64_t* out, size_t cap, size_t* n) {
+    const sg_engine::SloSpace& x = e->slo.sp[k];
+    if (const int rc = stage_ready(e, x, call, kSloWords[k])) return rc;
+    const NodeSpace ns = slo_node_space(e, k);
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, ns.roll->count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const size_t N = (size_t)std::min<u64>(cnt, e->slo.plan.sp[k].cap);
+    const std::string beyond = std::string(call) + ": a node index beyond the window's " + ns.rows_of;
+    return copy_indexed(e, (const SloRow*)x.rows[e->cur], N, index, n_index, (SloRow*)out, cap, n, (SloRow*)x.stage, x.stage_idx,
+                        (size_t)sgplan::kSloStageRows, beyond.c_str());
+}
+int slo_entries(sg_engine* e, int k, const char* call, uint64_t* out, size_t cap, size_t* n) {
+    const sg_engine::SloSpace& x = e->slo.sp[k];
+    if (!x.on) { e->err = std::string(call) + ": " + kSloWords[k].off; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    const size_t keys = (size_t)e->slo.plan.sp[k].keys;
+    std::vector<u64> sums(keys * 12);
+    HIP_TRY(e, hipMemcpy(sums.data(), x.sums, sums.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    size_t m = 0;
+    for (size_t key = 0; key < keys; key++) {
+        const u64* s = sums.data() + key * 12;
+        if (!(s[3] | s[9])) continue;
+        if (out && m < cap) {
+            uint64_t* o = out + m * SG_SLO_ENTRY_WORDS;
+            o[0] = key; std::memcpy(o + 1, s, 12 * sizeof(u64)); o[13] = x.h_obj[key];
+        }
+        m++;
+    }
+    if (n) *n = m;
+    return SG_OK;
+}
+int slo_stats(sg_engine* e, int k, const char* call, sg_slo_stats* out) {
+    const sg_engine::SloSpace& x = e->slo.sp[k];
+    if (!x.on) { e->err = std::string(call) + ": " + kSloWords[k].off; return SG_ESTATE; }
+    if (x.pending) HIP_TRY(e, hipEventSynchronize(x.ev));
+    const sgplan::SloSpace& P = e->slo.plan.sp[k];
+    u64 ctl[K24C_WORDS];
+    HIP_TRY(e, hipMemsetAsync(x.ctl + K24C_ACTIVE, 0, sizeof(u64), e->rd_stream));
+    hipLaunchKernelGGL(k24_count, dim3(P.key_wgs), dim3(K24_THREADS), 0, e->rd_stream, (const u64*)x.sums, (u32)P.keys, x.ctl);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(ctl, x.ctl, sizeof(ctl), hipMemcpyDeviceToHost, e->rd_stream));
+    HIP_TRY(e, hipStreamSynchronize(e->rd_stream));
+    out->windows = x.w; out->keys_active = ctl[K24C_ACTIVE]; out->sides_burning = ctl[K24C_BURNING]; out->keys = P.keys;
+    return SG_OK;
+}
+// the selection by a burn rate over node space ns (the space's rows and SLO rows of the last read window): k24_keys reads the SLO
+// rows and the row count alone, behind the stage's update
+int nodes_top_slo(sg_engine* e, int k, const char* call, u32 by, u32 kk, u32 min_value_q10, sg_node_out* out, uint32_t* index, size_t cap,
+                  size_t* n_selected, size_t* n_rows) {
+    const NodeSpace ns = slo_node_space(e, k);
+    const u32 side = by & (SG_SLOSEL_IN | SG_SLOSEL_OUT);
+    if ((by & ~7u) || (side != SG_SLOSEL_IN && side != SG_SLOSEL_OUT)) {
+        e->err = std::string(call) + ": by is SG_SLOSEL_ERR or SG_SLOSEL_SLOW ORed with SG_SLOSEL_IN or SG_SLOSEL_OUT";
+        return SG_EINVAL;
+    }
+    const sg_engine::SloSpace& x = e->slo.sp[k];
+    if (const int rc = stage_ready(e, x, call, kSloWords[k])) return rc;
+    if (const int rc = check_nsel(e, ns, SG_NSEL_SCORE, e->cur)) return rc;
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    const u64 min_requests = e->slo.p.min_requests;
+    return node_top_host(e, ns, [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
+        const SelView<sg_node_out> v = node_sel_view(ns, e->cur);
+        return launch_index_select(e, v, e->rd_stream, kk, 0.f, d_out, (u32*)nullptr, stage, d_n, [&](const SelArgs& a, u32 wgs) {
+            hipLaunchKernelGGL(k24_keys, dim3(wgs), dim3(K7_THREADS), 0, e->rd_stream, a, v.count, (const u64*)x.rows[e->cur], side == SG_SLOSEL_OUT ? 1u : 0u,
+                               by & 1u, min_value_q10, min_requests, v.sel->ctr);
+            return (int)SG_OK;
+        }, [](const SelArgs&, dim3) {});
+    }, out, nullptr, nullptr, index, cap, n_selected, n_rows);
+}
+}  // namespace
+int sg_set_slo(sg_handle e, uint32_t spaces, const sg_slo_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    return slo_set(e, spaces, p);
+}
+int sg_slo_assign(sg_handle e, uint32_t space, const uint32_t* refs, const uint32_t* objectives, size_t n) {
+    if (!e || (n && (!refs || !objectives))) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = slo_space(space);
+    return k < 0 ? bad_slo_space(e, "sg_slo_assign") : slo_assign(e, k, refs, objectives, n);
+}
+int sg_window_node_slo(sg_handle e, const uint32_t* node_index, size_t n_index, uint64_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return slo_read(e, kSNodes, "sg_window_node_slo", node_index, n_index, out, cap, n);
+}
+int sg_window_group_node_slo(sg_handle e, const uint32_t* node_index, size_t n_index, uint64_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return slo_read(e, kSWorkloads, "sg_window_group_node_slo", node_index, n_index, out, cap, n);
+}
+int sg_window_slo_buffer(sg_handle e, uint32_t space, void** d_rows) {
+    if (!e || !d_rows) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = slo_space(space);
+    if (k < 0) return bad_slo_space(e, "sg_window_slo_buffer");
+    int slot;
+    if (const int rc = stage_slot(e, e->slo.sp[k], "sg_window_slo_buffer", kSloWords[k], &slot)) return rc;
+    *d_rows = e->slo.sp[k].rows[slot];
+    return SG_OK;
+}
+int sg_slo_entries(sg_handle e, uint32_t space, uint64_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = slo_space(space);
+    return k < 0 ? bad_slo_space(e, "sg_slo_entries") : slo_entries(e, k, "sg_slo_entries", out, cap, n);
+}
+int sg_slo_stats_get(sg_handle e, uint32_t space, sg_slo_stats* out) {
+    if (!e || !out) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int k = slo_space(space);
+    return k < 0 ? bad_slo_space(e, "sg_slo_stats_get") : slo_stats(e, k, "sg_slo_stats_get", out);
+}
+int sg_window_nodes_top_slo(sg_handle e, uint32_t by, uint32_t k, uint32_t min_value_q10, sg_node_out* out, uint32_t* index, size_t cap, size_t* n_selected,
+                            size_t* n_rows) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return nodes_top_slo(e, kSNodes, "sg_window_nodes_top_slo", by, k, min_value_q10, out, index, cap, n_selected, n_rows);
+}
+int sg_window_group_nodes_top_slo(sg_handle e, uint32_t by, uint32_t k, uint32_t min_value_q10, sg_node_out* out, uint32_t* index, size_t cap,
+                                  size_t* n_selected, size_t* n_rows) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return nodes_top_slo(e, kSWorkloads, "sg_window_group_nodes_top_slo", by, k, min_value_q10, out, index, cap, n_selected, n_rows);
 }
 
 int sg_window_hist(sg_handle e, uint32_t* bins, size_t cap_rows, size_t* n) {

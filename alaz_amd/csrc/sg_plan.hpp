@@ -1542,6 +1542,77 @@ inline int plan_traffic_trend(const sg_traffic_params& p, u32 spaces, u32 on, u6
     return SG_OK;
 }
 
+// K24, the SLO burn rates (sg_slo.h): per requested space (SG_Q_NODES: 0, SG_Q_GROUP_NODES: 1) one device block — the ring
+// [L][keys][2][3] u64, the sums [keys][2][6] u64, the objective words [keys] u32, the counters, a staging of kSloStageRows rows for the
+// index reads and per slot the rows [cap][SG_SLO_WORDS] u64.  keys: the KNOWN and LABEL ids, behind the groups for the workloads;
+// at most 2^21.  sg_set_slo allocates it, never sg_create.  At max_known_nodes 15 000, max_labels 64, max_groups 5 564 and L = 64
+// the two rings are 46.3 + 63.4 MB: L is the caller's choice for that reason.  Sizes are 64-bit.
+constexpr u32 kSloThreads = 256, kSloMaxWgs = 1024, kSloStageRows = 1024, kSloSpaces = 2, kSloCtlWords = 4;
+constexpr u64 kSloMaxKeys = 1ull << 21;
+struct SloSpace {
+    bool on = false;
+    u64 keys = 0, cap = 0;        // the key space; the rows a window slot holds
+    u32 key_wgs = 0, row_wgs = 0; // k24_retire / k24_count; k24_update
+    u64 ring_bytes = 0, sums_bytes = 0, obj_bytes = 0, rows_bytes = 0;
+    u64 ring_off = 0, sums_off = 0, obj_off = 0, ctl_off = 0, stage_off = 0, stage_idx_off = 0, slot_rows = 0;
+    Slots slot;
+    u64 total_bytes = 0;
+    std::vector<Piece> layout;
+};
+struct SloPlan {
+    u32 spaces = 0;               // the SG_Q_* bits that are on
+    u32 lat_budget = 0, err_budget = 0;   // 10^6 - target, in ppm
+    SloSpace sp[kSloSpaces];      // nodes, workloads
+    u64 total_bytes = 0;
+};
+// a budget code of an objective word: exp << 10 | mant -> mant * 10^exp ppm, 0 for a code that is none
+inline u32 slo_budget(u32 code) {
+    const u32 e = code >> 10 & 3u, m = code & 1023u;
+    const u64 b = (u64)m * (e == 0 ? 1u : e == 1 ? 10u : e == 2 ? 100u : 1000u);
+    return code >> 12 || m < 1 || m > 1000 || b > 999999 ? 0u : (u32)b;
+}
+// an objective word sg_slo_assign admits: 0, or a bin of 0 .. 14, bits 27..24 zero and two budget codes
+inline bool slo_objective_ok(u32 w) {
+    return w == 0 || ((w >> 28) <= 14 && !(w >> 24 & 15u) && slo_budget(w >> 12 & 0xFFFu) && slo_budget(w & 0xFFFu));
+}
+// spaces: the SG_Q_* bits asked for; on: the spaces K20 has on; mk, ml: max_known_nodes and max_labels; max_groups, nc: K16's (read
+// only for SG_Q_GROUP_NODES); ncap: the node rows a slot holds.  SG_OK and *out, SG_EINVAL or SG_ESTATE
+inline int plan_slo(const sg_slo_params& p, u32 spaces, u32 on, u64 mk, u64 ml, u64 max_groups, u32 ncap, u32 nc, u32 slots, SloPlan* out) {
+    if (!spaces || (spaces & ~(SG_Q_NODES | SG_Q_GROUP_NODES))) return SG_EINVAL;
+    if (p.struct_size != sizeof(sg_slo_params) || p.reserved != 0 || p.latency_bin > 14) return SG_EINVAL;
+    if (p.latency_target_ppm < 1 || p.latency_target_ppm > 999999 || p.error_target_ppm < 1 || p.error_target_ppm > 999999) return SG_EINVAL;
+    if (p.short_windows < 1 || p.short_windows > p.long_windows || p.long_windows > SG_SLO_MAX_WINDOWS) return SG_EINVAL;
+    const u64 keys[kSloSpaces] = {mk + ml, max_groups + mk + ml}, caps[kSloSpaces] = {std::max<u32>(ncap, 1), std::max<u32>(nc, 1)};
+    const u32 bits[kSloSpaces] = {SG_Q_NODES, SG_Q_GROUP_NODES};
+    for (u32 k = 0; k < kSloSpaces; k++) if ((spaces & bits[k]) && keys[k] > kSloMaxKeys) return SG_EINVAL;
+    if (spaces & ~on) return SG_ESTATE;
+    SloPlan q;
+    q.spaces = spaces;
+    q.lat_budget = 1000000u - p.latency_target_ppm; q.err_budget = 1000000u - p.error_target_ppm;
+    for (u32 k = 0; k < kSloSpaces; k++) {
+        SloSpace& s = q.sp[k];
+        s.on = (spaces & bits[k]) != 0;
+        if (!s.on) continue;
+        Block b;
+        s.keys = std::max<u64>(keys[k], 1); s.cap = caps[k];
+        s.key_wgs = (u32)std::max<u64>(1, std::min<u64>(kSloMaxWgs, (s.keys + kSloThreads - 1) / kSloThreads));
+        s.row_wgs = (u32)std::max<u64>(1, std::min<u64>(kSloMaxWgs, (s.cap + kSloThreads - 1) / kSloThreads));
+        s.ring_bytes = (u64)p.long_windows * s.keys * 6 * 8; s.sums_bytes = s.keys * 12 * 8; s.obj_bytes = s.keys * 4;
+        s.rows_bytes = trend_align(s.cap * SG_SLO_WORDS * 8);
+        s.ring_off = b.take("ring", s.ring_bytes);
+        s.sums_off = b.take("sums", s.sums_bytes);
+        s.obj_off = b.take("objectives", s.obj_bytes);
+        s.ctl_off = b.take("ctl", (u64)kSloCtlWords * 8);
+        s.stage_off = b.take("stage", (u64)kSloStageRows * SG_SLO_WORDS * 8);
+        s.stage_idx_off = b.take("stage_idx", (u64)kSloStageRows * 4);
+        s.slot = b.slots(slots, {{"rows", s.rows_bytes, &s.slot_rows}});
+        s.total_bytes = b.up(b.end); s.layout = std::move(b.pieces);
+        q.total_bytes += s.total_bytes;
+    }
+    *out = q;
+    return SG_OK;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

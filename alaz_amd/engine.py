@@ -97,6 +97,19 @@ T_SPACES = dict(edges=1, nodes=2, groups=4, group_nodes=8)
 TSEL_BY = dict(surge=0, drop=1, load_up=2, load_down=3)
 TSEL_SIDE = {"in": 4, "out": 8}
 TRAFFIC_DEFAULTS = dict(shift=4, warmup=4, ttl=64, max_entries=0, load_floor_ns=1000000, rate_floor=8)
+#: SG_SLO_*: an SLO row (K24) is SLO_WORDS u64 words — SLO_SIDE_FIELDS for the in side (words 0 .. 7), again for the out side
+#: (8 .. 15), flags | objective << 32, then the windows the short | long << 32 span covers; a state entry is SLO_ENTRY_WORDS words
+#: (the key, the twelve sums, the objective word).  SLOSEL_*: the key of a selection by a burn rate, a kind ORed with a side.
+#: SLO_DEFAULTS: 99 % below 2^27 ns (134 ms), 99.9 % without error, over 2 and 12 windows, the 14.4 x burn of a page
+SLO_WORDS = 18
+SLO_ENTRY_WORDS = 14
+SLO_MAX_WINDOWS = 64
+SLO_SIDE_FIELDS = ("total_short", "err_short", "slow_short", "total_long", "err_long", "slow_long", "burn_err", "burn_slow")
+SLO_UNTRACKED, SLO_ERR_BURNING_IN, SLO_SLOW_BURNING_IN, SLO_ERR_BURNING_OUT, SLO_SLOW_BURNING_OUT = 1, 2, 4, 8, 16
+SLOSEL_BY = dict(err=0, slow=1)
+SLOSEL_SIDE = {"in": 2, "out": 4}
+SLO_DEFAULTS = dict(latency_bin=10, latency_target_ppm=990000, error_target_ppm=999000, short_windows=2, long_windows=12, min_burn_q10=14746,
+                    min_requests=100)
 #: SG_IMPACT_*: an impact row of the workload impact (K22) is IMPACT_WORDS u64 words, named by IMPACT_FIELDS in word order; the
 #: parameters' limits; SG_NO_HOPS: a workload row no covered incident reaches within max_hops
 IMPACT_WORDS = 8
@@ -155,6 +168,35 @@ class TrafficParams(C.Structure):
     """sg_traffic_params (K23); tests/test_traffic_host.py holds its layout to the header with the compiler"""
     _fields_ = [("struct_size", C.c_uint32), ("shift", C.c_uint32), ("warmup", C.c_uint32), ("ttl", C.c_uint32),
                 ("max_entries", C.c_uint64), ("load_floor_ns", C.c_uint64), ("rate_floor", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SloParams(C.Structure):
+    """sg_slo_params (K24); tests/test_slo_host.py holds its layout to the header with the compiler"""
+    _fields_ = [("struct_size", C.c_uint32), ("latency_bin", C.c_uint32), ("latency_target_ppm", C.c_uint32), ("error_target_ppm", C.c_uint32),
+                ("short_windows", C.c_uint32), ("long_windows", C.c_uint32), ("min_burn_q10", C.c_uint32), ("reserved", C.c_uint32),
+                ("min_requests", C.c_uint64)]
+
+
+class SloStats(C.Structure):
+    """sg_slo_stats (K24)"""
+    _fields_ = [(n, C.c_uint64) for n in ("windows", "keys_active", "sides_burning", "keys")]
+
+
+def slo_budget_code(budget_ppm: int) -> int:
+    """SG_SLO_BUDGET_CODE of a budget in ppm: exp << 10 | mant with budget = mant * 10^exp, mant 1 .. 1000 — the smallest exp that
+    holds it; ValueError for a budget that has more than three significant digits or lies outside 1 .. 999 999"""
+    for exp in range(4):
+        mant, rest = divmod(budget_ppm, 10 ** exp)
+        if rest == 0 and 1 <= mant <= 1000 and budget_ppm <= 999999:
+            return exp << 10 | mant
+    raise ValueError(f"a budget of {budget_ppm} ppm is no mant * 10^exp with mant 1 .. 1000, exp 0 .. 3")
+
+
+def slo_objective(latency_bin: int, latency_target_ppm: int, error_target_ppm: int) -> int:
+    """SG_SLO_OBJECTIVE: the objective word of sg_slo_assign from a bin (0 .. 14) and two targets in ppm"""
+    if not 0 <= latency_bin <= 14:
+        raise ValueError("latency_bin is 0 .. 14")
+    return latency_bin << 28 | slo_budget_code(1000000 - latency_target_ppm) << 12 | slo_budget_code(1000000 - error_target_ppm)
 
 
 class SgVanishedParams(C.Structure):
@@ -325,6 +367,12 @@ def _signatures() -> dict:
         "sg_window_nodes_top_traffic": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
         "sg_window_groups_top_traffic": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
         "sg_window_group_nodes_top_traffic": (I, [H, u32, u32, f32, P, P, sz, Psz, Psz]),
+        "sg_set_slo": (I, [H, u32, P]), "sg_slo_assign": (I, [H, u32, P, P, sz]),
+        "sg_window_node_slo": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_node_slo": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_slo_buffer": (I, [H, u32, PP]),
+        "sg_slo_entries": (I, [H, u32, P, sz, Psz]), "sg_slo_stats_get": (I, [H, u32, P]),
+        "sg_window_nodes_top_slo": (I, [H, u32, u32, u32, P, P, sz, Psz, Psz]),
+        "sg_window_group_nodes_top_slo": (I, [H, u32, u32, u32, P, P, sz, Psz, Psz]),
     }
 
 
@@ -377,6 +425,7 @@ _STAGES = dict(
                           "tail trend"),
     traffic_trend=_Stage("sg_set_traffic_trend", TrafficParams, TRAFFIC_DEFAULTS, "set_traffic_trend(params=None) switches the traffic baselines off",
                          "traffic trend"),
+    slo=_Stage("sg_set_slo", SloParams, SLO_DEFAULTS, "set_slo(params=None) switches the SLO stage off", "SLO"),
 )
 
 _lib = None
@@ -1322,6 +1371,69 @@ class ServiceGraph:
         window_nodes_top_traffic: "the 20 workloads whose inbound traffic fell furthest" is (20, by="drop", side="in")."""
         b = self._tby(by, side)
         return self._top(lambda *a: self._l.sg_window_group_nodes_top_traffic(self._h, b, k, min_value, *a),
+                         self._node_cap(k, cap, self._l.sg_window_group_nodes), NODE_DTYPE, np.uint32)
+
+    # ---- SLO burn rates (K24): each service's and workload's error budget over a short and a long span of windows ----
+    def set_slo(self, spaces=("group_nodes",), params: Optional[dict] = (), **kw):
+        """Switch the SLO stage on (sg_set_slo): per space ("nodes" / "group_nodes", or the SG_Q_* bits as an int; each needs
+        set_quantiles on for it) exact sums of requests, errors and slow requests per key and side over the last short_windows and
+        long_windows windows, and their burn rates; SLO_DEFAULTS' parameters as keywords or a dict.  Every call starts empty state.
+        spaces None / 0 or params=None switches the stage off."""
+        bits = 0 if spaces is None else spaces if isinstance(spaces, int) else self._qbits(spaces)
+        self._set_stage("slo", params, kw, bits)
+
+    def slo_assign(self, space, refs, objectives) -> None:
+        """objective words (slo_objective(); 0 = the defaults) for the keys of refs — KNOWN, LABEL or, in the workload space, GROUP
+        refs (sg_slo_assign)"""
+        r = np.ascontiguousarray(refs, dtype=np.uint32)
+        o = np.ascontiguousarray(objectives, dtype=np.uint32)
+        if r.shape != o.shape or r.ndim != 1:
+            raise ValueError("refs and objectives are two lists of one length")
+        self._ck(self._l.sg_slo_assign(self._h, self._qbit(space), r.ctypes.data, o.ctypes.data, len(r)))
+
+    def window_node_slo(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, SLO_WORDS) u64 SLO rows of the last read window (sg_window_node_slo), row k for row k of window_nodes(); or the rows
+        at `index` (only those cross PCIe)"""
+        return self._window_rows(self._l.sg_window_node_slo, np.dtype(("<u8", (SLO_WORDS,))), index)
+
+    def window_group_node_slo(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, SLO_WORDS) u64 SLO rows (sg_window_group_node_slo), row k for row k of window_group_nodes(); or those at `index`"""
+        return self._window_rows(self._l.sg_window_group_node_slo, np.dtype(("<u8", (SLO_WORDS,))), index)
+
+    def window_slo_buffer(self, space) -> int:
+        """device pointer of the SLO rows of one space of the window window_run closed last (sg_window_slo_buffer)"""
+        bits = self._qbit(space)
+        return self._pointers(lambda h, *a: self._l.sg_window_slo_buffer(h, bits, *a), 1)[0]
+
+    def slo_entries(self, space) -> np.ndarray:
+        """(n, SLO_ENTRY_WORDS) u64: the state of one space, a key with traffic in the long span a row, ascending (sg_slo_entries)"""
+        bits = self._qbit(space)
+        return self._counted(lambda h, *a: self._l.sg_slo_entries(h, bits, *a), np.dtype("<u8"), (SLO_ENTRY_WORDS,))
+
+    def slo_stats(self, space) -> SloStats:
+        bits = self._qbit(space)
+        return self._stats(lambda h, *a: self._l.sg_slo_stats_get(h, bits, *a), SloStats)
+
+    @staticmethod
+    def _sloby(by, side=None) -> int:
+        """SG_SLOSEL_*: an int as it is; else a kind of SLOSEL_BY with side "in" / "out" (SLOSEL_SIDE) ORed in"""
+        if isinstance(by, int):
+            return by
+        if by not in SLOSEL_BY or side not in SLOSEL_SIDE:
+            raise ValueError(f"unknown SLO key {by!r} / side {side!r}: one of {sorted(SLOSEL_BY)}, {sorted(SLOSEL_SIDE)}")
+        return SLOSEL_BY[by] | SLOSEL_SIDE[side]
+
+    def window_nodes_top_slo(self, k: int, min_value_q10: int = 0, by="err", side="in", cap: Optional[int] = None):
+        """(the selected node rows, their indices, the row count) by a burn rate (sg_window_nodes_top_slo): by "err" / "slow" of side
+        "in" / "out" (or by as the SG_SLOSEL_* int), min(short burn, long burn) descending, k = 0 every row >= min_value_q10."""
+        b = self._sloby(by, side)
+        return self._top(lambda *a: self._l.sg_window_nodes_top_slo(self._h, b, k, min_value_q10, *a), self._node_cap(k, cap), NODE_DTYPE, np.uint32)
+
+    def window_group_nodes_top_slo(self, k: int, min_value_q10: int = 0, by="err", side="in", cap: Optional[int] = None):
+        """(the selected workload rows, their indices, the row count) by a burn rate (sg_window_group_nodes_top_slo): "the 20
+        workloads burning their error budget fastest" is (20, 1024, by="err", side="in")."""
+        b = self._sloby(by, side)
+        return self._top(lambda *a: self._l.sg_window_group_nodes_top_slo(self._h, b, k, min_value_q10, *a),
                          self._node_cap(k, cap, self._l.sg_window_group_nodes), NODE_DTYPE, np.uint32)
 
     @staticmethod

@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .engine import LIB_PATH as ENGINE_LIB, SgConfig
+from .engine import LIB_PATH as ENGINE_LIB, SLO_WORDS, SgConfig
 from .replay import EVENT_DTYPE, L7_WIRE_SIZE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -152,6 +152,9 @@ def load() -> C.CDLL:
             "sgh_graphds_workload_tail_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]), "sgh_mock_k21_ops": (sz, [P, P, sz]),
             "sgh_graphds_set_traffic_trend": (C.c_int, [P, u32, C.c_int, u32, u32, u32, C.c_uint64, u32, C.c_uint64]),
             "sgh_graphds_workload_traffic_top": (C.c_long, [P, u32, u32, C.c_float, P, P, sz]), "sgh_mock_k23_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_slo": (C.c_int, [P, u32, C.c_int, u32, u32, u32, u32, u32, u32, C.c_uint64]),
+            "sgh_graphds_set_workload_slo": (C.c_int, [P, C.c_char_p, u32]), "sgh_graphds_workload_slo": (C.c_long, [P, P, sz]),
+            "sgh_graphds_workload_slo_top": (C.c_long, [P, u32, u32, u32, P, P, sz]), "sgh_mock_k24_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -787,6 +790,45 @@ class GraphDS:
         n = self._l.sgh_mock_k23_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k23_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the SLO burn rates (K24) ----
+    def set_slo(self, spaces: int = 4, on: bool = True, latency_bin: int = 10, latency_target_ppm: int = 990000, error_target_ppm: int = 999000,
+                short_windows: int = 2, long_windows: int = 12, min_burn_q10: int = 14746, min_requests: int = 100) -> int:
+        """GraphDS::SetSLO: exact sums and burn rates per space (SG_Q_NODES | SG_Q_GROUP_NODES bits; 0 or on=False: off; rc)"""
+        return self._l.sgh_graphds_set_slo(self._g, spaces, 1 if on else 0, latency_bin, latency_target_ppm, error_target_ppm, short_windows,
+                                           long_windows, min_burn_q10, min_requests)
+
+    def set_workload_slo(self, workload: str, objective: int) -> int:
+        """GraphDS::SetWorkloadSLO: the objective word (engine.slo_objective(); 0 = the defaults) of the workload with this owner UID (rc)"""
+        return self._l.sgh_graphds_set_workload_slo(self._g, workload.encode(), objective)
+
+    def workload_slo(self) -> np.ndarray:
+        """GraphDS::WorkloadSLO: (n, SLO_WORDS) u64, the SLO row of every row of workload_nodes()"""
+        n = self._l.sgh_graphds_workload_slo(self._g, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadSLO failed: {n}")
+        out = np.zeros((max(n, 1), SLO_WORDS), dtype=np.uint64)
+        self._l.sgh_graphds_workload_slo(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    def workload_slo_top(self, by: int, k: int, min_value_q10: int = 0):
+        """GraphDS::WorkloadSLOTop: (the selected workload rows as workload_nodes() gives them, their indices) — by = SG_SLOSEL_ERR or
+        SG_SLOSEL_SLOW ORed with SG_SLOSEL_IN or SG_SLOSEL_OUT, ranked by min(short burn, long burn)"""
+        n = self._l.sgh_graphds_workload_slo_top(self._g, by, k, min_value_q10, None, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadSLOTop failed: {n}")
+        out, idx = np.zeros(max(n, 1), dtype=_workload_node_dtype()), np.zeros(max(n, 1), dtype=np.uint32)
+        self._l.sgh_graphds_workload_slo_top(self._g, by, k, min_value_q10, out.ctypes.data, idx.ctypes.data, n)
+        return out[:n], idx[:n]
+
+    def mock_k24_ops(self) -> np.ndarray:
+        """the stand-in engine's K24 calls in order, four u64 each: (1, spaces, latency_bin | long_windows << 32 or all ones for NULL,
+        min_requests) per sg_set_slo, (2, space, ref, objective) per ref of sg_slo_assign, (3, cap, 0, 0) per
+        sg_window_group_node_slo, (4, by, k, min_value_q10) per sg_window_group_nodes_top_slo"""
+        n = self._l.sgh_mock_k24_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k24_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     def set_selection(self, k: int, min_score: float = float("-inf")) -> int:

@@ -2152,3 +2152,134 @@ func (g *GraphDS) Run(ctx context.Context, every time.Duration, sink func(window
 		}
 	}
 }
+
+// ---- SLO burn rates (K24) ---------------------------------------------------------------------------------------------
+
+// SLO spaces, selection keys and row flags of include/servicegraph.h ("SLO burn rates").
+const (
+	SLOServices  = uint32(C.SG_Q_NODES)
+	SLOWorkloads = uint32(C.SG_Q_GROUP_NODES)
+	SLOErr       = uint32(C.SG_SLOSEL_ERR)
+	SLOSlow      = uint32(C.SG_SLOSEL_SLOW)
+	SLOIn        = uint32(C.SG_SLOSEL_IN)
+	SLOOut       = uint32(C.SG_SLOSEL_OUT)
+	SLOUntracked = uint64(C.SG_SLO_UNTRACKED)
+	sloWords     = int(C.SG_SLO_WORDS)
+)
+
+// SLOParams is sg_slo_params: a request is slow when its latency bin is above LatencyBin (duration >= 2^(17 + LatencyBin) ns); the
+// targets are in ppm (990000 = 99 %); a kind burns when its burn over the last ShortWindows and over the last LongWindows windows
+// are both >= MinBurnQ10 (1/1024 of "exactly on budget": 14746 = 14.4 x) and the long span holds MinRequests requests.
+type SLOParams struct {
+	LatencyBin, LatencyTargetPpm, ErrorTargetPpm, ShortWindows, LongWindows, MinBurnQ10 uint32
+	MinRequests                                                                           uint64
+}
+
+// SLOSide is one side of an SLO row: the exact sums of requests, errors and slow requests over the short and the long span, and
+// the four burn rates in 1/1024 of "exactly on budget".
+type SLOSide struct {
+	TotalShort, ErrShort, SlowShort, TotalLong, ErrLong, SlowLong uint64
+	BurnErrShort, BurnErrLong, BurnSlowShort, BurnSlowLong        uint32
+}
+
+// SLORow is sg_window_group_node_slo's row of one workload row: the calls it receives (In), the calls it makes (Out), the flags
+// (SLOUntracked, then err / slow burning per side), the objective word it was judged by (0: the defaults) and the windows each
+// span covers.
+type SLORow struct {
+	In, Out                   SLOSide
+	Flags, Objective          uint32
+	ShortCovers, LongCovers   uint32
+}
+
+// SetSLO switches the SLO stage on for the spaces given (SLOServices needs SetLatencyQuantiles over the services, SLOWorkloads over
+// the workloads): per service and workload key the exact sums of the last ShortWindows and LongWindows windows and their burn
+// rates against an absolute objective.  State belongs to the key, so a workload keeps its sums through a rollout.  Every call
+// starts empty state; the ring is LongWindows x keys x 48 bytes.
+func (g *GraphDS) SetSLO(spaces uint32, p SLOParams) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sp C.sg_slo_params
+	sp.struct_size = C.uint32_t(unsafe.Sizeof(sp))
+	sp.latency_bin, sp.latency_target_ppm, sp.error_target_ppm = C.uint32_t(p.LatencyBin), C.uint32_t(p.LatencyTargetPpm), C.uint32_t(p.ErrorTargetPpm)
+	sp.short_windows, sp.long_windows, sp.min_burn_q10 = C.uint32_t(p.ShortWindows), C.uint32_t(p.LongWindows), C.uint32_t(p.MinBurnQ10)
+	sp.min_requests = C.uint64_t(p.MinRequests)
+	if rc := C.sg_set_slo(g.h, C.uint32_t(spaces), &sp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_slo = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+// ClearSLO switches the SLO stage off and frees it.
+func (g *GraphDS) ClearSLO() error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	if rc := C.sg_set_slo(g.h, 0, nil); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_slo = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+// SLOObjective packs an objective word (SG_SLO_OBJECTIVE): a latency bin (0 .. 14) and the two budgets as mant x 10^exp ppm, mant
+// 1 .. 1000, exp 0 .. 3.  99.9 % is a budget of 1000 ppm: (1, 3), (10, 2), (100, 1) or (1000, 0).
+func SLOObjective(latencyBin, latMant, latExp, errMant, errExp uint32) uint32 {
+	return latencyBin<<28 | (latExp<<10|latMant)<<12 | (errExp<<10 | errMant)
+}
+
+// SetWorkloadObjective sets the objective word (SLOObjective; 0: the defaults of SetSLO) of the workload with this group id, the
+// id AssignGroups was told.  It takes effect with the next window; history is not rewritten, the sums are counts.
+func (g *GraphDS) SetWorkloadObjective(group, objective uint32) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	ref := C.uint32_t(uint32(C.SG_REF_GROUP)<<30 | group&0x3FFFFFFF)
+	obj := C.uint32_t(objective)
+	if rc := C.sg_slo_assign(g.h, C.SG_Q_GROUP_NODES, &ref, &obj, 1); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_slo_assign = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func goSLOSide(w []uint64) SLOSide {
+	return SLOSide{w[0], w[1], w[2], w[3], w[4], w[5], uint32(w[6]), uint32(w[6] >> 32), uint32(w[7]), uint32(w[7] >> 32)}
+}
+
+// WindowSLOBurn selects the workloads of the window FlushWindow returned last by a burn rate (sg_window_group_nodes_top_slo): by is
+// SLOErr or SLOSlow ORed with SLOIn or SLOOut, a row's value min(short burn, long burn), 0 below MinRequests; the k largest values
+// >= minValueQ10, descending, with their SLO rows (sg_window_group_node_slo at the selected indices) and their indices into
+// WindowWorkloadNodes.  k = 0: every such row, in order.  WindowSLOBurn(SLOErr|SLOIn, 20, 1024) is "the 20 workloads burning
+// their error budget fastest".  It needs SetSLO over SLOWorkloads.
+func (g *GraphDS) WindowSLOBurn(by, k, minValueQ10 uint32) ([]WorkloadNode, []SLORow, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_group_nodes_top_slo(g.h, C.uint32_t(by), 0, C.uint32_t(minValueQ10), nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_nodes_top_slo = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil, nil
+	}
+	ns, index := make([]C.sg_node_out, room), make([]uint32, room)
+	if rc := C.sg_window_group_nodes_top_slo(g.h, C.uint32_t(by), C.uint32_t(k), C.uint32_t(minValueQ10), &ns[0], (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_nodes_top_slo = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		ns, index = ns[:int(sel)], index[:int(sel)]
+	}
+	if len(index) == 0 {
+		return nil, nil, nil, nil
+	}
+	var n C.size_t
+	words := make([]uint64, len(index)*sloWords)
+	if rc := C.sg_window_group_node_slo(g.h, (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index)), (*C.uint64_t)(unsafe.Pointer(&words[0])), C.size_t(len(index)), &n); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_group_node_slo = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	rows := make([]SLORow, len(index))
+	for i := range rows {
+		w := words[i*sloWords : (i+1)*sloWords]
+		rows[i] = SLORow{goSLOSide(w[0:8]), goSLOSide(w[8:16]), uint32(w[16]), uint32(w[16] >> 32), uint32(w[17]), uint32(w[17] >> 32)}
+	}
+	return goWorkloadNodes(ns), rows, index, nil
+}

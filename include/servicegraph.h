@@ -1249,6 +1249,113 @@ int sg_window_nodes_top_traffic(sg_handle h, uint32_t by, uint32_t k, float min_
 int sg_window_groups_top_traffic(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_group_edge* out, uint32_t* group_index, size_t cap, size_t* n_selected, size_t* n_groups);
 int sg_window_group_nodes_top_traffic(sg_handle h, uint32_t by, uint32_t k, float min_value, sg_node_out* out, uint32_t* node_index, size_t cap, size_t* n_selected, size_t* n_nodes);
 
+/* ---- SLO burn rates (K24): is each service and workload meeting its objective, and how fast does it burn its budget --------------- *
+ * Opt-in (sg_set_slo); without it nothing is launched or allocated, and every other output is byte for byte the same either way.
+ * Every baseline asks whether a window is unusual against the entity's own past.  This stage asks the on-call question: an
+ * ABSOLUTE objective ("99.9 % of requests succeed", "99 % are faster than 134 ms"), the bad fraction over a short and a long span
+ * of windows as EXACT sums, each divided by the error budget: the multi-window, multi-burn-rate alert.  A service that has
+ * always served 2 % errors is calm in every baseline and burning here.
+ * Spaces.  The two node-shaped K20 spaces, named by their SG_Q_* bits: SG_Q_NODES (the node rows of sg_window_nodes) and
+ * SG_Q_GROUP_NODES (the workload rows of sg_window_group_nodes).  A space needs K20 on for it (sg_set_quantiles), SG_ESTATE
+ * otherwise; whatever frees a space's K20 tables frees this stage's state of that space first: any sg_set_quantiles call,
+ * sg_set_nodes(h, 0), any sg_set_groups call, sg_set_group_nodes(h, 0).  Pod edges and group edges have no SLO state.
+ * Key.  A row is TRACKED when its ref is KNOWN or LABEL (node space) or GROUP, KNOWN or LABEL (workload space); its key is
+ *   node space       KNOWN id v -> v, LABEL v -> max_known_nodes + v                      keys = max_known_nodes + max_labels
+ *   workload space   GROUP g -> g, KNOWN v -> max_groups + v, LABEL v -> max_groups + max_known_nodes + v   (K16's group key)
+ * Rows with an OBIP ref are untracked: their id is a rank in the window's outbound-IP list and changes from window to window (the
+ * anchor rule of the workload tracks).  State belongs to the key: sg_group_assign migrates nothing — a pod that joins a workload
+ * starts to count under the workload's key, and what it counted under its own stays there until it leaves the spans.
+ * Sample.  Per side of a tracked row the window's sample is (total, err, slow): total and err the side's request and error counts
+ * of the row (in_count / in_err, out_count / out_err), slow the sum of bins latency_bin + 1 .. 15 of the side's K20 histogram —
+ * the requests with duration_ns >= 2^(17 + latency_bin), the lower edge of bin latency_bin + 1.  A key without a row in a window
+ * samples zeros on both sides; its old windows still leave the spans on time.
+ * Sums.  Per key and side T_S, E_S, W_S — total, err, slow summed over the last S windows — and T_L, E_L, W_L over the last L, all
+ * exact uint64_t sums; the closing window is in both spans, and before S (L) windows have closed since sg_set_slo a span covers
+ * what exists.  Windows are assumed to be of equal length.
+ * Burn rates.  Four per side (err or slow, short or long span), from bad = min(E or W, T) and total = T of the span:
+ *   r        = floor(bad * 2^20 / total), 0 when total == 0          (<= 2^20)
+ *   burn_q10 = floor(r * 10^6 / (budget_ppm * 1024))                 (<= 1 024 000 000: a uint32_t)
+ * in 1/1024 of "exactly on budget": 1024 burns the budget exactly as fast as the objective allows, 14 746 is the 14.4 x of a
+ * page.  budget_ppm = 10^6 - target_ppm.  A kind on a side is BURNING when its short burn and its long burn are both >=
+ * min_burn_q10 and T_L >= min_requests.
+ * Objectives.  sg_slo_params holds the defaults; sg_slo_assign sets an objective WORD per key:
+ *   bits 31..28 latency_bin (0 .. 14) | bits 23..12 latency budget code | bits 11..0 error budget code, bits 27..24 zero
+ *   a budget code is exp << 10 | mant: budget_ppm = mant * 10^exp with mant 1 .. 1000, exp 0 .. 3, budget_ppm <= 999 999 — three
+ *   significant digits of budget from 1 ppm up (two targets of 20 bits each do not fit a word beside the bin)
+ * (SG_SLO_OBJECTIVE builds one).  The word 0 means "the defaults of sg_slo_params"; a valid word is never 0.  A row reports the
+ * word it was judged by.  Changing an objective does not rewrite history: the sums are counts, and the slow count of a past
+ * window was taken under the latency_bin in force then.
+ * Row (SG_SLO_WORDS uint64_t words an entity, row k for row k of the space's node rows):
+ *   words 0 .. 7 the in side, 8 .. 15 the out side (sg_node_trend's order); within a side
+ *     0 .. 5  T_S, E_S, W_S, T_L, E_L, W_L
+ *     6       burn_err_short | (uint64_t) burn_err_long << 32
+ *     7       burn_slow_short | (uint64_t) burn_slow_long << 32
+ *   word 16   flags | (uint64_t) objective word << 32
+ *   word 17   windows the short span covers | (uint64_t) windows the long span covers << 32
+ * An untracked row is all zero except SG_SLO_UNTRACKED.
+ * Every close path computes it, behind K20 of the same space and window on the window's stream; with several windows in flight
+ * the state updates run in window order.  An engine with world > 1 has no K20 and so no SLO stage.                                */
+#define SG_SLO_WORDS            18u
+#define SG_SLO_MAX_WINDOWS      64u
+#define SG_SLO_UNTRACKED        1u    /* flags of word 16 */
+#define SG_SLO_ERR_BURNING_IN   2u
+#define SG_SLO_SLOW_BURNING_IN  4u
+#define SG_SLO_ERR_BURNING_OUT  8u
+#define SG_SLO_SLOW_BURNING_OUT 16u
+#define SG_SLO_BUDGET_CODE(mant, exp)  (((uint32_t)(exp) << 10) | (uint32_t)(mant))
+#define SG_SLO_OBJECTIVE(latency_bin, lat_mant, lat_exp, err_mant, err_exp) \
+    (((uint32_t)(latency_bin) << 28) | (SG_SLO_BUDGET_CODE(lat_mant, lat_exp) << 12) | SG_SLO_BUDGET_CODE(err_mant, err_exp))
+typedef struct sg_slo_params {
+    uint32_t struct_size;        /* sizeof(sg_slo_params)                                                                    */
+    uint32_t latency_bin;        /* 0 .. 14: a request is slow when its latency bin is above this value                      */
+    uint32_t latency_target_ppm; /* 1 .. 999 999: the default latency objective; its budget is 10^6 - target                 */
+    uint32_t error_target_ppm;   /* 1 .. 999 999: the default error objective                                                */
+    uint32_t short_windows;      /* S, 1 <= S <= L                                                                           */
+    uint32_t long_windows;       /* L, S <= L <= SG_SLO_MAX_WINDOWS: the ring is L x keys x 48 bytes, the caller's choice    */
+    uint32_t min_burn_q10;       /* the burn threshold, in 1/1024 of "exactly on budget"                                     */
+    uint32_t reserved;           /* 0                                                                                        */
+    uint64_t min_requests;       /* a side burns, and is selected, only with T_L >= min_requests                             */
+} sg_slo_params;                 /* 40 bytes, no padding */
+typedef struct sg_slo_stats {
+    uint64_t windows;            /* windows closed since sg_set_slo                                                          */
+    uint64_t keys_active;        /* tracked keys with a non-zero T_L on either side                                          */
+    uint64_t sides_burning;      /* sides of the last window's rows with a burning kind                                      */
+    uint64_t keys;               /* the key space of the stage's state                                                       */
+} sg_slo_stats;
+/* spaces == 0 or p == NULL switches the stage off and frees it; every call replaces the previous setting and starts empty state
+ * (sums, ring, objectives).  spaces: SG_Q_NODES | SG_Q_GROUP_NODES.  SG_EINVAL for other bits, bad parameters or more than 2^21
+ * keys; SG_ESTATE for a space K20 has not on, or while a flush is open: such a call leaves the stage as it was.  Memory is
+ * allocated here, never at sg_create; a failed allocation (SG_ENOMEM) leaves the stage off.                                      */
+int sg_set_slo(sg_handle h, uint32_t spaces, const sg_slo_params* p);
+/* Objective words per key of one space (exactly one SG_Q_* bit): refs[i] is a KNOWN or LABEL ref (and a GROUP ref in the workload
+ * space) below the engine's id spaces, objectives[i] a valid word or 0; anything else is SG_EINVAL before any word is set.  It
+ * waits for the updates enqueued so far and takes effect with the next window closed.                                            */
+int sg_slo_assign(sg_handle h, uint32_t space, const uint32_t* refs, const uint32_t* objectives, size_t n);
+/* The SLO rows of the last READ window, with the shape of sg_window_group_node_hops: index NULL: every row of the space, *n = their
+ * count; else out[k] = the row of entity index[k] (each < the count, else SG_EINVAL), *n = n_index.  cap counts rows of
+ * SG_SLO_WORDS words; min(*n, cap) rows are written.                                                                             */
+int sg_window_node_slo(sg_handle h, const uint32_t* node_index, size_t n_index, uint64_t* out, size_t cap, size_t* n);
+int sg_window_group_node_slo(sg_handle h, const uint32_t* node_index, size_t n_index, uint64_t* out, size_t cap, size_t* n);
+/* The device rows (uint64_t[rows][SG_SLO_WORDS]) of one space of the window sg_window_run closed last.                            */
+int sg_window_slo_buffer(sg_handle h, uint32_t space, void** d_rows);
+/* The state of one space: for each key with a non-zero T_L on either side one entry of SG_SLO_ENTRY_WORDS words — the key, the
+ * twelve sums in row order (in: T_S .. W_L, out: T_S .. W_L), the objective word — ascending by key.  *n = their count,
+ * min(*n, cap) entries are written.  It waits for the updates enqueued so far, as sg_slo_stats_get does.                          */
+#define SG_SLO_ENTRY_WORDS 14u
+int sg_slo_entries(sg_handle h, uint32_t space, uint64_t* out, size_t cap, size_t* n);
+int sg_slo_stats_get(sg_handle h, uint32_t space, sg_slo_stats* out);
+/* Selections over the SLO rows of the last READ window: `by` is SG_SLOSEL_ERR or SG_SLOSEL_SLOW ORed with exactly one of
+ * SG_SLOSEL_IN / SG_SLOSEL_OUT, else SG_EINVAL.  A row's value is min(short burn, long burn) of that kind and side, 0 when the row
+ * is untracked or T_L < min_requests; the k largest values >= min_value_q10 are selected (k = 0: every such row), ties by row
+ * position, rows and indices as sg_window_nodes_top gives them.  "The 20 workloads burning their error budget fastest" is
+ * sg_window_group_nodes_top_slo(h, SG_SLOSEL_ERR | SG_SLOSEL_IN, 20, 1024, ...).                                                   */
+#define SG_SLOSEL_ERR   0u
+#define SG_SLOSEL_SLOW  1u
+#define SG_SLOSEL_IN    2u      /* the in side: the calls the entity receives */
+#define SG_SLOSEL_OUT   4u      /* the out side: the calls it makes */
+int sg_window_nodes_top_slo(sg_handle h, uint32_t by, uint32_t k, uint32_t min_value_q10, sg_node_out* out, uint32_t* index, size_t cap, size_t* n_selected, size_t* n_rows);
+int sg_window_group_nodes_top_slo(sg_handle h, uint32_t by, uint32_t k, uint32_t min_value_q10, sg_node_out* out, uint32_t* index, size_t cap, size_t* n_selected, size_t* n_rows);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
