@@ -57,6 +57,9 @@ bool SgApi::FromLibrary(void* dl, SgApi* o) {
     o->slo_assign = reinterpret_cast<decltype(o->slo_assign)>(dlsym(dl, "sg_slo_assign"));
     o->window_group_node_slo = reinterpret_cast<decltype(o->window_group_node_slo)>(dlsym(dl, "sg_window_group_node_slo"));
     o->window_group_nodes_top_slo = reinterpret_cast<decltype(o->window_group_nodes_top_slo)>(dlsym(dl, "sg_window_group_nodes_top_slo"));
+    o->set_replicas = reinterpret_cast<decltype(o->set_replicas)>(dlsym(dl, "sg_set_replicas"));   // optional (K25)
+    o->window_replicas = reinterpret_cast<decltype(o->window_replicas)>(dlsym(dl, "sg_window_replicas"));
+    o->window_replicas_top = reinterpret_cast<decltype(o->window_replicas_top)>(dlsym(dl, "sg_window_replicas_top"));
 #undef SG_SYM
     return true;
 }
@@ -507,6 +510,49 @@ int GraphDS::SetTrafficTrend(uint32_t spaces, const sg_traffic_params* p) {
 }
 long GraphDS::WorkloadTrafficTop(uint32_t by, uint32_t k, float min_value, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index) {
     return WorkloadNodesTopBy(api_.window_group_nodes_top_traffic, by, k, min_value, out, index);
+}
+// ---- the replica outliers (K25) ----
+int GraphDS::SetReplicaOutliers(const sg_replica_params* p) {
+    if (!api_.set_replicas) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    return api_.set_replicas(h_, p);
+}
+long GraphDS::WorkloadReplicaOutliers(uint32_t by, uint32_t k, uint32_t min_value, std::vector<ReplicaOutlier>* out) {
+    if (!out || !api_.window_replicas_top || !api_.window_replicas || !api_.window_group_nodes) return SG_EINVAL;
+    std::lock_guard<std::mutex> fg(flush_mu_);
+    size_t sel = 0, total = 0;
+    std::vector<sg_node_out> rows;
+    std::vector<uint32_t> idx;
+    if (k) { rows.resize(k); idx.resize(k); }                        // at most k are selected; k = 0: the count first
+    int rc = api_.window_replicas_top(h_, by, k, min_value, rows.data(), idx.data(), rows.size(), &sel, &total);
+    if (rc != SG_OK) return rc;
+    if (!k && sel) {
+        rows.resize(sel); idx.resize(sel);
+        if ((rc = api_.window_replicas_top(h_, by, 0, min_value, rows.data(), idx.data(), rows.size(), &sel, &total)) != SG_OK) return rc;
+    }
+    const size_t m = std::min(sel, rows.size());
+    rows.resize(m); idx.resize(m);
+    out->assign(m, ReplicaOutlier{});
+    if (!m) return 0;
+    std::vector<uint32_t> pods(m * SG_REPLICA_WORDS);
+    size_t n = 0;
+    if ((rc = api_.window_replicas(h_, idx.data(), m, pods.data(), m, &n)) != SG_OK) return rc;
+    if ((rc = api_.window_group_nodes(h_, nullptr, 0, &n)) != SG_OK) return rc;
+    std::vector<sg_node_out> wl(n);
+    if (n && (rc = api_.window_group_nodes(h_, wl.data(), n, &n)) != SG_OK) return rc;
+    const uint32_t* side0 = pods.data() + 2 + ((by & SG_RSEL_OUT) ? 5 : 0);
+    std::lock_guard<std::mutex> g(id_mu_);
+    for (size_t i = 0; i < m; i++) {
+        ReplicaOutlier& o = (*out)[i];
+        const uint32_t* r = pods.data() + i * SG_REPLICA_WORDS;
+        const uint32_t* s = side0 + i * SG_REPLICA_WORDS;
+        std::string type;
+        NameRef(rows[i].ref, &type, &o.PodUID);
+        o.NodeIndex = idx[i]; o.WorkloadIndex = r[0]; o.Flags = r[1];
+        if (r[0] < wl.size()) NameRef(wl[r[0]].ref, &type, &o.Workload);
+        o.ErrExcessQ20 = (int32_t)s[0]; o.LatRatioQ10 = s[1]; o.ShareQ10 = s[2]; o.TailPod = s[3] & 255u; o.TailPeers = s[3] >> 8 & 255u; o.Replicas = s[4];
+    }
+    return (long)m;
 }
 // ---- the SLO burn rates (K24) ----
 int GraphDS::SetSLO(uint32_t spaces, const sg_slo_params* p) {

@@ -95,6 +95,10 @@ struct SgApi {
     int (*slo_assign)(sg_handle, uint32_t, const uint32_t*, const uint32_t*, size_t) = nullptr;
     int (*window_group_node_slo)(sg_handle, const uint32_t*, size_t, uint64_t*, size_t, size_t*) = nullptr;
     int (*window_group_nodes_top_slo)(sg_handle, uint32_t, uint32_t, uint32_t, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
+    // optional (K25; absent in an older library): SetReplicaOutliers and WorkloadReplicaOutliers each need the entries they forward to
+    int (*set_replicas)(sg_handle, const sg_replica_params*) = nullptr;
+    int (*window_replicas)(sg_handle, const uint32_t*, size_t, uint32_t*, size_t, size_t*) = nullptr;
+    int (*window_replicas_top)(sg_handle, uint32_t, uint32_t, uint32_t, sg_node_out*, uint32_t*, size_t, size_t*, size_t*) = nullptr;
     static bool FromLibrary(void* dl_handle, SgApi* out);      // dlsym of every entry; false if one is missing
 };
 
@@ -121,6 +125,13 @@ struct VanishedWorkload {              // one vanished workload dependency of a 
     uint32_t N = 0, Last = 0, Row = 0;                 // Row: the window's group edge with the key and no request, else 0xFFFFFFFF
 };
 
+struct ReplicaOutlier {                // one selected replica of a closed window (K25): who it is, whose replica, and one side of its pod row
+    std::string PodUID, Workload;      // the pod's UID; the owner UID of its workload
+    uint32_t NodeIndex = 0, WorkloadIndex = 0;   // into ServiceNodes' / WorkloadNodes' rows of the window
+    uint32_t Flags = 0;                // word 1 of the pod row: SG_REPL_* of both sides
+    int32_t ErrExcessQ20 = 0;          // the side `by` names: error rate above the peers', 2^20 = 100 points
+    uint32_t LatRatioQ10 = 0, ShareQ10 = 0, TailPod = 0, TailPeers = 0, Replicas = 0;   // mean over the peers' mean, share of the fair share (1024 = 1); K20 bins; R
+};
 struct WorkloadNode {                  // one workload row of a closed window (K16): who it is, and the engine's row as it is
     std::string Type, UID;                             // "workload" (UID = the owner's UID), or pod / service / outbound as the rows' are
     sg_node_out Row{};
@@ -293,6 +304,13 @@ public:
     int SetWorkloadSLO(const std::string& workload, uint32_t objective);
     long WorkloadSLO(std::vector<uint64_t>* out);
     long WorkloadSLOTop(uint32_t by, uint32_t k, uint32_t min_value_q10, std::vector<WorkloadNode>* out, std::vector<uint32_t>* index);
+    // The replica outliers (K25; needs the node rollup, SetWorkloadGroups and the workload rows, and SetLatencyQuantiles over the
+    // services for tails): each pod against the other pods of its workload.  SetReplicaOutliers forwards sg_set_replicas (p NULL = off;
+    // the engine's return code; SG_EINVAL without the entry).  WorkloadReplicaOutliers: the selection sg_window_replicas_top over the
+    // last flushed window (`by` = SG_RSEL_ERR / _LAT / _TAIL / _SHARE ORed with SG_RSEL_IN or SG_RSEL_OUT), each selected pod named by
+    // its UID and its workload's owner UID, with that side's words of its pod row.  The count, or a negative SG_* code.
+    int SetReplicaOutliers(const sg_replica_params* p);
+    long WorkloadReplicaOutliers(uint32_t by, uint32_t k, uint32_t min_value, std::vector<ReplicaOutlier>* out);
 
     uint64_t EventsOffered() const { return offered_.load(); }
     uint64_t BatchesDropped() const { return batches_dropped_.load(); }

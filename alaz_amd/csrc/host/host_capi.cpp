@@ -32,6 +32,7 @@ struct MockEngine {
     std::vector<std::array<uint64_t, 4>> k17_ops;      // {1, iters, damping_q8, seed} per sg_set_group_rank (NULL: ~0 in the three), {2, k, the bits of min_share, cap} per sg_window_group_rank_top
     std::vector<std::array<uint64_t, 4>> k21_ops;      // {1, spaces, permille, shift (NULL: ~0)} per sg_set_quantile_trend, {2 / 3 / 4, cap, 0, 0} per sg_window_node_quantile_trend / sg_window_group_quantile_trend / sg_window_group_node_quantile_trend, {5, by, k, the bits of min_value} per sg_window_group_nodes_top_tail
     std::vector<std::array<uint64_t, 4>> k23_ops;      // {1, spaces, shift (NULL: ~0), rate_floor | load_floor_ns << 32} per sg_set_traffic_trend, {2, by, k, the bits of min_value} per sg_window_group_nodes_top_traffic
+    std::vector<std::array<uint64_t, 4>> k25_ops;      // {1, min_replicas | tail_permille << 32 (NULL: ~0), min_requests, min_err_excess_q20 | min_lat_ratio_q10 << 32} per sg_set_replicas, {2, n_index, cap, 0} per sg_window_replicas, {3, by, k, min_value} per sg_window_replicas_top
     std::vector<std::array<uint64_t, 4>> k24_ops;      // {1, spaces, latency_bin | long_windows << 32 (NULL: ~0), min_requests} per sg_set_slo, {2, space, ref, objective} per ref of sg_slo_assign, {3, cap, 0, 0} per sg_window_group_node_slo, {4, by, k, min_value_q10} per sg_window_group_nodes_top_slo
     std::vector<std::array<uint64_t, 4>> k20_ops;      // {1, spaces, n_q, the first four per-mille 16 bits each} per sg_set_quantiles, {2 / 3 / 4, n_index (~0: no index), cap, 0} per sg_window_node_quantiles / sg_window_group_quantiles / sg_window_group_node_quantiles
     size_t k20_nq = 2;
@@ -308,6 +309,36 @@ int m_window_group_nodes_top_slo(sg_handle h, uint32_t by, uint32_t k, uint32_t 
     for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
     return SG_OK;
 }
+// K25's stand-ins: the switch recorded; the pod row of node row j is a member of workload row 1 (word 0), its words 1 .. 11 are
+// 100 j + w; the selection gives node rows 2 and 0 of three: KNOWN 1, then KNOWN 0
+int m_set_replicas(sg_handle h, const sg_replica_params* p) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k25_ops.push_back({1u, p ? (uint64_t)p->min_replicas | (uint64_t)p->tail_permille << 32 : ~0ull, p ? p->min_requests : 0u,
+                                                         p ? (uint64_t)p->min_err_excess_q20 | (uint64_t)p->min_lat_ratio_q10 << 32 : 0u});
+    return p && p->min_replicas == 1 ? SG_EINVAL : SG_OK;
+}
+int m_window_replicas(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k25_ops.push_back({2u, idx ? (uint64_t)n_idx : ~0ull, (uint64_t)cap, 0u});
+    const size_t N = idx ? n_idx : 3;
+    if (n) *n = N;
+    for (size_t i = 0; out && i < std::min(N, cap); i++) {
+        const uint32_t j = idx ? idx[i] : (uint32_t)i;
+        out[i * SG_REPLICA_WORDS] = 1u;
+        for (uint32_t w = 1; w < SG_REPLICA_WORDS; w++) out[i * SG_REPLICA_WORDS + w] = 100 * j + w;
+    }
+    return SG_OK;
+}
+int m_window_replicas_top(sg_handle h, uint32_t by, uint32_t k, uint32_t min_value, sg_node_out* out, uint32_t* idx, size_t cap, size_t* n_sel, size_t* n) {
+    M_LOCK(h);
+    reinterpret_cast<MockEngine*>(h)->k25_ops.push_back({3u, by, k, min_value});
+    if (n_sel) *n_sel = 2;
+    if (n) *n = 3;
+    const sg_node_out e[2] = {m_node(SG_MAKE_REF(SG_REF_KNOWN, 1), 0, 7, 0, 1, 0.5f), m_node(SG_MAKE_REF(SG_REF_KNOWN, 0), 0, 4, 0, 1, 0.25f)};
+    const uint32_t at[2] = {2u, 0u};
+    for (size_t i = 0; i < std::min<size_t>(2, cap); i++) { if (out) out[i] = e[i]; if (idx) idx[i] = at[i]; }
+    return SG_OK;
+}
 int m_window_group_node_incident(sg_handle h, const uint32_t* idx, size_t n_idx, uint32_t* out, size_t cap, size_t* n) {
     M_LOCK(h);
     reinterpret_cast<MockEngine*>(h)->k18_ops.push_back({3u, (uint64_t)n_idx, (uint64_t)cap, 0u});
@@ -414,6 +445,7 @@ void* sgh_graphds_create2(const char* engine_lib, const sg_config* cfg, size_t b
         c->api.window_group_quantile_trend = m_window_group_quantile_trend; c->api.window_group_node_quantile_trend = m_window_group_node_quantile_trend;
         c->api.window_group_nodes_top_tail = m_window_group_nodes_top_tail;
         c->api.set_traffic_trend = m_set_traffic_trend; c->api.window_group_nodes_top_traffic = m_window_group_nodes_top_traffic;
+        c->api.set_replicas = m_set_replicas; c->api.window_replicas = m_window_replicas; c->api.window_replicas_top = m_window_replicas_top;
         c->api.set_slo = m_set_slo; c->api.slo_assign = m_slo_assign; c->api.window_group_node_slo = m_window_group_node_slo;
         c->api.window_group_nodes_top_slo = m_window_group_nodes_top_slo;
         c->api.set_group_incidents = m_set_group_incidents; c->api.window_group_incidents = m_window_group_incidents;
@@ -692,6 +724,30 @@ long sgh_graphds_workload_slo_top(void* g, uint32_t by, uint32_t k, uint32_t min
     const long n = static_cast<HostCtx*>(g)->ds->WorkloadSLOTop(by, k, min_value_q10, &v, &idx);
     if (n < 0) return n;
     for (size_t i = 0; i < std::min(cap, v.size()); i++) { if (out) put_workload_node(v[i], out + i); if (index) index[i] = idx[i]; }
+    return n;
+}
+// the replica outliers (K25): the switch (on = 0: off; a 0 among the parameters is the engine's default) and the selection — per
+// selected pod its UID, its workload's owner UID, the two row indices, the flags and the words of the side `by` names
+struct sgh_replica_outlier { char pod[160]; char workload[160]; uint32_t node_index, workload_index, flags; int32_t err_excess_q20;
+                             uint32_t lat_ratio_q10, share_q10, tail_pod, tail_peers, replicas; };
+static_assert(sizeof(sgh_replica_outlier) == 320 + 36, "sgh_replica_outlier: the names, then nine words");
+int sgh_graphds_set_replica_outliers(void* g, int on, uint32_t min_replicas, uint64_t min_requests, uint32_t min_err_excess_q20, uint32_t min_lat_ratio_q10,
+                                     uint32_t tail_permille, uint32_t min_tail_bins) {
+    sg_replica_params p{}; p.struct_size = sizeof p; p.min_replicas = min_replicas; p.min_requests = min_requests; p.min_err_excess_q20 = min_err_excess_q20;
+    p.min_lat_ratio_q10 = min_lat_ratio_q10; p.tail_permille = tail_permille; p.min_tail_bins = min_tail_bins;
+    return static_cast<HostCtx*>(g)->ds->SetReplicaOutliers(on ? &p : nullptr);
+}
+long sgh_graphds_workload_replica_outliers(void* g, uint32_t by, uint32_t k, uint32_t min_value, sgh_replica_outlier* out, size_t cap) {
+    std::vector<ReplicaOutlier> v;
+    const long n = static_cast<HostCtx*>(g)->ds->WorkloadReplicaOutliers(by, k, min_value, &v);
+    if (n < 0) return n;
+    for (size_t i = 0; out && i < std::min(cap, v.size()); i++) {
+        sgh_replica_outlier* o = out + i;
+        std::memset(o, 0, sizeof *o);
+        std::strncpy(o->pod, v[i].PodUID.c_str(), sizeof o->pod - 1); std::strncpy(o->workload, v[i].Workload.c_str(), sizeof o->workload - 1);
+        o->node_index = v[i].NodeIndex; o->workload_index = v[i].WorkloadIndex; o->flags = v[i].Flags; o->err_excess_q20 = v[i].ErrExcessQ20;
+        o->lat_ratio_q10 = v[i].LatRatioQ10; o->share_q10 = v[i].ShareQ10; o->tail_pod = v[i].TailPod; o->tail_peers = v[i].TailPeers; o->replicas = v[i].Replicas;
+    }
     return n;
 }
 int sgh_graphds_ingest_wire(void* g, const uint8_t* recs, size_t n, const uint32_t* kafka_msgs) {
@@ -1020,6 +1076,14 @@ size_t sgh_mock_k23_ops(void* g, uint64_t* out4, size_t cap) {
     std::lock_guard<std::mutex> lk(m->mu);
     for (size_t i = 0; i < std::min(cap, m->k23_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k23_ops[i].data(), 32);
     return m->k23_ops.size();
+}
+size_t sgh_mock_k25_ops(void* g, uint64_t* out4, size_t cap) {
+    auto* c = static_cast<HostCtx*>(g);
+    if (!c->mock) return 0;
+    auto* m = reinterpret_cast<MockEngine*>(c->h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t i = 0; i < std::min(cap, m->k25_ops.size()); i++) std::memcpy(out4 + 4 * i, m->k25_ops[i].data(), 32);
+    return m->k25_ops.size();
 }
 size_t sgh_mock_k24_ops(void* g, uint64_t* out4, size_t cap) {
     auto* c = static_cast<HostCtx*>(g);

@@ -41,6 +41,7 @@
 #include "sg_quantiles.h"
 #include "sg_quantile_trend.h"
 #include "sg_slo.h"
+#include "sg_replicas.h"
 #include "shard_seq.hpp"
 
 namespace {
@@ -292,6 +293,14 @@ struct sg_engine {
                       u64* stage = nullptr; u32* stage_idx = nullptr; std::vector<u64*> rows; std::vector<char> valid; u64 w = 0;
                       std::vector<u32> h_obj; hipEvent_t ev = nullptr; bool pending = false; };
     struct Slo { sg_slo_params p{}; sgplan::SloPlan plan; SloSpace sp[2]; } slo;
+    // K25, the replica outliers (sg_replicas.h): one block (sg_plan.hpp plan_replicas), allocated at sg_set_replicas, freed in front
+    // of whichever of its inputs goes first (the node rows, the groups, the workload rows; K20's node space when tails are on).  The
+    // position table, the targets, the partials and the sums are scratch shared by the window slots: every run waits for the previous
+    // one (ev), whichever slot's stream it runs on — and so does the next upload of the group map, which the run reads.  Per slot: the
+    // pod rows, the workload rows, and whether the window in the slot made them.  Nothing is kept across windows.
+    struct Replicas { bool on = false; sgplan::ReplicaPlan plan; char* mem = nullptr; u32* pos = nullptr; u32* tgt = nullptr; u64* part = nullptr;
+                      u64* vpart = nullptr; u64* wsum = nullptr; u32* stage = nullptr; u32* stage_idx = nullptr; std::vector<u32*> pods, groups;
+                      std::vector<char> valid; hipEvent_t ev = nullptr; bool pending = false; } rep;
 };
 
 namespace {
@@ -1153,6 +1162,7 @@ int launch_groups(sg_engine* e, hipStream_t s) {
     if (const int rc = stage_wait(e, x, s)) return rc;
     if (x.dirty_hi > x.dirty_lo) {                                    // the windows closed before read the map as it was: the upload is behind them
         if (x.up_pending) HIP_TRY(e, hipEventSynchronize(x.up_ev));
+        if (e->rep.on) { if (const int rc = stage_wait(e, e->rep, s)) return rc; }   // (K25 of the windows before reads the map behind K16, not behind K14)
         const size_t n = x.dirty_hi - x.dirty_lo;
         std::memcpy(x.h_up + x.dirty_lo, x.h_map.data() + x.dirty_lo, n * sizeof(u32));
         HIP_TRY(e, hipMemcpyAsync(x.map + x.dirty_lo, x.h_up + x.dirty_lo, n * sizeof(u32), hipMemcpyHostToDevice, s));
@@ -1462,11 +1472,47 @@ void free_slo(sg_engine* e, int k) {
     e->slo.plan.sp[k] = sgplan::SloSpace{};
     e->slo.plan.spaces &= ~(k == kSNodes ? SG_Q_NODES : SG_Q_GROUP_NODES);
 }
+// ---- K25, the replica outliers (engine lock held) -------------------------------------------------------------------------------------
+static_assert(sgplan::kReplThreads == K25_THREADS && sgplan::kReplMaxWgs == K25_MAX_WGS && sgplan::kReplSideWords == K25_SIDE_WORDS &&
+              sgplan::kReplVerdictWords == K25_VERDICT_WORDS && sgplan::kQThreads == K20_THREADS, "plan_replicas sizes the launches of sg_replicas.h");
+constexpr StageWords kReplicaWords{"the replica outliers are off (sg_set_replicas)", "the replica outliers were off"};
+// enqueue the replica outliers of the window in slot cur on stream s (behind K16 and, with tails, K20's node space, on the same
+// stream) and behind the previous run (any stream): the positions, the members, the sums' fold and table, the pod rows, the
+// verdicts' fold, the workload rows
+int launch_replicas(sg_engine* e, hipStream_t s) {
+    sg_engine::Replicas& x = e->rep;
+    const sgplan::ReplicaPlan& P = x.plan;
+    ReplicaArgs a{};
+    a.g = group_nodes_view(e);
+    a.map = e->grp.map; a.kind = work(e).d.kind;
+    a.nodes = e->nodes.rows[e->cur]; a.ncount = e->nodes.count[e->cur]; a.ncap = (u32)P.ncap;
+    a.wrows = e->gnodes.rows[e->cur]; a.wcount = e->gnodes.count[e->cur]; a.nc = (u32)P.nc;
+    a.tails = P.tails; a.hist = P.tails ? e->qnt.sp[kQNodes].hist[e->cur] : nullptr;
+    a.words = P.words; a.range_rows = P.range_rows; a.slices = P.slices;
+    a.min_replicas = P.p.min_replicas; a.min_err = P.p.min_err_excess_q20; a.min_lat = P.p.min_lat_ratio_q10; a.permille = P.p.tail_permille;
+    a.min_tail = P.p.min_tail_bins; a.min_requests = P.p.min_requests;
+    a.pos = x.pos; a.tgt = x.tgt; a.part = x.part; a.vpart = x.vpart; a.wsum = x.wsum;
+    a.pods = x.pods[e->cur]; a.groups = x.groups[e->cur];
+    if (const int rc = stage_wait(e, x, s)) return rc;
+    const dim3 nt(K25_THREADS), fold(P.ranges * P.slices);
+    hipLaunchKernelGGL(k20_pos_groups, dim3(P.pos_wgs), dim3(K20_THREADS), 0, s, a.g, a.wrows, a.wcount, x.pos);
+    hipLaunchKernelGGL(k25_member<0>, dim3(P.node_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k25_fold<K25Sums>, fold, nt, (size_t)P.lds_bytes, s, a);
+    hipLaunchKernelGGL(k25_reduce<0>, dim3(P.sum_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k25_rows<0>, dim3(P.node_wgs), nt, 0, s, a);
+    hipLaunchKernelGGL(k25_fold<K25Verdict>, fold, nt, (size_t)P.vlds_bytes, s, a);
+    hipLaunchKernelGGL(k25_groups<0>, dim3(P.group_wgs), nt, 0, s, a);
+    if (const int rc = stage_done(e, x, s)) return rc;
+    x.valid[e->cur] = 1;
+    return SG_OK;
+}
+void free_replicas(sg_engine* e) { free_stage(e->rep); }
 void free_quantile_trend(sg_engine* e, int k) {
     if (k == kQGroups) free_baseline(e->qtr.groups);
     else free_baseline(k == kQNodes ? e->qtr.nodes : e->qtr.workloads);
 }
 void free_quantiles(sg_engine* e, int k) {
+    if (k == kQNodes && e->rep.on && e->rep.plan.tails) free_replicas(e);   // (K25's tails read the node histograms)
     if (k != kQGroups) free_slo(e, k == kQNodes ? kSNodes : kSWorkloads);   // (K24 reads the space's histograms)
     free_quantile_trend(e, k);                                        // (the tail baseline reads the space's table)
     free_stage(e->qnt.sp[k]);
@@ -1483,6 +1529,7 @@ void free_idxsel(sg_engine::IdxSel<Row>& s) {
     s = sg_engine::IdxSel<Row>{};
 }
 void free_group_nodes(sg_engine* e) {
+    free_replicas(e);                                                 // (K25 reads the workload rows and the group map)
     free_traffic(e, kTWorkloads);                                     // (the traffic baseline reads the workload rows)
     free_quantiles(e, kQWorkloads);
     free_group_incidents(e);
@@ -1510,6 +1557,7 @@ void free_incidents(sg_engine* e) {
 }
 
 void free_nodes(sg_engine* e) {
+    free_replicas(e);                                                 // (K25 reads the node rows)
     free_traffic(e, kTNodes);                                         // (the traffic baseline reads the node rows)
     free_quantiles(e, kQNodes);
     free_incidents(e);
@@ -1572,6 +1620,7 @@ int do_score(sg_engine* e, hipStream_t s, bool proj_done, bool fuse_reset, bool*
             if (e->qnt.sp[kQWorkloads].on) { if (const int rc = launch_quantiles(e, kQWorkloads, s)) return rc; }   // K20 behind K16: and the workload rows
             if (e->slo.sp[kSWorkloads].on) { if (const int rc = launch_slo(e, kSWorkloads, s)) return rc; }   // K24 behind K20: the workload rows, their count, the histograms
             if (e->qtr.workloads.on) { if (const int rc = launch_node_tail(e, tail_workload_space(e), kQWorkloads, s, k21_wcount, k21_wwrite)) return rc; }   // K21 behind K20
+            if (e->rep.on) { if (const int rc = launch_replicas(e, s)) return rc; }   // K25 behind K9, K14 and K16 (with tails K20's node space): the node rows, the map, the workload rows
         }
     }
     return SG_OK;
@@ -4658,6 +4707,111 @@ int sg_window_group_nodes_top_slo(sg_handle e, uint32_t by, uint32_t k, uint32_t
     if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     return nodes_top_slo(e, kSWorkloads, "sg_window_group_nodes_top_slo", by, k, min_value_q10, out, index, cap, n_selected, n_rows);
+}
+
+// ---- K25, the replica outliers: the C ABI -----------------------------------------------------------------------------------------------
+namespace {
+static_assert(sizeof(sg_replica_params) == 40, "the layout include/servicegraph.h states");
+struct ReplicaRow { u32 w[SG_REPLICA_WORDS]; };        // the rows as the gathers move them
+struct ReplicaGroupRow { u32 w[SG_REPLICA_GROUP_WORDS]; };
+static_assert(sizeof(ReplicaGroupRow) <= sizeof(ReplicaRow), "one staging serves both reads");
+// the switch: off (p NULL), or on; a refused call leaves the stage as it was, a failed allocation leaves it off
+int replicas_set(sg_engine* e, const sg_replica_params* p) {
+    const char* call = "sg_set_replicas";
+    if (e->closing || e->flush_open) { e->err = std::string(call) + " while a flush is open"; return SG_ESTATE; }
+    if (!p) { free_replicas(e); return SG_OK; }
+    const u32 upstream = (e->nodes.on ? 1u : 0u) | (e->grp.on ? 2u : 0u) | (e->gnodes.on ? 4u : 0u) | (e->qnt.sp[kQNodes].on ? 8u : 0u);
+    const u32 slots = (u32)e->slots.size();
+    sgplan::ReplicaPlan P;
+    const int prc = sgplan::plan_replicas(*p, e->cfg.world, upstream, e->plan.ncap, e->gnodes.on ? e->gnodes.plan.gk : 0, e->gnodes.on ? e->gnodes.plan.nc : 0,
+                                          slots, &P);
+    if (prc == SG_ESTATE) {
+        e->err = std::string(call) + ": " + (!e->nodes.on ? kNodesWords.off : !e->grp.on ? kGroupsWords.off : !e->gnodes.on ? kGroupNodesWords.off : kQuantWords[kQNodes].off);
+        return SG_ESTATE;
+    }
+    if (prc) { e->err = std::string(call) + ": bad parameters, or an engine with world > 1"; return SG_EINVAL; }
+    free_replicas(e);
+    sg_engine::Replicas& x = e->rep;
+    HIP_TRY(e, hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (const int rc = alloc_block(e, &x.mem, P.total_bytes, call, [e] { free_replicas(e); })) return rc;
+    x.plan = P;
+    x.pos = at<u32>(x.mem, P.pos_off); x.tgt = at<u32>(x.mem, P.tgt_off); x.part = at<u64>(x.mem, P.part_off); x.vpart = at<u64>(x.mem, P.vpart_off);
+    x.wsum = at<u64>(x.mem, P.wsum_off); x.stage = at<u32>(x.mem, P.stage_off); x.stage_idx = at<u32>(x.mem, P.stage_idx_off);
+    for (u32 s = 0; s < slots; s++) {
+        x.pods.push_back(at<u32>(x.mem, P.slot.off + s * P.slot.bytes + P.slot_pods));
+        x.groups.push_back(at<u32>(x.mem, P.slot.off + s * P.slot.bytes + P.slot_groups));
+    }
+    x.valid.assign(slots, 0);
+    x.on = true;
+    return SG_OK;
+}
+// the pod rows (groups false) or the workload rows of the last read window, every row or those at index
+int replicas_read(sg_engine* e, bool groups, const char* call, const uint32_t* index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    const sg_engine::Replicas& x = e->rep;
+    if (const int rc = stage_ready(e, x, call, kReplicaWords)) return rc;
+    const NodeSpace ns = groups ? workload_space(e) : node_space(e);
+    u64 cnt = 0;
+    HIP_TRY(e, hipMemcpy(&cnt, ns.roll->count[e->cur], sizeof(u64), hipMemcpyDeviceToHost));
+    const size_t N = (size_t)std::min<u64>(cnt, ns.cap);
+    const std::string beyond = std::string(call) + ": a node index beyond the window's " + ns.rows_of;
+    if (groups) return copy_indexed(e, (const ReplicaGroupRow*)x.groups[e->cur], N, index, n_index, (ReplicaGroupRow*)out, cap, n, (ReplicaGroupRow*)x.stage,
+                                    x.stage_idx, (size_t)sgplan::kReplStageRows, beyond.c_str());
+    return copy_indexed(e, (const ReplicaRow*)x.pods[e->cur], N, index, n_index, (ReplicaRow*)out, cap, n, (ReplicaRow*)x.stage, x.stage_idx,
+                        (size_t)sgplan::kReplStageRows, beyond.c_str());
+}
+// the selection by a pod row's value (the node rows and pod rows of the last read window): k25_keys reads the pod rows and the row
+// count alone, behind the stage's run
+int replicas_top(sg_engine* e, const char* call, u32 by, u32 kk, u32 min_value, sg_node_out* out, uint32_t* index, size_t cap, size_t* n_selected,
+                 size_t* n_rows) {
+    const NodeSpace ns = node_space(e);
+    const u32 side = by & (SG_RSEL_IN | SG_RSEL_OUT);
+    if ((by & ~15u) || (side != SG_RSEL_IN && side != SG_RSEL_OUT)) {
+        e->err = std::string(call) + ": by is SG_RSEL_ERR, _LAT, _TAIL or _SHARE ORed with SG_RSEL_IN or SG_RSEL_OUT";
+        return SG_EINVAL;
+    }
+    const sg_engine::Replicas& x = e->rep;
+    if (const int rc = stage_ready(e, x, call, kReplicaWords)) return rc;
+    if (const int rc = check_nsel(e, ns, SG_NSEL_SCORE, e->cur)) return rc;
+    if (const int rc = nsel_reserve(e, ns)) return rc;
+    return node_top_host(e, ns, [&](sg_node_out* d_out, sg_node_rank*, u64 stage, u64* d_n) {
+        const SelView<sg_node_out> v = node_sel_view(ns, e->cur);
+        return launch_index_select(e, v, e->rd_stream, kk, 0.f, d_out, (u32*)nullptr, stage, d_n, [&](const SelArgs& a, u32 wgs) {
+            hipLaunchKernelGGL(k25_keys<0>, dim3(wgs), dim3(K7_THREADS), 0, e->rd_stream, a, v.count, (const u32*)x.pods[e->cur], side == SG_RSEL_OUT ? 1u : 0u,
+                               by & 3u, min_value, v.sel->ctr);
+            return (int)SG_OK;
+        }, [](const SelArgs&, dim3) {});
+    }, out, nullptr, nullptr, index, cap, n_selected, n_rows);
+}
+}  // namespace
+int sg_set_replicas(sg_handle e, const sg_replica_params* p) {
+    if (!e) return SG_EINVAL;
+    std::unique_lock<std::mutex> g(e->mu);
+    return replicas_set(e, p);
+}
+int sg_window_replicas(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return replicas_read(e, false, "sg_window_replicas", node_index, n_index, out, cap, n);
+}
+int sg_window_group_replicas(sg_handle e, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return replicas_read(e, true, "sg_window_group_replicas", node_index, n_index, out, cap, n);
+}
+int sg_window_replicas_buffer(sg_handle e, void** d_pod_rows, void** d_group_rows) {
+    if (!e) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    int slot;
+    if (const int rc = stage_slot(e, e->rep, "sg_window_replicas_buffer", kReplicaWords, &slot)) return rc;
+    if (d_pod_rows) *d_pod_rows = e->rep.pods[slot];
+    if (d_group_rows) *d_group_rows = e->rep.groups[slot];
+    return SG_OK;
+}
+int sg_window_replicas_top(sg_handle e, uint32_t by, uint32_t k, uint32_t min_value, sg_node_out* out, uint32_t* index, size_t cap, size_t* n_selected,
+                           size_t* n_rows) {
+    if (!e || k > SG_SELECT_MAX_K) return SG_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    return replicas_top(e, "sg_window_replicas_top", by, k, min_value, out, index, cap, n_selected, n_rows);
 }
 
 int sg_window_hist(sg_handle e, uint32_t* bins, size_t cap_rows, size_t* n) {

@@ -1613,6 +1613,78 @@ inline int plan_slo(const sg_slo_params& p, u32 spaces, u32 on, u64 mk, u64 ml, 
     return SG_OK;
 }
 
+// K25, the replica outliers (sg_replicas.h): one device block — the position table pos [gk] u32 (k20_pos_groups' shape), the target
+// workload row of every node row tgt [ncap] u32, the member sums' partials [ranges][slices][range_rows][words] u64, the verdicts'
+// partials [ranges][slices][range_rows][6] u64, the member sums per workload row [nc][words] u64, a staging of kReplStageRows pod
+// rows for the index reads and per slot the pod rows [ncap][12] u32 and the workload rows [nc][8] u32.  words: 4 a side (R, C, E, T),
+// and the 16 bins behind them with tails on; range_rows is what 64 KiB of LDS hold of them (1024 or 204 workload rows: two
+// k25_fold workgroups a CU); one slice per 2048 node rows, at most 64, cut until the partials fit 256 MiB.  sg_set_replicas
+// allocates it, never sg_create.  The parameters come back with their defaults filled in.
+constexpr u32 kReplThreads = 256, kReplMaxWgs = 1024, kReplStageRows = 1024, kReplSliceItems = 2048, kReplMaxSlices = 64, kReplSideWords = 4,
+              kReplVerdictWords = 6, kReplLdsBytes = 64 * 1024;
+constexpr u64 kReplPartBudget = 256ull << 20;
+static_assert(2 * kReplLdsBytes <= kLdsBytes, "two k25_fold workgroups a CU");
+struct ReplicaPlan {
+    bool on = false;
+    sg_replica_params p{};        // the parameters in force: no zero left that stands for a default
+    u32 tails = 0;                // 1: tail_permille != 0, the stage reads K20's node histograms
+    u32 words = 0;                // u64 words a workload row of the member sums: 8, or 40 with tails
+    u32 range_rows = 0, ranges = 0, slices = 0;   // k25_fold's grid: ranges x slices workgroups
+    u32 lds_bytes = 0, vlds_bytes = 0;            // k25_fold's LDS under the sums' policy and the verdicts'
+    u32 node_wgs = 0, group_wgs = 0, sum_wgs = 0, pos_wgs = 0;   // k25_member / k25_rows; k25_groups; k25_reduce; k20_pos_groups
+    u64 ncap = 0, nc = 0, gk = 0;
+    u64 pos_off = 0, tgt_off = 0, part_off = 0, vpart_off = 0, wsum_off = 0, stage_off = 0, stage_idx_off = 0, slot_pods = 0, slot_groups = 0;
+    u64 part_bytes = 0, vpart_bytes = 0, wsum_bytes = 0, pod_bytes = 0, group_bytes = 0;
+    Slots slot;
+    u64 total_bytes = 0;
+    std::vector<Piece> layout;
+};
+// upstream: bit 0 the node rollup, bit 1 the groups, bit 2 the workload rows, bit 3 K20's SG_Q_NODES space — what is on.  ncap: the
+// node rows a slot holds; gk, nc: K16's group keys and workload rows a slot.  SG_OK and *out, SG_EINVAL or SG_ESTATE
+inline int plan_replicas(const sg_replica_params& in, u32 world, u32 upstream, u32 ncap, u64 gk, u32 nc, u32 slots, ReplicaPlan* out) {
+    if (in.struct_size != sizeof(sg_replica_params) || in.reserved[0] || in.reserved[1] || world > 1) return SG_EINVAL;
+    if (in.min_replicas == 1 || in.min_err_excess_q20 > (1u << 20) || in.tail_permille > 999 || in.min_tail_bins > 15) return SG_EINVAL;
+    ReplicaPlan q;
+    q.p = in;
+    if (!q.p.min_replicas) q.p.min_replicas = 3;
+    if (!q.p.min_requests) q.p.min_requests = 20;
+    if (!q.p.min_err_excess_q20) q.p.min_err_excess_q20 = 20972;
+    if (!q.p.min_lat_ratio_q10) q.p.min_lat_ratio_q10 = 2048;
+    if (!q.p.min_tail_bins) q.p.min_tail_bins = 2;
+    q.tails = q.p.tail_permille != 0;
+    if ((upstream & 7u) != 7u || (q.tails && !(upstream & 8u))) return SG_ESTATE;
+    if (gk > kQMaxKeys) return SG_EINVAL;
+    q.on = true;
+    q.ncap = std::max<u32>(ncap, 1); q.nc = std::max<u32>(nc, 1); q.gk = std::max<u64>(gk, 1);
+    q.words = 2 * (kReplSideWords + (q.tails ? kQBins : 0u));
+    q.range_rows = kReplLdsBytes / (q.words * 8);
+    q.ranges = (u32)((q.nc + q.range_rows - 1) / q.range_rows);
+    const u64 range_bytes = (u64)q.range_rows * q.words * 8;
+    const u64 want = std::min<u64>(kReplMaxSlices, (q.ncap + kReplSliceItems - 1) / kReplSliceItems);
+    q.slices = (u32)std::max<u64>(1, std::min<u64>(want, kReplPartBudget / ((u64)q.ranges * range_bytes)));
+    q.lds_bytes = (u32)range_bytes; q.vlds_bytes = q.range_rows * kReplVerdictWords * 8;
+    q.node_wgs = (u32)std::max<u64>(1, std::min<u64>(kReplMaxWgs, (q.ncap + kReplThreads - 1) / kReplThreads));
+    q.group_wgs = (u32)std::max<u64>(1, std::min<u64>(kReplMaxWgs, (q.nc + kReplThreads - 1) / kReplThreads));
+    q.sum_wgs = (u32)std::max<u64>(1, std::min<u64>(kReplMaxWgs, (q.nc * q.words + kReplThreads - 1) / kReplThreads));
+    q.pos_wgs = (u32)std::max<u64>(1, std::min<u64>(kQMaxWgs, (q.nc + kQThreads - 1) / kQThreads));
+    q.part_bytes = (u64)q.ranges * q.slices * range_bytes;
+    q.vpart_bytes = (u64)q.ranges * q.slices * q.vlds_bytes;
+    q.wsum_bytes = q.nc * q.words * 8;
+    q.pod_bytes = trend_align(q.ncap * SG_REPLICA_WORDS * 4); q.group_bytes = trend_align(q.nc * SG_REPLICA_GROUP_WORDS * 4);
+    Block b;
+    q.pos_off = b.take("pos", trend_align(q.gk * 4));
+    q.tgt_off = b.take("tgt", trend_align(q.ncap * 4));
+    q.part_off = b.take("part", q.part_bytes);
+    q.vpart_off = b.take("vpart", q.vpart_bytes);
+    q.wsum_off = b.take("wsum", q.wsum_bytes);
+    q.stage_off = b.take("stage", (u64)kReplStageRows * SG_REPLICA_WORDS * 4);
+    q.stage_idx_off = b.take("stage_idx", (u64)kReplStageRows * 4);
+    q.slot = b.slots(slots, {{"pod_rows", q.pod_bytes, &q.slot_pods}, {"group_rows", q.group_bytes, &q.slot_groups}});
+    q.total_bytes = b.up(b.end); q.layout = std::move(b.pieces);
+    *out = q;
+    return SG_OK;
+}
+
 // Does THIS close launch no kc_prepare (Plan::prepare_fold)?  warm: the close keeps the state (not one the back-off closes the plain way);
 // warm_try: the host tries the warm path (sg_set_warm), so the close launches the warm attempt; ob_mode 1: the engine collects its own raw
 // outbound IPs (0 / 2: a sharded driver's union or gathered lists, which are kc_prepare arguments the attempt's launch does not carry).

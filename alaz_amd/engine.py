@@ -199,6 +199,26 @@ def slo_objective(latency_bin: int, latency_target_ppm: int, error_target_ppm: i
     return latency_bin << 28 | slo_budget_code(1000000 - latency_target_ppm) << 12 | slo_budget_code(1000000 - error_target_ppm)
 
 
+#: SG_REPL_* / SG_RSEL_* (K25): a pod row is REPLICA_WORDS u32 words — the workload row index (0xFFFFFFFF: no member), the flags, then
+#: REPLICA_SIDE_FIELDS for the in side (words 2 .. 6) and again for the out side (7 .. 11); a workload row is REPLICA_GROUP_WORDS
+#: words, REPLICA_GROUP_FIELDS a side.  A side's flags are the in side's << 4 * side.  REPLICA_DEFAULTS: every 0 is the stage's own default
+REPLICA_WORDS = 12
+REPLICA_GROUP_WORDS = 8
+REPLICA_SIDE_FIELDS = ("err_excess_q20", "lat_ratio_q10", "share_q10", "tail_bins", "replicas")
+REPLICA_GROUP_FIELDS = ("replicas", "judged", "outliers", "first_outlier")
+REPL_MEMBER, REPL_JUDGED_IN, REPL_ERR_IN, REPL_LAT_IN, REPL_TAIL_IN = 1, 2, 4, 8, 16
+REPL_JUDGED_OUT, REPL_ERR_OUT, REPL_LAT_OUT, REPL_TAIL_OUT = 32, 64, 128, 256
+RSEL_BY = dict(err=0, lat=1, tail=2, share=3)
+RSEL_SIDE = {"in": 4, "out": 8}
+REPLICA_DEFAULTS = dict(min_replicas=0, min_requests=0, min_err_excess_q20=0, min_lat_ratio_q10=0, tail_permille=0, min_tail_bins=0)
+
+
+class ReplicaParams(C.Structure):
+    """sg_replica_params (K25); tests/test_replicas_host.py holds its layout to the header with the compiler"""
+    _fields_ = [("struct_size", C.c_uint32), ("min_replicas", C.c_uint32), ("min_requests", C.c_uint64), ("min_err_excess_q20", C.c_uint32),
+                ("min_lat_ratio_q10", C.c_uint32), ("tail_permille", C.c_uint32), ("min_tail_bins", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class SgVanishedParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("silent_windows", C.c_uint32), ("min_seen", C.c_uint32), ("max_rows", C.c_uint32)]
 
@@ -373,6 +393,10 @@ def _signatures() -> dict:
         "sg_slo_entries": (I, [H, u32, P, sz, Psz]), "sg_slo_stats_get": (I, [H, u32, P]),
         "sg_window_nodes_top_slo": (I, [H, u32, u32, u32, P, P, sz, Psz, Psz]),
         "sg_window_group_nodes_top_slo": (I, [H, u32, u32, u32, P, P, sz, Psz, Psz]),
+        "sg_set_replicas": (I, [H, P]),
+        "sg_window_replicas": (I, [H, P, sz, P, sz, Psz]), "sg_window_group_replicas": (I, [H, P, sz, P, sz, Psz]),
+        "sg_window_replicas_buffer": (I, [H, PP, PP]),
+        "sg_window_replicas_top": (I, [H, u32, u32, u32, P, P, sz, Psz, Psz]),
     }
 
 
@@ -426,6 +450,8 @@ _STAGES = dict(
     traffic_trend=_Stage("sg_set_traffic_trend", TrafficParams, TRAFFIC_DEFAULTS, "set_traffic_trend(params=None) switches the traffic baselines off",
                          "traffic trend"),
     slo=_Stage("sg_set_slo", SloParams, SLO_DEFAULTS, "set_slo(params=None) switches the SLO stage off", "SLO"),
+    replicas=_Stage("sg_set_replicas", ReplicaParams, REPLICA_DEFAULTS, "set_replicas(None) switches the replica outliers off", "replica",
+                    dict(reserved=lambda r: (C.c_uint32 * 2)(*((r, 0) if isinstance(r, int) else tuple(r))))),
 )
 
 _lib = None
@@ -1435,6 +1461,44 @@ class ServiceGraph:
         b = self._sloby(by, side)
         return self._top(lambda *a: self._l.sg_window_group_nodes_top_slo(self._h, b, k, min_value_q10, *a),
                          self._node_cap(k, cap, self._l.sg_window_group_nodes), NODE_DTYPE, np.uint32)
+
+    # ---- replica outliers (K25): each pod against the other pods of its workload ----
+    def set_replicas(self, params: Optional[dict] = (), **kw):
+        """Switch the replica outliers on (sg_set_replicas; needs set_nodes, set_groups and set_group_nodes, and with tail_permille
+        set_quantiles over "nodes"): per pod of a workload the error rate, mean latency, load share and tail bin of each side against
+        its siblings' leave-one-out remainder.  REPLICA_DEFAULTS' parameters as keywords or a dict (0: the stage's default);
+        set_replicas(None) switches it off.  Returns the parameters given."""
+        return self._set_stage("replicas", params, kw)
+
+    def window_replicas(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, REPLICA_WORDS) u32 pod rows of the last read window (sg_window_replicas), row k for row k of window_nodes(); or the
+        rows at `index`"""
+        return self._window_rows(self._l.sg_window_replicas, np.dtype(("<u4", (REPLICA_WORDS,))), index)
+
+    def window_group_replicas(self, index: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, REPLICA_GROUP_WORDS) u32 workload rows (sg_window_group_replicas), row k for row k of window_group_nodes(); or those
+        at `index`"""
+        return self._window_rows(self._l.sg_window_group_replicas, np.dtype(("<u4", (REPLICA_GROUP_WORDS,))), index)
+
+    def window_replicas_buffer(self) -> tuple:
+        """device pointers of the pod rows and the workload rows of the window window_run closed last (sg_window_replicas_buffer)"""
+        return self._pointers(self._l.sg_window_replicas_buffer, 2)
+
+    @staticmethod
+    def _rselby(by, side=None) -> int:
+        """SG_RSEL_*: an int as it is; else a kind of RSEL_BY with side "in" / "out" (RSEL_SIDE) ORed in"""
+        if not isinstance(by, str):
+            return by
+        if by not in RSEL_BY or side not in RSEL_SIDE:
+            raise ValueError(f"unknown replica key {by!r} / side {side!r}: one of {sorted(RSEL_BY)}, {sorted(RSEL_SIDE)}")
+        return RSEL_BY[by] | RSEL_SIDE[side]
+
+    def window_replicas_top(self, k: int, min_value: int = 0, by="err", side="in", cap: Optional[int] = None):
+        """(the selected node rows, their indices, the row count) by a pod row's value (sg_window_replicas_top): by "err" / "lat" /
+        "tail" / "share" of side "in" / "out" (or by as the SG_RSEL_* int), descending, k = 0 every judged side with a value >=
+        max(min_value, 1).  "The 20 replicas furthest above their peers' error rate" is (20, by="err", side="in")."""
+        b = self._rselby(by, side)
+        return self._top(lambda *a: self._l.sg_window_replicas_top(self._h, b, k, min_value, *a), self._node_cap(k, cap), NODE_DTYPE, np.uint32)
 
     @staticmethod
     def _rows_view(ptr, n) -> np.ndarray:

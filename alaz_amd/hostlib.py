@@ -45,6 +45,14 @@ def _workload_node_dtype():
     return np.dtype([("type", "S16"), ("uid", "S160"), ("row", NODE_DTYPE)])
 
 
+#: sgh_replica_outlier of host_capi.cpp: one selected replica (GraphDS::WorkloadReplicaOutliers) — the pod's UID, its workload's owner
+#: UID, its node row and workload row indices, the pod row's flags and the words of the selected side
+def _replica_outlier_dtype():
+    return np.dtype([("pod", "S160"), ("workload", "S160"), ("node_index", "<u4"), ("workload_index", "<u4"), ("flags", "<u4"),
+                     ("err_excess_q20", "<i4"), ("lat_ratio_q10", "<u4"), ("share_q10", "<u4"), ("tail_pod", "<u4"), ("tail_peers", "<u4"),
+                     ("replicas", "<u4")])
+
+
 #: sgh_workload_culprit of host_capi.cpp: one selected workload of the ranking (GraphDS::WorkloadCulprits) — the workload row as
 #: _workload_node_dtype has it, then the engine's sg_node_rank as engine.RANK_DTYPE has it
 def _workload_culprit_dtype():
@@ -155,6 +163,8 @@ def load() -> C.CDLL:
             "sgh_graphds_set_slo": (C.c_int, [P, u32, C.c_int, u32, u32, u32, u32, u32, u32, C.c_uint64]),
             "sgh_graphds_set_workload_slo": (C.c_int, [P, C.c_char_p, u32]), "sgh_graphds_workload_slo": (C.c_long, [P, P, sz]),
             "sgh_graphds_workload_slo_top": (C.c_long, [P, u32, u32, u32, P, P, sz]), "sgh_mock_k24_ops": (sz, [P, P, sz]),
+            "sgh_graphds_set_replica_outliers": (C.c_int, [P, C.c_int, u32, C.c_uint64, u32, u32, u32, u32]),
+            "sgh_graphds_workload_replica_outliers": (C.c_long, [P, u32, u32, u32, P, sz]), "sgh_mock_k25_ops": (sz, [P, P, sz]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name); f.restype = res; f.argtypes = args
@@ -790,6 +800,32 @@ class GraphDS:
         n = self._l.sgh_mock_k23_ops(self._g, None, 0)
         out = np.zeros((max(n, 1), 4), dtype=np.uint64)
         self._l.sgh_mock_k23_ops(self._g, out.ctypes.data, n)
+        return out[:n]
+
+    # ---- the replica outliers (K25) ----
+    def set_replica_outliers(self, on: bool = True, min_replicas: int = 0, min_requests: int = 0, min_err_excess_q20: int = 0,
+                             min_lat_ratio_q10: int = 0, tail_permille: int = 0, min_tail_bins: int = 0) -> int:
+        """GraphDS::SetReplicaOutliers: each pod against the other pods of its workload (0: the engine's default; on=False: off; rc)"""
+        return self._l.sgh_graphds_set_replica_outliers(self._g, 1 if on else 0, min_replicas, min_requests, min_err_excess_q20, min_lat_ratio_q10,
+                                                        tail_permille, min_tail_bins)
+
+    def workload_replica_outliers(self, by: int, k: int, min_value: int = 0) -> np.ndarray:
+        """GraphDS::WorkloadReplicaOutliers: the selected replicas (_replica_outlier_dtype) — by = SG_RSEL_ERR / _LAT / _TAIL / _SHARE ORed
+        with SG_RSEL_IN or SG_RSEL_OUT, ranked by that side's value"""
+        n = self._l.sgh_graphds_workload_replica_outliers(self._g, by, k, min_value, None, 0)
+        if n < 0:
+            raise RuntimeError(f"WorkloadReplicaOutliers failed: {n}")
+        out = np.zeros(max(n, 1), dtype=_replica_outlier_dtype())
+        self._l.sgh_graphds_workload_replica_outliers(self._g, by, k, min_value, out.ctypes.data, n)
+        return out[:n]
+
+    def mock_k25_ops(self) -> np.ndarray:
+        """the stand-in engine's K25 calls in order, four u64 each: (1, min_replicas | tail_permille << 32 or all ones for NULL,
+        min_requests, min_err_excess_q20 | min_lat_ratio_q10 << 32) per sg_set_replicas, (2, n_index or all ones, cap, 0) per
+        sg_window_replicas, (3, by, k, min_value) per sg_window_replicas_top"""
+        n = self._l.sgh_mock_k25_ops(self._g, None, 0)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._l.sgh_mock_k25_ops(self._g, out.ctypes.data, n)
         return out[:n]
 
     # ---- the SLO burn rates (K24) ----

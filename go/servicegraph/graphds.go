@@ -2283,3 +2283,120 @@ func (g *GraphDS) WindowSLOBurn(by, k, minValueQ10 uint32) ([]WorkloadNode, []SL
 	}
 	return goWorkloadNodes(ns), rows, index, nil
 }
+
+// ---- replica outliers (K25) -------------------------------------------------------------------------------------------
+
+// Selection keys and row flags of include/servicegraph.h ("replica outliers").
+const (
+	ReplicaErr      = uint32(C.SG_RSEL_ERR)
+	ReplicaLat      = uint32(C.SG_RSEL_LAT)
+	ReplicaTail     = uint32(C.SG_RSEL_TAIL)
+	ReplicaShare    = uint32(C.SG_RSEL_SHARE)
+	ReplicaIn       = uint32(C.SG_RSEL_IN)
+	ReplicaOut      = uint32(C.SG_RSEL_OUT)
+	ReplicaMember   = uint32(C.SG_REPL_MEMBER)
+	ReplicaJudged   = uint32(C.SG_REPL_JUDGED_IN) // a side's flags: Judged, ErrFlag, LatFlag, TailFlag; << 4 for the out side
+	ReplicaErrFlag  = uint32(C.SG_REPL_ERR_IN)
+	ReplicaLatFlag  = uint32(C.SG_REPL_LAT_IN)
+	ReplicaTailFlag = uint32(C.SG_REPL_TAIL_IN)
+	replicaWords    = int(C.SG_REPLICA_WORDS)
+)
+
+// ReplicaParams is sg_replica_params; a zero is the engine's default: a side is judged with MinReplicas (3) active replicas and
+// MinRequests (20) requests on the pod and on its peers; it is an outlier from MinErrExcessQ20 (20972: two points of error rate),
+// MinLatRatioQ10 (2048: twice the peers' mean) or, with TailPermille set, MinTailBins (2) octaves of that percentile.
+type ReplicaParams struct {
+	MinReplicas                                                 uint32
+	MinRequests                                                 uint64
+	MinErrExcessQ20, MinLatRatioQ10, TailPermille, MinTailBins uint32
+}
+
+// ReplicaSide is one side of a pod row: the error rate above the peers' (2^20 = 100 points), the mean latency over the peers'
+// mean and the share of the fair share (1024 = 1), the percentile's K20 bin of the pod and of its peers, and the active replicas.
+type ReplicaSide struct {
+	ErrExcessQ20          int32
+	LatRatioQ10, ShareQ10 uint32
+	TailPod, TailPeers    uint32
+	Replicas              uint32
+}
+
+// ReplicaRow is sg_window_replicas' row of one node row: the workload row it is a member of, the flags, the calls it receives
+// (In) and the calls it makes (Out).
+type ReplicaRow struct {
+	Workload, Flags uint32
+	In, Out         ReplicaSide
+}
+
+// SetReplicaOutliers switches the replica stage on: each pod of a workload against the leave-one-out remainder of its siblings, per
+// window and without state.  It needs the node rollup, AssignGroups' map and the workload rows, and with TailPermille the latency
+// quantiles over the services.
+func (g *GraphDS) SetReplicaOutliers(p ReplicaParams) error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sp C.sg_replica_params
+	sp.struct_size = C.uint32_t(unsafe.Sizeof(sp))
+	sp.min_replicas, sp.min_requests = C.uint32_t(p.MinReplicas), C.uint64_t(p.MinRequests)
+	sp.min_err_excess_q20, sp.min_lat_ratio_q10 = C.uint32_t(p.MinErrExcessQ20), C.uint32_t(p.MinLatRatioQ10)
+	sp.tail_permille, sp.min_tail_bins = C.uint32_t(p.TailPermille), C.uint32_t(p.MinTailBins)
+	if rc := C.sg_set_replicas(g.h, &sp); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_replicas = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+// ClearReplicaOutliers switches the replica stage off and frees it.
+func (g *GraphDS) ClearReplicaOutliers() error {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	if rc := C.sg_set_replicas(g.h, nil); rc != 0 {
+		return fmt.Errorf("servicegraph: sg_set_replicas = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	return nil
+}
+
+func goReplicaSide(w []uint32) ReplicaSide {
+	return ReplicaSide{int32(w[0]), w[1], w[2], w[3] & 255, w[3] >> 8 & 255, w[4]}
+}
+
+// WindowReplicaOutliers selects the pods of the window FlushWindow returned last by a replica value (sg_window_replicas_top): by is
+// ReplicaErr, ReplicaLat, ReplicaTail or ReplicaShare ORed with ReplicaIn or ReplicaOut; the k largest values >= minValue of
+// judged sides, descending, with their pod rows (sg_window_replicas at the selected indices) and their indices into the node
+// rows.  k = 0: every such pod, in order.  WindowReplicaOutliers(ReplicaErr|ReplicaIn, 20, 1) is "the 20 replicas furthest above
+// their peers' error rate".  The first result holds NODE rows, one per selected pod: sg_node_out is the row type of the node rows and
+// of the workload rows alike, and WorkloadNode is this package's one Go form of it; Ref is the pod's KNOWN ref here, not a group's.
+func (g *GraphDS) WindowReplicaOutliers(by, k, minValue uint32) ([]WorkloadNode, []ReplicaRow, []uint32, error) {
+	g.flushMu.Lock()
+	defer g.flushMu.Unlock()
+	var sel, total C.size_t
+	room := int(k)
+	if k == 0 { // the count first
+		if rc := C.sg_window_replicas_top(g.h, C.uint32_t(by), 0, C.uint32_t(minValue), nil, nil, 0, &sel, &total); rc != 0 {
+			return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_replicas_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+		}
+		room = int(sel)
+	}
+	if room == 0 {
+		return nil, nil, nil, nil
+	}
+	ns, index := make([]C.sg_node_out, room), make([]uint32, room)
+	if rc := C.sg_window_replicas_top(g.h, C.uint32_t(by), C.uint32_t(k), C.uint32_t(minValue), &ns[0], (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(room), &sel, &total); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_replicas_top = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	if int(sel) < room {
+		ns, index = ns[:int(sel)], index[:int(sel)]
+	}
+	if len(index) == 0 {
+		return nil, nil, nil, nil
+	}
+	var n C.size_t
+	words := make([]uint32, len(index)*replicaWords)
+	if rc := C.sg_window_replicas(g.h, (*C.uint32_t)(unsafe.Pointer(&index[0])), C.size_t(len(index)), (*C.uint32_t)(unsafe.Pointer(&words[0])), C.size_t(len(index)), &n); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("servicegraph: sg_window_replicas = %d: %s", int(rc), C.GoString(C.sg_last_error(g.h)))
+	}
+	pods := make([]ReplicaRow, len(index))
+	for i := range pods {
+		w := words[i*replicaWords : (i+1)*replicaWords]
+		pods[i] = ReplicaRow{w[0], w[1], goReplicaSide(w[2:7]), goReplicaSide(w[7:12])}
+	}
+	return goWorkloadNodes(ns), pods, index, nil
+}

@@ -1356,6 +1356,96 @@ int sg_slo_stats_get(sg_handle h, uint32_t space, sg_slo_stats* out);
 int sg_window_nodes_top_slo(sg_handle h, uint32_t by, uint32_t k, uint32_t min_value_q10, sg_node_out* out, uint32_t* index, size_t cap, size_t* n_selected, size_t* n_rows);
 int sg_window_group_nodes_top_slo(sg_handle h, uint32_t by, uint32_t k, uint32_t min_value_q10, sg_node_out* out, uint32_t* index, size_t cap, size_t* n_selected, size_t* n_rows);
 
+/* ---- replica outliers (K25): each pod against the other pods of its workload ---------------------------------------------------- *
+ * Opt-in (sg_set_replicas); without it nothing is launched or allocated, and every other output is byte for byte the same either
+ * way.  Every baseline judges an entity against its own past and the SLO stage against an absolute objective; this stage judges a
+ * pod against its SIBLINGS: is `checkout` red, or one replica of it (a bad node, a poisoned connection pool, three times its share
+ * of the load)?  The stage is stateless: a window's rows depend on that window alone, and integer arithmetic gives them one value.
+ * Members.  Over the closed window's node rows v (sg_window_nodes order) and workload rows w (sg_window_group_nodes order).  Node
+ * row v is a MEMBER of workload row w when its ref is KNOWN with id, the device kind[id] is SG_NODE_POD, group[id] = g !=
+ * SG_NO_GROUP under the map the window was contracted under, and w is the workload row whose ref is SG_REF_GROUP | g.  Services
+ * are never members, not even a Service that service binding has put into the group: its in side is the whole workload's traffic,
+ * not a replica's.  LABEL, OBIP and ungrouped nodes are never members.
+ * Member sums, per workload row and side s (in or out, sg_node_trend's order), exact uint64_t, T wrapping:
+ *   R = members with count_s > 0      C = sum count_s      E = sum err_s      T = sum sum_ns_s
+ *   with tails on, H[b] = sum of bin b of the members' K20 node histograms of that side
+ * Judged.  Side s of member v with (c, e, S, h[16]) is JUDGED when c >= min_requests, C - c >= min_requests and R >=
+ * min_replicas.  The peers are the leave-one-out remainder (C - c, E - e, T - S, H - h); T - S wraps.  For a judged side
+ *   x_err(e, c)     = floor(min(e, c) * 2^20 / c)                        (K10's sample rule, by long division)
+ *   err_excess_q20  = (int32) x_err(e, c) - (int32) x_err(E - e, C - c)
+ *   mean(S, c)      = min(floor(S / c), 2^52)                            (K10's x_lat)
+ *   lat_ratio_q10   = min(floor(mean(S, c) * 1024 / max(mean(T - S, C - c), 1)), 2^32 - 1)
+ *   share_q10       = min(floor(min(c, 2^53) * 1024 / max(floor(C / R), 1)), 2^32 - 1)      (1024 is exactly the fair share)
+ *   tails, only when tail_permille != 0: qbin(h) is the first bin whose cumulative count reaches K20's rank
+ *   max(1, ceil(total * permille / 1000)), bin 15 when none does and 0 for total == 0; bins are compared, so no max_ns cap applies
+ *   tail_pod = qbin(h), tail_peers = qbin(H - h), tail_excess = tail_pod - tail_peers in octaves
+ * A side that is not judged has all of these 0.
+ * Example.  Four member pods each received 100 requests; pod A has 10 errors and a 4 000 000 ns mean, the others 1 error each and
+ * a 1 000 000 ns mean.  With min_requests 20 and min_replicas 3, A's in side: x_err = 104857, the peers' floor(3 * 2^20 / 300) =
+ * 10485, err_excess_q20 = 94372; lat_ratio_q10 = 4096; share_q10 = 1024.
+ * Flags.  SG_REPL_MEMBER; per side SG_REPL_JUDGED_*, SG_REPL_ERR_* when err_excess_q20 >= min_err_excess_q20, SG_REPL_LAT_* when
+ * lat_ratio_q10 >= min_lat_ratio_q10, SG_REPL_TAIL_* when tails are on and tail_excess >= min_tail_bins.  A side that carries any
+ * of ERR, LAT or TAIL is an OUTLIER side.
+ * Pod row k (SG_REPLICA_WORDS uint32_t words, for node row k):
+ *   word 0        the workload row index, 0xFFFFFFFF for a non-member
+ *   word 1        flags
+ *   words 2 .. 6  the in side: err_excess_q20 (two's complement), lat_ratio_q10, share_q10, tail_pod | tail_peers << 8, R
+ *   words 7 .. 11 the out side, the same
+ * A non-member row is 0xFFFFFFFF followed by zeros.
+ * Workload row k (SG_REPLICA_GROUP_WORDS words, for workload row k), four words a side, the in side first:
+ *   R, judged members, outlier members, the smallest node-row index among the outlier members (0xFFFFFFFF: none)
+ * Every close path computes it on the window's stream, behind K16 (and behind K20's node space when tails are on).  An engine
+ * with world > 1 has no node rollup and so no replica stage.                                                                      */
+#define SG_REPLICA_WORDS        12u
+#define SG_REPLICA_GROUP_WORDS  8u
+#define SG_REPL_MEMBER      1u      /* flags of word 1 */
+#define SG_REPL_JUDGED_IN   2u
+#define SG_REPL_ERR_IN      4u
+#define SG_REPL_LAT_IN      8u
+#define SG_REPL_TAIL_IN     16u
+#define SG_REPL_JUDGED_OUT  32u     /* the in side's flags << 4 */
+#define SG_REPL_ERR_OUT     64u
+#define SG_REPL_LAT_OUT     128u
+#define SG_REPL_TAIL_OUT    256u
+typedef struct sg_replica_params {
+    uint32_t struct_size;        /* sizeof(sg_replica_params)                                                                */
+    uint32_t min_replicas;       /* a side is judged with R >= min_replicas; at least 2, 0 = 3                               */
+    uint64_t min_requests;       /* ... and with c and C - c >= min_requests; 0 = 20                                         */
+    uint32_t min_err_excess_q20; /* 0 = 20972 (two points), at most 2^20                                                     */
+    uint32_t min_lat_ratio_q10;  /* 0 = 2048 (twice the peers' mean)                                                         */
+    uint32_t tail_permille;      /* 0 = no tails, else 1 .. 999: needs K20's SG_Q_NODES space                                */
+    uint32_t min_tail_bins;      /* 0 = 2, at most 15                                                                        */
+    uint32_t reserved[2];        /* 0                                                                                        */
+} sg_replica_params;             /* 40 bytes, no padding */
+/* p == NULL switches the stage off and frees it; every call replaces the previous setting.  SG_EINVAL for bad parameters and on an
+ * engine with world > 1; SG_ESTATE when the node rollup, the groups or the workload rows are off, when tails are asked for and
+ * K20's SG_Q_NODES space is off, or while a flush is open: such a call leaves the stage as it was.  Memory is allocated here, never
+ * at sg_create; a failed allocation (SG_ENOMEM) leaves the stage off.  Whatever frees one of its inputs frees this stage first:
+ * sg_set_nodes(h, 0), any sg_set_groups call, sg_set_group_nodes(h, 0), and any sg_set_quantiles call when tails are on.
+ * sg_group_assign does not touch it: each window is judged under the map it was contracted under.                               */
+int sg_set_replicas(sg_handle h, const sg_replica_params* p);
+/* The pod rows / workload rows of the last READ window, with sg_window_node_slo's shape: index NULL: every row, *n = their count;
+ * else out[k] = the row of index[k] (each < the count, else SG_EINVAL), *n = n_index.  cap counts rows of SG_REPLICA_WORDS /
+ * SG_REPLICA_GROUP_WORDS words; min(*n, cap) rows are written.                                                                   */
+int sg_window_replicas(sg_handle h, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n);
+int sg_window_group_replicas(sg_handle h, const uint32_t* node_index, size_t n_index, uint32_t* out, size_t cap, size_t* n);
+/* The device rows (uint32_t[node rows][SG_REPLICA_WORDS], uint32_t[workload rows][SG_REPLICA_GROUP_WORDS]) of the window
+ * sg_window_run closed last; either pointer may be NULL.                                                                         */
+int sg_window_replicas_buffer(sg_handle h, void** d_pod_rows, void** d_group_rows);
+/* Selection over the pod rows of the last READ window: `by` is one of SG_RSEL_ERR / _LAT / _TAIL / _SHARE ORed with exactly one of
+ * SG_RSEL_IN / SG_RSEL_OUT, else SG_EINVAL.  A row's key is max(err_excess_q20, 0), lat_ratio_q10, max(tail_excess, 0) or
+ * share_q10 of that side when it is judged; key 0 and sides that are not judged are never candidates.  The k largest keys >=
+ * min_value are selected (k = 0: every such row), ties by node position; rows and indices as sg_window_nodes_top gives them, the
+ * rows byte-identical to sg_window_nodes'.  "The 20 replicas furthest above their peers' error rate" is
+ * sg_window_replicas_top(h, SG_RSEL_ERR | SG_RSEL_IN, 20, 1, ...).                                                               */
+#define SG_RSEL_ERR    0u
+#define SG_RSEL_LAT    1u
+#define SG_RSEL_TAIL   2u
+#define SG_RSEL_SHARE  3u
+#define SG_RSEL_IN     4u       /* the in side: the calls the pod receives */
+#define SG_RSEL_OUT    8u       /* the out side: the calls it makes */
+int sg_window_replicas_top(sg_handle h, uint32_t by, uint32_t k, uint32_t min_value, sg_node_out* out, uint32_t* index, size_t cap, size_t* n_selected, size_t* n_rows);
+
 /* The window close in two halves, for hosts whose feeders keep running (the aggregator's worker goroutines do): sg_flush_begin
  * marks the window boundary — it waits for the staging copies that began before it (at most one batch copy per feeder; sg_ingest
  * calls that arrive meanwhile wait that long too, then belong to the NEXT window), enqueues K1 pass B .. K5 and returns.
